@@ -18,15 +18,20 @@ RCCL all-gather of the per-item result rows (parallel.all_gather_rows for C4/C5:
 
 metric  = tet-tri clip+integrate ops/s, one op = one broadphase candidate (triangle, tet) pair pushed through
           the narrowphase; contact-pairs/s (items/s) is reported beside it.
-timing  = ``--reps`` repetitions of the K-step block, each bracketed by barrier + synchronize; ``value`` and
-          ``ms_per_step`` are the MEDIAN repetition (max over ranks per repetition); the spread is reported.
+timing  = the K = ``--steps`` timed steps, bracketed by barrier + synchronize; ``ms_per_step`` is their time / K (max over
+          ranks).  ``--reps R`` (default 1) times the K-step block R times and reports the MEDIAN repetition and the spread.
+outputs: ``--dump-outputs DIR`` writes what the last timed step returned, every rank's rows in item order (C3: rank r's poses
+          are items r * poses ...), one float64 ``DIR/<name>.npy`` each: ``wrench`` (n, 6), ``sdot`` (n, 6), ``counts`` (n, 4)
+          and ``item_ids`` (n,), the item index of each row.
+          The inputs are seeded, so two builds run with the same arguments can be compared row for row.  Above 64 MB in all
+          a fixed, seeded sample of the rows is written.
 roofline: the dominant kernel with the SURVEY §8(d) accounting (algorithmic bytes / kernel time vs the 8 TB/s HBM
           peak; kernel time from HIP events on the launch stream inside libpfc_hip) plus the measured PMC traffic and
           the vector-issue view (``valu``), which is what actually bounds these kernels.  The other hot kernel is
           reported under ``roofline_other`` against the bound that applies to it (vector issue), never against HBM with
           cache-served algorithmic bytes.
-validation: after the timed region ``validated_items`` random items of the batch are re-evaluated by the CPU oracle
-          and compared (counts bit-equal, wrench 1e-9, sdot 1e-6).
+validation: after the timed region ``validated_items`` random items of the last timed step (rank 0's) are re-evaluated by
+          the CPU oracle and compared (counts bit-equal, wrench 1e-9, sdot 1e-6).
 cpu_baseline: the plain-C oracle (a scalar port of the reference algorithm; the Julia reference cannot run here)
           timed single-threaded on a bounded sample of the same items, rank 0, N = 1 only.
 """
@@ -281,14 +286,38 @@ def dual_block(pfc, dev, n_dir: int = 6):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, item_ids, outputs, seed: int = 0):
+    """--dump-outputs: one float64 DIR/<name>.npy per output array (rows = items) plus item_ids.  If the rows would take more
+    than DUMP_LIMIT_BYTES, a fixed, seeded sample of them is written, in item order."""
+    import numpy as np
+    arrays = {"item_ids": np.asarray(item_ids, dtype=np.float64)}
+    arrays.update((k, np.asarray(v, dtype=np.float64)) for k, v in outputs.items())
+    n = len(arrays["item_ids"])
+    row_bytes = sum(8 * int(np.prod(a.shape[1:], dtype=np.int64)) for a in arrays.values())
+    max_rows = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // row_bytes       # (room for the .npy headers)
+    if n > max_rows:
+        keep = np.sort(np.random.default_rng(seed).choice(n, size=max_rows, replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+    return {"dir": path, "files": sorted(k + ".npy" for k in arrays), "items_written": int(len(arrays["item_ids"])),
+            "items_computed": n, "sampled": n > max_rows}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", choices=["C3", "C4", "C5"], default="C3")
     ap.add_argument("--poses", type=int, default=8192, help="C3: Monte-Carlo poses (items) per GPU per step")
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the K-step block (median reported)")
+    ap.add_argument("--reps", type=int, default=1, help="times the K-step block is timed (median reported)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy, float64, at most 64 MB")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 = skip)")
     ap.add_argument("--validate", type=int, default=8, help="items re-evaluated by the CPU oracle after the timed region")
     ap.add_argument("--no-validate", action="store_true")
@@ -304,6 +333,8 @@ def main():
                     help="ONE process drives the --gpus devices through a multi-device handle (pfc_create_multi: the form the "
                          "single-process Julia host uses) instead of one rank per GPU; PFC_BENCH_DEVICES=0,0 rehearses it on one GPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.reps < 1 or args.warmup < 0:
+        ap.error("--steps and --reps must be at least 1, --warmup at least 0")
 
     import numpy as np
     import torch
@@ -479,9 +510,9 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # ---- timed region: --reps repetitions of the K-step block ------------------------------------------------------
+    # ---- timed region: the K-step block, --reps times -----------------------------------------------------------------
     rep_dt = []
-    for _ in range(max(args.reps, 1)):
+    for _ in range(args.reps):
         fence()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -495,22 +526,35 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         rep_dt.append(float(t.item()))
     dt = statistics.median(rep_dt)
+    # what the last timed step returned, read back before the untimed steps below overwrite it: validate() checks these rows
+    # and --dump-outputs writes them
+    last = {"wrench": d_wrench[:n].cpu().numpy(), "sdot": d_sdot[:n].cpu().numpy(), "counts": d_counts[:n].cpu().numpy()}
+    # C3 ranks evaluate poses of their own (weak scaling): rank r's rows follow rank r - 1's, as the exchange orders them
+    dump_ids, dump_rows = np.asarray(mine) + (rank * w.n_items if args.config == "C3" else 0), last
+    if args.dump_outputs and world > 1:
+        got = [None] * world          # every rank's rows, as the exchange hands them to a caller
+        dist.all_gather_object(got, (dump_ids, last))
+        order = np.argsort(np.concatenate([g[0] for g in got]), kind="stable")
+        dump_ids = np.concatenate([g[0] for g in got])[order]
+        dump_rows = {k: np.concatenate([g[1][k] for g in got])[order] for k in last}
     st = m.stats() if n else {"candidates": 0, "node_tests": 0, "tractions": 0}
     path = m.last_parts() if n else 1      # 0: fused small-scene kernel, 1: batched, 2: batched as two concurrent halves
     # ---- per-stage kernel times (HIP events inside the library, batched path) and the exchange's share: extra steps --
+    n_diag = min(args.steps, 10)           # untimed steps per diagnostic pass
     stage = {}
     if n:
         m.set_option("profile", 1)
-        for _ in range(args.steps):
+        for _ in range(n_diag):
             step()
             for k, v in m.stage_ms().items():
                 stage[k] = stage.get(k, 0.0) + v
         st_prof = m.stats()
         parts_prof = max(m.last_parts(), 1)
         m.set_option("profile", 0)
-    for _ in range(args.steps):
-        step(timed=True)
-    xchg_per_step = xchg_ms[0] / max(args.steps, 1)
+    if world > 1 or force_x:
+        for _ in range(n_diag):
+            step(timed=True)
+    xchg_per_step = xchg_ms[0] / n_diag
 
     tot = torch.tensor([float(st["candidates"]), float(n), float(st["node_tests"]), float(st["tractions"])],
                        dtype=torch.float64, device=dev)
@@ -522,8 +566,8 @@ def main():
 
     if rank == 0:
         K = args.steps
-        np_ms = stage["narrowphase"] / K
-        bp_ms = stage["broadphase"] / K
+        np_ms = stage["narrowphase"] / n_diag
+        bp_ms = stage["broadphase"] / n_diag
         parts_n = parts_prof * (max(m.last_shards(), 1) if multi_devs else 1)      # launches the step's units are spread over
         # SURVEY §8(d) accounting: algorithmic bytes / kernel time against the HBM peak (well below 1: these kernels re-read
         # their 64..256-byte records from L2 / Infinity Cache and are bound by vector issue, see "valu").
@@ -620,7 +664,7 @@ def main():
                        "seconds_timed": sum(rep_dt)},
             "contact_pairs_per_s": items_step * K / dt,
             "node_tests_per_s": nodes_step * K / dt,
-            "stage_ms_per_step": {k: v / K for k, v in stage.items()},
+            "stage_ms_per_step": {k: v / n_diag for k, v in stage.items()},
             "exchange_ms_per_step": xchg_per_step,
             "exchange_share": (xchg_per_step / (dt / K * 1e3)) if (world > 1 or force_x) else 0.0,
             "path": {0: "fused small-scene kernel", 1: "batched", 2: "batched, two concurrent halves"}[path],
@@ -632,9 +676,10 @@ def main():
             "roofline": roof_np if (args.config != "C3" or np_ms >= bp_ms) else roof_bp,
             "roofline_other": roof_bp if (args.config != "C3" or np_ms >= bp_ms) else roof_np,
         }
+        if args.dump_outputs:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, dump_ids, dump_rows)
         if not args.no_validate and n:
-            out.update(validate(pfc, w, mine, d_wrench[:n].cpu().numpy(), d_sdot[:n].cpu().numpy(),
-                                d_counts[:n].cpu().numpy(), args.validate))
+            out.update(validate(pfc, w, mine, last["wrench"], last["sdot"], last["counts"], args.validate))
         if world == 1 and not args.no_extras:
             # single-pose rate of the C3 scene and the small reference-sized scenes (latency, not throughput)
             out["small_scenes"] = small_scene_latencies(pfc)
