@@ -336,6 +336,12 @@ int pfc_debug_stamps(pfc_handle h, long long *out16);
  * GPU, so tests can check that device division / sqrt / fma are correctly rounded (bitwise = host). */
 int pfc_selftest_math(pfc_handle h, int n, const double *x, const double *y, double *out3n);
 
+/* Device self-test of the Dual path's eigen step: for n symmetric 6x6 K̄ (Kbar36) and directions dK̄ (dKbar36), column-major,
+ * out72 per matrix = K̄^{-1/2} (36) then its Frechet derivative along dK̄ (36), by the code k_dual_eig runs (one wave per
+ * matrix).  Vlam42 NULL: the device Jacobi diagonalises K̄; else per matrix the eigenvectors V (36, column-major) and the
+ * eigenvalues (6) are taken from it, as with a stored decomposition (option fixed_order, PFC_DUAL_VALUE_K). */
+int pfc_selftest_kis(pfc_handle h, int n, const double *Kbar36, const double *dKbar36, const double *Vlam42, double *out72);
+
 #ifdef __cplusplus
 }
 #endif

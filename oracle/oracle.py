@@ -107,6 +107,8 @@ def lib():
         L.pfo_bb_bb_intersect.restype = C.c_int
         L.pfo_bb_bb_intersect.argtypes = [_dp] * 8
         L.pfo_decompose_K.argtypes = [_dp, C.c_double, _dp, _dp]
+        L.pfo_kis_dual.restype = C.c_int
+        L.pfo_kis_dual.argtypes = [C.c_int, _dp, _dp, _dp]
         L.pfo_tri_quad_rule.restype = C.c_int
         L.pfo_tri_quad_rule.argtypes = [C.c_int, _dp, _dp]
         _lib = L
@@ -246,3 +248,19 @@ def evaluate_dual(m1: OracleMesh, m2: OracleMesh, ins: _Ins, pose, twist, s, d_p
                          wrench.ctypes.data_as(_dp), sdot.ctypes.data_as(_dp), dw.ctypes.data_as(_dp),
                          dsd.ctypes.data_as(_dp))
     return st, wrench, sdot, dw, dsd
+
+
+def kis_dual(Kbar, dKbar):
+    """pfo_kis_dual: K̄^{-1/2} and its Frechet derivative along dK̄ by the Dual decompose_K!'s own eigen step.
+    Kbar, dKbar: (n, 6, 6) symmetric.  Returns (Kis, dKis), each (n, 6, 6)."""
+    L = lib()
+    Kbar = np.asarray(Kbar, dtype=np.float64).reshape(-1, 6, 6)
+    n = Kbar.shape[0]
+    k_a, k_p = _d(Kbar.transpose(0, 2, 1))          # column-major per matrix
+    d_a, d_p = _d(np.asarray(dKbar, dtype=np.float64).reshape(n, 6, 6).transpose(0, 2, 1))
+    out = np.zeros((n, 2, 6, 6))
+    st = L.pfo_kis_dual(n, k_p, d_p, out.ctypes.data_as(_dp))
+    if st:
+        raise RuntimeError(f"pfo_kis_dual: status {st}")
+    out = out.transpose(0, 1, 3, 2)                 # back to row-major (i, j)
+    return out[:, 0].copy(), out[:, 1].copy()

@@ -117,6 +117,9 @@ int pfo_bb_bb_intersect(const double ca[3], const double ea[3], const double Ra[
                         const double cb[3], const double eb[3], const double Rb[9],
                         const double R_a_b[9], const double t_a_b[3]);
 void pfo_decompose_K(const double K[36], double magic, double Kbar_inv_sqrt[36], double Sinv[6]);
+/* pfc_oracle_dual.cpp: K̄^{-1/2} and its Frechet derivative along dK̄ for n symmetric 6 x 6 matrices (column-major), by the
+ * code the Dual decompose_K! runs; out72 per matrix: K̄^{-1/2} (36), then the derivative (36). */
+int pfo_kis_dual(int n, const double *Kbar36, const double *dKbar36, double *out72);
 int pfo_tri_quad_rule(int n_rule, double *zeta, double *w);                            /* returns n points */
 
 #ifdef __cplusplus

@@ -12,10 +12,11 @@
  * symmetric eigen-solver (eigen!(Hermitian{Dual}), src/contact_algorithms_friction.jl:88; GenericLinearAlgebra >= 0.1.0
  * is a Project.toml dependency that is not vendored under /root/reference).  Here the partials of K̄^{-1/2} are the
  * analytic Frechet derivative of the same matrix function (Daleckii-Krein divided differences on the eigen-basis,
- * clamp max(sigma, 1e-16 sigma_max) differentiated as ForwardDiff's max does).  They agree with the reference wherever
- * the eigenvalues that are not clamped are distinct; for clustered eigenvalues the reference's partials are
- * themselves rounding noise.  Everything else follows the reference operation by operation; the partials are pinned in
- * tests/test_oracle_dual.py by central differences of the value oracle.
+ * clamp max(sigma, 1e-16 sigma_max) differentiated as ForwardDiff's max does; kis_frechet).  That step is pinned on its
+ * own to a 60-digit reference in tests/test_kis_frechet.py: accurate up to the conditioning of K̄, clustered eigenvalues
+ * included; only an eigenvalue within rounding of the clamp remains ill-conditioned.  Everything else follows the
+ * reference operation by operation; the partials are pinned in tests/test_oracle_dual.py by central differences of the
+ * value oracle.
  */
 #include "pfc_oracle.h"
 
@@ -430,19 +431,14 @@ void jacobi6(double A[36], double V[36], double w[6]) {
     for (int i = 0; i < 6; ++i) w[i] = A[7 * i];
 }
 
-/* decompose_K! + calc_K̄_sqrt_inv (:85-117) on Duals; see the header for how the eigen step is differentiated. */
-void decompose_K(const D K[36], double magic, D Kis[36], D Sinv[6]) {
-    D t1 = (K[0] + K[7]) + K[14], t2 = (K[21] + K[28]) + K[35];
-    D s1 = D(1.0) / dsqrt(t1), s2 = D(1.0) / dsqrt(t2);
-    for (int k = 0; k < 3; ++k) { Sinv[k] = s1 * D(magic); Sinv[k + 3] = s2; }
-    D Kb[36];
-    for (int j = 0; j < 6; ++j)
-        for (int i = 0; i < 6; ++i) {
-            D kij = (i <= j) ? K[i + 6 * j] : K[j + 6 * i];
-            Kb[i + 6 * j] = (Sinv[i] * kij) * Sinv[j];
-        }
-    double A[36], V[36], lam[6], dK[36];
-    for (int k = 0; k < 36; ++k) { A[k] = Kb[k].v; dK[k] = Kb[k].d; }
+/* K̄^{-1/2} and its Frechet derivative along dK (both symmetric, column-major): the eigen step of decompose_K! (:85-117)
+ * on Duals; see the header for how it is differentiated.  A is overwritten (Jacobi).  With x = max(sigma, floor) and
+ * f(x) = x^{-1/2}, the divided difference of two unclamped eigenvalues is f[x_i, x_j] = -1 / (s_i s_j (s_i + s_j)),
+ * s = sqrt(x): no subtraction, so it stays accurate where eigenvalues cluster (a flat patch's K22 has a double
+ * eigenvalue that rounding splits by a few ulps) and equals f'(x) at ties.  With one eigenvalue clamped the divided
+ * difference of x -> f(max(x, floor)) is f[x_i, x_j] (x_i - x_j) / (lam_i - lam_j); with two it is 0. */
+void kis_frechet(double A[36], const double dK[36], double KisV[36], double KisD[36]) {
+    double V[36], lam[6];
     jacobi6(A, V, lam);
     double mx = lam[0];
     int imx = 0;
@@ -462,13 +458,14 @@ void decompose_K(const D K[36], double magic, D Kis[36], D Sinv[6]) {
             M[i + 6 * j] = a;
         }
     const double floor_v = mx * 1.0e-16, dfloor = M[imx + 6 * imx] * 1.0e-16;   /* d(sigma_max) = v_max' dK v_max */
-    double f[6], fp[6], fx[6];  /* f(sigma), df/dsigma (own eigenvalue), df via the floor */
+    double f[6], fp[6], fx[6], x[6], sq[6];  /* f(x), df/dsigma (own eigenvalue), df via the floor; x = max(sigma, floor), sqrt(x) */
     bool clamped[6];
     for (int k = 0; k < 6; ++k) {
         clamped[k] = !(lam[k] > floor_v);   /* max(sigma, floor): ties take the floor */
-        const double x = clamped[k] ? floor_v : lam[k];
-        f[k] = 1.0 / std::sqrt(x);
-        const double dfdx = -0.5 * f[k] / x;
+        x[k] = clamped[k] ? floor_v : lam[k];
+        sq[k] = std::sqrt(x[k]);
+        f[k] = 1.0 / sq[k];
+        const double dfdx = -0.5 * f[k] / x[k];
         fp[k] = clamped[k] ? 0.0 : dfdx;
         fx[k] = clamped[k] ? dfdx * dfloor : 0.0;
     }
@@ -478,8 +475,10 @@ void decompose_K(const D K[36], double magic, D Kis[36], D Sinv[6]) {
             double g;
             if (i == j) g = fp[i];
             else if (clamped[i] && clamped[j]) g = 0.0;
-            else if (lam[i] != lam[j]) g = (f[i] - f[j]) / (lam[i] - lam[j]);
-            else g = fp[i];
+            else {
+                g = -1.0 / ((sq[i] * sq[j]) * (sq[i] + sq[j]));               /* f[x_i, x_j] */
+                if (clamped[i] || clamped[j]) g *= (x[i] - x[j]) / (lam[i] - lam[j]);
+            }
             G[i + 6 * j] = g * M[i + 6 * j];
         }
     for (int k = 0; k < 6; ++k) G[7 * k] += fx[k];
@@ -488,7 +487,7 @@ void decompose_K(const D K[36], double magic, D Kis[36], D Sinv[6]) {
         for (int j = 0; j < 6; ++j) {
             double a = 0.0;
             for (int k = 0; k < 6; ++k) a += (V[i + 6 * k] * f[k]) * V[j + 6 * k];
-            Kis[i + 6 * j].v = a;
+            KisV[i + 6 * j] = a;
         }
     for (int i = 0; i < 6; ++i)
         for (int j = 0; j < 6; ++j) {
@@ -500,8 +499,25 @@ void decompose_K(const D K[36], double magic, D Kis[36], D Sinv[6]) {
         for (int j = 0; j < 6; ++j) {
             double a = 0.0;
             for (int k = 0; k < 6; ++k) a += V[i + 6 * k] * T[k + 6 * j];
-            Kis[i + 6 * j].d = a;
+            KisD[i + 6 * j] = a;
         }
+}
+
+/* decompose_K! + calc_K̄_sqrt_inv (:85-117) on Duals */
+void decompose_K(const D K[36], double magic, D Kis[36], D Sinv[6]) {
+    D t1 = (K[0] + K[7]) + K[14], t2 = (K[21] + K[28]) + K[35];
+    D s1 = D(1.0) / dsqrt(t1), s2 = D(1.0) / dsqrt(t2);
+    for (int k = 0; k < 3; ++k) { Sinv[k] = s1 * D(magic); Sinv[k + 3] = s2; }
+    D Kb[36];
+    for (int j = 0; j < 6; ++j)
+        for (int i = 0; i < 6; ++i) {
+            D kij = (i <= j) ? K[i + 6 * j] : K[j + 6 * i];
+            Kb[i + 6 * j] = (Sinv[i] * kij) * Sinv[j];
+        }
+    double A[36], dK[36], KisV[36], KisD[36];
+    for (int k = 0; k < 36; ++k) { A[k] = Kb[k].v; dK[k] = Kb[k].d; }
+    kis_frechet(A, dK, KisV, KisD);
+    for (int k = 0; k < 36; ++k) Kis[k] = D(KisV[k], KisD[k]);
 }
 
 void mat6v(const D M[36], const D v[6], D o[6]) {
@@ -583,6 +599,24 @@ void yes_contact_bristle(Ctx &c, const D s[6], D wrench[6], D sdot[6]) {
 }
 
 }  // namespace
+
+/* The eigen step of the Dual decompose_K! alone (kis_frechet, the code pfo_eval_dual runs), for n matrices: Kbar36 and
+ * dKbar36 column-major 6 x 6 each (upper triangles authoritative, as decompose_K! reads K); out72: K̄^{-1/2} (36) then its
+ * derivative along dK̄ (36) per matrix. */
+extern "C" int pfo_kis_dual(int n, const double *Kbar36, const double *dKbar36, double *out72) {
+    if (n < 0 || (n > 0 && (!Kbar36 || !dKbar36 || !out72))) return PFO_ERR_BAD_ARG;
+    for (int m = 0; m < n; ++m) {
+        const double *K = Kbar36 + 36 * (size_t)m, *dK = dKbar36 + 36 * (size_t)m;
+        double A[36], dA[36];
+        for (int j = 0; j < 6; ++j)
+            for (int i = 0; i < 6; ++i) {
+                const int e = (i <= j) ? i + 6 * j : j + 6 * i;
+                A[i + 6 * j] = K[e]; dA[i + 6 * j] = dK[e];
+            }
+        kis_frechet(A, dA, out72 + 72 * (size_t)m, out72 + 72 * (size_t)m + 36);
+    }
+    return 0;
+}
 
 /*
  * force_single_elastic_intersection! on Duals with n_dir partials.  pose/twist/s as in pfo_eval; d_pose (n_dir x 24),

@@ -60,6 +60,7 @@ SIGNATURES = {
                                                   C.c_int, C.c_void_p]),
     "pfc_debug_stamps": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     "pfc_selftest_math": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp]),
+    "pfc_selftest_kis": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]),
 }
 
 

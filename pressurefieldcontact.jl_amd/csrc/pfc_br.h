@@ -539,3 +539,21 @@ __global__ void k_selftest(int n, const double *x, const double *y, double *out)
     out[2 * n + i] = __builtin_fma(x[i], y[i], x[i]);
 }
 
+// pfc_selftest_kis: one wave per matrix runs k_dual_eig's eigen step (kis_frechet_wave) on a given K̄ and dK̄ (upper
+// triangles authoritative, as k_dual_eig forms A); vl non-null: the stored_v path, V (36) and the eigenvalues (6) per matrix.
+__global__ void __launch_bounds__(64) k_selftest_kis(int n, const double *Kb, const double *dKb, const double *vl, double *out) {
+    __shared__ KisLds E;
+    const int m = blockIdx.x, lane = threadIdx.x;
+    if (m >= n) return;
+    const bool ent = lane < 36;
+    const int i = ent ? lane % 6 : 0, j = ent ? lane / 6 : 0;
+    if (ent) {
+        const int e = (i <= j) ? i + 6 * j : j + 6 * i;
+        E.A[lane] = Kb[36 * (size_t)m + e]; E.dK[lane] = dKb[36 * (size_t)m + e];
+        if (vl) { E.V[lane] = vl[42 * (size_t)m + lane]; if (i == j) E.A[lane] = vl[42 * (size_t)m + 36 + i]; }
+    }
+    wave_lds_sync();
+    kis_frechet_wave(E, vl == nullptr, lane);
+    if (ent) { out[72 * (size_t)m + lane] = E.KisV[lane]; out[72 * (size_t)m + 36 + lane] = E.KisD[lane]; }
+}
+

@@ -15,8 +15,10 @@
 // Bristle model: three passes over the candidates, as in the reference (normal_wrench_cop; then
 // calc_patch_spatial_stiffness! about the cop; then calc_spatial_bristle_force), src/contact_algorithms_friction.jl
 // :119-201.  The partials of K̄^{-1/2} are the Frechet derivative of the matrix function on the eigen-basis
-// (Daleckii-Krein); the reference differentiates through GenericLinearAlgebra's eigen-solver instead (not vendored),
-// which agrees wherever the unclamped eigenvalues are distinct ("Dual path").
+// (Daleckii-Krein, the divided differences of x^{-1/2} in closed form: kis_frechet_wave); the reference differentiates
+// through GenericLinearAlgebra's eigen-solver instead (not vendored).  The derivative is accurate up to the conditioning
+// of K̄, clustered eigenvalues included (tests/test_kis_frechet.py); only the clamp band -- an eigenvalue within rounding
+// of 1e-16 sigma_max -- remains ill-conditioned ("Dual oracle").
 #pragma once
 
 struct Du { double v, d; };
@@ -886,14 +888,96 @@ __global__ void __launch_bounds__(64) k_fixed_reduce(FixedSink fx, int n_keys, d
 // forward declarations (pfc_br.h, included after this header)
 __device__ __forceinline__ void jacobi6_wave(double *A, double *V, int lane);
 
+// K̄^{-1/2} and its Frechet derivative along dK̄ (decompose_K!'s eigen step on Duals, friction.jl:88-96), carried by ONE
+// wave: lane e = i + 6 j (e < 36) owns entry (i, j).  In: A = K̄ (its diagonal the eigenvalues if V is given), dK; iterate:
+// Jacobi-diagonalise A into V first, else V (and A's diagonal) are the stored decomposition.  Out: KisV, KisD.
+// With x = max(sigma, 1e-16 sigma_max) and f(x) = x^{-1/2}, the divided difference of two unclamped eigenvalues is
+// f[x_i, x_j] = -1 / (s_i s_j (s_i + s_j)), s = sqrt(x): no subtraction, so it stays accurate where eigenvalues cluster (a
+// flat patch's K22 has a double eigenvalue that rounding splits by a few ulps) and equals f'(x) at ties.  With one eigenvalue
+// clamped the divided difference of sigma -> f(max(sigma, floor)) is f[x_i, x_j] (x_i - x_j) / (lam_i - lam_j); with two, 0.
+// The Dual oracle states the same thing, statement for statement.
+struct KisLds { double A[36], dK[36], V[36], T[36], M[36], KisV[36], KisD[36], f[6], fp[6], fx[6], lam[6], x[6], sq[6]; int clamped[6]; };
+__device__ __forceinline__ void kis_frechet_wave(KisLds &E, bool iterate, int lane) {
+    double *A = E.A, *dK = E.dK, *V = E.V, *T = E.T, *M = E.M, *KisV = E.KisV, *KisD = E.KisD;
+    double *f = E.f, *fp = E.fp, *fx = E.fx, *lam = E.lam, *xs = E.x, *sq = E.sq;
+    int *clamped = E.clamped;
+    const bool ent = lane < 36;
+    const int i = ent ? lane % 6 : 0, j = ent ? lane / 6 : 0;
+    if (iterate) jacobi6_wave(A, V, lane);
+    // M = V' dK V
+    if (ent) {
+        double x = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) x += dK[i + 6 * k] * V[k + 6 * j];
+        T[lane] = x;
+    }
+    wave_lds_sync();
+    if (ent) {
+        double x = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) x += V[k + 6 * i] * T[k + 6 * j];
+        M[lane] = x;
+    }
+    wave_lds_sync();
+    if (lane < 6) {
+        double mx = A[0];
+        int imx = 0;
+#pragma unroll
+        for (int k = 1; k < 6; ++k) if (A[7 * k] > mx) { mx = A[7 * k]; imx = k; }
+        const double floor_v = mx * 1.0e-16, dfloor = M[imx + 6 * imx] * 1.0e-16;   // d(sigma_max) = v_max' dK v_max
+        const double l = A[7 * lane];
+        const bool cl = !(l > floor_v);          // max(sigma, floor): ties take the floor
+        const double x = cl ? floor_v : l;
+        const double s = __builtin_sqrt(x);
+        const double fv = 1.0 / s, dfdx = -0.5 * fv / x;
+        lam[lane] = l; xs[lane] = x; sq[lane] = s; f[lane] = fv; clamped[lane] = cl ? 1 : 0;
+        fp[lane] = cl ? 0.0 : dfdx;              // df/dsigma of the own eigenvalue
+        fx[lane] = cl ? dfdx * dfloor : 0.0;     // df through the floor
+    }
+    wave_lds_sync();
+    double gm = 0.0;
+    if (ent) {
+        double gij;
+        if (i == j) gij = fp[i];
+        else if (clamped[i] && clamped[j]) gij = 0.0;
+        else {
+            gij = -1.0 / ((sq[i] * sq[j]) * (sq[i] + sq[j]));                       // f[x_i, x_j]
+            if (clamped[i] || clamped[j]) gij *= (xs[i] - xs[j]) / (lam[i] - lam[j]);
+        }
+        gm = gij * M[lane] + (i == j ? fx[i] : 0.0);
+        double x = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) x += (V[i + 6 * k] * f[k]) * V[j + 6 * k];
+        KisV[lane] = x;
+    }
+    wave_lds_sync();
+    if (ent) M[lane] = gm;          // G o M (+ floor terms on the diagonal)
+    wave_lds_sync();
+    if (ent) {
+        double x = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) x += M[i + 6 * k] * V[j + 6 * k];
+        T[lane] = x;
+    }
+    wave_lds_sync();
+    if (ent) {
+        double x = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) x += V[i + 6 * k] * T[k + 6 * j];
+        KisD[lane] = x;
+    }
+    wave_lds_sync();
+}
+
 // per (item, direction), one wave: cop, decompose_K! (friction.jl:96-117) with the Frechet derivative of K̄^{-1/2},
 // Delta (:130-131).  Lane e = i + 6 j (e < 36) owns entry (i, j) of every 6 x 6 matrix; the matrices live in LDS.
 // (The first version ran one thread per (item, direction) with its matrices in scratch: a 0.4 ms dependency chain,
 // half of the latency of a Dual evaluation of a single bristle scene.)
 __global__ void __launch_bounds__(64) k_dual_eig(DualArgs g) {
-    __shared__ double Kv[36], Kd[36], A[36], dK[36], V[36], T[36], M[36], KisV[36], KisD[36];
-    __shared__ double SinvV[6], SinvD[6], f[6], fp[6], fx[6], lam[6];
-    __shared__ int clamped[6];
+    __shared__ double Kv[36], Kd[36];
+    __shared__ KisLds E;
+    __shared__ double SinvV[6], SinvD[6];
+    double *A = E.A, *dK = E.dK, *V = E.V, *KisV = E.KisV, *KisD = E.KisD;
     __shared__ double copV[3], copD[3];
     const int key = blockIdx.x, lane = threadIdx.x;
     if (key >= g.n_items * g.n_dir) return;
@@ -970,75 +1054,15 @@ __global__ void __launch_bounds__(64) k_dual_eig(DualArgs g) {
         A[lane] = kb.v; dK[lane] = kb.d;
     }
     wave_lds_sync();
-    if (vk && g.stored_v) {
+    const bool stored = vk && g.stored_v;      // uniform
+    if (stored) {
         // the decomposition the value pass made of this very matrix (k_eig: same K, same scaling, same iteration): the six
         // directions of an item -- and every chunk of a Jacobian -- need not repeat its ~8 us dependency chain
         if (ent) { V[lane] = vk[kResV + lane]; if (i == j) A[lane] = vk[kResLam + i]; }
         wave_lds_sync();
-    } else {
-        jacobi6_wave(A, V, lane);
     }
-    // M = V' dK V
-    if (ent) {
-        double x = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) x += dK[i + 6 * k] * V[k + 6 * j];
-        T[lane] = x;
-    }
-    wave_lds_sync();
-    if (ent) {
-        double x = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) x += V[k + 6 * i] * T[k + 6 * j];
-        M[lane] = x;
-    }
-    wave_lds_sync();
-    if (lane < 6) {
-        double mx = A[0];
-        int imx = 0;
-#pragma unroll
-        for (int k = 1; k < 6; ++k) if (A[7 * k] > mx) { mx = A[7 * k]; imx = k; }
-        const double floor_v = mx * 1.0e-16, dfloor = M[imx + 6 * imx] * 1.0e-16;   // d(sigma_max) = v_max' dK v_max
-        const double l = A[7 * lane];
-        const bool cl = !(l > floor_v);          // max(sigma, floor): ties take the floor
-        const double x = cl ? floor_v : l;
-        const double fv = 1.0 / __builtin_sqrt(x), dfdx = -0.5 * fv / x;
-        lam[lane] = l; f[lane] = fv; clamped[lane] = cl ? 1 : 0;
-        fp[lane] = cl ? 0.0 : dfdx;              // df/dsigma of the own eigenvalue
-        fx[lane] = cl ? dfdx * dfloor : 0.0;     // df through the floor
-    }
-    wave_lds_sync();
-    double gm = 0.0;
-    if (ent) {
-        double gij;
-        if (i == j) gij = fp[i];
-        else if (clamped[i] && clamped[j]) gij = 0.0;
-        else if (lam[i] != lam[j]) gij = (f[i] - f[j]) / (lam[i] - lam[j]);
-        else gij = fp[i];
-        gm = gij * M[lane] + (i == j ? fx[i] : 0.0);
-        double x = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) x += (V[i + 6 * k] * f[k]) * V[j + 6 * k];
-        KisV[lane] = x;
-    }
-    wave_lds_sync();
-    if (ent) M[lane] = gm;          // G o M (+ floor terms on the diagonal)
-    wave_lds_sync();
-    if (ent) {
-        double x = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) x += M[i + 6 * k] * V[j + 6 * k];
-        T[lane] = x;
-    }
-    wave_lds_sync();
-    if (ent) {
-        double x = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) x += V[i + 6 * k] * T[k + 6 * j];
-        KisD[lane] = x;
-        res[kDrKis + lane] = KisV[lane]; res[kDrKis + 36 + lane] = x;
-    }
-    wave_lds_sync();
+    kis_frechet_wave(E, !stored, lane);
+    if (ent) { res[kDrKis + lane] = KisV[lane]; res[kDrKis + 36 + lane] = KisD[lane]; }
     if (lane < 6) {
         const double *ds = g.d_s + (size_t)key * 6;
         Du acc = du(0.0);

@@ -3003,4 +3003,24 @@ int pfc_selftest_math(pfc_handle h, int n, const double *x, const double *y, dou
     return PFC_OK;
 }
 
+int pfc_selftest_kis(pfc_handle h, int n, const double *Kbar36, const double *dKbar36, const double *Vlam42, double *out72) {
+    if (!h || n <= 0 || !Kbar36 || !dKbar36 || !out72) return PFC_ERR_BAD_ARG;
+    if (h->multi) return pfc_selftest_kis(h->multi->shard[0], n, Kbar36, dKbar36, Vlam42, out72);
+    HIP_TRY(h, hipSetDevice(h->device));
+    double *dk = nullptr, *ddk = nullptr, *dvl = nullptr, *dout = nullptr;
+    HIP_TRY(h, hipMalloc((void **)&dk, sizeof(double) * 36 * (size_t)n));
+    HIP_TRY(h, hipMalloc((void **)&ddk, sizeof(double) * 36 * (size_t)n));
+    HIP_TRY(h, hipMalloc((void **)&dout, sizeof(double) * 72 * (size_t)n));
+    if (Vlam42) HIP_TRY(h, hipMalloc((void **)&dvl, sizeof(double) * 42 * (size_t)n));
+    HIP_TRY(h, copy_sync(h, dk, Kbar36, sizeof(double) * 36 * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(h, copy_sync(h, ddk, dKbar36, sizeof(double) * 36 * (size_t)n, hipMemcpyHostToDevice));
+    if (Vlam42) HIP_TRY(h, copy_sync(h, dvl, Vlam42, sizeof(double) * 42 * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_selftest_kis, dim3(n), dim3(64), 0, h->stream, n, dk, ddk, dvl, dout);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, copy_sync(h, out72, dout, sizeof(double) * 72 * (size_t)n, hipMemcpyDeviceToHost));
+    (void)hipFree(dk); (void)hipFree(ddk); (void)hipFree(dvl); (void)hipFree(dout);
+    return PFC_OK;
+}
+
 }  // extern "C"
