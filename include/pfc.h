@@ -245,6 +245,47 @@ int pfc_scatter_generalized_device(pfc_handle h, int n_items, const double *d_wr
                                    const int *d_body_2, const int *d_scene, int n_scene, int nv, const double *d_jac, double *d_f,
                                    int accumulate, void *stream);
 
+/*
+ * The contact surface of n_items items: per item what the reference's TractionCache holds after forceAllElasticIntersections!
+ * (src/structs.jl; filled by src/contact_algorithms_non_friction.jl:217-265), the clipped polygons it was integrated over, and
+ * normal_wrench / normal_wrench_cop (src/contact_algorithms_normal.jl:2-34) -- what test/test_normal.jl:31-41 and
+ * test/test_friction.jl:251-256 read.  Inputs as pfc_eval (the pressure depends on the twist through the damping term
+ * max(0, 1 + chi edot), non_friction.jl:251-265; not on s, not on the friction model).  Everything is in frame r2.
+ *   poly_off   n_items + 1        OUT CSR: the polygons of item i are [poly_off[i], poly_off[i + 1])
+ *   poly_idx   cap_poly x 3       OUT {element of mesh_1, element of mesh_2, vertex count 3..8}
+ *   poly_xyz   cap_poly x 8 x 3   OUT the vertices; unused slots 0
+ *   poly_trac  cap_poly + 1       OUT CSR: the traction points of polygon k are [poly_trac[k], poly_trac[k + 1])
+ *   trac       cap_trac x 8       OUT n(3) r(3) dA p per traction point (pfc_debug_tractions' layout)
+ *   summary    n_items x 11       OUT normal wrench about the r2 origin [ang 3; lin 3], cop 3, sum p dA, sum dA; an item without
+ *                                     traction points gets zeros (the reference's cop would be 0/0 there)
+ *   counts     n_items x 4        OUT as pfc_eval's (may be NULL)
+ *   totals     2                  OUT polygons, traction points
+ * Canonical order whatever the options ("fused", "team", "split_min", "fixed_order", "debug"): polygons of an item by ascending
+ * (element of mesh_1, element of mesh_2), only pairs whose clip left 3 or more vertices; the points of a polygon in the reference's
+ * fan and quadrature order, skipping fan triangles of zero area and points with p <= 0 (integrate_patch, fillTractionCache*).  The
+ * summary is summed in that order as well: two calls on the same inputs return the same bytes in every output.  Traction points
+ * are bit-identical to the ones pfc_eval integrates.
+ * Capacity: if totals exceed cap_poly or cap_trac the call returns PFC_ERR_OVERFLOW after writing totals, poly_off, summary and
+ * counts, and writes no byte of poly_idx, poly_xyz, poly_trac or trac: grow the buffers and call again.  Internal work-list
+ * overflows are handled inside the call, as pfc_eval handles them.  n_items = 0 writes poly_off[0] = poly_trac[0] = 0 and zero
+ * totals.  poly_idx / poly_xyz may be NULL when cap_poly = 0, trac when cap_trac = 0.
+ * The call counts as an evaluation: pfc_eval_dual_device_more after it returns PFC_ERR_STATE and pfc_eval_dual's automatic reuse
+ * does not reach across it.  It changes no option.  A multi-device handle runs the call on its first device, with the same
+ * result, bit for bit, as a single-device handle.  The candidate order is that of option fixed_order and has its limits:
+ * log2(items) + log2(elements of mesh_1) + log2(tets of mesh_2) <= 64 (PFC_ERR_BAD_ARG otherwise); an item with more than
+ * 4 096 candidates switches the handle's surface calls to a sort of the whole list.  Host buffers, synchronous.
+ */
+int pfc_contact_surface(pfc_handle h, int n_items, const int *ins_ids, const double *pose, const double *twist, long long cap_poly,
+                        long long cap_trac, long long *poly_off, int *poly_idx, double *poly_xyz, long long *poly_trac, double *trac,
+                        double *summary, int *counts, long long *totals);
+/* The same with every buffer in device memory, enqueued on `stream` (NULL = the handle's own) without a host synchronisation; then
+ * pfc_check(): PFC_ERR_OVERFLOW means re-issue -- after growing the buffers if *d_totals exceeds a capacity (the outputs named
+ * above are written then), else a work list has grown. */
+int pfc_contact_surface_device(pfc_handle h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
+                               long long cap_poly, long long cap_trac, long long *d_poly_off, int *d_poly_idx, double *d_poly_xyz,
+                               long long *d_poly_trac, double *d_trac, double *d_summary, int *d_counts, long long *d_totals,
+                               void *stream);
+
 /* Options: "debug" (1: keep per-pair clip counts and materialise traction points of every item so that the
  * pfc_debug_* calls work), "profile" (1: bracket each stage with HIP events), "max_levels" (0 = automatic),
  * "bfs_levels" (-1 = automatic: level-synchronous seed expansion only until there are >= 2048 seed pairs),

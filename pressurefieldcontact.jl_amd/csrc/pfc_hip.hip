@@ -14,6 +14,7 @@
 //   option "fixed_order" (bit-reproducible evaluations): k_integ_fixed / k_fric_fixed (pfc_np.h), k_shift_fixed (pfc_br.h),
 //                  k_fixed_reduce (pfc_dual.h), the FixedSink record lists of accumulate_items / dual_accumulate, and
 //                  pfc_sort.hip (a translation unit of its own: rocPRIM radix sort of the candidate list)
+//   pfc_surface.h  k_surf_count / k_surf_summary / k_surf_emit: the contact surface in canonical order (pfc_contact_surface)
 //   pfc_multi.h    host code: multi-device handles (pfc_create_multi)
 // This file: mesh record preparation (k_prep_tri, k_prep_tet), per-item setup (k_setup_items), work-list management,
 // hipGraph capture / replay, the two-half evaluation and every extern "C" entry point.
@@ -179,6 +180,7 @@ __global__ void k_repose(int n_items, const double *__restrict__ pose, ItemRec *
 #include "pfc_dual.h"
 #include "pfc_br.h"
 #include "pfc_fused.h"
+#include "pfc_surface.h"
 
 }  // namespace pfc
 
@@ -424,6 +426,23 @@ struct pfc_context {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join0 = nullptr;
     int twin_queue_fallback = 0;         // make_twin: 0 the two streams run side by side as created; 1 the twin's stream was re-created with another priority because they did not; 2 they still do not
     hipStream_t twin_stream = nullptr;   // created right behind `stream` (the runtime deals streams out to its hardware queues in order of creation), handed to the twin
+    // pfc_contact_surface (pfc_surface.h): buffers of its own, so that no captured evaluation graph sees them move
+    DevBuf<long long> surf_cnt, surf_off, surf_out;   // per list slot {polygon, points} and their exclusive scan; packed status block
+    DevBuf<double> surf_part;                         // per candidate partial sums
+    DevBuf<int> surf_seg, surf_canon_off, surf_canon_fill, surf_canon_item;
+    DevBuf<unsigned long long> surf_keys[2];
+    DevBuf<char> surf_tmp;                            // rocPRIM scan / sort
+    long long *h_surf = nullptr;                      // pinned mirror of surf_out
+    size_t h_surf_cap = 0;
+    bool pending_surface = false;
+    bool surf_whole_list = false;       // an item had more candidates than the segment sort takes: the whole list is sorted from then on
+    bool surf_cap_short = false;        // the last checked surface call failed only for the caller's capacities
+    int surf_n_ctr = 0;
+    long long surf_cap_poly = 0, surf_cap_trac = 0;   // capacities of the pending call
+    DevBuf<long long> surf_hl;          // host-pointer form: device staging of the outputs
+    DevBuf<int> surf_hi;
+    DevBuf<double> surf_hd, surf_in;
+    size_t surf_hcap_poly = 0, surf_hcap_trac = 0;    // ... sized for this many polygons / traction points
 };
 
 namespace {
@@ -646,33 +665,9 @@ int bp_block_for(const pfc_context *h, int n_items) {
     return 256;
 }
 
-// The launch sequence of one evaluation on stream st (eagerly, or while st is being captured into a graph).
-int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
-                const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, hipStream_t st, bool prof) {
-    h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false; h->pending_more = false; h->last_dual_reused = false;
-    ++h->value_serial;
-    const int levels = eff_levels(h);
-    int *ccount = h->ctr.p, *tcount = h->ctr.p + 1, *next_seed = h->ctr.p + 2;   // ctr[3]: total records, filled by k_final
-    int *ucount = h->ctr.p + 4, *fcount = h->ctr.p + 6;
-    int *pcount = h->ctr.p + ((levels + 9) & ~1);   // after the per-level frontier counts; 8-byte aligned pair
-    // counters and status are zero here: k_final of the previous evaluation (or ensure_work after an allocation) left them so
-#ifdef PFC_STAMPS
-    HIP_TRY(h, hipMemsetAsync(h->stamps.p, 0, sizeof(unsigned long long) * 16, st));
-#endif
-    if (prof) HIP_TRY(h, hipEventRecord(h->ev[EV_START], st));
-
-    EvalArgs ea;
-    ea.n_items = n_items; ea.ins_ids = d_ins_ids; ea.pose = d_pose; ea.twist = d_twist; ea.s = d_s;
-    ea.bp_pose = h->bp_dev;
-    ea.ins = h->d_ins; ea.meshes = h->d_meshes; ea.n_ins = (int)h->ins.size(); ea.items = h->items.p;
-    ea.frontier0 = h->frontier[0].p; ea.fcount = fcount; ea.acc = h->acc.p; ea.icnt = h->icnt.p;
-    ea.status = h->status.p;
-    hipLaunchKernelGGL(k_setup_items, dim3(grid_for(n_items, 64, 1 << 20)), dim3(64), 0, st, ea);
-    if (prof) HIP_TRY(h, hipEventRecord(h->ev[EV_SETUP], st));
-
-    // broadphase: a few level-synchronous expansions to get enough independent seed pairs, then the per-wave
-    // depth-first kernel for everything below
-    const int L = bfs_levels_for(h, n_items, levels);
+// The batched broadphase of an evaluation on stream st, behind k_setup_items: L level-synchronous seed expansions, then the
+// depth-first kernel (record_eval; pfc_contact_surface).
+void launch_broadphase(pfc_context *h, int n_items, int L, int *ccount, int *fcount, int *next_seed, int *ucount, hipStream_t st) {
     for (int lv = 0; lv < L; ++lv) {
         BpArgs b;
         b.items = h->items.p; b.fin = h->frontier[lv & 1].p; b.fout = h->frontier[(lv + 1) & 1].p;
@@ -713,6 +708,36 @@ int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double 
                 hipLaunchKernelGGL((k_bp_dfs32<kDfsBlock>), dim3(grid_for(bound, 1, 256 * 6)), dim3(kDfsBlock), 0, st, f);
         }
     }
+}
+
+// The launch sequence of one evaluation on stream st (eagerly, or while st is being captured into a graph).
+int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
+                const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, hipStream_t st, bool prof) {
+    h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false; h->pending_more = false; h->last_dual_reused = false;
+    ++h->value_serial;
+    const int levels = eff_levels(h);
+    int *ccount = h->ctr.p, *tcount = h->ctr.p + 1, *next_seed = h->ctr.p + 2;   // ctr[3]: total records, filled by k_final
+    int *ucount = h->ctr.p + 4, *fcount = h->ctr.p + 6;
+    int *pcount = h->ctr.p + ((levels + 9) & ~1);   // after the per-level frontier counts; 8-byte aligned pair
+    // counters and status are zero here: k_final of the previous evaluation (or ensure_work after an allocation) left them so
+#ifdef PFC_STAMPS
+    HIP_TRY(h, hipMemsetAsync(h->stamps.p, 0, sizeof(unsigned long long) * 16, st));
+#endif
+    if (prof) HIP_TRY(h, hipEventRecord(h->ev[EV_START], st));
+
+    EvalArgs ea;
+    ea.n_items = n_items; ea.ins_ids = d_ins_ids; ea.pose = d_pose; ea.twist = d_twist; ea.s = d_s;
+    ea.bp_pose = h->bp_dev;
+    ea.ins = h->d_ins; ea.meshes = h->d_meshes; ea.n_ins = (int)h->ins.size(); ea.items = h->items.p;
+    ea.frontier0 = h->frontier[0].p; ea.fcount = fcount; ea.acc = h->acc.p; ea.icnt = h->icnt.p;
+    ea.status = h->status.p;
+    hipLaunchKernelGGL(k_setup_items, dim3(grid_for(n_items, 64, 1 << 20)), dim3(64), 0, st, ea);
+    if (prof) HIP_TRY(h, hipEventRecord(h->ev[EV_SETUP], st));
+
+    // broadphase: a few level-synchronous expansions to get enough independent seed pairs, then the per-wave
+    // depth-first kernel for everything below
+    const int L = bfs_levels_for(h, n_items, levels);
+    launch_broadphase(h, n_items, L, ccount, fcount, next_seed, ucount, st);
     if (h->bp_dev)      // the broadphase ran on a pose of its own: the item records get the evaluation's x_r1_r2 back
         hipLaunchKernelGGL(k_repose, dim3(grid_for(n_items, 64, 1 << 20)), dim3(64), 0, st, n_items, d_pose, h->items.p);
     if (h->opt_fixed_order) {
@@ -1328,7 +1353,7 @@ void pfc_destroy(pfc_handle h) {
     if (h->multi) { multi_destroy(h); delete h; return; }
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->pending && h->last_stream) (void)hipStreamSynchronize(h->last_stream);   // an unchecked pfc_eval_device on the caller's stream
+    if ((h->pending || h->pending_surface) && h->last_stream) (void)hipStreamSynchronize(h->last_stream);   // an unchecked pfc_eval_device on the caller's stream
     team_release(h);
     if (h->pin_bp) (void)hipHostFree(h->pin_bp);
     if (h->twin) { pfc_destroy(h->twin); h->twin = nullptr; }
@@ -1369,6 +1394,11 @@ void pfc_destroy(pfc_handle h) {
     h->rgn.release(); h->poly_item.release(); h->pcnt.release(); h->poly_cand.release(); h->poly.release(); h->surv.release(); h->scat_d.release(); h->scat_i.release();
     h->dual_poly.release(); h->dual_pkey.release(); h->dual_sel.release(); h->dual_flag.release();
     h->dual_in.release(); h->dual_acc.release(); h->dual_res.release(); h->dual_out.release(); h->dual_zero.release();
+    h->surf_cnt.release(); h->surf_off.release(); h->surf_out.release(); h->surf_part.release(); h->surf_seg.release();
+    h->surf_canon_off.release(); h->surf_canon_fill.release(); h->surf_canon_item.release();
+    h->surf_keys[0].release(); h->surf_keys[1].release(); h->surf_tmp.release();
+    h->surf_hl.release(); h->surf_hi.release(); h->surf_hd.release(); h->surf_in.release();
+    if (h->h_surf) (void)hipHostFree(h->h_surf);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -1748,10 +1778,259 @@ int pfc_eval_device(pfc_handle h, int n_items, const int *d_ins_ids, const doubl
     return PFC_OK;
 }
 
+namespace {
+
+// ---- pfc_contact_surface (pfc_surface.h) ----------------------------------------------------------------------------
+// The whole call on stream st: item setup, the batched broadphase, the candidate list in canonical order, count, scan, item
+// segments, summary and -- when both capacities suffice -- the emission; the status block goes to pinned memory for
+// check_surface.  Always this launch sequence, whatever "fused", "team", "split_min", "fixed_order" or "debug" say.
+int surface_enqueue(pfc_context *h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist, long long cap_poly,
+                    long long cap_trac, long long *d_poly_off, int *d_poly_idx, double *d_poly_xyz, long long *d_poly_trac,
+                    double *d_trac, double *d_summary, int *d_counts, long long *d_totals, hipStream_t st) {
+    // an evaluation for the call-order rules: the candidate list and the counters a Dual evaluation could reuse are overwritten
+    h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false; h->pending_more = false;
+    h->pin_in_dual_n = 0; h->pin_din_valid = false;
+    ++h->value_serial;
+    h->pending = false; h->pending_dual = false; h->pending_dual_hyb = false; h->split_n0 = 0;
+    if (h->pending_fused) { h->pending_fused = false; team_release(h); }
+    int ba, bb;
+    const int bits = pfc_sort_key_bits(n_items, h->max_elem1, h->max_elem2, &ba, &bb);
+    if (bits > 64)
+        return fail(h, PFC_ERR_BAD_ARG, "pfc_contact_surface: (item, element, element) needs %d key bits for %d items, more than 64", bits, n_items);
+    HIP_TRY(h, ensure_work(h, n_items));
+    const size_t c = h->ccap;
+    HIP_TRY(h, h->surf_cnt.ensure(2 * (c + 1)));
+    HIP_TRY(h, h->surf_off.ensure(2 * (c + 1)));
+    HIP_TRY(h, h->surf_part.ensure(c * kSurfSums));
+    HIP_TRY(h, h->surf_seg.ensure((size_t)n_items + 1));
+    HIP_TRY(h, h->surf_canon_off.ensure((size_t)n_items + 1));
+    HIP_TRY(h, h->surf_canon_fill.ensure((size_t)n_items));
+    HIP_TRY(h, h->surf_canon_item.ensure(c));
+    HIP_TRY(h, h->surf_keys[0].ensure(c));
+    HIP_TRY(h, h->surf_keys[1].ensure(c));
+    size_t scan_bytes = 0, sort_bytes = 0;
+    HIP_TRY(h, pfc_scan_pairs(nullptr, &scan_bytes, nullptr, nullptr, c + 1, st));
+    if (h->surf_whole_list) HIP_TRY(h, pfc_sort_temp_bytes(c, bits, &sort_bytes));
+    HIP_TRY(h, h->surf_tmp.ensure((scan_bytes > sort_bytes ? scan_bytes : sort_bytes) + 16));
+    const int levels = eff_levels(h);
+    const int n_ctr = levels + 12;
+    HIP_TRY(h, h->surf_out.ensure((size_t)n_ctr + 3));
+    if (h->h_surf_cap < (size_t)n_ctr + 3) {
+        if (h->h_surf) (void)hipHostFree(h->h_surf);
+        h->h_surf = nullptr; h->h_surf_cap = 0;
+        HIP_TRY(h, hipHostMalloc((void **)&h->h_surf, sizeof(long long) * ((size_t)n_ctr + 3)));
+        h->h_surf_cap = (size_t)n_ctr + 3;
+    }
+    int *ccount = h->ctr.p, *next_seed = h->ctr.p + 2, *ucount = h->ctr.p + 4, *fcount = h->ctr.p + 6;   // (record_eval's layout)
+
+    EvalArgs ea;
+    ea.n_items = n_items; ea.ins_ids = d_ins_ids; ea.pose = d_pose; ea.twist = d_twist; ea.s = nullptr; ea.bp_pose = nullptr;
+    ea.ins = h->d_ins; ea.meshes = h->d_meshes; ea.n_ins = (int)h->ins.size(); ea.items = h->items.p;
+    ea.frontier0 = h->frontier[0].p; ea.fcount = fcount; ea.acc = h->acc.p; ea.icnt = h->icnt.p;
+    ea.status = h->status.p;
+    hipLaunchKernelGGL(k_setup_items, dim3(grid_for(n_items, 64, 1 << 20)), dim3(64), 0, st, ea);
+    const int L = bfs_levels_for(h, n_items, levels);
+    launch_broadphase(h, n_items, L, ccount, fcount, next_seed, ucount, st);
+    // (item, element of mesh 1, element of mesh 2): the per-item segments sorted in LDS, or -- once an item had more candidates
+    // than a segment sort takes -- one sort of the whole list
+    if (h->surf_whole_list)
+        HIP_TRY(h, pfc_sort_candidates(h->cand.p, ccount, c, h->surf_keys[0].p, h->surf_keys[1].p, h->surf_tmp.p, h->surf_tmp.cap, n_items,
+                                       ba, bb, bits, h->status.p, kStFixedCover, st));
+    else
+        HIP_TRY(h, pfc_canon_candidates(h->cand.p, ccount, c, h->icnt.p, n_items, h->surf_keys[0].p, h->surf_keys[1].p, h->surf_canon_off.p,
+                                        h->surf_canon_fill.p, h->surf_canon_item.p, bb, h->status.p, kStFixedCover, kStFixedBig, st));
+    SurfArgs g;
+    g.items = h->items.p; g.cand = h->cand.p; g.ccount = ccount; g.ccap = (int)c; g.n_items = n_items; g.icnt = h->icnt.p;
+    g.status = h->status.p; g.cnt = h->surf_cnt.p; g.part = h->surf_part.p; g.off = h->surf_off.p; g.seg = h->surf_seg.p;
+    g.cap_poly = cap_poly; g.cap_trac = cap_trac; g.poly_off = d_poly_off; g.poly_idx = d_poly_idx; g.poly_xyz = d_poly_xyz;
+    g.poly_trac = d_poly_trac; g.trac = d_trac; g.summary = d_summary; g.counts = d_counts; g.totals = d_totals;
+    const int grid = grid_for(c + 1, kSurfBlock, kNpMaxBlocks);
+    if (h->any_tet_tet) hipLaunchKernelGGL((k_surf_count<true>), dim3(grid), dim3(kSurfBlock), 0, st, g);
+    else hipLaunchKernelGGL((k_surf_count<false>), dim3(grid), dim3(kSurfBlock), 0, st, g);
+    HIP_TRY(h, pfc_scan_pairs(h->surf_tmp.p, &scan_bytes, h->surf_cnt.p, h->surf_off.p, c + 1, st));
+    HIP_TRY(h, hipMemsetAsync(h->surf_seg.p, 0, sizeof(int) * ((size_t)n_items + 1), st));
+    hipLaunchKernelGGL(k_surf_seg, dim3(grid_for(c + 1, 256, 4096)), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(k_surf_summary, dim3(n_items < 8192 ? n_items : 8192), dim3(64), 0, st, g);
+    if (h->any_tet_tet) hipLaunchKernelGGL((k_surf_emit<true>), dim3(grid), dim3(kSurfBlock), 0, st, g);
+    else hipLaunchKernelGGL((k_surf_emit<false>), dim3(grid), dim3(kSurfBlock), 0, st, g);
+    hipLaunchKernelGGL(k_surf_final, dim3(1), dim3(64), 0, st, h->ctr.p, n_ctr, h->status.p, (const long long *)h->surf_off.p, (int)c,
+                       h->surf_out.p);
+    HIP_TRY(h, hipMemcpyAsync(h->h_surf, h->surf_out.p, sizeof(long long) * ((size_t)n_ctr + 3), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipGetLastError());
+    h->pending_surface = true; h->last_stream = st; h->surf_n_ctr = n_ctr;
+    h->surf_cap_poly = cap_poly; h->surf_cap_trac = cap_trac;
+    h->last_n_items = n_items; h->last_levels = levels; h->last_bfs_levels = L;
+    return PFC_OK;
+}
+
+// Synchronise the pending surface call and judge it: internal work lists grown (PFC_ERR_OVERFLOW, re-issue), or the caller's
+// capacities short (PFC_ERR_OVERFLOW with surf_cap_short: totals, offsets, summary and counters are written, nothing else).
+int check_surface(pfc_context *h) {
+    h->pending_surface = false;
+    h->surf_cap_short = false;
+    HIP_TRY(h, hipStreamSynchronize(h->last_stream));
+    const long long *o = h->h_surf;
+    const unsigned status = (unsigned)o[0];
+    const long long *ctr = o + 3;
+    long long fpeak = 0;
+    for (int lv = 0; lv <= h->last_bfs_levels && lv <= h->last_levels; ++lv)
+        if (ctr[6 + lv] > fpeak) fpeak = ctr[6 + lv];
+    if (status & kStBadIns) return fail(h, PFC_ERR_BAD_ARG, "instruction id out of range in ins_ids");
+    if (status & kStHole) return fail(h, PFC_ERR_STATE, "internal error: a work-list slot was read before it was written");
+    if (status & (kStFrontierOvf | kStCandOvf)) {      // as check_one
+        if (status & kStFrontierOvf) { size_t f = h->fcap * 2; while (f < (size_t)fpeak) f *= 2; h->fcap = f; }
+        if (status & kStCandOvf) { size_t c = h->ccap * 2; while (c < (size_t)ctr[0]) c *= 2; h->ccap = c; }
+        if (h->fcap > ((size_t)1 << 30) || h->ccap > ((size_t)1 << 30))
+            return fail(h, PFC_ERR_NOMEM, "work lists beyond 2^30 entries (frontier %zu, candidates %zu): evaluate the batch in parts", h->fcap, h->ccap);
+        return fail(h, PFC_ERR_OVERFLOW, "work list overflow (status %u): capacities grown to frontier %zu, candidates %zu", status, h->fcap, h->ccap);
+    }
+    if (status & kStAbort) return fail(h, PFC_ERR_STATE, "broadphase aborted: iteration guard hit (corrupt tree?)");
+    if (status & kStFixedBig) {
+        h->surf_whole_list = true;
+        return fail(h, PFC_ERR_OVERFLOW, "pfc_contact_surface: an item has more than 4096 candidates: the whole list is sorted from now on, re-issue");
+    }
+    if (status & kStFixedCover) return fail(h, PFC_ERR_OVERFLOW, "pfc_contact_surface: the candidate list outgrew its capacity: re-issue");
+    if (status & kStNonFinite) return fail(h, PFC_ERR_NONFINITE, "Non-finite vertex likely");
+    if (o[1] > h->surf_cap_poly || o[2] > h->surf_cap_trac) {
+        h->surf_cap_short = true;
+        return fail(h, PFC_ERR_OVERFLOW, "pfc_contact_surface: %lld polygons and %lld traction points, capacities %lld and %lld: grow the buffers and call again",
+                    o[1], o[2], h->surf_cap_poly, h->surf_cap_trac);
+    }
+    return PFC_OK;
+}
+
+// The context a surface call runs on: the handle's own, or the first device's of a multi-device handle (whose pending
+// device-pointer evaluation and Dual reuse end here, as with any other evaluation).
+pfc_context *surface_ctx(pfc_context *h) {
+    if (!h->multi) return h;
+    h->multi->dev_pending = false; h->multi->dev_reuse_ok = false;
+    return h->multi->shard[0];
+}
+
+int surface_args(pfc_context *h, int n_items, const void *ins_ids, const void *pose, const void *twist, long long cap_poly,
+                 long long cap_trac, const void *poly_off, const void *poly_idx, const void *poly_xyz, const void *poly_trac,
+                 const void *trac, const void *summary, const void *totals) {
+    if (!h->finalized) return fail(h, PFC_ERR_STATE, "pfc_contact_surface before pfc_finalize");
+    if (n_items < 0 || cap_poly < 0 || cap_trac < 0) return fail(h, PFC_ERR_BAD_ARG, "pfc_contact_surface: negative n_items or capacity");
+    if (!poly_off || !poly_trac || !totals || (n_items > 0 && (!pose || !twist || !summary)) || (cap_poly > 0 && (!poly_idx || !poly_xyz)) ||
+        (cap_trac > 0 && !trac))
+        return fail(h, PFC_ERR_BAD_ARG, "pfc_contact_surface: null buffer");
+    if (n_items > 0 && h->ins.empty()) return fail(h, PFC_ERR_STATE, "no contact instructions");
+    if (!ins_ids && n_items > (int)h->ins.size())
+        return fail(h, PFC_ERR_BAD_ARG, "n_items exceeds the number of instructions and no ins_ids given");
+    return PFC_OK;
+}
+
+}  // namespace
+
+int pfc_contact_surface(pfc_handle hh, int n_items, const int *ins_ids, const double *pose, const double *twist, long long cap_poly,
+                        long long cap_trac, long long *poly_off, int *poly_idx, double *poly_xyz, long long *poly_trac, double *trac,
+                        double *summary, int *counts, long long *totals) {
+    if (!hh) return PFC_ERR_BAD_ARG;
+    pfc_context *h = surface_ctx(hh);
+    int rc = surface_args(h, n_items, ins_ids, pose, twist, cap_poly, cap_trac, poly_off, poly_idx, poly_xyz, poly_trac, trac, summary, totals);
+    if (rc != PFC_OK) { if (hh != h) hh->err = h->err; return rc; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)n_items;
+    if (n_items == 0) {
+        h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false; h->pin_in_dual_n = 0; h->pin_din_valid = false;
+        ++h->value_serial;
+        poly_off[0] = 0; poly_trac[0] = 0; totals[0] = totals[1] = 0;
+        return PFC_OK;
+    }
+    // inputs: pose | twist | ins_ids
+    HIP_TRY(h, h->surf_in.ensure(n * 30 + (n + 1) / 2 + 1));
+    double *di = h->surf_in.p;
+    HIP_TRY(h, hipMemcpyAsync(di, pose, sizeof(double) * n * 24, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(di + n * 24, twist, sizeof(double) * n * 6, hipMemcpyHostToDevice, h->stream));
+    if (ins_ids) HIP_TRY(h, hipMemcpyAsync(di + n * 30, ins_ids, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
+    // outputs are staged in device buffers sized for what the last calls needed (at most the caller's capacities): a call that
+    // needs more within the caller's capacities grows them and runs again
+    long long tot_p = 0, tot_t = 0;
+    for (int attempt = 0; attempt < 40; ++attempt) {
+        const size_t dp = (size_t)(cap_poly < (long long)h->surf_hcap_poly ? cap_poly : (long long)h->surf_hcap_poly);
+        const size_t dt = (size_t)(cap_trac < (long long)h->surf_hcap_trac ? cap_trac : (long long)h->surf_hcap_trac);
+        HIP_TRY(h, h->surf_hl.ensure((n + 1) + 2 + (dp + 1)));
+        HIP_TRY(h, h->surf_hi.ensure(4 * n + 3 * dp + 1));
+        HIP_TRY(h, h->surf_hd.ensure(11 * n + 24 * dp + 8 * dt + 1));
+        long long *l_off = h->surf_hl.p, *l_tot = l_off + n + 1, *l_ptr = l_tot + 2;
+        int *i_cnt = h->surf_hi.p, *i_idx = i_cnt + 4 * n;
+        double *d_sum = h->surf_hd.p, *d_xyz = d_sum + 11 * n, *d_trac = d_xyz + 24 * dp;
+        rc = surface_enqueue(h, n_items, ins_ids ? (const int *)(di + n * 30) : nullptr, di, di + n * 24, (long long)dp, (long long)dt, l_off,
+                             i_idx, d_xyz, l_ptr, d_trac, d_sum, i_cnt, l_tot, h->stream);
+        if (rc == PFC_OK) rc = check_surface(h);
+        if (rc == PFC_ERR_OVERFLOW && h->surf_cap_short) {
+            tot_p = h->h_surf[1]; tot_t = h->h_surf[2];
+            if (tot_p <= cap_poly && tot_t <= cap_trac) {      // the staging was short, not the caller's buffers
+                if ((size_t)tot_p > h->surf_hcap_poly) h->surf_hcap_poly = (size_t)tot_p;
+                if ((size_t)tot_t > h->surf_hcap_trac) h->surf_hcap_trac = (size_t)tot_t;
+                continue;
+            }
+            rc = fail(h, PFC_ERR_OVERFLOW, "pfc_contact_surface: %lld polygons and %lld traction points, capacities %lld and %lld: grow the buffers and call again",
+                      tot_p, tot_t, cap_poly, cap_trac);
+            break;
+        }
+        if (rc != PFC_ERR_OVERFLOW) break;
+    }
+    if (rc != PFC_OK && !(rc == PFC_ERR_OVERFLOW && h->surf_cap_short)) { if (hh != h) hh->err = h->err; return rc; }
+    const long long *l_off = h->surf_hl.p, *l_tot = l_off + n + 1, *l_ptr = l_tot + 2;
+    const size_t dp = (size_t)(cap_poly < (long long)h->surf_hcap_poly ? cap_poly : (long long)h->surf_hcap_poly);
+    const int *i_cnt = h->surf_hi.p, *i_idx = i_cnt + 4 * n;
+    const double *d_sum = h->surf_hd.p, *d_xyz = d_sum + 11 * n, *d_trac = d_xyz + 24 * dp;
+    HIP_TRY(h, hipMemcpyAsync(poly_off, l_off, sizeof(long long) * (n + 1), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(totals, l_tot, sizeof(long long) * 2, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(summary, d_sum, sizeof(double) * 11 * n, hipMemcpyDeviceToHost, h->stream));
+    if (counts) HIP_TRY(h, hipMemcpyAsync(counts, i_cnt, sizeof(int) * 4 * n, hipMemcpyDeviceToHost, h->stream));
+    if (rc == PFC_OK) {
+        tot_p = h->h_surf[1]; tot_t = h->h_surf[2];
+        HIP_TRY(h, hipMemcpyAsync(poly_trac, l_ptr, sizeof(long long) * ((size_t)tot_p + 1), hipMemcpyDeviceToHost, h->stream));
+        if (tot_p > 0) {
+            HIP_TRY(h, hipMemcpyAsync(poly_idx, i_idx, sizeof(int) * 3 * (size_t)tot_p, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(poly_xyz, d_xyz, sizeof(double) * 24 * (size_t)tot_p, hipMemcpyDeviceToHost, h->stream));
+        }
+        if (tot_t > 0) HIP_TRY(h, hipMemcpyAsync(trac, d_trac, sizeof(double) * 8 * (size_t)tot_t, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (rc != PFC_OK && hh != h) hh->err = h->err;
+    return rc;
+}
+
+int pfc_contact_surface_device(pfc_handle hh, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
+                               long long cap_poly, long long cap_trac, long long *d_poly_off, int *d_poly_idx, double *d_poly_xyz,
+                               long long *d_poly_trac, double *d_trac, double *d_summary, int *d_counts, long long *d_totals, void *stream) {
+    if (!hh) return PFC_ERR_BAD_ARG;
+    pfc_context *h = surface_ctx(hh);
+    int rc = surface_args(h, n_items, d_ins_ids, d_pose, d_twist, cap_poly, cap_trac, d_poly_off, d_poly_idx, d_poly_xyz, d_poly_trac,
+                          d_trac, d_summary, d_totals);
+    if (rc != PFC_OK) { if (hh != h) hh->err = h->err; return rc; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    if (n_items == 0) {
+        h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false; h->pin_in_dual_n = 0; h->pin_din_valid = false;
+        ++h->value_serial;
+        HIP_TRY(h, hipMemsetAsync(d_poly_off, 0, sizeof(long long), st));
+        HIP_TRY(h, hipMemsetAsync(d_poly_trac, 0, sizeof(long long), st));
+        HIP_TRY(h, hipMemsetAsync(d_totals, 0, sizeof(long long) * 2, st));
+        return PFC_OK;
+    }
+    rc = surface_enqueue(h, n_items, d_ins_ids, d_pose, d_twist, cap_poly, cap_trac, d_poly_off, d_poly_idx, d_poly_xyz, d_poly_trac,
+                         d_trac, d_summary, d_counts, d_totals, st);
+    if (rc != PFC_OK && hh != h) hh->err = h->err;
+    return rc;
+}
+
 int pfc_check(pfc_handle h) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi) return multi_check(h);
+    if (h->multi) {
+        pfc_context *c0 = h->multi->shard[0];
+        if (!c0->pending_surface) return multi_check(h);
+        (void)hipSetDevice(c0->device);
+        const int rc = check_surface(c0);
+        if (rc != PFC_OK) h->err = c0->err;
+        return rc;
+    }
     HIP_TRY(h, hipSetDevice(h->device));
+    if (h->pending_surface) return check_surface(h);
     if (h->pending_more) {       // Dual passes on a value pass that was checked before: nothing to read back
         h->pending_more = false;
         HIP_TRY(h, hipStreamSynchronize(h->last_stream));

@@ -21,3 +21,6 @@ hipError_t pfc_sort_indices(int *list, const int *count, size_t cap, unsigned *k
 hipError_t pfc_canon_candidates(void *cand, const int *ccount, size_t cap, const int *icnt, int n_items, unsigned long long *keys_in,
                                 unsigned long long *keys_out, int *off, int *fill, int *item_of, int bits_b, unsigned *status,
                                 unsigned cover_bit, unsigned big_bit, hipStream_t st);
+// Exclusive scan of n pairs of 64-bit counts, in[2 k], in[2 k + 1] (pfc_contact_surface: polygon and traction-point offsets of the
+// candidates), on stream st.  temp NULL: only *temp_bytes is set.
+hipError_t pfc_scan_pairs(void *temp, size_t *temp_bytes, const long long *in, long long *out, size_t n, hipStream_t st);

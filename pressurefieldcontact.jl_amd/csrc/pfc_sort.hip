@@ -11,6 +11,7 @@
 // the same in every run; pfc_np.h / pfc_br.h then add the per-(chunk, item) records of an item in chunk order.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 #include "pfc_sort.h"
 
@@ -246,4 +247,17 @@ hipError_t pfc_canon_candidates(void *cand, const int *ccount, size_t cap, const
     hipLaunchKernelGGL(k_canon_unpack, dim3((unsigned)g), dim3(256), 0, st, (Rec16 *)cand, ccount, cap, (const unsigned long long *)keys_out,
                        (const int *)item_of, bits_b);
     return hipGetLastError();
+}
+
+// ---- pfc_contact_surface: every candidate's polygon and traction-point offset (an exclusive scan of {0 / 1, points} pairs)
+namespace {
+struct alignas(16) LL2 { long long a, b; };
+struct LL2Plus {
+    __host__ __device__ LL2 operator()(const LL2 &x, const LL2 &y) const { return LL2{x.a + y.a, x.b + y.b}; }
+};
+}  // namespace
+
+hipError_t pfc_scan_pairs(void *temp, size_t *temp_bytes, const long long *in, long long *out, size_t n, hipStream_t st) {
+    return rocprim::exclusive_scan(temp, *temp_bytes, reinterpret_cast<const LL2 *>(in), reinterpret_cast<LL2 *>(out), LL2{0, 0}, n,
+                                   LL2Plus(), st);
 }

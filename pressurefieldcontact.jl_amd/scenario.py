@@ -9,6 +9,7 @@ the trailing ``!``), restricted to what the hot path needs:
   add_friction_bristle(id_1, id_2, ..)     :384-399      -> ContactInstructions with Bristle (:5-20)
   finalize()                               :206-231      -> uploads meshes/trees/instructions (pfc_finalize)
   force_all_elastic_intersections(...)     src/contact_algorithms_non_friction.jl:60-84 -> pfc_eval
+  contact_surface(pose, twist, ins_ids=)   TractionCache + normal_wrench_cop per item     -> pfc_contact_surface
 
 The rigid-body side of calcXd! (RigidBodyDynamics: poses, twists, Jacobians, mass matrix, third-law scatter)
 stays with the host integrator; this class takes the per-instruction relative pose / twist / bristle state that
@@ -28,6 +29,7 @@ from .geometry import EMesh, OBBTree, build_tree
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
+_llp = C.POINTER(C.c_longlong)
 
 
 def default_chi() -> float:
@@ -189,6 +191,66 @@ class BoundEvaluation:
         if rc != 0:
             self._m._check(rc)
         return self.wrench, self.sdot, self.counts
+
+
+@dataclass(eq=False)
+class ContactSurface:
+    """The contact surface of n items (pfc_contact_surface), frame r2 of every item:
+
+    poly_off  (n+1,)    int64    the polygons of item i are poly_off[i] : poly_off[i+1]
+    poly_idx  (P, 3)    int32    element of mesh_1, element of mesh_2, vertex count (3..8); ascending pairs within an item
+    poly_xyz  (P, 8, 3) float64  vertices, unused slots 0
+    poly_trac (P+1,)    int64    the traction points of polygon k are poly_trac[k] : poly_trac[k+1]
+    trac      (T, 8)    float64  TractionCache entries n̂ (3), r (3), dA, p -- in the reference's fan and quadrature order
+    summary   (n, 11)   float64  normal wrench [ang 3; lin 3] about the r2 origin, cop (3), sum p dA, sum dA; zeros without points
+    counts    (n, 4)    int32    as force_all_elastic_intersections'
+    """
+
+    poly_off: np.ndarray
+    poly_idx: np.ndarray
+    poly_xyz: np.ndarray
+    poly_trac: np.ndarray
+    trac: np.ndarray
+    summary: np.ndarray
+    counts: np.ndarray
+
+    def __post_init__(self):
+        for f in ("poly_off", "poly_idx", "poly_xyz", "poly_trac", "trac", "summary", "counts"):
+            setattr(self, f, np.asarray(getattr(self, f)))
+        n = self.poly_off.shape[0] - 1 if self.poly_off.ndim == 1 else -1
+        P, T = self.poly_idx.shape[0] if self.poly_idx.ndim == 2 else -1, self.trac.shape[0] if self.trac.ndim == 2 else -1
+        if n < 0:
+            raise ValueError("poly_off must be a vector of n_items + 1 offsets")
+        if self.poly_idx.shape != (P, 3) or P < 0:
+            raise ValueError("poly_idx must be (P, 3)")
+        if self.poly_xyz.shape != (P, 8, 3):
+            raise ValueError("poly_xyz must be (P, 8, 3)")
+        if self.poly_trac.shape != (P + 1,):
+            raise ValueError("poly_trac must have P + 1 offsets")
+        if self.trac.shape != (T, 8) or T < 0:
+            raise ValueError("trac must be (T, 8)")
+        if self.summary.shape != (n, 11):
+            raise ValueError("summary must be (n_items, 11)")
+        if self.counts.shape != (n, 4):
+            raise ValueError("counts must be (n_items, 4)")
+        if int(self.poly_off[0]) != 0 or int(self.poly_off[-1]) != P or int(self.poly_trac[0]) != 0 or int(self.poly_trac[-1]) != T:
+            raise ValueError("offsets do not cover the polygon and traction arrays")
+
+    @property
+    def n_items(self) -> int:
+        return self.poly_off.shape[0] - 1
+
+    def item(self, i: int) -> dict:
+        """Views of item i: keys (m, 2) element pairs, n_vert (m,), xyz (m, 8, 3), poly_trac (m + 1,) offsets into its own trac,
+        trac (t, 8), wrench (6,), cop (3,), sum_p_dA, area, counts (4,)."""
+        if not 0 <= i < self.n_items:
+            raise IndexError(i)
+        p0, p1 = int(self.poly_off[i]), int(self.poly_off[i + 1])
+        t0, t1 = int(self.poly_trac[p0]), int(self.poly_trac[p1])
+        s = self.summary[i]
+        return dict(keys=self.poly_idx[p0:p1, :2], n_vert=self.poly_idx[p0:p1, 2], xyz=self.poly_xyz[p0:p1],
+                    poly_trac=self.poly_trac[p0:p1 + 1] - t0, trac=self.trac[t0:t1], wrench=s[0:6], cop=s[6:9],
+                    sum_p_dA=float(s[9]), area=float(s[10]), counts=self.counts[i])
 
 
 class MechanismScenario:
@@ -461,6 +523,53 @@ class MechanismScenario:
         (the chunks of one Jacobian); only the Dual passes run.  Follow with check()."""
         self._check(_lib.lib().pfc_eval_dual_device_more(self._h, int(n_dir), d_dpose, d_dtwist, d_ds or None, d_dwrench,
                                                          d_dsdot, stream or None))
+
+    def contact_surface(self, pose, twist, ins_ids: Optional[Sequence[int]] = None) -> ContactSurface:
+        """The contact surface of every item (pfc_contact_surface): clipped polygons, traction points and normal wrench / cop in
+        one canonical order (see ContactSurface).  pose (n,24), twist (n,6), ins_ids (n,) or None.  The buffers start at the
+        size of the previous call's surface; if the surface is bigger they are grown to its totals and the call is issued again."""
+        if not self._finalized:
+            raise RuntimeError("finalize the scenario first")
+        pose_a, pose_p = _da(pose)
+        n = pose_a.size // 24
+        if pose_a.size != 24 * n:
+            raise ValueError("pose must have 24 entries per item")
+        tw_a, tw_p = _da(twist)
+        if tw_a.size != 6 * n:
+            raise ValueError("twist must have 6 entries per item")
+        id_p = None
+        if ins_ids is not None:
+            id_a, id_p = _ia(ins_ids)
+            if id_a.size != n:
+                raise ValueError("ins_ids must have one entry per item")
+        cap_p, cap_t = getattr(self, "_surf_caps", (max(64, 8 * n), max(512, 64 * n)))
+        L = _lib.lib()
+        for attempt in range(2):
+            poly_off = np.zeros(n + 1, dtype=np.int64); poly_idx = np.zeros((cap_p, 3), dtype=np.int32)
+            poly_xyz = np.zeros((cap_p, 8, 3)); poly_trac = np.zeros(cap_p + 1, dtype=np.int64); trac = np.zeros((cap_t, 8))
+            summary = np.zeros((n, 11)); counts = np.zeros((n, 4), dtype=np.int32); totals = np.zeros(2, dtype=np.int64)
+            rc = L.pfc_contact_surface(self._h, n, None if id_p is None else C.cast(id_p, _ip), C.cast(pose_p, _dp), C.cast(tw_p, _dp),
+                                       cap_p, cap_t, poly_off.ctypes.data_as(_llp), poly_idx.ctypes.data_as(_ip),
+                                       poly_xyz.ctypes.data_as(_dp), poly_trac.ctypes.data_as(_llp), trac.ctypes.data_as(_dp),
+                                       summary.ctypes.data_as(_dp), counts.ctypes.data_as(_ip), totals.ctypes.data_as(_llp))
+            if rc == _lib.ERR_OVERFLOW and attempt == 0:
+                cap_p, cap_t = max(cap_p, int(totals[0])), max(cap_t, int(totals[1]))
+                continue
+            self._check(rc)
+            break
+        self._surf_caps = (cap_p, cap_t)
+        P, T = int(totals[0]), int(totals[1])
+        return ContactSurface(poly_off, poly_idx[:P], poly_xyz[:P], poly_trac[:P + 1], trac[:T], summary, counts)
+
+    def contact_surface_device(self, n_items: int, d_ins_ids: int, d_pose: int, d_twist: int, cap_poly: int, cap_trac: int,
+                               d_poly_off: int, d_poly_idx: int, d_poly_xyz: int, d_poly_trac: int, d_trac: int, d_summary: int,
+                               d_counts: int, d_totals: int, stream: int = 0):
+        """pfc_contact_surface_device: raw device addresses; asynchronous; follow with check() (ERR_OVERFLOW: re-issue, after
+        growing the buffers if the totals exceed a capacity)."""
+        self._check(_lib.lib().pfc_contact_surface_device(self._h, int(n_items), d_ins_ids or None, d_pose, d_twist, int(cap_poly),
+                                                          int(cap_trac), d_poly_off, d_poly_idx or None, d_poly_xyz or None, d_poly_trac,
+                                                          d_trac or None, d_summary or None, d_counts or None, d_totals,
+                                                          stream or None))
 
     def check(self) -> int:
         """pfc_check: synchronise; returns the status (PFC_ERR_OVERFLOW means: re-issue, buffers were grown)."""
