@@ -286,6 +286,41 @@ int pfc_contact_surface_device(pfc_handle h, int n_items, const int *d_ins_ids, 
                                long long *d_poly_trac, double *d_trac, double *d_summary, int *d_counts, long long *d_totals,
                                void *stream);
 
+/*
+ * The contact surface with its friction half: what pfc_contact_surface returns, plus per traction point the friction force that
+ * traction() computes (src/contact_algorithms_friction.jl:12-48) and per item the friction wrench, the total wrench, ṡ and the
+ * bristle patch state.  pose, twist, s and ins_ids as pfc_eval (s may be NULL when no item is bristle: zeros).  poly_off,
+ * poly_idx, poly_xyz, poly_trac, trac, summary, counts and totals are byte-identical to what pfc_contact_surface returns for the
+ * same (ins_ids, pose, twist): the same launches compute them.  Frame r2 throughout.
+ *   fric          cap_trac x 4       OUT per point in trac order: T_c (3) = traction(...) (already times p dA), and the branch
+ *                                        taken as a double: 0 the first (regularized |vel_t|^2 < v_c^2, bristle |T̄s|^2 < mu_s^2), 1 the other
+ *   fric_summary  n_items x 20       OUT [0:6] total wrench about the r2 origin [ang; lin] (= summary[0:6] + fric_summary[6:12], one
+ *                                        add per component: what pfc_eval returns, in this order of summation);
+ *                                        [6:12] friction wrench about the r2 origin;
+ *                                        [12:18] ṡ: -(1/tau) (K̄^{-1/2} S⁻¹ w_fric_cop + s) for a bristle item with points, -s/tau
+ *                                        for one without, zeros for a regularized item (bristle_wrench_in_world, no_contact!);
+ *                                        [18] sum p dA and [19] the number of the points that took the first branch
+ *   stiff         n_items x 84       OUT (may be NULL) K (36, column-major, k̄ included; calc_patch_spatial_stiffness! about the
+ *                                        cop of summary), K̄^{-1/2} (36), diag S⁻¹ (6), Δ² (6) (decompose_K!, :85-132): what
+ *                                        pfc_debug_stiffness exposes; zeros for regularized items and items without points
+ * Every per-item sum is a fixed function of the canonical candidate list (no grid, timing, option or handle enters, no
+ * atomics): two calls on the same inputs return the same bytes in every output.  Capacity as pfc_contact_surface, extended: on
+ * PFC_ERR_OVERFLOW the call writes totals, poly_off, summary, fric_summary, stiff and counts, and writes no byte of poly_idx,
+ * poly_xyz, poly_trac, trac or fric -- cap_poly = cap_trac = 0 returns every per-item row and no per-point output.  fric may be
+ * NULL when cap_trac = 0.  The key limit, the sort fallback, the end of Dual reuse and the multi-device rule are those of
+ * pfc_contact_surface.  Host buffers, synchronous.
+ */
+int pfc_contact_surface_fric(pfc_handle h, int n_items, const int *ins_ids, const double *pose, const double *twist, const double *s,
+                             long long cap_poly, long long cap_trac, long long *poly_off, int *poly_idx, double *poly_xyz,
+                             long long *poly_trac, double *trac, double *fric, double *summary, double *fric_summary, double *stiff,
+                             int *counts, long long *totals);
+/* The same with every buffer in device memory, enqueued on `stream` (NULL = the handle's own) without a host synchronisation;
+ * then pfc_check(), as after pfc_contact_surface_device. */
+int pfc_contact_surface_fric_device(pfc_handle h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
+                                    const double *d_s, long long cap_poly, long long cap_trac, long long *d_poly_off, int *d_poly_idx,
+                                    double *d_poly_xyz, long long *d_poly_trac, double *d_trac, double *d_fric, double *d_summary,
+                                    double *d_fric_summary, double *d_stiff, int *d_counts, long long *d_totals, void *stream);
+
 /* Options: "debug" (1: keep per-pair clip counts and materialise traction points of every item so that the
  * pfc_debug_* calls work), "profile" (1: bracket each stage with HIP events), "max_levels" (0 = automatic),
  * "bfs_levels" (-1 = automatic: level-synchronous seed expansion only until there are >= 2048 seed pairs),

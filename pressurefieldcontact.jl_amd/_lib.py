@@ -66,6 +66,10 @@ SIGNATURES = {
                                       _ip, _llp]),
     "pfc_contact_surface_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong]
                                    + [C.c_void_p] * 9),
+    "pfc_contact_surface_fric": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp, _dp, C.c_longlong, C.c_longlong, _llp, _ip, _dp, _llp,
+                                           _dp, _dp, _dp, _dp, _dp, _ip, _llp]),
+    "pfc_contact_surface_fric_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                                                  C.c_longlong] + [C.c_void_p] * 12),
 }
 
 
@@ -77,7 +81,7 @@ class PFCError(RuntimeError):
 
 def build(force: bool = False) -> str:
     """Compile csrc/pfc_hip.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("pfc_hip.hip", "pfc_tree.cpp", "pfc_sort.hip", "pfc_kernels.h", "pfc_bp.h", "pfc_np.h", "pfc_br.h", "pfc_dual.h", "pfc_fused.h", "pfc_clip.h", "pfc_multi.h", "pfc_sort.h", "pfc_surface.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("pfc_hip.hip", "pfc_tree.cpp", "pfc_sort.hip", "pfc_kernels.h", "pfc_bp.h", "pfc_np.h", "pfc_br.h", "pfc_dual.h", "pfc_fused.h", "pfc_clip.h", "pfc_multi.h", "pfc_sort.h", "pfc_surface.h", "pfc_surface_fric.h")]
     srcs.append(os.path.join(os.path.dirname(HERE), "include", "pfc.h"))
     srcs.append(os.path.abspath(__file__))      # the compiler flags live here
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)

@@ -15,6 +15,7 @@
 //                  k_fixed_reduce (pfc_dual.h), the FixedSink record lists of accumulate_items / dual_accumulate, and
 //                  pfc_sort.hip (a translation unit of its own: rocPRIM radix sort of the candidate list)
 //   pfc_surface.h  k_surf_count / k_surf_summary / k_surf_emit: the contact surface in canonical order (pfc_contact_surface)
+//   pfc_surface_fric.h  k_sfric_mom / k_sfric_eig / k_sfric_pass / k_sfric_final: its friction half (pfc_contact_surface_fric)
 //   pfc_multi.h    host code: multi-device handles (pfc_create_multi)
 // This file: mesh record preparation (k_prep_tri, k_prep_tet), per-item setup (k_setup_items), work-list management,
 // hipGraph capture / replay, the two-half evaluation and every extern "C" entry point.
@@ -181,6 +182,7 @@ __global__ void k_repose(int n_items, const double *__restrict__ pose, ItemRec *
 #include "pfc_br.h"
 #include "pfc_fused.h"
 #include "pfc_surface.h"
+#include "pfc_surface_fric.h"
 
 }  // namespace pfc
 
@@ -443,6 +445,9 @@ struct pfc_context {
     DevBuf<int> surf_hi;
     DevBuf<double> surf_hd, surf_in;
     size_t surf_hcap_poly = 0, surf_hcap_trac = 0;    // ... sized for this many polygons / traction points
+    // pfc_contact_surface_fric (pfc_surface_fric.h): per item the moment and friction records of its waves and eig_item's block
+    DevBuf<double> sfric_mom, sfric_sum, sfric_res;
+    DevBuf<double> sfric_hd;            // host-pointer form: device staging of fric_summary, stiff and fric
 };
 
 namespace {
@@ -1398,6 +1403,7 @@ void pfc_destroy(pfc_handle h) {
     h->surf_canon_off.release(); h->surf_canon_fill.release(); h->surf_canon_item.release();
     h->surf_keys[0].release(); h->surf_keys[1].release(); h->surf_tmp.release();
     h->surf_hl.release(); h->surf_hi.release(); h->surf_hd.release(); h->surf_in.release();
+    h->sfric_mom.release(); h->sfric_sum.release(); h->sfric_res.release(); h->sfric_hd.release();
     if (h->h_surf) (void)hipHostFree(h->h_surf);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -1781,12 +1787,20 @@ int pfc_eval_device(pfc_handle h, int n_items, const int *d_ins_ids, const doubl
 namespace {
 
 // ---- pfc_contact_surface (pfc_surface.h) ----------------------------------------------------------------------------
+// The outputs of pfc_contact_surface_fric beyond the surface's (device pointers); s may be null, stiff may be null.
+struct SurfFricOut {
+    const double *s;
+    double *fric, *fric_summary, *stiff;
+};
+
 // The whole call on stream st: item setup, the batched broadphase, the candidate list in canonical order, count, scan, item
 // segments, summary and -- when both capacities suffice -- the emission; the status block goes to pinned memory for
-// check_surface.  Always this launch sequence, whatever "fused", "team", "split_min", "fixed_order" or "debug" say.
+// check_surface.  Always this launch sequence, whatever "fused", "team", "split_min", "fixed_order" or "debug" say.  With fo
+// (pfc_contact_surface_fric) the same launches, the bristle state s in the item setup, and the four friction kernels of
+// pfc_surface_fric.h between the emission and k_surf_final.
 int surface_enqueue(pfc_context *h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist, long long cap_poly,
                     long long cap_trac, long long *d_poly_off, int *d_poly_idx, double *d_poly_xyz, long long *d_poly_trac,
-                    double *d_trac, double *d_summary, int *d_counts, long long *d_totals, hipStream_t st) {
+                    double *d_trac, double *d_summary, int *d_counts, long long *d_totals, hipStream_t st, const SurfFricOut *fo = nullptr) {
     // an evaluation for the call-order rules: the candidate list and the counters a Dual evaluation could reuse are overwritten
     h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false; h->pending_more = false;
     h->pin_in_dual_n = 0; h->pin_din_valid = false;
@@ -1808,6 +1822,11 @@ int surface_enqueue(pfc_context *h, int n_items, const int *d_ins_ids, const dou
     HIP_TRY(h, h->surf_canon_item.ensure(c));
     HIP_TRY(h, h->surf_keys[0].ensure(c));
     HIP_TRY(h, h->surf_keys[1].ensure(c));
+    if (fo) {
+        HIP_TRY(h, h->sfric_mom.ensure((size_t)n_items * kFricSplit * kFricMom));
+        HIP_TRY(h, h->sfric_sum.ensure((size_t)n_items * kFricSplit * kFricSums));
+        HIP_TRY(h, h->sfric_res.ensure((size_t)n_items * kResStride));
+    }
     size_t scan_bytes = 0, sort_bytes = 0;
     HIP_TRY(h, pfc_scan_pairs(nullptr, &scan_bytes, nullptr, nullptr, c + 1, st));
     if (h->surf_whole_list) HIP_TRY(h, pfc_sort_temp_bytes(c, bits, &sort_bytes));
@@ -1824,7 +1843,7 @@ int surface_enqueue(pfc_context *h, int n_items, const int *d_ins_ids, const dou
     int *ccount = h->ctr.p, *next_seed = h->ctr.p + 2, *ucount = h->ctr.p + 4, *fcount = h->ctr.p + 6;   // (record_eval's layout)
 
     EvalArgs ea;
-    ea.n_items = n_items; ea.ins_ids = d_ins_ids; ea.pose = d_pose; ea.twist = d_twist; ea.s = nullptr; ea.bp_pose = nullptr;
+    ea.n_items = n_items; ea.ins_ids = d_ins_ids; ea.pose = d_pose; ea.twist = d_twist; ea.s = fo ? fo->s : nullptr; ea.bp_pose = nullptr;
     ea.ins = h->d_ins; ea.meshes = h->d_meshes; ea.n_ins = (int)h->ins.size(); ea.items = h->items.p;
     ea.frontier0 = h->frontier[0].p; ea.fcount = fcount; ea.acc = h->acc.p; ea.icnt = h->icnt.p;
     ea.status = h->status.p;
@@ -1853,6 +1872,19 @@ int surface_enqueue(pfc_context *h, int n_items, const int *d_ins_ids, const dou
     hipLaunchKernelGGL(k_surf_summary, dim3(n_items < 8192 ? n_items : 8192), dim3(64), 0, st, g);
     if (h->any_tet_tet) hipLaunchKernelGGL((k_surf_emit<true>), dim3(grid), dim3(kSurfBlock), 0, st, g);
     else hipLaunchKernelGGL((k_surf_emit<false>), dim3(grid), dim3(kSurfBlock), 0, st, g);
+    if (fo) {
+        SurfFricArgs f;
+        f.mom = h->sfric_mom.p; f.fsum = h->sfric_sum.p; f.res = h->sfric_res.p;
+        f.fric = fo->fric; f.fric_summary = fo->fric_summary; f.stiff = fo->stiff;
+        const int grid_w = n_items * kFricSplit;                  // one workgroup per wave of an item (n_items <= 2^27: surface_fric_args)
+        const int grid_i = n_items < 8192 ? n_items : 8192;                                                  // one wave per item
+        if (h->any_tet_tet) hipLaunchKernelGGL((k_sfric_mom<true>), dim3(grid_w), dim3(kSurfBlock), 0, st, g, f);
+        else hipLaunchKernelGGL((k_sfric_mom<false>), dim3(grid_w), dim3(kSurfBlock), 0, st, g, f);
+        hipLaunchKernelGGL(k_sfric_eig, dim3(grid_i), dim3(64), 0, st, g, f);
+        if (h->any_tet_tet) hipLaunchKernelGGL((k_sfric_pass<true>), dim3(grid_w), dim3(kSurfBlock), 0, st, g, f);
+        else hipLaunchKernelGGL((k_sfric_pass<false>), dim3(grid_w), dim3(kSurfBlock), 0, st, g, f);
+        hipLaunchKernelGGL(k_sfric_final, dim3(grid_for(n_items, 64, 4096)), dim3(64), 0, st, g, f);
+    }
     hipLaunchKernelGGL(k_surf_final, dim3(1), dim3(64), 0, st, h->ctr.p, n_ctr, h->status.p, (const long long *)h->surf_off.p, (int)c,
                        h->surf_out.p);
     HIP_TRY(h, hipMemcpyAsync(h->h_surf, h->surf_out.p, sizeof(long long) * ((size_t)n_ctr + 3), hipMemcpyDeviceToHost, st));
@@ -1923,13 +1955,12 @@ int surface_args(pfc_context *h, int n_items, const void *ins_ids, const void *p
 
 }  // namespace
 
-int pfc_contact_surface(pfc_handle hh, int n_items, const int *ins_ids, const double *pose, const double *twist, long long cap_poly,
-                        long long cap_trac, long long *poly_off, int *poly_idx, double *poly_xyz, long long *poly_trac, double *trac,
-                        double *summary, int *counts, long long *totals) {
-    if (!hh) return PFC_ERR_BAD_ARG;
-    pfc_context *h = surface_ctx(hh);
-    int rc = surface_args(h, n_items, ins_ids, pose, twist, cap_poly, cap_trac, poly_off, poly_idx, poly_xyz, poly_trac, trac, summary, totals);
-    if (rc != PFC_OK) { if (hh != h) hh->err = h->err; return rc; }
+namespace {
+
+// The host-pointer form of both surface calls; fo (pfc_contact_surface_fric) holds host pointers here: s, fric, fric_summary, stiff.
+int surface_host(pfc_context *hh, pfc_context *h, int n_items, const int *ins_ids, const double *pose, const double *twist, long long cap_poly,
+                 long long cap_trac, long long *poly_off, int *poly_idx, double *poly_xyz, long long *poly_trac, double *trac,
+                 double *summary, int *counts, long long *totals, const SurfFricOut *fo) {
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t n = (size_t)n_items;
     if (n_items == 0) {
@@ -1938,14 +1969,17 @@ int pfc_contact_surface(pfc_handle hh, int n_items, const int *ins_ids, const do
         poly_off[0] = 0; poly_trac[0] = 0; totals[0] = totals[1] = 0;
         return PFC_OK;
     }
-    // inputs: pose | twist | ins_ids
-    HIP_TRY(h, h->surf_in.ensure(n * 30 + (n + 1) / 2 + 1));
+    // inputs: pose | twist | ins_ids (| s)
+    const size_t s_at = n * 30 + (n + 1) / 2 + 1;
+    HIP_TRY(h, h->surf_in.ensure(fo ? s_at + n * 6 : s_at));
     double *di = h->surf_in.p;
     HIP_TRY(h, hipMemcpyAsync(di, pose, sizeof(double) * n * 24, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(di + n * 24, twist, sizeof(double) * n * 6, hipMemcpyHostToDevice, h->stream));
     if (ins_ids) HIP_TRY(h, hipMemcpyAsync(di + n * 30, ins_ids, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
+    if (fo && fo->s) HIP_TRY(h, hipMemcpyAsync(di + s_at, fo->s, sizeof(double) * n * 6, hipMemcpyHostToDevice, h->stream));
     // outputs are staged in device buffers sized for what the last calls needed (at most the caller's capacities): a call that
     // needs more within the caller's capacities grows them and runs again
+    int rc = PFC_OK;
     long long tot_p = 0, tot_t = 0;
     for (int attempt = 0; attempt < 40; ++attempt) {
         const size_t dp = (size_t)(cap_poly < (long long)h->surf_hcap_poly ? cap_poly : (long long)h->surf_hcap_poly);
@@ -1956,8 +1990,14 @@ int pfc_contact_surface(pfc_handle hh, int n_items, const int *ins_ids, const do
         long long *l_off = h->surf_hl.p, *l_tot = l_off + n + 1, *l_ptr = l_tot + 2;
         int *i_cnt = h->surf_hi.p, *i_idx = i_cnt + 4 * n;
         double *d_sum = h->surf_hd.p, *d_xyz = d_sum + 11 * n, *d_trac = d_xyz + 24 * dp;
+        SurfFricOut dfo;
+        if (fo) {
+            HIP_TRY(h, h->sfric_hd.ensure((kFricOut + kStiffOut) * n + 4 * dt + 1));
+            dfo.s = fo->s ? di + s_at : nullptr;
+            dfo.fric_summary = h->sfric_hd.p; dfo.stiff = dfo.fric_summary + kFricOut * n; dfo.fric = dfo.stiff + kStiffOut * n;
+        }
         rc = surface_enqueue(h, n_items, ins_ids ? (const int *)(di + n * 30) : nullptr, di, di + n * 24, (long long)dp, (long long)dt, l_off,
-                             i_idx, d_xyz, l_ptr, d_trac, d_sum, i_cnt, l_tot, h->stream);
+                             i_idx, d_xyz, l_ptr, d_trac, d_sum, i_cnt, l_tot, h->stream, fo ? &dfo : nullptr);
         if (rc == PFC_OK) rc = check_surface(h);
         if (rc == PFC_ERR_OVERFLOW && h->surf_cap_short) {
             tot_p = h->h_surf[1]; tot_t = h->h_surf[2];
@@ -1981,6 +2021,11 @@ int pfc_contact_surface(pfc_handle hh, int n_items, const int *ins_ids, const do
     HIP_TRY(h, hipMemcpyAsync(totals, l_tot, sizeof(long long) * 2, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(summary, d_sum, sizeof(double) * 11 * n, hipMemcpyDeviceToHost, h->stream));
     if (counts) HIP_TRY(h, hipMemcpyAsync(counts, i_cnt, sizeof(int) * 4 * n, hipMemcpyDeviceToHost, h->stream));
+    const double *f_sum = fo ? h->sfric_hd.p : nullptr;
+    if (fo) {
+        HIP_TRY(h, hipMemcpyAsync(fo->fric_summary, f_sum, sizeof(double) * kFricOut * n, hipMemcpyDeviceToHost, h->stream));
+        if (fo->stiff) HIP_TRY(h, hipMemcpyAsync(fo->stiff, f_sum + kFricOut * n, sizeof(double) * kStiffOut * n, hipMemcpyDeviceToHost, h->stream));
+    }
     if (rc == PFC_OK) {
         tot_p = h->h_surf[1]; tot_t = h->h_surf[2];
         HIP_TRY(h, hipMemcpyAsync(poly_trac, l_ptr, sizeof(long long) * ((size_t)tot_p + 1), hipMemcpyDeviceToHost, h->stream));
@@ -1989,10 +2034,47 @@ int pfc_contact_surface(pfc_handle hh, int n_items, const int *ins_ids, const do
             HIP_TRY(h, hipMemcpyAsync(poly_xyz, d_xyz, sizeof(double) * 24 * (size_t)tot_p, hipMemcpyDeviceToHost, h->stream));
         }
         if (tot_t > 0) HIP_TRY(h, hipMemcpyAsync(trac, d_trac, sizeof(double) * 8 * (size_t)tot_t, hipMemcpyDeviceToHost, h->stream));
+        if (fo && tot_t > 0)
+            HIP_TRY(h, hipMemcpyAsync(fo->fric, f_sum + (kFricOut + kStiffOut) * n, sizeof(double) * 4 * (size_t)tot_t, hipMemcpyDeviceToHost,
+                                      h->stream));
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (rc != PFC_OK && hh != h) hh->err = h->err;
     return rc;
+}
+
+// pfc_contact_surface_fric's buffers beyond the surface call's
+int surface_fric_args(pfc_context *h, int n_items, long long cap_trac, const void *fric, const void *fric_summary) {
+    if ((n_items > 0 && !fric_summary) || (cap_trac > 0 && !fric)) return fail(h, PFC_ERR_BAD_ARG, "pfc_contact_surface_fric: null buffer");
+    if (n_items > (1 << 27)) return fail(h, PFC_ERR_BAD_ARG, "pfc_contact_surface_fric: more than 2^27 items: evaluate the batch in parts");
+    return PFC_OK;
+}
+
+}  // namespace
+
+int pfc_contact_surface(pfc_handle hh, int n_items, const int *ins_ids, const double *pose, const double *twist, long long cap_poly,
+                        long long cap_trac, long long *poly_off, int *poly_idx, double *poly_xyz, long long *poly_trac, double *trac,
+                        double *summary, int *counts, long long *totals) {
+    if (!hh) return PFC_ERR_BAD_ARG;
+    pfc_context *h = surface_ctx(hh);
+    int rc = surface_args(h, n_items, ins_ids, pose, twist, cap_poly, cap_trac, poly_off, poly_idx, poly_xyz, poly_trac, trac, summary, totals);
+    if (rc != PFC_OK) { if (hh != h) hh->err = h->err; return rc; }
+    return surface_host(hh, h, n_items, ins_ids, pose, twist, cap_poly, cap_trac, poly_off, poly_idx, poly_xyz, poly_trac, trac, summary, counts,
+                        totals, nullptr);
+}
+
+int pfc_contact_surface_fric(pfc_handle hh, int n_items, const int *ins_ids, const double *pose, const double *twist, const double *s,
+                             long long cap_poly, long long cap_trac, long long *poly_off, int *poly_idx, double *poly_xyz, long long *poly_trac,
+                             double *trac, double *fric, double *summary, double *fric_summary, double *stiff, int *counts, long long *totals) {
+    if (!hh) return PFC_ERR_BAD_ARG;
+    pfc_context *h = surface_ctx(hh);
+    int rc = surface_args(h, n_items, ins_ids, pose, twist, cap_poly, cap_trac, poly_off, poly_idx, poly_xyz, poly_trac, trac, summary, totals);
+    if (rc == PFC_OK) rc = surface_fric_args(h, n_items, cap_trac, fric, fric_summary);
+    if (rc != PFC_OK) { if (hh != h) hh->err = h->err; return rc; }
+    SurfFricOut fo;
+    fo.s = s; fo.fric = fric; fo.fric_summary = fric_summary; fo.stiff = stiff;
+    return surface_host(hh, h, n_items, ins_ids, pose, twist, cap_poly, cap_trac, poly_off, poly_idx, poly_xyz, poly_trac, trac, summary, counts,
+                        totals, &fo);
 }
 
 int pfc_contact_surface_device(pfc_handle hh, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
@@ -2015,6 +2097,34 @@ int pfc_contact_surface_device(pfc_handle hh, int n_items, const int *d_ins_ids,
     }
     rc = surface_enqueue(h, n_items, d_ins_ids, d_pose, d_twist, cap_poly, cap_trac, d_poly_off, d_poly_idx, d_poly_xyz, d_poly_trac,
                          d_trac, d_summary, d_counts, d_totals, st);
+    if (rc != PFC_OK && hh != h) hh->err = h->err;
+    return rc;
+}
+
+int pfc_contact_surface_fric_device(pfc_handle hh, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
+                                    const double *d_s, long long cap_poly, long long cap_trac, long long *d_poly_off, int *d_poly_idx,
+                                    double *d_poly_xyz, long long *d_poly_trac, double *d_trac, double *d_fric, double *d_summary,
+                                    double *d_fric_summary, double *d_stiff, int *d_counts, long long *d_totals, void *stream) {
+    if (!hh) return PFC_ERR_BAD_ARG;
+    pfc_context *h = surface_ctx(hh);
+    int rc = surface_args(h, n_items, d_ins_ids, d_pose, d_twist, cap_poly, cap_trac, d_poly_off, d_poly_idx, d_poly_xyz, d_poly_trac,
+                          d_trac, d_summary, d_totals);
+    if (rc == PFC_OK) rc = surface_fric_args(h, n_items, cap_trac, d_fric, d_fric_summary);
+    if (rc != PFC_OK) { if (hh != h) hh->err = h->err; return rc; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    if (n_items == 0) {
+        h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false; h->pin_in_dual_n = 0; h->pin_din_valid = false;
+        ++h->value_serial;
+        HIP_TRY(h, hipMemsetAsync(d_poly_off, 0, sizeof(long long), st));
+        HIP_TRY(h, hipMemsetAsync(d_poly_trac, 0, sizeof(long long), st));
+        HIP_TRY(h, hipMemsetAsync(d_totals, 0, sizeof(long long) * 2, st));
+        return PFC_OK;
+    }
+    SurfFricOut fo;
+    fo.s = d_s; fo.fric = d_fric; fo.fric_summary = d_fric_summary; fo.stiff = d_stiff;
+    rc = surface_enqueue(h, n_items, d_ins_ids, d_pose, d_twist, cap_poly, cap_trac, d_poly_off, d_poly_idx, d_poly_xyz, d_poly_trac,
+                         d_trac, d_summary, d_counts, d_totals, st, &fo);
     if (rc != PFC_OK && hh != h) hh->err = h->err;
     return rc;
 }

@@ -10,6 +10,7 @@ the trailing ``!``), restricted to what the hot path needs:
   finalize()                               :206-231      -> uploads meshes/trees/instructions (pfc_finalize)
   force_all_elastic_intersections(...)     src/contact_algorithms_non_friction.jl:60-84 -> pfc_eval
   contact_surface(pose, twist, ins_ids=)   TractionCache + normal_wrench_cop per item     -> pfc_contact_surface
+  contact_surface_fric(pose, twist, s=, ins_ids=)  ... + per-point friction, ṡ, K       -> pfc_contact_surface_fric
 
 The rigid-body side of calcXd! (RigidBodyDynamics: poses, twists, Jacobians, mass matrix, third-law scatter)
 stays with the host integrator; this class takes the per-instruction relative pose / twist / bristle state that
@@ -251,6 +252,53 @@ class ContactSurface:
         return dict(keys=self.poly_idx[p0:p1, :2], n_vert=self.poly_idx[p0:p1, 2], xyz=self.poly_xyz[p0:p1],
                     poly_trac=self.poly_trac[p0:p1 + 1] - t0, trac=self.trac[t0:t1], wrench=s[0:6], cop=s[6:9],
                     sum_p_dA=float(s[9]), area=float(s[10]), counts=self.counts[i])
+
+
+@dataclass(eq=False)
+class FrictionSurface:
+    """The contact surface with its friction half (pfc_contact_surface_fric), frame r2 of every item:
+
+    surface       ContactSurface           what contact_surface returns for the same inputs, byte for byte
+    fric          (T, 4)   float64  per traction point (surface.trac order): T_c (3) = traction() times p dA, branch (0.0 the first)
+    fric_summary  (n, 20)  float64  total wrench [ang 3; lin 3] about the r2 origin (= summary[0:6] + friction wrench), friction
+                                    wrench (6), ṡ (6), first-branch sum p dA, first-branch count
+    stiff         (n, 84)  float64  K (36, column-major), K̄^{-1/2} (36), diag S⁻¹ (6), Δ² (6); zeros unless bristle with points
+    """
+
+    surface: ContactSurface
+    fric: np.ndarray
+    fric_summary: np.ndarray
+    stiff: np.ndarray
+
+    def __post_init__(self):
+        if not isinstance(self.surface, ContactSurface):
+            raise ValueError("surface must be a ContactSurface")
+        for f in ("fric", "fric_summary", "stiff"):
+            setattr(self, f, np.asarray(getattr(self, f)))
+        n, T = self.surface.n_items, self.surface.trac.shape[0]
+        if self.fric.shape != (T, 4):
+            raise ValueError("fric must be (T, 4): one row per traction point")
+        if self.fric_summary.shape != (n, 20):
+            raise ValueError("fric_summary must be (n_items, 20)")
+        if self.stiff.shape != (n, 84):
+            raise ValueError("stiff must be (n_items, 84)")
+
+    @property
+    def n_items(self) -> int:
+        return self.surface.n_items
+
+    def item(self, i: int) -> dict:
+        """ContactSurface.item(i), and: fric (t, 4), total_wrench (6,), fric_wrench (6,), sdot (6,), first_p_dA, n_first,
+        K (6, 6), Kbar_inv_sqrt (6, 6), Sinv (6,), Delta (6,)."""
+        d = self.surface.item(i)
+        S = self.surface
+        p0, p1 = int(S.poly_off[i]), int(S.poly_off[i + 1])
+        t0, t1 = int(S.poly_trac[p0]), int(S.poly_trac[p1])
+        f, k = self.fric_summary[i], self.stiff[i]
+        d.update(fric=self.fric[t0:t1], total_wrench=f[0:6], fric_wrench=f[6:12], sdot=f[12:18], first_p_dA=float(f[18]),
+                 n_first=int(f[19]), K=k[0:36].reshape(6, 6, order="F"), Kbar_inv_sqrt=k[36:72].reshape(6, 6, order="F"),
+                 Sinv=k[72:78], Delta=k[78:84])
+        return d
 
 
 class MechanismScenario:
@@ -561,6 +609,51 @@ class MechanismScenario:
         P, T = int(totals[0]), int(totals[1])
         return ContactSurface(poly_off, poly_idx[:P], poly_xyz[:P], poly_trac[:P + 1], trac[:T], summary, counts)
 
+    def contact_surface_fric(self, pose, twist, s=None, ins_ids: Optional[Sequence[int]] = None) -> FrictionSurface:
+        """The contact surface with its friction half (pfc_contact_surface_fric; see FrictionSurface).  pose (n,24), twist (n,6),
+        s (n,6) or None (zeros), ins_ids (n,) or None.  Buffers grow and the call is re-issued as in contact_surface."""
+        if not self._finalized:
+            raise RuntimeError("finalize the scenario first")
+        pose_a, pose_p = _da(pose)
+        n = pose_a.size // 24
+        if pose_a.size != 24 * n:
+            raise ValueError("pose must have 24 entries per item")
+        tw_a, tw_p = _da(twist)
+        if tw_a.size != 6 * n:
+            raise ValueError("twist must have 6 entries per item")
+        s_p = None
+        if s is not None:
+            s_a, s_p = _da(s)
+            if s_a.size != 6 * n:
+                raise ValueError("s must have 6 entries per item")
+        id_p = None
+        if ins_ids is not None:
+            id_a, id_p = _ia(ins_ids)
+            if id_a.size != n:
+                raise ValueError("ins_ids must have one entry per item")
+        cap_p, cap_t = getattr(self, "_surf_caps", (max(64, 8 * n), max(512, 64 * n)))
+        L = _lib.lib()
+        for attempt in range(2):
+            poly_off = np.zeros(n + 1, dtype=np.int64); poly_idx = np.zeros((cap_p, 3), dtype=np.int32)
+            poly_xyz = np.zeros((cap_p, 8, 3)); poly_trac = np.zeros(cap_p + 1, dtype=np.int64); trac = np.zeros((cap_t, 8))
+            fric = np.zeros((cap_t, 4)); summary = np.zeros((n, 11)); fric_summary = np.zeros((n, 20)); stiff = np.zeros((n, 84))
+            counts = np.zeros((n, 4), dtype=np.int32); totals = np.zeros(2, dtype=np.int64)
+            rc = L.pfc_contact_surface_fric(self._h, n, None if id_p is None else C.cast(id_p, _ip), C.cast(pose_p, _dp), C.cast(tw_p, _dp),
+                                            None if s_p is None else C.cast(s_p, _dp), cap_p, cap_t, poly_off.ctypes.data_as(_llp),
+                                            poly_idx.ctypes.data_as(_ip), poly_xyz.ctypes.data_as(_dp), poly_trac.ctypes.data_as(_llp),
+                                            trac.ctypes.data_as(_dp), fric.ctypes.data_as(_dp), summary.ctypes.data_as(_dp),
+                                            fric_summary.ctypes.data_as(_dp), stiff.ctypes.data_as(_dp), counts.ctypes.data_as(_ip),
+                                            totals.ctypes.data_as(_llp))
+            if rc == _lib.ERR_OVERFLOW and attempt == 0:
+                cap_p, cap_t = max(cap_p, int(totals[0])), max(cap_t, int(totals[1]))
+                continue
+            self._check(rc)
+            break
+        self._surf_caps = (cap_p, cap_t)
+        P, T = int(totals[0]), int(totals[1])
+        surface = ContactSurface(poly_off, poly_idx[:P], poly_xyz[:P], poly_trac[:P + 1], trac[:T], summary, counts)
+        return FrictionSurface(surface, fric[:T], fric_summary, stiff)
+
     def contact_surface_device(self, n_items: int, d_ins_ids: int, d_pose: int, d_twist: int, cap_poly: int, cap_trac: int,
                                d_poly_off: int, d_poly_idx: int, d_poly_xyz: int, d_poly_trac: int, d_trac: int, d_summary: int,
                                d_counts: int, d_totals: int, stream: int = 0):
@@ -570,6 +663,18 @@ class MechanismScenario:
                                                           int(cap_trac), d_poly_off, d_poly_idx or None, d_poly_xyz or None, d_poly_trac,
                                                           d_trac or None, d_summary or None, d_counts or None, d_totals,
                                                           stream or None))
+
+    def contact_surface_fric_device(self, n_items: int, d_ins_ids: int, d_pose: int, d_twist: int, d_s: int, cap_poly: int,
+                                    cap_trac: int, d_poly_off: int, d_poly_idx: int, d_poly_xyz: int, d_poly_trac: int, d_trac: int,
+                                    d_fric: int, d_summary: int, d_fric_summary: int, d_stiff: int, d_counts: int, d_totals: int,
+                                    stream: int = 0):
+        """pfc_contact_surface_fric_device: raw device addresses (d_s, d_stiff, d_counts may be 0); asynchronous; follow with
+        check(), as after contact_surface_device."""
+        self._check(_lib.lib().pfc_contact_surface_fric_device(self._h, int(n_items), d_ins_ids or None, d_pose, d_twist, d_s or None,
+                                                               int(cap_poly), int(cap_trac), d_poly_off, d_poly_idx or None,
+                                                               d_poly_xyz or None, d_poly_trac, d_trac or None, d_fric or None,
+                                                               d_summary or None, d_fric_summary or None, d_stiff or None,
+                                                               d_counts or None, d_totals, stream or None))
 
     def check(self) -> int:
         """pfc_check: synchronise; returns the status (PFC_ERR_OVERFLOW means: re-issue, buffers were grown)."""
