@@ -246,6 +246,42 @@ int pfc_scatter_generalized_device(pfc_handle h, int n_items, const double *d_wr
                                    int accumulate, void *stream);
 
 /*
+ * addGeneralizedForcesThirdLaw! on Dual numbers (src/contact_algorithms_non_friction.jl:267-286 as the reference runs it in
+ * each Jacobian chunk of the Radau iteration matrix, src/radau/radau_functions.jl:2-14): the wrench, x_rw_r2 and the geometric
+ * Jacobians (refreshJacobians!, :86-92) carry partials, and f_generalized gets values and partials.  Arguments as
+ * pfc_scatter_generalized, plus, for n_dir (1..16) seed directions:
+ *   d_wrench  n_items x n_dir x 6          partials of the wrenches, as pfc_eval_dual[_device][_more] writes them
+ *   d_x_w_r2  n_items x n_dir x 12         partials of x_rw_r2, or NULL (constant: the same bytes as an array of zeros)
+ *   d_jac     n_body x n_dir x nv x 6      partials of the Jacobians, or NULL (constant, likewise)
+ *   f_out     n_scene x nv                 OUT values (overwritten), or NULL
+ *   d_f_out   n_scene x n_dir x nv         OUT partials (overwritten): one f-vector per direction
+ * Order: every output entry (scene, direction, coordinate) is summed over the scene's items in ascending item order,
+ * +tau(body_2) then -tau(body_1), as the reference loops over its instructions; every product of a value and a partial follows
+ * ForwardDiff (d(a b) = da b + a db).  No atomics: f_out equals pfo_scatter_generalized's result bit for bit (and
+ * pfc_scatter_generalized's up to summation order), and both outputs are the same bytes for the same inputs on every call,
+ * handle, stream and entry point.  Scene ids need not be contiguous.  Limits: n_scene * n_items < 2^31 (PFC_ERR_BAD_ARG).
+ * Host buffers, synchronous; body and scene ids are range-checked.
+ */
+int pfc_scatter_generalized_dual(pfc_handle h, int n_items, int n_dir, const double *wrench, const double *d_wrench,
+                                 const double *x_w_r2, const double *d_x_w_r2, const int *body_1, const int *body_2,
+                                 const int *scene, int n_scene, int n_body, int nv, const double *jac, const double *d_jac,
+                                 double *f_out, double *d_f_out);
+
+/*
+ * pfc_scatter_generalized_dual with every buffer in device memory, enqueued on `stream` without a host synchronisation: the
+ * Dual wrenches pfc_eval_dual_device / pfc_eval_dual_device_more left in HBM are projected where they are, chunk after chunk on
+ * one stream.  accumulate = 0: d_f and d_df are overwritten; 1: the contact terms are added onto what they hold (that content is
+ * the first term of every sum).  d_f may be NULL (partials only); d_scene may be NULL (one mechanism).  Body ids are not
+ * range-checked (device data, as in pfc_scatter_generalized_device); an item whose scene id lies outside [0, n_scene) is left
+ * out.  Multi-device handles: the first device.  The call keeps work buffers in the handle: calls on different streams must be
+ * ordered by the caller.
+ */
+int pfc_scatter_generalized_dual_device(pfc_handle h, int n_items, int n_dir, const double *d_wrench_val, const double *d_dwrench,
+                                        const double *d_x_w_r2, const double *d_dx_w_r2, const int *d_body_1, const int *d_body_2,
+                                        const int *d_scene, int n_scene, int nv, const double *d_jac, const double *d_djac,
+                                        double *d_f, double *d_df, int accumulate, void *stream);
+
+/*
  * The contact surface of n_items items: per item what the reference's TractionCache holds after forceAllElasticIntersections!
  * (src/structs.jl; filled by src/contact_algorithms_non_friction.jl:217-265), the clipped polygons it was integrated over, and
  * normal_wrench / normal_wrench_cop (src/contact_algorithms_normal.jl:2-34) -- what test/test_normal.jl:31-41 and

@@ -16,6 +16,8 @@
 //                  pfc_sort.hip (a translation unit of its own: rocPRIM radix sort of the candidate list)
 //   pfc_surface.h  k_surf_count / k_surf_summary / k_surf_emit: the contact surface in canonical order (pfc_contact_surface)
 //   pfc_surface_fric.h  k_sfric_mom / k_sfric_eig / k_sfric_pass / k_sfric_final: its friction half (pfc_contact_surface_fric)
+//   pfc_scatter.h  k_scat_keys / k_scat_off / k_scat_world / k_scat_proj: the third-law scatter on Dual numbers in the reference's
+//                  item order (pfc_scatter_generalized_dual)
 //   pfc_multi.h    host code: multi-device handles (pfc_create_multi)
 // This file: mesh record preparation (k_prep_tri, k_prep_tet), per-item setup (k_setup_items), work-list management,
 // hipGraph capture / replay, the two-half evaluation and every extern "C" entry point.
@@ -183,6 +185,7 @@ __global__ void k_repose(int n_items, const double *__restrict__ pose, ItemRec *
 #include "pfc_fused.h"
 #include "pfc_surface.h"
 #include "pfc_surface_fric.h"
+#include "pfc_scatter.h"
 
 }  // namespace pfc
 
@@ -344,6 +347,9 @@ struct pfc_context {
     DevBuf<int> dual_sel, dual_flag;                        // pairs a chunk has work for; per-item marks (+ the list's counter)
     DevBuf<double> scat_d;                                  // pfc_scatter_generalized
     DevBuf<int> scat_i;
+    DevBuf<double> sdual_d, sdual_w;                        // pfc_scatter_generalized_dual: host-form staging; world wrenches
+    DevBuf<int> sdual_i;                                    // ids, CSR keys (+ the sort's second key array), offsets, count
+    DevBuf<char> sdual_tmp;                                 // its rocPRIM sort storage
     DevBuf<int> surv;                                       // candidate indices of contributing pairs
     DevBuf<int> rgn;                                        // region counters of the polygon / record lists
     DevBuf<int> poly_item, pcnt, poly_cand;                 // kept polygons (k_narrow -> k_integ, k_fric): keys, count per chunk, candidate index (Dual list)
@@ -1397,6 +1403,7 @@ void pfc_destroy(pfc_handle h) {
     if (h->pin_dout) (void)hipHostFree(h->pin_dout);
     h->tail.release();
     h->rgn.release(); h->poly_item.release(); h->pcnt.release(); h->poly_cand.release(); h->poly.release(); h->surv.release(); h->scat_d.release(); h->scat_i.release();
+    h->sdual_d.release(); h->sdual_w.release(); h->sdual_i.release(); h->sdual_tmp.release();
     h->dual_poly.release(); h->dual_pkey.release(); h->dual_sel.release(); h->dual_flag.release();
     h->dual_in.release(); h->dual_acc.release(); h->dual_res.release(); h->dual_out.release(); h->dual_zero.release();
     h->surf_cnt.release(); h->surf_off.release(); h->surf_out.release(); h->surf_part.release(); h->surf_seg.release();
@@ -3359,6 +3366,134 @@ int pfc_scatter_generalized_device(pfc_handle h, int n_items, const double *d_wr
         HIP_TRY(h, hipGetLastError());
     }
     return PFC_OK;
+}
+
+// pfc_scatter_generalized_dual[_device] behind the scene CSR (keys / off, or NULL: one segment): the world wrenches and the ordered
+// projection (pfc_scatter.h), enqueued on st.
+static int scatter_dual_launch(pfc_handle h, int n_items, int n_dir, const double *wrench, const double *dwrench, const double *x_w_r2,
+                               const double *dx_w_r2, const int *body_1, const int *body_2, const int *keys, const int *off, int n_scene,
+                               int nv, const double *jac, const double *djac, double *f, double *df, int accumulate, hipStream_t st) {
+    const size_t n = (size_t)n_items, nc = 1 + (size_t)n_dir;
+    HIP_TRY(h, h->sdual_w.ensure(n * nc * 6 + 1));
+    if (n_items > 0) {
+        const long long lanes = (long long)n * nc;
+        const long long g = std::min<long long>((lanes + 255) / 256, 1 << 16);
+        hipLaunchKernelGGL(k_scat_world, dim3((unsigned)g), dim3(256), 0, st, n_items, n_dir, wrench, dwrench, x_w_r2, dx_w_r2,
+                           h->sdual_w.p);
+        HIP_TRY(h, hipGetLastError());
+    }
+    ScatDualArgs a;
+    a.n_items = n_items; a.n_dir = n_dir; a.nv = nv; a.n_scene = n_scene; a.n_jb = (nv + kScatJB - 1) / kScatJB;
+    a.accumulate = accumulate ? 1 : 0; a.W = h->sdual_w.p; a.jac = jac; a.djac = djac; a.body_1 = body_1; a.body_2 = body_2;
+    a.keys = keys; a.off = off; a.f = f; a.df = df;
+    const long long blocks = (long long)n_scene * (long long)nc * a.n_jb;
+    hipLaunchKernelGGL(k_scat_proj, dim3((unsigned)std::min<long long>(blocks, 1 << 16)), dim3(256), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+int pfc_scatter_generalized_dual(pfc_handle h, int n_items, int n_dir, const double *wrench, const double *d_wrench,
+                                 const double *x_w_r2, const double *d_x_w_r2, const int *body_1, const int *body_2,
+                                 const int *scene, int n_scene, int n_body, int nv, const double *jac, const double *d_jac,
+                                 double *f_out, double *d_f_out) {
+    if (h && h->multi) {      // as pfc_scatter_generalized: the first device does it
+        const int rc = pfc_scatter_generalized_dual(h->multi->shard[0], n_items, n_dir, wrench, d_wrench, x_w_r2, d_x_w_r2, body_1,
+                                                    body_2, scene, n_scene, n_body, nv, jac, d_jac, f_out, d_f_out);
+        if (rc != PFC_OK) h->err = h->multi->shard[0]->err;
+        return rc;
+    }
+    if (!h || n_items < 0 || n_dir < 1 || n_dir > kScatMaxDir || nv <= 0 || n_scene <= 0 || n_body < 0 || !d_f_out)
+        return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual: bad argument");
+    if ((long long)n_scene * n_items >= (1ll << 31))
+        return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual: n_scene * n_items must be below 2^31");
+    if (n_items > 0 && (!wrench || !d_wrench || !x_w_r2 || !body_1 || !body_2 || (n_body > 0 && !jac)))
+        return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual: null buffer");
+    for (int i = 0; i < n_items; ++i) {
+        if (body_1[i] >= n_body || body_2[i] >= n_body || (scene && (scene[i] < 0 || scene[i] >= n_scene)))
+            return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual: body / scene id out of range (item %d)", i);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)n_items, nd = (size_t)n_dir, nf = (size_t)n_scene * nv, nj = (size_t)n_body * nv * 6;
+    const size_t ndx = d_x_w_r2 ? n * nd * 12 : 0, ndj = d_jac ? nj * nd : 0;
+    // staging (grown on demand, reused): [f | df | wrench | dwrench | x_w_r2 | dx_w_r2 | jac | djac]; [body_1 | body_2 | keys | off]
+    HIP_TRY(h, h->sdual_d.ensure(nf * (1 + nd) + n * 6 * (1 + nd) + n * 12 + ndx + nj + ndj + 1));
+    double *df = h->sdual_d.p, *ddf = df + nf, *dw = ddf + nf * nd, *ddw = dw + n * 6, *dx = ddw + n * nd * 6, *ddx = dx + n * 12;
+    double *dj = ddx + ndx, *ddj = dj + nj;
+    const bool csr = scene && n_items > 0;
+    HIP_TRY(h, h->sdual_i.ensure(n * 3 + (size_t)n_scene + 2));
+    int *db = h->sdual_i.p, *dkeys = db + 2 * n, *doff = dkeys + n;
+    std::vector<int> keys, off;
+    if (csr) {      // the items by scene in ascending item order: a counting sort
+        off.assign((size_t)n_scene + 1, 0);
+        for (int i = 0; i < n_items; ++i) ++off[(size_t)scene[i] + 1];
+        for (int s = 0; s < n_scene; ++s) off[(size_t)s + 1] += off[(size_t)s];
+        std::vector<int> fill(off.begin(), off.end() - 1);
+        keys.resize(n);
+        for (int i = 0; i < n_items; ++i) keys[(size_t)fill[(size_t)scene[i]]++] = scene[i] * n_items + i;
+    }
+    hipStream_t st = h->stream;
+    if (n_items > 0) {
+        HIP_TRY(h, hipMemcpyAsync(dw, wrench, sizeof(double) * n * 6, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipMemcpyAsync(ddw, d_wrench, sizeof(double) * n * nd * 6, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipMemcpyAsync(dx, x_w_r2, sizeof(double) * n * 12, hipMemcpyHostToDevice, st));
+        if (ndx) HIP_TRY(h, hipMemcpyAsync(ddx, d_x_w_r2, sizeof(double) * ndx, hipMemcpyHostToDevice, st));
+        if (nj) HIP_TRY(h, hipMemcpyAsync(dj, jac, sizeof(double) * nj, hipMemcpyHostToDevice, st));
+        if (ndj) HIP_TRY(h, hipMemcpyAsync(ddj, d_jac, sizeof(double) * ndj, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipMemcpyAsync(db, body_1, sizeof(int) * n, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipMemcpyAsync(db + n, body_2, sizeof(int) * n, hipMemcpyHostToDevice, st));
+        if (csr) {
+            HIP_TRY(h, hipMemcpyAsync(dkeys, keys.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
+            HIP_TRY(h, hipMemcpyAsync(doff, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice, st));
+        }
+    }
+    const int rc = scatter_dual_launch(h, n_items, n_dir, dw, ddw, dx, ndx ? ddx : nullptr, db, db + n, csr ? dkeys : nullptr,
+                                       csr ? doff : nullptr, n_scene, nv, nj ? dj : nullptr, ndj ? ddj : nullptr, f_out ? df : nullptr,
+                                       ddf, 0, st);
+    if (rc != PFC_OK) return rc;
+    if (f_out) HIP_TRY(h, hipMemcpyAsync(f_out, df, sizeof(double) * nf, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(d_f_out, ddf, sizeof(double) * nf * nd, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return PFC_OK;
+}
+
+int pfc_scatter_generalized_dual_device(pfc_handle h, int n_items, int n_dir, const double *d_wrench_val, const double *d_dwrench,
+                                        const double *d_x_w_r2, const double *d_dx_w_r2, const int *d_body_1, const int *d_body_2,
+                                        const int *d_scene, int n_scene, int nv, const double *d_jac, const double *d_djac,
+                                        double *d_f, double *d_df, int accumulate, void *stream) {
+    if (h && h->multi) {      // the wrenches of a multi-device evaluation end up on the first device: so does this
+        const int rc = pfc_scatter_generalized_dual_device(h->multi->shard[0], n_items, n_dir, d_wrench_val, d_dwrench, d_x_w_r2,
+                                                           d_dx_w_r2, d_body_1, d_body_2, d_scene, n_scene, nv, d_jac, d_djac, d_f,
+                                                           d_df, accumulate, stream);
+        if (rc != PFC_OK) h->err = h->multi->shard[0]->err;
+        return rc;
+    }
+    if (!h || n_items < 0 || n_dir < 1 || n_dir > kScatMaxDir || nv <= 0 || n_scene <= 0 || !d_df)
+        return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual_device: bad argument");
+    if ((long long)n_scene * n_items >= (1ll << 31))
+        return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual_device: n_scene * n_items must be below 2^31");
+    if (n_items > 0 && (!d_wrench_val || !d_dwrench || !d_x_w_r2 || !d_body_1 || !d_body_2 || !d_jac))
+        return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual_device: null buffer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const bool csr = d_scene && n_items > 0;
+    int *keys = nullptr, *off = nullptr;
+    if (csr) {      // the items by scene in ascending item order: sorted keys scene * n_items + item, offsets per scene
+        const size_t n = (size_t)n_items;
+        size_t bytes = 0;
+        HIP_TRY(h, h->sdual_i.ensure(n * 3 + (size_t)n_scene + 2));
+        HIP_TRY(h, pfc_sort_temp_bytes(n, 32, &bytes));
+        HIP_TRY(h, h->sdual_tmp.ensure(bytes ? bytes : 1));
+        keys = h->sdual_i.p; off = keys + n;
+        int *count = off + n_scene + 1;
+        unsigned *kin = reinterpret_cast<unsigned *>(count + 1), *kout = kin + n;
+        hipLaunchKernelGGL(k_scat_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n_items, n_scene, d_scene, keys, count);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, pfc_sort_indices(keys, count, n, kin, kout, h->sdual_tmp.p, h->sdual_tmp.cap, st));
+        hipLaunchKernelGGL(k_scat_off, dim3((unsigned)(((size_t)n_scene + 256) / 256)), dim3(256), 0, st, n_items, n_scene, keys, off);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return scatter_dual_launch(h, n_items, n_dir, d_wrench_val, d_dwrench, d_x_w_r2, d_dx_w_r2, d_body_1, d_body_2, keys, off, n_scene,
+                               nv, d_jac, d_djac, d_f, d_df, accumulate, st);
 }
 
 int pfc_debug_stamps(pfc_handle h, long long *out16) {

@@ -551,6 +551,57 @@ class MechanismScenario:
                                                               d_scene or None, int(n_scene), int(nv), d_jac, d_f,
                                                               1 if accumulate else 0, stream or None))
 
+    def scatter_generalized_dual(self, wrench, d_wrench, x_w_r2, d_x_w_r2, body_1, body_2, jac, d_jac, scene=None,
+                                 n_scene: int = 1):
+        """addGeneralizedForcesThirdLaw! on Dual numbers (pfc_scatter_generalized_dual): arguments as scatter_generalized, plus
+        d_wrench (n, n_dir, 6), d_x_w_r2 (n, n_dir, 12) or None, d_jac (n_body, n_dir, nv, 6) or None (None: constant).
+        Sums run over each scene's items in item order, so the result is the same bytes on every call.
+        Returns (f (n_scene, nv), d_f (n_scene, n_dir, nv))."""
+        w_a, w_p = _d(wrench); x_a, x_p = _d(x_w_r2)
+        n = w_a.size // 6
+        dw_a, dw_p = _d(d_wrench)
+        if n == 0:
+            n_dir = int(np.shape(d_wrench)[1]) if np.ndim(d_wrench) == 3 else 0
+        elif dw_a.size % (6 * n) != 0:
+            raise ValueError("d_wrench must be (n, n_dir, 6)")
+        else:
+            n_dir = dw_a.size // (6 * n)
+        if w_a.size != 6 * n or x_a.size != 12 * n:
+            raise ValueError("wrench must be (n, 6) and x_w_r2 (n, 12)")
+        b1_a, b1_p = _i(body_1); b2_a, b2_p = _i(body_2)
+        if b1_a.size != n or b2_a.size != n:
+            raise ValueError("body_1 and body_2 must have one entry per item")
+        j_a, j_p = _d(jac)
+        if j_a.ndim != 3 or j_a.shape[2] != 6:
+            raise ValueError("jac must be (n_body, nv, 6)")
+        n_body, nv = j_a.shape[0], j_a.shape[1]
+        dx_p = dj_p = sc_p = None
+        if d_x_w_r2 is not None:
+            dx_a, dx_p = _d(d_x_w_r2)
+            if dx_a.size != 12 * n * n_dir:
+                raise ValueError("d_x_w_r2 must be (n, n_dir, 12)")
+        if d_jac is not None:
+            dj_a, dj_p = _d(d_jac)
+            if dj_a.size != n_body * n_dir * nv * 6:
+                raise ValueError("d_jac must be (n_body, n_dir, nv, 6)")
+        if scene is not None:
+            sc_a, sc_p = _i(scene)
+            if sc_a.size != n:
+                raise ValueError("scene must have one entry per item")
+        f = np.zeros((n_scene, nv)); d_f = np.zeros((n_scene, n_dir, nv))
+        self._check(_lib.lib().pfc_scatter_generalized_dual(self._h, n, n_dir, w_p, dw_p, x_p, dx_p, b1_p, b2_p, sc_p, n_scene, n_body,
+                                                            nv, j_p, dj_p, f.ctypes.data_as(_dp), d_f.ctypes.data_as(_dp)))
+        return f, d_f
+
+    def scatter_generalized_dual_device(self, n_items: int, n_dir: int, d_wrench: int, d_dwrench: int, d_x_w_r2: int,
+                                        d_dx_w_r2: int, d_body_1: int, d_body_2: int, d_scene: int, n_scene: int, nv: int, d_jac: int,
+                                        d_djac: int, d_f: int, d_df: int, accumulate: bool = False, stream: int = 0):
+        """pfc_scatter_generalized_dual_device: raw device addresses (0: NULL for d_dx_w_r2, d_scene, d_djac, d_f), asynchronous
+        on `stream`; f_generalized and its partials stay in HBM."""
+        self._check(_lib.lib().pfc_scatter_generalized_dual_device(
+            self._h, int(n_items), int(n_dir), d_wrench, d_dwrench, d_x_w_r2, d_dx_w_r2 or None, d_body_1, d_body_2, d_scene or None,
+            int(n_scene), int(nv), d_jac, d_djac or None, d_f or None, d_df, 1 if accumulate else 0, stream or None))
+
     def eval_device(self, n_items: int, d_ins_ids: int, d_pose: int, d_twist: int, d_s: int, d_wrench: int,
                     d_sdot: int, d_counts: int, stream: int = 0):
         """pfc_eval_device: raw device addresses (e.g. torch.Tensor.data_ptr()); asynchronous."""
