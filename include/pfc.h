@@ -198,6 +198,47 @@ int pfc_eval_dual_device_more(pfc_handle h, int n_dir, const double *d_dpose, co
                               double *d_dwrench, double *d_dsdot, void *stream);
 
 /*
+ * The contact Jacobian of every item AT THE POINT OF THE LAST CHECKED pfc_eval_dual_device[_bp] EVALUATION of this handle.  Every
+ * branch of the Dual passes compares values (the clip, max(0, 1 + chi edot), the friction ramps, the eigenvalue clamp) and the
+ * Frechet derivative of K̄^{-1/2} is linear in dK, so at one value point an item's partials are one matrix times its seeds:
+ *   [d_wrench; d_sdot] (12 x n_dir) = L (12 x 36) . [d_pose 24; d_twist 6; d_s 6] (36 x n_dir).
+ *   d_L  n_items x 12 x 36   OUT row-major per item: row r = output r (wrench [ang; lin] 0..5, then sdot 6..11), column k = input k
+ *                            (the 24 pose numbers in pfc_eval's packing 0..23, twist 24..29, s 30..35).  The pose columns are the
+ *                            contact stiffness, the twist columns the damping.
+ * Three Dual passes (16 + 16 + 4 unit-seed directions) run on the kept value pass, as pfc_eval_dual_device_more runs its one: the
+ * columns are bit for bit the partials _more returns for those unit seeds.  Precondition, state and check as _more: PFC_ERR_STATE
+ * without a checked Dual evaluation to extend; follow with pfc_check(); the handle is left as _more leaves it (further _more calls and
+ * pfc_local_jacobian_device at the same point still work).  Multi-device handles: each device builds the rows of its items, d_L lives
+ * on the first device.
+ * Flat patches: on a default handle each Dual pass forms K from its own atomically summed Dual sums; where decompose_K! clamps an
+ * eigenvalue (src/contact_algorithms_friction.jl:92) two passes can take different clamp decisions and their partials then differ
+ * by O(1) -- L's columns come from three passes, a chunk of _more from one.  Under option fixed_order every pass takes the value
+ * pass's K and a fixed summation order: L equals _more's partials for the same unit seeds byte for byte.
+ */
+int pfc_local_jacobian_device(pfc_handle h, double *d_L, void *stream);
+/* The host-buffer, synchronous one-shot: the value pass of pfc_eval at (ins_ids, pose, twist, s) -- a Dual evaluation whose seeds are
+ * all zero -- then L (n_items x 12 x 36).  Arguments as pfc_eval, plus L; counts may be NULL.  Work-list overflows are handled
+ * internally.  The call counts as a Dual evaluation: pfc_eval_dual_device_more and pfc_local_jacobian_device may follow at its point. */
+int pfc_local_jacobian(pfc_handle h, int n_items, const int *ins_ids, const double *pose, const double *twist, const double *s,
+                       double *wrench, double *sdot, double *L, int *counts);
+
+/*
+ * Further seed chunks from L: d_wrench / d_sdot of every (item, direction) = L_item . [d_pose; d_twist; d_s], with exactly the
+ * layouts of pfc_eval_dual_device_more (n_dir 1..16; d_ds may be NULL = zeros), so the result goes straight into
+ * pfc_scatter_generalized_dual_device.  A key whose 36 seeds are all zero gets exact zeros without reading L (an item without a
+ * nonzero key reads no L at all); NaN seeds propagate.  L is caller data: the call reads and changes no evaluation state of the handle,
+ * so it stays valid after later evaluations and pfc_set_option -- the same flat-patch caveat as pfc_local_jacobian_device applies to
+ * the L it is given.  d_L must be 16-byte aligned.  Enqueued on `stream` (NULL = the handle's own) without a synchronisation and
+ * needs no pfc_check.  Multi-device handles: the first device, over all items.  Each output is one FMA chain over the 36 columns in
+ * order: the same bytes on every call.
+ */
+int pfc_apply_local_jacobian_device(pfc_handle h, int n_items, int n_dir, const double *d_L, const double *d_dpose,
+                                    const double *d_dtwist, const double *d_ds, double *d_dwrench, double *d_dsdot, void *stream);
+/* The same with host buffers, synchronous. */
+int pfc_apply_local_jacobian(pfc_handle h, int n_items, int n_dir, const double *L, const double *d_pose, const double *d_twist,
+                             const double *d_s, double *d_wrench, double *d_sdot);
+
+/*
  * eMesh_to_tree (src/geometry/blob_types.jl:136-173) on the host: builds the flattened binary OBB tree that
  * pfc_add_mesh takes.  method PFC_TREE_BLOB follows the reference (bottom-up merging of face/edge-adjacent blobs by
  * marginal cost :74-134, median-split top-down over the remaining blobs src/geometry/top_down.jl:10-32, tight leaf

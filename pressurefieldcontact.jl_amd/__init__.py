@@ -8,4 +8,5 @@ _lib       ctypes binding / build of csrc/libpfc_hip.so
 """
 from . import geometry, _lib, scenario, configs, parallel  # noqa: F401
 from .scenario import (MechanismScenario, ContactProperties, Regularized, Bristle, ContactInstructions,  # noqa: F401
-                       MeshCache, ContactSurface, FrictionSurface, relative_pose, relative_twist)
+                       MeshCache, ContactSurface, FrictionSurface, relative_pose, relative_twist,
+                       local_jacobian_tangent)

@@ -18,6 +18,8 @@
 //   pfc_surface_fric.h  k_sfric_mom / k_sfric_eig / k_sfric_pass / k_sfric_final: its friction half (pfc_contact_surface_fric)
 //   pfc_scatter.h  k_scat_keys / k_scat_off / k_scat_world / k_scat_proj: the third-law scatter on Dual numbers in the reference's
 //                  item order (pfc_scatter_generalized_dual)
+//   pfc_ljac.h     k_ljac_seeds / k_ljac_pack / k_ljac_apply: per-item contact Jacobians from unit-seed Dual passes and their
+//                  product with further seed chunks (pfc_local_jacobian, pfc_apply_local_jacobian)
 //   pfc_multi.h    host code: multi-device handles (pfc_create_multi)
 // This file: mesh record preparation (k_prep_tri, k_prep_tet), per-item setup (k_setup_items), work-list management,
 // hipGraph capture / replay, the two-half evaluation and every extern "C" entry point.
@@ -186,6 +188,7 @@ __global__ void k_repose(int n_items, const double *__restrict__ pose, ItemRec *
 #include "pfc_surface.h"
 #include "pfc_surface_fric.h"
 #include "pfc_scatter.h"
+#include "pfc_ljac.h"
 
 }  // namespace pfc
 
@@ -438,6 +441,11 @@ struct pfc_context {
     DevBuf<long long> surf_cnt, surf_off, surf_out;   // per list slot {polygon, points} and their exclusive scan; packed status block
     DevBuf<double> surf_part;                         // per candidate partial sums
     DevBuf<int> surf_seg, surf_canon_off, surf_canon_fill, surf_canon_item;
+    // per-item contact Jacobians (pfc_ljac.h)
+    DevBuf<double> ljac_seed;          // unit seeds of the three passes for ljac_seed.cap / kLjacSeedDoubles items (k_ljac_seeds)
+    DevBuf<double> ljac_out;           // the passes' partials, n_items x 432
+    DevBuf<double> ljac_io;            // staging of the host-buffer forms
+    DevBuf<int> ljac_ids;
     DevBuf<unsigned long long> surf_keys[2];
     DevBuf<char> surf_tmp;                            // rocPRIM scan / sort
     long long *h_surf = nullptr;                      // pinned mirror of surf_out
@@ -1411,6 +1419,7 @@ void pfc_destroy(pfc_handle h) {
     h->surf_keys[0].release(); h->surf_keys[1].release(); h->surf_tmp.release();
     h->surf_hl.release(); h->surf_hi.release(); h->surf_hd.release(); h->surf_in.release();
     h->sfric_mom.release(); h->sfric_sum.release(); h->sfric_res.release(); h->sfric_hd.release();
+    h->ljac_seed.release(); h->ljac_out.release(); h->ljac_io.release(); h->ljac_ids.release();
     if (h->h_surf) (void)hipHostFree(h->h_surf);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -2904,6 +2913,138 @@ int pfc_eval_dual_device_more(pfc_handle h, int n_dir, const double *d_dpose, co
     if (rc != PFC_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->h_more, more_status, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     h->pending_more = true; h->last_stream = st; h->last_dual_reused = true;
+    return PFC_OK;
+}
+
+// The contact Jacobian L of every item at the point of the last checked Dual evaluation: the Dual passes of
+// pfc_eval_dual_device_more, run three times on the kept value pass with unit seeds (16 + 16 + 4 directions), then packed.
+int pfc_local_jacobian_device(pfc_handle h, double *d_L, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi) return multi_local_jacobian_device(h, d_L, stream);
+    if (!h->dual_reuse_ok)
+        return fail(h, PFC_ERR_STATE, "pfc_local_jacobian_device: no checked pfc_eval_dual_device evaluation on this handle");
+    if (!d_L) return fail(h, PFC_ERR_BAD_ARG, "pfc_local_jacobian_device: null buffer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const int n_items = h->dual_reuse_n;
+    const size_t n = (size_t)n_items;
+    if (h->ljac_seed.cap < n * kLjacSeedDoubles) {      // the constant seeds: written once per capacity (a power of two of items)
+        size_t cap = 64;
+        while (cap < n) cap *= 2;
+        HIP_TRY(h, h->ljac_seed.ensure(cap * kLjacSeedDoubles));
+        hipLaunchKernelGGL(k_ljac_seeds, dim3((unsigned)((cap * kLjacCols + 255) / 256)), dim3(256), 0, st, (int)cap, h->ljac_seed.p);
+        HIP_TRY(h, hipGetLastError());
+    }
+    const size_t cap = h->ljac_seed.cap / kLjacSeedDoubles;
+    HIP_TRY(h, h->ljac_out.ensure(n * kLjacSize));
+    // as pfc_eval_dual_device_more: the exact pair count, and a status word of the passes' own that pfc_check reads back
+    const size_t bound = (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) + 64;
+    if (!h->h_more) HIP_TRY(h, hipHostMalloc((void **)&h->h_more, sizeof(unsigned) * 4));
+    unsigned *more_status = h->status.p + 1;
+    HIP_TRY(h, hipMemsetAsync(more_status, 0, sizeof(unsigned), st));
+    for (int p = 0; p < kLjacPasses; ++p) {
+        const int nd = ljac_pass_dirs(p);
+        const double *dp = h->ljac_seed.p + cap * 576 * p, *dt = dp + cap * nd * 24, *dsd = dt + cap * nd * 6;
+        double *dw = h->ljac_out.p + n * 192 * p, *dsdot = dw + n * nd * 6;
+        const int rc = launch_dual(h, n_items, nd, h->tail.p, dp, dt, dsd, dw, dsdot, bound, st, nullptr, false,
+                                   h->dual_reuse_emit ? h->emit_ctr.p : nullptr, more_status);
+        if (rc != PFC_OK) return rc;
+    }
+    hipLaunchKernelGGL(k_ljac_pack, dim3((unsigned)((n * kLjacSize + 255) / 256)), dim3(256), 0, st, n_items, h->ljac_out.p, d_L);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(h->h_more, more_status, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    h->pending_more = true; h->last_stream = st; h->last_dual_reused = true;
+    return PFC_OK;
+}
+
+// Value pass (a Dual evaluation whose keys all have zero seeds: they cost nothing) and L, through the device entry points on staging
+// buffers of the first device; re-issued on PFC_ERR_OVERFLOW as pfc_eval_dual does.
+int pfc_local_jacobian(pfc_handle h, int n_items, const int *ins_ids, const double *pose, const double *twist, const double *s,
+                       double *wrench, double *sdot, double *L, int *counts) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (n_items < 0) return fail(h, PFC_ERR_BAD_ARG, "pfc_local_jacobian: negative n_items");
+    if (n_items == 0) return PFC_OK;
+    if (!pose || !twist || !wrench || !sdot || !L) return fail(h, PFC_ERR_BAD_ARG, "pfc_local_jacobian: null buffer");
+    pfc_context *c = h->multi ? h->multi->shard[0] : h;
+    HIP_TRY(h, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const size_t n = (size_t)n_items;
+    // [pose 24 | twist 6 | s 6 | zero seeds 36 | wrench 6 | sdot 6 | d_wrench 6 | d_sdot 6 | L 432] x n; [ids | counts 4] x n
+    HIP_TRY(h, c->ljac_io.ensure(n * 528));
+    HIP_TRY(h, c->ljac_ids.ensure(n * 5));
+    double *dpose = c->ljac_io.p, *dtw = dpose + n * 24, *ds = dtw + n * 6, *dz = ds + n * 6, *dwr = dz + n * 36, *dsd = dwr + n * 6;
+    double *ddw = dsd + n * 6, *ddsd = ddw + n * 6, *dL = ddsd + n * 6;
+    int *dids = c->ljac_ids.p, *dcnt = dids + n;
+    HIP_TRY(h, hipMemcpyAsync(dpose, pose, sizeof(double) * n * 24, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(dtw, twist, sizeof(double) * n * 6, hipMemcpyHostToDevice, st));
+    if (s) HIP_TRY(h, hipMemcpyAsync(ds, s, sizeof(double) * n * 6, hipMemcpyHostToDevice, st));
+    if (ins_ids) HIP_TRY(h, hipMemcpyAsync(dids, ins_ids, sizeof(int) * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemsetAsync(dz, 0, sizeof(double) * n * 36, st));
+    int rc = PFC_OK;
+    for (int attempt = 0; attempt < 40; ++attempt) {
+        rc = pfc_eval_dual_device(h, n_items, 1, ins_ids ? dids : nullptr, dpose, dtw, s ? ds : nullptr, dz, dz + n * 24, dz + n * 30,
+                                  dwr, dsd, ddw, ddsd, dcnt, st);
+        if (rc != PFC_OK) return rc;
+        rc = pfc_check(h);
+        if (rc != PFC_ERR_OVERFLOW) break;
+    }
+    if (rc != PFC_OK) return rc;
+    rc = pfc_local_jacobian_device(h, dL, st);
+    if (rc != PFC_OK) return rc;
+    rc = pfc_check(h);
+    if (rc != PFC_OK) return rc;
+    HIP_TRY(h, hipSetDevice(c->device));
+    HIP_TRY(h, hipMemcpyAsync(wrench, dwr, sizeof(double) * n * 6, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(sdot, dsd, sizeof(double) * n * 6, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(L, dL, sizeof(double) * n * kLjacSize, hipMemcpyDeviceToHost, st));
+    if (counts) HIP_TRY(h, hipMemcpyAsync(counts, dcnt, sizeof(int) * n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return PFC_OK;
+}
+
+// [d_wrench; d_sdot] = L . seeds for every (item, direction): no handle state is read or changed, only the device and its stream.
+int pfc_apply_local_jacobian_device(pfc_handle h, int n_items, int n_dir, const double *d_L, const double *d_dpose, const double *d_dtwist,
+                                    const double *d_ds, double *d_dwrench, double *d_dsdot, void *stream) {
+    if (h && h->multi) {      // L and the seeds of a multi-device evaluation are on the first device: so is this
+        const int rc = pfc_apply_local_jacobian_device(h->multi->shard[0], n_items, n_dir, d_L, d_dpose, d_dtwist, d_ds, d_dwrench,
+                                                       d_dsdot, stream);
+        if (rc != PFC_OK) h->err = h->multi->shard[0]->err;
+        return rc;
+    }
+    if (!h || n_items < 0 || n_dir < 1 || n_dir > 16)
+        return fail(h, PFC_ERR_BAD_ARG, "pfc_apply_local_jacobian_device: n_items >= 0 and n_dir in 1..16");
+    if (n_items == 0) return PFC_OK;
+    if (!d_L || !d_dpose || !d_dtwist || !d_dwrench || !d_dsdot)
+        return fail(h, PFC_ERR_BAD_ARG, "pfc_apply_local_jacobian_device: null buffer");
+    if (reinterpret_cast<uintptr_t>(d_L) % 16 != 0) return fail(h, PFC_ERR_BAD_ARG, "pfc_apply_local_jacobian_device: d_L must be 16-byte aligned");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipLaunchKernelGGL(k_ljac_apply, dim3((unsigned)n_items), dim3(64), 0, st, n_dir, d_L, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+int pfc_apply_local_jacobian(pfc_handle h, int n_items, int n_dir, const double *L, const double *d_pose, const double *d_twist,
+                             const double *d_s, double *d_wrench, double *d_sdot) {
+    pfc_context *c = h && h->multi ? h->multi->shard[0] : h;
+    if (!h || n_items < 0 || n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "pfc_apply_local_jacobian: n_items >= 0 and n_dir in 1..16");
+    if (n_items == 0) return PFC_OK;
+    if (!L || !d_pose || !d_twist || !d_wrench || !d_sdot) return fail(h, PFC_ERR_BAD_ARG, "pfc_apply_local_jacobian: null buffer");
+    HIP_TRY(h, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const size_t n = (size_t)n_items, nk = n * n_dir;
+    // [L 432 | seeds 36 n_dir | outputs 12 n_dir] x n
+    HIP_TRY(h, c->ljac_io.ensure(n * kLjacSize + nk * 48));
+    double *dL = c->ljac_io.p, *dp = dL + n * kLjacSize, *dt = dp + nk * 24, *ds = dt + nk * 6, *dw = ds + nk * 6, *dsd = dw + nk * 6;
+    HIP_TRY(h, hipMemcpyAsync(dL, L, sizeof(double) * n * kLjacSize, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(dp, d_pose, sizeof(double) * nk * 24, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(dt, d_twist, sizeof(double) * nk * 6, hipMemcpyHostToDevice, st));
+    if (d_s) HIP_TRY(h, hipMemcpyAsync(ds, d_s, sizeof(double) * nk * 6, hipMemcpyHostToDevice, st));
+    const int rc = pfc_apply_local_jacobian_device(c, n_items, n_dir, dL, dp, dt, d_s ? ds : nullptr, dw, dsd, st);
+    if (rc != PFC_OK) { if (c != h) h->err = c->err; return rc; }
+    HIP_TRY(h, hipMemcpyAsync(d_wrench, dw, sizeof(double) * nk * 6, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(d_sdot, dsd, sizeof(double) * nk * 6, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
     return PFC_OK;
 }
 

@@ -444,6 +444,62 @@ int multi_eval_dual_device_more(pfc_context *h, int n_dir, const double *d_dpose
     return PFC_OK;
 }
 
+// pfc_local_jacobian_device over the shards: each builds the rows of L of its range on the value pass it keeps; shards 1.. write
+// theirs into staging on their device and copy them into d_L on the first.  One exit for errors: once shards have work enqueued
+// (their copies write into the caller's d_L, their staging may be reallocated by the next call), every stream that may hold some
+// is synchronised before the error is returned.
+int multi_local_jacobian_device(pfc_context *h, double *d_L, void *stream) {
+    pfc_multi *M = h->multi;
+    if (!M->dev_reuse_ok)
+        return fail(h, PFC_ERR_STATE, "pfc_local_jacobian_device: no checked pfc_eval_dual_device evaluation on this handle");
+    if (!d_L) return fail(h, PFC_ERR_BAD_ARG, "pfc_local_jacobian_device: null buffer");
+    const int dev0 = M->dev[0];
+    HIP_TRY(h, hipSetDevice(dev0));
+    MultiDeviceGuard back_to_first(dev0);
+    hipStream_t st0 = stream ? (hipStream_t)stream : M->shard[0]->stream;
+    if (M->n_used > 1) HIP_TRY(h, hipEventRecord(M->ev_fork, st0));
+    int rc = PFC_OK, enq = 1;      // shards [1, enq) may have work enqueued
+    hipError_t e = hipSuccess;
+    for (int k = 1; k < M->n_used; ++k) {
+        const size_t b0 = (size_t)M->bound[k];
+        const int nk = M->bound[k + 1] - (int)b0;
+        if (nk <= 0) continue;
+        pfc_context *c = M->shard[k];
+        pfc_multi::Stage &S = M->stage[k];
+        const int dk = M->dev[k];
+        hipStream_t sk = c->stream;
+        if ((e = hipSetDevice(dk)) != hipSuccess || (e = S.dout.ensure((size_t)nk * kLjacSize)) != hipSuccess ||
+            (e = hipStreamWaitEvent(sk, M->ev_fork, 0)) != hipSuccess)
+            break;
+        enq = k + 1;
+        rc = pfc_local_jacobian_device(c, S.dout.p, sk);
+        if (rc != PFC_OK) { h->err = c->err; break; }
+        if ((e = multi_copy(d_L + kLjacSize * b0, dev0, S.dout.p, dk, sizeof(double) * nk * kLjacSize, sk)) != hipSuccess ||
+            (e = hipEventRecord(S.done, sk)) != hipSuccess)
+            break;
+    }
+    if (rc == PFC_OK && e == hipSuccess && (e = hipSetDevice(dev0)) == hipSuccess) {
+        rc = pfc_local_jacobian_device(M->shard[0], d_L, st0);
+        if (rc != PFC_OK) h->err = M->shard[0]->err;
+        for (int k = 1; k < M->n_used && rc == PFC_OK && e == hipSuccess; ++k)
+            if (M->bound[k + 1] > M->bound[k]) e = hipStreamWaitEvent(st0, M->stage[k].done, 0);
+    }
+    if (rc == PFC_OK && e != hipSuccess) rc = fail(h, PFC_ERR_HIP, "pfc_local_jacobian_device: %s", hipGetErrorString(e));
+    if (rc != PFC_OK) {
+        for (int k = 1; k < enq; ++k) {
+            (void)hipSetDevice(M->dev[k]);
+            (void)hipStreamSynchronize(M->shard[k]->stream);
+            M->shard[k]->pending_more = false;
+        }
+        (void)hipSetDevice(dev0);
+        (void)hipStreamSynchronize(st0);
+        M->shard[0]->pending_more = false;
+        return rc;
+    }
+    M->dev_pending = true; M->dev_stream = st0; M->dev_reuse_ndir = -1;      // pfc_check as after pfc_eval_dual_device_more
+    return PFC_OK;
+}
+
 int multi_check(pfc_context *h) {
     pfc_multi *M = h->multi;
     if (!M->dev_pending) return PFC_OK;

@@ -11,6 +11,8 @@ the trailing ``!``), restricted to what the hot path needs:
   force_all_elastic_intersections(...)     src/contact_algorithms_non_friction.jl:60-84 -> pfc_eval
   contact_surface(pose, twist, ins_ids=)   TractionCache + normal_wrench_cop per item     -> pfc_contact_surface
   contact_surface_fric(pose, twist, s=, ins_ids=)  ... + per-point friction, ṡ, K       -> pfc_contact_surface_fric
+  local_jacobian(pose, twist, s=, ins_ids=)        per-item contact Jacobian L (12 x 36)  -> pfc_local_jacobian
+  apply_local_jacobian(L, d_pose, d_twist, d_s=)   partials of further seed chunks from L -> pfc_apply_local_jacobian
 
 The rigid-body side of calcXd! (RigidBodyDynamics: poses, twists, Jacobians, mass matrix, third-law scatter)
 stays with the host integrator; this class takes the per-instruction relative pose / twist / bristle state that
@@ -623,6 +625,75 @@ class MechanismScenario:
         self._check(_lib.lib().pfc_eval_dual_device_more(self._h, int(n_dir), d_dpose, d_dtwist, d_ds or None, d_dwrench,
                                                          d_dsdot, stream or None))
 
+    def local_jacobian(self, pose, twist, s=None, ins_ids: Optional[Sequence[int]] = None):
+        """The contact Jacobian of every item at (pose, twist, s) (pfc_local_jacobian): [d_wrench; d_sdot] = L . [d_pose; d_twist; d_s]
+        for any seeds at this point.  Returns (wrench (n,6), sdot (n,6), L (n,12,36), counts (n,4)); L's rows are the wrench
+        [ang; lin] then ṡ, its columns the 24 pose numbers (pose packing), twist 6 and s 6.  The handle may then extend this point
+        with eval_dual_device_more / local_jacobian_device."""
+        if not self._finalized:
+            raise RuntimeError("finalize the scenario first")
+        pose_a, pose_p = _da(pose)
+        n = pose_a.size // 24
+        if pose_a.size != 24 * n:
+            raise ValueError("pose must have 24 entries per item")
+        tw_a, tw_p = _da(twist)
+        if tw_a.size != 6 * n:
+            raise ValueError("twist must have 6 entries per item")
+        s_p = id_p = None
+        if s is not None:
+            s_a, s_p = _d(s)
+            if s_a.size != 6 * n:
+                raise ValueError("s must have 6 entries per item")
+        if ins_ids is not None:
+            id_a, id_p = _i(ins_ids)
+            if id_a.size != n:
+                raise ValueError("ins_ids must have one entry per item")
+        wrench = np.zeros((n, 6)); sdot = np.zeros((n, 6)); L = np.zeros((n, 12, 36)); counts = np.zeros((n, 4), dtype=np.int32)
+        self._check(_lib.lib().pfc_local_jacobian(self._h, n, id_p, pose_a.ctypes.data_as(_dp), tw_a.ctypes.data_as(_dp), s_p,
+                                                  wrench.ctypes.data_as(_dp), sdot.ctypes.data_as(_dp), L.ctypes.data_as(_dp),
+                                                  counts.ctypes.data_as(_ip)))
+        return wrench, sdot, L, counts
+
+    def apply_local_jacobian(self, L, d_pose, d_twist, d_s=None):
+        """Partials of a seed chunk from the contact Jacobians L (n,12,36) (pfc_apply_local_jacobian): d_pose (n,n_dir,24),
+        d_twist (n,n_dir,6), d_s (n,n_dir,6) or None.  Returns (d_wrench (n,n_dir,6), d_sdot (n,n_dir,6)), what
+        force_all_elastic_intersections_dual returns for these seeds at L's point.  Keys with all-zero seeds get exact zeros."""
+        L_a, L_p = _d(L)
+        n = L_a.size // 432
+        if L_a.size != 432 * n:
+            raise ValueError("L must be (n, 12, 36)")
+        dp_a, dp_p = _d(d_pose)
+        if n == 0:
+            n_dir = int(np.shape(d_pose)[1]) if np.ndim(d_pose) == 3 else 1
+        elif dp_a.size % (24 * n) != 0:
+            raise ValueError("d_pose must be (n, n_dir, 24)")
+        else:
+            n_dir = dp_a.size // (24 * n)
+        dt_a, dt_p = _d(d_twist)
+        if dt_a.size != 6 * n * n_dir:
+            raise ValueError("d_twist must be (n, n_dir, 6)")
+        ds_p = None
+        if d_s is not None:
+            ds_a, ds_p = _d(d_s)
+            if ds_a.size != 6 * n * n_dir:
+                raise ValueError("d_s must be (n, n_dir, 6)")
+        dw = np.zeros((n, n_dir, 6)); dsd = np.zeros((n, n_dir, 6))
+        self._check(_lib.lib().pfc_apply_local_jacobian(self._h, n, n_dir, L_p, dp_p, dt_p, ds_p, dw.ctypes.data_as(_dp),
+                                                        dsd.ctypes.data_as(_dp)))
+        return dw, dsd
+
+    def local_jacobian_device(self, d_L: int, stream: int = 0):
+        """pfc_local_jacobian_device: L (n_items x 12 x 36 doubles at raw device address d_L) at the point of the previous
+        eval_dual_device evaluation; asynchronous.  Follow with check()."""
+        self._check(_lib.lib().pfc_local_jacobian_device(self._h, d_L, stream or None))
+
+    def apply_local_jacobian_device(self, n_items: int, n_dir: int, d_L: int, d_dpose: int, d_dtwist: int, d_ds: int, d_dwrench: int,
+                                    d_dsdot: int, stream: int = 0):
+        """pfc_apply_local_jacobian_device: raw device addresses (d_ds 0: zeros), the layouts of eval_dual_device_more; asynchronous on
+        `stream`, no check() needed."""
+        self._check(_lib.lib().pfc_apply_local_jacobian_device(self._h, int(n_items), int(n_dir), d_L, d_dpose, d_dtwist, d_ds or None,
+                                                               d_dwrench, d_dsdot, stream or None))
+
     def contact_surface(self, pose, twist, ins_ids: Optional[Sequence[int]] = None) -> ContactSurface:
         """The contact surface of every item (pfc_contact_surface): clipped polygons, traction points and normal wrench / cop in
         one canonical order (see ContactSurface).  pose (n,24), twist (n,6), ins_ids (n,) or None.  The buffers start at the
@@ -813,3 +884,34 @@ def relative_twist(R_w2, t_w2, twist_w1, twist_w2) -> np.ndarray:
     ang = R @ tw[:3]
     lin = R @ tw[3:] + np.cross(t, ang)
     return np.concatenate([ang, lin])
+
+
+def local_jacobian_tangent(L, pose) -> np.ndarray:
+    """The contact Jacobians L (n,12,36) of MechanismScenario.local_jacobian on the 18 tangent coordinates of the state:
+    (δθ 3, δt 3, twist 6, s 6).  The pose columns are contracted with the consistent seeds of the perturbation
+    x_r2_r1 = (exp(δθ) R0, t0 + δt), pose (n,24) giving (R0, t0) -- the convention of tests/test_oracle_dual.py's tangents():
+    δθ is a rotation of body 1 relative to body 2 expressed in frame r2 (left perturbation of R_r2_r1), δt the displacement of
+    frame r1's origin in frame r2.  Returns (n,12,18): columns 0..5 are the contact stiffness on (δθ, δt), 6..11 the damping,
+    12..17 the bristle-state columns."""
+    L = np.asarray(L, dtype=np.float64)
+    pose = np.asarray(pose, dtype=np.float64).reshape(-1, 24)
+    one = L.ndim == 2
+    L = L.reshape(-1, 12, 36)
+    if L.shape[0] != pose.shape[0]:
+        raise ValueError("L and pose must have the same number of items")
+    out = np.zeros((L.shape[0], 12, 18))
+    for k in range(L.shape[0]):
+        R0 = pose[k, :9].reshape(3, 3, order="F"); t0 = pose[k, 9:12]
+        T = np.zeros((24, 6))
+        for j in range(3):
+            e = np.eye(3)[j]
+            E = np.array([[0, -e[2], e[1]], [e[2], 0, -e[0]], [-e[1], e[0], 0]])
+            dR = E @ R0
+            T[:9, j] = dR.reshape(-1, order="F")
+            T[12:21, j] = dR.T.reshape(-1, order="F")
+            T[21:24, j] = R0.T @ np.cross(e, t0)
+            T[9:12, 3 + j] = e
+            T[21:24, 3 + j] = -R0.T @ e
+        out[k, :, :6] = L[k, :, :24] @ T
+        out[k, :, 6:] = L[k, :, 24:]
+    return out[0] if one else out
