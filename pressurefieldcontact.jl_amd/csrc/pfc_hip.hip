@@ -294,32 +294,35 @@ struct pfc_context {
     long long dual_hint = -1;                     // contributing pairs of the last Dual evaluation (-1: none yet)
     bool pending_dual = false;                    // pfc_eval_dual_device enqueued: pfc_check also checks the speculative polygon capacity
     bool pending_dual_hyb = false;                // ... through the small-scene kernel (value pass + hand-over) and the batched Dual passes
-    bool dual_reuse_emit = false;                 // the reusable value pass is a hand-over of the small-scene kernel (pair count: emit_ctr)
     int dual_dev_hyb_skip = 0;                    // evaluations for which pfc_eval_dual_device leaves that path alone after a miss
-    // Reuse of a value pass by further Dual evaluations at the same point (the chunks of one Jacobian,
-    // src/radau/radau_functions.jl:2-14): set by pfc_check after a Dual evaluation on the device path, cleared by every
-    // other evaluation and option change
-    bool dual_reuse_ok = false;
-    int dual_reuse_n = 0;                         // its item count
-    int pin_in_dual_n = 0;                        // pin_in holds the value inputs of a small-scene Dual evaluation of this many items (0: not)
-    bool pin_in_dual_ids = false;
-    bool small_reuse_ok = false;                  // the same for the one-graph small-scene path (eval_dual_small)
-    int small_reuse_n = 0;
-    bool small_reuse_ids = false;
-    bool hyb_reuse_ok = false;                    // the same for the small-scene hybrid path (fused value kernel + batched Dual passes)
-    int hyb_reuse_n = 0;
-    bool hyb_reuse_ids = false;
+    // The kept pass: the value pass the device lists hold, reused by further Dual evaluations at the same point (the chunks of
+    // one Jacobian, src/radau/radau_functions.jl:2-14).  Recorded by pfc_check after pfc_eval_dual_device (Batched: the batched
+    // value pass; HandOver: the small-scene kernel's hand-over, pair count in emit_ctr), by eval_dual_hybrid (Hybrid) and by
+    // eval_dual_small (OneGraph); ended by every value pass (new_value_pass) and by end_kept_pass.
+    struct KeptPass {
+        enum Kind { None, Batched, HandOver, Hybrid, OneGraph } kind = None;
+        int n = 0;                                // its item count
+        bool ids = false;                         // ... given by ins_ids
+    } kept;
+    bool device_kept() const { return kept.kind == KeptPass::Batched || kept.kind == KeptPass::HandOver; }   // pfc_eval_dual_device_more may follow
+    // What a pinned input block holds: the value inputs (pose | twist | s, n x 36 doubles; the ids ids_at doubles in) of n items
+    // (0: nothing to compare with), of the value pass with that value_serial
+    struct HostPoint {
+        int n = 0;
+        bool ids = false;
+        unsigned long long serial = 0;
+        size_t ids_at = 0;
+    };
+    HostPoint pin_in_pt;                          // pin_in: a small-scene Dual evaluation's (a repeat of its point goes to the hybrid path)
+    HostPoint pin_din_pt;                         // pin_din / pin_dout: the one-sync path's evaluation (inputs, seeds; outputs)
     bool pending_more = false;                    // pfc_eval_dual_device_more enqueued: pfc_check only synchronises
     bool last_dual_reused = false;                // the last Dual evaluation ran on a reused value pass (pfc_last_dual_reused)
     int opt_dual_reuse = 1;
-    bool pin_din_valid = false;                   // pin_din / pin_dout still hold the value inputs / outputs of that evaluation
-    unsigned long long value_serial = 0;          // bumped by every value pass that overwrites the device lists (record_eval, enqueue_eval, enqueue_fused)
-    unsigned long long pin_din_serial = 0;        // value_serial of the evaluation pin_din / pin_dout belong to: the host cache is only valid for THAT value pass
-    bool pin_din_ids = false;                     // ... which had ins_ids
-    size_t pin_din_nk36 = 0;                      // doubles of seeds between the value block and the ids in pin_din
-    std::vector<int> dual_counts_cache;           // its per-item counters
+    unsigned long long value_serial = 0;          // bumped by every value pass that overwrites the device lists (new_value_pass)
+    std::vector<int> dual_counts_cache;           // the per-item counters of pin_din_pt's evaluation
     size_t pending_dpcap = 0;
     int pending_ndir = 0;
+    bool pending_ids = false;                     // the pending pfc_eval_dual_device evaluation has ins_ids (the kept pass pfc_check records)
     DevBuf<double> dual_zero;                     // zeros standing in for a null d_ds
     unsigned long long epoch = 0;        // bumped whenever a device work buffer is reallocated
     // captured launch sequence (hipGraph) of the last evaluation shape
@@ -507,6 +510,14 @@ int grid_for(size_t n, int block, int max_blocks) {
     if (b < 1) b = 1;
     if (b > (size_t)max_blocks) b = max_blocks;
     return (int)b;
+}
+
+// The kept pass (pfc_context::kept) ends: an option change, another broadphase pose, a device entry point, a reallocated pinned block.
+void end_kept_pass(pfc_context *h) { h->kept = {}; }
+// A value pass is about to overwrite the device lists.
+void new_value_pass(pfc_context *h) {
+    end_kept_pass(h);
+    ++h->value_serial;
 }
 
 // Kept-polygon slots: chunk ch of the candidate list owns slots [ch C, ch C + C) (pfc_np.h, np_chunk): the candidate
@@ -732,8 +743,8 @@ void launch_broadphase(pfc_context *h, int n_items, int L, int *ccount, int *fco
 // The launch sequence of one evaluation on stream st (eagerly, or while st is being captured into a graph).
 int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
                 const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, hipStream_t st, bool prof) {
-    h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false; h->pending_more = false; h->last_dual_reused = false;
-    ++h->value_serial;
+    new_value_pass(h);
+    h->pending_more = false; h->last_dual_reused = false;
     const int levels = eff_levels(h);
     int *ccount = h->ctr.p, *tcount = h->ctr.p + 1, *next_seed = h->ctr.p + 2;   // ctr[3]: total records, filled by k_final
     int *ucount = h->ctr.p + 4, *fcount = h->ctr.p + 6;
@@ -877,10 +888,8 @@ int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double 
 // costs.  Profiling (HIP events between stages) uses the eager path.
 int enqueue_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
                  const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, hipStream_t st) {
-    h->dual_reuse_ok = false; h->pending_more = false;     // a new value pass overwrites what a Dual evaluation could reuse
-    ++h->value_serial;
-    h->hyb_reuse_ok = false; h->small_reuse_ok = false;
-    h->last_dual_reused = false;
+    new_value_pass(h);
+    h->pending_more = false; h->last_dual_reused = false;
     HIP_TRY(h, ensure_work(h, n_items));
     const int levels = eff_levels(h);
     const bool prof = h->opt_profile != 0;
@@ -1091,8 +1100,8 @@ int fused_team(const pfc_context *h, int n_items) {
 
 int enqueue_fused(pfc_context *h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
                   const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, hipStream_t st) {
-    h->dual_reuse_ok = false; h->pending_more = false; h->last_dual_reused = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false;
-    ++h->value_serial;
+    new_value_pass(h);
+    h->pending_more = false; h->last_dual_reused = false;
     FuArgs a;
     a.n_items = n_items; a.n_ins = (int)h->ins.size(); a.ins_ids = d_ins_ids; a.pose = d_pose; a.twist = d_twist; a.s = d_s;
     a.ins = h->d_insfull; a.wrench = d_wrench; a.sdot = d_sdot; a.counts = d_counts;
@@ -1751,13 +1760,15 @@ int pfc_eval_device(pfc_handle h, int n_items, const int *d_ins_ids, const doubl
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     h->split_n0 = 0;
     h->pending_fused = false;
-    h->dual_reuse_ok = false; h->pending_more = false;
+    end_kept_pass(h);
+    h->pending_more = false;
     int team = fused_team(h, n_items);
     if (team > 1 && !team_acquire(h)) team = fused_ok(h, n_items) ? 1 : 0;     // another handle's teams are in flight on this device
     if (team) {
         h->fu_nw = team;
         const int rc_t = enqueue_fused(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, st);
         h->fu_nw = 1;
+        if (rc_t != PFC_OK) team_release(h);      // no fused evaluation pending: the slot is free again
         return rc_t;
     }
     if (h->fused_skip > 0 && n_items <= kFusedMaxItems) --h->fused_skip;
@@ -1818,9 +1829,9 @@ int surface_enqueue(pfc_context *h, int n_items, const int *d_ins_ids, const dou
                     long long cap_trac, long long *d_poly_off, int *d_poly_idx, double *d_poly_xyz, long long *d_poly_trac,
                     double *d_trac, double *d_summary, int *d_counts, long long *d_totals, hipStream_t st, const SurfFricOut *fo = nullptr) {
     // an evaluation for the call-order rules: the candidate list and the counters a Dual evaluation could reuse are overwritten
-    h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false; h->pending_more = false;
-    h->pin_in_dual_n = 0; h->pin_din_valid = false;
-    ++h->value_serial;
+    new_value_pass(h);
+    h->pending_more = false;
+    h->pin_in_pt = {}; h->pin_din_pt = {};
     h->pending = false; h->pending_dual = false; h->pending_dual_hyb = false; h->split_n0 = 0;
     if (h->pending_fused) { h->pending_fused = false; team_release(h); }
     int ba, bb;
@@ -1951,7 +1962,7 @@ int check_surface(pfc_context *h) {
 // device-pointer evaluation and Dual reuse end here, as with any other evaluation).
 pfc_context *surface_ctx(pfc_context *h) {
     if (!h->multi) return h;
-    h->multi->dev_pending = false; h->multi->dev_reuse_ok = false;
+    h->multi->dev_pending = false; h->multi->dev_kept = false;
     return h->multi->shard[0];
 }
 
@@ -1980,8 +1991,8 @@ int surface_host(pfc_context *hh, pfc_context *h, int n_items, const int *ins_id
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t n = (size_t)n_items;
     if (n_items == 0) {
-        h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false; h->pin_in_dual_n = 0; h->pin_din_valid = false;
-        ++h->value_serial;
+        new_value_pass(h);
+        h->pin_in_pt = {}; h->pin_din_pt = {};
         poly_off[0] = 0; poly_trac[0] = 0; totals[0] = totals[1] = 0;
         return PFC_OK;
     }
@@ -2104,8 +2115,8 @@ int pfc_contact_surface_device(pfc_handle hh, int n_items, const int *d_ins_ids,
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     if (n_items == 0) {
-        h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false; h->pin_in_dual_n = 0; h->pin_din_valid = false;
-        ++h->value_serial;
+        new_value_pass(h);
+        h->pin_in_pt = {}; h->pin_din_pt = {};
         HIP_TRY(h, hipMemsetAsync(d_poly_off, 0, sizeof(long long), st));
         HIP_TRY(h, hipMemsetAsync(d_poly_trac, 0, sizeof(long long), st));
         HIP_TRY(h, hipMemsetAsync(d_totals, 0, sizeof(long long) * 2, st));
@@ -2130,8 +2141,8 @@ int pfc_contact_surface_fric_device(pfc_handle hh, int n_items, const int *d_ins
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     if (n_items == 0) {
-        h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false; h->pin_in_dual_n = 0; h->pin_din_valid = false;
-        ++h->value_serial;
+        new_value_pass(h);
+        h->pin_in_pt = {}; h->pin_din_pt = {};
         HIP_TRY(h, hipMemsetAsync(d_poly_off, 0, sizeof(long long), st));
         HIP_TRY(h, hipMemsetAsync(d_poly_trac, 0, sizeof(long long), st));
         HIP_TRY(h, hipMemsetAsync(d_totals, 0, sizeof(long long) * 2, st));
@@ -2161,13 +2172,14 @@ int pfc_check(pfc_handle h) {
         h->pending_more = false;
         HIP_TRY(h, hipStreamSynchronize(h->last_stream));
         if (h->h_more && (h->h_more[0] & kStHole)) {
-            h->dual_reuse_ok = false;
+            end_kept_pass(h);
             return fail(h, PFC_ERR_STATE, "internal error: a Dual pass on a reused value pass read a work-list slot out of range");
         }
         return PFC_OK;
     }
+    // (a Dual evaluation pending here has no kept pass: its value pass ended it; recorded below once it is checked)
     if (h->pending_dual_hyb) {
-        h->pending_dual_hyb = false; h->pending_dual = false; h->dual_reuse_ok = false;
+        h->pending_dual_hyb = false; h->pending_dual = false;
         const int rch = check_eval(h);            // the fused kernel's per-item words (copied down, stream synchronised)
         if (rch != PFC_OK) { h->dual_dev_hyb_skip = 64; return rch; }
         if (h->stats[6] & kStCandOvf) {
@@ -2180,12 +2192,12 @@ int pfc_check(pfc_handle h) {
         const int cpw_h = 64 / h->pending_ndir;
         if ((h->any_bristle || h->opt_fixed_order) && (size_t)((pairs_h + cpw_h - 1) / cpw_h) * 64 + 64 > h->pending_dpcap)
             return fail(h, PFC_ERR_OVERFLOW, "Dual evaluation: %lld contributing pairs exceed the speculative polygon capacity: re-issue", pairs_h);
-        h->dual_reuse_ok = true; h->dual_reuse_n = h->last_n_items; h->dual_reuse_emit = true;
+        h->kept = {pfc_context::KeptPass::HandOver, h->last_n_items, h->pending_ids};
         return PFC_OK;
     }
     const bool dual = h->pending_dual;
     h->pending_dual = false;
-    h->dual_reuse_ok = false;
+    if (h->device_kept()) end_kept_pass(h);      // a check with no Dual evaluation pending ends a kept device pass
     const int rc = check_eval(h);
     if (rc != PFC_OK || !dual) return rc;
     // did the kept Dual polygons of pfc_eval_dual_device fit?  (contributing pairs: the counter next to the polygon total
@@ -2195,7 +2207,7 @@ int pfc_check(pfc_handle h) {
     const int cpw = 64 / h->pending_ndir;
     if ((h->any_bristle || h->opt_fixed_order) && (size_t)((pairs + cpw - 1) / cpw) * 64 + 64 > h->pending_dpcap)
         return fail(h, PFC_ERR_OVERFLOW, "Dual evaluation: %lld contributing pairs exceed the speculative polygon capacity: re-issue", pairs);
-    h->dual_reuse_ok = true; h->dual_reuse_n = h->last_n_items; h->dual_reuse_emit = false;
+    h->kept = {pfc_context::KeptPass::Batched, h->last_n_items, h->pending_ids};
     return PFC_OK;
 }
 
@@ -2249,6 +2261,58 @@ static hipError_t ensure_pinned(void **p, size_t *cap, size_t bytes) {
     return e;
 }
 
+// Value inputs of n items into a host-written block: pose | twist | s (zeros for a null s), the ids ids_at doubles in.
+static void pack_values(double *pi, size_t n, size_t ids_at, const int *ins_ids, const double *pose, const double *twist, const double *s) {
+    std::memcpy(pi, pose, sizeof(double) * n * 24);
+    std::memcpy(pi + n * 24, twist, sizeof(double) * n * 6);
+    if (s) std::memcpy(pi + n * 30, s, sizeof(double) * n * 6); else std::memset(pi + n * 30, 0, sizeof(double) * n * 6);
+    if (ins_ids) std::memcpy(pi + ids_at, ins_ids, sizeof(int) * n);
+}
+// Seeds of nk (item, direction) pairs: d_pose | d_twist, then -- with_s -- d_s (zeros for a null d_s).
+static void pack_seeds(double *pd, size_t nk, const double *d_pose, const double *d_twist, const double *d_s, bool with_s) {
+    std::memcpy(pd, d_pose, sizeof(double) * nk * 24);
+    std::memcpy(pd + nk * 24, d_twist, sizeof(double) * nk * 6);
+    if (!with_s) return;
+    if (d_s) std::memcpy(pd + nk * 30, d_s, sizeof(double) * nk * 6); else std::memset(pd + nk * 30, 0, sizeof(double) * nk * 6);
+}
+// The same-point test of the host Dual paths: are the value inputs of n items bit for bit those a pinned block laid out as by
+// pack_values holds?  zero_s: a null s must find zeros stored (without it a null s is not compared: no bristle item reads s).
+static bool same_point(const double *pi, size_t n, size_t ids_at, const int *ins_ids, const double *pose, const double *twist,
+                       const double *s, bool zero_s) {
+    if (std::memcmp(pi, pose, sizeof(double) * n * 24) != 0 || std::memcmp(pi + n * 24, twist, sizeof(double) * n * 6) != 0) return false;
+    if (s) {
+        if (std::memcmp(pi + n * 30, s, sizeof(double) * n * 6) != 0) return false;
+    } else if (zero_s) {
+        for (size_t k = 0; k < n * 6; ++k)
+            if (std::memcmp(pi + n * 30 + k, "\0\0\0\0\0\0\0\0", 8) != 0) return false;
+    }
+    return !ins_ids || std::memcmp(pi + ids_at, ins_ids, sizeof(int) * n) == 0;
+}
+// Device-visible addresses of the four pinned blocks of a small-scene Dual evaluation the host has just filled, the input blocks
+// through their BAR mirrors where they fit (bar_mirror), then one bar_publish.
+struct PinnedDev { void *in = nullptr, *out = nullptr, *din = nullptr, *dout = nullptr; };
+static int map_pinned(pfc_context *h, PinnedDev *v, size_t in_bytes, size_t din_bytes) {
+    HIP_TRY(h, hipHostGetDevicePointer(&v->in, h->pin_in, 0));
+    HIP_TRY(h, hipHostGetDevicePointer(&v->out, h->pin_out, 0));
+    HIP_TRY(h, hipHostGetDevicePointer(&v->din, h->pin_din, 0));
+    HIP_TRY(h, hipHostGetDevicePointer(&v->dout, h->pin_dout, 0));
+    bar_mirror(h, &v->in, h->pin_in, in_bytes, 0);
+    bar_mirror(h, &v->din, h->pin_din, din_bytes, 1);
+    bar_publish();
+    return PFC_OK;
+}
+// Results out of the pinned output blocks: wrench | sdot of n items at po and their counters (n x 4) at pc ...
+static void copy_out(const double *po, const int *pc, size_t n, double *wrench, double *sdot, int *counts) {
+    std::memcpy(wrench, po, sizeof(double) * n * 6);
+    std::memcpy(sdot, po + n * 6, sizeof(double) * n * 6);
+    if (counts) std::memcpy(counts, pc, sizeof(int) * n * 4);
+}
+// ... and the partials d_wrench | d_sdot of nk (item, direction) pairs at pdo.
+static void copy_out_dual(const double *pdo, size_t nk, double *d_wrench, double *d_sdot) {
+    std::memcpy(d_wrench, pdo, sizeof(double) * nk * 6);
+    std::memcpy(d_sdot, pdo + nk * 6, sizeof(double) * nk * 6);
+}
+
 int pfc_eval(pfc_handle h, int n_items, const int *ins_ids, const double *pose, const double *twist,
              const double *s, double *wrench, double *sdot, int *counts) {
     if (!h) return PFC_ERR_BAD_ARG;
@@ -2258,7 +2322,7 @@ int pfc_eval(pfc_handle h, int n_items, const int *ins_ids, const double *pose, 
     if (n_items == 0) return PFC_OK;
     if (!pose || !twist || !wrench || !sdot) return fail(h, PFC_ERR_BAD_ARG, "null buffer");
     HIP_TRY(h, hipSetDevice(h->device));
-    h->pin_in_dual_n = 0; h->pin_din_valid = false;      // the pinned blocks are about to be overwritten
+    h->pin_in_pt = {}; h->pin_din_pt = {};      // the pinned blocks are about to be overwritten
     const size_t n = (size_t)n_items;
     // one pinned block in (pose | twist | s | ins_ids), one pinned block out (tail | wrench | sdot | counts): two async
     // copies around the launch sequence and a single synchronisation.  The device side of the output block lives
@@ -2280,10 +2344,7 @@ int pfc_eval(pfc_handle h, int n_items, const int *ins_ids, const double *pose, 
     // 256 66.5 -> 64.5, 128 full-size poses on the batched path 333 -> 328; scripts/variants/bar_items_run.py)
     const bool bar = n <= kBarItems && !h->want_surv && bar_ready(h);
     double *pi = bar ? (double *)h->bar_in : (double *)h->pin_in;
-    std::memcpy(pi, pose, sizeof(double) * n * 24);
-    std::memcpy(pi + n * 24, twist, sizeof(double) * n * 6);
-    if (s) std::memcpy(pi + n * 30, s, sizeof(double) * n * 6); else std::memset(pi + n * 30, 0, sizeof(double) * n * 6);
-    if (ins_ids) std::memcpy(pi + in_d, ins_ids, sizeof(int) * n);
+    pack_values(pi, n, in_d, ins_ids, pose, twist, s);
     if (bar) bar_publish();
     hipStream_t st = h->stream;
     // A small scene (what a Radau stage evaluates) pays ~5 us per staging copy, more than the kernels spend on the data:
@@ -2321,9 +2382,7 @@ int pfc_eval(pfc_handle h, int n_items, const int *ins_ids, const double *pose, 
     }
     if (rc != PFC_OK) return rc;
     const double *po = reinterpret_cast<const double *>((const int *)h->pin_out + t0);
-    std::memcpy(wrench, po, sizeof(double) * n * 6);
-    std::memcpy(sdot, po + n * 6, sizeof(double) * n * 6);
-    if (counts) std::memcpy(counts, po + out_d, sizeof(int) * n * 4);
+    copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
     return PFC_OK;
 }
 
@@ -2470,7 +2529,7 @@ int launch_dual(pfc_context *h, int n_items, int n_dir, const int *tail, const d
 int eval_dual_fused(pfc_context *h, int n_items, int n_dir, const int *ins_ids, const double *pose, const double *twist,
                     const double *s, const double *d_pose, const double *d_twist, double *wrench, double *sdot,
                     double *d_wrench, double *d_sdot, int *counts) {
-    h->pin_din_valid = false;    // these pinned blocks are about to be reused
+    h->pin_din_pt = {};    // these pinned blocks are about to be reused
     const size_t n = (size_t)n_items, nk = n * n_dir;
     const size_t in_d = n * 36, in_bytes = in_d * sizeof(double) + n * sizeof(int);
     const size_t out_d = n * 12, out_bytes = out_d * sizeof(double) + n * 4 * sizeof(int) + n * 8 * sizeof(int);
@@ -2478,23 +2537,11 @@ int eval_dual_fused(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     HIP_TRY(h, ensure_pinned(&h->pin_out, &h->pin_out_cap, out_bytes + 64));
     HIP_TRY(h, ensure_pinned(&h->pin_din, &h->pin_din_cap, sizeof(double) * nk * 30));
     HIP_TRY(h, ensure_pinned(&h->pin_dout, &h->pin_dout_cap, sizeof(double) * nk * 12));
-    double *pi = (double *)h->pin_in;
-    std::memcpy(pi, pose, sizeof(double) * n * 24);
-    std::memcpy(pi + n * 24, twist, sizeof(double) * n * 6);
-    if (s) std::memcpy(pi + n * 30, s, sizeof(double) * n * 6); else std::memset(pi + n * 30, 0, sizeof(double) * n * 6);
-    if (ins_ids) std::memcpy(pi + in_d, ins_ids, sizeof(int) * n);
-    double *pdi = (double *)h->pin_din;
-    std::memcpy(pdi, d_pose, sizeof(double) * nk * 24);
-    std::memcpy(pdi + nk * 24, d_twist, sizeof(double) * nk * 6);
-    void *v_in = nullptr, *v_out = nullptr, *v_din = nullptr, *v_dout = nullptr;
-    HIP_TRY(h, hipHostGetDevicePointer(&v_in, h->pin_in, 0));
-    HIP_TRY(h, hipHostGetDevicePointer(&v_out, h->pin_out, 0));
-    HIP_TRY(h, hipHostGetDevicePointer(&v_din, h->pin_din, 0));
-    HIP_TRY(h, hipHostGetDevicePointer(&v_dout, h->pin_dout, 0));
-    bar_mirror(h, &v_in, h->pin_in, in_bytes, 0);
-    bar_mirror(h, &v_din, h->pin_din, sizeof(double) * nk * 30, 1);
-    bar_publish();
-    double *di = (double *)v_in, *dout = (double *)v_out, *ddi = (double *)v_din, *ddo = (double *)v_dout;
+    pack_values((double *)h->pin_in, n, in_d, ins_ids, pose, twist, s);
+    pack_seeds((double *)h->pin_din, nk, d_pose, d_twist, nullptr, false);
+    PinnedDev v;
+    { const int rc = map_pinned(h, &v, in_bytes, sizeof(double) * nk * 30); if (rc != PFC_OK) return rc; }
+    double *di = (double *)v.in, *dout = (double *)v.out, *ddi = (double *)v.din, *ddo = (double *)v.dout;
     h->fout_dev = reinterpret_cast<int *>(dout + out_d) + n * 4;
     h->fout_host = reinterpret_cast<const int *>((const double *)h->pin_out + out_d) + n * 4;
     h->fu_ndir = n_dir; h->fu_dpose = ddi; h->fu_dtwist = ddi + nk * 24; h->fu_dwrench = ddo; h->fu_dsdot = ddo + nk * 6;
@@ -2506,12 +2553,9 @@ int eval_dual_fused(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     h->fout_host = nullptr;
     if (rc != PFC_OK) return rc;
     const double *po = (const double *)h->pin_out;
-    std::memcpy(wrench, po, sizeof(double) * n * 6);
-    std::memcpy(sdot, po + n * 6, sizeof(double) * n * 6);
-    if (counts) std::memcpy(counts, po + out_d, sizeof(int) * n * 4);
-    std::memcpy(d_wrench, h->pin_dout, sizeof(double) * nk * 6);
-    std::memcpy(d_sdot, (const double *)h->pin_dout + nk * 6, sizeof(double) * nk * 6);
-    h->pin_in_dual_n = n_items; h->pin_in_dual_ids = ins_ids != nullptr;     // a repeat of this point goes to the hybrid path
+    copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
+    copy_out_dual((const double *)h->pin_dout, nk, d_wrench, d_sdot);
+    h->pin_in_pt = {n_items, ins_ids != nullptr, h->value_serial, in_d};     // a repeat of this point goes to the hybrid path
     return PFC_OK;
 }
 
@@ -2523,7 +2567,7 @@ int eval_dual_fused(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
 int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids, const double *pose, const double *twist,
                      const double *s, const double *d_pose, const double *d_twist, const double *d_s, double *wrench,
                      double *sdot, double *d_wrench, double *d_sdot, int *counts) {
-    h->pin_din_valid = false;    // these pinned blocks are about to be reused
+    h->pin_din_pt = {};    // these pinned blocks are about to be reused
     const size_t n = (size_t)n_items, nk = n * n_dir;
     const size_t in_d = n * 36, in_bytes = in_d * sizeof(double) + n * sizeof(int);
     const size_t out_d = n * 12, out_bytes = out_d * sizeof(double) + n * 4 * sizeof(int) + n * 8 * sizeof(int);
@@ -2531,7 +2575,7 @@ int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids,
         const void *p0 = h->pin_in, *q0 = h->pin_out;
         HIP_TRY(h, ensure_pinned(&h->pin_in, &h->pin_in_cap, in_bytes));
         HIP_TRY(h, ensure_pinned(&h->pin_out, &h->pin_out_cap, out_bytes + 64));
-        if (h->pin_in != p0 || h->pin_out != q0) h->hyb_reuse_ok = false;      // reallocated: the cached blocks are gone
+        if (h->pin_in != p0 || h->pin_out != q0) end_kept_pass(h);      // reallocated: the cached blocks are gone
     }
     HIP_TRY(h, ensure_pinned(&h->pin_din, &h->pin_din_cap, sizeof(double) * nk * 36));
     HIP_TRY(h, ensure_pinned(&h->pin_dout, &h->pin_dout_cap, sizeof(double) * nk * 12));
@@ -2540,35 +2584,17 @@ int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids,
     double *pi = (double *)h->pin_in;
     // the chunks of one Jacobian (pfc_eval_dual's large path has the same test): value inputs bitwise equal to those still
     // in the pinned input block -> the lists and item records the fused kernel handed over are reused, only the Dual passes run
-    bool same = h->opt_dual_reuse && h->hyb_reuse_ok && h->hyb_reuse_n == n_items && h->hyb_reuse_ids == (ins_ids != nullptr) &&
-                std::memcmp(pi, pose, sizeof(double) * n * 24) == 0 && std::memcmp(pi + n * 24, twist, sizeof(double) * n * 6) == 0;
-    if (same && s) same = std::memcmp(pi + n * 30, s, sizeof(double) * n * 6) == 0;
-    if (same && !s) {
-        const double *z = pi + n * 30;
-        for (size_t k = 0; k < n * 6 && same; ++k) same = std::memcmp(z + k, "\0\0\0\0\0\0\0\0", 8) == 0;
-    }
-    if (same && ins_ids) same = std::memcmp(pi + in_d, ins_ids, sizeof(int) * n) == 0;
+    const bool same = h->opt_dual_reuse && h->kept.kind == pfc_context::KeptPass::Hybrid && h->kept.n == n_items &&
+                      h->kept.ids == (ins_ids != nullptr) && same_point(pi, n, in_d, ins_ids, pose, twist, s, true);
     if (!same) {
-        h->hyb_reuse_ok = false;
+        end_kept_pass(h);
         HIP_TRY(h, ensure_work(h, n_items));      // (not before a reuse: option poison refills the work lists there)
-        std::memcpy(pi, pose, sizeof(double) * n * 24);
-        std::memcpy(pi + n * 24, twist, sizeof(double) * n * 6);
-        if (s) std::memcpy(pi + n * 30, s, sizeof(double) * n * 6); else std::memset(pi + n * 30, 0, sizeof(double) * n * 6);
-        if (ins_ids) std::memcpy(pi + in_d, ins_ids, sizeof(int) * n);
+        pack_values(pi, n, in_d, ins_ids, pose, twist, s);
     }
-    double *pdi = (double *)h->pin_din;
-    std::memcpy(pdi, d_pose, sizeof(double) * nk * 24);
-    std::memcpy(pdi + nk * 24, d_twist, sizeof(double) * nk * 6);
-    if (d_s) std::memcpy(pdi + nk * 30, d_s, sizeof(double) * nk * 6); else std::memset(pdi + nk * 30, 0, sizeof(double) * nk * 6);
-    void *v_in = nullptr, *v_out = nullptr, *v_din = nullptr, *v_dout = nullptr;
-    HIP_TRY(h, hipHostGetDevicePointer(&v_in, h->pin_in, 0));
-    HIP_TRY(h, hipHostGetDevicePointer(&v_out, h->pin_out, 0));
-    HIP_TRY(h, hipHostGetDevicePointer(&v_din, h->pin_din, 0));
-    HIP_TRY(h, hipHostGetDevicePointer(&v_dout, h->pin_dout, 0));
-    bar_mirror(h, &v_in, h->pin_in, in_bytes, 0);
-    bar_mirror(h, &v_din, h->pin_din, sizeof(double) * nk * 36, 1);
-    bar_publish();
-    double *di = (double *)v_in, *dout = (double *)v_out;
+    pack_seeds((double *)h->pin_din, nk, d_pose, d_twist, d_s, true);
+    PinnedDev v;
+    { const int rc = map_pinned(h, &v, in_bytes, sizeof(double) * nk * 36); if (rc != PFC_OK) return rc; }
+    double *di = (double *)v.in, *dout = (double *)v.out;
     hipStream_t st = h->stream;
     // seeds / results of up to kBarKeys (512 without a BAR block) (item, direction) pairs are read / written in place by the kernels, larger ones staged
     const bool zc = nk <= (h->bar_state == 1 ? (int)kBarKeys : 512);
@@ -2577,7 +2603,8 @@ int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids,
         HIP_TRY(h, ensure_dual(h, h->dual_out, nk * 12));
         HIP_TRY(h, hipMemcpyAsync(h->dual_in.p, h->pin_din, sizeof(double) * nk * 36, hipMemcpyHostToDevice, st));
     }
-    double *ddi = zc ? (double *)v_din : h->dual_in.p, *ddo = zc ? (double *)v_dout : h->dual_out.p;
+    double *ddi = zc ? (double *)v.din : h->dual_in.p, *ddo = zc ? (double *)v.dout : h->dual_out.p;
+    const double *po = (const double *)h->pin_out;
     if (same) {
         HIP_TRY(h, ensure_dual(h, h->dual_acc, nk * kDaStride));
         HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
@@ -2587,12 +2614,8 @@ int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids,
         if (rcr != PFC_OK) return rcr;
         if (!zc) HIP_TRY(h, hipMemcpyAsync(h->pin_dout, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
         HIP_TRY(h, hipStreamSynchronize(st));
-        const double *po = (const double *)h->pin_out;
-        std::memcpy(wrench, po, sizeof(double) * n * 6);
-        std::memcpy(sdot, po + n * 6, sizeof(double) * n * 6);
-        if (counts) std::memcpy(counts, po + out_d, sizeof(int) * n * 4);
-        std::memcpy(d_wrench, h->pin_dout, sizeof(double) * nk * 6);
-        std::memcpy(d_sdot, (const double *)h->pin_dout + nk * 6, sizeof(double) * nk * 6);
+        copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
+        copy_out_dual((const double *)h->pin_dout, nk, d_wrench, d_sdot);
         h->last_dual_reused = true;
         return PFC_OK;
     }
@@ -2627,14 +2650,10 @@ int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids,
     h->dual_hint = pairs;
     const int cpw = 64 / n_dir;
     if ((h->any_bristle || h->opt_fixed_order) && (size_t)((pairs + cpw - 1) / cpw) * 64 + 64 > dpcap) return PFC_ERR_OVERFLOW;
-    const double *po = (const double *)h->pin_out;
-    std::memcpy(wrench, po, sizeof(double) * n * 6);
-    std::memcpy(sdot, po + n * 6, sizeof(double) * n * 6);
-    if (counts) std::memcpy(counts, po + out_d, sizeof(int) * n * 4);
-    std::memcpy(d_wrench, h->pin_dout, sizeof(double) * nk * 6);
-    std::memcpy(d_sdot, (const double *)h->pin_dout + nk * 6, sizeof(double) * nk * 6);
-    h->hyb_reuse_ok = true; h->hyb_reuse_n = n_items; h->hyb_reuse_ids = ins_ids != nullptr;
-    h->pin_in_dual_n = n_items; h->pin_in_dual_ids = ins_ids != nullptr;
+    copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
+    copy_out_dual((const double *)h->pin_dout, nk, d_wrench, d_sdot);
+    h->kept = {pfc_context::KeptPass::Hybrid, n_items, ins_ids != nullptr};
+    h->pin_in_pt = {n_items, ins_ids != nullptr, h->value_serial, in_d};
     return PFC_OK;
 }
 
@@ -2645,8 +2664,8 @@ int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids,
 int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, const double *pose, const double *twist,
                     const double *s, const double *d_pose, const double *d_twist, const double *d_s, double *wrench,
                     double *sdot, double *d_wrench, double *d_sdot, int *counts) {
-    h->pin_din_valid = false;    // these pinned blocks are about to be reused
-    h->pin_in_dual_n = 0;
+    h->pin_din_pt = {};    // these pinned blocks are about to be reused
+    h->pin_in_pt = {};
     const size_t n = (size_t)n_items, nk = n * n_dir;
     const size_t in_d = n * 36, in_bytes = in_d * sizeof(double) + n * sizeof(int);
     const size_t out_d = n * 12, out_bytes = out_d * sizeof(double) + n * 4 * sizeof(int);
@@ -2656,40 +2675,23 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
         const void *p0 = h->pin_in, *q0 = h->pin_out;
         HIP_TRY(h, ensure_pinned(&h->pin_in, &h->pin_in_cap, in_bytes));
         HIP_TRY(h, ensure_pinned(&h->pin_out, &h->pin_out_cap, back_bytes));
-        if (h->pin_in != p0 || h->pin_out != q0) h->small_reuse_ok = false;     // reallocated: the cached blocks are gone
+        if (h->pin_in != p0 || h->pin_out != q0) end_kept_pass(h);     // reallocated: the cached blocks are gone
     }
     HIP_TRY(h, ensure_pinned(&h->pin_din, &h->pin_din_cap, sizeof(double) * nk * 36));
     HIP_TRY(h, ensure_pinned(&h->pin_dout, &h->pin_dout_cap, sizeof(double) * nk * 12));
     double *pi = (double *)h->pin_in;
     // the chunks of one Jacobian: value inputs bitwise equal to those still in the pinned input block -> only the Dual passes
-    bool same = h->opt_dual_reuse && h->small_reuse_ok && h->small_reuse_n == n_items && h->small_reuse_ids == (ins_ids != nullptr) &&
-                std::memcmp(pi, pose, sizeof(double) * n * 24) == 0 && std::memcmp(pi + n * 24, twist, sizeof(double) * n * 6) == 0;
-    if (same && s) same = std::memcmp(pi + n * 30, s, sizeof(double) * n * 6) == 0;
-    if (same && !s) {
-        const double *z = pi + n * 30;
-        for (size_t k = 0; k < n * 6 && same; ++k) same = std::memcmp(z + k, "\0\0\0\0\0\0\0\0", 8) == 0;
-    }
-    if (same && ins_ids) same = std::memcmp(pi + in_d, ins_ids, sizeof(int) * n) == 0;
+    const bool same = h->opt_dual_reuse && h->kept.kind == pfc_context::KeptPass::OneGraph && h->kept.n == n_items &&
+                      h->kept.ids == (ins_ids != nullptr) && same_point(pi, n, in_d, ins_ids, pose, twist, s, true);
     if (!same) {
-        h->small_reuse_ok = false;
-        std::memcpy(pi, pose, sizeof(double) * n * 24);
-        std::memcpy(pi + n * 24, twist, sizeof(double) * n * 6);
-        if (s) std::memcpy(pi + n * 30, s, sizeof(double) * n * 6); else std::memset(pi + n * 30, 0, sizeof(double) * n * 6);
-        if (ins_ids) std::memcpy(pi + in_d, ins_ids, sizeof(int) * n);
+        end_kept_pass(h);
+        pack_values(pi, n, in_d, ins_ids, pose, twist, s);
     }
-    double *pdi = (double *)h->pin_din;
-    std::memcpy(pdi, d_pose, sizeof(double) * nk * 24);
-    std::memcpy(pdi + nk * 24, d_twist, sizeof(double) * nk * 6);
-    if (d_s) std::memcpy(pdi + nk * 30, d_s, sizeof(double) * nk * 6); else std::memset(pdi + nk * 30, 0, sizeof(double) * nk * 6);
-    void *v_in = nullptr, *v_out = nullptr, *v_din = nullptr, *v_dout = nullptr;
-    HIP_TRY(h, hipHostGetDevicePointer(&v_in, h->pin_in, 0));
-    HIP_TRY(h, hipHostGetDevicePointer(&v_out, h->pin_out, 0));
-    HIP_TRY(h, hipHostGetDevicePointer(&v_din, h->pin_din, 0));
-    HIP_TRY(h, hipHostGetDevicePointer(&v_dout, h->pin_dout, 0));
-    bar_mirror(h, &v_in, h->pin_in, in_bytes, 0);
-    bar_mirror(h, &v_din, h->pin_din, sizeof(double) * nk * 36, 1);
-    bar_publish();
-    double *di = (double *)v_in, *dout = reinterpret_cast<double *>((int *)v_out + t0);
+    pack_seeds((double *)h->pin_din, nk, d_pose, d_twist, d_s, true);
+    PinnedDev v;
+    { const int rc = map_pinned(h, &v, in_bytes, sizeof(double) * nk * 36); if (rc != PFC_OK) return rc; }
+    double *di = (double *)v.in, *dout = reinterpret_cast<double *>((int *)v.out + t0);
+    const double *po = reinterpret_cast<const double *>((const int *)h->pin_out + t0);
     hipStream_t st = h->stream;
     // One captured graph: accumulator fill, the value pass, the Dual passes.  (Launched eagerly behind the replayed value
     // graph, the Dual kernels started 9 us late.)  The capacity of the kept Dual polygons is a power of two above twice
@@ -2712,7 +2714,7 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
         HIP_TRY(h, ensure_dual(h, h->dual_in, nk * 36));
         HIP_TRY(h, ensure_dual(h, h->dual_out, nk * 12));
     }
-    double *ddi = zc_dual ? (double *)v_din : h->dual_in.p, *ddo = zc_dual ? (double *)v_dout : h->dual_out.p;
+    double *ddi = zc_dual ? (double *)v.din : h->dual_in.p, *ddo = zc_dual ? (double *)v.dout : h->dual_out.p;
     if (same) {
         // eager launches of the Dual passes on the value pass the last graph replay left (lists, item records, the packed tail
         // in the pinned output block); the pair count is known, so there is no speculation to check
@@ -2720,17 +2722,13 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
         if (!zc_dual) HIP_TRY(h, hipMemcpyAsync(ddi, h->pin_din, sizeof(double) * nk * 36, hipMemcpyHostToDevice, st));
         h->last_levels = levels;
         const size_t bound_r = (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) + 64;
-        int rcr = launch_dual(h, n_items, n_dir, (const int *)v_out, ddi, ddi + nk * 24, ddi + nk * 30, ddo, ddo + nk * 6, bound_r, st,
+        int rcr = launch_dual(h, n_items, n_dir, (const int *)v.out, ddi, ddi + nk * 24, ddi + nk * 30, ddo, ddo + nk * 6, bound_r, st,
                               nullptr, true);
         if (rcr != PFC_OK) return rcr;
         if (!zc_dual) HIP_TRY(h, hipMemcpyAsync(h->pin_dout, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
         HIP_TRY(h, hipStreamSynchronize(st));
-        const double *po = reinterpret_cast<const double *>((const int *)h->pin_out + t0);
-        std::memcpy(wrench, po, sizeof(double) * n * 6);
-        std::memcpy(sdot, po + n * 6, sizeof(double) * n * 6);
-        if (counts) std::memcpy(counts, po + out_d, sizeof(int) * n * 4);
-        std::memcpy(d_wrench, h->pin_dout, sizeof(double) * nk * 6);
-        std::memcpy(d_sdot, (const double *)h->pin_dout + nk * 6, sizeof(double) * nk * 6);
+        copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
+        copy_out_dual((const double *)h->pin_dout, nk, d_wrench, d_sdot);
         h->last_dual_reused = true;
         return PFC_OK;
     }
@@ -2740,10 +2738,10 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     key.v.n_items = n_items; key.v.levels = levels; key.v.L = L; key.v.debug = 0;
     key.v.bristle = (h->any_bristle ? 1 : 0) | (h->any_tet_tet ? 2 : 0); key.v.surv = 1;
     key.v.p[0] = d_ins; key.v.p[1] = di; key.v.p[2] = di + n * 24; key.v.p[3] = d_sv; key.v.p[4] = dout;
-    key.v.p[5] = dout + n * 6; key.v.p[6] = dout + out_d; key.v.p[7] = v_out; key.v.p[8] = h->bp_dev; key.v.stream = (void *)st; key.v.epoch = h->epoch;
+    key.v.p[5] = dout + n * 6; key.v.p[6] = dout + out_d; key.v.p[7] = v.out; key.v.p[8] = h->bp_dev; key.v.stream = (void *)st; key.v.epoch = h->epoch;
     key.n_dir = n_dir; key.bound = bound; key.din = ddi; key.dout = ddo;
     h->want_surv = true;
-    h->tail_dev = (int *)v_out;
+    h->tail_dev = (int *)v.out;
     h->last_levels = levels;      // launch_dual locates the pair counter in the tail by it
     int rc = PFC_OK;
     if (!h->dghave || std::memcmp(&key, &h->dgkey, sizeof key) != 0) {
@@ -2756,7 +2754,7 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
             if (!zc_dual && e == hipSuccess) e = hipMemcpyAsync(ddi, h->pin_din, sizeof(double) * nk * 36, hipMemcpyHostToDevice, st);
             rc = record_eval(h, n_items, d_ins, di, di + n * 24, d_sv, dout, dout + n * 6, (int *)(dout + out_d), st, false);
             if (rc == PFC_OK)
-                rc = launch_dual(h, n_items, n_dir, (const int *)v_out, ddi, ddi + nk * 24, ddi + nk * 30, ddo, ddo + nk * 6, bound,
+                rc = launch_dual(h, n_items, n_dir, (const int *)v.out, ddi, ddi + nk * 24, ddi + nk * 30, ddo, ddo + nk * 6, bound,
                                  st, nullptr, true);
             if (!zc_dual && rc == PFC_OK && e == hipSuccess)
                 e = hipMemcpyAsync(h->pin_dout, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st);
@@ -2771,7 +2769,8 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
         h->dgkey = key; h->dghave = true;
     }
     h->want_surv = false; h->tail_dev = nullptr;
-    h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false; h->last_dual_reused = false;   // the replay overwrites the device state
+    new_value_pass(h);      // the replay overwrites the device state
+    h->last_dual_reused = false;
     HIP_TRY(h, hipGraphLaunch(h->dgexec, st));
     h->last_bfs_levels = L; h->last_n_items = n_items; h->pending = true; h->last_stream = st; h->ev_valid = false;
     h->split_n0 = 0;
@@ -2784,13 +2783,9 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     const long long pairs = tail[12 + (((h->last_levels + 9) & ~1) + 1)];
     h->dual_hint = pairs;
     if ((h->any_bristle || h->opt_fixed_order) && (size_t)((pairs + cpw - 1) / cpw) * 64 + 64 > dpcap) return PFC_ERR_OVERFLOW;
-    const double *po = reinterpret_cast<const double *>((const int *)h->pin_out + t0);
-    std::memcpy(wrench, po, sizeof(double) * n * 6);
-    std::memcpy(sdot, po + n * 6, sizeof(double) * n * 6);
-    if (counts) std::memcpy(counts, po + out_d, sizeof(int) * n * 4);
-    std::memcpy(d_wrench, h->pin_dout, sizeof(double) * nk * 6);
-    std::memcpy(d_sdot, (const double *)h->pin_dout + nk * 6, sizeof(double) * nk * 6);
-    h->small_reuse_ok = true; h->small_reuse_n = n_items; h->small_reuse_ids = ins_ids != nullptr;
+    copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
+    copy_out_dual((const double *)h->pin_dout, nk, d_wrench, d_sdot);
+    h->kept = {pfc_context::KeptPass::OneGraph, n_items, ins_ids != nullptr};
     return PFC_OK;
 }
 }  // namespace
@@ -2820,7 +2815,8 @@ int pfc_eval_dual_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_
                                  d_dwrench, d_dsdot, d_counts, stream);
     if (n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "pfc_eval_dual_device: n_dir must be in 1..16");
     { const int rc = check_eval_args(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot); if (rc != PFC_OK) return rc; }
-    h->pending_dual = false; h->dual_reuse_ok = false; h->pending_more = false;
+    h->pending_dual = false; h->pending_more = false;
+    end_kept_pass(h);
     if (n_items == 0) { h->pending = false; h->last_n_items = 0; return PFC_OK; }
     if (!d_dpose || !d_dtwist || !d_dwrench || !d_dsdot) return fail(h, PFC_ERR_BAD_ARG, "pfc_eval_dual_device: null buffer");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -2864,7 +2860,7 @@ int pfc_eval_dual_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_
             rcf = launch_dual(h, n_items, n_dir, h->tail.p, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, bh, st, &dpcap_h, true, h->emit_ctr.p);
             if (rcf != PFC_OK) return rcf;
             HIP_TRY(h, hipMemcpyAsync(h->h_emit, h->emit_ctr.p, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-            h->pending_dual_hyb = true; h->pending_dpcap = dpcap_h; h->pending_ndir = n_dir;
+            h->pending_dual_hyb = true; h->pending_dpcap = dpcap_h; h->pending_ndir = n_dir; h->pending_ids = d_ins_ids != nullptr;
             return PFC_OK;
         }
     }
@@ -2875,7 +2871,7 @@ int pfc_eval_dual_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_
     size_t dpcap = 0;
     rc = launch_dual(h, n_items, n_dir, h->tail.p, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, bound, st, &dpcap, true);
     if (rc != PFC_OK) return rc;
-    h->pending_dual = true; h->pending_dpcap = dpcap; h->pending_ndir = n_dir;
+    h->pending_dual = true; h->pending_dpcap = dpcap; h->pending_ndir = n_dir; h->pending_ids = d_ins_ids != nullptr;
     return PFC_OK;
 }
 
@@ -2884,12 +2880,12 @@ int pfc_eval_dual_device_more(pfc_handle h, int n_dir, const double *d_dpose, co
     if (!h) return PFC_ERR_BAD_ARG;
     if (h->multi) return multi_eval_dual_device_more(h, n_dir, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, stream);
     if (n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "pfc_eval_dual_device_more: n_dir must be in 1..16");
-    if (!h->dual_reuse_ok)
+    if (!h->device_kept())
         return fail(h, PFC_ERR_STATE, "pfc_eval_dual_device_more: no checked pfc_eval_dual_device evaluation on this handle to extend");
     if (!d_dpose || !d_dtwist || !d_dwrench || !d_dsdot) return fail(h, PFC_ERR_BAD_ARG, "pfc_eval_dual_device_more: null buffer");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    const int n_items = h->dual_reuse_n;
+    const int n_items = h->kept.n;
     const size_t nk = (size_t)n_items * n_dir;
     HIP_TRY(h, ensure_dual(h, h->dual_acc, nk * kDaStride));
     HIP_TRY(h, ensure_dual(h, h->dual_res, nk * kDrStride));
@@ -2909,7 +2905,7 @@ int pfc_eval_dual_device_more(pfc_handle h, int n_dir, const double *d_dpose, co
     unsigned *more_status = h->status.p + 1;
     HIP_TRY(h, hipMemsetAsync(more_status, 0, sizeof(unsigned), st));
     const int rc = launch_dual(h, n_items, n_dir, h->tail.p, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, bound, st, nullptr, true,
-                               h->dual_reuse_emit ? h->emit_ctr.p : nullptr, more_status);
+                               h->kept.kind == pfc_context::KeptPass::HandOver ? h->emit_ctr.p : nullptr, more_status);
     if (rc != PFC_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->h_more, more_status, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     h->pending_more = true; h->last_stream = st; h->last_dual_reused = true;
@@ -2921,12 +2917,12 @@ int pfc_eval_dual_device_more(pfc_handle h, int n_dir, const double *d_dpose, co
 int pfc_local_jacobian_device(pfc_handle h, double *d_L, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
     if (h->multi) return multi_local_jacobian_device(h, d_L, stream);
-    if (!h->dual_reuse_ok)
+    if (!h->device_kept())
         return fail(h, PFC_ERR_STATE, "pfc_local_jacobian_device: no checked pfc_eval_dual_device evaluation on this handle");
     if (!d_L) return fail(h, PFC_ERR_BAD_ARG, "pfc_local_jacobian_device: null buffer");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    const int n_items = h->dual_reuse_n;
+    const int n_items = h->kept.n;
     const size_t n = (size_t)n_items;
     if (h->ljac_seed.cap < n * kLjacSeedDoubles) {      // the constant seeds: written once per capacity (a power of two of items)
         size_t cap = 64;
@@ -2947,7 +2943,7 @@ int pfc_local_jacobian_device(pfc_handle h, double *d_L, void *stream) {
         const double *dp = h->ljac_seed.p + cap * 576 * p, *dt = dp + cap * nd * 24, *dsd = dt + cap * nd * 6;
         double *dw = h->ljac_out.p + n * 192 * p, *dsdot = dw + n * nd * 6;
         const int rc = launch_dual(h, n_items, nd, h->tail.p, dp, dt, dsd, dw, dsdot, bound, st, nullptr, false,
-                                   h->dual_reuse_emit ? h->emit_ctr.p : nullptr, more_status);
+                                   h->kept.kind == pfc_context::KeptPass::HandOver ? h->emit_ctr.p : nullptr, more_status);
         if (rc != PFC_OK) return rc;
     }
     hipLaunchKernelGGL(k_ljac_pack, dim3((unsigned)((n * kLjacSize + 255) / 256)), dim3(256), 0, st, n_items, h->ljac_out.p, d_L);
@@ -3067,7 +3063,8 @@ int pfc_eval_dual_bp(pfc_handle h, int n_items, int n_dir, const int *ins_ids, c
     }
     if (h->pin_bp_n != n_items || std::memcmp(h->pin_bp, bp_pose, bytes) != 0) {
         // another broadphase pose: nothing a previous Dual evaluation left can be reused (the candidate lists differ)
-        h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false; h->pin_in_dual_n = 0; h->pin_din_valid = false;
+        end_kept_pass(h);
+        h->pin_in_pt = {}; h->pin_din_pt = {};
         std::memcpy(h->pin_bp, bp_pose, bytes);
         h->pin_bp_n = n_items;
     }
@@ -3087,7 +3084,8 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
         return multi_eval_dual(h, n_items, n_dir, ins_ids, pose, nullptr, twist, s, d_pose, d_twist, d_s, wrench, sdot, d_wrench, d_sdot, counts);
     if (!h->bp_dev && h->pin_bp_n != 0) {
         // the previous host-buffer Dual evaluation culled with a pose of its own: its lists are not this evaluation's
-        h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false; h->pin_in_dual_n = 0; h->pin_din_valid = false;
+        end_kept_pass(h);
+        h->pin_in_pt = {}; h->pin_din_pt = {};
         h->pin_bp_n = 0;
     }
     if (n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "pfc_eval_dual: n_dir must be in 1..16");
@@ -3097,15 +3095,9 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
     { const int rc = check_eval_args(h, n_items, ins_ids, pose, twist, s, wrench, sdot); if (rc != PFC_OK) return rc; }
     // A repeat of the previous small-scene Dual evaluation's point (the next chunk of a Jacobian): leave the all-in-one
     // kernel, whose Dual passes keep nothing, for the hybrid path, which hands lists over that the chunks after it reuse.
-    bool repeat = false;
-    if (n_items > 0 && h->opt_dual_reuse && h->pin_in_dual_n == n_items && h->pin_in && h->pin_in_dual_ids == (ins_ids != nullptr)) {
-        const double *pi = (const double *)h->pin_in;
-        const size_t n = (size_t)n_items;
-        repeat = std::memcmp(pi, pose, sizeof(double) * n * 24) == 0 && std::memcmp(pi + n * 24, twist, sizeof(double) * n * 6) == 0 &&
-                 (!s || std::memcmp(pi + n * 30, s, sizeof(double) * n * 6) == 0) &&
-                 (!ins_ids || std::memcmp(pi + n * 36, ins_ids, sizeof(int) * n) == 0);
-    }
-    if (!repeat) h->pin_in_dual_n = 0;
+    const bool repeat = n_items > 0 && h->opt_dual_reuse && h->pin_in_pt.n == n_items && h->pin_in && h->pin_in_pt.ids == (ins_ids != nullptr) &&
+                        same_point((const double *)h->pin_in, (size_t)n_items, h->pin_in_pt.ids_at, ins_ids, pose, twist, s, false);
+    if (!repeat) h->pin_in_pt = {};
     if (n_items > 0 && !h->any_bristle && fused_ok(h, n_items) && !repeat) {
         if (h->dual_fused_skip > 0) {
             --h->dual_fused_skip;
@@ -3146,7 +3138,7 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
             const void *p0 = h->pin_din, *q0 = h->pin_dout;
             HIP_TRY(h, ensure_pinned(&h->pin_din, &h->pin_din_cap, in_bytes));
             HIP_TRY(h, ensure_pinned(&h->pin_dout, &h->pin_dout_cap, out_bytes));
-            if (h->pin_din != p0 || h->pin_dout != q0) h->pin_din_valid = false;      // reallocated: the cached blocks are gone
+            if (h->pin_din != p0 || h->pin_dout != q0) h->pin_din_pt = {};      // reallocated: the cached blocks are gone
         }
         HIP_TRY(h, ensure_dual(h, h->dual_in, in_d + (n + 1) / 2 + 1));
         HIP_TRY(h, ensure_dual(h, h->dual_out, out_d + (n * 4 + 1) / 2 + 1));
@@ -3157,23 +3149,17 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
         // the path ceil(NX / N_chunk) times with the same values and different partials, src/radau/radau_functions.jl:2-14):
         // if the value inputs equal, bit for bit, those still sitting in the pinned input block, the value pass on the
         // device is reused -- candidates, contributing pairs, per-item results -- and only the Dual passes run.
-        static const double kZero6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         // (the device lists must be those of the evaluation the pinned block belongs to: a pfc_eval_dual_device + pfc_check of
-        // the caller's own in between leaves dual_reuse_ok set for ITS point -- the serial tells the two apart)
-        bool same = h->opt_dual_reuse && h->dual_reuse_ok && h->pin_din_valid && h->pin_din_serial == h->value_serial && h->dual_reuse_n == n_items &&
-                    h->pin_din_ids == (ins_ids != nullptr) && h->dual_counts_cache.size() == n * 4 &&
-                    std::memcmp(pi, pose, sizeof(double) * n * 24) == 0 && std::memcmp(pi + n * 24, twist, sizeof(double) * n * 6) == 0;
-        if (same && s) same = std::memcmp(pi + n * 30, s, sizeof(double) * n * 6) == 0;
-        if (same && !s)
-            for (size_t k = 0; k < n && same; ++k) same = std::memcmp(pi + n * 30 + 6 * k, kZero6, sizeof kZero6) == 0;
-        if (same && ins_ids) same = std::memcmp(pi + n * 36 + h->pin_din_nk36, ins_ids, sizeof(int) * n) == 0;
+        // the caller's own in between keeps a pass of ITS point -- the serial tells the two apart)
+        const auto &pt = h->pin_din_pt;
+        const bool same = h->opt_dual_reuse && h->device_kept() && h->kept.n == n_items && pt.n == n_items && pt.serial == h->value_serial &&
+                          pt.ids == (ins_ids != nullptr) && h->dual_counts_cache.size() == n * 4 &&
+                          same_point(pi, n, pt.ids_at, ins_ids, pose, twist, s, true);
         if (same) {
             // the seeds go behind the value block as before (the ids of the cached evaluation are not needed again)
-            std::memcpy(pd, d_pose, sizeof(double) * nk * 24);
-            std::memcpy(pd + nk * 24, d_twist, sizeof(double) * nk * 6);
-            if (d_s) std::memcpy(pd + nk * 30, d_s, sizeof(double) * nk * 6); else std::memset(pd + nk * 30, 0, sizeof(double) * nk * 6);
+            pack_seeds(pd, nk, d_pose, d_twist, d_s, true);
             if (ins_ids) std::memcpy(pd + nk * 36, ins_ids, sizeof(int) * n);      // keep the block's layout: ids behind the seeds
-            h->pin_din_nk36 = nk * 36;
+            h->pin_din_pt.ids_at = in_d;
             HIP_TRY(h, hipMemcpyAsync(dd, pd, sizeof(double) * nk * 36, hipMemcpyHostToDevice, st));
             int rc3 = pfc_eval_dual_device_more(h, n_dir, dd, dd + nk * 24, dd + nk * 30, ddo, ddo + nk * 6, st);
             if (rc3 != PFC_OK) return rc3;
@@ -3181,22 +3167,13 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
             HIP_TRY(h, hipMemcpyAsync(pdo, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
             rc3 = pfc_check(h);
             if (rc3 != PFC_OK) return rc3;
-            const double *po = (const double *)h->pin_dout;
-            std::memcpy(wrench, po, sizeof(double) * n * 6);
-            std::memcpy(sdot, po + n * 6, sizeof(double) * n * 6);
-            std::memcpy(d_wrench, pdo, sizeof(double) * nk * 6);
-            std::memcpy(d_sdot, pdo + nk * 6, sizeof(double) * nk * 6);
-            if (counts) std::memcpy(counts, h->dual_counts_cache.data(), sizeof(int) * n * 4);
+            copy_out((const double *)h->pin_dout, h->dual_counts_cache.data(), n, wrench, sdot, counts);
+            copy_out_dual(pdo, nk, d_wrench, d_sdot);
             return PFC_OK;
         }
-        h->pin_din_valid = false;
-        std::memcpy(pi, pose, sizeof(double) * n * 24);
-        std::memcpy(pi + n * 24, twist, sizeof(double) * n * 6);
-        if (s) std::memcpy(pi + n * 30, s, sizeof(double) * n * 6); else std::memset(pi + n * 30, 0, sizeof(double) * n * 6);
-        std::memcpy(pd, d_pose, sizeof(double) * nk * 24);
-        std::memcpy(pd + nk * 24, d_twist, sizeof(double) * nk * 6);
-        if (d_s) std::memcpy(pd + nk * 30, d_s, sizeof(double) * nk * 6); else std::memset(pd + nk * 30, 0, sizeof(double) * nk * 6);
-        if (ins_ids) std::memcpy(pi + in_d, ins_ids, sizeof(int) * n);
+        h->pin_din_pt = {};
+        pack_values(pi, n, in_d, ins_ids, pose, twist, s);
+        pack_seeds(pd, nk, d_pose, d_twist, d_s, true);
         HIP_TRY(h, hipMemcpyAsync(di, pi, ins_ids ? in_bytes : in_d * sizeof(double), hipMemcpyHostToDevice, st));
         int rc2 = PFC_OK;
         for (int attempt = 0; attempt < 40; ++attempt) {
@@ -3210,14 +3187,12 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
         }
         if (rc2 != PFC_OK) return rc2;
         const double *po = (const double *)h->pin_dout;
-        std::memcpy(wrench, po, sizeof(double) * n * 6);
-        std::memcpy(sdot, po + n * 6, sizeof(double) * n * 6);
-        std::memcpy(d_wrench, po + n * 12, sizeof(double) * nk * 6);
-        std::memcpy(d_sdot, po + n * 12 + nk * 6, sizeof(double) * nk * 6);
-        if (counts) std::memcpy(counts, po + out_d, sizeof(int) * n * 4);
+        const int *pc = reinterpret_cast<const int *>(po + out_d);
+        copy_out(po, pc, n, wrench, sdot, counts);
+        copy_out_dual(po + n * 12, nk, d_wrench, d_sdot);
         // what a following call at the same point needs: the counters (the pinned blocks keep the rest)
-        h->dual_counts_cache.assign(reinterpret_cast<const int *>(po + out_d), reinterpret_cast<const int *>(po + out_d) + n * 4);
-        h->pin_din_valid = true; h->pin_din_ids = ins_ids != nullptr; h->pin_din_nk36 = nk * 36; h->pin_din_serial = h->value_serial;
+        h->dual_counts_cache.assign(pc, pc + n * 4);
+        h->pin_din_pt = {n_items, ins_ids != nullptr, h->value_serial, in_d};
         return PFC_OK;
     }
     // two-stage path (debug option, or PFC_DUAL_TWO_STAGE set for A/B runs): values, candidate list and per-item counters
@@ -3237,21 +3212,14 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
     const size_t in_bytes = sizeof(double) * nk * 36, out_bytes = sizeof(double) * nk * 12;
     HIP_TRY(h, ensure_pinned(&h->pin_in, &h->pin_in_cap, in_bytes));
     HIP_TRY(h, ensure_pinned(&h->pin_out, &h->pin_out_cap, out_bytes));
-    {
-        double *pi = (double *)h->pin_in;
-        std::memcpy(pi, d_pose, sizeof(double) * nk * 24);
-        std::memcpy(pi + nk * 24, d_twist, sizeof(double) * nk * 6);
-        if (d_s) std::memcpy(pi + nk * 30, d_s, sizeof(double) * nk * 6);
-        else std::memset(pi + nk * 30, 0, sizeof(double) * nk * 6);
-        HIP_TRY(h, hipMemcpyAsync(dp, pi, in_bytes, hipMemcpyHostToDevice, st));
-    }
+    pack_seeds((double *)h->pin_in, nk, d_pose, d_twist, d_s, true);
+    HIP_TRY(h, hipMemcpyAsync(dp, h->pin_in, in_bytes, hipMemcpyHostToDevice, st));
     rc = launch_dual(h, n_items, n_dir, h->tail.p, dp, dt, dsd, h->dual_out.p, h->dual_out.p + nk * 6, (size_t)h->stats[2], st, nullptr);
     if (rc != PFC_OK) return rc;
     h->dual_hint = h->stats[2];
     HIP_TRY(h, hipMemcpyAsync(h->pin_out, h->dual_out.p, out_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
-    std::memcpy(d_wrench, h->pin_out, sizeof(double) * nk * 6);
-    std::memcpy(d_sdot, (const double *)h->pin_out + nk * 6, sizeof(double) * nk * 6);
+    copy_out_dual((const double *)h->pin_out, nk, d_wrench, d_sdot);
     return PFC_OK;
 }
 
@@ -3259,13 +3227,14 @@ int pfc_set_option(pfc_handle h, const char *name, long long value) {
     if (!h || !name) return PFC_ERR_BAD_ARG;
     if (h->multi) {
         if (!std::strcmp(name, "multi_min")) { h->multi->opt_min_items = value < 1 ? 1 : (int)value; h->multi->part_n = 0; return PFC_OK; }
+        h->multi->dev_kept = false;      // (as every shard's kept pass below)
         for (pfc_context *c : h->multi->shard) {
             const int rc = pfc_set_option(c, name, value);
             if (rc != PFC_OK) { h->err = c->err; return rc; }
         }
         return PFC_OK;
     }
-    h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false;
+    end_kept_pass(h);      // every option change ends the kept pass, also one that sets an option to what it is
     if (!std::strcmp(name, "debug")) h->opt_debug = value != 0;
     else if (!std::strcmp(name, "profile")) h->opt_profile = value != 0;
     else if (!std::strcmp(name, "max_levels")) {
@@ -3289,10 +3258,9 @@ int pfc_set_option(pfc_handle h, const char *name, long long value) {
         // the batched path only while it is on, whatever "fused" / "team" / "split_min" / "graph" say (fused_ok, fused_team, the split
         // rule and use_graph look at it): no one-launch kernel, no two-half split, eager launches (the sort is library code)
         const int on = value != 0;
-        if (on != h->opt_fixed_order) {      // (setting it to what it is changes nothing: a kept value pass stays reusable)
+        if (on != h->opt_fixed_order) {      // (setting it to what it is keeps the graphs and the record list)
             h->opt_fixed_order = on; h->fused_skip = 0;
             h->ghave[0] = h->ghave[1] = false; h->dghave = false;
-            h->dual_reuse_ok = false; h->hyb_reuse_ok = false; h->small_reuse_ok = false;
             h->rec.release();      // (the records change their stride)
         }
     }

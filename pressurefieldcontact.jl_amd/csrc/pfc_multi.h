@@ -58,7 +58,7 @@ struct pfc_multi {
     bool dev_pending = false;              // a device-pointer evaluation is enqueued and not checked yet
     const int *dev_counts = nullptr;       // where shard k's counters lie on ITS device: stage[k].cnt (k = 0: the caller's array or stage[0].cnt)
     hipStream_t dev_stream = nullptr;
-    bool dev_reuse_ok = false;             // pfc_eval_dual_device_more may follow (same partition)
+    bool dev_kept = false;                 // every shard keeps its pass: pfc_eval_dual_device_more may follow (same partition)
     int dev_reuse_ndir = 0;
 };
 
@@ -178,7 +178,7 @@ void multi_partition(pfc_context *h, int n, const int *ins_ids, bool has_ids, bo
     M->n_used = k_use;
     M->part_n = n; M->part_ids = has_ids; M->part_dev = is_dev;
     if (ins_ids && !is_dev) M->part_ins.assign(ins_ids, ins_ids + n); else M->part_ins.clear();
-    M->dev_reuse_ok = false;
+    M->dev_kept = false;
 }
 
 int multi_ensure_host(pfc_context *h, int n) {
@@ -231,7 +231,7 @@ int multi_eval(pfc_context *h, int n_items, const int *ins_ids, const double *po
     if (M->shard[0]->any_bristle && !s) return fail(h, PFC_ERR_BAD_ARG, "bristle instructions need the state buffer s");
     { const int rc = multi_ensure_host(h, n_items); if (rc != PFC_OK) return rc; }
     multi_partition(h, n_items, ins_ids, ins_ids != nullptr, false);
-    M->dev_pending = false; M->dev_reuse_ok = false;
+    M->dev_pending = false; M->dev_kept = false;
     const int *ids = ins_ids ? ins_ids : M->iota.data();
     int *cnt = M->h_counts;
     std::vector<std::function<int()>> jobs((size_t)M->n_used);
@@ -263,7 +263,7 @@ int multi_eval_dual(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     if (M->shard[0]->any_bristle && !s) return fail(h, PFC_ERR_BAD_ARG, "bristle instructions need the state buffer s");
     { const int rc = multi_ensure_host(h, n_items); if (rc != PFC_OK) return rc; }
     multi_partition(h, n_items, ins_ids, ins_ids != nullptr, false);
-    M->dev_pending = false; M->dev_reuse_ok = false;
+    M->dev_pending = false; M->dev_kept = false;
     const int *ids = ins_ids ? ins_ids : M->iota.data();
     int *cnt = M->h_counts;
     const size_t nd = (size_t)n_dir;
@@ -290,13 +290,6 @@ int multi_eval_dual(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
 }
 
 // ---- device-pointer entry points ---------------------------------------------------------------------------------
-// The enqueueing thread walks over the devices of the list; whichever way an entry point is left (HIP_TRY returns from the middle
-// of a shard's enqueue), the caller's thread is back on the first device -- the one its buffers and its stream live on.
-struct MultiDeviceGuard {
-    int dev;
-    explicit MultiDeviceGuard(int d) : dev(d) {}
-    ~MultiDeviceGuard() { (void)hipSetDevice(dev); }
-};
 hipError_t multi_copy(void *dst, int dst_dev, const void *src, int src_dev, size_t bytes, hipStream_t st) {
     if (bytes == 0) return hipSuccess;
     if (dst_dev == src_dev) return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st);
@@ -314,13 +307,60 @@ int multi_dev_iota(pfc_context *h, int k, int n) {
     return PFC_OK;
 }
 
+// A shard whose stream has been synchronised after a failed fan-out: nothing of it is pending any more (nor its team slot).
+void multi_drop_pending(pfc_context *c) {
+    c->pending = c->pending_fused = c->pending_dual = c->pending_dual_hyb = c->pending_more = false;
+    team_release(c);
+}
+
+// The fan-out of the device-pointer entry points.  Every shard k >= 1 with items runs on its device and stream behind the caller's
+// stream st0 (fork event): stage(k) makes its staging ready (nothing there waits for st0), run(k, stream) copies its range in, calls
+// the shard and copies the results back into the caller's buffers; then run(0, st0) evaluates shard 0 on the caller's arrays and
+// stream, which waits for every other shard.  Both return a status with its message in h->err.  One exit for errors: once shards
+// have work enqueued (copies that write into the caller's buffers; staging the next call may reallocate), the streams that may
+// hold some are synchronised and the shards' pending state dropped before the first error is returned.  The caller's thread is
+// back on the first device -- the one its buffers and its stream live on -- whichever way this returns.
+template <class StageFn, class RunFn>
+int multi_fan_out(pfc_context *h, hipStream_t st0, const char *what, StageFn stage, RunFn run) {
+    pfc_multi *M = h->multi;
+    const int dev0 = M->dev[0];
+    int rc = PFC_OK, enq = 1;      // shards [1, enq) may have work enqueued
+    hipError_t e = hipSetDevice(dev0);
+    if (e == hipSuccess && M->n_used > 1) e = hipEventRecord(M->ev_fork, st0);
+    for (int k = 1; k < M->n_used && rc == PFC_OK && e == hipSuccess; ++k) {
+        if (M->bound[k + 1] <= M->bound[k]) continue;
+        hipStream_t sk = M->shard[k]->stream;
+        if ((e = hipSetDevice(M->dev[k])) != hipSuccess || (rc = stage(k)) != PFC_OK || (e = hipStreamWaitEvent(sk, M->ev_fork, 0)) != hipSuccess)
+            break;
+        enq = k + 1;
+        if ((rc = run(k, sk)) == PFC_OK) e = hipEventRecord(M->stage[k].done, sk);
+    }
+    if (rc == PFC_OK && e == hipSuccess && (e = hipSetDevice(dev0)) == hipSuccess) {
+        rc = run(0, st0);
+        for (int k = 1; k < M->n_used && rc == PFC_OK && e == hipSuccess; ++k)
+            if (M->bound[k + 1] > M->bound[k]) e = hipStreamWaitEvent(st0, M->stage[k].done, 0);
+    }
+    if (rc == PFC_OK && e != hipSuccess) rc = fail(h, PFC_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+    if (rc != PFC_OK) {
+        for (int k = 1; k < enq; ++k) {
+            (void)hipSetDevice(M->dev[k]);
+            (void)hipStreamSynchronize(M->shard[k]->stream);
+            multi_drop_pending(M->shard[k]);
+        }
+        (void)hipSetDevice(dev0);
+        (void)hipStreamSynchronize(st0);
+        multi_drop_pending(M->shard[0]);
+    }
+    return rc;
+}
+
 // value evaluation (n_dir == 0) or Dual evaluation with every buffer on device dev[0]
 int multi_eval_device(pfc_context *h, int n_items, int n_dir, const int *d_ins_ids, const double *d_pose, const double *d_bp,
                       const double *d_twist, const double *d_s, const double *d_dpose, const double *d_dtwist, const double *d_ds,
                       double *d_wrench, double *d_sdot, double *d_dwrench, double *d_dsdot, int *d_counts, void *stream) {
     pfc_multi *M = h->multi;
     { const int rc = multi_check_args(h, n_items, d_ins_ids, d_pose, d_twist, d_wrench, d_sdot); if (rc != PFC_OK) return rc; }
-    M->dev_pending = false; M->dev_reuse_ok = false;
+    M->dev_pending = false; M->dev_kept = false;
     if (n_items == 0) return PFC_OK;
     if (M->shard[0]->any_bristle && !d_s) return fail(h, PFC_ERR_BAD_ARG, "bristle instructions need the state buffer s");
     if (n_dir && (n_dir < 1 || n_dir > 16)) return fail(h, PFC_ERR_BAD_ARG, "pfc_eval_dual_device: n_dir must be in 1..16");
@@ -330,27 +370,35 @@ int multi_eval_device(pfc_context *h, int n_items, int n_dir, const int *d_ins_i
     // previous check brought back
     multi_partition(h, n_items, nullptr, d_ins_ids != nullptr, true);
     const int dev0 = M->dev[0];
-    HIP_TRY(h, hipSetDevice(dev0));
-    MultiDeviceGuard back_to_first(dev0);
     hipStream_t st0 = stream ? (hipStream_t)stream : M->shard[0]->stream;
     const size_t nd = (size_t)n_dir;
-    if (M->n_used > 1) HIP_TRY(h, hipEventRecord(M->ev_fork, st0));
-    int rc = PFC_OK;
-    for (int k = 1; k < M->n_used && rc == PFC_OK; ++k) {
+    auto stage = [&](int k) -> int {
+        pfc_multi::Stage &S = M->stage[k];
+        const size_t n = (size_t)(M->bound[k + 1] - M->bound[k]);
+        HIP_TRY(h, S.in.ensure(n * 60)); HIP_TRY(h, S.out.ensure(n * 12)); HIP_TRY(h, S.cnt.ensure(n * 4));
+        if (d_ins_ids) HIP_TRY(h, S.ids.ensure(n));
+        else return multi_dev_iota(h, k, n_items);
+        return PFC_OK;
+    };
+    auto run = [&](int k, hipStream_t sk) -> int {
+        pfc_context *c = M->shard[k];
         const size_t b0 = (size_t)M->bound[k];
         const int nk = M->bound[k + 1] - (int)b0;
-        if (nk <= 0) continue;
-        pfc_context *c = M->shard[k];
+        int rc;
+        if (k == 0) {      // the caller's arrays in place
+            int *cnt0 = d_counts;
+            if (!cnt0) { HIP_TRY(h, M->stage[0].cnt.ensure((size_t)nk * 4)); cnt0 = M->stage[0].cnt.p; }
+            M->dev_counts = cnt0;
+            if (n_dir == 0) rc = pfc_eval_device(c, nk, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, cnt0, st0);
+            else rc = pfc_eval_dual_device_bp(c, nk, n_dir, d_ins_ids, d_pose, d_bp, d_twist, d_s, d_dpose, d_dtwist, d_ds, d_wrench, d_sdot,
+                                              d_dwrench, d_dsdot, cnt0, st0);
+            if (rc != PFC_OK) h->err = c->err;
+            return rc;
+        }
         pfc_multi::Stage &S = M->stage[k];
         const int dk = M->dev[k];
-        HIP_TRY(h, hipSetDevice(dk));
-        hipStream_t sk = c->stream;
         const size_t n = (size_t)nk;
-        HIP_TRY(h, S.in.ensure(n * 60)); HIP_TRY(h, S.out.ensure(n * 12)); HIP_TRY(h, S.cnt.ensure(n * 4));
-        const int *idk = nullptr;
-        if (d_ins_ids) { HIP_TRY(h, S.ids.ensure(n)); idk = S.ids.p; }
-        else { const int r2 = multi_dev_iota(h, k, n_items); if (r2 != PFC_OK) return r2; idk = S.iota.p + b0; }
-        HIP_TRY(h, hipStreamWaitEvent(sk, M->ev_fork, 0));
+        const int *idk = d_ins_ids ? S.ids.p : S.iota.p + b0;
         double *ip = S.in.p, *it = ip + n * 24, *is = it + n * 6, *ib = is + n * 6;
         if (d_ins_ids) HIP_TRY(h, multi_copy(S.ids.p, dk, d_ins_ids + b0, dev0, sizeof(int) * n, sk));
         HIP_TRY(h, multi_copy(ip, dk, d_pose + 24 * b0, dev0, sizeof(double) * n * 24, sk));
@@ -374,27 +422,14 @@ int multi_eval_device(pfc_context *h, int n_items, int n_dir, const int *d_ins_i
                 HIP_TRY(h, multi_copy(d_dsdot + 6 * nd * b0, dev0, dsdot, dk, sizeof(double) * n * nd * 6, sk));
             }
         }
-        if (rc != PFC_OK) { h->err = c->err; break; }
+        if (rc != PFC_OK) { h->err = c->err; return rc; }
         HIP_TRY(h, multi_copy(d_wrench + 6 * b0, dev0, ow, dk, sizeof(double) * n * 6, sk));
         HIP_TRY(h, multi_copy(d_sdot + 6 * b0, dev0, os, dk, sizeof(double) * n * 6, sk));
         if (d_counts) HIP_TRY(h, multi_copy(d_counts + 4 * b0, dev0, S.cnt.p, dk, sizeof(int) * n * 4, sk));
-        HIP_TRY(h, hipEventRecord(S.done, sk));
-    }
-    HIP_TRY(h, hipSetDevice(dev0));
+        return PFC_OK;
+    };
+    const int rc = multi_fan_out(h, st0, n_dir ? "pfc_eval_dual_device" : "pfc_eval_device", stage, run);
     if (rc != PFC_OK) return rc;
-    {   // shard 0: the caller's arrays in place, on the caller's stream
-        const int n0 = M->bound[1];
-        pfc_context *c = M->shard[0];
-        int *cnt0 = d_counts;
-        if (!cnt0) { HIP_TRY(h, M->stage[0].cnt.ensure((size_t)n0 * 4)); cnt0 = M->stage[0].cnt.p; }
-        M->dev_counts = cnt0;
-        if (n_dir == 0) rc = pfc_eval_device(c, n0, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, cnt0, st0);
-        else rc = pfc_eval_dual_device_bp(c, n0, n_dir, d_ins_ids, d_pose, d_bp, d_twist, d_s, d_dpose, d_dtwist, d_ds, d_wrench, d_sdot,
-                                          d_dwrench, d_dsdot, cnt0, st0);
-        if (rc != PFC_OK) { h->err = c->err; return rc; }
-    }
-    for (int k = 1; k < M->n_used; ++k)
-        if (M->bound[k + 1] > M->bound[k]) HIP_TRY(h, hipStreamWaitEvent(st0, M->stage[k].done, 0));
     M->dev_pending = true; M->dev_stream = st0; M->dev_reuse_ndir = n_dir;
     return PFC_OK;
 }
@@ -403,99 +438,68 @@ int multi_eval_dual_device_more(pfc_context *h, int n_dir, const double *d_dpose
                                 double *d_dwrench, double *d_dsdot, void *stream) {
     pfc_multi *M = h->multi;
     if (n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "pfc_eval_dual_device_more: n_dir must be in 1..16");
-    if (!M->dev_reuse_ok)
+    if (!M->dev_kept)
         return fail(h, PFC_ERR_STATE, "pfc_eval_dual_device_more: no checked pfc_eval_dual_device evaluation on this handle to extend");
     if (!d_dpose || !d_dtwist || !d_dwrench || !d_dsdot) return fail(h, PFC_ERR_BAD_ARG, "pfc_eval_dual_device_more: null buffer");
     const int dev0 = M->dev[0];
-    HIP_TRY(h, hipSetDevice(dev0));
-    MultiDeviceGuard back_to_first(dev0);
     hipStream_t st0 = stream ? (hipStream_t)stream : M->shard[0]->stream;
     const size_t nd = (size_t)n_dir;
-    if (M->n_used > 1) HIP_TRY(h, hipEventRecord(M->ev_fork, st0));
-    int rc = PFC_OK;
-    for (int k = 1; k < M->n_used; ++k) {
-        const size_t b0 = (size_t)M->bound[k];
-        const int nk = M->bound[k + 1] - (int)b0;
-        if (nk <= 0) continue;
+    auto stage = [&](int k) -> int {
+        pfc_multi::Stage &S = M->stage[k];
+        const size_t n = (size_t)(M->bound[k + 1] - M->bound[k]);
+        HIP_TRY(h, S.din.ensure(n * nd * 36)); HIP_TRY(h, S.dout.ensure(n * nd * 12));
+        return PFC_OK;
+    };
+    auto run = [&](int k, hipStream_t sk) -> int {
         pfc_context *c = M->shard[k];
+        if (k == 0) {
+            const int rc = pfc_eval_dual_device_more(c, n_dir, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, st0);
+            if (rc != PFC_OK) h->err = c->err;
+            return rc;
+        }
         pfc_multi::Stage &S = M->stage[k];
         const int dk = M->dev[k];
-        HIP_TRY(h, hipSetDevice(dk));
-        hipStream_t sk = c->stream;
-        const size_t n = (size_t)nk;
-        HIP_TRY(h, S.din.ensure(n * nd * 36)); HIP_TRY(h, S.dout.ensure(n * nd * 12));
+        const size_t b0 = (size_t)M->bound[k], n = (size_t)M->bound[k + 1] - b0;
         double *dp = S.din.p, *dt = dp + n * nd * 24, *dsd = dt + n * nd * 6, *dw = S.dout.p, *dsdot = dw + n * nd * 6;
-        HIP_TRY(h, hipStreamWaitEvent(sk, M->ev_fork, 0));
         HIP_TRY(h, multi_copy(dp, dk, d_dpose + 24 * nd * b0, dev0, sizeof(double) * n * nd * 24, sk));
         HIP_TRY(h, multi_copy(dt, dk, d_dtwist + 6 * nd * b0, dev0, sizeof(double) * n * nd * 6, sk));
         if (d_ds) HIP_TRY(h, multi_copy(dsd, dk, d_ds + 6 * nd * b0, dev0, sizeof(double) * n * nd * 6, sk));
-        rc = pfc_eval_dual_device_more(c, n_dir, dp, dt, d_ds ? dsd : nullptr, dw, dsdot, sk);
-        if (rc != PFC_OK) { h->err = c->err; (void)hipSetDevice(dev0); return rc; }
+        const int rc = pfc_eval_dual_device_more(c, n_dir, dp, dt, d_ds ? dsd : nullptr, dw, dsdot, sk);
+        if (rc != PFC_OK) { h->err = c->err; return rc; }
         HIP_TRY(h, multi_copy(d_dwrench + 6 * nd * b0, dev0, dw, dk, sizeof(double) * n * nd * 6, sk));
         HIP_TRY(h, multi_copy(d_dsdot + 6 * nd * b0, dev0, dsdot, dk, sizeof(double) * n * nd * 6, sk));
-        HIP_TRY(h, hipEventRecord(S.done, sk));
-    }
-    HIP_TRY(h, hipSetDevice(dev0));
-    rc = pfc_eval_dual_device_more(M->shard[0], n_dir, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, st0);
-    if (rc != PFC_OK) { h->err = M->shard[0]->err; return rc; }
-    for (int k = 1; k < M->n_used; ++k)
-        if (M->bound[k + 1] > M->bound[k]) HIP_TRY(h, hipStreamWaitEvent(st0, M->stage[k].done, 0));
+        return PFC_OK;
+    };
+    const int rc = multi_fan_out(h, st0, "pfc_eval_dual_device_more", stage, run);
+    if (rc != PFC_OK) return rc;
     M->dev_pending = true; M->dev_stream = st0; M->dev_reuse_ndir = -1;      // (-1: a further chunk -- the counters are not brought back again)
     return PFC_OK;
 }
 
 // pfc_local_jacobian_device over the shards: each builds the rows of L of its range on the value pass it keeps; shards 1.. write
-// theirs into staging on their device and copy them into d_L on the first.  One exit for errors: once shards have work enqueued
-// (their copies write into the caller's d_L, their staging may be reallocated by the next call), every stream that may hold some
-// is synchronised before the error is returned.
+// theirs into staging on their device and copy them into d_L on the first.
 int multi_local_jacobian_device(pfc_context *h, double *d_L, void *stream) {
     pfc_multi *M = h->multi;
-    if (!M->dev_reuse_ok)
+    if (!M->dev_kept)
         return fail(h, PFC_ERR_STATE, "pfc_local_jacobian_device: no checked pfc_eval_dual_device evaluation on this handle");
     if (!d_L) return fail(h, PFC_ERR_BAD_ARG, "pfc_local_jacobian_device: null buffer");
     const int dev0 = M->dev[0];
-    HIP_TRY(h, hipSetDevice(dev0));
-    MultiDeviceGuard back_to_first(dev0);
     hipStream_t st0 = stream ? (hipStream_t)stream : M->shard[0]->stream;
-    if (M->n_used > 1) HIP_TRY(h, hipEventRecord(M->ev_fork, st0));
-    int rc = PFC_OK, enq = 1;      // shards [1, enq) may have work enqueued
-    hipError_t e = hipSuccess;
-    for (int k = 1; k < M->n_used; ++k) {
-        const size_t b0 = (size_t)M->bound[k];
-        const int nk = M->bound[k + 1] - (int)b0;
-        if (nk <= 0) continue;
+    auto stage = [&](int k) -> int {
+        HIP_TRY(h, M->stage[k].dout.ensure((size_t)(M->bound[k + 1] - M->bound[k]) * kLjacSize));
+        return PFC_OK;
+    };
+    auto run = [&](int k, hipStream_t sk) -> int {
         pfc_context *c = M->shard[k];
-        pfc_multi::Stage &S = M->stage[k];
-        const int dk = M->dev[k];
-        hipStream_t sk = c->stream;
-        if ((e = hipSetDevice(dk)) != hipSuccess || (e = S.dout.ensure((size_t)nk * kLjacSize)) != hipSuccess ||
-            (e = hipStreamWaitEvent(sk, M->ev_fork, 0)) != hipSuccess)
-            break;
-        enq = k + 1;
-        rc = pfc_local_jacobian_device(c, S.dout.p, sk);
-        if (rc != PFC_OK) { h->err = c->err; break; }
-        if ((e = multi_copy(d_L + kLjacSize * b0, dev0, S.dout.p, dk, sizeof(double) * nk * kLjacSize, sk)) != hipSuccess ||
-            (e = hipEventRecord(S.done, sk)) != hipSuccess)
-            break;
-    }
-    if (rc == PFC_OK && e == hipSuccess && (e = hipSetDevice(dev0)) == hipSuccess) {
-        rc = pfc_local_jacobian_device(M->shard[0], d_L, st0);
-        if (rc != PFC_OK) h->err = M->shard[0]->err;
-        for (int k = 1; k < M->n_used && rc == PFC_OK && e == hipSuccess; ++k)
-            if (M->bound[k + 1] > M->bound[k]) e = hipStreamWaitEvent(st0, M->stage[k].done, 0);
-    }
-    if (rc == PFC_OK && e != hipSuccess) rc = fail(h, PFC_ERR_HIP, "pfc_local_jacobian_device: %s", hipGetErrorString(e));
-    if (rc != PFC_OK) {
-        for (int k = 1; k < enq; ++k) {
-            (void)hipSetDevice(M->dev[k]);
-            (void)hipStreamSynchronize(M->shard[k]->stream);
-            M->shard[k]->pending_more = false;
-        }
-        (void)hipSetDevice(dev0);
-        (void)hipStreamSynchronize(st0);
-        M->shard[0]->pending_more = false;
-        return rc;
-    }
+        double *out = k == 0 ? d_L : M->stage[k].dout.p;
+        const int rc = pfc_local_jacobian_device(c, out, sk);
+        if (rc != PFC_OK) { h->err = c->err; return rc; }
+        const size_t b0 = (size_t)M->bound[k], n = (size_t)M->bound[k + 1] - b0;
+        if (k > 0) HIP_TRY(h, multi_copy(d_L + kLjacSize * b0, dev0, out, M->dev[k], sizeof(double) * n * kLjacSize, sk));
+        return PFC_OK;
+    };
+    const int rc = multi_fan_out(h, st0, "pfc_local_jacobian_device", stage, run);
+    if (rc != PFC_OK) return rc;
     M->dev_pending = true; M->dev_stream = st0; M->dev_reuse_ndir = -1;      // pfc_check as after pfc_eval_dual_device_more
     return PFC_OK;
 }
@@ -530,10 +534,10 @@ int multi_check(pfc_context *h) {
     if (!more) M->counts_valid = rc == PFC_OK;
     if (rc == PFC_OK) {
         if (!more) multi_merge_stats(h);
-        M->dev_reuse_ok = more ? true : M->dev_reuse_ndir > 0;
-        if (M->dev_reuse_ok)
+        M->dev_kept = more ? true : M->dev_reuse_ndir > 0;
+        if (M->dev_kept)
             for (int k = 0; k < M->n_used; ++k)
-                if (M->bound[k + 1] > M->bound[k] && !M->shard[k]->dual_reuse_ok) M->dev_reuse_ok = false;
+                if (M->bound[k + 1] > M->bound[k] && !M->shard[k]->device_kept()) M->dev_kept = false;
     }
     return rc;
 }

@@ -284,6 +284,62 @@ def test_dual_device_entry_points_with_bp_pose_and_multi(pfc, O):
         m.close()
 
 
+@pytest.mark.parametrize("devs", [None, [0, 0]], ids=["single", "multi"])
+def test_option_change_ends_the_kept_value_pass(pfc, devs):
+    """Every pfc_set_option ends the value pass a checked pfc_eval_dual_device keeps -- also fixed_order set to the value it has --
+    on a single-device handle and on a {0, 0} handle: pfc_eval_dual_device_more and pfc_local_jacobian_device are refused with
+    PFC_ERR_STATE.  A new pfc_eval_dual_device, check and pfc_eval_dual_device_more then give what a fresh handle gives."""
+    import torch
+    C, L = pfc.configs, pfc._lib
+    w = C.c3_blob_tool(48, seed=9, n_div_blob=6, n_div_tool=4)
+    n, n_dir = w.n_items, 6
+    dev = torch.device("cuda:0")
+    t = lambda a, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
+    z = lambda *shape, dt=torch.float64: torch.zeros(shape, dtype=dt, device=dev)
+    T = dict(ids=t(w.ins_ids, torch.int32), pose=t(w.pose), twist=t(w.twist), s=t(w.s))
+    T["dp"], T["dt"], T["ds"] = (t(a) for a in _dual_inputs(w, n_dir, 31))
+    T["dp2"], T["dt2"], T["ds2"] = (t(a) for a in _dual_inputs(w, 3, 32))
+    st = torch.cuda.current_stream().cuda_stream
+
+    def first(m):
+        o = dict(w=z(n, 6), sd=z(n, 6), dw=z(n, n_dir, 6), dsd=z(n, n_dir, 6), c=z(n, 4, dt=torch.int32), dw2=z(n, 3, 6), dsd2=z(n, 3, 6))
+        for attempt in range(40):
+            m.eval_dual_device(n, n_dir, *[T[k].data_ptr() for k in ("ids", "pose", "twist", "s", "dp", "dt", "ds")],
+                               *[o[k].data_ptr() for k in ("w", "sd", "dw", "dsd", "c")], st)
+            if m.check() == L.OK:
+                break
+        return o
+
+    def more(m, o):
+        m.eval_dual_device_more(3, T["dp2"].data_ptr(), T["dt2"].data_ptr(), T["ds2"].data_ptr(), o["dw2"].data_ptr(), o["dsd2"].data_ptr(), st)
+
+    m = C.build_scenario(w, devices=devs)
+    d_L = z(n, 12, 36)
+    for name, value in (("fixed_order", 0), ("dual_reuse", 1)):      # both set to the value they have
+        o = first(m)
+        m.set_option(name, value)
+        with pytest.raises(L.PFCError) as ei:
+            more(m, o)
+        assert ei.value.status == L.ERR_STATE
+        with pytest.raises(L.PFCError) as ei:
+            m.local_jacobian_device(d_L.data_ptr(), st)
+        assert ei.value.status == L.ERR_STATE
+    o = first(m)
+    more(m, o)
+    assert m.check() == L.OK and m.last_dual_reused()
+    got = {k: v.cpu().numpy() for k, v in o.items()}
+    m.close()
+    f = C.build_scenario(w, devices=devs)
+    o = first(f)
+    more(f, o)
+    assert f.check() == L.OK
+    want = {k: v.cpu().numpy() for k, v in o.items()}
+    f.close()
+    assert np.array_equal(got["c"], want["c"])
+    for k, tol in (("w", 1e-10), ("sd", 1e-6), ("dw", 1e-8), ("dsd", 1e-5), ("dw2", 1e-8), ("dsd2", 1e-5)):
+        np.testing.assert_allclose(got[k], want[k], rtol=tol, atol=tol * max(np.abs(want[k]).max(), 1e-300))
+
+
 def test_multi_handle_dual_host_buffers(pfc):
     """pfc_eval_dual on {0, 0}: every shard runs the ordinary Dual entry point on its range; chunks at the same point reuse
     each shard's value pass once the ranges have settled."""
