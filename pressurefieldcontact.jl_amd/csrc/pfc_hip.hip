@@ -199,23 +199,107 @@ using namespace pfc;
 
 namespace {
 
+// ---- owning types -------------------------------------------------------------------------------------------------------
+// Every GPU resource the host code holds -- device blocks, pinned host blocks, events, streams, graph executables -- is a
+// member of one of these move-only types and is freed by its destructor: a context (pfc_context, pfc_multi) is torn down by
+// `delete`, with its device current and its streams synchronised (pfc_destroy, multi_destroy).  No other code frees anything.
+// PFC_LOG_ALLOC=1 logs every block with its address range when it is allocated and with its address when it is freed
+// (diagnostic: match a faulting address with the buffer it lies behind; tests/test_gpu_ownership.py pairs the two).
+inline bool log_alloc() { return std::getenv("PFC_LOG_ALLOC") != nullptr; }
+
+// A device block of cap elements.  ensure() grows it (the content is lost) and reports through `moved` whether it did.
 template <class T>
 struct DevBuf {
     T *p = nullptr;
     size_t cap = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    hipError_t ensure(size_t n, bool *moved = nullptr) { return grow(n, moved, false); }
+    // fine-grained memory (host stores through the PCIe BAR: pfc_context::bar_in)
+    hipError_t ensure_fine_grained(size_t n) { return grow(n, nullptr, true); }
+    void release() {
+        if (p) {
+            if (log_alloc()) std::fprintf(stderr, "pfc free %p\n", (void *)p);
+            (void)hipFree(p);
+        }
         p = nullptr; cap = 0;
-        hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        if (std::getenv("PFC_LOG_ALLOC"))      // diagnostic: match a faulting address with the buffer it lies behind
+    }
+
+private:
+    hipError_t grow(size_t n, bool *moved, bool fine) {
+        if (moved) *moved = false;
+        if (n <= cap) return hipSuccess;
+        release();
+        if (moved) *moved = true;
+        hipError_t e = fine ? hipExtMallocWithFlags((void **)&p, n * sizeof(T), hipDeviceMallocFinegrained) : hipMalloc((void **)&p, n * sizeof(T));
+        if (e == hipSuccess) cap = n; else p = nullptr;
+        if (log_alloc())
             std::fprintf(stderr, "pfc alloc %p .. %p (%zu bytes, element %zu)\n", (void *)p, (void *)((char *)p + n * sizeof(T)),
                          n * sizeof(T), sizeof(T));
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
+
+// A pinned host block of cap elements: grown to kSlack times what is asked for, never shrunk, zeroed when it is allocated
+// (completion words are polled from these blocks: never start from stale bytes).
+template <class T, int kSlack = 1>
+struct PinBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    ~PinBuf() { release(); }
+    hipError_t ensure(size_t n, bool *moved = nullptr) {
+        if (moved) *moved = false;
+        if (n <= cap) return hipSuccess;
+        release();
+        if (moved) *moved = true;
+        const size_t bytes = n * kSlack * sizeof(T);
+        hipError_t e = hipHostMalloc((void **)&p, bytes);
+        if (e == hipSuccess) { cap = n * kSlack; std::memset(p, 0, bytes); } else p = nullptr;
+        if (log_alloc()) std::fprintf(stderr, "pfc pinned %p .. %p\n", (void *)p, (void *)((char *)p + bytes));
+        return e;
+    }
+
+private:
+    void release() {
+        if (p) {
+            if (log_alloc()) std::fprintf(stderr, "pfc unpinned %p\n", (void *)p);
+            (void)hipHostFree(p);
+        }
+        p = nullptr; cap = 0;
+    }
+};
+
+// An event, stream or graph executable; converts to the raw handle for the runtime's calls, put() is where a create call
+// writes a new one.
+template <class H, hipError_t (*Destroy)(H)>
+struct Owned {
+    H h = nullptr;
+    Owned() = default;
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    Owned(Owned &&o) noexcept : h(o.h) { o.h = nullptr; }
+    Owned &operator=(Owned &&o) noexcept {
+        if (this != &o) { reset(); h = o.h; o.h = nullptr; }
+        return *this;
+    }
+    ~Owned() { reset(); }
+    void reset() { if (h) (void)Destroy(h); h = nullptr; }
+    H *put() { reset(); return &h; }
+    operator H() const { return h; }
+};
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using GraphExec = Owned<hipGraphExec_t, hipGraphExecDestroy>;
 
 struct HostMesh {
     int n_pt = 0, n_tri = 0, n_tet = 0, n_node = 0, n_leaf = 0, depth = 0;
@@ -244,23 +328,30 @@ struct pfc_context {
     // Broadphase pose of the evaluation being enqueued (device-visible, n_items x 24, only x_r1_r2 is read) or null: set by the
     // pfc_eval_dual*_bp entry points around the value pass (record_eval, enqueue_fused)
     const double *bp_dev = nullptr;
-    void *pin_bp = nullptr;              // pinned host copy of the last broadphase pose block (pfc_eval_dual_bp)
-    size_t pin_bp_cap = 0;
+    // The streams come first: members are destroyed in reverse order, so everything made against a stream (events, graph
+    // executables, buffers its work may touch) goes before it.
+    Stream stream;
+    Stream twin_stream;                  // created right behind `stream` (the runtime deals streams out to its hardware queues in order of creation), moved into the twin by make_twin
+    PinBuf<char, 2> pin_bp;              // pinned host copy of the last broadphase pose block (pfc_eval_dual_bp)
     int pin_bp_n = 0;                    // items it holds (0: the last host-buffer Dual evaluation had none)
     bool team_owner = false;             // this handle holds its device's team slot (team_acquire)
     int opt_team_fault = -1;             // diagnostic option "team_fault": rank of every team that simulates a timed-out wait
     int opt_dual_fold = 1;               // option "dual_fold": pass B of the Dual evaluation formed inside pass A (tri-tet scenes, batched value pass)
     int opt_fused_f32 = 1;               // option "fused_f32": single-precision SAT filter in the one-launch kernel (A/B knob; same results)
     std::string err;
-    hipStream_t stream = nullptr;
     std::vector<HostMesh> meshes;
     std::vector<InsDev> ins;
+    // The mesh and instruction tables the kernels read: the handle's own (own_* below), or -- a twin -- its parent's, borrowed.
     MeshDev *d_meshes = nullptr;
+    InsDev *d_ins = nullptr;
+    InsFull *d_insfull = nullptr;        // small scenes: one self-contained record per instruction (pfc_fused.h)
+    DevBuf<MeshDev> own_meshes;
+    DevBuf<InsDev> own_ins;
+    DevBuf<InsFull> own_insfull;
     // every mesh's device records (NodeF, NodeRec, TriRec / TetRec, raw eps) are carved out of ONE allocation, the
     // single-precision nodes of all meshes first (a pile of 128 meshes used to make ~600 small hipMallocs; measured neutral
     // for C5's evaluation time, kept for the contiguous hot set and the one free)
-    char *mesh_arena = nullptr;
-    InsDev *d_ins = nullptr;
+    DevBuf<char> mesh_arena;
     int max_levels = 1;
     int max_leaves = 2;                // largest n_leaf(mesh_1) + n_leaf(mesh_2) over the instructions
     bool any_bristle = false, any_tet_tet = false;
@@ -275,22 +366,19 @@ struct pfc_context {
     DevBuf<unsigned> status;
     DevBuf<unsigned long long> stamps;   // diagnostic builds
     DevBuf<int> tail;                    // packed status, totals, counters (block 0 of k_final)
-    int *h_tail = nullptr;               // pinned host mirror of tail
+    PinBuf<int> h_tail;                  // pinned host mirror of tail
     const int *tail_host = nullptr;      // set by pfc_eval: the tail is already on its way to this pinned block (with the outputs)
     int *tail_dev = nullptr;             // set by pfc_eval for a small scene: k_final packs straight into pinned host memory
-    size_t h_tail_cap = 0;
-    void *pin_in = nullptr, *pin_out = nullptr;   // pinned staging of the host-buffer path
-    size_t pin_in_cap = 0, pin_out_cap = 0;
+    PinBuf<char, 2> pin_in, pin_out;     // pinned staging of the host-buffer path
     // Inputs of a very small scene written by the host straight into DEVICE memory (fine-grained allocation, reachable through
     // the PCIe BAR when the device has a large one): the one-launch kernel's first two dependent reads -- instruction id, then
     // the instruction's record -- start from HBM instead of from host memory (scripts/micro/bar_probe.hip: launch + two
     // dependent reads + completion word 7.5 -> 6.2 us).  Host stores into it are write-combined: written once per evaluation,
     // never read back; they leave the core with the locked update of the queue's write index that every launch begins with.
-    void *bar_in = nullptr;
-    void *bar_din = nullptr;                      // the same for the seeds of a small-scene Dual evaluation (up to kBarKeys (item, direction) pairs)
+    DevBuf<char> bar_in;
+    DevBuf<char> bar_din;                         // the same for the seeds of a small-scene Dual evaluation (up to kBarKeys (item, direction) pairs)
     int bar_state = 0;                            // 0: not probed, 1: in use, -1: no large BAR / allocation failed / PFC_NO_BAR_INPUTS
-    void *pin_din = nullptr, *pin_dout = nullptr; // pinned blocks of the small-scene Dual path (partials in / out)
-    size_t pin_din_cap = 0, pin_dout_cap = 0;
+    PinBuf<char, 2> pin_din, pin_dout;            // pinned blocks of the small-scene Dual path (partials in / out)
     long long dual_hint = -1;                     // contributing pairs of the last Dual evaluation (-1: none yet)
     bool pending_dual = false;                    // pfc_eval_dual_device enqueued: pfc_check also checks the speculative polygon capacity
     bool pending_dual_hyb = false;                // ... through the small-scene kernel (value pass + hand-over) and the batched Dual passes
@@ -326,7 +414,7 @@ struct pfc_context {
     DevBuf<double> dual_zero;                     // zeros standing in for a null d_ds
     unsigned long long epoch = 0;        // bumped whenever a device work buffer is reallocated
     // captured launch sequence (hipGraph) of the last evaluation shape
-    hipGraphExec_t gexec[2] = {nullptr, nullptr};   // [0] plain evaluation, [1] with the contributing-pair list (Dual)
+    GraphExec gexec[2];                  // [0] plain evaluation, [1] with the contributing-pair list (Dual)
     struct GraphKey {
         int n_items, levels, L, debug, bristle, surv;
         const void *p[9];
@@ -335,7 +423,7 @@ struct pfc_context {
     } gkey[2] = {};
     bool ghave[2] = {false, false};
     // value pass + Dual passes of a small scene as ONE graph (eval_dual_small)
-    hipGraphExec_t dgexec = nullptr;
+    GraphExec dgexec;
     struct DualGraphKey { GraphKey v; int n_dir; size_t bound; const void *din, *dout; } dgkey = {};
     bool dghave = false;
     bool want_surv = false;   // the narrowphase also lists the contributing candidates (pfc_eval_dual)
@@ -378,7 +466,7 @@ struct pfc_context {
         return false;
     }
     long long last_tslots = 0;         // traction slots used by the last evaluation (>= traction points)
-    hipEvent_t ev[EV_COUNT] = {};
+    Event ev[EV_COUNT];
     bool ev_valid = false;
     // Large batches are evaluated as two concurrent halves: a second set of work buffers on a second stream, so that
     // the broadphase of one half (vector-ALU bound) shares the CUs with the narrowphase of the other (parked on
@@ -386,10 +474,8 @@ struct pfc_context {
     pfc_context *twin = nullptr;
     bool is_twin = false;
     // small scenes: one fused kernel, one workgroup per item (pfc_fused.h)
-    InsFull *d_insfull = nullptr;
     DevBuf<int> fout;                  // per item 8 ints (status, counts) of the fused kernel (device-buffer entry point)
-    int *h_fout = nullptr;             // pinned host mirror
-    size_t h_fout_cap = 0;
+    PinBuf<int> h_fout;                // pinned host mirror
     int *fout_dev = nullptr;           // set by pfc_eval: the kernel writes its per-item block straight into pinned host memory
     const int *fout_host = nullptr;    //   ... and this is where the host reads it
     int opt_fused = 1;                 // option "fused"
@@ -423,8 +509,8 @@ struct pfc_context {
     int opt_team = 48;                 // option "team": big pairs (more leaves than one workgroup takes) run as teams of up to this many workgroups (0: batched path; <= kTeamMaxWg = 48: s_team and the gather's per-thread granule count are sized from it).  Eight single C3 poses, mean / worst us (an earlier build that allowed 64): 64: 113 / 122, 48: 112 / 118, 32: 113 / 122, 24: 126 / 190, 16: 178 / 249, batched 132 / 136 (scripts/lat_c3_poses.py)
     DevBuf<unsigned long long> team;   // team partial sums: kTeamMaxBlocks x 3 x 2 kTeamSlots granules, zeroed once (tags are launch sequence numbers >= 1)
     DevBuf<int> emit_ctr;              // pair counter of the fused kernel's hand-over to the batched Dual passes
-    int *h_emit = nullptr;             // pinned mirror
-    unsigned *h_more = nullptr;        // pinned: status word of the Dual passes of pfc_eval_dual_device_more (device word: status.p + 1)
+    PinBuf<int> h_emit;                // pinned mirror
+    PinBuf<unsigned> h_more;           // pinned: status word of the Dual passes of pfc_eval_dual_device_more (device word: status.p + 1)
     bool fu_emit = false;              // set by eval_dual_hybrid around enqueue_fused
     int dual_fused_skip = 0;           // Dual evaluations left for which the in-kernel Dual passes stay off (an item had too many polygons)
     const double *fu_dpose = nullptr, *fu_dtwist = nullptr;    // set by eval_dual_fused around enqueue_fused
@@ -437,9 +523,8 @@ struct pfc_context {
     int split_n0 = 0;                  // items in the first half of the pending evaluation (0: not split)
     bool in_split = false;             // this context's launches are one half of a two-half evaluation (set while they are enqueued)
     int last_parts = 1;                // 2 if the last checked evaluation ran as two halves
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join0 = nullptr;
+    Event ev_fork, ev_join, ev_join0;
     int twin_queue_fallback = 0;         // make_twin: 0 the two streams run side by side as created; 1 the twin's stream was re-created with another priority because they did not; 2 they still do not
-    hipStream_t twin_stream = nullptr;   // created right behind `stream` (the runtime deals streams out to its hardware queues in order of creation), handed to the twin
     // pfc_contact_surface (pfc_surface.h): buffers of its own, so that no captured evaluation graph sees them move
     DevBuf<long long> surf_cnt, surf_off, surf_out;   // per list slot {polygon, points} and their exclusive scan; packed status block
     DevBuf<double> surf_part;                         // per candidate partial sums
@@ -451,8 +536,7 @@ struct pfc_context {
     DevBuf<int> ljac_ids;
     DevBuf<unsigned long long> surf_keys[2];
     DevBuf<char> surf_tmp;                            // rocPRIM scan / sort
-    long long *h_surf = nullptr;                      // pinned mirror of surf_out
-    size_t h_surf_cap = 0;
+    PinBuf<long long> h_surf;                         // pinned mirror of surf_out
     bool pending_surface = false;
     bool surf_whole_list = false;       // an item had more candidates than the segment sort takes: the whole list is sorted from then on
     bool surf_cap_short = false;        // the last checked surface call failed only for the caller's capacities
@@ -537,30 +621,42 @@ hipError_t copy_sync(pfc_context *h, void *dst, const void *src, size_t bytes, h
 
 size_t fixed_fric_cap(size_t ccap, int n_items) { return 2 * (ccap / 64 + 1) + (size_t)n_items + 64; }      // (FixedSink of k_fric_fixed)
 
+// A work buffer that kernels inside a captured launch sequence are given (the value graphs of enqueue_eval, the one-graph Dual
+// path of eval_dual_small): captured graphs bake its address in, so when it moves, the epoch that is part of their keys moves
+// on and the next evaluation records its graph again -- whichever path reallocates (the two-stage Dual path, which replays no
+// graph itself, sizes the dual_* buffers the one-graph path's kernels were captured with).  A call that reallocates nothing
+// leaves the epoch alone: a steady-state evaluation keeps replaying its graph.
+template <class T>
+hipError_t ensure_graphed(pfc_context *h, DevBuf<T> &b, size_t n, bool *moved = nullptr) {
+    bool m = false;
+    const hipError_t e = b.ensure(n, &m);
+    if (m) ++h->epoch;
+    if (moved) *moved = m;
+    return e;
+}
+
+// ... and one the kernels rely on being zero on entry (they leave it so).  They run on non-blocking streams (the handle's, the
+// twin's or the caller's), which are not ordered against the legacy null stream: a new block is cleared on the handle's stream
+// and waited for.
+template <class T>
+hipError_t ensure_zeroed(pfc_context *h, DevBuf<T> &b, size_t n) {
+    bool moved = false;
+    hipError_t e = ensure_graphed(h, b, n, &moved);
+    if (e != hipSuccess || !moved) return e;
+    if ((e = hipMemsetAsync(b.p, 0, sizeof(T) * b.cap, h->stream)) != hipSuccess) return e;
+    return hipStreamSynchronize(h->stream);
+}
+
 hipError_t ensure_work(pfc_context *h, int n_items) {
     hipError_t e;
-    const size_t caps0[] = {h->items.cap, h->acc.cap, h->res.cap, h->icnt.cap, h->ctr.cap, h->frontier[0].cap,
-                            h->frontier[1].cap, h->cand.cap, h->clip_n.cap, h->trac_item.cap, h->trac_d.cap, h->rec.cap,
-                            h->tail.cap, h->poly_item.cap, h->poly.cap, h->pcnt.cap, h->poly_cand.cap};
-    if ((e = h->items.ensure(n_items)) != hipSuccess) return e;
-    if ((e = h->acc.ensure((size_t)n_items * kAccStride)) != hipSuccess) return e;
-    if ((e = h->res.ensure((size_t)n_items * kResStride)) != hipSuccess) return e;
-    if ((e = h->icnt.ensure((size_t)n_items * 4)) != hipSuccess) return e;
-    {
-        const size_t c0 = h->ctr.cap, s0 = h->status.cap;
-        if ((e = h->ctr.ensure((size_t)h->max_levels + 12)) != hipSuccess) return e;
-        if ((e = h->status.ensure(4)) != hipSuccess) return e;
-        // The kernels rely on these being zero on entry and run on non-blocking streams (the handle's, the twin's or
-        // the caller's), which are not ordered against the legacy null stream: clear on the handle's stream and wait.
-        bool cleared = false;
-        if (h->ctr.cap != c0) { if ((e = hipMemsetAsync(h->ctr.p, 0, sizeof(int) * h->ctr.cap, h->stream)) != hipSuccess) return e; cleared = true; }
-        if (h->status.cap != s0) { if ((e = hipMemsetAsync(h->status.p, 0, sizeof(unsigned) * h->status.cap, h->stream)) != hipSuccess) return e; cleared = true; }
-        const size_t r0 = h->rgn.cap;
-        if ((e = h->rgn.ensure((size_t)kRgn * kRgnStride)) != hipSuccess) return e;
-        if (h->rgn.cap != r0) { if ((e = hipMemsetAsync(h->rgn.p, 0, sizeof(int) * h->rgn.cap, h->stream)) != hipSuccess) return e; cleared = true; }
-        if (cleared && (e = hipStreamSynchronize(h->stream)) != hipSuccess) return e;
-    }
-    if ((e = h->stamps.ensure(16)) != hipSuccess) return e;
+    if ((e = ensure_graphed(h, h->items, n_items)) != hipSuccess) return e;
+    if ((e = ensure_graphed(h, h->acc, (size_t)n_items * kAccStride)) != hipSuccess) return e;
+    if ((e = ensure_graphed(h, h->res, (size_t)n_items * kResStride)) != hipSuccess) return e;
+    if ((e = ensure_graphed(h, h->icnt, (size_t)n_items * 4)) != hipSuccess) return e;
+    if ((e = ensure_zeroed(h, h->ctr, (size_t)h->max_levels + 12)) != hipSuccess) return e;
+    if ((e = ensure_zeroed(h, h->status, 4)) != hipSuccess) return e;
+    if ((e = ensure_zeroed(h, h->rgn, (size_t)kRgn * kRgnStride)) != hipSuccess) return e;
+    if ((e = ensure_graphed(h, h->stamps, 16)) != hipSuccess) return e;
     size_t f = h->fcap ? h->fcap : 1u << 16;
     while (f < (size_t)n_items * 8) f *= 2;
     size_t c = h->ccap ? h->ccap : 1u << 16;
@@ -569,51 +665,41 @@ hipError_t ensure_work(pfc_context *h, int n_items) {
     size_t rc = h->rcap ? h->rcap : 1u << 12;
     while (rc < c / 32 + (size_t)n_items * 2) rc *= 2;   // about one record per wave round and item boundary
     h->fcap = f; h->ccap = c; h->tcap = t; h->rcap = rc;
-    if ((e = h->rec.ensure(rc * (h->opt_fixed_order ? kRecStrideFixed : kRecStride))) != hipSuccess) return e;
+    if ((e = ensure_graphed(h, h->rec, rc * (h->opt_fixed_order ? kRecStrideFixed : kRecStride))) != hipSuccess) return e;
     if (h->opt_fixed_order) {
-        if ((e = h->det.ensure((size_t)n_items * 3)) != hipSuccess) return e;
-        if ((e = h->vfx_rec.ensure(fixed_fric_cap(c, n_items) * kSinkStride)) != hipSuccess) return e;
-        if ((e = h->vfx_head.ensure((size_t)n_items + 2)) != hipSuccess) return e;
-        if ((e = h->sort_keys[0].ensure(c)) != hipSuccess) return e;
-        if ((e = h->sort_keys[1].ensure(c)) != hipSuccess) return e;
+        if ((e = ensure_graphed(h, h->det, (size_t)n_items * 3)) != hipSuccess) return e;
+        if ((e = ensure_graphed(h, h->vfx_rec, fixed_fric_cap(c, n_items) * kSinkStride)) != hipSuccess) return e;
+        if ((e = ensure_graphed(h, h->vfx_head, (size_t)n_items + 2)) != hipSuccess) return e;
+        if ((e = ensure_graphed(h, h->sort_keys[0], c)) != hipSuccess) return e;
+        if ((e = ensure_graphed(h, h->sort_keys[1], c)) != hipSuccess) return e;
         int ba, bb;
         const int bits = pfc_sort_key_bits(n_items, h->max_elem1, h->max_elem2, &ba, &bb);
-        if ((e = h->canon_off.ensure((size_t)n_items + 1)) != hipSuccess) return e;
-        if ((e = h->canon_fill.ensure((size_t)n_items)) != hipSuccess) return e;
-        if ((e = h->canon_item.ensure(c)) != hipSuccess) return e;
+        if ((e = ensure_graphed(h, h->canon_off, (size_t)n_items + 1)) != hipSuccess) return e;
+        if ((e = ensure_graphed(h, h->canon_fill, (size_t)n_items)) != hipSuccess) return e;
+        if ((e = ensure_graphed(h, h->canon_item, c)) != hipSuccess) return e;
         if (h->sort_tmp_for != c || h->sort_tmp_bits != bits || h->sort_tmp_items < n_items) {
             size_t bytes = 0;
             if ((e = pfc_sort_temp_bytes(c, bits > 64 ? 64 : bits, &bytes)) != hipSuccess) return e;      // (covers the index sort too)
-            if ((e = h->sort_tmp.ensure(bytes ? bytes : 1)) != hipSuccess) return e;
+            if ((e = ensure_graphed(h, h->sort_tmp, bytes ? bytes : 1)) != hipSuccess) return e;
             h->sort_tmp_for = c; h->sort_tmp_bits = bits; h->sort_tmp_items = n_items;
         }
     }
-    if ((e = h->frontier[0].ensure(f)) != hipSuccess) return e;
-    if ((e = h->frontier[1].ensure(f)) != hipSuccess) return e;
-    if ((e = h->cand.ensure(c)) != hipSuccess) return e;
-    if ((e = h->clip_n.ensure(c)) != hipSuccess) return e;
-    if ((e = h->surv.ensure(c)) != hipSuccess) return e;
+    if ((e = ensure_graphed(h, h->frontier[0], f)) != hipSuccess) return e;
+    if ((e = ensure_graphed(h, h->frontier[1], f)) != hipSuccess) return e;
+    if ((e = ensure_graphed(h, h->cand, c)) != hipSuccess) return e;
+    if ((e = ensure_graphed(h, h->clip_n, c)) != hipSuccess) return e;
+    if ((e = ensure_graphed(h, h->surv, c)) != hipSuccess) return e;
     {   // kept polygons: bristle items always (friction pass), every item when the clip-only narrowphase + k_integ run
         const size_t pc = poly_cap(c);
-        if ((e = h->poly_item.ensure(pc)) != hipSuccess) return e;
-        if ((e = h->poly.ensure(pc * 34)) != hipSuccess) return e;
-        if ((e = h->pcnt.ensure(pc / kNpBlock + 1)) != hipSuccess) return e;
-        if (h->want_surv && (e = h->poly_cand.ensure(pc)) != hipSuccess) return e;
+        if ((e = ensure_graphed(h, h->poly_item, pc)) != hipSuccess) return e;
+        if ((e = ensure_graphed(h, h->poly, pc * 34)) != hipSuccess) return e;
+        if ((e = ensure_graphed(h, h->pcnt, pc / kNpBlock + 1)) != hipSuccess) return e;
+        if (h->want_surv && (e = ensure_graphed(h, h->poly_cand, pc)) != hipSuccess) return e;
     }
-    if ((e = h->trac_item.ensure(t)) != hipSuccess) return e;
-    if ((e = h->trac_d.ensure(t * 8)) != hipSuccess) return e;
-    if ((e = h->tail.ensure((size_t)h->max_levels + 40)) != hipSuccess) return e;
-    if (h->h_tail_cap < (size_t)h->max_levels + 40) {
-        if (h->h_tail) (void)hipHostFree(h->h_tail);
-        h->h_tail = nullptr; h->h_tail_cap = 0;
-        if ((e = hipHostMalloc((void **)&h->h_tail, sizeof(int) * ((size_t)h->max_levels + 40))) != hipSuccess) return e;
-        h->h_tail_cap = (size_t)h->max_levels + 40;
-    }
-    const size_t caps1[] = {h->items.cap, h->acc.cap, h->res.cap, h->icnt.cap, h->ctr.cap, h->frontier[0].cap,
-                            h->frontier[1].cap, h->cand.cap, h->clip_n.cap, h->trac_item.cap, h->trac_d.cap, h->rec.cap,
-                            h->tail.cap, h->poly_item.cap, h->poly.cap, h->pcnt.cap, h->poly_cand.cap};
-    for (size_t k = 0; k < sizeof caps0 / sizeof caps0[0]; ++k)
-        if (caps0[k] != caps1[k]) { ++h->epoch; break; }
+    if ((e = ensure_graphed(h, h->trac_item, t)) != hipSuccess) return e;
+    if ((e = ensure_graphed(h, h->trac_d, t * 8)) != hipSuccess) return e;
+    if ((e = ensure_graphed(h, h->tail, (size_t)h->max_levels + 40)) != hipSuccess) return e;
+    if ((e = h->h_tail.ensure((size_t)h->max_levels + 40)) != hipSuccess) return e;
     if (h->opt_poison) {    // every evaluation starts from lists full of entries that must never be followed
         if ((e = hipMemsetAsync(h->frontier[0].p, 0xFF, sizeof(WorkRec) * h->frontier[0].cap, h->stream)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(h->frontier[1].p, 0xFF, sizeof(WorkRec) * h->frontier[1].cap, h->stream)) != hipSuccess) return e;
@@ -894,7 +980,7 @@ int enqueue_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double
     const int levels = eff_levels(h);
     const bool prof = h->opt_profile != 0;
     if (prof && !h->ev[0])
-        for (int k = 0; k < EV_COUNT; ++k) HIP_TRY(h, hipEventCreate(&h->ev[k]));
+        for (int k = 0; k < EV_COUNT; ++k) HIP_TRY(h, hipEventCreate(h->ev[k].put()));
     const int L = bfs_levels_for(h, n_items, levels);
     bool use_graph = h->opt_graph && !prof;
 #ifdef PFC_STAMPS
@@ -915,7 +1001,7 @@ int enqueue_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double
         key.p[5] = d_sdot; key.p[6] = d_counts; key.p[7] = h->tail_dev; key.p[8] = h->bp_dev; key.stream = (void *)st; key.epoch = h->epoch;
         const int gi = key.surv;   // Radau alternates value and Dual evaluations: both graphs stay instantiated
         if (!h->ghave[gi] || std::memcmp(&key, &h->gkey[gi], sizeof key) != 0) {
-            if (h->gexec[gi]) { (void)hipGraphExecDestroy(h->gexec[gi]); h->gexec[gi] = nullptr; }
+            h->gexec[gi].reset();
             h->ghave[gi] = false;
             hipGraph_t graph = nullptr;
             HIP_TRY(h, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
@@ -923,7 +1009,7 @@ int enqueue_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double
             hipError_t e = hipStreamEndCapture(st, &graph);
             if (rc != PFC_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
             if (e != hipSuccess) return fail(h, PFC_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
-            e = hipGraphInstantiate(&h->gexec[gi], graph, nullptr, nullptr, 0);
+            e = hipGraphInstantiate(h->gexec[gi].put(), graph, nullptr, nullptr, 0);
             (void)hipGraphDestroy(graph);
             if (e != hipSuccess) return fail(h, PFC_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
             h->gkey[gi] = key; h->ghave[gi] = true;
@@ -944,11 +1030,11 @@ int check_one(pfc_context *h) {
     if (!h->pending) return PFC_OK;
     const int levels = h->last_levels;
     const size_t n_tail = (size_t)levels + 12 + 12;
-    const int *tail = h->h_tail;
+    const int *tail = h->h_tail.p;
     if (h->tail_host) {     // pfc_eval: one D2H copy carries the tail and the outputs
         tail = h->tail_host; h->tail_host = nullptr;
     } else {
-        HIP_TRY(h, hipMemcpyAsync(h->h_tail, h->tail.p, sizeof(int) * n_tail, hipMemcpyDeviceToHost, h->last_stream));
+        HIP_TRY(h, hipMemcpyAsync(h->h_tail.p, h->tail.p, sizeof(int) * n_tail, hipMemcpyDeviceToHost, h->last_stream));
     }
     HIP_TRY(h, hipStreamSynchronize(h->last_stream));
     h->pending = false;
@@ -1109,10 +1195,7 @@ int enqueue_fused(pfc_context *h, int n_items, const int *d_ins_ids, const doubl
         a.fout = h->fout_dev;
     } else {
         HIP_TRY(h, h->fout.ensure((size_t)kFusedMaxItems * 8));
-        if (!h->h_fout) {
-            HIP_TRY(h, hipHostMalloc((void **)&h->h_fout, sizeof(int) * kFusedMaxItems * 8));
-            h->h_fout_cap = (size_t)kFusedMaxItems * 8;
-        }
+        HIP_TRY(h, h->h_fout.ensure((size_t)kFusedMaxItems * 8));
         a.fout = h->fout.p;
     }
     if (++h->fused_seq == 0) h->fused_seq = 1;
@@ -1162,8 +1245,8 @@ int check_fused(pfc_context *h) {
     const int n = h->last_n_items;
     const int *fo = h->fout_host;
     if (!fo) {
-        HIP_TRY(h, hipMemcpyAsync(h->h_fout, h->fout.p, sizeof(int) * 8 * (size_t)n, hipMemcpyDeviceToHost, h->last_stream));
-        fo = h->h_fout;
+        HIP_TRY(h, hipMemcpyAsync(h->h_fout.p, h->fout.p, sizeof(int) * 8 * (size_t)n, hipMemcpyDeviceToHost, h->last_stream));
+        fo = h->h_fout.p;
         HIP_TRY(h, hipStreamSynchronize(h->last_stream));
     } else {
         // The kernel wrote its results straight into pinned host memory; every workgroup ends with a system-scope
@@ -1243,12 +1326,11 @@ int make_twin(pfc_context *h) {
     t->ins = h->ins; t->d_meshes = h->d_meshes; t->d_ins = h->d_ins; t->max_levels = h->max_levels;
     t->max_leaves = h->max_leaves; t->max_elem1 = h->max_elem1; t->max_elem2 = h->max_elem2;
     t->any_bristle = h->any_bristle; t->any_tet_tet = h->any_tet_tet; t->opt_split_min = 0;
-    t->stream = h->twin_stream; h->twin_stream = nullptr;
-    if ((!t->stream && hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess) ||
-        hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_join0, hipEventDisableTiming) != hipSuccess) {
-        if (t->stream) (void)hipStreamDestroy(t->stream);
+    t->stream = std::move(h->twin_stream);
+    if ((!t->stream && hipStreamCreateWithFlags(t->stream.put(), hipStreamNonBlocking) != hipSuccess) ||
+        hipEventCreateWithFlags(h->ev_fork.put(), hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(h->ev_join.put(), hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(h->ev_join0.put(), hipEventDisableTiming) != hipSuccess) {
         delete t;
         return fail(h, PFC_ERR_HIP, "could not create the second stream");
     }
@@ -1257,11 +1339,10 @@ int make_twin(pfc_context *h) {
     h->twin_queue_fallback = 0;
     if (!std::getenv("PFC_NO_QUEUE_TEST") && !streams_overlap(h, h->stream, t->stream)) {
         int lo = 0, hi = 0;
-        hipStream_t s2 = nullptr;
+        Stream s2;
         if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo &&
-            hipStreamCreateWithPriority(&s2, hipStreamNonBlocking, hi) == hipSuccess) {
-            (void)hipStreamDestroy(t->stream);
-            t->stream = s2;
+            hipStreamCreateWithPriority(s2.put(), hipStreamNonBlocking, hi) == hipSuccess) {
+            t->stream = std::move(s2);
             h->twin_queue_fallback = streams_overlap(h, h->stream, t->stream) ? 1 : 2;      // 2: still serial (reported, not fatal)
         } else {
             h->twin_queue_fallback = 2;
@@ -1276,17 +1357,6 @@ int make_twin(pfc_context *h) {
 // =================================================================================================================
 // C ABI
 // =================================================================================================================
-// The one-graph Dual path replays kernels with the addresses of the dual_* buffers baked in: a reallocation anywhere
-// (also by the two-stage path, which sizes them from the value pass) must invalidate that graph, i.e. bump the epoch
-// that is part of its key.
-template <class T>
-hipError_t ensure_dual(pfc_context *h, DevBuf<T> &b, size_t n) {
-    const T *p0 = b.p;
-    const hipError_t e = b.ensure(n);
-    if (b.p != p0) ++h->epoch;
-    return e;
-}
-
 #include "pfc_multi.h"
 
 extern "C" {
@@ -1314,8 +1384,8 @@ int pfc_create(int device, pfc_handle *out) {
     pfc_context *h = new (std::nothrow) pfc_context();
     if (!h) return PFC_ERR_NOMEM;
     h->device = device;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return PFC_ERR_HIP; }
-    if (hipStreamCreateWithFlags(&h->twin_stream, hipStreamNonBlocking) != hipSuccess) h->twin_stream = nullptr;   // (make_twin creates one then)
+    if (hipStreamCreateWithFlags(h->stream.put(), hipStreamNonBlocking) != hipSuccess) { delete h; return PFC_ERR_HIP; }
+    if (hipStreamCreateWithFlags(h->twin_stream.put(), hipStreamNonBlocking) != hipSuccess) h->twin_stream.reset();   // (make_twin creates one then)
     { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess) h->n_cu = cu; }
     *out = h;
     return PFC_OK;
@@ -1342,7 +1412,7 @@ int pfc_create_multi(const int *devices, int n_devices, pfc_handle *out) {
         rc = pfc_create(devices[k], &c);
         if (rc != PFC_OK) break;
         M->shard.push_back(c);
-        if (hipEventCreateWithFlags(&M->stage[k].done, hipEventDisableTiming) != hipSuccess) rc = PFC_ERR_HIP;
+        if (hipEventCreateWithFlags(M->stage[k].done.put(), hipEventDisableTiming) != hipSuccess) rc = PFC_ERR_HIP;
         // direct peer copies between the first device and this one where the hardware allows it (xGMI); failures -- same device,
         // already enabled, no peer path -- leave the staged copy of hipMemcpyPeerAsync
         if (devices[k] != devices[0]) {
@@ -1359,7 +1429,7 @@ int pfc_create_multi(const int *devices, int n_devices, pfc_handle *out) {
                 if (hipDeviceCanAccessPeer(&can, devices[0], devices[k]) == hipSuccess && can) (void)hipDeviceEnablePeerAccess(devices[k], 0);
                 (void)hipGetLastError();
             }
-        if (hipEventCreateWithFlags(&M->ev_fork, hipEventDisableTiming) != hipSuccess) rc = PFC_ERR_HIP;
+        if (hipEventCreateWithFlags(M->ev_fork.put(), hipEventDisableTiming) != hipSuccess) rc = PFC_ERR_HIP;
     }
     if (rc == PFC_OK) {
         for (int k = 1; k < n_devices; ++k) {
@@ -1369,7 +1439,7 @@ int pfc_create_multi(const int *devices, int n_devices, pfc_handle *out) {
             w->th = std::thread(multi_worker_loop, w, devices[k]);
         }
     }
-    if (rc != PFC_OK) { multi_destroy(h); delete h; return rc; }
+    if (rc != PFC_OK) { pfc_destroy(h); return rc; }
     *out = h;
     return PFC_OK;
 }
@@ -1383,55 +1453,8 @@ void pfc_destroy(pfc_handle h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if ((h->pending || h->pending_surface) && h->last_stream) (void)hipStreamSynchronize(h->last_stream);   // an unchecked pfc_eval_device on the caller's stream
     team_release(h);
-    if (h->pin_bp) (void)hipHostFree(h->pin_bp);
-    if (h->twin) { pfc_destroy(h->twin); h->twin = nullptr; }
-    if (h->twin_stream) { (void)hipStreamDestroy(h->twin_stream); h->twin_stream = nullptr; }
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->ev_join0) (void)hipEventDestroy(h->ev_join0);
-    if (h->is_twin) { h->d_meshes = nullptr; h->d_ins = nullptr; h->d_insfull = nullptr; }   // owned by the parent
-    if (h->mesh_arena) (void)hipFree(h->mesh_arena);      // the meshes' d_* pointers point into it
-    if (h->d_meshes) (void)hipFree(h->d_meshes);
-    if (h->d_ins) (void)hipFree(h->d_ins);
-    if (h->d_insfull) (void)hipFree(h->d_insfull);
-    if (h->h_fout) (void)hipHostFree(h->h_fout);
-    if (h->h_emit) (void)hipHostFree(h->h_emit);
-    if (h->h_more) (void)hipHostFree(h->h_more);
-    h->emit_ctr.release();
-    h->fout.release(); h->team.release();
-    h->items.release(); h->frontier[0].release(); h->frontier[1].release(); h->cand.release();
-    h->clip_n.release(); h->icnt.release(); h->trac_item.release(); h->acc.release(); h->res.release();
-    h->fx_rec.release(); h->fx_head.release(); h->vfx_rec.release(); h->vfx_head.release();
-    h->canon_off.release(); h->canon_fill.release(); h->canon_item.release();
-    h->det.release(); h->sort_keys[0].release(); h->sort_keys[1].release(); h->sort_tmp.release();
-    h->trac_d.release(); h->rec.release(); h->ctr.release(); h->status.release(); h->stamps.release();
-    h->h_pose.release();
-    for (int k = 0; k < EV_COUNT; ++k)
-        if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
-    for (int gi = 0; gi < 2; ++gi)
-        if (h->gexec[gi]) (void)hipGraphExecDestroy(h->gexec[gi]);
-    if (h->dgexec) (void)hipGraphExecDestroy(h->dgexec);
-    if (h->h_tail) (void)hipHostFree(h->h_tail);
-    if (h->pin_in) (void)hipHostFree(h->pin_in);
-    if (h->bar_in) (void)hipFree(h->bar_in);
-    if (h->bar_din) (void)hipFree(h->bar_din);
-    if (h->pin_out) (void)hipHostFree(h->pin_out);
-    if (h->pin_din) (void)hipHostFree(h->pin_din);
-    if (h->pin_dout) (void)hipHostFree(h->pin_dout);
-    h->tail.release();
-    h->rgn.release(); h->poly_item.release(); h->pcnt.release(); h->poly_cand.release(); h->poly.release(); h->surv.release(); h->scat_d.release(); h->scat_i.release();
-    h->sdual_d.release(); h->sdual_w.release(); h->sdual_i.release(); h->sdual_tmp.release();
-    h->dual_poly.release(); h->dual_pkey.release(); h->dual_sel.release(); h->dual_flag.release();
-    h->dual_in.release(); h->dual_acc.release(); h->dual_res.release(); h->dual_out.release(); h->dual_zero.release();
-    h->surf_cnt.release(); h->surf_off.release(); h->surf_out.release(); h->surf_part.release(); h->surf_seg.release();
-    h->surf_canon_off.release(); h->surf_canon_fill.release(); h->surf_canon_item.release();
-    h->surf_keys[0].release(); h->surf_keys[1].release(); h->surf_tmp.release();
-    h->surf_hl.release(); h->surf_hi.release(); h->surf_hd.release(); h->surf_in.release();
-    h->sfric_mom.release(); h->sfric_sum.release(); h->sfric_res.release(); h->sfric_hd.release();
-    h->ljac_seed.release(); h->ljac_out.release(); h->ljac_io.release(); h->ljac_ids.release();
-    if (h->h_surf) (void)hipHostFree(h->h_surf);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    if (h->twin) pfc_destroy(h->twin);
+    delete h;      // every buffer, event, graph and stream is a member that frees itself; the streams go last
 }
 
 const char *pfc_last_error(pfc_handle h) { return h ? h->err.c_str() : "null handle"; }
@@ -1443,9 +1466,9 @@ int pfc_add_mesh(pfc_handle h, int n_pt, const double *xyz, int n_tri, const int
     if (h->multi) {      // replicated on every shard (the ids agree: same sequence of calls)
         int id0 = -1;
         for (size_t k = 0; k < h->multi->shard.size(); ++k) {
-            const int id = pfc_add_mesh(h->multi->shard[k], n_pt, xyz, n_tri, tri, n_tet, tet, eps, Ebar, n_node, node_c, node_e, node_R,
-                                        node_child, node_leaf);
-            if (id < 0) { h->err = h->multi->shard[k]->err; return id; }
+            const int id = on_shard(h, h->multi->shard[k], [&](pfc_context *c) {
+                return pfc_add_mesh(c, n_pt, xyz, n_tri, tri, n_tet, tet, eps, Ebar, n_node, node_c, node_e, node_R, node_child, node_leaf); }, true);
+            if (id < 0) return id;
             if (k == 0) id0 = id;
         }
         return id0;
@@ -1586,8 +1609,8 @@ int pfc_add_instruction(pfc_handle h, int id_1, int id_2, double chi, int n_quad
     if (h->multi) {
         int id0 = -1;
         for (size_t k = 0; k < h->multi->shard.size(); ++k) {
-            const int id = pfc_add_instruction(h->multi->shard[k], id_1, id_2, chi, n_quad, model, params);
-            if (id < 0) { h->err = h->multi->shard[k]->err; return id; }
+            const int id = on_shard(h, h->multi->shard[k], [&](pfc_context *c) { return pfc_add_instruction(c, id_1, id_2, chi, n_quad, model, params); }, true);
+            if (id < 0) return id;
             if (k == 0) id0 = id;
         }
         return id0;
@@ -1640,42 +1663,40 @@ int pfc_finalize(pfc_handle h) {
         for (HostMesh &m : h->meshes)
             total += up(sizeof(NodeRec) * m.nodes.size()) + (m.n_tri ? up(sizeof(TriRec) * m.n_tri)
                                                                       : up(sizeof(TetRec) * m.n_tet) + up(sizeof(double) * 4 * m.n_tet));
-        if (total) HIP_TRY(h, hipMalloc((void **)&h->mesh_arena, total));
+        HIP_TRY(h, h->mesh_arena.ensure(total));
         size_t off = 0;
-        for (HostMesh &m : h->meshes) { m.d_nodesf = (NodeF *)(h->mesh_arena + off); off += up(sizeof(NodeF) * m.nodesf.size()); }
+        for (HostMesh &m : h->meshes) { m.d_nodesf = (NodeF *)(h->mesh_arena.p + off); off += up(sizeof(NodeF) * m.nodesf.size()); }
         for (HostMesh &m : h->meshes) {
-            m.d_nodes = (NodeRec *)(h->mesh_arena + off); off += up(sizeof(NodeRec) * m.nodes.size());
-            if (m.n_tri) { m.d_tri = (TriRec *)(h->mesh_arena + off); off += up(sizeof(TriRec) * m.n_tri); }
+            m.d_nodes = (NodeRec *)(h->mesh_arena.p + off); off += up(sizeof(NodeRec) * m.nodes.size());
+            if (m.n_tri) { m.d_tri = (TriRec *)(h->mesh_arena.p + off); off += up(sizeof(TriRec) * m.n_tri); }
             else {
-                m.d_tet = (TetRec *)(h->mesh_arena + off); off += up(sizeof(TetRec) * m.n_tet);
-                m.d_tet_eps = (double *)(h->mesh_arena + off); off += up(sizeof(double) * 4 * m.n_tet);
+                m.d_tet = (TetRec *)(h->mesh_arena.p + off); off += up(sizeof(TetRec) * m.n_tet);
+                m.d_tet_eps = (double *)(h->mesh_arena.p + off); off += up(sizeof(double) * 4 * m.n_tet);
             }
         }
     }
     for (size_t k = 0; k < h->meshes.size(); ++k) {
         HostMesh &m = h->meshes[k];
-        double *d_xyz = nullptr, *d_eps = nullptr;
-        int *d_idx = nullptr;
+        DevBuf<double> d_xyz, d_eps;      // the raw vertices / pressures and the element indices: until the records are made
+        DevBuf<int> d_idx;
         HIP_TRY(h, copy_sync(h, m.d_nodes, m.nodes.data(), sizeof(NodeRec) * m.nodes.size(), hipMemcpyHostToDevice));
         HIP_TRY(h, copy_sync(h, m.d_nodesf, m.nodesf.data(), sizeof(NodeF) * m.nodesf.size(), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMalloc((void **)&d_xyz, sizeof(double) * m.xyz.size()));
-        HIP_TRY(h, copy_sync(h, d_xyz, m.xyz.data(), sizeof(double) * m.xyz.size(), hipMemcpyHostToDevice));
+        HIP_TRY(h, d_xyz.ensure(m.xyz.size()));
+        HIP_TRY(h, copy_sync(h, d_xyz.p, m.xyz.data(), sizeof(double) * m.xyz.size(), hipMemcpyHostToDevice));
         if (m.n_tri) {
-            HIP_TRY(h, hipMalloc((void **)&d_idx, sizeof(int) * m.tri.size()));
-            HIP_TRY(h, copy_sync(h, d_idx, m.tri.data(), sizeof(int) * m.tri.size(), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(k_prep_tri, dim3((m.n_tri + 127) / 128), dim3(128), 0, h->stream, m.n_tri, d_xyz, d_idx, m.d_tri);
+            HIP_TRY(h, d_idx.ensure(m.tri.size()));
+            HIP_TRY(h, copy_sync(h, d_idx.p, m.tri.data(), sizeof(int) * m.tri.size(), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(k_prep_tri, dim3((m.n_tri + 127) / 128), dim3(128), 0, h->stream, m.n_tri, d_xyz.p, d_idx.p, m.d_tri);
         } else {
-            HIP_TRY(h, hipMalloc((void **)&d_idx, sizeof(int) * m.tet.size()));
-            HIP_TRY(h, copy_sync(h, d_idx, m.tet.data(), sizeof(int) * m.tet.size(), hipMemcpyHostToDevice));
-            HIP_TRY(h, hipMalloc((void **)&d_eps, sizeof(double) * m.eps.size()));
-            HIP_TRY(h, copy_sync(h, d_eps, m.eps.data(), sizeof(double) * m.eps.size(), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(k_prep_tet, dim3((m.n_tet + 127) / 128), dim3(128), 0, h->stream, m.n_tet, d_xyz, d_eps, d_idx,
+            HIP_TRY(h, d_idx.ensure(m.tet.size()));
+            HIP_TRY(h, copy_sync(h, d_idx.p, m.tet.data(), sizeof(int) * m.tet.size(), hipMemcpyHostToDevice));
+            HIP_TRY(h, d_eps.ensure(m.eps.size()));
+            HIP_TRY(h, copy_sync(h, d_eps.p, m.eps.data(), sizeof(double) * m.eps.size(), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(k_prep_tet, dim3((m.n_tet + 127) / 128), dim3(128), 0, h->stream, m.n_tet, d_xyz.p, d_eps.p, d_idx.p,
                                m.d_tet, m.d_tet_eps, h->status.p);
         }
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(d_xyz); (void)hipFree(d_idx);
-        if (d_eps) (void)hipFree(d_eps);
         md[k].nodes = m.d_nodes; md[k].nodesf = m.d_nodesf; md[k].tri = m.d_tri; md[k].tet = m.d_tet; md[k].tet_eps = m.d_tet_eps; md[k].Ebar = m.Ebar; md[k].cmax = m.cmax;
         md[k].n_tri = m.n_tri; md[k].n_tet = m.n_tet; md[k].n_node = m.n_node; md[k].depth = m.depth;
     }
@@ -1683,7 +1704,8 @@ int pfc_finalize(pfc_handle h) {
     HIP_TRY(h, copy_sync(h, &status, h->status.p, sizeof(unsigned), hipMemcpyDeviceToHost));
     if (status & kStNonFinite) return fail(h, PFC_ERR_NONFINITE, "singular tetrahedron (non-finite zeta transform)");
     if (!md.empty()) {
-        HIP_TRY(h, hipMalloc((void **)&h->d_meshes, sizeof(MeshDev) * md.size()));
+        HIP_TRY(h, h->own_meshes.ensure(md.size()));
+        h->d_meshes = h->own_meshes.p;
         HIP_TRY(h, copy_sync(h, h->d_meshes, md.data(), sizeof(MeshDev) * md.size(), hipMemcpyHostToDevice));
     }
     h->max_levels = 1;
@@ -1708,7 +1730,8 @@ int pfc_finalize(pfc_handle h) {
     if (3 * h->max_levels + 3 > kDfsStack - 128 || 3 * h->max_levels + 3 > kDfsStack32 - 1024)
         return fail(h, PFC_ERR_BAD_ARG, "OBB trees too deep (depth sum %d): rebuild them balanced", h->max_levels - 1);
     if (!h->ins.empty()) {
-        HIP_TRY(h, hipMalloc((void **)&h->d_ins, sizeof(InsDev) * h->ins.size()));
+        HIP_TRY(h, h->own_ins.ensure(h->ins.size()));
+        h->d_ins = h->own_ins.p;
         HIP_TRY(h, copy_sync(h, h->d_ins, h->ins.data(), sizeof(InsDev) * h->ins.size(), hipMemcpyHostToDevice));
         // one self-contained record per instruction for the fused small-scene kernel
         std::vector<InsFull> full(h->ins.size());
@@ -1726,7 +1749,8 @@ int pfc_finalize(pfc_handle h) {
             f.cmax12 = m1.cmax + m2.cmax;
             full[k] = f;
         }
-        HIP_TRY(h, hipMalloc((void **)&h->d_insfull, sizeof(InsFull) * full.size()));
+        HIP_TRY(h, h->own_insfull.ensure(full.size()));
+        h->d_insfull = h->own_insfull.p;
         HIP_TRY(h, copy_sync(h, h->d_insfull, full.data(), sizeof(InsFull) * full.size(), hipMemcpyHostToDevice));
     }
     h->finalized = true;
@@ -1861,12 +1885,7 @@ int surface_enqueue(pfc_context *h, int n_items, const int *d_ins_ids, const dou
     const int levels = eff_levels(h);
     const int n_ctr = levels + 12;
     HIP_TRY(h, h->surf_out.ensure((size_t)n_ctr + 3));
-    if (h->h_surf_cap < (size_t)n_ctr + 3) {
-        if (h->h_surf) (void)hipHostFree(h->h_surf);
-        h->h_surf = nullptr; h->h_surf_cap = 0;
-        HIP_TRY(h, hipHostMalloc((void **)&h->h_surf, sizeof(long long) * ((size_t)n_ctr + 3)));
-        h->h_surf_cap = (size_t)n_ctr + 3;
-    }
+    HIP_TRY(h, h->h_surf.ensure((size_t)n_ctr + 3));
     int *ccount = h->ctr.p, *next_seed = h->ctr.p + 2, *ucount = h->ctr.p + 4, *fcount = h->ctr.p + 6;   // (record_eval's layout)
 
     EvalArgs ea;
@@ -1914,7 +1933,7 @@ int surface_enqueue(pfc_context *h, int n_items, const int *d_ins_ids, const dou
     }
     hipLaunchKernelGGL(k_surf_final, dim3(1), dim3(64), 0, st, h->ctr.p, n_ctr, h->status.p, (const long long *)h->surf_off.p, (int)c,
                        h->surf_out.p);
-    HIP_TRY(h, hipMemcpyAsync(h->h_surf, h->surf_out.p, sizeof(long long) * ((size_t)n_ctr + 3), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(h->h_surf.p, h->surf_out.p, sizeof(long long) * ((size_t)n_ctr + 3), hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipGetLastError());
     h->pending_surface = true; h->last_stream = st; h->surf_n_ctr = n_ctr;
     h->surf_cap_poly = cap_poly; h->surf_cap_trac = cap_trac;
@@ -1928,7 +1947,7 @@ int check_surface(pfc_context *h) {
     h->pending_surface = false;
     h->surf_cap_short = false;
     HIP_TRY(h, hipStreamSynchronize(h->last_stream));
-    const long long *o = h->h_surf;
+    const long long *o = h->h_surf.p;
     const unsigned status = (unsigned)o[0];
     const long long *ctr = o + 3;
     long long fpeak = 0;
@@ -1958,14 +1977,6 @@ int check_surface(pfc_context *h) {
     return PFC_OK;
 }
 
-// The context a surface call runs on: the handle's own, or the first device's of a multi-device handle (whose pending
-// device-pointer evaluation and Dual reuse end here, as with any other evaluation).
-pfc_context *surface_ctx(pfc_context *h) {
-    if (!h->multi) return h;
-    h->multi->dev_pending = false; h->multi->dev_kept = false;
-    return h->multi->shard[0];
-}
-
 int surface_args(pfc_context *h, int n_items, const void *ins_ids, const void *pose, const void *twist, long long cap_poly,
                  long long cap_trac, const void *poly_off, const void *poly_idx, const void *poly_xyz, const void *poly_trac,
                  const void *trac, const void *summary, const void *totals) {
@@ -1985,7 +1996,7 @@ int surface_args(pfc_context *h, int n_items, const void *ins_ids, const void *p
 namespace {
 
 // The host-pointer form of both surface calls; fo (pfc_contact_surface_fric) holds host pointers here: s, fric, fric_summary, stiff.
-int surface_host(pfc_context *hh, pfc_context *h, int n_items, const int *ins_ids, const double *pose, const double *twist, long long cap_poly,
+int surface_host(pfc_context *h, int n_items, const int *ins_ids, const double *pose, const double *twist, long long cap_poly,
                  long long cap_trac, long long *poly_off, int *poly_idx, double *poly_xyz, long long *poly_trac, double *trac,
                  double *summary, int *counts, long long *totals, const SurfFricOut *fo) {
     HIP_TRY(h, hipSetDevice(h->device));
@@ -2027,7 +2038,7 @@ int surface_host(pfc_context *hh, pfc_context *h, int n_items, const int *ins_id
                              i_idx, d_xyz, l_ptr, d_trac, d_sum, i_cnt, l_tot, h->stream, fo ? &dfo : nullptr);
         if (rc == PFC_OK) rc = check_surface(h);
         if (rc == PFC_ERR_OVERFLOW && h->surf_cap_short) {
-            tot_p = h->h_surf[1]; tot_t = h->h_surf[2];
+            tot_p = h->h_surf.p[1]; tot_t = h->h_surf.p[2];
             if (tot_p <= cap_poly && tot_t <= cap_trac) {      // the staging was short, not the caller's buffers
                 if ((size_t)tot_p > h->surf_hcap_poly) h->surf_hcap_poly = (size_t)tot_p;
                 if ((size_t)tot_t > h->surf_hcap_trac) h->surf_hcap_trac = (size_t)tot_t;
@@ -2039,7 +2050,7 @@ int surface_host(pfc_context *hh, pfc_context *h, int n_items, const int *ins_id
         }
         if (rc != PFC_ERR_OVERFLOW) break;
     }
-    if (rc != PFC_OK && !(rc == PFC_ERR_OVERFLOW && h->surf_cap_short)) { if (hh != h) hh->err = h->err; return rc; }
+    if (rc != PFC_OK && !(rc == PFC_ERR_OVERFLOW && h->surf_cap_short)) return rc;
     const long long *l_off = h->surf_hl.p, *l_tot = l_off + n + 1, *l_ptr = l_tot + 2;
     const size_t dp = (size_t)(cap_poly < (long long)h->surf_hcap_poly ? cap_poly : (long long)h->surf_hcap_poly);
     const int *i_cnt = h->surf_hi.p, *i_idx = i_cnt + 4 * n;
@@ -2054,7 +2065,7 @@ int surface_host(pfc_context *hh, pfc_context *h, int n_items, const int *ins_id
         if (fo->stiff) HIP_TRY(h, hipMemcpyAsync(fo->stiff, f_sum + kFricOut * n, sizeof(double) * kStiffOut * n, hipMemcpyDeviceToHost, h->stream));
     }
     if (rc == PFC_OK) {
-        tot_p = h->h_surf[1]; tot_t = h->h_surf[2];
+        tot_p = h->h_surf.p[1]; tot_t = h->h_surf.p[2];
         HIP_TRY(h, hipMemcpyAsync(poly_trac, l_ptr, sizeof(long long) * ((size_t)tot_p + 1), hipMemcpyDeviceToHost, h->stream));
         if (tot_p > 0) {
             HIP_TRY(h, hipMemcpyAsync(poly_idx, i_idx, sizeof(int) * 3 * (size_t)tot_p, hipMemcpyDeviceToHost, h->stream));
@@ -2066,7 +2077,6 @@ int surface_host(pfc_context *hh, pfc_context *h, int n_items, const int *ins_id
                                       h->stream));
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (rc != PFC_OK && hh != h) hh->err = h->err;
     return rc;
 }
 
@@ -2079,39 +2089,45 @@ int surface_fric_args(pfc_context *h, int n_items, long long cap_trac, const voi
 
 }  // namespace
 
-int pfc_contact_surface(pfc_handle hh, int n_items, const int *ins_ids, const double *pose, const double *twist, long long cap_poly,
+int pfc_contact_surface(pfc_handle h, int n_items, const int *ins_ids, const double *pose, const double *twist, long long cap_poly,
                         long long cap_trac, long long *poly_off, int *poly_idx, double *poly_xyz, long long *poly_trac, double *trac,
                         double *summary, int *counts, long long *totals) {
-    if (!hh) return PFC_ERR_BAD_ARG;
-    pfc_context *h = surface_ctx(hh);
-    int rc = surface_args(h, n_items, ins_ids, pose, twist, cap_poly, cap_trac, poly_off, poly_idx, poly_xyz, poly_trac, trac, summary, totals);
-    if (rc != PFC_OK) { if (hh != h) hh->err = h->err; return rc; }
-    return surface_host(hh, h, n_items, ins_ids, pose, twist, cap_poly, cap_trac, poly_off, poly_idx, poly_xyz, poly_trac, trac, summary, counts,
-                        totals, nullptr);
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return surface_ctx(h, [&](pfc_context *c) {
+            return pfc_contact_surface(c, n_items, ins_ids, pose, twist, cap_poly, cap_trac, poly_off, poly_idx, poly_xyz, poly_trac, trac, summary,
+                                       counts, totals); });
+    const int rc = surface_args(h, n_items, ins_ids, pose, twist, cap_poly, cap_trac, poly_off, poly_idx, poly_xyz, poly_trac, trac, summary, totals);
+    if (rc != PFC_OK) return rc;
+    return surface_host(h, n_items, ins_ids, pose, twist, cap_poly, cap_trac, poly_off, poly_idx, poly_xyz, poly_trac, trac, summary, counts, totals,
+                        nullptr);
 }
 
-int pfc_contact_surface_fric(pfc_handle hh, int n_items, const int *ins_ids, const double *pose, const double *twist, const double *s,
+int pfc_contact_surface_fric(pfc_handle h, int n_items, const int *ins_ids, const double *pose, const double *twist, const double *s,
                              long long cap_poly, long long cap_trac, long long *poly_off, int *poly_idx, double *poly_xyz, long long *poly_trac,
                              double *trac, double *fric, double *summary, double *fric_summary, double *stiff, int *counts, long long *totals) {
-    if (!hh) return PFC_ERR_BAD_ARG;
-    pfc_context *h = surface_ctx(hh);
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return surface_ctx(h, [&](pfc_context *c) {
+            return pfc_contact_surface_fric(c, n_items, ins_ids, pose, twist, s, cap_poly, cap_trac, poly_off, poly_idx, poly_xyz, poly_trac, trac,
+                                            fric, summary, fric_summary, stiff, counts, totals); });
     int rc = surface_args(h, n_items, ins_ids, pose, twist, cap_poly, cap_trac, poly_off, poly_idx, poly_xyz, poly_trac, trac, summary, totals);
     if (rc == PFC_OK) rc = surface_fric_args(h, n_items, cap_trac, fric, fric_summary);
-    if (rc != PFC_OK) { if (hh != h) hh->err = h->err; return rc; }
+    if (rc != PFC_OK) return rc;
     SurfFricOut fo;
     fo.s = s; fo.fric = fric; fo.fric_summary = fric_summary; fo.stiff = stiff;
-    return surface_host(hh, h, n_items, ins_ids, pose, twist, cap_poly, cap_trac, poly_off, poly_idx, poly_xyz, poly_trac, trac, summary, counts,
-                        totals, &fo);
+    return surface_host(h, n_items, ins_ids, pose, twist, cap_poly, cap_trac, poly_off, poly_idx, poly_xyz, poly_trac, trac, summary, counts, totals,
+                        &fo);
 }
 
-int pfc_contact_surface_device(pfc_handle hh, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
-                               long long cap_poly, long long cap_trac, long long *d_poly_off, int *d_poly_idx, double *d_poly_xyz,
-                               long long *d_poly_trac, double *d_trac, double *d_summary, int *d_counts, long long *d_totals, void *stream) {
-    if (!hh) return PFC_ERR_BAD_ARG;
-    pfc_context *h = surface_ctx(hh);
+// The device-pointer form of both surface calls; fo (pfc_contact_surface_fric_device) holds device pointers.
+static int surface_device(pfc_context *h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist, long long cap_poly,
+                          long long cap_trac, long long *d_poly_off, int *d_poly_idx, double *d_poly_xyz, long long *d_poly_trac,
+                          double *d_trac, double *d_summary, int *d_counts, long long *d_totals, void *stream, const SurfFricOut *fo) {
     int rc = surface_args(h, n_items, d_ins_ids, d_pose, d_twist, cap_poly, cap_trac, d_poly_off, d_poly_idx, d_poly_xyz, d_poly_trac,
                           d_trac, d_summary, d_totals);
-    if (rc != PFC_OK) { if (hh != h) hh->err = h->err; return rc; }
+    if (rc == PFC_OK && fo) rc = surface_fric_args(h, n_items, cap_trac, fo->fric, fo->fric_summary);
+    if (rc != PFC_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     if (n_items == 0) {
@@ -2122,38 +2138,31 @@ int pfc_contact_surface_device(pfc_handle hh, int n_items, const int *d_ins_ids,
         HIP_TRY(h, hipMemsetAsync(d_totals, 0, sizeof(long long) * 2, st));
         return PFC_OK;
     }
-    rc = surface_enqueue(h, n_items, d_ins_ids, d_pose, d_twist, cap_poly, cap_trac, d_poly_off, d_poly_idx, d_poly_xyz, d_poly_trac,
-                         d_trac, d_summary, d_counts, d_totals, st);
-    if (rc != PFC_OK && hh != h) hh->err = h->err;
-    return rc;
+    return surface_enqueue(h, n_items, d_ins_ids, d_pose, d_twist, cap_poly, cap_trac, d_poly_off, d_poly_idx, d_poly_xyz, d_poly_trac,
+                           d_trac, d_summary, d_counts, d_totals, st, fo);
 }
 
-int pfc_contact_surface_fric_device(pfc_handle hh, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
+int pfc_contact_surface_device(pfc_handle h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
+                               long long cap_poly, long long cap_trac, long long *d_poly_off, int *d_poly_idx, double *d_poly_xyz,
+                               long long *d_poly_trac, double *d_trac, double *d_summary, int *d_counts, long long *d_totals, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    auto call = [&](pfc_context *c) {
+        return surface_device(c, n_items, d_ins_ids, d_pose, d_twist, cap_poly, cap_trac, d_poly_off, d_poly_idx, d_poly_xyz, d_poly_trac, d_trac,
+                              d_summary, d_counts, d_totals, stream, nullptr); };
+    return h->multi ? surface_ctx(h, call) : call(h);
+}
+
+int pfc_contact_surface_fric_device(pfc_handle h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
                                     const double *d_s, long long cap_poly, long long cap_trac, long long *d_poly_off, int *d_poly_idx,
                                     double *d_poly_xyz, long long *d_poly_trac, double *d_trac, double *d_fric, double *d_summary,
                                     double *d_fric_summary, double *d_stiff, int *d_counts, long long *d_totals, void *stream) {
-    if (!hh) return PFC_ERR_BAD_ARG;
-    pfc_context *h = surface_ctx(hh);
-    int rc = surface_args(h, n_items, d_ins_ids, d_pose, d_twist, cap_poly, cap_trac, d_poly_off, d_poly_idx, d_poly_xyz, d_poly_trac,
-                          d_trac, d_summary, d_totals);
-    if (rc == PFC_OK) rc = surface_fric_args(h, n_items, cap_trac, d_fric, d_fric_summary);
-    if (rc != PFC_OK) { if (hh != h) hh->err = h->err; return rc; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    if (n_items == 0) {
-        new_value_pass(h);
-        h->pin_in_pt = {}; h->pin_din_pt = {};
-        HIP_TRY(h, hipMemsetAsync(d_poly_off, 0, sizeof(long long), st));
-        HIP_TRY(h, hipMemsetAsync(d_poly_trac, 0, sizeof(long long), st));
-        HIP_TRY(h, hipMemsetAsync(d_totals, 0, sizeof(long long) * 2, st));
-        return PFC_OK;
-    }
+    if (!h) return PFC_ERR_BAD_ARG;
     SurfFricOut fo;
     fo.s = d_s; fo.fric = d_fric; fo.fric_summary = d_fric_summary; fo.stiff = d_stiff;
-    rc = surface_enqueue(h, n_items, d_ins_ids, d_pose, d_twist, cap_poly, cap_trac, d_poly_off, d_poly_idx, d_poly_xyz, d_poly_trac,
-                         d_trac, d_summary, d_counts, d_totals, st, &fo);
-    if (rc != PFC_OK && hh != h) hh->err = h->err;
-    return rc;
+    auto call = [&](pfc_context *c) {
+        return surface_device(c, n_items, d_ins_ids, d_pose, d_twist, cap_poly, cap_trac, d_poly_off, d_poly_idx, d_poly_xyz, d_poly_trac, d_trac,
+                              d_summary, d_counts, d_totals, stream, &fo); };
+    return h->multi ? surface_ctx(h, call) : call(h);
 }
 
 int pfc_check(pfc_handle h) {
@@ -2162,16 +2171,14 @@ int pfc_check(pfc_handle h) {
         pfc_context *c0 = h->multi->shard[0];
         if (!c0->pending_surface) return multi_check(h);
         (void)hipSetDevice(c0->device);
-        const int rc = check_surface(c0);
-        if (rc != PFC_OK) h->err = c0->err;
-        return rc;
+        return on_first_shard(h, check_surface);
     }
     HIP_TRY(h, hipSetDevice(h->device));
     if (h->pending_surface) return check_surface(h);
     if (h->pending_more) {       // Dual passes on a value pass that was checked before: nothing to read back
         h->pending_more = false;
         HIP_TRY(h, hipStreamSynchronize(h->last_stream));
-        if (h->h_more && (h->h_more[0] & kStHole)) {
+        if (h->h_more.p && (h->h_more.p[0] & kStHole)) {
             end_kept_pass(h);
             return fail(h, PFC_ERR_STATE, "internal error: a Dual pass on a reused value pass read a work-list slot out of range");
         }
@@ -2186,8 +2193,8 @@ int pfc_check(pfc_handle h) {
             h->dual_dev_hyb_skip = 64;
             return fail(h, PFC_ERR_OVERFLOW, "hand-over list of the small-scene kernel overflowed: re-issue (batched path)");
         }
-        if ((unsigned)h->h_emit[2] & kStHole) return fail(h, PFC_ERR_STATE, "internal error: a work-list slot was read before it was written");
-        const long long pairs_h = h->h_emit[0];
+        if ((unsigned)h->h_emit.p[2] & kStHole) return fail(h, PFC_ERR_STATE, "internal error: a work-list slot was read before it was written");
+        const long long pairs_h = h->h_emit.p[0];
         h->dual_hint = pairs_h;
         const int cpw_h = 64 / h->pending_ndir;
         if ((h->any_bristle || h->opt_fixed_order) && (size_t)((pairs_h + cpw_h - 1) / cpw_h) * 64 + 64 > h->pending_dpcap)
@@ -2202,7 +2209,7 @@ int pfc_check(pfc_handle h) {
     if (rc != PFC_OK || !dual) return rc;
     // did the kept Dual polygons of pfc_eval_dual_device fit?  (contributing pairs: the counter next to the polygon total
     // in the packed tail, which check_eval has just brought over)
-    const long long pairs = h->h_tail[12 + (((h->last_levels + 9) & ~1) + 1)];
+    const long long pairs = h->h_tail.p[12 + (((h->last_levels + 9) & ~1) + 1)];
     h->dual_hint = pairs;
     const int cpw = 64 / h->pending_ndir;
     if ((h->any_bristle || h->opt_fixed_order) && (size_t)((pairs + cpw - 1) / cpw) * 64 + 64 > h->pending_dpcap)
@@ -2222,10 +2229,9 @@ static bool bar_ready(pfc_context *h) {
 #if defined(__x86_64__)      // the ordering argument (a locked instruction drains the write-combining buffers) is x86's
         int large_bar = 0;
         if (!std::getenv("PFC_NO_BAR_INPUTS") && hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, h->device) == hipSuccess &&
-            large_bar && hipExtMallocWithFlags(&h->bar_in, kBarItems * (36 * sizeof(double) + sizeof(int)), hipDeviceMallocFinegrained) == hipSuccess) {
-            if (hipExtMallocWithFlags(&h->bar_din, kBarKeys * 36 * sizeof(double), hipDeviceMallocFinegrained) == hipSuccess) h->bar_state = 1;
-            else { (void)hipFree(h->bar_in); h->bar_in = nullptr; }
-        }
+            large_bar && h->bar_in.ensure_fine_grained(kBarItems * (36 * sizeof(double) + sizeof(int))) == hipSuccess &&
+            h->bar_din.ensure_fine_grained(kBarKeys * 36 * sizeof(double)) == hipSuccess)
+            h->bar_state = 1;
 #endif
     }
     return h->bar_state == 1;
@@ -2243,22 +2249,11 @@ static inline void bar_publish() {
 // (the Dual paths compare the next call's inputs with it).  The caller ends its mirrors with one bar_publish().
 static void bar_mirror(pfc_context *h, void **dev, const void *pinned, size_t bytes, int slot) {
     if (!bar_ready(h)) return;
-    void *dst = slot == 0 ? h->bar_in : h->bar_din;
+    void *dst = slot == 0 ? h->bar_in.p : h->bar_din.p;
     const size_t cap = slot == 0 ? kBarItems * (36 * sizeof(double) + sizeof(int)) : kBarKeys * 36 * sizeof(double);
     if (bytes > cap) return;
     std::memcpy(dst, pinned, bytes);
     *dev = dst;
-}
-
-// pinned staging block of at least `bytes` (grown with slack, never shrunk)
-static hipError_t ensure_pinned(void **p, size_t *cap, size_t bytes) {
-    if (*cap >= bytes) return hipSuccess;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr; *cap = 0;
-    hipError_t e = hipHostMalloc(p, bytes * 2);
-    if (e == hipSuccess) { *cap = bytes * 2; std::memset(*p, 0, bytes * 2); }   // completion words are polled: never start from stale bytes
-    if (std::getenv("PFC_LOG_ALLOC")) std::fprintf(stderr, "pfc pinned %p .. %p\n", *p, (void *)((char *)*p + bytes * 2));
-    return e;
 }
 
 // Value inputs of n items into a host-written block: pose | twist | s (zeros for a null s), the ids ids_at doubles in.
@@ -2292,12 +2287,12 @@ static bool same_point(const double *pi, size_t n, size_t ids_at, const int *ins
 // through their BAR mirrors where they fit (bar_mirror), then one bar_publish.
 struct PinnedDev { void *in = nullptr, *out = nullptr, *din = nullptr, *dout = nullptr; };
 static int map_pinned(pfc_context *h, PinnedDev *v, size_t in_bytes, size_t din_bytes) {
-    HIP_TRY(h, hipHostGetDevicePointer(&v->in, h->pin_in, 0));
-    HIP_TRY(h, hipHostGetDevicePointer(&v->out, h->pin_out, 0));
-    HIP_TRY(h, hipHostGetDevicePointer(&v->din, h->pin_din, 0));
-    HIP_TRY(h, hipHostGetDevicePointer(&v->dout, h->pin_dout, 0));
-    bar_mirror(h, &v->in, h->pin_in, in_bytes, 0);
-    bar_mirror(h, &v->din, h->pin_din, din_bytes, 1);
+    HIP_TRY(h, hipHostGetDevicePointer(&v->in, h->pin_in.p, 0));
+    HIP_TRY(h, hipHostGetDevicePointer(&v->out, h->pin_out.p, 0));
+    HIP_TRY(h, hipHostGetDevicePointer(&v->din, h->pin_din.p, 0));
+    HIP_TRY(h, hipHostGetDevicePointer(&v->dout, h->pin_dout.p, 0));
+    bar_mirror(h, &v->in, h->pin_in.p, in_bytes, 0);
+    bar_mirror(h, &v->din, h->pin_din.p, din_bytes, 1);
     bar_publish();
     return PFC_OK;
 }
@@ -2331,19 +2326,15 @@ int pfc_eval(pfc_handle h, int n_items, const int *ins_ids, const double *pose, 
     const size_t out_d = n * 12, out_bytes = out_d * sizeof(double) + n * 4 * sizeof(int);
     const size_t t0 = (((size_t)h->max_levels + 40) + 3) & ~(size_t)3;      // ints in front of the outputs (16-byte multiple)
     const size_t back_bytes = t0 * sizeof(int) + out_bytes;
-    HIP_TRY(h, ensure_pinned(&h->pin_in, &h->pin_in_cap, in_bytes));
+    HIP_TRY(h, h->pin_in.ensure(in_bytes));
     // behind the outputs: the per-item words of the fused small-scene kernel (status, counts: 8 ints per item)
-    HIP_TRY(h, ensure_pinned(&h->pin_out, &h->pin_out_cap, back_bytes + (n <= (size_t)kFusedMaxItems ? n * 8 * sizeof(int) : 0)));
+    HIP_TRY(h, h->pin_out.ensure(back_bytes + (n <= (size_t)kFusedMaxItems ? n * 8 * sizeof(int) : 0)));
     HIP_TRY(h, h->h_pose.ensure(in_d + (n + 1) / 2 + 1));      // device mirror of the input block (doubles)
-    {
-        const size_t cap0 = h->tail.cap;
-        HIP_TRY(h, h->tail.ensure(t0 + out_bytes / sizeof(int) + 4));   // only ever grows; ensure_work asks for less
-        if (h->tail.cap != cap0) ++h->epoch;                   // captured graphs hold the old address
-    }
+    HIP_TRY(h, ensure_graphed(h, h->tail, t0 + out_bytes / sizeof(int) + 4));   // only ever grows; ensure_work asks for less
     // (every evaluation whose kernels read the inputs in place, i.e. up to 512 items: 64 box-on-plane scenes 52.2 -> 48.7 us, C4's
     // 256 66.5 -> 64.5, 128 full-size poses on the batched path 333 -> 328; scripts/variants/bar_items_run.py)
     const bool bar = n <= kBarItems && !h->want_surv && bar_ready(h);
-    double *pi = bar ? (double *)h->bar_in : (double *)h->pin_in;
+    double *pi = bar ? (double *)h->bar_in.p : (double *)h->pin_in.p;
     pack_values(pi, n, in_d, ins_ids, pose, twist, s);
     if (bar) bar_publish();
     hipStream_t st = h->stream;
@@ -2355,9 +2346,9 @@ int pfc_eval(pfc_handle h, int n_items, const int *ins_ids, const double *pose, 
     const bool zero_copy = n_items <= (bar ? (int)kBarItems : 512) && !h->want_surv;
     double *di = h->h_pose.p, *dout = reinterpret_cast<double *>(h->tail.p + t0);
     if (zero_copy) {
-        void *dpi = h->bar_in, *dpo = nullptr;
-        if (!bar) HIP_TRY(h, hipHostGetDevicePointer(&dpi, h->pin_in, 0));
-        HIP_TRY(h, hipHostGetDevicePointer(&dpo, h->pin_out, 0));
+        void *dpi = h->bar_in.p, *dpo = nullptr;
+        if (!bar) HIP_TRY(h, hipHostGetDevicePointer(&dpi, h->pin_in.p, 0));
+        HIP_TRY(h, hipHostGetDevicePointer(&dpo, h->pin_out.p, 0));
         di = (double *)dpi;
         dout = reinterpret_cast<double *>((int *)dpo + t0);
     } else {
@@ -2368,20 +2359,20 @@ int pfc_eval(pfc_handle h, int n_items, const int *ins_ids, const double *pose, 
         h->tail_dev = zero_copy ? reinterpret_cast<int *>(dout) - t0 : nullptr;
         if (zero_copy && n <= (size_t)kFusedMaxItems) {
             h->fout_dev = reinterpret_cast<int *>(reinterpret_cast<char *>(dout) + out_bytes);
-            h->fout_host = reinterpret_cast<const int *>(reinterpret_cast<const char *>(h->pin_out) + back_bytes);
+            h->fout_host = reinterpret_cast<const int *>(reinterpret_cast<const char *>(h->pin_out.p) + back_bytes);
         }
         rc = pfc_eval_device(h, n_items, ins_ids ? (const int *)(di + in_d) : nullptr, di, di + n * 24,
                              s ? di + n * 30 : nullptr, dout, dout + n * 6, (int *)(dout + out_d), st);
         h->tail_dev = nullptr; h->fout_dev = nullptr;
         if (rc != PFC_OK) { h->fout_host = nullptr; return rc; }
-        if (!zero_copy && !h->pending_fused) HIP_TRY(h, hipMemcpyAsync(h->pin_out, h->tail.p, back_bytes, hipMemcpyDeviceToHost, st));
-        h->tail_host = (const int *)h->pin_out;
+        if (!zero_copy && !h->pending_fused) HIP_TRY(h, hipMemcpyAsync(h->pin_out.p, h->tail.p, back_bytes, hipMemcpyDeviceToHost, st));
+        h->tail_host = (const int *)h->pin_out.p;
         rc = check_eval(h);
         h->tail_host = nullptr; h->fout_host = nullptr;
         if (rc != PFC_ERR_OVERFLOW) break;
     }
     if (rc != PFC_OK) return rc;
-    const double *po = reinterpret_cast<const double *>((const int *)h->pin_out + t0);
+    const double *po = reinterpret_cast<const double *>((const int *)h->pin_out.p + t0);
     copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
     return PFC_OK;
 }
@@ -2395,8 +2386,8 @@ int launch_dual(pfc_context *h, int n_items, int n_dir, const int *tail, const d
                 const double *dsd, double *dw, double *dsdot, size_t n_pairs_bound, hipStream_t st, size_t *dpcap_out,
                 bool acc_cleared = false, const int *pair_count = nullptr, unsigned *status_word = nullptr) {
     const size_t nk = (size_t)n_items * n_dir;
-    HIP_TRY(h, ensure_dual(h, h->dual_acc, nk * kDaStride));
-    HIP_TRY(h, ensure_dual(h, h->dual_res, nk * kDrStride));
+    HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
+    HIP_TRY(h, ensure_graphed(h, h->dual_res, nk * kDrStride));
     if (!acc_cleared) HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
     DualArgs a;
     a.items = h->items.p; a.cand = h->cand.p; a.ccount = tail + 12; a.ccap = (int)h->ccap;   // packed copy of the counters
@@ -2417,8 +2408,8 @@ int launch_dual(pfc_context *h, int n_items, int n_dir, const int *tail, const d
     // (option fixed_order: the bound also sizes the record list of the passes' sums, for every model -- the callers compare the pair count
     // with this capacity after their synchronisation and re-issue the passes when it was exceeded)
     const size_t dpcap = (h->any_bristle || h->opt_fixed_order) ? ((n_pairs_bound + cpw - 1) / cpw) * 64 + 64 : 64;   // 64 slots per group of cpw pairs
-    HIP_TRY(h, ensure_dual(h, h->dual_poly, dpcap * kDpFields));
-    HIP_TRY(h, ensure_dual(h, h->dual_pkey, dpcap));
+    HIP_TRY(h, ensure_graphed(h, h->dual_poly, dpcap * kDpFields));
+    HIP_TRY(h, ensure_graphed(h, h->dual_pkey, dpcap));
     a.dpoly = h->dual_poly.p; a.dpoly_key = h->dual_pkey.p; a.dpcap = (long long)dpcap;
     if (dpcap_out) *dpcap_out = dpcap;
     // Scenes of many items: the passes walk only the contributing pairs of items this chunk seeds (pfc_dual.h, k_dual_select).
@@ -2429,8 +2420,8 @@ int launch_dual(pfc_context *h, int n_items, int n_dir, const int *tail, const d
     (void)hipStreamIsCapturing(st, &cap);
     // (nor under option fixed_order: the selected list is compacted block by block in the order the blocks come by)
     if (!pair_count && n_items >= kDualSelectMin && cap == hipStreamCaptureStatusNone && !h->opt_fixed_order && std::getenv("PFC_NO_SELECT") == nullptr) {
-        HIP_TRY(h, ensure_dual(h, h->dual_sel, h->ccap));
-        HIP_TRY(h, ensure_dual(h, h->dual_flag, (size_t)n_items + 1));
+        HIP_TRY(h, ensure_graphed(h, h->dual_sel, h->ccap));
+        HIP_TRY(h, ensure_graphed(h, h->dual_flag, (size_t)n_items + 1));
         int *selcount = h->dual_flag.p + n_items;
         hipLaunchKernelGGL(k_dual_flags, dim3(n_items), dim3(64), 0, st, a, h->dual_flag.p, selcount);
         // (grid from the list's capacity, not from n_pairs_bound: the first evaluation of a handle has no pair count to go by)
@@ -2474,8 +2465,8 @@ int launch_dual(pfc_context *h, int n_items, int n_dir, const int *tail, const d
         const size_t n_pos = n_grp + 1, direct = n_pos * (size_t)n_dir;
         const size_t cap = 3 * direct + 3 * (size_t)n_dir * (size_t)n_items + 64;
         if (cap > ((size_t)1 << 30)) return fail(h, PFC_ERR_NOMEM, "option fixed_order: %zu Dual sum records: evaluate the batch in parts", cap);
-        HIP_TRY(h, ensure_dual(h, h->fx_rec, cap * kSinkStride));
-        HIP_TRY(h, ensure_dual(h, h->fx_head, 3 * nk + 2));
+        HIP_TRY(h, ensure_graphed(h, h->fx_rec, cap * kSinkStride));
+        HIP_TRY(h, ensure_graphed(h, h->fx_head, 3 * nk + 2));
         HIP_TRY(h, hipMemsetAsync(h->fx_head.p, 0xFF, sizeof(int) * 3 * nk, st));
         HIP_TRY(h, hipMemsetAsync(h->fx_head.p + 3 * nk, 0, sizeof(int) * 2, st));
         a.sink_a = FixedSink{h->fx_rec.p, h->fx_head.p + 3 * nk, h->fx_head.p, 0, n_dir, (int)n_pos, (int)(3 * direct), (int)cap, a.status};
@@ -2533,17 +2524,17 @@ int eval_dual_fused(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     const size_t n = (size_t)n_items, nk = n * n_dir;
     const size_t in_d = n * 36, in_bytes = in_d * sizeof(double) + n * sizeof(int);
     const size_t out_d = n * 12, out_bytes = out_d * sizeof(double) + n * 4 * sizeof(int) + n * 8 * sizeof(int);
-    HIP_TRY(h, ensure_pinned(&h->pin_in, &h->pin_in_cap, in_bytes));
-    HIP_TRY(h, ensure_pinned(&h->pin_out, &h->pin_out_cap, out_bytes + 64));
-    HIP_TRY(h, ensure_pinned(&h->pin_din, &h->pin_din_cap, sizeof(double) * nk * 30));
-    HIP_TRY(h, ensure_pinned(&h->pin_dout, &h->pin_dout_cap, sizeof(double) * nk * 12));
-    pack_values((double *)h->pin_in, n, in_d, ins_ids, pose, twist, s);
-    pack_seeds((double *)h->pin_din, nk, d_pose, d_twist, nullptr, false);
+    HIP_TRY(h, h->pin_in.ensure(in_bytes));
+    HIP_TRY(h, h->pin_out.ensure(out_bytes + 64));
+    HIP_TRY(h, h->pin_din.ensure(sizeof(double) * nk * 30));
+    HIP_TRY(h, h->pin_dout.ensure(sizeof(double) * nk * 12));
+    pack_values((double *)h->pin_in.p, n, in_d, ins_ids, pose, twist, s);
+    pack_seeds((double *)h->pin_din.p, nk, d_pose, d_twist, nullptr, false);
     PinnedDev v;
     { const int rc = map_pinned(h, &v, in_bytes, sizeof(double) * nk * 30); if (rc != PFC_OK) return rc; }
     double *di = (double *)v.in, *dout = (double *)v.out, *ddi = (double *)v.din, *ddo = (double *)v.dout;
     h->fout_dev = reinterpret_cast<int *>(dout + out_d) + n * 4;
-    h->fout_host = reinterpret_cast<const int *>((const double *)h->pin_out + out_d) + n * 4;
+    h->fout_host = reinterpret_cast<const int *>((const double *)h->pin_out.p + out_d) + n * 4;
     h->fu_ndir = n_dir; h->fu_dpose = ddi; h->fu_dtwist = ddi + nk * 24; h->fu_dwrench = ddo; h->fu_dsdot = ddo + nk * 6;
     int rc = enqueue_fused(h, n_items, ins_ids ? (const int *)(di + in_d) : nullptr, di, di + n * 24, s ? di + n * 30 : nullptr,
                            dout, dout + n * 6, reinterpret_cast<int *>(dout + out_d), h->stream);
@@ -2552,9 +2543,9 @@ int eval_dual_fused(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     if (rc == PFC_OK) rc = check_eval(h);
     h->fout_host = nullptr;
     if (rc != PFC_OK) return rc;
-    const double *po = (const double *)h->pin_out;
+    const double *po = (const double *)h->pin_out.p;
     copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
-    copy_out_dual((const double *)h->pin_dout, nk, d_wrench, d_sdot);
+    copy_out_dual((const double *)h->pin_dout.p, nk, d_wrench, d_sdot);
     h->pin_in_pt = {n_items, ins_ids != nullptr, h->value_serial, in_d};     // a repeat of this point goes to the hybrid path
     return PFC_OK;
 }
@@ -2572,16 +2563,16 @@ int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids,
     const size_t in_d = n * 36, in_bytes = in_d * sizeof(double) + n * sizeof(int);
     const size_t out_d = n * 12, out_bytes = out_d * sizeof(double) + n * 4 * sizeof(int) + n * 8 * sizeof(int);
     {
-        const void *p0 = h->pin_in, *q0 = h->pin_out;
-        HIP_TRY(h, ensure_pinned(&h->pin_in, &h->pin_in_cap, in_bytes));
-        HIP_TRY(h, ensure_pinned(&h->pin_out, &h->pin_out_cap, out_bytes + 64));
-        if (h->pin_in != p0 || h->pin_out != q0) end_kept_pass(h);      // reallocated: the cached blocks are gone
+        bool in_moved, out_moved;
+        HIP_TRY(h, h->pin_in.ensure(in_bytes, &in_moved));
+        HIP_TRY(h, h->pin_out.ensure(out_bytes + 64, &out_moved));
+        if (in_moved || out_moved) end_kept_pass(h);      // reallocated: the cached blocks are gone
     }
-    HIP_TRY(h, ensure_pinned(&h->pin_din, &h->pin_din_cap, sizeof(double) * nk * 36));
-    HIP_TRY(h, ensure_pinned(&h->pin_dout, &h->pin_dout_cap, sizeof(double) * nk * 12));
+    HIP_TRY(h, h->pin_din.ensure(sizeof(double) * nk * 36));
+    HIP_TRY(h, h->pin_dout.ensure(sizeof(double) * nk * 12));
     HIP_TRY(h, h->emit_ctr.ensure(4));
-    if (!h->h_emit) HIP_TRY(h, hipHostMalloc((void **)&h->h_emit, sizeof(int) * 4));
-    double *pi = (double *)h->pin_in;
+    HIP_TRY(h, h->h_emit.ensure(4));
+    double *pi = (double *)h->pin_in.p;
     // the chunks of one Jacobian (pfc_eval_dual's large path has the same test): value inputs bitwise equal to those still
     // in the pinned input block -> the lists and item records the fused kernel handed over are reused, only the Dual passes run
     const bool same = h->opt_dual_reuse && h->kept.kind == pfc_context::KeptPass::Hybrid && h->kept.n == n_items &&
@@ -2591,7 +2582,7 @@ int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids,
         HIP_TRY(h, ensure_work(h, n_items));      // (not before a reuse: option poison refills the work lists there)
         pack_values(pi, n, in_d, ins_ids, pose, twist, s);
     }
-    pack_seeds((double *)h->pin_din, nk, d_pose, d_twist, d_s, true);
+    pack_seeds((double *)h->pin_din.p, nk, d_pose, d_twist, d_s, true);
     PinnedDev v;
     { const int rc = map_pinned(h, &v, in_bytes, sizeof(double) * nk * 36); if (rc != PFC_OK) return rc; }
     double *di = (double *)v.in, *dout = (double *)v.out;
@@ -2599,29 +2590,29 @@ int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids,
     // seeds / results of up to kBarKeys (512 without a BAR block) (item, direction) pairs are read / written in place by the kernels, larger ones staged
     const bool zc = nk <= (h->bar_state == 1 ? (int)kBarKeys : 512);
     if (!zc) {
-        HIP_TRY(h, ensure_dual(h, h->dual_in, nk * 36));
-        HIP_TRY(h, ensure_dual(h, h->dual_out, nk * 12));
-        HIP_TRY(h, hipMemcpyAsync(h->dual_in.p, h->pin_din, sizeof(double) * nk * 36, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, ensure_graphed(h, h->dual_in, nk * 36));
+        HIP_TRY(h, ensure_graphed(h, h->dual_out, nk * 12));
+        HIP_TRY(h, hipMemcpyAsync(h->dual_in.p, h->pin_din.p, sizeof(double) * nk * 36, hipMemcpyHostToDevice, st));
     }
     double *ddi = zc ? (double *)v.din : h->dual_in.p, *ddo = zc ? (double *)v.dout : h->dual_out.p;
-    const double *po = (const double *)h->pin_out;
+    const double *po = (const double *)h->pin_out.p;
     if (same) {
-        HIP_TRY(h, ensure_dual(h, h->dual_acc, nk * kDaStride));
+        HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
         HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
         const size_t bound_r = (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) + 64;     // known exactly
         int rcr = launch_dual(h, n_items, n_dir, h->tail.p, ddi, ddi + nk * 24, ddi + nk * 30, ddo, ddo + nk * 6, bound_r, st, nullptr,
                               true, h->emit_ctr.p);
         if (rcr != PFC_OK) return rcr;
-        if (!zc) HIP_TRY(h, hipMemcpyAsync(h->pin_dout, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
+        if (!zc) HIP_TRY(h, hipMemcpyAsync(h->pin_dout.p, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
         HIP_TRY(h, hipStreamSynchronize(st));
         copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
-        copy_out_dual((const double *)h->pin_dout, nk, d_wrench, d_sdot);
+        copy_out_dual((const double *)h->pin_dout.p, nk, d_wrench, d_sdot);
         h->last_dual_reused = true;
         return PFC_OK;
     }
     size_t bound = 64;
     while (bound < (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) * 2 + 64) bound *= 2;
-    HIP_TRY(h, ensure_dual(h, h->dual_acc, nk * kDaStride));
+    HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
     HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
     HIP_TRY(h, hipMemsetAsync(h->emit_ctr.p, 0, sizeof(int) * 4, st));
     h->fout_dev = reinterpret_cast<int *>(dout + out_d) + n * 4;
@@ -2636,22 +2627,22 @@ int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids,
     rc = launch_dual(h, n_items, n_dir, h->tail.p, ddi, ddi + nk * 24, ddi + nk * 30, ddo, ddo + nk * 6, bound, st, &dpcap, true,
                      h->emit_ctr.p);
     if (rc != PFC_OK) return rc;
-    if (!zc) HIP_TRY(h, hipMemcpyAsync(h->pin_dout, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(h->h_emit, h->emit_ctr.p, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-    h->fout_host = reinterpret_cast<const int *>((const double *)h->pin_out + out_d) + n * 4;
+    if (!zc) HIP_TRY(h, hipMemcpyAsync(h->pin_dout.p, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(h->h_emit.p, h->emit_ctr.p, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
+    h->fout_host = reinterpret_cast<const int *>((const double *)h->pin_out.p + out_d) + n * 4;
     // check_fused would poll; here the stream is synchronised (the completion words of the fused kernel are long written)
     HIP_TRY(h, hipStreamSynchronize(st));
     rc = check_eval(h);
     h->fout_host = nullptr;
     if (rc != PFC_OK) return rc;
     if (h->stats[6] & kStCandOvf) return fail(h, PFC_ERR_OVERFLOW, "hand-over list of the small-scene kernel overflowed: batched path");
-    if ((unsigned)h->h_emit[2] & kStHole) return fail(h, PFC_ERR_STATE, "internal error: a work-list slot was read before it was written");
-    const long long pairs = h->h_emit[0];
+    if ((unsigned)h->h_emit.p[2] & kStHole) return fail(h, PFC_ERR_STATE, "internal error: a work-list slot was read before it was written");
+    const long long pairs = h->h_emit.p[0];
     h->dual_hint = pairs;
     const int cpw = 64 / n_dir;
     if ((h->any_bristle || h->opt_fixed_order) && (size_t)((pairs + cpw - 1) / cpw) * 64 + 64 > dpcap) return PFC_ERR_OVERFLOW;
     copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
-    copy_out_dual((const double *)h->pin_dout, nk, d_wrench, d_sdot);
+    copy_out_dual((const double *)h->pin_dout.p, nk, d_wrench, d_sdot);
     h->kept = {pfc_context::KeptPass::Hybrid, n_items, ins_ids != nullptr};
     h->pin_in_pt = {n_items, ins_ids != nullptr, h->value_serial, in_d};
     return PFC_OK;
@@ -2672,14 +2663,14 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     const size_t t0 = (((size_t)h->max_levels + 40) + 3) & ~(size_t)3;
     const size_t back_bytes = t0 * sizeof(int) + out_bytes;
     {
-        const void *p0 = h->pin_in, *q0 = h->pin_out;
-        HIP_TRY(h, ensure_pinned(&h->pin_in, &h->pin_in_cap, in_bytes));
-        HIP_TRY(h, ensure_pinned(&h->pin_out, &h->pin_out_cap, back_bytes));
-        if (h->pin_in != p0 || h->pin_out != q0) end_kept_pass(h);     // reallocated: the cached blocks are gone
+        bool in_moved, out_moved;
+        HIP_TRY(h, h->pin_in.ensure(in_bytes, &in_moved));
+        HIP_TRY(h, h->pin_out.ensure(back_bytes, &out_moved));
+        if (in_moved || out_moved) end_kept_pass(h);     // reallocated: the cached blocks are gone
     }
-    HIP_TRY(h, ensure_pinned(&h->pin_din, &h->pin_din_cap, sizeof(double) * nk * 36));
-    HIP_TRY(h, ensure_pinned(&h->pin_dout, &h->pin_dout_cap, sizeof(double) * nk * 12));
-    double *pi = (double *)h->pin_in;
+    HIP_TRY(h, h->pin_din.ensure(sizeof(double) * nk * 36));
+    HIP_TRY(h, h->pin_dout.ensure(sizeof(double) * nk * 12));
+    double *pi = (double *)h->pin_in.p;
     // the chunks of one Jacobian: value inputs bitwise equal to those still in the pinned input block -> only the Dual passes
     const bool same = h->opt_dual_reuse && h->kept.kind == pfc_context::KeptPass::OneGraph && h->kept.n == n_items &&
                       h->kept.ids == (ins_ids != nullptr) && same_point(pi, n, in_d, ins_ids, pose, twist, s, true);
@@ -2687,11 +2678,11 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
         end_kept_pass(h);
         pack_values(pi, n, in_d, ins_ids, pose, twist, s);
     }
-    pack_seeds((double *)h->pin_din, nk, d_pose, d_twist, d_s, true);
+    pack_seeds((double *)h->pin_din.p, nk, d_pose, d_twist, d_s, true);
     PinnedDev v;
     { const int rc = map_pinned(h, &v, in_bytes, sizeof(double) * nk * 36); if (rc != PFC_OK) return rc; }
     double *di = (double *)v.in, *dout = reinterpret_cast<double *>((int *)v.out + t0);
-    const double *po = reinterpret_cast<const double *>((const int *)h->pin_out + t0);
+    const double *po = reinterpret_cast<const double *>((const int *)h->pin_out.p + t0);
     hipStream_t st = h->stream;
     // One captured graph: accumulator fill, the value pass, the Dual passes.  (Launched eagerly behind the replayed value
     // graph, the Dual kernels started 9 us late.)  The capacity of the kept Dual polygons is a power of two above twice
@@ -2700,35 +2691,35 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     while (bound < (size_t)h->dual_hint * 2 + 64) bound *= 2;
     const int cpw = 64 / n_dir;
     if (!same) HIP_TRY(h, ensure_work(h, n_items));      // (not before a reuse: option poison refills the work lists there)
-    HIP_TRY(h, ensure_dual(h, h->dual_acc, nk * kDaStride));
-    HIP_TRY(h, ensure_dual(h, h->dual_res, nk * kDrStride));
+    HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
+    HIP_TRY(h, ensure_graphed(h, h->dual_res, nk * kDrStride));
     const size_t dpcap = (h->any_bristle || h->opt_fixed_order) ? ((bound + cpw - 1) / cpw) * 64 + 64 : 64;
-    HIP_TRY(h, ensure_dual(h, h->dual_poly, dpcap * kDpFields));
-    HIP_TRY(h, ensure_dual(h, h->dual_pkey, dpcap));
+    HIP_TRY(h, ensure_graphed(h, h->dual_poly, dpcap * kDpFields));
+    HIP_TRY(h, ensure_graphed(h, h->dual_pkey, dpcap));
     const int levels = eff_levels(h);
     const int L = bfs_levels_for(h, n_items, levels);
     // seeds / results of up to 512 (item, direction) pairs are read / written in place by the kernels; larger ones are
     // copied by memcpy nodes of the graph (reading 288 B per pair over PCIe from inside k_narrow_dual stops paying)
     const bool zc_dual = nk <= (h->bar_state == 1 ? (int)kBarKeys : 512);
     if (!zc_dual) {
-        HIP_TRY(h, ensure_dual(h, h->dual_in, nk * 36));
-        HIP_TRY(h, ensure_dual(h, h->dual_out, nk * 12));
+        HIP_TRY(h, ensure_graphed(h, h->dual_in, nk * 36));
+        HIP_TRY(h, ensure_graphed(h, h->dual_out, nk * 12));
     }
     double *ddi = zc_dual ? (double *)v.din : h->dual_in.p, *ddo = zc_dual ? (double *)v.dout : h->dual_out.p;
     if (same) {
         // eager launches of the Dual passes on the value pass the last graph replay left (lists, item records, the packed tail
         // in the pinned output block); the pair count is known, so there is no speculation to check
         HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
-        if (!zc_dual) HIP_TRY(h, hipMemcpyAsync(ddi, h->pin_din, sizeof(double) * nk * 36, hipMemcpyHostToDevice, st));
+        if (!zc_dual) HIP_TRY(h, hipMemcpyAsync(ddi, h->pin_din.p, sizeof(double) * nk * 36, hipMemcpyHostToDevice, st));
         h->last_levels = levels;
         const size_t bound_r = (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) + 64;
         int rcr = launch_dual(h, n_items, n_dir, (const int *)v.out, ddi, ddi + nk * 24, ddi + nk * 30, ddo, ddo + nk * 6, bound_r, st,
                               nullptr, true);
         if (rcr != PFC_OK) return rcr;
-        if (!zc_dual) HIP_TRY(h, hipMemcpyAsync(h->pin_dout, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
+        if (!zc_dual) HIP_TRY(h, hipMemcpyAsync(h->pin_dout.p, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
         HIP_TRY(h, hipStreamSynchronize(st));
         copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
-        copy_out_dual((const double *)h->pin_dout, nk, d_wrench, d_sdot);
+        copy_out_dual((const double *)h->pin_dout.p, nk, d_wrench, d_sdot);
         h->last_dual_reused = true;
         return PFC_OK;
     }
@@ -2745,23 +2736,23 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     h->last_levels = levels;      // launch_dual locates the pair counter in the tail by it
     int rc = PFC_OK;
     if (!h->dghave || std::memcmp(&key, &h->dgkey, sizeof key) != 0) {
-        if (h->dgexec) { (void)hipGraphExecDestroy(h->dgexec); h->dgexec = nullptr; }
+        h->dgexec.reset();
         h->dghave = false;
         hipGraph_t graph = nullptr;
         hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
         if (e == hipSuccess) {
             e = hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st);
-            if (!zc_dual && e == hipSuccess) e = hipMemcpyAsync(ddi, h->pin_din, sizeof(double) * nk * 36, hipMemcpyHostToDevice, st);
+            if (!zc_dual && e == hipSuccess) e = hipMemcpyAsync(ddi, h->pin_din.p, sizeof(double) * nk * 36, hipMemcpyHostToDevice, st);
             rc = record_eval(h, n_items, d_ins, di, di + n * 24, d_sv, dout, dout + n * 6, (int *)(dout + out_d), st, false);
             if (rc == PFC_OK)
                 rc = launch_dual(h, n_items, n_dir, (const int *)v.out, ddi, ddi + nk * 24, ddi + nk * 30, ddo, ddo + nk * 6, bound,
                                  st, nullptr, true);
             if (!zc_dual && rc == PFC_OK && e == hipSuccess)
-                e = hipMemcpyAsync(h->pin_dout, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st);
+                e = hipMemcpyAsync(h->pin_dout.p, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st);
             const hipError_t e2 = hipStreamEndCapture(st, &graph);
             if (e == hipSuccess) e = e2;
         }
-        if (rc == PFC_OK && e == hipSuccess) e = hipGraphInstantiate(&h->dgexec, graph, nullptr, nullptr, 0);
+        if (rc == PFC_OK && e == hipSuccess) e = hipGraphInstantiate(h->dgexec.put(), graph, nullptr, nullptr, 0);
         if (graph) (void)hipGraphDestroy(graph);
         h->want_surv = false; h->tail_dev = nullptr;
         if (rc != PFC_OK) return rc;
@@ -2774,17 +2765,17 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     HIP_TRY(h, hipGraphLaunch(h->dgexec, st));
     h->last_bfs_levels = L; h->last_n_items = n_items; h->pending = true; h->last_stream = st; h->ev_valid = false;
     h->split_n0 = 0;
-    h->tail_host = (const int *)h->pin_out;
+    h->tail_host = (const int *)h->pin_out.p;
     rc = check_eval(h);                 // the one synchronisation; grows the work lists on overflow
     h->tail_host = nullptr;
     if (rc != PFC_OK) return rc;
     // did the kept Dual polygons fit?  (contributing pairs: the counter next to the polygon total in the packed tail)
-    const int *tail = (const int *)h->pin_out;
+    const int *tail = (const int *)h->pin_out.p;
     const long long pairs = tail[12 + (((h->last_levels + 9) & ~1) + 1)];
     h->dual_hint = pairs;
     if ((h->any_bristle || h->opt_fixed_order) && (size_t)((pairs + cpw - 1) / cpw) * 64 + 64 > dpcap) return PFC_ERR_OVERFLOW;
     copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
-    copy_out_dual((const double *)h->pin_dout, nk, d_wrench, d_sdot);
+    copy_out_dual((const double *)h->pin_dout.p, nk, d_wrench, d_sdot);
     h->kept = {pfc_context::KeptPass::OneGraph, n_items, ins_ids != nullptr};
     return PFC_OK;
 }
@@ -2827,12 +2818,12 @@ int pfc_eval_dual_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_
     // count with the capacity after the one synchronisation and asks for a re-issue if it fell short.
     size_t bound = 4096;
     while (bound < (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) * 2 + 64 || bound < (size_t)n_items * 8) bound *= 2;
-    HIP_TRY(h, ensure_dual(h, h->dual_acc, nk * kDaStride));
-    HIP_TRY(h, ensure_dual(h, h->dual_res, nk * kDrStride));
+    HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
+    HIP_TRY(h, ensure_graphed(h, h->dual_res, nk * kDrStride));
     if (!d_ds) {
-        const size_t c0 = h->dual_zero.cap;
-        HIP_TRY(h, h->dual_zero.ensure(nk * 6));
-        if (h->dual_zero.cap != c0) HIP_TRY(h, hipMemsetAsync(h->dual_zero.p, 0, sizeof(double) * h->dual_zero.cap, st));
+        bool moved;
+        HIP_TRY(h, h->dual_zero.ensure(nk * 6, &moved));
+        if (moved) HIP_TRY(h, hipMemsetAsync(h->dual_zero.p, 0, sizeof(double) * h->dual_zero.cap, st));
         d_ds = h->dual_zero.p;
     }
     HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
@@ -2847,7 +2838,7 @@ int pfc_eval_dual_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_
         } else {
             HIP_TRY(h, ensure_work(h, n_items));
             HIP_TRY(h, h->emit_ctr.ensure(4));
-            if (!h->h_emit) HIP_TRY(h, hipHostMalloc((void **)&h->h_emit, sizeof(int) * 4));
+            HIP_TRY(h, h->h_emit.ensure(4));
             size_t bh = 64;
             while (bh < (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) * 2 + 64) bh *= 2;
             HIP_TRY(h, hipMemsetAsync(h->emit_ctr.p, 0, sizeof(int) * 4, st));
@@ -2859,7 +2850,7 @@ int pfc_eval_dual_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_
             size_t dpcap_h = 0;
             rcf = launch_dual(h, n_items, n_dir, h->tail.p, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, bh, st, &dpcap_h, true, h->emit_ctr.p);
             if (rcf != PFC_OK) return rcf;
-            HIP_TRY(h, hipMemcpyAsync(h->h_emit, h->emit_ctr.p, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipMemcpyAsync(h->h_emit.p, h->emit_ctr.p, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
             h->pending_dual_hyb = true; h->pending_dpcap = dpcap_h; h->pending_ndir = n_dir; h->pending_ids = d_ins_ids != nullptr;
             return PFC_OK;
         }
@@ -2887,12 +2878,12 @@ int pfc_eval_dual_device_more(pfc_handle h, int n_dir, const double *d_dpose, co
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     const int n_items = h->kept.n;
     const size_t nk = (size_t)n_items * n_dir;
-    HIP_TRY(h, ensure_dual(h, h->dual_acc, nk * kDaStride));
-    HIP_TRY(h, ensure_dual(h, h->dual_res, nk * kDrStride));
+    HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
+    HIP_TRY(h, ensure_graphed(h, h->dual_res, nk * kDrStride));
     if (!d_ds) {
-        const size_t c0 = h->dual_zero.cap;
-        HIP_TRY(h, h->dual_zero.ensure(nk * 6));
-        if (h->dual_zero.cap != c0) HIP_TRY(h, hipMemsetAsync(h->dual_zero.p, 0, sizeof(double) * h->dual_zero.cap, st));
+        bool moved;
+        HIP_TRY(h, h->dual_zero.ensure(nk * 6, &moved));
+        if (moved) HIP_TRY(h, hipMemsetAsync(h->dual_zero.p, 0, sizeof(double) * h->dual_zero.cap, st));
         d_ds = h->dual_zero.p;
     }
     HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
@@ -2901,13 +2892,13 @@ int pfc_eval_dual_device_more(pfc_handle h, int n_dir, const double *d_dpose, co
     // The passes report (kStHole: a list entry out of range, capacity guards) into a word of their own, cleared here and read
     // back by pfc_check in front of its synchronisation: neither the value pass's status word (read by ITS k_final only) nor
     // the hand-over block (read with the pair count of a first chunk only) is looked at again on this path.
-    if (!h->h_more) HIP_TRY(h, hipHostMalloc((void **)&h->h_more, sizeof(unsigned) * 4));
+    HIP_TRY(h, h->h_more.ensure(4));
     unsigned *more_status = h->status.p + 1;
     HIP_TRY(h, hipMemsetAsync(more_status, 0, sizeof(unsigned), st));
     const int rc = launch_dual(h, n_items, n_dir, h->tail.p, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, bound, st, nullptr, true,
                                h->kept.kind == pfc_context::KeptPass::HandOver ? h->emit_ctr.p : nullptr, more_status);
     if (rc != PFC_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->h_more, more_status, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(h->h_more.p, more_status, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     h->pending_more = true; h->last_stream = st; h->last_dual_reused = true;
     return PFC_OK;
 }
@@ -2935,7 +2926,7 @@ int pfc_local_jacobian_device(pfc_handle h, double *d_L, void *stream) {
     HIP_TRY(h, h->ljac_out.ensure(n * kLjacSize));
     // as pfc_eval_dual_device_more: the exact pair count, and a status word of the passes' own that pfc_check reads back
     const size_t bound = (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) + 64;
-    if (!h->h_more) HIP_TRY(h, hipHostMalloc((void **)&h->h_more, sizeof(unsigned) * 4));
+    HIP_TRY(h, h->h_more.ensure(4));
     unsigned *more_status = h->status.p + 1;
     HIP_TRY(h, hipMemsetAsync(more_status, 0, sizeof(unsigned), st));
     for (int p = 0; p < kLjacPasses; ++p) {
@@ -2948,7 +2939,7 @@ int pfc_local_jacobian_device(pfc_handle h, double *d_L, void *stream) {
     }
     hipLaunchKernelGGL(k_ljac_pack, dim3((unsigned)((n * kLjacSize + 255) / 256)), dim3(256), 0, st, n_items, h->ljac_out.p, d_L);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(h->h_more, more_status, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(h->h_more.p, more_status, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     h->pending_more = true; h->last_stream = st; h->last_dual_reused = true;
     return PFC_OK;
 }
@@ -3001,12 +2992,9 @@ int pfc_local_jacobian(pfc_handle h, int n_items, const int *ins_ids, const doub
 // [d_wrench; d_sdot] = L . seeds for every (item, direction): no handle state is read or changed, only the device and its stream.
 int pfc_apply_local_jacobian_device(pfc_handle h, int n_items, int n_dir, const double *d_L, const double *d_dpose, const double *d_dtwist,
                                     const double *d_ds, double *d_dwrench, double *d_dsdot, void *stream) {
-    if (h && h->multi) {      // L and the seeds of a multi-device evaluation are on the first device: so is this
-        const int rc = pfc_apply_local_jacobian_device(h->multi->shard[0], n_items, n_dir, d_L, d_dpose, d_dtwist, d_ds, d_dwrench,
-                                                       d_dsdot, stream);
-        if (rc != PFC_OK) h->err = h->multi->shard[0]->err;
-        return rc;
-    }
+    if (h && h->multi)      // L and the seeds of a multi-device evaluation are on the first device: so is this
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_apply_local_jacobian_device(c, n_items, n_dir, d_L, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, stream); });
     if (!h || n_items < 0 || n_dir < 1 || n_dir > 16)
         return fail(h, PFC_ERR_BAD_ARG, "pfc_apply_local_jacobian_device: n_items >= 0 and n_dir in 1..16");
     if (n_items == 0) return PFC_OK;
@@ -3036,8 +3024,8 @@ int pfc_apply_local_jacobian(pfc_handle h, int n_items, int n_dir, const double 
     HIP_TRY(h, hipMemcpyAsync(dp, d_pose, sizeof(double) * nk * 24, hipMemcpyHostToDevice, st));
     HIP_TRY(h, hipMemcpyAsync(dt, d_twist, sizeof(double) * nk * 6, hipMemcpyHostToDevice, st));
     if (d_s) HIP_TRY(h, hipMemcpyAsync(ds, d_s, sizeof(double) * nk * 6, hipMemcpyHostToDevice, st));
-    const int rc = pfc_apply_local_jacobian_device(c, n_items, n_dir, dL, dp, dt, d_s ? ds : nullptr, dw, dsd, st);
-    if (rc != PFC_OK) { if (c != h) h->err = c->err; return rc; }
+    const int rc = on_shard(h, c, [&](pfc_context *c1) { return pfc_apply_local_jacobian_device(c1, n_items, n_dir, dL, dp, dt, d_s ? ds : nullptr, dw, dsd, st); });
+    if (rc != PFC_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(d_wrench, dw, sizeof(double) * nk * 6, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipMemcpyAsync(d_sdot, dsd, sizeof(double) * nk * 6, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
@@ -3057,19 +3045,19 @@ int pfc_eval_dual_bp(pfc_handle h, int n_items, int n_dir, const int *ins_ids, c
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t bytes = sizeof(double) * 24 * (size_t)n_items;
     {
-        const void *p0 = h->pin_bp;
-        HIP_TRY(h, ensure_pinned(&h->pin_bp, &h->pin_bp_cap, bytes));
-        if (h->pin_bp != p0) h->pin_bp_n = -1;
+        bool moved;
+        HIP_TRY(h, h->pin_bp.ensure(bytes, &moved));
+        if (moved) h->pin_bp_n = -1;
     }
-    if (h->pin_bp_n != n_items || std::memcmp(h->pin_bp, bp_pose, bytes) != 0) {
+    if (h->pin_bp_n != n_items || std::memcmp(h->pin_bp.p, bp_pose, bytes) != 0) {
         // another broadphase pose: nothing a previous Dual evaluation left can be reused (the candidate lists differ)
         end_kept_pass(h);
         h->pin_in_pt = {}; h->pin_din_pt = {};
-        std::memcpy(h->pin_bp, bp_pose, bytes);
+        std::memcpy(h->pin_bp.p, bp_pose, bytes);
         h->pin_bp_n = n_items;
     }
     void *dev = nullptr;
-    HIP_TRY(h, hipHostGetDevicePointer(&dev, h->pin_bp, 0));
+    HIP_TRY(h, hipHostGetDevicePointer(&dev, h->pin_bp.p, 0));
     h->bp_dev = (const double *)dev;
     const int rc = pfc_eval_dual(h, n_items, n_dir, ins_ids, pose, twist, s, d_pose, d_twist, d_s, wrench, sdot, d_wrench, d_sdot, counts);
     h->bp_dev = nullptr;
@@ -3095,8 +3083,8 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
     { const int rc = check_eval_args(h, n_items, ins_ids, pose, twist, s, wrench, sdot); if (rc != PFC_OK) return rc; }
     // A repeat of the previous small-scene Dual evaluation's point (the next chunk of a Jacobian): leave the all-in-one
     // kernel, whose Dual passes keep nothing, for the hybrid path, which hands lists over that the chunks after it reuse.
-    const bool repeat = n_items > 0 && h->opt_dual_reuse && h->pin_in_pt.n == n_items && h->pin_in && h->pin_in_pt.ids == (ins_ids != nullptr) &&
-                        same_point((const double *)h->pin_in, (size_t)n_items, h->pin_in_pt.ids_at, ins_ids, pose, twist, s, false);
+    const bool repeat = n_items > 0 && h->opt_dual_reuse && h->pin_in_pt.n == n_items && h->pin_in.p && h->pin_in_pt.ids == (ins_ids != nullptr) &&
+                        same_point((const double *)h->pin_in.p, (size_t)n_items, h->pin_in_pt.ids_at, ins_ids, pose, twist, s, false);
     if (!repeat) h->pin_in_pt = {};
     if (n_items > 0 && !h->any_bristle && fused_ok(h, n_items) && !repeat) {
         if (h->dual_fused_skip > 0) {
@@ -3135,14 +3123,14 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
         const size_t in_d = n * 36 + nk * 36, in_bytes = in_d * sizeof(double) + n * sizeof(int);
         const size_t out_d = n * 12 + nk * 12, out_bytes = out_d * sizeof(double) + n * 4 * sizeof(int);
         {
-            const void *p0 = h->pin_din, *q0 = h->pin_dout;
-            HIP_TRY(h, ensure_pinned(&h->pin_din, &h->pin_din_cap, in_bytes));
-            HIP_TRY(h, ensure_pinned(&h->pin_dout, &h->pin_dout_cap, out_bytes));
-            if (h->pin_din != p0 || h->pin_dout != q0) h->pin_din_pt = {};      // reallocated: the cached blocks are gone
+            bool in_moved, out_moved;
+            HIP_TRY(h, h->pin_din.ensure(in_bytes, &in_moved));
+            HIP_TRY(h, h->pin_dout.ensure(out_bytes, &out_moved));
+            if (in_moved || out_moved) h->pin_din_pt = {};      // reallocated: the cached blocks are gone
         }
-        HIP_TRY(h, ensure_dual(h, h->dual_in, in_d + (n + 1) / 2 + 1));
-        HIP_TRY(h, ensure_dual(h, h->dual_out, out_d + (n * 4 + 1) / 2 + 1));
-        double *pi = (double *)h->pin_din;
+        HIP_TRY(h, ensure_graphed(h, h->dual_in, in_d + (n + 1) / 2 + 1));
+        HIP_TRY(h, ensure_graphed(h, h->dual_out, out_d + (n * 4 + 1) / 2 + 1));
+        double *pi = (double *)h->pin_din.p;
         double *pd = pi + n * 36;
         double *di = h->dual_in.p, *dd = di + n * 36, *dout = h->dual_out.p, *ddo = dout + n * 12;
         // Further seed directions at the point of the previous Dual evaluation (the chunks of one Jacobian: Radau calls
@@ -3163,11 +3151,11 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
             HIP_TRY(h, hipMemcpyAsync(dd, pd, sizeof(double) * nk * 36, hipMemcpyHostToDevice, st));
             int rc3 = pfc_eval_dual_device_more(h, n_dir, dd, dd + nk * 24, dd + nk * 30, ddo, ddo + nk * 6, st);
             if (rc3 != PFC_OK) return rc3;
-            double *pdo = (double *)h->pin_dout + n * 12;
+            double *pdo = (double *)h->pin_dout.p + n * 12;
             HIP_TRY(h, hipMemcpyAsync(pdo, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
             rc3 = pfc_check(h);
             if (rc3 != PFC_OK) return rc3;
-            copy_out((const double *)h->pin_dout, h->dual_counts_cache.data(), n, wrench, sdot, counts);
+            copy_out((const double *)h->pin_dout.p, h->dual_counts_cache.data(), n, wrench, sdot, counts);
             copy_out_dual(pdo, nk, d_wrench, d_sdot);
             return PFC_OK;
         }
@@ -3181,12 +3169,12 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
                                        s ? di + n * 30 : nullptr, dd, dd + nk * 24, dd + nk * 30, dout, dout + n * 6,
                                        ddo, ddo + nk * 6, (int *)(dout + out_d), st);
             if (rc2 != PFC_OK) return rc2;
-            HIP_TRY(h, hipMemcpyAsync(h->pin_dout, dout, out_bytes, hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipMemcpyAsync(h->pin_dout.p, dout, out_bytes, hipMemcpyDeviceToHost, st));
             rc2 = pfc_check(h);
             if (rc2 != PFC_ERR_OVERFLOW) break;
         }
         if (rc2 != PFC_OK) return rc2;
-        const double *po = (const double *)h->pin_dout;
+        const double *po = (const double *)h->pin_dout.p;
         const int *pc = reinterpret_cast<const int *>(po + out_d);
         copy_out(po, pc, n, wrench, sdot, counts);
         copy_out_dual(po + n * 12, nk, d_wrench, d_sdot);
@@ -3202,24 +3190,24 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
     int rc = pfc_eval(h, n_items, ins_ids, pose, twist, s, wrench, sdot, counts);
     h->want_surv = false;
     if (rc != PFC_OK) return rc;
-    HIP_TRY(h, ensure_dual(h, h->dual_in, nk * 36));
-    HIP_TRY(h, ensure_dual(h, h->dual_acc, nk * kDaStride));
-    HIP_TRY(h, ensure_dual(h, h->dual_res, nk * kDrStride));
-    HIP_TRY(h, ensure_dual(h, h->dual_out, nk * 12));
+    HIP_TRY(h, ensure_graphed(h, h->dual_in, nk * 36));
+    HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
+    HIP_TRY(h, ensure_graphed(h, h->dual_res, nk * kDrStride));
+    HIP_TRY(h, ensure_graphed(h, h->dual_out, nk * 12));
     double *dp = h->dual_in.p, *dt = dp + nk * 24, *dsd = dt + nk * 6;
     // one pinned block up (d_pose | d_twist | d_s), one down (d_wrench | d_sdot), as in pfc_eval (whose staging
     // buffers are free again at this point)
     const size_t in_bytes = sizeof(double) * nk * 36, out_bytes = sizeof(double) * nk * 12;
-    HIP_TRY(h, ensure_pinned(&h->pin_in, &h->pin_in_cap, in_bytes));
-    HIP_TRY(h, ensure_pinned(&h->pin_out, &h->pin_out_cap, out_bytes));
-    pack_seeds((double *)h->pin_in, nk, d_pose, d_twist, d_s, true);
-    HIP_TRY(h, hipMemcpyAsync(dp, h->pin_in, in_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, h->pin_in.ensure(in_bytes));
+    HIP_TRY(h, h->pin_out.ensure(out_bytes));
+    pack_seeds((double *)h->pin_in.p, nk, d_pose, d_twist, d_s, true);
+    HIP_TRY(h, hipMemcpyAsync(dp, h->pin_in.p, in_bytes, hipMemcpyHostToDevice, st));
     rc = launch_dual(h, n_items, n_dir, h->tail.p, dp, dt, dsd, h->dual_out.p, h->dual_out.p + nk * 6, (size_t)h->stats[2], st, nullptr);
     if (rc != PFC_OK) return rc;
     h->dual_hint = h->stats[2];
-    HIP_TRY(h, hipMemcpyAsync(h->pin_out, h->dual_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(h->pin_out.p, h->dual_out.p, out_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
-    copy_out_dual((const double *)h->pin_out, nk, d_wrench, d_sdot);
+    copy_out_dual((const double *)h->pin_out.p, nk, d_wrench, d_sdot);
     return PFC_OK;
 }
 
@@ -3229,8 +3217,8 @@ int pfc_set_option(pfc_handle h, const char *name, long long value) {
         if (!std::strcmp(name, "multi_min")) { h->multi->opt_min_items = value < 1 ? 1 : (int)value; h->multi->part_n = 0; return PFC_OK; }
         h->multi->dev_kept = false;      // (as every shard's kept pass below)
         for (pfc_context *c : h->multi->shard) {
-            const int rc = pfc_set_option(c, name, value);
-            if (rc != PFC_OK) { h->err = c->err; return rc; }
+            const int rc = on_shard(h, c, [&](pfc_context *c1) { return pfc_set_option(c1, name, value); });
+            if (rc != PFC_OK) return rc;
         }
         return PFC_OK;
     }
@@ -3278,11 +3266,8 @@ int pfc_get_stats(pfc_handle h, long long *out8) {
 
 int pfc_get_stage_ms(pfc_handle h, float *out6) {
     if (!h || !out6) return PFC_ERR_BAD_ARG;
-    if (h->multi) {      // the first shard's stages (every shard runs the same sequence on its range)
-        const int rc = pfc_get_stage_ms(h->multi->shard[0], out6);
-        if (rc != PFC_OK) h->err = h->multi->shard[0]->err;
-        return rc;
-    }
+    if (h->multi)      // the first shard's stages (every shard runs the same sequence on its range)
+        return on_first_shard(h, [&](pfc_context *c) { return pfc_get_stage_ms(c, out6); });
     if (!h->ev_valid) return fail(h, PFC_ERR_STATE, "profile option was off for the last evaluation");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipEventSynchronize(h->ev[EV_FIN]));
@@ -3319,9 +3304,7 @@ int pfc_debug_pairs(pfc_handle h, int item, int *pairs, int *clip_n, int cap) {
         int local = 0;
         pfc_context *c = multi_locate(h, item, &local);
         if (!c) return -fail(h, PFC_ERR_BAD_ARG, "bad item");
-        const int r = pfc_debug_pairs(c, local, pairs, clip_n, cap);
-        if (r < 0) h->err = c->err;
-        return r;
+        return on_shard(h, c, [&](pfc_context *c1) { return pfc_debug_pairs(c1, local, pairs, clip_n, cap); }, true);
     }
     if (!h->opt_debug) return -fail(h, PFC_ERR_STATE, "debug option is off");
     if (h->pending) { int rc = check_eval(h); if (rc) return -rc; }
@@ -3352,9 +3335,7 @@ int pfc_debug_tractions(pfc_handle h, int item, double *buf, int cap) {
         int local = 0;
         pfc_context *c = multi_locate(h, item, &local);
         if (!c) return -fail(h, PFC_ERR_BAD_ARG, "bad item");
-        const int r = pfc_debug_tractions(c, local, buf, cap);
-        if (r < 0) h->err = c->err;
-        return r;
+        return on_shard(h, c, [&](pfc_context *c1) { return pfc_debug_tractions(c1, local, buf, cap); }, true);
     }
     if (!h->opt_debug) return -fail(h, PFC_ERR_STATE, "debug option is off");
     if (h->pending) { int rc = check_eval(h); if (rc) return -rc; }
@@ -3385,9 +3366,7 @@ int pfc_debug_stiffness(pfc_handle h, int item, double *K36, double *Kis36, doub
         int local = 0;
         pfc_context *c = multi_locate(h, item, &local);
         if (!c) return -fail(h, PFC_ERR_BAD_ARG, "bad item");
-        const int r = pfc_debug_stiffness(c, local, K36, Kis36, Sinv6, cop3);
-        if (r < 0) h->err = c->err;
-        return r;
+        return on_shard(h, c, [&](pfc_context *c1) { return pfc_debug_stiffness(c1, local, K36, Kis36, Sinv6, cop3); }, true);
     }
     if (h->pending) { int rc = check_eval(h); if (rc) return -rc; }
     if (h->last_fused)      // the fused small-scene kernel keeps K in LDS only
@@ -3409,11 +3388,9 @@ int pfc_debug_stiffness(pfc_handle h, int item, double *K36, double *Kis36, doub
 int pfc_scatter_generalized(pfc_handle h, int n_items, const double *wrench, const double *x_w_r2, const int *body_1,
                             const int *body_2, const int *scene, int n_scene, int n_body, int nv, const double *jac,
                             double *f_out) {
-    if (h && h->multi) {      // a few microseconds of work: the first device does it
-        const int rc = pfc_scatter_generalized(h->multi->shard[0], n_items, wrench, x_w_r2, body_1, body_2, scene, n_scene, n_body, nv, jac, f_out);
-        if (rc != PFC_OK) h->err = h->multi->shard[0]->err;
-        return rc;
-    }
+    if (h && h->multi)      // a few microseconds of work: the first device does it
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_scatter_generalized(c, n_items, wrench, x_w_r2, body_1, body_2, scene, n_scene, n_body, nv, jac, f_out); });
     if (!h || n_items < 0 || nv <= 0 || n_scene <= 0 || n_body < 0 || !f_out)
         return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized: bad argument");
     if (n_items > 0 && (!wrench || !x_w_r2 || !body_1 || !body_2 || (n_body > 0 && !jac)))
@@ -3453,12 +3430,10 @@ int pfc_scatter_generalized(pfc_handle h, int n_items, const double *wrench, con
 int pfc_scatter_generalized_device(pfc_handle h, int n_items, const double *d_wrench, const double *d_x_w_r2, const int *d_body_1,
                                    const int *d_body_2, const int *d_scene, int n_scene, int nv, const double *d_jac, double *d_f,
                                    int accumulate, void *stream) {
-    if (h && h->multi) {      // the wrenches of a multi-device evaluation end up on the first device: so does this
-        const int rc = pfc_scatter_generalized_device(h->multi->shard[0], n_items, d_wrench, d_x_w_r2, d_body_1, d_body_2, d_scene, n_scene, nv,
-                                                      d_jac, d_f, accumulate, stream);
-        if (rc != PFC_OK) h->err = h->multi->shard[0]->err;
-        return rc;
-    }
+    if (h && h->multi)      // the wrenches of a multi-device evaluation end up on the first device: so does this
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_scatter_generalized_device(c, n_items, d_wrench, d_x_w_r2, d_body_1, d_body_2, d_scene, n_scene, nv, d_jac, d_f, accumulate,
+                                                  stream); });
     if (!h || n_items < 0 || nv <= 0 || n_scene <= 0 || !d_f)
         return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_device: bad argument");
     if (n_items > 0 && (!d_wrench || !d_x_w_r2 || !d_body_1 || !d_body_2 || !d_jac))
@@ -3505,12 +3480,10 @@ int pfc_scatter_generalized_dual(pfc_handle h, int n_items, int n_dir, const dou
                                  const double *x_w_r2, const double *d_x_w_r2, const int *body_1, const int *body_2,
                                  const int *scene, int n_scene, int n_body, int nv, const double *jac, const double *d_jac,
                                  double *f_out, double *d_f_out) {
-    if (h && h->multi) {      // as pfc_scatter_generalized: the first device does it
-        const int rc = pfc_scatter_generalized_dual(h->multi->shard[0], n_items, n_dir, wrench, d_wrench, x_w_r2, d_x_w_r2, body_1,
-                                                    body_2, scene, n_scene, n_body, nv, jac, d_jac, f_out, d_f_out);
-        if (rc != PFC_OK) h->err = h->multi->shard[0]->err;
-        return rc;
-    }
+    if (h && h->multi)      // as pfc_scatter_generalized: the first device does it
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_scatter_generalized_dual(c, n_items, n_dir, wrench, d_wrench, x_w_r2, d_x_w_r2, body_1, body_2, scene, n_scene, n_body, nv,
+                                                jac, d_jac, f_out, d_f_out); });
     if (!h || n_items < 0 || n_dir < 1 || n_dir > kScatMaxDir || nv <= 0 || n_scene <= 0 || n_body < 0 || !d_f_out)
         return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual: bad argument");
     if ((long long)n_scene * n_items >= (1ll << 31))
@@ -3569,13 +3542,10 @@ int pfc_scatter_generalized_dual_device(pfc_handle h, int n_items, int n_dir, co
                                         const double *d_x_w_r2, const double *d_dx_w_r2, const int *d_body_1, const int *d_body_2,
                                         const int *d_scene, int n_scene, int nv, const double *d_jac, const double *d_djac,
                                         double *d_f, double *d_df, int accumulate, void *stream) {
-    if (h && h->multi) {      // the wrenches of a multi-device evaluation end up on the first device: so does this
-        const int rc = pfc_scatter_generalized_dual_device(h->multi->shard[0], n_items, n_dir, d_wrench_val, d_dwrench, d_x_w_r2,
-                                                           d_dx_w_r2, d_body_1, d_body_2, d_scene, n_scene, nv, d_jac, d_djac, d_f,
-                                                           d_df, accumulate, stream);
-        if (rc != PFC_OK) h->err = h->multi->shard[0]->err;
-        return rc;
-    }
+    if (h && h->multi)      // the wrenches of a multi-device evaluation end up on the first device: so does this
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_scatter_generalized_dual_device(c, n_items, n_dir, d_wrench_val, d_dwrench, d_x_w_r2, d_dx_w_r2, d_body_1, d_body_2, d_scene,
+                                                       n_scene, nv, d_jac, d_djac, d_f, d_df, accumulate, stream); });
     if (!h || n_items < 0 || n_dir < 1 || n_dir > kScatMaxDir || nv <= 0 || n_scene <= 0 || !d_df)
         return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual_device: bad argument");
     if ((long long)n_scene * n_items >= (1ll << 31))
@@ -3623,16 +3593,15 @@ int pfc_selftest_math(pfc_handle h, int n, const double *x, const double *y, dou
     if (!h || n <= 0 || !x || !y || !out3n) return PFC_ERR_BAD_ARG;
     if (h->multi) return pfc_selftest_math(h->multi->shard[0], n, x, y, out3n);
     HIP_TRY(h, hipSetDevice(h->device));
-    double *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    HIP_TRY(h, hipMalloc((void **)&dx, sizeof(double) * n));
-    HIP_TRY(h, hipMalloc((void **)&dy, sizeof(double) * n));
-    HIP_TRY(h, hipMalloc((void **)&dout, sizeof(double) * 3 * (size_t)n));
-    HIP_TRY(h, copy_sync(h, dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
-    HIP_TRY(h, copy_sync(h, dy, y, sizeof(double) * n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_selftest, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, dx, dy, dout);
+    DevBuf<double> dx, dy, dout;
+    HIP_TRY(h, dx.ensure(n));
+    HIP_TRY(h, dy.ensure(n));
+    HIP_TRY(h, dout.ensure(3 * (size_t)n));
+    HIP_TRY(h, copy_sync(h, dx.p, x, sizeof(double) * n, hipMemcpyHostToDevice));
+    HIP_TRY(h, copy_sync(h, dy.p, y, sizeof(double) * n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_selftest, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, dx.p, dy.p, dout.p);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, copy_sync(h, out3n, dout, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost));
-    (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dout);
+    HIP_TRY(h, copy_sync(h, out3n, dout.p, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost));
     return PFC_OK;
 }
 
@@ -3640,19 +3609,18 @@ int pfc_selftest_kis(pfc_handle h, int n, const double *Kbar36, const double *dK
     if (!h || n <= 0 || !Kbar36 || !dKbar36 || !out72) return PFC_ERR_BAD_ARG;
     if (h->multi) return pfc_selftest_kis(h->multi->shard[0], n, Kbar36, dKbar36, Vlam42, out72);
     HIP_TRY(h, hipSetDevice(h->device));
-    double *dk = nullptr, *ddk = nullptr, *dvl = nullptr, *dout = nullptr;
-    HIP_TRY(h, hipMalloc((void **)&dk, sizeof(double) * 36 * (size_t)n));
-    HIP_TRY(h, hipMalloc((void **)&ddk, sizeof(double) * 36 * (size_t)n));
-    HIP_TRY(h, hipMalloc((void **)&dout, sizeof(double) * 72 * (size_t)n));
-    if (Vlam42) HIP_TRY(h, hipMalloc((void **)&dvl, sizeof(double) * 42 * (size_t)n));
-    HIP_TRY(h, copy_sync(h, dk, Kbar36, sizeof(double) * 36 * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(h, copy_sync(h, ddk, dKbar36, sizeof(double) * 36 * (size_t)n, hipMemcpyHostToDevice));
-    if (Vlam42) HIP_TRY(h, copy_sync(h, dvl, Vlam42, sizeof(double) * 42 * (size_t)n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_selftest_kis, dim3(n), dim3(64), 0, h->stream, n, dk, ddk, dvl, dout);
+    DevBuf<double> dk, ddk, dvl, dout;
+    HIP_TRY(h, dk.ensure(36 * (size_t)n));
+    HIP_TRY(h, ddk.ensure(36 * (size_t)n));
+    HIP_TRY(h, dout.ensure(72 * (size_t)n));
+    if (Vlam42) HIP_TRY(h, dvl.ensure(42 * (size_t)n));
+    HIP_TRY(h, copy_sync(h, dk.p, Kbar36, sizeof(double) * 36 * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(h, copy_sync(h, ddk.p, dKbar36, sizeof(double) * 36 * (size_t)n, hipMemcpyHostToDevice));
+    if (Vlam42) HIP_TRY(h, copy_sync(h, dvl.p, Vlam42, sizeof(double) * 42 * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_selftest_kis, dim3(n), dim3(64), 0, h->stream, n, dk.p, ddk.p, dvl.p, dout.p);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, copy_sync(h, out72, dout, sizeof(double) * 72 * (size_t)n, hipMemcpyDeviceToHost));
-    (void)hipFree(dk); (void)hipFree(ddk); (void)hipFree(dvl); (void)hipFree(dout);
+    HIP_TRY(h, copy_sync(h, out72, dout.p, sizeof(double) * 72 * (size_t)n, hipMemcpyDeviceToHost));
     return PFC_OK;
 }
 

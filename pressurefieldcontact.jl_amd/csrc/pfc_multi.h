@@ -33,8 +33,7 @@ struct pfc_multi {
     std::vector<int> part_ins;             // the ins_ids the partition (and the costs) belong to (host-pointer entry points)
     std::vector<double> cost;
     bool counts_valid = false;
-    int *h_counts = nullptr;               // pinned: n x 4 counters of the last evaluation
-    size_t h_counts_cap = 0;
+    PinBuf<int, 2> h_counts;               // pinned: n x 4 counters of the last evaluation
     std::vector<int> iota;
     long long stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // ---- worker threads (host-pointer entry points) ----
@@ -51,10 +50,10 @@ struct pfc_multi {
     struct Stage {
         DevBuf<double> in, out, din, dout;
         DevBuf<int> ids, cnt, iota;
-        hipEvent_t done = nullptr;
+        Event done;
     };
     std::vector<Stage> stage;
-    hipEvent_t ev_fork = nullptr;
+    Event ev_fork;
     bool dev_pending = false;              // a device-pointer evaluation is enqueued and not checked yet
     const int *dev_counts = nullptr;       // where shard k's counters lie on ITS device: stage[k].cnt (k = 0: the caller's array or stage[0].cnt)
     hipStream_t dev_stream = nullptr;
@@ -137,7 +136,7 @@ void multi_partition(pfc_context *h, int n, const int *ins_ids, bool has_ids, bo
                            (is_dev || !ins_ids || std::memcmp(M->part_ins.data(), ins_ids, sizeof(int) * (size_t)n) == 0);
     M->cost.resize((size_t)n);
     if (same_list && M->counts_valid) {
-        for (int i = 0; i < n; ++i) M->cost[i] = 64.0 + (double)M->h_counts[4 * (size_t)i] + 4.0 * (double)M->h_counts[4 * (size_t)i + 1];
+        for (int i = 0; i < n; ++i) M->cost[i] = 64.0 + (double)M->h_counts.p[4 * (size_t)i] + 4.0 * (double)M->h_counts.p[4 * (size_t)i + 1];
     } else {
         const pfc_context *c0 = M->shard[0];
         for (int i = 0; i < n; ++i) {
@@ -183,12 +182,10 @@ void multi_partition(pfc_context *h, int n, const int *ins_ids, bool has_ids, bo
 
 int multi_ensure_host(pfc_context *h, int n) {
     pfc_multi *M = h->multi;
-    if (M->h_counts_cap < (size_t)n * 4) {
-        if (M->h_counts) (void)hipHostFree(M->h_counts);
-        M->h_counts = nullptr; M->h_counts_cap = 0; M->counts_valid = false;
-        HIP_TRY(h, hipHostMalloc((void **)&M->h_counts, sizeof(int) * (size_t)n * 8));
-        M->h_counts_cap = (size_t)n * 8;
-    }
+    bool moved = false;
+    const hipError_t e = M->h_counts.ensure((size_t)n * 4, &moved);
+    if (moved) M->counts_valid = false;
+    HIP_TRY(h, e);
     if ((int)M->iota.size() < n) {
         const int n0 = (int)M->iota.size();
         M->iota.resize((size_t)n * 2);
@@ -233,7 +230,7 @@ int multi_eval(pfc_context *h, int n_items, const int *ins_ids, const double *po
     multi_partition(h, n_items, ins_ids, ins_ids != nullptr, false);
     M->dev_pending = false; M->dev_kept = false;
     const int *ids = ins_ids ? ins_ids : M->iota.data();
-    int *cnt = M->h_counts;
+    int *cnt = M->h_counts.p;
     std::vector<std::function<int()>> jobs((size_t)M->n_used);
     for (int k = 0; k < M->n_used; ++k) {
         const int b0 = M->bound[k], nk = M->bound[k + 1] - b0;
@@ -265,7 +262,7 @@ int multi_eval_dual(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     multi_partition(h, n_items, ins_ids, ins_ids != nullptr, false);
     M->dev_pending = false; M->dev_kept = false;
     const int *ids = ins_ids ? ins_ids : M->iota.data();
-    int *cnt = M->h_counts;
+    int *cnt = M->h_counts.p;
     const size_t nd = (size_t)n_dir;
     std::vector<std::function<int()>> jobs((size_t)M->n_used);
     for (int k = 0; k < M->n_used; ++k) {
@@ -519,7 +516,7 @@ int multi_check(pfc_context *h) {
         if (!more) {
             const int *src = k == 0 ? M->dev_counts : M->stage[k].cnt.p;
             hipStream_t sk = k == 0 ? M->dev_stream : c->stream;
-            if (hipMemcpyAsync(M->h_counts + 4 * (size_t)M->bound[k], src, sizeof(int) * 4 * (size_t)nk, hipMemcpyDeviceToHost, sk) != hipSuccess)
+            if (hipMemcpyAsync(M->h_counts.p + 4 * (size_t)M->bound[k], src, sizeof(int) * 4 * (size_t)nk, hipMemcpyDeviceToHost, sk) != hipSuccess)
                 (void)hipGetLastError();
         }
         const int rk = pfc_check(c);
@@ -550,6 +547,26 @@ pfc_context *multi_locate(pfc_context *h, int item, int *local) {
     return nullptr;
 }
 
+// An entry point run on shard c of a multi-device handle h: a failure -- a status other than PFC_OK, or a negative id / count
+// where the entry point returns one (`count`) -- leaves the shard's message in h.
+template <class F>
+int on_shard(pfc_context *h, pfc_context *c, F call, bool count = false) {
+    const int r = call(c);
+    if (count ? r < 0 : r != PFC_OK) h->err = c->err;
+    return r;
+}
+// ... on the first shard: what runs on one device only (the scatter calls, the contact surface, L times seeds, the stage times).
+template <class F>
+int on_first_shard(pfc_context *h, F call) { return on_shard(h, h->multi->shard[0], call); }
+
+// A surface call on a multi-device handle runs on the first device's context; the handle's pending device-pointer evaluation
+// and its Dual reuse end here, as with any other evaluation.
+template <class F>
+int surface_ctx(pfc_context *h, F call) {
+    h->multi->dev_pending = false; h->multi->dev_kept = false;
+    return on_first_shard(h, call);
+}
+
 void multi_destroy(pfc_context *h) {
     pfc_multi *M = h->multi;
     for (pfc_multi::Worker *w : M->workers) {
@@ -561,16 +578,10 @@ void multi_destroy(pfc_context *h) {
     for (size_t k = 0; k < M->shard.size(); ++k) {
         (void)hipSetDevice(M->dev[k]);
         if (M->shard[k]->stream) (void)hipStreamSynchronize(M->shard[k]->stream);
-        if (k < M->stage.size()) {
-            pfc_multi::Stage &S = M->stage[k];
-            S.in.release(); S.out.release(); S.din.release(); S.dout.release(); S.ids.release(); S.cnt.release(); S.iota.release();
-            if (S.done) (void)hipEventDestroy(S.done);
-        }
+        if (k < M->stage.size()) M->stage[k] = pfc_multi::Stage();      // its staging goes with the shard's device current
         pfc_destroy(M->shard[k]);
     }
     (void)hipSetDevice(M->dev.empty() ? 0 : M->dev[0]);
-    if (M->ev_fork) (void)hipEventDestroy(M->ev_fork);
-    if (M->h_counts) (void)hipHostFree(M->h_counts);
     delete M;
     h->multi = nullptr;
 }
