@@ -421,7 +421,11 @@ int pfc_contact_surface_fric_device(pfc_handle h, int n_items, const int *d_ins_
  * launch sequence -- the scene sizes Radau evaluates, src/radau/radau_functions.jl:2-14,64-70; same results; 0 = always
  * batched; the debug / profile options imply the batched path), "clip_queue" (default 1: the clip-only kernel of a
  * tri-tet launch queues the candidates that pass the trivial reject in its polygon ring and clips 64 of them at a time;
- * 0 = the lane-per-candidate clip rounds; same results bit for bit), "team" (default 48, at most 48; 0 = never: an evaluation of a few
+ * 0 = the lane-per-candidate clip rounds; same results bit for bit), "vertex_fields" (default 1: the bristle friction pass
+ * over the kept polygons, k_fric, evaluates pressure, damping argument and bristle traction once per fan corner and combines
+ * them per quadrature point -- they are affine in the point; 0 = re-derives them at every point as the counting kernels do;
+ * counts identical, friction wrench equal to rounding: ~1e-15 relative; "debug" evaluations always use the per-point form, so that the
+ * friction sums are formed at exactly the traction points pfc_debug_tractions returns; other values PFC_ERR_BAD_ARG), "team" (default 48, at most 48; 0 = never: an evaluation of a few
  * pairs too big for one workgroup -- BASELINE's single 9 680-tet x 5 120-triangle pair -- runs as ONE kernel with a team
  * of up to this many workgroups per item -- while a workgroup of the team has at most ~1 200 leaves of the pair to descend: up
  * to 16 poses of that pair; beyond that the batched path is faster --, and a few mid-sized items -- a 972-tet box on the

@@ -500,6 +500,7 @@ struct pfc_context {
     // reference-sized scene sorts 1 024 keys in one launch instead of 65 536 in fifteen.
     size_t sort_cover = 0;                    // 0: the capacity
     size_t sort_cover_used = 0;               // what the pending evaluation covered
+    int opt_vertex_fields = 1;         // option "vertex_fields": k_fric<true> evaluates the fan-point fields per corner; 0: the per-point kernels
     int opt_clip_queue = 1;            // option "clip_queue": clip-only narrowphase of big tri-tet batches in k_clip_queue (survivors queued in the ring); 0: k_narrow<.., 2 / 3>
     int fused_skip = 0;                // evaluations left for which the fused kernel stays off after an item did not fit
     int fused_seq = 0;                 // sequence number of the last fused launch (completion word of the polled path)
@@ -955,11 +956,15 @@ int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double 
             HIP_TRY(h, hipMemsetAsync(h->vfx_head.p + n_items, 0, sizeof(int) * 2, st));
             fr.sink = FixedSink{h->vfx_rec.p, h->vfx_head.p + n_items, h->vfx_head.p, 0, 2, (int)n_pos, (int)(2 * n_pos), (int)cap, h->status.p};
         }
+        // "debug" keeps the per-point kernel: the friction sums are then formed at exactly the traction points the debug views hand out
+        const bool vertex_fields = h->opt_vertex_fields && !h->opt_debug;
         // (grid cap 256 x 32, twice the other narrowphase kernels': paired A/B 4.32 -> 4.22 ms per 8 192-pose step; x 64 and x 128 alike)
         if (fr.sink.rec) {
-            hipLaunchKernelGGL(k_fric_fixed, dim3(grid_for(h->ccap, 64, 256 * 32)), dim3(64), 0, st, fr);
+            if (vertex_fields) hipLaunchKernelGGL(k_fric_fixed<true>, dim3(grid_for(h->ccap, 64, 256 * 32)), dim3(64), 0, st, fr);
+            else hipLaunchKernelGGL(k_fric_fixed<false>, dim3(grid_for(h->ccap, 64, 256 * 32)), dim3(64), 0, st, fr);
             hipLaunchKernelGGL(k_fixed_reduce, dim3(n_items), dim3(64), 0, st, fr.sink, n_items, h->acc.p, kAccStride, kAccFric, 6);
-        } else hipLaunchKernelGGL(k_fric, dim3(grid_for(h->ccap, 64, 256 * 32)), dim3(64), 0, st, fr);
+        } else if (vertex_fields) hipLaunchKernelGGL(k_fric<true>, dim3(grid_for(h->ccap, 64, 256 * 32)), dim3(64), 0, st, fr);
+        else hipLaunchKernelGGL(k_fric<false>, dim3(grid_for(h->ccap, 64, 256 * 32)), dim3(64), 0, st, fr);
     }
     if (prof) HIP_TRY(h, hipEventRecord(h->ev[EV_BR], st));
     hipLaunchKernelGGL(k_final, dim3(grid_for(n_items, 128, 1 << 20)), dim3(128), 0, st, br);
@@ -1806,6 +1811,7 @@ int pfc_eval_device(pfc_handle h, int n_items, const int *d_ins_ids, const doubl
     t->opt_poison = h->opt_poison;
     if (t->opt_clip_min != h->opt_clip_min) { t->opt_clip_min = h->opt_clip_min; t->ghave[0] = t->ghave[1] = false; }
     if (t->opt_clip_queue != h->opt_clip_queue) { t->opt_clip_queue = h->opt_clip_queue; t->ghave[0] = t->ghave[1] = false; }
+    if (t->opt_vertex_fields != h->opt_vertex_fields) { t->opt_vertex_fields = h->opt_vertex_fields; t->ghave[0] = t->ghave[1] = false; }
     t->opt_graph = h->opt_graph;
     if (t->opt_no_filter != h->opt_no_filter) { t->opt_no_filter = h->opt_no_filter; t->ghave[0] = t->ghave[1] = false; }
     const int n0 = n_items / 2, n1 = n_items - n0;      // (55 / 45 is the same within noise, 60 / 40 and 45 / 55 are slower: round 3)
@@ -3236,6 +3242,10 @@ int pfc_set_option(pfc_handle h, const char *name, long long value) {
     else if (!std::strcmp(name, "dual_reuse")) h->opt_dual_reuse = (int)value;
     else if (!std::strcmp(name, "clip_min")) { h->opt_clip_min = (int)value; h->ghave[0] = h->ghave[1] = false; h->dghave = false; }
     else if (!std::strcmp(name, "clip_queue")) { h->opt_clip_queue = (int)value; h->ghave[0] = h->ghave[1] = false; h->dghave = false; }
+    else if (!std::strcmp(name, "vertex_fields")) {
+        if (value != 0 && value != 1) return fail(h, PFC_ERR_BAD_ARG, "vertex_fields must be 0 (per-point k_fric) or 1 (per-corner fields)");
+        h->opt_vertex_fields = (int)value; h->ghave[0] = h->ghave[1] = false; h->dghave = false;
+    }
     else if (!std::strcmp(name, "poison")) h->opt_poison = value != 0;
     else if (!std::strcmp(name, "fused")) { h->opt_fused = value != 0; h->fused_skip = 0; }
     else if (!std::strcmp(name, "team")) h->opt_team = value < 0 ? 0 : (value > kTeamMaxWg ? kTeamMaxWg : (int)value);

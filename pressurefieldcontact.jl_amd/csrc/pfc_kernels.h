@@ -398,10 +398,13 @@ __device__ __forceinline__ bool pose_quat(const double *R, float *qf) {
 
 // The traction points of ONE fan triangle (v1, v2, polygon centroid): fillTractionCacheForTriangle! +
 // fillTractionCacheInnerLoop! (src/contact_algorithms_non_friction.jl:236-265) with TriTetQuadRule rules 1 and 2 (literal
-// decimals of src/clip/quadrature.jl:24-39).  The ONE statement of r, p and dA shared by every value kernel (k_narrow,
-// k_integ, k_fric, k_fused): the per-item traction counts and the bit-identity of the traction points between the
-// passes rest on these expressions being the same everywhere.  body(r, rdot, p, dA) is called for every point with
-// 0 < p (:245); returns the number of such points.
+// decimals of src/clip/quadrature.jl:24-39).  The ONE statement of r, p and dA shared by every kernel that COUNTS traction
+// points or hands them on (k_narrow, k_integ, k_fused, k_surf_*, and k_fric with option vertex_fields = 0): the per-item
+// traction counts and the bit-identity of the traction points between those passes rest on these expressions being the
+// same everywhere.  body(r, rdot, p, dA) is called for every point with 0 < p (:245); returns the number of such points.
+// The default k_fric does NOT use it: it evaluates the same fields per fan CORNER (FanFields below).  It counts nothing --
+// the counts and the kept / dropped decision of a polygon are k_narrow's / k_integ's, which stay on this statement, so
+// they are exact as before -- and its sums are compared by tolerance only.
 struct PointParams {
     V3 w, vl;                          // twist of the item: angular, linear
     double chi, Ebar, er0, er1, er2, er3;   // damping, modulus, the tet's strain row eps_r2
@@ -437,6 +440,57 @@ __device__ __forceinline__ int fan_triangle_points(const PointParams &c, const V
         body(r, rdot, p, dA);
     }
     return n_pt;
+}
+
+// The same fields stated per fan CORNER (option vertex_fields).  Everything a point needs before the pressure test is
+// affine in the point r: a(r) = eps.r + eps3 (eq above), d(r) = 1 + chi ee = d0 + dg.r with d0 = 1 - chi (eps.v),
+// dg = -chi (eps x w) (ee = -eps.(v + w x r), eps.(w x r) = (eps x w).r), and a kernel's own affine fields (k_fric: the
+// projected bristle traction, the arm).  A fan triangle shares v1, v2 with its neighbours and the centroid with all of them,
+// and a quadrature point is a fixed combination of the corners whose weights add up to 1.  So a field f is split into its
+// value at the centroid, fc (once per polygon), and its LINEAR part at the corner's offset from the centroid, f'(c - cen)
+// (once per corner, zero for the centroid), and then costs
+//   per triangle  S_f = fma(qa, f1' + f2', fc),      per point  f_q = fma(qb - qa, f'_corner(q), S_f),  centroid point: S_f
+// (point 0 leans on v2, 1 on v1, 2 on the centroid, as q0/q1/q2 above; rule 1: qa = 1/3, qb - qa = 0, one point).
+// Against the per-point statement this changes the rounding of eq and d by a few ulp of the sum of the magnitudes of their
+// terms: good for sums compared by tolerance, NOT for the test 0 < p where a traction count depends on it.
+struct FanFields {
+    double er0, er1, er2, er3;         // a(c)
+    double d0;                         // d(c) = d0 + dg.c
+    V3 dg;
+    double qa, qd, qw;                 // the rule: corner weight, qb - qa, point weight
+    int nq;
+};
+__device__ __forceinline__ FanFields fan_fields(const PointParams &c) {
+    FanFields f;
+    f.er0 = c.er0; f.er1 = c.er1; f.er2 = c.er2; f.er3 = c.er3;
+    const V3 e = mk3(c.er0, c.er1, c.er2);
+    f.d0 = __builtin_fma(-c.chi, dot(e, c.vl), 1.0);
+    f.dg = cross(e, c.w) * (-c.chi);
+    f.nq = c.nq;
+    if (c.nq == 1) { f.qa = 0.33333333333333331483; f.qd = 0.0; f.qw = 1.0; }
+    else { f.qa = 0.16666666666666674068; f.qd = 0.66666666666666651864 - 0.16666666666666674068; f.qw = 0.33333333333333331483; }
+    return f;
+}
+// the fields at the centroid, and their linear parts at an offset from it
+__device__ __forceinline__ double fan_field_a(const FanFields &f, const V3 &c) {
+    return __builtin_fma(f.er2, c.z, __builtin_fma(f.er1, c.y, __builtin_fma(f.er0, c.x, f.er3)));
+}
+__device__ __forceinline__ double fan_field_d(const FanFields &f, const V3 &c) {
+    return __builtin_fma(f.dg.z, c.z, __builtin_fma(f.dg.y, c.y, __builtin_fma(f.dg.x, c.x, f.d0)));
+}
+__device__ __forceinline__ double fan_linear_a(const FanFields &f, const V3 &r) {
+    return __builtin_fma(f.er2, r.z, __builtin_fma(f.er1, r.y, f.er0 * r.x));
+}
+__device__ __forceinline__ double fan_linear_d(const FanFields &f, const V3 &r) {
+    return __builtin_fma(f.dg.z, r.z, __builtin_fma(f.dg.y, r.y, f.dg.x * r.x));
+}
+__device__ __forceinline__ double fan_sum(const FanFields &f, double f1, double f2, double fc) { return __builtin_fma(f.qa, f1 + f2, fc); }
+__device__ __forceinline__ V3 fan_sum(const FanFields &f, const V3 &f1, const V3 &f2, const V3 &fc) {
+    return mk3(fan_sum(f, f1.x, f2.x, fc.x), fan_sum(f, f1.y, f2.y, fc.y), fan_sum(f, f1.z, f2.z, fc.z));
+}
+__device__ __forceinline__ double fan_at(const FanFields &f, double S, double corner) { return __builtin_fma(f.qd, corner, S); }
+__device__ __forceinline__ V3 fan_at(const FanFields &f, const V3 &S, const V3 &corner) {
+    return mk3(fan_at(f, S.x, corner.x), fan_at(f, S.y, corner.y), fan_at(f, S.z, corner.z));
 }
 
 // The 15 axes on Float32 inputs with a caller-supplied error radius E (see k_bp_dfs32).

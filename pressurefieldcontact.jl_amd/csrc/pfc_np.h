@@ -1386,7 +1386,9 @@ __global__ void __launch_bounds__(64, 2) k_integ_fixed(IntegArgs g) {
 
 // Bristle friction pass (after k_eig): calc_spatial_bristle_force (friction.jl:171-201) + traction(::Bristle) (:32-48)
 // over the polygons k_narrow kept.  One lane per kept polygon, every load is a coalesced read of consecutive slots;
-// the fan / quadrature arithmetic is the one of k_narrow, so the traction points are bit-identical.
+// the fan / quadrature arithmetic of fric_body<.., false> is the one of k_narrow, so its traction points are bit-identical;
+// fric_body<.., true> (the default) states the same fields per fan corner.  Neither counts anything: the polygons the pass sees
+// are the ones k_integ (or the one-kernel narrowphase) found a pressure point in.
 struct FricArgs {
     const ItemRec *items;
     const int *poly_item;
@@ -1401,7 +1403,9 @@ struct FricArgs {
     double *acc;
     FixedSink sink;      // k_fric_fixed (option "fixed_order"): the six sums of a piece's runs leave as records (k_fixed_reduce)
 };
-template <bool FX>
+// VF (option "vertex_fields", the default): eq, the damping argument and T̄s are evaluated once per fan corner and combined
+// per point (FanFields, pfc_kernels.h) instead of re-derived from r at every point; !VF is the per-point statement.
+template <bool FX, bool VF>
 __device__ __forceinline__ void fric_body(const FricArgs &g) {
     const int lane = threadIdx.x;
     const size_t P = (size_t)g.pcap;
@@ -1445,6 +1449,63 @@ __device__ __forceinline__ void fric_body(const FricArgs &g) {
             V3 vn = mk3(o[10 * P], o[11 * P], o[12 * P]);
             PointParams pp;
             pp.w = w; pp.vl = vl; pp.chi = chi; pp.Ebar = Ebar; pp.er0 = er0; pp.er1 = er1; pp.er2 = er2; pp.er3 = er3; pp.nq = nq;
+            if constexpr (VF) {
+                const FanFields ff = fan_fields(pp);
+                const double mu_s2 = mu_s * mu_s;
+                // the fields at the centroid: eq, damping argument, T̄s = P_n̂ (c0 + e x cen), arm
+                const double a_c = fan_field_a(ff, cen), d_c = fan_field_d(ff, cen);
+                const V3 Ts_c0 = ts_c0 + cross_fma(ts_e, cen);
+                const V3 ts_c = axpy_fma(-dot_fma(Ts_c0, nh), nh, Ts_c0);      // vec_sub_vec_proj
+                const V3 x_c = cen - cop;
+                // a corner: position (the area needs it as it is), offset from the centroid, the fields' linear parts there
+                struct Corner { V3 c, r; double a, d; V3 ts; };
+                auto corner = [&](const V3 &c) {
+                    Corner f;
+                    f.c = c; f.r = c - cen;
+                    f.a = fan_linear_a(ff, f.r); f.d = fan_linear_d(ff, f.r);
+                    const V3 Ts = cross_fma(ts_e, f.r);
+                    f.ts = axpy_fma(-dot_fma(Ts, nh), nh, Ts);
+                    return f;
+                };
+                Corner f2 = corner(v2);
+                for (int k = 0; k < n; ++k) {
+                    // a corner's fields travel to the next fan triangle as its position does in the per-point loop
+                    const Corner f1 = f2;
+                    f2 = corner(vn);
+                    if (k + 1 < n) vn = mk3(o[(13 + 3 * k) * P], o[(14 + 3 * k) * P], o[(15 + 3 * k) * P]);
+                    const double area = triangle_area(f1.c, f2.c, cen, nh);
+                    if (!(0.0 < area)) continue;       // :232, as fan_triangle_points
+                    const double dA = ff.qw * area;
+                    const double Sa = fan_sum(ff, f1.a, f2.a, a_c), Sd = fan_sum(ff, f1.d, f2.d, d_c);
+                    const V3 Sts = fan_sum(ff, f1.ts, f2.ts, ts_c), Sx = fan_sum(ff, f1.r, f2.r, x_c);
+                    auto point = [&](double eq, double d, const V3 &Ts, const V3 &x) {
+                        const double p = eq * Ebar * fmax(0.0, d);
+                        if (!(0.0 < p)) return;      // :245
+                        contributed = true;
+                        const double m2 = dot_fma(Ts, Ts);
+                        // traction(::Bristle) as in the per-point loop below; mu / |T̄s| and p dA as ONE factor sc of T̄s,
+                        // which goes straight into the sums: force += sc T̄s, torque += sc (x x T̄s)
+                        double sc = p * dA;
+                        if (!(m2 < mu_s2)) {
+                            double ri = __builtin_amdgcn_rsq(m2);
+                            const double hm = 0.5 * m2;
+                            ri = ri * __builtin_fma(-hm * ri, ri, 1.5);
+                            ri = ri * __builtin_fma(-hm * ri, ri, 1.5);
+                            const double mg = m2 * ri;
+                            const double y = mu_s + (mg - 2 * mu_s) * mu_slope;
+                            const double mu = (y > mu_s) ? mu_s : ((y < mu_d) ? mu_d : y);
+                            sc *= mu * ri;
+                        }
+                        const V3 xt = cross_fma(x, Ts);
+                        sum[0] = __builtin_fma(sc, xt.x, sum[0]); sum[1] = __builtin_fma(sc, xt.y, sum[1]);
+                        sum[2] = __builtin_fma(sc, xt.z, sum[2]); sum[3] = __builtin_fma(sc, Ts.x, sum[3]);
+                        sum[4] = __builtin_fma(sc, Ts.y, sum[4]); sum[5] = __builtin_fma(sc, Ts.z, sum[5]);
+                    };
+                    auto at = [&](const Corner &q) { point(fan_at(ff, Sa, q.a), fan_at(ff, Sd, q.d), fan_at(ff, Sts, q.ts), fan_at(ff, Sx, q.r)); };
+                    at(f2);
+                    if (ff.nq != 1) { at(f1); point(Sa, Sd, Sts, Sx); }
+                }
+            } else {
             for (int k = 0; k < n; ++k) {
                 const V3 v1 = v2;
                 v2 = vn;
@@ -1485,11 +1546,12 @@ __device__ __forceinline__ void fric_body(const FricArgs &g) {
                 }))
                     contributed = true;
             }
+            }
         }
         accumulate_items<6, FX>(g.acc, item, FX ? (active && (pk >> 28) >= 3u) : active, contributed, sum, kAccFric, kAccStride, &g.sink, (ch * C + p0) >> 6);
       }
     }
 }
-__global__ void __launch_bounds__(64, 3) k_fric(FricArgs g) { fric_body<false>(g); }
-__global__ void __launch_bounds__(64, 3) k_fric_fixed(FricArgs g) { fric_body<true>(g); }
+template <bool VF> __global__ void __launch_bounds__(64, 3) k_fric(FricArgs g) { fric_body<false, VF>(g); }
+template <bool VF> __global__ void __launch_bounds__(64, 3) k_fric_fixed(FricArgs g) { fric_body<true, VF>(g); }
 
