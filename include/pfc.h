@@ -323,6 +323,62 @@ int pfc_scatter_generalized_dual_device(pfc_handle h, int n_items, int n_dir, co
                                         double *d_f, double *d_df, int accumulate, void *stream);
 
 /*
+ * Contact items from body states: refreshBodyBodyTransform! / refreshBodyBodyCache! (src/contact_algorithms_non_friction.jl:103-134)
+ * on the device, for rigid bodies whose world poses and twists the host (or another kernel) keeps in HBM -- the front of the chain
+ * body states -> items -> pfc_eval_device -> pfc_scatter_generalized_device, which then runs on one stream without a host copy.
+ *
+ * pfc_set_instruction_bodies binds instruction `ins` to the bodies of its mesh_1 / mesh_2 (MeshCache.BodyID; meshes are given in
+ * their body's frame).  -1 is the world: identity pose, zero twist, no Jacobian (pfc_scatter_generalized's convention).  Allowed
+ * before and after pfc_finalize (before: any id >= 0; after: an instruction of the scenario); a second call overwrites the first and
+ * takes effect with the next call below.  The first of them after a binding uploads the table (one stream synchronisation).
+ * Multi-device handles keep the table on their first device.
+ */
+int pfc_set_instruction_bodies(pfc_handle h, int ins, int body_1, int body_2);
+
+/*
+ * One kernel, one item per lane, enqueued on `stream` (NULL = the handle's own) without a host synchronisation:
+ *   d_ins_ids    n_items, or NULL: item i uses instruction i           d_scene  n_items, or NULL: scene 0
+ *   d_x_w_b      n_scene n_body x 12   world pose of body b of scene s at row s n_body + b: R (9, column-major), t (3)
+ *   d_twist_w_b  n_scene n_body x 6    its twist [angular; linear] in world about the world origin (RigidBodyDynamics' twist_wrt_world)
+ *   d_pose       n_items x 24  OUT x_r2_r1 then x_r1_r2, pfc_eval's packing       d_twist  n_items x 6  OUT twist_r2_r1_r2
+ *   d_x_w_r2     n_items x 12  OUT x_rw_r2, pfc_scatter_generalized's packing (the pose of body 2, copied)
+ *   d_body_1, d_body_2  n_items  OUT the bound bodies; with d_scene given offset by scene n_body, so that they index a Jacobian array
+ *                       of n_scene n_body bodies; -1 stays -1
+ * Any OUT pointer may be NULL (not wanted, not written).  The arithmetic is plain Float64, every 3-term dot product summed left to
+ * right without fma, the world going through the same expressions with R = I, t = 0:
+ *   R2w = R_w2', t2w = -(R2w t_w2);  R21 = R2w R_w1, t21 = (R2w t_w1) + t2w;  R12 = R21', t12 = -(R12 t21);
+ *   tw = tw_2 - tw_1;  ang = R2w tw_ang;  lin = (R2w tw_lin) + t2w x ang
+ * -- the same bytes on every call, handle and entry point.  The call is NOT an evaluation: a kept value pass, Dual reuse,
+ * pfc_check and pfc_last_* are as they were.  n_items = 0 is a no-op.
+ * PFC_ERR_STATE: before pfc_finalize; an instruction without bodies (the message names it) -- the ids are device data and are not
+ * read by the host, so without d_ins_ids the instructions 0 .. n_items - 1 must be bound, with d_ins_ids every instruction of the
+ * scenario.  PFC_ERR_BAD_ARG: such an instruction bound to a body >= n_body.  Instruction and scene ids are not range-checked (the
+ * rule of pfc_scatter_generalized_device), but no item follows one out of range: such an item writes nothing.
+ */
+int pfc_items_from_bodies_device(pfc_handle h, int n_items, const int *d_ins_ids, const int *d_scene, int n_scene, int n_body,
+                                 const double *d_x_w_b, const double *d_twist_w_b, double *d_pose, double *d_twist, double *d_x_w_r2,
+                                 int *d_body_1, int *d_body_2, void *stream);
+/* The same with host buffers, synchronous.  Only the instructions the items use must be bound; instruction, scene and body ids are
+ * range-checked (PFC_ERR_BAD_ARG, nothing is written). */
+int pfc_items_from_bodies(pfc_handle h, int n_items, const int *ins_ids, const int *scene, int n_scene, int n_body, const double *x_w_b,
+                          const double *twist_w_b, double *pose, double *twist, double *x_w_r2, int *body_1, int *body_2);
+
+/*
+ * pfc_items_from_bodies_device followed by exactly pfc_eval_device on the same stream, reading the d_pose / d_twist the kernel
+ * wrote (both required here; the other three item outputs may be NULL).  The item buffers are the caller's: the scatter needs three
+ * of them, and the handle allocates nothing per evaluation.  pfc_check() afterwards as after pfc_eval_device; on PFC_ERR_OVERFLOW
+ * re-issue this call (the items are formed again, to the same bytes).
+ */
+int pfc_eval_bodies_device(pfc_handle h, int n_items, const int *d_ins_ids, const int *d_scene, int n_scene, int n_body,
+                           const double *d_x_w_b, const double *d_twist_w_b, const double *d_s, double *d_pose, double *d_twist,
+                           double *d_x_w_r2, int *d_body_1, int *d_body_2, double *d_wrench, double *d_sdot, int *d_counts, void *stream);
+/* The host-buffer form: pfc_items_from_bodies, then pfc_eval.  pose, twist, x_w_r2, body_1, body_2 are optional OUT arguments
+ * (NULL: the items are not returned).  Synchronous. */
+int pfc_eval_bodies(pfc_handle h, int n_items, const int *ins_ids, const int *scene, int n_scene, int n_body, const double *x_w_b,
+                    const double *twist_w_b, const double *s, double *pose, double *twist, double *x_w_r2, int *body_1, int *body_2,
+                    double *wrench, double *sdot, int *counts);
+
+/*
  * The contact surface of n_items items: per item what the reference's TractionCache holds after forceAllElasticIntersections!
  * (src/structs.jl; filled by src/contact_algorithms_non_friction.jl:217-265), the clipped polygons it was integrated over, and
  * normal_wrench / normal_wrench_cop (src/contact_algorithms_normal.jl:2-34) -- what test/test_normal.jl:31-41 and

@@ -58,6 +58,11 @@ SIGNATURES = {
     "pfc_local_jacobian": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "pfc_apply_local_jacobian_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7),
     "pfc_apply_local_jacobian": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "pfc_set_instruction_bodies": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "pfc_items_from_bodies_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8),
+    "pfc_items_from_bodies": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip]),
+    "pfc_eval_bodies_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 12),
+    "pfc_eval_bodies": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _ip]),
     "pfc_build_tree": (C.c_int, [C.c_int, _dp, C.c_int, C.c_int, _ip, _dp, C.c_int, _dp, _dp, _dp, _ip, _ip]),
     "pfc_tree_last_error": (C.c_char_p, []),
     "pfc_scatter_generalized": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _ip, _ip, C.c_int, C.c_int, C.c_int, _dp, _dp]),
@@ -89,7 +94,7 @@ class PFCError(RuntimeError):
 
 def build(force: bool = False) -> str:
     """Compile csrc/pfc_hip.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("pfc_hip.hip", "pfc_tree.cpp", "pfc_sort.hip", "pfc_kernels.h", "pfc_bp.h", "pfc_np.h", "pfc_br.h", "pfc_dual.h", "pfc_fused.h", "pfc_clip.h", "pfc_multi.h", "pfc_sort.h", "pfc_surface.h", "pfc_surface_fric.h", "pfc_scatter.h", "pfc_ljac.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("pfc_hip.hip", "pfc_tree.cpp", "pfc_sort.hip", "pfc_kernels.h", "pfc_bp.h", "pfc_np.h", "pfc_br.h", "pfc_dual.h", "pfc_fused.h", "pfc_clip.h", "pfc_multi.h", "pfc_sort.h", "pfc_surface.h", "pfc_surface_fric.h", "pfc_scatter.h", "pfc_ljac.h", "pfc_bodies.h")]
     srcs.append(os.path.join(os.path.dirname(HERE), "include", "pfc.h"))
     srcs.append(os.path.abspath(__file__))      # the compiler flags live here
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)

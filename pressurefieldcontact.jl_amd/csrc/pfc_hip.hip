@@ -20,6 +20,8 @@
 //                  item order (pfc_scatter_generalized_dual)
 //   pfc_ljac.h     k_ljac_seeds / k_ljac_pack / k_ljac_apply: per-item contact Jacobians from unit-seed Dual passes and their
 //                  product with further seed chunks (pfc_local_jacobian, pfc_apply_local_jacobian)
+//   pfc_bodies.h   k_items_from_bodies: pose, twist, x_rw_r2 and body ids of every item from the bodies' world poses and twists
+//                  (pfc_items_from_bodies, pfc_eval_bodies)
 //   pfc_multi.h    host code: multi-device handles (pfc_create_multi)
 // This file: mesh record preparation (k_prep_tri, k_prep_tet), per-item setup (k_setup_items), work-list management,
 // hipGraph capture / replay, the two-half evaluation and every extern "C" entry point.
@@ -189,6 +191,7 @@ __global__ void k_repose(int n_items, const double *__restrict__ pose, ItemRec *
 #include "pfc_surface_fric.h"
 #include "pfc_scatter.h"
 #include "pfc_ljac.h"
+#include "pfc_bodies.h"
 
 }  // namespace pfc
 
@@ -535,6 +538,12 @@ struct pfc_context {
     DevBuf<double> ljac_out;           // the passes' partials, n_items x 432
     DevBuf<double> ljac_io;            // staging of the host-buffer forms
     DevBuf<int> ljac_ids;
+    // contact items from body states (pfc_bodies.h)
+    std::vector<int> ins_bodies;       // per instruction {body of mesh_1, body of mesh_2} (pfc_set_instruction_bodies); grows with the ids it is given
+    DevBuf<int> bodies_bind;           // its device copy, one pair per instruction (kBodiesUnbound where none was given)
+    bool bodies_stale = true;          // the device copy is older than ins_bodies: uploaded by the next launch
+    DevBuf<double> bodies_d;           // staging of the host-buffer form: body states in, items out
+    DevBuf<int> bodies_i;
     DevBuf<unsigned long long> surf_keys[2];
     DevBuf<char> surf_tmp;                            // rocPRIM scan / sort
     PinBuf<long long> h_surf;                         // pinned mirror of surf_out
@@ -3036,6 +3045,152 @@ int pfc_apply_local_jacobian(pfc_handle h, int n_items, int n_dir, const double 
     HIP_TRY(h, hipMemcpyAsync(d_sdot, dsd, sizeof(double) * nk * 6, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     return PFC_OK;
+}
+
+// ---- contact items from body states (pfc_bodies.h) ------------------------------------------------------------------------
+int pfc_set_instruction_bodies(pfc_handle h, int ins, int body_1, int body_2) {
+    if (h && h->multi)      // the table lives with the first device, where the items are formed
+        return on_first_shard(h, [&](pfc_context *c) { return pfc_set_instruction_bodies(c, ins, body_1, body_2); });
+    if (!h || ins < 0 || body_1 < -1 || body_2 < -1)
+        return fail(h, PFC_ERR_BAD_ARG, "pfc_set_instruction_bodies: instruction id >= 0 and body ids >= -1 (-1: the world)");
+    if (h->finalized && ins >= (int)h->ins.size())
+        return fail(h, PFC_ERR_BAD_ARG, "pfc_set_instruction_bodies: the scenario has no instruction %d", ins);
+    if (h->ins_bodies.size() < 2 * ((size_t)ins + 1)) h->ins_bodies.resize(2 * ((size_t)ins + 1), kBodiesUnbound);
+    h->ins_bodies[2 * (size_t)ins] = body_1; h->ins_bodies[2 * (size_t)ins + 1] = body_2;
+    h->bodies_stale = true;
+    return PFC_OK;
+}
+
+// The binding of instruction `ins` checked against n_body: PFC_ERR_STATE if it was never bound.
+static int bodies_check_ins(pfc_context *h, const char *who, int ins, int n_body) {
+    const size_t k = 2 * (size_t)ins;
+    if (k + 1 >= h->ins_bodies.size() || h->ins_bodies[k] == kBodiesUnbound)
+        return fail(h, PFC_ERR_STATE, "%s: instruction %d has no bodies (pfc_set_instruction_bodies)", who, ins);
+    if (h->ins_bodies[k] >= n_body || h->ins_bodies[k + 1] >= n_body)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: instruction %d is bound to bodies (%d, %d), n_body is %d", who, ins, h->ins_bodies[k],
+                    h->ins_bodies[k + 1], n_body);
+    return PFC_OK;
+}
+
+// Argument checks of both forms (the ids are checked by the callers: they are device data for one of them).
+static int bodies_check_args(pfc_context *h, const char *who, int n_items, const int *ins_ids, int n_scene, int n_body, const double *x_w_b,
+                             const double *twist_w_b) {
+    if (!h->finalized) return fail(h, PFC_ERR_STATE, "%s before pfc_finalize", who);
+    if (n_items < 0 || n_scene < 1 || n_body < 0) return fail(h, PFC_ERR_BAD_ARG, "%s: n_items >= 0, n_scene >= 1, n_body >= 0", who);
+    if (n_items == 0) return PFC_OK;
+    if (n_body > 0 && (!x_w_b || !twist_w_b)) return fail(h, PFC_ERR_BAD_ARG, "%s: null body-state buffer", who);
+    if (!ins_ids && n_items > (int)h->ins.size())
+        return fail(h, PFC_ERR_BAD_ARG, "%s: n_items exceeds the number of instructions and no ins_ids given", who);
+    return PFC_OK;
+}
+
+// The table's upload if it is stale, and the kernel, on st.  Every pointer is a device pointer.
+static int bodies_launch(pfc_context *h, int n_items, const int *ins_ids, const int *scene, int n_scene, int n_body, const double *x_w_b,
+                         const double *twist_w_b, double *pose, double *twist, double *x_w_r2, int *body_1, int *body_2, hipStream_t st) {
+    const int n_ins = (int)h->ins.size();
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (h->bodies_stale) {      // (the one synchronisation of this path: once per binding, ordered behind st's earlier work)
+        h->ins_bodies.resize(2 * (size_t)n_ins, kBodiesUnbound);
+        HIP_TRY(h, h->bodies_bind.ensure(2 * (size_t)n_ins));
+        HIP_TRY(h, hipMemcpyAsync(h->bodies_bind.p, h->ins_bodies.data(), sizeof(int) * 2 * (size_t)n_ins, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        h->bodies_stale = false;
+    }
+    BodiesArgs a;
+    a.n_items = n_items; a.n_ins = n_ins; a.n_scene = n_scene; a.n_body = n_body; a.ins_ids = ins_ids; a.scene = scene;
+    a.bind = h->bodies_bind.p; a.x_w_b = x_w_b; a.twist_w_b = twist_w_b; a.pose = pose; a.twist = twist; a.x_w_r2 = x_w_r2;
+    a.body_1 = body_1; a.body_2 = body_2;
+    hipLaunchKernelGGL(k_items_from_bodies, dim3((unsigned)((n_items + kBodiesWave - 1) / kBodiesWave)),
+                       dim3(kBodiesWave), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+// The ids are device data here: without d_ins_ids the instructions 0 .. n_items - 1 must be bound, with them every instruction.
+int pfc_items_from_bodies_device(pfc_handle h, int n_items, const int *d_ins_ids, const int *d_scene, int n_scene, int n_body,
+                                 const double *d_x_w_b, const double *d_twist_w_b, double *d_pose, double *d_twist, double *d_x_w_r2,
+                                 int *d_body_1, int *d_body_2, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_items_from_bodies_device(c, n_items, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_pose, d_twist,
+                                                d_x_w_r2, d_body_1, d_body_2, stream); });
+    const char *who = "pfc_items_from_bodies_device";
+    int rc = bodies_check_args(h, who, n_items, d_ins_ids, n_scene, n_body, d_x_w_b, d_twist_w_b);
+    if (rc != PFC_OK || n_items == 0) return rc;
+    const int n_used = d_ins_ids ? (int)h->ins.size() : n_items;
+    for (int k = 0; k < n_used; ++k)
+        if ((rc = bodies_check_ins(h, who, k, n_body)) != PFC_OK) return rc;
+    return bodies_launch(h, n_items, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_pose, d_twist, d_x_w_r2, d_body_1, d_body_2,
+                         stream ? (hipStream_t)stream : h->stream);
+}
+
+int pfc_items_from_bodies(pfc_handle h, int n_items, const int *ins_ids, const int *scene, int n_scene, int n_body, const double *x_w_b,
+                          const double *twist_w_b, double *pose, double *twist, double *x_w_r2, int *body_1, int *body_2) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_items_from_bodies(c, n_items, ins_ids, scene, n_scene, n_body, x_w_b, twist_w_b, pose, twist, x_w_r2, body_1, body_2); });
+    const char *who = "pfc_items_from_bodies";
+    int rc = bodies_check_args(h, who, n_items, ins_ids, n_scene, n_body, x_w_b, twist_w_b);
+    if (rc != PFC_OK || n_items == 0) return rc;
+    for (int i = 0; i < n_items; ++i) {
+        const int ins = ins_ids ? ins_ids[i] : i;
+        if (ins < 0 || ins >= (int)h->ins.size() || (scene && (scene[i] < 0 || scene[i] >= n_scene)))
+            return fail(h, PFC_ERR_BAD_ARG, "%s: instruction / scene id out of range (item %d)", who, i);
+        if ((rc = bodies_check_ins(h, who, ins, n_body)) != PFC_OK) return rc;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    const size_t n = (size_t)n_items, nb = (size_t)n_scene * n_body;
+    // [x_w_b 12 | twist_w_b 6] x bodies, [pose 24 | twist 6 | x_w_r2 12] x n; [ids | scene | body_1 | body_2] x n
+    HIP_TRY(h, h->bodies_d.ensure(nb * 18 + n * 42 + 1));
+    HIP_TRY(h, h->bodies_i.ensure(n * 4));
+    double *dx = h->bodies_d.p, *dtw = dx + nb * 12, *dpose = dtw + nb * 6, *dtwist = dpose + n * 24, *dxr = dtwist + n * 6;
+    int *dids = h->bodies_i.p, *dsc = dids + n, *db1 = dsc + n, *db2 = db1 + n;
+    if (nb) {
+        HIP_TRY(h, hipMemcpyAsync(dx, x_w_b, sizeof(double) * nb * 12, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipMemcpyAsync(dtw, twist_w_b, sizeof(double) * nb * 6, hipMemcpyHostToDevice, st));
+    }
+    if (ins_ids) HIP_TRY(h, hipMemcpyAsync(dids, ins_ids, sizeof(int) * n, hipMemcpyHostToDevice, st));
+    if (scene) HIP_TRY(h, hipMemcpyAsync(dsc, scene, sizeof(int) * n, hipMemcpyHostToDevice, st));
+    rc = bodies_launch(h, n_items, ins_ids ? dids : nullptr, scene ? dsc : nullptr, n_scene, n_body, dx, dtw, pose ? dpose : nullptr,
+                       twist ? dtwist : nullptr, x_w_r2 ? dxr : nullptr, body_1 ? db1 : nullptr, body_2 ? db2 : nullptr, st);
+    if (rc != PFC_OK) return rc;
+    if (pose) HIP_TRY(h, hipMemcpyAsync(pose, dpose, sizeof(double) * n * 24, hipMemcpyDeviceToHost, st));
+    if (twist) HIP_TRY(h, hipMemcpyAsync(twist, dtwist, sizeof(double) * n * 6, hipMemcpyDeviceToHost, st));
+    if (x_w_r2) HIP_TRY(h, hipMemcpyAsync(x_w_r2, dxr, sizeof(double) * n * 12, hipMemcpyDeviceToHost, st));
+    if (body_1) HIP_TRY(h, hipMemcpyAsync(body_1, db1, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+    if (body_2) HIP_TRY(h, hipMemcpyAsync(body_2, db2, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return PFC_OK;
+}
+
+// k_items_from_bodies, then exactly pfc_eval_device on the pose and twist it wrote, on the same stream.
+int pfc_eval_bodies_device(pfc_handle h, int n_items, const int *d_ins_ids, const int *d_scene, int n_scene, int n_body,
+                           const double *d_x_w_b, const double *d_twist_w_b, const double *d_s, double *d_pose, double *d_twist,
+                           double *d_x_w_r2, int *d_body_1, int *d_body_2, double *d_wrench, double *d_sdot, int *d_counts, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (n_items > 0 && (!d_pose || !d_twist)) return fail(h, PFC_ERR_BAD_ARG, "pfc_eval_bodies_device: d_pose and d_twist are the evaluation's inputs");
+    const int rc = pfc_items_from_bodies_device(h, n_items, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_pose, d_twist,
+                                                d_x_w_r2, d_body_1, d_body_2, stream);
+    if (rc != PFC_OK) return rc;
+    return pfc_eval_device(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, stream);
+}
+
+int pfc_eval_bodies(pfc_handle h, int n_items, const int *ins_ids, const int *scene, int n_scene, int n_body, const double *x_w_b,
+                    const double *twist_w_b, const double *s, double *pose, double *twist, double *x_w_r2, int *body_1, int *body_2,
+                    double *wrench, double *sdot, int *counts) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    std::vector<double> tmp;
+    if (n_items > 0 && (!pose || !twist)) {
+        tmp.resize((size_t)n_items * 30);
+        if (!pose) pose = tmp.data();
+        if (!twist) twist = tmp.data() + (size_t)n_items * 24;
+    }
+    const int rc = pfc_items_from_bodies(h, n_items, ins_ids, scene, n_scene, n_body, x_w_b, twist_w_b, pose, twist, x_w_r2, body_1, body_2);
+    if (rc != PFC_OK) return rc;
+    return pfc_eval(h, n_items, ins_ids, pose, twist, s, wrench, sdot, counts);
 }
 
 // The Dual evaluation with the broadphase pose of m.float's state (calcTriTetIntersections!, non_friction.jl:94-101): the block is

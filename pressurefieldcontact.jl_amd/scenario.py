@@ -303,6 +303,16 @@ class FrictionSurface:
         return d
 
 
+@dataclass(eq=False)
+class BodyItems:
+    """What MechanismScenario.items_from_bodies returns: the per-item inputs of the evaluation and of the third-law scatter."""
+    pose: np.ndarray        # (n,24) x_r2_r1 then x_r1_r2
+    twist: np.ndarray       # (n,6) twist_r2_r1_r2
+    x_w_r2: np.ndarray      # (n,12) x_rw_r2
+    body_1: np.ndarray      # (n,) int32: body of mesh_1 (-1: the world), offset by scene * n_body when scenes are given
+    body_2: np.ndarray
+
+
 class MechanismScenario:
     """Contact part of MechanismScenario{T} (src/mechanism_scenario.jl:166-199), backed by a pfc_handle."""
 
@@ -316,6 +326,7 @@ class MechanismScenario:
         self.devices = None if devices is None else [int(d) for d in devices]
         self._h = None
         self._finalized = False
+        self._ins_bodies = {}        # bindings made before finalize(): the handle does not exist yet
 
     # ---- scenario construction ---------------------------------------------------------------------------------
     def add_contact(self, name: str, e_mesh: EMesh, c_prop: Optional[ContactProperties] = None,
@@ -431,6 +442,18 @@ class MechanismScenario:
             self._id(L.pfc_add_instruction(h, c.id_1, c.id_2, c.chi, c.n_quad_rule, model, ap))
         self._check(L.pfc_finalize(h))
         self._finalized = True
+        for ins, (b1, b2) in self._ins_bodies.items():
+            self._check(L.pfc_set_instruction_bodies(h, ins, b1, b2))
+
+    def set_instruction_bodies(self, ins: int, body_1: int, body_2: int):
+        """pfc_set_instruction_bodies: instruction `ins` (0-based, the order of the add_friction_* calls) acts between body_1 (of
+        its mesh_1) and body_2 (of its mesh_2); -1 is the world.  Before or after finalize(); a second call overwrites."""
+        ins, body_1, body_2 = int(ins), int(body_1), int(body_2)
+        if not (0 <= ins < len(self.ContactInstructions)) or body_1 < -1 or body_2 < -1:
+            raise ValueError("set_instruction_bodies: an instruction of the scenario and body ids >= -1")
+        self._ins_bodies[ins] = (body_1, body_2)
+        if self._finalized:
+            self._check(_lib.lib().pfc_set_instruction_bodies(self._h, ins, body_1, body_2))
 
     def close(self):
         if self._h is not None:
@@ -693,6 +716,74 @@ class MechanismScenario:
         `stream`, no check() needed."""
         self._check(_lib.lib().pfc_apply_local_jacobian_device(self._h, int(n_items), int(n_dir), d_L, d_dpose, d_dtwist, d_ds or None,
                                                                d_dwrench, d_dsdot, stream or None))
+
+    def _bodies_call(self, x_w_b, twist_w_b, ins_ids, scene):
+        """Shared argument handling of the host-buffer *_bodies calls: (n, leading ctypes arguments, empty BodyItems, its pointers)."""
+        if not self._finalized:
+            raise RuntimeError("finalize the scenario first")
+        x_a = np.ascontiguousarray(x_w_b, dtype=np.float64)
+        if x_a.ndim == 2:
+            x_a = x_a[None]
+        if x_a.ndim != 3 or x_a.shape[2] != 12:
+            raise ValueError("x_w_b must be (n_body, 12) or (n_scene, n_body, 12)")
+        n_scene, n_body = x_a.shape[0], x_a.shape[1]
+        tw_a = np.ascontiguousarray(twist_w_b, dtype=np.float64).reshape(n_scene, n_body, 6)
+        id_a = sc_a = id_p = sc_p = None
+        n = len(self.ContactInstructions)
+        if ins_ids is not None:
+            id_a, id_p = _i(ins_ids)
+            n = id_a.size
+        if scene is not None:
+            sc_a, sc_p = _i(scene)
+            if ins_ids is None:
+                n = sc_a.size
+            elif sc_a.size != n:
+                raise ValueError("scene must have one entry per item")
+        it = BodyItems(np.zeros((n, 24)), np.zeros((n, 6)), np.zeros((n, 12)), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32))
+        head = (self._h, n, id_p, sc_p, n_scene, n_body, x_a.ctypes.data_as(_dp), tw_a.ctypes.data_as(_dp))
+        outs = (it.pose.ctypes.data_as(_dp), it.twist.ctypes.data_as(_dp), it.x_w_r2.ctypes.data_as(_dp), it.body_1.ctypes.data_as(_ip),
+                it.body_2.ctypes.data_as(_ip))
+        return n, head, it, outs, (x_a, tw_a, id_a, sc_a)
+
+    def items_from_bodies(self, x_w_b, twist_w_b, ins_ids: Optional[Sequence[int]] = None, scene=None) -> BodyItems:
+        """The items of refreshBodyBodyTransform! / refreshBodyBodyCache! from the bodies' world states (pfc_items_from_bodies, host
+        buffers, synchronous).  x_w_b (n_body,12) or (n_scene,n_body,12): R column-major then t; twist_w_b likewise with 6:
+        [angular; linear] in world about the world origin.  ins_ids (n,) or None (item i = instruction i); scene (n,) or None
+        (scene 0).  Every instruction used must have been given its bodies (set_instruction_bodies)."""
+        n, head, it, outs, keep = self._bodies_call(x_w_b, twist_w_b, ins_ids, scene)
+        self._check(_lib.lib().pfc_items_from_bodies(*head, *outs))
+        return it
+
+    def force_all_elastic_intersections_bodies(self, x_w_b, twist_w_b, s=None, ins_ids: Optional[Sequence[int]] = None, scene=None):
+        """force_all_elastic_intersections on the items of items_from_bodies (pfc_eval_bodies, host buffers, synchronous).
+        Returns (wrench (n,6), sdot (n,6), counts (n,4), items: BodyItems)."""
+        n, head, it, outs, keep = self._bodies_call(x_w_b, twist_w_b, ins_ids, scene)
+        s_p = None
+        if s is not None:
+            s_a, s_p = _d(s)
+            if s_a.size != 6 * n:
+                raise ValueError("s must have 6 entries per item")
+        wrench = np.zeros((n, 6)); sdot = np.zeros((n, 6)); counts = np.zeros((n, 4), dtype=np.int32)
+        self._check(_lib.lib().pfc_eval_bodies(*head, s_p, *outs, wrench.ctypes.data_as(_dp), sdot.ctypes.data_as(_dp),
+                                               counts.ctypes.data_as(_ip)))
+        return wrench, sdot, counts, it
+
+    def items_from_bodies_device(self, n_items: int, d_ins_ids: int, d_scene: int, n_scene: int, n_body: int, d_x_w_b: int,
+                                 d_twist_w_b: int, d_pose: int, d_twist: int, d_x_w_r2: int, d_body_1: int, d_body_2: int, stream: int = 0):
+        """pfc_items_from_bodies_device: raw device addresses (0: NULL for d_ins_ids, d_scene and any output not wanted); asynchronous
+        on `stream`, not an evaluation, no check() needed."""
+        self._check(_lib.lib().pfc_items_from_bodies_device(self._h, int(n_items), d_ins_ids or None, d_scene or None, int(n_scene),
+                                                            int(n_body), d_x_w_b or None, d_twist_w_b or None, d_pose or None, d_twist or None,
+                                                            d_x_w_r2 or None, d_body_1 or None, d_body_2 or None, stream or None))
+
+    def eval_bodies_device(self, n_items: int, d_ins_ids: int, d_scene: int, n_scene: int, n_body: int, d_x_w_b: int, d_twist_w_b: int,
+                           d_s: int, d_pose: int, d_twist: int, d_x_w_r2: int, d_body_1: int, d_body_2: int, d_wrench: int, d_sdot: int,
+                           d_counts: int, stream: int = 0):
+        """pfc_eval_bodies_device: items_from_bodies_device then eval_device on the d_pose / d_twist it wrote, on one stream;
+        asynchronous, follow with check() (re-issue on ERR_OVERFLOW)."""
+        self._check(_lib.lib().pfc_eval_bodies_device(self._h, int(n_items), d_ins_ids or None, d_scene or None, int(n_scene), int(n_body),
+                                                      d_x_w_b or None, d_twist_w_b or None, d_s or None, d_pose, d_twist, d_x_w_r2 or None,
+                                                      d_body_1 or None, d_body_2 or None, d_wrench, d_sdot, d_counts or None, stream or None))
 
     def contact_surface(self, pose, twist, ins_ids: Optional[Sequence[int]] = None) -> ContactSurface:
         """The contact surface of every item (pfc_contact_surface): clipped polygons, traction points and normal wrench / cop in
