@@ -137,3 +137,65 @@ def fuzz_workload(pfc, rng, n_items, degenerate, tet_tet=False):
         twist.append(rng.standard_normal(6) * np.array([1, 1, 1, 0.1, 0.1, 0.1]))
         s.append(rng.standard_normal(6) * 1e-3)
     return Cf.Workload("fuzz", meshes, ins, ids, np.array(pose), np.array(twist), np.array(s))
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# The four regimes of traction() (friction.jl): x = |v_t| / v_c (regularized) or |T̄s| / mu_s (bristle); stick x < 1,
+# plateau at mu_s 1 <= x < 2, ramp to mu_d 2 <= x < 3, slide x >= 3.  Scenes with mu_s > mu_d whose points populate all
+# four, and the classifier that counts them from the oracle's debug result.
+# ----------------------------------------------------------------------------------------------------------------
+REGIME_MU_S = 0.6
+REGIME_EDGES = (1.0, 2.0, 3.0)
+REGIME_NAMES = ("stick", "plateau", "ramp", "slide")
+
+
+def friction_branch_input(c, mu_s, trac, twist, Delta=None, cop=None):
+    """Per traction point (rows n 3, r 3, dA, p) of one item: the vector traction() takes (vel_t, regularized, or T̄s,
+    bristle: from the item's Delta and cop), projected off n̂; p dA; and the threshold of the first branch."""
+    n, r, pdA = trac[:, 0:3], trac[:, 3:6], trac[:, 6] * trac[:, 7]
+    ang, lin = twist[0:3], twist[3:6]
+    rdot = lin + np.cross(ang, r)
+    if c.model == "regularized":
+        v = rdot
+        thr = c.v_tol
+    else:
+        x = r - cop
+        v = -c.k_bar * ((Delta[3:6] + np.cross(Delta[0:3], x)) + c.tau * rdot)
+        thr = mu_s
+    v = v - np.sum(v * n, axis=1)[:, None] * n      # vec_sub_vec_proj
+    return v, pdA, thr
+
+
+def friction_regime_scenes(pfc):
+    """{name: Workload}: R1 (regularized tri-tet), B1 (bristle tri-tet), V_reg / V_bri (tet-tet), every instruction with
+    mu_s = 0.6 > mu_d = 0.3, twists and bristle states scaled so that every regime holds traction points."""
+    Cf = pfc.configs
+    r1 = Cf.c2_box_on_plane(4, n_div=3)
+    r1.twist = np.array([[0.0, 0.0, 0.6, 0.005 * k, 0.0, 0.0] for k in range(r1.n_items)])
+    b1 = Cf.c3_blob_tool(4, n_div_blob=6, n_div_tool=4)
+    b1.twist = b1.twist * 0.04
+    b1.s = np.random.default_rng(5).standard_normal((4, 6)) * 1e-4
+    v_reg = Cf.vol_vol(4, n_div=3, model="regularized")
+    v_reg.twist = v_reg.twist * 0.3
+    v_bri = Cf.vol_vol(4, n_div=3, model="bristle")
+    v_bri.twist = v_bri.twist * 0.04
+    v_bri.s = np.random.default_rng(5).standard_normal((8, 6)) * 1e-4
+    scenes = {"R1": r1, "B1": b1, "V_reg": v_reg, "V_bri": v_bri}
+    for w in scenes.values():
+        for c in w.instructions:
+            c.mu_s = REGIME_MU_S
+        w.twist = np.ascontiguousarray(w.twist); w.s = np.ascontiguousarray(w.s)
+    return scenes
+
+
+def friction_regimes(pfc, w, k, ref):
+    """Regimes of item k's traction points from its oracle debug result ref: (counts of stick, plateau, ramp, slide;
+    the smallest |x - e| over the points and the edges e = 1, 2, 3 -- inf without points)."""
+    c = w.instructions[int(w.ins_ids[k])]
+    mu_s, _ = pfc.scenario.determine_mu_s_mu_d(c.mu_s, c.mu_d)
+    if ref.trac is None or ref.trac.shape[0] == 0:
+        return np.zeros(4, dtype=int), np.inf
+    v, _, thr = friction_branch_input(c, mu_s, ref.trac, w.twist[k], ref.Delta, ref.cop)
+    x = np.linalg.norm(v, axis=1) / thr
+    counts = np.bincount(np.searchsorted(np.array(REGIME_EDGES), x, side="right"), minlength=4)
+    return counts, float(np.abs(x[:, None] - np.array(REGIME_EDGES)[None, :]).min())

@@ -73,19 +73,9 @@ def _branch_input(pfc, w, F, k):
     own trac rows, the twist, the call's cop (summary) and Δ² (stiff)."""
     it = F.item(k)
     c, mu_s, mu_d = _ins_params(pfc, w, k)
-    T = it["trac"]
-    n, r, pdA = T[:, 0:3], T[:, 3:6], T[:, 6] * T[:, 7]
-    ang, lin = w.twist[k, 0:3], w.twist[k, 3:6]
-    rdot = lin + np.cross(ang, r)
-    if c.model == "regularized":
-        v = rdot
-        thr = c.v_tol
-    else:
-        D = it["Delta"]
-        x = r - it["cop"]
-        v = -c.k_bar * ((D[3:6] + np.cross(D[0:3], x)) + c.tau * rdot)
-        thr = mu_s
-    v = v - np.sum(v * n, axis=1)[:, None] * n      # vec_sub_vec_proj
+    bristle = c.model == "bristle"
+    v, pdA, thr = H.friction_branch_input(c, mu_s, it["trac"], w.twist[k], it["Delta"] if bristle else None,
+                                          it["cop"] if bristle else None)
     return c, mu_s, mu_d, v, pdA, thr
 
 

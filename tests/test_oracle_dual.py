@@ -4,6 +4,7 @@ path is what Radau's Jacobian evaluation runs (src/mechanism_scenario.jl:187, sr
 import numpy as np
 import pytest
 
+import helpers as H
 from helpers import oracle_ins, oracle_meshes
 
 
@@ -95,3 +96,45 @@ def test_dual_no_contact_bristle(pfc, O):
     assert st == 0 and np.all(wr == 0) and np.all(dw == 0)
     np.testing.assert_allclose(sd, -np.ones(6) / c.tau)
     np.testing.assert_allclose(dsd, -ds / c.tau)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# mu_s > mu_d: the scenes of helpers.friction_regime_scenes put traction points into all four regimes of traction(),
+# so the slope of the ramp and the derivative of mu through |v_t| / |T̄s| are live in the Dual oracle.
+# ----------------------------------------------------------------------------------------------------------------
+REGIME_SCENES = ["R1", "B1", "V_reg", "V_bri"]
+REGIME_MIN_POINTS = 30
+REGIME_MIN_EDGE_DISTANCE = 1e-4      # in thresholds; a branch decided the other way by rounding needs ~1e-15
+
+
+@pytest.fixture(scope="module")
+def regime_scenes(pfc):
+    return H.friction_regime_scenes(pfc)
+
+
+@pytest.mark.parametrize("name", REGIME_SCENES)
+def test_regime_scenes_populate_every_regime_away_from_the_edges(pfc, O, regime_scenes, name):
+    """What keeps the device tests of tests/test_gpu_friction_regimes.py meaningful: every regime holds at least 30 traction
+    points, and no point lies within 1e-4 thresholds of an edge, so that no branch can differ between oracle and device."""
+    w = regime_scenes[name]
+    assert all(c.mu_s == H.REGIME_MU_S and c.mu_d == 0.3 for c in w.instructions)
+    total, nearest = np.zeros(4, dtype=int), np.inf
+    for k, r in enumerate(H.oracle_run(pfc, w)):
+        counts, edge = H.friction_regimes(pfc, w, k, r)
+        assert counts.sum() == r.counts[3]
+        total += counts
+        nearest = min(nearest, edge)
+    print(name, dict(zip(H.REGIME_NAMES, total.tolist())), f"nearest edge {nearest:.2e}")
+    assert np.all(total >= REGIME_MIN_POINTS), (name, total)
+    assert nearest >= REGIME_MIN_EDGE_DISTANCE, (name, nearest)
+
+
+@pytest.mark.parametrize("name", REGIME_SCENES)
+def test_dual_oracle_with_mu_s_above_mu_d(pfc, O, regime_scenes, name):
+    """Central differences of the value oracle against the Dual oracle on every item of the regime scenes (h = 1e-6
+    straddles no kink: the points lie >= 1e-4 thresholds from every edge)."""
+    w = regime_scenes[name]
+    rng = np.random.default_rng(4)
+    for k in range(w.n_items):
+        bristle = w.instructions[int(w.ins_ids[k])].model == "bristle"
+        fd_check(O, pfc, w, k, rng, sdot_rtol=1e-3 if bristle else None)
