@@ -379,6 +379,64 @@ int pfc_eval_bodies(pfc_handle h, int n_items, const int *ins_ids, const int *sc
                     double *wrench, double *sdot, int *counts);
 
 /*
+ * Dual seeds of the items from body states: refreshBodyBodyTransform! / refreshBodyBodyCache! as the reference runs them on the Dual
+ * state of a Jacobian chunk (src/radau/radau_functions.jl:2-14), where the bodies' world poses and twists carry partials -- the front
+ * of the chain body states + partials -> seeds -> pfc_eval_dual_device[_more] -> pfc_scatter_generalized_dual_device.  One kernel, one
+ * lane per (item, direction), enqueued on `stream` (NULL = the handle's own) without a host synchronisation.  Arguments as
+ * pfc_items_from_bodies_device, plus, for n_dir (1..16, else PFC_ERR_BAD_ARG) seed directions:
+ *   d_dx_w_b      n_scene n_body x n_dir x 12   partials of d_x_w_b, direction dir of body b of scene s at row (s n_body + b) n_dir + dir
+ *   d_dtwist_w_b  n_scene n_body x n_dir x 6    partials of d_twist_w_b, likewise
+ *                 each may be NULL: zeros, the same bytes as an array of zeros (the chunk that seeds only velocities or only
+ *                 configurations)
+ *   d_dpose       n_items x n_dir x 24  OUT partials of x_r2_r1 then x_r1_r2, pfc_eval_dual_device's d_dpose
+ *   d_dtwist      n_items x n_dir x 6   OUT partials of twist_r2_r1_r2, its d_dtwist
+ *   d_dx_w_r2     n_items x n_dir x 12  OUT partials of x_rw_r2, pfc_scatter_generalized_dual_device's d_dx_w_r2 (the partials of body
+ *                 2's pose, gathered; zeros for the world)
+ * Any OUT pointer may be NULL (not wanted, not written).  The arithmetic is the statement of pfc_items_from_bodies_device on
+ * (value, partial) numbers with ForwardDiff's rules -- sums and differences componentwise, d(a b) = da b + a db, no fma -- and the
+ * world going through it with R = I, t = 0, a zero twist and zero partials: the same bytes on every call, handle and entry point.
+ * The call is NOT an evaluation: a kept value pass, Dual reuse, pfc_check and pfc_last_* are as they were (a pfc_eval_dual_device_more
+ * may still follow the evaluation before it).  n_items = 0 is a no-op.  States, errors and the treatment of ids are those of
+ * pfc_items_from_bodies_device: an item with an instruction or scene id out of range writes nothing.  Multi-device handles: the first
+ * device.
+ */
+int pfc_dual_seeds_from_bodies_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene,
+                                      int n_scene, int n_body, const double *d_x_w_b, const double *d_twist_w_b,
+                                      const double *d_dx_w_b, const double *d_dtwist_w_b,
+                                      double *d_dpose, double *d_dtwist, double *d_dx_w_r2, void *stream);
+/* The same with host buffers, synchronous.  Only the instructions the items use must be bound; instruction, scene and body ids are
+ * range-checked (PFC_ERR_BAD_ARG, nothing is written). */
+int pfc_dual_seeds_from_bodies(pfc_handle h, int n_items, int n_dir, const int *ins_ids, const int *scene,
+                               int n_scene, int n_body, const double *x_w_b, const double *twist_w_b,
+                               const double *d_x_w_b, const double *d_twist_w_b, double *d_pose, double *d_twist, double *d_x_w_r2);
+
+/*
+ * pfc_items_from_bodies_device, pfc_dual_seeds_from_bodies_device, then exactly pfc_eval_dual_device on the same stream, reading the
+ * d_pose / d_twist / d_dpose / d_dtwist the kernels wrote (all four required here; d_x_w_r2, d_body_1, d_body_2 and d_dx_w_r2 may be
+ * NULL).  d_s / d_ds as pfc_eval_dual_device.  The item and seed buffers are the caller's: the Dual scatter needs four of them, and
+ * the handle allocates nothing per evaluation.  pfc_check() afterwards as after pfc_eval_dual_device; on PFC_ERR_OVERFLOW re-issue
+ * this call (items and seeds are formed again, to the same bytes).
+ */
+int pfc_eval_dual_bodies_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene,
+                                int n_scene, int n_body, const double *d_x_w_b, const double *d_twist_w_b,
+                                const double *d_dx_w_b, const double *d_dtwist_w_b, const double *d_s, const double *d_ds,
+                                double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
+                                double *d_dpose, double *d_dtwist, double *d_dx_w_r2,
+                                double *d_wrench, double *d_sdot, double *d_dwrench, double *d_dsdot, int *d_counts, void *stream);
+/*
+ * The later chunks of a Jacobian at the kept point, from body-state partials: pfc_dual_seeds_from_bodies_device, then exactly
+ * pfc_eval_dual_device_more on the d_dpose / d_dtwist it wrote (both required; d_dx_w_r2 may be NULL).  The value states are read
+ * again (the partials of a product need them) but no value output is written.  Single-device handles check _more's preconditions before
+ * anything is launched -- PFC_ERR_STATE without a checked pfc_eval_dual_device evaluation to extend, PFC_ERR_BAD_ARG if n_items is not
+ * that evaluation's -- and then write nothing.  Multi-device handles form the seeds on the first device and then return _more's own
+ * status: there the seed buffers are written even where _more refuses.  Follow with pfc_check() as after pfc_eval_dual_device_more.
+ */
+int pfc_eval_dual_bodies_device_more(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene,
+                                     int n_scene, int n_body, const double *d_x_w_b, const double *d_twist_w_b,
+                                     const double *d_dx_w_b, const double *d_dtwist_w_b, const double *d_ds,
+                                     double *d_dpose, double *d_dtwist, double *d_dx_w_r2, double *d_dwrench, double *d_dsdot, void *stream);
+
+/*
  * The contact surface of n_items items: per item what the reference's TractionCache holds after forceAllElasticIntersections!
  * (src/structs.jl; filled by src/contact_algorithms_non_friction.jl:217-265), the clipped polygons it was integrated over, and
  * normal_wrench / normal_wrench_cop (src/contact_algorithms_normal.jl:2-34) -- what test/test_normal.jl:31-41 and

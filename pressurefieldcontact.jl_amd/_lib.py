@@ -63,6 +63,13 @@ SIGNATURES = {
     "pfc_items_from_bodies": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip]),
     "pfc_eval_bodies_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 12),
     "pfc_eval_bodies": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _ip]),
+    "pfc_dual_seeds_from_bodies_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+                                          + [C.c_void_p] * 8),
+    "pfc_dual_seeds_from_bodies": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "pfc_eval_dual_bodies_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+                                    + [C.c_void_p] * 20),
+    "pfc_eval_dual_bodies_device_more": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+                                         + [C.c_void_p] * 11),
     "pfc_build_tree": (C.c_int, [C.c_int, _dp, C.c_int, C.c_int, _ip, _dp, C.c_int, _dp, _dp, _dp, _ip, _ip]),
     "pfc_tree_last_error": (C.c_char_p, []),
     "pfc_scatter_generalized": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _ip, _ip, C.c_int, C.c_int, C.c_int, _dp, _dp]),

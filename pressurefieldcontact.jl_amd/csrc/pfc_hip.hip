@@ -21,7 +21,8 @@
 //   pfc_ljac.h     k_ljac_seeds / k_ljac_pack / k_ljac_apply: per-item contact Jacobians from unit-seed Dual passes and their
 //                  product with further seed chunks (pfc_local_jacobian, pfc_apply_local_jacobian)
 //   pfc_bodies.h   k_items_from_bodies: pose, twist, x_rw_r2 and body ids of every item from the bodies' world poses and twists
-//                  (pfc_items_from_bodies, pfc_eval_bodies)
+//                  (pfc_items_from_bodies, pfc_eval_bodies); k_dual_seeds_from_bodies: their partials from the partials of the body
+//                  states (pfc_dual_seeds_from_bodies, pfc_eval_dual_bodies_device[_more])
 //   pfc_multi.h    host code: multi-device handles (pfc_create_multi)
 // This file: mesh record preparation (k_prep_tri, k_prep_tet), per-item setup (k_setup_items), work-list management,
 // hipGraph capture / replay, the two-half evaluation and every extern "C" entry point.
@@ -3084,18 +3085,25 @@ static int bodies_check_args(pfc_context *h, const char *who, int n_items, const
     return PFC_OK;
 }
 
+// The bind table's upload on st if it is stale (the one synchronisation of this path: once per binding, ordered behind st's
+// earlier work).
+static int bodies_upload_bind(pfc_context *h, hipStream_t st) {
+    const int n_ins = (int)h->ins.size();
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!h->bodies_stale) return PFC_OK;
+    h->ins_bodies.resize(2 * (size_t)n_ins, kBodiesUnbound);
+    HIP_TRY(h, h->bodies_bind.ensure(2 * (size_t)n_ins));
+    HIP_TRY(h, hipMemcpyAsync(h->bodies_bind.p, h->ins_bodies.data(), sizeof(int) * 2 * (size_t)n_ins, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    h->bodies_stale = false;
+    return PFC_OK;
+}
+
 // The table's upload if it is stale, and the kernel, on st.  Every pointer is a device pointer.
 static int bodies_launch(pfc_context *h, int n_items, const int *ins_ids, const int *scene, int n_scene, int n_body, const double *x_w_b,
                          const double *twist_w_b, double *pose, double *twist, double *x_w_r2, int *body_1, int *body_2, hipStream_t st) {
     const int n_ins = (int)h->ins.size();
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (h->bodies_stale) {      // (the one synchronisation of this path: once per binding, ordered behind st's earlier work)
-        h->ins_bodies.resize(2 * (size_t)n_ins, kBodiesUnbound);
-        HIP_TRY(h, h->bodies_bind.ensure(2 * (size_t)n_ins));
-        HIP_TRY(h, hipMemcpyAsync(h->bodies_bind.p, h->ins_bodies.data(), sizeof(int) * 2 * (size_t)n_ins, hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipStreamSynchronize(st));
-        h->bodies_stale = false;
-    }
+    { const int rc = bodies_upload_bind(h, st); if (rc != PFC_OK) return rc; }
     BodiesArgs a;
     a.n_items = n_items; a.n_ins = n_ins; a.n_scene = n_scene; a.n_body = n_body; a.ins_ids = ins_ids; a.scene = scene;
     a.bind = h->bodies_bind.p; a.x_w_b = x_w_b; a.twist_w_b = twist_w_b; a.pose = pose; a.twist = twist; a.x_w_r2 = x_w_r2;
@@ -3191,6 +3199,141 @@ int pfc_eval_bodies(pfc_handle h, int n_items, const int *ins_ids, const int *sc
     const int rc = pfc_items_from_bodies(h, n_items, ins_ids, scene, n_scene, n_body, x_w_b, twist_w_b, pose, twist, x_w_r2, body_1, body_2);
     if (rc != PFC_OK) return rc;
     return pfc_eval(h, n_items, ins_ids, pose, twist, s, wrench, sdot, counts);
+}
+
+// ---- Dual seeds of the items from body states and their partials (pfc_bodies.h) -------------------------------------------------
+// Argument, state and binding checks of the device forms: those of pfc_items_from_bodies_device, and n_dir.
+static int bodies_seeds_check_device(pfc_context *h, const char *who, int n_items, int n_dir, const int *d_ins_ids, int n_scene, int n_body,
+                                     const double *d_x_w_b, const double *d_twist_w_b) {
+    int rc = bodies_check_args(h, who, n_items, d_ins_ids, n_scene, n_body, d_x_w_b, d_twist_w_b);
+    if (rc != PFC_OK) return rc;
+    if (n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "%s: n_dir must be in 1..16", who);
+    if (n_items == 0) return PFC_OK;
+    const int n_used = d_ins_ids ? (int)h->ins.size() : n_items;
+    for (int k = 0; k < n_used; ++k)
+        if ((rc = bodies_check_ins(h, who, k, n_body)) != PFC_OK) return rc;
+    return PFC_OK;
+}
+
+// The table's upload if it is stale, and k_dual_seeds_from_bodies, on st.  Every pointer is a device pointer.
+static int bodies_seeds_launch(pfc_context *h, int n_items, int n_dir, const int *ins_ids, const int *scene, int n_scene, int n_body,
+                               const double *x_w_b, const double *twist_w_b, const double *dx_w_b, const double *dtwist_w_b, double *dpose,
+                               double *dtwist, double *dx_w_r2, hipStream_t st) {
+    { const int rc = bodies_upload_bind(h, st); if (rc != PFC_OK) return rc; }
+    if (!dpose && !dtwist && !dx_w_r2) return PFC_OK;
+    BodiesSeedArgs a;
+    a.n_items = n_items; a.n_dir = n_dir; a.n_ins = (int)h->ins.size(); a.n_scene = n_scene; a.n_body = n_body;
+    a.ins_ids = ins_ids; a.scene = scene; a.bind = h->bodies_bind.p; a.x_w_b = x_w_b; a.twist_w_b = twist_w_b;
+    a.dx_w_b = dx_w_b; a.dtwist_w_b = dtwist_w_b; a.dpose = dpose; a.dtwist = dtwist; a.dx_w_r2 = dx_w_r2;
+    const size_t nk = (size_t)n_items * n_dir;
+    hipLaunchKernelGGL(k_dual_seeds_from_bodies, dim3((unsigned)((nk + kBodiesWave - 1) / kBodiesWave)), dim3(kBodiesWave), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+int pfc_dual_seeds_from_bodies_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
+                                      int n_body, const double *d_x_w_b, const double *d_twist_w_b, const double *d_dx_w_b,
+                                      const double *d_dtwist_w_b, double *d_dpose, double *d_dtwist, double *d_dx_w_r2, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_dual_seeds_from_bodies_device(c, n_items, n_dir, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_dx_w_b,
+                                                     d_dtwist_w_b, d_dpose, d_dtwist, d_dx_w_r2, stream); });
+    const int rc = bodies_seeds_check_device(h, "pfc_dual_seeds_from_bodies_device", n_items, n_dir, d_ins_ids, n_scene, n_body, d_x_w_b,
+                                             d_twist_w_b);
+    if (rc != PFC_OK || n_items == 0) return rc;
+    return bodies_seeds_launch(h, n_items, n_dir, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b, d_dpose,
+                               d_dtwist, d_dx_w_r2, stream ? (hipStream_t)stream : h->stream);
+}
+
+int pfc_dual_seeds_from_bodies(pfc_handle h, int n_items, int n_dir, const int *ins_ids, const int *scene, int n_scene, int n_body,
+                               const double *x_w_b, const double *twist_w_b, const double *d_x_w_b, const double *d_twist_w_b,
+                               double *d_pose, double *d_twist, double *d_x_w_r2) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_dual_seeds_from_bodies(c, n_items, n_dir, ins_ids, scene, n_scene, n_body, x_w_b, twist_w_b, d_x_w_b, d_twist_w_b,
+                                              d_pose, d_twist, d_x_w_r2); });
+    const char *who = "pfc_dual_seeds_from_bodies";
+    int rc = bodies_check_args(h, who, n_items, ins_ids, n_scene, n_body, x_w_b, twist_w_b);
+    if (rc != PFC_OK) return rc;
+    if (n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "%s: n_dir must be in 1..16", who);
+    if (n_items == 0) return PFC_OK;
+    for (int i = 0; i < n_items; ++i) {
+        const int ins = ins_ids ? ins_ids[i] : i;
+        if (ins < 0 || ins >= (int)h->ins.size() || (scene && (scene[i] < 0 || scene[i] >= n_scene)))
+            return fail(h, PFC_ERR_BAD_ARG, "%s: instruction / scene id out of range (item %d)", who, i);
+        if ((rc = bodies_check_ins(h, who, ins, n_body)) != PFC_OK) return rc;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    const size_t n = (size_t)n_items, nb = (size_t)n_scene * n_body, nk = n * n_dir, nbk = nb * n_dir;
+    // [x_w_b 12 | twist_w_b 6] x bodies, their partials x n_dir, [d_pose 24 | d_twist 6 | d_x_w_r2 12] x n n_dir; [ids | scene] x n
+    HIP_TRY(h, h->bodies_d.ensure(nb * 18 + nbk * 18 + nk * 42 + 1));
+    HIP_TRY(h, h->bodies_i.ensure(n * 2));
+    double *dx = h->bodies_d.p, *dtw = dx + nb * 12, *ddx = dtw + nb * 6, *ddtw = ddx + nbk * 12, *dpose = ddtw + nbk * 6,
+           *dtwist = dpose + nk * 24, *dxr = dtwist + nk * 6;
+    int *dids = h->bodies_i.p, *dsc = dids + n;
+    if (nb) {
+        HIP_TRY(h, hipMemcpyAsync(dx, x_w_b, sizeof(double) * nb * 12, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipMemcpyAsync(dtw, twist_w_b, sizeof(double) * nb * 6, hipMemcpyHostToDevice, st));
+        if (d_x_w_b) HIP_TRY(h, hipMemcpyAsync(ddx, d_x_w_b, sizeof(double) * nbk * 12, hipMemcpyHostToDevice, st));
+        if (d_twist_w_b) HIP_TRY(h, hipMemcpyAsync(ddtw, d_twist_w_b, sizeof(double) * nbk * 6, hipMemcpyHostToDevice, st));
+    }
+    if (ins_ids) HIP_TRY(h, hipMemcpyAsync(dids, ins_ids, sizeof(int) * n, hipMemcpyHostToDevice, st));
+    if (scene) HIP_TRY(h, hipMemcpyAsync(dsc, scene, sizeof(int) * n, hipMemcpyHostToDevice, st));
+    rc = bodies_seeds_launch(h, n_items, n_dir, ins_ids ? dids : nullptr, scene ? dsc : nullptr, n_scene, n_body, dx, dtw,
+                             d_x_w_b ? ddx : nullptr, d_twist_w_b ? ddtw : nullptr, d_pose ? dpose : nullptr, d_twist ? dtwist : nullptr,
+                             d_x_w_r2 ? dxr : nullptr, st);
+    if (rc != PFC_OK) return rc;
+    if (d_pose) HIP_TRY(h, hipMemcpyAsync(d_pose, dpose, sizeof(double) * nk * 24, hipMemcpyDeviceToHost, st));
+    if (d_twist) HIP_TRY(h, hipMemcpyAsync(d_twist, dtwist, sizeof(double) * nk * 6, hipMemcpyDeviceToHost, st));
+    if (d_x_w_r2) HIP_TRY(h, hipMemcpyAsync(d_x_w_r2, dxr, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return PFC_OK;
+}
+
+// k_items_from_bodies, k_dual_seeds_from_bodies, then exactly pfc_eval_dual_device on the buffers they wrote, on the same stream.
+int pfc_eval_dual_bodies_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene, int n_body,
+                                const double *d_x_w_b, const double *d_twist_w_b, const double *d_dx_w_b, const double *d_dtwist_w_b,
+                                const double *d_s, const double *d_ds, double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1,
+                                int *d_body_2, double *d_dpose, double *d_dtwist, double *d_dx_w_r2, double *d_wrench, double *d_sdot,
+                                double *d_dwrench, double *d_dsdot, int *d_counts, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    const char *who = "pfc_eval_dual_bodies_device";
+    if (n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "%s: n_dir must be in 1..16", who);
+    if (n_items > 0 && (!d_pose || !d_twist || !d_dpose || !d_dtwist))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: d_pose, d_twist, d_dpose and d_dtwist are the evaluation's inputs", who);
+    int rc = pfc_items_from_bodies_device(h, n_items, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_pose, d_twist, d_x_w_r2,
+                                          d_body_1, d_body_2, stream);
+    if (rc != PFC_OK) return rc;
+    rc = pfc_dual_seeds_from_bodies_device(h, n_items, n_dir, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_dx_w_b,
+                                           d_dtwist_w_b, d_dpose, d_dtwist, d_dx_w_r2, stream);
+    if (rc != PFC_OK) return rc;
+    return pfc_eval_dual_device(h, n_items, n_dir, d_ins_ids, d_pose, d_twist, d_s, d_dpose, d_dtwist, d_ds, d_wrench, d_sdot, d_dwrench,
+                                d_dsdot, d_counts, stream);
+}
+
+// k_dual_seeds_from_bodies, then exactly pfc_eval_dual_device_more on the seeds it wrote, on the same stream.
+int pfc_eval_dual_bodies_device_more(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene, int n_body,
+                                     const double *d_x_w_b, const double *d_twist_w_b, const double *d_dx_w_b, const double *d_dtwist_w_b,
+                                     const double *d_ds, double *d_dpose, double *d_dtwist, double *d_dx_w_r2, double *d_dwrench,
+                                     double *d_dsdot, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    const char *who = "pfc_eval_dual_bodies_device_more";
+    if (!h->multi) {      // _more's own preconditions, before the seeds are written
+        const int rc = bodies_seeds_check_device(h, who, n_items, n_dir, d_ins_ids, n_scene, n_body, d_x_w_b, d_twist_w_b);
+        if (rc != PFC_OK) return rc;
+        if (!h->device_kept())
+            return fail(h, PFC_ERR_STATE, "%s: no checked pfc_eval_dual_device evaluation on this handle to extend", who);
+        if (n_items != h->kept.n)
+            return fail(h, PFC_ERR_BAD_ARG, "%s: n_items is %d, the kept evaluation has %d items", who, n_items, h->kept.n);
+        if (!d_dpose || !d_dtwist || !d_dwrench || !d_dsdot) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    }
+    const int rc = pfc_dual_seeds_from_bodies_device(h, n_items, n_dir, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_dx_w_b,
+                                                     d_dtwist_w_b, d_dpose, d_dtwist, d_dx_w_r2, stream);
+    if (rc != PFC_OK) return rc;
+    return pfc_eval_dual_device_more(h, n_dir, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, stream);
 }
 
 // The Dual evaluation with the broadphase pose of m.float's state (calcTriTetIntersections!, non_friction.jl:94-101): the block is

@@ -19,10 +19,11 @@ constexpr int kScatTile = 64;      // items per LDS tile of k_scat_proj
 constexpr int kScatMaxDir = 16;
 
 // One partial of a ForwardDiff.Dual: value and the partial of one seed direction, with ForwardDiff's rules (the product in the
-// order of _mul_partials: d(a b) = da b + a db).
+// order of _mul_partials: d(a b) = da b + a db).  pfc_bodies.h evaluates the item expressions on the same type.
 struct ScatDual { double v, d; };
 __device__ inline ScatDual operator+(ScatDual a, ScatDual b) { return {a.v + b.v, a.d + b.d}; }
 __device__ inline ScatDual operator-(ScatDual a, ScatDual b) { return {a.v - b.v, a.d - b.d}; }
+__device__ inline ScatDual operator-(ScatDual a) { return {-a.v, -a.d}; }
 __device__ inline ScatDual operator*(ScatDual a, ScatDual b) { return {a.v * b.v, a.d * b.v + a.v * b.d}; }
 
 // RigidBodyDynamics transform(wrench, x_rw_r2) (the C oracle's statements): w [ang; lin], x = R (9, column-major), t (3);

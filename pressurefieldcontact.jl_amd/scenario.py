@@ -313,6 +313,17 @@ class BodyItems:
     body_2: np.ndarray
 
 
+@dataclass(eq=False)
+class BodySeeds:
+    """What MechanismScenario.dual_seeds_from_bodies returns: the partials of BodyItems' pose, twist and x_w_r2 per seed direction."""
+    d_pose: np.ndarray      # (n,n_dir,24) partials of x_r2_r1 then x_r1_r2
+    d_twist: np.ndarray     # (n,n_dir,6) partials of twist_r2_r1_r2
+    d_x_w_r2: np.ndarray    # (n,n_dir,12) partials of x_rw_r2
+
+    def __iter__(self):
+        return iter((self.d_pose, self.d_twist, self.d_x_w_r2))
+
+
 class MechanismScenario:
     """Contact part of MechanismScenario{T} (src/mechanism_scenario.jl:166-199), backed by a pfc_handle."""
 
@@ -784,6 +795,77 @@ class MechanismScenario:
         self._check(_lib.lib().pfc_eval_bodies_device(self._h, int(n_items), d_ins_ids or None, d_scene or None, int(n_scene), int(n_body),
                                                       d_x_w_b or None, d_twist_w_b or None, d_s or None, d_pose, d_twist, d_x_w_r2 or None,
                                                       d_body_1 or None, d_body_2 or None, d_wrench, d_sdot, d_counts or None, stream or None))
+
+    def dual_seeds_from_bodies(self, x_w_b, twist_w_b, d_x_w_b, d_twist_w_b, ins_ids: Optional[Sequence[int]] = None,
+                               scene=None) -> BodySeeds:
+        """The Dual seeds of items_from_bodies' items from the partials of the bodies' world states (pfc_dual_seeds_from_bodies, host
+        buffers, synchronous).  x_w_b, twist_w_b, ins_ids, scene as items_from_bodies; d_x_w_b (n_body,n_dir,12) or
+        (n_scene,n_body,n_dir,12) and d_twist_w_b likewise with 6, either may be None (zeros), not both (n_dir comes from them)."""
+        n, head, it, outs, keep = self._bodies_call(x_w_b, twist_w_b, ins_ids, scene)
+        n_scene, n_body = head[4], head[5]
+        if d_x_w_b is None and d_twist_w_b is None:
+            raise ValueError("one of d_x_w_b and d_twist_w_b must be given: they carry n_dir")
+        dx_a = dtw_a = dx_p = dtw_p = None
+        n_dir = None
+        for a, width, name in ((d_x_w_b, 12, "d_x_w_b"), (d_twist_w_b, 6, "d_twist_w_b")):
+            if a is None:
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.ndim == 3:
+                a = a[None]
+            if a.ndim != 4 or a.shape[0] != n_scene or a.shape[1] != n_body or a.shape[3] != width or (n_dir not in (None, a.shape[2])):
+                raise ValueError(f"{name} must be (n_body, n_dir, {width}) or (n_scene, n_body, n_dir, {width})")
+            n_dir = a.shape[2]
+            if width == 12:
+                dx_a, dx_p = a, a.ctypes.data_as(_dp)
+            else:
+                dtw_a, dtw_p = a, a.ctypes.data_as(_dp)
+        sd = BodySeeds(np.zeros((n, n_dir, 24)), np.zeros((n, n_dir, 6)), np.zeros((n, n_dir, 12)))
+        self._check(_lib.lib().pfc_dual_seeds_from_bodies(head[0], n, n_dir, *head[2:], dx_p, dtw_p, sd.d_pose.ctypes.data_as(_dp),
+                                                          sd.d_twist.ctypes.data_as(_dp), sd.d_x_w_r2.ctypes.data_as(_dp)))
+        return sd
+
+    def force_all_elastic_intersections_dual_bodies(self, x_w_b, twist_w_b, s, d_x_w_b, d_twist_w_b, d_s=None,
+                                                    ins_ids: Optional[Sequence[int]] = None, scene=None):
+        """force_all_elastic_intersections_dual on the items of items_from_bodies and the seeds of dual_seeds_from_bodies (host
+        buffers, synchronous; three calls composed here).  Returns (wrench, sdot, d_wrench, d_sdot, counts, items: BodyItems,
+        seeds: BodySeeds)."""
+        it = self.items_from_bodies(x_w_b, twist_w_b, ins_ids, scene)
+        sd = self.dual_seeds_from_bodies(x_w_b, twist_w_b, d_x_w_b, d_twist_w_b, ins_ids, scene)
+        out = self.force_all_elastic_intersections_dual(it.pose, it.twist, s, sd.d_pose, sd.d_twist, d_s, ins_ids)
+        return (*out, it, sd)
+
+    def dual_seeds_from_bodies_device(self, n_items: int, n_dir: int, d_ins_ids: int, d_scene: int, n_scene: int, n_body: int,
+                                      d_x_w_b: int, d_twist_w_b: int, d_dx_w_b: int, d_dtwist_w_b: int, d_dpose: int, d_dtwist: int,
+                                      d_dx_w_r2: int, stream: int = 0):
+        """pfc_dual_seeds_from_bodies_device: raw device addresses (0: NULL for d_ins_ids, d_scene, either partial array and any output
+        not wanted); asynchronous on `stream`, not an evaluation, no check() needed."""
+        self._check(_lib.lib().pfc_dual_seeds_from_bodies_device(
+            self._h, int(n_items), int(n_dir), d_ins_ids or None, d_scene or None, int(n_scene), int(n_body), d_x_w_b or None,
+            d_twist_w_b or None, d_dx_w_b or None, d_dtwist_w_b or None, d_dpose or None, d_dtwist or None, d_dx_w_r2 or None,
+            stream or None))
+
+    def eval_dual_bodies_device(self, n_items: int, n_dir: int, d_ins_ids: int, d_scene: int, n_scene: int, n_body: int, d_x_w_b: int,
+                                d_twist_w_b: int, d_dx_w_b: int, d_dtwist_w_b: int, d_s: int, d_ds: int, d_pose: int, d_twist: int,
+                                d_x_w_r2: int, d_body_1: int, d_body_2: int, d_dpose: int, d_dtwist: int, d_dx_w_r2: int, d_wrench: int,
+                                d_sdot: int, d_dwrench: int, d_dsdot: int, d_counts: int, stream: int = 0):
+        """pfc_eval_dual_bodies_device: items_from_bodies_device, dual_seeds_from_bodies_device, then eval_dual_device on the buffers
+        they wrote, on one stream; asynchronous, follow with check() (re-issue on ERR_OVERFLOW)."""
+        self._check(_lib.lib().pfc_eval_dual_bodies_device(
+            self._h, int(n_items), int(n_dir), d_ins_ids or None, d_scene or None, int(n_scene), int(n_body), d_x_w_b or None,
+            d_twist_w_b or None, d_dx_w_b or None, d_dtwist_w_b or None, d_s or None, d_ds or None, d_pose, d_twist, d_x_w_r2 or None,
+            d_body_1 or None, d_body_2 or None, d_dpose, d_dtwist, d_dx_w_r2 or None, d_wrench, d_sdot, d_dwrench, d_dsdot,
+            d_counts or None, stream or None))
+
+    def eval_dual_bodies_device_more(self, n_items: int, n_dir: int, d_ins_ids: int, d_scene: int, n_scene: int, n_body: int,
+                                     d_x_w_b: int, d_twist_w_b: int, d_dx_w_b: int, d_dtwist_w_b: int, d_ds: int, d_dpose: int,
+                                     d_dtwist: int, d_dx_w_r2: int, d_dwrench: int, d_dsdot: int, stream: int = 0):
+        """pfc_eval_dual_bodies_device_more: dual_seeds_from_bodies_device, then eval_dual_device_more on the seeds it wrote (a later
+        chunk of the Jacobian at the kept point); asynchronous, follow with check()."""
+        self._check(_lib.lib().pfc_eval_dual_bodies_device_more(
+            self._h, int(n_items), int(n_dir), d_ins_ids or None, d_scene or None, int(n_scene), int(n_body), d_x_w_b or None,
+            d_twist_w_b or None, d_dx_w_b or None, d_dtwist_w_b or None, d_ds or None, d_dpose, d_dtwist, d_dx_w_r2 or None, d_dwrench,
+            d_dsdot, stream or None))
 
     def contact_surface(self, pose, twist, ins_ids: Optional[Sequence[int]] = None) -> ContactSurface:
         """The contact surface of every item (pfc_contact_surface): clipped polygons, traction points and normal wrench / cop in
