@@ -305,6 +305,53 @@ using Event = Owned<hipEvent_t, hipEventDestroy>;
 using Stream = Owned<hipStream_t, hipStreamDestroy>;
 using GraphExec = Owned<hipGraphExec_t, hipGraphExecDestroy>;
 
+// What the host-pointer form of a _device call does with its arguments.  The fields are declared in order: a host pointer (null:
+// the caller gave none), an element count and a direction.  commit() places each at the next 256-byte boundary of ONE device block
+// (ints and doubles share it), grows the block (its content is lost) and enqueues the uploads of the inputs; at<T>(k) is field
+// k's device pointer, null where the host gave none; finish() enqueues the downloads of the outputs and synchronises.  Every form
+// synchronises before it returns, so one block per context (pfc_context::stage) serves them all.
+struct Stage {
+    enum { In = 1, Out = 2, Part = 4 };      // Part: an output whose used length the caller learns later (fetch)
+    struct Field { void *host; size_t elem, count, off; int dir; };
+    DevBuf<char> &buf;
+    hipStream_t st;
+    static constexpr int kMaxFields = 16;
+    Field f[kMaxFields];
+    int nf = 0;                              // fields declared; one past kMaxFields: too many, commit() fails
+    size_t total = 0;
+    Stage(DevBuf<char> &b, hipStream_t s) : buf(b), st(s) {}
+    void clear() { nf = 0; total = 0; }
+    template <class T> int add(int dir, const T *host, size_t count) {
+        if (nf >= kMaxFields) { nf = kMaxFields + 1; return 0; }
+        f[nf] = Field{const_cast<T *>(host), sizeof(T), count, total, dir};
+        total = (total + sizeof(T) * count + 255) & ~(size_t)255;
+        return nf++;
+    }
+    template <class T> int in(const T *host, size_t count) { return add(In, host, count); }
+    template <class T> int out(T *host, size_t count) { return add(Out, host, count); }
+    // a field without a host side: device scratch the caller fills (hipMemsetAsync)
+    template <class T> int scratch(size_t count) { return add(0, (const T *)nullptr, count); }
+    hipError_t commit() {
+        hipError_t e = nf > kMaxFields ? hipErrorInvalidValue : buf.ensure(total);
+        for (int k = 0; k < nf && e == hipSuccess; ++k)
+            if ((f[k].dir & In) && f[k].host && f[k].count)
+                e = hipMemcpyAsync(buf.p + f[k].off, f[k].host, f[k].elem * f[k].count, hipMemcpyHostToDevice, st);
+        return e;
+    }
+    template <class T> T *at(int k) const { return f[k].host || !f[k].dir ? reinterpret_cast<T *>(buf.p + f[k].off) : nullptr; }
+    // the download of the first `count` elements of field k, enqueued
+    hipError_t fetch(int k, size_t count) {
+        if (!f[k].host || !count) return hipSuccess;
+        return hipMemcpyAsync(f[k].host, buf.p + f[k].off, f[k].elem * count, hipMemcpyDeviceToHost, st);
+    }
+    hipError_t finish() {
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < nf && e == hipSuccess; ++k)
+            if (f[k].dir & Out) e = fetch(k, f[k].count);
+        return e == hipSuccess ? hipStreamSynchronize(st) : e;
+    }
+};
+
 struct HostMesh {
     int n_pt = 0, n_tri = 0, n_tet = 0, n_node = 0, n_leaf = 0, depth = 0;
     double Ebar = 0.0;
@@ -443,10 +490,9 @@ struct pfc_context {
     DevBuf<double> dual_in, dual_acc, dual_res, dual_out, dual_poly;   // pfc_eval_dual
     DevBuf<int2> dual_pkey;
     DevBuf<int> dual_sel, dual_flag;                        // pairs a chunk has work for; per-item marks (+ the list's counter)
-    DevBuf<double> scat_d;                                  // pfc_scatter_generalized
-    DevBuf<int> scat_i;
-    DevBuf<double> sdual_d, sdual_w;                        // pfc_scatter_generalized_dual: host-form staging; world wrenches
-    DevBuf<int> sdual_i;                                    // ids, CSR keys (+ the sort's second key array), offsets, count
+    DevBuf<char> stage;                                     // the host-pointer forms' arguments on the device (Stage): every form synchronises before it returns
+    DevBuf<double> sdual_w;                                 // pfc_scatter_generalized_dual[_device]: world wrenches
+    DevBuf<int> sdual_i;                                    // its device form's CSR keys (+ the sort's second key array), offsets, count
     DevBuf<char> sdual_tmp;                                 // its rocPRIM sort storage
     DevBuf<int> surv;                                       // candidate indices of contributing pairs
     DevBuf<int> rgn;                                        // region counters of the polygon / record lists
@@ -537,14 +583,10 @@ struct pfc_context {
     // per-item contact Jacobians (pfc_ljac.h)
     DevBuf<double> ljac_seed;          // unit seeds of the three passes for ljac_seed.cap / kLjacSeedDoubles items (k_ljac_seeds)
     DevBuf<double> ljac_out;           // the passes' partials, n_items x 432
-    DevBuf<double> ljac_io;            // staging of the host-buffer forms
-    DevBuf<int> ljac_ids;
     // contact items from body states (pfc_bodies.h)
     std::vector<int> ins_bodies;       // per instruction {body of mesh_1, body of mesh_2} (pfc_set_instruction_bodies); grows with the ids it is given
     DevBuf<int> bodies_bind;           // its device copy, one pair per instruction (kBodiesUnbound where none was given)
     bool bodies_stale = true;          // the device copy is older than ins_bodies: uploaded by the next launch
-    DevBuf<double> bodies_d;           // staging of the host-buffer form: body states in, items out
-    DevBuf<int> bodies_i;
     DevBuf<unsigned long long> surf_keys[2];
     DevBuf<char> surf_tmp;                            // rocPRIM scan / sort
     PinBuf<long long> h_surf;                         // pinned mirror of surf_out
@@ -553,13 +595,9 @@ struct pfc_context {
     bool surf_cap_short = false;        // the last checked surface call failed only for the caller's capacities
     int surf_n_ctr = 0;
     long long surf_cap_poly = 0, surf_cap_trac = 0;   // capacities of the pending call
-    DevBuf<long long> surf_hl;          // host-pointer form: device staging of the outputs
-    DevBuf<int> surf_hi;
-    DevBuf<double> surf_hd, surf_in;
-    size_t surf_hcap_poly = 0, surf_hcap_trac = 0;    // ... sized for this many polygons / traction points
+    size_t surf_hcap_poly = 0, surf_hcap_trac = 0;    // host-pointer form: its outputs are staged for this many polygons / traction points
     // pfc_contact_surface_fric (pfc_surface_fric.h): per item the moment and friction records of its waves and eig_item's block
     DevBuf<double> sfric_mom, sfric_sum, sfric_res;
-    DevBuf<double> sfric_hd;            // host-pointer form: device staging of fric_summary, stiff and fric
 };
 
 namespace {
@@ -2023,35 +2061,29 @@ int surface_host(pfc_context *h, int n_items, const int *ins_ids, const double *
         poly_off[0] = 0; poly_trac[0] = 0; totals[0] = totals[1] = 0;
         return PFC_OK;
     }
-    // inputs: pose | twist | ins_ids (| s)
-    const size_t s_at = n * 30 + (n + 1) / 2 + 1;
-    HIP_TRY(h, h->surf_in.ensure(fo ? s_at + n * 6 : s_at));
-    double *di = h->surf_in.p;
-    HIP_TRY(h, hipMemcpyAsync(di, pose, sizeof(double) * n * 24, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(di + n * 24, twist, sizeof(double) * n * 6, hipMemcpyHostToDevice, h->stream));
-    if (ins_ids) HIP_TRY(h, hipMemcpyAsync(di + n * 30, ins_ids, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
-    if (fo && fo->s) HIP_TRY(h, hipMemcpyAsync(di + s_at, fo->s, sizeof(double) * n * 6, hipMemcpyHostToDevice, h->stream));
-    // outputs are staged in device buffers sized for what the last calls needed (at most the caller's capacities): a call that
-    // needs more within the caller's capacities grows them and runs again
+    // The outputs are staged for what the last calls needed (at most the caller's capacities): a call that needs more within the
+    // caller's capacities lays the block out again and runs again -- so every attempt uploads the inputs, the block may have grown.
+    Stage sg(h->stage, h->stream);
+    int k_off = 0, k_tot = 0, k_ptr = 0, k_idx = 0, k_xyz = 0, k_trac = 0, k_sum = 0, k_cnt = 0, k_fsum = 0, k_stiff = 0, k_fric = 0;
     int rc = PFC_OK;
     long long tot_p = 0, tot_t = 0;
     for (int attempt = 0; attempt < 40; ++attempt) {
         const size_t dp = (size_t)(cap_poly < (long long)h->surf_hcap_poly ? cap_poly : (long long)h->surf_hcap_poly);
         const size_t dt = (size_t)(cap_trac < (long long)h->surf_hcap_trac ? cap_trac : (long long)h->surf_hcap_trac);
-        HIP_TRY(h, h->surf_hl.ensure((n + 1) + 2 + (dp + 1)));
-        HIP_TRY(h, h->surf_hi.ensure(4 * n + 3 * dp + 1));
-        HIP_TRY(h, h->surf_hd.ensure(11 * n + 24 * dp + 8 * dt + 1));
-        long long *l_off = h->surf_hl.p, *l_tot = l_off + n + 1, *l_ptr = l_tot + 2;
-        int *i_cnt = h->surf_hi.p, *i_idx = i_cnt + 4 * n;
-        double *d_sum = h->surf_hd.p, *d_xyz = d_sum + 11 * n, *d_trac = d_xyz + 24 * dp;
+        sg.clear();
+        const int k_pose = sg.in(pose, n * 24), k_twist = sg.in(twist, n * 6), k_ids = sg.in(ins_ids, n);
+        const int k_s = sg.in(fo ? fo->s : nullptr, n * 6);      // (no fo: its fields are null)
+        k_off = sg.out(poly_off, n + 1); k_tot = sg.out(totals, 2); k_sum = sg.out(summary, 11 * n); k_cnt = sg.out(counts, 4 * n);
+        k_fsum = sg.out(fo ? fo->fric_summary : nullptr, kFricOut * n); k_stiff = sg.out(fo ? fo->stiff : nullptr, kStiffOut * n);
+        k_ptr = sg.add(Stage::Part, poly_trac, dp + 1); k_idx = sg.add(Stage::Part, poly_idx, 3 * dp);
+        k_xyz = sg.add(Stage::Part, poly_xyz, 24 * dp); k_trac = sg.add(Stage::Part, trac, 8 * dt);
+        k_fric = sg.add(Stage::Part, fo ? fo->fric : nullptr, 4 * dt);
+        HIP_TRY(h, sg.commit());
         SurfFricOut dfo;
-        if (fo) {
-            HIP_TRY(h, h->sfric_hd.ensure((kFricOut + kStiffOut) * n + 4 * dt + 1));
-            dfo.s = fo->s ? di + s_at : nullptr;
-            dfo.fric_summary = h->sfric_hd.p; dfo.stiff = dfo.fric_summary + kFricOut * n; dfo.fric = dfo.stiff + kStiffOut * n;
-        }
-        rc = surface_enqueue(h, n_items, ins_ids ? (const int *)(di + n * 30) : nullptr, di, di + n * 24, (long long)dp, (long long)dt, l_off,
-                             i_idx, d_xyz, l_ptr, d_trac, d_sum, i_cnt, l_tot, h->stream, fo ? &dfo : nullptr);
+        dfo.s = sg.at<double>(k_s); dfo.fric_summary = sg.at<double>(k_fsum); dfo.stiff = sg.at<double>(k_stiff); dfo.fric = sg.at<double>(k_fric);
+        rc = surface_enqueue(h, n_items, sg.at<int>(k_ids), sg.at<double>(k_pose), sg.at<double>(k_twist), (long long)dp, (long long)dt,
+                             sg.at<long long>(k_off), sg.at<int>(k_idx), sg.at<double>(k_xyz), sg.at<long long>(k_ptr), sg.at<double>(k_trac),
+                             sg.at<double>(k_sum), sg.at<int>(k_cnt), sg.at<long long>(k_tot), h->stream, fo ? &dfo : nullptr);
         if (rc == PFC_OK) rc = check_surface(h);
         if (rc == PFC_ERR_OVERFLOW && h->surf_cap_short) {
             tot_p = h->h_surf.p[1]; tot_t = h->h_surf.p[2];
@@ -2067,32 +2099,15 @@ int surface_host(pfc_context *h, int n_items, const int *ins_ids, const double *
         if (rc != PFC_ERR_OVERFLOW) break;
     }
     if (rc != PFC_OK && !(rc == PFC_ERR_OVERFLOW && h->surf_cap_short)) return rc;
-    const long long *l_off = h->surf_hl.p, *l_tot = l_off + n + 1, *l_ptr = l_tot + 2;
-    const size_t dp = (size_t)(cap_poly < (long long)h->surf_hcap_poly ? cap_poly : (long long)h->surf_hcap_poly);
-    const int *i_cnt = h->surf_hi.p, *i_idx = i_cnt + 4 * n;
-    const double *d_sum = h->surf_hd.p, *d_xyz = d_sum + 11 * n, *d_trac = d_xyz + 24 * dp;
-    HIP_TRY(h, hipMemcpyAsync(poly_off, l_off, sizeof(long long) * (n + 1), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(totals, l_tot, sizeof(long long) * 2, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(summary, d_sum, sizeof(double) * 11 * n, hipMemcpyDeviceToHost, h->stream));
-    if (counts) HIP_TRY(h, hipMemcpyAsync(counts, i_cnt, sizeof(int) * 4 * n, hipMemcpyDeviceToHost, h->stream));
-    const double *f_sum = fo ? h->sfric_hd.p : nullptr;
-    if (fo) {
-        HIP_TRY(h, hipMemcpyAsync(fo->fric_summary, f_sum, sizeof(double) * kFricOut * n, hipMemcpyDeviceToHost, h->stream));
-        if (fo->stiff) HIP_TRY(h, hipMemcpyAsync(fo->stiff, f_sum + kFricOut * n, sizeof(double) * kStiffOut * n, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (rc == PFC_OK) {
+    if (rc == PFC_OK) {      // the lists: as long as the totals say
         tot_p = h->h_surf.p[1]; tot_t = h->h_surf.p[2];
-        HIP_TRY(h, hipMemcpyAsync(poly_trac, l_ptr, sizeof(long long) * ((size_t)tot_p + 1), hipMemcpyDeviceToHost, h->stream));
-        if (tot_p > 0) {
-            HIP_TRY(h, hipMemcpyAsync(poly_idx, i_idx, sizeof(int) * 3 * (size_t)tot_p, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(poly_xyz, d_xyz, sizeof(double) * 24 * (size_t)tot_p, hipMemcpyDeviceToHost, h->stream));
-        }
-        if (tot_t > 0) HIP_TRY(h, hipMemcpyAsync(trac, d_trac, sizeof(double) * 8 * (size_t)tot_t, hipMemcpyDeviceToHost, h->stream));
-        if (fo && tot_t > 0)
-            HIP_TRY(h, hipMemcpyAsync(fo->fric, f_sum + (kFricOut + kStiffOut) * n, sizeof(double) * 4 * (size_t)tot_t, hipMemcpyDeviceToHost,
-                                      h->stream));
+        HIP_TRY(h, sg.fetch(k_ptr, (size_t)tot_p + 1));
+        HIP_TRY(h, sg.fetch(k_idx, 3 * (size_t)tot_p));
+        HIP_TRY(h, sg.fetch(k_xyz, 24 * (size_t)tot_p));
+        HIP_TRY(h, sg.fetch(k_trac, 8 * (size_t)tot_t));
+        HIP_TRY(h, sg.fetch(k_fric, 4 * (size_t)tot_t));
     }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, sg.finish());
     return rc;
 }
 
@@ -2972,36 +2987,29 @@ int pfc_local_jacobian(pfc_handle h, int n_items, const int *ins_ids, const doub
     HIP_TRY(h, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const size_t n = (size_t)n_items;
-    // [pose 24 | twist 6 | s 6 | zero seeds 36 | wrench 6 | sdot 6 | d_wrench 6 | d_sdot 6 | L 432] x n; [ids | counts 4] x n
-    HIP_TRY(h, c->ljac_io.ensure(n * 528));
-    HIP_TRY(h, c->ljac_ids.ensure(n * 5));
-    double *dpose = c->ljac_io.p, *dtw = dpose + n * 24, *ds = dtw + n * 6, *dz = ds + n * 6, *dwr = dz + n * 36, *dsd = dwr + n * 6;
-    double *ddw = dsd + n * 6, *ddsd = ddw + n * 6, *dL = ddsd + n * 6;
-    int *dids = c->ljac_ids.p, *dcnt = dids + n;
-    HIP_TRY(h, hipMemcpyAsync(dpose, pose, sizeof(double) * n * 24, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dtw, twist, sizeof(double) * n * 6, hipMemcpyHostToDevice, st));
-    if (s) HIP_TRY(h, hipMemcpyAsync(ds, s, sizeof(double) * n * 6, hipMemcpyHostToDevice, st));
-    if (ins_ids) HIP_TRY(h, hipMemcpyAsync(dids, ins_ids, sizeof(int) * n, hipMemcpyHostToDevice, st));
+    Stage sg(c->stage, st);
+    const int k_pose = sg.in(pose, n * 24), k_twist = sg.in(twist, n * 6), k_s = sg.in(s, n * 6), k_ids = sg.in(ins_ids, n);
+    const int k_zero = sg.scratch<double>(n * 36), k_dw = sg.scratch<double>(n * 6), k_dsd = sg.scratch<double>(n * 6);      // one direction of zero seeds and its partials
+    const int k_wr = sg.out(wrench, n * 6), k_sd = sg.out(sdot, n * 6), k_L = sg.out(L, n * kLjacSize), k_cnt = sg.out(counts, n * 4);
+    HIP_TRY(h, sg.commit());
+    double *dz = sg.at<double>(k_zero);
     HIP_TRY(h, hipMemsetAsync(dz, 0, sizeof(double) * n * 36, st));
     int rc = PFC_OK;
     for (int attempt = 0; attempt < 40; ++attempt) {
-        rc = pfc_eval_dual_device(h, n_items, 1, ins_ids ? dids : nullptr, dpose, dtw, s ? ds : nullptr, dz, dz + n * 24, dz + n * 30,
-                                  dwr, dsd, ddw, ddsd, dcnt, st);
+        rc = pfc_eval_dual_device(h, n_items, 1, sg.at<int>(k_ids), sg.at<double>(k_pose), sg.at<double>(k_twist), sg.at<double>(k_s), dz,
+                                  dz + n * 24, dz + n * 30, sg.at<double>(k_wr), sg.at<double>(k_sd), sg.at<double>(k_dw), sg.at<double>(k_dsd),
+                                  sg.at<int>(k_cnt), st);
         if (rc != PFC_OK) return rc;
         rc = pfc_check(h);
         if (rc != PFC_ERR_OVERFLOW) break;
     }
     if (rc != PFC_OK) return rc;
-    rc = pfc_local_jacobian_device(h, dL, st);
+    rc = pfc_local_jacobian_device(h, sg.at<double>(k_L), st);
     if (rc != PFC_OK) return rc;
     rc = pfc_check(h);
     if (rc != PFC_OK) return rc;
     HIP_TRY(h, hipSetDevice(c->device));
-    HIP_TRY(h, hipMemcpyAsync(wrench, dwr, sizeof(double) * n * 6, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(sdot, dsd, sizeof(double) * n * 6, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(L, dL, sizeof(double) * n * kLjacSize, hipMemcpyDeviceToHost, st));
-    if (counts) HIP_TRY(h, hipMemcpyAsync(counts, dcnt, sizeof(int) * n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
+    HIP_TRY(h, sg.finish());
     return PFC_OK;
 }
 
@@ -3033,18 +3041,15 @@ int pfc_apply_local_jacobian(pfc_handle h, int n_items, int n_dir, const double 
     HIP_TRY(h, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const size_t n = (size_t)n_items, nk = n * n_dir;
-    // [L 432 | seeds 36 n_dir | outputs 12 n_dir] x n
-    HIP_TRY(h, c->ljac_io.ensure(n * kLjacSize + nk * 48));
-    double *dL = c->ljac_io.p, *dp = dL + n * kLjacSize, *dt = dp + nk * 24, *ds = dt + nk * 6, *dw = ds + nk * 6, *dsd = dw + nk * 6;
-    HIP_TRY(h, hipMemcpyAsync(dL, L, sizeof(double) * n * kLjacSize, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dp, d_pose, sizeof(double) * nk * 24, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(dt, d_twist, sizeof(double) * nk * 6, hipMemcpyHostToDevice, st));
-    if (d_s) HIP_TRY(h, hipMemcpyAsync(ds, d_s, sizeof(double) * nk * 6, hipMemcpyHostToDevice, st));
-    const int rc = on_shard(h, c, [&](pfc_context *c1) { return pfc_apply_local_jacobian_device(c1, n_items, n_dir, dL, dp, dt, d_s ? ds : nullptr, dw, dsd, st); });
+    Stage sg(c->stage, st);
+    const int k_L = sg.in(L, n * kLjacSize), k_dp = sg.in(d_pose, nk * 24), k_dt = sg.in(d_twist, nk * 6), k_ds = sg.in(d_s, nk * 6);
+    const int k_dw = sg.out(d_wrench, nk * 6), k_dsd = sg.out(d_sdot, nk * 6);
+    HIP_TRY(h, sg.commit());
+    const int rc = on_shard(h, c, [&](pfc_context *c1) {
+        return pfc_apply_local_jacobian_device(c1, n_items, n_dir, sg.at<double>(k_L), sg.at<double>(k_dp), sg.at<double>(k_dt), sg.at<double>(k_ds),
+                                               sg.at<double>(k_dw), sg.at<double>(k_dsd), st); });
     if (rc != PFC_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(d_wrench, dw, sizeof(double) * nk * 6, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(d_sdot, dsd, sizeof(double) * nk * 6, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
+    HIP_TRY(h, sg.finish());
     return PFC_OK;
 }
 
@@ -3085,6 +3090,28 @@ static int bodies_check_args(pfc_context *h, const char *who, int n_items, const
     return PFC_OK;
 }
 
+// The host forms' ids: every item's instruction and scene id in range, its instruction bound.
+static int bodies_check_ids_host(pfc_context *h, const char *who, int n_items, const int *ins_ids, const int *scene, int n_scene, int n_body) {
+    for (int i = 0; i < n_items; ++i) {
+        const int ins = ins_ids ? ins_ids[i] : i;
+        if (ins < 0 || ins >= (int)h->ins.size() || (scene && (scene[i] < 0 || scene[i] >= n_scene)))
+            return fail(h, PFC_ERR_BAD_ARG, "%s: instruction / scene id out of range (item %d)", who, i);
+        const int rc = bodies_check_ins(h, who, ins, n_body);
+        if (rc != PFC_OK) return rc;
+    }
+    return PFC_OK;
+}
+
+// The device forms' ids are device data: without d_ins_ids the instructions 0 .. n_items - 1 must be bound, with them every instruction.
+static int bodies_check_bound_device(pfc_context *h, const char *who, int n_items, const int *d_ins_ids, int n_body) {
+    const int n_used = d_ins_ids ? (int)h->ins.size() : n_items;
+    for (int k = 0; k < n_used; ++k) {
+        const int rc = bodies_check_ins(h, who, k, n_body);
+        if (rc != PFC_OK) return rc;
+    }
+    return PFC_OK;
+}
+
 // The bind table's upload on st if it is stale (the one synchronisation of this path: once per binding, ordered behind st's
 // earlier work).
 static int bodies_upload_bind(pfc_context *h, hipStream_t st) {
@@ -3114,7 +3141,6 @@ static int bodies_launch(pfc_context *h, int n_items, const int *ins_ids, const 
     return PFC_OK;
 }
 
-// The ids are device data here: without d_ins_ids the instructions 0 .. n_items - 1 must be bound, with them every instruction.
 int pfc_items_from_bodies_device(pfc_handle h, int n_items, const int *d_ins_ids, const int *d_scene, int n_scene, int n_body,
                                  const double *d_x_w_b, const double *d_twist_w_b, double *d_pose, double *d_twist, double *d_x_w_r2,
                                  int *d_body_1, int *d_body_2, void *stream) {
@@ -3126,9 +3152,7 @@ int pfc_items_from_bodies_device(pfc_handle h, int n_items, const int *d_ins_ids
     const char *who = "pfc_items_from_bodies_device";
     int rc = bodies_check_args(h, who, n_items, d_ins_ids, n_scene, n_body, d_x_w_b, d_twist_w_b);
     if (rc != PFC_OK || n_items == 0) return rc;
-    const int n_used = d_ins_ids ? (int)h->ins.size() : n_items;
-    for (int k = 0; k < n_used; ++k)
-        if ((rc = bodies_check_ins(h, who, k, n_body)) != PFC_OK) return rc;
+    if ((rc = bodies_check_bound_device(h, who, n_items, d_ins_ids, n_body)) != PFC_OK) return rc;
     return bodies_launch(h, n_items, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_pose, d_twist, d_x_w_r2, d_body_1, d_body_2,
                          stream ? (hipStream_t)stream : h->stream);
 }
@@ -3142,35 +3166,18 @@ int pfc_items_from_bodies(pfc_handle h, int n_items, const int *ins_ids, const i
     const char *who = "pfc_items_from_bodies";
     int rc = bodies_check_args(h, who, n_items, ins_ids, n_scene, n_body, x_w_b, twist_w_b);
     if (rc != PFC_OK || n_items == 0) return rc;
-    for (int i = 0; i < n_items; ++i) {
-        const int ins = ins_ids ? ins_ids[i] : i;
-        if (ins < 0 || ins >= (int)h->ins.size() || (scene && (scene[i] < 0 || scene[i] >= n_scene)))
-            return fail(h, PFC_ERR_BAD_ARG, "%s: instruction / scene id out of range (item %d)", who, i);
-        if ((rc = bodies_check_ins(h, who, ins, n_body)) != PFC_OK) return rc;
-    }
+    if ((rc = bodies_check_ids_host(h, who, n_items, ins_ids, scene, n_scene, n_body)) != PFC_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = h->stream;
     const size_t n = (size_t)n_items, nb = (size_t)n_scene * n_body;
-    // [x_w_b 12 | twist_w_b 6] x bodies, [pose 24 | twist 6 | x_w_r2 12] x n; [ids | scene | body_1 | body_2] x n
-    HIP_TRY(h, h->bodies_d.ensure(nb * 18 + n * 42 + 1));
-    HIP_TRY(h, h->bodies_i.ensure(n * 4));
-    double *dx = h->bodies_d.p, *dtw = dx + nb * 12, *dpose = dtw + nb * 6, *dtwist = dpose + n * 24, *dxr = dtwist + n * 6;
-    int *dids = h->bodies_i.p, *dsc = dids + n, *db1 = dsc + n, *db2 = db1 + n;
-    if (nb) {
-        HIP_TRY(h, hipMemcpyAsync(dx, x_w_b, sizeof(double) * nb * 12, hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipMemcpyAsync(dtw, twist_w_b, sizeof(double) * nb * 6, hipMemcpyHostToDevice, st));
-    }
-    if (ins_ids) HIP_TRY(h, hipMemcpyAsync(dids, ins_ids, sizeof(int) * n, hipMemcpyHostToDevice, st));
-    if (scene) HIP_TRY(h, hipMemcpyAsync(dsc, scene, sizeof(int) * n, hipMemcpyHostToDevice, st));
-    rc = bodies_launch(h, n_items, ins_ids ? dids : nullptr, scene ? dsc : nullptr, n_scene, n_body, dx, dtw, pose ? dpose : nullptr,
-                       twist ? dtwist : nullptr, x_w_r2 ? dxr : nullptr, body_1 ? db1 : nullptr, body_2 ? db2 : nullptr, st);
+    Stage sg(h->stage, h->stream);
+    const int k_x = sg.in(x_w_b, nb * 12), k_tw = sg.in(twist_w_b, nb * 6), k_ids = sg.in(ins_ids, n), k_sc = sg.in(scene, n);
+    const int k_pose = sg.out(pose, n * 24), k_twist = sg.out(twist, n * 6), k_xr = sg.out(x_w_r2, n * 12);
+    const int k_b1 = sg.out(body_1, n), k_b2 = sg.out(body_2, n);
+    HIP_TRY(h, sg.commit());
+    rc = bodies_launch(h, n_items, sg.at<int>(k_ids), sg.at<int>(k_sc), n_scene, n_body, sg.at<double>(k_x), sg.at<double>(k_tw),
+                       sg.at<double>(k_pose), sg.at<double>(k_twist), sg.at<double>(k_xr), sg.at<int>(k_b1), sg.at<int>(k_b2), sg.st);
     if (rc != PFC_OK) return rc;
-    if (pose) HIP_TRY(h, hipMemcpyAsync(pose, dpose, sizeof(double) * n * 24, hipMemcpyDeviceToHost, st));
-    if (twist) HIP_TRY(h, hipMemcpyAsync(twist, dtwist, sizeof(double) * n * 6, hipMemcpyDeviceToHost, st));
-    if (x_w_r2) HIP_TRY(h, hipMemcpyAsync(x_w_r2, dxr, sizeof(double) * n * 12, hipMemcpyDeviceToHost, st));
-    if (body_1) HIP_TRY(h, hipMemcpyAsync(body_1, db1, sizeof(int) * n, hipMemcpyDeviceToHost, st));
-    if (body_2) HIP_TRY(h, hipMemcpyAsync(body_2, db2, sizeof(int) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
+    HIP_TRY(h, sg.finish());
     return PFC_OK;
 }
 
@@ -3208,11 +3215,7 @@ static int bodies_seeds_check_device(pfc_context *h, const char *who, int n_item
     int rc = bodies_check_args(h, who, n_items, d_ins_ids, n_scene, n_body, d_x_w_b, d_twist_w_b);
     if (rc != PFC_OK) return rc;
     if (n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "%s: n_dir must be in 1..16", who);
-    if (n_items == 0) return PFC_OK;
-    const int n_used = d_ins_ids ? (int)h->ins.size() : n_items;
-    for (int k = 0; k < n_used; ++k)
-        if ((rc = bodies_check_ins(h, who, k, n_body)) != PFC_OK) return rc;
-    return PFC_OK;
+    return n_items == 0 ? PFC_OK : bodies_check_bound_device(h, who, n_items, d_ins_ids, n_body);
 }
 
 // The table's upload if it is stale, and k_dual_seeds_from_bodies, on st.  Every pointer is a device pointer.
@@ -3259,37 +3262,18 @@ int pfc_dual_seeds_from_bodies(pfc_handle h, int n_items, int n_dir, const int *
     if (rc != PFC_OK) return rc;
     if (n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "%s: n_dir must be in 1..16", who);
     if (n_items == 0) return PFC_OK;
-    for (int i = 0; i < n_items; ++i) {
-        const int ins = ins_ids ? ins_ids[i] : i;
-        if (ins < 0 || ins >= (int)h->ins.size() || (scene && (scene[i] < 0 || scene[i] >= n_scene)))
-            return fail(h, PFC_ERR_BAD_ARG, "%s: instruction / scene id out of range (item %d)", who, i);
-        if ((rc = bodies_check_ins(h, who, ins, n_body)) != PFC_OK) return rc;
-    }
+    if ((rc = bodies_check_ids_host(h, who, n_items, ins_ids, scene, n_scene, n_body)) != PFC_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = h->stream;
     const size_t n = (size_t)n_items, nb = (size_t)n_scene * n_body, nk = n * n_dir, nbk = nb * n_dir;
-    // [x_w_b 12 | twist_w_b 6] x bodies, their partials x n_dir, [d_pose 24 | d_twist 6 | d_x_w_r2 12] x n n_dir; [ids | scene] x n
-    HIP_TRY(h, h->bodies_d.ensure(nb * 18 + nbk * 18 + nk * 42 + 1));
-    HIP_TRY(h, h->bodies_i.ensure(n * 2));
-    double *dx = h->bodies_d.p, *dtw = dx + nb * 12, *ddx = dtw + nb * 6, *ddtw = ddx + nbk * 12, *dpose = ddtw + nbk * 6,
-           *dtwist = dpose + nk * 24, *dxr = dtwist + nk * 6;
-    int *dids = h->bodies_i.p, *dsc = dids + n;
-    if (nb) {
-        HIP_TRY(h, hipMemcpyAsync(dx, x_w_b, sizeof(double) * nb * 12, hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipMemcpyAsync(dtw, twist_w_b, sizeof(double) * nb * 6, hipMemcpyHostToDevice, st));
-        if (d_x_w_b) HIP_TRY(h, hipMemcpyAsync(ddx, d_x_w_b, sizeof(double) * nbk * 12, hipMemcpyHostToDevice, st));
-        if (d_twist_w_b) HIP_TRY(h, hipMemcpyAsync(ddtw, d_twist_w_b, sizeof(double) * nbk * 6, hipMemcpyHostToDevice, st));
-    }
-    if (ins_ids) HIP_TRY(h, hipMemcpyAsync(dids, ins_ids, sizeof(int) * n, hipMemcpyHostToDevice, st));
-    if (scene) HIP_TRY(h, hipMemcpyAsync(dsc, scene, sizeof(int) * n, hipMemcpyHostToDevice, st));
-    rc = bodies_seeds_launch(h, n_items, n_dir, ins_ids ? dids : nullptr, scene ? dsc : nullptr, n_scene, n_body, dx, dtw,
-                             d_x_w_b ? ddx : nullptr, d_twist_w_b ? ddtw : nullptr, d_pose ? dpose : nullptr, d_twist ? dtwist : nullptr,
-                             d_x_w_r2 ? dxr : nullptr, st);
+    Stage sg(h->stage, h->stream);
+    const int k_x = sg.in(x_w_b, nb * 12), k_tw = sg.in(twist_w_b, nb * 6), k_dx = sg.in(d_x_w_b, nbk * 12), k_dtw = sg.in(d_twist_w_b, nbk * 6);
+    const int k_ids = sg.in(ins_ids, n), k_sc = sg.in(scene, n);
+    const int k_dpose = sg.out(d_pose, nk * 24), k_dtwist = sg.out(d_twist, nk * 6), k_dxr = sg.out(d_x_w_r2, nk * 12);
+    HIP_TRY(h, sg.commit());
+    rc = bodies_seeds_launch(h, n_items, n_dir, sg.at<int>(k_ids), sg.at<int>(k_sc), n_scene, n_body, sg.at<double>(k_x), sg.at<double>(k_tw),
+                             sg.at<double>(k_dx), sg.at<double>(k_dtw), sg.at<double>(k_dpose), sg.at<double>(k_dtwist), sg.at<double>(k_dxr), sg.st);
     if (rc != PFC_OK) return rc;
-    if (d_pose) HIP_TRY(h, hipMemcpyAsync(d_pose, dpose, sizeof(double) * nk * 24, hipMemcpyDeviceToHost, st));
-    if (d_twist) HIP_TRY(h, hipMemcpyAsync(d_twist, dtwist, sizeof(double) * nk * 6, hipMemcpyDeviceToHost, st));
-    if (d_x_w_r2) HIP_TRY(h, hipMemcpyAsync(d_x_w_r2, dxr, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
+    HIP_TRY(h, sg.finish());
     return PFC_OK;
 }
 
@@ -3693,6 +3677,21 @@ int pfc_debug_stiffness(pfc_handle h, int item, double *K36, double *Kis36, doub
     return 1;
 }
 
+// Both forms of pfc_scatter_generalized behind their checks: f zeroed unless it accumulates, then k_scatter, enqueued on st.
+static int scatter_launch(pfc_context *h, int n_items, int nv, const double *wrench, const double *x_w_r2, const int *body_1, const int *body_2,
+                          const int *scene, int n_scene, const double *jac, double *f, int accumulate, hipStream_t st) {
+    if (!accumulate) HIP_TRY(h, hipMemsetAsync(f, 0, sizeof(double) * (size_t)n_scene * nv, st));
+    if (n_items > 0) {
+        ScatterArgs a;
+        a.n_items = n_items; a.nv = nv; a.wrench = wrench; a.x_w_r2 = x_w_r2; a.body_1 = body_1; a.body_2 = body_2;
+        a.scene = scene; a.jac = jac; a.f = f;
+        const long long tot = (long long)n_items * nv;
+        hipLaunchKernelGGL(k_scatter, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, a);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return PFC_OK;
+}
+
 int pfc_scatter_generalized(pfc_handle h, int n_items, const double *wrench, const double *x_w_r2, const int *body_1,
                             const int *body_2, const int *scene, int n_scene, int n_body, int nv, const double *jac,
                             double *f_out) {
@@ -3708,30 +3707,15 @@ int pfc_scatter_generalized(pfc_handle h, int n_items, const double *wrench, con
             return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized: body / scene id out of range (item %d)", i);
     }
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (size_t)n_items, nf = (size_t)n_scene * nv, nj = (size_t)n_body * 6 * nv;
-    // work buffers of the handle (grown on demand, reused by later calls): [f | wrench | x_w_r2 | jac] and the ids
-    HIP_TRY(h, h->scat_d.ensure(nf + n * 18 + nj + 1));
-    HIP_TRY(h, h->scat_i.ensure(n * 3 + 1));
-    double *df = h->scat_d.p, *dw = df + nf, *dx = dw + n * 6, *dj = dx + n * 12;
-    int *db = h->scat_i.p;
-    hipStream_t st = h->stream;
-    HIP_TRY(h, hipMemsetAsync(df, 0, sizeof(double) * nf, st));
-    if (n) {
-        HIP_TRY(h, hipMemcpyAsync(dw, wrench, sizeof(double) * n * 6, hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipMemcpyAsync(dx, x_w_r2, sizeof(double) * n * 12, hipMemcpyHostToDevice, st));
-        if (nj) HIP_TRY(h, hipMemcpyAsync(dj, jac, sizeof(double) * nj, hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipMemcpyAsync(db, body_1, sizeof(int) * n, hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipMemcpyAsync(db + n, body_2, sizeof(int) * n, hipMemcpyHostToDevice, st));
-        if (scene) HIP_TRY(h, hipMemcpyAsync(db + 2 * n, scene, sizeof(int) * n, hipMemcpyHostToDevice, st));
-        ScatterArgs a;
-        a.n_items = n_items; a.nv = nv; a.wrench = dw; a.x_w_r2 = dx; a.body_1 = db; a.body_2 = db + n;
-        a.scene = scene ? db + 2 * n : nullptr; a.jac = dj; a.f = df;
-        const long long tot = (long long)n_items * nv;
-        hipLaunchKernelGGL(k_scatter, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, a);
-        HIP_TRY(h, hipGetLastError());
-    }
-    HIP_TRY(h, hipMemcpyAsync(f_out, df, sizeof(double) * nf, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
+    const size_t n = (size_t)n_items, nf = (size_t)n_scene * nv, nj = n ? (size_t)n_body * 6 * nv : 0;
+    Stage sg(h->stage, h->stream);
+    const int k_w = sg.in(wrench, n * 6), k_x = sg.in(x_w_r2, n * 12), k_j = sg.in(jac, nj);
+    const int k_b1 = sg.in(body_1, n), k_b2 = sg.in(body_2, n), k_sc = sg.in(scene, n), k_f = sg.out(f_out, nf);
+    HIP_TRY(h, sg.commit());
+    const int rc = scatter_launch(h, n_items, nv, sg.at<double>(k_w), sg.at<double>(k_x), sg.at<int>(k_b1), sg.at<int>(k_b2), sg.at<int>(k_sc),
+                                  n_scene, sg.at<double>(k_j), sg.at<double>(k_f), 0, sg.st);
+    if (rc != PFC_OK) return rc;
+    HIP_TRY(h, sg.finish());
     return PFC_OK;
 }
 
@@ -3748,16 +3732,7 @@ int pfc_scatter_generalized_device(pfc_handle h, int n_items, const double *d_wr
         return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_device: null buffer");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    if (!accumulate) HIP_TRY(h, hipMemsetAsync(d_f, 0, sizeof(double) * (size_t)n_scene * nv, st));
-    if (n_items > 0) {
-        ScatterArgs a;
-        a.n_items = n_items; a.nv = nv; a.wrench = d_wrench; a.x_w_r2 = d_x_w_r2; a.body_1 = d_body_1; a.body_2 = d_body_2;
-        a.scene = d_scene; a.jac = d_jac; a.f = d_f;
-        const long long tot = (long long)n_items * nv;
-        hipLaunchKernelGGL(k_scatter, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, a);
-        HIP_TRY(h, hipGetLastError());
-    }
-    return PFC_OK;
+    return scatter_launch(h, n_items, nv, d_wrench, d_x_w_r2, d_body_1, d_body_2, d_scene, n_scene, d_jac, d_f, accumulate, st);
 }
 
 // pfc_scatter_generalized_dual[_device] behind the scene CSR (keys / off, or NULL: one segment): the world wrenches and the ordered
@@ -3803,17 +3778,9 @@ int pfc_scatter_generalized_dual(pfc_handle h, int n_items, int n_dir, const dou
             return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual: body / scene id out of range (item %d)", i);
     }
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (size_t)n_items, nd = (size_t)n_dir, nf = (size_t)n_scene * nv, nj = (size_t)n_body * nv * 6;
-    const size_t ndx = d_x_w_r2 ? n * nd * 12 : 0, ndj = d_jac ? nj * nd : 0;
-    // staging (grown on demand, reused): [f | df | wrench | dwrench | x_w_r2 | dx_w_r2 | jac | djac]; [body_1 | body_2 | keys | off]
-    HIP_TRY(h, h->sdual_d.ensure(nf * (1 + nd) + n * 6 * (1 + nd) + n * 12 + ndx + nj + ndj + 1));
-    double *df = h->sdual_d.p, *ddf = df + nf, *dw = ddf + nf * nd, *ddw = dw + n * 6, *dx = ddw + n * nd * 6, *ddx = dx + n * 12;
-    double *dj = ddx + ndx, *ddj = dj + nj;
-    const bool csr = scene && n_items > 0;
-    HIP_TRY(h, h->sdual_i.ensure(n * 3 + (size_t)n_scene + 2));
-    int *db = h->sdual_i.p, *dkeys = db + 2 * n, *doff = dkeys + n;
+    const size_t n = (size_t)n_items, nd = (size_t)n_dir, nf = (size_t)n_scene * nv, nj = n ? (size_t)n_body * nv * 6 : 0;
     std::vector<int> keys, off;
-    if (csr) {      // the items by scene in ascending item order: a counting sort
+    if (scene && n_items > 0) {      // the items by scene in ascending item order: a counting sort
         off.assign((size_t)n_scene + 1, 0);
         for (int i = 0; i < n_items; ++i) ++off[(size_t)scene[i] + 1];
         for (int s = 0; s < n_scene; ++s) off[(size_t)s + 1] += off[(size_t)s];
@@ -3821,28 +3788,17 @@ int pfc_scatter_generalized_dual(pfc_handle h, int n_items, int n_dir, const dou
         keys.resize(n);
         for (int i = 0; i < n_items; ++i) keys[(size_t)fill[(size_t)scene[i]]++] = scene[i] * n_items + i;
     }
-    hipStream_t st = h->stream;
-    if (n_items > 0) {
-        HIP_TRY(h, hipMemcpyAsync(dw, wrench, sizeof(double) * n * 6, hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipMemcpyAsync(ddw, d_wrench, sizeof(double) * n * nd * 6, hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipMemcpyAsync(dx, x_w_r2, sizeof(double) * n * 12, hipMemcpyHostToDevice, st));
-        if (ndx) HIP_TRY(h, hipMemcpyAsync(ddx, d_x_w_r2, sizeof(double) * ndx, hipMemcpyHostToDevice, st));
-        if (nj) HIP_TRY(h, hipMemcpyAsync(dj, jac, sizeof(double) * nj, hipMemcpyHostToDevice, st));
-        if (ndj) HIP_TRY(h, hipMemcpyAsync(ddj, d_jac, sizeof(double) * ndj, hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipMemcpyAsync(db, body_1, sizeof(int) * n, hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipMemcpyAsync(db + n, body_2, sizeof(int) * n, hipMemcpyHostToDevice, st));
-        if (csr) {
-            HIP_TRY(h, hipMemcpyAsync(dkeys, keys.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
-            HIP_TRY(h, hipMemcpyAsync(doff, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice, st));
-        }
-    }
-    const int rc = scatter_dual_launch(h, n_items, n_dir, dw, ddw, dx, ndx ? ddx : nullptr, db, db + n, csr ? dkeys : nullptr,
-                                       csr ? doff : nullptr, n_scene, nv, nj ? dj : nullptr, ndj ? ddj : nullptr, f_out ? df : nullptr,
-                                       ddf, 0, st);
+    Stage sg(h->stage, h->stream);
+    const int k_w = sg.in(wrench, n * 6), k_dw = sg.in(d_wrench, n * nd * 6), k_x = sg.in(x_w_r2, n * 12), k_dx = sg.in(d_x_w_r2, n * nd * 12);
+    const int k_j = sg.in(jac, nj), k_dj = sg.in(d_jac, nj * nd), k_b1 = sg.in(body_1, n), k_b2 = sg.in(body_2, n);
+    const int k_keys = sg.in(keys.empty() ? nullptr : keys.data(), keys.size()), k_off = sg.in(off.empty() ? nullptr : off.data(), off.size());
+    const int k_f = sg.out(f_out, nf), k_df = sg.out(d_f_out, nf * nd);
+    HIP_TRY(h, sg.commit());
+    const int rc = scatter_dual_launch(h, n_items, n_dir, sg.at<double>(k_w), sg.at<double>(k_dw), sg.at<double>(k_x), sg.at<double>(k_dx),
+                                       sg.at<int>(k_b1), sg.at<int>(k_b2), sg.at<int>(k_keys), sg.at<int>(k_off), n_scene, nv, sg.at<double>(k_j),
+                                       sg.at<double>(k_dj), sg.at<double>(k_f), sg.at<double>(k_df), 0, sg.st);
     if (rc != PFC_OK) return rc;
-    if (f_out) HIP_TRY(h, hipMemcpyAsync(f_out, df, sizeof(double) * nf, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(d_f_out, ddf, sizeof(double) * nf * nd, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
+    HIP_TRY(h, sg.finish());
     return PFC_OK;
 }
 

@@ -199,3 +199,145 @@ def friction_regimes(pfc, w, k, ref):
     x = np.linalg.norm(v, axis=1) / thr
     counts = np.bincount(np.searchsorted(np.array(REGIME_EDGES), x, side="right"), minlength=4)
     return counts, float(np.abs(x[:, None] - np.array(REGIME_EDGES)[None, :]).min())
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# The host-pointer forms that stage through the context's block (csrc/pfc_hip.hip, Stage): a small scene and raw calls
+# with any optional pointer null.
+# ----------------------------------------------------------------------------------------------------------------
+import ctypes as C
+
+
+def random_body_states(pfc, rng, n_scene, n_body):
+    """World states of n_scene x n_body bodies: x (R column-major, then t) and twist."""
+    x = np.zeros((n_scene, n_body, 12)); tw = rng.standard_normal((n_scene, n_body, 6))
+    for s in range(n_scene):
+        for b in range(n_body):
+            x[s, b, :9] = pfc.configs.random_rotation(rng).reshape(-1, order="F")
+            x[s, b, 9:] = rng.uniform(-1, 1, 3) * rng.uniform(0, 10)
+    return x, tw
+
+
+HOST_FORMS_ORDER = ("surface_fric", "items", "local_jacobian", "scatter", "seeds", "apply", "scatter_dual", "surface")   # staging need large -> small -> large
+N_SCENE, N_BODY, NV = 2, 3, 5
+BIND = [(-1, 0), (1, 2), (0, 2), (2, -1)]
+LJAC = ("local_jacobian", "local_jacobian3", "local_jacobian_c1")
+_CT = {np.dtype(np.float64): C.c_double, np.dtype(np.int32): C.c_int, np.dtype(np.int64): C.c_longlong}
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(_CT[a.dtype]))
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+class HostFormsCase:
+    """The inputs of every host-pointer form that stages through the context's block, made once, and one call of a form through the C
+    ABI (tests/test_gpu_host_staging.py, scripts/host_forms_rate.py)."""
+
+    def __init__(self, pfc):
+        rng = np.random.default_rng(3)
+        self.w = w = fuzz_workload(pfc, rng, 5, False)
+        w.ins_ids[:3] = np.arange(3)       # a null ins_ids of three items names these
+        self.c1 = pfc.configs.c1_boxes()   # regularized instructions only: s may be null
+        self.x, self.tw = random_body_states(pfc, rng, N_SCENE, N_BODY)
+        self.scene = _i32([0, 1, 1, 0, 1])
+        self.dx, self.dtw = rng.standard_normal((N_SCENE, N_BODY, 3, 12)), rng.standard_normal((N_SCENE, N_BODY, 3, 6))
+        self.L = rng.standard_normal((3, 12, 36))
+        self.seed = [rng.standard_normal((3, 1, 24)), rng.standard_normal((3, 1, 6)), rng.standard_normal((3, 1, 6))]
+        xr = np.zeros((5, 12))
+        for k in range(5):
+            xr[k, :9] = pfc.configs.random_rotation(rng).reshape(-1, order="F"); xr[k, 9:] = rng.standard_normal(3)
+        self.sc = dict(wrench=rng.standard_normal((5, 6)), d_wrench=rng.standard_normal((5, 3, 6)), x_w_r2=xr,
+                       d_x_w_r2=rng.standard_normal((5, 3, 12)), body_1=_i32([-1, 0, 2, 1, 0]), body_2=_i32([1, 2, -1, 0, 2]),
+                       jac=rng.standard_normal((N_BODY, NV, 6)), d_jac=rng.standard_normal((N_BODY, 3, NV, 6)))
+
+    def handle(self, pfc, devices=None, c1=False, **options):
+        m = pfc.configs.build_scenario(self.c1 if c1 else self.w, devices=devices)
+        for k, v in options.items():
+            m.set_option(k, v)
+        for k, (b1, b2) in enumerate(BIND):
+            m.set_instruction_bodies(k, b1, b2)
+        return m
+
+    # Every form: (inputs that may be null or replaced, outputs); drop names the arguments passed as NULL.
+    def args(self, form):
+        w, s, z = self.w, self.sc, np.zeros
+        if form == "items":
+            return dict(ins_ids=_i32(w.ins_ids[:3]), scene=self.scene[:3].copy()), dict(
+                pose=z((3, 24)), twist=z((3, 6)), x_w_r2=z((3, 12)), body_1=z(3, np.int32), body_2=z(3, np.int32))
+        if form == "seeds":
+            return dict(d_x_w_b=self.dx, d_twist_w_b=self.dtw), dict(d_pose=z((5, 3, 24)), d_twist=z((5, 3, 6)), d_x_w_r2=z((5, 3, 12)))
+        if form in LJAC:      # five items; three, instructions 0 .. 2; three of C1's, on a handle of C1
+            n = 5 if form == "local_jacobian" else 3
+            w = self.c1 if form == "local_jacobian_c1" else w
+            return dict(ins_ids=_i32(w.ins_ids[:n]), s=np.ascontiguousarray(w.s[:n])), dict(
+                wrench=z((n, 6)), sdot=z((n, 6)), L=z((n, 12, 36)), counts=z((n, 4), np.int32))
+        if form == "apply":
+            return dict(d_s=self.seed[2]), dict(d_wrench=z((3, 1, 6)), d_sdot=z((3, 1, 6)))
+        if form == "scatter":
+            return dict(scene=self.scene), dict(f=z((N_SCENE, NV)))
+        if form == "scatter_dual":
+            return dict(d_x_w_r2=s["d_x_w_r2"], d_jac=s["d_jac"], scene=self.scene), dict(f=z((N_SCENE, NV)), d_f=z((N_SCENE, 3, NV)))
+        raise KeyError(form)
+
+    def run(self, pfc, m, form, drop=(), **over):
+        """One call of a form through the C ABI; returns {output name: array} of the outputs asked for."""
+        if form in ("surface", "surface_fric"):
+            return self.surface(pfc, m, form == "surface_fric", drop)
+        L, w, s = pfc._lib.lib(), self.w, self.sc
+        a, o = self.args(form)
+        a.update(over)
+        for k in drop:
+            (a if k in a else o)[k] = None
+        h, out = m._h, [_ptr(v) for v in o.values()]
+        if form == "items":
+            rc = L.pfc_items_from_bodies(h, 3, _ptr(a["ins_ids"]), _ptr(a["scene"]), N_SCENE, N_BODY, _ptr(self.x), _ptr(self.tw), *out)
+        elif form == "seeds":
+            rc = L.pfc_dual_seeds_from_bodies(h, 5, 3, _ptr(_i32(w.ins_ids)), _ptr(self.scene), N_SCENE, N_BODY, _ptr(self.x), _ptr(self.tw),
+                                              _ptr(a["d_x_w_b"]), _ptr(a["d_twist_w_b"]), *out)
+        elif form in LJAC:
+            n, w = o["wrench"].shape[0], self.c1 if form == "local_jacobian_c1" else w
+            rc = L.pfc_local_jacobian(h, n, _ptr(a["ins_ids"]), _ptr(np.ascontiguousarray(w.pose[:n])), _ptr(np.ascontiguousarray(w.twist[:n])),
+                                      _ptr(a["s"]), *out)
+        elif form == "apply":
+            rc = L.pfc_apply_local_jacobian(h, 3, 1, _ptr(self.L), _ptr(self.seed[0]), _ptr(self.seed[1]), _ptr(a["d_s"]), *out)
+        elif form == "scatter":
+            rc = L.pfc_scatter_generalized(h, 5, _ptr(s["wrench"]), _ptr(s["x_w_r2"]), _ptr(s["body_1"]), _ptr(s["body_2"]), _ptr(a["scene"]),
+                                           N_SCENE, N_BODY, NV, _ptr(s["jac"]), *out)
+        else:
+            rc = L.pfc_scatter_generalized_dual(h, 5, 3, _ptr(s["wrench"]), _ptr(s["d_wrench"]), _ptr(s["x_w_r2"]), _ptr(a["d_x_w_r2"]),
+                                                _ptr(s["body_1"]), _ptr(s["body_2"]), _ptr(a["scene"]), N_SCENE, N_BODY, NV, _ptr(s["jac"]),
+                                                _ptr(a["d_jac"]), *out)
+        m._check(rc)
+        return {k: v for k, v in o.items() if v is not None}
+
+    def surface(self, pfc, m, fric, drop=(), caps=(64, 512)):
+        """pfc_contact_surface[_fric] with the caller's half of the capacity protocol (grow to the totals, call again); the lists cut
+        to the totals."""
+        L, w, z = pfc._lib.lib(), self.w, np.zeros
+        n = w.n_items
+        ids, pose, twist, s = _i32(w.ins_ids), np.ascontiguousarray(w.pose), np.ascontiguousarray(w.twist), np.ascontiguousarray(w.s)
+        cp, ct = caps
+        for attempt in range(2):
+            o = dict(poly_off=z(n + 1, np.int64), poly_idx=z((cp, 3), np.int32), poly_xyz=z((cp, 8, 3)), poly_trac=z(cp + 1, np.int64),
+                     trac=z((ct, 8)), fric=z((ct, 4)), summary=z((n, 11)), fric_summary=z((n, 20)), stiff=z((n, 84)),
+                     counts=z((n, 4), np.int32), totals=z(2, np.int64))
+            if not fric:
+                for k in ("fric", "fric_summary", "stiff"):
+                    del o[k]
+            for k in drop:
+                o[k] = None
+            rc = (L.pfc_contact_surface_fric(m._h, n, _ptr(ids), _ptr(pose), _ptr(twist), _ptr(s), cp, ct, *[_ptr(v) for v in o.values()]) if fric
+                  else L.pfc_contact_surface(m._h, n, _ptr(ids), _ptr(pose), _ptr(twist), cp, ct, *[_ptr(v) for v in o.values()]))
+            if rc == pfc._lib.ERR_OVERFLOW and attempt == 0:
+                cp, ct = max(cp, int(o["totals"][0])), max(ct, int(o["totals"][1]))
+                continue
+            m._check(rc)
+            break
+        P, T = int(o["totals"][0]), int(o["totals"][1])
+        assert P > 0 and T > 0      # the scene has contact
+        cut = dict(poly_idx=P, poly_xyz=P, poly_trac=P + 1, trac=T, fric=T)
+        return {k: (v[:cut[k]] if k in cut else v) for k, v in o.items() if v is not None}
