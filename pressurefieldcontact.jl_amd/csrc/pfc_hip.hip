@@ -29,6 +29,7 @@
 #include "pfc_kernels.h"
 
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <functional>
 #include <mutex>
@@ -376,9 +377,6 @@ struct pfc_context {
     int device = 0;
     bool finalized = false;
     pfc_multi *multi = nullptr;          // non-null: a multi-device handle (pfc_create_multi); everything below belongs to its shards
-    // Broadphase pose of the evaluation being enqueued (device-visible, n_items x 24, only x_r1_r2 is read) or null: set by the
-    // pfc_eval_dual*_bp entry points around the value pass (record_eval, enqueue_fused)
-    const double *bp_dev = nullptr;
     // The streams come first: members are destroyed in reverse order, so everything made against a stream (events, graph
     // executables, buffers its work may touch) goes before it.
     Stream stream;
@@ -418,8 +416,6 @@ struct pfc_context {
     DevBuf<unsigned long long> stamps;   // diagnostic builds
     DevBuf<int> tail;                    // packed status, totals, counters (block 0 of k_final)
     PinBuf<int> h_tail;                  // pinned host mirror of tail
-    const int *tail_host = nullptr;      // set by pfc_eval: the tail is already on its way to this pinned block (with the outputs)
-    int *tail_dev = nullptr;             // set by pfc_eval for a small scene: k_final packs straight into pinned host memory
     PinBuf<char, 2> pin_in, pin_out;     // pinned staging of the host-buffer path
     // Inputs of a very small scene written by the host straight into DEVICE memory (fine-grained allocation, reachable through
     // the PCIe BAR when the device has a large one): the one-launch kernel's first two dependent reads -- instruction id, then
@@ -477,7 +473,6 @@ struct pfc_context {
     GraphExec dgexec;
     struct DualGraphKey { GraphKey v; int n_dir; size_t bound; const void *din, *dout; } dgkey = {};
     bool dghave = false;
-    bool want_surv = false;   // the narrowphase also lists the contributing candidates (pfc_eval_dual)
     int opt_graph = 1;
     size_t fcap = 0, ccap = 0, tcap = 0, rcap = 0;
     // host-pointer path staging
@@ -526,8 +521,6 @@ struct pfc_context {
     // small scenes: one fused kernel, one workgroup per item (pfc_fused.h)
     DevBuf<int> fout;                  // per item 8 ints (status, counts) of the fused kernel (device-buffer entry point)
     PinBuf<int> h_fout;                // pinned host mirror
-    int *fout_dev = nullptr;           // set by pfc_eval: the kernel writes its per-item block straight into pinned host memory
-    const int *fout_host = nullptr;    //   ... and this is where the host reads it
     int opt_fused = 1;                 // option "fused"
     // option "fixed_order": the candidate list sorted (pfc_sort.hip), an item's run records added in chunk order (k_integ_fixed,
     // k_shift_fixed), the Dual passes' eigen-decomposition on the value pass's K -- batched path only, no graph, no split
@@ -554,7 +547,6 @@ struct pfc_context {
     int opt_clip_queue = 1;            // option "clip_queue": clip-only narrowphase of big tri-tet batches in k_clip_queue (survivors queued in the ring); 0: k_narrow<.., 2 / 3>
     int fused_skip = 0;                // evaluations left for which the fused kernel stays off after an item did not fit
     int fused_seq = 0;                 // sequence number of the last fused launch (completion word of the polled path)
-    int fu_nw = 1;                     // workgroups per item of the next fused launch (teams: k_fused<.., true>)
     int last_fu_nw = 0, last_team = 0; // of the last fused launch / of the last checked evaluation (pfc_last_team)
     int n_cu = 0;                      // compute units of the device (a team launch keeps every workgroup resident: one per CU)
     int opt_team = 48;                 // option "team": big pairs (more leaves than one workgroup takes) run as teams of up to this many workgroups (0: batched path; <= kTeamMaxWg = 48: s_team and the gather's per-thread granule count are sized from it).  Eight single C3 poses, mean / worst us (an earlier build that allowed 64): 64: 113 / 122, 48: 112 / 118, 32: 113 / 122, 24: 126 / 190, 16: 178 / 249, batched 132 / 136 (scripts/lat_c3_poses.py)
@@ -562,17 +554,12 @@ struct pfc_context {
     DevBuf<int> emit_ctr;              // pair counter of the fused kernel's hand-over to the batched Dual passes
     PinBuf<int> h_emit;                // pinned mirror
     PinBuf<unsigned> h_more;           // pinned: status word of the Dual passes of pfc_eval_dual_device_more (device word: status.p + 1)
-    bool fu_emit = false;              // set by eval_dual_hybrid around enqueue_fused
     int dual_fused_skip = 0;           // Dual evaluations left for which the in-kernel Dual passes stay off (an item had too many polygons)
-    const double *fu_dpose = nullptr, *fu_dtwist = nullptr;    // set by eval_dual_fused around enqueue_fused
-    double *fu_dwrench = nullptr, *fu_dsdot = nullptr;
-    int fu_ndir = 0;
     bool pending_fused = false, last_fused = false;
     int opt_split_min = 1025;          // 0: never split.  (Paired sweeps at the end of round 2: 1 024 poses -- one seed per resident broadphase workgroup -- 0.80 ms unsplit / 0.90 split; 1 100 0.95 / 0.93, 1 280 1.09 / 1.01, 2 048 1.50 / 1.28.)
     int opt_clip_min = 384;            // items per launch from which the narrowphase runs as clip-only kernel + k_integ; 0: never.  (End of round 3, k_clip_queue for every such launch, scripts/sweep_clip_min.py: full-size C3 poses 256: 405 vs 405 us one-kernel / split, 400: 518 vs 502, 511: 598 vs 568; 400 box-on-plane scenes 120 vs 123 -- 384, was 512.)  (First set at 1 024 from scripts/sweep_clip.sh; a paired sweep with the final kernels: 512 poses 0.61 vs 0.63 ms, 768 0.80 vs 0.83, 1 536 as 2 x 768 1.14 vs 1.19, 1 920 1.33 vs 1.40; 384 poses and below are indifferent.)
     int opt_poison = 0;                // diagnostic: fill (re)allocated work lists with 0xFF bytes (item index -1)
     int split_n0 = 0;                  // items in the first half of the pending evaluation (0: not split)
-    bool in_split = false;             // this context's launches are one half of a two-half evaluation (set while they are enqueued)
     int last_parts = 1;                // 2 if the last checked evaluation ran as two halves
     Event ev_fork, ev_join, ev_join0;
     int twin_queue_fallback = 0;         // make_twin: 0 the two streams run side by side as created; 1 the twin's stream was re-created with another priority because they did not; 2 they still do not
@@ -653,6 +640,37 @@ void new_value_pass(pfc_context *h) {
     ++h->value_serial;
 }
 
+// What one value pass is told beyond its buffers: filled by the entry point that starts the pass and handed down by const
+// reference (fused_ok, fused_team, enqueue_eval, record_eval, enqueue_fused); nothing of it outlives the call.
+struct PassOpts {
+    const double *bp_pose = nullptr;   // broadphase pose (device-visible, n_items x 24, only x_r1_r2 is read), null: the evaluation's own
+    bool list = false;                 // the narrowphase also lists the contributing candidates (the Dual passes walk them)
+    int *tail = nullptr;               // device-visible block k_final packs the tail into (a small scene: pinned host memory), null: h->tail
+    int *fout = nullptr;               // fused kernel: device-visible per-item block (8 ints per item, pinned host memory), null: h->fout
+    const int *fout_host = nullptr;    // ... the host's view of it: completion words cleared before the launch, polled by check_fused
+    bool emit = false;                 // ... hands item records, counters and the contributing candidates to the batched Dual passes
+    int n_dir = 0;                     // ... runs the Dual passes itself: directions (0: none), seeds and partials (device-visible)
+    const double *d_pose = nullptr, *d_twist = nullptr; double *d_wrench = nullptr, *d_sdot = nullptr;
+    int nw = 1;                        // ... workgroups per item (teams: k_fused<.., true>)
+    bool half = false;                 // the launches are one half of a two-half evaluation
+};
+
+// ---- sizes and tail layout of the Dual passes (launch_dual), each stated once ----------------------------------------
+// Kept Dual polygons for up to `pairs` contributing pairs: a wave of k_narrow_dual takes 64 / n_dir pairs and owns 64 slots
+// (option fixed_order: the same bound sizes the record list of the passes' sums, for every model) ...
+size_t dual_poly_cap(const pfc_context *h, int n_dir, size_t pairs) { return (h->any_bristle || h->opt_fixed_order) ? ((pairs + 64 / n_dir - 1) / (64 / n_dir)) * 64 + 64 : 64; }
+// ... and whether the pairs a value pass turned out to have fit the capacity its Dual passes were enqueued with.
+bool dual_pairs_fit(const pfc_context *h, int n_dir, long long pairs, size_t dpcap) { return dual_poly_cap(h, n_dir, (size_t)pairs) <= dpcap; }
+// Pair bound of passes enqueued before the count is known: floor x 2^k above twice the previous Dual evaluation's count (hint,
+// -1: none yet), so that buffers and captured graphs settle.
+size_t dual_spec_bound(long long hint, size_t floor) { while (floor < (size_t)(hint > 0 ? hint : 0) * 2 + 64) floor *= 2; return floor; }
+// ctr[] index of the kept-polygon total (behind the per-level frontier counts; 8-byte aligned pair: the contributing-pair
+// counter follows it), that counter's index in the packed tail (12 ints of status and totals, then the counters), and the
+// ints in front of the outputs where one block carries the tail and the results (16-byte multiple).
+constexpr int ctr_pcount(int levels) { return (levels + 9) & ~1; }
+constexpr int tail_pairs(int levels) { return 12 + ctr_pcount(levels) + 1; }
+size_t tail_prefix(const pfc_context *h) { return (((size_t)h->max_levels + 40) + 3) & ~(size_t)3; }
+
 // Kept-polygon slots: chunk ch of the candidate list owns slots [ch C, ch C + C) (pfc_np.h, np_chunk): the candidate
 // capacity rounded up to a whole chunk.
 constexpr int kNpMaxBlocks = 256 * 16;
@@ -696,7 +714,7 @@ hipError_t ensure_zeroed(pfc_context *h, DevBuf<T> &b, size_t n) {
     return hipStreamSynchronize(h->stream);
 }
 
-hipError_t ensure_work(pfc_context *h, int n_items) {
+hipError_t ensure_work(pfc_context *h, int n_items, bool list) {
     hipError_t e;
     if ((e = ensure_graphed(h, h->items, n_items)) != hipSuccess) return e;
     if ((e = ensure_graphed(h, h->acc, (size_t)n_items * kAccStride)) != hipSuccess) return e;
@@ -743,7 +761,7 @@ hipError_t ensure_work(pfc_context *h, int n_items) {
         if ((e = ensure_graphed(h, h->poly_item, pc)) != hipSuccess) return e;
         if ((e = ensure_graphed(h, h->poly, pc * 34)) != hipSuccess) return e;
         if ((e = ensure_graphed(h, h->pcnt, pc / kNpBlock + 1)) != hipSuccess) return e;
-        if (h->want_surv && (e = ensure_graphed(h, h->poly_cand, pc)) != hipSuccess) return e;
+        if (list && (e = ensure_graphed(h, h->poly_cand, pc)) != hipSuccess) return e;
     }
     if ((e = ensure_graphed(h, h->trac_item, t)) != hipSuccess) return e;
     if ((e = ensure_graphed(h, h->trac_d, t * 8)) != hipSuccess) return e;
@@ -779,7 +797,7 @@ int eff_levels(const pfc_context *h) {
 constexpr int kDualSelectMin = 512;       // items from which a Dual evaluation first selects the pairs its seeds touch
 constexpr int kBpSmallBlockMin = 3072;   // items per launch from which k_bp_dfs32 runs in 128-thread workgroups (paired A/B: 2 048 per launch 2.31 vs 2.36 ms for 256 / 128 threads, 3 072 per launch 3.39 vs 3.30)
 
-int bfs_levels_for(const pfc_context *h, int n_items, int levels) {
+int bfs_levels_for(const pfc_context *h, int n_items, int levels, bool half) {
     int L = 0;
     if (h->opt_bfs_levels >= 0) {
         L = h->opt_bfs_levels;
@@ -801,7 +819,7 @@ int bfs_levels_for(const pfc_context *h, int n_items, int levels) {
         // 512-thread workgroups instead, pile_mode.)
         // (a half of a two-half evaluation shares the chip with its twin's seeds: 1 100 poses as 2 x 550, 891 vs 930 us
         // without / with the level its own 550 items would ask for)
-        const int n_eff = h->in_split ? 2 * n_items : n_items;
+        const int n_eff = half ? 2 * n_items : n_items;
         const double target = big ? (n_eff >= 600 ? 1.0 : (n_eff >= 256 ? 1024.0 : (n_eff >= 128 ? 2048.0 : (n_eff >= 32 ? 16384.0 : 49152.0))))
                                   : (mid ? 256.0 : 64.0);
         double seeds = (double)n_items;
@@ -822,9 +840,9 @@ bool pile_mode(const pfc_context *h, int n_items) {
 // over big trees (16 full-size C3 poses 198 -> 183 us, 128: 386 -> 314, 256: 459 -> 399, 600: 681 -> 662; from 1 024 items
 // on 256 threads win again) and sparse piles: an iteration costs ~1.7 us whatever its width, 512 pairs per iteration halve
 // the chain.  (1 024 threads: no further gain, C5 105 vs 97 us of broadphase.)  256 otherwise.
-int bp_block_for(const pfc_context *h, int n_items) {
+int bp_block_for(const pfc_context *h, int n_items, bool half) {
     if (n_items >= kBpSmallBlockMin) return 128;
-    if (h->in_split) return 256;
+    if (half) return 256;
     if (h->max_leaves >= 8192 && n_items >= 8 && n_items < 1024) return 512;
     if (pile_mode(h, n_items)) return 512;
     return 256;
@@ -832,7 +850,7 @@ int bp_block_for(const pfc_context *h, int n_items) {
 
 // The batched broadphase of an evaluation on stream st, behind k_setup_items: L level-synchronous seed expansions, then the
 // depth-first kernel (record_eval; pfc_contact_surface).
-void launch_broadphase(pfc_context *h, int n_items, int L, int *ccount, int *fcount, int *next_seed, int *ucount, hipStream_t st) {
+void launch_broadphase(pfc_context *h, int n_items, int L, bool half, int *ccount, int *fcount, int *next_seed, int *ucount, hipStream_t st) {
     for (int lv = 0; lv < L; ++lv) {
         BpArgs b;
         b.items = h->items.p; b.fin = h->frontier[lv & 1].p; b.fout = h->frontier[(lv + 1) & 1].p;
@@ -864,7 +882,7 @@ void launch_broadphase(pfc_context *h, int n_items, int L, int *ccount, int *fco
             // kernel alone runs as fast either way (2.08 ms), but next to the other half's narrowphase the finer grain
             // shares the CUs better (8 192-pose step 4.53 -> 4.39 ms; 4 096: 2.33 vs 2.38, 2 048: 1.30 vs 1.45 -- a smaller
             // launch needs the 256 pairs per iteration; profiles/r02_sweep_bp_block.txt).  Grid = resident workgroups.
-            const int blk = bp_block_for(h, n_items);
+            const int blk = bp_block_for(h, n_items, half);
             if (blk == 128 && f.reserve <= 128 * 10 - 512)
                 hipLaunchKernelGGL((k_bp_dfs32<128>), dim3(grid_for(bound, 1, 256 * 8)), dim3(128), 0, st, f);
             else if (blk == 512)
@@ -877,13 +895,13 @@ void launch_broadphase(pfc_context *h, int n_items, int L, int *ccount, int *fco
 
 // The launch sequence of one evaluation on stream st (eagerly, or while st is being captured into a graph).
 int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
-                const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, hipStream_t st, bool prof) {
+                const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, hipStream_t st, bool prof, const PassOpts &o) {
     new_value_pass(h);
     h->pending_more = false; h->last_dual_reused = false;
     const int levels = eff_levels(h);
     int *ccount = h->ctr.p, *tcount = h->ctr.p + 1, *next_seed = h->ctr.p + 2;   // ctr[3]: total records, filled by k_final
     int *ucount = h->ctr.p + 4, *fcount = h->ctr.p + 6;
-    int *pcount = h->ctr.p + ((levels + 9) & ~1);   // after the per-level frontier counts; 8-byte aligned pair
+    int *pcount = h->ctr.p + ctr_pcount(levels);
     // counters and status are zero here: k_final of the previous evaluation (or ensure_work after an allocation) left them so
 #ifdef PFC_STAMPS
     HIP_TRY(h, hipMemsetAsync(h->stamps.p, 0, sizeof(unsigned long long) * 16, st));
@@ -892,7 +910,7 @@ int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double 
 
     EvalArgs ea;
     ea.n_items = n_items; ea.ins_ids = d_ins_ids; ea.pose = d_pose; ea.twist = d_twist; ea.s = d_s;
-    ea.bp_pose = h->bp_dev;
+    ea.bp_pose = o.bp_pose;
     ea.ins = h->d_ins; ea.meshes = h->d_meshes; ea.n_ins = (int)h->ins.size(); ea.items = h->items.p;
     ea.frontier0 = h->frontier[0].p; ea.fcount = fcount; ea.acc = h->acc.p; ea.icnt = h->icnt.p;
     ea.status = h->status.p;
@@ -901,9 +919,9 @@ int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double 
 
     // broadphase: a few level-synchronous expansions to get enough independent seed pairs, then the per-wave
     // depth-first kernel for everything below
-    const int L = bfs_levels_for(h, n_items, levels);
-    launch_broadphase(h, n_items, L, ccount, fcount, next_seed, ucount, st);
-    if (h->bp_dev)      // the broadphase ran on a pose of its own: the item records get the evaluation's x_r1_r2 back
+    const int L = bfs_levels_for(h, n_items, levels, o.half);
+    launch_broadphase(h, n_items, L, o.half, ccount, fcount, next_seed, ucount, st);
+    if (o.bp_pose)      // the broadphase ran on a pose of its own: the item records get the evaluation's x_r1_r2 back
         hipLaunchKernelGGL(k_repose, dim3(grid_for(n_items, 64, 1 << 20)), dim3(64), 0, st, n_items, d_pose, h->items.p);
     if (h->opt_fixed_order) {
         int ba, bb;
@@ -933,8 +951,8 @@ int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double 
     np.stamps = h->stamps.p;
     np.rec = h->rec.p; np.rgn = h->rgn.p; np.rr_cap = (int)(h->rcap / kRgn);
     np.poly_item = h->poly_item.p; np.poly = h->poly.p; np.pcap = (int)poly_cap(h->ccap);
-    np.pcnt = h->pcnt.p; np.chunk_switch = kNpChunkSwitch; np.poly_cand = h->want_surv ? h->poly_cand.p : nullptr;
-    np.surv = h->want_surv ? h->surv.p : nullptr; np.scount = pcount + 1;
+    np.pcnt = h->pcnt.p; np.chunk_switch = kNpChunkSwitch; np.poly_cand = o.list ? h->poly_cand.p : nullptr;
+    np.surv = o.list ? h->surv.p : nullptr; np.scount = pcount + 1;
     const int np_grid = grid_for(h->ccap, kNpBlock, kNpMaxBlocks);
     // (fixed_order: always the clip-only kernel + k_integ_fixed, whose run records carry every sum)
     const int np_mode = h->opt_debug ? 1 : ((h->opt_fixed_order || (h->opt_clip_min > 0 && n_items >= h->opt_clip_min)) ? 2 : 0);
@@ -955,7 +973,7 @@ int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double 
             // 4.17 -> 4.13 ms as two halves, 4.87 -> 4.70 ms unsplit, 2 048 poses 1.288 -> 1.278; 768 poses lose, 0.712 -> 0.721:
             // paired A/B, profiles/r03_ab_clip_queue.txt; option value 2 forces it for every clip-only launch: tests)
             hipLaunchKernelGGL(k_clip_queue, dim3(np_grid), dim3(kNpBlock), 0, st, np);
-        } else if (h->in_split || (n_items >= 640 && n_items < 1024)) {
+        } else if (o.half || (n_items >= 640 && n_items < 1024)) {
             if (h->any_tet_tet) hipLaunchKernelGGL((k_narrow<true, 3>), dim3(np_grid), dim3(kNpBlock), 0, st, np);
             else hipLaunchKernelGGL((k_narrow<false, 3>), dim3(np_grid), dim3(kNpBlock), 0, st, np);
         } else {
@@ -977,8 +995,8 @@ int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double 
     br.items = h->items.p; br.n_items = n_items; br.acc = h->acc.p; br.res = h->res.p; br.icnt = h->icnt.p;
     br.trac = trac_view(h); br.tcount = tcount; br.tcap = (int)h->tcap; br.wrench = d_wrench; br.sdot = d_sdot;
     br.counts = d_counts;
-    br.ctr = h->ctr.p; br.n_ctr = levels + 12; br.status = h->status.p; br.tail = h->tail_dev ? h->tail_dev : h->tail.p;
-    br.rgn = h->rgn.p; br.i_pcount = (levels + 9) & ~1;
+    br.ctr = h->ctr.p; br.n_ctr = levels + 12; br.status = h->status.p; br.tail = o.tail ? o.tail : h->tail.p;
+    br.rgn = h->rgn.p; br.i_pcount = ctr_pcount(levels);
     if (h->opt_fixed_order && np_mode == 2) {
         FixedArgs fx;
         fx.rec = h->rec.p; fx.det = h->det.p; fx.n_items = n_items; fx.n_slots = (int)(h->rcap / kRgn) * kRgn; fx.items = h->items.p;
@@ -1026,22 +1044,22 @@ int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double 
 // own scene sizes (a handful of instructions per calcXd!) launch overhead, not kernel time, is what an evaluation
 // costs.  Profiling (HIP events between stages) uses the eager path.
 int enqueue_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
-                 const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, hipStream_t st) {
+                 const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, hipStream_t st, const PassOpts &o) {
     new_value_pass(h);
     h->pending_more = false; h->last_dual_reused = false;
-    HIP_TRY(h, ensure_work(h, n_items));
+    HIP_TRY(h, ensure_work(h, n_items, o.list));
     const int levels = eff_levels(h);
     const bool prof = h->opt_profile != 0;
     if (prof && !h->ev[0])
         for (int k = 0; k < EV_COUNT; ++k) HIP_TRY(h, hipEventCreate(h->ev[k].put()));
-    const int L = bfs_levels_for(h, n_items, levels);
+    const int L = bfs_levels_for(h, n_items, levels, o.half);
     bool use_graph = h->opt_graph && !prof;
 #ifdef PFC_STAMPS
     use_graph = false;
 #endif
     if (use_graph) {
         pfc_context::GraphKey key = {};
-        key.n_items = n_items; key.levels = levels; key.L = L; key.debug = (h->opt_debug ? 1 : 0) | (h->in_split ? 2 : 0) | (bp_block_for(h, n_items) << 4);
+        key.n_items = n_items; key.levels = levels; key.L = L; key.debug = (h->opt_debug ? 1 : 0) | (o.half ? 2 : 0) | (bp_block_for(h, n_items, o.half) << 4);
         if (h->opt_fixed_order) {      // (the sort's launches depend on the slots it covers: 2^k, k in the key)
             size_t cover = h->sort_cover ? h->sort_cover : h->ccap;
             int lg = 0;
@@ -1049,16 +1067,16 @@ int enqueue_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double
             key.debug |= ((lg + 1) << 16) | (h->fixed_whole_list ? 1 << 24 : 0);
         }
         key.bristle = (h->any_bristle ? 1 : 0) | (h->any_tet_tet ? 2 : 0);
-        key.surv = h->want_surv ? 1 : 0;
+        key.surv = o.list ? 1 : 0;
         key.p[0] = d_ins_ids; key.p[1] = d_pose; key.p[2] = d_twist; key.p[3] = d_s; key.p[4] = d_wrench;
-        key.p[5] = d_sdot; key.p[6] = d_counts; key.p[7] = h->tail_dev; key.p[8] = h->bp_dev; key.stream = (void *)st; key.epoch = h->epoch;
+        key.p[5] = d_sdot; key.p[6] = d_counts; key.p[7] = o.tail; key.p[8] = o.bp_pose; key.stream = (void *)st; key.epoch = h->epoch;
         const int gi = key.surv;   // Radau alternates value and Dual evaluations: both graphs stay instantiated
         if (!h->ghave[gi] || std::memcmp(&key, &h->gkey[gi], sizeof key) != 0) {
             h->gexec[gi].reset();
             h->ghave[gi] = false;
             hipGraph_t graph = nullptr;
             HIP_TRY(h, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            int rc = record_eval(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, st, false);
+            int rc = record_eval(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, st, false, o);
             hipError_t e = hipStreamEndCapture(st, &graph);
             if (rc != PFC_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
             if (e != hipSuccess) return fail(h, PFC_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
@@ -1069,7 +1087,7 @@ int enqueue_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double
         }
         HIP_TRY(h, hipGraphLaunch(h->gexec[gi], st));
     } else {
-        int rc = record_eval(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, st, prof);
+        int rc = record_eval(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, st, prof, o);
         if (rc != PFC_OK) return rc;
     }
     h->last_bfs_levels = L;
@@ -1079,15 +1097,13 @@ int enqueue_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double
 }
 
 // Synchronise, read counters, grow on overflow.
-int check_one(pfc_context *h) {
+int check_one(pfc_context *h, const int *tail) {
     if (!h->pending) return PFC_OK;
     const int levels = h->last_levels;
     const size_t n_tail = (size_t)levels + 12 + 12;
-    const int *tail = h->h_tail.p;
-    if (h->tail_host) {     // pfc_eval: one D2H copy carries the tail and the outputs
-        tail = h->tail_host; h->tail_host = nullptr;
-    } else {
+    if (!tail) {
         HIP_TRY(h, hipMemcpyAsync(h->h_tail.p, h->tail.p, sizeof(int) * n_tail, hipMemcpyDeviceToHost, h->last_stream));
+        tail = h->h_tail.p;
     }
     HIP_TRY(h, hipStreamSynchronize(h->last_stream));
     h->pending = false;
@@ -1149,21 +1165,23 @@ int check_one(pfc_context *h) {
 }
 
 // Synchronise the pending evaluation (both halves of a split one) and merge the counters.
-int check_fused(pfc_context *h);
+// (tail, fout: the pinned blocks the packed tail / the fused kernel's per-item words are on their way to with the outputs, or
+// were written to by the kernels; null: fetched into the handle's own mirrors h_tail / h_fout here)
+int check_fused(pfc_context *h, const int *fout);
 void team_release(pfc_context *h);
-int check_eval(pfc_context *h) {
-    if (h->pending_fused) return check_fused(h);
+int check_eval(pfc_context *h, const int *tail = nullptr, const int *fout = nullptr) {
+    if (h->pending_fused) return check_fused(h, fout);
     h->last_fused = false;
     team_release(h);
     if (!h->split_n0) {
         h->last_parts = 1;
-        const int rc0 = check_one(h);
+        const int rc0 = check_one(h, tail);
         if (rc0 == PFC_OK) h->note_shape(h->last_n_items, h->last_active * 4 <= (long long)h->last_n_items);
         return rc0;
     }
     h->last_parts = 2;
     pfc_context *t = h->twin;
-    const int rc1 = check_one(h), rc2 = check_one(t);   // both always run: each grows its own work lists on overflow
+    const int rc1 = check_one(h, tail), rc2 = check_one(t, nullptr);   // both always run: each grows its own work lists on overflow (the second half reads its own h_tail)
     h->split_n0 = 0;
     if (rc1 != PFC_OK) return rc1;
     if (rc2 != PFC_OK) { h->err = t->err; return rc2; }
@@ -1201,8 +1219,8 @@ void team_release(pfc_context *h) {
     g_team_slot[h->device & 63].store(nullptr);
 }
 
-bool fused_ok(const pfc_context *h, int n_items) {
-    return h->opt_fused && !h->opt_fixed_order && h->fused_skip == 0 && !h->opt_debug && !h->opt_profile && !h->want_surv &&
+bool fused_ok(const pfc_context *h, int n_items, const PassOpts &o) {
+    return h->opt_fused && !h->opt_fixed_order && h->fused_skip == 0 && !h->opt_debug && !h->opt_profile && !o.list &&
            !h->is_twin && h->d_insfull && n_items <= kFusedMaxItems && h->max_leaves <= kFusedMaxLeaves;
 }
 // Team size for an evaluation of a few BIG pairs (more leaves than one workgroup takes: BASELINE config 3 as written is one
@@ -1211,9 +1229,9 @@ bool fused_ok(const pfc_context *h, int n_items) {
 // Small scenes (fused_ok): 1 -- unless the items are few and mid-sized (a 972-tet box on the ground keeps ONE CU busy for
 // 52 us, a third of it dealing 1 100 fan triangles out to 256 threads): then a small team, one workgroup per 128 leaves of
 // the pair, at most 32 (C2 64 -> 48 us, four reduced C3 poses 106 -> 81 us; a team of 2 loses to its own team sum).
-int fused_team(const pfc_context *h, int n_items) {
+int fused_team(const pfc_context *h, int n_items, const PassOpts &o) {
     const int blocks = h->n_cu < kTeamMaxBlocks ? h->n_cu : kTeamMaxBlocks;      // (a partitioned device has fewer CUs)
-    if (fused_ok(h, n_items)) {
+    if (fused_ok(h, n_items, o)) {
         // (end of round 3, scripts/variants/team_cap_run.py: a workgroup per 128 leaves, at most 32 -- a 4 880-leaf pair alone
         // 94 -> 82 us, four of them 132 -> 86, sixteen 148 -> 94; 2 000-leaf pairs 84 -> 79 (x 4), 88 -> 80 (x 16); C2 unchanged)
         int nw = (h->max_leaves + 64) / 128;
@@ -1222,7 +1240,7 @@ int fused_team(const pfc_context *h, int n_items) {
         if (nw > h->opt_team) nw = h->opt_team;
         return nw >= 4 ? nw : 1;
     }
-    if (!(h->opt_fused && !h->opt_fixed_order && h->opt_team && h->fused_skip == 0 && !h->opt_debug && !h->opt_profile && !h->want_surv && !h->is_twin &&
+    if (!(h->opt_fused && !h->opt_fixed_order && h->opt_team && h->fused_skip == 0 && !h->opt_debug && !h->opt_profile && !o.list && !h->is_twin &&
           h->d_insfull && h->max_leaves > kFusedMaxLeaves && n_items >= 1 && n_items <= kFusedMaxItems))
         return 0;
     int nw = blocks / n_items;
@@ -1238,32 +1256,30 @@ int fused_team(const pfc_context *h, int n_items) {
 }
 
 int enqueue_fused(pfc_context *h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
-                  const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, hipStream_t st) {
+                  const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, hipStream_t st, const PassOpts &o) {
     new_value_pass(h);
     h->pending_more = false; h->last_dual_reused = false;
     FuArgs a;
     a.n_items = n_items; a.n_ins = (int)h->ins.size(); a.ins_ids = d_ins_ids; a.pose = d_pose; a.twist = d_twist; a.s = d_s;
     a.ins = h->d_insfull; a.wrench = d_wrench; a.sdot = d_sdot; a.counts = d_counts;
-    if (h->fout_dev) {
-        a.fout = h->fout_dev;
-    } else {
+    if (!o.fout) {
         HIP_TRY(h, h->fout.ensure((size_t)kFusedMaxItems * 8));
         HIP_TRY(h, h->h_fout.ensure((size_t)kFusedMaxItems * 8));
-        a.fout = h->fout.p;
     }
+    a.fout = o.fout ? o.fout : h->fout.p;
     if (++h->fused_seq == 0) h->fused_seq = 1;
     a.seq = h->fused_seq;
-    if (h->fout_host) {
+    if (o.fout_host) {
         // polled path: the completion words live in pinned host memory that several block layouts share (offsets depend on
         // n_items and the number of levels), so a stale small integer of an earlier layout could equal this launch's
         // sequence number -- clear this launch's n words before the kernel can write them (<= 256 host stores)
-        volatile int *vf = const_cast<volatile int *>(h->fout_host);
+        volatile int *vf = const_cast<volatile int *>(o.fout_host);
         for (int i = 0; i < n_items; ++i) vf[8 * i + 5] = 0;
         std::atomic_thread_fence(std::memory_order_release);
     }
-    a.n_dir = h->fu_ndir; a.d_pose = h->fu_dpose; a.d_twist = h->fu_dtwist; a.d_wrench = h->fu_dwrench; a.d_sdot = h->fu_dsdot;
+    a.n_dir = o.n_dir; a.d_pose = o.d_pose; a.d_twist = o.d_twist; a.d_wrench = o.d_wrench; a.d_sdot = o.d_sdot;
     a.emit_items = nullptr; a.emit_cand = nullptr; a.emit_surv = nullptr; a.emit_icnt = nullptr; a.emit_ctr = nullptr; a.emit_cap = 0;
-    if (h->fu_emit) {
+    if (o.emit) {
         a.emit_items = h->items.p; a.emit_cand = h->cand.p; a.emit_surv = h->surv.p; a.emit_icnt = h->icnt.p;
         a.emit_ctr = h->emit_ctr.p; a.emit_cap = (int)h->ccap;
     }
@@ -1272,8 +1288,8 @@ int enqueue_fused(pfc_context *h, int n_items, const int *d_ins_ids, const doubl
     HIP_TRY(h, h->stamps.ensure(16));
     a.stamps = h->stamps.p;
 #endif
-    a.bp_pose = h->bp_dev; a.team_fault = h->opt_team_fault; a.f32 = h->opt_fused_f32;
-    a.nw = h->fu_nw; a.team = nullptr;
+    a.bp_pose = o.bp_pose; a.team_fault = h->opt_team_fault; a.f32 = h->opt_fused_f32;
+    a.nw = o.nw; a.team = nullptr;
     a.team_seeds = h->max_leaves > kFusedMaxLeaves ? kTeamSeedsBig : kTeamSeeds;
     h->last_fu_nw = a.nw;
     if (a.nw > 1) {
@@ -1294,9 +1310,8 @@ int enqueue_fused(pfc_context *h, int n_items, const int *d_ins_ids, const doubl
     return PFC_OK;
 }
 
-int check_fused(pfc_context *h) {
+int check_fused(pfc_context *h, const int *fo) {
     const int n = h->last_n_items;
-    const int *fo = h->fout_host;
     if (!fo) {
         HIP_TRY(h, hipMemcpyAsync(h->h_fout.p, h->fout.p, sizeof(int) * 8 * (size_t)n, hipMemcpyDeviceToHost, h->last_stream));
         fo = h->h_fout.p;
@@ -1304,12 +1319,16 @@ int check_fused(pfc_context *h) {
     } else {
         // The kernel wrote its results straight into pinned host memory; every workgroup ends with a system-scope
         // release and its completion word.  Polling those words returns ~3 us earlier than hipStreamSynchronize wakes
-        // up; after ~200 us without completion (a long evaluation, a stalled queue) the stream is synchronised instead.
+        // up; after 200 us without completion (a long evaluation, a stalled queue) the stream is synchronised instead.
+        // (By the clock: the 200 000 spins this used to be lasted as long as the loop's code made them, ~85 us of one item's word, and a
+        // single full-size C3 pose was polled or synchronised depending on how the loop compiled: 82.5 against 88.0 us, profiles/pass_opts_ab.json.)
         const volatile int *vf = fo;
         const int seq = h->fused_seq;
         bool done = false;
         static const bool no_poll = std::getenv("PFC_FUSED_SYNC") != nullptr;     // A/B knob: synchronise instead of polling
-        for (int spin = 0; spin < 200000 && !done && !no_poll; ++spin) {
+        const auto give_up = std::chrono::steady_clock::now() + std::chrono::microseconds(200);
+        for (int spin = 0; !done && !no_poll; ++spin) {
+            if ((spin & 63) == 63 && std::chrono::steady_clock::now() > give_up) break;
             done = true;
             for (int i = n - 1; i >= 0; --i)
                 if (vf[8 * i + 5] != seq) { done = false; break; }
@@ -1825,12 +1844,9 @@ static int check_eval_args(pfc_context *h, int n_items, const void *ins_ids, con
     return PFC_OK;
 }
 
-int pfc_eval_device(pfc_handle h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
-                    const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return multi_eval_device(h, n_items, 0, d_ins_ids, d_pose, nullptr, d_twist, d_s, nullptr, nullptr, nullptr, d_wrench, d_sdot,
-                                 nullptr, nullptr, d_counts, stream);
+// pfc_eval_device on one device.  o: what the caller decides (pose, list, targets); nw and half are set here, with the route.
+static int eval_device(pfc_context *h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
+                       const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, void *stream, PassOpts o) {
     { const int rc = check_eval_args(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot); if (rc != PFC_OK) return rc; }
     if (n_items == 0) { h->pending = false; h->last_n_items = 0; return PFC_OK; }
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1839,19 +1855,18 @@ int pfc_eval_device(pfc_handle h, int n_items, const int *d_ins_ids, const doubl
     h->pending_fused = false;
     end_kept_pass(h);
     h->pending_more = false;
-    int team = fused_team(h, n_items);
-    if (team > 1 && !team_acquire(h)) team = fused_ok(h, n_items) ? 1 : 0;     // another handle's teams are in flight on this device
+    int team = fused_team(h, n_items, o);
+    if (team > 1 && !team_acquire(h)) team = fused_ok(h, n_items, o) ? 1 : 0;     // another handle's teams are in flight on this device
     if (team) {
-        h->fu_nw = team;
-        const int rc_t = enqueue_fused(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, st);
-        h->fu_nw = 1;
+        o.nw = team;
+        const int rc_t = enqueue_fused(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, st, o);
         if (rc_t != PFC_OK) team_release(h);      // no fused evaluation pending: the slot is free again
         return rc_t;
     }
     if (h->fused_skip > 0 && n_items <= kFusedMaxItems) --h->fused_skip;
     const bool split = h->opt_split_min > 0 && n_items >= h->opt_split_min && d_ins_ids && !h->opt_debug && !h->opt_fixed_order &&
-                       !h->want_surv && !h->is_twin && !pile_mode(h, n_items);
-    if (!split) return enqueue_eval(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, st);
+                       !o.list && !h->is_twin && !pile_mode(h, n_items);
+    if (!split) return enqueue_eval(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, st, o);
     int rc = make_twin(h);
     if (rc != PFC_OK) return rc;
     pfc_context *t = h->twin;
@@ -1871,13 +1886,14 @@ int pfc_eval_device(pfc_handle h, int n_items, const int *d_ins_ids, const doubl
     HIP_TRY(h, hipEventRecord(h->ev_fork, st));
     if (s0 != st) HIP_TRY(h, hipStreamWaitEvent(s0, h->ev_fork, 0));
     HIP_TRY(h, hipStreamWaitEvent(t->stream, h->ev_fork, 0));
-    h->in_split = true; t->in_split = true;
-    rc = enqueue_eval(h, n0, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, s0);
-    h->in_split = false;
+    o.half = true;
+    rc = enqueue_eval(h, n0, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, s0, o);
     if (rc != PFC_OK) return rc;
+    if (o.bp_pose) o.bp_pose += 24 * (size_t)n0;
+    o.tail = nullptr;      // the second half packs its tail into its own buffer (check_eval reads it there)
     rc = enqueue_eval(t, n1, d_ins_ids + n0, d_pose + 24 * (size_t)n0, d_twist + 6 * (size_t)n0,
                       d_s ? d_s + 6 * (size_t)n0 : nullptr, d_wrench + 6 * (size_t)n0, d_sdot + 6 * (size_t)n0,
-                      d_counts ? d_counts + 4 * (size_t)n0 : nullptr, t->stream);
+                      d_counts ? d_counts + 4 * (size_t)n0 : nullptr, t->stream, o);
     if (rc != PFC_OK) { h->err = t->err; return rc; }
     HIP_TRY(h, hipEventRecord(h->ev_join, t->stream));
     HIP_TRY(h, hipStreamWaitEvent(st, h->ev_join, 0));
@@ -1887,6 +1903,15 @@ int pfc_eval_device(pfc_handle h, int n_items, const int *d_ins_ids, const doubl
     }
     h->split_n0 = n0;
     return PFC_OK;
+}
+
+int pfc_eval_device(pfc_handle h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
+                    const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return multi_eval_device(h, n_items, 0, d_ins_ids, d_pose, nullptr, d_twist, d_s, nullptr, nullptr, nullptr, d_wrench, d_sdot,
+                                 nullptr, nullptr, d_counts, stream);
+    return eval_device(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, stream, PassOpts());
 }
 
 namespace {
@@ -1916,7 +1941,7 @@ int surface_enqueue(pfc_context *h, int n_items, const int *d_ins_ids, const dou
     const int bits = pfc_sort_key_bits(n_items, h->max_elem1, h->max_elem2, &ba, &bb);
     if (bits > 64)
         return fail(h, PFC_ERR_BAD_ARG, "pfc_contact_surface: (item, element, element) needs %d key bits for %d items, more than 64", bits, n_items);
-    HIP_TRY(h, ensure_work(h, n_items));
+    HIP_TRY(h, ensure_work(h, n_items, false));
     const size_t c = h->ccap;
     HIP_TRY(h, h->surf_cnt.ensure(2 * (c + 1)));
     HIP_TRY(h, h->surf_off.ensure(2 * (c + 1)));
@@ -1948,8 +1973,8 @@ int surface_enqueue(pfc_context *h, int n_items, const int *d_ins_ids, const dou
     ea.frontier0 = h->frontier[0].p; ea.fcount = fcount; ea.acc = h->acc.p; ea.icnt = h->icnt.p;
     ea.status = h->status.p;
     hipLaunchKernelGGL(k_setup_items, dim3(grid_for(n_items, 64, 1 << 20)), dim3(64), 0, st, ea);
-    const int L = bfs_levels_for(h, n_items, levels);
-    launch_broadphase(h, n_items, L, ccount, fcount, next_seed, ucount, st);
+    const int L = bfs_levels_for(h, n_items, levels, false);
+    launch_broadphase(h, n_items, L, false, ccount, fcount, next_seed, ucount, st);
     // (item, element of mesh 1, element of mesh 2): the per-item segments sorted in LDS, or -- once an item had more candidates
     // than a segment sort takes -- one sort of the whole list
     if (h->surf_whole_list)
@@ -2227,8 +2252,7 @@ int pfc_check(pfc_handle h) {
         if ((unsigned)h->h_emit.p[2] & kStHole) return fail(h, PFC_ERR_STATE, "internal error: a work-list slot was read before it was written");
         const long long pairs_h = h->h_emit.p[0];
         h->dual_hint = pairs_h;
-        const int cpw_h = 64 / h->pending_ndir;
-        if ((h->any_bristle || h->opt_fixed_order) && (size_t)((pairs_h + cpw_h - 1) / cpw_h) * 64 + 64 > h->pending_dpcap)
+        if (!dual_pairs_fit(h, h->pending_ndir, pairs_h, h->pending_dpcap))
             return fail(h, PFC_ERR_OVERFLOW, "Dual evaluation: %lld contributing pairs exceed the speculative polygon capacity: re-issue", pairs_h);
         h->kept = {pfc_context::KeptPass::HandOver, h->last_n_items, h->pending_ids};
         return PFC_OK;
@@ -2240,10 +2264,9 @@ int pfc_check(pfc_handle h) {
     if (rc != PFC_OK || !dual) return rc;
     // did the kept Dual polygons of pfc_eval_dual_device fit?  (contributing pairs: the counter next to the polygon total
     // in the packed tail, which check_eval has just brought over)
-    const long long pairs = h->h_tail.p[12 + (((h->last_levels + 9) & ~1) + 1)];
+    const long long pairs = h->h_tail.p[tail_pairs(h->last_levels)];
     h->dual_hint = pairs;
-    const int cpw = 64 / h->pending_ndir;
-    if ((h->any_bristle || h->opt_fixed_order) && (size_t)((pairs + cpw - 1) / cpw) * 64 + 64 > h->pending_dpcap)
+    if (!dual_pairs_fit(h, h->pending_ndir, pairs, h->pending_dpcap))
         return fail(h, PFC_ERR_OVERFLOW, "Dual evaluation: %lld contributing pairs exceed the speculative polygon capacity: re-issue", pairs);
     h->kept = {pfc_context::KeptPass::Batched, h->last_n_items, h->pending_ids};
     return PFC_OK;
@@ -2339,10 +2362,9 @@ static void copy_out_dual(const double *pdo, size_t nk, double *d_wrench, double
     std::memcpy(d_sdot, pdo + nk * 6, sizeof(double) * nk * 6);
 }
 
-int pfc_eval(pfc_handle h, int n_items, const int *ins_ids, const double *pose, const double *twist,
-             const double *s, double *wrench, double *sdot, int *counts) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi) return multi_eval(h, n_items, ins_ids, pose, twist, s, wrench, sdot, counts);
+// pfc_eval on one device.  o: pose and list flag of a Dual evaluation's value pass (two-stage path); the pinned targets are set here.
+static int eval_host(pfc_context *h, int n_items, const int *ins_ids, const double *pose, const double *twist,
+                     const double *s, double *wrench, double *sdot, int *counts, PassOpts o) {
     if (!h->finalized) return fail(h, PFC_ERR_STATE, "pfc_eval before pfc_finalize");
     if (n_items < 0) return fail(h, PFC_ERR_BAD_ARG, "negative n_items");
     if (n_items == 0) return PFC_OK;
@@ -2355,7 +2377,7 @@ int pfc_eval(pfc_handle h, int n_items, const int *ins_ids, const double *pose, 
     // behind the packed tail in the same buffer, so that the status / counters and the results come back together.
     const size_t in_d = n * 36, in_bytes = in_d * sizeof(double) + n * sizeof(int);
     const size_t out_d = n * 12, out_bytes = out_d * sizeof(double) + n * 4 * sizeof(int);
-    const size_t t0 = (((size_t)h->max_levels + 40) + 3) & ~(size_t)3;      // ints in front of the outputs (16-byte multiple)
+    const size_t t0 = tail_prefix(h);
     const size_t back_bytes = t0 * sizeof(int) + out_bytes;
     HIP_TRY(h, h->pin_in.ensure(in_bytes));
     // behind the outputs: the per-item words of the fused small-scene kernel (status, counts: 8 ints per item)
@@ -2364,7 +2386,7 @@ int pfc_eval(pfc_handle h, int n_items, const int *ins_ids, const double *pose, 
     HIP_TRY(h, ensure_graphed(h, h->tail, t0 + out_bytes / sizeof(int) + 4));   // only ever grows; ensure_work asks for less
     // (every evaluation whose kernels read the inputs in place, i.e. up to 512 items: 64 box-on-plane scenes 52.2 -> 48.7 us, C4's
     // 256 66.5 -> 64.5, 128 full-size poses on the batched path 333 -> 328; scripts/variants/bar_items_run.py)
-    const bool bar = n <= kBarItems && !h->want_surv && bar_ready(h);
+    const bool bar = n <= kBarItems && !o.list && bar_ready(h);
     double *pi = bar ? (double *)h->bar_in.p : (double *)h->pin_in.p;
     pack_values(pi, n, in_d, ins_ids, pose, twist, s);
     if (bar) bar_publish();
@@ -2374,7 +2396,7 @@ int pfc_eval(pfc_handle h, int n_items, const int *ins_ids, const double *pose, 
     // (Up to 512 items while the inputs sat in host memory -- a kernel's reads over PCIe stop paying beyond that; with BAR-resident
     // inputs up to 4 096: C5 through host buffers 307 -> 282 us, 1 000 box-on-plane scenes 198 -> 178, 600 full-size poses
     // 635 -> 619, 2 048 unchanged; scripts/variants/zero_copy_limit_run.py.)
-    const bool zero_copy = n_items <= (bar ? (int)kBarItems : 512) && !h->want_surv;
+    const bool zero_copy = n_items <= (bar ? (int)kBarItems : 512) && !o.list;
     double *di = h->h_pose.p, *dout = reinterpret_cast<double *>(h->tail.p + t0);
     if (zero_copy) {
         void *dpi = h->bar_in.p, *dpo = nullptr;
@@ -2382,30 +2404,34 @@ int pfc_eval(pfc_handle h, int n_items, const int *ins_ids, const double *pose, 
         HIP_TRY(h, hipHostGetDevicePointer(&dpo, h->pin_out.p, 0));
         di = (double *)dpi;
         dout = reinterpret_cast<double *>((int *)dpo + t0);
+        o.tail = (int *)dpo;      // k_final packs the tail, the small-scene kernel its per-item words, straight into the pinned block
+        if (n <= (size_t)kFusedMaxItems) {
+            o.fout = reinterpret_cast<int *>(reinterpret_cast<char *>(dout) + out_bytes);
+            o.fout_host = reinterpret_cast<const int *>(reinterpret_cast<const char *>(h->pin_out.p) + back_bytes);
+        }
     } else {
         HIP_TRY(h, hipMemcpyAsync(di, pi, ins_ids ? in_bytes : in_d * sizeof(double), hipMemcpyHostToDevice, st));
     }
     int rc = PFC_OK;
     for (int attempt = 0; attempt < 40; ++attempt) {
-        h->tail_dev = zero_copy ? reinterpret_cast<int *>(dout) - t0 : nullptr;
-        if (zero_copy && n <= (size_t)kFusedMaxItems) {
-            h->fout_dev = reinterpret_cast<int *>(reinterpret_cast<char *>(dout) + out_bytes);
-            h->fout_host = reinterpret_cast<const int *>(reinterpret_cast<const char *>(h->pin_out.p) + back_bytes);
-        }
-        rc = pfc_eval_device(h, n_items, ins_ids ? (const int *)(di + in_d) : nullptr, di, di + n * 24,
-                             s ? di + n * 30 : nullptr, dout, dout + n * 6, (int *)(dout + out_d), st);
-        h->tail_dev = nullptr; h->fout_dev = nullptr;
-        if (rc != PFC_OK) { h->fout_host = nullptr; return rc; }
+        rc = eval_device(h, n_items, ins_ids ? (const int *)(di + in_d) : nullptr, di, di + n * 24,
+                         s ? di + n * 30 : nullptr, dout, dout + n * 6, (int *)(dout + out_d), st, o);
+        if (rc != PFC_OK) return rc;
         if (!zero_copy && !h->pending_fused) HIP_TRY(h, hipMemcpyAsync(h->pin_out.p, h->tail.p, back_bytes, hipMemcpyDeviceToHost, st));
-        h->tail_host = (const int *)h->pin_out.p;
-        rc = check_eval(h);
-        h->tail_host = nullptr; h->fout_host = nullptr;
+        rc = check_eval(h, (const int *)h->pin_out.p, o.fout_host);      // one D2H copy carries the tail and the outputs
         if (rc != PFC_ERR_OVERFLOW) break;
     }
     if (rc != PFC_OK) return rc;
     const double *po = reinterpret_cast<const double *>((const int *)h->pin_out.p + t0);
     copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
     return PFC_OK;
+}
+
+int pfc_eval(pfc_handle h, int n_items, const int *ins_ids, const double *pose, const double *twist,
+             const double *s, double *wrench, double *sdot, int *counts) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi) return multi_eval(h, n_items, ins_ids, pose, twist, s, wrench, sdot, counts);
+    return eval_host(h, n_items, ins_ids, pose, twist, s, wrench, sdot, counts, PassOpts());
 }
 
 namespace {
@@ -2422,7 +2448,7 @@ int launch_dual(pfc_context *h, int n_items, int n_dir, const int *tail, const d
     if (!acc_cleared) HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
     DualArgs a;
     a.items = h->items.p; a.cand = h->cand.p; a.ccount = tail + 12; a.ccap = (int)h->ccap;   // packed copy of the counters
-    a.surv = h->surv.p; a.scount = tail + 12 + (((h->last_levels + 9) & ~1) + 1);
+    a.surv = h->surv.p; a.scount = tail + tail_pairs(h->last_levels);
     if (pair_count) a.ccount = a.scount = pair_count;       // hand-over from the fused small-scene kernel: one list, one count
     a.n_items = n_items; a.n_dir = n_dir; a.d_pose = dp; a.d_twist = dt; a.d_s = dsd; a.icnt = h->icnt.p;
     a.dacc = h->dual_acc.p; a.dres = h->dual_res.p; a.d_wrench = dw; a.d_sdot = dsdot;
@@ -2438,7 +2464,7 @@ int launch_dual(pfc_context *h, int n_items, int n_dir, const int *tail, const d
     // Dual polygons kept between the passes: a wave of k_narrow_dual owns 64 consecutive slots (no slot counter)
     // (option fixed_order: the bound also sizes the record list of the passes' sums, for every model -- the callers compare the pair count
     // with this capacity after their synchronisation and re-issue the passes when it was exceeded)
-    const size_t dpcap = (h->any_bristle || h->opt_fixed_order) ? ((n_pairs_bound + cpw - 1) / cpw) * 64 + 64 : 64;   // 64 slots per group of cpw pairs
+    const size_t dpcap = dual_poly_cap(h, n_dir, n_pairs_bound);
     HIP_TRY(h, ensure_graphed(h, h->dual_poly, dpcap * kDpFields));
     HIP_TRY(h, ensure_graphed(h, h->dual_pkey, dpcap));
     a.dpoly = h->dual_poly.p; a.dpoly_key = h->dual_pkey.p; a.dpcap = (long long)dpcap;
@@ -2545,12 +2571,22 @@ int launch_dual(pfc_context *h, int n_items, int n_dir, const int *tail, const d
     return PFC_OK;
 }
 
+// A null d_ds of nk (item, direction) pairs becomes the handle's block of zeros (cleared on st when it is new).
+hipError_t zero_ds(pfc_context *h, size_t nk, const double **d_ds, hipStream_t st) {
+    if (*d_ds) return hipSuccess;
+    bool moved = false;
+    hipError_t e = h->dual_zero.ensure(nk * 6, &moved);
+    if (e == hipSuccess && moved) e = hipMemsetAsync(h->dual_zero.p, 0, sizeof(double) * h->dual_zero.cap, st);
+    *d_ds = h->dual_zero.p;
+    return e;
+}
+
 // Smallest scenes, all instructions regularized (test/boxes.jl and the like): value AND Dual passes inside the fused
 // small-scene kernel -- one launch, results polled from pinned memory.  Returns PFC_ERR_OVERFLOW when an item does not fit
 // (too many candidates / polygons): the caller takes the batched Dual path and this one stays off for a while.
 int eval_dual_fused(pfc_context *h, int n_items, int n_dir, const int *ins_ids, const double *pose, const double *twist,
                     const double *s, const double *d_pose, const double *d_twist, double *wrench, double *sdot,
-                    double *d_wrench, double *d_sdot, int *counts) {
+                    double *d_wrench, double *d_sdot, int *counts, const double *bp_pose) {
     h->pin_din_pt = {};    // these pinned blocks are about to be reused
     const size_t n = (size_t)n_items, nk = n * n_dir;
     const size_t in_d = n * 36, in_bytes = in_d * sizeof(double) + n * sizeof(int);
@@ -2564,15 +2600,13 @@ int eval_dual_fused(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     PinnedDev v;
     { const int rc = map_pinned(h, &v, in_bytes, sizeof(double) * nk * 30); if (rc != PFC_OK) return rc; }
     double *di = (double *)v.in, *dout = (double *)v.out, *ddi = (double *)v.din, *ddo = (double *)v.dout;
-    h->fout_dev = reinterpret_cast<int *>(dout + out_d) + n * 4;
-    h->fout_host = reinterpret_cast<const int *>((const double *)h->pin_out.p + out_d) + n * 4;
-    h->fu_ndir = n_dir; h->fu_dpose = ddi; h->fu_dtwist = ddi + nk * 24; h->fu_dwrench = ddo; h->fu_dsdot = ddo + nk * 6;
+    PassOpts o = {bp_pose};
+    o.fout = reinterpret_cast<int *>(dout + out_d) + n * 4;
+    o.fout_host = reinterpret_cast<const int *>((const double *)h->pin_out.p + out_d) + n * 4;
+    o.n_dir = n_dir; o.d_pose = ddi; o.d_twist = ddi + nk * 24; o.d_wrench = ddo; o.d_sdot = ddo + nk * 6;
     int rc = enqueue_fused(h, n_items, ins_ids ? (const int *)(di + in_d) : nullptr, di, di + n * 24, s ? di + n * 30 : nullptr,
-                           dout, dout + n * 6, reinterpret_cast<int *>(dout + out_d), h->stream);
-    h->fu_ndir = 0; h->fu_dpose = h->fu_dtwist = nullptr; h->fu_dwrench = h->fu_dsdot = nullptr;
-    h->fout_dev = nullptr;
-    if (rc == PFC_OK) rc = check_eval(h);
-    h->fout_host = nullptr;
+                           dout, dout + n * 6, reinterpret_cast<int *>(dout + out_d), h->stream, o);
+    if (rc == PFC_OK) rc = check_eval(h, nullptr, o.fout_host);
     if (rc != PFC_OK) return rc;
     const double *po = (const double *)h->pin_out.p;
     copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
@@ -2588,7 +2622,7 @@ int eval_dual_fused(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
 // the batched paths).
 int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids, const double *pose, const double *twist,
                      const double *s, const double *d_pose, const double *d_twist, const double *d_s, double *wrench,
-                     double *sdot, double *d_wrench, double *d_sdot, int *counts) {
+                     double *sdot, double *d_wrench, double *d_sdot, int *counts, const double *bp_pose) {
     h->pin_din_pt = {};    // these pinned blocks are about to be reused
     const size_t n = (size_t)n_items, nk = n * n_dir;
     const size_t in_d = n * 36, in_bytes = in_d * sizeof(double) + n * sizeof(int);
@@ -2610,7 +2644,7 @@ int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids,
                       h->kept.ids == (ins_ids != nullptr) && same_point(pi, n, in_d, ins_ids, pose, twist, s, true);
     if (!same) {
         end_kept_pass(h);
-        HIP_TRY(h, ensure_work(h, n_items));      // (not before a reuse: option poison refills the work lists there)
+        HIP_TRY(h, ensure_work(h, n_items, false));      // (not before a reuse: option poison refills the work lists there)
         pack_values(pi, n, in_d, ins_ids, pose, twist, s);
     }
     pack_seeds((double *)h->pin_din.p, nk, d_pose, d_twist, d_s, true);
@@ -2641,17 +2675,14 @@ int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids,
         h->last_dual_reused = true;
         return PFC_OK;
     }
-    size_t bound = 64;
-    while (bound < (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) * 2 + 64) bound *= 2;
+    const size_t bound = dual_spec_bound(h->dual_hint, 64);
     HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
     HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
     HIP_TRY(h, hipMemsetAsync(h->emit_ctr.p, 0, sizeof(int) * 4, st));
-    h->fout_dev = reinterpret_cast<int *>(dout + out_d) + n * 4;
-    h->fout_host = nullptr;           // this path synchronises (the Dual kernels run behind the fused one)
-    h->fu_emit = true;
+    PassOpts o = {bp_pose};
+    o.emit = true; o.fout = reinterpret_cast<int *>(dout + out_d) + n * 4;      // (no words to poll: this path synchronises, the Dual kernels run behind the fused one)
     int rc = enqueue_fused(h, n_items, ins_ids ? (const int *)(di + in_d) : nullptr, di, di + n * 24, s ? di + n * 30 : nullptr,
-                           dout, dout + n * 6, reinterpret_cast<int *>(dout + out_d), st);
-    h->fu_emit = false; h->fout_dev = nullptr;
+                           dout, dout + n * 6, reinterpret_cast<int *>(dout + out_d), st, o);
     if (rc != PFC_OK) return rc;
     size_t dpcap = 0;
     h->last_levels = eff_levels(h);
@@ -2660,18 +2691,15 @@ int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids,
     if (rc != PFC_OK) return rc;
     if (!zc) HIP_TRY(h, hipMemcpyAsync(h->pin_dout.p, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipMemcpyAsync(h->h_emit.p, h->emit_ctr.p, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-    h->fout_host = reinterpret_cast<const int *>((const double *)h->pin_out.p + out_d) + n * 4;
     // check_fused would poll; here the stream is synchronised (the completion words of the fused kernel are long written)
     HIP_TRY(h, hipStreamSynchronize(st));
-    rc = check_eval(h);
-    h->fout_host = nullptr;
+    rc = check_eval(h, nullptr, reinterpret_cast<const int *>((const double *)h->pin_out.p + out_d) + n * 4);
     if (rc != PFC_OK) return rc;
     if (h->stats[6] & kStCandOvf) return fail(h, PFC_ERR_OVERFLOW, "hand-over list of the small-scene kernel overflowed: batched path");
     if ((unsigned)h->h_emit.p[2] & kStHole) return fail(h, PFC_ERR_STATE, "internal error: a work-list slot was read before it was written");
     const long long pairs = h->h_emit.p[0];
     h->dual_hint = pairs;
-    const int cpw = 64 / n_dir;
-    if ((h->any_bristle || h->opt_fixed_order) && (size_t)((pairs + cpw - 1) / cpw) * 64 + 64 > dpcap) return PFC_ERR_OVERFLOW;
+    if (!dual_pairs_fit(h, n_dir, pairs, dpcap)) return PFC_ERR_OVERFLOW;
     copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
     copy_out_dual((const double *)h->pin_dout.p, nk, d_wrench, d_sdot);
     h->kept = {pfc_context::KeptPass::Hybrid, n_items, ins_ids != nullptr};
@@ -2685,13 +2713,13 @@ int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids,
 // takes the two-stage path, which sizes everything from the value pass.
 int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, const double *pose, const double *twist,
                     const double *s, const double *d_pose, const double *d_twist, const double *d_s, double *wrench,
-                    double *sdot, double *d_wrench, double *d_sdot, int *counts) {
+                    double *sdot, double *d_wrench, double *d_sdot, int *counts, const double *bp_pose) {
     h->pin_din_pt = {};    // these pinned blocks are about to be reused
     h->pin_in_pt = {};
     const size_t n = (size_t)n_items, nk = n * n_dir;
     const size_t in_d = n * 36, in_bytes = in_d * sizeof(double) + n * sizeof(int);
     const size_t out_d = n * 12, out_bytes = out_d * sizeof(double) + n * 4 * sizeof(int);
-    const size_t t0 = (((size_t)h->max_levels + 40) + 3) & ~(size_t)3;
+    const size_t t0 = tail_prefix(h);
     const size_t back_bytes = t0 * sizeof(int) + out_bytes;
     {
         bool in_moved, out_moved;
@@ -2718,17 +2746,16 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     // One captured graph: accumulator fill, the value pass, the Dual passes.  (Launched eagerly behind the replayed value
     // graph, the Dual kernels started 9 us late.)  The capacity of the kept Dual polygons is a power of two above twice
     // the previous pair count, so that the graph survives the small changes from one evaluation to the next.
-    size_t bound = 64;
-    while (bound < (size_t)h->dual_hint * 2 + 64) bound *= 2;
-    const int cpw = 64 / n_dir;
-    if (!same) HIP_TRY(h, ensure_work(h, n_items));      // (not before a reuse: option poison refills the work lists there)
+    const size_t bound = dual_spec_bound(h->dual_hint, 64);
+    const PassOpts o = {bp_pose, true, (int *)v.out};      // the value pass lists the contributing candidates and packs its tail into the pinned output block
+    if (!same) HIP_TRY(h, ensure_work(h, n_items, o.list));      // (not before a reuse: option poison refills the work lists there)
     HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
     HIP_TRY(h, ensure_graphed(h, h->dual_res, nk * kDrStride));
-    const size_t dpcap = (h->any_bristle || h->opt_fixed_order) ? ((bound + cpw - 1) / cpw) * 64 + 64 : 64;
+    const size_t dpcap = dual_poly_cap(h, n_dir, bound);
     HIP_TRY(h, ensure_graphed(h, h->dual_poly, dpcap * kDpFields));
     HIP_TRY(h, ensure_graphed(h, h->dual_pkey, dpcap));
     const int levels = eff_levels(h);
-    const int L = bfs_levels_for(h, n_items, levels);
+    const int L = bfs_levels_for(h, n_items, levels, o.half);
     // seeds / results of up to 512 (item, direction) pairs are read / written in place by the kernels; larger ones are
     // copied by memcpy nodes of the graph (reading 288 B per pair over PCIe from inside k_narrow_dual stops paying)
     const bool zc_dual = nk <= (h->bar_state == 1 ? (int)kBarKeys : 512);
@@ -2760,10 +2787,8 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     key.v.n_items = n_items; key.v.levels = levels; key.v.L = L; key.v.debug = 0;
     key.v.bristle = (h->any_bristle ? 1 : 0) | (h->any_tet_tet ? 2 : 0); key.v.surv = 1;
     key.v.p[0] = d_ins; key.v.p[1] = di; key.v.p[2] = di + n * 24; key.v.p[3] = d_sv; key.v.p[4] = dout;
-    key.v.p[5] = dout + n * 6; key.v.p[6] = dout + out_d; key.v.p[7] = v.out; key.v.p[8] = h->bp_dev; key.v.stream = (void *)st; key.v.epoch = h->epoch;
+    key.v.p[5] = dout + n * 6; key.v.p[6] = dout + out_d; key.v.p[7] = o.tail; key.v.p[8] = o.bp_pose; key.v.stream = (void *)st; key.v.epoch = h->epoch;
     key.n_dir = n_dir; key.bound = bound; key.din = ddi; key.dout = ddo;
-    h->want_surv = true;
-    h->tail_dev = (int *)v.out;
     h->last_levels = levels;      // launch_dual locates the pair counter in the tail by it
     int rc = PFC_OK;
     if (!h->dghave || std::memcmp(&key, &h->dgkey, sizeof key) != 0) {
@@ -2774,7 +2799,7 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
         if (e == hipSuccess) {
             e = hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st);
             if (!zc_dual && e == hipSuccess) e = hipMemcpyAsync(ddi, h->pin_din.p, sizeof(double) * nk * 36, hipMemcpyHostToDevice, st);
-            rc = record_eval(h, n_items, d_ins, di, di + n * 24, d_sv, dout, dout + n * 6, (int *)(dout + out_d), st, false);
+            rc = record_eval(h, n_items, d_ins, di, di + n * 24, d_sv, dout, dout + n * 6, (int *)(dout + out_d), st, false, o);
             if (rc == PFC_OK)
                 rc = launch_dual(h, n_items, n_dir, (const int *)v.out, ddi, ddi + nk * 24, ddi + nk * 30, ddo, ddo + nk * 6, bound,
                                  st, nullptr, true);
@@ -2785,26 +2810,22 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
         }
         if (rc == PFC_OK && e == hipSuccess) e = hipGraphInstantiate(h->dgexec.put(), graph, nullptr, nullptr, 0);
         if (graph) (void)hipGraphDestroy(graph);
-        h->want_surv = false; h->tail_dev = nullptr;
         if (rc != PFC_OK) return rc;
         if (e != hipSuccess) return fail(h, PFC_ERR_HIP, "Dual graph capture failed: %s", hipGetErrorString(e));
         h->dgkey = key; h->dghave = true;
     }
-    h->want_surv = false; h->tail_dev = nullptr;
     new_value_pass(h);      // the replay overwrites the device state
     h->last_dual_reused = false;
     HIP_TRY(h, hipGraphLaunch(h->dgexec, st));
     h->last_bfs_levels = L; h->last_n_items = n_items; h->pending = true; h->last_stream = st; h->ev_valid = false;
     h->split_n0 = 0;
-    h->tail_host = (const int *)h->pin_out.p;
-    rc = check_eval(h);                 // the one synchronisation; grows the work lists on overflow
-    h->tail_host = nullptr;
+    const int *tail = (const int *)h->pin_out.p;
+    rc = check_eval(h, tail);           // the one synchronisation; grows the work lists on overflow
     if (rc != PFC_OK) return rc;
     // did the kept Dual polygons fit?  (contributing pairs: the counter next to the polygon total in the packed tail)
-    const int *tail = (const int *)h->pin_out.p;
-    const long long pairs = tail[12 + (((h->last_levels + 9) & ~1) + 1)];
+    const long long pairs = tail[tail_pairs(h->last_levels)];
     h->dual_hint = pairs;
-    if ((h->any_bristle || h->opt_fixed_order) && (size_t)((pairs + cpw - 1) / cpw) * 64 + 64 > dpcap) return PFC_ERR_OVERFLOW;
+    if (!dual_pairs_fit(h, n_dir, pairs, dpcap)) return PFC_ERR_OVERFLOW;
     copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
     copy_out_dual((const double *)h->pin_dout.p, nk, d_wrench, d_sdot);
     h->kept = {pfc_context::KeptPass::OneGraph, n_items, ins_ids != nullptr};
@@ -2820,21 +2841,6 @@ int pfc_eval_dual_device_bp(pfc_handle h, int n_items, int n_dir, const int *d_i
     if (h->multi)
         return multi_eval_device(h, n_items, n_dir, d_ins_ids, d_pose, d_bp_pose, d_twist, d_s, d_dpose, d_dtwist, d_ds, d_wrench, d_sdot,
                                  d_dwrench, d_dsdot, d_counts, stream);
-    h->bp_dev = d_bp_pose;
-    const int rc = pfc_eval_dual_device(h, n_items, n_dir, d_ins_ids, d_pose, d_twist, d_s, d_dpose, d_dtwist, d_ds, d_wrench, d_sdot,
-                                        d_dwrench, d_dsdot, d_counts, stream);
-    h->bp_dev = nullptr;
-    return rc;
-}
-
-int pfc_eval_dual_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const double *d_pose,
-                         const double *d_twist, const double *d_s, const double *d_dpose, const double *d_dtwist,
-                         const double *d_ds, double *d_wrench, double *d_sdot, double *d_dwrench, double *d_dsdot,
-                         int *d_counts, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return multi_eval_device(h, n_items, n_dir, d_ins_ids, d_pose, nullptr, d_twist, d_s, d_dpose, d_dtwist, d_ds, d_wrench, d_sdot,
-                                 d_dwrench, d_dsdot, d_counts, stream);
     if (n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "pfc_eval_dual_device: n_dir must be in 1..16");
     { const int rc = check_eval_args(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot); if (rc != PFC_OK) return rc; }
     h->pending_dual = false; h->pending_more = false;
@@ -2847,35 +2853,29 @@ int pfc_eval_dual_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_
     // Kept Dual polygons are sized WITHOUT reading the value pass back: twice the contributing pairs of the previous Dual
     // evaluation (a power of two, so that the buffers settle), a guess the first time.  pfc_check compares the actual
     // count with the capacity after the one synchronisation and asks for a re-issue if it fell short.
-    size_t bound = 4096;
-    while (bound < (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) * 2 + 64 || bound < (size_t)n_items * 8) bound *= 2;
+    size_t bound = dual_spec_bound(h->dual_hint, 4096);
+    while (bound < (size_t)n_items * 8) bound *= 2;
     HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
     HIP_TRY(h, ensure_graphed(h, h->dual_res, nk * kDrStride));
-    if (!d_ds) {
-        bool moved;
-        HIP_TRY(h, h->dual_zero.ensure(nk * 6, &moved));
-        if (moved) HIP_TRY(h, hipMemsetAsync(h->dual_zero.p, 0, sizeof(double) * h->dual_zero.cap, st));
-        d_ds = h->dual_zero.p;
-    }
+    HIP_TRY(h, zero_ds(h, nk, &d_ds, st));
     HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
     h->split_n0 = 0; h->pending_fused = false; h->pending_dual_hyb = false;
     // Small scenes: the value pass in the one-workgroup-per-item kernel, which hands item records and lists to the batched
     // Dual passes (what pfc_eval_dual does for host buffers, eval_dual_hybrid).  A miss (an item that does not fit, a
     // hand-over list or a speculation that fell short) is reported by pfc_check as PFC_ERR_OVERFLOW and the re-issue takes
     // the batched value pass below.
-    if (fused_ok(h, n_items) && nk <= 4096 && (h->dual_hint >= 0 || !h->any_bristle) && std::getenv("PFC_NO_HYBRID") == nullptr) {
+    PassOpts o = {d_bp_pose};
+    if (fused_ok(h, n_items, o) && nk <= 4096 && (h->dual_hint >= 0 || !h->any_bristle) && std::getenv("PFC_NO_HYBRID") == nullptr) {
         if (h->dual_dev_hyb_skip > 0) {
             --h->dual_dev_hyb_skip;
         } else {
-            HIP_TRY(h, ensure_work(h, n_items));
+            HIP_TRY(h, ensure_work(h, n_items, false));
             HIP_TRY(h, h->emit_ctr.ensure(4));
             HIP_TRY(h, h->h_emit.ensure(4));
-            size_t bh = 64;
-            while (bh < (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) * 2 + 64) bh *= 2;
+            const size_t bh = dual_spec_bound(h->dual_hint, 64);
             HIP_TRY(h, hipMemsetAsync(h->emit_ctr.p, 0, sizeof(int) * 4, st));
-            h->fu_emit = true; h->fout_dev = nullptr; h->fout_host = nullptr;
-            int rcf = enqueue_fused(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, st);
-            h->fu_emit = false;
+            o.emit = true;
+            int rcf = enqueue_fused(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, st, o);
             if (rcf != PFC_OK) return rcf;
             h->last_levels = eff_levels(h);
             size_t dpcap_h = 0;
@@ -2886,15 +2886,22 @@ int pfc_eval_dual_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_
             return PFC_OK;
         }
     }
-    h->want_surv = true;         // the value pass also lists the contributing candidates; batched path, one part
-    int rc = enqueue_eval(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, st);
-    h->want_surv = false;
+    o.list = true;         // the value pass also lists the contributing candidates; batched path, one part
+    int rc = enqueue_eval(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, st, o);
     if (rc != PFC_OK) return rc;
     size_t dpcap = 0;
     rc = launch_dual(h, n_items, n_dir, h->tail.p, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, bound, st, &dpcap, true);
     if (rc != PFC_OK) return rc;
     h->pending_dual = true; h->pending_dpcap = dpcap; h->pending_ndir = n_dir; h->pending_ids = d_ins_ids != nullptr;
     return PFC_OK;
+}
+
+int pfc_eval_dual_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const double *d_pose,
+                         const double *d_twist, const double *d_s, const double *d_dpose, const double *d_dtwist,
+                         const double *d_ds, double *d_wrench, double *d_sdot, double *d_dwrench, double *d_dsdot,
+                         int *d_counts, void *stream) {
+    return pfc_eval_dual_device_bp(h, n_items, n_dir, d_ins_ids, d_pose, nullptr, d_twist, d_s, d_dpose, d_dtwist, d_ds, d_wrench, d_sdot,
+                                   d_dwrench, d_dsdot, d_counts, stream);
 }
 
 int pfc_eval_dual_device_more(pfc_handle h, int n_dir, const double *d_dpose, const double *d_dtwist, const double *d_ds,
@@ -2911,12 +2918,7 @@ int pfc_eval_dual_device_more(pfc_handle h, int n_dir, const double *d_dpose, co
     const size_t nk = (size_t)n_items * n_dir;
     HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
     HIP_TRY(h, ensure_graphed(h, h->dual_res, nk * kDrStride));
-    if (!d_ds) {
-        bool moved;
-        HIP_TRY(h, h->dual_zero.ensure(nk * 6, &moved));
-        if (moved) HIP_TRY(h, hipMemsetAsync(h->dual_zero.p, 0, sizeof(double) * h->dual_zero.cap, st));
-        d_ds = h->dual_zero.p;
-    }
+    HIP_TRY(h, zero_ds(h, nk, &d_ds, st));
     HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
     // the contributing pairs are known exactly (dual_hint, from the value pass pfc_check has seen): no speculation
     const size_t bound = (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) + 64;
@@ -3320,45 +3322,34 @@ int pfc_eval_dual_bodies_device_more(pfc_handle h, int n_items, int n_dir, const
     return pfc_eval_dual_device_more(h, n_dir, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, stream);
 }
 
-// The Dual evaluation with the broadphase pose of m.float's state (calcTriTetIntersections!, non_friction.jl:94-101): the block is
-// kept in pinned host memory, which the value pass reads in place (96 bytes per item, once).
+// The Dual evaluation, with the broadphase pose of m.float's state where bp_pose is given (calcTriTetIntersections!,
+// non_friction.jl:94-101): that block is kept in pinned host memory, which the value pass reads in place (96 bytes per item, once),
+// and handed down as an argument to whichever path runs the value pass.
 int pfc_eval_dual_bp(pfc_handle h, int n_items, int n_dir, const int *ins_ids, const double *pose, const double *bp_pose,
                      const double *twist, const double *s, const double *d_pose, const double *d_twist, const double *d_s,
                      double *wrench, double *sdot, double *d_wrench, double *d_sdot, int *counts) {
     if (!h) return PFC_ERR_BAD_ARG;
     if (h->multi)
         return multi_eval_dual(h, n_items, n_dir, ins_ids, pose, bp_pose, twist, s, d_pose, d_twist, d_s, wrench, sdot, d_wrench, d_sdot, counts);
-    if (!bp_pose || n_items <= 0)
-        return pfc_eval_dual(h, n_items, n_dir, ins_ids, pose, twist, s, d_pose, d_twist, d_s, wrench, sdot, d_wrench, d_sdot, counts);
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t bytes = sizeof(double) * 24 * (size_t)n_items;
-    {
+    if (n_items <= 0) bp_pose = nullptr;
+    if (bp_pose) {
+        HIP_TRY(h, hipSetDevice(h->device));
+        const size_t bytes = sizeof(double) * 24 * (size_t)n_items;
         bool moved;
         HIP_TRY(h, h->pin_bp.ensure(bytes, &moved));
         if (moved) h->pin_bp_n = -1;
+        if (h->pin_bp_n != n_items || std::memcmp(h->pin_bp.p, bp_pose, bytes) != 0) {
+            // another broadphase pose: nothing a previous Dual evaluation left can be reused (the candidate lists differ)
+            end_kept_pass(h);
+            h->pin_in_pt = {}; h->pin_din_pt = {};
+            std::memcpy(h->pin_bp.p, bp_pose, bytes);
+            h->pin_bp_n = n_items;
+        }
+        void *dev = nullptr;
+        HIP_TRY(h, hipHostGetDevicePointer(&dev, h->pin_bp.p, 0));
+        bp_pose = (const double *)dev;      // from here on: the device-visible block
     }
-    if (h->pin_bp_n != n_items || std::memcmp(h->pin_bp.p, bp_pose, bytes) != 0) {
-        // another broadphase pose: nothing a previous Dual evaluation left can be reused (the candidate lists differ)
-        end_kept_pass(h);
-        h->pin_in_pt = {}; h->pin_din_pt = {};
-        std::memcpy(h->pin_bp.p, bp_pose, bytes);
-        h->pin_bp_n = n_items;
-    }
-    void *dev = nullptr;
-    HIP_TRY(h, hipHostGetDevicePointer(&dev, h->pin_bp.p, 0));
-    h->bp_dev = (const double *)dev;
-    const int rc = pfc_eval_dual(h, n_items, n_dir, ins_ids, pose, twist, s, d_pose, d_twist, d_s, wrench, sdot, d_wrench, d_sdot, counts);
-    h->bp_dev = nullptr;
-    return rc;
-}
-
-int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, const double *pose, const double *twist,
-                  const double *s, const double *d_pose, const double *d_twist, const double *d_s, double *wrench,
-                  double *sdot, double *d_wrench, double *d_sdot, int *counts) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return multi_eval_dual(h, n_items, n_dir, ins_ids, pose, nullptr, twist, s, d_pose, d_twist, d_s, wrench, sdot, d_wrench, d_sdot, counts);
-    if (!h->bp_dev && h->pin_bp_n != 0) {
+    if (!bp_pose && h->pin_bp_n != 0) {
         // the previous host-buffer Dual evaluation culled with a pose of its own: its lists are not this evaluation's
         end_kept_pass(h);
         h->pin_in_pt = {}; h->pin_din_pt = {};
@@ -3374,21 +3365,22 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
     const bool repeat = n_items > 0 && h->opt_dual_reuse && h->pin_in_pt.n == n_items && h->pin_in.p && h->pin_in_pt.ids == (ins_ids != nullptr) &&
                         same_point((const double *)h->pin_in.p, (size_t)n_items, h->pin_in_pt.ids_at, ins_ids, pose, twist, s, false);
     if (!repeat) h->pin_in_pt = {};
-    if (n_items > 0 && !h->any_bristle && fused_ok(h, n_items) && !repeat) {
+    PassOpts o = {bp_pose};
+    if (n_items > 0 && !h->any_bristle && fused_ok(h, n_items, o) && !repeat) {
         if (h->dual_fused_skip > 0) {
             --h->dual_fused_skip;
         } else {
             HIP_TRY(h, hipSetDevice(h->device));
             const int rc_f = eval_dual_fused(h, n_items, n_dir, ins_ids, pose, twist, s, d_pose, d_twist, wrench, sdot, d_wrench,
-                                             d_sdot, counts);
+                                             d_sdot, counts, bp_pose);
             if (rc_f != PFC_ERR_OVERFLOW) return rc_f;       // else: an item did not fit -> the batched Dual paths below
         }
     }
-    if (n_items > 0 && fused_ok(h, n_items) && (h->dual_hint >= 0 || !h->any_bristle) && (size_t)n_items * n_dir <= 4096 &&
+    if (n_items > 0 && fused_ok(h, n_items, o) && (h->dual_hint >= 0 || !h->any_bristle) && (size_t)n_items * n_dir <= 4096 &&
         std::getenv("PFC_NO_HYBRID") == nullptr) {
         HIP_TRY(h, hipSetDevice(h->device));
         const int rc_h = eval_dual_hybrid(h, n_items, n_dir, ins_ids, pose, twist, s, d_pose, d_twist, d_s, wrench, sdot, d_wrench,
-                                          d_sdot, counts);
+                                          d_sdot, counts, bp_pose);
         if (rc_h != PFC_ERR_OVERFLOW) return rc_h;           // else: batched paths below (lists grown / speculation short)
         if (h->dual_dev_hyb_skip < 1) h->dual_dev_hyb_skip = 1;   // (not the same sequence again inside pfc_eval_dual_device)
     }
@@ -3396,7 +3388,7 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
         wrench && sdot && !h->opt_debug && !h->opt_fixed_order && !(h->opt_split_min > 0 && n_items >= h->opt_split_min)) {
         HIP_TRY(h, hipSetDevice(h->device));
         const int rc_small = eval_dual_small(h, n_items, n_dir, ins_ids, pose, twist, s, d_pose, d_twist, d_s, wrench, sdot,
-                                             d_wrench, d_sdot, counts);
+                                             d_wrench, d_sdot, counts, bp_pose);
         if (rc_small != PFC_ERR_OVERFLOW) return rc_small;    // else: lists grown / speculation short -> two-stage path
     }
     if (n_items == 0) return PFC_OK;
@@ -3453,9 +3445,9 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
         HIP_TRY(h, hipMemcpyAsync(di, pi, ins_ids ? in_bytes : in_d * sizeof(double), hipMemcpyHostToDevice, st));
         int rc2 = PFC_OK;
         for (int attempt = 0; attempt < 40; ++attempt) {
-            rc2 = pfc_eval_dual_device(h, n_items, n_dir, ins_ids ? (const int *)(di + in_d) : nullptr, di, di + n * 24,
-                                       s ? di + n * 30 : nullptr, dd, dd + nk * 24, dd + nk * 30, dout, dout + n * 6,
-                                       ddo, ddo + nk * 6, (int *)(dout + out_d), st);
+            rc2 = pfc_eval_dual_device_bp(h, n_items, n_dir, ins_ids ? (const int *)(di + in_d) : nullptr, di, bp_pose, di + n * 24,
+                                          s ? di + n * 30 : nullptr, dd, dd + nk * 24, dd + nk * 30, dout, dout + n * 6,
+                                          ddo, ddo + nk * 6, (int *)(dout + out_d), st);
             if (rc2 != PFC_OK) return rc2;
             HIP_TRY(h, hipMemcpyAsync(h->pin_dout.p, dout, out_bytes, hipMemcpyDeviceToHost, st));
             rc2 = pfc_check(h);
@@ -3474,9 +3466,8 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
     // two-stage path (debug option, or PFC_DUAL_TWO_STAGE set for A/B runs): values, candidate list and per-item counters
     // by the ordinary evaluation (the broadphase ignores partials, src/contact_algorithms_non_friction.jl:95), read the
     // contributing-pair count, then the Dual passes
-    h->want_surv = true;
-    int rc = pfc_eval(h, n_items, ins_ids, pose, twist, s, wrench, sdot, counts);
-    h->want_surv = false;
+    o.list = true;
+    int rc = eval_host(h, n_items, ins_ids, pose, twist, s, wrench, sdot, counts, o);
     if (rc != PFC_OK) return rc;
     HIP_TRY(h, ensure_graphed(h, h->dual_in, nk * 36));
     HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
@@ -3497,6 +3488,12 @@ int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, cons
     HIP_TRY(h, hipStreamSynchronize(st));
     copy_out_dual((const double *)h->pin_out.p, nk, d_wrench, d_sdot);
     return PFC_OK;
+}
+
+int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, const double *pose, const double *twist,
+                  const double *s, const double *d_pose, const double *d_twist, const double *d_s, double *wrench,
+                  double *sdot, double *d_wrench, double *d_sdot, int *counts) {
+    return pfc_eval_dual_bp(h, n_items, n_dir, ins_ids, pose, nullptr, twist, s, d_pose, d_twist, d_s, wrench, sdot, d_wrench, d_sdot, counts);
 }
 
 int pfc_set_option(pfc_handle h, const char *name, long long value) {

@@ -730,3 +730,79 @@ def test_pass_b_folded_into_pass_a_equals_the_three_pass_form(pfc):
         ss = np.abs(y[3]).max(axis=(1, 2), keepdims=True) + 1e-300
         okw = (np.abs(x[2] - y[2]) <= 1e-8 * sw).all(axis=(1, 2)); oks = (np.abs(x[3] - y[3]) <= 1e-6 * ss).all(axis=(1, 2))
         assert okw.mean() > 0.99 and oks.mean() > 0.98, (okw.mean(), oks.mean())
+
+
+# What each step of test_one_handle_across_the_entry_points left behind: (pfc_last_parts, pfc_last_team, pfc_last_dual_reused,
+# stats[7] = items).  Recorded by running this test's body on the build of the commit before the per-call options moved out of
+# the handle (79824b3): the route an evaluation takes must not depend on what an earlier call on the handle was told.
+ROUTE_STEPS = ("value", "dual", "dual again", "dual third", "dual bp", "dual bp again", "dual without bp", "dual debug",
+               "value after debug", "dual device", "value after device")
+ROUTE_EXPECTED = {
+    "c1": ((0, 1, 0, 4), (0, 1, 0, 4), (0, 1, 0, 4), (0, 1, 1, 4), (0, 1, 0, 4), (0, 1, 0, 4), (0, 1, 0, 4), (1, 0, 0, 4), (0, 1, 0, 4),
+           (0, 1, 0, 4), (0, 1, 0, 4)),
+    "blob2": ((0, 8, 0, 2), (1, 0, 0, 2), (0, 1, 0, 2), (0, 1, 1, 2), (0, 1, 0, 2), (0, 1, 1, 2), (0, 1, 0, 2), (1, 0, 0, 2), (0, 8, 0, 2),
+              (0, 1, 0, 2), (0, 8, 0, 2)),
+}
+
+
+@pytest.mark.parametrize("cfg", ["c1", "blob2"])
+def test_one_handle_across_the_entry_points(pfc, cfg):
+    """One handle through host value, host Dual (three times), Dual with a broadphase pose that changes the candidate set (twice),
+    the same point without it, the two-stage path (option debug), value again, pfc_eval_dual_device + pfc_check, value again:
+    every step against a fresh handle (counts exact, values and partials at the tolerances of
+    test_gpu_scale.py::test_soak_mixed_value_and_dual_on_one_handle), and the route of every step pinned (ROUTE_EXPECTED)."""
+    import torch
+    from test_gpu_multi import _dual_inputs, _nearby_pose
+    C = pfc.configs
+    w = C.c1_boxes() if cfg == "c1" else C.c3_blob_tool(2, n_div_blob=6, n_div_tool=4)
+    n, nd = w.n_items, 6
+    d_pose, d_twist, d_s = _dual_inputs(w, nd, 11)
+    bp = _nearby_pose(w, 5, scale=8e-3 if cfg == "c1" else 2e-2)
+    value_args = (w.pose, w.twist, w.s, w.ins_ids)
+    dual_args = (w.pose, w.twist, w.s, d_pose, d_twist, d_s, w.ins_ids)
+
+    def fresh(dual, debug=0, **kw):
+        f = C.build_scenario(w)
+        f.set_option("debug", debug)
+        out = f.force_all_elastic_intersections_dual(*dual_args, **kw) if dual else f.force_all_elastic_intersections(*value_args)
+        f.close()
+        return out
+
+    ref_value, ref_dual, ref_bp, ref_debug = fresh(False), fresh(True), fresh(True, bp_pose=bp), fresh(True, debug=1)
+    assert not np.array_equal(ref_bp[4], ref_dual[4]), "bp_pose does not change the candidate sets of this scene"
+    m = C.build_scenario(w)
+    route = []
+
+    def step(got, ref):
+        dual = len(ref) == 5
+        assert np.array_equal(got[-1], ref[-1]), (cfg, len(route))
+        for k, tol in ((0, 1e-11), (1, 1e-7), (2, 1e-9), (3, 1e-6)) if dual else ((0, 1e-11), (1, 1e-7)):
+            np.testing.assert_allclose(got[k], ref[k], rtol=tol, atol=tol * max(np.abs(ref[k]).max(), 1e-300), err_msg=f"{cfg} {len(route)} {k}")
+        route.append((m.last_parts(), m.last_team(), int(m.last_dual_reused()), m.stats()["n_items"]))
+
+    step(m.force_all_elastic_intersections(*value_args), ref_value)
+    for _ in range(3):
+        step(m.force_all_elastic_intersections_dual(*dual_args), ref_dual)
+    for _ in range(2):
+        step(m.force_all_elastic_intersections_dual(*dual_args, bp_pose=bp), ref_bp)
+    step(m.force_all_elastic_intersections_dual(*dual_args), ref_dual)
+    m.set_option("debug", 1)
+    step(m.force_all_elastic_intersections_dual(*dual_args), ref_debug)
+    m.set_option("debug", 0)
+    step(m.force_all_elastic_intersections(*value_args), ref_value)
+    dev = torch.device("cuda:0")
+    t = lambda a, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
+    T = [t(w.ins_ids, torch.int32), t(w.pose), t(w.twist), t(w.s), t(d_pose), t(d_twist), t(d_s)]
+    o = [torch.zeros(s, dtype=torch.float64, device=dev) for s in ((n, 6), (n, 6), (n, nd, 6), (n, nd, 6))] + \
+        [torch.zeros((n, 4), dtype=torch.int32, device=dev)]
+    for attempt in range(40):
+        m.eval_dual_device(n, nd, *[x.data_ptr() for x in T], *[x.data_ptr() for x in o], torch.cuda.current_stream().cuda_stream)
+        if m.check() == pfc._lib.OK:
+            break
+    step([x.cpu().numpy() for x in o], ref_dual)
+    step(m.force_all_elastic_intersections(*value_args), ref_value)
+    m.close()
+    print(f"route {cfg}: {tuple(route)!r}")
+    assert len(route) == len(ROUTE_STEPS)
+    for name, got, want in zip(ROUTE_STEPS, route, ROUTE_EXPECTED[cfg]):
+        assert got == want, (cfg, name, got, want)
