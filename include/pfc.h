@@ -437,6 +437,91 @@ int pfc_eval_dual_bodies_device_more(pfc_handle h, int n_items, int n_dir, const
                                      double *d_dpose, double *d_dtwist, double *d_dx_w_r2, double *d_dwrench, double *d_dsdot, void *stream);
 
 /*
+ * Kinematics from joint states: what transform_to_root / twist_wrt_world (src/contact_algorithms_non_friction.jl:109-110,125-126) and
+ * refreshJacobians! (:86-92) give the reference per evaluation -- the bodies' world poses, twists and geometric Jacobians -- formed on
+ * the device from the state vector (q, v), the front of the chain state -> body states -> items -> pfc_eval_device ->
+ * pfc_scatter_generalized_device.  Value path only.
+ *
+ * pfc_set_mechanism gives the tree.  Body b is the successor of joint b; parent[b] lies in [-1, b), -1 is the world, so the order is
+ * topological.  x_p_j (n_body x 12) is the joint's joint_pose -- the frame before the joint in the parent body's frame, R (9,
+ * column-major) then t, pfc_scatter_generalized's packing -- and the body's frame is the joint's frame after.  axis (n_body x 3) is
+ * given in the joint frame and read for revolute and prismatic joints only.  Joint types:
+ */
+#define PFC_JOINT_FIXED 0          /* no coordinates */
+#define PFC_JOINT_REVOLUTE 1       /* 1 q (angle), 1 v */
+#define PFC_JOINT_PRISMATIC 2      /* 1 q (displacement), 1 v */
+#define PFC_JOINT_FLOATING_MRP 3   /* 6 q = [modified Rodrigues parameters (3); translation (3)], 6 v = [omega; v] in the frame after:
+                                      RigidBodyDynamics' SPQuatFloating */
+/*
+ * Coordinate offsets are cumulative in body order (RigidBodyDynamics' tree order when the host numbers bodies in attach order).
+ * Allowed before and after pfc_finalize; a second call replaces the first and takes effect with the next call below, the first of
+ * which uploads the tables (one stream synchronisation).  Multi-device handles keep the tables on their first device.
+ * PFC_ERR_BAD_ARG, the message naming the body: n_body < 1, a parent outside [-1, b), an unknown joint type, a null table, a revolute
+ * or prismatic axis with | |a|^2 - 1 | > 1e-12.  pfc_mechanism_sizes returns n_body, nq, nv (any pointer may be NULL; PFC_ERR_STATE
+ * before pfc_set_mechanism).
+ */
+int pfc_set_mechanism(pfc_handle h, int n_body, const int *parent, const int *joint_type, const double *x_p_j, const double *axis);
+int pfc_mechanism_sizes(pfc_handle h, int *n_body, int *nq, int *nv);
+
+/*
+ * Two kernels enqueued on `stream` (NULL = the handle's own) without a host synchronisation:
+ *   d_q          n_scene x nq             d_v  n_scene x nv (may be NULL when d_twist_w_b is: zeros)
+ *   d_x_w_b      n_scene n_body x 12  OUT world pose of body b of scene s at row s n_body + b, pfc_items_from_bodies_device's d_x_w_b
+ *   d_twist_w_b  n_scene n_body x 6   OUT its twist [angular; linear] in world about the world origin, likewise
+ *   d_jac        n_scene n_body x nv x 6  OUT the geometric Jacobians, pfc_scatter_generalized_device's d_jac for the scene-offset
+ *                body ids pfc_items_from_bodies_device writes
+ * Any OUT pointer may be NULL: it is not written, and the work it alone needs is not launched.  The arithmetic is plain Float64, every
+ * 3-term dot product summed left to right without fma, a translation added last; the world goes through the same expressions with
+ * R = I, t = 0 and a zero twist:
+ *   joint transform X_j(q).  fixed: (I, 0).  prismatic: R = I, t_r = a_r d.
+ *     floating: a2 = (p0 p0 + p1 p1) + p2 p2; den = a2 + 1; w = (1 - a2) / den; x = (2 p0) / den, y, z likewise;
+ *       R00 = ((ww + xx) - yy) - zz   R01 = 2 (xy - zw)             R02 = 2 (xz + yw)
+ *       R10 = 2 (xy + zw)             R11 = ((ww - xx) + yy) - zz   R12 = 2 (yz - xw)
+ *       R20 = 2 (xz - yw)             R21 = 2 (yz + xw)             R22 = ((ww - xx) - yy) + zz;     t = q[3..6)
+ *     revolute: c = cos q, s = sin q, c1 = 1 - c; R_rr = (c1 a_r) a_r + c;
+ *       R10 = (c1 a0) a1 + s a2, R01 = (c1 a0) a1 - s a2;  R20 = (c1 a0) a2 - s a1, R02 = (c1 a0) a2 + s a1;
+ *       R21 = (c1 a1) a2 + s a0, R12 = (c1 a1) a2 - s a0;  t = 0
+ *   pose.  A = x_p_j o X_j: R_A = R_pj R_j, t_A = (R_pj t_j) + t_pj;  x_w_b = x_w_parent o A: R = R_wp R_A, t = (R_wp t_A) + t_wp
+ *   twist.  joint twist in the frame after: floating [omega; v], revolute [a qdot; 0], prismatic [0; a qdot], fixed 0;
+ *     ang_w = R_wb ang_j;  lin_w = (R_wb lin_j) + t_wb x ang_w;  tw_b = tw_parent + [ang_w; lin_w] elementwise
+ *   motion-subspace column of velocity coordinate c, owned by joint b, in world.  floating k < 3: ang = R_wb[:,k], lin = t_wb x ang;
+ *     k >= 3: ang = 0, lin = R_wb[:,k-3];  revolute: ang = R_wb a, lin = t_wb x ang;  prismatic: ang = 0, lin = R_wb a
+ *   Jacobian of body b (the root -> b path of refreshJacobians!): column c is that column if the owning joint lies on the path, +0.0
+ *     six times otherwise.  A body behind fixed joints only gets an all-zero Jacobian (the scatter adds zeros: the reference's
+ *     jac::Nothing for the root).
+ * -- the same bytes on every call, handle and entry point.  The call is NOT an evaluation: a kept value pass, Dual reuse, pfc_check
+ * and pfc_last_* are as they were.  n_scene = 0 is a no-op.  PFC_ERR_STATE before pfc_set_mechanism.  The call keeps the columns in a
+ * handle buffer that grows on demand only: calls on different streams must be ordered by the caller.  Multi-device handles: the first
+ * device.
+ */
+int pfc_kinematics_device(pfc_handle h, int n_scene, const double *d_q, const double *d_v, double *d_x_w_b, double *d_twist_w_b,
+                          double *d_jac, void *stream);
+/* The same with host buffers, synchronous: the same kernels, the same bytes. */
+int pfc_kinematics(pfc_handle h, int n_scene, const double *q, const double *v, double *x_w_b, double *twist_w_b, double *jac);
+
+/*
+ * pfc_kinematics_device, then exactly pfc_eval_bodies_device, then pfc_scatter_generalized_device with accumulate = 0, on one stream,
+ * with n_body and nv of the mechanism: the only per-step upload left is the state vector.  d_f (n_scene x nv) = NULL skips the scatter.
+ * All buffers are the caller's and all are required but d_ins_ids, d_scene, d_s, d_counts (as pfc_eval_bodies_device) and d_f; with d_f
+ * also d_jac, d_x_w_r2, d_body_1 and d_body_2.  pfc_check() afterwards as after pfc_eval_device; on PFC_ERR_OVERFLOW d_f is undefined
+ * and the call is re-issued (the items are formed again, to the same bytes).  States and errors are those of the parts, checked
+ * before anything is launched; PFC_ERR_BAD_ARG if an instruction the items use is bound to a body >= n_body of the mechanism.  There
+ * is no accumulate variant: a host that accumulates calls the parts.
+ */
+int pfc_eval_state_device(pfc_handle h, int n_items, const int *d_ins_ids, const int *d_scene, int n_scene,
+                          const double *d_q, const double *d_v, const double *d_s,
+                          double *d_x_w_b, double *d_twist_w_b, double *d_jac,
+                          double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
+                          double *d_wrench, double *d_sdot, int *d_counts, double *d_f, void *stream);
+/* The host-buffer form: pfc_kinematics, pfc_eval_bodies, pfc_scatter_generalized.  x_w_b, twist_w_b, jac, pose, twist, x_w_r2, body_1,
+ * body_2 are optional OUT arguments (NULL: not returned), and so is f (NULL: no scatter).  Synchronous. */
+int pfc_eval_state(pfc_handle h, int n_items, const int *ins_ids, const int *scene, int n_scene,
+                   const double *q, const double *v, const double *s,
+                   double *x_w_b, double *twist_w_b, double *jac,
+                   double *pose, double *twist, double *x_w_r2, int *body_1, int *body_2,
+                   double *wrench, double *sdot, int *counts, double *f);
+
+/*
  * The contact surface of n_items items: per item what the reference's TractionCache holds after forceAllElasticIntersections!
  * (src/structs.jl; filled by src/contact_algorithms_non_friction.jl:217-265), the clipped polygons it was integrated over, and
  * normal_wrench / normal_wrench_cop (src/contact_algorithms_normal.jl:2-34) -- what test/test_normal.jl:31-41 and

@@ -18,6 +18,7 @@ OK, ERR_NONFINITE, ERR_OVERFLOW, ERR_BAD_ARG, ERR_NOMEM, ERR_HIP, ERR_STATE, ERR
 STATUS_NAMES = {0: "PFC_OK", 1: "PFC_ERR_NONFINITE", 2: "PFC_ERR_OVERFLOW", 3: "PFC_ERR_BAD_ARG", 4: "PFC_ERR_NOMEM",
                 5: "PFC_ERR_HIP", 6: "PFC_ERR_STATE", 7: "PFC_ERR_INVERTED_TET"}
 REGULARIZED, BRISTLE = 0, 1
+JOINT_FIXED, JOINT_REVOLUTE, JOINT_PRISMATIC, JOINT_FLOATING_MRP = range(4)      # PFC_JOINT_*: pfc_set_mechanism's joint types
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -70,6 +71,13 @@ SIGNATURES = {
                                     + [C.c_void_p] * 20),
     "pfc_eval_dual_bodies_device_more": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
                                          + [C.c_void_p] * 11),
+    "pfc_set_mechanism": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _dp, _dp]),
+    "pfc_mechanism_sizes": (C.c_int, [C.c_void_p, _ip, _ip, _ip]),
+    "pfc_kinematics_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6),
+    "pfc_kinematics": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "pfc_eval_state_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 16),
+    "pfc_eval_state": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip,
+                                 _dp, _dp, _ip, _dp]),
     "pfc_build_tree": (C.c_int, [C.c_int, _dp, C.c_int, C.c_int, _ip, _dp, C.c_int, _dp, _dp, _dp, _ip, _ip]),
     "pfc_tree_last_error": (C.c_char_p, []),
     "pfc_scatter_generalized": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _ip, _ip, C.c_int, C.c_int, C.c_int, _dp, _dp]),
@@ -101,7 +109,7 @@ class PFCError(RuntimeError):
 
 def build(force: bool = False) -> str:
     """Compile csrc/pfc_hip.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("pfc_hip.hip", "pfc_tree.cpp", "pfc_sort.hip", "pfc_kernels.h", "pfc_bp.h", "pfc_np.h", "pfc_br.h", "pfc_dual.h", "pfc_fused.h", "pfc_clip.h", "pfc_multi.h", "pfc_sort.h", "pfc_surface.h", "pfc_surface_fric.h", "pfc_scatter.h", "pfc_ljac.h", "pfc_bodies.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("pfc_hip.hip", "pfc_tree.cpp", "pfc_sort.hip", "pfc_kernels.h", "pfc_bp.h", "pfc_np.h", "pfc_br.h", "pfc_dual.h", "pfc_fused.h", "pfc_clip.h", "pfc_multi.h", "pfc_sort.h", "pfc_surface.h", "pfc_surface_fric.h", "pfc_scatter.h", "pfc_ljac.h", "pfc_bodies.h", "pfc_kin.h")]
     srcs.append(os.path.join(os.path.dirname(HERE), "include", "pfc.h"))
     srcs.append(os.path.abspath(__file__))      # the compiler flags live here
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)

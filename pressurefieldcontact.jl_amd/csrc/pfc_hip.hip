@@ -23,6 +23,8 @@
 //   pfc_bodies.h   k_items_from_bodies: pose, twist, x_rw_r2 and body ids of every item from the bodies' world poses and twists
 //                  (pfc_items_from_bodies, pfc_eval_bodies); k_dual_seeds_from_bodies: their partials from the partials of the body
 //                  states (pfc_dual_seeds_from_bodies, pfc_eval_dual_bodies_device[_more])
+//   pfc_kin.h      k_kinematics / k_kin_jacobian: the bodies' world poses, twists and geometric Jacobians from the joint state (q, v)
+//                  of a small tree (pfc_set_mechanism, pfc_kinematics, pfc_eval_state)
 //   pfc_multi.h    host code: multi-device handles (pfc_create_multi)
 // This file: mesh record preparation (k_prep_tri, k_prep_tet), per-item setup (k_setup_items), work-list management,
 // hipGraph capture / replay, the two-half evaluation and every extern "C" entry point.
@@ -194,6 +196,7 @@ __global__ void k_repose(int n_items, const double *__restrict__ pose, ItemRec *
 #include "pfc_scatter.h"
 #include "pfc_ljac.h"
 #include "pfc_bodies.h"
+#include "pfc_kin.h"
 
 }  // namespace pfc
 
@@ -350,6 +353,20 @@ struct Stage {
         for (int k = 0; k < nf && e == hipSuccess; ++k)
             if (f[k].dir & Out) e = fetch(k, f[k].count);
         return e == hipSuccess ? hipStreamSynchronize(st) : e;
+    }
+};
+
+// The mechanism of pfc_set_mechanism, validated and packed: every table k_kinematics / k_kin_jacobian read lies in `blob` at a
+// 256-byte boundary (KinArgs' names), so one copy uploads them.
+struct KinHost {
+    int n_body = 0, nq = 0, nv = 0;
+    std::vector<char> blob;
+    size_t o_jtype = 0, o_qoff = 0, o_voff = 0, o_path_off = 0, o_path = 0, o_x_p_j = 0, o_axis = 0, o_anc = 0;
+    template <class T> size_t put(const std::vector<T> &v) {
+        const size_t off = blob.size(), bytes = sizeof(T) * v.size();
+        blob.resize((off + bytes + 255) & ~(size_t)255);
+        if (bytes) std::memcpy(blob.data() + off, v.data(), bytes);
+        return off;
     }
 };
 
@@ -574,6 +591,11 @@ struct pfc_context {
     std::vector<int> ins_bodies;       // per instruction {body of mesh_1, body of mesh_2} (pfc_set_instruction_bodies); grows with the ids it is given
     DevBuf<int> bodies_bind;           // its device copy, one pair per instruction (kBodiesUnbound where none was given)
     bool bodies_stale = true;          // the device copy is older than ins_bodies: uploaded by the next launch
+    // kinematics from joint states (pfc_kin.h)
+    KinHost kin;                       // the mechanism's tables as pfc_set_mechanism packed them (kin.n_body = 0: none given)
+    DevBuf<char> kin_tab;              // their device copy, one block
+    bool kin_stale = true;             // the device copy is older than kin: uploaded by the next kinematics call
+    DevBuf<double> kin_sw;             // S_w, n_scene x nv x 6: grows on demand only
     DevBuf<unsigned long long> surf_keys[2];
     DevBuf<char> surf_tmp;                            // rocPRIM scan / sort
     PinBuf<long long> h_surf;                         // pinned mirror of surf_out
@@ -3320,6 +3342,213 @@ int pfc_eval_dual_bodies_device_more(pfc_handle h, int n_items, int n_dir, const
                                                      d_dtwist_w_b, d_dpose, d_dtwist, d_dx_w_r2, stream);
     if (rc != PFC_OK) return rc;
     return pfc_eval_dual_device_more(h, n_dir, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, stream);
+}
+
+// ---- kinematics from joint states (pfc_kin.h) -----------------------------------------------------------------------------------
+int pfc_set_mechanism(pfc_handle h, int n_body, const int *parent, const int *joint_type, const double *x_p_j, const double *axis) {
+    if (h && h->multi)      // the tables live with the first device, where the states are formed
+        return on_first_shard(h, [&](pfc_context *c) { return pfc_set_mechanism(c, n_body, parent, joint_type, x_p_j, axis); });
+    if (!h) return PFC_ERR_BAD_ARG;
+    const char *who = "pfc_set_mechanism";
+    if (n_body < 1) return fail(h, PFC_ERR_BAD_ARG, "%s: n_body is %d, a mechanism has at least one body", who, n_body);
+    if (!parent || !joint_type || !x_p_j || !axis) return fail(h, PFC_ERR_BAD_ARG, "%s: null table", who);
+    const size_t nb = (size_t)n_body;
+    std::vector<int> jtype(nb), qoff(nb), voff(nb), path_off(nb + 1, 0), path, depth(nb);
+    int nv = 0;
+    for (int b = 0; b < n_body; ++b) {
+        if (parent[b] < -1 || parent[b] >= b)
+            return fail(h, PFC_ERR_BAD_ARG, "%s: body %d has parent %d, outside [-1, %d)", who, b, parent[b], b);
+        const int t = joint_type[b];
+        if (t != PFC_JOINT_FIXED && t != PFC_JOINT_REVOLUTE && t != PFC_JOINT_PRISMATIC && t != PFC_JOINT_FLOATING_MRP)
+            return fail(h, PFC_ERR_BAD_ARG, "%s: body %d has the unknown joint type %d", who, b, t);
+        if (t == PFC_JOINT_REVOLUTE || t == PFC_JOINT_PRISMATIC) {
+            const double *a = axis + 3 * (size_t)b;
+            const double n2 = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2];
+            if (!(std::fabs(n2 - 1.0) <= 1e-12))
+                return fail(h, PFC_ERR_BAD_ARG, "%s: body %d's joint axis is not a unit vector (|a|^2 = %.17g)", who, b, n2);
+        }
+        jtype[b] = t; qoff[b] = voff[b] = nv;      // nq = nv for every joint type here
+        nv += kin_joint_nq(t);
+        depth[b] = parent[b] < 0 ? 1 : depth[parent[b]] + 1;
+        path_off[b + 1] = path_off[b] + depth[b];
+    }
+    path.resize((size_t)path_off[nb]);
+    std::vector<unsigned char> anc(nb * (size_t)nv, 0);
+    for (int b = 0; b < n_body; ++b) {
+        int k = path_off[b + 1];
+        for (int a = b; a >= 0; a = parent[a]) {
+            path[--k] = a;
+            for (int c = 0; c < kin_joint_nq(jtype[a]); ++c) anc[(size_t)b * nv + voff[a] + c] = 1;
+        }
+    }
+    KinHost &K = h->kin;
+    K.blob.clear();
+    K.o_jtype = K.put(jtype); K.o_qoff = K.put(qoff); K.o_voff = K.put(voff); K.o_path_off = K.put(path_off); K.o_path = K.put(path);
+    K.o_x_p_j = K.put(std::vector<double>(x_p_j, x_p_j + 12 * nb)); K.o_axis = K.put(std::vector<double>(axis, axis + 3 * nb));
+    K.o_anc = K.put(anc);
+    K.n_body = n_body; K.nq = nv; K.nv = nv;
+    h->kin_stale = true;
+    return PFC_OK;
+}
+
+int pfc_mechanism_sizes(pfc_handle h, int *n_body, int *nq, int *nv) {
+    if (h && h->multi) return on_first_shard(h, [&](pfc_context *c) { return pfc_mechanism_sizes(c, n_body, nq, nv); });
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->kin.n_body == 0) return fail(h, PFC_ERR_STATE, "pfc_mechanism_sizes before pfc_set_mechanism");
+    if (n_body) *n_body = h->kin.n_body;
+    if (nq) *nq = h->kin.nq;
+    if (nv) *nv = h->kin.nv;
+    return PFC_OK;
+}
+
+// Argument and state checks of both forms of pfc_kinematics.
+static int kin_check_args(pfc_context *h, const char *who, int n_scene, const double *q, const double *v, bool want_twist) {
+    if (h->kin.n_body == 0) return fail(h, PFC_ERR_STATE, "%s before pfc_set_mechanism", who);
+    if (n_scene < 0) return fail(h, PFC_ERR_BAD_ARG, "%s: negative n_scene", who);
+    if (n_scene == 0) return PFC_OK;
+    if (h->kin.nq > 0 && (!q || (want_twist && !v))) return fail(h, PFC_ERR_BAD_ARG, "%s: null state vector", who);
+    if (((long long)n_scene * h->kin.n_body * std::max(h->kin.nv, 1) + kKinJacBlock - 1) / kKinJacBlock >= (1ll << 31))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: n_scene n_body nv must be below 2^39", who);
+    return PFC_OK;
+}
+
+// The tables' upload on st if they are stale (one synchronisation per pfc_set_mechanism, as bodies_upload_bind), S_w grown if a
+// Jacobian is wanted and too small, and the kernels, on st.  Every pointer is a device pointer; an output that is null is not
+// written, and the kernel only it needs is not launched.
+static int kin_launch(pfc_context *h, int n_scene, const double *q, const double *v, double *x_w_b, double *twist_w_b, double *jac,
+                      hipStream_t st) {
+    const KinHost &K = h->kin;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (h->kin_stale) {
+        HIP_TRY(h, h->kin_tab.ensure(K.blob.size()));
+        HIP_TRY(h, hipMemcpyAsync(h->kin_tab.p, K.blob.data(), K.blob.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        h->kin_stale = false;
+    }
+    const bool want_jac = jac && K.nv > 0;
+    if (!x_w_b && !twist_w_b && !want_jac) return PFC_OK;
+    if (want_jac) HIP_TRY(h, h->kin_sw.ensure((size_t)n_scene * K.nv * 6));
+    const char *t = h->kin_tab.p;
+    KinArgs a;
+    a.n_scene = n_scene; a.n_body = K.n_body; a.nq = K.nq; a.nv = K.nv;
+    a.jtype = (const int *)(t + K.o_jtype); a.qoff = (const int *)(t + K.o_qoff); a.voff = (const int *)(t + K.o_voff);
+    a.path_off = (const int *)(t + K.o_path_off); a.path = (const int *)(t + K.o_path);
+    a.x_p_j = (const double *)(t + K.o_x_p_j); a.axis = (const double *)(t + K.o_axis); a.anc = (const unsigned char *)(t + K.o_anc);
+    a.q = q; a.v = v; a.x_w_b = x_w_b; a.twist_w_b = twist_w_b; a.S_w = want_jac ? h->kin_sw.p : nullptr; a.jac = jac;
+    const long long lanes = (long long)n_scene * K.n_body;
+    hipLaunchKernelGGL(k_kinematics, dim3((unsigned)((lanes + kKinWave - 1) / kKinWave)), dim3(kKinWave), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    if (want_jac) {
+        const long long tot = lanes * K.nv;
+        hipLaunchKernelGGL(k_kin_jacobian, dim3((unsigned)((tot + kKinJacBlock - 1) / kKinJacBlock)), dim3(kKinJacBlock), 0, st, a);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return PFC_OK;
+}
+
+int pfc_kinematics_device(pfc_handle h, int n_scene, const double *d_q, const double *d_v, double *d_x_w_b, double *d_twist_w_b,
+                          double *d_jac, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_kinematics_device(c, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_jac, stream); });
+    const int rc = kin_check_args(h, "pfc_kinematics_device", n_scene, d_q, d_v, d_twist_w_b != nullptr);
+    if (rc != PFC_OK || n_scene == 0) return rc;
+    return kin_launch(h, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_jac, stream ? (hipStream_t)stream : h->stream);
+}
+
+int pfc_kinematics(pfc_handle h, int n_scene, const double *q, const double *v, double *x_w_b, double *twist_w_b, double *jac) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) { return pfc_kinematics(c, n_scene, q, v, x_w_b, twist_w_b, jac); });
+    int rc = kin_check_args(h, "pfc_kinematics", n_scene, q, v, twist_w_b != nullptr);
+    if (rc != PFC_OK || n_scene == 0) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t ns = (size_t)n_scene, nb = ns * h->kin.n_body;
+    Stage sg(h->stage, h->stream);
+    const int k_q = sg.in(q, ns * h->kin.nq), k_v = sg.in(v, ns * h->kin.nv);
+    const int k_x = sg.out(x_w_b, nb * 12), k_tw = sg.out(twist_w_b, nb * 6), k_j = sg.out(jac, nb * h->kin.nv * 6);
+    HIP_TRY(h, sg.commit());
+    rc = kin_launch(h, n_scene, sg.at<double>(k_q), sg.at<double>(k_v), sg.at<double>(k_x), sg.at<double>(k_tw), sg.at<double>(k_j), sg.st);
+    if (rc != PFC_OK) return rc;
+    HIP_TRY(h, sg.finish());
+    return PFC_OK;
+}
+
+// What both forms of pfc_eval_state check before anything is launched or written: the mechanism, the scenario, and the bodies of the
+// instructions against the mechanism's n_body (device form: bodies_check_bound_device; host form: the ids themselves).
+static int eval_state_check(pfc_context *c, const char *who, int n_items, const int *ins_ids, const int *scene, int n_scene, bool host,
+                            const double *q, const double *v) {
+    if (c->kin.n_body == 0) return fail(c, PFC_ERR_STATE, "%s before pfc_set_mechanism", who);
+    if (!c->finalized) return fail(c, PFC_ERR_STATE, "%s before pfc_finalize", who);
+    if (n_items < 0 || n_scene < 1) return fail(c, PFC_ERR_BAD_ARG, "%s: n_items >= 0, n_scene >= 1", who);
+    int rc = kin_check_args(c, who, n_scene, q, v, true);
+    if (rc != PFC_OK) return rc;
+    if (!ins_ids && n_items > (int)c->ins.size())
+        return fail(c, PFC_ERR_BAD_ARG, "%s: n_items exceeds the number of instructions and no ins_ids given", who);
+    if (n_items == 0) return PFC_OK;
+    return host ? bodies_check_ids_host(c, who, n_items, ins_ids, scene, n_scene, c->kin.n_body)
+                : bodies_check_bound_device(c, who, n_items, ins_ids, c->kin.n_body);
+}
+
+int pfc_eval_state_device(pfc_handle h, int n_items, const int *d_ins_ids, const int *d_scene, int n_scene,
+                          const double *d_q, const double *d_v, const double *d_s,
+                          double *d_x_w_b, double *d_twist_w_b, double *d_jac,
+                          double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
+                          double *d_wrench, double *d_sdot, int *d_counts, double *d_f, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    const char *who = "pfc_eval_state_device";
+    pfc_context *c = h->multi ? h->multi->shard[0] : h;
+    int rc = on_shard(h, c, [&](pfc_context *c1) { return eval_state_check(c1, who, n_items, d_ins_ids, d_scene, n_scene, false, d_q, d_v); });
+    if (rc != PFC_OK) return rc;
+    const int n_body = c->kin.n_body, nv = c->kin.nv;
+    const bool scatter = d_f && nv > 0;
+    if (!d_x_w_b || !d_twist_w_b || !d_pose || !d_twist || !d_wrench || !d_sdot ||
+        (scatter && (!d_jac || !d_x_w_r2 || !d_body_1 || !d_body_2)))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    if ((rc = pfc_kinematics_device(h, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_jac, stream)) != PFC_OK) return rc;
+    rc = pfc_eval_bodies_device(h, n_items, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_s, d_pose, d_twist, d_x_w_r2,
+                                d_body_1, d_body_2, d_wrench, d_sdot, d_counts, stream);
+    if (rc != PFC_OK || !scatter) return rc;
+    return pfc_scatter_generalized_device(h, n_items, d_wrench, d_x_w_r2, d_body_1, d_body_2, d_scene, n_scene, nv, d_jac, d_f, 0, stream);
+}
+
+int pfc_eval_state(pfc_handle h, int n_items, const int *ins_ids, const int *scene, int n_scene,
+                   const double *q, const double *v, const double *s,
+                   double *x_w_b, double *twist_w_b, double *jac,
+                   double *pose, double *twist, double *x_w_r2, int *body_1, int *body_2,
+                   double *wrench, double *sdot, int *counts, double *f) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    const char *who = "pfc_eval_state";
+    pfc_context *c = h->multi ? h->multi->shard[0] : h;
+    int rc = on_shard(h, c, [&](pfc_context *c1) { return eval_state_check(c1, who, n_items, ins_ids, scene, n_scene, true, q, v); });
+    if (rc != PFC_OK) return rc;
+    if (n_items > 0 && (!wrench || !sdot)) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    const int n_body = c->kin.n_body, nv = c->kin.nv;
+    const bool scatter = f && nv > 0;
+    const size_t n = (size_t)n_items, nb = (size_t)n_scene * n_body;
+    std::vector<double> tmp;      // the intermediate buffers the caller did not ask for
+    std::vector<int> itmp;
+    {
+        size_t need = (x_w_b ? 0 : nb * 12) + (twist_w_b ? 0 : nb * 6);
+        if (scatter) need += (jac ? 0 : nb * nv * 6) + (x_w_r2 ? 0 : n * 12);
+        tmp.resize(need);
+        double *p = tmp.data();
+        if (!x_w_b) { x_w_b = p; p += nb * 12; }
+        if (!twist_w_b) { twist_w_b = p; p += nb * 6; }
+        if (scatter && !jac) { jac = p; p += nb * nv * 6; }
+        if (scatter && !x_w_r2) { x_w_r2 = p; p += n * 12; }
+        if (scatter && (!body_1 || !body_2)) {
+            itmp.resize(2 * n);
+            if (!body_1) body_1 = itmp.data();
+            if (!body_2) body_2 = itmp.data() + n;
+        }
+    }
+    if ((rc = pfc_kinematics(h, n_scene, q, v, x_w_b, twist_w_b, jac)) != PFC_OK) return rc;
+    rc = pfc_eval_bodies(h, n_items, ins_ids, scene, n_scene, n_body, x_w_b, twist_w_b, s, pose, twist, x_w_r2, body_1, body_2, wrench, sdot,
+                         counts);
+    if (rc != PFC_OK || !scatter) return rc;
+    return pfc_scatter_generalized(h, n_items, wrench, x_w_r2, body_1, body_2, scene, n_scene, n_scene * n_body, nv, jac, f);
 }
 
 // The Dual evaluation, with the broadphase pose of m.float's state where bp_pose is given (calcTriTetIntersections!,

@@ -338,6 +338,7 @@ class MechanismScenario:
         self._h = None
         self._finalized = False
         self._ins_bodies = {}        # bindings made before finalize(): the handle does not exist yet
+        self._mechanism = None       # set_mechanism's tables, likewise
 
     # ---- scenario construction ---------------------------------------------------------------------------------
     def add_contact(self, name: str, e_mesh: EMesh, c_prop: Optional[ContactProperties] = None,
@@ -455,6 +456,41 @@ class MechanismScenario:
         self._finalized = True
         for ins, (b1, b2) in self._ins_bodies.items():
             self._check(L.pfc_set_instruction_bodies(h, ins, b1, b2))
+        if self._mechanism is not None:
+            self._send_mechanism()
+
+    def set_mechanism(self, parent, joint_type, x_p_j, axis=None):
+        """pfc_set_mechanism: the tree the kinematics calls below evaluate.  Body b is the successor of joint b; parent (n_body,) in
+        [-1, b), -1 the world; joint_type (n_body,) of _lib.JOINT_FIXED / JOINT_REVOLUTE / JOINT_PRISMATIC / JOINT_FLOATING_MRP;
+        x_p_j (n_body,12) the joint_pose, R column-major then t; axis (n_body,3) in the joint frame (None: no revolute or prismatic
+        joint).  Before or after finalize(); a second call replaces the first."""
+        parent = np.ascontiguousarray(parent, dtype=np.int32).reshape(-1)
+        n_body = parent.size
+        joint_type = np.ascontiguousarray(joint_type, dtype=np.int32).reshape(-1)
+        x_p_j = np.ascontiguousarray(x_p_j, dtype=np.float64).reshape(-1)
+        axis = np.zeros(3 * n_body) if axis is None else np.ascontiguousarray(axis, dtype=np.float64).reshape(-1)
+        if joint_type.size != n_body or x_p_j.size != 12 * n_body or axis.size != 3 * n_body:
+            raise ValueError("set_mechanism: one parent, joint type, joint_pose (12) and axis (3) per body")
+        mech = (n_body, parent, joint_type, x_p_j, axis)
+        if not self._finalized:
+            self._mechanism = mech      # sent by finalize(): the library validates it there
+            return
+        self._send_mechanism(mech)
+
+    def _send_mechanism(self, mech=None):
+        n_body, parent, joint_type, x_p_j, axis = mech or self._mechanism
+        L = _lib.lib()
+        self._check(L.pfc_set_mechanism(self._h, n_body, parent.ctypes.data_as(_ip), joint_type.ctypes.data_as(_ip),
+                                        x_p_j.ctypes.data_as(_dp), axis.ctypes.data_as(_dp)))
+        self._mechanism = mech or self._mechanism
+
+    def mechanism_sizes(self):
+        """pfc_mechanism_sizes: (n_body, nq, nv) of the mechanism the library holds."""
+        if not self._finalized:
+            raise RuntimeError("finalize the scenario first")
+        nb, nq, nv = C.c_int(), C.c_int(), C.c_int()
+        self._check(_lib.lib().pfc_mechanism_sizes(self._h, C.byref(nb), C.byref(nq), C.byref(nv)))
+        return nb.value, nq.value, nv.value
 
     def set_instruction_bodies(self, ins: int, body_1: int, body_2: int):
         """pfc_set_instruction_bodies: instruction `ins` (0-based, the order of the add_friction_* calls) acts between body_1 (of
@@ -796,6 +832,61 @@ class MechanismScenario:
                                                       d_x_w_b or None, d_twist_w_b or None, d_s or None, d_pose, d_twist, d_x_w_r2 or None,
                                                       d_body_1 or None, d_body_2 or None, d_wrench, d_sdot, d_counts or None, stream or None))
 
+    def _state_arrays(self, q, v):
+        """(n_scene, n_body, nv, q (n_scene,nq), v (n_scene,nv)) for the mechanism the library holds."""
+        n_body, nq, nv = self.mechanism_sizes()
+        q_a = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, nq) if nq else np.zeros((np.shape(q)[0] if np.ndim(q) == 2 else 1, 0))
+        v_a = np.ascontiguousarray(v, dtype=np.float64).reshape(q_a.shape[0], nv)
+        return q_a.shape[0], n_body, nv, q_a, v_a
+
+    def kinematics(self, q, v, want_jac: bool = True):
+        """The bodies' world poses, twists and geometric Jacobians from the joint state (pfc_kinematics, host buffers, synchronous).
+        q (nq,) or (n_scene,nq), v likewise with nv, in the coordinate order of set_mechanism's bodies.  Returns x_w_b
+        (n_scene,n_body,12), twist_w_b (n_scene,n_body,6) and jac (n_scene n_body, nv, 6) (None without want_jac): the inputs of
+        items_from_bodies and of scatter_generalized."""
+        n_scene, n_body, nv, q_a, v_a = self._state_arrays(q, v)
+        x = np.zeros((n_scene, n_body, 12)); tw = np.zeros((n_scene, n_body, 6))
+        jac = np.zeros((n_scene * n_body, nv, 6)) if want_jac else None
+        self._check(_lib.lib().pfc_kinematics(self._h, n_scene, q_a.ctypes.data_as(_dp), v_a.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
+                                              tw.ctypes.data_as(_dp), jac.ctypes.data_as(_dp) if want_jac else None))
+        return x, tw, jac
+
+    def kinematics_device(self, n_scene: int, d_q: int, d_v: int, d_x_w_b: int, d_twist_w_b: int, d_jac: int, stream: int = 0):
+        """pfc_kinematics_device: raw device addresses (0: NULL for any output not wanted); asynchronous on `stream`, not an
+        evaluation, no check() needed."""
+        self._check(_lib.lib().pfc_kinematics_device(self._h, int(n_scene), d_q or None, d_v or None, d_x_w_b or None, d_twist_w_b or None,
+                                                     d_jac or None, stream or None))
+
+    def force_all_elastic_intersections_state(self, q, v, s=None, ins_ids: Optional[Sequence[int]] = None, scene=None):
+        """kinematics, force_all_elastic_intersections_bodies and scatter_generalized in one call (pfc_eval_state, host buffers,
+        synchronous): from the joint state to f_generalized.  q, v as kinematics; s, ins_ids, scene as
+        force_all_elastic_intersections_bodies.  Returns (wrench (n,6), sdot (n,6), counts (n,4), f (n_scene,nv), items: BodyItems,
+        (x_w_b, twist_w_b, jac))."""
+        n_scene, n_body, nv, q_a, v_a = self._state_arrays(q, v)
+        x = np.zeros((n_scene, n_body, 12)); tw = np.zeros((n_scene, n_body, 6)); jac = np.zeros((n_scene * n_body, nv, 6))
+        n, head, it, outs, keep = self._bodies_call(x, tw, ins_ids, scene)
+        s_p = None
+        if s is not None:
+            s_a, s_p = _d(s)
+            if s_a.size != 6 * n:
+                raise ValueError("s must have 6 entries per item")
+        wrench = np.zeros((n, 6)); sdot = np.zeros((n, 6)); counts = np.zeros((n, 4), dtype=np.int32); f = np.zeros((n_scene, nv))
+        self._check(_lib.lib().pfc_eval_state(self._h, n, head[2], head[3], n_scene, q_a.ctypes.data_as(_dp), v_a.ctypes.data_as(_dp), s_p,
+                                              x.ctypes.data_as(_dp), tw.ctypes.data_as(_dp), jac.ctypes.data_as(_dp), *outs,
+                                              wrench.ctypes.data_as(_dp), sdot.ctypes.data_as(_dp), counts.ctypes.data_as(_ip),
+                                              f.ctypes.data_as(_dp)))
+        return wrench, sdot, counts, f, it, (x, tw, jac)
+
+    def eval_state_device(self, n_items: int, d_ins_ids: int, d_scene: int, n_scene: int, d_q: int, d_v: int, d_s: int, d_x_w_b: int,
+                          d_twist_w_b: int, d_jac: int, d_pose: int, d_twist: int, d_x_w_r2: int, d_body_1: int, d_body_2: int,
+                          d_wrench: int, d_sdot: int, d_counts: int, d_f: int, stream: int = 0):
+        """pfc_eval_state_device: kinematics_device, eval_bodies_device and scatter_generalized_device (d_f 0: no scatter) on one
+        stream; asynchronous, follow with check() (re-issue on ERR_OVERFLOW)."""
+        self._check(_lib.lib().pfc_eval_state_device(self._h, int(n_items), d_ins_ids or None, d_scene or None, int(n_scene), d_q or None,
+                                                     d_v or None, d_s or None, d_x_w_b or None, d_twist_w_b or None, d_jac or None,
+                                                     d_pose or None, d_twist or None, d_x_w_r2 or None, d_body_1 or None, d_body_2 or None,
+                                                     d_wrench or None, d_sdot or None, d_counts or None, d_f or None, stream or None))
+
     def dual_seeds_from_bodies(self, x_w_b, twist_w_b, d_x_w_b, d_twist_w_b, ins_ids: Optional[Sequence[int]] = None,
                                scene=None) -> BodySeeds:
         """The Dual seeds of items_from_bodies' items from the partials of the bodies' world states (pfc_dual_seeds_from_bodies, host
@@ -1057,6 +1148,57 @@ def relative_twist(R_w2, t_w2, twist_w1, twist_w2) -> np.ndarray:
     ang = R @ tw[:3]
     lin = R @ tw[3:] + np.cross(t, ang)
     return np.concatenate([ang, lin])
+
+
+def _hat(a) -> np.ndarray:
+    return np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+
+
+def joint_kinematics(parent, joint_type, x_p_j, axis, q, v):
+    """World poses, twists and geometric Jacobians of a tree's bodies from its joint state: transform_to_root, twist_wrt_world and
+    refreshJacobians! (src/contact_algorithms_non_friction.jl:86-92,109-110,125-126) in NumPy, for one scene -- the matrix
+    formulation (4x4 homogeneous products, 6x6 adjoints, Rodrigues' formula), deliberately not the scalar statement of
+    pfc_kinematics, which the tests compare with it.  Arguments as MechanismScenario.set_mechanism, q (nq,), v (nv,).
+    Returns x_w_b (n_body,12), twist_w_b (n_body,6), jac (n_body,nv,6)."""
+    parent = np.asarray(parent, dtype=np.int64).reshape(-1)
+    n_body = parent.size
+    joint_type = np.asarray(joint_type, dtype=np.int64).reshape(-1)
+    x_p_j = np.asarray(x_p_j, dtype=np.float64).reshape(n_body, 12)
+    axis = np.zeros((n_body, 3)) if axis is None else np.asarray(axis, dtype=np.float64).reshape(n_body, 3)
+    ndof = [{_lib.JOINT_FIXED: 0, _lib.JOINT_REVOLUTE: 1, _lib.JOINT_PRISMATIC: 1, _lib.JOINT_FLOATING_MRP: 6}[int(t)] for t in joint_type]
+    off = np.concatenate([[0], np.cumsum(ndof)]).astype(int)
+    nv = int(off[-1])
+    q = np.asarray(q, dtype=np.float64).reshape(nv); v = np.asarray(v, dtype=np.float64).reshape(nv)
+    H, tw, J = [None] * n_body, np.zeros((n_body, 6)), np.zeros((n_body, nv, 6))
+    for b in range(n_body):
+        qb, vb, a = q[off[b]:off[b + 1]], v[off[b]:off[b + 1]], axis[b]
+        Xj, S = np.eye(4), np.zeros((6, ndof[b]))
+        if joint_type[b] == _lib.JOINT_REVOLUTE:
+            K = _hat(a)
+            Xj[:3, :3] = np.eye(3) + np.sin(qb[0]) * K + (1.0 - np.cos(qb[0])) * (K @ K)
+            S[:3, 0] = a
+        elif joint_type[b] == _lib.JOINT_PRISMATIC:
+            Xj[:3, 3] = a * qb[0]
+            S[3:, 0] = a
+        elif joint_type[b] == _lib.JOINT_FLOATING_MRP:
+            p, P = qb[:3], _hat(qb[:3])
+            p2 = float(p @ p)
+            Xj[:3, :3] = np.eye(3) + (4.0 * (1.0 - p2) * P + 8.0 * (P @ P)) / (1.0 + p2) ** 2
+            Xj[:3, 3] = qb[3:]
+            S = np.eye(6)
+        Xp = np.eye(4)
+        Xp[:3, :3] = x_p_j[b, :9].reshape(3, 3, order="F"); Xp[:3, 3] = x_p_j[b, 9:]
+        H[b] = (H[parent[b]] if parent[b] >= 0 else np.eye(4)) @ Xp @ Xj
+        R, t = H[b][:3, :3], H[b][:3, 3]
+        Ad = np.zeros((6, 6))      # a motion vector [angular; linear] of the body frame in world about the world origin
+        Ad[:3, :3] = R; Ad[3:, 3:] = R; Ad[3:, :3] = _hat(t) @ R
+        Sw = Ad @ S
+        tw[b] = (tw[parent[b]] if parent[b] >= 0 else 0.0) + Sw @ vb
+        if parent[b] >= 0:
+            J[b] = J[parent[b]]
+        J[b, off[b]:off[b + 1]] = Sw.T
+    x = np.array([np.concatenate([h[:3, :3].reshape(-1, order="F"), h[:3, 3]]) for h in H])
+    return x, tw, J
 
 
 def local_jacobian_tangent(L, pose) -> np.ndarray:
