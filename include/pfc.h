@@ -191,7 +191,8 @@ int pfc_eval_dual_device_bp(pfc_handle h, int n_items, int n_dir, const int *d_i
  * results of that evaluation's value pass are reused, its value outputs are not written again.  n_dir may differ from the
  * first call.  Requires that pfc_check() returned PFC_OK for that evaluation and that nothing else was evaluated on the
  * handle since (PFC_ERR_STATE otherwise); follow with pfc_check() (synchronises; no speculation: it cannot ask for a
- * re-issue).  pfc_eval_dual applies the same reuse by itself when the value inputs of a call equal, bit for bit, those
+ * re-issue).  An evaluation of zero items through a device-pointer entry point is an evaluation too: it drops an unchecked
+ * call and ends this reuse, on single- and multi-device handles alike.  pfc_eval_dual applies the same reuse by itself when the value inputs of a call equal, bit for bit, those
  * of the previous call (option "dual_reuse", default 1).
  */
 int pfc_eval_dual_device_more(pfc_handle h, int n_dir, const double *d_dpose, const double *d_dtwist, const double *d_ds,

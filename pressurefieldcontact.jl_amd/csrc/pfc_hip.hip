@@ -43,6 +43,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/pfc.h"
@@ -444,8 +445,6 @@ struct pfc_context {
     int bar_state = 0;                            // 0: not probed, 1: in use, -1: no large BAR / allocation failed / PFC_NO_BAR_INPUTS
     PinBuf<char, 2> pin_din, pin_dout;            // pinned blocks of the small-scene Dual path (partials in / out)
     long long dual_hint = -1;                     // contributing pairs of the last Dual evaluation (-1: none yet)
-    bool pending_dual = false;                    // pfc_eval_dual_device enqueued: pfc_check also checks the speculative polygon capacity
-    bool pending_dual_hyb = false;                // ... through the small-scene kernel (value pass + hand-over) and the batched Dual passes
     int dual_dev_hyb_skip = 0;                    // evaluations for which pfc_eval_dual_device leaves that path alone after a miss
     // The kept pass: the value pass the device lists hold, reused by further Dual evaluations at the same point (the chunks of
     // one Jacobian, src/radau/radau_functions.jl:2-14).  Recorded by pfc_check after pfc_eval_dual_device (Batched: the batched
@@ -457,6 +456,17 @@ struct pfc_context {
         bool ids = false;                         // ... given by ins_ids
     } kept;
     bool device_kept() const { return kept.kind == KeptPass::Batched || kept.kind == KeptPass::HandOver; }   // pfc_eval_dual_device_more may follow
+    // The pending call: what is enqueued and not checked yet.  Set whole by the site that enqueues (begin), reset whole by drop_pending
+    // (an entry point replaces it unchecked) and by the check_* that drain() dispatches to.  A twin keeps one of its own for its half.
+    struct Pending {
+        enum Kind { None, Batched, Fused, More, Surface } kind = None;   // a batched value pass, a small-scene launch, Dual passes on a kept pass (_more, pfc_local_jacobian_device), a surface call
+        hipStream_t stream = nullptr;             // the stream it was enqueued on
+        int split_n0 = 0, n_ctr = 0;              // Batched: items in the first half of a split evaluation (0: not split); Surface: its counter count
+        // a pfc_eval_dual_device rides on the value pass -- Batched: the batched route, Fused: the small-scene kernel's hand-over -- and
+        // pfc_check judges its speculation: directions, speculative polygon capacity, ins_ids given (the kept pass it records)
+        enum Dual { NoDual, DualBatched, DualHandOver } dual = NoDual;
+        int n_dir = 0; size_t dpcap = 0; bool ids = false;
+    } pend;
     // What a pinned input block holds: the value inputs (pose | twist | s, n x 36 doubles; the ids ids_at doubles in) of n items
     // (0: nothing to compare with), of the value pass with that value_serial
     struct HostPoint {
@@ -467,14 +477,10 @@ struct pfc_context {
     };
     HostPoint pin_in_pt;                          // pin_in: a small-scene Dual evaluation's (a repeat of its point goes to the hybrid path)
     HostPoint pin_din_pt;                         // pin_din / pin_dout: the one-sync path's evaluation (inputs, seeds; outputs)
-    bool pending_more = false;                    // pfc_eval_dual_device_more enqueued: pfc_check only synchronises
     bool last_dual_reused = false;                // the last Dual evaluation ran on a reused value pass (pfc_last_dual_reused)
     int opt_dual_reuse = 1;
     unsigned long long value_serial = 0;          // bumped by every value pass that overwrites the device lists (new_value_pass)
     std::vector<int> dual_counts_cache;           // the per-item counters of pin_din_pt's evaluation
-    size_t pending_dpcap = 0;
-    int pending_ndir = 0;
-    bool pending_ids = false;                     // the pending pfc_eval_dual_device evaluation has ins_ids (the kept pass pfc_check records)
     DevBuf<double> dual_zero;                     // zeros standing in for a null d_ds
     unsigned long long epoch = 0;        // bumped whenever a device work buffer is reallocated
     // captured launch sequence (hipGraph) of the last evaluation shape
@@ -496,8 +502,6 @@ struct pfc_context {
     DevBuf<double> h_pose;               // device mirror of pfc_eval's pinned input block (pose | twist | s | ins_ids)
     // last evaluation
     int last_n_items = 0, last_levels = 0, last_bfs_levels = 0;
-    bool pending = false;
-    hipStream_t last_stream = nullptr;
     long long stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     DevBuf<double> dual_in, dual_acc, dual_res, dual_out, dual_poly;   // pfc_eval_dual
     DevBuf<int2> dual_pkey;
@@ -572,11 +576,10 @@ struct pfc_context {
     PinBuf<int> h_emit;                // pinned mirror
     PinBuf<unsigned> h_more;           // pinned: status word of the Dual passes of pfc_eval_dual_device_more (device word: status.p + 1)
     int dual_fused_skip = 0;           // Dual evaluations left for which the in-kernel Dual passes stay off (an item had too many polygons)
-    bool pending_fused = false, last_fused = false;
+    bool last_fused = false;
     int opt_split_min = 1025;          // 0: never split.  (Paired sweeps at the end of round 2: 1 024 poses -- one seed per resident broadphase workgroup -- 0.80 ms unsplit / 0.90 split; 1 100 0.95 / 0.93, 1 280 1.09 / 1.01, 2 048 1.50 / 1.28.)
     int opt_clip_min = 384;            // items per launch from which the narrowphase runs as clip-only kernel + k_integ; 0: never.  (End of round 3, k_clip_queue for every such launch, scripts/sweep_clip_min.py: full-size C3 poses 256: 405 vs 405 us one-kernel / split, 400: 518 vs 502, 511: 598 vs 568; 400 box-on-plane scenes 120 vs 123 -- 384, was 512.)  (First set at 1 024 from scripts/sweep_clip.sh; a paired sweep with the final kernels: 512 poses 0.61 vs 0.63 ms, 768 0.80 vs 0.83, 1 536 as 2 x 768 1.14 vs 1.19, 1 920 1.33 vs 1.40; 384 poses and below are indifferent.)
     int opt_poison = 0;                // diagnostic: fill (re)allocated work lists with 0xFF bytes (item index -1)
-    int split_n0 = 0;                  // items in the first half of the pending evaluation (0: not split)
     int last_parts = 1;                // 2 if the last checked evaluation ran as two halves
     Event ev_fork, ev_join, ev_join0;
     int twin_queue_fallback = 0;         // make_twin: 0 the two streams run side by side as created; 1 the twin's stream was re-created with another priority because they did not; 2 they still do not
@@ -599,10 +602,8 @@ struct pfc_context {
     DevBuf<unsigned long long> surf_keys[2];
     DevBuf<char> surf_tmp;                            // rocPRIM scan / sort
     PinBuf<long long> h_surf;                         // pinned mirror of surf_out
-    bool pending_surface = false;
     bool surf_whole_list = false;       // an item had more candidates than the segment sort takes: the whole list is sorted from then on
     bool surf_cap_short = false;        // the last checked surface call failed only for the caller's capacities
-    int surf_n_ctr = 0;
     long long surf_cap_poly = 0, surf_cap_trac = 0;   // capacities of the pending call
     size_t surf_hcap_poly = 0, surf_hcap_trac = 0;    // host-pointer form: its outputs are staged for this many polygons / traction points
     // pfc_contact_surface_fric (pfc_surface_fric.h): per item the moment and friction records of its waves and eig_item's block
@@ -681,8 +682,18 @@ struct PassOpts {
 // Kept Dual polygons for up to `pairs` contributing pairs: a wave of k_narrow_dual takes 64 / n_dir pairs and owns 64 slots
 // (option fixed_order: the same bound sizes the record list of the passes' sums, for every model) ...
 size_t dual_poly_cap(const pfc_context *h, int n_dir, size_t pairs) { return (h->any_bristle || h->opt_fixed_order) ? ((pairs + 64 / n_dir - 1) / (64 / n_dir)) * 64 + 64 : 64; }
-// ... and whether the pairs a value pass turned out to have fit the capacity its Dual passes were enqueued with.
-bool dual_pairs_fit(const pfc_context *h, int n_dir, long long pairs, size_t dpcap) { return dual_poly_cap(h, n_dir, (size_t)pairs) <= dpcap; }
+// ... and whether the pairs a checked value pass turned out to have fit the capacity its Dual passes were enqueued with ...
+int dual_spec_fit(pfc_context *h, int n_dir, long long pairs, size_t dpcap) {
+    h->dual_hint = pairs;
+    if (dual_poly_cap(h, n_dir, (size_t)pairs) <= dpcap) return PFC_OK;
+    return fail(h, PFC_ERR_OVERFLOW, "Dual evaluation: %lld contributing pairs exceed the speculative polygon capacity: re-issue", pairs);
+}
+// ... for the small-scene kernel's hand-over (h_emit: its pair count and status, fetched with the check): the list first.
+int dual_handover_fit(pfc_context *h, int n_dir, size_t dpcap) {
+    if (h->stats[6] & kStCandOvf) return fail(h, PFC_ERR_OVERFLOW, "hand-over list of the small-scene kernel overflowed: re-issue (batched path)");
+    if ((unsigned)h->h_emit.p[2] & kStHole) return fail(h, PFC_ERR_STATE, "internal error: a work-list slot was read before it was written");
+    return dual_spec_fit(h, n_dir, h->h_emit.p[0], dpcap);
+}
 // Pair bound of passes enqueued before the count is known: floor x 2^k above twice the previous Dual evaluation's count (hint,
 // -1: none yet), so that buffers and captured graphs settle.
 size_t dual_spec_bound(long long hint, size_t floor) { while (floor < (size_t)(hint > 0 ? hint : 0) * 2 + 64) floor *= 2; return floor; }
@@ -919,7 +930,7 @@ void launch_broadphase(pfc_context *h, int n_items, int L, bool half, int *ccoun
 int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
                 const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, hipStream_t st, bool prof, const PassOpts &o) {
     new_value_pass(h);
-    h->pending_more = false; h->last_dual_reused = false;
+    h->last_dual_reused = false;
     const int levels = eff_levels(h);
     int *ccount = h->ctr.p, *tcount = h->ctr.p + 1, *next_seed = h->ctr.p + 2;   // ctr[3]: total records, filled by k_final
     int *ucount = h->ctr.p + 4, *fcount = h->ctr.p + 6;
@@ -1068,7 +1079,7 @@ int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double 
 int enqueue_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
                  const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, hipStream_t st, const PassOpts &o) {
     new_value_pass(h);
-    h->pending_more = false; h->last_dual_reused = false;
+    h->last_dual_reused = false;
     HIP_TRY(h, ensure_work(h, n_items, o.list));
     const int levels = eff_levels(h);
     const bool prof = h->opt_profile != 0;
@@ -1113,22 +1124,21 @@ int enqueue_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double
         if (rc != PFC_OK) return rc;
     }
     h->last_bfs_levels = L;
-    h->last_n_items = n_items; h->last_levels = levels; h->pending = true; h->last_stream = st;
+    h->last_n_items = n_items; h->last_levels = levels; h->pend = {pfc_context::Pending::Batched, st};
     h->ev_valid = prof;
     return PFC_OK;
 }
 
 // Synchronise, read counters, grow on overflow.
 int check_one(pfc_context *h, const int *tail) {
-    if (!h->pending) return PFC_OK;
+    const hipStream_t st = std::exchange(h->pend, {}).stream;      // (always a Batched record: this handle's, or the twin's for its half)
     const int levels = h->last_levels;
     const size_t n_tail = (size_t)levels + 12 + 12;
     if (!tail) {
-        HIP_TRY(h, hipMemcpyAsync(h->h_tail.p, h->tail.p, sizeof(int) * n_tail, hipMemcpyDeviceToHost, h->last_stream));
+        HIP_TRY(h, hipMemcpyAsync(h->h_tail.p, h->tail.p, sizeof(int) * n_tail, hipMemcpyDeviceToHost, st));
         tail = h->h_tail.p;
     }
-    HIP_TRY(h, hipStreamSynchronize(h->last_stream));
-    h->pending = false;
+    HIP_TRY(h, hipStreamSynchronize(st));
     const unsigned status = (unsigned)tail[0];
     const unsigned long long *tot = reinterpret_cast<const unsigned long long *>(tail + 4);
     const int *ctr = tail + 12;
@@ -1192,10 +1202,10 @@ int check_one(pfc_context *h, const int *tail) {
 int check_fused(pfc_context *h, const int *fout);
 void team_release(pfc_context *h);
 int check_eval(pfc_context *h, const int *tail = nullptr, const int *fout = nullptr) {
-    if (h->pending_fused) return check_fused(h, fout);
+    if (h->pend.kind == pfc_context::Pending::Fused) return check_fused(h, fout);
     h->last_fused = false;
     team_release(h);
-    if (!h->split_n0) {
+    if (!h->pend.split_n0) {
         h->last_parts = 1;
         const int rc0 = check_one(h, tail);
         if (rc0 == PFC_OK) h->note_shape(h->last_n_items, h->last_active * 4 <= (long long)h->last_n_items);
@@ -1204,7 +1214,6 @@ int check_eval(pfc_context *h, const int *tail = nullptr, const int *fout = null
     h->last_parts = 2;
     pfc_context *t = h->twin;
     const int rc1 = check_one(h, tail), rc2 = check_one(t, nullptr);   // both always run: each grows its own work lists on overflow (the second half reads its own h_tail)
-    h->split_n0 = 0;
     if (rc1 != PFC_OK) return rc1;
     if (rc2 != PFC_OK) { h->err = t->err; return rc2; }
     for (int k = 0; k < 4; ++k) h->stats[k] += t->stats[k];
@@ -1239,6 +1248,13 @@ void team_release(pfc_context *h) {
     if (!h->team_owner) return;
     h->team_owner = false;
     g_team_slot[h->device & 63].store(nullptr);
+}
+// The unchecked call, if any, is replaced or given up: nothing is pending any more, neither the twin's half nor the team slot a
+// small-scene launch held.  Every entry point that starts another call, the zero-item evaluations, a failed multi-device fan-out.
+void drop_pending(pfc_context *h) {
+    if (h->pend.split_n0) h->twin->pend = {};
+    h->pend = {};
+    team_release(h);
 }
 
 bool fused_ok(const pfc_context *h, int n_items, const PassOpts &o) {
@@ -1280,7 +1296,7 @@ int fused_team(const pfc_context *h, int n_items, const PassOpts &o) {
 int enqueue_fused(pfc_context *h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
                   const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, hipStream_t st, const PassOpts &o) {
     new_value_pass(h);
-    h->pending_more = false; h->last_dual_reused = false;
+    h->last_dual_reused = false;
     FuArgs a;
     a.n_items = n_items; a.n_ins = (int)h->ins.size(); a.ins_ids = d_ins_ids; a.pose = d_pose; a.twist = d_twist; a.s = d_s;
     a.ins = h->d_insfull; a.wrench = d_wrench; a.sdot = d_sdot; a.counts = d_counts;
@@ -1327,17 +1343,17 @@ int enqueue_fused(pfc_context *h, int n_items, const int *d_ins_ids, const doubl
     if (h->any_tet_tet) hipLaunchKernelGGL((k_fused<true>), dim3(n_items), dim3(kFuBlock), 0, st, a);
     else hipLaunchKernelGGL((k_fused<false>), dim3(n_items), dim3(kFuBlock), 0, st, a);
     HIP_TRY(h, hipGetLastError());
-    h->last_n_items = n_items; h->pending = true; h->pending_fused = true; h->last_stream = st; h->ev_valid = false;
-    h->last_bfs_levels = 0; h->split_n0 = 0;
+    h->last_n_items = n_items; h->pend = {pfc_context::Pending::Fused, st}; h->ev_valid = false;
+    h->last_bfs_levels = 0;
     return PFC_OK;
 }
 
 int check_fused(pfc_context *h, const int *fo) {
     const int n = h->last_n_items;
     if (!fo) {
-        HIP_TRY(h, hipMemcpyAsync(h->h_fout.p, h->fout.p, sizeof(int) * 8 * (size_t)n, hipMemcpyDeviceToHost, h->last_stream));
+        HIP_TRY(h, hipMemcpyAsync(h->h_fout.p, h->fout.p, sizeof(int) * 8 * (size_t)n, hipMemcpyDeviceToHost, h->pend.stream));
         fo = h->h_fout.p;
-        HIP_TRY(h, hipStreamSynchronize(h->last_stream));
+        HIP_TRY(h, hipStreamSynchronize(h->pend.stream));
     } else {
         // The kernel wrote its results straight into pinned host memory; every workgroup ends with a system-scope
         // release and its completion word.  Polling those words returns ~3 us earlier than hipStreamSynchronize wakes
@@ -1358,10 +1374,10 @@ int check_fused(pfc_context *h, const int *fo) {
         if (done) std::atomic_thread_fence(std::memory_order_acquire);
         else {
             if (std::getenv("PFC_LOG_POLL")) std::fprintf(stderr, "pfc: completion poll timed out, synchronising\n");
-            HIP_TRY(h, hipStreamSynchronize(h->last_stream));
+            HIP_TRY(h, hipStreamSynchronize(h->pend.stream));
         }
     }
-    h->pending = false; h->pending_fused = false; h->last_parts = 1; h->last_fused = true;
+    h->pend = {}; h->last_parts = 1; h->last_fused = true;
     team_release(h);
     unsigned status = 0;
     long long tot[4] = {0, 0, 0, 0};
@@ -1545,7 +1561,7 @@ void pfc_destroy(pfc_handle h) {
     if (h->multi) { multi_destroy(h); delete h; return; }
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if ((h->pending || h->pending_surface) && h->last_stream) (void)hipStreamSynchronize(h->last_stream);   // an unchecked pfc_eval_device on the caller's stream
+    if (h->pend.kind && h->pend.stream) (void)hipStreamSynchronize(h->pend.stream);   // an unchecked call of any kind on the caller's stream
     team_release(h);
     if (h->twin) pfc_destroy(h->twin);
     delete h;      // every buffer, event, graph and stream is a member that frees itself; the streams go last
@@ -1870,13 +1886,11 @@ static int check_eval_args(pfc_context *h, int n_items, const void *ins_ids, con
 static int eval_device(pfc_context *h, int n_items, const int *d_ins_ids, const double *d_pose, const double *d_twist,
                        const double *d_s, double *d_wrench, double *d_sdot, int *d_counts, void *stream, PassOpts o) {
     { const int rc = check_eval_args(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot); if (rc != PFC_OK) return rc; }
-    if (n_items == 0) { h->pending = false; h->last_n_items = 0; return PFC_OK; }
+    drop_pending(h);
+    end_kept_pass(h);
+    if (n_items == 0) { h->last_n_items = 0; return PFC_OK; }
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    h->split_n0 = 0;
-    h->pending_fused = false;
-    end_kept_pass(h);
-    h->pending_more = false;
     int team = fused_team(h, n_items, o);
     if (team > 1 && !team_acquire(h)) team = fused_ok(h, n_items, o) ? 1 : 0;     // another handle's teams are in flight on this device
     if (team) {
@@ -1923,7 +1937,7 @@ static int eval_device(pfc_context *h, int n_items, const int *d_ins_ids, const 
         HIP_TRY(h, hipEventRecord(h->ev_join0, s0));
         HIP_TRY(h, hipStreamWaitEvent(st, h->ev_join0, 0));
     }
-    h->split_n0 = n0;
+    h->pend = {pfc_context::Pending::Batched, s0, n0};
     return PFC_OK;
 }
 
@@ -1955,10 +1969,8 @@ int surface_enqueue(pfc_context *h, int n_items, const int *d_ins_ids, const dou
                     double *d_trac, double *d_summary, int *d_counts, long long *d_totals, hipStream_t st, const SurfFricOut *fo = nullptr) {
     // an evaluation for the call-order rules: the candidate list and the counters a Dual evaluation could reuse are overwritten
     new_value_pass(h);
-    h->pending_more = false;
+    drop_pending(h);
     h->pin_in_pt = {}; h->pin_din_pt = {};
-    h->pending = false; h->pending_dual = false; h->pending_dual_hyb = false; h->split_n0 = 0;
-    if (h->pending_fused) { h->pending_fused = false; team_release(h); }
     int ba, bb;
     const int bits = pfc_sort_key_bits(n_items, h->max_elem1, h->max_elem2, &ba, &bb);
     if (bits > 64)
@@ -2036,7 +2048,7 @@ int surface_enqueue(pfc_context *h, int n_items, const int *d_ins_ids, const dou
                        h->surf_out.p);
     HIP_TRY(h, hipMemcpyAsync(h->h_surf.p, h->surf_out.p, sizeof(long long) * ((size_t)n_ctr + 3), hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipGetLastError());
-    h->pending_surface = true; h->last_stream = st; h->surf_n_ctr = n_ctr;
+    h->pend = {pfc_context::Pending::Surface, st, 0, n_ctr};
     h->surf_cap_poly = cap_poly; h->surf_cap_trac = cap_trac;
     h->last_n_items = n_items; h->last_levels = levels; h->last_bfs_levels = L;
     return PFC_OK;
@@ -2045,9 +2057,9 @@ int surface_enqueue(pfc_context *h, int n_items, const int *d_ins_ids, const dou
 // Synchronise the pending surface call and judge it: internal work lists grown (PFC_ERR_OVERFLOW, re-issue), or the caller's
 // capacities short (PFC_ERR_OVERFLOW with surf_cap_short: totals, offsets, summary and counters are written, nothing else).
 int check_surface(pfc_context *h) {
-    h->pending_surface = false;
+    const hipStream_t st = std::exchange(h->pend, {}).stream;
     h->surf_cap_short = false;
-    HIP_TRY(h, hipStreamSynchronize(h->last_stream));
+    HIP_TRY(h, hipStreamSynchronize(st));
     const long long *o = h->h_surf.p;
     const unsigned status = (unsigned)o[0];
     const long long *ctr = o + 3;
@@ -2243,55 +2255,49 @@ int pfc_contact_surface_fric_device(pfc_handle h, int n_items, const int *d_ins_
     return h->multi ? surface_ctx(h, call) : call(h);
 }
 
-int pfc_check(pfc_handle h) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi) {
-        pfc_context *c0 = h->multi->shard[0];
-        if (!c0->pending_surface) return multi_check(h);
-        (void)hipSetDevice(c0->device);
-        return on_first_shard(h, check_surface);
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (h->pending_surface) return check_surface(h);
-    if (h->pending_more) {       // Dual passes on a value pass that was checked before: nothing to read back
-        h->pending_more = false;
-        HIP_TRY(h, hipStreamSynchronize(h->last_stream));
+// Synchronise and judge the pending call: the single-device body of pfc_check, and what the debug readers drain with.
+static int drain(pfc_context *h) {
+    using P = pfc_context::Pending;
+    const P p = h->pend;
+    switch (p.kind) {
+    case P::None: return PFC_OK;
+    case P::Surface: return check_surface(h);
+    case P::More:        // Dual passes on a value pass that was checked before: nothing to read back
+        h->pend = {};
+        HIP_TRY(h, hipStreamSynchronize(p.stream));
         if (h->h_more.p && (h->h_more.p[0] & kStHole)) {
             end_kept_pass(h);
             return fail(h, PFC_ERR_STATE, "internal error: a Dual pass on a reused value pass read a work-list slot out of range");
         }
         return PFC_OK;
+    case P::Batched: case P::Fused: break;
     }
-    // (a Dual evaluation pending here has no kept pass: its value pass ended it; recorded below once it is checked)
-    if (h->pending_dual_hyb) {
-        h->pending_dual_hyb = false; h->pending_dual = false;
-        const int rch = check_eval(h);            // the fused kernel's per-item words (copied down, stream synchronised)
-        if (rch != PFC_OK) { h->dual_dev_hyb_skip = 64; return rch; }
-        if (h->stats[6] & kStCandOvf) {
-            h->dual_dev_hyb_skip = 64;
-            return fail(h, PFC_ERR_OVERFLOW, "hand-over list of the small-scene kernel overflowed: re-issue (batched path)");
-        }
-        if ((unsigned)h->h_emit.p[2] & kStHole) return fail(h, PFC_ERR_STATE, "internal error: a work-list slot was read before it was written");
-        const long long pairs_h = h->h_emit.p[0];
-        h->dual_hint = pairs_h;
-        if (!dual_pairs_fit(h, h->pending_ndir, pairs_h, h->pending_dpcap))
-            return fail(h, PFC_ERR_OVERFLOW, "Dual evaluation: %lld contributing pairs exceed the speculative polygon capacity: re-issue", pairs_h);
-        h->kept = {pfc_context::KeptPass::HandOver, h->last_n_items, h->pending_ids};
-        return PFC_OK;
+    // (no kept pass here: the value pass ended it; a Dual evaluation that rides on it records its own below once it is checked)
+    int rc = check_eval(h);      // (Fused: the small-scene kernel's per-item words copied down, stream synchronised)
+    switch (p.dual) {
+    case P::NoDual: return rc;
+    case P::DualHandOver:
+        if (rc != PFC_OK || (h->stats[6] & kStCandOvf)) h->dual_dev_hyb_skip = 64;
+        if (rc == PFC_OK) rc = dual_handover_fit(h, p.n_dir, p.dpcap);
+        break;
+    case P::DualBatched:      // contributing pairs: the counter next to the polygon total in the packed tail, which check_eval has just brought over
+        if (rc == PFC_OK) rc = dual_spec_fit(h, p.n_dir, h->h_tail.p[tail_pairs(h->last_levels)], p.dpcap);
+        break;
     }
-    const bool dual = h->pending_dual;
-    h->pending_dual = false;
-    if (h->device_kept()) end_kept_pass(h);      // a check with no Dual evaluation pending ends a kept device pass
-    const int rc = check_eval(h);
-    if (rc != PFC_OK || !dual) return rc;
-    // did the kept Dual polygons of pfc_eval_dual_device fit?  (contributing pairs: the counter next to the polygon total
-    // in the packed tail, which check_eval has just brought over)
-    const long long pairs = h->h_tail.p[tail_pairs(h->last_levels)];
-    h->dual_hint = pairs;
-    if (!dual_pairs_fit(h, h->pending_ndir, pairs, h->pending_dpcap))
-        return fail(h, PFC_ERR_OVERFLOW, "Dual evaluation: %lld contributing pairs exceed the speculative polygon capacity: re-issue", pairs);
-    h->kept = {pfc_context::KeptPass::Batched, h->last_n_items, h->pending_ids};
-    return PFC_OK;
+    if (rc == PFC_OK) h->kept = {p.dual == P::DualHandOver ? pfc_context::KeptPass::HandOver : pfc_context::KeptPass::Batched, h->last_n_items, p.ids};
+    return rc;
+}
+
+int pfc_check(pfc_handle h) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi) {
+        pfc_context *c0 = h->multi->shard[0];
+        if (c0->pend.kind != pfc_context::Pending::Surface) return multi_check(h);
+        (void)hipSetDevice(c0->device);
+        return on_first_shard(h, check_surface);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    return drain(h);
 }
 
 // BAR-resident input blocks (pfc_context::bar_in): allocated on first use if the device has a large BAR.
@@ -2439,7 +2445,7 @@ static int eval_host(pfc_context *h, int n_items, const int *ins_ids, const doub
         rc = eval_device(h, n_items, ins_ids ? (const int *)(di + in_d) : nullptr, di, di + n * 24,
                          s ? di + n * 30 : nullptr, dout, dout + n * 6, (int *)(dout + out_d), st, o);
         if (rc != PFC_OK) return rc;
-        if (!zero_copy && !h->pending_fused) HIP_TRY(h, hipMemcpyAsync(h->pin_out.p, h->tail.p, back_bytes, hipMemcpyDeviceToHost, st));
+        if (!zero_copy && h->pend.kind != pfc_context::Pending::Fused) HIP_TRY(h, hipMemcpyAsync(h->pin_out.p, h->tail.p, back_bytes, hipMemcpyDeviceToHost, st));
         rc = check_eval(h, (const int *)h->pin_out.p, o.fout_host);      // one D2H copy carries the tail and the outputs
         if (rc != PFC_ERR_OVERFLOW) break;
     }
@@ -2716,12 +2722,8 @@ int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids,
     // check_fused would poll; here the stream is synchronised (the completion words of the fused kernel are long written)
     HIP_TRY(h, hipStreamSynchronize(st));
     rc = check_eval(h, nullptr, reinterpret_cast<const int *>((const double *)h->pin_out.p + out_d) + n * 4);
+    if (rc == PFC_OK) rc = dual_handover_fit(h, n_dir, dpcap);
     if (rc != PFC_OK) return rc;
-    if (h->stats[6] & kStCandOvf) return fail(h, PFC_ERR_OVERFLOW, "hand-over list of the small-scene kernel overflowed: batched path");
-    if ((unsigned)h->h_emit.p[2] & kStHole) return fail(h, PFC_ERR_STATE, "internal error: a work-list slot was read before it was written");
-    const long long pairs = h->h_emit.p[0];
-    h->dual_hint = pairs;
-    if (!dual_pairs_fit(h, n_dir, pairs, dpcap)) return PFC_ERR_OVERFLOW;
     copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
     copy_out_dual((const double *)h->pin_dout.p, nk, d_wrench, d_sdot);
     h->kept = {pfc_context::KeptPass::Hybrid, n_items, ins_ids != nullptr};
@@ -2839,15 +2841,12 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     new_value_pass(h);      // the replay overwrites the device state
     h->last_dual_reused = false;
     HIP_TRY(h, hipGraphLaunch(h->dgexec, st));
-    h->last_bfs_levels = L; h->last_n_items = n_items; h->pending = true; h->last_stream = st; h->ev_valid = false;
-    h->split_n0 = 0;
+    h->last_bfs_levels = L; h->last_n_items = n_items; h->pend = {pfc_context::Pending::Batched, st}; h->ev_valid = false;
     const int *tail = (const int *)h->pin_out.p;
     rc = check_eval(h, tail);           // the one synchronisation; grows the work lists on overflow
-    if (rc != PFC_OK) return rc;
     // did the kept Dual polygons fit?  (contributing pairs: the counter next to the polygon total in the packed tail)
-    const long long pairs = tail[tail_pairs(h->last_levels)];
-    h->dual_hint = pairs;
-    if (!dual_pairs_fit(h, n_dir, pairs, dpcap)) return PFC_ERR_OVERFLOW;
+    if (rc == PFC_OK) rc = dual_spec_fit(h, n_dir, tail[tail_pairs(h->last_levels)], dpcap);
+    if (rc != PFC_OK) return rc;
     copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
     copy_out_dual((const double *)h->pin_dout.p, nk, d_wrench, d_sdot);
     h->kept = {pfc_context::KeptPass::OneGraph, n_items, ins_ids != nullptr};
@@ -2865,9 +2864,9 @@ int pfc_eval_dual_device_bp(pfc_handle h, int n_items, int n_dir, const int *d_i
                                  d_dwrench, d_dsdot, d_counts, stream);
     if (n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "pfc_eval_dual_device: n_dir must be in 1..16");
     { const int rc = check_eval_args(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot); if (rc != PFC_OK) return rc; }
-    h->pending_dual = false; h->pending_more = false;
+    drop_pending(h);
     end_kept_pass(h);
-    if (n_items == 0) { h->pending = false; h->last_n_items = 0; return PFC_OK; }
+    if (n_items == 0) { h->last_n_items = 0; return PFC_OK; }
     if (!d_dpose || !d_dtwist || !d_dwrench || !d_dsdot) return fail(h, PFC_ERR_BAD_ARG, "pfc_eval_dual_device: null buffer");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
@@ -2881,7 +2880,6 @@ int pfc_eval_dual_device_bp(pfc_handle h, int n_items, int n_dir, const int *d_i
     HIP_TRY(h, ensure_graphed(h, h->dual_res, nk * kDrStride));
     HIP_TRY(h, zero_ds(h, nk, &d_ds, st));
     HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
-    h->split_n0 = 0; h->pending_fused = false; h->pending_dual_hyb = false;
     // Small scenes: the value pass in the one-workgroup-per-item kernel, which hands item records and lists to the batched
     // Dual passes (what pfc_eval_dual does for host buffers, eval_dual_hybrid).  A miss (an item that does not fit, a
     // hand-over list or a speculation that fell short) is reported by pfc_check as PFC_ERR_OVERFLOW and the re-issue takes
@@ -2904,7 +2902,7 @@ int pfc_eval_dual_device_bp(pfc_handle h, int n_items, int n_dir, const int *d_i
             rcf = launch_dual(h, n_items, n_dir, h->tail.p, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, bh, st, &dpcap_h, true, h->emit_ctr.p);
             if (rcf != PFC_OK) return rcf;
             HIP_TRY(h, hipMemcpyAsync(h->h_emit.p, h->emit_ctr.p, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-            h->pending_dual_hyb = true; h->pending_dpcap = dpcap_h; h->pending_ndir = n_dir; h->pending_ids = d_ins_ids != nullptr;
+            h->pend = {pfc_context::Pending::Fused, st, 0, 0, pfc_context::Pending::DualHandOver, n_dir, dpcap_h, d_ins_ids != nullptr};
             return PFC_OK;
         }
     }
@@ -2914,7 +2912,7 @@ int pfc_eval_dual_device_bp(pfc_handle h, int n_items, int n_dir, const int *d_i
     size_t dpcap = 0;
     rc = launch_dual(h, n_items, n_dir, h->tail.p, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, bound, st, &dpcap, true);
     if (rc != PFC_OK) return rc;
-    h->pending_dual = true; h->pending_dpcap = dpcap; h->pending_ndir = n_dir; h->pending_ids = d_ins_ids != nullptr;
+    h->pend = {pfc_context::Pending::Batched, st, 0, 0, pfc_context::Pending::DualBatched, n_dir, dpcap, d_ins_ids != nullptr};
     return PFC_OK;
 }
 
@@ -2954,7 +2952,7 @@ int pfc_eval_dual_device_more(pfc_handle h, int n_dir, const double *d_dpose, co
                                h->kept.kind == pfc_context::KeptPass::HandOver ? h->emit_ctr.p : nullptr, more_status);
     if (rc != PFC_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->h_more.p, more_status, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    h->pending_more = true; h->last_stream = st; h->last_dual_reused = true;
+    h->pend = {pfc_context::Pending::More, st}; h->last_dual_reused = true;
     return PFC_OK;
 }
 
@@ -2995,7 +2993,7 @@ int pfc_local_jacobian_device(pfc_handle h, double *d_L, void *stream) {
     hipLaunchKernelGGL(k_ljac_pack, dim3((unsigned)((n * kLjacSize + 255) / 256)), dim3(256), 0, st, n_items, h->ljac_out.p, d_L);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(h->h_more.p, more_status, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    h->pending_more = true; h->last_stream = st; h->last_dual_reused = true;
+    h->pend = {pfc_context::Pending::More, st}; h->last_dual_reused = true;
     return PFC_OK;
 }
 
@@ -3825,7 +3823,7 @@ int pfc_debug_pairs(pfc_handle h, int item, int *pairs, int *clip_n, int cap) {
         return on_shard(h, c, [&](pfc_context *c1) { return pfc_debug_pairs(c1, local, pairs, clip_n, cap); }, true);
     }
     if (!h->opt_debug) return -fail(h, PFC_ERR_STATE, "debug option is off");
-    if (h->pending) { int rc = check_eval(h); if (rc) return -rc; }
+    { int rc = drain(h); if (rc) return -rc; }
     if (item < 0 || item >= h->last_n_items) return -fail(h, PFC_ERR_BAD_ARG, "bad item");
     size_t nc = (size_t)h->stats[1];
     std::vector<WorkRec> c(nc);
@@ -3856,7 +3854,7 @@ int pfc_debug_tractions(pfc_handle h, int item, double *buf, int cap) {
         return on_shard(h, c, [&](pfc_context *c1) { return pfc_debug_tractions(c1, local, buf, cap); }, true);
     }
     if (!h->opt_debug) return -fail(h, PFC_ERR_STATE, "debug option is off");
-    if (h->pending) { int rc = check_eval(h); if (rc) return -rc; }
+    { int rc = drain(h); if (rc) return -rc; }
     if (item < 0 || item >= h->last_n_items) return -fail(h, PFC_ERR_BAD_ARG, "bad item");
     size_t nt = (size_t)h->last_tslots;
     std::vector<int> ti(nt);
@@ -3886,7 +3884,7 @@ int pfc_debug_stiffness(pfc_handle h, int item, double *K36, double *Kis36, doub
         if (!c) return -fail(h, PFC_ERR_BAD_ARG, "bad item");
         return on_shard(h, c, [&](pfc_context *c1) { return pfc_debug_stiffness(c1, local, K36, Kis36, Sinv6, cop3); }, true);
     }
-    if (h->pending) { int rc = check_eval(h); if (rc) return -rc; }
+    { int rc = drain(h); if (rc) return -rc; }
     if (h->last_fused)      // the fused small-scene kernel keeps K in LDS only
         return -fail(h, PFC_ERR_STATE, "pfc_debug_stiffness: set option debug (or fused = 0) before the evaluation");
     if (item < 0 || item >= h->last_n_items) return -fail(h, PFC_ERR_BAD_ARG, "bad item");
@@ -4068,7 +4066,7 @@ int pfc_scatter_generalized_dual_device(pfc_handle h, int n_items, int n_dir, co
 int pfc_debug_stamps(pfc_handle h, long long *out16) {
     if (!h || !out16) return PFC_ERR_BAD_ARG;
     if (h->multi) return pfc_debug_stamps(h->multi->shard[0], out16);
-    if (h->pending) { int rc = check_eval(h); if (rc) return rc; }
+    { int rc = drain(h); if (rc) return rc; }
     unsigned long long v[16] = {0};
     if (h->stamps.p) HIP_TRY(h, copy_sync(h, v, h->stamps.p, sizeof v, hipMemcpyDeviceToHost));
     for (int k = 0; k < 16; ++k) out16[k] = (long long)v[k];

@@ -304,18 +304,12 @@ int multi_dev_iota(pfc_context *h, int k, int n) {
     return PFC_OK;
 }
 
-// A shard whose stream has been synchronised after a failed fan-out: nothing of it is pending any more (nor its team slot).
-void multi_drop_pending(pfc_context *c) {
-    c->pending = c->pending_fused = c->pending_dual = c->pending_dual_hyb = c->pending_more = false;
-    team_release(c);
-}
-
 // The fan-out of the device-pointer entry points.  Every shard k >= 1 with items runs on its device and stream behind the caller's
 // stream st0 (fork event): stage(k) makes its staging ready (nothing there waits for st0), run(k, stream) copies its range in, calls
 // the shard and copies the results back into the caller's buffers; then run(0, st0) evaluates shard 0 on the caller's arrays and
 // stream, which waits for every other shard.  Both return a status with its message in h->err.  One exit for errors: once shards
 // have work enqueued (copies that write into the caller's buffers; staging the next call may reallocate), the streams that may
-// hold some are synchronised and the shards' pending state dropped before the first error is returned.  The caller's thread is
+// hold some are synchronised and the shards' pending calls dropped (drop_pending) before the first error is returned.  The caller's thread is
 // back on the first device -- the one its buffers and its stream live on -- whichever way this returns.
 template <class StageFn, class RunFn>
 int multi_fan_out(pfc_context *h, hipStream_t st0, const char *what, StageFn stage, RunFn run) {
@@ -342,11 +336,11 @@ int multi_fan_out(pfc_context *h, hipStream_t st0, const char *what, StageFn sta
         for (int k = 1; k < enq; ++k) {
             (void)hipSetDevice(M->dev[k]);
             (void)hipStreamSynchronize(M->shard[k]->stream);
-            multi_drop_pending(M->shard[k]);
+            drop_pending(M->shard[k]);
         }
         (void)hipSetDevice(dev0);
         (void)hipStreamSynchronize(st0);
-        multi_drop_pending(M->shard[0]);
+        drop_pending(M->shard[0]);
     }
     return rc;
 }
