@@ -441,7 +441,7 @@ int pfc_eval_dual_bodies_device_more(pfc_handle h, int n_items, int n_dir, const
  * Kinematics from joint states: what transform_to_root / twist_wrt_world (src/contact_algorithms_non_friction.jl:109-110,125-126) and
  * refreshJacobians! (:86-92) give the reference per evaluation -- the bodies' world poses, twists and geometric Jacobians -- formed on
  * the device from the state vector (q, v), the front of the chain state -> body states -> items -> pfc_eval_device ->
- * pfc_scatter_generalized_device.  Value path only.
+ * pfc_scatter_generalized_device.  The value path; its Dual sibling is pfc_kinematics_dual_device below.
  *
  * pfc_set_mechanism gives the tree.  Body b is the successor of joint b; parent[b] lies in [-1, b), -1 is the world, so the order is
  * topological.  x_p_j (n_body x 12) is the joint's joint_pose -- the frame before the joint in the parent body's frame, R (9,
@@ -521,6 +521,80 @@ int pfc_eval_state(pfc_handle h, int n_items, const int *ins_ids, const int *sce
                    double *x_w_b, double *twist_w_b, double *jac,
                    double *pose, double *twist, double *x_w_r2, int *body_1, int *body_2,
                    double *wrench, double *sdot, int *counts, double *f);
+
+/*
+ * Dual kinematics from joint states: the partials of the bodies' world poses, twists and geometric Jacobians that RigidBodyDynamics
+ * gives the reference on the Dual state of a Jacobian chunk (src/radau/radau_functions.jl:2-14), formed on the device from (q, v) and
+ * the chunk's seed directions -- the front of the chain state + seeds -> body-state partials -> item seeds ->
+ * pfc_eval_dual_device[_more] -> pfc_scatter_generalized_dual_device.  Two kernels enqueued on `stream` (NULL = the handle's own)
+ * without a host synchronisation, for n_dir (1..16, else PFC_ERR_BAD_ARG) seed directions:
+ *   d_q, d_v      the values, as pfc_kinematics_device (d_v may be NULL only when d_dtwist_w_b is: PFC_ERR_BAD_ARG otherwise)
+ *   d_dq          n_scene x n_dir x nq   partials of q, direction dir of scene s at row s n_dir + dir
+ *   d_dv          n_scene x n_dir x nv   partials of v, likewise
+ *                 each may be NULL: zeros, the same bytes as an array of zeros (the chunk that seeds only velocities or only
+ *                 configurations)
+ *   d_dx_w_b      n_scene n_body x n_dir x 12      OUT partials of x_w_b, pfc_dual_seeds_from_bodies_device's d_dx_w_b: direction dir of
+ *                 body b of scene s at row (s n_body + b) n_dir + dir
+ *   d_dtwist_w_b  n_scene n_body x n_dir x 6       OUT partials of twist_w_b, its d_dtwist_w_b
+ *   d_djac        n_scene n_body x n_dir x nv x 6  OUT partials of the Jacobians, pfc_scatter_generalized_dual_device's d_djac for the
+ *                 scene-offset body ids pfc_items_from_bodies_device writes: column c at row ((s n_body + b) n_dir + dir) nv + c
+ * Any OUT pointer may be NULL: it is not written, and the work it alone needs is not launched.  The arithmetic is the statement of
+ * pfc_kinematics_device run on (value, partial) numbers with ForwardDiff's rules, without fma and with nothing restated:
+ *   sums and differences componentwise;  d(a b) = da b + a db;  a literal or a mechanism constant (x_p_j, an axis) is {x, 0.0};
+ *   a / b = {a.v / b.v, a.d (1.0 / b.v) + b.d (-(a.v / (b.v b.v)))};
+ *   sin th = {sin th.v, cos th.v th.d},  cos th = {cos th.v, -(sin th.v th.d)}, the values being those of pfc_kinematics_device.
+ * There is no shortcut for a zero seed: a direction that seeds none of a body's ancestors goes through the same expressions, and
+ * its partials are the signed zeros of that arithmetic.  The partial columns of a body's non-ancestors are +0.0 six times.  The value
+ * parts are pfc_kinematics_device's bytes and are not stored.  The same bytes on every call, handle and entry point.  The call is NOT
+ * an evaluation: a kept value pass, Dual reuse, pfc_check and pfc_last_* are as they were (a pfc_eval_dual_device_more may still
+ * follow the evaluation before it).  n_scene = 0 is a no-op.  PFC_ERR_STATE before pfc_set_mechanism; nothing is written where the
+ * call is refused.  The call keeps the partial columns in a handle buffer that grows on demand only: calls on different streams must
+ * be ordered by the caller.  Multi-device handles: the first device.
+ */
+int pfc_kinematics_dual_device(pfc_handle h, int n_scene, int n_dir, const double *d_q, const double *d_v,
+                               const double *d_dq, const double *d_dv,
+                               double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac, void *stream);
+/* The same with host buffers, synchronous: the same kernels, the same bytes. */
+int pfc_kinematics_dual(pfc_handle h, int n_scene, int n_dir, const double *q, const double *v, const double *dq, const double *dv,
+                        double *dx_w_b, double *dtwist_w_b, double *djac);
+
+/*
+ * The Dual sibling of pfc_eval_state_device.  On one stream, with n_body and nv of the mechanism: pfc_kinematics_device,
+ * pfc_kinematics_dual_device, exactly pfc_eval_dual_bodies_device, then pfc_scatter_generalized_dual_device with accumulate = 0 into
+ * d_f (n_scene x nv) and d_df (n_scene x n_dir x nv): (q, v) and their seed directions in, f_generalized and its partials out, with no
+ * upload per chunk but the seeds.  d_df = NULL skips the scatter; d_f may be NULL even with d_df given (partials only).  All buffers are
+ * the caller's and all are required but d_ins_ids, d_scene, d_s, d_ds, d_dq, d_dv, d_counts (as in the parts), d_f and d_df; with
+ * d_df also d_jac, d_djac, d_x_w_r2, d_dx_w_r2, d_body_1 and d_body_2 (without it each of these may be NULL: not written).
+ * pfc_check() afterwards as after pfc_eval_dual_device; on PFC_ERR_OVERFLOW the outputs are undefined and the call is re-issued
+ * (everything is formed again, to the same bytes).  States and errors are those of the parts, checked before anything is launched;
+ * PFC_ERR_BAD_ARG if an instruction the items use is bound to a body >= n_body of the mechanism.  There is no accumulate variant: a
+ * host that accumulates calls the parts.
+ */
+int pfc_eval_dual_state_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
+                               const double *d_q, const double *d_v, const double *d_dq, const double *d_dv,
+                               const double *d_s, const double *d_ds,
+                               double *d_x_w_b, double *d_twist_w_b, double *d_jac,
+                               double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac,
+                               double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
+                               double *d_dpose, double *d_dtwist, double *d_dx_w_r2,
+                               double *d_wrench, double *d_sdot, double *d_dwrench, double *d_dsdot, int *d_counts,
+                               double *d_f, double *d_df, void *stream);
+/*
+ * The later chunks of a Jacobian at the kept point, from the seeds of (q, v): pfc_kinematics_dual_device, then exactly
+ * pfc_eval_dual_bodies_device_more, then the Dual scatter into d_df (NULL: no scatter).  It reads the value buffers the first chunk
+ * left -- d_x_w_b, d_twist_w_b, d_jac, d_x_w_r2, d_body_1, d_body_2 and d_wrench (the last five with d_df only) -- and writes only
+ * partials: no value output, no f.  Single-device handles check _more's preconditions before anything is launched --
+ * PFC_ERR_STATE without a checked pfc_eval_dual_device evaluation to extend, PFC_ERR_BAD_ARG if n_items is not that evaluation's -- and
+ * then write nothing.  Multi-device handles form the kinematics partials and the seeds on the first device and then return _more's own
+ * status, as pfc_eval_dual_bodies_device_more documents.  Follow with pfc_check() as after pfc_eval_dual_device_more.
+ */
+int pfc_eval_dual_state_device_more(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
+                                    const double *d_q, const double *d_v, const double *d_dq, const double *d_dv, const double *d_ds,
+                                    const double *d_x_w_b, const double *d_twist_w_b, const double *d_jac,
+                                    double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac,
+                                    const double *d_x_w_r2, const int *d_body_1, const int *d_body_2, const double *d_wrench,
+                                    double *d_dpose, double *d_dtwist, double *d_dx_w_r2, double *d_dwrench, double *d_dsdot,
+                                    double *d_df, void *stream);
 
 /*
  * The contact surface of n_items items: per item what the reference's TractionCache holds after forceAllElasticIntersections!

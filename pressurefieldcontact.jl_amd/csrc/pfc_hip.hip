@@ -24,7 +24,8 @@
 //                  (pfc_items_from_bodies, pfc_eval_bodies); k_dual_seeds_from_bodies: their partials from the partials of the body
 //                  states (pfc_dual_seeds_from_bodies, pfc_eval_dual_bodies_device[_more])
 //   pfc_kin.h      k_kinematics / k_kin_jacobian: the bodies' world poses, twists and geometric Jacobians from the joint state (q, v)
-//                  of a small tree (pfc_set_mechanism, pfc_kinematics, pfc_eval_state)
+//                  of a small tree (pfc_set_mechanism, pfc_kinematics, pfc_eval_state); k_kinematics_dual / k_kin_jacobian_dual: their
+//                  partials from the seed directions of a Jacobian chunk (pfc_kinematics_dual, pfc_eval_dual_state_device[_more])
 //   pfc_multi.h    host code: multi-device handles (pfc_create_multi)
 // This file: mesh record preparation (k_prep_tri, k_prep_tet), per-item setup (k_setup_items), work-list management,
 // hipGraph capture / replay, the two-half evaluation and every extern "C" entry point.
@@ -599,6 +600,7 @@ struct pfc_context {
     DevBuf<char> kin_tab;              // their device copy, one block
     bool kin_stale = true;             // the device copy is older than kin: uploaded by the next kinematics call
     DevBuf<double> kin_sw;             // S_w, n_scene x nv x 6: grows on demand only
+    DevBuf<double> kin_dsw;            // dS_w, n_scene x n_dir x nv x 6 (pfc_kinematics_dual): likewise
     DevBuf<unsigned long long> surf_keys[2];
     DevBuf<char> surf_tmp;                            // rocPRIM scan / sort
     PinBuf<long long> h_surf;                         // pinned mirror of surf_out
@@ -3413,8 +3415,7 @@ static int kin_check_args(pfc_context *h, const char *who, int n_scene, const do
 // The tables' upload on st if they are stale (one synchronisation per pfc_set_mechanism, as bodies_upload_bind), S_w grown if a
 // Jacobian is wanted and too small, and the kernels, on st.  Every pointer is a device pointer; an output that is null is not
 // written, and the kernel only it needs is not launched.
-static int kin_launch(pfc_context *h, int n_scene, const double *q, const double *v, double *x_w_b, double *twist_w_b, double *jac,
-                      hipStream_t st) {
+static int kin_upload_tables(pfc_context *h, hipStream_t st) {
     const KinHost &K = h->kin;
     HIP_TRY(h, hipSetDevice(h->device));
     if (h->kin_stale) {
@@ -3423,16 +3424,31 @@ static int kin_launch(pfc_context *h, int n_scene, const double *q, const double
         HIP_TRY(h, hipStreamSynchronize(st));
         h->kin_stale = false;
     }
-    const bool want_jac = jac && K.nv > 0;
-    if (!x_w_b && !twist_w_b && !want_jac) return PFC_OK;
-    if (want_jac) HIP_TRY(h, h->kin_sw.ensure((size_t)n_scene * K.nv * 6));
+    return PFC_OK;
+}
+
+// The sizes, the tables' device addresses and the state of both kernels' arguments; the outputs are left null.
+static KinArgs kin_table_args(const pfc_context *h, int n_scene, const double *q, const double *v) {
+    const KinHost &K = h->kin;
     const char *t = h->kin_tab.p;
     KinArgs a;
     a.n_scene = n_scene; a.n_body = K.n_body; a.nq = K.nq; a.nv = K.nv;
     a.jtype = (const int *)(t + K.o_jtype); a.qoff = (const int *)(t + K.o_qoff); a.voff = (const int *)(t + K.o_voff);
     a.path_off = (const int *)(t + K.o_path_off); a.path = (const int *)(t + K.o_path);
     a.x_p_j = (const double *)(t + K.o_x_p_j); a.axis = (const double *)(t + K.o_axis); a.anc = (const unsigned char *)(t + K.o_anc);
-    a.q = q; a.v = v; a.x_w_b = x_w_b; a.twist_w_b = twist_w_b; a.S_w = want_jac ? h->kin_sw.p : nullptr; a.jac = jac;
+    a.q = q; a.v = v; a.x_w_b = nullptr; a.twist_w_b = nullptr; a.S_w = nullptr; a.jac = nullptr;
+    return a;
+}
+
+static int kin_launch(pfc_context *h, int n_scene, const double *q, const double *v, double *x_w_b, double *twist_w_b, double *jac,
+                      hipStream_t st) {
+    const KinHost &K = h->kin;
+    { const int rc = kin_upload_tables(h, st); if (rc != PFC_OK) return rc; }
+    const bool want_jac = jac && K.nv > 0;
+    if (!x_w_b && !twist_w_b && !want_jac) return PFC_OK;
+    if (want_jac) HIP_TRY(h, h->kin_sw.ensure((size_t)n_scene * K.nv * 6));
+    KinArgs a = kin_table_args(h, n_scene, q, v);
+    a.x_w_b = x_w_b; a.twist_w_b = twist_w_b; a.S_w = want_jac ? h->kin_sw.p : nullptr; a.jac = jac;
     const long long lanes = (long long)n_scene * K.n_body;
     hipLaunchKernelGGL(k_kinematics, dim3((unsigned)((lanes + kKinWave - 1) / kKinWave)), dim3(kKinWave), 0, st, a);
     HIP_TRY(h, hipGetLastError());
@@ -3547,6 +3563,148 @@ int pfc_eval_state(pfc_handle h, int n_items, const int *ins_ids, const int *sce
                          counts);
     if (rc != PFC_OK || !scatter) return rc;
     return pfc_scatter_generalized(h, n_items, wrench, x_w_r2, body_1, body_2, scene, n_scene, n_scene * n_body, nv, jac, f);
+}
+
+// ---- Dual kinematics: partials of the body states and Jacobians (the second half of pfc_kin.h) ----------------------------------
+// Argument and state checks of every form: those of pfc_kinematics, n_dir, and the grids of the two Dual kernels.
+static int kin_dual_check_args(pfc_context *h, const char *who, int n_scene, int n_dir, const double *q, const double *v, bool want_twist) {
+    const int rc = kin_check_args(h, who, n_scene, q, v, want_twist);
+    if (rc != PFC_OK) return rc;
+    if (n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "%s: n_dir must be in 1..16", who);
+    if (((long long)n_scene * h->kin.n_body * n_dir * std::max(h->kin.nv, 1) + kKinWave - 1) / kKinWave >= (1ll << 31))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: n_scene n_body n_dir nv must be below 2^37", who);
+    return PFC_OK;
+}
+
+// The tables' upload if they are stale, dS_w grown if Jacobian partials are wanted and it is too small, and the kernels, on st.
+// Every pointer is a device pointer; an output that is null is not written, and the kernel only it needs is not launched.
+static int kin_dual_launch(pfc_context *h, int n_scene, int n_dir, const double *q, const double *v, const double *dq, const double *dv,
+                           double *dx_w_b, double *dtwist_w_b, double *djac, hipStream_t st) {
+    const KinHost &K = h->kin;
+    { const int rc = kin_upload_tables(h, st); if (rc != PFC_OK) return rc; }
+    const bool want_jac = djac && K.nv > 0;
+    if (!dx_w_b && !dtwist_w_b && !want_jac) return PFC_OK;
+    if (want_jac) HIP_TRY(h, h->kin_dsw.ensure((size_t)n_scene * n_dir * K.nv * 6));
+    KinDualArgs a;
+    a.k = kin_table_args(h, n_scene, q, v);
+    a.n_dir = n_dir; a.dq = dq; a.dv = dv; a.dx_w_b = dx_w_b; a.dtwist_w_b = dtwist_w_b;
+    a.dS_w = want_jac ? h->kin_dsw.p : nullptr; a.djac = djac;
+    const long long lanes = (long long)n_scene * K.n_body * n_dir;
+    hipLaunchKernelGGL(k_kinematics_dual, dim3((unsigned)((lanes + kKinWave - 1) / kKinWave)), dim3(kKinWave), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    if (want_jac) {
+        const long long tot = lanes * K.nv;
+        hipLaunchKernelGGL(k_kin_jacobian_dual, dim3((unsigned)((tot + kKinJacBlock - 1) / kKinJacBlock)), dim3(kKinJacBlock), 0, st, a);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return PFC_OK;
+}
+
+int pfc_kinematics_dual_device(pfc_handle h, int n_scene, int n_dir, const double *d_q, const double *d_v, const double *d_dq,
+                               const double *d_dv, double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_kinematics_dual_device(c, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_dx_w_b, d_dtwist_w_b, d_djac, stream); });
+    const int rc = kin_dual_check_args(h, "pfc_kinematics_dual_device", n_scene, n_dir, d_q, d_v, d_dtwist_w_b != nullptr);
+    if (rc != PFC_OK || n_scene == 0) return rc;
+    return kin_dual_launch(h, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_dx_w_b, d_dtwist_w_b, d_djac, stream ? (hipStream_t)stream : h->stream);
+}
+
+int pfc_kinematics_dual(pfc_handle h, int n_scene, int n_dir, const double *q, const double *v, const double *dq, const double *dv,
+                        double *dx_w_b, double *dtwist_w_b, double *djac) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_kinematics_dual(c, n_scene, n_dir, q, v, dq, dv, dx_w_b, dtwist_w_b, djac); });
+    int rc = kin_dual_check_args(h, "pfc_kinematics_dual", n_scene, n_dir, q, v, dtwist_w_b != nullptr);
+    if (rc != PFC_OK || n_scene == 0) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t ns = (size_t)n_scene, nk = ns * n_dir, nbk = ns * h->kin.n_body * n_dir;
+    Stage sg(h->stage, h->stream);
+    const int k_q = sg.in(q, ns * h->kin.nq), k_v = sg.in(v, ns * h->kin.nv), k_dq = sg.in(dq, nk * h->kin.nq), k_dv = sg.in(dv, nk * h->kin.nv);
+    const int k_x = sg.out(dx_w_b, nbk * 12), k_tw = sg.out(dtwist_w_b, nbk * 6), k_j = sg.out(djac, nbk * h->kin.nv * 6);
+    HIP_TRY(h, sg.commit());
+    rc = kin_dual_launch(h, n_scene, n_dir, sg.at<double>(k_q), sg.at<double>(k_v), sg.at<double>(k_dq), sg.at<double>(k_dv),
+                         sg.at<double>(k_x), sg.at<double>(k_tw), sg.at<double>(k_j), sg.st);
+    if (rc != PFC_OK) return rc;
+    HIP_TRY(h, sg.finish());
+    return PFC_OK;
+}
+
+// What both chained Dual calls check before anything is launched or written: eval_state_check, n_dir and the Dual grids, and what the
+// Dual scatter would refuse.
+static int eval_dual_state_check(pfc_context *c, const char *who, int n_items, int n_dir, const int *ins_ids, const int *scene, int n_scene,
+                                 const double *q, const double *v, bool scatter) {
+    int rc = eval_state_check(c, who, n_items, ins_ids, scene, n_scene, false, q, v);
+    if (rc != PFC_OK) return rc;
+    if ((rc = kin_dual_check_args(c, who, n_scene, n_dir, q, v, true)) != PFC_OK) return rc;
+    if (scatter && (long long)n_scene * n_items >= (1ll << 31)) return fail(c, PFC_ERR_BAD_ARG, "%s: n_scene * n_items must be below 2^31", who);
+    return PFC_OK;
+}
+
+int pfc_eval_dual_state_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
+                               const double *d_q, const double *d_v, const double *d_dq, const double *d_dv,
+                               const double *d_s, const double *d_ds,
+                               double *d_x_w_b, double *d_twist_w_b, double *d_jac,
+                               double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac,
+                               double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
+                               double *d_dpose, double *d_dtwist, double *d_dx_w_r2,
+                               double *d_wrench, double *d_sdot, double *d_dwrench, double *d_dsdot, int *d_counts,
+                               double *d_f, double *d_df, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    const char *who = "pfc_eval_dual_state_device";
+    pfc_context *c = h->multi ? h->multi->shard[0] : h;
+    const bool scatter = d_df && c->kin.nv > 0;
+    int rc = on_shard(h, c, [&](pfc_context *c1) {
+        return eval_dual_state_check(c1, who, n_items, n_dir, d_ins_ids, d_scene, n_scene, d_q, d_v, scatter); });
+    if (rc != PFC_OK) return rc;
+    const int n_body = c->kin.n_body, nv = c->kin.nv;
+    if (!d_x_w_b || !d_twist_w_b || !d_dx_w_b || !d_dtwist_w_b || !d_pose || !d_twist || !d_dpose || !d_dtwist || !d_wrench || !d_sdot ||
+        !d_dwrench || !d_dsdot || (scatter && (!d_jac || !d_djac || !d_x_w_r2 || !d_dx_w_r2 || !d_body_1 || !d_body_2)))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    if ((rc = pfc_kinematics_device(h, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_jac, stream)) != PFC_OK) return rc;
+    rc = pfc_kinematics_dual_device(h, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_dx_w_b, d_dtwist_w_b, d_djac, stream);
+    if (rc != PFC_OK) return rc;
+    rc = pfc_eval_dual_bodies_device(h, n_items, n_dir, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b, d_s,
+                                     d_ds, d_pose, d_twist, d_x_w_r2, d_body_1, d_body_2, d_dpose, d_dtwist, d_dx_w_r2, d_wrench, d_sdot,
+                                     d_dwrench, d_dsdot, d_counts, stream);
+    if (rc != PFC_OK || !scatter) return rc;
+    return pfc_scatter_generalized_dual_device(h, n_items, n_dir, d_wrench, d_dwrench, d_x_w_r2, d_dx_w_r2, d_body_1, d_body_2, d_scene,
+                                               n_scene, nv, d_jac, d_djac, d_f, d_df, 0, stream);
+}
+
+int pfc_eval_dual_state_device_more(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
+                                    const double *d_q, const double *d_v, const double *d_dq, const double *d_dv, const double *d_ds,
+                                    const double *d_x_w_b, const double *d_twist_w_b, const double *d_jac,
+                                    double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac,
+                                    const double *d_x_w_r2, const int *d_body_1, const int *d_body_2, const double *d_wrench,
+                                    double *d_dpose, double *d_dtwist, double *d_dx_w_r2, double *d_dwrench, double *d_dsdot,
+                                    double *d_df, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    const char *who = "pfc_eval_dual_state_device_more";
+    pfc_context *c = h->multi ? h->multi->shard[0] : h;
+    const bool scatter = d_df && c->kin.nv > 0;
+    int rc = on_shard(h, c, [&](pfc_context *c1) {
+        return eval_dual_state_check(c1, who, n_items, n_dir, d_ins_ids, d_scene, n_scene, d_q, d_v, scatter); });
+    if (rc != PFC_OK) return rc;
+    const int n_body = c->kin.n_body, nv = c->kin.nv;
+    if (!h->multi) {      // _more's own preconditions, before the partials are written
+        if (!h->device_kept())
+            return fail(h, PFC_ERR_STATE, "%s: no checked pfc_eval_dual_device evaluation on this handle to extend", who);
+        if (n_items != h->kept.n)
+            return fail(h, PFC_ERR_BAD_ARG, "%s: n_items is %d, the kept evaluation has %d items", who, n_items, h->kept.n);
+    }
+    if (!d_x_w_b || !d_twist_w_b || !d_dx_w_b || !d_dtwist_w_b || !d_dpose || !d_dtwist || !d_dwrench || !d_dsdot ||
+        (scatter && (!d_jac || !d_djac || !d_x_w_r2 || !d_dx_w_r2 || !d_body_1 || !d_body_2 || !d_wrench)))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    rc = pfc_kinematics_dual_device(h, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_dx_w_b, d_dtwist_w_b, d_djac, stream);
+    if (rc != PFC_OK) return rc;
+    rc = pfc_eval_dual_bodies_device_more(h, n_items, n_dir, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b,
+                                          d_ds, d_dpose, d_dtwist, d_dx_w_r2, d_dwrench, d_dsdot, stream);
+    if (rc != PFC_OK || !scatter) return rc;
+    return pfc_scatter_generalized_dual_device(h, n_items, n_dir, d_wrench, d_dwrench, d_x_w_r2, d_dx_w_r2, d_body_1, d_body_2, d_scene,
+                                               n_scene, nv, d_jac, d_djac, nullptr, d_df, 0, stream);
 }
 
 // The Dual evaluation, with the broadphase pose of m.float's state where bp_pose is given (calcTriTetIntersections!,

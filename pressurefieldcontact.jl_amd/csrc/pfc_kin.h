@@ -7,8 +7,8 @@
 //
 // Arithmetic (the contract, stated in include/pfc.h): plain Float64, every 3-term dot product summed left to right, no fma (the
 // build has -ffp-contract=off), a translation added last; the world goes through the same expressions with R = I, t = 0 and a zero
-// twist.  One statement over the number type T (kin_joint, kin_compose, kin_twist_add, kin_column), as bodies_item<T> is: a Dual
-// instantiation needs kin_lit, kin_sincos and operator/ on its type and restates nothing.
+// twist.  One statement over the number type T (kin_joint, kin_compose, kin_twist_add, kin_column), as bodies_item<T> is: the Dual
+// instantiation (the second half of this file) adds kin_lit, kin_sincos and operator/ on its type and restates nothing.
 // The kernels:
 //   k_kinematics    one lane per (scene, body), one wave per workgroup.  The lane walks its root -> body path from the flattened
 //                   path table, repeating its ancestors' expressions in their order -- so it gets their bytes, without a
@@ -176,6 +176,113 @@ __global__ void __launch_bounds__(kKinJacBlock) k_kin_jacobian(KinArgs g) {
     double *out = g.jac + 6 * (size_t)i;
     if (g.anc[r]) {
         const double *in = g.S_w + 6 * ((size_t)sc * (size_t)g.nv + (size_t)c);
+#pragma unroll
+        for (int e = 0; e < 6; ++e) out[e] = in[e];
+    } else {
+#pragma unroll
+        for (int e = 0; e < 6; ++e) out[e] = 0.0;
+    }
+}
+
+// ---- the Dual half: partials of the poses, twists and Jacobians (pfc_kinematics_dual[_device], pfc_eval_dual_state_device[_more]) ----
+// What the reference gets from RigidBodyDynamics on the Dual state of a Jacobian chunk (src/radau/radau_functions.jl:2-14): the
+// statements above instantiated on ScatDual (pfc_scatter.h), the (value, one partial) pair with ForwardDiff's rules.  Nothing is
+// restated and nothing is skipped for a zero seed: a direction that seeds none of a lane's joints runs the same expressions, and its
+// partials are the signed zeros of that arithmetic.  Mechanism constants (x_p_j, the axes) and literals carry a zero partial.
+// The kernels:
+//   k_kinematics_dual    one lane per (scene, body, direction), one wave per workgroup, the walk of k_kinematics on ScatDual: the
+//                        value parts are k_kinematics' bytes and are not stored; the partial parts of the pose (12), the twist (6)
+//                        and the lane's own joint's columns (dS_w, n_scene x n_dir x nv x 6) are.
+//   k_kin_jacobian_dual  one lane per (scene, body, direction, coordinate): six doubles copied from dS_w where anc says so, +0.0 six
+//                        times otherwise.
+// No atomics, no dependency between lanes, plain per-lane stores; n_scene and n_dir bound the grids.
+template <> __device__ inline ScatDual kin_lit<ScatDual>(double x) { return {x, 0.0}; }
+__device__ inline void kin_sincos(ScatDual th, ScatDual &c, ScatDual &s) {
+    const double sv = sin(th.v), cv = cos(th.v);
+    s = ScatDual{sv, cv * th.d};
+    c = ScatDual{cv, -(sv * th.d)};
+}
+
+struct KinDualArgs {
+    KinArgs k;                          // the tables, n_scene, q and v (values); its outputs are not read
+    int n_dir;
+    const double *dq, *dv;              // n_scene x n_dir x nq, x nv: the seeds; each may be NULL (zeros)
+    double *dx_w_b, *dtwist_w_b;        // n_scene n_body x n_dir x 12, x 6; each may be NULL (not wanted)
+    double *dS_w;                       // n_scene x n_dir x nv x 6, or NULL (no Jacobian partials wanted)
+    double *djac;                       // n_scene n_body x n_dir x nv x 6 (k_kin_jacobian_dual)
+};
+
+__global__ void __launch_bounds__(kKinWave) k_kinematics_dual(KinDualArgs h) {
+    const KinArgs &g = h.k;
+    const long long i = (long long)blockIdx.x * kKinWave + (long long)threadIdx.x;      // (scene n_body + body) n_dir + dir
+    if (i >= (long long)g.n_scene * g.n_body * h.n_dir) return;
+    const int dir = (int)(i % h.n_dir);
+    const long long sb = i / h.n_dir;
+    const int sc = (int)(sb / g.n_body), b = (int)(sb % g.n_body);
+    const size_t row = (size_t)sc * (size_t)h.n_dir + (size_t)dir;
+    const double *q = g.q + (size_t)sc * (size_t)g.nq;
+    const double *v = g.v ? g.v + (size_t)sc * (size_t)g.nv : nullptr;
+    const double *dq = h.dq ? h.dq + row * (size_t)g.nq : nullptr;
+    const double *dv = h.dv ? h.dv + row * (size_t)g.nv : nullptr;
+    ScatDual x[12], tw[6], xj[12], tj[6], xa[12], xn[12], o[6], xp[12], ax[3], qj[6], vj[6];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) x[e] = kin_lit<ScatDual>((e == 0 || e == 4 || e == 8) ? 1.0 : 0.0);      // the world
+#pragma unroll
+    for (int e = 0; e < 6; ++e) tw[e] = kin_lit<ScatDual>(0.0);
+    for (int k = g.path_off[b]; k < g.path_off[b + 1]; ++k) {
+        const int a = g.path[k], type = g.jtype[a], n = kin_joint_nq(type), qo = g.qoff[a], vo = g.voff[a];
+#pragma unroll
+        for (int e = 0; e < 12; ++e) xp[e] = kin_lit<ScatDual>(g.x_p_j[12 * (size_t)a + e]);
+#pragma unroll
+        for (int e = 0; e < 3; ++e) ax[e] = kin_lit<ScatDual>(g.axis[3 * (size_t)a + e]);
+#pragma unroll
+        for (int e = 0; e < 6; ++e) {      // the joint's own coordinates only: nothing is read past the state's rows
+            qj[e] = e < n ? ScatDual{q[qo + e], dq ? dq[qo + e] : 0.0} : kin_lit<ScatDual>(0.0);
+            vj[e] = (v && e < n) ? ScatDual{v[vo + e], dv ? dv[vo + e] : 0.0} : kin_lit<ScatDual>(0.0);
+        }
+        kin_joint<ScatDual>(type, ax, qj, vj, xj, tj);      // (without v, vj is the literal zero the statement takes for a null v)
+        kin_compose<ScatDual>(xp, xj, xa);
+        kin_compose<ScatDual>(x, xa, xn);
+#pragma unroll
+        for (int e = 0; e < 12; ++e) x[e] = xn[e];
+        kin_to_world<ScatDual>(x, tj, o);
+#pragma unroll
+        for (int e = 0; e < 6; ++e) tw[e] = tw[e] + o[e];
+    }
+    if (h.dx_w_b) {
+        double *out = h.dx_w_b + 12 * (size_t)i;
+#pragma unroll
+        for (int e = 0; e < 12; ++e) out[e] = x[e].d;
+    }
+    if (h.dtwist_w_b) {
+        double *out = h.dtwist_w_b + 6 * (size_t)i;
+#pragma unroll
+        for (int e = 0; e < 6; ++e) out[e] = tw[e].d;
+    }
+    if (h.dS_w) {
+        const int type = g.jtype[b], n = kin_joint_nq(type);      // ax is body b's: the path ends with b
+        for (int k = 0; k < n; ++k) {
+            kin_column<ScatDual>(type, k, ax, x, o);
+            double *out = h.dS_w + 6 * (row * (size_t)g.nv + (size_t)(g.voff[b] + k));
+#pragma unroll
+            for (int e = 0; e < 6; ++e) out[e] = o[e].d;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kKinJacBlock) k_kin_jacobian_dual(KinDualArgs h) {
+    const KinArgs &g = h.k;
+    const long long i = (long long)blockIdx.x * kKinJacBlock + (long long)threadIdx.x;      // ((scene n_body + body) n_dir + dir) nv + c
+    if (i >= (long long)g.n_scene * g.n_body * h.n_dir * g.nv) return;
+    const int c = (int)(i % g.nv);
+    const long long t = i / g.nv;
+    const int dir = (int)(t % h.n_dir);
+    const long long sb = t / h.n_dir;
+    const long long sc = sb / g.n_body;
+    const int b = (int)(sb % g.n_body);
+    double *out = h.djac + 6 * (size_t)i;
+    if (g.anc[(size_t)b * (size_t)g.nv + (size_t)c]) {
+        const double *in = h.dS_w + 6 * (((size_t)sc * (size_t)h.n_dir + (size_t)dir) * (size_t)g.nv + (size_t)c);
 #pragma unroll
         for (int e = 0; e < 6; ++e) out[e] = in[e];
     } else {

@@ -25,6 +25,11 @@ __device__ inline ScatDual operator+(ScatDual a, ScatDual b) { return {a.v + b.v
 __device__ inline ScatDual operator-(ScatDual a, ScatDual b) { return {a.v - b.v, a.d - b.d}; }
 __device__ inline ScatDual operator-(ScatDual a) { return {-a.v, -a.d}; }
 __device__ inline ScatDual operator*(ScatDual a, ScatDual b) { return {a.v * b.v, a.d * b.v + a.v * b.d}; }
+// The quotient in the order of _div_partials through _mul_partials: d(a / b) = da (1 / b) + db (-(a / b^2)).  (Written as recalled:
+// bit parity with ForwardDiff for this rule is unpinned)  Used by the Dual kinematics (pfc_kin.h).
+__device__ inline ScatDual operator/(ScatDual a, ScatDual b) {
+    return {a.v / b.v, a.d * (1.0 / b.v) + b.d * (-(a.v / (b.v * b.v)))};
+}
 
 // RigidBodyDynamics transform(wrench, x_rw_r2) (the C oracle's statements): w [ang; lin], x = R (9, column-major), t (3);
 // o = [R ang + t x lin; R lin].

@@ -887,6 +887,87 @@ class MechanismScenario:
                                                      d_pose or None, d_twist or None, d_x_w_r2 or None, d_body_1 or None, d_body_2 or None,
                                                      d_wrench or None, d_sdot or None, d_counts or None, d_f or None, stream or None))
 
+    def _seed_arrays(self, n_scene, nq, nv, dq, dv):
+        """(n_dir, dq (n_scene,n_dir,nq) or None, dv (n_scene,n_dir,nv) or None): the seed directions of a Jacobian chunk."""
+        if dq is None and dv is None:
+            raise ValueError("one of dq and dv must be given: they carry n_dir")
+        out, n_dir = [], None
+        for a, w, name in ((dq, nq, "dq"), (dv, nv, "dv")):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.ndim == 2:
+                    a = a[None]
+                if a.ndim != 3 or a.shape[0] != n_scene or a.shape[2] != w or n_dir not in (None, a.shape[1]):
+                    raise ValueError(f"{name} must be (n_dir, {w}) or (n_scene, n_dir, {w})")
+                n_dir = a.shape[1]
+            out.append(a)
+        return n_dir, out[0], out[1]
+
+    def kinematics_dual(self, q, v, dq, dv, want_jac: bool = True):
+        """The partials of kinematics' three outputs for the seed directions of a Jacobian chunk (pfc_kinematics_dual, host buffers,
+        synchronous).  q, v as kinematics; dq (n_dir,nq) or (n_scene,n_dir,nq) and dv likewise with nv: the partials of the state,
+        either may be None (zeros), not both (n_dir comes from them).  Returns d_x_w_b (n_scene,n_body,n_dir,12), d_twist_w_b
+        (n_scene,n_body,n_dir,6) and d_jac (n_scene n_body, n_dir, nv, 6) (None without want_jac): the inputs of
+        dual_seeds_from_bodies and of scatter_generalized_dual."""
+        n_scene, n_body, nv, q_a, v_a = self._state_arrays(q, v)
+        n_dir, dq_a, dv_a = self._seed_arrays(n_scene, q_a.shape[1], nv, dq, dv)
+        dx = np.zeros((n_scene, n_body, n_dir, 12)); dtw = np.zeros((n_scene, n_body, n_dir, 6))
+        djac = np.zeros((n_scene * n_body, n_dir, nv, 6)) if want_jac else None
+        self._check(_lib.lib().pfc_kinematics_dual(
+            self._h, n_scene, n_dir, q_a.ctypes.data_as(_dp), v_a.ctypes.data_as(_dp),
+            dq_a.ctypes.data_as(_dp) if dq_a is not None else None, dv_a.ctypes.data_as(_dp) if dv_a is not None else None,
+            dx.ctypes.data_as(_dp), dtw.ctypes.data_as(_dp), djac.ctypes.data_as(_dp) if want_jac else None))
+        return dx, dtw, djac
+
+    def kinematics_dual_device(self, n_scene: int, n_dir: int, d_q: int, d_v: int, d_dq: int, d_dv: int, d_dx_w_b: int,
+                               d_dtwist_w_b: int, d_djac: int, stream: int = 0):
+        """pfc_kinematics_dual_device: raw device addresses (0: NULL for either seed array and any output not wanted); asynchronous on
+        `stream`, not an evaluation, no check() needed."""
+        self._check(_lib.lib().pfc_kinematics_dual_device(self._h, int(n_scene), int(n_dir), d_q or None, d_v or None, d_dq or None,
+                                                          d_dv or None, d_dx_w_b or None, d_dtwist_w_b or None, d_djac or None,
+                                                          stream or None))
+
+    def eval_dual_state_device(self, n_items: int, n_dir: int, d_ins_ids: int, d_scene: int, n_scene: int, d_q: int, d_v: int,
+                               d_dq: int, d_dv: int, d_s: int, d_ds: int, d_x_w_b: int, d_twist_w_b: int, d_jac: int, d_dx_w_b: int,
+                               d_dtwist_w_b: int, d_djac: int, d_pose: int, d_twist: int, d_x_w_r2: int, d_body_1: int, d_body_2: int,
+                               d_dpose: int, d_dtwist: int, d_dx_w_r2: int, d_wrench: int, d_sdot: int, d_dwrench: int, d_dsdot: int,
+                               d_counts: int, d_f: int, d_df: int, stream: int = 0):
+        """pfc_eval_dual_state_device: kinematics_device, kinematics_dual_device, eval_dual_bodies_device and
+        scatter_generalized_dual_device (d_df 0: no scatter) on one stream; asynchronous, follow with check() (re-issue on
+        ERR_OVERFLOW)."""
+        p = lambda a: a or None
+        self._check(_lib.lib().pfc_eval_dual_state_device(
+            self._h, int(n_items), int(n_dir), p(d_ins_ids), p(d_scene), int(n_scene), p(d_q), p(d_v), p(d_dq), p(d_dv), p(d_s), p(d_ds),
+            p(d_x_w_b), p(d_twist_w_b), p(d_jac), p(d_dx_w_b), p(d_dtwist_w_b), p(d_djac), p(d_pose), p(d_twist), p(d_x_w_r2),
+            p(d_body_1), p(d_body_2), p(d_dpose), p(d_dtwist), p(d_dx_w_r2), p(d_wrench), p(d_sdot), p(d_dwrench), p(d_dsdot),
+            p(d_counts), p(d_f), p(d_df), stream or None))
+
+    def eval_dual_state_device_more(self, n_items: int, n_dir: int, d_ins_ids: int, d_scene: int, n_scene: int, d_q: int, d_v: int,
+                                    d_dq: int, d_dv: int, d_ds: int, d_x_w_b: int, d_twist_w_b: int, d_jac: int, d_dx_w_b: int,
+                                    d_dtwist_w_b: int, d_djac: int, d_x_w_r2: int, d_body_1: int, d_body_2: int, d_wrench: int,
+                                    d_dpose: int, d_dtwist: int, d_dx_w_r2: int, d_dwrench: int, d_dsdot: int, d_df: int,
+                                    stream: int = 0):
+        """pfc_eval_dual_state_device_more: kinematics_dual_device, eval_dual_bodies_device_more and the Dual scatter into d_df (0: no
+        scatter) for a later chunk of the Jacobian at the kept point; reads the value buffers the first chunk left, writes only
+        partials; asynchronous, follow with check()."""
+        p = lambda a: a or None
+        self._check(_lib.lib().pfc_eval_dual_state_device_more(
+            self._h, int(n_items), int(n_dir), p(d_ins_ids), p(d_scene), int(n_scene), p(d_q), p(d_v), p(d_dq), p(d_dv), p(d_ds),
+            p(d_x_w_b), p(d_twist_w_b), p(d_jac), p(d_dx_w_b), p(d_dtwist_w_b), p(d_djac), p(d_x_w_r2), p(d_body_1), p(d_body_2),
+            p(d_wrench), p(d_dpose), p(d_dtwist), p(d_dx_w_r2), p(d_dwrench), p(d_dsdot), p(d_df), stream or None))
+
+    def force_all_elastic_intersections_dual_state(self, q, v, s, dq, dv, ds=None, ins_ids: Optional[Sequence[int]] = None, scene=None):
+        """From the joint state and its seed directions to f_generalized and its partials (host arrays, synchronous; composed here
+        from kinematics, kinematics_dual, force_all_elastic_intersections_dual_bodies and scatter_generalized_dual, the calls
+        pfc_eval_dual_state_device chains on the device).  q, v, dq, dv as kinematics_dual; s, ds, ins_ids, scene as
+        force_all_elastic_intersections_dual_bodies.  Returns (wrench, sdot, d_wrench, d_sdot, counts, f (n_scene,nv),
+        d_f (n_scene,n_dir,nv), items: BodyItems, seeds: BodySeeds, (x_w_b, twist_w_b, jac), (d_x_w_b, d_twist_w_b, d_jac))."""
+        x, tw, jac = self.kinematics(q, v)
+        dx, dtw, djac = self.kinematics_dual(q, v, dq, dv)
+        wrench, sdot, dw, dsd, counts, it, sd = self.force_all_elastic_intersections_dual_bodies(x, tw, s, dx, dtw, ds, ins_ids, scene)
+        f, d_f = self.scatter_generalized_dual(wrench, dw, it.x_w_r2, sd.d_x_w_r2, it.body_1, it.body_2, jac, djac, scene, x.shape[0])
+        return wrench, sdot, dw, dsd, counts, f, d_f, it, sd, (x, tw, jac), (dx, dtw, djac)
+
     def dual_seeds_from_bodies(self, x_w_b, twist_w_b, d_x_w_b, d_twist_w_b, ins_ids: Optional[Sequence[int]] = None,
                                scene=None) -> BodySeeds:
         """The Dual seeds of items_from_bodies' items from the partials of the bodies' world states (pfc_dual_seeds_from_bodies, host
@@ -1199,6 +1280,78 @@ def joint_kinematics(parent, joint_type, x_p_j, axis, q, v):
         J[b, off[b]:off[b + 1]] = Sw.T
     x = np.array([np.concatenate([h[:3, :3].reshape(-1, order="F"), h[:3, 3]]) for h in H])
     return x, tw, J
+
+
+def joint_kinematics_partials(parent, joint_type, x_p_j, axis, q, v, dq, dv):
+    """The directional derivatives of joint_kinematics' three outputs along the seed directions of a Jacobian chunk, for one scene and
+    all directions at once: the matrix form of the derivative in joint_kinematics' formulation (derivatives of Rodrigues' formula and
+    of the MRP rotation, the product rule on the 4x4 homogeneous products and the 6x6 adjoints), deliberately not the scalar Dual
+    statement of pfc_kinematics_dual, which the tests compare with it.  Arguments as joint_kinematics, plus dq (n_dir,nq) and dv
+    (n_dir,nv), the partials of the state (None: zeros; not both).  Returns d_x_w_b (n_body,n_dir,12), d_twist_w_b (n_body,n_dir,6),
+    d_jac (n_body,n_dir,nv,6)."""
+    parent = np.asarray(parent, dtype=np.int64).reshape(-1)
+    n_body = parent.size
+    joint_type = np.asarray(joint_type, dtype=np.int64).reshape(-1)
+    x_p_j = np.asarray(x_p_j, dtype=np.float64).reshape(n_body, 12)
+    axis = np.zeros((n_body, 3)) if axis is None else np.asarray(axis, dtype=np.float64).reshape(n_body, 3)
+    ndof = [{_lib.JOINT_FIXED: 0, _lib.JOINT_REVOLUTE: 1, _lib.JOINT_PRISMATIC: 1, _lib.JOINT_FLOATING_MRP: 6}[int(t)] for t in joint_type]
+    off = np.concatenate([[0], np.cumsum(ndof)]).astype(int)
+    nv = int(off[-1])
+    q = np.asarray(q, dtype=np.float64).reshape(nv); v = np.asarray(v, dtype=np.float64).reshape(nv)
+    if dq is None and dv is None:
+        raise ValueError("one of dq and dv must be given: they carry n_dir")
+    dq = None if dq is None else np.asarray(dq, dtype=np.float64).reshape(-1, nv)
+    dv = None if dv is None else np.asarray(dv, dtype=np.float64).reshape(-1, nv)
+    n_dir = (dq if dq is not None else dv).shape[0]
+    dq = np.zeros((n_dir, nv)) if dq is None else dq
+    dv = np.zeros((n_dir, nv)) if dv is None else dv
+    hat_all = lambda A: np.stack([_hat(a) for a in A])      # (n_dir,3) -> (n_dir,3,3)
+    H, dH = [None] * n_body, [None] * n_body
+    tw, dtw, dJ = np.zeros((n_body, 6)), np.zeros((n_body, n_dir, 6)), np.zeros((n_body, n_dir, nv, 6))
+    for b in range(n_body):
+        sl = slice(off[b], off[b + 1])
+        qb, vb, dqb, dvb, a = q[sl], v[sl], dq[:, sl], dv[:, sl], axis[b]
+        Xj, dXj, S = np.eye(4), np.zeros((n_dir, 4, 4)), np.zeros((6, ndof[b]))
+        if joint_type[b] == _lib.JOINT_REVOLUTE:
+            K = _hat(a)
+            Xj[:3, :3] = np.eye(3) + np.sin(qb[0]) * K + (1.0 - np.cos(qb[0])) * (K @ K)
+            dXj[:, :3, :3] = dqb[:, 0, None, None] * (np.cos(qb[0]) * K + np.sin(qb[0]) * (K @ K))
+            S[:3, 0] = a
+        elif joint_type[b] == _lib.JOINT_PRISMATIC:
+            Xj[:3, 3] = a * qb[0]
+            dXj[:, :3, 3] = dqb[:, 0, None] * a
+            S[3:, 0] = a
+        elif joint_type[b] == _lib.JOINT_FLOATING_MRP:
+            p, P = qb[:3], _hat(qb[:3])
+            p2 = float(p @ p)
+            N, den = 4.0 * (1.0 - p2) * P + 8.0 * (P @ P), 1.0 + p2
+            Xj[:3, :3] = np.eye(3) + N / den ** 2
+            Xj[:3, 3] = qb[3:]
+            dP = hat_all(dqb[:, :3])
+            dp2 = 2.0 * (dqb[:, :3] @ p)
+            dN = 4.0 * (1.0 - p2) * dP - 4.0 * dp2[:, None, None] * P + 8.0 * (dP @ P + P @ dP)
+            dXj[:, :3, :3] = dN / den ** 2 - (2.0 * dp2 / den ** 3)[:, None, None] * N
+            dXj[:, :3, 3] = dqb[:, 3:]
+            S = np.eye(6)
+        Xp = np.eye(4)
+        Xp[:3, :3] = x_p_j[b, :9].reshape(3, 3, order="F"); Xp[:3, 3] = x_p_j[b, 9:]
+        Hp = H[parent[b]] if parent[b] >= 0 else np.eye(4)
+        dHp = dH[parent[b]] if parent[b] >= 0 else np.zeros((n_dir, 4, 4))
+        B = Hp @ Xp
+        H[b] = B @ Xj
+        dH[b] = (dHp @ Xp) @ Xj + B @ dXj
+        R, t, dR, dt = H[b][:3, :3], H[b][:3, 3], dH[b][:, :3, :3], dH[b][:, :3, 3]
+        Ad, dAd = np.zeros((6, 6)), np.zeros((n_dir, 6, 6))
+        Ad[:3, :3] = R; Ad[3:, 3:] = R; Ad[3:, :3] = _hat(t) @ R
+        dAd[:, :3, :3] = dR; dAd[:, 3:, 3:] = dR; dAd[:, 3:, :3] = hat_all(dt) @ R + _hat(t) @ dR
+        Sw, dSw = Ad @ S, dAd @ S
+        tw[b] = (tw[parent[b]] if parent[b] >= 0 else 0.0) + Sw @ vb
+        dtw[b] = (dtw[parent[b]] if parent[b] >= 0 else 0.0) + dSw @ vb + dvb @ Sw.T
+        if parent[b] >= 0:
+            dJ[b] = dJ[parent[b]]
+        dJ[b, :, sl] = dSw.transpose(0, 2, 1)
+    dx = np.array([np.concatenate([d[:, :3, :3].transpose(0, 2, 1).reshape(n_dir, 9), d[:, :3, 3]], axis=1) for d in dH])
+    return dx, dtw, dJ
 
 
 def local_jacobian_tangent(L, pose) -> np.ndarray:
