@@ -523,6 +523,105 @@ int pfc_eval_state(pfc_handle h, int n_items, const int *ins_ids, const int *sce
                    double *wrench, double *sdot, int *counts, double *f);
 
 /*
+ * Forward dynamics from joint states: what configuration_derivative!, mass_matrix!, dynamics_bias!, sum_all_forces!, cholesky! and
+ * ldiv! (src/contact_algorithms_non_friction.jl:18-52) give the reference per evaluation -- qdot, the mass matrix H, the bias c and
+ * vdot = H^-1 ((f - c) + tau) -- formed on the device, so that xx = [qdot; vdot; sdot] follows from x = [q; v; s] without a host that
+ * owns a dynamics library.  The value path; there is no Dual sibling yet.
+ *
+ * pfc_set_inertia gives the bodies' inertias and gravity.  inertia (n_body x 13) holds per body RigidBodyDynamics' SpatialInertia in
+ * the body's own frame: moment (9, column-major, about the frame origin), cross_part = m com (3), mass (1).  gravity (3) is the
+ * gravitational acceleration in world, e.g. (0, 0, -9.81).  Allowed only after pfc_set_mechanism (PFC_ERR_STATE before it); a later
+ * pfc_set_mechanism drops the inertias.  PFC_ERR_BAD_ARG, the message naming the body: n_body different from the mechanism's, a null
+ * table, a negative or non-finite mass, a non-finite entry, a moment with |M_rc - M_cr| > 1e-12 max|M|.  Zero mass is allowed (a dummy
+ * body behind a fixed joint).  A failed call leaves the previous inertias in place.  The table is uploaded with the mechanism's, by
+ * the first call that needs it (one stream synchronisation), on the first device of a multi-device handle.
+ */
+int pfc_set_inertia(pfc_handle h, int n_body, const double *inertia, const double *gravity);
+
+/*
+ * One kernel (one 64-lane workgroup per scene) enqueued on `stream` (NULL = the handle's own) without a host synchronisation:
+ *   d_q, d_v     as pfc_kinematics_device           d_x_w_b, d_twist_w_b  pfc_kinematics_device's outputs for the same (q, v)
+ *   d_qdot       n_scene x nq       OUT configuration_derivative!
+ *   d_H          n_scene x nv x nv  OUT mass_matrix!, the full symmetric matrix, row-major
+ *   d_c          n_scene x nv       OUT dynamics_bias!: H vdot + c = tau + f
+ * Any OUT pointer may be NULL: it is not written and the work it alone needs is not done (d_qdot reads d_q and d_v only; d_H reads
+ * d_x_w_b only; d_c reads d_x_w_b, d_twist_w_b and d_v; PFC_ERR_BAD_ARG if an input an output needs is NULL).  The arithmetic is plain
+ * Float64 without fma, `x` the 3-vector cross product (a x b)_0 = a1 b2 - a2 b1 and cyclic, every 3-term dot product summed left to
+ * right, dot6(a, b) = ((((a0 b0 + a1 b1) + a2 b2) + a3 b3) + a4 b4) + a5 b5; motion vectors and wrenches are [angular; linear] in
+ * world about the world origin:
+ *   qdot.  revolute, prismatic: v.  floating, q = [p; t], v = [w; u] in the frame after: p2 = (p0 p0 + p1 p1) + p2 p2,
+ *     pw = (p0 w0 + p1 w1) + p2 w2;  pdot_r = 0.25 (((1 - p2) w_r + 2 (p x w)_r) + (2 pw) p_r);  tdot_r = (R_r0 u0 + R_r1 u1) + R_r2 u2
+ *     with R the joint rotation R_j(p) of pfc_kinematics_device.
+ *   world inertia of body b, pose (R, t), record (M, cp, m): hc_r = (R_r0 cp0 + R_r1 cp1) + R_r2 cp2;  mt_r = m t_r;  h_r = hc_r + mt_r;
+ *     B_rc = (R_r0 M_0c + R_r1 M_1c) + R_r2 M_2c;  A_rc = (B_r0 R_c0 + B_r1 R_c1) + B_r2 R_c2;  s1 = (t0 hc0 + t1 hc1) + t2 hc2;
+ *     s2 = (t0 mt0 + t1 mt1) + t2 mt2;  for r <= c: J_rc = (A_rc - (hc_r t_c + t_r hc_c)) - mt_r t_c, on the diagonal + (2 s1 + s2)
+ *     added last;  J_cr = J_rc.  I_b = (J, h, m), added componentwise.
+ *   I [w; u] = [((J_r0 w0 + J_r1 w1) + J_r2 w2) + (h x u)_r;  m u_r - (h x w)_r]
+ *   a x_m b = [a_w x b_w;  (a_w x b_u) + (a_u x b_w)]        a x* f = [(a_w x f_n) + (a_u x f_f);  a_w x f_f]
+ *   the columns S_i of pfc_kinematics_device, formed again from d_x_w_b (the same bytes; the handle's column buffer is not read)
+ *   composite inertia Ic_b = I_b + I_d1 + I_d2 + ... over b's descendants in increasing body order, summed left to right
+ *   H[i,j] for j <= i, b = the body whose joint owns i: dot6(S_j, Ic_b S_i) if j's joint lies on the root -> b path, +0.0 otherwise;
+ *     H[j,i] is a copy of H[i,j].
+ *   joint twist jt_b = (S_i0 v_i0 + S_i1 v_i1) + ... over the joint's coordinates (fixed: +0.0 six times)
+ *   a_b = a_parent + (tw_b x_m jt_b) elementwise, from a_world = [+0.0 (3); -g], tw_b = d_twist_w_b's row
+ *   w_b = I_b a_b + (tw_b x* (I_b tw_b)) elementwise;  W_b = w_b + w_d1 + w_d2 + ... as the composite inertia;  c_i = dot6(S_i, W_b)
+ * -- the same bytes on every call, handle and entry point; no atomics.  The call is NOT an evaluation: a kept value pass, Dual reuse,
+ * pfc_check and pfc_last_* are as they were.  n_scene = 0 is a no-op.  PFC_ERR_STATE before pfc_set_inertia; PFC_ERR_BAD_ARG if
+ * 44 n_body + 12.5 nv doubles exceed 64 KiB (the scene's tables live in LDS).  Multi-device handles: the first device.
+ */
+int pfc_dynamics_device(pfc_handle h, int n_scene, const double *d_q, const double *d_v, const double *d_x_w_b, const double *d_twist_w_b,
+                        double *d_qdot, double *d_H, double *d_c, void *stream);
+/* The same with host buffers, synchronous: the same kernel, the same bytes. */
+int pfc_dynamics(pfc_handle h, int n_scene, const double *q, const double *v, const double *x_w_b, const double *twist_w_b,
+                 double *qdot, double *H, double *c);
+
+/*
+ * vdot = H^-1 ((f - c) + tau): sum_all_forces!, cholesky! and ldiv!.  One kernel, one workgroup per scene with L in LDS, enqueued on
+ * `stream`:
+ *   d_H, d_c   pfc_dynamics_device's outputs (the lower triangle of H is read)      d_f  n_scene x nv, f_generalized
+ *   d_tau      n_scene x nv, or NULL: zeros (a controller's or any other generalized force)
+ *   d_vdot     n_scene x nv  OUT            d_info  n_scene OUT, or NULL
+ * The mechanism's nv must not exceed PFC_MAX_NV_SOLVE (one lane per row, L of 64 x 64 doubles = 32 KiB of LDS): PFC_ERR_BAD_ARG
+ * before anything is launched.  LAPACK's bits are not reproduced; the order is this, in plain Float64 without fma, sqrt and /
+ * correctly rounded:
+ *   rhs_i = (f_i - c_i) + tau_i  (tau NULL: + 0.0)
+ *   for j ascending: s_ij = ((H_ij - L_i0 L_j0) - L_i1 L_j1) - ... - L_i,j-1 L_j,j-1 for i >= j;  L_jj = sqrt(s_jj);  L_ij = s_ij / L_jj
+ *   y_i = (((rhs_i - L_i0 y_0) - L_i1 y_1) - ... - L_i,i-1 y_i-1) / L_ii, i ascending
+ *   vdot_i = (((y_i - L_n-1,i vdot_n-1) - L_n-2,i vdot_n-2) - ... - L_i+1,i vdot_i+1) / L_ii, i descending
+ * If a pivot s_jj is not > 0 (NaN included) the scene's whole vdot is NaN and d_info[scene] = j + 1; otherwise d_info[scene] = 0.
+ * That is a per-scene numeric flag, not an error state: other scenes are unaffected and pfc_check is not involved.  Not an
+ * evaluation; n_scene = 0 is a no-op; PFC_ERR_STATE before pfc_set_mechanism (the inertias are not needed).
+ */
+#define PFC_MAX_NV_SOLVE 64
+int pfc_accelerations_device(pfc_handle h, int n_scene, const double *d_H, const double *d_c, const double *d_f, const double *d_tau,
+                             double *d_vdot, int *d_info, void *stream);
+/* The same with host buffers, synchronous: the same kernel, the same bytes. */
+int pfc_accelerations(pfc_handle h, int n_scene, const double *H, const double *c, const double *f, const double *tau, double *vdot,
+                      int *info);
+
+/*
+ * Exactly pfc_eval_state_device with d_f required, then pfc_dynamics_device, then pfc_accelerations_device, on one stream: from
+ * x = [q; v; s] to qdot, vdot and sdot (which stays in d_sdot's rows; the host lays out xx).  All buffers are the caller's; required
+ * are those pfc_eval_state_device requires with d_f, and d_qdot, d_H, d_c, d_vdot; d_tau and d_info may be NULL.  Everything the parts
+ * would refuse -- missing inertias and the nv cap included -- is checked before the first launch.  pfc_check() afterwards as after
+ * pfc_eval_device; on PFC_ERR_OVERFLOW the outputs are undefined and the call is re-issued.
+ */
+int pfc_state_derivative_device(pfc_handle h, int n_items, const int *d_ins_ids, const int *d_scene, int n_scene,
+                                const double *d_q, const double *d_v, const double *d_s, const double *d_tau,
+                                double *d_x_w_b, double *d_twist_w_b, double *d_jac,
+                                double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
+                                double *d_wrench, double *d_sdot, int *d_counts, double *d_f,
+                                double *d_qdot, double *d_H, double *d_c, double *d_vdot, int *d_info, void *stream);
+/* The host-buffer form: pfc_eval_state, pfc_dynamics, pfc_accelerations.  Optional are pfc_eval_state's optional arguments but f, and
+ * tau and info.  Synchronous. */
+int pfc_state_derivative(pfc_handle h, int n_items, const int *ins_ids, const int *scene, int n_scene,
+                         const double *q, const double *v, const double *s, const double *tau,
+                         double *x_w_b, double *twist_w_b, double *jac,
+                         double *pose, double *twist, double *x_w_r2, int *body_1, int *body_2,
+                         double *wrench, double *sdot, int *counts, double *f,
+                         double *qdot, double *H, double *c, double *vdot, int *info);
+
+/*
  * Dual kinematics from joint states: the partials of the bodies' world poses, twists and geometric Jacobians that RigidBodyDynamics
  * gives the reference on the Dual state of a Jacobian chunk (src/radau/radau_functions.jl:2-14), formed on the device from (q, v) and
  * the chunk's seed directions -- the front of the chain state + seeds -> body-state partials -> item seeds ->

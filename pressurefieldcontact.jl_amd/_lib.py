@@ -78,6 +78,14 @@ SIGNATURES = {
     "pfc_eval_state_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 16),
     "pfc_eval_state": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip,
                                  _dp, _dp, _ip, _dp]),
+    "pfc_set_inertia": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    "pfc_dynamics_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 8),
+    "pfc_dynamics": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "pfc_accelerations_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 7),
+    "pfc_accelerations": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "pfc_state_derivative_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 22),
+    "pfc_state_derivative": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip,
+                                       _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp, _ip]),
     "pfc_kinematics_dual_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8),
     "pfc_kinematics_dual": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "pfc_eval_dual_state_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 28),
@@ -113,7 +121,7 @@ class PFCError(RuntimeError):
 
 def build(force: bool = False) -> str:
     """Compile csrc/pfc_hip.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("pfc_hip.hip", "pfc_tree.cpp", "pfc_sort.hip", "pfc_kernels.h", "pfc_bp.h", "pfc_np.h", "pfc_br.h", "pfc_dual.h", "pfc_fused.h", "pfc_clip.h", "pfc_multi.h", "pfc_sort.h", "pfc_surface.h", "pfc_surface_fric.h", "pfc_scatter.h", "pfc_ljac.h", "pfc_bodies.h", "pfc_kin.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("pfc_hip.hip", "pfc_tree.cpp", "pfc_sort.hip", "pfc_kernels.h", "pfc_bp.h", "pfc_np.h", "pfc_br.h", "pfc_dual.h", "pfc_fused.h", "pfc_clip.h", "pfc_multi.h", "pfc_sort.h", "pfc_surface.h", "pfc_surface_fric.h", "pfc_scatter.h", "pfc_ljac.h", "pfc_bodies.h", "pfc_kin.h", "pfc_dyn.h")]
     srcs.append(os.path.join(os.path.dirname(HERE), "include", "pfc.h"))
     srcs.append(os.path.abspath(__file__))      # the compiler flags live here
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)

@@ -26,11 +26,15 @@
 //   pfc_kin.h      k_kinematics / k_kin_jacobian: the bodies' world poses, twists and geometric Jacobians from the joint state (q, v)
 //                  of a small tree (pfc_set_mechanism, pfc_kinematics, pfc_eval_state); k_kinematics_dual / k_kin_jacobian_dual: their
 //                  partials from the seed directions of a Jacobian chunk (pfc_kinematics_dual, pfc_eval_dual_state_device[_more])
+//   pfc_dyn.h      k_dynamics: qdot, the mass matrix and the bias from (q, v), the bodies' world states and their inertias
+//                  (pfc_set_inertia, pfc_dynamics); k_accel: vdot = H^-1 ((f - c) + tau) by Cholesky (pfc_accelerations,
+//                  pfc_state_derivative)
 //   pfc_multi.h    host code: multi-device handles (pfc_create_multi)
 // This file: mesh record preparation (k_prep_tri, k_prep_tet), per-item setup (k_setup_items), work-list management,
 // hipGraph capture / replay, the two-half evaluation and every extern "C" entry point.
 #include "pfc_kernels.h"
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -199,6 +203,7 @@ __global__ void k_repose(int n_items, const double *__restrict__ pose, ItemRec *
 #include "pfc_ljac.h"
 #include "pfc_bodies.h"
 #include "pfc_kin.h"
+#include "pfc_dyn.h"
 
 }  // namespace pfc
 
@@ -359,11 +364,15 @@ struct Stage {
 };
 
 // The mechanism of pfc_set_mechanism, validated and packed: every table k_kinematics / k_kin_jacobian read lies in `blob` at a
-// 256-byte boundary (KinArgs' names), so one copy uploads them.
+// 256-byte boundary (KinArgs' names), so one copy uploads them.  k_dynamics' tables lie there too: each body's subtree (CSR) and the
+// inertias of pfc_set_inertia (zeros until it is called: has_inertia).
 struct KinHost {
     int n_body = 0, nq = 0, nv = 0;
     std::vector<char> blob;
     size_t o_jtype = 0, o_qoff = 0, o_voff = 0, o_path_off = 0, o_path = 0, o_x_p_j = 0, o_axis = 0, o_anc = 0;
+    size_t o_sub_off = 0, o_sub = 0, o_inertia = 0;
+    bool has_inertia = false;
+    double gravity[3] = {0.0, 0.0, 0.0};
     template <class T> size_t put(const std::vector<T> &v) {
         const size_t off = blob.size(), bytes = sizeof(T) * v.size();
         blob.resize((off + bytes + 255) & ~(size_t)255);
@@ -3386,6 +3395,17 @@ int pfc_set_mechanism(pfc_handle h, int n_body, const int *parent, const int *jo
     K.o_jtype = K.put(jtype); K.o_qoff = K.put(qoff); K.o_voff = K.put(voff); K.o_path_off = K.put(path_off); K.o_path = K.put(path);
     K.o_x_p_j = K.put(std::vector<double>(x_p_j, x_p_j + 12 * nb)); K.o_axis = K.put(std::vector<double>(axis, axis + 3 * nb));
     K.o_anc = K.put(anc);
+    {   // the subtrees: b and its descendants in increasing body order (a descendant's path holds b)
+        std::vector<int> sub_off(nb + 1, 0), sub;
+        for (int b = 0; b < n_body; ++b) {
+            for (int d = b; d < n_body; ++d)
+                if (std::find(path.begin() + path_off[d], path.begin() + path_off[d + 1], b) != path.begin() + path_off[d + 1]) sub.push_back(d);
+            sub_off[b + 1] = (int)sub.size();
+        }
+        K.o_sub_off = K.put(sub_off); K.o_sub = K.put(sub);
+        K.o_inertia = K.put(std::vector<double>(13 * nb, 0.0));
+        K.has_inertia = false;
+    }
     K.n_body = n_body; K.nq = nv; K.nv = nv;
     h->kin_stale = true;
     return PFC_OK;
@@ -3563,6 +3583,221 @@ int pfc_eval_state(pfc_handle h, int n_items, const int *ins_ids, const int *sce
                          counts);
     if (rc != PFC_OK || !scatter) return rc;
     return pfc_scatter_generalized(h, n_items, wrench, x_w_r2, body_1, body_2, scene, n_scene, n_scene * n_body, nv, jac, f);
+}
+
+// ---- forward dynamics from joint states (pfc_dyn.h) -------------------------------------------------------------------------------
+static_assert(PFC_MAX_NV_SOLVE == kDynWave, "k_accel runs one lane per row");
+
+int pfc_set_inertia(pfc_handle h, int n_body, const double *inertia, const double *gravity) {
+    if (h && h->multi) return on_first_shard(h, [&](pfc_context *c) { return pfc_set_inertia(c, n_body, inertia, gravity); });
+    if (!h) return PFC_ERR_BAD_ARG;
+    const char *who = "pfc_set_inertia";
+    KinHost &K = h->kin;
+    if (K.n_body == 0) return fail(h, PFC_ERR_STATE, "%s before pfc_set_mechanism", who);
+    if (n_body != K.n_body) return fail(h, PFC_ERR_BAD_ARG, "%s: n_body is %d, the mechanism has %d bodies", who, n_body, K.n_body);
+    if (!inertia || !gravity) return fail(h, PFC_ERR_BAD_ARG, "%s: null table", who);
+    for (int r = 0; r < 3; ++r)
+        if (!std::isfinite(gravity[r])) return fail(h, PFC_ERR_BAD_ARG, "%s: gravity is not finite", who);
+    for (int b = 0; b < n_body; ++b) {
+        const double *in = inertia + 13 * (size_t)b;
+        if (!std::isfinite(in[12]) || in[12] < 0.0) return fail(h, PFC_ERR_BAD_ARG, "%s: body %d has the mass %.17g", who, b, in[12]);
+        double big = 0.0;
+        for (int e = 0; e < 12; ++e) {
+            if (!std::isfinite(in[e])) return fail(h, PFC_ERR_BAD_ARG, "%s: body %d's inertia is not finite", who, b);
+            if (e < 9) big = std::max(big, std::fabs(in[e]));
+        }
+        for (int r = 0; r < 3; ++r)
+            for (int c = r + 1; c < 3; ++c)
+                if (std::fabs(in[3 * c + r] - in[3 * r + c]) > 1e-12 * big)
+                    return fail(h, PFC_ERR_BAD_ARG, "%s: body %d's moment is not symmetric (M%d%d = %.17g, M%d%d = %.17g)", who, b, r, c,
+                                in[3 * c + r], c, r, in[3 * r + c]);
+    }
+    std::memcpy(K.blob.data() + K.o_inertia, inertia, sizeof(double) * 13 * (size_t)n_body);
+    for (int r = 0; r < 3; ++r) K.gravity[r] = gravity[r];
+    K.has_inertia = true;
+    h->kin_stale = true;
+    return PFC_OK;
+}
+
+// What every dynamics call needs of the handle: a mechanism, its inertias, and a scene whose tables fit k_dynamics' LDS.
+static int dyn_check_state(pfc_context *h, const char *who) {
+    const KinHost &K = h->kin;
+    if (K.n_body == 0) return fail(h, PFC_ERR_STATE, "%s before pfc_set_mechanism", who);
+    if (!K.has_inertia) return fail(h, PFC_ERR_STATE, "%s before pfc_set_inertia", who);
+    if (dyn_lds_bytes(K.n_body, K.nv) > kDynMaxLds)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: 44 n_body + 12.5 nv doubles must fit 64 KiB of LDS (n_body = %d, nv = %d)", who, K.n_body, K.nv);
+    return PFC_OK;
+}
+
+static int dyn_check_args(pfc_context *h, const char *who, int n_scene, const double *q, const double *v, const double *x_w_b,
+                          const double *twist_w_b, const double *qdot, const double *H, const double *c) {
+    const int rc = dyn_check_state(h, who);
+    if (rc != PFC_OK) return rc;
+    if (n_scene < 0) return fail(h, PFC_ERR_BAD_ARG, "%s: negative n_scene", who);
+    if (n_scene == 0 || h->kin.nv == 0) return PFC_OK;
+    if ((qdot && (!q || !v)) || ((H || c) && !x_w_b) || (c && (!twist_w_b || !v)))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null input (qdot needs q and v, H the poses, c the poses, the twists and v)", who);
+    return PFC_OK;
+}
+
+// The tables' upload on st if they are stale, then k_dynamics on st.  Every pointer is a device pointer.
+static int dyn_launch(pfc_context *h, int n_scene, const double *q, const double *v, const double *x_w_b, const double *twist_w_b,
+                      double *qdot, double *H, double *c, hipStream_t st) {
+    const KinHost &K = h->kin;
+    if (K.nv == 0 || (!qdot && !H && !c)) return PFC_OK;
+    { const int rc = kin_upload_tables(h, st); if (rc != PFC_OK) return rc; }
+    DynArgs a;
+    a.k = kin_table_args(h, n_scene, q, v);
+    const char *t = h->kin_tab.p;
+    a.inertia = (const double *)(t + K.o_inertia); a.sub_off = (const int *)(t + K.o_sub_off); a.sub = (const int *)(t + K.o_sub);
+    for (int r = 0; r < 3; ++r) a.g[r] = K.gravity[r];
+    a.x_w_b = x_w_b; a.twist_w_b = twist_w_b; a.qdot = qdot; a.H = H; a.c = c;
+    hipLaunchKernelGGL(k_dynamics, dim3((unsigned)n_scene), dim3(kDynWave), dyn_lds_bytes(K.n_body, K.nv), st, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+int pfc_dynamics_device(pfc_handle h, int n_scene, const double *d_q, const double *d_v, const double *d_x_w_b, const double *d_twist_w_b,
+                        double *d_qdot, double *d_H, double *d_c, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_dynamics_device(c, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_qdot, d_H, d_c, stream); });
+    const int rc = dyn_check_args(h, "pfc_dynamics_device", n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_qdot, d_H, d_c);
+    if (rc != PFC_OK || n_scene == 0) return rc;
+    return dyn_launch(h, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_qdot, d_H, d_c, stream ? (hipStream_t)stream : h->stream);
+}
+
+int pfc_dynamics(pfc_handle h, int n_scene, const double *q, const double *v, const double *x_w_b, const double *twist_w_b,
+                 double *qdot, double *H, double *c) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c1) { return pfc_dynamics(c1, n_scene, q, v, x_w_b, twist_w_b, qdot, H, c); });
+    int rc = dyn_check_args(h, "pfc_dynamics", n_scene, q, v, x_w_b, twist_w_b, qdot, H, c);
+    if (rc != PFC_OK || n_scene == 0) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t ns = (size_t)n_scene, nb = ns * h->kin.n_body, nv = (size_t)h->kin.nv;
+    Stage sg(h->stage, h->stream);
+    const int k_q = sg.in(q, ns * h->kin.nq), k_v = sg.in(v, ns * nv), k_x = sg.in(x_w_b, nb * 12), k_tw = sg.in(twist_w_b, nb * 6);
+    const int k_qd = sg.out(qdot, ns * h->kin.nq), k_H = sg.out(H, ns * nv * nv), k_c = sg.out(c, ns * nv);
+    HIP_TRY(h, sg.commit());
+    rc = dyn_launch(h, n_scene, sg.at<double>(k_q), sg.at<double>(k_v), sg.at<double>(k_x), sg.at<double>(k_tw), sg.at<double>(k_qd),
+                    sg.at<double>(k_H), sg.at<double>(k_c), sg.st);
+    if (rc != PFC_OK) return rc;
+    HIP_TRY(h, sg.finish());
+    return PFC_OK;
+}
+
+// The solve needs the mechanism's nv only; its cap is checked before anything is launched.
+static int accel_check_state(pfc_context *h, const char *who) {
+    if (h->kin.n_body == 0) return fail(h, PFC_ERR_STATE, "%s before pfc_set_mechanism", who);
+    if (h->kin.nv > PFC_MAX_NV_SOLVE)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: nv is %d, the solve takes at most PFC_MAX_NV_SOLVE = %d", who, h->kin.nv, PFC_MAX_NV_SOLVE);
+    return PFC_OK;
+}
+
+static int accel_check_args(pfc_context *h, const char *who, int n_scene, const double *H, const double *c, const double *f,
+                            const double *vdot) {
+    const int rc = accel_check_state(h, who);
+    if (rc != PFC_OK) return rc;
+    if (n_scene < 0) return fail(h, PFC_ERR_BAD_ARG, "%s: negative n_scene", who);
+    if (n_scene > 0 && h->kin.nv > 0 && (!H || !c || !f || !vdot)) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    return PFC_OK;
+}
+
+static int accel_launch(pfc_context *h, int n_scene, const double *H, const double *c, const double *f, const double *tau, double *vdot,
+                        int *info, hipStream_t st) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int nv = h->kin.nv;
+    if (nv == 0) {      // nothing to solve: every scene's flag is 0
+        if (info) HIP_TRY(h, hipMemsetAsync(info, 0, sizeof(int) * (size_t)n_scene, st));
+        return PFC_OK;
+    }
+    AccelArgs a;
+    a.n_scene = n_scene; a.nv = nv; a.H = H; a.c = c; a.f = f; a.tau = tau; a.vdot = vdot; a.info = info;
+    hipLaunchKernelGGL(k_accel, dim3((unsigned)n_scene), dim3(kDynWave), accel_lds_bytes(nv), st, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+int pfc_accelerations_device(pfc_handle h, int n_scene, const double *d_H, const double *d_c, const double *d_f, const double *d_tau,
+                             double *d_vdot, int *d_info, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_accelerations_device(c, n_scene, d_H, d_c, d_f, d_tau, d_vdot, d_info, stream); });
+    const int rc = accel_check_args(h, "pfc_accelerations_device", n_scene, d_H, d_c, d_f, d_vdot);
+    if (rc != PFC_OK || n_scene == 0) return rc;
+    return accel_launch(h, n_scene, d_H, d_c, d_f, d_tau, d_vdot, d_info, stream ? (hipStream_t)stream : h->stream);
+}
+
+int pfc_accelerations(pfc_handle h, int n_scene, const double *H, const double *c, const double *f, const double *tau, double *vdot,
+                      int *info) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c1) { return pfc_accelerations(c1, n_scene, H, c, f, tau, vdot, info); });
+    int rc = accel_check_args(h, "pfc_accelerations", n_scene, H, c, f, vdot);
+    if (rc != PFC_OK || n_scene == 0) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t ns = (size_t)n_scene, nv = (size_t)h->kin.nv;
+    Stage sg(h->stage, h->stream);
+    const int k_H = sg.in(H, ns * nv * nv), k_c = sg.in(c, ns * nv), k_f = sg.in(f, ns * nv), k_t = sg.in(tau, ns * nv);
+    const int k_vd = sg.out(vdot, ns * nv), k_i = sg.out(info, ns);
+    HIP_TRY(h, sg.commit());
+    rc = accel_launch(h, n_scene, sg.at<double>(k_H), sg.at<double>(k_c), sg.at<double>(k_f), sg.at<double>(k_t), sg.at<double>(k_vd),
+                      sg.at<int>(k_i), sg.st);
+    if (rc != PFC_OK) return rc;
+    HIP_TRY(h, sg.finish());
+    return PFC_OK;
+}
+
+int pfc_state_derivative_device(pfc_handle h, int n_items, const int *d_ins_ids, const int *d_scene, int n_scene,
+                                const double *d_q, const double *d_v, const double *d_s, const double *d_tau,
+                                double *d_x_w_b, double *d_twist_w_b, double *d_jac,
+                                double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
+                                double *d_wrench, double *d_sdot, int *d_counts, double *d_f,
+                                double *d_qdot, double *d_H, double *d_c, double *d_vdot, int *d_info, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    const char *who = "pfc_state_derivative_device";
+    pfc_context *c = h->multi ? h->multi->shard[0] : h;
+    int rc = on_shard(h, c, [&](pfc_context *c1) {
+        const int r = dyn_check_state(c1, who);
+        return r != PFC_OK ? r : accel_check_state(c1, who); });
+    if (rc != PFC_OK) return rc;
+    if (!d_f || !d_qdot || !d_H || !d_c || !d_vdot) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    rc = pfc_eval_state_device(h, n_items, d_ins_ids, d_scene, n_scene, d_q, d_v, d_s, d_x_w_b, d_twist_w_b, d_jac, d_pose, d_twist, d_x_w_r2,
+                               d_body_1, d_body_2, d_wrench, d_sdot, d_counts, d_f, stream);
+    if (rc != PFC_OK) return rc;
+    if ((rc = pfc_dynamics_device(h, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_qdot, d_H, d_c, stream)) != PFC_OK) return rc;
+    return pfc_accelerations_device(h, n_scene, d_H, d_c, d_f, d_tau, d_vdot, d_info, stream);
+}
+
+int pfc_state_derivative(pfc_handle h, int n_items, const int *ins_ids, const int *scene, int n_scene,
+                         const double *q, const double *v, const double *s, const double *tau,
+                         double *x_w_b, double *twist_w_b, double *jac,
+                         double *pose, double *twist, double *x_w_r2, int *body_1, int *body_2,
+                         double *wrench, double *sdot, int *counts, double *f,
+                         double *qdot, double *H, double *c, double *vdot, int *info) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    const char *who = "pfc_state_derivative";
+    pfc_context *c0 = h->multi ? h->multi->shard[0] : h;
+    int rc = on_shard(h, c0, [&](pfc_context *c1) {
+        const int r = dyn_check_state(c1, who);
+        return r != PFC_OK ? r : accel_check_state(c1, who); });
+    if (rc != PFC_OK) return rc;
+    if (!f || !qdot || !H || !c || !vdot) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    std::vector<double> tmp;      // the body states, where the caller did not ask for them
+    if (n_scene > 0 && (!x_w_b || !twist_w_b)) {
+        const size_t nb = (size_t)n_scene * c0->kin.n_body;
+        tmp.resize(nb * 18);
+        if (!x_w_b) x_w_b = tmp.data();
+        if (!twist_w_b) twist_w_b = tmp.data() + nb * 12;
+    }
+    rc = pfc_eval_state(h, n_items, ins_ids, scene, n_scene, q, v, s, x_w_b, twist_w_b, jac, pose, twist, x_w_r2, body_1, body_2, wrench, sdot,
+                        counts, f);
+    if (rc != PFC_OK) return rc;
+    if ((rc = pfc_dynamics(h, n_scene, q, v, x_w_b, twist_w_b, qdot, H, c)) != PFC_OK) return rc;
+    return pfc_accelerations(h, n_scene, H, c, f, tau, vdot, info);
 }
 
 // ---- Dual kinematics: partials of the body states and Jacobians (the second half of pfc_kin.h) ----------------------------------

@@ -25,6 +25,7 @@ reference's sentinel, src/obb/tree_types.jl:11,56) for internal nodes and the el
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Optional
 
@@ -492,3 +493,39 @@ def build_tree(m: EMesh, method: str = "blob") -> OBBTree:
         raise ValueError(L.pfc_tree_last_error().decode())
     assert rc == n
     return OBBTree(c, e, R, child, leaf)
+
+
+# ---- body inertia from a mesh (src/body_inertia.jl:2-9,30-68) ------------------------------------------------------------
+def mesh_inertia(emesh: EMesh, rho: float, d: Optional[float] = None) -> np.ndarray:
+    """The spatial inertia of a body of density rho whose shape is `emesh`, as the 13-double record of pfc_set_inertia:
+    moment (9, column-major, about the frame origin), cross_part = m com (3), mass.  A tet mesh is a solid (d None); a tri mesh is
+    a shell of thickness d, each triangle weighing rho d area (makeInertiaTensor / centroidVolumeCombo with equiv_volume).  The
+    moment about the centre of mass, sum over elements of rho V_k integral of (r.r I - r r'), is integrated with the degree-2 rules
+    -- three points (2/3, 1/6, 1/6) on a triangle, four points ((5 + 3 sqrt 5) / 20, (5 - sqrt 5) / 20 x 3) in a tet -- which are
+    exact for this quadratic integrand, as the reference's higher rules are: the two differ by rounding only.  It is then moved to
+    the frame origin, I + m [com]x [com]x', as newBodyFromInertia does.  Setup-time NumPy; nothing here runs on the device."""
+    pts = np.asarray(emesh.point, dtype=np.float64)
+    if (emesh.tet is None) == (d is None):
+        raise ValueError("mesh_inertia: a tet mesh without d, or a tri mesh with the shell thickness d")
+    if emesh.tet is not None:
+        p = pts[np.asarray(emesh.tet)]                      # (n, 4, 3)
+        vol = tet_volume(p)
+        a, b = (5.0 - math.sqrt(5.0)) / 20.0, (5.0 + 3.0 * math.sqrt(5.0)) / 20.0
+        zeta = np.full((4, 4), a) + (b - a) * np.eye(4)
+        w = np.full(4, 0.25)
+    else:
+        p = pts[np.asarray(emesh.tri)]                      # (n, 3, 3)
+        vol = _tri_area(p) * float(d)
+        zeta = np.full((3, 3), 1.0 / 6.0) + 0.5 * np.eye(3)
+        w = np.full(3, 1.0 / 3.0)
+    v_cum = float(vol.sum())
+    com = (vol[:, None] * p.mean(axis=1)).sum(axis=0) / v_cum
+    r = np.einsum("qk,nkc->nqc", zeta, p) - com             # (n, n_quad, 3)
+    mass_q = float(rho) * w[None, :] * vol[:, None]
+    rr = np.einsum("nqc,nqc->nq", r, r)
+    I3 = np.einsum("nq,nq->", mass_q, rr) * np.eye(3) - np.einsum("nq,nqa,nqb->ab", mass_q, r, r)
+    m = v_cum * float(rho)
+    K = np.array([[0.0, -com[2], com[1]], [com[2], 0.0, -com[0]], [-com[1], com[0], 0.0]])
+    moment = I3 + m * (K @ K.T)
+    moment = 0.5 * (moment + moment.T)                      # the sums above are symmetric up to rounding
+    return np.concatenate([moment.reshape(-1, order="F"), m * com, [m]])

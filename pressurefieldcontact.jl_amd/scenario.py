@@ -339,6 +339,7 @@ class MechanismScenario:
         self._finalized = False
         self._ins_bodies = {}        # bindings made before finalize(): the handle does not exist yet
         self._mechanism = None       # set_mechanism's tables, likewise
+        self._inertia = None         # set_inertia's, likewise (dropped by a later set_mechanism, as the library drops them)
 
     # ---- scenario construction ---------------------------------------------------------------------------------
     def add_contact(self, name: str, e_mesh: EMesh, c_prop: Optional[ContactProperties] = None,
@@ -458,6 +459,8 @@ class MechanismScenario:
             self._check(L.pfc_set_instruction_bodies(h, ins, b1, b2))
         if self._mechanism is not None:
             self._send_mechanism()
+            if self._inertia is not None:
+                self._send_inertia()
 
     def set_mechanism(self, parent, joint_type, x_p_j, axis=None):
         """pfc_set_mechanism: the tree the kinematics calls below evaluate.  Body b is the successor of joint b; parent (n_body,) in
@@ -472,6 +475,7 @@ class MechanismScenario:
         if joint_type.size != n_body or x_p_j.size != 12 * n_body or axis.size != 3 * n_body:
             raise ValueError("set_mechanism: one parent, joint type, joint_pose (12) and axis (3) per body")
         mech = (n_body, parent, joint_type, x_p_j, axis)
+        self._inertia = None
         if not self._finalized:
             self._mechanism = mech      # sent by finalize(): the library validates it there
             return
@@ -483,6 +487,24 @@ class MechanismScenario:
         self._check(L.pfc_set_mechanism(self._h, n_body, parent.ctypes.data_as(_ip), joint_type.ctypes.data_as(_ip),
                                         x_p_j.ctypes.data_as(_dp), axis.ctypes.data_as(_dp)))
         self._mechanism = mech or self._mechanism
+
+    def set_inertia(self, inertia, gravity=(0.0, 0.0, -9.81)):
+        """pfc_set_inertia: the bodies' spatial inertias in their own frames, (n_body,13) = moment (9, column-major, about the frame
+        origin), cross_part = m com (3), mass (1) -- geometry.mesh_inertia's record -- and gravity (3) in world.  After
+        set_mechanism; a later set_mechanism drops them."""
+        if self._mechanism is None:
+            raise RuntimeError("set_mechanism first")
+        inertia = np.ascontiguousarray(inertia, dtype=np.float64).reshape(-1)
+        gravity = np.ascontiguousarray(gravity, dtype=np.float64).reshape(-1)
+        if inertia.size % 13 or gravity.size != 3:
+            raise ValueError("set_inertia: 13 doubles per body and a gravity vector")
+        self._inertia = (inertia.size // 13, inertia, gravity)
+        if self._finalized:
+            self._send_inertia()
+
+    def _send_inertia(self):
+        n_body, inertia, gravity = self._inertia
+        self._check(_lib.lib().pfc_set_inertia(self._h, n_body, inertia.ctypes.data_as(_dp), gravity.ctypes.data_as(_dp)))
 
     def mechanism_sizes(self):
         """pfc_mechanism_sizes: (n_body, nq, nv) of the mechanism the library holds."""
@@ -887,6 +909,84 @@ class MechanismScenario:
                                                      d_pose or None, d_twist or None, d_x_w_r2 or None, d_body_1 or None, d_body_2 or None,
                                                      d_wrench or None, d_sdot or None, d_counts or None, d_f or None, stream or None))
 
+    def dynamics(self, q, v, x_w_b=None, twist_w_b=None):
+        """qdot, the mass matrix and the bias from the joint state (pfc_dynamics, host buffers, synchronous).  q, v as kinematics;
+        x_w_b, twist_w_b its outputs for the same state (None: computed here).  Returns qdot (n_scene,nq), H (n_scene,nv,nv),
+        c (n_scene,nv): H vdot + c = tau + f."""
+        n_scene, n_body, nv, q_a, v_a = self._state_arrays(q, v)
+        if x_w_b is None or twist_w_b is None:
+            x_w_b, twist_w_b, _ = self.kinematics(q_a, v_a, want_jac=False)
+        x = np.ascontiguousarray(x_w_b, dtype=np.float64).reshape(n_scene, n_body, 12)
+        tw = np.ascontiguousarray(twist_w_b, dtype=np.float64).reshape(n_scene, n_body, 6)
+        qd = np.zeros((n_scene, nv)); H = np.zeros((n_scene, nv, nv)); c = np.zeros((n_scene, nv))
+        self._check(_lib.lib().pfc_dynamics(self._h, n_scene, q_a.ctypes.data_as(_dp), v_a.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
+                                            tw.ctypes.data_as(_dp), qd.ctypes.data_as(_dp), H.ctypes.data_as(_dp), c.ctypes.data_as(_dp)))
+        return qd, H, c
+
+    def dynamics_device(self, n_scene: int, d_q: int, d_v: int, d_x_w_b: int, d_twist_w_b: int, d_qdot: int, d_H: int, d_c: int,
+                        stream: int = 0):
+        """pfc_dynamics_device: raw device addresses (0: NULL for any output not wanted); asynchronous on `stream`, not an
+        evaluation, no check() needed."""
+        self._check(_lib.lib().pfc_dynamics_device(self._h, int(n_scene), d_q or None, d_v or None, d_x_w_b or None, d_twist_w_b or None,
+                                                   d_qdot or None, d_H or None, d_c or None, stream or None))
+
+    def accelerations(self, H, c, f, tau=None):
+        """vdot = H^-1 ((f - c) + tau) by Cholesky (pfc_accelerations, host buffers, synchronous).  H (n_scene,nv,nv), c, f and tau
+        (None: zeros) (n_scene,nv).  Returns vdot (n_scene,nv) and info (n_scene,): 0, or the 1-based index of the pivot that was
+        not > 0 (that scene's vdot is NaN)."""
+        _, _, nv = self.mechanism_sizes()
+        c_a = np.ascontiguousarray(c, dtype=np.float64).reshape(-1, nv)
+        n_scene = c_a.shape[0]
+        H_a = np.ascontiguousarray(H, dtype=np.float64).reshape(n_scene, nv, nv)
+        f_a = np.ascontiguousarray(f, dtype=np.float64).reshape(n_scene, nv)
+        t_a = None if tau is None else np.ascontiguousarray(tau, dtype=np.float64).reshape(n_scene, nv)
+        vdot = np.zeros((n_scene, nv)); info = np.zeros(n_scene, dtype=np.int32)
+        self._check(_lib.lib().pfc_accelerations(self._h, n_scene, H_a.ctypes.data_as(_dp), c_a.ctypes.data_as(_dp), f_a.ctypes.data_as(_dp),
+                                                 None if t_a is None else t_a.ctypes.data_as(_dp), vdot.ctypes.data_as(_dp),
+                                                 info.ctypes.data_as(_ip)))
+        return vdot, info
+
+    def accelerations_device(self, n_scene: int, d_H: int, d_c: int, d_f: int, d_tau: int, d_vdot: int, d_info: int, stream: int = 0):
+        """pfc_accelerations_device: raw device addresses (d_tau 0: zeros; d_info 0: not wanted); asynchronous on `stream`."""
+        self._check(_lib.lib().pfc_accelerations_device(self._h, int(n_scene), d_H or None, d_c or None, d_f or None, d_tau or None,
+                                                        d_vdot or None, d_info or None, stream or None))
+
+    def state_derivative(self, q, v, s=None, tau=None, ins_ids: Optional[Sequence[int]] = None, scene=None):
+        """From x = [q; v; s] to qdot, vdot and sdot in one call (pfc_state_derivative, host buffers, synchronous):
+        force_all_elastic_intersections_state, dynamics and accelerations.  Arguments as force_all_elastic_intersections_state; tau
+        (n_scene,nv) or None.  Returns (qdot (n_scene,nq), vdot (n_scene,nv), sdot (n,6), info (n_scene,), f (n_scene,nv),
+        (H, c), (wrench, counts))."""
+        n_scene, n_body, nv, q_a, v_a = self._state_arrays(q, v)
+        x = np.zeros((n_scene, n_body, 12)); tw = np.zeros((n_scene, n_body, 6))
+        n, head, it, outs, keep = self._bodies_call(x, tw, ins_ids, scene)
+        s_p = None
+        if s is not None:
+            s_a, s_p = _d(s)
+            if s_a.size != 6 * n:
+                raise ValueError("s must have 6 entries per item")
+        t_a = None if tau is None else np.ascontiguousarray(tau, dtype=np.float64).reshape(n_scene, nv)
+        wrench = np.zeros((n, 6)); sdot = np.zeros((n, 6)); counts = np.zeros((n, 4), dtype=np.int32); f = np.zeros((n_scene, nv))
+        qd = np.zeros((n_scene, nv)); H = np.zeros((n_scene, nv, nv)); c = np.zeros((n_scene, nv)); vdot = np.zeros((n_scene, nv))
+        info = np.zeros(n_scene, dtype=np.int32)
+        self._check(_lib.lib().pfc_state_derivative(
+            self._h, n, head[2], head[3], n_scene, q_a.ctypes.data_as(_dp), v_a.ctypes.data_as(_dp), s_p,
+            None if t_a is None else t_a.ctypes.data_as(_dp), x.ctypes.data_as(_dp), tw.ctypes.data_as(_dp), None, *outs,
+            wrench.ctypes.data_as(_dp), sdot.ctypes.data_as(_dp), counts.ctypes.data_as(_ip), f.ctypes.data_as(_dp),
+            qd.ctypes.data_as(_dp), H.ctypes.data_as(_dp), c.ctypes.data_as(_dp), vdot.ctypes.data_as(_dp), info.ctypes.data_as(_ip)))
+        return qd, vdot, sdot, info, f, (H, c), (wrench, counts)
+
+    def state_derivative_device(self, n_items: int, d_ins_ids: int, d_scene: int, n_scene: int, d_q: int, d_v: int, d_s: int, d_tau: int,
+                                d_x_w_b: int, d_twist_w_b: int, d_jac: int, d_pose: int, d_twist: int, d_x_w_r2: int, d_body_1: int,
+                                d_body_2: int, d_wrench: int, d_sdot: int, d_counts: int, d_f: int, d_qdot: int, d_H: int, d_c: int,
+                                d_vdot: int, d_info: int, stream: int = 0):
+        """pfc_state_derivative_device: eval_state_device (d_f required), dynamics_device and accelerations_device on one stream;
+        asynchronous, follow with check() (re-issue on ERR_OVERFLOW)."""
+        a = [d_ins_ids, d_scene]
+        b = [d_q, d_v, d_s, d_tau, d_x_w_b, d_twist_w_b, d_jac, d_pose, d_twist, d_x_w_r2, d_body_1, d_body_2, d_wrench, d_sdot, d_counts, d_f,
+             d_qdot, d_H, d_c, d_vdot, d_info, stream]
+        self._check(_lib.lib().pfc_state_derivative_device(self._h, int(n_items), *[p or None for p in a], int(n_scene),
+                                                           *[p or None for p in b]))
+
     def _seed_arrays(self, n_scene, nq, nv, dq, dv):
         """(n_dir, dq (n_scene,n_dir,nq) or None, dv (n_scene,n_dir,nv) or None): the seed directions of a Jacobian chunk."""
         if dq is None and dv is None:
@@ -1280,6 +1380,57 @@ def joint_kinematics(parent, joint_type, x_p_j, axis, q, v):
         J[b, off[b]:off[b + 1]] = Sw.T
     x = np.array([np.concatenate([h[:3, :3].reshape(-1, order="F"), h[:3, 3]]) for h in H])
     return x, tw, J
+
+
+def joint_dynamics(parent, joint_type, x_p_j, axis, inertia, gravity, q, v):
+    """qdot, the mass matrix H and the bias c of a tree (H vdot + c = tau + f) for one scene in NumPy -- the matrix formulation
+    on joint_kinematics' Jacobians, deliberately not the recursion of pfc_dynamics, which the tests compare with it.  With I_b the
+    6x6 spatial inertia of body b in world about the world origin, J_b (6,nv) its geometric Jacobian and tw_b its twist:
+        H = sum_b J_b' I_b J_b,      c = sum_b J_b' (I_b (Jdot_b v - [0; g]) + tw_b x* I_b tw_b),
+    column k of Jdot_b being tw_body(k) x_m S_k where k's joint lies on b's path.  qdot: v for revolute and prismatic joints;
+    (1/4 [(1 - p'p) I + 2 [p]x + 2 p p'] omega, R_j(p) v_lin) for a floating one.  inertia (n_body,13) as
+    MechanismScenario.set_inertia, gravity (3) in world.  Returns qdot (nq,), H (nv,nv), c (nv,)."""
+    x, tw, J = joint_kinematics(parent, joint_type, x_p_j, axis, q, v)
+    parent = np.asarray(parent, dtype=np.int64).reshape(-1)
+    joint_type = np.asarray(joint_type, dtype=np.int64).reshape(-1)
+    n_body, nv = parent.size, J.shape[1]
+    inertia = np.asarray(inertia, dtype=np.float64).reshape(n_body, 13)
+    g6 = np.concatenate([np.zeros(3), np.asarray(gravity, dtype=np.float64).reshape(3)])
+    ndof = [{_lib.JOINT_FIXED: 0, _lib.JOINT_REVOLUTE: 1, _lib.JOINT_PRISMATIC: 1, _lib.JOINT_FLOATING_MRP: 6}[int(t)] for t in joint_type]
+    off = np.concatenate([[0], np.cumsum(ndof)]).astype(int)
+    owner = np.repeat(np.arange(n_body), ndof)
+    q = np.asarray(q, dtype=np.float64).reshape(nv); v = np.asarray(v, dtype=np.float64).reshape(nv)
+
+    def crm(t):      # the 6x6 matrix of t x_m
+        M = np.zeros((6, 6))
+        M[:3, :3] = _hat(t[:3]); M[3:, 3:] = _hat(t[:3]); M[3:, :3] = _hat(t[3:])
+        return M
+
+    H, c = np.zeros((nv, nv)), np.zeros(nv)
+    for b in range(n_body):
+        R, t = x[b, :9].reshape(3, 3, order="F"), x[b, 9:]
+        M, cp, m = inertia[b, :9].reshape(3, 3, order="F"), inertia[b, 9:12], inertia[b, 12]
+        hw = R @ cp + m * t                       # m times the centre of mass, world
+        C_, T_ = _hat(R @ cp), _hat(t)
+        I6 = np.zeros((6, 6))
+        I6[:3, :3] = R @ M @ R.T - m * (T_ @ T_) - (T_ @ C_ + C_ @ T_)      # the moment moved from the frame origin to the world's
+        I6[:3, 3:] = _hat(hw); I6[3:, :3] = -_hat(hw); I6[3:, 3:] = m * np.eye(3)
+        Jb = J[b].T                               # (6, nv)
+        Jd = np.zeros((6, nv))
+        for k in range(nv):
+            if Jb[:, k].any():
+                Jd[:, k] = crm(tw[owner[k]]) @ Jb[:, k]
+        H += Jb.T @ I6 @ Jb
+        c += Jb.T @ (I6 @ (Jd @ v - g6) - crm(tw[b]).T @ (I6 @ tw[b]))
+    qd = v.copy()
+    for b in range(n_body):
+        if joint_type[b] == _lib.JOINT_FLOATING_MRP:
+            p, w, u = q[off[b]:off[b] + 3], v[off[b]:off[b] + 3], v[off[b] + 3:off[b] + 6]
+            P = _hat(p)
+            p2 = float(p @ p)
+            qd[off[b]:off[b] + 3] = 0.25 * (((1.0 - p2) * np.eye(3) + 2.0 * P + 2.0 * np.outer(p, p)) @ w)
+            qd[off[b] + 3:off[b] + 6] = (np.eye(3) + (4.0 * (1.0 - p2) * P + 8.0 * (P @ P)) / (1.0 + p2) ** 2) @ u
+    return qd, H, c
 
 
 def joint_kinematics_partials(parent, joint_type, x_p_j, axis, q, v, dq, dv):
