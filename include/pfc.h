@@ -526,7 +526,7 @@ int pfc_eval_state(pfc_handle h, int n_items, const int *ins_ids, const int *sce
  * Forward dynamics from joint states: what configuration_derivative!, mass_matrix!, dynamics_bias!, sum_all_forces!, cholesky! and
  * ldiv! (src/contact_algorithms_non_friction.jl:18-52) give the reference per evaluation -- qdot, the mass matrix H, the bias c and
  * vdot = H^-1 ((f - c) + tau) -- formed on the device, so that xx = [qdot; vdot; sdot] follows from x = [q; v; s] without a host that
- * owns a dynamics library.  The value path; there is no Dual sibling yet.
+ * owns a dynamics library.  The value path; the Dual siblings are pfc_dynamics_dual_device and pfc_accelerations_dual_device below.
  *
  * pfc_set_inertia gives the bodies' inertias and gravity.  inertia (n_body x 13) holds per body RigidBodyDynamics' SpatialInertia in
  * the body's own frame: moment (9, column-major, about the frame origin), cross_part = m com (3), mass (1).  gravity (3) is the
@@ -694,6 +694,100 @@ int pfc_eval_dual_state_device_more(pfc_handle h, int n_items, int n_dir, const 
                                     const double *d_x_w_r2, const int *d_body_1, const int *d_body_2, const double *d_wrench,
                                     double *d_dpose, double *d_dtwist, double *d_dx_w_r2, double *d_dwrench, double *d_dsdot,
                                     double *d_df, void *stream);
+
+/*
+ * Dual forward dynamics from joint states: the partials of qdot, H, c and vdot that the Dual method of calcXd! gets from
+ * RigidBodyDynamics on the Dual state of a Jacobian chunk (src/radau/radau_functions.jl:2-14), so that one call per chunk yields a
+ * column block of d[qdot; vdot; sdot] / d[q; v; s] with no upload but the seed directions.
+ *
+ * pfc_dynamics_dual_device: one kernel (one 64-lane workgroup per (scene, direction), its tables in LDS) enqueued on `stream`
+ * (NULL = the handle's own) without a host synchronisation, for n_dir (1..16, else PFC_ERR_BAD_ARG) seed directions:
+ *   d_q, d_v, d_dq, d_dv        as pfc_kinematics_dual_device (d_dq / d_dv NULL: zeros, the same bytes as an array of zeros)
+ *   d_x_w_b, d_twist_w_b        pfc_kinematics_device's outputs for the same (q, v)
+ *   d_dx_w_b, d_dtwist_w_b      pfc_kinematics_dual_device's outputs for the same (q, v) and seeds, in its layout
+ *   d_dqdot      n_scene x n_dir x nq       OUT partials of qdot, direction dir of scene s at row s n_dir + dir
+ *   d_dH         n_scene x n_dir x nv x nv  OUT partials of H, the full matrix, row-major, the mirror a copy
+ *   d_dc         n_scene x n_dir x nv       OUT partials of c
+ * Any OUT pointer may be NULL: it is not written and its stages are skipped.  An input an output needs must not be NULL
+ * (PFC_ERR_BAD_ARG): d_dqdot needs d_q and d_v; d_dH needs d_x_w_b and d_dx_w_b; d_dc needs d_x_w_b, d_twist_w_b, d_dx_w_b,
+ * d_dtwist_w_b and d_v.  The arithmetic is the statement of pfc_dynamics_device run on (value, one partial) numbers with the rules
+ * pfc_kinematics_dual_device states, without fma and with nothing restated: gravity, the inertia records, the axes and the literals
+ * are {x, 0.0} (a_world = [{+0.0, +0.0} (3); -{g, 0.0}]); the poses and twists are {d_x_w_b, d_dx_w_b} and {d_twist_w_b,
+ * d_dtwist_w_b}, q and v are {q, dq} and {v, dv}.  Revolute and prismatic joints: dqdot = dv; floating joints: the qdot statement on
+ * {q, dq}, {v, dv}, the joint rotation through the quotient rule.  dH[i,j] is +0.0 where j's joint is not on the root -> body(i)
+ * path.  There is no shortcut for zero seeds.  The value parts are pfc_dynamics_device's bytes and are not stored.  The same bytes on
+ * every call, handle and entry point; no atomics.  The Dual tables are twice the value tables: PFC_ERR_BAD_ARG, before anything is
+ * launched and with nothing written, if 88 n_body + 24.5 nv doubles exceed 64 KiB (the value call for the same mechanism may still
+ * pass; a 64-link chain takes 57.6 kB).  PFC_ERR_STATE before pfc_set_inertia.  The call is NOT an evaluation: a kept value pass, Dual
+ * reuse, pfc_check and pfc_last_* are as they were.  n_scene = 0 is a no-op.  Multi-device handles: the first device.
+ */
+int pfc_dynamics_dual_device(pfc_handle h, int n_scene, int n_dir, const double *d_q, const double *d_v, const double *d_dq,
+                             const double *d_dv, const double *d_x_w_b, const double *d_twist_w_b, const double *d_dx_w_b,
+                             const double *d_dtwist_w_b, double *d_dqdot, double *d_dH, double *d_dc, void *stream);
+/* The same with host buffers, synchronous: the same kernel, the same bytes. */
+int pfc_dynamics_dual(pfc_handle h, int n_scene, int n_dir, const double *q, const double *v, const double *dq, const double *dv,
+                      const double *x_w_b, const double *twist_w_b, const double *dx_w_b, const double *dtwist_w_b,
+                      double *dqdot, double *dH, double *dc);
+
+/*
+ * vdot and its partials: the exact derivative of the solve, dvdot = H^-1 (d rhs - dH vdot), with the value factor -- not the
+ * factorisation run on (value, partial) numbers, from which it differs by rounding of order kappa(H) eps.  One kernel, one 64-lane
+ * workgroup per scene, lane = row, enqueued on `stream`:
+ *   d_H, d_c, d_f, d_tau   as pfc_accelerations_device
+ *   d_dH, d_dc             pfc_dynamics_dual_device's outputs       d_df  n_scene x n_dir x nv, pfc_eval_dual_state_device's d_df
+ *   d_dtau                 n_scene x n_dir x nv, or NULL: zeros
+ *   d_vdot   n_scene x nv          OUT, or NULL: pfc_accelerations_device's bytes
+ *   d_dvdot  n_scene x n_dir x nv  OUT       d_info  n_scene OUT, or NULL: as pfc_accelerations_device
+ * The order, in plain Float64 without fma: L, y and vdot as pfc_accelerations_device states; then per direction
+ *   t_i = ((dH_i0 vdot_0 + dH_i1 vdot_1) + ...) + dH_i,n-1 vdot_n-1, j ascending
+ *   r_i = ((df_i - dc_i) + dtau_i) - t_i  (dtau NULL: + 0.0)
+ * and dvdot from r by the same two substitutions with the same L (the directions run together: each lane carries n_dir
+ * accumulators, so the number of sequential steps does not grow with n_dir).  A pivot that is not > 0 makes the scene's vdot and all
+ * its dvdot NaN and sets d_info[scene] = j + 1.  n_dir in 1..16 and nv <= PFC_MAX_NV_SOLVE, else PFC_ERR_BAD_ARG before anything is
+ * launched.  LDS: L and (1 + N) nv doubles, N = n_dir rounded up to 1, 2, 4, 8 or 16 (a lane's accumulators; the slots beyond n_dir
+ * repeat the last direction and are not stored), 41.5 kB at the cap.  Not an evaluation; n_scene = 0 is a no-op; PFC_ERR_STATE before
+ * pfc_set_mechanism.
+ */
+int pfc_accelerations_dual_device(pfc_handle h, int n_scene, int n_dir, const double *d_H, const double *d_c, const double *d_f,
+                                  const double *d_tau, const double *d_dH, const double *d_dc, const double *d_df, const double *d_dtau,
+                                  double *d_vdot, double *d_dvdot, int *d_info, void *stream);
+/* The same with host buffers, synchronous: the same kernel, the same bytes. */
+int pfc_accelerations_dual(pfc_handle h, int n_scene, int n_dir, const double *H, const double *c, const double *f, const double *tau,
+                           const double *dH, const double *dc, const double *df, const double *dtau, double *vdot, double *dvdot,
+                           int *info);
+
+/*
+ * Exactly pfc_eval_dual_state_device with d_f and d_df required, then pfc_dynamics_device, pfc_dynamics_dual_device and
+ * pfc_accelerations_dual_device, on one stream: three launches more than the Dual evaluation (k_accel is not launched).  d_tau and
+ * d_dtau may be NULL (zeros), d_info may be NULL; d_qdot, d_H, d_c, d_vdot, d_dqdot, d_dH, d_dc and d_dvdot are required.  Everything
+ * a part would refuse -- missing inertias, the nv cap, the Dual LDS limit and n_dir included -- is checked before the first launch,
+ * and then nothing is written.  pfc_check() afterwards as after pfc_eval_dual_device.  There is no host-buffer form.
+ */
+int pfc_state_derivative_dual_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
+                                     const double *d_q, const double *d_v, const double *d_dq, const double *d_dv,
+                                     const double *d_s, const double *d_ds, const double *d_tau, const double *d_dtau,
+                                     double *d_x_w_b, double *d_twist_w_b, double *d_jac,
+                                     double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac,
+                                     double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
+                                     double *d_dpose, double *d_dtwist, double *d_dx_w_r2,
+                                     double *d_wrench, double *d_sdot, double *d_dwrench, double *d_dsdot, int *d_counts,
+                                     double *d_f, double *d_df,
+                                     double *d_qdot, double *d_H, double *d_c, double *d_vdot, int *d_info,
+                                     double *d_dqdot, double *d_dH, double *d_dc, double *d_dvdot, void *stream);
+/*
+ * The later chunks at the kept point: exactly pfc_eval_dual_state_device_more with d_df required, then pfc_dynamics_dual_device,
+ * then pfc_accelerations_dual_device with d_vdot = NULL.  It reads d_H, d_c, d_f and d_tau as the first chunk left them and writes
+ * only partials.  Checks and pfc_check() as above and as pfc_eval_dual_state_device_more.
+ */
+int pfc_state_derivative_dual_device_more(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
+                                          const double *d_q, const double *d_v, const double *d_dq, const double *d_dv, const double *d_ds,
+                                          const double *d_tau, const double *d_dtau,
+                                          const double *d_x_w_b, const double *d_twist_w_b, const double *d_jac,
+                                          double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac,
+                                          const double *d_x_w_r2, const int *d_body_1, const int *d_body_2, const double *d_wrench,
+                                          double *d_dpose, double *d_dtwist, double *d_dx_w_r2, double *d_dwrench, double *d_dsdot,
+                                          double *d_df, const double *d_H, const double *d_c, const double *d_f,
+                                          double *d_dqdot, double *d_dH, double *d_dc, double *d_dvdot, void *stream);
 
 /*
  * The contact surface of n_items items: per item what the reference's TractionCache holds after forceAllElasticIntersections!

@@ -90,6 +90,12 @@ SIGNATURES = {
     "pfc_kinematics_dual": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "pfc_eval_dual_state_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 28),
     "pfc_eval_dual_state_device_more": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 22),
+    "pfc_dynamics_dual_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 12),
+    "pfc_dynamics_dual": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [_dp] * 11),
+    "pfc_accelerations_dual_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 12),
+    "pfc_accelerations_dual": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [_dp] * 10 + [_ip]),
+    "pfc_state_derivative_dual_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 39),
+    "pfc_state_derivative_dual_device_more": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 31),
     "pfc_build_tree": (C.c_int, [C.c_int, _dp, C.c_int, C.c_int, _ip, _dp, C.c_int, _dp, _dp, _dp, _ip, _ip]),
     "pfc_tree_last_error": (C.c_char_p, []),
     "pfc_scatter_generalized": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _ip, _ip, C.c_int, C.c_int, C.c_int, _dp, _dp]),

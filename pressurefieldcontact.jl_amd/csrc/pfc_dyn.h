@@ -6,7 +6,9 @@
 //
 // Arithmetic (the contract, stated in include/pfc.h): plain Float64, every dot product and every subtree sum in a written order, no
 // fma (the build has -ffp-contract=off), no atomics.  One statement over the number type T (dyn_inertia_to_world, dyn_mul,
-// dyn_crossm, dyn_crossf, dyn_dot6, dyn_add, dyn_mrp_rate), as kin_*<T> are: a later Dual instantiation on ScatDual restates nothing.
+// dyn_crossm, dyn_crossf, dyn_dot6, dyn_mrp_rate and the five stages themselves, dyn_stages<T>), as kin_*<T> are: the Dual
+// instantiation on ScatDual (pfc_dynamics_dual[_device]) restates nothing.  DynIo<T> is what differs: where a stage's numbers come
+// from and which part of a result is stored.
 // The motion-subspace columns are formed again from the world poses with kin_column<double> -- a column depends on the pose and the
 // axis only, so these are S_w's bytes -- and nothing is read from the handle's S_w buffer.
 // The kernels, one 64-lane workgroup (one wave) per scene, the scene's intermediate tables in LDS, a workgroup barrier between stages:
@@ -16,8 +18,13 @@
 //               (4) lanes over coordinates: F_i = Ic_body(i) S_i, c_i = S_i . W_body(i)
 //               (5) lanes over the nv x nv entries: H[i,j] = S_j . F_i for j <= i where anc says so, +0.0 otherwise, and its mirror
 //               A stage whose outputs nobody asked for is skipped (uniformly: the flags are kernel arguments).
+//   k_dynamics_dual  the same five stages on ScatDual, one workgroup per (scene, direction): the partials of qdot, H and c; the tables
+//               in LDS are twice the value tables (the host refuses a mechanism whose Dual tables exceed 64 KiB).
 //   k_accel     the lower triangle of H into LDS (column-major: lane = row, so neighbouring lanes read neighbouring words), the
-//               left-looking Cholesky factorisation one column at a time, the two substitutions one unknown at a time; lane = row.
+//               left-looking Cholesky factorisation one column at a time (accel_factor), the two substitutions one unknown at a
+//               time (accel_solve<1>); lane = row.
+//   k_accel_dual<N>  accel_factor and accel_solve<1> as k_accel (vdot), then the right-hand sides ((df - dc) + dtau) - dH vdot of
+//               all directions and accel_solve<N> with the same L: the exact derivative of the solve, not a Dual factorisation.
 // No id is followed out of range: the tables are validated on the host, n_scene bounds the grids, every loop over bodies,
 // coordinates or entries is bounded by n_body, nv or nv^2, and the LDS the host asks for is computed from the same n_body and nv.
 #pragma once
@@ -27,10 +34,14 @@ constexpr int kDynBodyDoubles = 44;          // LDS doubles per body: I (10), tw
 constexpr int kDynCoordDoubles = 12;         // LDS doubles per coordinate: S (6), F (6)
 constexpr size_t kDynMaxLds = 64 * 1024;     // what a workgroup may ask for without an opt-in
 
-__host__ __device__ inline size_t dyn_lds_bytes(int n_body, int nv) {
-    return sizeof(double) * ((size_t)kDynBodyDoubles * (size_t)n_body + (size_t)kDynCoordDoubles * (size_t)nv) + sizeof(int) * (size_t)nv;
+// num: bytes per table entry, sizeof(double) for k_dynamics, sizeof(ScatDual) for k_dynamics_dual.
+__host__ __device__ inline size_t dyn_lds_bytes(int n_body, int nv, size_t num = sizeof(double)) {
+    return num * ((size_t)kDynBodyDoubles * (size_t)n_body + (size_t)kDynCoordDoubles * (size_t)nv) + sizeof(int) * (size_t)nv;
 }
-__host__ __device__ inline size_t accel_lds_bytes(int nv) { return sizeof(double) * ((size_t)nv * (size_t)nv + (size_t)nv) + sizeof(int); }
+// n_rhs: right-hand sides kept in LDS, 1 for k_accel, 1 + n_dir for k_accel_dual.
+__host__ __device__ inline size_t accel_lds_bytes(int nv, int n_rhs = 1) {
+    return sizeof(double) * ((size_t)nv * (size_t)nv + (size_t)n_rhs * (size_t)nv) + sizeof(int);
+}
 
 struct DynArgs {
     KinArgs k;                          // the tables, n_scene, q and v; its outputs are not read
@@ -136,58 +147,120 @@ template <class T> __device__ inline void dyn_mrp_rate(const T *q, const T *v, T
     for (int r = 0; r < 3; ++r) qd[3 + r] = (xj[r] * v[3] + xj[3 + r] * v[4]) + xj[6 + r] * v[5];
 }
 
-__global__ void __launch_bounds__(kDynWave) k_dynamics(DynArgs d) {
-    extern __shared__ double dyn_lds[];
+// What the five stages read and write, per number type.  double: the value of one scene.  ScatDual: {value, the partial of one
+// direction}; only the partial parts are stored.
+template <class T> struct DynIo;
+
+template <> struct DynIo<double> {
+    const double *q_, *v_, *x_, *tw_;
+    double *qdot_, *H_, *c_;
+    __device__ DynIo(const DynArgs &d, int sc) {
+        const KinArgs &g = d.k;
+        const size_t nb = (size_t)g.n_body, nv = (size_t)g.nv;
+        q_ = g.q + (size_t)sc * (size_t)g.nq; v_ = g.v + (size_t)sc * nv;
+        x_ = d.x_w_b + 12 * ((size_t)sc * nb); tw_ = d.twist_w_b + 6 * ((size_t)sc * nb);
+        qdot_ = d.qdot ? d.qdot + (size_t)sc * (size_t)g.nq : nullptr;
+        H_ = d.H ? d.H + (size_t)sc * nv * nv : nullptr;
+        c_ = d.c ? d.c + (size_t)sc * nv : nullptr;
+    }
+    __device__ double q(int i) const { return q_[i]; }
+    __device__ double v(int i) const { return v_[i]; }
+    __device__ double x(int b, int e) const { return x_[12 * (size_t)b + e]; }
+    __device__ double tw(int b, int e) const { return tw_[6 * (size_t)b + e]; }
+    __device__ bool want_qdot() const { return qdot_ != nullptr; }
+    __device__ bool want_H() const { return H_ != nullptr; }
+    __device__ bool want_c() const { return c_ != nullptr; }
+    __device__ void qdot(int i, double a) const { qdot_[i] = a; }
+    __device__ void H(size_t e, double a) const { H_[e] = a; }
+    __device__ void c(int i, double a) const { c_[i] = a; }
+};
+
+struct DynDualArgs {
+    DynArgs d;                          // the tables, the values (q, v, x_w_b, twist_w_b); its outputs are not written
+    int n_dir;
+    const double *dq, *dv;              // n_scene x n_dir x nq, x nv: the seeds; each may be NULL (zeros)
+    const double *dx_w_b, *dtwist_w_b;  // n_scene n_body x n_dir x 12, x 6: pfc_kinematics_dual_device's outputs
+    double *dqdot, *dH, *dc;            // n_scene x n_dir x nq, x nv x nv, x nv; each may be NULL (not wanted)
+};
+
+template <> struct DynIo<ScatDual> {
+    DynIo<double> val;
+    const double *dq_, *dv_, *dx_, *dtw_;
+    double *dqdot_, *dH_, *dc_;
+    int n_dir;
+    __device__ DynIo(const DynDualArgs &h, int sc, int dir) : val(h.d, sc), n_dir(h.n_dir) {
+        const KinArgs &g = h.d.k;
+        const size_t nb = (size_t)g.n_body, nv = (size_t)g.nv, row = (size_t)sc * (size_t)h.n_dir + (size_t)dir;
+        dq_ = h.dq ? h.dq + row * (size_t)g.nq : nullptr;
+        dv_ = h.dv ? h.dv + row * nv : nullptr;
+        dx_ = h.dx_w_b + 12 * ((size_t)sc * nb * (size_t)h.n_dir + (size_t)dir);          // body b: + 12 n_dir b
+        dtw_ = h.dtwist_w_b + 6 * ((size_t)sc * nb * (size_t)h.n_dir + (size_t)dir);
+        dqdot_ = h.dqdot ? h.dqdot + row * (size_t)g.nq : nullptr;
+        dH_ = h.dH ? h.dH + row * nv * nv : nullptr;
+        dc_ = h.dc ? h.dc + row * nv : nullptr;
+    }
+    __device__ ScatDual q(int i) const { return {val.q(i), dq_ ? dq_[i] : 0.0}; }
+    __device__ ScatDual v(int i) const { return {val.v(i), dv_ ? dv_[i] : 0.0}; }
+    __device__ ScatDual x(int b, int e) const { return {val.x(b, e), dx_[12 * (size_t)n_dir * (size_t)b + e]}; }
+    __device__ ScatDual tw(int b, int e) const { return {val.tw(b, e), dtw_[6 * (size_t)n_dir * (size_t)b + e]}; }
+    __device__ bool want_qdot() const { return dqdot_ != nullptr; }
+    __device__ bool want_H() const { return dH_ != nullptr; }
+    __device__ bool want_c() const { return dc_ != nullptr; }
+    __device__ void qdot(int i, ScatDual a) const { dqdot_[i] = a.d; }
+    __device__ void H(size_t e, ScatDual a) const { dH_[e] = a.d; }
+    __device__ void c(int i, ScatDual a) const { dc_[i] = a.d; }
+};
+
+// The five stages for one scene (and, on ScatDual, one direction) by one 64-lane workgroup; lds holds dyn_lds_bytes(.., sizeof(T)).
+template <class T> __device__ inline void dyn_stages(const DynArgs &d, const DynIo<T> &io, double *lds) {
     const KinArgs &g = d.k;
-    const int nb = g.n_body, nv = g.nv, tid = (int)threadIdx.x, sc = (int)blockIdx.x;
-    double *sI = dyn_lds, *sTw = sI + 10 * nb, *sJt = sTw + 6 * nb, *sW = sJt + 6 * nb, *sIc = sW + 6 * nb, *sWc = sIc + 10 * nb;
-    double *sS = sWc + 6 * nb, *sF = sS + 6 * nv;
+    const int nb = g.n_body, nv = g.nv, tid = (int)threadIdx.x;
+    T *sI = reinterpret_cast<T *>(lds), *sTw = sI + 10 * nb, *sJt = sTw + 6 * nb, *sW = sJt + 6 * nb, *sIc = sW + 6 * nb, *sWc = sIc + 10 * nb;
+    T *sS = sWc + 6 * nb, *sF = sS + 6 * nv;
     int *sBody = reinterpret_cast<int *>(sF + 6 * nv);
-    const double *q = g.q + (size_t)sc * (size_t)g.nq;
-    const double *v = g.v + (size_t)sc * (size_t)nv;
-    const bool want_H = d.H != nullptr, want_c = d.c != nullptr;
+    const bool want_H = io.want_H(), want_c = io.want_c();
+    const T zero = kin_lit<T>(0.0);
 
     // (1) qdot; world inertia, columns, joint twist
     for (int b = tid; b < nb; b += kDynWave) {
-        const int type = g.jtype[b], n = kin_joint_nq(type), vo = g.voff[b];
-        if (d.qdot) {
-            double *out = d.qdot + (size_t)sc * (size_t)g.nq + (size_t)g.qoff[b];
+        const int type = g.jtype[b], n = kin_joint_nq(type), vo = g.voff[b], qo = g.qoff[b];
+        if (io.want_qdot()) {
             if (type == PFC_JOINT_FLOATING_MRP) {
-                double qd[6];
-                dyn_mrp_rate<double>(q + g.qoff[b], v + vo, qd);
+                T qj[6], vj[6], qd[6];
 #pragma unroll
-                for (int e = 0; e < 6; ++e) out[e] = qd[e];
+                for (int e = 0; e < 6; ++e) { qj[e] = io.q(qo + e); vj[e] = io.v(vo + e); }
+                dyn_mrp_rate<T>(qj, vj, qd);
+#pragma unroll
+                for (int e = 0; e < 6; ++e) io.qdot(qo + e, qd[e]);
             } else if (n == 1) {
-                out[0] = v[vo];
+                io.qdot(qo, io.v(vo));
             }
         }
         if (want_H || want_c) {
-            double x[12], in[13], I[10], ax[3], o[6], jt[6];
-            const double *xin = d.x_w_b + 12 * ((size_t)sc * (size_t)nb + (size_t)b);
+            T x[12], in[13], I[10], ax[3], o[6], jt[6];
 #pragma unroll
-            for (int e = 0; e < 12; ++e) x[e] = xin[e];
+            for (int e = 0; e < 12; ++e) x[e] = io.x(b, e);
 #pragma unroll
-            for (int e = 0; e < 13; ++e) in[e] = d.inertia[13 * (size_t)b + e];
+            for (int e = 0; e < 13; ++e) in[e] = kin_lit<T>(d.inertia[13 * (size_t)b + e]);
 #pragma unroll
-            for (int e = 0; e < 3; ++e) ax[e] = g.axis[3 * (size_t)b + e];
-            dyn_inertia_to_world<double>(in, x, I);
+            for (int e = 0; e < 3; ++e) ax[e] = kin_lit<T>(g.axis[3 * (size_t)b + e]);
+            dyn_inertia_to_world<T>(in, x, I);
 #pragma unroll
             for (int e = 0; e < 10; ++e) sI[10 * b + e] = I[e];
 #pragma unroll
-            for (int e = 0; e < 6; ++e) jt[e] = 0.0;
+            for (int e = 0; e < 6; ++e) jt[e] = zero;
             for (int k = 0; k < n; ++k) {
-                kin_column<double>(type, k, ax, x, o);
+                kin_column<T>(type, k, ax, x, o);
                 sBody[vo + k] = b;
 #pragma unroll
                 for (int e = 0; e < 6; ++e) {
                     sS[6 * (vo + k) + e] = o[e];
-                    if (want_c) jt[e] = k == 0 ? o[e] * v[vo] : jt[e] + o[e] * v[vo + k];
+                    if (want_c) jt[e] = k == 0 ? o[e] * io.v(vo) : jt[e] + o[e] * io.v(vo + k);
                 }
             }
             if (want_c) {
-                const double *twin = d.twist_w_b + 6 * ((size_t)sc * (size_t)nb + (size_t)b);
 #pragma unroll
-                for (int e = 0; e < 6; ++e) { sTw[6 * b + e] = twin[e]; sJt[6 * b + e] = jt[e]; }
+                for (int e = 0; e < 6; ++e) { sTw[6 * b + e] = io.tw(b, e); sJt[6 * b + e] = jt[e]; }
             }
         }
     }
@@ -197,16 +270,16 @@ __global__ void __launch_bounds__(kDynWave) k_dynamics(DynArgs d) {
     // (2) bias acceleration along the path, body wrench
     if (want_c) {
         for (int b = tid; b < nb; b += kDynWave) {
-            double a[6] = {0.0, 0.0, 0.0, -d.g[0], -d.g[1], -d.g[2]}, o[6], w1[6], w2[6], w3[6];
+            T a[6] = {zero, zero, zero, -kin_lit<T>(d.g[0]), -kin_lit<T>(d.g[1]), -kin_lit<T>(d.g[2])}, o[6], w1[6], w2[6], w3[6];
             for (int k = g.path_off[b]; k < g.path_off[b + 1]; ++k) {
                 const int p = g.path[k];
-                dyn_crossm<double>(sTw + 6 * p, sJt + 6 * p, o);
+                dyn_crossm<T>(sTw + 6 * p, sJt + 6 * p, o);
 #pragma unroll
                 for (int e = 0; e < 6; ++e) a[e] = a[e] + o[e];
             }
-            dyn_mul<double>(sI + 10 * b, a, w1);
-            dyn_mul<double>(sI + 10 * b, sTw + 6 * b, w2);
-            dyn_crossf<double>(sTw + 6 * b, w2, w3);
+            dyn_mul<T>(sI + 10 * b, a, w1);
+            dyn_mul<T>(sI + 10 * b, sTw + 6 * b, w2);
+            dyn_crossf<T>(sTw + 6 * b, w2, w3);
 #pragma unroll
             for (int e = 0; e < 6; ++e) sW[6 * b + e] = w1[e] + w3[e];
         }
@@ -217,7 +290,7 @@ __global__ void __launch_bounds__(kDynWave) k_dynamics(DynArgs d) {
     for (int b = tid; b < nb; b += kDynWave) {
         const int s0 = d.sub_off[b], s1 = d.sub_off[b + 1];
         if (want_H) {
-            double I[10];
+            T I[10];
 #pragma unroll
             for (int e = 0; e < 10; ++e) I[e] = sI[10 * b + e];
             for (int k = s0 + 1; k < s1; ++k) {
@@ -229,7 +302,7 @@ __global__ void __launch_bounds__(kDynWave) k_dynamics(DynArgs d) {
             for (int e = 0; e < 10; ++e) sIc[10 * b + e] = I[e];
         }
         if (want_c) {
-            double W[6];
+            T W[6];
 #pragma unroll
             for (int e = 0; e < 6; ++e) W[e] = sW[6 * b + e];
             for (int k = s0 + 1; k < s1; ++k) {
@@ -247,43 +320,47 @@ __global__ void __launch_bounds__(kDynWave) k_dynamics(DynArgs d) {
     for (int i = tid; i < nv; i += kDynWave) {
         const int b = sBody[i];
         if (want_H) {
-            double F[6];
-            dyn_mul<double>(sIc + 10 * b, sS + 6 * i, F);
+            T F[6];
+            dyn_mul<T>(sIc + 10 * b, sS + 6 * i, F);
 #pragma unroll
             for (int e = 0; e < 6; ++e) sF[6 * i + e] = F[e];
         }
-        if (want_c) d.c[(size_t)sc * (size_t)nv + (size_t)i] = dyn_dot6<double>(sS + 6 * i, sWc + 6 * b);
+        if (want_c) io.c(i, dyn_dot6<T>(sS + 6 * i, sWc + 6 * b));
     }
     if (!want_H) return;
     __syncthreads();
 
     // (5) H: the lower triangle and its mirror
-    double *H = d.H + (size_t)sc * (size_t)nv * (size_t)nv;
     for (int e = tid; e < nv * nv; e += kDynWave) {
         const int i = e / nv, j = e % nv;
         if (j > i) continue;
-        const double h = g.anc[(size_t)sBody[i] * (size_t)nv + (size_t)j] ? dyn_dot6<double>(sS + 6 * j, sF + 6 * i) : 0.0;
-        H[(size_t)i * nv + j] = h;
-        H[(size_t)j * nv + i] = h;
+        const T h = g.anc[(size_t)sBody[i] * (size_t)nv + (size_t)j] ? dyn_dot6<T>(sS + 6 * j, sF + 6 * i) : zero;
+        io.H((size_t)i * nv + j, h);
+        io.H((size_t)j * nv + i, h);
     }
 }
 
-// vdot = H^-1 ((f - c) + tau) by H = L L', L y = rhs, L' x = y, in the order include/pfc.h states.  nv <= kDynWave: lane = row.
-__global__ void __launch_bounds__(kDynWave) k_accel(AccelArgs g) {
+__global__ void __launch_bounds__(kDynWave) k_dynamics(DynArgs d) {
     extern __shared__ double dyn_lds[];
-    const int nv = g.nv, i = (int)threadIdx.x, sc = (int)blockIdx.x;
-    double *L = dyn_lds, *sv = L + nv * nv;      // L(i, j) at L[j nv + i]
-    int *flag = reinterpret_cast<int *>(sv + nv);
-    const double *H = g.H + (size_t)sc * (size_t)nv * (size_t)nv;
-    const size_t row = (size_t)sc * (size_t)nv;
+    dyn_stages<double>(d, DynIo<double>(d, (int)blockIdx.x), dyn_lds);
+}
+
+// The same statement on ScatDual: one workgroup per (scene, direction), block scene n_dir + dir.
+__global__ void __launch_bounds__(kDynWave) k_dynamics_dual(DynDualArgs h) {
+    extern __shared__ double dyn_lds[];
+    const int sc = (int)(blockIdx.x / (unsigned)h.n_dir), dir = (int)(blockIdx.x % (unsigned)h.n_dir);
+    dyn_stages<ScatDual>(h.d, DynIo<ScatDual>(h, sc, dir), dyn_lds);
+}
+
+// The lower triangle of a scene's H into L (column-major: L(i, j) at L[j nv + i]) and its left-looking Cholesky factorisation, one
+// column at a time; lane i = row i.  Returns 0, or j + 1 for the first pivot that is not > 0 (NaN included): the same for every lane.
+__device__ inline int accel_factor(const double *H, int nv, int i, double *L, int *flag) {
     const bool act = i < nv;
     for (int e = i; e < nv * nv; e += kDynWave) {
         const int r = e / nv, c = e % nv;
         if (c <= r) L[c * nv + r] = H[e];
     }
     if (i == 0) *flag = 0;
-    double acc = 0.0;
-    if (act) acc = (g.f[row + i] - g.c[row + i]) + (g.tau ? g.tau[row + i] : 0.0);
     __syncthreads();
     for (int j = 0; j < nv; ++j) {
         double s = 0.0;
@@ -300,21 +377,116 @@ __global__ void __launch_bounds__(kDynWave) k_accel(AccelArgs g) {
         if (act && i > j) L[j * nv + i] = s / L[j * nv + j];
         __syncthreads();
     }
-    const int bad = *flag;
-    if (!bad) {
-        for (int k = 0; k < nv; ++k) {          // L y = rhs, k ascending
-            if (i == k) sv[k] = acc / L[k * nv + k];
-            __syncthreads();
-            if (act && i > k) acc = acc - L[k * nv + i] * sv[k];
+    return *flag;
+}
+
+// L y = rhs, then L' x = y, for N right-hand sides together: lane i enters with rhs_i of side d in acc[d]; x of side d is left in
+// sv[d nv .. d nv + nv), visible to every lane.  The sides share L and the barriers; nothing branches on a side, so their LDS
+// reads are in flight together.
+template <int N> __device__ inline void accel_solve(const double *L, int nv, int i, double (&acc)[N], double *sv) {
+    const bool act = i < nv;
+    for (int k = 0; k < nv; ++k) {          // L y = rhs, k ascending
+        if (i == k) {
+#pragma unroll
+            for (int d = 0; d < N; ++d) sv[d * nv + k] = acc[d] / L[k * nv + k];
         }
-        if (act) acc = sv[i];
         __syncthreads();
-        for (int k = nv - 1; k >= 0; --k) {     // L' x = y, k descending
-            if (i == k) sv[k] = acc / L[k * nv + k];
-            __syncthreads();
-            if (act && i < k) acc = acc - L[i * nv + k] * sv[k];
+        if (act && i > k) {
+#pragma unroll
+            for (int d = 0; d < N; ++d) acc[d] = acc[d] - L[k * nv + i] * sv[d * nv + k];
         }
     }
+    if (act) {
+#pragma unroll
+        for (int d = 0; d < N; ++d) acc[d] = sv[d * nv + i];
+    }
+    __syncthreads();
+    for (int k = nv - 1; k >= 0; --k) {     // L' x = y, k descending
+        if (i == k) {
+#pragma unroll
+            for (int d = 0; d < N; ++d) sv[d * nv + k] = acc[d] / L[k * nv + k];
+        }
+        __syncthreads();
+        if (act && i < k) {
+#pragma unroll
+            for (int d = 0; d < N; ++d) acc[d] = acc[d] - L[i * nv + k] * sv[d * nv + k];
+        }
+    }
+}
+
+// vdot = H^-1 ((f - c) + tau) by H = L L', L y = rhs, L' x = y, in the order include/pfc.h states.  nv <= kDynWave: lane = row.
+__global__ void __launch_bounds__(kDynWave) k_accel(AccelArgs g) {
+    extern __shared__ double dyn_lds[];
+    const int nv = g.nv, i = (int)threadIdx.x, sc = (int)blockIdx.x;
+    double *L = dyn_lds, *sv = L + nv * nv;
+    int *flag = reinterpret_cast<int *>(sv + nv);
+    const size_t row = (size_t)sc * (size_t)nv;
+    const bool act = i < nv;
+    double acc[1] = {0.0};
+    if (act) acc[0] = (g.f[row + i] - g.c[row + i]) + (g.tau ? g.tau[row + i] : 0.0);
+    const int bad = accel_factor(g.H + row * (size_t)nv, nv, i, L, flag);
+    if (!bad) accel_solve<1>(L, nv, i, acc, sv);
     if (act) g.vdot[row + i] = bad ? __longlong_as_double(0x7ff8000000000000ll) : sv[i];
     if (i == 0 && g.info) g.info[sc] = bad;
+}
+
+struct AccelDualArgs {
+    AccelArgs a;                        // the value solve; a.vdot and a.info may be NULL
+    int n_dir;
+    const double *dH, *dc, *df, *dtau;  // n_scene x n_dir x nv x nv, x nv, x nv, x nv (dtau may be NULL: zeros)
+    double *dvdot;                      // n_scene x n_dir x nv
+};
+
+__host__ __device__ inline int accel_dual_slots(int n_dir) { return n_dir <= 1 ? 1 : n_dir <= 2 ? 2 : n_dir <= 4 ? 4 : n_dir <= 8 ? 8 : 16; }
+
+// k_accel's factor and vdot, then dvdot = H^-1 (((df - dc) + dtau) - dH vdot) for every direction with the same factor, the
+// substitutions of all directions together.  N = accel_dual_slots(n_dir) accumulators per lane; a slot d >= n_dir repeats direction
+// n_dir - 1 (so that no load, product or LDS access sits behind a branch on the direction) and is not stored.
+// LDS: L, vdot (nv), the slots' unknowns (N nv), the flag.
+template <int N> __global__ void __launch_bounds__(kDynWave) k_accel_dual(AccelDualArgs h) {
+    extern __shared__ double dyn_lds[];
+    const AccelArgs &g = h.a;
+    const int nv = g.nv, n_dir = h.n_dir, i = (int)threadIdx.x, sc = (int)blockIdx.x;
+    double *L = dyn_lds, *sv = L + nv * nv, *sd = sv + nv;
+    int *flag = reinterpret_cast<int *>(sd + N * nv);
+    const size_t row = (size_t)sc * (size_t)nv;
+    const bool act = i < nv;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    double acc[1] = {0.0};
+    if (act) acc[0] = (g.f[row + i] - g.c[row + i]) + (g.tau ? g.tau[row + i] : 0.0);
+    const int bad = accel_factor(g.H + row * (size_t)nv, nv, i, L, flag);
+    if (!bad) accel_solve<1>(L, nv, i, acc, sv);      // ends behind a barrier: sv holds vdot for every lane
+    if (act && g.vdot) g.vdot[row + i] = bad ? nan : sv[i];
+    if (i == 0 && g.info) g.info[sc] = bad;
+    double r[N];
+#pragma unroll
+    for (int d = 0; d < N; ++d) r[d] = 0.0;
+    if (!bad) {
+        if (act) {
+            const size_t d0 = (size_t)sc * (size_t)n_dir * (size_t)nv, nn = (size_t)nv * (size_t)nv;
+            const double *dHi = h.dH + (d0 + (size_t)i) * (size_t)nv;      // row i of direction 0; direction d: + d nv nv
+            size_t off[N];
+#pragma unroll
+            for (int d = 0; d < N; ++d) off[d] = (size_t)(d < n_dir ? d : n_dir - 1);
+            const double v0 = sv[0];
+#pragma unroll
+            for (int d = 0; d < N; ++d) r[d] = dHi[off[d] * nn] * v0;
+            for (int j = 1; j < nv; ++j) {      // t_i, j ascending; the slots are the inner loop: their loads are in flight together
+                const double vj = sv[j];
+#pragma unroll
+                for (int d = 0; d < N; ++d) r[d] = r[d] + dHi[off[d] * nn + j] * vj;
+            }
+#pragma unroll
+            for (int d = 0; d < N; ++d) {
+                const size_t e = d0 + off[d] * (size_t)nv + (size_t)i;
+                r[d] = ((h.df[e] - h.dc[e]) + (h.dtau ? h.dtau[e] : 0.0)) - r[d];
+            }
+        }
+        accel_solve<N>(L, nv, i, r, sd);
+    }
+    if (act) {
+#pragma unroll
+        for (int d = 0; d < N; ++d)
+            if (d < n_dir) h.dvdot[((size_t)sc * (size_t)n_dir + (size_t)d) * (size_t)nv + i] = bad ? nan : sd[d * nv + i];
+    }
 }

@@ -28,7 +28,8 @@
 //                  partials from the seed directions of a Jacobian chunk (pfc_kinematics_dual, pfc_eval_dual_state_device[_more])
 //   pfc_dyn.h      k_dynamics: qdot, the mass matrix and the bias from (q, v), the bodies' world states and their inertias
 //                  (pfc_set_inertia, pfc_dynamics); k_accel: vdot = H^-1 ((f - c) + tau) by Cholesky (pfc_accelerations,
-//                  pfc_state_derivative)
+//                  pfc_state_derivative); k_dynamics_dual / k_accel_dual: their partials for the seed directions of a Jacobian
+//                  chunk (pfc_dynamics_dual, pfc_accelerations_dual, pfc_state_derivative_dual_device[_more])
 //   pfc_multi.h    host code: multi-device handles (pfc_create_multi)
 // This file: mesh record preparation (k_prep_tri, k_prep_tet), per-item setup (k_setup_items), work-list management,
 // hipGraph capture / replay, the two-half evaluation and every extern "C" entry point.
@@ -3940,6 +3941,234 @@ int pfc_eval_dual_state_device_more(pfc_handle h, int n_items, int n_dir, const 
     if (rc != PFC_OK || !scatter) return rc;
     return pfc_scatter_generalized_dual_device(h, n_items, n_dir, d_wrench, d_dwrench, d_x_w_r2, d_dx_w_r2, d_body_1, d_body_2, d_scene,
                                                n_scene, nv, d_jac, d_djac, nullptr, d_df, 0, stream);
+}
+
+// ---- Dual forward dynamics: partials of qdot, H, c and vdot (the ScatDual instantiation and k_accel_dual of pfc_dyn.h) ------------
+// What every Dual dynamics call needs of the handle: what the value call needs, and Dual tables -- twice the value tables -- that fit.
+static int dyn_dual_check_state(pfc_context *h, const char *who) {
+    const int rc = dyn_check_state(h, who);
+    if (rc != PFC_OK) return rc;
+    const KinHost &K = h->kin;
+    if (dyn_lds_bytes(K.n_body, K.nv, sizeof(ScatDual)) > kDynMaxLds)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: the Dual tables, 88 n_body + 24.5 nv doubles, must fit 64 KiB of LDS (n_body = %d, nv = %d)", who,
+                    K.n_body, K.nv);
+    return PFC_OK;
+}
+
+static int dual_dir_check(pfc_context *h, const char *who, int n_scene, int n_dir) {
+    if (n_scene < 0) return fail(h, PFC_ERR_BAD_ARG, "%s: negative n_scene", who);
+    if (n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "%s: n_dir must be in 1..16", who);
+    if ((long long)n_scene * n_dir >= (1ll << 31)) return fail(h, PFC_ERR_BAD_ARG, "%s: n_scene n_dir must be below 2^31", who);
+    return PFC_OK;
+}
+
+static int dyn_dual_check_args(pfc_context *h, const char *who, int n_scene, int n_dir, const double *q, const double *v,
+                               const double *x_w_b, const double *twist_w_b, const double *dx_w_b, const double *dtwist_w_b,
+                               const double *dqdot, const double *dH, const double *dc) {
+    int rc = dyn_dual_check_state(h, who);
+    if (rc != PFC_OK) return rc;
+    if ((rc = dual_dir_check(h, who, n_scene, n_dir)) != PFC_OK) return rc;
+    if (n_scene == 0 || h->kin.nv == 0) return PFC_OK;
+    if ((dqdot && (!q || !v)) || ((dH || dc) && (!x_w_b || !dx_w_b)) || (dc && (!twist_w_b || !dtwist_w_b || !v)))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null input (dqdot needs q and v, dH the poses and their partials, dc the poses, the twists, "
+                    "their partials and v)", who);
+    return PFC_OK;
+}
+
+// The tables' upload on st if they are stale, then k_dynamics_dual on st.  Every pointer is a device pointer.
+static int dyn_dual_launch(pfc_context *h, int n_scene, int n_dir, const double *q, const double *v, const double *dq, const double *dv,
+                           const double *x_w_b, const double *twist_w_b, const double *dx_w_b, const double *dtwist_w_b,
+                           double *dqdot, double *dH, double *dc, hipStream_t st) {
+    const KinHost &K = h->kin;
+    if (K.nv == 0 || (!dqdot && !dH && !dc)) return PFC_OK;
+    { const int rc = kin_upload_tables(h, st); if (rc != PFC_OK) return rc; }
+    DynDualArgs a;
+    a.d.k = kin_table_args(h, n_scene, q, v);
+    const char *t = h->kin_tab.p;
+    a.d.inertia = (const double *)(t + K.o_inertia); a.d.sub_off = (const int *)(t + K.o_sub_off); a.d.sub = (const int *)(t + K.o_sub);
+    for (int r = 0; r < 3; ++r) a.d.g[r] = K.gravity[r];
+    a.d.x_w_b = x_w_b; a.d.twist_w_b = twist_w_b; a.d.qdot = nullptr; a.d.H = nullptr; a.d.c = nullptr;
+    a.n_dir = n_dir; a.dq = dq; a.dv = dv; a.dx_w_b = dx_w_b; a.dtwist_w_b = dtwist_w_b; a.dqdot = dqdot; a.dH = dH; a.dc = dc;
+    hipLaunchKernelGGL(k_dynamics_dual, dim3((unsigned)n_scene * (unsigned)n_dir), dim3(kDynWave),
+                       dyn_lds_bytes(K.n_body, K.nv, sizeof(ScatDual)), st, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+int pfc_dynamics_dual_device(pfc_handle h, int n_scene, int n_dir, const double *d_q, const double *d_v, const double *d_dq,
+                             const double *d_dv, const double *d_x_w_b, const double *d_twist_w_b, const double *d_dx_w_b,
+                             const double *d_dtwist_w_b, double *d_dqdot, double *d_dH, double *d_dc, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_dynamics_dual_device(c, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b, d_dqdot,
+                                            d_dH, d_dc, stream); });
+    const int rc = dyn_dual_check_args(h, "pfc_dynamics_dual_device", n_scene, n_dir, d_q, d_v, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b,
+                                       d_dqdot, d_dH, d_dc);
+    if (rc != PFC_OK || n_scene == 0) return rc;
+    return dyn_dual_launch(h, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b, d_dqdot, d_dH, d_dc,
+                           stream ? (hipStream_t)stream : h->stream);
+}
+
+int pfc_dynamics_dual(pfc_handle h, int n_scene, int n_dir, const double *q, const double *v, const double *dq, const double *dv,
+                      const double *x_w_b, const double *twist_w_b, const double *dx_w_b, const double *dtwist_w_b,
+                      double *dqdot, double *dH, double *dc) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c1) {
+            return pfc_dynamics_dual(c1, n_scene, n_dir, q, v, dq, dv, x_w_b, twist_w_b, dx_w_b, dtwist_w_b, dqdot, dH, dc); });
+    int rc = dyn_dual_check_args(h, "pfc_dynamics_dual", n_scene, n_dir, q, v, x_w_b, twist_w_b, dx_w_b, dtwist_w_b, dqdot, dH, dc);
+    if (rc != PFC_OK || n_scene == 0) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t ns = (size_t)n_scene, nk = ns * n_dir, nb = ns * h->kin.n_body, nv = (size_t)h->kin.nv, nq = (size_t)h->kin.nq;
+    Stage sg(h->stage, h->stream);
+    const int k_q = sg.in(q, ns * nq), k_v = sg.in(v, ns * nv), k_dq = sg.in(dq, nk * nq), k_dv = sg.in(dv, nk * nv);
+    const int k_x = sg.in(x_w_b, nb * 12), k_tw = sg.in(twist_w_b, nb * 6), k_dx = sg.in(dx_w_b, nb * n_dir * 12),
+              k_dtw = sg.in(dtwist_w_b, nb * n_dir * 6);
+    const int k_qd = sg.out(dqdot, nk * nq), k_H = sg.out(dH, nk * nv * nv), k_c = sg.out(dc, nk * nv);
+    HIP_TRY(h, sg.commit());
+    rc = dyn_dual_launch(h, n_scene, n_dir, sg.at<double>(k_q), sg.at<double>(k_v), sg.at<double>(k_dq), sg.at<double>(k_dv),
+                         sg.at<double>(k_x), sg.at<double>(k_tw), sg.at<double>(k_dx), sg.at<double>(k_dtw), sg.at<double>(k_qd),
+                         sg.at<double>(k_H), sg.at<double>(k_c), sg.st);
+    if (rc != PFC_OK) return rc;
+    HIP_TRY(h, sg.finish());
+    return PFC_OK;
+}
+
+static int accel_dual_check_args(pfc_context *h, const char *who, int n_scene, int n_dir, const double *H, const double *c, const double *f,
+                                 const double *dH, const double *dc, const double *df, const double *dvdot) {
+    int rc = accel_check_state(h, who);
+    if (rc != PFC_OK) return rc;
+    if ((rc = dual_dir_check(h, who, n_scene, n_dir)) != PFC_OK) return rc;
+    if (n_scene > 0 && h->kin.nv > 0 && (!H || !c || !f || !dH || !dc || !df || !dvdot)) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    return PFC_OK;
+}
+
+static int accel_dual_launch(pfc_context *h, int n_scene, int n_dir, const double *H, const double *c, const double *f, const double *tau,
+                             const double *dH, const double *dc, const double *df, const double *dtau, double *vdot, double *dvdot,
+                             int *info, hipStream_t st) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int nv = h->kin.nv;
+    if (nv == 0) {      // nothing to solve: every scene's flag is 0
+        if (info) HIP_TRY(h, hipMemsetAsync(info, 0, sizeof(int) * (size_t)n_scene, st));
+        return PFC_OK;
+    }
+    AccelDualArgs a;
+    a.a.n_scene = n_scene; a.a.nv = nv; a.a.H = H; a.a.c = c; a.a.f = f; a.a.tau = tau; a.a.vdot = vdot; a.a.info = info;
+    a.n_dir = n_dir; a.dH = dH; a.dc = dc; a.df = df; a.dtau = dtau; a.dvdot = dvdot;
+    const int slots = accel_dual_slots(n_dir);
+    const dim3 grid((unsigned)n_scene), block(kDynWave);
+    const size_t lds = accel_lds_bytes(nv, 1 + slots);
+    switch (slots) {
+        case 1: hipLaunchKernelGGL(k_accel_dual<1>, grid, block, lds, st, a); break;
+        case 2: hipLaunchKernelGGL(k_accel_dual<2>, grid, block, lds, st, a); break;
+        case 4: hipLaunchKernelGGL(k_accel_dual<4>, grid, block, lds, st, a); break;
+        case 8: hipLaunchKernelGGL(k_accel_dual<8>, grid, block, lds, st, a); break;
+        default: hipLaunchKernelGGL(k_accel_dual<16>, grid, block, lds, st, a); break;
+    }
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+int pfc_accelerations_dual_device(pfc_handle h, int n_scene, int n_dir, const double *d_H, const double *d_c, const double *d_f,
+                                  const double *d_tau, const double *d_dH, const double *d_dc, const double *d_df, const double *d_dtau,
+                                  double *d_vdot, double *d_dvdot, int *d_info, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_accelerations_dual_device(c, n_scene, n_dir, d_H, d_c, d_f, d_tau, d_dH, d_dc, d_df, d_dtau, d_vdot, d_dvdot, d_info,
+                                                 stream); });
+    const int rc = accel_dual_check_args(h, "pfc_accelerations_dual_device", n_scene, n_dir, d_H, d_c, d_f, d_dH, d_dc, d_df, d_dvdot);
+    if (rc != PFC_OK || n_scene == 0) return rc;
+    return accel_dual_launch(h, n_scene, n_dir, d_H, d_c, d_f, d_tau, d_dH, d_dc, d_df, d_dtau, d_vdot, d_dvdot, d_info,
+                             stream ? (hipStream_t)stream : h->stream);
+}
+
+int pfc_accelerations_dual(pfc_handle h, int n_scene, int n_dir, const double *H, const double *c, const double *f, const double *tau,
+                           const double *dH, const double *dc, const double *df, const double *dtau, double *vdot, double *dvdot,
+                           int *info) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c1) {
+            return pfc_accelerations_dual(c1, n_scene, n_dir, H, c, f, tau, dH, dc, df, dtau, vdot, dvdot, info); });
+    int rc = accel_dual_check_args(h, "pfc_accelerations_dual", n_scene, n_dir, H, c, f, dH, dc, df, dvdot);
+    if (rc != PFC_OK || n_scene == 0) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t ns = (size_t)n_scene, nk = ns * n_dir, nv = (size_t)h->kin.nv;
+    Stage sg(h->stage, h->stream);
+    const int k_H = sg.in(H, ns * nv * nv), k_c = sg.in(c, ns * nv), k_f = sg.in(f, ns * nv), k_t = sg.in(tau, ns * nv);
+    const int k_dH = sg.in(dH, nk * nv * nv), k_dc = sg.in(dc, nk * nv), k_df = sg.in(df, nk * nv), k_dt = sg.in(dtau, nk * nv);
+    const int k_vd = sg.out(vdot, ns * nv), k_dvd = sg.out(dvdot, nk * nv), k_i = sg.out(info, ns);
+    HIP_TRY(h, sg.commit());
+    rc = accel_dual_launch(h, n_scene, n_dir, sg.at<double>(k_H), sg.at<double>(k_c), sg.at<double>(k_f), sg.at<double>(k_t),
+                           sg.at<double>(k_dH), sg.at<double>(k_dc), sg.at<double>(k_df), sg.at<double>(k_dt), sg.at<double>(k_vd),
+                           sg.at<double>(k_dvd), sg.at<int>(k_i), sg.st);
+    if (rc != PFC_OK) return rc;
+    HIP_TRY(h, sg.finish());
+    return PFC_OK;
+}
+
+// What both Dual chains check before the first launch, beyond what the Dual evaluation checks itself: the inertias, the Dual LDS
+// limit, the nv cap and n_dir.
+static int state_derivative_dual_check(pfc_context *c, const char *who, int n_scene, int n_dir) {
+    int rc = dyn_dual_check_state(c, who);
+    if (rc != PFC_OK) return rc;
+    if ((rc = accel_check_state(c, who)) != PFC_OK) return rc;
+    return dual_dir_check(c, who, n_scene, n_dir);
+}
+
+int pfc_state_derivative_dual_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
+                                     const double *d_q, const double *d_v, const double *d_dq, const double *d_dv,
+                                     const double *d_s, const double *d_ds, const double *d_tau, const double *d_dtau,
+                                     double *d_x_w_b, double *d_twist_w_b, double *d_jac,
+                                     double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac,
+                                     double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
+                                     double *d_dpose, double *d_dtwist, double *d_dx_w_r2,
+                                     double *d_wrench, double *d_sdot, double *d_dwrench, double *d_dsdot, int *d_counts,
+                                     double *d_f, double *d_df,
+                                     double *d_qdot, double *d_H, double *d_c, double *d_vdot, int *d_info,
+                                     double *d_dqdot, double *d_dH, double *d_dc, double *d_dvdot, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    const char *who = "pfc_state_derivative_dual_device";
+    pfc_context *c = h->multi ? h->multi->shard[0] : h;
+    int rc = on_shard(h, c, [&](pfc_context *c1) { return state_derivative_dual_check(c1, who, n_scene, n_dir); });
+    if (rc != PFC_OK) return rc;
+    if (!d_f || !d_df || !d_qdot || !d_H || !d_c || !d_vdot || !d_dqdot || !d_dH || !d_dc || !d_dvdot)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    rc = pfc_eval_dual_state_device(h, n_items, n_dir, d_ins_ids, d_scene, n_scene, d_q, d_v, d_dq, d_dv, d_s, d_ds, d_x_w_b, d_twist_w_b,
+                                    d_jac, d_dx_w_b, d_dtwist_w_b, d_djac, d_pose, d_twist, d_x_w_r2, d_body_1, d_body_2, d_dpose, d_dtwist,
+                                    d_dx_w_r2, d_wrench, d_sdot, d_dwrench, d_dsdot, d_counts, d_f, d_df, stream);
+    if (rc != PFC_OK) return rc;
+    if ((rc = pfc_dynamics_device(h, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_qdot, d_H, d_c, stream)) != PFC_OK) return rc;
+    rc = pfc_dynamics_dual_device(h, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b, d_dqdot, d_dH, d_dc,
+                                  stream);
+    if (rc != PFC_OK) return rc;
+    return pfc_accelerations_dual_device(h, n_scene, n_dir, d_H, d_c, d_f, d_tau, d_dH, d_dc, d_df, d_dtau, d_vdot, d_dvdot, d_info, stream);
+}
+
+int pfc_state_derivative_dual_device_more(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
+                                          const double *d_q, const double *d_v, const double *d_dq, const double *d_dv, const double *d_ds,
+                                          const double *d_tau, const double *d_dtau,
+                                          const double *d_x_w_b, const double *d_twist_w_b, const double *d_jac,
+                                          double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac,
+                                          const double *d_x_w_r2, const int *d_body_1, const int *d_body_2, const double *d_wrench,
+                                          double *d_dpose, double *d_dtwist, double *d_dx_w_r2, double *d_dwrench, double *d_dsdot,
+                                          double *d_df, const double *d_H, const double *d_c, const double *d_f,
+                                          double *d_dqdot, double *d_dH, double *d_dc, double *d_dvdot, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    const char *who = "pfc_state_derivative_dual_device_more";
+    pfc_context *c = h->multi ? h->multi->shard[0] : h;
+    int rc = on_shard(h, c, [&](pfc_context *c1) { return state_derivative_dual_check(c1, who, n_scene, n_dir); });
+    if (rc != PFC_OK) return rc;
+    if (!d_df || !d_H || !d_c || !d_f || !d_dqdot || !d_dH || !d_dc || !d_dvdot) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    rc = pfc_eval_dual_state_device_more(h, n_items, n_dir, d_ins_ids, d_scene, n_scene, d_q, d_v, d_dq, d_dv, d_ds, d_x_w_b, d_twist_w_b, d_jac,
+                                         d_dx_w_b, d_dtwist_w_b, d_djac, d_x_w_r2, d_body_1, d_body_2, d_wrench, d_dpose, d_dtwist, d_dx_w_r2,
+                                         d_dwrench, d_dsdot, d_df, stream);
+    if (rc != PFC_OK) return rc;
+    rc = pfc_dynamics_dual_device(h, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b, d_dqdot, d_dH, d_dc,
+                                  stream);
+    if (rc != PFC_OK) return rc;
+    return pfc_accelerations_dual_device(h, n_scene, n_dir, d_H, d_c, d_f, d_tau, d_dH, d_dc, d_df, d_dtau, nullptr, d_dvdot, nullptr, stream);
 }
 
 // The Dual evaluation, with the broadphase pose of m.float's state where bp_pose is given (calcTriTetIntersections!,

@@ -1068,6 +1068,102 @@ class MechanismScenario:
         f, d_f = self.scatter_generalized_dual(wrench, dw, it.x_w_r2, sd.d_x_w_r2, it.body_1, it.body_2, jac, djac, scene, x.shape[0])
         return wrench, sdot, dw, dsd, counts, f, d_f, it, sd, (x, tw, jac), (dx, dtw, djac)
 
+    def dynamics_dual(self, q, v, dq, dv, x_w_b=None, twist_w_b=None, d_x_w_b=None, d_twist_w_b=None):
+        """The partials of dynamics' three outputs for the seed directions of a Jacobian chunk (pfc_dynamics_dual, host buffers,
+        synchronous).  q, v, dq, dv as kinematics_dual; x_w_b, twist_w_b and d_x_w_b, d_twist_w_b the outputs of kinematics and
+        kinematics_dual for them (None: computed here).  Returns d_qdot (n_scene,n_dir,nq), d_H (n_scene,n_dir,nv,nv) and d_c
+        (n_scene,n_dir,nv)."""
+        n_scene, n_body, nv, q_a, v_a = self._state_arrays(q, v)
+        nq = q_a.shape[1]
+        n_dir, dq_a, dv_a = self._seed_arrays(n_scene, nq, nv, dq, dv)
+        if x_w_b is None or twist_w_b is None:
+            x_w_b, twist_w_b, _ = self.kinematics(q_a, v_a, want_jac=False)
+        if d_x_w_b is None or d_twist_w_b is None:
+            d_x_w_b, d_twist_w_b, _ = self.kinematics_dual(q_a, v_a, dq_a, dv_a, want_jac=False)
+        x = np.ascontiguousarray(x_w_b, dtype=np.float64).reshape(n_scene, n_body, 12)
+        tw = np.ascontiguousarray(twist_w_b, dtype=np.float64).reshape(n_scene, n_body, 6)
+        dx = np.ascontiguousarray(d_x_w_b, dtype=np.float64).reshape(n_scene, n_body, n_dir, 12)
+        dtw = np.ascontiguousarray(d_twist_w_b, dtype=np.float64).reshape(n_scene, n_body, n_dir, 6)
+        dqd = np.zeros((n_scene, n_dir, nq)); dH = np.zeros((n_scene, n_dir, nv, nv)); dc = np.zeros((n_scene, n_dir, nv))
+        p = lambda a: None if a is None else a.ctypes.data_as(_dp)
+        self._check(_lib.lib().pfc_dynamics_dual(self._h, n_scene, n_dir, p(q_a), p(v_a), p(dq_a), p(dv_a), p(x), p(tw), p(dx), p(dtw),
+                                                 p(dqd), p(dH), p(dc)))
+        return dqd, dH, dc
+
+    def dynamics_dual_device(self, n_scene: int, n_dir: int, d_q: int, d_v: int, d_dq: int, d_dv: int, d_x_w_b: int, d_twist_w_b: int,
+                             d_dx_w_b: int, d_dtwist_w_b: int, d_dqdot: int, d_dH: int, d_dc: int, stream: int = 0):
+        """pfc_dynamics_dual_device: raw device addresses (0: NULL for either seed array and any output not wanted); asynchronous on
+        `stream`, not an evaluation, no check() needed."""
+        a = [d_q, d_v, d_dq, d_dv, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b, d_dqdot, d_dH, d_dc, stream]
+        self._check(_lib.lib().pfc_dynamics_dual_device(self._h, int(n_scene), int(n_dir), *[p or None for p in a]))
+
+    def accelerations_dual(self, H, c, f, dH, dc, df, tau=None, dtau=None):
+        """vdot and its partials dvdot = H^-1 (((df - dc) + dtau) - dH vdot) with the value factor (pfc_accelerations_dual, host
+        buffers, synchronous).  H, c, f, tau as accelerations; dH (n_scene,n_dir,nv,nv), dc, df and dtau (None: zeros)
+        (n_scene,n_dir,nv).  Returns vdot (n_scene,nv), dvdot (n_scene,n_dir,nv) and info (n_scene,)."""
+        _, _, nv = self.mechanism_sizes()
+        c_a = np.ascontiguousarray(c, dtype=np.float64).reshape(-1, nv)
+        n_scene = c_a.shape[0]
+        dc_a = np.ascontiguousarray(dc, dtype=np.float64).reshape(n_scene, -1, nv)
+        n_dir = dc_a.shape[1]
+        arr = lambda a, *shape: None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(*shape)
+        H_a, f_a, t_a = arr(H, n_scene, nv, nv), arr(f, n_scene, nv), arr(tau, n_scene, nv)
+        dH_a, df_a, dt_a = arr(dH, n_scene, n_dir, nv, nv), arr(df, n_scene, n_dir, nv), arr(dtau, n_scene, n_dir, nv)
+        vdot = np.zeros((n_scene, nv)); dvdot = np.zeros((n_scene, n_dir, nv)); info = np.zeros(n_scene, dtype=np.int32)
+        p = lambda a: None if a is None else a.ctypes.data_as(_dp)
+        self._check(_lib.lib().pfc_accelerations_dual(self._h, n_scene, n_dir, p(H_a), p(c_a), p(f_a), p(t_a), p(dH_a), p(dc_a), p(df_a),
+                                                      p(dt_a), p(vdot), p(dvdot), info.ctypes.data_as(_ip)))
+        return vdot, dvdot, info
+
+    def accelerations_dual_device(self, n_scene: int, n_dir: int, d_H: int, d_c: int, d_f: int, d_tau: int, d_dH: int, d_dc: int,
+                                  d_df: int, d_dtau: int, d_vdot: int, d_dvdot: int, d_info: int, stream: int = 0):
+        """pfc_accelerations_dual_device: raw device addresses (d_tau, d_dtau 0: zeros; d_vdot, d_info 0: not wanted); asynchronous on
+        `stream`."""
+        a = [d_H, d_c, d_f, d_tau, d_dH, d_dc, d_df, d_dtau, d_vdot, d_dvdot, d_info, stream]
+        self._check(_lib.lib().pfc_accelerations_dual_device(self._h, int(n_scene), int(n_dir), *[p or None for p in a]))
+
+    def state_derivative_dual_device(self, n_items: int, n_dir: int, d_ins_ids: int, d_scene: int, n_scene: int, d_q: int, d_v: int,
+                                     d_dq: int, d_dv: int, d_s: int, d_ds: int, d_tau: int, d_dtau: int, d_x_w_b: int, d_twist_w_b: int,
+                                     d_jac: int, d_dx_w_b: int, d_dtwist_w_b: int, d_djac: int, d_pose: int, d_twist: int,
+                                     d_x_w_r2: int, d_body_1: int, d_body_2: int, d_dpose: int, d_dtwist: int, d_dx_w_r2: int,
+                                     d_wrench: int, d_sdot: int, d_dwrench: int, d_dsdot: int, d_counts: int, d_f: int, d_df: int,
+                                     d_qdot: int, d_H: int, d_c: int, d_vdot: int, d_info: int, d_dqdot: int, d_dH: int, d_dc: int,
+                                     d_dvdot: int, stream: int = 0):
+        """pfc_state_derivative_dual_device: eval_dual_state_device (d_f, d_df required), dynamics_device, dynamics_dual_device and
+        accelerations_dual_device on one stream; asynchronous, follow with check() (re-issue on ERR_OVERFLOW)."""
+        a = [d_q, d_v, d_dq, d_dv, d_s, d_ds, d_tau, d_dtau, d_x_w_b, d_twist_w_b, d_jac, d_dx_w_b, d_dtwist_w_b, d_djac, d_pose, d_twist,
+             d_x_w_r2, d_body_1, d_body_2, d_dpose, d_dtwist, d_dx_w_r2, d_wrench, d_sdot, d_dwrench, d_dsdot, d_counts, d_f, d_df,
+             d_qdot, d_H, d_c, d_vdot, d_info, d_dqdot, d_dH, d_dc, d_dvdot, stream]
+        self._check(_lib.lib().pfc_state_derivative_dual_device(self._h, int(n_items), int(n_dir), d_ins_ids or None, d_scene or None,
+                                                                int(n_scene), *[p or None for p in a]))
+
+    def state_derivative_dual_device_more(self, n_items: int, n_dir: int, d_ins_ids: int, d_scene: int, n_scene: int, d_q: int, d_v: int,
+                                          d_dq: int, d_dv: int, d_ds: int, d_tau: int, d_dtau: int, d_x_w_b: int, d_twist_w_b: int,
+                                          d_jac: int, d_dx_w_b: int, d_dtwist_w_b: int, d_djac: int, d_x_w_r2: int, d_body_1: int,
+                                          d_body_2: int, d_wrench: int, d_dpose: int, d_dtwist: int, d_dx_w_r2: int, d_dwrench: int,
+                                          d_dsdot: int, d_df: int, d_H: int, d_c: int, d_f: int, d_dqdot: int, d_dH: int, d_dc: int,
+                                          d_dvdot: int, stream: int = 0):
+        """pfc_state_derivative_dual_device_more: eval_dual_state_device_more (d_df required), dynamics_dual_device and
+        accelerations_dual_device (no vdot) for a later chunk at the kept point; reads d_H, d_c, d_f and d_tau as the first chunk
+        left them, writes only partials; asynchronous, follow with check()."""
+        a = [d_q, d_v, d_dq, d_dv, d_ds, d_tau, d_dtau, d_x_w_b, d_twist_w_b, d_jac, d_dx_w_b, d_dtwist_w_b, d_djac, d_x_w_r2, d_body_1,
+             d_body_2, d_wrench, d_dpose, d_dtwist, d_dx_w_r2, d_dwrench, d_dsdot, d_df, d_H, d_c, d_f, d_dqdot, d_dH, d_dc, d_dvdot, stream]
+        self._check(_lib.lib().pfc_state_derivative_dual_device_more(self._h, int(n_items), int(n_dir), d_ins_ids or None, d_scene or None,
+                                                                     int(n_scene), *[p or None for p in a]))
+
+    def state_derivative_dual(self, q, v, s, dq, dv, ds=None, tau=None, dtau=None, ins_ids: Optional[Sequence[int]] = None, scene=None):
+        """From x = [q; v; s] and the seed directions of a Jacobian chunk to [qdot; vdot; sdot] and a column block of its Jacobian
+        (host arrays, synchronous; composed here from force_all_elastic_intersections_dual_state, dynamics, dynamics_dual and
+        accelerations_dual, the calls pfc_state_derivative_dual_device chains on the device).  Arguments as
+        force_all_elastic_intersections_dual_state; tau (n_scene,nv) and dtau (n_scene,n_dir,nv) or None.  Returns (qdot, vdot, sdot,
+        d_qdot (n_scene,n_dir,nq), d_vdot (n_scene,n_dir,nv), d_sdot, info, (f, d_f), (H, c), (d_H, d_c), (wrench, d_wrench, counts))."""
+        wrench, sdot, dw, dsd, counts, f, d_f, _, _, (x, tw, _), (dx, dtw, _) = self.force_all_elastic_intersections_dual_state(
+            q, v, s, dq, dv, ds, ins_ids, scene)
+        qd, H, c = self.dynamics(q, v, x, tw)
+        dqd, dH, dc = self.dynamics_dual(q, v, dq, dv, x, tw, dx, dtw)
+        vdot, dvdot, info = self.accelerations_dual(H, c, f, dH, dc, d_f, tau, dtau)
+        return qd, vdot, sdot, dqd, dvdot, dsd, info, (f, d_f), (H, c), (dH, dc), (wrench, dw, counts)
+
     def dual_seeds_from_bodies(self, x_w_b, twist_w_b, d_x_w_b, d_twist_w_b, ins_ids: Optional[Sequence[int]] = None,
                                scene=None) -> BodySeeds:
         """The Dual seeds of items_from_bodies' items from the partials of the bodies' world states (pfc_dual_seeds_from_bodies, host
