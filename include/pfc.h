@@ -892,7 +892,13 @@ int pfc_contact_surface_fric_device(pfc_handle h, int n_items, const int *d_ins_
  * over the kept polygons, k_fric, evaluates pressure, damping argument and bristle traction once per fan corner and combines
  * them per quadrature point -- they are affine in the point; 0 = re-derives them at every point as the counting kernels do;
  * counts identical, friction wrench equal to rounding: ~1e-15 relative; "debug" evaluations always use the per-point form, so that the
- * friction sums are formed at exactly the traction points pfc_debug_tractions returns; other values PFC_ERR_BAD_ARG), "team" (default 48, at most 48; 0 = never: an evaluation of a few
+ * friction sums are formed at exactly the traction points pfc_debug_tractions returns; other values PFC_ERR_BAD_ARG), "bin_split"
+ * (default 5: the queueing clip kernel -- "clip_queue" -- keeps the clipped polygons of fewer than this many vertices from the front
+ * of a candidate chunk's slot range upward and the others from its back downward, so that the 64 polygons a wave of the
+ * integration and friction passes holds have fans of like length; value evaluations without a Dual list and without "fixed_order"
+ * only, and launches of at least 2^20 candidates only -- 512-candidate chunks, what the gain was measured on; every other path keeps
+ * the dense fill; same counts and traction points, sums equal up to their order; 0 = dense fill everywhere, the behaviour before the
+ * option existed; 3..9 allowed; -9..-3: the split |value| in launches of every size, for tests; other values PFC_ERR_BAD_ARG), "team" (default 48, at most 48; 0 = never: an evaluation of a few
  * pairs too big for one workgroup -- BASELINE's single 9 680-tet x 5 120-triangle pair -- runs as ONE kernel with a team
  * of up to this many workgroups per item -- while a workgroup of the team has at most ~1 200 leaves of the pair to descend: up
  * to 16 poses of that pair; beyond that the batched path is faster --, and a few mid-sized items -- a 972-tet box on the

@@ -576,6 +576,11 @@ struct pfc_context {
     size_t sort_cover = 0;                    // 0: the capacity
     size_t sort_cover_used = 0;               // what the pending evaluation covered
     int opt_vertex_fields = 1;         // option "vertex_fields": k_fric<true> evaluates the fan-point fields per corner; 0: the per-point kernels
+    // option "bin_split": k_clip_queue fills a chunk's slot range from both ends by vertex count (n_poly < bin_split from the front,
+    // the others from the back: kept_slot, pfc_np.h), so that a 64-polygon piece of k_integ / k_fric holds fans of like length.  Value
+    // passes without a Dual list and without fixed_order only, and launches with 512-candidate chunks only (-s: split s at every chunk
+    // size, np_bin_split); 0: dense fill everywhere
+    int opt_bin_split = 5;             // (5: triangles and quadrilaterals from the front, 85 % of the C3 batch's polygons; 4 measured slower)
     int opt_clip_queue = 1;            // option "clip_queue": clip-only narrowphase of big tri-tet batches in k_clip_queue (survivors queued in the ring); 0: k_narrow<.., 2 / 3>
     int fused_skip = 0;                // evaluations left for which the fused kernel stays off after an item did not fit
     int fused_seq = 0;                 // sequence number of the last fused launch (completion word of the polled path)
@@ -999,6 +1004,8 @@ int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double 
     np.pcnt = h->pcnt.p; np.chunk_switch = kNpChunkSwitch; np.poly_cand = o.list ? h->poly_cand.p : nullptr;
     np.surv = o.list ? h->surv.p : nullptr; np.scount = pcount + 1;
     const int np_grid = grid_for(h->ccap, kNpBlock, kNpMaxBlocks);
+    int bin_split = 0;      // binned fill of the kept polygons: k_clip_queue's launches below only (set there)
+    np.bin_split = 0;
     // (fixed_order: always the clip-only kernel + k_integ_fixed, whose run records carry every sum)
     const int np_mode = h->opt_debug ? 1 : ((h->opt_fixed_order || (h->opt_clip_min > 0 && n_items >= h->opt_clip_min)) ? 2 : 0);
     if (np_mode == 1) {
@@ -1017,6 +1024,9 @@ int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double 
             // big tri-tet launches: survivors of the trivial reject queued in the ring, clipped 64 at a time (8 192-pose step
             // 4.17 -> 4.13 ms as two halves, 4.87 -> 4.70 ms unsplit, 2 048 poses 1.288 -> 1.278; 768 poses lose, 0.712 -> 0.721:
             // paired A/B, profiles/r03_ab_clip_queue.txt; option value 2 forces it for every clip-only launch: tests)
+            // (k_integ_fixed / k_fric_fixed count on one record per (chunk, item), the Dual list on candidate order: dense fill)
+            if (!o.list && !h->opt_fixed_order) bin_split = h->opt_bin_split;
+            np.bin_split = bin_split;
             hipLaunchKernelGGL(k_clip_queue, dim3(np_grid), dim3(kNpBlock), 0, st, np);
         } else if (o.half || (n_items >= 640 && n_items < 1024)) {
             if (h->any_tet_tet) hipLaunchKernelGGL((k_narrow<true, 3>), dim3(np_grid), dim3(kNpBlock), 0, st, np);
@@ -1027,7 +1037,7 @@ int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double 
         }
         IntegArgs ig;
         ig.items = h->items.p; ig.n_items = n_items; ig.ccount = ccount; ig.ccap = (int)h->ccap; ig.chunk_switch = kNpChunkSwitch;
-        ig.pcnt = h->pcnt.p; ig.poly_item = h->poly_item.p; ig.poly = h->poly.p; ig.pcap = np.pcap;
+        ig.pcnt = h->pcnt.p; ig.bin_split = bin_split; ig.poly_item = h->poly_item.p; ig.poly = h->poly.p; ig.pcap = np.pcap;
         ig.poly_cand = np.poly_cand; ig.surv = np.surv; ig.scount = np.scount; ig.acc = h->acc.p; ig.rec = h->rec.p;
         ig.rgn = h->rgn.p; ig.rr_cap = np.rr_cap; ig.icnt = h->icnt.p; ig.status = h->status.p;
         ig.det = h->opt_fixed_order ? h->det.p : nullptr;
@@ -1055,7 +1065,7 @@ int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double 
         hipLaunchKernelGGL(k_eig, dim3(n_items), dim3(64), 0, st, br);   // one wave per item
         FricArgs fr;
         fr.items = h->items.p; fr.poly_item = h->poly_item.p; fr.poly = h->poly.p; fr.ccount = ccount; fr.ccap = (int)h->ccap;
-        fr.chunk_switch = kNpChunkSwitch; fr.pcnt = h->pcnt.p;
+        fr.chunk_switch = kNpChunkSwitch; fr.pcnt = h->pcnt.p; fr.bin_split = bin_split;
         fr.pcap = np.pcap; fr.res = h->res.p; fr.acc = h->acc.p;
         fr.n_items = n_items; fr.status = h->status.p;
         fr.sink = FixedSink{nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr};
@@ -1922,6 +1932,7 @@ static int eval_device(pfc_context *h, int n_items, const int *d_ins_ids, const 
     t->opt_poison = h->opt_poison;
     if (t->opt_clip_min != h->opt_clip_min) { t->opt_clip_min = h->opt_clip_min; t->ghave[0] = t->ghave[1] = false; }
     if (t->opt_clip_queue != h->opt_clip_queue) { t->opt_clip_queue = h->opt_clip_queue; t->ghave[0] = t->ghave[1] = false; }
+    if (t->opt_bin_split != h->opt_bin_split) { t->opt_bin_split = h->opt_bin_split; t->ghave[0] = t->ghave[1] = false; }
     if (t->opt_vertex_fields != h->opt_vertex_fields) { t->opt_vertex_fields = h->opt_vertex_fields; t->ghave[0] = t->ghave[1] = false; }
     t->opt_graph = h->opt_graph;
     if (t->opt_no_filter != h->opt_no_filter) { t->opt_no_filter = h->opt_no_filter; t->ghave[0] = t->ghave[1] = false; }
@@ -4373,6 +4384,12 @@ int pfc_set_option(pfc_handle h, const char *name, long long value) {
     else if (!std::strcmp(name, "vertex_fields")) {
         if (value != 0 && value != 1) return fail(h, PFC_ERR_BAD_ARG, "vertex_fields must be 0 (per-point k_fric) or 1 (per-corner fields)");
         h->opt_vertex_fields = (int)value; h->ghave[0] = h->ghave[1] = false; h->dghave = false;
+    }
+    else if (!std::strcmp(name, "bin_split")) {
+        const long long sp = value < 0 ? -value : value;
+        if (value != 0 && (sp < 3 || sp > 9))
+            return fail(h, PFC_ERR_BAD_ARG, "bin_split must be 0 (dense fill), 3..9 (polygons of fewer vertices fill a 512-candidate chunk from its front) or -9..-3 (chunks of every size)");
+        h->opt_bin_split = (int)value; h->ghave[0] = h->ghave[1] = false; h->dghave = false;
     }
     else if (!std::strcmp(name, "poison")) h->opt_poison = value != 0;
     else if (!std::strcmp(name, "fused")) { h->opt_fused = value != 0; h->fused_skip = 0; }

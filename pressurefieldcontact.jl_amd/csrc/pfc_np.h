@@ -19,6 +19,7 @@ struct NpArgs {
     int *rgn;        // region counters of the record list (kRgn x kRgnStride ints, word 1)
     int rr_cap;      // record slots per region
     int *pcnt;       // kept polygons per candidate chunk (written for every chunk of the evaluation)
+    int bin_split;   // k_clip_queue: option "bin_split" as set (np_bin_split turns it into the launch's split; 0 dense fill)
     int chunk_switch;  // number of chunks a batch must at least fall into (np_chunk picks the chunk size from it)
     int *poly_cand;  // clip-only mode with the Dual list on: candidate index of every kept polygon, or null
     int *icnt;
@@ -69,6 +70,13 @@ __device__ __forceinline__ int np_chunk(int n_c, int chunk_switch) {
     int C = kNpChunkBig;
     while (C > kNpBlock && (long long)C * chunk_switch > n_c) C >>= 1;
     return C;
+}
+// The split of a launch's kept polygons (kept_slot below) from option "bin_split": s > 0 bins launches with full-size chunks only --
+// where it was measured to pay; a smaller chunk keeps one or two pieces of polygons, which binning cannot shorten by much, and such
+// launches keep the order of their sums --, -s bins every launch (tests), 0 none.  The clip kernel and both passes over the kept
+// polygons derive it from the same candidate count.
+__device__ __forceinline__ int np_bin_split(int opt, int C) {
+    return opt > 0 ? (C == kNpChunkBig ? opt : 0) : -opt;
 }
 
 // weightPoly (src/math_kernel/utility.jl:21-26) on 4-vectors held in LDS slots
@@ -951,8 +959,12 @@ __global__ void __launch_bounds__(kNpBlock) k_clip_queue(NpArgs g) {
     for (int ch = blockIdx.x; ch < n_chunk; ch += gridDim.x) {
         const int n_here = n_c - ch * C < C ? n_c - ch * C : C;
         const int n_round = (n_here + kNpBlock - 1) / kNpBlock;
+        const int bin_split = np_bin_split(g.bin_split, C);
         int q = 0;    // queued entries
-        int pc = 0;   // polygons kept so far in this chunk's slot range
+        // polygons kept so far in this chunk's slot range: the front class counts up from slot 0, the back class (option
+        // "bin_split": n_poly >= bin_split; none with bin_split 0) down from slot C - 1 -- both never exceed the chunk's
+        // survivors <= C together, so the two regions cannot meet
+        int pc = 0, pcb = 0;
         // clips entries 0 .. min(q, 64) - 1, one per lane; entries 64 .. q - 1 become entries 0 .. q - 65
         auto dense_round = [&]() {
             const int n_take = q < kNpBlock ? q : kNpBlock;
@@ -996,9 +1008,11 @@ __global__ void __launch_bounds__(kNpBlock) k_clip_queue(NpArgs g) {
                 if (err) atomicOr(g.status, kStNonFinite);
             }
             const bool has_poly = n_poly >= 3;
-            const unsigned long long km = __ballot(has_poly);
-            const int slot = ch * C + pc + __popcll(km & below);
-            pc += __popcll(km);
+            const bool back = has_poly && bin_split > 0 && n_poly >= bin_split;
+            const unsigned long long km = __ballot(has_poly), kb = __ballot(back), ka = km & ~kb;
+            const int slot = back ? ch * C + C - 1 - (pcb + __popcll(kb & below)) : ch * C + pc + __popcll(ka & below);
+            pc += __popcll(ka);
+            pcb += __popcll(kb);
             if (has_poly) np_keep_polygon(ring, n_poly, V, E, nh, g, slot, item, ch * C + pos);
             if (km) {
                 const int item_first = __builtin_amdgcn_readfirstlane(item);      // lane 0 always holds an entry here
@@ -1055,10 +1069,52 @@ __global__ void __launch_bounds__(kNpBlock) k_clip_queue(NpArgs g) {
             if (q >= kNpBlock) dense_round();
         }
         if (q > 0) dense_round();
-        if (lane == 0) g.pcnt[ch] = pc;
+        if (lane == 0) g.pcnt[ch] = pc | (pcb << 16);
     }
 #undef QZ
 #undef QX
+}
+
+// =================================================================================================================
+// Where the passes over the kept polygons (k_integ, k_fric) find a chunk's polygons.  Dense fill (k_narrow; k_clip_queue with
+// bin_split 0): pcnt[ch] polygons in the slots from ch C upward, walked 64 at a time.  Binned fill (k_clip_queue, option
+// "bin_split"): pcnt[ch] = cntA | cntB << 16, cntA polygons of the small-fan class from ch C upward and cntB of the large-fan class
+// from ch C + C - 1 downward.  A 64-polygon PIECE is an aligned block of 64 slots of one region, so a wave's fan loop is as long as
+// the longest fan of its class and the vertex fields beyond it are never touched.  The front pieces come first, in slot order
+// (= candidate order); then the back pieces from the LOWEST slots (the chunk's last candidates) to the highest: the item the front
+// region ends with is the one the back region starts with, so a chunk that holds a run boundary of the candidate list costs
+// k_integ one run more than the dense fill, not two.  Where the two regions end in the SAME block (a chunk filled to its last block;
+// always when C = 64, a small launch) that block is walked once, with the front's last piece: no more pieces than the dense fill.
+// =================================================================================================================
+struct KeptChunk { int cntA, cntB, nA, n; };       // polygons per region, front pieces, pieces
+__device__ __forceinline__ KeptChunk kept_chunk(int word, int C, int binned) {
+    KeptChunk k;
+    if (binned) {
+        k.cntA = word & 0xFFFF; k.cntB = (word >> 16) & 0xFFFF;
+        if (k.cntA > C) k.cntA = C;
+        if (k.cntB > C - k.cntA) k.cntB = C - k.cntA;
+    } else {
+        k.cntA = word > C ? C : (word < 0 ? 0 : word); k.cntB = 0;
+    }
+    k.nA = (k.cntA + 63) >> 6;
+    const int nB = (k.cntB + 63) >> 6;
+    // cntA + cntB <= C: the blocks of the two regions are disjoint, or share exactly one (nA + nB = C / 64 + 1)
+    k.n = k.nA + nB - ((k.nA > 0 && nB > 0 && k.nA + nB > (C >> 6)) ? 1 : 0);
+    return k;
+}
+// slot (offset in the chunk's range, 0 .. C - 1) of lane `lane` of piece `piece` < k.n, and whether it holds a polygon.  Back piece p
+// (counted from the back) is the 64 slots below C - 64 p; C is a multiple of 64, so no offset leaves the range.  With cntB = 0 these
+// are the dense fill's indices.
+__device__ __forceinline__ int kept_slot(const KeptChunk &k, int C, int piece, int lane, bool &active) {
+    if (piece < k.nA) {
+        const int off = piece * 64 + lane;
+        active = off < k.cntA || off >= C - k.cntB;      // (the second: the block both regions end in)
+        return off;
+    }
+    const int p = k.n - 1 - piece;
+    const int off = C - 64 * (p + 1) + lane;
+    active = off >= C - k.cntB;
+    return off;
 }
 
 // =================================================================================================================
@@ -1079,6 +1135,7 @@ struct IntegArgs {
     const int *ccount;
     int ccap, chunk_switch;
     const int *pcnt;
+    int bin_split;           // the fill of the clip kernel that wrote pcnt (NpArgs::bin_split, np_bin_split)
     int *poly_item;          // key of a polygon that must not reach k_fric (no pressure point, regularized item) is cleared
     const double *poly;
     int pcap;
@@ -1131,8 +1188,7 @@ __device__ __forceinline__ void integ_body(const IntegArgs &g, double *m27) {
     const int n_chunk = (n_c + C - 1) / C;
     const size_t P = (size_t)g.pcap;
     for (int ch = blockIdx.x; ch < n_chunk; ch += gridDim.x) {
-        int cnt = __builtin_amdgcn_readfirstlane(g.pcnt[ch]);
-        if (cnt > C) cnt = C;
+        const KeptChunk kc = kept_chunk(__builtin_amdgcn_readfirstlane(g.pcnt[ch]), C, np_bin_split(g.bin_split, C));
         // the running sums of the current (chunk, item) run: ten in registers, the 27 moments in this lane's LDS column
         int cur = -1, n_tr = 0;
         bool cur_reg = false;
@@ -1213,9 +1269,9 @@ __device__ __forceinline__ void integ_body(const IntegArgs &g, double *m27) {
             const int nt = wave_total_i(n_tr, lane);
             if (lane == 0 && nt) atomicAdd(&g.icnt[4 * (size_t)cur + 3], nt);
         };
-        for (int p0 = 0; p0 < cnt; p0 += 64) {
-            const int idx = ch * C + p0 + lane;
-            const bool active = p0 + lane < cnt;
+        for (int piece = 0; piece < kc.n; ++piece) {
+            bool active;
+            const int idx = ch * C + kept_slot(kc, C, piece, lane, active);
             unsigned pk = active ? (unsigned)g.poly_item[idx] : 0u;
             if ((pk >> 28) > 8u || ((pk >> 28) >= 3u && (pk & 0x0FFFFFFFu) >= (unsigned)g.n_items)) {
                 atomicOr(g.status, kStHole);     // not a key k_narrow writes: an unwritten slot is reported, never followed
@@ -1396,6 +1452,7 @@ struct FricArgs {
     const int *ccount;   // candidate count and the chunk rule (np_chunk): the kept polygons sit in per-chunk slot ranges
     int ccap, chunk_switch;
     const int *pcnt;     // kept polygons per chunk
+    int bin_split;       // the fill of the clip kernel that wrote pcnt (NpArgs::bin_split, np_bin_split)
     int pcap;
     int n_items;
     unsigned *status;
@@ -1414,11 +1471,10 @@ __device__ __forceinline__ void fric_body(const FricArgs &g) {
     const int C = np_chunk(n_c, g.chunk_switch);
     const int n_chunk = (n_c + C - 1) / C;
     for (int ch = blockIdx.x; ch < n_chunk; ch += gridDim.x) {
-      int cnt = __builtin_amdgcn_readfirstlane(g.pcnt[ch]);
-      if (cnt > C) cnt = C;
-      for (int p0 = 0; p0 < cnt; p0 += 64) {
-        const int idx = ch * C + p0 + lane;
-        const bool active = p0 + lane < cnt;
+      const KeptChunk kc = kept_chunk(__builtin_amdgcn_readfirstlane(g.pcnt[ch]), C, np_bin_split(g.bin_split, C));
+      for (int piece = 0; piece < kc.n; ++piece) {
+        bool active;
+        const int idx = ch * C + kept_slot(kc, C, piece, lane, active);
         double sum[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k) sum[k] = 0.0;
@@ -1548,7 +1604,7 @@ __device__ __forceinline__ void fric_body(const FricArgs &g) {
             }
             }
         }
-        accumulate_items<6, FX>(g.acc, item, FX ? (active && (pk >> 28) >= 3u) : active, contributed, sum, kAccFric, kAccStride, &g.sink, (ch * C + p0) >> 6);
+        accumulate_items<6, FX>(g.acc, item, FX ? (active && (pk >> 28) >= 3u) : active, contributed, sum, kAccFric, kAccStride, &g.sink, ((ch * C) >> 6) + piece);
       }
     }
 }
