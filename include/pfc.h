@@ -89,6 +89,16 @@ const char *pfc_last_error(pfc_handle h);
  *   Ebar     ContactProperties.Ē (tet meshes; ignored for tri meshes)
  *   nodes    n_node entries, node 0 = root: c (x3), e (x3), R (x9 column-major), child (x2), leaf (element index,
  *            or PFC_INTERNAL_NODE)
+ * The tree is used as given, like the reference's tree_tree_intersect / BB_BB_intersect (src/obb/tree_types.jl:88-111,
+ * src/obb/bb_intersection.jl:2-74): any R is honoured on every node, leaf or internal, by every broadphase kernel; any
+ * binary topology over the elements is taken (every internal node has two children in [1, n_node), each node is reached
+ * once from the root, leaf ids are element indices: anything else is PFC_ERR_BAD_ARG); a box need not contain its children --
+ * a child pair is tested iff its parent pair intersects.  An internal box whose R is not bitwise the identity is always
+ * settled by the Float64 test, never by the single-precision filter (whose 24 u radius is derived for axis-aligned internal
+ * boxes), so such trees cost broadphase time, not accuracy.
+ * Depth limit: for every instruction, depth(tree_1) + depth(tree_2) <= 296 (root = depth 0; the depth-first kernels keep
+ * 3 (depth sum + 1) + 3 of their 1 024 stack slots in reserve and need 128 free ones); pfc_finalize returns PFC_ERR_BAD_ARG
+ * for a deeper pair ("OBB trees too deep").
  * Returns the mesh id (>= 0) or -(pfc_status).
  */
 int pfc_add_mesh(pfc_handle h, int n_pt, const double *xyz, int n_tri, const int *tri, int n_tet, const int *tet,

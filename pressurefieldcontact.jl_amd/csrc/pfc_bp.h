@@ -260,6 +260,10 @@ __device__ __forceinline__ NodeF load_nodef(const NodeF *n) {
 //       Face axis of A: u |t_i| + u e_a,i + (9 + 1 + 3) u sum e_b + 2 u S <= 15 u S; face axis of B: (9 + 1 + 3) u |v|_1 +
 //       13 u sum e_a + u e_b,j + 2 u S <= 15 u S; edge-edge: (9 + 1) u on each product + 2 u of fused rounding, + 2 u S:
 //       <= 14 u S.  E = 24 u S.
+//       Premise: a pair without a leaf (any_leaf = false, the 24 u radius) holds two identity quaternions.  The library's
+//       builders only make such internal boxes; a host-supplied tree may rotate them.  Enforced in pfc_add_mesh: an
+//       internal node whose R is not bitwise the identity gets the exact-only mark (NaN e[0]), so every pair with such a
+//       node comes back undecided and is settled by the Float64 test; the kernels need no branch for it.
 // Hence |d_float - d_ref| < E = k S + eabs on every axis: d_float > E proves the reference separates on that axis, d_float < -E on all
 // 15 axes proves it does not separate on any; everything else is settled by the exact Float64 test.  The constants in the
 // code are 1.44e-6 (>= 24 u = 1.4305e-6) and 1.92e-5 (>= 320 u = 1.9073e-5).  tests/test_gpu_broadphase.py probes touching
@@ -662,9 +666,10 @@ __global__ void __launch_bounds__(64) k_bp_dfs(DfsArgs g) {
             const int ia = node_index(e.x), ib = node_index(e.y);
             // The path is chosen per wave, never per lane: popped pairs sit at similar depths, so a wave is usually
             // all internal-internal (axis-aligned shortcut: R_tot = R_a_b, 128 bytes per pair) or reaches the
-            // tight-fitted leaves together (general composition; exact for identity rotations too).  Leaf-ness comes
-            // with the link, so all loads of the iteration are issued before the first use.
-            const bool general = __any(la || lb);
+            // tight-fitted leaves together (general composition; exact for identity rotations too).  A node's R is
+            // read where the link says leaf or the head says "not axis aligned" (aabb == 0: a host-supplied tree may
+            // hold rotated internal boxes, include/pfc.h), and one such node in an active lane sends the whole wave
+            // through the general composition.
             NodeHead a, b;
             a.leaf = kInternal; b.leaf = kInternal; a.child0 = a.child1 = b.child0 = b.child1 = 0; a.aabb = b.aabb = 1;
 #pragma unroll
@@ -673,16 +678,16 @@ __global__ void __launch_bounds__(64) k_bp_dfs(DfsArgs g) {
             if (act) {
                 a = load_head(n1 + ia);
                 b = load_head(n2 + ib);
-                if (general) {
-                    if (la) {
+            }
+            const bool ra = la || (act && !a.aabb), rb = lb || (act && !b.aabb);
+            const bool general = __any(ra || rb);
+            if (ra) {
 #pragma unroll
-                        for (int k = 0; k < 9; ++k) Ra[k] = ((const GNodeRec *)n1)[ia].R[k];
-                    }
-                    if (lb) {
+                for (int k = 0; k < 9; ++k) Ra[k] = ((const GNodeRec *)n1)[ia].R[k];
+            }
+            if (rb) {
 #pragma unroll
-                        for (int k = 0; k < 9; ++k) Rb[k] = ((const GNodeRec *)n2)[ib].R[k];
-                    }
-                }
+                for (int k = 0; k < 9; ++k) Rb[k] = ((const GNodeRec *)n2)[ib].R[k];
             }
 #ifdef PFC_STAMPS
             { double keep = a.c[0] + b.c[0] + Ra[4] + Rb[4]; asm volatile("" ::"v"(keep)); }   // the loads have landed

@@ -1673,6 +1673,12 @@ int pfc_add_mesh(pfc_handle h, int n_pt, const double *xyz, int n_tri, const int
             if (r.leaf == kInternal) { order.push_back(r.child0); order.push_back(r.child1); }
         }
         if ((int)order.size() != n_node) return -fail(h, PFC_ERR_BAD_ARG, "pfc_add_mesh: the node array is not a tree");
+        // ... and every node once: a child shared by two parents next to a node nobody points to has the right count too
+        std::vector<char> seen(n_node, 0);
+        for (int k : order) {
+            if (seen[k]) return -fail(h, PFC_ERR_BAD_ARG, "pfc_add_mesh: the node array is not a tree");
+            seen[k] = 1;
+        }
         std::vector<int> inv(n_node);
         for (int k = 0; k < n_node; ++k) inv[order[k]] = k;
         std::vector<NodeRec> bfs(n_node);
@@ -1727,6 +1733,10 @@ int pfc_add_mesh(pfc_handle h, int n_pt, const double *xyz, int n_tri, const int
             const double n2 = w * w + x * x + y * y + z * z, u = 5.9604644775390625e-8;
             // a node that fails is never decided in single precision: NaN extent -> S = NaN -> exact test (test_pair_f32)
             if (!(std::isfinite(qn) && worst <= 4.0 * u && std::fabs(n2 - 1.0) <= 2.25 * u)) f.e[0] = std::numeric_limits<float>::quiet_NaN();
+            // The 24 u radius of an internal x internal pair is derived for identity quaternions ("Error radius E", (5)); an
+            // internal node with any other R (a host-supplied tree) carries the same exact-only mark, so that premise holds
+            // for every pair the single-precision test decides at that radius.
+            if (r.leaf == kInternal && !r.aabb) f.e[0] = std::numeric_limits<float>::quiet_NaN();
         }
         if (r.leaf == kInternal) { f.link0 = r.child0; f.link1 = r.child1; }
         else { f.link0 = r.leaf; f.link1 = -1; }

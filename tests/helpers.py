@@ -35,6 +35,19 @@ def sorted_pairs(pairs, clip_n):
     return pairs[order], clip_n[order]
 
 
+def sdot_tolerance(r):
+    """The project's parity bound for ṡ of one item against its oracle debug result r (tests/test_gpu_scale.py, bench.py's
+    validation): 1e-6, and 1e-3 for a bristle patch whose scaled stiffness K̄ has two or more eigenvalues below 1e-12 σ_max
+    (slivers, edge and single-triangle contacts), where the reference's own ṡ moves by more than 1e-6 under a rounding-level
+    change of K̄ (tests/test_sdot_sensitivity.py)."""
+    if r.has_K:
+        Kb = np.diag(r.Sinv) @ r.K @ np.diag(r.Sinv)
+        ev = np.linalg.eigvalsh((Kb + Kb.T) / 2)
+        if np.sum(ev < 1e-12 * ev[-1]) >= 2:
+            return 1e-3
+    return 1e-6
+
+
 def rel_err(a, b):
     a = np.asarray(a, dtype=np.float64); b = np.asarray(b, dtype=np.float64)
     scale = max(np.linalg.norm(b), 1e-300)
@@ -341,3 +354,182 @@ class HostFormsCase:
         assert P > 0 and T > 0      # the scene has contact
         cut = dict(poly_idx=P, poly_xyz=P, poly_trac=P + 1, trac=T, fric=T)
         return {k: (v[:cut[k]] if k in cut else v) for k, v in o.items() if v is not None}
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# Host-supplied OBB trees that the library's builders never make (pfc_add_mesh takes any flattened tree, include/pfc.h):
+# rotated, dishonest (shrunk) and mixed internal boxes, random and degenerate topologies.  Every generator returns a
+# tree of the same container type over the same leaf set, nodes in preorder (node 0 = root, parents before children).
+# ----------------------------------------------------------------------------------------------------------------
+def _node_axes(tree, k):
+    return np.asarray(tree.R[k], dtype=np.float64).reshape(3, 3, order="F")
+
+
+def _is_internal(tree):
+    return np.asarray(tree.child)[:, 0] >= 0
+
+
+def _random_rotation(rng):
+    q = rng.standard_normal(4)
+    q /= np.linalg.norm(q)
+    w, x, y, z = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def tree_rotated(tree, rng, fraction=1.0, scale=1.0):
+    """Internal nodes (a random `fraction` of them) get a random rotation Q and the extents of the box with those axes
+    that encloses the node's own box (same centre): R = Q, e = |Q' A| e for a box with axes A; then e *= scale."""
+    c, e, R = tree.c.copy(), tree.e.copy(), tree.R.copy()
+    for k in np.nonzero(_is_internal(tree))[0]:
+        Q = _random_rotation(rng)               # drawn for every node: the stream does not depend on `fraction`
+        if rng.random() >= fraction:
+            continue
+        e[k] = (np.abs(Q.T @ _node_axes(tree, k)) @ tree.e[k]) * scale
+        R[k] = Q.reshape(-1, order="F")
+    return type(tree)(c, e, R, tree.child.copy(), tree.leaf.copy())
+
+
+def tree_shrunk(tree, rng):
+    """tree_rotated with the internal extents x 0.7: boxes that do not contain their children.  A pair is tested iff its
+    parent pair hit, on the device as in the reference."""
+    return tree_rotated(tree, rng, scale=0.7)
+
+
+def tree_mixed(tree, rng):
+    """A random half of the internal nodes rotated, the rest left as they are: waves hold both kinds."""
+    return tree_rotated(tree, rng, fraction=0.5)
+
+
+def tree_identity_twin(tree):
+    """The same centres and extents with R := I on every internal node (what a kernel that ignores R on internal
+    nodes would see)."""
+    R = tree.R.copy()
+    R[_is_internal(tree)] = np.eye(3).reshape(-1)
+    return type(tree)(tree.c.copy(), tree.e.copy(), R, tree.child.copy(), tree.leaf.copy())
+
+
+def _leaf_boxes(tree):
+    """[(c, e, R9, element)] of the leaves, and their axis-aligned bounds (lo, hi)."""
+    out = []
+    for k in np.nonzero(~_is_internal(tree))[0]:
+        h = np.abs(_node_axes(tree, k)) @ tree.e[k]
+        out.append(((tree.c[k].copy(), tree.e[k].copy(), tree.R[k].copy(), int(tree.leaf[k])), tree.c[k] - h, tree.c[k] + h))
+    return out
+
+
+def _flatten(tree, root, internal_code):
+    """root: nested (leaf_box, None, None, lo, hi) / (None, left, right, lo, hi) -> preorder arrays (iterative: a chain of
+    a hundred levels is a legitimate input)."""
+    C_, E_, R_, CH, LF = [], [], [], [], []
+    stack = [(root, -1, 0)]
+    I9 = np.eye(3).reshape(-1)
+    while stack:
+        t, parent, side = stack.pop()
+        k = len(C_)
+        if parent >= 0:
+            CH[parent][side] = k
+        if t[0] is not None:
+            c, e, R9, elem = t[0]
+            C_.append(c); E_.append(e); R_.append(R9); CH.append([-1, -1]); LF.append(elem)
+        else:
+            lo, hi = t[3], t[4]
+            C_.append((hi + lo) * 0.5); E_.append((hi - lo) * 0.5); R_.append(I9); CH.append([-1, -1]); LF.append(internal_code)
+            stack.append((t[2], k, 1))
+            stack.append((t[1], k, 0))
+    return type(tree)(np.array(C_), np.array(E_), np.array(R_), np.array(CH, dtype=np.int32), np.array(LF, dtype=np.int32))
+
+
+def _internal_code(tree):
+    ii = np.nonzero(_is_internal(tree))[0]
+    return int(tree.leaf[ii[0]]) if ii.size else -9999
+
+
+def _join(a, b):
+    return (None, a, b, np.minimum(a[3], b[3]), np.maximum(a[4], b[4]))
+
+
+def tree_random_topology(tree, rng):
+    """A random binary tree over the leaves of `tree` (their tight boxes kept): two random subtrees are joined until one
+    is left; an internal box is the axis-aligned union of its children."""
+    forest = [(lb, None, None, lo, hi) for lb, lo, hi in _leaf_boxes(tree)]
+    while len(forest) > 1:
+        i, j = rng.choice(len(forest), 2, replace=False)
+        a, b = forest[i], forest[j]
+        forest = [t for k, t in enumerate(forest) if k != i and k != j] + [_join(a, b)]
+    return _flatten(tree, forest[0], _internal_code(tree))
+
+
+def tree_caterpillar(tree, rng):
+    """Every internal node has one leaf child (randomly the first or the second) and the rest of the chain as the other:
+    depth n_leaf - 1, long runs of leaf x internal descent (tree_types.jl:97-103)."""
+    leaves = [(lb, None, None, lo, hi) for lb, lo, hi in _leaf_boxes(tree)]
+    order = rng.permutation(len(leaves))
+    t = leaves[order[0]]
+    for k in order[1:]:
+        t = _join(leaves[k], t) if rng.random() < 0.5 else _join(t, leaves[k])
+    return _flatten(tree, t, _internal_code(tree))
+
+
+def single_leaf_mesh(mesh, rng):
+    """(mesh of one random element of `mesh`, its one-node tree): the leaf's box is the element's axis-aligned box, as
+    the reference leaves it for a single element (blob_types.jl:139-146)."""
+    tri = mesh.tri is not None
+    elem = mesh.tri if tri else mesh.tet
+    idx = elem[int(rng.integers(0, elem.shape[0]))]
+    pts = mesh.point[idx]
+    one = np.arange(idx.size, dtype=elem.dtype).reshape(1, -1)
+    m1 = type(mesh)(pts.copy(), tri=one) if tri else type(mesh)(pts.copy(), tet=one, eps=mesh.eps[idx].copy())
+    lo, hi = pts.min(axis=0), pts.max(axis=0)
+    return m1, ((hi + lo) * 0.5).reshape(1, 3), ((hi - lo) * 0.5).reshape(1, 3)
+
+
+HOST_TREE_GENERATORS = {"rotated": tree_rotated, "shrunk": tree_shrunk, "mixed": tree_mixed,
+                        "random_topology": tree_random_topology, "caterpillar": tree_caterpillar}
+HOST_TREE_SCENES = tuple(HOST_TREE_GENERATORS) + ("single_leaf",)
+
+
+def host_tree_meshes(pfc, fine=False):
+    """The 80-triangle sphere (r 0.3) and the 48-tet box (half-width 0.5) with their built trees; fine: 320 triangles and
+    192 tets (512 leaves: a team of four workgroups per item)."""
+    G = pfc.geometry
+    import tree_reference
+    sph = G.as_tri_emesh(G.emesh_sphere(0.3, 4 if fine else 2))
+    box = G.as_tet_emesh(G.emesh_box_div(np.array([0.5, 0.5, 0.5]), 4 if fine else 2))
+    return sph, tree_reference.build_tree_py(G, sph), box, tree_reference.build_tree_py(G, box)
+
+
+def host_tree_poses(pfc, rng, n, span):
+    """n random relative poses (translations uniform in +-span), twists and bristle states, all non-zero."""
+    pose = np.array([pfc.scenario.relative_pose(pfc.configs.random_rotation(rng), rng.uniform(-span, span, 3), np.eye(3), np.zeros(3))
+                     for _ in range(n)])
+    twist = rng.standard_normal((n, 6)) * np.array([1, 1, 1, 0.1, 0.1, 0.1])
+    return pose, twist, rng.standard_normal((n, 6)) * 1e-3
+
+
+# translations: the shares of items with and without candidates are asserted by the tests
+HOST_TREE_SPAN = {"single_leaf": 0.7}
+
+
+def host_tree_workload(pfc, scene, n_items, seed=7, fine=False, span=None):
+    """One scenario of tests/test_gpu_host_trees.py: the sphere / box pair under the generated trees of `scene`
+    ("built": the builder's own), a regularized and a bristle instruction, items alternating between them."""
+    G, Cf = pfc.geometry, pfc.configs
+    span = HOST_TREE_SPAN.get(scene, 1.0) if span is None else span
+    rng = np.random.default_rng([seed, sorted(HOST_TREE_SCENES + ("built",)).index(scene)])
+    sph, t1, box, t2 = host_tree_meshes(pfc, fine)
+    if scene == "single_leaf":
+        # one tet of the box under the whole sphere (a one-triangle mesh would make every bristle patch planar: a stiffness of
+        # rank 3, whose sdot is rounding noise in the reference itself, tests/test_sdot_sensitivity.py)
+        box, c, e = single_leaf_mesh(box, rng)
+        t2 = G.OBBTree(c, e, np.eye(3).reshape(1, 9), np.full((1, 2), -1, dtype=np.int32), np.zeros(1, dtype=np.int32))
+        t1 = tree_caterpillar(t1, rng)
+    elif scene != "built":
+        gen = HOST_TREE_GENERATORS[scene]
+        t1, t2 = gen(t1, rng), gen(t2, rng)
+    meshes = [Cf.MeshSpec("sphere", sph, t1, None), Cf.MeshSpec("box", box, t2, 1.0e6)]
+    ins = [Cf.InsSpec(0, 1, "regularized", chi=0.5, mu_d=0.3, v_tol=1e-2), Cf.InsSpec(0, 1, "bristle", chi=0.3, mu_d=0.4)]
+    pose, twist, s = host_tree_poses(pfc, np.random.default_rng(seed), n_items, span)     # the same poses for every scene
+    ids = (np.arange(n_items) % 2).astype(np.int32)
+    return Cf.Workload("host trees: " + scene, meshes, ins, ids, pose, twist, s)

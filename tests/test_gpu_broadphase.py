@@ -9,6 +9,10 @@ tol = 1e-3 (decided by the Float32 filter), 1e-6 (the reference's tolerance), 1e
 error radius: the pair must come back "undecided" and be settled by the exact Float64 test), with the filter on
 (k_bp_dfs32), off (option no_filter = 1: k_bp_dfs, all Float64) and through the seed-expansion kernel (k_bp_expand).  Every verdict must equal the oracle's
 BB_BB_intersect (src/obb/bb_intersection.jl:2-74) and, for tol >= 1e-9, the geometric truth.
+
+The same cases also run in evaluations of 256 items through the one-launch kernel k_fused (its own lookahead descent, filter
+on and off), and, on every path, with the boxes rotated in their mesh frames (rotated leaf: the quaternion path; rotated
+internal box: exact-only, pfc_add_mesh) at the further tolerances 3e-6 and 1e-5, between the filter's two radii.
 """
 import ctypes as C
 
@@ -42,7 +46,7 @@ def _axis_angle(th, a):
     return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
 
 
-def _cases():
+def _cases(tols=TOLS):
     """(e1, e2, R_a_b, t_a_b, expected) for the face-corner (6 x 8 x 2) and edge-edge (6 x 15 x 5 x 3) touching
     configurations at 1 -/+ tol."""
     out = []
@@ -54,7 +58,7 @@ def _cases():
             for d1, d2 in ((f, c), (c, f)):
                 R = _rot_between(d2, d1)
                 sep = d1 * e1 + R @ (d2 * e2)
-                for tol in TOLS:
+                for tol in tols:
                     out.append((0, R, sep * (1 - tol), 1, tol))
                     out.append((0, R, sep * (1 + tol), 0, tol))
     rng = np.random.default_rng(3)
@@ -65,21 +69,23 @@ def _cases():
                 for ax in np.eye(3):
                     R = _axis_angle(th, e) @ _axis_angle(extra, ax)
                     sep = e * 2.0
-                    for tol in TOLS:
+                    for tol in tols:
                         out.append((1, R, sep * (1 - tol), 1, tol))
                         out.append((1, R, sep * (1 + tol), 0, tol))
     return out
 
 
-def _tree(pfc, e, internal):
+def _tree(pfc, e, internal, Q=None):
+    """Q: the rotation of the box that carries the test (the one node, or the root of three); default the identity."""
     G = pfc.geometry
     I9 = np.eye(3).reshape(-1)
+    Q9 = I9 if Q is None else np.asarray(Q, dtype=float).reshape(-1, order="F")
     if not internal:
-        return G.OBBTree(np.zeros((1, 3)), np.asarray(e, dtype=float).reshape(1, 3), I9.reshape(1, 9),
+        return G.OBBTree(np.zeros((1, 3)), np.asarray(e, dtype=float).reshape(1, 3), Q9.reshape(1, 9),
                          np.full((1, 2), -1, dtype=np.int32), np.zeros(1, dtype=np.int32))
     c = np.zeros((3, 3))
     ee = np.array([e, [1e-3] * 3, [1e-3] * 3], dtype=float)
-    return G.OBBTree(c, ee, np.tile(I9, (3, 1)), np.array([[1, 2], [-1, -1], [-1, -1]], dtype=np.int32),
+    return G.OBBTree(c, ee, np.array([Q9, I9, I9]), np.array([[1, 2], [-1, -1], [-1, -1]], dtype=np.int32),
                      np.array([G.INTERNAL, 0, 1], dtype=np.int32))
 
 
@@ -102,32 +108,50 @@ def _meshes(pfc, n_elem):
 # small trees starts with; Float64 bb_bb_intersect)
 PATHS = {"dfs32": dict(no_filter=0, bfs_levels=0), "dfs64": dict(no_filter=1, bfs_levels=0),
          "expand": dict(no_filter=0, bfs_levels=1)}
+# ... or the one-launch small-scene kernel (evaluations of <= 256 items), with and without its Float32 filter
+FUSED_PATHS = {"fused": dict(fused_f32=1), "fused_exact": dict(fused_f32=0)}
+EXT = ((np.array([1.0, 2.0, 3.0]), np.array([2.1, 2.2, 2.3])), (np.ones(3), np.ones(3)))
+I3 = np.eye(3)
 
 
-@pytest.mark.parametrize("path", list(PATHS))
-@pytest.mark.parametrize("internal", [False, True])
-def test_sat_touching_through_the_device_broadphase(pfc, path, internal):
-    cases = _cases()
-    ext = ((np.array([1.0, 2.0, 3.0]), np.array([2.1, 2.2, 2.3])), (np.ones(3), np.ones(3)))
+def _root_verdicts(pfc, cases, internal, options, Q=((I3, I3), (I3, I3)), chunk=None):
+    """The device's verdict of every case's root pair under `options`, checked against the oracle's BB_BB_intersect and,
+    for tol >= 1e-9, the constructed truth.  Q[kind] = (Q_a, Q_b): the boxes' rotations in their mesh frames; the pose is
+    R_a_b = Q_a R Q_b', t_a_b = Q_a t, so the world geometry -- and the expected verdict -- is that of the unrotated case.
+    chunk: items per evaluation, each of which must run as the fused kernel (None: one evaluation of all cases).
+    Returns (pairs settled by the exact test in the last evaluation, cases with tol <= 1e-9)."""
     n_elem = 2 if internal else 1
     tri, tet = _meshes(pfc, n_elem)
     S = pfc.scenario
     m = S.MechanismScenario()
-    for k, (ea, eb) in enumerate(ext):
-        i1 = m.add_contact(f"a{k}", tri, tree=_tree(pfc, ea, internal))
-        i2 = m.add_contact(f"b{k}", tet, c_prop=S.ContactProperties(1.0e6), tree=_tree(pfc, eb, internal))
+    for k, (ea, eb) in enumerate(EXT):
+        i1 = m.add_contact(f"a{k}", tri, tree=_tree(pfc, ea, internal, Q[k][0]))
+        i2 = m.add_contact(f"b{k}", tet, c_prop=S.ContactProperties(1.0e6), tree=_tree(pfc, eb, internal, Q[k][1]))
         m.add_friction_regularize(i1, i2, mu_d=0.3)
     m.finalize()
-    for k, v in PATHS[path].items():
+    for k, v in options.items():
         m.set_option(k, v)
     n = len(cases)
     ids = np.array([c[0] for c in cases], dtype=np.int32)
     pose = np.zeros((n, 24))
-    for k, (_, R, t, _, _) in enumerate(cases):
+    Rs, ts = [], []
+    for k, (kind, R, t, _, _) in enumerate(cases):
+        Qa, Qb = Q[kind]
+        R, t = Qa @ R @ Qb.T, Qa @ t
+        Rs.append(R); ts.append(t)
         # the broadphase reads x_r1_r2 = (R_a_b, t_a_b) (src/obb/tree_types.jl:43-50); x_r2_r1 is its inverse
         pose[k, 12:21] = R.reshape(-1, order="F"); pose[k, 21:24] = t
         pose[k, 0:9] = R.T.reshape(-1, order="F"); pose[k, 9:12] = -(R.T @ t)
-    wrench, sdot, counts = m.force_all_elastic_intersections(pose, np.zeros((n, 6)), np.zeros((n, 6)), ids)
+    if chunk is None:
+        wrench, sdot, counts = m.force_all_elastic_intersections(pose, np.zeros((n, 6)), np.zeros((n, 6)), ids)
+    else:
+        parts = []
+        for lo in range(0, n, chunk):
+            sl = slice(lo, min(lo + chunk, n))
+            nn = sl.stop - sl.start
+            parts.append(m.force_all_elastic_intersections(pose[sl], np.zeros((nn, 6)), np.zeros((nn, 6)), ids[sl])[2])
+            assert m.last_parts() == 0, "the fused kernel did not run"
+        counts = np.concatenate(parts)
     if internal:
         assert set(np.unique(counts[:, 0])) <= {1, 5}
         hit = counts[:, 0] == 5
@@ -139,21 +163,59 @@ def test_sat_touching_through_the_device_broadphase(pfc, path, internal):
     L = Orc.lib()
     dp = C.POINTER(C.c_double)
     P = lambda a: np.ascontiguousarray(a, dtype=np.float64).ctypes.data_as(dp)
-    z, I = np.zeros(3), np.eye(3).reshape(-1)
+    z = np.zeros(3)
     n_und_expected = 0
-    for k, (kind, R, t, expect, tol) in enumerate(cases):
-        ea, eb = ext[kind]
-        ref = L.pfo_bb_bb_intersect(P(z), P(ea), P(I), P(z), P(eb), P(I), P(R.reshape(-1, order="F")), P(t))
+    for k, (kind, _, _, expect, tol) in enumerate(cases):
+        ea, eb = EXT[kind]
+        Qa, Qb = Q[kind]
+        ref = L.pfo_bb_bb_intersect(P(z), P(ea), P(Qa.reshape(-1, order="F")), P(z), P(eb), P(Qb.reshape(-1, order="F")),
+                                    P(Rs[k].reshape(-1, order="F")), P(ts[k]))
         assert bool(hit[k]) == bool(ref), (k, kind, tol, expect, counts[k])
         if tol >= 1e-9:       # the reference's own assertion (test_intersection.jl:86-88,98-103), tightened to 1e-9
             assert bool(hit[k]) == bool(expect), (k, kind, tol)
         n_und_expected += tol <= 1e-9
+    out = (C.c_longlong * 16)()
+    assert pfc._lib.lib().pfc_debug_stamps(m._h, out) == 0
+    m.close()
+    return int(out[7]), n_und_expected
+
+
+@pytest.mark.parametrize("path", list(PATHS))
+@pytest.mark.parametrize("internal", [False, True])
+def test_sat_touching_through_the_device_broadphase(pfc, path, internal):
+    n_und, n_und_expected = _root_verdicts(pfc, _cases(), internal, PATHS[path])
     if path == "dfs32":
         # the Float32 filter must have handed the near-touching pairs to the exact test (statistics word [7] of the stamps view)
-        out = (C.c_longlong * 16)()
-        assert pfc._lib.lib().pfc_debug_stamps(m._h, out) == 0
-        assert out[7] >= n_und_expected, (out[7], n_und_expected)
-    m.close()
+        assert n_und >= n_und_expected, (n_und, n_und_expected)
+
+
+@pytest.mark.parametrize("path", list(FUSED_PATHS))
+@pytest.mark.parametrize("internal", [False, True])
+def test_sat_touching_through_the_fused_kernel(pfc, path, internal):
+    """The same cases through k_fused's own broadphase (the kernel small scenes run): evaluations of 256 items, the filter
+    on (settled in the same iteration) and off."""
+    _root_verdicts(pfc, _cases(), internal, FUSED_PATHS[path], chunk=256)
+
+
+# tolerances between the filter's two radii (24 u = 1.4e-6, 320 u = 1.9e-5) join the list
+TOLS_ROTATED = TOLS + (3.0e-6, 1.0e-5)
+
+
+@pytest.mark.parametrize("path", list(PATHS) + list(FUSED_PATHS))
+@pytest.mark.parametrize("internal", [False, True])
+def test_sat_touching_with_rotated_nodes(pfc, path, internal):
+    """The boxes carry rotations Q_a, Q_b in their mesh frames (a host-supplied tree may rotate any node, include/pfc.h)
+    and the pose undoes them: the same world geometry, the same verdicts, on every path.  A rotated internal box is never
+    decided by the Float32 filter: every root pair of the internal trees is settled exactly."""
+    rng = np.random.default_rng(29)
+    Q = tuple((_axis_angle(rng.random() * 2 * np.pi, rng.standard_normal(3)), _axis_angle(rng.random() * 2 * np.pi, rng.standard_normal(3)))
+              for _ in EXT)
+    cases = _cases(TOLS_ROTATED)
+    fused = path in FUSED_PATHS
+    n_und, n_und_expected = _root_verdicts(pfc, cases, internal, FUSED_PATHS[path] if fused else PATHS[path], Q=Q,
+                                           chunk=256 if fused else None)
+    if path == "dfs32":
+        assert n_und >= (len(cases) if internal else n_und_expected), (n_und, n_und_expected)
 
 
 def test_filtered_and_exact_broadphase_agree_on_a_contact_scene(pfc):
