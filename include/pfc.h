@@ -982,6 +982,168 @@ int pfc_selftest_math(pfc_handle h, int n, const double *x, const double *y, dou
  * eigenvalues (6) are taken from it, as with a stored decomposition (option fixed_order, PFC_DUAL_VALUE_K). */
 int pfc_selftest_kis(pfc_handle h, int n, const double *Kbar36, const double *dKbar36, const double *Vlam42, double *out72);
 
+/*
+ * Parts of the Radau IIA step (csrc/pfc_radau.h): the reference's simplified-Newton integrator src/radau/ (updateInvC!, calcEw!,
+ * updateStageX!, simple_newton!; radau_functions.jl:72-125, radau_solve.jl:47-99) for a batch of n_scene independent scenes of NX
+ * states each, every scene with its own step size h and rule.  Rule 1 (one stage, implicit Euler) and rule 2 (three stages, order 5)
+ * only; the reference's rules 3 - 6 are refused.  These are the parts on caller buffers and a caller stream (NULL: the handle's);
+ * asynchronous.  They read nothing of the handle but its device and stream.
+ * Arithmetic: plain Float64, no fma, in the written order below -- tests/test_radau_abi.py restates it in Python floats and
+ * tests/test_gpu_radau.py compares bytes.  A "wave sum" of 64 numbers v[0..64) (entries >= NX are +0.0) is six rounds
+ * v[i] <- v[i] + v[i ^ off], off = 32, 16, 8, 4, 2, 1.  Complex numbers are (re, im) pairs; (a + bi)(c + di) = (ac - bd) + (ad + bc)i,
+ * (a + bi) / (c + di) = ((ac + bd) / (cc + dd)) + ((bc - ad) / (cc + dd))i.
+ */
+#define PFC_MAX_NX_RADAU 64   /* states per scene: one lane per state */
+
+/* The compiled constants of a rule (generated by scripts/radau_tables.py from 50-digit arithmetic): *ns stages; c (ns), A (ns x ns, by
+ * rows); lam (ns complex), T and Tinv (ns x ns complex, by rows) with A^-1 T = T diag(lam), unit-norm columns, lam[0] real and
+ * lam[2] = conj(lam[1]); bhat (1 + ns): bhat0 = 1 / lam[0], then bhat.  Any output may be NULL.  PFC_ERR_BAD_ARG for a rule other
+ * than 1 or 2. */
+int pfc_radau_table(int rule, int *ns, double *c, double *A, double *lam, double *T, double *Tinv, double *bhat);
+
+/* updateInvC! as factorisations instead of explicit inverses.  d_neg_J: n_scene x NX x NX, column-major (-J(i, j) of scene s at
+ * (s NX + j) NX + i); d_h, d_rule: n_scene; d_active: n_scene or NULL -- a scene whose word is not 1 is left alone.  Per scene, with
+ * hinv = 1 / h:  factor 0 = P0 (-J + (hinv lam_1) I), real;  factor 1, rule 2 only, = P1 (-J + (hinv lam_2) I), complex, the diagonal
+ * (-J_kk + hinv Re lam_2, hinv Im lam_2).  The matrix of lam_3 is the conjugate of the second (J is real) and is not factored (the
+ * reference inverts all three).  Right-looking LU, column k = 0 .. NX - 1: the pivot row p is the first row >= k of maximal
+ * |re| + |im| (a NaN counts as +inf); rows k and p are exchanged; l_i = a_ik / a_kk, then a_ij <- a_ij - l_i a_kj, j = k + 1 .. NX - 1.
+ * d_lu0 (n_scene x NX x NX) and d_lu1 (n_scene x NX x NX x 2) receive L (unit diagonal, not stored) and U over each other,
+ * column-major; d_perm (n_scene x 2 x NX): row i of P A is row perm[i] of A; d_info (n_scene x 2): 0, or k + 1 at the first exactly
+ * zero pivot, where the factorisation stops (columns < k final, the rest as reduced so far).  info of the absent factor 1 of a
+ * rule-1 scene is 0; its lu1 and perm rows are not written.  One launch, 2 n_scene one-wave workgroups; each reserves the complex
+ * factor's 16 NX^2 bytes of LDS (the real factor uses 8 NX^2 of them).  PFC_ERR_BAD_ARG: NX outside 1 .. PFC_MAX_NX_RADAU, null buffer. */
+int pfc_radau_factor_device(pfc_handle h, int n_scene, int nx, const double *d_neg_J, const double *d_h, const int *d_rule,
+                            const int *d_active, double *d_lu0, double *d_lu1, int *d_perm, int *d_info, void *stream);
+
+/* One iteration of simple_newton! for every scene whose d_istate word 0 is 1; the other scenes are not touched.
+ * The stage-scene of (stage s, scene) is s n_scene + scene, three stages whatever the rule.  F_s, the state derivative of stage-scene
+ * s, is read in place: [d_qdot (3 n_scene x nq); d_vdot (3 n_scene x nv); rows br_items[0 .. n_br) (host array, increasing, < n_ips) of
+ * d_sdot (3 n_scene n_ips x 6)], NX = nq + nv + 6 n_br.  d_x0: n_scene x NX; d_X: 3 n_scene x NX, the stage states, updated.
+ * d_nstate (n_scene x 8) = {theta, theta of the iteration before, Psi_k, the residuals of the last two iterations (+inf at the start of
+ * an attempt), this iteration's residual, the h of the last committed step, unused}; d_istate (n_scene x 8) = {iterating, k_iter (0 at
+ * the start of an attempt), the attempt's exit flag (-1 while iterating), attempt open (1 from the arming to pfc_radau_finish_device),
+ * attempts of this step, the step's exit flag, k_iter of the last attempt, unused}.  *d_count is set to the number of scenes still
+ * iterating.  Per scene, NS = 1 or 3 stages:
+ *   k_iter += 1; a nonzero info of a factor the rule uses: flag 4, done.
+ *   r_s = ((X_s - x0) + (-h A[s,0]) F_0) + (-h A[s,1]) F_1 ...;  residual = ((0 + sum r_0 r_0) + sum r_1 r_1) + .. (wave sums);
+ *   Ew_0 = ((0 + ((hinv lam_1) Tinv[0,0]) r_0) + ..;  Ew_1 likewise with the complex product (hinv lam_2) Tinv[1,s]       (calcEw!)
+ *   w_0 = factor 0 \ Ew_0, w_1 = factor 1 \ Ew_1: b <- P b; y_k, k ascending: b_i <- b_i - l_ik y_k (i > k); x_k = b_k / u_kk,
+ *   k descending: b_i <- b_i - u_ik x_k (i < k)
+ *   dZ_s = T[s,0] w_0 + 2 (Re T[s,1] Re w_1 - Im T[s,1] Im w_1)   -- the reference adds the three products T[s,j] w_j and takes the
+ *   real part; w_2 = conj(w_1), so this differs by rounding only
+ *   stage by stage: 10 < max |dZ_s| -> flag 3, done (earlier stages stay updated, as in the reference); else X_s <- X_s - dZ_s
+ *   residual < tol_newton -> flag 0, done (declared after the update is applied, as in the reference)
+ *   theta, Psi_k: k_iter == 1: theta = sqrt(residual), Psi_k = theta; else theta' = theta, theta = sqrt(residual), Psi_k = sqrt(theta' theta)
+ *   three residuals rising strictly -> flag 3; else k_iter == k_iter_max -> flag 1
+ * d_F_save (3 n_scene x NX, or NULL) receives F_s of this iteration in d_X's layout: the derivative buffers are overwritten by the
+ * next evaluation, in which a scene that has converged is evaluated at x0, and pfc_radau_finish_device needs F of the last iteration.
+ * Deviations from the reference: a non-finite residual or dZ gives flag 3 at once and updates nothing (the reference iterates on
+ * NaNs to its limit); a singular factor gives flag 4 (the reference's getri! would throw).  Exit flag 2 is never produced, as in
+ * the reference.  PFC_ERR_BAD_ARG: NX, the layout sizes, the item list, tol_newton < 0, k_iter_max < 1, null buffer. */
+int pfc_radau_newton_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items,
+                            const double *d_qdot, const double *d_vdot, const double *d_sdot, const double *d_x0, const double *d_h,
+                            const int *d_rule, const double *d_lu0, const double *d_lu1, const int *d_perm, const int *d_info,
+                            double tol_newton, int k_iter_max, double *d_X, double *d_F_save, double *d_nstate, int *d_istate,
+                            int *d_count, void *stream);
+
+/*
+ * The step itself: solveRadau (radau_solve.jl:2-30) for a batch of n_scene scenes of the handle's mechanism, each with n_ips items
+ * whose instructions are ins_ids[0 .. n_ips) (item i of scene s is global item s n_ips + i; every instruction bound with
+ * pfc_set_instruction_bodies).  The integrator state -- x, t, h, rule, cooldown, the norms -- and the workspace of every call below
+ * live in device memory owned by the handle and are freed with it.  The differential equation is pfc_state_derivative_device on the
+ * 3 n_scene stage-scenes and pfc_state_derivative_dual_device[_more] on the n_scene scenes, called unchanged.
+ * pfc_radau_configure: params = {h0, tol_a, tol_r, tol_newton, h_max, h_min} or NULL for the reference's defaults {1e-4, 1e-4, 1e-4,
+ * 1e-16, 0.01, 1e-8}; the reference's other defaults are k_iter_max 15, max_rule 2 (utility.jl:10), n_chunk 6, cooldown 10.
+ * NX = nq + nv + 6 (items of a scene whose instruction is bristle).  PFC_ERR_STATE before pfc_finalize, pfc_set_mechanism or
+ * pfc_set_inertia; PFC_ERR_BAD_ARG, with a message, for NX > PFC_MAX_NX_RADAU, nv > PFC_MAX_NV_SOLVE, a mechanism beyond the Dual
+ * dynamics' LDS limit, max_rule other than 1 or 2, n_chunk outside 1..16, an unknown instruction.  A second call replaces the first.
+ */
+int pfc_radau_configure(pfc_handle h, int n_scene, int n_ips, const int *ins_ids, const double *params, int k_iter_max, int max_rule,
+                        int n_chunk, int cooldown);
+/* NX, the bristle items per scene and their item indices (bristle_items: room for PFC_MAX_NX_RADAU / 6).  Any may be NULL. */
+int pfc_radau_sizes(pfc_handle h, int *nx, int *n_bristle, int *bristle_items);
+/* x (n_scene x NX, host) and t (n_scene, host; NULL: zeros) in; h, rule, cooldown, theta, Psi_k and the norms are reset to what the
+ * reference's constructors give (h0, rule 1, the cooldown, -9999, 9999, -9999), and every scene is active again. */
+int pfc_radau_set_state(pfc_handle h, const double *x, const double *t);
+int pfc_radau_get_state(pfc_handle h, double *x, double *t);      /* either may be NULL */
+/* After pfc_radau_set_state: a step size, rule (1 .. max_rule) and cooldown (>= 0) per scene (n_scene each, host; NULL: as it is)
+ * in place of the reset values -- a restart from pfc_radau_rule_state's figures, or scenes that start at different h.
+ * PFC_ERR_BAD_ARG, and nothing is changed, for an h that is not finite and > 0, a rule or a cooldown out of range. */
+int pfc_radau_set_rule_state(pfc_handle h, const double *h_scene, const int *rule, const int *cooldown);
+/* tau (n_scene x nv, host; NULL: zeros), held constant over a step; its partials are zero. */
+int pfc_radau_set_tau(pfc_handle h, const double *tau);
+/*
+ * One step of every scene that is not retired; synchronous.  The Jacobian chunks (seed, pfc_state_derivative_dual_device then _more,
+ * each followed by pfc_check and re-issued on PFC_ERR_OVERFLOW, the columns gathered), then per attempt the factors and the loop
+ * unpack -> pfc_state_derivative_device -> pfc_check -> newton, one word read back per pass (the scenes still iterating), then finish;
+ * attempts repeat for the scenes finish armed again.  Converged and retired scenes are still evaluated (the shape is fixed) and
+ * ignored.  Per scene (each may be NULL): h_taken (0 where no step was taken), the exit flag (0, or 5: "time step is too small,
+ * something is wrong" -- x and t are unchanged and the scene stays retired until pfc_radau_set_state), k_iter of the last attempt,
+ * the attempts.  Any other status of an evaluation or its pfc_check (a state that left the scene non-finite, say) is returned as it
+ * is; the integrator state is then undefined until pfc_radau_set_state.  No dense output: every attempt starts from X = x0
+ * (the reference's interpolate.jl is not built).  Multi-device handles use their first device.  Every scene that is not retired is
+ * stepped by every call: a caller that integrates a batch to an end time steps the scenes that have arrived on with the others (they
+ * overshoot), or reads the state after each step; there is no per-scene stop.  n_scene and n_ips are limited at configure time so that
+ * 3 n_scene max(n_ips, n_body) rows of 24 words are indexed in int.
+ */
+int pfc_radau_step(pfc_handle h, double *h_taken, int *flags, int *iters, int *attempts);
+/* Per scene 7 doubles: h, rule, cooldown, theta, Psi_k, x_err_norm, x_err_norm k+1. */
+int pfc_radau_rule_state(pfc_handle h, double *out7);
+
+/* The state layout the other parts share (nx, nq, nv, n_ips, n_br, br_items as above): scene s holds x = [q (nq); v (nv); 6 states per
+ * bristle item], the reference's copyto! (src/extensions.jl:21-51); the items are uniform across scenes, item i of scene s is global
+ * item s n_ips + i.  Chunk k of n_chunk-wide (1..16) chunks covers the states [k n_chunk, min((k + 1) n_chunk, NX)): direction d is
+ * state k n_chunk + d, and the last chunk has fewer directions (n_dir).
+ *
+ * seed_indices! (radau_functions.jl:16-26): every entry of d_dq (n_scene x n_dir x nq), d_dv (n_scene x n_dir x nv) and d_ds
+ * (n_scene n_ips x n_dir x 6) -- pfc_state_derivative_dual_device's seed layouts -- is written: 1.0 where the entry is the state its
+ * direction seeds, +0.0 elsewhere (the s rows of items that are not bristle included). */
+int pfc_radau_seed_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int chunk,
+                          int n_chunk, double *d_dq, double *d_dv, double *d_ds, void *stream);
+
+/* write_indices! (radau_functions.jl:28-40): columns k n_chunk + d of d_neg_J (pfc_radau_factor_device's layout) = -[dqdot; dvdot; the
+ * bristle rows of dsdot] of direction d, from pfc_state_derivative_dual_device[_more]'s outputs d_dqdot (n_scene x n_dir x nq), d_dvdot
+ * (n_scene x n_dir x nv), d_dsdot (n_scene n_ips x n_dir x 6).  Chunk 0 also writes d_xdot0 (n_scene x NX) = [qdot; vdot; sdot] of the
+ * value buffers (the reference's xx_0; they are not read for the later chunks and may be NULL there) and, where d_nstate and d_istate
+ * are given, arms every scene whose step exit flag is not 5 for the first attempt of a step: iterating = 1, k_iter = 0, attempt flag -1,
+ * attempt open, attempts = 1, both remembered residuals +inf. */
+int pfc_radau_jacobian_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int chunk,
+                              int n_chunk, const double *d_dqdot, const double *d_dvdot, const double *d_dsdot, const double *d_qdot,
+                              const double *d_vdot, const double *d_sdot, double *d_neg_J, double *d_xdot0, double *d_nstate,
+                              int *d_istate, void *stream);
+
+/* The stage states into the inputs of pfc_state_derivative_device on the 3 n_scene stage-scenes: d_q (3 n_scene x nq), d_v (.. x nv),
+ * d_s (3 n_scene n_ips x 6; the rows of items that are not bristle are +0.0).  The evaluation shape is 3 n_scene whatever the rules, so
+ * that a captured evaluation graph is reused: the unused stages of a rule-1 scene carry copies of its stage 0 and their derivatives
+ * are ignored (two wasted scene evaluations per iteration of such a scene), and a scene that is not iterating is evaluated at d_x0
+ * and ignored.  A scene at the start of an attempt (k_iter = 0) gets initialize_X_with_X0!: its three rows of d_X become d_x0. */
+int pfc_radau_unpack_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items,
+                            const double *d_x0, const int *d_rule, const int *d_istate, double *d_X, double *d_q, double *d_v, double *d_s,
+                            void *stream);
+
+/* The end of an attempt, for every scene whose attempt is open and which is not iterating any more (solveRadau_inner,
+ * radau_solve.jl:8-30; adaptive.jl).  params = {tol_a, tol_r, h_max, h_min} (host); mrp_off (host): the offsets in q of the n_mrp
+ * floating joints' MRPs.  d_F: pfc_radau_newton_device's d_F_save, the F_k of the attempt's last iteration.  d_x, d_t, d_h, d_rule, d_cool (n_scene .. each): the committed state, time, step size, rule and cooldown,
+ * updated; d_enorm (n_scene x 2): x_err_norm and x_err_norm k+1.  *d_count is set to the number of scenes armed for another attempt.
+ * Attempt flag 0:
+ *   update_x_err_norm!: d = (0 + (bhat0 h) xdot0) + ((bhat_k - A[NS,k]) h) F_k, k ascending (Eq. 8.17); e = factor 0 \ d (Eq. 8.19, the
+ *   reference multiplies by its explicit inverse); sc_i = tol_a + max(|X_NS,i|, |x0_i|) tol_r; err = sqrt((wave sum of (e_i / sc_i)^2) / NX)
+ *   (Eq. 8.21; the reference adds in index order)
+ *   calc_and_update_h!: h_new = min(h_max, 2 h, ((0.9 (2 k_iter_max + 1)) / (2 k_iter_max + k_iter)) h (1 / err)^(1 / (1 + NS))), the
+ *   power as sqrt or sqrt(sqrt) (the reference calls pow: rounding only); err = 0 gives 2 h; a NaN estimate is skipped by the min
+ *   update_rule!: cooldown -= 1; cooldown < 1 and Psi_k < 0.1: rule = min(rule + 1, max_rule)
+ *   x <- X_NS, t <- t + h, h <- h_new; principal_value! on each MRP: sigma <- -(sigma / |sigma|^2) where |sigma|^2 = (s0 s0 + s1 s1) +
+ *   s2 s2 > 1 (RigidBodyDynamics' rule for SPQuatFloating, written as recalled: parity unpinned)
+ * Any other attempt flag: h <- min(h_max, 2 h, 0.1 h), cooldown <- its reset value, rule <- max(rule - 1, 1); if the new h < h_min the
+ * step's exit flag is 5 ("time step is too small, something is wrong": x and t stay, the scene is retired until its records are reset),
+ * else the scene is armed for another attempt with the same Jacobian (its factors must be formed again: h and the rule changed).
+ * PFC_ERR_BAD_ARG: the layout, the offsets, the parameters, max_rule other than 1 or 2, null buffer. */
+int pfc_radau_finish_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int n_mrp,
+                            const int *mrp_off, const double *params, int k_iter_max, int max_rule, int cooldown,
+                            const double *d_F, const double *d_xdot0, const double *d_X,
+                            const double *d_lu0, const int *d_perm, double *d_x, double *d_t, double *d_h, int *d_rule, int *d_cool,
+                            double *d_enorm, double *d_nstate, int *d_istate, int *d_count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,23 @@ SIGNATURES = {
                                            _dp, _dp, _dp, _dp, _dp, _ip, _llp]),
     "pfc_contact_surface_fric_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
                                                   C.c_longlong] + [C.c_void_p] * 12),
+    "pfc_radau_table": (C.c_int, [C.c_int, _ip] + [_dp] * 6),
+    "pfc_radau_factor_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9),
+    "pfc_radau_newton_device": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [_ip] + [C.c_void_p] * 10 + [C.c_double, C.c_int]
+                                + [C.c_void_p] * 6),
+    "pfc_radau_configure": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _dp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "pfc_radau_sizes": (C.c_int, [C.c_void_p, _ip, _ip, _ip]),
+    "pfc_radau_set_state": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "pfc_radau_get_state": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "pfc_radau_set_rule_state": (C.c_int, [C.c_void_p, _dp, _ip, _ip]),
+    "pfc_radau_set_tau": (C.c_int, [C.c_void_p, _dp]),
+    "pfc_radau_step": (C.c_int, [C.c_void_p, _dp, _ip, _ip, _ip]),
+    "pfc_radau_rule_state": (C.c_int, [C.c_void_p, _dp]),
+    "pfc_radau_seed_device": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [_ip, C.c_int, C.c_int] + [C.c_void_p] * 4),
+    "pfc_radau_jacobian_device": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [_ip, C.c_int, C.c_int] + [C.c_void_p] * 11),
+    "pfc_radau_unpack_device": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [_ip] + [C.c_void_p] * 8),
+    "pfc_radau_finish_device": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [_ip, C.c_int, _ip, _dp, C.c_int, C.c_int, C.c_int]
+                                + [C.c_void_p] * 15),
 }
 
 
@@ -127,7 +144,7 @@ class PFCError(RuntimeError):
 
 def build(force: bool = False) -> str:
     """Compile csrc/pfc_hip.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("pfc_hip.hip", "pfc_tree.cpp", "pfc_sort.hip", "pfc_kernels.h", "pfc_bp.h", "pfc_np.h", "pfc_br.h", "pfc_dual.h", "pfc_fused.h", "pfc_clip.h", "pfc_multi.h", "pfc_sort.h", "pfc_surface.h", "pfc_surface_fric.h", "pfc_scatter.h", "pfc_ljac.h", "pfc_bodies.h", "pfc_kin.h", "pfc_dyn.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("pfc_hip.hip", "pfc_tree.cpp", "pfc_sort.hip", "pfc_kernels.h", "pfc_bp.h", "pfc_np.h", "pfc_br.h", "pfc_dual.h", "pfc_fused.h", "pfc_clip.h", "pfc_multi.h", "pfc_sort.h", "pfc_surface.h", "pfc_surface_fric.h", "pfc_scatter.h", "pfc_ljac.h", "pfc_bodies.h", "pfc_kin.h", "pfc_dyn.h", "pfc_radau.h", "pfc_radau_tables.h")]
     srcs.append(os.path.join(os.path.dirname(HERE), "include", "pfc.h"))
     srcs.append(os.path.abspath(__file__))      # the compiler flags live here
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)

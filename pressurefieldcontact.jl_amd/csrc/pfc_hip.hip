@@ -205,6 +205,8 @@ __global__ void k_repose(int n_items, const double *__restrict__ pose, ItemRec *
 #include "pfc_bodies.h"
 #include "pfc_kin.h"
 #include "pfc_dyn.h"
+#include "pfc_radau.h"
+#include "pfc_radau_tables.h"
 
 }  // namespace pfc
 
@@ -625,6 +627,16 @@ struct pfc_context {
     size_t surf_hcap_poly = 0, surf_hcap_trac = 0;    // host-pointer form: its outputs are staged for this many polygons / traction points
     // pfc_contact_surface_fric (pfc_surface_fric.h): per item the moment and friction records of its waves and eig_item's block
     DevBuf<double> sfric_mom, sfric_sum, sfric_res;
+    // the Radau IIA step (pfc_radau.h): integrator state and workspace of pfc_radau_configure, carved out of two blocks
+    struct RadauHost {
+        bool configured = false, has_state = false, has_tau = false;
+        RadauLayout L;
+        int n_chunk = 0, k_iter_max = 0, max_rule = 0, cooldown = 0, n_mrp = 0, mrp_off[kRadMaxBr];
+        double h0 = 0, tol_newton = 0, fin[4];      // fin = {tol_a, tol_r, h_max, h_min}
+        DevBuf<double> dbl;
+        DevBuf<int> itg;
+        std::vector<size_t> od, oi;                 // offsets of the parts (RadauD, RadauI)
+    } radau;
 };
 
 namespace {
@@ -4759,6 +4771,583 @@ int pfc_selftest_kis(pfc_handle h, int n, const double *Kbar36, const double *dK
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     HIP_TRY(h, copy_sync(h, out72, dout.p, sizeof(double) * 72 * (size_t)n, hipMemcpyDeviceToHost));
     return PFC_OK;
+}
+
+// ---- parts of the Radau IIA step (pfc_radau.h; the constants: pfc_radau_tables.h, generated by scripts/radau_tables.py) ----------
+static_assert(PFC_MAX_NX_RADAU == kRadWave, "k_radau_factor and k_radau_newton run one lane per state");
+
+int pfc_radau_table(int rule, int *ns, double *c, double *A, double *lam, double *T, double *Tinv, double *bhat) {
+    if (rule < 1 || rule > 2) return PFC_ERR_BAD_ARG;
+    const RadauTableHost &t = kRadauTables[rule - 1];
+    const int s = t.ns;
+    if (ns) *ns = s;
+    if (c) std::memcpy(c, t.c, sizeof(double) * s);
+    if (A) std::memcpy(A, t.A, sizeof(double) * s * s);
+    if (lam) std::memcpy(lam, t.lam, sizeof(double) * 2 * s);
+    if (T) std::memcpy(T, t.T, sizeof(double) * 2 * s * s);
+    if (Tinv) std::memcpy(Tinv, t.Tinv, sizeof(double) * 2 * s * s);
+    if (bhat) { bhat[0] = t.bhat0; std::memcpy(bhat + 1, t.bhat, sizeof(double) * s); }
+    return PFC_OK;
+}
+
+// What the kernels read of a rule's table: columns 0 and 1 of T, rows 0 and 1 of T^-1 (the third of each is a conjugate).
+static RadauTab radau_tab(int rule) {
+    const RadauTableHost &t = kRadauTables[rule - 1];
+    const int s = t.ns;
+    RadauTab r;
+    std::memset(&r, 0, sizeof r);
+    for (int e = 0; e < s * s; ++e) r.A[e] = t.A[e];
+    r.lam0 = t.lam[0];
+    if (s > 1) { r.lam1_re = t.lam[2]; r.lam1_im = t.lam[3]; }
+    for (int k = 0; k < s; ++k) {
+        r.T0[k] = t.T[2 * (k * s)];
+        r.Ti0[k] = t.Tinv[2 * k];
+        if (s > 1) {
+            r.T1_re[k] = t.T[2 * (k * s + 1)]; r.T1_im[k] = t.T[2 * (k * s + 1) + 1];
+            r.Ti1_re[k] = t.Tinv[2 * (s + k)]; r.Ti1_im[k] = t.Tinv[2 * (s + k) + 1];
+        }
+    }
+    return r;
+}
+
+static int radau_check_nx(pfc_context *h, const char *who, int n_scene, int nx) {
+    if (n_scene < 0) return fail(h, PFC_ERR_BAD_ARG, "%s: negative n_scene", who);
+    if (nx < 1 || nx > PFC_MAX_NX_RADAU)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: NX is %d, the step takes 1 .. PFC_MAX_NX_RADAU = %d states per scene", who, nx, PFC_MAX_NX_RADAU);
+    return PFC_OK;
+}
+
+static int radau_factor_launch(pfc_context *h, int n_scene, int nx, const double *d_neg_J, const double *d_h, const int *d_rule,
+                               const int *d_active, int active_stride, double *d_lu0, double *d_lu1, int *d_perm, int *d_info,
+                               hipStream_t st);
+
+// The state layout every part but the factorisation takes, validated: NX = nq + nv + 6 n_br, the bristle items increasing and < n_ips.
+static int radau_layout(pfc_context *h, const char *who, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items,
+                        RadauLayout *L) {
+    const int rc = radau_check_nx(h, who, n_scene, nx);
+    if (rc != PFC_OK) return rc;
+    if (nq < 0 || nv < 0 || n_ips < 0 || n_br < 0 || n_br > kRadMaxBr || (long long)nq + nv + 6ll * n_br != nx)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: NX = %d is not nq + nv + 6 bristle items (nq = %d, nv = %d, %d items)", who, nx, nq, nv, n_br);
+    if (n_br > 0 && !br_items) return fail(h, PFC_ERR_BAD_ARG, "%s: null bristle item list", who);
+    for (int k = 0; k < n_br; ++k)
+        if (br_items[k] < 0 || br_items[k] >= n_ips || (k > 0 && br_items[k] <= br_items[k - 1]))
+            return fail(h, PFC_ERR_BAD_ARG, "%s: bristle item %d is %d: the items are increasing and below n_ips = %d", who, k, br_items[k], n_ips);
+    if (n_ips > (1 << 24)) return fail(h, PFC_ERR_BAD_ARG, "%s: n_ips is %d, at most 2^24 items per scene", who, n_ips);
+    L->n_scene = n_scene; L->nx = nx; L->nq = nq; L->nv = nv; L->n_ips = n_ips; L->n_br = n_br;
+    for (int k = 0; k < kRadMaxBr; ++k) L->br_items[k] = k < n_br ? br_items[k] : 0;
+    return PFC_OK;
+}
+
+static unsigned radau_grid(size_t total) { return (unsigned)std::min<size_t>((total + kRadBlock - 1) / kRadBlock, 4096); }
+
+// The chunk's first state and its directions: chunk k of n_chunk-wide chunks covers states [k n_chunk, min((k + 1) n_chunk, NX)).
+static int radau_chunk(pfc_context *h, const char *who, int nx, int chunk, int n_chunk, int *j0, int *n_dir) {
+    if (n_chunk < 1 || n_chunk > 16) return fail(h, PFC_ERR_BAD_ARG, "%s: n_chunk is %d, 1 .. 16 directions per chunk", who, n_chunk);
+    if (chunk < 0 || (long long)chunk * n_chunk >= nx)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: chunk %d of %d-wide chunks starts beyond NX = %d", who, chunk, n_chunk, nx);
+    *j0 = chunk * n_chunk;
+    *n_dir = std::min(n_chunk, nx - *j0);
+    return PFC_OK;
+}
+
+int pfc_radau_seed_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int chunk,
+                          int n_chunk, double *d_dq, double *d_dv, double *d_ds, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_radau_seed_device(c, n_scene, nx, nq, nv, n_ips, n_br, br_items, chunk, n_chunk, d_dq, d_dv, d_ds, stream); });
+    const char *who = "pfc_radau_seed_device";
+    RadauSeedArgs a;
+    int rc = radau_layout(h, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &a.L);
+    if (rc != PFC_OK || (rc = radau_chunk(h, who, nx, chunk, n_chunk, &a.j0, &a.n_dir)) != PFC_OK || n_scene == 0) return rc;
+    if ((nq > 0 && !d_dq) || (nv > 0 && !d_dv) || (n_ips > 0 && !d_ds)) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    a.dq = d_dq; a.dv = d_dv; a.ds = d_ds;
+    const size_t total = (size_t)n_scene * a.n_dir * (size_t)(nq + nv + 6 * n_ips);
+    hipLaunchKernelGGL(k_radau_seed, dim3(radau_grid(total)), dim3(kRadBlock), 0, stream ? (hipStream_t)stream : h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+int pfc_radau_jacobian_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int chunk,
+                              int n_chunk, const double *d_dqdot, const double *d_dvdot, const double *d_dsdot, const double *d_qdot,
+                              const double *d_vdot, const double *d_sdot, double *d_neg_J, double *d_xdot0, double *d_nstate,
+                              int *d_istate, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_radau_jacobian_device(c, n_scene, nx, nq, nv, n_ips, n_br, br_items, chunk, n_chunk, d_dqdot, d_dvdot, d_dsdot, d_qdot,
+                                             d_vdot, d_sdot, d_neg_J, d_xdot0, d_nstate, d_istate, stream); });
+    const char *who = "pfc_radau_jacobian_device";
+    RadauJacArgs a;
+    int rc = radau_layout(h, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &a.L);
+    if (rc != PFC_OK || (rc = radau_chunk(h, who, nx, chunk, n_chunk, &a.j0, &a.n_dir)) != PFC_OK || n_scene == 0) return rc;
+    a.first = chunk == 0;
+    if ((nq > 0 && !d_dqdot) || (nv > 0 && !d_dvdot) || (n_br > 0 && !d_dsdot) || !d_neg_J ||
+        (a.first && ((nq > 0 && !d_qdot) || (nv > 0 && !d_vdot) || (n_br > 0 && !d_sdot) || !d_xdot0)))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    a.dqdot = d_dqdot; a.dvdot = d_dvdot; a.dsdot = d_dsdot; a.qdot = d_qdot; a.vdot = d_vdot; a.sdot = d_sdot;
+    a.neg_J = d_neg_J; a.xdot0 = d_xdot0; a.nstate = d_nstate; a.istate = d_istate;
+    const size_t total = (size_t)n_scene * (size_t)(a.n_dir + a.first) * (size_t)nx;
+    hipLaunchKernelGGL(k_radau_jac, dim3(radau_grid(total)), dim3(kRadBlock), 0, stream ? (hipStream_t)stream : h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+int pfc_radau_unpack_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items,
+                            const double *d_x0, const int *d_rule, const int *d_istate, double *d_X, double *d_q, double *d_v, double *d_s,
+                            void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_radau_unpack_device(c, n_scene, nx, nq, nv, n_ips, n_br, br_items, d_x0, d_rule, d_istate, d_X, d_q, d_v, d_s, stream); });
+    const char *who = "pfc_radau_unpack_device";
+    RadauUnpackArgs a;
+    const int rc = radau_layout(h, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &a.L);
+    if (rc != PFC_OK || n_scene == 0) return rc;
+    if (!d_x0 || !d_rule || !d_istate || !d_X || (nq > 0 && !d_q) || (nv > 0 && !d_v) || (n_ips > 0 && !d_s))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    a.x0 = d_x0; a.rule = d_rule; a.istate = d_istate; a.X = d_X; a.q = d_q; a.v = d_v; a.s = d_s;
+    const size_t total = 3 * (size_t)n_scene * (size_t)(nq + nv + 6 * n_ips);
+    hipLaunchKernelGGL(k_radau_unpack, dim3(radau_grid(total)), dim3(kRadBlock), 0, stream ? (hipStream_t)stream : h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+int pfc_radau_finish_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int n_mrp,
+                            const int *mrp_off, const double *params, int k_iter_max, int max_rule, int cooldown,
+                            const double *d_F, const double *d_xdot0, const double *d_X,
+                            const double *d_lu0, const int *d_perm, double *d_x, double *d_t, double *d_h, int *d_rule, int *d_cool,
+                            double *d_enorm, double *d_nstate, int *d_istate, int *d_count, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_radau_finish_device(c, n_scene, nx, nq, nv, n_ips, n_br, br_items, n_mrp, mrp_off, params, k_iter_max, max_rule,
+                                           cooldown, d_F, d_xdot0, d_X, d_lu0, d_perm, d_x, d_t, d_h, d_rule, d_cool,
+                                           d_enorm, d_nstate, d_istate, d_count, stream); });
+    const char *who = "pfc_radau_finish_device";
+    RadauFinishArgs a;
+    const int rc = radau_layout(h, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &a.L);
+    if (rc != PFC_OK) return rc;
+    if (n_mrp < 0 || n_mrp > kRadMaxBr || (n_mrp > 0 && !mrp_off)) return fail(h, PFC_ERR_BAD_ARG, "%s: the list of MRP offsets", who);
+    for (int m = 0; m < n_mrp; ++m)
+        if (mrp_off[m] < 0 || mrp_off[m] + 3 > nq || (m > 0 && mrp_off[m] < mrp_off[m - 1] + 3))
+            return fail(h, PFC_ERR_BAD_ARG, "%s: MRP %d at q offset %d: increasing, disjoint and within nq = %d", who, m, mrp_off[m], nq);
+    if (!params || !(params[0] >= 0.0) || !(params[1] >= 0.0) || !(params[2] > 0.0) || !(params[3] > 0.0))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: params are {tol_a >= 0, tol_r >= 0, h_max > 0, h_min > 0}", who);
+    if (k_iter_max < 1 || max_rule < 1 || max_rule > 2 || cooldown < 0)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: k_iter_max >= 1, max_rule 1 or 2 (rules 3 - 6 are not built), cooldown >= 0", who);
+    if (n_scene == 0) return PFC_OK;
+    if (!d_F || !d_xdot0 || !d_X || !d_lu0 || !d_perm || !d_x || !d_t || !d_h ||
+        !d_rule || !d_cool || !d_enorm || !d_nstate || !d_istate || !d_count)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    a.k_iter_max = k_iter_max; a.max_rule = max_rule; a.cooldown_reset = cooldown; a.n_mrp = n_mrp;
+    for (int m = 0; m < kRadMaxBr; ++m) a.mrp_off[m] = m < n_mrp ? mrp_off[m] : 0;
+    a.tol_a = params[0]; a.tol_r = params[1]; a.h_max = params[2]; a.h_min = params[3];
+    for (int r = 0; r < 2; ++r) {
+        const RadauTableHost &t = kRadauTables[r];
+        a.bhat0[r] = t.bhat0;
+        for (int k = 0; k < 3; ++k) { a.bhat[r][k] = t.bhat[k]; a.a_last[r][k] = k < t.ns ? t.A[(t.ns - 1) * t.ns + k] : 0.0; }
+    }
+    a.F = d_F; a.xdot0 = d_xdot0; a.X = d_X; a.lu0 = d_lu0; a.perm = d_perm;
+    a.x = d_x; a.t = d_t; a.h = d_h; a.rule = d_rule; a.cool = d_cool; a.enorm = d_enorm; a.nstate = d_nstate; a.istate = d_istate;
+    a.count = d_count;
+    HIP_TRY(h, hipMemsetAsync(d_count, 0, sizeof(int), st));
+    hipLaunchKernelGGL(k_radau_finish, dim3((unsigned)n_scene), dim3(kRadWave), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+int pfc_radau_factor_device(pfc_handle h, int n_scene, int nx, const double *d_neg_J, const double *d_h, const int *d_rule,
+                            const int *d_active, double *d_lu0, double *d_lu1, int *d_perm, int *d_info, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_radau_factor_device(c, n_scene, nx, d_neg_J, d_h, d_rule, d_active, d_lu0, d_lu1, d_perm, d_info, stream); });
+    const char *who = "pfc_radau_factor_device";
+    const int rc = radau_check_nx(h, who, n_scene, nx);
+    if (rc != PFC_OK || n_scene == 0) return rc;
+    if (!d_neg_J || !d_h || !d_rule || !d_lu0 || !d_lu1 || !d_perm || !d_info) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    return radau_factor_launch(h, n_scene, nx, d_neg_J, d_h, d_rule, d_active, 1, d_lu0, d_lu1, d_perm, d_info,
+                               stream ? (hipStream_t)stream : h->stream);
+}
+
+static int radau_factor_launch(pfc_context *h, int n_scene, int nx, const double *d_neg_J, const double *d_h, const int *d_rule,
+                               const int *d_active, int active_stride, double *d_lu0, double *d_lu1, int *d_perm, int *d_info,
+                               hipStream_t st) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    RadauFactorArgs a;
+    a.n_scene = n_scene; a.nx = nx; a.neg_J = d_neg_J; a.h = d_h; a.rule = d_rule; a.active = d_active; a.active_stride = active_stride;
+    a.lam0[0] = kRadauTables[0].lam[0]; a.lam0[1] = kRadauTables[1].lam[0];
+    a.lam1_re = kRadauTables[1].lam[2]; a.lam1_im = kRadauTables[1].lam[3];
+    a.lu0 = d_lu0; a.lu1 = d_lu1; a.perm = d_perm; a.info = d_info;
+    // one size for both factors: see k_radau_factor
+    hipLaunchKernelGGL(k_radau_factor, dim3(2u * (unsigned)n_scene), dim3(kRadWave), sizeof(RadC) * (size_t)nx * (size_t)nx, st, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+int pfc_radau_newton_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items,
+                            const double *d_qdot, const double *d_vdot, const double *d_sdot, const double *d_x0, const double *d_h,
+                            const int *d_rule, const double *d_lu0, const double *d_lu1, const int *d_perm, const int *d_info,
+                            double tol_newton, int k_iter_max, double *d_X, double *d_F_save, double *d_nstate, int *d_istate, int *d_count,
+                            void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    if (h->multi)
+        return on_first_shard(h, [&](pfc_context *c) {
+            return pfc_radau_newton_device(c, n_scene, nx, nq, nv, n_ips, n_br, br_items, d_qdot, d_vdot, d_sdot, d_x0, d_h, d_rule, d_lu0,
+                                           d_lu1, d_perm, d_info, tol_newton, k_iter_max, d_X, d_F_save, d_nstate, d_istate, d_count, stream); });
+    const char *who = "pfc_radau_newton_device";
+    RadauNewtonArgs a;
+    const int rc = radau_layout(h, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &a.L);
+    if (rc != PFC_OK) return rc;
+    if (!(tol_newton >= 0.0) || k_iter_max < 1) return fail(h, PFC_ERR_BAD_ARG, "%s: tol_newton or k_iter_max", who);
+    if (n_scene == 0) return PFC_OK;
+    if ((nq > 0 && !d_qdot) || (nv > 0 && !d_vdot) || (n_br > 0 && !d_sdot) || !d_x0 || !d_h || !d_rule || !d_lu0 || !d_lu1 || !d_perm ||
+        !d_info || !d_X || !d_nstate || !d_istate || !d_count)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    a.k_iter_max = k_iter_max;
+    a.tol_newton = tol_newton;
+    a.qdot = d_qdot; a.vdot = d_vdot; a.sdot = d_sdot; a.x0 = d_x0; a.h = d_h; a.rule = d_rule;
+    a.lu0 = d_lu0; a.lu1 = d_lu1; a.perm = d_perm; a.info = d_info;
+    a.tab[0] = radau_tab(1); a.tab[1] = radau_tab(2);
+    a.X = d_X; a.F_save = d_F_save; a.nstate = d_nstate; a.istate = d_istate; a.count = d_count;
+    HIP_TRY(h, hipMemsetAsync(d_count, 0, sizeof(int), st));
+    hipLaunchKernelGGL(k_radau_newton, dim3((unsigned)n_scene), dim3(kRadWave), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+// ---- the Radau IIA step: configuration, state and the driver (solveRadau, src/radau/radau_solve.jl:2-30) -----------------------
+// Parts of the handle's two blocks.  The value buffers (RD_V*, RI_V*) are those of pfc_state_derivative_device on the 3 n_scene
+// stage-scenes; the Jacobian chunks run on the first n_scene of them -- before the first attempt every stage-scene holds x0 -- and
+// write their value outputs there as well, so only the partials (RD_DD*) have buffers of their own.
+enum RadauD { RD_X, RD_T, RD_H, RD_ENORM, RD_NSTATE, RD_XS, RD_FS, RD_XDOT0, RD_NEGJ, RD_LU0, RD_LU1, RD_TAU,
+              RD_VQ, RD_VV, RD_VS, RD_VXWB, RD_VTW, RD_VJAC, RD_VPOSE, RD_VTWI, RD_VXR2, RD_VWR, RD_VSD, RD_VF, RD_VQD, RD_VH, RD_VC, RD_VVD,
+              RD_DDQ, RD_DDV, RD_DDS, RD_DDXWB, RD_DDTW, RD_DDJAC, RD_DDPOSE, RD_DDTWI, RD_DDXR2, RD_DDWR, RD_DDSD, RD_DDF, RD_DDQD, RD_DDH,
+              RD_DDC, RD_DDVD, RD_N };
+enum RadauI { RI_RULE, RI_COOL, RI_ISTATE, RI_PERM, RI_INFO, RI_COUNT, RI_VINS, RI_VSC, RI_VB1, RI_VB2, RI_VCNT, RI_VINFO, RI_N };
+
+static int radau_configure_ctx(pfc_context *c, int n_scene, int n_ips, const int *ins_ids, const double *params, int k_iter_max,
+                               int max_rule, int n_chunk, int cooldown) {
+    const char *who = "pfc_radau_configure";
+    pfc_context::RadauHost &R = c->radau;
+    if (!c->finalized) return fail(c, PFC_ERR_STATE, "%s before pfc_finalize", who);
+    if (n_chunk < 1 || n_chunk > 16) return fail(c, PFC_ERR_BAD_ARG, "%s: n_chunk is %d, 1 .. 16 directions per chunk", who, n_chunk);
+    if (n_scene < 1 || n_scene > (1 << 20)) return fail(c, PFC_ERR_BAD_ARG, "%s: n_scene is %d", who, n_scene);
+    int rc = state_derivative_dual_check(c, who, n_scene, n_chunk);      // the mechanism, its inertias, the nv cap, the Dual LDS limit
+    if (rc != PFC_OK) return rc;
+    if (max_rule < 1 || max_rule > 2) return fail(c, PFC_ERR_BAD_ARG, "%s: max_rule is %d: rules 1 and 2 only (3 - 6 are not built)", who, max_rule);
+    if (n_ips < 1 || n_ips > 4096 || !ins_ids) return fail(c, PFC_ERR_BAD_ARG, "%s: 1 .. 4096 items per scene and their instruction ids", who);
+    static const double defaults[6] = {1e-4, 1e-4, 1e-4, 1e-16, 0.01, 1e-8};      // h0, tol_a, tol_r, tol_newton, h_max, h_min
+    const double *p = params ? params : defaults;
+    if (!(p[0] > 0.0) || !(p[1] >= 0.0) || !(p[2] >= 0.0) || !(p[3] >= 0.0) || !(p[4] > 0.0) || !(p[5] > 0.0) || !std::isfinite(p[0]) ||
+        k_iter_max < 1 || cooldown < 0)
+        return fail(c, PFC_ERR_BAD_ARG, "%s: h0, h_max, h_min > 0, the tolerances >= 0, k_iter_max >= 1, cooldown >= 0", who);
+    const KinHost &K = c->kin;
+    // the step counts items, bodies and their rows in int: 3 n_scene n_ips items and 3 n_scene n_body bodies, 24 words a row at most
+    if (3ll * n_scene * (long long)std::max(n_ips, K.n_body) > (long long)std::numeric_limits<int>::max() / 24)
+        return fail(c, PFC_ERR_BAD_ARG, "%s: 3 n_scene x max(n_ips, n_body) = 3 x %d x %d is beyond what the step indexes (INT_MAX / 24)", who,
+                    n_scene, std::max(n_ips, K.n_body));
+    std::vector<int> br;
+    for (int k = 0; k < n_ips; ++k) {
+        if (ins_ids[k] < 0 || ins_ids[k] >= (int)c->ins.size())
+            return fail(c, PFC_ERR_BAD_ARG, "%s: item %d uses instruction %d, the scenario has %d", who, k, ins_ids[k], (int)c->ins.size());
+        if (c->ins[ins_ids[k]].model == PFC_BRISTLE) br.push_back(k);
+    }
+    const long long nx = (long long)K.nq + K.nv + 6ll * (long long)br.size();
+    if (nx < 1 || nx > PFC_MAX_NX_RADAU)
+        return fail(c, PFC_ERR_BAD_ARG, "%s: NX = nq + nv + 6 bristle items = %d + %d + 6 x %d = %lld, at most PFC_MAX_NX_RADAU = %d", who, K.nq,
+                    K.nv, (int)br.size(), nx, PFC_MAX_NX_RADAU);
+    RadauLayout L;
+    rc = radau_layout(c, who, n_scene, (int)nx, K.nq, K.nv, n_ips, (int)br.size(), br.data(), &L);
+    if (rc != PFC_OK) return rc;
+    R.configured = false; R.has_state = false; R.has_tau = false;
+    R.L = L; R.n_chunk = n_chunk; R.k_iter_max = k_iter_max; R.max_rule = max_rule; R.cooldown = cooldown;
+    R.h0 = p[0]; R.tol_newton = p[3]; R.fin[0] = p[1]; R.fin[1] = p[2]; R.fin[2] = p[4]; R.fin[3] = p[5];
+    R.n_mrp = 0;
+    const int *jtype = (const int *)(K.blob.data() + K.o_jtype), *qoff = (const int *)(K.blob.data() + K.o_qoff);
+    for (int b = 0; b < K.n_body; ++b)
+        if (jtype[b] == PFC_JOINT_FLOATING_MRP && R.n_mrp < kRadMaxBr) R.mrp_off[R.n_mrp++] = qoff[b];
+    const size_t ns = (size_t)n_scene, N3 = 3 * ns, n3 = N3 * (size_t)n_ips, n1 = ns * (size_t)n_ips, nd = (size_t)n_chunk, nb = (size_t)K.n_body;
+    const size_t n = (size_t)nx, nq = (size_t)K.nq, nv = (size_t)K.nv;
+    size_t sd[RD_N], si[RI_N];
+    sd[RD_X] = ns * n; sd[RD_T] = ns; sd[RD_H] = ns; sd[RD_ENORM] = 2 * ns; sd[RD_NSTATE] = 8 * ns; sd[RD_XS] = N3 * n; sd[RD_FS] = N3 * n; sd[RD_XDOT0] = ns * n;
+    sd[RD_NEGJ] = ns * n * n; sd[RD_LU0] = ns * n * n; sd[RD_LU1] = 2 * ns * n * n; sd[RD_TAU] = N3 * nv;
+    sd[RD_VQ] = N3 * nq; sd[RD_VV] = N3 * nv; sd[RD_VS] = n3 * 6; sd[RD_VXWB] = N3 * nb * 12; sd[RD_VTW] = N3 * nb * 6; sd[RD_VJAC] = N3 * nb * nv * 6;
+    sd[RD_VPOSE] = n3 * 24; sd[RD_VTWI] = n3 * 6; sd[RD_VXR2] = n3 * 12; sd[RD_VWR] = n3 * 6; sd[RD_VSD] = n3 * 6; sd[RD_VF] = N3 * nv;
+    sd[RD_VQD] = N3 * nq; sd[RD_VH] = N3 * nv * nv; sd[RD_VC] = N3 * nv; sd[RD_VVD] = N3 * nv;
+    sd[RD_DDQ] = ns * nd * nq; sd[RD_DDV] = ns * nd * nv; sd[RD_DDS] = n1 * nd * 6; sd[RD_DDXWB] = ns * nb * nd * 12; sd[RD_DDTW] = ns * nb * nd * 6;
+    sd[RD_DDJAC] = ns * nb * nd * nv * 6; sd[RD_DDPOSE] = n1 * nd * 24; sd[RD_DDTWI] = n1 * nd * 6; sd[RD_DDXR2] = n1 * nd * 12;
+    sd[RD_DDWR] = n1 * nd * 6; sd[RD_DDSD] = n1 * nd * 6; sd[RD_DDF] = ns * nd * nv; sd[RD_DDQD] = ns * nd * nq; sd[RD_DDH] = ns * nd * nv * nv;
+    sd[RD_DDC] = ns * nd * nv; sd[RD_DDVD] = ns * nd * nv;
+    si[RI_RULE] = ns; si[RI_COOL] = ns; si[RI_ISTATE] = 8 * ns; si[RI_PERM] = 2 * ns * n; si[RI_INFO] = 2 * ns; si[RI_COUNT] = 2;
+    si[RI_VINS] = n3; si[RI_VSC] = n3; si[RI_VB1] = n3; si[RI_VB2] = n3; si[RI_VCNT] = 4 * n3; si[RI_VINFO] = N3;
+    R.od.assign(RD_N, 0); R.oi.assign(RI_N, 0);
+    size_t td = 0, ti = 0;
+    for (int k = 0; k < RD_N; ++k) { R.od[k] = td; td += (std::max<size_t>(sd[k], 1) + 31) & ~(size_t)31; }
+    for (int k = 0; k < RI_N; ++k) { R.oi[k] = ti; ti += (std::max<size_t>(si[k], 1) + 63) & ~(size_t)63; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, R.dbl.ensure(td));
+    HIP_TRY(c, R.itg.ensure(ti));
+    HIP_TRY(c, hipMemset(R.dbl.p, 0, sizeof(double) * td));
+    HIP_TRY(c, hipMemset(R.itg.p, 0, sizeof(int) * ti));
+    std::vector<int> tab(2 * n3);
+    for (size_t ss = 0; ss < N3; ++ss)
+        for (int k = 0; k < n_ips; ++k) { tab[ss * n_ips + k] = ins_ids[k]; tab[n3 + ss * n_ips + k] = (int)ss; }
+    HIP_TRY(c, hipMemcpy(R.itg.p + R.oi[RI_VINS], tab.data(), sizeof(int) * n3, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(R.itg.p + R.oi[RI_VSC], tab.data() + n3, sizeof(int) * n3, hipMemcpyHostToDevice));
+    R.configured = true;
+    return PFC_OK;
+}
+
+// The context the step runs on: the handle, or the first shard of a multi-device handle.
+static pfc_context *radau_ctx(pfc_context *h) { return h->multi ? h->multi->shard[0] : h; }
+
+int pfc_radau_configure(pfc_handle h, int n_scene, int n_ips, const int *ins_ids, const double *params, int k_iter_max, int max_rule,
+                        int n_chunk, int cooldown) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+        return radau_configure_ctx(c, n_scene, n_ips, ins_ids, params, k_iter_max, max_rule, n_chunk, cooldown); });
+}
+
+static int radau_need(pfc_context *c, const char *who, bool state) {
+    if (!c->radau.configured) return fail(c, PFC_ERR_STATE, "%s before pfc_radau_configure", who);
+    if (state && !c->radau.has_state) return fail(c, PFC_ERR_STATE, "%s before pfc_radau_set_state", who);
+    return PFC_OK;
+}
+
+int pfc_radau_sizes(pfc_handle h, int *nx, int *n_bristle, int *bristle_items) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+        const int rc = radau_need(c, "pfc_radau_sizes", false);
+        if (rc != PFC_OK) return rc;
+        const RadauLayout &L = c->radau.L;
+        if (nx) *nx = L.nx;
+        if (n_bristle) *n_bristle = L.n_br;
+        if (bristle_items) for (int k = 0; k < L.n_br; ++k) bristle_items[k] = L.br_items[k];
+        return (int)PFC_OK; });
+}
+
+int pfc_radau_set_state(pfc_handle h, const double *x, const double *t) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+        const char *who = "pfc_radau_set_state";
+        int rc = radau_need(c, who, false);
+        if (rc != PFC_OK) return rc;
+        if (!x) return fail(c, PFC_ERR_BAD_ARG, "%s: null state", who);
+        pfc_context::RadauHost &R = c->radau;
+        const size_t ns = (size_t)R.L.n_scene, n = (size_t)R.L.nx;
+        for (size_t e = 0; e < ns * n; ++e)
+            if (!std::isfinite(x[e])) return fail(c, PFC_ERR_NONFINITE, "%s: x of scene %zu is not finite", who, e / n);
+        const double inf = std::numeric_limits<double>::infinity();
+        std::vector<double> hh(ns, R.h0), tt(ns, 0.0), en(2 * ns, -9999.0), nst(8 * ns, 0.0);
+        std::vector<int> rule(ns, 1), cool(ns, R.cooldown), ist(8 * ns, 0);
+        for (size_t s = 0; s < ns; ++s) {
+            if (t) tt[s] = t[s];
+            double *a = nst.data() + 8 * s;
+            a[kRadTheta] = -9999.0; a[kRadThetaPrev] = -9999.0; a[kRadPsi] = 9999.0; a[kRadRes1] = inf; a[kRadRes2] = inf;
+            ist[8 * s + kRadFlag] = -1; ist[8 * s + kRadExit] = -9999;
+        }
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        double *D = R.dbl.p; int *I = R.itg.p;
+        HIP_TRY(c, hipMemcpy(D + R.od[RD_X], x, sizeof(double) * ns * n, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(D + R.od[RD_T], tt.data(), sizeof(double) * ns, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(D + R.od[RD_H], hh.data(), sizeof(double) * ns, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(D + R.od[RD_ENORM], en.data(), sizeof(double) * 2 * ns, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(D + R.od[RD_NSTATE], nst.data(), sizeof(double) * 8 * ns, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(I + R.oi[RI_RULE], rule.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(I + R.oi[RI_COOL], cool.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(I + R.oi[RI_ISTATE], ist.data(), sizeof(int) * 8 * ns, hipMemcpyHostToDevice));
+        R.has_state = true;
+        return (int)PFC_OK; });
+}
+
+int pfc_radau_set_rule_state(pfc_handle h, const double *h_scene, const int *rule, const int *cooldown) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+        const char *who = "pfc_radau_set_rule_state";
+        const int rc = radau_need(c, who, true);
+        if (rc != PFC_OK) return rc;
+        pfc_context::RadauHost &R = c->radau;
+        const size_t ns = (size_t)R.L.n_scene;
+        for (size_t s = 0; s < ns; ++s) {
+            if (h_scene && !(h_scene[s] > 0.0 && std::isfinite(h_scene[s]))) return fail(c, PFC_ERR_BAD_ARG, "%s: h of scene %zu is %.17g", who, s, h_scene[s]);
+            if (rule && (rule[s] < 1 || rule[s] > R.max_rule)) return fail(c, PFC_ERR_BAD_ARG, "%s: rule of scene %zu is %d, 1 .. max_rule = %d", who, s, rule[s], R.max_rule);
+            if (cooldown && cooldown[s] < 0) return fail(c, PFC_ERR_BAD_ARG, "%s: cooldown of scene %zu is %d", who, s, cooldown[s]);
+        }
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (h_scene) HIP_TRY(c, hipMemcpy(R.dbl.p + R.od[RD_H], h_scene, sizeof(double) * ns, hipMemcpyHostToDevice));
+        if (rule) HIP_TRY(c, hipMemcpy(R.itg.p + R.oi[RI_RULE], rule, sizeof(int) * ns, hipMemcpyHostToDevice));
+        if (cooldown) HIP_TRY(c, hipMemcpy(R.itg.p + R.oi[RI_COOL], cooldown, sizeof(int) * ns, hipMemcpyHostToDevice));
+        return (int)PFC_OK; });
+}
+
+int pfc_radau_get_state(pfc_handle h, double *x, double *t) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+        const int rc = radau_need(c, "pfc_radau_get_state", true);
+        if (rc != PFC_OK) return rc;
+        pfc_context::RadauHost &R = c->radau;
+        const size_t ns = (size_t)R.L.n_scene, n = (size_t)R.L.nx;
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (x) HIP_TRY(c, hipMemcpy(x, R.dbl.p + R.od[RD_X], sizeof(double) * ns * n, hipMemcpyDeviceToHost));
+        if (t) HIP_TRY(c, hipMemcpy(t, R.dbl.p + R.od[RD_T], sizeof(double) * ns, hipMemcpyDeviceToHost));
+        return (int)PFC_OK; });
+}
+
+int pfc_radau_set_tau(pfc_handle h, const double *tau) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+        const int rc = radau_need(c, "pfc_radau_set_tau", false);
+        if (rc != PFC_OK) return rc;
+        pfc_context::RadauHost &R = c->radau;
+        const size_t ns = (size_t)R.L.n_scene, nv = (size_t)R.L.nv;
+        R.has_tau = tau != nullptr && nv > 0;
+        if (!R.has_tau) return (int)PFC_OK;
+        for (size_t e = 0; e < ns * nv; ++e)
+            if (!std::isfinite(tau[e])) return fail(c, PFC_ERR_NONFINITE, "pfc_radau_set_tau: tau of scene %zu is not finite", e / nv);
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (int k = 0; k < 3; ++k)      // the same tau for the three stage-scenes of a scene
+            HIP_TRY(c, hipMemcpy(R.dbl.p + R.od[RD_TAU] + (size_t)k * ns * nv, tau, sizeof(double) * ns * nv, hipMemcpyHostToDevice));
+        return (int)PFC_OK; });
+}
+
+int pfc_radau_rule_state(pfc_handle h, double *out7) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+        const int rc = radau_need(c, "pfc_radau_rule_state", true);
+        if (rc != PFC_OK) return rc;
+        if (!out7) return fail(c, PFC_ERR_BAD_ARG, "pfc_radau_rule_state: null buffer");
+        pfc_context::RadauHost &R = c->radau;
+        const size_t ns = (size_t)R.L.n_scene;
+        std::vector<double> hh(ns), en(2 * ns), nst(8 * ns);
+        std::vector<int> rule(ns), cool(ns);
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpy(hh.data(), R.dbl.p + R.od[RD_H], sizeof(double) * ns, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(en.data(), R.dbl.p + R.od[RD_ENORM], sizeof(double) * 2 * ns, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(nst.data(), R.dbl.p + R.od[RD_NSTATE], sizeof(double) * 8 * ns, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(rule.data(), R.itg.p + R.oi[RI_RULE], sizeof(int) * ns, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(cool.data(), R.itg.p + R.oi[RI_COOL], sizeof(int) * ns, hipMemcpyDeviceToHost));
+        for (size_t s = 0; s < ns; ++s) {
+            double *o = out7 + 7 * s;
+            o[0] = hh[s]; o[1] = rule[s]; o[2] = cool[s]; o[3] = nst[8 * s + kRadTheta]; o[4] = nst[8 * s + kRadPsi];
+            o[5] = en[2 * s]; o[6] = en[2 * s + 1];
+        }
+        return (int)PFC_OK; });
+}
+
+// An evaluation and its pfc_check, re-issued while the work lists grow.
+static int radau_checked(pfc_context *c, const std::function<int()> &issue) {
+    for (int k = 0; k < 40; ++k) {
+        int rc = issue();
+        if (rc != PFC_OK) return rc;
+        rc = pfc_check(c);
+        if (rc != PFC_ERR_OVERFLOW) return rc;
+    }
+    return fail(c, PFC_ERR_OVERFLOW, "pfc_radau_step: the work lists still overflow after 40 re-issues");
+}
+
+static int radau_read_count(pfc_context *c, int *count) {
+    pfc_context::RadauHost &R = c->radau;
+    HIP_TRY(c, hipMemcpyAsync(count, R.itg.p + R.oi[RI_COUNT], sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PFC_OK;
+}
+
+static int radau_step_ctx(pfc_context *c, double *h_taken, int *flags, int *iters, int *attempts) {
+    const char *who = "pfc_radau_step";
+    int rc = radau_need(c, who, true);
+    if (rc != PFC_OK) return rc;
+    pfc_context::RadauHost &R = c->radau;
+    const RadauLayout &L = R.L;
+    const int ns = L.n_scene, n1 = ns * L.n_ips, N3 = 3 * ns, n3 = 3 * n1;
+    auto D = [&](int k) { return R.dbl.p + R.od[k]; };
+    auto I = [&](int k) { return R.itg.p + R.oi[k]; };
+    const double *tau = R.has_tau ? D(RD_TAU) : nullptr;
+    const int *br = L.br_items;
+    auto unpack = [&]() {
+        return pfc_radau_unpack_device(c, ns, L.nx, L.nq, L.nv, L.n_ips, L.n_br, br, D(RD_X), I(RI_RULE), I(RI_ISTATE), D(RD_XS), D(RD_VQ),
+                                       D(RD_VV), D(RD_VS), nullptr); };
+    // calcJacobian!: no scene is iterating, so every stage-scene -- the first n_scene of them are the scenes themselves -- gets x0
+    if ((rc = unpack()) != PFC_OK) return rc;
+    const int n_chunks = (L.nx + R.n_chunk - 1) / R.n_chunk;
+    for (int k = 0; k < n_chunks; ++k) {
+        const int nd = std::min(R.n_chunk, L.nx - k * R.n_chunk);
+        rc = pfc_radau_seed_device(c, ns, L.nx, L.nq, L.nv, L.n_ips, L.n_br, br, k, R.n_chunk, D(RD_DDQ), D(RD_DDV), D(RD_DDS), nullptr);
+        if (rc != PFC_OK) return rc;
+        rc = radau_checked(c, [&]() {
+            if (k == 0)
+                return pfc_state_derivative_dual_device(
+                    c, n1, nd, I(RI_VINS), I(RI_VSC), ns, D(RD_VQ), D(RD_VV), D(RD_DDQ), D(RD_DDV), D(RD_VS), D(RD_DDS), tau, nullptr,
+                    D(RD_VXWB), D(RD_VTW), D(RD_VJAC), D(RD_DDXWB), D(RD_DDTW), D(RD_DDJAC), D(RD_VPOSE), D(RD_VTWI), D(RD_VXR2), I(RI_VB1),
+                    I(RI_VB2), D(RD_DDPOSE), D(RD_DDTWI), D(RD_DDXR2), D(RD_VWR), D(RD_VSD), D(RD_DDWR), D(RD_DDSD), I(RI_VCNT), D(RD_VF),
+                    D(RD_DDF), D(RD_VQD), D(RD_VH), D(RD_VC), D(RD_VVD), I(RI_VINFO), D(RD_DDQD), D(RD_DDH), D(RD_DDC), D(RD_DDVD), nullptr);
+            return pfc_state_derivative_dual_device_more(
+                c, n1, nd, I(RI_VINS), I(RI_VSC), ns, D(RD_VQ), D(RD_VV), D(RD_DDQ), D(RD_DDV), D(RD_DDS), tau, nullptr, D(RD_VXWB), D(RD_VTW),
+                D(RD_VJAC), D(RD_DDXWB), D(RD_DDTW), D(RD_DDJAC), D(RD_VXR2), I(RI_VB1), I(RI_VB2), D(RD_VWR), D(RD_DDPOSE), D(RD_DDTWI),
+                D(RD_DDXR2), D(RD_DDWR), D(RD_DDSD), D(RD_DDF), D(RD_VH), D(RD_VC), D(RD_VF), D(RD_DDQD), D(RD_DDH), D(RD_DDC), D(RD_DDVD),
+                nullptr); });
+        if (rc != PFC_OK) return rc;
+        rc = pfc_radau_jacobian_device(c, ns, L.nx, L.nq, L.nv, L.n_ips, L.n_br, br, k, R.n_chunk, D(RD_DDQD), D(RD_DDVD), D(RD_DDSD),
+                                       D(RD_VQD), D(RD_VVD), D(RD_VSD), D(RD_NEGJ), D(RD_XDOT0), D(RD_NSTATE), I(RI_ISTATE), nullptr);
+        if (rc != PFC_OK) return rc;
+    }
+    // solveRadau_inner: attempts until no scene is armed again
+    for (int attempt = 0; attempt < 64; ++attempt) {
+        rc = radau_factor_launch(c, ns, L.nx, D(RD_NEGJ), D(RD_H), I(RI_RULE), I(RI_ISTATE) + kRadIter, 8, D(RD_LU0), D(RD_LU1), I(RI_PERM),
+                                 I(RI_INFO), c->stream);
+        if (rc != PFC_OK) return rc;
+        int count = 1;
+        for (int it = 0; it <= R.k_iter_max && count > 0; ++it) {
+            if ((rc = unpack()) != PFC_OK) return rc;
+            rc = radau_checked(c, [&]() {
+                return pfc_state_derivative_device(c, n3, I(RI_VINS), I(RI_VSC), N3, D(RD_VQ), D(RD_VV), D(RD_VS), tau, D(RD_VXWB), D(RD_VTW),
+                                                   D(RD_VJAC), D(RD_VPOSE), D(RD_VTWI), D(RD_VXR2), I(RI_VB1), I(RI_VB2), D(RD_VWR), D(RD_VSD),
+                                                   I(RI_VCNT), D(RD_VF), D(RD_VQD), D(RD_VH), D(RD_VC), D(RD_VVD), I(RI_VINFO), nullptr); });
+            if (rc != PFC_OK) return rc;
+            rc = pfc_radau_newton_device(c, ns, L.nx, L.nq, L.nv, L.n_ips, L.n_br, br, D(RD_VQD), D(RD_VVD), D(RD_VSD), D(RD_X), D(RD_H),
+                                         I(RI_RULE), D(RD_LU0), D(RD_LU1), I(RI_PERM), I(RI_INFO), R.tol_newton, R.k_iter_max, D(RD_XS),
+                                         D(RD_FS), D(RD_NSTATE), I(RI_ISTATE), I(RI_COUNT), nullptr);
+            if (rc != PFC_OK || (rc = radau_read_count(c, &count)) != PFC_OK) return rc;
+        }
+        if (count > 0) return fail(c, PFC_ERR_STATE, "%s: %d scenes still iterate after k_iter_max + 1 passes", who, count);
+        rc = pfc_radau_finish_device(c, ns, L.nx, L.nq, L.nv, L.n_ips, L.n_br, br, R.n_mrp, R.mrp_off, R.fin, R.k_iter_max, R.max_rule,
+                                     R.cooldown, D(RD_FS), D(RD_XDOT0), D(RD_XS), D(RD_LU0), I(RI_PERM), D(RD_X),
+                                     D(RD_T), D(RD_H), I(RI_RULE), I(RI_COOL), D(RD_ENORM), D(RD_NSTATE), I(RI_ISTATE), I(RI_COUNT), nullptr);
+        if (rc != PFC_OK || (rc = radau_read_count(c, &count)) != PFC_OK) return rc;
+        if (count == 0) break;
+        if (attempt == 63) return fail(c, PFC_ERR_STATE, "%s: scenes are still armed after 64 attempts", who);
+    }
+    std::vector<double> nst(8 * (size_t)ns);
+    std::vector<int> ist(8 * (size_t)ns);
+    HIP_TRY(c, hipMemcpy(nst.data(), D(RD_NSTATE), sizeof(double) * nst.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(ist.data(), I(RI_ISTATE), sizeof(int) * ist.size(), hipMemcpyDeviceToHost));
+    for (int s = 0; s < ns; ++s) {
+        const int *is = ist.data() + 8 * (size_t)s;
+        if (h_taken) h_taken[s] = is[kRadExit] == 0 ? nst[8 * (size_t)s + kRadHTaken] : 0.0;
+        if (flags) flags[s] = is[kRadExit];
+        if (iters) iters[s] = is[kRadExitIter];
+        if (attempts) attempts[s] = is[kRadAttempts];
+    }
+    return PFC_OK;
+}
+
+int pfc_radau_step(pfc_handle h, double *h_taken, int *flags, int *iters, int *attempts) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) { return radau_step_ctx(c, h_taken, flags, iters, attempts); });
 }
 
 }  // extern "C"

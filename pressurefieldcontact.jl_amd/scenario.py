@@ -1164,6 +1164,138 @@ class MechanismScenario:
         vdot, dvdot, info = self.accelerations_dual(H, c, f, dH, dc, d_f, tau, dtau)
         return qd, vdot, sdot, dqd, dvdot, dsd, info, (f, d_f), (H, c), (dH, dc), (wrench, dw, counts)
 
+    # ---- the Radau IIA step on the device (include/pfc.h; mirrors integrate_scenario_radau, src/example_integrator.jl) -----------
+    def radau_configure(self, n_scene: int, ins_ids: Sequence[int], h0: float = 1e-4, tol_a: float = 1e-4, tol_r: float = 1e-4,
+                        tol_newton: float = 1e-16, h_max: float = 0.01, h_min: float = 1e-8, k_iter_max: int = 15, max_rule: int = 2,
+                        n_chunk: int = 6, cooldown: int = 10):
+        """pfc_radau_configure: a batch of n_scene scenes of the mechanism, each with the items ins_ids; the reference's defaults.
+        Returns NX = nq + nv + 6 (bristle items per scene)."""
+        ids = np.ascontiguousarray(ins_ids, dtype=np.int32).reshape(-1)
+        par = np.array([h0, tol_a, tol_r, tol_newton, h_max, h_min], dtype=np.float64)
+        self._check(_lib.lib().pfc_radau_configure(self._h, int(n_scene), int(ids.size), ids.ctypes.data_as(_ip), par.ctypes.data_as(_dp),
+                                                   int(k_iter_max), int(max_rule), int(n_chunk), int(cooldown)))
+        self._radau_n_scene = int(n_scene)
+        return self.radau_sizes()[0]
+
+    def radau_sizes(self):
+        """(NX, item indices of the bristle items of a scene)."""
+        nx, nb = C.c_int(0), C.c_int(0)
+        items = np.zeros(16, dtype=np.int32)
+        self._check(_lib.lib().pfc_radau_sizes(self._h, C.byref(nx), C.byref(nb), items.ctypes.data_as(_ip)))
+        return nx.value, items[:nb.value].copy()
+
+    def radau_set_state(self, x, t=None):
+        """x (n_scene, NX) = [q; v; s of the bristle items] and t (n_scene,) or None (zeros); resets h, rule, cooldown and the norms."""
+        nx = self.radau_sizes()[0]
+        x_a = np.ascontiguousarray(x, dtype=np.float64).reshape(self._radau_n_scene, nx)
+        t_a = None if t is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.float64), (self._radau_n_scene,)))
+        self._check(_lib.lib().pfc_radau_set_state(self._h, x_a.ctypes.data_as(_dp), None if t_a is None else t_a.ctypes.data_as(_dp)))
+
+    def radau_set_rule_state(self, h=None, rule=None, cooldown=None):
+        """pfc_radau_set_rule_state: per-scene step size, rule and cooldown (each (n_scene,) or a scalar, or None: unchanged) in
+        place of what radau_set_state reset them to."""
+        n = self._radau_n_scene
+        arr = lambda a, dt: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=dt), (n,)))
+        h_a, r_a, c_a = arr(h, np.float64), arr(rule, np.int32), arr(cooldown, np.int32)
+        self._check(_lib.lib().pfc_radau_set_rule_state(self._h, None if h_a is None else h_a.ctypes.data_as(_dp),
+                                                        None if r_a is None else r_a.ctypes.data_as(_ip),
+                                                        None if c_a is None else c_a.ctypes.data_as(_ip)))
+
+    def radau_get_state(self):
+        """(x (n_scene, NX), t (n_scene,))."""
+        nx = self.radau_sizes()[0]
+        x = np.zeros((self._radau_n_scene, nx)); t = np.zeros(self._radau_n_scene)
+        self._check(_lib.lib().pfc_radau_get_state(self._h, x.ctypes.data_as(_dp), t.ctypes.data_as(_dp)))
+        return x, t
+
+    def radau_set_tau(self, tau=None):
+        """tau (n_scene, nv) held constant over the steps that follow, or None (zeros)."""
+        t_a = None if tau is None else np.ascontiguousarray(tau, dtype=np.float64).reshape(self._radau_n_scene, -1)
+        self._check(_lib.lib().pfc_radau_set_tau(self._h, None if t_a is None else t_a.ctypes.data_as(_dp)))
+
+    def radau_rule_state(self):
+        """Per scene: dict of h, rule, cooldown, theta, psi_k, x_err_norm, x_err_norm_next (arrays of n_scene)."""
+        out = np.zeros((self._radau_n_scene, 7))
+        self._check(_lib.lib().pfc_radau_rule_state(self._h, out.ctypes.data_as(_dp)))
+        return dict(h=out[:, 0].copy(), rule=out[:, 1].astype(np.int32), cooldown=out[:, 2].astype(np.int32), theta=out[:, 3].copy(),
+                    psi_k=out[:, 4].copy(), x_err_norm=out[:, 5].copy(), x_err_norm_next=out[:, 6].copy())
+
+    def radau_step(self):
+        """pfc_radau_step: one step of every scene.  Returns dict(h_taken, flags, iters, attempts) and raises PFCError("time step is
+        too small, something is wrong") naming the scenes whose exit flag is 5, as the reference's solveRadau_inner throws."""
+        n = getattr(self, "_radau_n_scene", 0)      # 0: not configured, the library says so
+        h = np.zeros(n); fl = np.zeros(n, dtype=np.int32); it = np.zeros(n, dtype=np.int32); at = np.zeros(n, dtype=np.int32)
+        self._check(_lib.lib().pfc_radau_step(self._h, h.ctypes.data_as(_dp), fl.ctypes.data_as(_ip), it.ctypes.data_as(_ip),
+                                              at.ctypes.data_as(_ip)))
+        if (fl == 5).any():
+            raise _lib.PFCError(_lib.ERR_STATE, "time step is too small, something is wrong (scenes %s)" % np.flatnonzero(fl == 5).tolist())
+        return dict(h_taken=h, flags=fl, iters=it, attempts=at)
+
+    def integrate_radau(self, t_final: float, max_steps: int = 100000):
+        """Steps until every scene's t >= t_final or max_steps steps were taken (integrate_scenario_radau steps while t < t_final
+        and does not shorten the last step).  A scene that has arrived is still stepped with the others.  Returns (x, t, steps)."""
+        steps = 0
+        x, t = self.radau_get_state()
+        while (t < t_final).any() and steps < max_steps:
+            self.radau_step()
+            steps += 1
+            x, t = self.radau_get_state()
+        return x, t, steps
+
+    # ---- parts of the Radau IIA step (include/pfc.h, csrc/pfc_radau.h): raw device addresses, asynchronous on `stream` ----------
+    # layout = (n_scene, nx, nq, nv, n_ips, br_items): x = [q; v; 6 states per bristle item], br_items the bristle items of a scene.
+    @staticmethod
+    def _radau_layout(layout):
+        n_scene, nx, nq, nv, n_ips, br = layout
+        br_a = np.ascontiguousarray(br, dtype=np.int32).reshape(-1)
+        return [int(n_scene), int(nx), int(nq), int(nv), int(n_ips), int(br_a.size), br_a.ctypes.data_as(_ip)], br_a
+
+    def radau_seed_device(self, layout, chunk: int, n_chunk: int, d_dq: int, d_dv: int, d_ds: int, stream: int = 0):
+        """pfc_radau_seed_device: the unit seeds of a Jacobian chunk in state_derivative_dual_device's seed layouts."""
+        head, keep = self._radau_layout(layout)
+        self._check(_lib.lib().pfc_radau_seed_device(self._h, *head, int(chunk), int(n_chunk), d_dq or None, d_dv or None, d_ds or None,
+                                                     stream or None))
+
+    def radau_jacobian_device(self, layout, chunk: int, n_chunk: int, d_dqdot: int, d_dvdot: int, d_dsdot: int, d_qdot: int, d_vdot: int,
+                              d_sdot: int, d_neg_J: int, d_xdot0: int, d_nstate: int = 0, d_istate: int = 0, stream: int = 0):
+        """pfc_radau_jacobian_device: a chunk's partials into columns of -J; chunk 0 also writes xdot0 and arms the scenes."""
+        head, keep = self._radau_layout(layout)
+        a = [d_dqdot, d_dvdot, d_dsdot, d_qdot, d_vdot, d_sdot, d_neg_J, d_xdot0, d_nstate, d_istate, stream]
+        self._check(_lib.lib().pfc_radau_jacobian_device(self._h, *head, int(chunk), int(n_chunk), *[p or None for p in a]))
+
+    def radau_factor_device(self, n_scene: int, nx: int, d_neg_J: int, d_h: int, d_rule: int, d_active: int, d_lu0: int, d_lu1: int,
+                            d_perm: int, d_info: int, stream: int = 0):
+        """pfc_radau_factor_device: the LU factors of -J + (lam / h) I per scene, real and (rule 2) complex."""
+        a = [d_neg_J, d_h, d_rule, d_active, d_lu0, d_lu1, d_perm, d_info, stream]
+        self._check(_lib.lib().pfc_radau_factor_device(self._h, int(n_scene), int(nx), *[p or None for p in a]))
+
+    def radau_unpack_device(self, layout, d_x0: int, d_rule: int, d_istate: int, d_X: int, d_q: int, d_v: int, d_s: int, stream: int = 0):
+        """pfc_radau_unpack_device: the stage states into (q, v, s) of the 3 n_scene stage-scenes."""
+        head, keep = self._radau_layout(layout)
+        a = [d_x0, d_rule, d_istate, d_X, d_q, d_v, d_s, stream]
+        self._check(_lib.lib().pfc_radau_unpack_device(self._h, *head, *[p or None for p in a]))
+
+    def radau_newton_device(self, layout, d_qdot: int, d_vdot: int, d_sdot: int, d_x0: int, d_h: int, d_rule: int, d_lu0: int, d_lu1: int,
+                            d_perm: int, d_info: int, tol_newton: float, k_iter_max: int, d_X: int, d_F_save: int, d_nstate: int,
+                            d_istate: int, d_count: int, stream: int = 0):
+        """pfc_radau_newton_device: one iteration of simple_newton! for every iterating scene (d_F_save 0: F is not kept)."""
+        head, keep = self._radau_layout(layout)
+        a = [d_qdot, d_vdot, d_sdot, d_x0, d_h, d_rule, d_lu0, d_lu1, d_perm, d_info]
+        b = [d_X, d_F_save, d_nstate, d_istate, d_count, stream]
+        self._check(_lib.lib().pfc_radau_newton_device(self._h, *head, *[p or None for p in a], float(tol_newton), int(k_iter_max),
+                                                       *[p or None for p in b]))
+
+    def radau_finish_device(self, layout, mrp_off, params, k_iter_max: int, max_rule: int, cooldown: int, d_F: int, d_xdot0: int, d_X: int, d_lu0: int, d_perm: int, d_x: int, d_t: int, d_h: int, d_rule: int,
+                            d_cool: int, d_enorm: int, d_nstate: int, d_istate: int, d_count: int, stream: int = 0):
+        """pfc_radau_finish_device: the end of an attempt -- error norm, new h and rule, the commit or the re-arming.  mrp_off: the
+        offsets in q of the floating joints' MRPs; params = (tol_a, tol_r, h_max, h_min)."""
+        head, keep = self._radau_layout(layout)
+        m_a = np.ascontiguousarray(mrp_off, dtype=np.int32).reshape(-1)
+        p_a = np.ascontiguousarray(params, dtype=np.float64).reshape(4)
+        a = [d_F, d_xdot0, d_X, d_lu0, d_perm, d_x, d_t, d_h, d_rule, d_cool, d_enorm, d_nstate, d_istate, d_count, stream]
+        self._check(_lib.lib().pfc_radau_finish_device(self._h, *head, int(m_a.size), m_a.ctypes.data_as(_ip), p_a.ctypes.data_as(_dp),
+                                                       int(k_iter_max), int(max_rule), int(cooldown), *[p or None for p in a]))
+
     def dual_seeds_from_bodies(self, x_w_b, twist_w_b, d_x_w_b, d_twist_w_b, ins_ids: Optional[Sequence[int]] = None,
                                scene=None) -> BodySeeds:
         """The Dual seeds of items_from_bodies' items from the partials of the bodies' world states (pfc_dual_seeds_from_bodies, host
@@ -1400,6 +1532,20 @@ class MechanismScenario:
 
 
 # ---- host helpers standing in for the RigidBodyDynamics calls of refreshBodyBodyTransform!/Cache! -----------------
+def radau_table(rule: int) -> dict:
+    """The Radau IIA constants compiled into the library (pfc_radau_table; generated by scripts/radau_tables.py): rule 1 (one stage) or
+    2 (three stages).  c (s,), A (s,s), lam (s,) complex, T and Tinv (s,s) complex with A^-1 T = T diag(lam), bhat0, bhat (s,)."""
+    ns = C.c_int(0)
+    c = np.zeros(3); A = np.zeros(9); lam = np.zeros(6); T = np.zeros(18); Ti = np.zeros(18); bh = np.zeros(4)
+    rc = _lib.lib().pfc_radau_table(int(rule), C.byref(ns), *[a.ctypes.data_as(_dp) for a in (c, A, lam, T, Ti, bh)])
+    if rc != _lib.OK:
+        raise _lib.PFCError(rc, "pfc_radau_table: rules 1 and 2 only")
+    s = ns.value
+    cx = lambda a, shape: (a[:2 * int(np.prod(shape))].reshape(-1, 2) @ np.array([1.0, 1.0j])).reshape(shape)
+    return dict(c=c[:s].copy(), A=A[:s * s].reshape(s, s).copy(), lam=cx(lam, (s,)), T=cx(T, (s, s)), Tinv=cx(Ti, (s, s)),
+                bhat0=float(bh[0]), bhat=bh[1:1 + s].copy())
+
+
 def relative_pose(R_w1, t_w1, R_w2, t_w2) -> np.ndarray:
     """pose[24] for bodies with world poses x_rw_r1 = (R_w1, t_w1), x_rw_r2 = (R_w2, t_w2):
     x_r2_rw = inv(x_rw_r2); x_r2_r1 = x_r2_rw * x_rw_r1; x_r1_r2 = inv(x_r2_r1)
