@@ -908,7 +908,16 @@ int pfc_contact_surface_fric_device(pfc_handle h, int n_items, const int *d_ins_
  * integration and friction passes holds have fans of like length; value evaluations without a Dual list and without "fixed_order"
  * only, and launches of at least 2^20 candidates only -- 512-candidate chunks, what the gain was measured on; every other path keeps
  * the dense fill; same counts and traction points, sums equal up to their order; 0 = dense fill everywhere, the behaviour before the
- * option existed; 3..9 allowed; -9..-3: the split |value| in launches of every size, for tests; other values PFC_ERR_BAD_ARG), "team" (default 48, at most 48; 0 = never: an evaluation of a few
+ * option existed; 3..9 allowed; -9..-3: the split |value| in launches of every size, for tests; other values PFC_ERR_BAD_ARG), "integ_spec"
+ * (default 2: a scenario WITHOUT a regularized instruction integrates its kept polygons -- the pass after the clip-only kernel,
+ * "clip_min" -- in a form of k_integ that does not carry the regularized-friction lane: 1 = that form at two waves per SIMD, 2 = the
+ * same at three waves, which the registers the lane held make room for; 0 = always the general kernel.  The arithmetic and the order
+ * of every sum are the general kernel's: under "fixed_order" the three values return the same bytes.  A scenario with any regularized
+ * instruction runs the general kernel whatever the value; Dual value passes and "fixed_order" use the forms too; other values
+ * PFC_ERR_BAD_ARG), "quad_const" (default 1: a scenario whose instructions ALL have quadrature rule 2 runs the bristle-only forms of
+ * "integ_spec" and the per-corner friction pass of "vertex_fields" with the rule as a compile-time constant -- the same literals and
+ * expressions, so the same bits; 0 = the kernels read the rule from the item; a scenario with a rule-1 instruction runs those whatever
+ * the value; other values PFC_ERR_BAD_ARG), "team" (default 48, at most 48; 0 = never: an evaluation of a few
  * pairs too big for one workgroup -- BASELINE's single 9 680-tet x 5 120-triangle pair -- runs as ONE kernel with a team
  * of up to this many workgroups per item -- while a workgroup of the team has at most ~1 200 leaves of the pair to descend: up
  * to 16 poses of that pair; beyond that the batched path is faster --, and a few mid-sized items -- a 972-tet box on the

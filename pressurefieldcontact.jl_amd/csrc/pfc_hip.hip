@@ -6,7 +6,8 @@
 //                  cooperative exact test), k_bp_dfs (all-Float64 descent, A/B option)         [tree_types.jl:88-111]
 //   pfc_np.h       narrowphase: k_narrow (gather, clip in an LDS polygon ring, fan quadrature, pressure, regularized
 //                  friction, bristle moments, kept polygons; MODE 2 = clip only for big batches), k_integ (quadrature
-//                  and per-item sums over the compacted polygons), k_fric (bristle friction over kept polygons)
+//                  and per-item sums over the compacted polygons), k_fric (bristle friction over kept polygons); their
+//                  forms for scenarios without a regularized instruction / with rule 2 throughout (k_integ_br*, k_fric_q3)
 //   pfc_fused.h    k_fused: a small scene's whole evaluation in one launch, one workgroup per item
 //   pfc_dual.h     the same path on (value, partial) numbers: k_dual_flags / k_dual_select (the pairs a chunk's seeds
 //                  touch), k_narrow_dual, k_dual_poly, k_dual_eig, k_dual_final
@@ -434,7 +435,8 @@ struct pfc_context {
     DevBuf<char> mesh_arena;
     int max_levels = 1;
     int max_leaves = 2;                // largest n_leaf(mesh_1) + n_leaf(mesh_2) over the instructions
-    bool any_bristle = false, any_tet_tet = false;
+    bool any_bristle = false, any_tet_tet = false, any_regularized = false;
+    bool all_rule2 = false;              // every instruction has quadrature rule 2 (three points per fan triangle)
     // options
     int opt_debug = 0, opt_profile = 0, opt_max_levels = 0, opt_bfs_levels = -1, opt_no_filter = 0;
     // work buffers
@@ -583,6 +585,12 @@ struct pfc_context {
     // passes without a Dual list and without fixed_order only, and launches with 512-candidate chunks only (-s: split s at every chunk
     // size, np_bin_split); 0: dense fill everywhere
     int opt_bin_split = 5;             // (5: triangles and quadrilaterals from the front, 85 % of the C3 batch's polygons; 4 measured slower)
+    // option "integ_spec": a scenario without a regularized instruction (any_regularized false) integrates its kept polygons in the
+    // bristle-only k_integ_br (1, two waves per SIMD) or k_integ_br3 (2, three waves); 0, or any regularized instruction: k_integ
+    int opt_integ_spec = 2;
+    // option "quad_const": where every instruction has quadrature rule 2 (all_rule2), the bristle-only k_integ forms and the per-corner
+    // k_fric run with the rule as a compile-time constant (k_integ_br*_q3, k_fric_q3); 0: the forms that read the item's rule
+    int opt_quad_const = 1;
     int opt_clip_queue = 1;            // option "clip_queue": clip-only narrowphase of big tri-tet batches in k_clip_queue (survivors queued in the ring); 0: k_narrow<.., 2 / 3>
     int fused_skip = 0;                // evaluations left for which the fused kernel stays off after an item did not fit
     int fused_seq = 0;                 // sequence number of the last fused launch (completion word of the polled path)
@@ -1053,8 +1061,17 @@ int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double 
         ig.poly_cand = np.poly_cand; ig.surv = np.surv; ig.scount = np.scount; ig.acc = h->acc.p; ig.rec = h->rec.p;
         ig.rgn = h->rgn.p; ig.rr_cap = np.rr_cap; ig.icnt = h->icnt.p; ig.status = h->status.p;
         ig.det = h->opt_fixed_order ? h->det.p : nullptr;
-        if (h->opt_fixed_order) hipLaunchKernelGGL(k_integ_fixed, dim3(grid_for(h->ccap, 64, kNpMaxBlocks)), dim3(64), 0, st, ig);
-        else hipLaunchKernelGGL(k_integ, dim3(grid_for(h->ccap, 64, kNpMaxBlocks)), dim3(64), 0, st, ig);
+        // the bristle-only forms where no instruction of the scenario is regularized (a property of the scenario, as any_tet_tet)
+        const int spec = h->any_regularized ? 0 : h->opt_integ_spec;
+        const dim3 ig_grid(grid_for(h->ccap, 64, kNpMaxBlocks));
+        const bool q3 = h->all_rule2 && h->opt_quad_const;      // (the bristle-only forms only)
+        if (h->opt_fixed_order) {
+            if (spec == 2) hipLaunchKernelGGL(q3 ? k_integ_br3_q3_fixed : k_integ_br3_fixed, ig_grid, dim3(64), 0, st, ig);
+            else if (spec == 1) hipLaunchKernelGGL(q3 ? k_integ_br_q3_fixed : k_integ_br_fixed, ig_grid, dim3(64), 0, st, ig);
+            else hipLaunchKernelGGL(k_integ_fixed, ig_grid, dim3(64), 0, st, ig);
+        } else if (spec == 2) hipLaunchKernelGGL(q3 ? k_integ_br3_q3 : k_integ_br3, ig_grid, dim3(64), 0, st, ig);
+        else if (spec == 1) hipLaunchKernelGGL(q3 ? k_integ_br_q3 : k_integ_br, ig_grid, dim3(64), 0, st, ig);
+        else hipLaunchKernelGGL(k_integ, ig_grid, dim3(64), 0, st, ig);
     }
     if (prof) HIP_TRY(h, hipEventRecord(h->ev[EV_NP], st));
 
@@ -1092,11 +1109,14 @@ int record_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double 
         // "debug" keeps the per-point kernel: the friction sums are then formed at exactly the traction points the debug views hand out
         const bool vertex_fields = h->opt_vertex_fields && !h->opt_debug;
         // (grid cap 256 x 32, twice the other narrowphase kernels': paired A/B 4.32 -> 4.22 ms per 8 192-pose step; x 64 and x 128 alike)
+        const bool fric_q3 = vertex_fields && h->all_rule2 && h->opt_quad_const;      // the rule as a constant (option "quad_const")
         if (fr.sink.rec) {
-            if (vertex_fields) hipLaunchKernelGGL(k_fric_fixed<true>, dim3(grid_for(h->ccap, 64, 256 * 32)), dim3(64), 0, st, fr);
+            if (fric_q3) hipLaunchKernelGGL(k_fric_q3_fixed, dim3(grid_for(h->ccap, 64, 256 * 32)), dim3(64), 0, st, fr);
+            else if (vertex_fields) hipLaunchKernelGGL(k_fric_fixed<true>, dim3(grid_for(h->ccap, 64, 256 * 32)), dim3(64), 0, st, fr);
             else hipLaunchKernelGGL(k_fric_fixed<false>, dim3(grid_for(h->ccap, 64, 256 * 32)), dim3(64), 0, st, fr);
             hipLaunchKernelGGL(k_fixed_reduce, dim3(n_items), dim3(64), 0, st, fr.sink, n_items, h->acc.p, kAccStride, kAccFric, 6);
-        } else if (vertex_fields) hipLaunchKernelGGL(k_fric<true>, dim3(grid_for(h->ccap, 64, 256 * 32)), dim3(64), 0, st, fr);
+        } else if (fric_q3) hipLaunchKernelGGL(k_fric_q3, dim3(grid_for(h->ccap, 64, 256 * 32)), dim3(64), 0, st, fr);
+        else if (vertex_fields) hipLaunchKernelGGL(k_fric<true>, dim3(grid_for(h->ccap, 64, 256 * 32)), dim3(64), 0, st, fr);
         else hipLaunchKernelGGL(k_fric<false>, dim3(grid_for(h->ccap, 64, 256 * 32)), dim3(64), 0, st, fr);
     }
     if (prof) HIP_TRY(h, hipEventRecord(h->ev[EV_BR], st));
@@ -1133,7 +1153,7 @@ int enqueue_eval(pfc_context *h, int n_items, const int *d_ins_ids, const double
             while (((size_t)1 << lg) < cover && lg < 40) ++lg;
             key.debug |= ((lg + 1) << 16) | (h->fixed_whole_list ? 1 << 24 : 0);
         }
-        key.bristle = (h->any_bristle ? 1 : 0) | (h->any_tet_tet ? 2 : 0);
+        key.bristle = (h->any_bristle ? 1 : 0) | (h->any_tet_tet ? 2 : 0) | (h->any_regularized ? 4 : 0) | (h->all_rule2 ? 8 : 0);
         key.surv = o.list ? 1 : 0;
         key.p[0] = d_ins_ids; key.p[1] = d_pose; key.p[2] = d_twist; key.p[3] = d_s; key.p[4] = d_wrench;
         key.p[5] = d_sdot; key.p[6] = d_counts; key.p[7] = o.tail; key.p[8] = o.bp_pose; key.stream = (void *)st; key.epoch = h->epoch;
@@ -1469,7 +1489,8 @@ int make_twin(pfc_context *h) {
     t->device = h->device; t->is_twin = true; t->finalized = true;
     t->ins = h->ins; t->d_meshes = h->d_meshes; t->d_ins = h->d_ins; t->max_levels = h->max_levels;
     t->max_leaves = h->max_leaves; t->max_elem1 = h->max_elem1; t->max_elem2 = h->max_elem2;
-    t->any_bristle = h->any_bristle; t->any_tet_tet = h->any_tet_tet; t->opt_split_min = 0;
+    t->any_bristle = h->any_bristle; t->any_tet_tet = h->any_tet_tet; t->any_regularized = h->any_regularized; t->all_rule2 = h->all_rule2;
+    t->opt_split_min = 0;
     t->stream = std::move(h->twin_stream);
     if ((!t->stream && hipStreamCreateWithFlags(t->stream.put(), hipStreamNonBlocking) != hipSuccess) ||
         hipEventCreateWithFlags(h->ev_fork.put(), hipEventDisableTiming) != hipSuccess ||
@@ -1865,8 +1886,10 @@ int pfc_finalize(pfc_handle h) {
     h->max_levels = 1;
     h->max_leaves = 2;
     h->max_elem1 = h->max_elem2 = 1;
-    h->any_bristle = false;
+    h->any_bristle = h->any_regularized = false;
+    h->all_rule2 = !h->ins.empty();
     for (const InsDev &in : h->ins) {
+        if (in.nq == 1) h->all_rule2 = false;      // (InsDev::nq is the rule; k_setup_items gives every other rule three points)
         {   // (key widths of the candidate sort, option "fixed_order": a candidate is (element of mesh_1, tet of mesh_2))
             const HostMesh &m1 = h->meshes[in.m1], &m2 = h->meshes[in.m2];
             const int e1 = m1.n_tri ? m1.n_tri : m1.n_tet;
@@ -1878,6 +1901,7 @@ int pfc_finalize(pfc_handle h) {
         const int lf = h->meshes[in.m1].n_leaf + h->meshes[in.m2].n_leaf;
         if (lf > h->max_leaves) h->max_leaves = lf;
         if (in.model == PFC_BRISTLE) h->any_bristle = true;
+        if (in.model == PFC_REGULARIZED) h->any_regularized = true;
         if (h->meshes[in.m1].n_tri == 0) h->any_tet_tet = true;
     }
     // the depth-first broadphase keeps 3 * levels + 3 stack slots in reserve (k_bp_dfs)
@@ -1956,6 +1980,8 @@ static int eval_device(pfc_context *h, int n_items, const int *d_ins_ids, const 
     if (t->opt_clip_queue != h->opt_clip_queue) { t->opt_clip_queue = h->opt_clip_queue; t->ghave[0] = t->ghave[1] = false; }
     if (t->opt_bin_split != h->opt_bin_split) { t->opt_bin_split = h->opt_bin_split; t->ghave[0] = t->ghave[1] = false; }
     if (t->opt_vertex_fields != h->opt_vertex_fields) { t->opt_vertex_fields = h->opt_vertex_fields; t->ghave[0] = t->ghave[1] = false; }
+    if (t->opt_integ_spec != h->opt_integ_spec) { t->opt_integ_spec = h->opt_integ_spec; t->ghave[0] = t->ghave[1] = false; }
+    if (t->opt_quad_const != h->opt_quad_const) { t->opt_quad_const = h->opt_quad_const; t->ghave[0] = t->ghave[1] = false; }
     t->opt_graph = h->opt_graph;
     if (t->opt_no_filter != h->opt_no_filter) { t->opt_no_filter = h->opt_no_filter; t->ghave[0] = t->ghave[1] = false; }
     const int n0 = n_items / 2, n1 = n_items - n0;      // (55 / 45 is the same within noise, 60 / 40 and 45 / 55 are slower: round 3)
@@ -2854,7 +2880,7 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     const double *d_sv = s ? di + n * 30 : nullptr;
     pfc_context::DualGraphKey key = {};
     key.v.n_items = n_items; key.v.levels = levels; key.v.L = L; key.v.debug = 0;
-    key.v.bristle = (h->any_bristle ? 1 : 0) | (h->any_tet_tet ? 2 : 0); key.v.surv = 1;
+    key.v.bristle = (h->any_bristle ? 1 : 0) | (h->any_tet_tet ? 2 : 0) | (h->any_regularized ? 4 : 0) | (h->all_rule2 ? 8 : 0); key.v.surv = 1;
     key.v.p[0] = d_ins; key.v.p[1] = di; key.v.p[2] = di + n * 24; key.v.p[3] = d_sv; key.v.p[4] = dout;
     key.v.p[5] = dout + n * 6; key.v.p[6] = dout + out_d; key.v.p[7] = o.tail; key.v.p[8] = o.bp_pose; key.v.stream = (void *)st; key.v.epoch = h->epoch;
     key.n_dir = n_dir; key.bound = bound; key.din = ddi; key.dout = ddo;
@@ -4412,6 +4438,15 @@ int pfc_set_option(pfc_handle h, const char *name, long long value) {
         if (value != 0 && (sp < 3 || sp > 9))
             return fail(h, PFC_ERR_BAD_ARG, "bin_split must be 0 (dense fill), 3..9 (polygons of fewer vertices fill a 512-candidate chunk from its front) or -9..-3 (chunks of every size)");
         h->opt_bin_split = (int)value; h->ghave[0] = h->ghave[1] = false; h->dghave = false;
+    }
+    else if (!std::strcmp(name, "integ_spec")) {
+        if (value < 0 || value > 2)
+            return fail(h, PFC_ERR_BAD_ARG, "integ_spec must be 0 (general k_integ), 1 (bristle-only form, two waves per SIMD) or 2 (the same at three waves)");
+        h->opt_integ_spec = (int)value; h->ghave[0] = h->ghave[1] = false; h->dghave = false;
+    }
+    else if (!std::strcmp(name, "quad_const")) {
+        if (value != 0 && value != 1) return fail(h, PFC_ERR_BAD_ARG, "quad_const must be 0 (the kernels read the item's quadrature rule) or 1 (rule 2 as a constant where every instruction has it)");
+        h->opt_quad_const = (int)value; h->ghave[0] = h->ghave[1] = false; h->dghave = false;
     }
     else if (!std::strcmp(name, "poison")) h->opt_poison = value != 0;
     else if (!std::strcmp(name, "fused")) { h->opt_fused = value != 0; h->fused_skip = 0; }

@@ -1178,7 +1178,12 @@ __device__ __forceinline__ double lds_rows_total(const double *buf, int lane, in
 // DET (option "fixed_order", the candidate list sorted: pfc_sort.hip): a run leaves NO atomic sum behind -- its ten sums travel in
 // its record next to the moments, the record carries its chunk index and hangs in a list per item, and k_shift_fixed adds an
 // item's records in chunk order.
-template <bool DET>
+// REG = false (option "integ_spec", a scenario without a regularized instruction): lane_reg is the constant false, so the
+// regularized lane -- fs[6], v_c, mu_s, mu_d, the clamp -- is not compiled and its registers are free; every other expression
+// and the order of every sum is the one of REG = true.
+// NQ = 3 (option "quad_const", a scenario whose instructions all have quadrature rule 2): the number of points per fan triangle is the
+// constant 3 instead of the item's field, so the point loop and the choice of the rule's literals are resolved at compile time; 0 reads it.
+template <bool DET, bool REG, int NQ = 0>
 __device__ __forceinline__ void integ_body(const IntegArgs &g, double *m27) {
     constexpr int RS = 66;                  // row stride of lds_row_sums / lds_rows_total with two lanes per row
     const int lane = threadIdx.x;
@@ -1290,8 +1295,8 @@ __device__ __forceinline__ void integ_body(const IntegArgs &g, double *m27) {
             }
             // the item's constants per lane (vector loads issued together with the polygon's: no dependent scalar round trip)
             const ItemRec *it = g.items + (has ? item : 0);
-            const bool lane_reg = it->model == PFC_REGULARIZED;
-            const int nq = it->nq;
+            const bool lane_reg = REG && it->model == PFC_REGULARIZED;
+            const int nq = NQ ? NQ : it->nq;
             const V3 w = ld3(it->w), vl = ld3(it->v);
             const double chi = it->chi, Ebar = it->Ebar;
             // ---- (A) the traction points of every polygon of the piece, ONCE: regularized lanes sum their wrench, bristle
@@ -1360,7 +1365,7 @@ __device__ __forceinline__ void integ_body(const IntegArgs &g, double *m27) {
                 const int run_item = __builtin_amdgcn_readlane(item, f);
                 const bool in_run = has && item == run_item;
                 todo &= ~__ballot(in_run);
-                const bool reg = __builtin_amdgcn_readlane((int)lane_reg, f) != 0;
+                const bool reg = REG && __builtin_amdgcn_readlane((int)lane_reg, f) != 0;
                 if (run_item != cur) {
                     flush();
                     cur = run_item;
@@ -1433,11 +1438,46 @@ __device__ __forceinline__ void integ_body(const IntegArgs &g, double *m27) {
 }
 __global__ void __launch_bounds__(64, 2) k_integ(IntegArgs g) {
     __shared__ double m27[27 * 66];         // the 27 running moments of the current run, one column per lane
-    integ_body<false>(g, m27);
+    integ_body<false, true>(g, m27);
 }
 __global__ void __launch_bounds__(64, 2) k_integ_fixed(IntegArgs g) {
     __shared__ double m27[27 * 66];
-    integ_body<true>(g, m27);
+    integ_body<true, true>(g, m27);
+}
+// the bristle-only forms (option "integ_spec" 1 and 2): REG = false at two waves per SIMD, and at three -- the registers the
+// regularized lane held are what takes the kernel under the 168 of three waves without a spill
+__global__ void __launch_bounds__(64, 2) k_integ_br(IntegArgs g) {
+    __shared__ double m27[27 * 66];
+    integ_body<false, false>(g, m27);
+}
+__global__ void __launch_bounds__(64, 2) k_integ_br_fixed(IntegArgs g) {
+    __shared__ double m27[27 * 66];
+    integ_body<true, false>(g, m27);
+}
+__global__ void __launch_bounds__(64, 3) k_integ_br3(IntegArgs g) {
+    __shared__ double m27[27 * 66];
+    integ_body<false, false>(g, m27);
+}
+__global__ void __launch_bounds__(64, 3) k_integ_br3_fixed(IntegArgs g) {
+    __shared__ double m27[27 * 66];
+    integ_body<true, false>(g, m27);
+}
+// ... and with the quadrature rule fixed at 2 (three points per fan triangle; option "quad_const")
+__global__ void __launch_bounds__(64, 2) k_integ_br_q3(IntegArgs g) {
+    __shared__ double m27[27 * 66];
+    integ_body<false, false, 3>(g, m27);
+}
+__global__ void __launch_bounds__(64, 2) k_integ_br_q3_fixed(IntegArgs g) {
+    __shared__ double m27[27 * 66];
+    integ_body<true, false, 3>(g, m27);
+}
+__global__ void __launch_bounds__(64, 3) k_integ_br3_q3(IntegArgs g) {
+    __shared__ double m27[27 * 66];
+    integ_body<false, false, 3>(g, m27);
+}
+__global__ void __launch_bounds__(64, 3) k_integ_br3_q3_fixed(IntegArgs g) {
+    __shared__ double m27[27 * 66];
+    integ_body<true, false, 3>(g, m27);
 }
 
 // Bristle friction pass (after k_eig): calc_spatial_bristle_force (friction.jl:171-201) + traction(::Bristle) (:32-48)
@@ -1462,7 +1502,8 @@ struct FricArgs {
 };
 // VF (option "vertex_fields", the default): eq, the damping argument and T̄s are evaluated once per fan corner and combined
 // per point (FanFields, pfc_kernels.h) instead of re-derived from r at every point; !VF is the per-point statement.
-template <bool FX, bool VF>
+// NQ = 3 (option "quad_const"): the rule is the constant 2 -- FanFields::nq / qa / qd / qw are literals -- as in integ_body; 0 reads the item's.
+template <bool FX, bool VF, int NQ = 0>
 __device__ __forceinline__ void fric_body(const FricArgs &g) {
     const int lane = threadIdx.x;
     const size_t P = (size_t)g.pcap;
@@ -1493,7 +1534,7 @@ __device__ __forceinline__ void fric_body(const FricArgs &g) {
             const V3 nh = mk3(o[0], o[P], o[2 * P]);
             const V3 cen = mk3(o[3 * P], o[4 * P], o[5 * P]);
             const double er0 = o[6 * P], er1 = o[7 * P], er2 = o[8 * P], er3 = o[9 * P];
-            const int nq = it->nq;
+            const int nq = NQ ? NQ : it->nq;
             const V3 w = ld3(it->w), vl = ld3(it->v);
             const double chi = it->chi, Ebar = it->Ebar, mu_s = it->mu_s, mu_d = it->mu_d;
             const double tau = it->tau, k_bar = it->k_bar;
@@ -1610,4 +1651,7 @@ __device__ __forceinline__ void fric_body(const FricArgs &g) {
 }
 template <bool VF> __global__ void __launch_bounds__(64, 3) k_fric(FricArgs g) { fric_body<false, VF>(g); }
 template <bool VF> __global__ void __launch_bounds__(64, 3) k_fric_fixed(FricArgs g) { fric_body<true, VF>(g); }
+// the per-corner form with the quadrature rule fixed at 2 (option "quad_const")
+__global__ void __launch_bounds__(64, 3) k_fric_q3(FricArgs g) { fric_body<false, true, 3>(g); }
+__global__ void __launch_bounds__(64, 3) k_fric_q3_fixed(FricArgs g) { fric_body<true, true, 3>(g); }
 
