@@ -1031,7 +1031,7 @@ int pfc_radau_factor_device(pfc_handle h, int n_scene, int nx, const double *d_n
  * d_nstate (n_scene x 8) = {theta, theta of the iteration before, Psi_k, the residuals of the last two iterations (+inf at the start of
  * an attempt), this iteration's residual, the h of the last committed step, unused}; d_istate (n_scene x 8) = {iterating, k_iter (0 at
  * the start of an attempt), the attempt's exit flag (-1 while iterating), attempt open (1 from the arming to pfc_radau_finish_device),
- * attempts of this step, the step's exit flag, k_iter of the last attempt, unused}.  *d_count is set to the number of scenes still
+ * attempts of this step, the step's exit flag, k_iter of the last attempt, the parked mark (0 unless pfc_radau_finish_end_device set it)}.  *d_count is set to the number of scenes still
  * iterating.  Per scene, NS = 1 or 3 stages:
  *   k_iter += 1; a nonzero info of a factor the rule uses: flag 4, done.
  *   r_s = ((X_s - x0) + (-h A[s,0]) F_0) + (-h A[s,1]) F_1 ...;  residual = ((0 + sum r_0 r_0) + sum r_1 r_1) + .. (wave sums);
@@ -1072,7 +1072,8 @@ int pfc_radau_configure(pfc_handle h, int n_scene, int n_ips, const int *ins_ids
 /* NX, the bristle items per scene and their item indices (bristle_items: room for PFC_MAX_NX_RADAU / 6).  Any may be NULL. */
 int pfc_radau_sizes(pfc_handle h, int *nx, int *n_bristle, int *bristle_items);
 /* x (n_scene x NX, host) and t (n_scene, host; NULL: zeros) in; h, rule, cooldown, theta, Psi_k and the norms are reset to what the
- * reference's constructors give (h0, rule 1, the cooldown, -9999, 9999, -9999), and every scene is active again. */
+ * reference's constructors give (h0, rule 1, the cooldown, -9999, 9999, -9999), and every scene is active again: no scene is retired
+ * or parked, and an end set with pfc_radau_set_end is dropped with its trajectory (end times +inf, nothing recorded). */
 int pfc_radau_set_state(pfc_handle h, const double *x, const double *t);
 int pfc_radau_get_state(pfc_handle h, double *x, double *t);      /* either may be NULL */
 /* After pfc_radau_set_state: a step size, rule (1 .. max_rule) and cooldown (>= 0) per scene (n_scene each, host; NULL: as it is)
@@ -1086,16 +1087,44 @@ int pfc_radau_set_tau(pfc_handle h, const double *tau);
  * each followed by pfc_check and re-issued on PFC_ERR_OVERFLOW, the columns gathered), then per attempt the factors and the loop
  * unpack -> pfc_state_derivative_device -> pfc_check -> newton, one word read back per pass (the scenes still iterating), then finish;
  * attempts repeat for the scenes finish armed again.  Converged and retired scenes are still evaluated (the shape is fixed) and
- * ignored.  Per scene (each may be NULL): h_taken (0 where no step was taken), the exit flag (0, or 5: "time step is too small,
- * something is wrong" -- x and t are unchanged and the scene stays retired until pfc_radau_set_state), k_iter of the last attempt,
- * the attempts.  Any other status of an evaluation or its pfc_check (a state that left the scene non-finite, say) is returned as it
+ * ignored.  Per scene (each may be NULL): h_taken (0 where no step was taken), the exit flag (0; 5: "time step is too small,
+ * something is wrong" -- x and t are unchanged and the scene stays retired until pfc_radau_set_state; 6: at or past its end, nothing
+ * done -- see pfc_radau_set_end; attempts and h_taken are then 0), k_iter of the last attempt, the attempts.  Any other status of an evaluation or its pfc_check (a state that left the scene non-finite, say) is returned as it
  * is; the integrator state is then undefined until pfc_radau_set_state.  No dense output: every attempt starts from X = x0
- * (the reference's interpolate.jl is not built).  Multi-device handles use their first device.  Every scene that is not retired is
- * stepped by every call: a caller that integrates a batch to an end time steps the scenes that have arrived on with the others (they
- * overshoot), or reads the state after each step; there is no per-scene stop.  n_scene and n_ips are limited at configure time so that
+ * (the reference's interpolate.jl is not built).  Multi-device handles use their first device.  Every scene that is neither retired
+ * nor parked is stepped by every call; scenes stop one by one at the end times of pfc_radau_set_end, and while an end is set the
+ * step records the trajectory as pfc_radau_integrate does.  n_scene and n_ips are limited at configure time so that
  * 3 n_scene max(n_ips, n_body) rows of 24 words are indexed in int.
  */
 int pfc_radau_step(pfc_handle h, double *h_taken, int *flags, int *iters, int *attempts);
+/*
+ * Integration to per-scene end times with the trajectory kept on the device: the loop of integrate_scenario_radau
+ * (src/example_integrator.jl) for every scene of the batch.  After pfc_radau_set_state (PFC_ERR_STATE before it or before
+ * pfc_radau_configure).
+ * pfc_radau_set_end: t_final (n_scene, host; NULL: +inf, which never stops a scene) and the row budget max_rows of each scene (the
+ * reference's max_steps + 1; 0: nothing is recorded).  Row 0 of a scene's trajectory becomes its (t, x) now, and no scene is parked
+ * any more.  From then on every committed step of a scene appends the row (t, x) -- x after principal_value!, as the reference stores
+ * it -- and the scene PARKS at the commit that leaves t_final < t (strict, as the reference's loop; a scene already past its end
+ * still takes one step: the reference steps first and tests afterwards) or that fills its last row.  That step's exit flag is 0.  A
+ * failed attempt and a retirement (flag 5) append nothing.  A parked scene is treated as a retired one: it is not armed, it is
+ * evaluated at its committed x (the evaluation shape stays 3 n_scene) and its x, t, h, rule, cooldown and norms stay byte for byte;
+ * pfc_radau_step reports exit flag 6 for it.  Parking ends with pfc_radau_set_state or the next pfc_radau_set_end.  The trajectory,
+ * n_scene x max_rows x (1 + NX) doubles, is device memory owned by the handle: freed by the next pfc_radau_set_end,
+ * pfc_radau_configure, pfc_radau_set_state and with the handle.  PFC_ERR_BAD_ARG, with a message and nothing changed: a NaN t_final,
+ * max_rows < 0 or max_rows = 1.  PFC_ERR_NOMEM if the trajectory cannot be allocated: the previous end stays in force.
+ * pfc_radau_integrate: batch steps -- pfc_radau_step's, parking and recording as above (with no end set: end times +inf, nothing
+ * recorded) -- until no scene is live (neither retired nor parked) or max_steps (>= 0) steps were taken; *steps_done and *n_live (either
+ * may be NULL) are the batch steps taken and the scenes live afterwards.  Per batch step the host reads one word per Newton pass and
+ * two per finish (the scenes armed again; the scenes live); neither the records nor x are copied.  tau stays what pfc_radau_set_tau
+ * set: a caller with a controller integrates one batch step at a time.
+ * pfc_radau_trajectory_rows: the rows written per scene (n_scene ints, host).  pfc_radau_trajectory: rows [row0, row0 + n) of a scene
+ * into t (n) and x (n x NX) (host; either may be NULL); PFC_ERR_BAD_ARG, nothing written, for a scene or a range outside what was
+ * recorded; PFC_ERR_STATE for either call before pfc_radau_set_end.
+ */
+int pfc_radau_set_end(pfc_handle h, const double *t_final, int max_rows);
+int pfc_radau_integrate(pfc_handle h, int max_steps, int *steps_done, int *n_live);
+int pfc_radau_trajectory_rows(pfc_handle h, int *rows);
+int pfc_radau_trajectory(pfc_handle h, int scene, int row0, int n, double *t, double *x);
 /* Per scene 7 doubles: h, rule, cooldown, theta, Psi_k, x_err_norm, x_err_norm k+1. */
 int pfc_radau_rule_state(pfc_handle h, double *out7);
 
@@ -1114,8 +1143,9 @@ int pfc_radau_seed_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int
  * bristle rows of dsdot] of direction d, from pfc_state_derivative_dual_device[_more]'s outputs d_dqdot (n_scene x n_dir x nq), d_dvdot
  * (n_scene x n_dir x nv), d_dsdot (n_scene n_ips x n_dir x 6).  Chunk 0 also writes d_xdot0 (n_scene x NX) = [qdot; vdot; sdot] of the
  * value buffers (the reference's xx_0; they are not read for the later chunks and may be NULL there) and, where d_nstate and d_istate
- * are given, arms every scene whose step exit flag is not 5 for the first attempt of a step: iterating = 1, k_iter = 0, attempt flag -1,
- * attempt open, attempts = 1, both remembered residuals +inf. */
+ * are given, arms every scene whose step exit flag is not 5 and whose parked mark (the last word of its integer record; 0 unless
+ * pfc_radau_finish_end_device set it) is 0 for the first attempt of a step: iterating = 1, k_iter = 0, attempt flag -1, attempt open,
+ * attempts = 1, both remembered residuals +inf.  A parked scene whose flag is not 5 gets step exit flag 6 and attempts 0 instead. */
 int pfc_radau_jacobian_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int chunk,
                               int n_chunk, const double *d_dqdot, const double *d_dvdot, const double *d_dsdot, const double *d_qdot,
                               const double *d_vdot, const double *d_sdot, double *d_neg_J, double *d_xdot0, double *d_nstate,
@@ -1152,6 +1182,19 @@ int pfc_radau_finish_device(pfc_handle h, int n_scene, int nx, int nq, int nv, i
                             const double *d_F, const double *d_xdot0, const double *d_X,
                             const double *d_lu0, const int *d_perm, double *d_x, double *d_t, double *d_h, int *d_rule, int *d_cool,
                             double *d_enorm, double *d_nstate, int *d_istate, int *d_count, void *stream);
+/* The same with ends (what pfc_radau_step runs while an end is set, and pfc_radau_integrate always).  d_t_final (n_scene; NULL: +inf),
+ * d_traj (n_scene x max_rows x (1 + NX): row r of scene s starts at (s max_rows + r) (1 + NX), t then the NX states), d_rows (n_scene:
+ * the rows written so far), max_rows (0: nothing is recorded, d_traj and d_rows are not touched; 1 is PFC_ERR_BAD_ARG), d_live (one
+ * word, NOT zeroed by the call).  At a commit, besides the above: the row (t, x after principal_value!) is stored at d_rows[scene] and
+ * the count incremented (no row is stored where the count is not below max_rows); the scene parks -- the last word of its integer
+ * record becomes 1, its step exit flag stays 0 -- if d_t_final[scene] < t or the row was the last; otherwise *d_live += 1.  Failed
+ * attempts and retirements record nothing and add nothing. */
+int pfc_radau_finish_end_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int n_mrp,
+                                const int *mrp_off, const double *params, int k_iter_max, int max_rule, int cooldown,
+                                const double *d_F, const double *d_xdot0, const double *d_X,
+                                const double *d_lu0, const int *d_perm, double *d_x, double *d_t, double *d_h, int *d_rule, int *d_cool,
+                                double *d_enorm, double *d_nstate, int *d_istate, int *d_count, const double *d_t_final, double *d_traj,
+                                int *d_rows, int max_rows, int *d_live, void *stream);
 
 #ifdef __cplusplus
 }

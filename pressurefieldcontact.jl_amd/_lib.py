@@ -133,6 +133,12 @@ SIGNATURES = {
     "pfc_radau_unpack_device": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [_ip] + [C.c_void_p] * 8),
     "pfc_radau_finish_device": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [_ip, C.c_int, _ip, _dp, C.c_int, C.c_int, C.c_int]
                                 + [C.c_void_p] * 15),
+    "pfc_radau_finish_end_device": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [_ip, C.c_int, _ip, _dp, C.c_int, C.c_int, C.c_int]
+                                    + [C.c_void_p] * 17 + [C.c_int, C.c_void_p, C.c_void_p]),
+    "pfc_radau_set_end": (C.c_int, [C.c_void_p, _dp, C.c_int]),
+    "pfc_radau_integrate": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip]),
+    "pfc_radau_trajectory_rows": (C.c_int, [C.c_void_p, _ip]),
+    "pfc_radau_trajectory": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp]),
 }
 
 

@@ -644,6 +644,13 @@ struct pfc_context {
         DevBuf<double> dbl;
         DevBuf<int> itg;
         std::vector<size_t> od, oi;                 // offsets of the parts (RadauD, RadauI)
+        // pfc_radau_set_end: the end times live in dbl (RD_TFINAL) and the row counts in itg (RI_ROWS); the trajectory is a block of
+        // its own, n_scene x max_rows x (1 + NX), replaced by the next pfc_radau_set_end and freed by pfc_radau_configure,
+        // pfc_radau_set_state and with the handle
+        bool has_end = false;
+        int max_rows = 0;
+        DevBuf<double> traj;
+        void drop_end() { has_end = false; max_rows = 0; traj.release(); }
     } radau;
 };
 
@@ -4855,6 +4862,7 @@ static int radau_check_nx(pfc_context *h, const char *who, int n_scene, int nx) 
 static int radau_factor_launch(pfc_context *h, int n_scene, int nx, const double *d_neg_J, const double *d_h, const int *d_rule,
                                const int *d_active, int active_stride, double *d_lu0, double *d_lu1, int *d_perm, int *d_info,
                                hipStream_t st);
+static pfc_context *radau_ctx(pfc_context *h);
 
 // The state layout every part but the factorisation takes, validated: NX = nq + nv + 6 n_br, the bristle items increasing and < n_ips.
 static int radau_layout(pfc_context *h, const char *who, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items,
@@ -4951,18 +4959,21 @@ int pfc_radau_unpack_device(pfc_handle h, int n_scene, int nx, int nq, int nv, i
     return PFC_OK;
 }
 
-int pfc_radau_finish_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int n_mrp,
-                            const int *mrp_off, const double *params, int k_iter_max, int max_rule, int cooldown,
-                            const double *d_F, const double *d_xdot0, const double *d_X,
-                            const double *d_lu0, const int *d_perm, double *d_x, double *d_t, double *d_h, int *d_rule, int *d_cool,
-                            double *d_enorm, double *d_nstate, int *d_istate, int *d_count, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_radau_finish_device(c, n_scene, nx, nq, nv, n_ips, n_br, br_items, n_mrp, mrp_off, params, k_iter_max, max_rule,
-                                           cooldown, d_F, d_xdot0, d_X, d_lu0, d_perm, d_x, d_t, d_h, d_rule, d_cool,
-                                           d_enorm, d_nstate, d_istate, d_count, stream); });
-    const char *who = "pfc_radau_finish_device";
+// What k_radau_finish<true> takes beyond k_radau_finish<false>'s arguments (pfc_radau_finish_end_device).
+struct RadauEndBufs {
+    const double *t_final;
+    double *traj;
+    int *rows;
+    int max_rows;
+    int *live;
+};
+
+// Both finish parts: `end` null launches k_radau_finish<false>, else <true> with those buffers.
+static int radau_finish_launch(pfc_context *h, const char *who, const RadauEndBufs *end, int n_scene, int nx, int nq, int nv, int n_ips,
+                               int n_br, const int *br_items, int n_mrp, const int *mrp_off, const double *params, int k_iter_max,
+                               int max_rule, int cooldown, const double *d_F, const double *d_xdot0, const double *d_X,
+                               const double *d_lu0, const int *d_perm, double *d_x, double *d_t, double *d_h, int *d_rule, int *d_cool,
+                               double *d_enorm, double *d_nstate, int *d_istate, int *d_count, void *stream) {
     RadauFinishArgs a;
     const int rc = radau_layout(h, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &a.L);
     if (rc != PFC_OK) return rc;
@@ -4974,9 +4985,12 @@ int pfc_radau_finish_device(pfc_handle h, int n_scene, int nx, int nq, int nv, i
         return fail(h, PFC_ERR_BAD_ARG, "%s: params are {tol_a >= 0, tol_r >= 0, h_max > 0, h_min > 0}", who);
     if (k_iter_max < 1 || max_rule < 1 || max_rule > 2 || cooldown < 0)
         return fail(h, PFC_ERR_BAD_ARG, "%s: k_iter_max >= 1, max_rule 1 or 2 (rules 3 - 6 are not built), cooldown >= 0", who);
+    if (end && (end->max_rows < 0 || end->max_rows == 1))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: max_rows is %d: 0 (no recording) or at least 2", who, end->max_rows);
     if (n_scene == 0) return PFC_OK;
     if (!d_F || !d_xdot0 || !d_X || !d_lu0 || !d_perm || !d_x || !d_t || !d_h ||
-        !d_rule || !d_cool || !d_enorm || !d_nstate || !d_istate || !d_count)
+        !d_rule || !d_cool || !d_enorm || !d_nstate || !d_istate || !d_count ||
+        (end && (!end->live || (end->max_rows > 0 && (!end->traj || !end->rows)))))
         return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
@@ -4991,10 +5005,39 @@ int pfc_radau_finish_device(pfc_handle h, int n_scene, int nx, int nq, int nv, i
     a.F = d_F; a.xdot0 = d_xdot0; a.X = d_X; a.lu0 = d_lu0; a.perm = d_perm;
     a.x = d_x; a.t = d_t; a.h = d_h; a.rule = d_rule; a.cool = d_cool; a.enorm = d_enorm; a.nstate = d_nstate; a.istate = d_istate;
     a.count = d_count;
+    a.t_final = end ? end->t_final : nullptr; a.traj = end ? end->traj : nullptr; a.rows = end ? end->rows : nullptr;
+    a.max_rows = end ? end->max_rows : 0; a.live = end ? end->live : nullptr;
     HIP_TRY(h, hipMemsetAsync(d_count, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_radau_finish, dim3((unsigned)n_scene), dim3(kRadWave), 0, st, a);
+    if (end) hipLaunchKernelGGL(k_radau_finish<true>, dim3((unsigned)n_scene), dim3(kRadWave), 0, st, a);
+    else hipLaunchKernelGGL(k_radau_finish<false>, dim3((unsigned)n_scene), dim3(kRadWave), 0, st, a);
     HIP_TRY(h, hipGetLastError());
     return PFC_OK;
+}
+
+int pfc_radau_finish_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int n_mrp,
+                            const int *mrp_off, const double *params, int k_iter_max, int max_rule, int cooldown,
+                            const double *d_F, const double *d_xdot0, const double *d_X,
+                            const double *d_lu0, const int *d_perm, double *d_x, double *d_t, double *d_h, int *d_rule, int *d_cool,
+                            double *d_enorm, double *d_nstate, int *d_istate, int *d_count, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+        return radau_finish_launch(c, "pfc_radau_finish_device", nullptr, n_scene, nx, nq, nv, n_ips, n_br, br_items, n_mrp, mrp_off, params,
+                                   k_iter_max, max_rule, cooldown, d_F, d_xdot0, d_X, d_lu0, d_perm, d_x, d_t, d_h, d_rule, d_cool, d_enorm,
+                                   d_nstate, d_istate, d_count, stream); });
+}
+
+int pfc_radau_finish_end_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int n_mrp,
+                                const int *mrp_off, const double *params, int k_iter_max, int max_rule, int cooldown,
+                                const double *d_F, const double *d_xdot0, const double *d_X,
+                                const double *d_lu0, const int *d_perm, double *d_x, double *d_t, double *d_h, int *d_rule, int *d_cool,
+                                double *d_enorm, double *d_nstate, int *d_istate, int *d_count, const double *d_t_final, double *d_traj,
+                                int *d_rows, int max_rows, int *d_live, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    const RadauEndBufs end{d_t_final, d_traj, d_rows, max_rows, d_live};
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+        return radau_finish_launch(c, "pfc_radau_finish_end_device", &end, n_scene, nx, nq, nv, n_ips, n_br, br_items, n_mrp, mrp_off, params,
+                                   k_iter_max, max_rule, cooldown, d_F, d_xdot0, d_X, d_lu0, d_perm, d_x, d_t, d_h, d_rule, d_cool, d_enorm,
+                                   d_nstate, d_istate, d_count, stream); });
 }
 
 int pfc_radau_factor_device(pfc_handle h, int n_scene, int nx, const double *d_neg_J, const double *d_h, const int *d_rule,
@@ -5066,8 +5109,9 @@ int pfc_radau_newton_device(pfc_handle h, int n_scene, int nx, int nq, int nv, i
 enum RadauD { RD_X, RD_T, RD_H, RD_ENORM, RD_NSTATE, RD_XS, RD_FS, RD_XDOT0, RD_NEGJ, RD_LU0, RD_LU1, RD_TAU,
               RD_VQ, RD_VV, RD_VS, RD_VXWB, RD_VTW, RD_VJAC, RD_VPOSE, RD_VTWI, RD_VXR2, RD_VWR, RD_VSD, RD_VF, RD_VQD, RD_VH, RD_VC, RD_VVD,
               RD_DDQ, RD_DDV, RD_DDS, RD_DDXWB, RD_DDTW, RD_DDJAC, RD_DDPOSE, RD_DDTWI, RD_DDXR2, RD_DDWR, RD_DDSD, RD_DDF, RD_DDQD, RD_DDH,
-              RD_DDC, RD_DDVD, RD_N };
-enum RadauI { RI_RULE, RI_COOL, RI_ISTATE, RI_PERM, RI_INFO, RI_COUNT, RI_VINS, RI_VSC, RI_VB1, RI_VB2, RI_VCNT, RI_VINFO, RI_N };
+              RD_DDC, RD_DDVD, RD_TFINAL, RD_N };
+// RI_COUNT has two words: the count a newton or finish part returns, and the scenes live after a batch step (k_radau_finish<true>).
+enum RadauI { RI_RULE, RI_COOL, RI_ISTATE, RI_PERM, RI_INFO, RI_COUNT, RI_VINS, RI_VSC, RI_VB1, RI_VB2, RI_VCNT, RI_VINFO, RI_ROWS, RI_N };
 
 static int radau_configure_ctx(pfc_context *c, int n_scene, int n_ips, const int *ins_ids, const double *params, int k_iter_max,
                                int max_rule, int n_chunk, int cooldown) {
@@ -5121,15 +5165,16 @@ static int radau_configure_ctx(pfc_context *c, int n_scene, int n_ips, const int
     sd[RD_DDQ] = ns * nd * nq; sd[RD_DDV] = ns * nd * nv; sd[RD_DDS] = n1 * nd * 6; sd[RD_DDXWB] = ns * nb * nd * 12; sd[RD_DDTW] = ns * nb * nd * 6;
     sd[RD_DDJAC] = ns * nb * nd * nv * 6; sd[RD_DDPOSE] = n1 * nd * 24; sd[RD_DDTWI] = n1 * nd * 6; sd[RD_DDXR2] = n1 * nd * 12;
     sd[RD_DDWR] = n1 * nd * 6; sd[RD_DDSD] = n1 * nd * 6; sd[RD_DDF] = ns * nd * nv; sd[RD_DDQD] = ns * nd * nq; sd[RD_DDH] = ns * nd * nv * nv;
-    sd[RD_DDC] = ns * nd * nv; sd[RD_DDVD] = ns * nd * nv;
+    sd[RD_DDC] = ns * nd * nv; sd[RD_DDVD] = ns * nd * nv; sd[RD_TFINAL] = ns;
     si[RI_RULE] = ns; si[RI_COOL] = ns; si[RI_ISTATE] = 8 * ns; si[RI_PERM] = 2 * ns * n; si[RI_INFO] = 2 * ns; si[RI_COUNT] = 2;
-    si[RI_VINS] = n3; si[RI_VSC] = n3; si[RI_VB1] = n3; si[RI_VB2] = n3; si[RI_VCNT] = 4 * n3; si[RI_VINFO] = N3;
+    si[RI_VINS] = n3; si[RI_VSC] = n3; si[RI_VB1] = n3; si[RI_VB2] = n3; si[RI_VCNT] = 4 * n3; si[RI_VINFO] = N3; si[RI_ROWS] = ns;
     R.od.assign(RD_N, 0); R.oi.assign(RI_N, 0);
     size_t td = 0, ti = 0;
     for (int k = 0; k < RD_N; ++k) { R.od[k] = td; td += (std::max<size_t>(sd[k], 1) + 31) & ~(size_t)31; }
     for (int k = 0; k < RI_N; ++k) { R.oi[k] = ti; ti += (std::max<size_t>(si[k], 1) + 63) & ~(size_t)63; }
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    R.drop_end();
     HIP_TRY(c, R.dbl.ensure(td));
     HIP_TRY(c, R.itg.ensure(ti));
     HIP_TRY(c, hipMemset(R.dbl.p, 0, sizeof(double) * td));
@@ -5202,6 +5247,7 @@ int pfc_radau_set_state(pfc_handle h, const double *x, const double *t) {
         HIP_TRY(c, hipMemcpy(I + R.oi[RI_RULE], rule.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
         HIP_TRY(c, hipMemcpy(I + R.oi[RI_COOL], cool.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
         HIP_TRY(c, hipMemcpy(I + R.oi[RI_ISTATE], ist.data(), sizeof(int) * 8 * ns, hipMemcpyHostToDevice));
+        R.drop_end();      // no scene is parked, and an end that was set is gone with the trajectory that started at the old state
         R.has_state = true;
         return (int)PFC_OK; });
 }
@@ -5295,17 +5341,18 @@ static int radau_checked(pfc_context *c, const std::function<int()> &issue) {
     return fail(c, PFC_ERR_OVERFLOW, "pfc_radau_step: the work lists still overflow after 40 re-issues");
 }
 
-static int radau_read_count(pfc_context *c, int *count) {
+// The count word, or (words = 2) the count and the live word behind it, in one copy.
+static int radau_read_count(pfc_context *c, int *count, int words = 1) {
     pfc_context::RadauHost &R = c->radau;
-    HIP_TRY(c, hipMemcpyAsync(count, R.itg.p + R.oi[RI_COUNT], sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(count, R.itg.p + R.oi[RI_COUNT], sizeof(int) * (size_t)words, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return PFC_OK;
 }
 
-static int radau_step_ctx(pfc_context *c, double *h_taken, int *flags, int *iters, int *attempts) {
-    const char *who = "pfc_radau_step";
-    int rc = radau_need(c, who, true);
-    if (rc != PFC_OK) return rc;
+// One batch step, the body of pfc_radau_step and pfc_radau_integrate.  `end`: the finish is k_radau_finish<true> on the handle's end
+// times and trajectory, and *live receives the scenes that committed a step and did not park.
+static int radau_step_body(pfc_context *c, const char *who, bool end, int *live) {
+    int rc = PFC_OK;
     pfc_context::RadauHost &R = c->radau;
     const RadauLayout &L = R.L;
     const int ns = L.n_scene, n1 = ns * L.n_ips, N3 = 3 * ns, n3 = 3 * n1;
@@ -5340,6 +5387,9 @@ static int radau_step_ctx(pfc_context *c, double *h_taken, int *flags, int *iter
                                        D(RD_VQD), D(RD_VVD), D(RD_VSD), D(RD_NEGJ), D(RD_XDOT0), D(RD_NSTATE), I(RI_ISTATE), nullptr);
         if (rc != PFC_OK) return rc;
     }
+    const RadauEndBufs eb{R.has_end ? D(RD_TFINAL) : nullptr, R.max_rows > 0 ? R.traj.p : nullptr, R.max_rows > 0 ? I(RI_ROWS) : nullptr,
+                          R.max_rows, I(RI_COUNT) + 1};
+    if (end) HIP_TRY(c, hipMemsetAsync(I(RI_COUNT) + 1, 0, sizeof(int), c->stream));      // live adds up over the attempts' finishes
     // solveRadau_inner: attempts until no scene is armed again
     for (int attempt = 0; attempt < 64; ++attempt) {
         rc = radau_factor_launch(c, ns, L.nx, D(RD_NEGJ), D(RD_H), I(RI_RULE), I(RI_ISTATE) + kRadIter, 8, D(RD_LU0), D(RD_LU1), I(RI_PERM),
@@ -5359,13 +5409,27 @@ static int radau_step_ctx(pfc_context *c, double *h_taken, int *flags, int *iter
             if (rc != PFC_OK || (rc = radau_read_count(c, &count)) != PFC_OK) return rc;
         }
         if (count > 0) return fail(c, PFC_ERR_STATE, "%s: %d scenes still iterate after k_iter_max + 1 passes", who, count);
-        rc = pfc_radau_finish_device(c, ns, L.nx, L.nq, L.nv, L.n_ips, L.n_br, br, R.n_mrp, R.mrp_off, R.fin, R.k_iter_max, R.max_rule,
-                                     R.cooldown, D(RD_FS), D(RD_XDOT0), D(RD_XS), D(RD_LU0), I(RI_PERM), D(RD_X),
-                                     D(RD_T), D(RD_H), I(RI_RULE), I(RI_COOL), D(RD_ENORM), D(RD_NSTATE), I(RI_ISTATE), I(RI_COUNT), nullptr);
-        if (rc != PFC_OK || (rc = radau_read_count(c, &count)) != PFC_OK) return rc;
+        rc = radau_finish_launch(c, who, end ? &eb : nullptr, ns, L.nx, L.nq, L.nv, L.n_ips, L.n_br, br, R.n_mrp, R.mrp_off, R.fin,
+                                 R.k_iter_max, R.max_rule, R.cooldown, D(RD_FS), D(RD_XDOT0), D(RD_XS), D(RD_LU0), I(RI_PERM), D(RD_X),
+                                 D(RD_T), D(RD_H), I(RI_RULE), I(RI_COOL), D(RD_ENORM), D(RD_NSTATE), I(RI_ISTATE), I(RI_COUNT), nullptr);
+        int words[2] = {0, 0};
+        if (rc != PFC_OK || (rc = radau_read_count(c, words, end ? 2 : 1)) != PFC_OK) return rc;
+        count = words[0];
+        if (live) *live = words[1];
         if (count == 0) break;
         if (attempt == 63) return fail(c, PFC_ERR_STATE, "%s: scenes are still armed after 64 attempts", who);
     }
+    return PFC_OK;
+}
+
+static int radau_step_ctx(pfc_context *c, double *h_taken, int *flags, int *iters, int *attempts) {
+    const char *who = "pfc_radau_step";
+    int rc = radau_need(c, who, true);
+    if (rc != PFC_OK || (rc = radau_step_body(c, who, c->radau.has_end, nullptr)) != PFC_OK) return rc;
+    pfc_context::RadauHost &R = c->radau;
+    const int ns = R.L.n_scene;
+    auto D = [&](int k) { return R.dbl.p + R.od[k]; };
+    auto I = [&](int k) { return R.itg.p + R.oi[k]; };
     std::vector<double> nst(8 * (size_t)ns);
     std::vector<int> ist(8 * (size_t)ns);
     HIP_TRY(c, hipMemcpy(nst.data(), D(RD_NSTATE), sizeof(double) * nst.size(), hipMemcpyDeviceToHost));
@@ -5383,6 +5447,107 @@ static int radau_step_ctx(pfc_context *c, double *h_taken, int *flags, int *iter
 int pfc_radau_step(pfc_handle h, double *h_taken, int *flags, int *iters, int *attempts) {
     if (!h) return PFC_ERR_BAD_ARG;
     return on_shard(h, radau_ctx(h), [&](pfc_context *c) { return radau_step_ctx(c, h_taken, flags, iters, attempts); });
+}
+
+// ---- integration to per-scene end times (integrate_scenario_radau, src/example_integrator.jl) ------------------------------------
+int pfc_radau_set_end(pfc_handle h, const double *t_final, int max_rows) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+        const char *who = "pfc_radau_set_end";
+        const int rc = radau_need(c, who, true);
+        if (rc != PFC_OK) return rc;
+        pfc_context::RadauHost &R = c->radau;
+        const size_t ns = (size_t)R.L.n_scene, w = 1 + (size_t)R.L.nx;
+        if (max_rows < 0 || max_rows == 1) return fail(c, PFC_ERR_BAD_ARG, "%s: max_rows is %d: 0 (no recording) or at least 2", who, max_rows);
+        std::vector<double> tf(ns, std::numeric_limits<double>::infinity());
+        for (size_t s = 0; t_final && s < ns; ++s) {
+            if (t_final[s] != t_final[s]) return fail(c, PFC_ERR_BAD_ARG, "%s: t_final of scene %zu is NaN", who, s);
+            tf[s] = t_final[s];
+        }
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        DevBuf<double> block;      // the new trajectory first: if it cannot be had, the previous end stays in force
+        if (max_rows > 0 && block.ensure(ns * (size_t)max_rows * w) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, PFC_ERR_NOMEM, "%s: no device memory for %zu scenes x %d rows x %zu doubles", who, ns, max_rows, w);
+        }
+        R.traj = std::move(block);
+        R.max_rows = max_rows; R.has_end = true;
+        HIP_TRY(c, hipMemcpyAsync(R.dbl.p + R.od[RD_TFINAL], tf.data(), sizeof(double) * ns, hipMemcpyHostToDevice, c->stream));
+        RadauSetEndArgs a;
+        a.n_scene = R.L.n_scene; a.nx = R.L.nx; a.max_rows = max_rows;
+        a.x = R.dbl.p + R.od[RD_X]; a.t = R.dbl.p + R.od[RD_T]; a.traj = R.traj.p; a.rows = R.itg.p + R.oi[RI_ROWS];
+        a.istate = R.itg.p + R.oi[RI_ISTATE];
+        hipLaunchKernelGGL(k_radau_set_end, dim3(radau_grid(ns * w)), dim3(kRadBlock), 0, c->stream, a);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));      // tf is read until here
+        return (int)PFC_OK; });
+}
+
+int pfc_radau_integrate(pfc_handle h, int max_steps, int *steps_done, int *n_live) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+        const char *who = "pfc_radau_integrate";
+        int rc = radau_need(c, who, true);
+        if (rc != PFC_OK) return rc;
+        if (max_steps < 0) return fail(c, PFC_ERR_BAD_ARG, "%s: max_steps is %d", who, max_steps);
+        pfc_context::RadauHost &R = c->radau;
+        // the scenes live at the start, read once: neither retired (exit flag 5) nor parked
+        std::vector<int> ist(8 * (size_t)R.L.n_scene);
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpy(ist.data(), R.itg.p + R.oi[RI_ISTATE], sizeof(int) * ist.size(), hipMemcpyDeviceToHost));
+        int live = 0, steps = 0;
+        for (int s = 0; s < R.L.n_scene; ++s) live += ist[8 * (size_t)s + kRadExit] != 5 && ist[8 * (size_t)s + kRadIntSpare] == 0;
+        while (rc == PFC_OK && live > 0 && steps < max_steps) {
+            rc = radau_step_body(c, who, true, &live);
+            if (rc == PFC_OK) ++steps;
+        }
+        if (steps_done) *steps_done = steps;
+        if (n_live) *n_live = live;
+        return rc; });
+}
+
+int pfc_radau_trajectory_rows(pfc_handle h, int *rows) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+        const char *who = "pfc_radau_trajectory_rows";
+        const int rc = radau_need(c, who, true);
+        if (rc != PFC_OK) return rc;
+        pfc_context::RadauHost &R = c->radau;
+        if (!R.has_end) return fail(c, PFC_ERR_STATE, "%s before pfc_radau_set_end", who);
+        if (!rows) return fail(c, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpy(rows, R.itg.p + R.oi[RI_ROWS], sizeof(int) * (size_t)R.L.n_scene, hipMemcpyDeviceToHost));
+        return (int)PFC_OK; });
+}
+
+int pfc_radau_trajectory(pfc_handle h, int scene, int row0, int n, double *t, double *x) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+        const char *who = "pfc_radau_trajectory";
+        const int rc = radau_need(c, who, true);
+        if (rc != PFC_OK) return rc;
+        pfc_context::RadauHost &R = c->radau;
+        if (!R.has_end) return fail(c, PFC_ERR_STATE, "%s before pfc_radau_set_end", who);
+        if (scene < 0 || scene >= R.L.n_scene) return fail(c, PFC_ERR_BAD_ARG, "%s: scene %d of %d", who, scene, R.L.n_scene);
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        int have = 0;
+        HIP_TRY(c, hipMemcpy(&have, R.itg.p + R.oi[RI_ROWS] + scene, sizeof(int), hipMemcpyDeviceToHost));
+        if (row0 < 0 || n < 0 || (long long)row0 + n > (long long)have)
+            return fail(c, PFC_ERR_BAD_ARG, "%s: rows %d .. %d + %d of scene %d, which has %d", who, row0, row0, n, scene, have);
+        if (n == 0) return (int)PFC_OK;
+        const size_t nx = (size_t)R.L.nx, w = 1 + nx;
+        std::vector<double> buf((size_t)n * w);
+        HIP_TRY(c, hipMemcpy(buf.data(), R.traj.p + ((size_t)scene * (size_t)R.max_rows + (size_t)row0) * w, sizeof(double) * buf.size(),
+                             hipMemcpyDeviceToHost));
+        for (size_t r = 0; r < (size_t)n; ++r) {
+            if (t) t[r] = buf[r * w];
+            if (x) std::memcpy(x + r * nx, buf.data() + r * w + 1, sizeof(double) * nx);
+        }
+        return (int)PFC_OK; });
 }
 
 }  // extern "C"

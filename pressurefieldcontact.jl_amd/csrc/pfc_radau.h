@@ -3,7 +3,9 @@
 // (k_radau_factor; pfc_radau_factor_device), one iteration of simple_newton! -- calcEw!, the solves, updateStageX! and the
 // loop's bookkeeping (k_radau_newton; pfc_radau_newton_device) --, the end of an attempt (k_radau_finish) and the elementwise parts
 // around them: seed_indices! (k_radau_seed), write_indices! (k_radau_jac), the stage states into the evaluation's inputs
-// (k_radau_unpack).  pfc_radau_step (pfc_hip.hip) strings them together with the state-derivative calls.
+// (k_radau_unpack).  pfc_radau_step (pfc_hip.hip) strings them together with the state-derivative calls; pfc_radau_integrate runs
+// the same body to per-scene end times with k_radau_finish<true>, which records the trajectory and parks the scenes that have arrived
+// (k_radau_set_end starts a trajectory).
 // Included by pfc_hip.hip inside namespace pfc (device code only), after pfc_dyn.h.
 //
 // Arithmetic (the contract, stated in include/pfc.h): plain Float64, every sum in a written order, no fma (the build has
@@ -167,6 +169,8 @@ struct RadauLayout {
 };
 
 // Words of a scene's integer and Float64 records (n_scene x 8 each).
+// kRadIntSpare is the parked mark: 1 from the commit that took the scene past its end time or filled its last trajectory row
+// (k_radau_finish<true>) until the records are reset; the callers without an end leave it 0.
 enum { kRadIter = 0, kRadKIter, kRadFlag, kRadPhase, kRadAttempts, kRadExit, kRadExitIter, kRadIntSpare };
 enum { kRadTheta = 0, kRadThetaPrev, kRadPsi, kRadRes1, kRadRes2, kRadRes, kRadHTaken, kRadDblSpare };
 
@@ -351,7 +355,8 @@ __global__ void __launch_bounds__(kRadBlock) k_radau_seed(RadauSeedArgs g) {
 }
 
 // write_indices!: columns j0 .. j0 + n_dir of -J from the partials of a chunk; with `first`, xdot0 = [qdot; vdot; sdot] of the value
-// buffers as well, and the scene is armed for the first attempt of a step (unless it is retired with exit flag 5).
+// buffers as well, and the scene is armed for the first attempt of a step -- unless it is retired with exit flag 5 (nothing is
+// written) or parked at its end (kRadIntSpare != 0: its exit flag becomes 6 and its attempts 0).
 struct RadauJacArgs {
     RadauLayout L;
     int j0, n_dir, first;
@@ -382,8 +387,12 @@ __global__ void __launch_bounds__(kRadBlock) k_radau_jac(RadauJacArgs g) {
             g.xdot0[s * n + i] = radau_F(L, g.qdot, g.vdot, g.sdot, s, i);
             if (i == 0 && g.istate && g.nstate && g.istate[8 * s + kRadExit] != 5) {
                 int *is = g.istate + 8 * s;
-                is[kRadIter] = 1; is[kRadKIter] = 0; is[kRadFlag] = -1; is[kRadPhase] = 1; is[kRadAttempts] = 1;
-                g.nstate[8 * s + kRadRes1] = inf; g.nstate[8 * s + kRadRes2] = inf;
+                if (is[kRadIntSpare] == 0) {
+                    is[kRadIter] = 1; is[kRadKIter] = 0; is[kRadFlag] = -1; is[kRadPhase] = 1; is[kRadAttempts] = 1;
+                    g.nstate[8 * s + kRadRes1] = inf; g.nstate[8 * s + kRadRes2] = inf;
+                } else {      // parked at its end (k_radau_finish<true>): exit flag 6, "at or past its end; nothing done"
+                    is[kRadExit] = 6; is[kRadAttempts] = 0;
+                }
             }
         }
     }
@@ -437,9 +446,18 @@ struct RadauFinishArgs {
     double *nstate;
     int *istate;
     int *count;                             // += 1 per scene armed for another attempt
+    // k_radau_finish<true> only: the end of each scene and its trajectory
+    const double *t_final;                  // n_scene, or NULL (+inf): the scene parks at the commit that leaves t_final < t
+    double *traj;                           // n_scene x max_rows x (1 + nx): row r of scene s at (s max_rows + r) (1 + nx), t then x
+    int *rows;                              // n_scene: the rows written; a scene also parks at the commit that fills its last row
+    int max_rows;                           // 0: nothing is recorded (traj and rows are not touched)
+    int *live;                              // += 1 per scene that committed and did not park
 };
 
-__global__ void __launch_bounds__(kRadWave) k_radau_finish(RadauFinishArgs g) {
+// END = false: the step without ends.  END = true adds, at a commit: the row (t, x) after principal_value!, the row count, the park
+// decision (kRadIntSpare = 1; kRadExit of the arriving step stays 0) and the count of scenes that go on.  A failed attempt and a
+// retirement (exit flag 5) record nothing and count as not live.
+template <bool END> __global__ void __launch_bounds__(kRadWave) k_radau_finish(RadauFinishArgs g) {
     const RadauLayout &L = g.L;
     const int sc = (int)blockIdx.x, n = L.nx, i = (int)threadIdx.x;
     const bool act = i < n;
@@ -488,6 +506,12 @@ __global__ void __launch_bounds__(kRadWave) k_radau_finish(RadauFinishArgs g) {
             if (nn > 1.0 && i >= o && i < o + 3) xi = -(xf / nn);
         }
         if (act) g.x[(size_t)sc * n + i] = xi;
+        if (END) {
+            if (g.max_rows > 0) {
+                const int row = g.rows[sc];      // read by every lane before lane 0 writes it: the stores below follow the reads in program order
+                if (act && row < g.max_rows) g.traj[((size_t)sc * (size_t)g.max_rows + (size_t)row) * (size_t)(1 + n) + 1 + (size_t)i] = xi;
+            }
+        }
     } else {
         cool = g.cooldown_reset;
         new_rule = rule - 1 > 1 ? rule - 1 : 1;
@@ -497,9 +521,22 @@ __global__ void __launch_bounds__(kRadWave) k_radau_finish(RadauFinishArgs g) {
         is[kRadExitIter] = k_iter;
         if (flag == 0) {
             g.enorm[2 * sc] = g.enorm[2 * sc + 1]; g.enorm[2 * sc + 1] = err;
-            g.t[sc] = g.t[sc] + h;
+            const double tn = g.t[sc] + h;
+            g.t[sc] = tn;
             st[kRadHTaken] = h;
             is[kRadExit] = 0; is[kRadPhase] = 0;
+            if (END) {
+                bool park = g.t_final && g.t_final[sc] < tn;      // strict, as the reference's `while !(t_final < t)`
+                if (g.max_rows > 0) {
+                    const int row = g.rows[sc];
+                    if (row < g.max_rows) {
+                        g.traj[((size_t)sc * (size_t)g.max_rows + (size_t)row) * (size_t)(1 + n)] = tn;
+                        g.rows[sc] = row + 1;
+                    }
+                    if (row + 1 >= g.max_rows) park = true;
+                }
+                if (park) is[kRadIntSpare] = 1; else atomicAdd(g.live, 1);
+            }
         } else if (h_new < g.h_min) {
             is[kRadExit] = 5; is[kRadPhase] = 0;      // "time step is too small, something is wrong": x and t stay
         } else {
@@ -507,6 +544,28 @@ __global__ void __launch_bounds__(kRadWave) k_radau_finish(RadauFinishArgs g) {
             is[kRadIter] = 1; is[kRadKIter] = 0; is[kRadFlag] = -1; is[kRadAttempts] = attempts + 1;
             st[kRadRes1] = inf; st[kRadRes2] = inf;
             atomicAdd(g.count, 1);
+        }
+    }
+}
+
+// ---- the end-setting call: row 0 of every scene's trajectory = its (t, x) now, one row counted, no scene parked -------------------
+struct RadauSetEndArgs {
+    int n_scene, nx, max_rows;              // max_rows = 0: no trajectory (traj and rows may be NULL)
+    const double *x, *t;                    // n_scene x nx; n_scene
+    double *traj;                           // n_scene x max_rows x (1 + nx)
+    int *rows;                              // n_scene
+    int *istate;                            // n_scene x 8: kRadIntSpare <- 0
+};
+
+__global__ void __launch_bounds__(kRadBlock) k_radau_set_end(RadauSetEndArgs g) {
+    const size_t w = (size_t)(1 + g.nx), total = (size_t)g.n_scene * w;
+    for (size_t e = (size_t)blockIdx.x * kRadBlock + threadIdx.x; e < total; e += (size_t)gridDim.x * kRadBlock) {
+        const size_t s = e / w;
+        const int c = (int)(e % w);
+        if (g.max_rows > 0) g.traj[s * (size_t)g.max_rows * w + (size_t)c] = c == 0 ? g.t[s] : g.x[s * (size_t)g.nx + (size_t)(c - 1)];
+        if (c == 0) {
+            if (g.rows) g.rows[s] = g.max_rows > 0 ? 1 : 0;
+            g.istate[8 * s + kRadIntSpare] = 0;
         }
     }
 }

@@ -1242,6 +1242,56 @@ class MechanismScenario:
             x, t = self.radau_get_state()
         return x, t, steps
 
+    def radau_set_end(self, t_final=None, max_rows: int = 0):
+        """pfc_radau_set_end: an end time per scene ((n_scene,) or a scalar; None: +inf) and the rows each scene may record (0:
+        none, else >= 2).  Row 0 of every trajectory is the state now; a scene parks at the commit that leaves t_final < t or fills its
+        last row, and radau_step reports flag 6 for it afterwards."""
+        n = getattr(self, "_radau_n_scene", 0)      # 0: not configured, the library says so
+        t_a = None if t_final is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t_final, dtype=np.float64), (n,)))
+        self._check(_lib.lib().pfc_radau_set_end(self._h, None if t_a is None else t_a.ctypes.data_as(_dp), int(max_rows)))
+
+    def radau_integrate(self, max_steps: int):
+        """pfc_radau_integrate: batch steps until no scene is live or max_steps were taken, the trajectory recorded on the device and
+        nothing but counts read back per step.  Returns (steps_done, n_live)."""
+        steps, live = C.c_int(0), C.c_int(0)
+        self._check(_lib.lib().pfc_radau_integrate(self._h, int(max_steps), C.byref(steps), C.byref(live)))
+        return steps.value, live.value
+
+    def radau_trajectory_rows(self):
+        """The rows recorded per scene since radau_set_end ((n_scene,) int32)."""
+        rows = np.zeros(getattr(self, "_radau_n_scene", 0), dtype=np.int32)
+        self._check(_lib.lib().pfc_radau_trajectory_rows(self._h, rows.ctypes.data_as(_ip)))
+        return rows
+
+    def radau_trajectory(self, scene: int, rows: Optional[int] = None):
+        """(data_time (rows,), data_state (rows, NX)) of a scene: row 0 is the state at radau_set_end, then one row per committed step.
+        rows: the scene's entry of radau_trajectory_rows() where the caller has it already."""
+        if rows is None:
+            rows = self.radau_trajectory_rows()[int(scene)] if 0 <= int(scene) < getattr(self, "_radau_n_scene", 0) else 0
+        n = int(rows)
+        nx = self.radau_sizes()[0]
+        t = np.zeros(n); x = np.zeros((n, nx))
+        self._check(_lib.lib().pfc_radau_trajectory(self._h, int(scene), 0, n, t.ctypes.data_as(_dp), x.ctypes.data_as(_dp)))
+        return t, x
+
+    def integrate_scenario_radau(self, t_final, max_steps: int = 1000):
+        """The reference's integrate_scenario_radau for every scene of the batch: from the state as it is, each scene steps while
+        t_final < t is false (t_final a scalar or (n_scene,); the last step is not shortened) and for at most max_steps steps.  Returns
+        per scene (data_time, data_state), the reference's return value: the start and every step.  A scene whose step size fell
+        below h_min raises the reference's "time step is too small, something is wrong" (the other scenes were integrated to their
+        ends first)."""
+        n = self._radau_n_scene
+        tf = np.ascontiguousarray(np.broadcast_to(np.asarray(t_final, dtype=np.float64), (n,)))
+        self.radau_set_end(tf, int(max_steps) + 1)
+        self.radau_integrate(int(max_steps))
+        rows = self.radau_trajectory_rows()
+        out = [self.radau_trajectory(s, rows[s]) for s in range(n)]
+        # a scene stops by parking -- past its end, or its rows full -- or by retiring with exit flag 5
+        small = [s for s in range(n) if out[s][0].size < int(max_steps) + 1 and not tf[s] < out[s][0][-1]]
+        if small:
+            raise _lib.PFCError(_lib.ERR_STATE, "time step is too small, something is wrong (scenes %s)" % small)
+        return out
+
     # ---- parts of the Radau IIA step (include/pfc.h, csrc/pfc_radau.h): raw device addresses, asynchronous on `stream` ----------
     # layout = (n_scene, nx, nq, nv, n_ips, br_items): x = [q; v; 6 states per bristle item], br_items the bristle items of a scene.
     @staticmethod
@@ -1295,6 +1345,20 @@ class MechanismScenario:
         a = [d_F, d_xdot0, d_X, d_lu0, d_perm, d_x, d_t, d_h, d_rule, d_cool, d_enorm, d_nstate, d_istate, d_count, stream]
         self._check(_lib.lib().pfc_radau_finish_device(self._h, *head, int(m_a.size), m_a.ctypes.data_as(_ip), p_a.ctypes.data_as(_dp),
                                                        int(k_iter_max), int(max_rule), int(cooldown), *[p or None for p in a]))
+
+    def radau_finish_end_device(self, layout, mrp_off, params, k_iter_max: int, max_rule: int, cooldown: int, d_F: int, d_xdot0: int,
+                                d_X: int, d_lu0: int, d_perm: int, d_x: int, d_t: int, d_h: int, d_rule: int, d_cool: int, d_enorm: int,
+                                d_nstate: int, d_istate: int, d_count: int, d_t_final: int, d_traj: int, d_rows: int, max_rows: int,
+                                d_live: int, stream: int = 0):
+        """pfc_radau_finish_end_device: radau_finish_device with ends -- a commit appends the row (t, x) to the scene's trajectory,
+        parks the scene past d_t_final (0: +inf) or on its last row, and counts the scenes that go on in *d_live (not zeroed)."""
+        head, keep = self._radau_layout(layout)
+        m_a = np.ascontiguousarray(mrp_off, dtype=np.int32).reshape(-1)
+        p_a = np.ascontiguousarray(params, dtype=np.float64).reshape(4)
+        a = [d_F, d_xdot0, d_X, d_lu0, d_perm, d_x, d_t, d_h, d_rule, d_cool, d_enorm, d_nstate, d_istate, d_count, d_t_final, d_traj, d_rows]
+        self._check(_lib.lib().pfc_radau_finish_end_device(self._h, *head, int(m_a.size), m_a.ctypes.data_as(_ip), p_a.ctypes.data_as(_dp),
+                                                           int(k_iter_max), int(max_rule), int(cooldown), *[p or None for p in a],
+                                                           int(max_rows), d_live or None, stream or None))
 
     def dual_seeds_from_bodies(self, x_w_b, twist_w_b, d_x_w_b, d_twist_w_b, ins_ids: Optional[Sequence[int]] = None,
                                scene=None) -> BodySeeds:
