@@ -1080,7 +1080,8 @@ int pfc_radau_get_state(pfc_handle h, double *x, double *t);      /* either may 
  * in place of the reset values -- a restart from pfc_radau_rule_state's figures, or scenes that start at different h.
  * PFC_ERR_BAD_ARG, and nothing is changed, for an h that is not finite and > 0, a rule or a cooldown out of range. */
 int pfc_radau_set_rule_state(pfc_handle h, const double *h_scene, const int *rule, const int *cooldown);
-/* tau (n_scene x nv, host; NULL: zeros), held constant over a step; its partials are zero. */
+/* tau (n_scene x nv, host; NULL: zeros), held constant over a step; its partials are zero.  With a controller set
+ * (pfc_radau_set_controller) the value of a scene lasts until the controller first fires for it: a fire overwrites all nv entries. */
 int pfc_radau_set_tau(pfc_handle h, const double *tau);
 /*
  * One step of every scene that is not retired; synchronous.  The Jacobian chunks (seed, pfc_state_derivative_dual_device then _more,
@@ -1116,7 +1117,8 @@ int pfc_radau_step(pfc_handle h, double *h_taken, int *flags, int *iters, int *a
  * recorded) -- until no scene is live (neither retired nor parked) or max_steps (>= 0) steps were taken; *steps_done and *n_live (either
  * may be NULL) are the batch steps taken and the scenes live afterwards.  Per batch step the host reads one word per Newton pass and
  * two per finish (the scenes armed again; the scenes live); neither the records nor x are copied.  tau stays what pfc_radau_set_tau
- * set: a caller with a controller integrates one batch step at a time.
+ * set unless pfc_radau_set_controller gave a controller (below), which then runs at the top of every batch step on the device; a
+ * caller with any other control law integrates one batch step at a time.
  * pfc_radau_trajectory_rows: the rows written per scene (n_scene ints, host).  pfc_radau_trajectory: rows [row0, row0 + n) of a scene
  * into t (n) and x (n x NX) (host; either may be NULL); PFC_ERR_BAD_ARG, nothing written, for a scene or a range outside what was
  * recorded; PFC_ERR_STATE for either call before pfc_radau_set_end.
@@ -1195,6 +1197,73 @@ int pfc_radau_finish_end_device(pfc_handle h, int n_scene, int nx, int nq, int n
                                 const double *d_lu0, const int *d_perm, double *d_x, double *d_t, double *d_h, int *d_rule, int *d_cool,
                                 double *d_enorm, double *d_nstate, int *d_istate, int *d_count, const double *d_t_final, double *d_traj,
                                 int *d_rows, int max_rows, int *d_live, void *stream);
+
+/*
+ * The discrete controller: the reference's DiscreteControl (src/example_integrator.jl:25-30, `while ctrl.t_last <= t: ctrl.t_last +=
+ * ctrl.dt; ctrl.control(x, mech_scen, t)` before every step) with a joint-space law that needs nothing but what the device holds at
+ * the committed state: a computed-torque PD law with a clamp, a feed-forward torque and setpoints on a time schedule (the law of the
+ * reference's test/pencil.jl, tau_ext[act] = H[act,act] qdd_des + c[act], with the schedule fixed in advance).  Zero-order hold: tau
+ * changes only when the controller fires.
+ * The law.  Plain Float64, no fma, in the written order; per scene, nv <= PFC_MAX_NV_SOLVE.  Coordinate i is an offset in q and in v
+ * alike (they coincide for the four joint types: fixed 0 / 0, revolute 1 / 1, prismatic 1 / 1, MRP-floating 6 / 6).
+ *   n_act >= 0 actuated coordinates act[0 .. n_act), strictly increasing; per actuated coordinate kp, kd and a_max (> 0; +inf: no
+ *   clamp); dt, finite and > 0; per scene t_last and a schedule of n_seg >= 1 segments: seg_t (n_scene x n_seg) the start times,
+ *   non-decreasing from index 1, entry 0 is not read; seg_q (n_scene x n_seg x n_act) the setpoints; seg_ff (n_scene x n_seg x nv) a
+ *   feed-forward torque on every coordinate (NULL: zeros).
+ *   fires = 0; while t_last <= t and fires < PFC_RADAU_MAX_FIRES: t_last = t_last + dt, fires += 1   (repeated additions, as in the
+ *   reference, so the bits of t_last are the reference's).  The bound: a scene that is still due after PFC_RADAU_MAX_FIRES additions
+ *   is treated as any scene that fired -- the law below, t_last as far as it got, the counter += PFC_RADAU_MAX_FIRES -- and is due
+ *   again at the next call, where it goes on catching up (a dt below the spacing of t_last's neighbours never catches up: t_last +
+ *   dt = t_last; the loop still ends).
+ *   fires = 0: nothing of the scene is written -- tau stays byte for byte.  Otherwise, once (the law has no memory):
+ *     k = the number of j in 1 .. n_seg - 1 with seg_t[j] <= t
+ *     for every actuated a: e_a = q_a - seg_q[k][a];  acc_a = (-(kd_a v_a)) - kp_a e_a;  if acc_a < -a_max_a: acc_a = -a_max_a;
+ *       if acc_a > a_max_a: acc_a = a_max_a   (a NaN passes)
+ *     tau_a = ((..((0 + H[a,b_0] acc_b_0) + H[a,b_1] acc_b_1) ..) + c_a) + ff[k][a], b over act in increasing order
+ *     tau_i = ff[k][i] for a coordinate that is not actuated
+ *   H (row-major) and c are pfc_dynamics_device's outputs at (q, v).  The partials of tau stay zero: the reference's m.tau_ext is a
+ *   Float64.
+ * pfc_radau_control_device: the part on caller buffers and a caller stream (NULL: the handle's), asynchronous, like the other parts;
+ * it reads nothing of the handle but its device and stream.  d_act (n_act ints), d_kp, d_kd, d_a_max (n_act), d_seg_t, d_seg_q,
+ * d_seg_ff (or NULL) as above; d_t (n_scene), d_q (n_scene x nq), d_v (n_scene x nv), d_H (n_scene x nv x nv), d_c (n_scene x nv);
+ * d_istate (n_scene x 8, pfc_radau_newton_device's records, or NULL: every scene is eligible): a scene whose step exit flag is 5 or
+ * whose parked mark is set is left alone; in/out d_t_last (n_scene), d_fires (n_scene, the additions accumulate), d_tau (3 n_scene x
+ * nv: the scene's rows scene, n_scene + scene and 2 n_scene + scene get the same tau).  The coordinates cannot be validated here
+ * (they are device memory): the caller guarantees 0 <= act[b] < min(nq, nv), increasing.  One launch of n_scene one-wave workgroups.
+ * PFC_ERR_BAD_ARG: nv outside 1 .. PFC_MAX_NV_SOLVE, nq outside 1 .. 64, n_act outside 0 .. min(nq, nv), n_seg < 1, dt not finite
+ * and > 0, null buffer.
+ */
+#define PFC_RADAU_MAX_FIRES 4096
+int pfc_radau_control_device(pfc_handle h, int n_scene, int nq, int nv, int n_act, int n_seg, double dt, const int *d_act,
+                             const double *d_kp, const double *d_kd, const double *d_a_max, const double *d_seg_t, const double *d_seg_q,
+                             const double *d_seg_ff, const double *d_t, const double *d_q, const double *d_v, const double *d_H,
+                             const double *d_c, const int *d_istate, double *d_t_last, int *d_fires, double *d_tau, void *stream);
+/*
+ * pfc_radau_set_controller: the law and the schedules of the handle's batch (host arrays, sizes as above with the handle's n_scene
+ * and nv; a_max NULL: +inf; seg_ff NULL: zeros; t_last0 (n_scene) NULL: every scene's current t -- the reference's constructor gives
+ * 0.0 and starts at t = 0), copied into device blocks owned by the handle.  After pfc_radau_configure (PFC_ERR_STATE before it).
+ * From then on every batch step of pfc_radau_step and pfc_radau_integrate begins, for the scenes that are neither retired (flag 5)
+ * nor parked, with pfc_kinematics_device and pfc_dynamics_device (H and c) at the committed state and the law above; the step reads
+ * tau from the device and no word is read back for it.  The attempts of one batch step share the tau of its start: the reference
+ * retries inside solveRadau.  Once a controller has fired for a scene it has overwritten all nv entries of its tau, so
+ * pfc_radau_set_tau only matters until the first fire (and for scenes that never fire).
+ * n_act = 0 with every pointer NULL and n_seg = 0 clears the controller: the step is the step without one again -- not one launch
+ * more --, with tau what pfc_radau_set_tau last set: the controller's last values if that was an array, zeros if it was NULL or never
+ * called.
+ * PFC_ERR_BAD_ARG, with a message and nothing changed: a coordinate out of range, not increasing, or owned by a floating or fixed
+ * joint; a gain that is not finite; an a_max that is not > 0 (NaN included); dt not finite and > 0, or so small that a step of h_max
+ * needs more than PFC_RADAU_MAX_FIRES additions (dt PFC_RADAU_MAX_FIRES < h_max); n_seg < 1; start times that decrease from index 1 or
+ * are NaN; setpoints, feed-forward or t_last0 that are not finite.  The new blocks are allocated before the old ones are freed:
+ * PFC_ERR_NOMEM leaves the previous controller in force.  pfc_radau_configure drops the controller.  pfc_radau_set_state keeps law
+ * and schedule and sets every scene's t_last to its t_last0 (or its new t) and its counter to 0; a controller set before the first
+ * pfc_radau_set_state takes t = 0 where t_last0 is NULL until then.
+ * pfc_radau_controller_state: t_last and the additions counted per scene (n_scene each, host; either may be NULL), for tests and
+ * restarts; PFC_ERR_STATE without a controller.  Multi-device handles use their first device, as the step does.
+ */
+int pfc_radau_set_controller(pfc_handle h, int n_act, const int *act, const double *kp, const double *kd, const double *a_max, double dt,
+                             const double *t_last0, int n_seg, const double *seg_t, const double *seg_q, const double *seg_ff);
+int pfc_radau_clear_controller(pfc_handle h);      /* pfc_radau_set_controller's clearing form */
+int pfc_radau_controller_state(pfc_handle h, double *t_last, int *fires);
 
 #ifdef __cplusplus
 }

@@ -139,6 +139,10 @@ SIGNATURES = {
     "pfc_radau_integrate": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip]),
     "pfc_radau_trajectory_rows": (C.c_int, [C.c_void_p, _ip]),
     "pfc_radau_trajectory": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp]),
+    "pfc_radau_control_device": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_void_p] * 17),
+    "pfc_radau_set_controller": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp, _dp, C.c_double, _dp, C.c_int, _dp, _dp, _dp]),
+    "pfc_radau_clear_controller": (C.c_int, [C.c_void_p]),
+    "pfc_radau_controller_state": (C.c_int, [C.c_void_p, _dp, _ip]),
 }
 
 

@@ -651,6 +651,19 @@ struct pfc_context {
         int max_rows = 0;
         DevBuf<double> traj;
         void drop_end() { has_end = false; max_rows = 0; traj.release(); }
+        // pfc_radau_set_controller: law, schedules, t_last (cdbl, parts RadauCD) and act, the counters (citg, parts RadauCI) in two
+        // blocks of their own, replaced by the next pfc_radau_set_controller and freed by its clearing form, pfc_radau_configure and
+        // with the handle.  t_last0 stays on the host for pfc_radau_set_state.
+        struct Control {
+            bool on = false, has_ff = false, has_t0 = false;
+            int n_act = 0, n_seg = 0;
+            double dt = 0;
+            DevBuf<double> cdbl;
+            DevBuf<int> citg;
+            size_t od[8] = {0}, oi[2] = {0};
+            std::vector<double> t_last0;
+        } ctl;
+        void drop_control() { ctl = Control(); }
     } radau;
 };
 
@@ -5112,6 +5125,9 @@ enum RadauD { RD_X, RD_T, RD_H, RD_ENORM, RD_NSTATE, RD_XS, RD_FS, RD_XDOT0, RD_
               RD_DDC, RD_DDVD, RD_TFINAL, RD_N };
 // RI_COUNT has two words: the count a newton or finish part returns, and the scenes live after a batch step (k_radau_finish<true>).
 enum RadauI { RI_RULE, RI_COOL, RI_ISTATE, RI_PERM, RI_INFO, RI_COUNT, RI_VINS, RI_VSC, RI_VB1, RI_VB2, RI_VCNT, RI_VINFO, RI_ROWS, RI_N };
+// Parts of the controller's two blocks (pfc_radau_set_controller).
+enum RadauCD { CD_KP, CD_KD, CD_AMAX, CD_SEGT, CD_SEGQ, CD_SEGFF, CD_TLAST, CD_N };
+enum RadauCI { CI_ACT, CI_FIRES, CI_N };
 
 static int radau_configure_ctx(pfc_context *c, int n_scene, int n_ips, const int *ins_ids, const double *params, int k_iter_max,
                                int max_rule, int n_chunk, int cooldown) {
@@ -5175,6 +5191,7 @@ static int radau_configure_ctx(pfc_context *c, int n_scene, int n_ips, const int
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     R.drop_end();
+    R.drop_control();
     HIP_TRY(c, R.dbl.ensure(td));
     HIP_TRY(c, R.itg.ensure(ti));
     HIP_TRY(c, hipMemset(R.dbl.p, 0, sizeof(double) * td));
@@ -5248,6 +5265,12 @@ int pfc_radau_set_state(pfc_handle h, const double *x, const double *t) {
         HIP_TRY(c, hipMemcpy(I + R.oi[RI_COOL], cool.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
         HIP_TRY(c, hipMemcpy(I + R.oi[RI_ISTATE], ist.data(), sizeof(int) * 8 * ns, hipMemcpyHostToDevice));
         R.drop_end();      // no scene is parked, and an end that was set is gone with the trajectory that started at the old state
+        if (R.ctl.on) {    // law and schedule stay; the controller's clock starts again
+            const std::vector<int> zero(ns, 0);
+            HIP_TRY(c, hipMemcpy(R.ctl.cdbl.p + R.ctl.od[CD_TLAST], R.ctl.has_t0 ? R.ctl.t_last0.data() : tt.data(), sizeof(double) * ns,
+                                 hipMemcpyHostToDevice));
+            HIP_TRY(c, hipMemcpy(R.ctl.citg.p + R.ctl.oi[CI_FIRES], zero.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
+        }
         R.has_state = true;
         return (int)PFC_OK; });
 }
@@ -5295,6 +5318,11 @@ int pfc_radau_set_tau(pfc_handle h, const double *tau) {
         pfc_context::RadauHost &R = c->radau;
         const size_t ns = (size_t)R.L.n_scene, nv = (size_t)R.L.nv;
         R.has_tau = tau != nullptr && nv > 0;
+        if (!R.has_tau && R.ctl.on) {      // with a controller the step reads RD_TAU: NULL means zeros there as well
+            HIP_TRY(c, hipSetDevice(c->device));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            HIP_TRY(c, hipMemset(R.dbl.p + R.od[RD_TAU], 0, sizeof(double) * 3 * ns * nv));
+        }
         if (!R.has_tau) return (int)PFC_OK;
         for (size_t e = 0; e < ns * nv; ++e)
             if (!std::isfinite(tau[e])) return fail(c, PFC_ERR_NONFINITE, "pfc_radau_set_tau: tau of scene %zu is not finite", e / nv);
@@ -5330,6 +5358,184 @@ int pfc_radau_rule_state(pfc_handle h, double *out7) {
         return (int)PFC_OK; });
 }
 
+// ---- the discrete controller (k_radau_control; the statement: include/pfc.h) ---------------------------------------------------------
+static_assert(PFC_RADAU_MAX_FIRES == kRadMaxFires, "the bound of k_radau_control's t_last loop");
+
+static int radau_control_launch(pfc_context *h, const char *who, int n_scene, int nq, int nv, int n_act, int n_seg, double dt,
+                                const int *d_act, const double *d_kp, const double *d_kd, const double *d_a_max, const double *d_seg_t,
+                                const double *d_seg_q, const double *d_seg_ff, const double *d_t, const double *d_q, const double *d_v,
+                                const double *d_H, const double *d_c, const int *d_istate, double *d_t_last, int *d_fires, double *d_tau,
+                                hipStream_t st) {
+    if (n_scene < 0) return fail(h, PFC_ERR_BAD_ARG, "%s: negative n_scene", who);
+    if (nv < 1 || nv > PFC_MAX_NV_SOLVE || nq < 1 || nq > kRadWave)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: nv is %d and nq %d, the law takes 1 .. PFC_MAX_NV_SOLVE = %d coordinates", who, nv, nq, PFC_MAX_NV_SOLVE);
+    if (n_act < 0 || n_act > std::min(nq, nv)) return fail(h, PFC_ERR_BAD_ARG, "%s: n_act is %d, 0 .. min(nq, nv) = %d", who, n_act, std::min(nq, nv));
+    if (n_seg < 1) return fail(h, PFC_ERR_BAD_ARG, "%s: n_seg is %d, at least one segment", who, n_seg);
+    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(h, PFC_ERR_BAD_ARG, "%s: dt is %.17g, finite and > 0", who, dt);
+    if (n_scene == 0) return PFC_OK;
+    if ((n_act > 0 && (!d_act || !d_kp || !d_kd || !d_a_max || !d_seg_q || !d_q || !d_H || !d_c)) || (n_seg > 1 && !d_seg_t) || !d_t ||
+        !d_v || !d_t_last || !d_fires || !d_tau)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    RadauControlArgs a;
+    a.n_scene = n_scene; a.nq = nq; a.nv = nv; a.n_act = n_act; a.n_seg = n_seg; a.dt = dt;
+    a.act = d_act; a.kp = d_kp; a.kd = d_kd; a.a_max = d_a_max; a.seg_t = d_seg_t; a.seg_q = d_seg_q; a.seg_ff = d_seg_ff;
+    a.t = d_t; a.q = d_q; a.v = d_v; a.H = d_H; a.c = d_c; a.istate = d_istate; a.t_last = d_t_last; a.fires = d_fires; a.tau = d_tau;
+    hipLaunchKernelGGL(k_radau_control, dim3((unsigned)n_scene), dim3(kRadWave), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+int pfc_radau_control_device(pfc_handle h, int n_scene, int nq, int nv, int n_act, int n_seg, double dt, const int *d_act,
+                             const double *d_kp, const double *d_kd, const double *d_a_max, const double *d_seg_t, const double *d_seg_q,
+                             const double *d_seg_ff, const double *d_t, const double *d_q, const double *d_v, const double *d_H,
+                             const double *d_c, const int *d_istate, double *d_t_last, int *d_fires, double *d_tau, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+        return radau_control_launch(c, "pfc_radau_control_device", n_scene, nq, nv, n_act, n_seg, dt, d_act, d_kp, d_kd, d_a_max, d_seg_t,
+                                    d_seg_q, d_seg_ff, d_t, d_q, d_v, d_H, d_c, d_istate, d_t_last, d_fires, d_tau,
+                                    stream ? (hipStream_t)stream : c->stream); });
+}
+
+// tau lives in RD_TAU while a controller is set; without pfc_radau_set_tau's array the block must read as zeros.
+static int radau_zero_tau_unless_set(pfc_context *c) {
+    pfc_context::RadauHost &R = c->radau;
+    if (R.has_tau) return PFC_OK;
+    HIP_TRY(c, hipMemset(R.dbl.p + R.od[RD_TAU], 0, sizeof(double) * 3 * (size_t)R.L.n_scene * (size_t)R.L.nv));
+    return PFC_OK;
+}
+
+static int radau_set_controller_ctx(pfc_context *c, int n_act, const int *act, const double *kp, const double *kd, const double *a_max,
+                                    double dt, const double *t_last0, int n_seg, const double *seg_t, const double *seg_q,
+                                    const double *seg_ff) {
+    const char *who = "pfc_radau_set_controller";
+    int rc = radau_need(c, who, false);
+    if (rc != PFC_OK) return rc;
+    pfc_context::RadauHost &R = c->radau;
+    const KinHost &K = c->kin;
+    const size_t ns = (size_t)R.L.n_scene, nv = (size_t)R.L.nv;
+    if (n_act == 0 && n_seg == 0 && !act && !kp && !kd && !a_max && !t_last0 && !seg_t && !seg_q && !seg_ff) {      // the clearing form
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        R.drop_control();
+        return radau_zero_tau_unless_set(c);
+    }
+    if (R.L.nv < 1 || R.L.nq != R.L.nv)
+        return fail(c, PFC_ERR_BAD_ARG, "%s: the mechanism has nq = %d and nv = %d: the law needs coordinates, the same in q and v", who, R.L.nq, R.L.nv);
+    if (n_act < 0 || n_act > R.L.nv || (n_act > 0 && (!act || !kp || !kd || !seg_q)))
+        return fail(c, PFC_ERR_BAD_ARG, "%s: n_act is %d (0 .. nv = %d) with act, kp, kd and seg_q given", who, n_act, R.L.nv);
+    if (n_seg < 1 || (n_seg > 1 && !seg_t)) return fail(c, PFC_ERR_BAD_ARG, "%s: n_seg is %d: at least one segment, with its start times", who, n_seg);
+    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(c, PFC_ERR_BAD_ARG, "%s: dt is %.17g, finite and > 0", who, dt);
+    if (dt * (double)PFC_RADAU_MAX_FIRES < R.fin[2])
+        return fail(c, PFC_ERR_BAD_ARG, "%s: dt is %.17g: a step of h_max = %.17g would need more than PFC_RADAU_MAX_FIRES = %d additions", who,
+                    dt, R.fin[2], PFC_RADAU_MAX_FIRES);
+    // the joint that owns a coordinate: revolute and prismatic joints own one, at the same offset in q and v
+    std::vector<int> owner(nv, PFC_JOINT_FIXED);
+    const int *jtype = (const int *)(K.blob.data() + K.o_jtype), *qoff = (const int *)(K.blob.data() + K.o_qoff);
+    const int *voff = (const int *)(K.blob.data() + K.o_voff);
+    for (int b = 0; b < K.n_body; ++b) {
+        const int w = jtype[b] == PFC_JOINT_FLOATING_MRP ? 6 : jtype[b] == PFC_JOINT_FIXED ? 0 : 1;
+        for (int k = 0; k < w && voff[b] + k < (int)nv; ++k) owner[voff[b] + k] = qoff[b] == voff[b] ? jtype[b] : PFC_JOINT_FIXED;
+    }
+    for (int a = 0; a < n_act; ++a) {
+        if (act[a] < 0 || act[a] >= (int)nv || (a > 0 && act[a] <= act[a - 1]))
+            return fail(c, PFC_ERR_BAD_ARG, "%s: actuated coordinate %d is %d: strictly increasing and below nv = %d", who, a, act[a], (int)nv);
+        if (owner[act[a]] != PFC_JOINT_REVOLUTE && owner[act[a]] != PFC_JOINT_PRISMATIC)
+            return fail(c, PFC_ERR_BAD_ARG, "%s: actuated coordinate %d belongs to a floating or fixed joint: revolute and prismatic only", who, act[a]);
+        if (!std::isfinite(kp[a]) || !std::isfinite(kd[a])) return fail(c, PFC_ERR_BAD_ARG, "%s: gain of coordinate %d is not finite", who, act[a]);
+        if (a_max && !(a_max[a] > 0.0)) return fail(c, PFC_ERR_BAD_ARG, "%s: a_max of coordinate %d is %.17g, not > 0", who, act[a], a_max[a]);
+    }
+    const size_t sg = (size_t)n_seg, na = (size_t)n_act;
+    for (size_t s = 0; s < ns; ++s) {
+        for (size_t j = 1; j < sg; ++j) {
+            const double a = seg_t[s * sg + j];
+            if (a != a || (j > 1 && a < seg_t[s * sg + j - 1]))
+                return fail(c, PFC_ERR_BAD_ARG, "%s: start time %zu of scene %zu is %.17g: the start times must not decrease", who, j, s, a);
+        }
+        for (size_t e = 0; e < sg * na; ++e)
+            if (!std::isfinite(seg_q[s * sg * na + e])) return fail(c, PFC_ERR_BAD_ARG, "%s: a setpoint of scene %zu is not finite", who, s);
+        for (size_t e = 0; seg_ff && e < sg * nv; ++e)
+            if (!std::isfinite(seg_ff[s * sg * nv + e])) return fail(c, PFC_ERR_BAD_ARG, "%s: a feed-forward torque of scene %zu is not finite", who, s);
+        if (t_last0 && !std::isfinite(t_last0[s])) return fail(c, PFC_ERR_BAD_ARG, "%s: t_last0 of scene %zu is not finite", who, s);
+    }
+    pfc_context::RadauHost::Control N;
+    size_t sd[CD_N], si[CI_N], td = 0, ti = 0;
+    sd[CD_KP] = na; sd[CD_KD] = na; sd[CD_AMAX] = na; sd[CD_SEGT] = ns * sg; sd[CD_SEGQ] = ns * sg * na; sd[CD_SEGFF] = seg_ff ? ns * sg * nv : 0;
+    sd[CD_TLAST] = ns; si[CI_ACT] = na; si[CI_FIRES] = ns;
+    for (int k = 0; k < CD_N; ++k) { N.od[k] = td; td += sd[k]; }
+    for (int k = 0; k < CI_N; ++k) { N.oi[k] = ti; ti += si[k]; }
+    std::vector<double> hd(td, 0.0);
+    std::vector<int> hi(ti, 0);
+    const double inf = std::numeric_limits<double>::infinity();
+    for (size_t a = 0; a < na; ++a) {
+        hd[N.od[CD_KP] + a] = kp[a]; hd[N.od[CD_KD] + a] = kd[a]; hd[N.od[CD_AMAX] + a] = a_max ? a_max[a] : inf;
+        hi[N.oi[CI_ACT] + a] = act[a];
+    }
+    for (size_t s = 0; s < ns; ++s)
+        for (size_t j = 1; j < sg; ++j) hd[N.od[CD_SEGT] + s * sg + j] = seg_t[s * sg + j];      // entry 0 is not read: +0.0
+    if (na) std::memcpy(hd.data() + N.od[CD_SEGQ], seg_q, sizeof(double) * ns * sg * na);
+    if (seg_ff) std::memcpy(hd.data() + N.od[CD_SEGFF], seg_ff, sizeof(double) * ns * sg * nv);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (t_last0) std::memcpy(hd.data() + N.od[CD_TLAST], t_last0, sizeof(double) * ns);
+    else if (R.has_state) HIP_TRY(c, hipMemcpy(hd.data() + N.od[CD_TLAST], R.dbl.p + R.od[RD_T], sizeof(double) * ns, hipMemcpyDeviceToHost));
+    // the new blocks first: if they cannot be had, the previous controller stays in force
+    if (N.cdbl.ensure(td) != hipSuccess || N.citg.ensure(ti) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, PFC_ERR_NOMEM, "%s: no device memory for %zu doubles and %zu ints", who, td, ti);
+    }
+    HIP_TRY(c, hipMemcpy(N.cdbl.p, hd.data(), sizeof(double) * td, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(N.citg.p, hi.data(), sizeof(int) * ti, hipMemcpyHostToDevice));
+    N.on = true; N.has_ff = seg_ff != nullptr; N.has_t0 = t_last0 != nullptr; N.n_act = n_act; N.n_seg = n_seg; N.dt = dt;
+    if (t_last0) N.t_last0.assign(t_last0, t_last0 + ns);
+    R.ctl = std::move(N);
+    return radau_zero_tau_unless_set(c);
+}
+
+int pfc_radau_set_controller(pfc_handle h, int n_act, const int *act, const double *kp, const double *kd, const double *a_max, double dt,
+                             const double *t_last0, int n_seg, const double *seg_t, const double *seg_q, const double *seg_ff) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+        return radau_set_controller_ctx(c, n_act, act, kp, kd, a_max, dt, t_last0, n_seg, seg_t, seg_q, seg_ff); });
+}
+
+int pfc_radau_clear_controller(pfc_handle h) {
+    return pfc_radau_set_controller(h, 0, nullptr, nullptr, nullptr, nullptr, 0.0, nullptr, 0, nullptr, nullptr, nullptr);
+}
+
+int pfc_radau_controller_state(pfc_handle h, double *t_last, int *fires) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+        const char *who = "pfc_radau_controller_state";
+        const int rc = radau_need(c, who, false);
+        if (rc != PFC_OK) return rc;
+        pfc_context::RadauHost &R = c->radau;
+        if (!R.ctl.on) return fail(c, PFC_ERR_STATE, "%s without a controller (pfc_radau_set_controller)", who);
+        const size_t ns = (size_t)R.L.n_scene;
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (t_last) HIP_TRY(c, hipMemcpy(t_last, R.ctl.cdbl.p + R.ctl.od[CD_TLAST], sizeof(double) * ns, hipMemcpyDeviceToHost));
+        if (fires) HIP_TRY(c, hipMemcpy(fires, R.ctl.citg.p + R.ctl.oi[CI_FIRES], sizeof(int) * ns, hipMemcpyDeviceToHost));
+        return (int)PFC_OK; });
+}
+
+// The controller at the top of a batch step: H and c at the committed state -- the first n_scene stage-scenes hold x0 after the
+// first unpack, and the Jacobian's first chunk overwrites the buffers used here -- then the law into RD_TAU.
+static int radau_control_step(pfc_context *c, const char *who) {
+    pfc_context::RadauHost &R = c->radau;
+    const pfc_context::RadauHost::Control &T = R.ctl;
+    const RadauLayout &L = R.L;
+    auto D = [&](int k) { return R.dbl.p + R.od[k]; };
+    auto CD = [&](int k) { return T.cdbl.p + T.od[k]; };
+    int rc = pfc_kinematics_device(c, L.n_scene, D(RD_VQ), D(RD_VV), D(RD_VXWB), D(RD_VTW), nullptr, nullptr);
+    if (rc != PFC_OK) return rc;
+    rc = pfc_dynamics_device(c, L.n_scene, D(RD_VQ), D(RD_VV), D(RD_VXWB), D(RD_VTW), nullptr, D(RD_VH), D(RD_VC), nullptr);
+    if (rc != PFC_OK) return rc;
+    return radau_control_launch(c, who, L.n_scene, L.nq, L.nv, T.n_act, T.n_seg, T.dt, T.citg.p + T.oi[CI_ACT], CD(CD_KP), CD(CD_KD),
+                                CD(CD_AMAX), CD(CD_SEGT), CD(CD_SEGQ), T.has_ff ? CD(CD_SEGFF) : nullptr, D(RD_T), D(RD_VQ), D(RD_VV),
+                                D(RD_VH), D(RD_VC), R.itg.p + R.oi[RI_ISTATE], CD(CD_TLAST), T.citg.p + T.oi[CI_FIRES], D(RD_TAU), c->stream);
+}
+
 // An evaluation and its pfc_check, re-issued while the work lists grow.
 static int radau_checked(pfc_context *c, const std::function<int()> &issue) {
     for (int k = 0; k < 40; ++k) {
@@ -5358,13 +5564,14 @@ static int radau_step_body(pfc_context *c, const char *who, bool end, int *live)
     const int ns = L.n_scene, n1 = ns * L.n_ips, N3 = 3 * ns, n3 = 3 * n1;
     auto D = [&](int k) { return R.dbl.p + R.od[k]; };
     auto I = [&](int k) { return R.itg.p + R.oi[k]; };
-    const double *tau = R.has_tau ? D(RD_TAU) : nullptr;
+    const double *tau = R.has_tau || R.ctl.on ? D(RD_TAU) : nullptr;
     const int *br = L.br_items;
     auto unpack = [&]() {
         return pfc_radau_unpack_device(c, ns, L.nx, L.nq, L.nv, L.n_ips, L.n_br, br, D(RD_X), I(RI_RULE), I(RI_ISTATE), D(RD_XS), D(RD_VQ),
                                        D(RD_VV), D(RD_VS), nullptr); };
     // calcJacobian!: no scene is iterating, so every stage-scene -- the first n_scene of them are the scenes themselves -- gets x0
     if ((rc = unpack()) != PFC_OK) return rc;
+    if (R.ctl.on && (rc = radau_control_step(c, who)) != PFC_OK) return rc;
     const int n_chunks = (L.nx + R.n_chunk - 1) / R.n_chunk;
     for (int k = 0; k < n_chunks; ++k) {
         const int nd = std::min(R.n_chunk, L.nx - k * R.n_chunk);

@@ -5,7 +5,8 @@
 // around them: seed_indices! (k_radau_seed), write_indices! (k_radau_jac), the stage states into the evaluation's inputs
 // (k_radau_unpack).  pfc_radau_step (pfc_hip.hip) strings them together with the state-derivative calls; pfc_radau_integrate runs
 // the same body to per-scene end times with k_radau_finish<true>, which records the trajectory and parks the scenes that have arrived
-// (k_radau_set_end starts a trajectory).
+// (k_radau_set_end starts a trajectory).  k_radau_control is the zero-order-hold joint controller that runs at the top of a batch
+// step when pfc_radau_set_controller gave one (the reference's DiscreteControl, src/example_integrator.jl:25-30).
 // Included by pfc_hip.hip inside namespace pfc (device code only), after pfc_dyn.h.
 //
 // Arithmetic (the contract, stated in include/pfc.h): plain Float64, every sum in a written order, no fma (the build has
@@ -568,4 +569,71 @@ __global__ void __launch_bounds__(kRadBlock) k_radau_set_end(RadauSetEndArgs g) 
             g.istate[8 * s + kRadIntSpare] = 0;
         }
     }
+}
+
+// ---- the discrete controller: the reference's DiscreteControl loop and a computed-torque PD law, once per batch step -----------------
+// The statement is in include/pfc.h (pfc_radau_control_device).  One wave per scene, lane i = coordinate i (nv <= 64); lane b < n_act
+// also computes the clamped acc of actuated coordinate act[b], which the row sums read with a lane read, b ascending.  The t_last
+// loop and the segment search depend on the scene only: wave-uniform.  Nothing in LDS, no scratch, plain vector stores, no atomics.
+// Every lane stays until the last lane read: the early returns above it are taken by the whole wave.
+// No index is followed out of range: n_scene bounds the grid, nv, nq <= 64, n_act <= nv and act[] < min(nq, nv) are validated on the
+// host, the segment index is a count of at most n_seg - 1 comparisons, lanes >= nv load and store nothing.
+constexpr int kRadMaxFires = 4096;          // PFC_RADAU_MAX_FIRES: additions to t_last per scene and call
+
+struct RadauControlArgs {
+    int n_scene, nq, nv, n_act, n_seg;
+    double dt;
+    const int *act;                         // n_act: the actuated coordinates, strictly increasing, < min(nq, nv)
+    const double *kp, *kd, *a_max;          // n_act
+    const double *seg_t;                    // n_scene x n_seg: entry 0 of a scene is not read
+    const double *seg_q;                    // n_scene x n_seg x n_act
+    const double *seg_ff;                   // n_scene x n_seg x nv, or NULL (zeros)
+    const double *t, *q, *v, *H, *c;        // n_scene; n_scene x nq; x nv; x nv x nv row-major; x nv
+    const int *istate;                      // n_scene x 8, or NULL: a scene with exit flag 5 or the parked mark is left alone
+    double *t_last;                         // n_scene
+    int *fires;                             // n_scene: += the additions to t_last
+    double *tau;                            // 3 n_scene x nv: rows scene, n_scene + scene, 2 n_scene + scene
+};
+
+__global__ void __launch_bounds__(kRadWave) k_radau_control(RadauControlArgs g) {
+    const int sc = (int)blockIdx.x, i = (int)threadIdx.x, nv = g.nv;
+    if (g.istate && (g.istate[8 * (size_t)sc + kRadExit] == 5 || g.istate[8 * (size_t)sc + kRadIntSpare] != 0)) return;
+    const double t = g.t[sc];
+    double t_last = g.t_last[sc];
+    int fires = 0;
+    while (t_last <= t && fires < kRadMaxFires) { t_last = t_last + g.dt; ++fires; }
+    if (fires == 0) return;                 // not due: tau is held
+    const double *st = g.seg_t + (size_t)sc * (size_t)g.n_seg;
+    int k = 0;
+    for (int j = 1; j < g.n_seg; ++j) k += st[j] <= t ? 1 : 0;
+    const size_t seg = (size_t)sc * (size_t)g.n_seg + (size_t)k;
+    double acc = 0.0;
+    if (i < g.n_act) {
+        const int co = g.act[i];
+        const double e = g.q[(size_t)sc * (size_t)g.nq + (size_t)co] - g.seg_q[seg * (size_t)g.n_act + (size_t)i];
+        acc = (-(g.kd[i] * g.v[(size_t)sc * (size_t)nv + (size_t)co])) - g.kp[i] * e;
+        const double am = g.a_max[i];
+        if (acc < -am) acc = -am;
+        if (acc > am) acc = am;
+    }
+    const bool lane = i < nv;
+    const double *Hrow = g.H + ((size_t)sc * (size_t)nv + (size_t)(lane ? i : 0)) * (size_t)nv;
+    const double ff = lane && g.seg_ff ? g.seg_ff[seg * (size_t)nv + (size_t)i] : 0.0;
+    const double ci = lane ? g.c[(size_t)sc * (size_t)nv + (size_t)i] : 0.0;
+    double sum = 0.0;
+    bool actuated = false;
+    for (int b = 0; b < g.n_act; ++b) {
+        const int co = g.act[b];
+        const double ab = rad_lane(acc, b);
+        if (lane) sum = sum + Hrow[co] * ab;
+        actuated = actuated || co == i;
+    }
+    const double tau = actuated ? (sum + ci) + ff : ff;
+    if (lane) {
+        const size_t ns = (size_t)g.n_scene;
+        g.tau[((size_t)sc) * (size_t)nv + (size_t)i] = tau;
+        g.tau[(ns + (size_t)sc) * (size_t)nv + (size_t)i] = tau;
+        g.tau[(2 * ns + (size_t)sc) * (size_t)nv + (size_t)i] = tau;
+    }
+    if (i == 0) { g.t_last[sc] = t_last; g.fires[sc] = g.fires[sc] + fires; }
 }

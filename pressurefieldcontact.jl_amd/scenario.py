@@ -1274,16 +1274,132 @@ class MechanismScenario:
         self._check(_lib.lib().pfc_radau_trajectory(self._h, int(scene), 0, n, t.ctypes.data_as(_dp), x.ctypes.data_as(_dp)))
         return t, x
 
-    def integrate_scenario_radau(self, t_final, max_steps: int = 1000):
+    def radau_set_controller(self, act, kp, kd, dt: float, seg_t, seg_q, seg_ff=None, a_max=None, t_last0=None):
+        """pfc_radau_set_controller: a zero-order-hold computed-torque PD controller that fires on the device at the top of every
+        batch step of radau_step / radau_integrate (the law: computed_torque_pd below, the clock: discrete_clock).  act (n_act,)
+        the actuated coordinates, strictly increasing, each owned by a revolute or prismatic joint; kp, kd, a_max (n_act,) or scalars
+        (a_max None: no clamp); dt the controller's period; seg_t (n_scene, n_seg) or (n_seg,) the segments' start times (entry 0 is
+        not read), seg_q (n_scene, n_seg, n_act) or (n_seg, n_act) the setpoints, seg_ff (n_scene, n_seg, nv) or (n_seg, nv) a
+        feed-forward torque (None: zeros); t_last0 (n_scene,) or a scalar (None: every scene's current t; the reference's constructor
+        gives 0.0).  Once it has fired for a scene, radau_set_tau's value for that scene is overwritten."""
+        n = getattr(self, "_radau_n_scene", 0)
+        nv = self.mechanism_sizes()[2]
+        act_a = np.ascontiguousarray(act, dtype=np.int32).reshape(-1)
+        na = act_a.size
+        vec = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (na,)))
+        kp_a, kd_a = vec(kp), vec(kd)
+        am_a = None if a_max is None else vec(a_max)
+        st = np.asarray(seg_t, dtype=np.float64)
+        n_seg = st.shape[-1] if st.ndim else 1
+        st_a = np.ascontiguousarray(np.broadcast_to(st.reshape(-1, n_seg), (n, n_seg)))
+        sq_a = np.zeros((n, n_seg, 0)) if na == 0 else \
+            np.ascontiguousarray(np.broadcast_to(np.asarray(seg_q, dtype=np.float64).reshape((-1, n_seg, na)), (n, n_seg, na)))
+        ff_a = None if seg_ff is None else np.ascontiguousarray(
+            np.broadcast_to(np.asarray(seg_ff, dtype=np.float64).reshape((-1, n_seg, nv)), (n, n_seg, nv)))
+        t0_a = None if t_last0 is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t_last0, dtype=np.float64), (n,)))
+        p = lambda a: None if a is None else a.ctypes.data_as(_dp)
+        self._check(_lib.lib().pfc_radau_set_controller(self._h, int(na), act_a.ctypes.data_as(_ip), p(kp_a), p(kd_a), p(am_a), float(dt),
+                                                        p(t0_a), int(n_seg), p(st_a), p(sq_a), p(ff_a)))
+
+    def radau_clear_controller(self):
+        """pfc_radau_clear_controller: the step is the step without a controller again."""
+        self._check(_lib.lib().pfc_radau_clear_controller(self._h))
+
+    def radau_controller_state(self):
+        """(t_last (n_scene,), fires (n_scene,) int32) of the device controller: its clock and the additions counted per scene."""
+        n = getattr(self, "_radau_n_scene", 0)
+        t_last = np.zeros(n); fires = np.zeros(n, dtype=np.int32)
+        self._check(_lib.lib().pfc_radau_controller_state(self._h, t_last.ctypes.data_as(_dp), fires.ctypes.data_as(_ip)))
+        return t_last, fires
+
+    def radau_control_device(self, n_scene: int, nq: int, nv: int, n_act: int, n_seg: int, dt: float, d_act: int, d_kp: int, d_kd: int,
+                             d_a_max: int, d_seg_t: int, d_seg_q: int, d_seg_ff: int, d_t: int, d_q: int, d_v: int, d_H: int, d_c: int,
+                             d_istate: int, d_t_last: int, d_fires: int, d_tau: int, stream: int = 0):
+        """pfc_radau_control_device: the controller's part on raw device addresses (0: NULL for d_seg_ff and d_istate); asynchronous
+        on `stream`."""
+        a = [d_act, d_kp, d_kd, d_a_max, d_seg_t, d_seg_q, d_seg_ff, d_t, d_q, d_v, d_H, d_c, d_istate, d_t_last, d_fires, d_tau, stream]
+        self._check(_lib.lib().pfc_radau_control_device(self._h, int(n_scene), int(nq), int(nv), int(n_act), int(n_seg), float(dt),
+                                                        *[x or None for x in a]))
+
+    def computed_torque_pd_fn(self, act, kp, kd, seg_t, seg_q, seg_ff=None, a_max=None):
+        """fn(x, t, scene) -> tau for integrate_scenario_radau(discrete_controller=(fn, dt)): computed_torque_pd on H and c of the
+        host form `dynamics` at the scene's (q, v).  The arrays are radau_set_controller's; a leading scene axis is indexed by
+        `scene`."""
+        _, nq, nv = self.mechanism_sizes()
+        act_l = [int(a) for a in np.asarray(act).reshape(-1)]
+        na = len(act_l)
+        vec = lambda a: [float(e) for e in np.broadcast_to(np.asarray(a, dtype=np.float64), (na,))]
+        kp_l, kd_l = vec(kp), vec(kd)
+        am_l = None if a_max is None else vec(a_max)
+        st = np.asarray(seg_t, dtype=np.float64)
+        n_seg = st.shape[-1] if st.ndim else 1
+        st = st.reshape(-1, n_seg)
+        sq = np.zeros((1, n_seg, 0)) if na == 0 else np.asarray(seg_q, dtype=np.float64).reshape(-1, n_seg, na)
+        ff = None if seg_ff is None else np.asarray(seg_ff, dtype=np.float64).reshape(-1, n_seg, nv)
+        row = lambda a, s: a[s if a.shape[0] > 1 else 0]
+
+        def fn(x, t, scene):
+            q, v = np.asarray(x[:nq], dtype=np.float64), np.asarray(x[nq:nq + nv], dtype=np.float64)
+            _, H, c = self.dynamics(q, v)
+            return computed_torque_pd(q.tolist(), v.tolist(), H[0].tolist(), c[0].tolist(), float(t), act_l, kp_l, kd_l,
+                                      row(st, scene).tolist(), row(sq, scene).tolist(), None if ff is None else row(ff, scene).tolist(), am_l)
+        return fn
+
+    def radau_host_controller_state(self):
+        """(t_last, fires) of the host route's clock after integrate_scenario_radau(discrete_controller=...)."""
+        t_last, fires = self._radau_host_ctl
+        return t_last.copy(), fires.copy()
+
+    def _integrate_with_callback(self, tf, max_steps: int, discrete_controller):
+        """The host route: the reference's loop (src/example_integrator.jl:25-30) per live scene before every batch step -- t_last by
+        repeated addition, fn called at every addition -- then radau_set_tau and one radau_step."""
+        fn, dt = discrete_controller[0], float(discrete_controller[1])
+        n, nv = self._radau_n_scene, self.mechanism_sizes()[2]
+        if not (dt > 0.0 and np.isfinite(dt)):
+            raise ValueError("discrete_controller: dt must be finite and > 0")
+        max_rows = int(max_steps) + 1
+        x, t = self.radau_get_state()
+        t_last = t.copy() if len(discrete_controller) < 3 or discrete_controller[2] is None else \
+            np.array(np.broadcast_to(np.asarray(discrete_controller[2], dtype=np.float64), (n,)))
+        fires = np.zeros(n, dtype=np.int32)
+        tau = np.zeros((n, nv))
+        live = np.ones(n, dtype=bool)
+        fl = np.zeros(n, dtype=np.int32)
+        steps = 0
+        while live.any() and steps < int(max_steps):
+            for s in np.flatnonzero(live):
+                k = 0
+                while t_last[s] <= t[s] and k < RADAU_MAX_FIRES:
+                    t_last[s] = t_last[s] + dt
+                    k += 1
+                    tau[s] = np.asarray(fn(x[s].copy(), float(t[s]), int(s)), dtype=np.float64).reshape(nv)
+                fires[s] += k
+            self.radau_set_tau(tau)
+            self._check(_lib.lib().pfc_radau_step(self._h, None, fl.ctypes.data_as(_ip), None, None))
+            steps += 1
+            x, t = self.radau_get_state()
+            rows = self.radau_trajectory_rows()
+            live = (fl == 0) & ~(tf < t) & (rows < max_rows)      # neither retired (5) nor parked (6, or by this commit)
+        self._radau_host_ctl = (t_last, fires)
+
+    def integrate_scenario_radau(self, t_final, max_steps: int = 1000, discrete_controller=None):
         """The reference's integrate_scenario_radau for every scene of the batch: from the state as it is, each scene steps while
         t_final < t is false (t_final a scalar or (n_scene,); the last step is not shortened) and for at most max_steps steps.  Returns
         per scene (data_time, data_state), the reference's return value: the start and every step.  A scene whose step size fell
         below h_min raises the reference's "time step is too small, something is wrong" (the other scenes were integrated to their
-        ends first)."""
+        ends first).
+        A controller given with radau_set_controller runs on the device inside the loop.  discrete_controller = (fn, dt) or (fn, dt,
+        t_last0) is the reference's general DiscreteControl instead, on the host: before every batch step, for every live scene,
+        `while t_last <= t: t_last += dt; tau[scene] = fn(x, t, scene)` (at most RADAU_MAX_FIRES additions per step), then
+        radau_set_tau and one radau_step -- any Python law, one batch step at a time, x downloaded and tau uploaded per step.  tau
+        starts from zeros; t_last0 None is every scene's t now.  Not to be combined with radau_set_controller."""
         n = self._radau_n_scene
         tf = np.ascontiguousarray(np.broadcast_to(np.asarray(t_final, dtype=np.float64), (n,)))
         self.radau_set_end(tf, int(max_steps) + 1)
-        self.radau_integrate(int(max_steps))
+        if discrete_controller is None:
+            self.radau_integrate(int(max_steps))
+        else:
+            self._integrate_with_callback(tf, int(max_steps), discrete_controller)
         rows = self.radau_trajectory_rows()
         out = [self.radau_trajectory(s, rows[s]) for s in range(n)]
         # a scene stops by parking -- past its end, or its rows full -- or by retiring with exit flag 5
@@ -1608,6 +1724,50 @@ def radau_table(rule: int) -> dict:
     cx = lambda a, shape: (a[:2 * int(np.prod(shape))].reshape(-1, 2) @ np.array([1.0, 1.0j])).reshape(shape)
     return dict(c=c[:s].copy(), A=A[:s * s].reshape(s, s).copy(), lam=cx(lam, (s,)), T=cx(T, (s, s)), Tinv=cx(Ti, (s, s)),
                 bhat0=float(bh[0]), bhat=bh[1:1 + s].copy())
+
+
+# ---- the discrete controller: the scalar statement of include/pfc.h (pfc_radau_control_device) in Python floats ---------------------
+RADAU_MAX_FIRES = 4096      # PFC_RADAU_MAX_FIRES
+
+
+def discrete_clock(t_last: float, t: float, dt: float):
+    """The reference's `while ctrl.t_last <= t: ctrl.t_last += ctrl.dt` by repeated addition, at most RADAU_MAX_FIRES times.
+    Returns (t_last, fires)."""
+    t_last, t, dt, fires = float(t_last), float(t), float(dt), 0
+    while t_last <= t and fires < RADAU_MAX_FIRES:
+        t_last = t_last + dt
+        fires += 1
+    return t_last, fires
+
+
+def computed_torque_pd(q, v, H, c, t, act, kp, kd, seg_t, seg_q, seg_ff=None, a_max=None):
+    """The law of one scene at one firing, in the written order: q, v (nv) the state; H (nv x nv, rows) and c (nv) the mass matrix and
+    bias at it; act the actuated coordinates, increasing; kp, kd, a_max (None: no clamp) per actuated coordinate; seg_t (n_seg; entry
+    0 is not read), seg_q (n_seg x n_act), seg_ff (n_seg x nv, or None: zeros) the schedule.  Returns tau (nv floats):
+    k = #{j >= 1: seg_t[j] <= t};  acc_a = (-(kd_a v_a)) - kp_a (q_a - seg_q[k][a]), clamped to [-a_max_a, a_max_a];
+    tau_a = ((..(0 + H[a][b0] acc_b0) + ..) + c_a) + ff[k][a];  tau_i = ff[k][i] elsewhere."""
+    t = float(t)
+    nv = len(c)
+    k = sum(1 for j in range(1, len(seg_t)) if float(seg_t[j]) <= t)
+    acc = []
+    for a, co in enumerate(act):
+        e = float(q[co]) - float(seg_q[k][a])
+        x = (-(float(kd[a]) * float(v[co]))) - float(kp[a]) * e
+        if a_max is not None:
+            am = float(a_max[a])
+            if x < -am:
+                x = -am
+            if x > am:
+                x = am
+        acc.append(x)
+    ff = [0.0] * nv if seg_ff is None else [float(e) for e in seg_ff[k]]
+    tau = list(ff)
+    for co in act:
+        s = 0.0
+        for b, cb in enumerate(act):
+            s = s + float(H[co][cb]) * acc[b]
+        tau[co] = (s + float(c[co])) + ff[co]
+    return tau
 
 
 def relative_pose(R_w1, t_w1, R_w2, t_w2) -> np.ndarray:
