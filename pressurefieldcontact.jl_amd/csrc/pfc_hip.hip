@@ -55,6 +55,7 @@
 
 #include "../../include/pfc.h"
 #include "pfc_sort.h"
+#include "pfc_hostblocks.h"
 
 namespace pfc {
 
@@ -215,6 +216,7 @@ __global__ void k_repose(int n_items, const double *__restrict__ pose, ItemRec *
 // host side
 // =================================================================================================================
 using namespace pfc;
+using namespace pfc_blocks;
 
 namespace {
 
@@ -714,6 +716,8 @@ int grid_for(size_t n, int block, int max_blocks) {
 
 // The kept pass (pfc_context::kept) ends: an option change, another broadphase pose, a device entry point, a reallocated pinned block.
 void end_kept_pass(pfc_context *h) { h->kept = {}; }
+// The pinned blocks no longer hold the value inputs of an evaluation a host Dual call could compare its own with.
+void forget_host_points(pfc_context *h) { h->pin_in_pt = {}; h->pin_din_pt = {}; }
 // A value pass is about to overwrite the device lists.
 void new_value_pass(pfc_context *h) {
     end_kept_pass(h);
@@ -754,6 +758,8 @@ int dual_handover_fit(pfc_context *h, int n_dir, size_t dpcap) {
 // Pair bound of passes enqueued before the count is known: floor x 2^k above twice the previous Dual evaluation's count (hint,
 // -1: none yet), so that buffers and captured graphs settle.
 size_t dual_spec_bound(long long hint, size_t floor) { while (floor < (size_t)(hint > 0 ? hint : 0) * 2 + 64) floor *= 2; return floor; }
+// ... and on a kept pass, whose contributing pairs are known exactly (dual_hint, from the value pass that was checked): no speculation.
+size_t dual_exact_bound(const pfc_context *h) { return (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) + 64; }
 // ctr[] index of the kept-polygon total (behind the per-level frontier counts; 8-byte aligned pair: the contributing-pair
 // counter follows it), that counter's index in the packed tail (12 ints of status and totals, then the counters), and the
 // ints in front of the outputs where one block carries the tail and the results (16-byte multiple).
@@ -2061,7 +2067,7 @@ int surface_enqueue(pfc_context *h, int n_items, const int *d_ins_ids, const dou
     // an evaluation for the call-order rules: the candidate list and the counters a Dual evaluation could reuse are overwritten
     new_value_pass(h);
     drop_pending(h);
-    h->pin_in_pt = {}; h->pin_din_pt = {};
+    forget_host_points(h);
     int ba, bb;
     const int bits = pfc_sort_key_bits(n_items, h->max_elem1, h->max_elem2, &ba, &bb);
     if (bits > 64)
@@ -2207,7 +2213,7 @@ int surface_host(pfc_context *h, int n_items, const int *ins_ids, const double *
     const size_t n = (size_t)n_items;
     if (n_items == 0) {
         new_value_pass(h);
-        h->pin_in_pt = {}; h->pin_din_pt = {};
+        forget_host_points(h);
         poly_off[0] = 0; poly_trac[0] = 0; totals[0] = totals[1] = 0;
         return PFC_OK;
     }
@@ -2313,7 +2319,7 @@ static int surface_device(pfc_context *h, int n_items, const int *d_ins_ids, con
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     if (n_items == 0) {
         new_value_pass(h);
-        h->pin_in_pt = {}; h->pin_din_pt = {};
+        forget_host_points(h);
         HIP_TRY(h, hipMemsetAsync(d_poly_off, 0, sizeof(long long), st));
         HIP_TRY(h, hipMemsetAsync(d_poly_trac, 0, sizeof(long long), st));
         HIP_TRY(h, hipMemsetAsync(d_totals, 0, sizeof(long long) * 2, st));
@@ -2429,33 +2435,6 @@ static void bar_mirror(pfc_context *h, void **dev, const void *pinned, size_t by
     *dev = dst;
 }
 
-// Value inputs of n items into a host-written block: pose | twist | s (zeros for a null s), the ids ids_at doubles in.
-static void pack_values(double *pi, size_t n, size_t ids_at, const int *ins_ids, const double *pose, const double *twist, const double *s) {
-    std::memcpy(pi, pose, sizeof(double) * n * 24);
-    std::memcpy(pi + n * 24, twist, sizeof(double) * n * 6);
-    if (s) std::memcpy(pi + n * 30, s, sizeof(double) * n * 6); else std::memset(pi + n * 30, 0, sizeof(double) * n * 6);
-    if (ins_ids) std::memcpy(pi + ids_at, ins_ids, sizeof(int) * n);
-}
-// Seeds of nk (item, direction) pairs: d_pose | d_twist, then -- with_s -- d_s (zeros for a null d_s).
-static void pack_seeds(double *pd, size_t nk, const double *d_pose, const double *d_twist, const double *d_s, bool with_s) {
-    std::memcpy(pd, d_pose, sizeof(double) * nk * 24);
-    std::memcpy(pd + nk * 24, d_twist, sizeof(double) * nk * 6);
-    if (!with_s) return;
-    if (d_s) std::memcpy(pd + nk * 30, d_s, sizeof(double) * nk * 6); else std::memset(pd + nk * 30, 0, sizeof(double) * nk * 6);
-}
-// The same-point test of the host Dual paths: are the value inputs of n items bit for bit those a pinned block laid out as by
-// pack_values holds?  zero_s: a null s must find zeros stored (without it a null s is not compared: no bristle item reads s).
-static bool same_point(const double *pi, size_t n, size_t ids_at, const int *ins_ids, const double *pose, const double *twist,
-                       const double *s, bool zero_s) {
-    if (std::memcmp(pi, pose, sizeof(double) * n * 24) != 0 || std::memcmp(pi + n * 24, twist, sizeof(double) * n * 6) != 0) return false;
-    if (s) {
-        if (std::memcmp(pi + n * 30, s, sizeof(double) * n * 6) != 0) return false;
-    } else if (zero_s) {
-        for (size_t k = 0; k < n * 6; ++k)
-            if (std::memcmp(pi + n * 30 + k, "\0\0\0\0\0\0\0\0", 8) != 0) return false;
-    }
-    return !ins_ids || std::memcmp(pi + ids_at, ins_ids, sizeof(int) * n) == 0;
-}
 // Device-visible addresses of the four pinned blocks of a small-scene Dual evaluation the host has just filled, the input blocks
 // through their BAR mirrors where they fit (bar_mirror), then one bar_publish.
 struct PinnedDev { void *in = nullptr, *out = nullptr, *din = nullptr, *dout = nullptr; };
@@ -2469,17 +2448,9 @@ static int map_pinned(pfc_context *h, PinnedDev *v, size_t in_bytes, size_t din_
     bar_publish();
     return PFC_OK;
 }
-// Results out of the pinned output blocks: wrench | sdot of n items at po and their counters (n x 4) at pc ...
-static void copy_out(const double *po, const int *pc, size_t n, double *wrench, double *sdot, int *counts) {
-    std::memcpy(wrench, po, sizeof(double) * n * 6);
-    std::memcpy(sdot, po + n * 6, sizeof(double) * n * 6);
-    if (counts) std::memcpy(counts, pc, sizeof(int) * n * 4);
-}
-// ... and the partials d_wrench | d_sdot of nk (item, direction) pairs at pdo.
-static void copy_out_dual(const double *pdo, size_t nk, double *d_wrench, double *d_sdot) {
-    std::memcpy(d_wrench, pdo, sizeof(double) * nk * 6);
-    std::memcpy(d_sdot, pdo + nk * 6, sizeof(double) * nk * 6);
-}
+// Seeds and partials of up to kBarKeys (item, direction) pairs (512 without a BAR block) are read and written in place by the
+// Dual kernels; larger blocks are staged.
+static bool dual_in_place(const pfc_context *h, size_t nk) { return nk <= (h->bar_state == 1 ? kBarKeys : (size_t)512); }
 
 // pfc_eval on one device.  o: pose and list flag of a Dual evaluation's value pass (two-stage path); the pinned targets are set here.
 static int eval_host(pfc_context *h, int n_items, const int *ins_ids, const double *pose, const double *twist,
@@ -2489,25 +2460,23 @@ static int eval_host(pfc_context *h, int n_items, const int *ins_ids, const doub
     if (n_items == 0) return PFC_OK;
     if (!pose || !twist || !wrench || !sdot) return fail(h, PFC_ERR_BAD_ARG, "null buffer");
     HIP_TRY(h, hipSetDevice(h->device));
-    h->pin_in_pt = {}; h->pin_din_pt = {};      // the pinned blocks are about to be overwritten
+    forget_host_points(h);      // the pinned blocks are about to be overwritten
     const size_t n = (size_t)n_items;
-    // one pinned block in (pose | twist | s | ins_ids), one pinned block out (tail | wrench | sdot | counts): two async
-    // copies around the launch sequence and a single synchronisation.  The device side of the output block lives
-    // behind the packed tail in the same buffer, so that the status / counters and the results come back together.
-    const size_t in_d = n * 36, in_bytes = in_d * sizeof(double) + n * sizeof(int);
-    const size_t out_d = n * 12, out_bytes = out_d * sizeof(double) + n * 4 * sizeof(int);
-    const size_t t0 = tail_prefix(h);
-    const size_t back_bytes = t0 * sizeof(int) + out_bytes;
-    HIP_TRY(h, h->pin_in.ensure(in_bytes));
-    // behind the outputs: the per-item words of the fused small-scene kernel (status, counts: 8 ints per item)
-    HIP_TRY(h, h->pin_out.ensure(back_bytes + (n <= (size_t)kFusedMaxItems ? n * 8 * sizeof(int) : 0)));
-    HIP_TRY(h, h->h_pose.ensure(in_d + (n + 1) / 2 + 1));      // device mirror of the input block (doubles)
-    HIP_TRY(h, ensure_graphed(h, h->tail, t0 + out_bytes / sizeof(int) + 4));   // only ever grows; ensure_work asks for less
+    // one pinned block in (a value block), one pinned block out (tail | result block): two async copies around the launch
+    // sequence and a single synchronisation.  The device side of the output block lives behind the packed tail in the same
+    // buffer, so that the status / counters and the results come back together.
+    const ValueBlock vs(nullptr, n); const ResultBlock rs(nullptr, n);      // (for their sizes)
+    const size_t t0 = tail_prefix(h), back_bytes = t0 * sizeof(int) + rs.bytes();
+    HIP_TRY(h, h->pin_in.ensure(vs.bytes(true)));
+    // behind the outputs: the per-item words of the fused small-scene kernel
+    HIP_TRY(h, h->pin_out.ensure(t0 * sizeof(int) + rs.bytes(n <= (size_t)kFusedMaxItems)));
+    HIP_TRY(h, h->h_pose.ensure(doubles_for(vs.bytes(true))));      // device mirror of the input block
+    HIP_TRY(h, ensure_graphed(h, h->tail, t0 + rs.bytes() / sizeof(int) + 4));   // only ever grows; ensure_work asks for less
     // (every evaluation whose kernels read the inputs in place, i.e. up to 512 items: 64 box-on-plane scenes 52.2 -> 48.7 us, C4's
     // 256 66.5 -> 64.5, 128 full-size poses on the batched path 333 -> 328; scripts/variants/bar_items_run.py)
     const bool bar = n <= kBarItems && !o.list && bar_ready(h);
-    double *pi = bar ? (double *)h->bar_in.p : (double *)h->pin_in.p;
-    pack_values(pi, n, in_d, ins_ids, pose, twist, s);
+    const ValueBlock pi(bar ? h->bar_in.p : h->pin_in.p, n);
+    pack_values(pi, ins_ids, pose, twist, s);
     if (bar) bar_publish();
     hipStream_t st = h->stream;
     // A small scene (what a Radau stage evaluates) pays ~5 us per staging copy, more than the kernels spend on the data:
@@ -2516,33 +2485,30 @@ static int eval_host(pfc_context *h, int n_items, const int *ins_ids, const doub
     // inputs up to 4 096: C5 through host buffers 307 -> 282 us, 1 000 box-on-plane scenes 198 -> 178, 600 full-size poses
     // 635 -> 619, 2 048 unchanged; scripts/variants/zero_copy_limit_run.py.)
     const bool zero_copy = n_items <= (bar ? (int)kBarItems : 512) && !o.list;
-    double *di = h->h_pose.p, *dout = reinterpret_cast<double *>(h->tail.p + t0);
+    ValueBlock di(h->h_pose.p, n); ResultBlock dout(h->tail.p + t0, n);
+    const ResultBlock po((int *)h->pin_out.p + t0, n);      // where the host reads the results
     if (zero_copy) {
         void *dpi = h->bar_in.p, *dpo = nullptr;
         if (!bar) HIP_TRY(h, hipHostGetDevicePointer(&dpi, h->pin_in.p, 0));
         HIP_TRY(h, hipHostGetDevicePointer(&dpo, h->pin_out.p, 0));
-        di = (double *)dpi;
-        dout = reinterpret_cast<double *>((int *)dpo + t0);
+        di = ValueBlock(dpi, n);
+        dout = ResultBlock((int *)dpo + t0, n);
         o.tail = (int *)dpo;      // k_final packs the tail, the small-scene kernel its per-item words, straight into the pinned block
-        if (n <= (size_t)kFusedMaxItems) {
-            o.fout = reinterpret_cast<int *>(reinterpret_cast<char *>(dout) + out_bytes);
-            o.fout_host = reinterpret_cast<const int *>(reinterpret_cast<const char *>(h->pin_out.p) + back_bytes);
-        }
+        if (n <= (size_t)kFusedMaxItems) { o.fout = dout.fused_words(); o.fout_host = po.fused_words(); }
     } else {
-        HIP_TRY(h, hipMemcpyAsync(di, pi, ins_ids ? in_bytes : in_d * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(h, hipMemcpyAsync(di.p, pi.p, pi.bytes(ins_ids != nullptr), hipMemcpyHostToDevice, st));
     }
     int rc = PFC_OK;
     for (int attempt = 0; attempt < 40; ++attempt) {
-        rc = eval_device(h, n_items, ins_ids ? (const int *)(di + in_d) : nullptr, di, di + n * 24,
-                         s ? di + n * 30 : nullptr, dout, dout + n * 6, (int *)(dout + out_d), st, o);
+        rc = eval_device(h, n_items, ins_ids ? di.ids() : nullptr, di.pose(), di.twist(), s ? di.s() : nullptr, dout.wrench(), dout.sdot(),
+                         dout.counts(), st, o);
         if (rc != PFC_OK) return rc;
         if (!zero_copy && h->pend.kind != pfc_context::Pending::Fused) HIP_TRY(h, hipMemcpyAsync(h->pin_out.p, h->tail.p, back_bytes, hipMemcpyDeviceToHost, st));
         rc = check_eval(h, (const int *)h->pin_out.p, o.fout_host);      // one D2H copy carries the tail and the outputs
         if (rc != PFC_ERR_OVERFLOW) break;
     }
     if (rc != PFC_OK) return rc;
-    const double *po = reinterpret_cast<const double *>((const int *)h->pin_out.p + t0);
-    copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
+    copy_out(po, wrench, sdot, counts);
     return PFC_OK;
 }
 
@@ -2700,125 +2666,147 @@ hipError_t zero_ds(pfc_context *h, size_t nk, const double **d_ds, hipStream_t s
     return e;
 }
 
+// A host-pointer Dual call: the arguments of pfc_eval_dual_bp, checked; bp_pose is the device-visible pinned block (or null).
+struct DualCall {
+    int n_items, n_dir;
+    const int *ins_ids;
+    const double *pose, *twist, *s, *d_pose, *d_twist, *d_s;
+    double *wrench, *sdot, *d_wrench, *d_sdot;
+    int *counts;
+    const double *bp_pose;
+    size_t n() const { return (size_t)n_items; }
+    size_t nk() const { return (size_t)n_items * n_dir; }
+    void deliver(ResultBlock res, PartialBlock part) const { copy_out(res, wrench, sdot, counts); copy_out_dual(part, d_wrench, d_sdot); }
+};
+
+// The Dual passes alone, on the value pass a host route kept (its lists and item records on the device, its results in the
+// pinned block `res`): tail and pair_count as launch_dual takes them, levels locates the pair counter in the tail.  The pair
+// count is known exactly, so there is no speculation to check.  dev_seeds / dev_part: where the kernels read and write; when
+// not in_place they are staged from pin_din and to pin_dout.
+int dual_on_kept_pass(pfc_context *h, const DualCall &c, const int *tail, const int *pair_count, int levels, bool in_place,
+                      SeedBlock dev_seeds, PartialBlock dev_part, ResultBlock res) {
+    const size_t nk = c.nk();
+    hipStream_t st = h->stream;
+    HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
+    HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
+    if (!in_place) HIP_TRY(h, hipMemcpyAsync(dev_seeds.p, h->pin_din.p, dev_seeds.bytes(), hipMemcpyHostToDevice, st));
+    h->last_levels = levels;
+    const int rc = launch_dual(h, c.n_items, c.n_dir, tail, dev_seeds.d_pose(), dev_seeds.d_twist(), dev_seeds.d_s(), dev_part.d_wrench(),
+                               dev_part.d_sdot(), dual_exact_bound(h), st, nullptr, true, pair_count);
+    if (rc != PFC_OK) return rc;
+    if (!in_place) HIP_TRY(h, hipMemcpyAsync(h->pin_dout.p, dev_part.p, dev_part.bytes(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    c.deliver(res, PartialBlock(h->pin_dout.p, nk));
+    h->last_dual_reused = true;
+    return PFC_OK;
+}
+
 // Smallest scenes, all instructions regularized (test/boxes.jl and the like): value AND Dual passes inside the fused
 // small-scene kernel -- one launch, results polled from pinned memory.  Returns PFC_ERR_OVERFLOW when an item does not fit
 // (too many candidates / polygons): the caller takes the batched Dual path and this one stays off for a while.
-int eval_dual_fused(pfc_context *h, int n_items, int n_dir, const int *ins_ids, const double *pose, const double *twist,
-                    const double *s, const double *d_pose, const double *d_twist, double *wrench, double *sdot,
-                    double *d_wrench, double *d_sdot, int *counts, const double *bp_pose) {
+int eval_dual_fused(pfc_context *h, const DualCall &c) {
     h->pin_din_pt = {};    // these pinned blocks are about to be reused
-    const size_t n = (size_t)n_items, nk = n * n_dir;
-    const size_t in_d = n * 36, in_bytes = in_d * sizeof(double) + n * sizeof(int);
-    const size_t out_d = n * 12, out_bytes = out_d * sizeof(double) + n * 4 * sizeof(int) + n * 8 * sizeof(int);
-    HIP_TRY(h, h->pin_in.ensure(in_bytes));
-    HIP_TRY(h, h->pin_out.ensure(out_bytes + 64));
-    HIP_TRY(h, h->pin_din.ensure(sizeof(double) * nk * 30));
-    HIP_TRY(h, h->pin_dout.ensure(sizeof(double) * nk * 12));
-    pack_values((double *)h->pin_in.p, n, in_d, ins_ids, pose, twist, s);
-    pack_seeds((double *)h->pin_din.p, nk, d_pose, d_twist, nullptr, false);
+    const size_t n = c.n(), nk = c.nk();
+    const ValueBlock vs(nullptr, n); const ResultBlock rs(nullptr, n); const SeedBlock ss(nullptr, nk); const PartialBlock ps(nullptr, nk);
+    HIP_TRY(h, h->pin_in.ensure(vs.bytes(true))); HIP_TRY(h, h->pin_out.ensure(rs.bytes(true) + 64));
+    HIP_TRY(h, h->pin_din.ensure(ss.bytes(false))); HIP_TRY(h, h->pin_dout.ensure(ps.bytes()));
+    const ValueBlock pi(h->pin_in.p, n); const ResultBlock po(h->pin_out.p, n);
+    pack_values(pi, c.ins_ids, c.pose, c.twist, c.s);
+    pack_seeds(SeedBlock(h->pin_din.p, nk), c.d_pose, c.d_twist, nullptr, false);
     PinnedDev v;
-    { const int rc = map_pinned(h, &v, in_bytes, sizeof(double) * nk * 30); if (rc != PFC_OK) return rc; }
-    double *di = (double *)v.in, *dout = (double *)v.out, *ddi = (double *)v.din, *ddo = (double *)v.dout;
-    PassOpts o = {bp_pose};
-    o.fout = reinterpret_cast<int *>(dout + out_d) + n * 4;
-    o.fout_host = reinterpret_cast<const int *>((const double *)h->pin_out.p + out_d) + n * 4;
-    o.n_dir = n_dir; o.d_pose = ddi; o.d_twist = ddi + nk * 24; o.d_wrench = ddo; o.d_sdot = ddo + nk * 6;
-    int rc = enqueue_fused(h, n_items, ins_ids ? (const int *)(di + in_d) : nullptr, di, di + n * 24, s ? di + n * 30 : nullptr,
-                           dout, dout + n * 6, reinterpret_cast<int *>(dout + out_d), h->stream, o);
+    { const int rc = map_pinned(h, &v, vs.bytes(true), ss.bytes(false)); if (rc != PFC_OK) return rc; }
+    const ValueBlock di(v.in, n); const ResultBlock dout(v.out, n); const SeedBlock ddi(v.din, nk); const PartialBlock ddo(v.dout, nk);
+    PassOpts o = {c.bp_pose};
+    o.fout = dout.fused_words(); o.fout_host = po.fused_words();
+    o.n_dir = c.n_dir; o.d_pose = ddi.d_pose(); o.d_twist = ddi.d_twist(); o.d_wrench = ddo.d_wrench(); o.d_sdot = ddo.d_sdot();
+    int rc = enqueue_fused(h, c.n_items, c.ins_ids ? di.ids() : nullptr, di.pose(), di.twist(), c.s ? di.s() : nullptr,
+                           dout.wrench(), dout.sdot(), dout.counts(), h->stream, o);
     if (rc == PFC_OK) rc = check_eval(h, nullptr, o.fout_host);
     if (rc != PFC_OK) return rc;
-    const double *po = (const double *)h->pin_out.p;
-    copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
-    copy_out_dual((const double *)h->pin_dout.p, nk, d_wrench, d_sdot);
-    h->pin_in_pt = {n_items, ins_ids != nullptr, h->value_serial, in_d};     // a repeat of this point goes to the hybrid path
+    c.deliver(po, PartialBlock(h->pin_dout.p, nk));
+    h->pin_in_pt = {c.n_items, c.ins_ids != nullptr, h->value_serial, pi.ids_at};     // a repeat of this point goes to the hybrid path
     return PFC_OK;
 }
+
+// What the hybrid and the one-graph route share.  prepare(): their four pinned blocks sized (the results res_at ints into pin_out,
+// out_bytes in all); the reuse test -- the chunks of one Jacobian: value inputs bitwise equal to those still in the pinned input
+// block, and the pass `kind` kept -> only the Dual passes run; values (unless reused) and seeds packed; the device-visible views,
+// seeds and partials in place (dual_in_place) or through dual_in / dual_out.
+struct SmallDual {
+    bool same = false, in_place = true;
+    PinnedDev v;
+    ValueBlock di{nullptr, 0};
+    ResultBlock dout{nullptr, 0}, po{nullptr, 0};      // the results as the device and as the host see them
+    SeedBlock ddi{nullptr, 0};
+    PartialBlock ddo{nullptr, 0};
+    int prepare(pfc_context *h, const DualCall &c, pfc_context::KeptPass::Kind kind, size_t res_at, size_t out_bytes, bool list) {
+        const size_t n = c.n(), nk = c.nk();
+        const ValueBlock vs(nullptr, n); const SeedBlock ss(nullptr, nk); const PartialBlock ps(nullptr, nk);
+        bool in_moved, out_moved;
+        HIP_TRY(h, h->pin_in.ensure(vs.bytes(true), &in_moved)); HIP_TRY(h, h->pin_out.ensure(out_bytes, &out_moved));
+        if (in_moved || out_moved) end_kept_pass(h);      // reallocated: the cached blocks are gone
+        HIP_TRY(h, h->pin_din.ensure(ss.bytes())); HIP_TRY(h, h->pin_dout.ensure(ps.bytes()));
+        const ValueBlock pi(h->pin_in.p, n);
+        po = ResultBlock((int *)h->pin_out.p + res_at, n);
+        same = h->opt_dual_reuse && h->kept.kind == kind && h->kept.n == c.n_items && h->kept.ids == (c.ins_ids != nullptr) &&
+               same_point(pi, c.ins_ids, c.pose, c.twist, c.s, true);
+        if (!same) {
+            end_kept_pass(h);
+            HIP_TRY(h, ensure_work(h, c.n_items, list));      // (not before a reuse: option poison refills the work lists there)
+            pack_values(pi, c.ins_ids, c.pose, c.twist, c.s);
+        }
+        pack_seeds(SeedBlock(h->pin_din.p, nk), c.d_pose, c.d_twist, c.d_s, true);
+        { const int rc = map_pinned(h, &v, vs.bytes(true), ss.bytes()); if (rc != PFC_OK) return rc; }
+        di = ValueBlock(v.in, n);
+        dout = ResultBlock((int *)v.out + res_at, n);
+        in_place = dual_in_place(h, nk);
+        if (!in_place) { HIP_TRY(h, ensure_graphed(h, h->dual_in, ss.doubles())); HIP_TRY(h, ensure_graphed(h, h->dual_out, ps.doubles())); }
+        ddi = SeedBlock(in_place ? v.din : h->dual_in.p, nk);
+        ddo = PartialBlock(in_place ? v.dout : h->dual_out.p, nk);
+        return PFC_OK;
+    }
+};
 
 // Small scenes the in-kernel Dual passes do not take (bristle items, many polygons per item): the fused kernel evaluates
 // the values and hands the item records, counters and the list of candidates with a polygon to the batched Dual passes
 // (k_narrow_dual ..., many workgroups), enqueued right behind it; one synchronisation.  Returns PFC_ERR_OVERFLOW when an
 // item does not fit the fused kernel or the speculative size of the kept Dual polygons fell short (the caller then takes
 // the batched paths).
-int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids, const double *pose, const double *twist,
-                     const double *s, const double *d_pose, const double *d_twist, const double *d_s, double *wrench,
-                     double *sdot, double *d_wrench, double *d_sdot, int *counts, const double *bp_pose) {
+int eval_dual_hybrid(pfc_context *h, const DualCall &c) {
     h->pin_din_pt = {};    // these pinned blocks are about to be reused
-    const size_t n = (size_t)n_items, nk = n * n_dir;
-    const size_t in_d = n * 36, in_bytes = in_d * sizeof(double) + n * sizeof(int);
-    const size_t out_d = n * 12, out_bytes = out_d * sizeof(double) + n * 4 * sizeof(int) + n * 8 * sizeof(int);
-    {
-        bool in_moved, out_moved;
-        HIP_TRY(h, h->pin_in.ensure(in_bytes, &in_moved));
-        HIP_TRY(h, h->pin_out.ensure(out_bytes + 64, &out_moved));
-        if (in_moved || out_moved) end_kept_pass(h);      // reallocated: the cached blocks are gone
-    }
-    HIP_TRY(h, h->pin_din.ensure(sizeof(double) * nk * 36));
-    HIP_TRY(h, h->pin_dout.ensure(sizeof(double) * nk * 12));
-    HIP_TRY(h, h->emit_ctr.ensure(4));
-    HIP_TRY(h, h->h_emit.ensure(4));
-    double *pi = (double *)h->pin_in.p;
-    // the chunks of one Jacobian (pfc_eval_dual's large path has the same test): value inputs bitwise equal to those still
-    // in the pinned input block -> the lists and item records the fused kernel handed over are reused, only the Dual passes run
-    const bool same = h->opt_dual_reuse && h->kept.kind == pfc_context::KeptPass::Hybrid && h->kept.n == n_items &&
-                      h->kept.ids == (ins_ids != nullptr) && same_point(pi, n, in_d, ins_ids, pose, twist, s, true);
-    if (!same) {
-        end_kept_pass(h);
-        HIP_TRY(h, ensure_work(h, n_items, false));      // (not before a reuse: option poison refills the work lists there)
-        pack_values(pi, n, in_d, ins_ids, pose, twist, s);
-    }
-    pack_seeds((double *)h->pin_din.p, nk, d_pose, d_twist, d_s, true);
-    PinnedDev v;
-    { const int rc = map_pinned(h, &v, in_bytes, sizeof(double) * nk * 36); if (rc != PFC_OK) return rc; }
-    double *di = (double *)v.in, *dout = (double *)v.out;
+    const int n_items = c.n_items, n_dir = c.n_dir;
+    const size_t nk = c.nk();
+    SmallDual b;
+    { const int rc = b.prepare(h, c, pfc_context::KeptPass::Hybrid, 0, ResultBlock(nullptr, c.n()).bytes(true) + 64, false); if (rc != PFC_OK) return rc; }
+    HIP_TRY(h, h->emit_ctr.ensure(4)); HIP_TRY(h, h->h_emit.ensure(4));
     hipStream_t st = h->stream;
-    // seeds / results of up to kBarKeys (512 without a BAR block) (item, direction) pairs are read / written in place by the kernels, larger ones staged
-    const bool zc = nk <= (h->bar_state == 1 ? (int)kBarKeys : 512);
-    if (!zc) {
-        HIP_TRY(h, ensure_graphed(h, h->dual_in, nk * 36));
-        HIP_TRY(h, ensure_graphed(h, h->dual_out, nk * 12));
-        HIP_TRY(h, hipMemcpyAsync(h->dual_in.p, h->pin_din.p, sizeof(double) * nk * 36, hipMemcpyHostToDevice, st));
-    }
-    double *ddi = zc ? (double *)v.din : h->dual_in.p, *ddo = zc ? (double *)v.dout : h->dual_out.p;
-    const double *po = (const double *)h->pin_out.p;
-    if (same) {
-        HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
-        HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
-        const size_t bound_r = (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) + 64;     // known exactly
-        int rcr = launch_dual(h, n_items, n_dir, h->tail.p, ddi, ddi + nk * 24, ddi + nk * 30, ddo, ddo + nk * 6, bound_r, st, nullptr,
-                              true, h->emit_ctr.p);
-        if (rcr != PFC_OK) return rcr;
-        if (!zc) HIP_TRY(h, hipMemcpyAsync(h->pin_dout.p, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipStreamSynchronize(st));
-        copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
-        copy_out_dual((const double *)h->pin_dout.p, nk, d_wrench, d_sdot);
-        h->last_dual_reused = true;
-        return PFC_OK;
-    }
+    // a repeat: the lists and item records the fused kernel handed over are still there
+    if (b.same) return dual_on_kept_pass(h, c, h->tail.p, h->emit_ctr.p, h->last_levels, b.in_place, b.ddi, b.ddo, b.po);
+    if (!b.in_place) HIP_TRY(h, hipMemcpyAsync(b.ddi.p, h->pin_din.p, b.ddi.bytes(), hipMemcpyHostToDevice, st));
     const size_t bound = dual_spec_bound(h->dual_hint, 64);
     HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
     HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
     HIP_TRY(h, hipMemsetAsync(h->emit_ctr.p, 0, sizeof(int) * 4, st));
-    PassOpts o = {bp_pose};
-    o.emit = true; o.fout = reinterpret_cast<int *>(dout + out_d) + n * 4;      // (no words to poll: this path synchronises, the Dual kernels run behind the fused one)
-    int rc = enqueue_fused(h, n_items, ins_ids ? (const int *)(di + in_d) : nullptr, di, di + n * 24, s ? di + n * 30 : nullptr,
-                           dout, dout + n * 6, reinterpret_cast<int *>(dout + out_d), st, o);
+    PassOpts o = {c.bp_pose};
+    o.emit = true; o.fout = b.dout.fused_words();      // (no words to poll: this path synchronises, the Dual kernels run behind the fused one)
+    int rc = enqueue_fused(h, n_items, c.ins_ids ? b.di.ids() : nullptr, b.di.pose(), b.di.twist(), c.s ? b.di.s() : nullptr,
+                           b.dout.wrench(), b.dout.sdot(), b.dout.counts(), st, o);
     if (rc != PFC_OK) return rc;
     size_t dpcap = 0;
     h->last_levels = eff_levels(h);
-    rc = launch_dual(h, n_items, n_dir, h->tail.p, ddi, ddi + nk * 24, ddi + nk * 30, ddo, ddo + nk * 6, bound, st, &dpcap, true,
-                     h->emit_ctr.p);
+    rc = launch_dual(h, n_items, n_dir, h->tail.p, b.ddi.d_pose(), b.ddi.d_twist(), b.ddi.d_s(), b.ddo.d_wrench(), b.ddo.d_sdot(), bound, st, &dpcap,
+                     true, h->emit_ctr.p);
     if (rc != PFC_OK) return rc;
-    if (!zc) HIP_TRY(h, hipMemcpyAsync(h->pin_dout.p, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
+    if (!b.in_place) HIP_TRY(h, hipMemcpyAsync(h->pin_dout.p, b.ddo.p, b.ddo.bytes(), hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipMemcpyAsync(h->h_emit.p, h->emit_ctr.p, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
     // check_fused would poll; here the stream is synchronised (the completion words of the fused kernel are long written)
     HIP_TRY(h, hipStreamSynchronize(st));
-    rc = check_eval(h, nullptr, reinterpret_cast<const int *>((const double *)h->pin_out.p + out_d) + n * 4);
+    rc = check_eval(h, nullptr, b.po.fused_words());
     if (rc == PFC_OK) rc = dual_handover_fit(h, n_dir, dpcap);
     if (rc != PFC_OK) return rc;
-    copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
-    copy_out_dual((const double *)h->pin_dout.p, nk, d_wrench, d_sdot);
-    h->kept = {pfc_context::KeptPass::Hybrid, n_items, ins_ids != nullptr};
-    h->pin_in_pt = {n_items, ins_ids != nullptr, h->value_serial, in_d};
+    c.deliver(b.po, PartialBlock(h->pin_dout.p, nk));
+    h->kept = {pfc_context::KeptPass::Hybrid, n_items, c.ins_ids != nullptr};
+    h->pin_in_pt = {n_items, c.ins_ids != nullptr, h->value_serial, b.di.ids_at};
     return PFC_OK;
 }
 
@@ -2826,44 +2814,18 @@ int eval_dual_hybrid(pfc_context *h, int n_items, int n_dir, const int *ins_ids,
 // staging copies (the kernels read and write the pinned blocks), the kept Dual polygons sized from the previous Dual
 // evaluation's pair count.  Returns PFC_ERR_OVERFLOW when the speculation or a work list fell short: the caller then
 // takes the two-stage path, which sizes everything from the value pass.
-int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, const double *pose, const double *twist,
-                    const double *s, const double *d_pose, const double *d_twist, const double *d_s, double *wrench,
-                    double *sdot, double *d_wrench, double *d_sdot, int *counts, const double *bp_pose) {
-    h->pin_din_pt = {};    // these pinned blocks are about to be reused
-    h->pin_in_pt = {};
-    const size_t n = (size_t)n_items, nk = n * n_dir;
-    const size_t in_d = n * 36, in_bytes = in_d * sizeof(double) + n * sizeof(int);
-    const size_t out_d = n * 12, out_bytes = out_d * sizeof(double) + n * 4 * sizeof(int);
-    const size_t t0 = tail_prefix(h);
-    const size_t back_bytes = t0 * sizeof(int) + out_bytes;
-    {
-        bool in_moved, out_moved;
-        HIP_TRY(h, h->pin_in.ensure(in_bytes, &in_moved));
-        HIP_TRY(h, h->pin_out.ensure(back_bytes, &out_moved));
-        if (in_moved || out_moved) end_kept_pass(h);     // reallocated: the cached blocks are gone
-    }
-    HIP_TRY(h, h->pin_din.ensure(sizeof(double) * nk * 36));
-    HIP_TRY(h, h->pin_dout.ensure(sizeof(double) * nk * 12));
-    double *pi = (double *)h->pin_in.p;
-    // the chunks of one Jacobian: value inputs bitwise equal to those still in the pinned input block -> only the Dual passes
-    const bool same = h->opt_dual_reuse && h->kept.kind == pfc_context::KeptPass::OneGraph && h->kept.n == n_items &&
-                      h->kept.ids == (ins_ids != nullptr) && same_point(pi, n, in_d, ins_ids, pose, twist, s, true);
-    if (!same) {
-        end_kept_pass(h);
-        pack_values(pi, n, in_d, ins_ids, pose, twist, s);
-    }
-    pack_seeds((double *)h->pin_din.p, nk, d_pose, d_twist, d_s, true);
-    PinnedDev v;
-    { const int rc = map_pinned(h, &v, in_bytes, sizeof(double) * nk * 36); if (rc != PFC_OK) return rc; }
-    double *di = (double *)v.in, *dout = reinterpret_cast<double *>((int *)v.out + t0);
-    const double *po = reinterpret_cast<const double *>((const int *)h->pin_out.p + t0);
+int eval_dual_small(pfc_context *h, const DualCall &c) {
+    forget_host_points(h);    // these pinned blocks are about to be reused
+    const int n_items = c.n_items, n_dir = c.n_dir;
+    const size_t nk = c.nk(), t0 = tail_prefix(h);      // the results sit behind the packed tail
+    SmallDual b;
+    { const int rc = b.prepare(h, c, pfc_context::KeptPass::OneGraph, t0, t0 * sizeof(int) + ResultBlock(nullptr, c.n()).bytes(), true); if (rc != PFC_OK) return rc; }
     hipStream_t st = h->stream;
     // One captured graph: accumulator fill, the value pass, the Dual passes.  (Launched eagerly behind the replayed value
     // graph, the Dual kernels started 9 us late.)  The capacity of the kept Dual polygons is a power of two above twice
     // the previous pair count, so that the graph survives the small changes from one evaluation to the next.
     const size_t bound = dual_spec_bound(h->dual_hint, 64);
-    const PassOpts o = {bp_pose, true, (int *)v.out};      // the value pass lists the contributing candidates and packs its tail into the pinned output block
-    if (!same) HIP_TRY(h, ensure_work(h, n_items, o.list));      // (not before a reuse: option poison refills the work lists there)
+    const PassOpts o = {c.bp_pose, true, (int *)b.v.out};      // the value pass lists the contributing candidates and packs its tail into the pinned output block
     HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
     HIP_TRY(h, ensure_graphed(h, h->dual_res, nk * kDrStride));
     const size_t dpcap = dual_poly_cap(h, n_dir, bound);
@@ -2871,39 +2833,20 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     HIP_TRY(h, ensure_graphed(h, h->dual_pkey, dpcap));
     const int levels = eff_levels(h);
     const int L = bfs_levels_for(h, n_items, levels, o.half);
-    // seeds / results of up to 512 (item, direction) pairs are read / written in place by the kernels; larger ones are
-    // copied by memcpy nodes of the graph (reading 288 B per pair over PCIe from inside k_narrow_dual stops paying)
-    const bool zc_dual = nk <= (h->bar_state == 1 ? (int)kBarKeys : 512);
-    if (!zc_dual) {
-        HIP_TRY(h, ensure_graphed(h, h->dual_in, nk * 36));
-        HIP_TRY(h, ensure_graphed(h, h->dual_out, nk * 12));
-    }
-    double *ddi = zc_dual ? (double *)v.din : h->dual_in.p, *ddo = zc_dual ? (double *)v.dout : h->dual_out.p;
-    if (same) {
-        // eager launches of the Dual passes on the value pass the last graph replay left (lists, item records, the packed tail
-        // in the pinned output block); the pair count is known, so there is no speculation to check
-        HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
-        if (!zc_dual) HIP_TRY(h, hipMemcpyAsync(ddi, h->pin_din.p, sizeof(double) * nk * 36, hipMemcpyHostToDevice, st));
-        h->last_levels = levels;
-        const size_t bound_r = (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) + 64;
-        int rcr = launch_dual(h, n_items, n_dir, (const int *)v.out, ddi, ddi + nk * 24, ddi + nk * 30, ddo, ddo + nk * 6, bound_r, st,
-                              nullptr, true);
-        if (rcr != PFC_OK) return rcr;
-        if (!zc_dual) HIP_TRY(h, hipMemcpyAsync(h->pin_dout.p, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipStreamSynchronize(st));
-        copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
-        copy_out_dual((const double *)h->pin_dout.p, nk, d_wrench, d_sdot);
-        h->last_dual_reused = true;
-        return PFC_OK;
-    }
-    const int *d_ins = ins_ids ? (const int *)(di + in_d) : nullptr;
-    const double *d_sv = s ? di + n * 30 : nullptr;
+    // a repeat: eager launches of the Dual passes on the value pass the last graph replay left (lists, item records, the packed
+    // tail in the pinned output block)
+    if (b.same) return dual_on_kept_pass(h, c, (const int *)b.v.out, nullptr, levels, b.in_place, b.ddi, b.ddo, b.po);
+    // (seed and partial blocks larger than the kernels take in place are copied by memcpy nodes of the graph: reading 288 B per
+    // pair over PCIe from inside k_narrow_dual stops paying)
+    const ValueBlock &di = b.di; const ResultBlock &dout = b.dout; const SeedBlock &ddi = b.ddi; const PartialBlock &ddo = b.ddo;
+    const int *d_ins = c.ins_ids ? di.ids() : nullptr;
+    const double *d_sv = c.s ? di.s() : nullptr;
     pfc_context::DualGraphKey key = {};
     key.v.n_items = n_items; key.v.levels = levels; key.v.L = L; key.v.debug = 0;
     key.v.bristle = (h->any_bristle ? 1 : 0) | (h->any_tet_tet ? 2 : 0) | (h->any_regularized ? 4 : 0) | (h->all_rule2 ? 8 : 0); key.v.surv = 1;
-    key.v.p[0] = d_ins; key.v.p[1] = di; key.v.p[2] = di + n * 24; key.v.p[3] = d_sv; key.v.p[4] = dout;
-    key.v.p[5] = dout + n * 6; key.v.p[6] = dout + out_d; key.v.p[7] = o.tail; key.v.p[8] = o.bp_pose; key.v.stream = (void *)st; key.v.epoch = h->epoch;
-    key.n_dir = n_dir; key.bound = bound; key.din = ddi; key.dout = ddo;
+    key.v.p[0] = d_ins; key.v.p[1] = di.pose(); key.v.p[2] = di.twist(); key.v.p[3] = d_sv; key.v.p[4] = dout.wrench();
+    key.v.p[5] = dout.sdot(); key.v.p[6] = dout.counts(); key.v.p[7] = o.tail; key.v.p[8] = o.bp_pose; key.v.stream = (void *)st; key.v.epoch = h->epoch;
+    key.n_dir = n_dir; key.bound = bound; key.din = ddi.p; key.dout = ddo.p;
     h->last_levels = levels;      // launch_dual locates the pair counter in the tail by it
     int rc = PFC_OK;
     if (!h->dghave || std::memcmp(&key, &h->dgkey, sizeof key) != 0) {
@@ -2913,13 +2856,13 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
         hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
         if (e == hipSuccess) {
             e = hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st);
-            if (!zc_dual && e == hipSuccess) e = hipMemcpyAsync(ddi, h->pin_din.p, sizeof(double) * nk * 36, hipMemcpyHostToDevice, st);
-            rc = record_eval(h, n_items, d_ins, di, di + n * 24, d_sv, dout, dout + n * 6, (int *)(dout + out_d), st, false, o);
+            if (!b.in_place && e == hipSuccess) e = hipMemcpyAsync(ddi.p, h->pin_din.p, ddi.bytes(), hipMemcpyHostToDevice, st);
+            rc = record_eval(h, n_items, d_ins, di.pose(), di.twist(), d_sv, dout.wrench(), dout.sdot(), dout.counts(), st, false, o);
             if (rc == PFC_OK)
-                rc = launch_dual(h, n_items, n_dir, (const int *)v.out, ddi, ddi + nk * 24, ddi + nk * 30, ddo, ddo + nk * 6, bound,
+                rc = launch_dual(h, n_items, n_dir, (const int *)b.v.out, ddi.d_pose(), ddi.d_twist(), ddi.d_s(), ddo.d_wrench(), ddo.d_sdot(), bound,
                                  st, nullptr, true);
-            if (!zc_dual && rc == PFC_OK && e == hipSuccess)
-                e = hipMemcpyAsync(h->pin_dout.p, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st);
+            if (!b.in_place && rc == PFC_OK && e == hipSuccess)
+                e = hipMemcpyAsync(h->pin_dout.p, ddo.p, ddo.bytes(), hipMemcpyDeviceToHost, st);
             const hipError_t e2 = hipStreamEndCapture(st, &graph);
             if (e == hipSuccess) e = e2;
         }
@@ -2938,11 +2881,125 @@ int eval_dual_small(pfc_context *h, int n_items, int n_dir, const int *ins_ids, 
     // did the kept Dual polygons fit?  (contributing pairs: the counter next to the polygon total in the packed tail)
     if (rc == PFC_OK) rc = dual_spec_fit(h, n_dir, tail[tail_pairs(h->last_levels)], dpcap);
     if (rc != PFC_OK) return rc;
-    copy_out(po, (const int *)(po + out_d), n, wrench, sdot, counts);
-    copy_out_dual((const double *)h->pin_dout.p, nk, d_wrench, d_sdot);
-    h->kept = {pfc_context::KeptPass::OneGraph, n_items, ins_ids != nullptr};
+    c.deliver(b.po, PartialBlock(h->pin_dout.p, nk));
+    h->kept = {pfc_context::KeptPass::OneGraph, n_items, c.ins_ids != nullptr};
     return PFC_OK;
 }
+
+// Larger batches.  One synchronisation: inputs up in one pinned block, pfc_eval_dual_device (value pass + Dual passes back to
+// back, kept Dual polygons sized from the previous evaluation), results down in one pinned block, pfc_check.  A work list
+// that overflowed or a speculation that fell short re-issues the evaluation (buffers have grown).
+int eval_dual_one_sync(pfc_context *h, const DualCall &c) {
+    const int n_items = c.n_items, n_dir = c.n_dir;
+    const size_t n = c.n(), nk = c.nk();
+    const bool ids = c.ins_ids != nullptr;
+    hipStream_t st = h->stream;
+    const OneSyncIn is(nullptr, n, nk); const OneSyncOut os(nullptr, n, nk);      // (for their sizes)
+    {
+        bool in_moved, out_moved;
+        HIP_TRY(h, h->pin_din.ensure(is.bytes(true), &in_moved));
+        HIP_TRY(h, h->pin_dout.ensure(os.bytes(), &out_moved));
+        if (in_moved || out_moved) h->pin_din_pt = {};      // reallocated: the cached blocks are gone
+    }
+    HIP_TRY(h, ensure_graphed(h, h->dual_in, doubles_for(is.bytes(true))));
+    HIP_TRY(h, ensure_graphed(h, h->dual_out, doubles_for(os.bytes())));
+    const OneSyncIn pin(h->pin_din.p, n, nk), din(h->dual_in.p, n, nk);
+    const OneSyncOut pout(h->pin_dout.p, n, nk), dout(h->dual_out.p, n, nk);
+    const SeedBlock dd = din.seeds(); const PartialBlock ddo = dout.partials();
+    // Further seed directions at the point of the previous Dual evaluation (the chunks of one Jacobian: Radau calls
+    // the path ceil(NX / N_chunk) times with the same values and different partials, src/radau/radau_functions.jl:2-14):
+    // if the value inputs equal, bit for bit, those still sitting in the pinned input block, the value pass on the
+    // device is reused -- candidates, contributing pairs, per-item results -- and only the Dual passes run.
+    // (the device lists must be those of the evaluation the pinned block belongs to: a pfc_eval_dual_device + pfc_check of
+    // the caller's own in between keeps a pass of ITS point -- the serial tells the two apart)
+    const auto &pt = h->pin_din_pt;
+    const bool same = h->opt_dual_reuse && h->device_kept() && h->kept.n == n_items && pt.n == n_items && pt.serial == h->value_serial &&
+                      pt.ids == ids && h->dual_counts_cache.size() == n * 4 &&
+                      same_point(ValueBlock(pin.p, n, pt.ids_at), c.ins_ids, c.pose, c.twist, c.s, true);
+    if (same) {
+        // the seeds go behind the value block as before; the ids move behind them (another n_dir: another place), the results
+        // stay in front of the output block and the counters, whose place moves too, come from the cache
+        pack_seeds(pin.seeds(), c.d_pose, c.d_twist, c.d_s, true);
+        if (ids) std::memcpy(pin.values().ids(), c.ins_ids, sizeof(int) * n);
+        h->pin_din_pt.ids_at = pin.values().ids_at;
+        HIP_TRY(h, hipMemcpyAsync(dd.p, pin.seeds().p, dd.bytes(), hipMemcpyHostToDevice, st));
+        int rc = pfc_eval_dual_device_more(h, n_dir, dd.d_pose(), dd.d_twist(), dd.d_s(), ddo.d_wrench(), ddo.d_sdot(), st);
+        if (rc != PFC_OK) return rc;
+        HIP_TRY(h, hipMemcpyAsync(pout.partials().p, ddo.p, ddo.bytes(), hipMemcpyDeviceToHost, st));
+        rc = pfc_check(h);
+        if (rc != PFC_OK) return rc;
+        copy_out(ResultBlock(pout.p, n), c.wrench, c.sdot, nullptr);
+        if (c.counts) std::memcpy(c.counts, h->dual_counts_cache.data(), sizeof(int) * h->dual_counts_cache.size());
+        copy_out_dual(pout.partials(), c.d_wrench, c.d_sdot);
+        return PFC_OK;
+    }
+    h->pin_din_pt = {};
+    pack_values(pin.values(), c.ins_ids, c.pose, c.twist, c.s);
+    pack_seeds(pin.seeds(), c.d_pose, c.d_twist, c.d_s, true);
+    HIP_TRY(h, hipMemcpyAsync(din.p, pin.p, pin.bytes(ids), hipMemcpyHostToDevice, st));
+    const ValueBlock di = din.values(); const ResultBlock dr = dout.results();
+    int rc = PFC_OK;
+    for (int attempt = 0; attempt < 40; ++attempt) {
+        rc = pfc_eval_dual_device_bp(h, n_items, n_dir, ids ? di.ids() : nullptr, di.pose(), c.bp_pose, di.twist(), c.s ? di.s() : nullptr,
+                                     dd.d_pose(), dd.d_twist(), dd.d_s(), dr.wrench(), dr.sdot(), ddo.d_wrench(), ddo.d_sdot(), dr.counts(), st);
+        if (rc != PFC_OK) return rc;
+        HIP_TRY(h, hipMemcpyAsync(pout.p, dout.p, pout.bytes(), hipMemcpyDeviceToHost, st));
+        rc = pfc_check(h);
+        if (rc != PFC_ERR_OVERFLOW) break;
+    }
+    if (rc != PFC_OK) return rc;
+    c.deliver(pout.results(), pout.partials());
+    // what a following call at the same point needs: the counters (the pinned blocks keep the rest)
+    const int *pc = pout.results().counts();
+    h->dual_counts_cache.assign(pc, pc + n * 4);
+    h->pin_din_pt = {n_items, ids, h->value_serial, pin.values().ids_at};
+    return PFC_OK;
+}
+
+// Option debug, or PFC_DUAL_TWO_STAGE set for A/B runs: values, candidate list and per-item counters by the ordinary evaluation
+// (the broadphase ignores partials, src/contact_algorithms_non_friction.jl:95), read the contributing-pair count, then the
+// Dual passes: one pinned seed block up, one partial block down, as in pfc_eval (whose staging buffers are free again by then).
+int eval_dual_two_stage(pfc_context *h, const DualCall &c) {
+    const size_t nk = c.nk();
+    hipStream_t st = h->stream;
+    PassOpts o = {c.bp_pose, true};      // the value pass lists the contributing candidates
+    int rc = eval_host(h, c.n_items, c.ins_ids, c.pose, c.twist, c.s, c.wrench, c.sdot, c.counts, o);
+    if (rc != PFC_OK) return rc;
+    const SeedBlock ss(nullptr, nk); const PartialBlock ps(nullptr, nk);
+    HIP_TRY(h, ensure_graphed(h, h->dual_in, ss.doubles()));
+    HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
+    HIP_TRY(h, ensure_graphed(h, h->dual_res, nk * kDrStride));
+    HIP_TRY(h, ensure_graphed(h, h->dual_out, ps.doubles()));
+    HIP_TRY(h, h->pin_in.ensure(ss.bytes())); HIP_TRY(h, h->pin_out.ensure(ps.bytes()));
+    const SeedBlock dd(h->dual_in.p, nk); const PartialBlock ddo(h->dual_out.p, nk);
+    pack_seeds(SeedBlock(h->pin_in.p, nk), c.d_pose, c.d_twist, c.d_s, true);
+    HIP_TRY(h, hipMemcpyAsync(dd.p, h->pin_in.p, ss.bytes(), hipMemcpyHostToDevice, st));
+    rc = launch_dual(h, c.n_items, c.n_dir, h->tail.p, dd.d_pose(), dd.d_twist(), dd.d_s(), ddo.d_wrench(), ddo.d_sdot(), (size_t)h->stats[2], st, nullptr);
+    if (rc != PFC_OK) return rc;
+    h->dual_hint = h->stats[2];
+    HIP_TRY(h, hipMemcpyAsync(h->pin_out.p, ddo.p, ps.bytes(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    copy_out_dual(PartialBlock(h->pin_out.p, nk), c.d_wrench, c.d_sdot);
+    return PFC_OK;
+}
+
+// Which route takes a call, asked in this order; a route that returns PFC_ERR_OVERFLOW hands the call to the next.  The
+// environment variables are read on every call (tests and A/B runs flip them in a running process).
+// Fused: no bristle item, and not a repeat of the previous small-scene point (the all-in-one kernel keeps nothing; the hybrid
+// route hands lists over that the chunks after it reuse).
+bool takes_fused(const pfc_context *h, const DualCall &c, bool repeat) {
+    return !h->any_bristle && fused_ok(h, c.n_items, PassOpts{c.bp_pose}) && !repeat;
+}
+// Hybrid: also the first choice of pfc_eval_dual_device, for device buffers.
+bool takes_hybrid(const pfc_context *h, int n_items, size_t nk, const PassOpts &o) {
+    return fused_ok(h, n_items, o) && nk <= 4096 && (h->dual_hint >= 0 || !h->any_bristle) && std::getenv("PFC_NO_HYBRID") == nullptr;
+}
+// One graph: up to 512 items once a Dual evaluation has left a pair count to size the kept polygons from.
+bool takes_small(const pfc_context *h, const DualCall &c) {
+    return c.n_items <= 512 && c.nk() <= 4096 && h->dual_hint >= 0 && !h->opt_debug && !h->opt_fixed_order &&
+           !(h->opt_split_min > 0 && c.n_items >= h->opt_split_min);
+}
+bool takes_one_sync(const pfc_context *h) { return !h->opt_debug && std::getenv("PFC_DUAL_TWO_STAGE") == nullptr; }
 }  // namespace
 
 int pfc_eval_dual_device_bp(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const double *d_pose, const double *d_bp_pose,
@@ -2976,7 +3033,7 @@ int pfc_eval_dual_device_bp(pfc_handle h, int n_items, int n_dir, const int *d_i
     // hand-over list or a speculation that fell short) is reported by pfc_check as PFC_ERR_OVERFLOW and the re-issue takes
     // the batched value pass below.
     PassOpts o = {d_bp_pose};
-    if (fused_ok(h, n_items, o) && nk <= 4096 && (h->dual_hint >= 0 || !h->any_bristle) && std::getenv("PFC_NO_HYBRID") == nullptr) {
+    if (takes_hybrid(h, n_items, nk, o)) {
         if (h->dual_dev_hyb_skip > 0) {
             --h->dual_dev_hyb_skip;
         } else {
@@ -3032,7 +3089,7 @@ int pfc_eval_dual_device_more(pfc_handle h, int n_dir, const double *d_dpose, co
     HIP_TRY(h, zero_ds(h, nk, &d_ds, st));
     HIP_TRY(h, hipMemsetAsync(h->dual_acc.p, 0, sizeof(double) * nk * kDaStride, st));
     // the contributing pairs are known exactly (dual_hint, from the value pass pfc_check has seen): no speculation
-    const size_t bound = (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) + 64;
+    const size_t bound = dual_exact_bound(h);
     // The passes report (kStHole: a list entry out of range, capacity guards) into a word of their own, cleared here and read
     // back by pfc_check in front of its synchronisation: neither the value pass's status word (read by ITS k_final only) nor
     // the hand-over block (read with the pair count of a first chunk only) is looked at again on this path.
@@ -3069,15 +3126,15 @@ int pfc_local_jacobian_device(pfc_handle h, double *d_L, void *stream) {
     const size_t cap = h->ljac_seed.cap / kLjacSeedDoubles;
     HIP_TRY(h, h->ljac_out.ensure(n * kLjacSize));
     // as pfc_eval_dual_device_more: the exact pair count, and a status word of the passes' own that pfc_check reads back
-    const size_t bound = (size_t)(h->dual_hint > 0 ? h->dual_hint : 0) + 64;
+    const size_t bound = dual_exact_bound(h);
     HIP_TRY(h, h->h_more.ensure(4));
     unsigned *more_status = h->status.p + 1;
     HIP_TRY(h, hipMemsetAsync(more_status, 0, sizeof(unsigned), st));
     for (int p = 0; p < kLjacPasses; ++p) {
         const int nd = ljac_pass_dirs(p);
-        const double *dp = h->ljac_seed.p + cap * 576 * p, *dt = dp + cap * nd * 24, *dsd = dt + cap * nd * 6;
-        double *dw = h->ljac_out.p + n * 192 * p, *dsdot = dw + n * nd * 6;
-        const int rc = launch_dual(h, n_items, nd, h->tail.p, dp, dt, dsd, dw, dsdot, bound, st, nullptr, false,
+        const SeedBlock sd(h->ljac_seed.p + cap * 576 * p, cap * nd);
+        const PartialBlock pd(h->ljac_out.p + n * 192 * p, n * nd);
+        const int rc = launch_dual(h, n_items, nd, h->tail.p, sd.d_pose(), sd.d_twist(), sd.d_s(), pd.d_wrench(), pd.d_sdot(), bound, st, nullptr, false,
                                    h->kept.kind == pfc_context::KeptPass::HandOver ? h->emit_ctr.p : nullptr, more_status);
         if (rc != PFC_OK) return rc;
     }
@@ -3102,15 +3159,15 @@ int pfc_local_jacobian(pfc_handle h, int n_items, const int *ins_ids, const doub
     const size_t n = (size_t)n_items;
     Stage sg(c->stage, st);
     const int k_pose = sg.in(pose, n * 24), k_twist = sg.in(twist, n * 6), k_s = sg.in(s, n * 6), k_ids = sg.in(ins_ids, n);
-    const int k_zero = sg.scratch<double>(n * 36), k_dw = sg.scratch<double>(n * 6), k_dsd = sg.scratch<double>(n * 6);      // one direction of zero seeds and its partials
+    const int k_zero = sg.scratch<double>(SeedBlock(nullptr, n).doubles()), k_dw = sg.scratch<double>(n * 6), k_dsd = sg.scratch<double>(n * 6);      // one direction of zero seeds and its partials
     const int k_wr = sg.out(wrench, n * 6), k_sd = sg.out(sdot, n * 6), k_L = sg.out(L, n * kLjacSize), k_cnt = sg.out(counts, n * 4);
     HIP_TRY(h, sg.commit());
-    double *dz = sg.at<double>(k_zero);
-    HIP_TRY(h, hipMemsetAsync(dz, 0, sizeof(double) * n * 36, st));
+    const SeedBlock dz(sg.at<double>(k_zero), n);
+    HIP_TRY(h, hipMemsetAsync(dz.p, 0, dz.bytes(), st));
     int rc = PFC_OK;
     for (int attempt = 0; attempt < 40; ++attempt) {
-        rc = pfc_eval_dual_device(h, n_items, 1, sg.at<int>(k_ids), sg.at<double>(k_pose), sg.at<double>(k_twist), sg.at<double>(k_s), dz,
-                                  dz + n * 24, dz + n * 30, sg.at<double>(k_wr), sg.at<double>(k_sd), sg.at<double>(k_dw), sg.at<double>(k_dsd),
+        rc = pfc_eval_dual_device(h, n_items, 1, sg.at<int>(k_ids), sg.at<double>(k_pose), sg.at<double>(k_twist), sg.at<double>(k_s), dz.d_pose(),
+                                  dz.d_twist(), dz.d_s(), sg.at<double>(k_wr), sg.at<double>(k_sd), sg.at<double>(k_dw), sg.at<double>(k_dsd),
                                   sg.at<int>(k_cnt), st);
         if (rc != PFC_OK) return rc;
         rc = pfc_check(h);
@@ -4250,172 +4307,68 @@ int pfc_state_derivative_dual_device_more(pfc_handle h, int n_items, int n_dir, 
     return pfc_accelerations_dual_device(h, n_scene, n_dir, d_H, d_c, d_f, d_tau, d_dH, d_dc, d_df, d_dtau, nullptr, d_dvdot, nullptr, stream);
 }
 
-// The Dual evaluation, with the broadphase pose of m.float's state where bp_pose is given (calcTriTetIntersections!,
-// non_friction.jl:94-101): that block is kept in pinned host memory, which the value pass reads in place (96 bytes per item, once),
-// and handed down as an argument to whichever path runs the value pass.
+// The broadphase pose of a host Dual call (m.float's state: calcTriTetIntersections!, non_friction.jl:94-101) is kept in pinned
+// host memory, which the value pass reads in place (96 bytes per item, once): *bp_pose becomes that block's device-visible
+// address.  A pose other than the previous call's -- or none after one -- ends everything a previous evaluation left to reuse.
+static int keep_bp_pose(pfc_context *h, int n_items, const double **bp_pose) {
+    if (n_items <= 0) *bp_pose = nullptr;
+    if (!*bp_pose) {
+        if (h->pin_bp_n == 0) return PFC_OK;
+        // the previous host-buffer Dual evaluation culled with a pose of its own: its lists are not this evaluation's
+        end_kept_pass(h);
+        forget_host_points(h);
+        h->pin_bp_n = 0;
+        return PFC_OK;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t bytes = sizeof(double) * 24 * (size_t)n_items;
+    bool moved;
+    HIP_TRY(h, h->pin_bp.ensure(bytes, &moved));
+    if (moved) h->pin_bp_n = -1;
+    if (h->pin_bp_n != n_items || std::memcmp(h->pin_bp.p, *bp_pose, bytes) != 0) {
+        // another broadphase pose: nothing a previous Dual evaluation left can be reused (the candidate lists differ)
+        end_kept_pass(h);
+        forget_host_points(h);
+        std::memcpy(h->pin_bp.p, *bp_pose, bytes);
+        h->pin_bp_n = n_items;
+    }
+    void *dev = nullptr;
+    HIP_TRY(h, hipHostGetDevicePointer(&dev, h->pin_bp.p, 0));
+    *bp_pose = (const double *)dev;
+    return PFC_OK;
+}
+
+// The host-pointer Dual evaluation: argument checks, the broadphase pose, then the first route that takes the call (DESIGN.md
+// "Host Dual routes").
 int pfc_eval_dual_bp(pfc_handle h, int n_items, int n_dir, const int *ins_ids, const double *pose, const double *bp_pose,
                      const double *twist, const double *s, const double *d_pose, const double *d_twist, const double *d_s,
                      double *wrench, double *sdot, double *d_wrench, double *d_sdot, int *counts) {
     if (!h) return PFC_ERR_BAD_ARG;
     if (h->multi)
         return multi_eval_dual(h, n_items, n_dir, ins_ids, pose, bp_pose, twist, s, d_pose, d_twist, d_s, wrench, sdot, d_wrench, d_sdot, counts);
-    if (n_items <= 0) bp_pose = nullptr;
-    if (bp_pose) {
-        HIP_TRY(h, hipSetDevice(h->device));
-        const size_t bytes = sizeof(double) * 24 * (size_t)n_items;
-        bool moved;
-        HIP_TRY(h, h->pin_bp.ensure(bytes, &moved));
-        if (moved) h->pin_bp_n = -1;
-        if (h->pin_bp_n != n_items || std::memcmp(h->pin_bp.p, bp_pose, bytes) != 0) {
-            // another broadphase pose: nothing a previous Dual evaluation left can be reused (the candidate lists differ)
-            end_kept_pass(h);
-            h->pin_in_pt = {}; h->pin_din_pt = {};
-            std::memcpy(h->pin_bp.p, bp_pose, bytes);
-            h->pin_bp_n = n_items;
-        }
-        void *dev = nullptr;
-        HIP_TRY(h, hipHostGetDevicePointer(&dev, h->pin_bp.p, 0));
-        bp_pose = (const double *)dev;      // from here on: the device-visible block
-    }
-    if (!bp_pose && h->pin_bp_n != 0) {
-        // the previous host-buffer Dual evaluation culled with a pose of its own: its lists are not this evaluation's
-        end_kept_pass(h);
-        h->pin_in_pt = {}; h->pin_din_pt = {};
-        h->pin_bp_n = 0;
-    }
+    { const int rc = keep_bp_pose(h, n_items, &bp_pose); if (rc != PFC_OK) return rc; }
     if (n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "pfc_eval_dual: n_dir must be in 1..16");
     if (n_items > 0 && (!d_pose || !d_twist || !d_wrench || !d_sdot))
         return fail(h, PFC_ERR_BAD_ARG, "pfc_eval_dual: null buffer");
-    // the same argument checks in front of BOTH paths (the one-graph path used to skip them)
     { const int rc = check_eval_args(h, n_items, ins_ids, pose, twist, s, wrench, sdot); if (rc != PFC_OK) return rc; }
-    // A repeat of the previous small-scene Dual evaluation's point (the next chunk of a Jacobian): leave the all-in-one
-    // kernel, whose Dual passes keep nothing, for the hybrid path, which hands lists over that the chunks after it reuse.
+    // A repeat of the previous small-scene Dual evaluation's point (the next chunk of a Jacobian)?
     const bool repeat = n_items > 0 && h->opt_dual_reuse && h->pin_in_pt.n == n_items && h->pin_in.p && h->pin_in_pt.ids == (ins_ids != nullptr) &&
-                        same_point((const double *)h->pin_in.p, (size_t)n_items, h->pin_in_pt.ids_at, ins_ids, pose, twist, s, false);
+                        same_point(ValueBlock(h->pin_in.p, (size_t)n_items, h->pin_in_pt.ids_at), ins_ids, pose, twist, s, false);
     if (!repeat) h->pin_in_pt = {};
-    PassOpts o = {bp_pose};
-    if (n_items > 0 && !h->any_bristle && fused_ok(h, n_items, o) && !repeat) {
-        if (h->dual_fused_skip > 0) {
-            --h->dual_fused_skip;
-        } else {
-            HIP_TRY(h, hipSetDevice(h->device));
-            const int rc_f = eval_dual_fused(h, n_items, n_dir, ins_ids, pose, twist, s, d_pose, d_twist, wrench, sdot, d_wrench,
-                                             d_sdot, counts, bp_pose);
-            if (rc_f != PFC_ERR_OVERFLOW) return rc_f;       // else: an item did not fit -> the batched Dual paths below
-        }
+    if (n_items == 0) return PFC_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const DualCall c = {n_items, n_dir, ins_ids, pose, twist, s, d_pose, d_twist, d_s, wrench, sdot, d_wrench, d_sdot, counts, bp_pose};
+    int rc;
+    if (takes_fused(h, c, repeat)) {
+        if (h->dual_fused_skip > 0) --h->dual_fused_skip;
+        else if ((rc = eval_dual_fused(h, c)) != PFC_ERR_OVERFLOW) return rc;      // else: an item did not fit
     }
-    if (n_items > 0 && fused_ok(h, n_items, o) && (h->dual_hint >= 0 || !h->any_bristle) && (size_t)n_items * n_dir <= 4096 &&
-        std::getenv("PFC_NO_HYBRID") == nullptr) {
-        HIP_TRY(h, hipSetDevice(h->device));
-        const int rc_h = eval_dual_hybrid(h, n_items, n_dir, ins_ids, pose, twist, s, d_pose, d_twist, d_s, wrench, sdot, d_wrench,
-                                          d_sdot, counts, bp_pose);
-        if (rc_h != PFC_ERR_OVERFLOW) return rc_h;           // else: batched paths below (lists grown / speculation short)
+    if (takes_hybrid(h, n_items, c.nk(), PassOpts{bp_pose})) {
+        if ((rc = eval_dual_hybrid(h, c)) != PFC_ERR_OVERFLOW) return rc;          // else: lists grown / speculation short
         if (h->dual_dev_hyb_skip < 1) h->dual_dev_hyb_skip = 1;   // (not the same sequence again inside pfc_eval_dual_device)
     }
-    if (h->finalized && n_items > 0 && n_items <= 512 && (size_t)n_items * n_dir <= 4096 && h->dual_hint >= 0 && pose && twist &&
-        wrench && sdot && !h->opt_debug && !h->opt_fixed_order && !(h->opt_split_min > 0 && n_items >= h->opt_split_min)) {
-        HIP_TRY(h, hipSetDevice(h->device));
-        const int rc_small = eval_dual_small(h, n_items, n_dir, ins_ids, pose, twist, s, d_pose, d_twist, d_s, wrench, sdot,
-                                             d_wrench, d_sdot, counts, bp_pose);
-        if (rc_small != PFC_ERR_OVERFLOW) return rc_small;    // else: lists grown / speculation short -> two-stage path
-    }
-    if (n_items == 0) return PFC_OK;
-    const size_t nk = (size_t)n_items * n_dir;
-    hipStream_t st = h->stream;
-    if (!h->opt_debug && std::getenv("PFC_DUAL_TWO_STAGE") == nullptr) {
-        // One synchronisation: inputs up in one pinned block, pfc_eval_dual_device (value pass + Dual passes back to back,
-        // kept Dual polygons sized from the previous evaluation), results down in one pinned block, pfc_check.  A work
-        // list that overflowed or a speculation that fell short re-issues the evaluation (buffers have grown).
-        HIP_TRY(h, hipSetDevice(h->device));
-        const size_t n = (size_t)n_items;
-        const size_t in_d = n * 36 + nk * 36, in_bytes = in_d * sizeof(double) + n * sizeof(int);
-        const size_t out_d = n * 12 + nk * 12, out_bytes = out_d * sizeof(double) + n * 4 * sizeof(int);
-        {
-            bool in_moved, out_moved;
-            HIP_TRY(h, h->pin_din.ensure(in_bytes, &in_moved));
-            HIP_TRY(h, h->pin_dout.ensure(out_bytes, &out_moved));
-            if (in_moved || out_moved) h->pin_din_pt = {};      // reallocated: the cached blocks are gone
-        }
-        HIP_TRY(h, ensure_graphed(h, h->dual_in, in_d + (n + 1) / 2 + 1));
-        HIP_TRY(h, ensure_graphed(h, h->dual_out, out_d + (n * 4 + 1) / 2 + 1));
-        double *pi = (double *)h->pin_din.p;
-        double *pd = pi + n * 36;
-        double *di = h->dual_in.p, *dd = di + n * 36, *dout = h->dual_out.p, *ddo = dout + n * 12;
-        // Further seed directions at the point of the previous Dual evaluation (the chunks of one Jacobian: Radau calls
-        // the path ceil(NX / N_chunk) times with the same values and different partials, src/radau/radau_functions.jl:2-14):
-        // if the value inputs equal, bit for bit, those still sitting in the pinned input block, the value pass on the
-        // device is reused -- candidates, contributing pairs, per-item results -- and only the Dual passes run.
-        // (the device lists must be those of the evaluation the pinned block belongs to: a pfc_eval_dual_device + pfc_check of
-        // the caller's own in between keeps a pass of ITS point -- the serial tells the two apart)
-        const auto &pt = h->pin_din_pt;
-        const bool same = h->opt_dual_reuse && h->device_kept() && h->kept.n == n_items && pt.n == n_items && pt.serial == h->value_serial &&
-                          pt.ids == (ins_ids != nullptr) && h->dual_counts_cache.size() == n * 4 &&
-                          same_point(pi, n, pt.ids_at, ins_ids, pose, twist, s, true);
-        if (same) {
-            // the seeds go behind the value block as before (the ids of the cached evaluation are not needed again)
-            pack_seeds(pd, nk, d_pose, d_twist, d_s, true);
-            if (ins_ids) std::memcpy(pd + nk * 36, ins_ids, sizeof(int) * n);      // keep the block's layout: ids behind the seeds
-            h->pin_din_pt.ids_at = in_d;
-            HIP_TRY(h, hipMemcpyAsync(dd, pd, sizeof(double) * nk * 36, hipMemcpyHostToDevice, st));
-            int rc3 = pfc_eval_dual_device_more(h, n_dir, dd, dd + nk * 24, dd + nk * 30, ddo, ddo + nk * 6, st);
-            if (rc3 != PFC_OK) return rc3;
-            double *pdo = (double *)h->pin_dout.p + n * 12;
-            HIP_TRY(h, hipMemcpyAsync(pdo, ddo, sizeof(double) * nk * 12, hipMemcpyDeviceToHost, st));
-            rc3 = pfc_check(h);
-            if (rc3 != PFC_OK) return rc3;
-            copy_out((const double *)h->pin_dout.p, h->dual_counts_cache.data(), n, wrench, sdot, counts);
-            copy_out_dual(pdo, nk, d_wrench, d_sdot);
-            return PFC_OK;
-        }
-        h->pin_din_pt = {};
-        pack_values(pi, n, in_d, ins_ids, pose, twist, s);
-        pack_seeds(pd, nk, d_pose, d_twist, d_s, true);
-        HIP_TRY(h, hipMemcpyAsync(di, pi, ins_ids ? in_bytes : in_d * sizeof(double), hipMemcpyHostToDevice, st));
-        int rc2 = PFC_OK;
-        for (int attempt = 0; attempt < 40; ++attempt) {
-            rc2 = pfc_eval_dual_device_bp(h, n_items, n_dir, ins_ids ? (const int *)(di + in_d) : nullptr, di, bp_pose, di + n * 24,
-                                          s ? di + n * 30 : nullptr, dd, dd + nk * 24, dd + nk * 30, dout, dout + n * 6,
-                                          ddo, ddo + nk * 6, (int *)(dout + out_d), st);
-            if (rc2 != PFC_OK) return rc2;
-            HIP_TRY(h, hipMemcpyAsync(h->pin_dout.p, dout, out_bytes, hipMemcpyDeviceToHost, st));
-            rc2 = pfc_check(h);
-            if (rc2 != PFC_ERR_OVERFLOW) break;
-        }
-        if (rc2 != PFC_OK) return rc2;
-        const double *po = (const double *)h->pin_dout.p;
-        const int *pc = reinterpret_cast<const int *>(po + out_d);
-        copy_out(po, pc, n, wrench, sdot, counts);
-        copy_out_dual(po + n * 12, nk, d_wrench, d_sdot);
-        // what a following call at the same point needs: the counters (the pinned blocks keep the rest)
-        h->dual_counts_cache.assign(pc, pc + n * 4);
-        h->pin_din_pt = {n_items, ins_ids != nullptr, h->value_serial, in_d};
-        return PFC_OK;
-    }
-    // two-stage path (debug option, or PFC_DUAL_TWO_STAGE set for A/B runs): values, candidate list and per-item counters
-    // by the ordinary evaluation (the broadphase ignores partials, src/contact_algorithms_non_friction.jl:95), read the
-    // contributing-pair count, then the Dual passes
-    o.list = true;
-    int rc = eval_host(h, n_items, ins_ids, pose, twist, s, wrench, sdot, counts, o);
-    if (rc != PFC_OK) return rc;
-    HIP_TRY(h, ensure_graphed(h, h->dual_in, nk * 36));
-    HIP_TRY(h, ensure_graphed(h, h->dual_acc, nk * kDaStride));
-    HIP_TRY(h, ensure_graphed(h, h->dual_res, nk * kDrStride));
-    HIP_TRY(h, ensure_graphed(h, h->dual_out, nk * 12));
-    double *dp = h->dual_in.p, *dt = dp + nk * 24, *dsd = dt + nk * 6;
-    // one pinned block up (d_pose | d_twist | d_s), one down (d_wrench | d_sdot), as in pfc_eval (whose staging
-    // buffers are free again at this point)
-    const size_t in_bytes = sizeof(double) * nk * 36, out_bytes = sizeof(double) * nk * 12;
-    HIP_TRY(h, h->pin_in.ensure(in_bytes));
-    HIP_TRY(h, h->pin_out.ensure(out_bytes));
-    pack_seeds((double *)h->pin_in.p, nk, d_pose, d_twist, d_s, true);
-    HIP_TRY(h, hipMemcpyAsync(dp, h->pin_in.p, in_bytes, hipMemcpyHostToDevice, st));
-    rc = launch_dual(h, n_items, n_dir, h->tail.p, dp, dt, dsd, h->dual_out.p, h->dual_out.p + nk * 6, (size_t)h->stats[2], st, nullptr);
-    if (rc != PFC_OK) return rc;
-    h->dual_hint = h->stats[2];
-    HIP_TRY(h, hipMemcpyAsync(h->pin_out.p, h->dual_out.p, out_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    copy_out_dual((const double *)h->pin_out.p, nk, d_wrench, d_sdot);
-    return PFC_OK;
+    if (takes_small(h, c) && (rc = eval_dual_small(h, c)) != PFC_ERR_OVERFLOW) return rc;      // else: as above
+    return takes_one_sync(h) ? eval_dual_one_sync(h, c) : eval_dual_two_stage(h, c);
 }
 
 int pfc_eval_dual(pfc_handle h, int n_items, int n_dir, const int *ins_ids, const double *pose, const double *twist,

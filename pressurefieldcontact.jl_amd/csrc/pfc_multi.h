@@ -366,7 +366,7 @@ int multi_eval_device(pfc_context *h, int n_items, int n_dir, const int *d_ins_i
     auto stage = [&](int k) -> int {
         pfc_multi::Stage &S = M->stage[k];
         const size_t n = (size_t)(M->bound[k + 1] - M->bound[k]);
-        HIP_TRY(h, S.in.ensure(n * 60)); HIP_TRY(h, S.out.ensure(n * 12)); HIP_TRY(h, S.cnt.ensure(n * 4));
+        HIP_TRY(h, S.in.ensure(ValueBlock(nullptr, n).doubles() + n * 24)); HIP_TRY(h, S.out.ensure(ResultBlock(nullptr, n).doubles())); HIP_TRY(h, S.cnt.ensure(n * 4));
         if (d_ins_ids) HIP_TRY(h, S.ids.ensure(n));
         else return multi_dev_iota(h, k, n_items);
         return PFC_OK;
@@ -390,22 +390,22 @@ int multi_eval_device(pfc_context *h, int n_items, int n_dir, const int *d_ins_i
         const int dk = M->dev[k];
         const size_t n = (size_t)nk;
         const int *idk = d_ins_ids ? S.ids.p : S.iota.p + b0;
-        double *ip = S.in.p, *it = ip + n * 24, *is = it + n * 6, *ib = is + n * 6;
+        const ValueBlock vi(S.in.p, n); const ResultBlock ro(S.out.p, n);      // (ids and counts apart: S.ids, S.cnt; the broadphase pose behind the values)
+        double *ip = vi.pose(), *it = vi.twist(), *is = vi.s(), *ib = vi.p + vi.doubles(), *ow = ro.wrench(), *os = ro.sdot();
         if (d_ins_ids) HIP_TRY(h, multi_copy(S.ids.p, dk, d_ins_ids + b0, dev0, sizeof(int) * n, sk));
         HIP_TRY(h, multi_copy(ip, dk, d_pose + 24 * b0, dev0, sizeof(double) * n * 24, sk));
         HIP_TRY(h, multi_copy(it, dk, d_twist + 6 * b0, dev0, sizeof(double) * n * 6, sk));
         if (d_s) HIP_TRY(h, multi_copy(is, dk, d_s + 6 * b0, dev0, sizeof(double) * n * 6, sk));
         if (d_bp) HIP_TRY(h, multi_copy(ib, dk, d_bp + 24 * b0, dev0, sizeof(double) * n * 24, sk));
-        double *ow = S.out.p, *os = ow + n * 6;
         if (n_dir == 0) {
             rc = pfc_eval_device(c, nk, idk, ip, it, d_s ? is : nullptr, ow, os, S.cnt.p, sk);
         } else {
-            HIP_TRY(h, S.din.ensure(n * nd * 36)); HIP_TRY(h, S.dout.ensure(n * nd * 12));
-            double *dp = S.din.p, *dt = dp + n * nd * 24, *dsd = dt + n * nd * 6;
+            HIP_TRY(h, S.din.ensure(SeedBlock(nullptr, n * nd).doubles())); HIP_TRY(h, S.dout.ensure(PartialBlock(nullptr, n * nd).doubles()));
+            const SeedBlock sd(S.din.p, n * nd); const PartialBlock pd(S.dout.p, n * nd);
+            double *dp = sd.d_pose(), *dt = sd.d_twist(), *dsd = sd.d_s(), *dw = pd.d_wrench(), *dsdot = pd.d_sdot();
             HIP_TRY(h, multi_copy(dp, dk, d_dpose + 24 * nd * b0, dev0, sizeof(double) * n * nd * 24, sk));
             HIP_TRY(h, multi_copy(dt, dk, d_dtwist + 6 * nd * b0, dev0, sizeof(double) * n * nd * 6, sk));
             if (d_ds) HIP_TRY(h, multi_copy(dsd, dk, d_ds + 6 * nd * b0, dev0, sizeof(double) * n * nd * 6, sk));
-            double *dw = S.dout.p, *dsdot = dw + n * nd * 6;
             rc = pfc_eval_dual_device_bp(c, nk, n_dir, idk, ip, d_bp ? ib : nullptr, it, d_s ? is : nullptr, dp, dt, d_ds ? dsd : nullptr,
                                          ow, os, dw, dsdot, S.cnt.p, sk);
             if (rc == PFC_OK) {
@@ -438,7 +438,7 @@ int multi_eval_dual_device_more(pfc_context *h, int n_dir, const double *d_dpose
     auto stage = [&](int k) -> int {
         pfc_multi::Stage &S = M->stage[k];
         const size_t n = (size_t)(M->bound[k + 1] - M->bound[k]);
-        HIP_TRY(h, S.din.ensure(n * nd * 36)); HIP_TRY(h, S.dout.ensure(n * nd * 12));
+        HIP_TRY(h, S.din.ensure(SeedBlock(nullptr, n * nd).doubles())); HIP_TRY(h, S.dout.ensure(PartialBlock(nullptr, n * nd).doubles()));
         return PFC_OK;
     };
     auto run = [&](int k, hipStream_t sk) -> int {
@@ -451,7 +451,8 @@ int multi_eval_dual_device_more(pfc_context *h, int n_dir, const double *d_dpose
         pfc_multi::Stage &S = M->stage[k];
         const int dk = M->dev[k];
         const size_t b0 = (size_t)M->bound[k], n = (size_t)M->bound[k + 1] - b0;
-        double *dp = S.din.p, *dt = dp + n * nd * 24, *dsd = dt + n * nd * 6, *dw = S.dout.p, *dsdot = dw + n * nd * 6;
+        const SeedBlock sd(S.din.p, n * nd); const PartialBlock pd(S.dout.p, n * nd);
+        double *dp = sd.d_pose(), *dt = sd.d_twist(), *dsd = sd.d_s(), *dw = pd.d_wrench(), *dsdot = pd.d_sdot();
         HIP_TRY(h, multi_copy(dp, dk, d_dpose + 24 * nd * b0, dev0, sizeof(double) * n * nd * 24, sk));
         HIP_TRY(h, multi_copy(dt, dk, d_dtwist + 6 * nd * b0, dev0, sizeof(double) * n * nd * 6, sk));
         if (d_ds) HIP_TRY(h, multi_copy(dsd, dk, d_ds + 6 * nd * b0, dev0, sizeof(double) * n * nd * 6, sk));

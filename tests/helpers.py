@@ -533,3 +533,66 @@ def host_tree_workload(pfc, scene, n_items, seed=7, fine=False, span=None):
     pose, twist, s = host_tree_poses(pfc, np.random.default_rng(seed), n_items, span)     # the same poses for every scene
     ids = (np.arange(n_items) % 2).astype(np.int32)
     return Cf.Workload("host trees: " + scene, meshes, ins, ids, pose, twist, s)
+
+
+# ---- the host Dual routes (tests/test_gpu_dual.py::test_host_dual_routes, scripts/dual_routes_dump.py) -------------------------
+DUAL_ROUTE_BATCH = 516      # items of the large batch: beyond the one-graph route's 512
+
+
+def dual_route_scenes(pfc):
+    """{name: (Workload, k)}: "boxes" (C1's four regularized items) and "blob" (two bristle poses of a reduced C3), each tiled to
+    DUAL_ROUTE_BATCH items with one instruction PER ITEM, so that a call may leave ins_ids out (item i is instruction i) at
+    every size.  Item i repeats item i % k: an oracle result of the k distinct items checks the whole batch."""
+    Cf = pfc.configs
+    out = {}
+    for name, base in (("boxes", Cf.c1_boxes()), ("blob", Cf.c3_blob_tool(2, seed=3, n_div_blob=6, n_div_tool=4))):
+        k = base.n_items
+        reps = DUAL_ROUTE_BATCH // k
+        ins = [base.instructions[int(i)] for i in base.ins_ids] * reps
+        out[name] = (Cf.Workload(name, base.meshes, ins, np.arange(k * reps, dtype=np.int32), np.tile(base.pose, (reps, 1)),
+                                 np.tile(base.twist, (reps, 1)), np.tile(base.s, (reps, 1))), k)
+    return out
+
+
+def dual_route_seeds(w, k, n_dir, seed):
+    """(d_pose, d_twist, d_s) of the batch: random seeds of the k distinct items (d_pose tangent to the pose), tiled like the items."""
+    from test_oracle_dual import tangents
+    rng = np.random.default_rng(seed)
+    dq = rng.standard_normal((k, n_dir, 6)) * np.array([1, 1, 1, 0.05, 0.05, 0.05])
+    d_pose = np.array([tangents(w.pose[i][:9].reshape(3, 3, order="F"), w.pose[i][9:12], dq[i]) for i in range(k)])
+    d_twist = rng.standard_normal((k, n_dir, 6)) * np.array([1, 1, 1, 0.1, 0.1, 0.1])
+    d_s = rng.standard_normal((k, n_dir, 6)) * 1e-3
+    reps = w.n_items // k
+    return tuple(np.ascontiguousarray(np.tile(a, (reps, 1, 1))) for a in (d_pose, d_twist, d_s))
+
+
+def dual_route_steps(m, w, seeds, ids_given, s_given):
+    """One handle through every host Dual route it can take.  seeds: {"A", "B": 6 directions; "C", "D": 2 directions}
+    (dual_route_seeds).  Yields (label, n_items, seed name, result of force_all_elastic_intersections_dual, (pfc_last_parts,
+    pfc_last_team, pfc_last_dual_reused)).  The value evaluation in front ends whatever an earlier sequence on the handle kept."""
+    import os
+
+    def call(n, name):
+        sd = seeds[name]
+        out = m.force_all_elastic_intersections_dual(w.pose[:n], w.twist[:n], w.s[:n] if s_given else None, sd[0][:n], sd[1][:n],
+                                                     sd[2][:n] if s_given else None, w.ins_ids[:n] if ids_given else None)
+        return n, name, out, (m.last_parts(), m.last_team(), int(m.last_dual_reused()))
+
+    m.force_all_elastic_intersections(w.pose[:2], w.twist[:2], w.s[:2] if s_given else None, w.ins_ids[:2] if ids_given else None)
+    big = w.n_items
+    try:
+        yield ("first",) + call(2, "A")
+        yield ("repeat",) + call(2, "B")
+        yield ("chunk",) + call(2, "A")
+        os.environ["PFC_NO_HYBRID"] = "1"
+        yield ("one-graph",) + call(2, "B")
+        yield ("one-graph chunk",) + call(2, "A")
+        os.environ.pop("PFC_NO_HYBRID")
+        yield ("one-sync",) + call(big, "C")
+        yield ("one-sync chunk",) + call(big, "D")
+        os.environ["PFC_DUAL_TWO_STAGE"] = "1"
+        yield ("two-stage",) + call(big, "C")
+        yield ("two-stage again",) + call(big, "D")
+    finally:
+        os.environ.pop("PFC_NO_HYBRID", None)
+        os.environ.pop("PFC_DUAL_TWO_STAGE", None)

@@ -806,3 +806,67 @@ def test_one_handle_across_the_entry_points(pfc, cfg):
     assert len(route) == len(ROUTE_STEPS)
     for name, got, want in zip(ROUTE_STEPS, route, ROUTE_EXPECTED[cfg]):
         assert got == want, (cfg, name, got, want)
+
+
+# (pfc_last_parts, pfc_last_team, pfc_last_dual_reused) after each step of helpers.dual_route_steps, recorded by running this
+# test's body on the build of the commit before the host Dual routes became functions behind one chooser (c81e139).
+# parts 0: the small-scene kernel ran the value pass (all-in-one, or handing over to the batched Dual passes); reused 1: only the
+# Dual passes ran.  What tells the routes apart is the sequence: the all-in-one kernel keeps nothing, so "repeat" is a full
+# evaluation -- by the hybrid route, or "chunk" could not reuse it; on a handle with a bristle instruction the first call is the
+# hybrid route's already and "repeat" reuses it; without the hybrid route the one-graph route runs the batched value pass (parts 1)
+# and its chunk reuses that (bristle handle; on the regularized one the one-graph route forgets the point, and its chunk goes back
+# to the all-in-one kernel); the large batch reuses through pfc_eval_dual_device_more, and never on the two-stage route.
+HOST_ROUTE_STEPS = ("first", "repeat", "chunk", "one-graph", "one-graph chunk", "one-sync", "one-sync chunk", "two-stage", "two-stage again")
+HOST_ROUTE_EXPECTED = {
+    "boxes": ((0, 1, 0), (0, 1, 0), (0, 1, 1), (1, 0, 0), (0, 1, 0), (1, 0, 0), (1, 0, 1), (1, 0, 0), (1, 0, 0)),
+    "blob": ((0, 1, 0), (0, 1, 1), (0, 1, 1), (1, 0, 0), (1, 0, 1), (1, 0, 0), (1, 0, 1), (1, 0, 0), (1, 0, 0)),
+}
+
+
+def test_host_dual_routes(pfc, O):
+    """Every route of the host-pointer Dual call -- all-in-one, hybrid, one-graph, one-sync, two-stage, and the reuse of each that
+    keeps its value pass -- from one handle per scene (a handle with a bristle instruction never takes the all-in-one kernel: the
+    regularized handle drives all five, the bristle handle the other four, after a first evaluation has set its pair count):
+    2 items, then a batch above 512; with and without ins_ids, and on the regularized scene with s and d_s null.  Each step: the
+    route taken (HOST_ROUTE_EXPECTED), partials against the Dual oracle at this file's tolerances (run_case), values and counts
+    against the handle's own pfc_eval as run_case compares them."""
+    import helpers as H
+    for scene, (w, k) in H.dual_route_scenes(pfc).items():
+        seeds = {name: H.dual_route_seeds(w, k, nd, 100 + j) for j, (name, nd) in enumerate((("A", 6), ("B", 6), ("C", 2), ("D", 2)))}
+        om = oracle_meshes(w)
+        m = pfc.configs.build_scenario(w)
+        if scene == "blob":      # the first Dual evaluation of a bristle handle has no pair count to speculate from: one-sync, batched
+            sd = seeds["A"]
+            m.force_all_elastic_intersections_dual(w.pose[:2], w.twist[:2], w.s[:2], sd[0][:2], sd[1][:2], sd[2][:2], w.ins_ids[:2])
+            assert (m.last_parts(), m.last_team(), int(m.last_dual_reused())) == (1, 0, 0)
+        val = m.force_all_elastic_intersections(w.pose, w.twist, w.s, w.ins_ids)
+        variants = [(True, True), (False, True)] + ([(True, False), (False, False)] if scene == "boxes" else [])
+        ref = {}      # (seed name, s given) -> oracle partials of the k distinct items
+        for ids_given, s_given in variants:
+            route = []
+            for label, n, name, got, r in H.dual_route_steps(m, w, seeds, ids_given, s_given):
+                route.append(r)
+                if (name, s_given) not in ref:
+                    sd = seeds[name]
+                    ref[name, s_given] = [O.evaluate_dual(om[c.id_1], om[c.id_2], oracle_ins(pfc, c), w.pose[i], w.twist[i], w.s[i], sd[0][i], sd[1][i],
+                                                          sd[2][i] if s_given else np.zeros_like(sd[2][i]))
+                                          for i, c in enumerate(w.instructions[:k])]
+                wr, sdt, dw, dsd, counts = got
+                what = (scene, ids_given, s_given, label)
+                assert np.array_equal(counts, val[2][:n]), what
+                np.testing.assert_allclose(wr, val[0][:n], rtol=1e-11, atol=1e-11 * np.abs(val[0]).max(), err_msg=str(what))
+                np.testing.assert_allclose(sdt, val[1][:n], rtol=1e-7, atol=1e-7 * max(np.abs(val[1]).max(), 1e-300), err_msg=str(what))
+                assert counts[:, 3].min() > 0, what
+                worst = [0.0, 0.0]
+                for i in range(n):
+                    st, rw, rs, rdw, rdsd = ref[name, s_given][i % k]
+                    assert st == 0
+                    worst[0] = max(worst[0], np.abs(dw[i] - rdw).max() / max(np.abs(rdw).max(), 1e-300))
+                    worst[1] = max(worst[1], np.abs(dsd[i] - rdsd).max() / max(np.abs(rdsd).max(), 1e-300))
+                print(f"host route {what}: {r}, partials off the oracle by {worst[0]:.2e} (wrench), {worst[1]:.2e} (sdot)")
+                assert worst[0] <= 1e-6 and worst[1] <= 1e-5, (what, worst)
+            print(f"host routes {scene} ids={ids_given} s={s_given}: {tuple(route)!r}")
+            assert len(route) == len(HOST_ROUTE_STEPS)
+            for label, got_r, want_r in zip(HOST_ROUTE_STEPS, route, HOST_ROUTE_EXPECTED[scene]):
+                assert got_r == want_r, (scene, ids_given, s_given, label, got_r, want_r)
+        m.close()
