@@ -250,16 +250,31 @@ __device__ __forceinline__ NodeF load_nodef(const NodeF *n) {
 //       representation, u |v_i| from the input; c = u x v - w v: three roundings of partial sums <= |v|_2: 3 u |v|_1;
 //       d = u x c (|c|_2 <= |v|_2): sqrt 2 x 3 u + 2 u = 6.3 u |v|_1; t = v + 2 d: 12.6 u + u.  |dt_i| <= 19 u |v|_1, and
 //       |t|_2 <= |v|_2 (1 + 1e-6).
-//   (4) Axes, leaf involved.  Face axis of B, |sum_i R_ij t_i| - (sum_i |R_ij| e_a,i + e_b,j), is the worst: dR against
-//       |t|_1 <= sqrt 3 |v|_1: 248 u |v|_1; dt against a column of R: 33 u |v|_1; three fused roundings 5 u |v|_1; r_a: (143 +
-//       1 + 3) u sum e_a; e_b,j: u; sum and difference 2 u S: below 290 u S.  Edge-edge axes: dR (|t_u| + |t_v|) <= 143 sqrt 2
-//       u |v|_1 = 203 u, dt 27 u, roundings 3 u; r_a + r_b: 146 u sum e; + 2 u S: below 236 u S.  Face axis of A: below 150 u S.
-//       E = 320 u S holds with 10 % to spare.
+//   (4) Axes, leaf involved.  sat15_f32_core forms an axis's radius sum s = r_a + r_b as ONE chain of fused multiply-adds over
+//       its terms e |R_..| (a face axis seeds the chain with its own extent, an edge x edge axis with its first product) and
+//       subtracts it from |T.L| once: d = |T.L| - s.  Every term is >= 0, so every partial sum of the chain is <= s and each of
+//       its roundings is <= u s; with |R_..| <= 1 + 143 u, s <= (1 + 143 u) x the sum of the extents that enter.  Per axis:
+//         face of B (j): |sum_i R_ij t_i| - fma(|R_2j|, e_a2, fma(|R_1j|, e_a1, fma(|R_0j|, e_a0, e_bj))), the worst.  |T.L|: dR
+//           against |t|_1 <= sqrt 3 |v|_1: 248 u |v|_1; dt against a column of R: 33 u |v|_1; its three roundings: 5 u |v|_1.
+//           Chain: dR 143 u sum e_a, inputs u sum e_a + u e_bj, THREE roundings 3 u (e_bj + sum e_a): 147 u sum e_a + 4 u e_bj.
+//           The difference rounds once: u max(|T.L|, s) <= u S.  Together 286 u |v|_1 + 147 u sum e_a + 4 u e_bj + u S <= 287 u S.
+//         edge x edge: |T.L|: dR (|t_u| + |t_v|) <= 143 sqrt 2 u |v|_1 = 203 u, dt 27 u, roundings 3 u: 233 u |v|_1.  Chain of four
+//           products, a multiplication and three fused multiply-adds: dR 143 u sum e, inputs u sum e, FOUR roundings 4 u sum e:
+//           148 u sum e.  Difference u S: <= 234 u S.
+//         face of A (i): |t_i|: 19 u |v|_1; chain seeded with e_ai: 147 u sum e_b + 4 u e_ai; difference u S: <= 148 u S.
+//       (Before, r_a and r_b were formed apart and added: edge x edge rounded 2 + 2 + 1 times with the bound 3 u (r_a + r_b) where
+//       the chain has 4 u (r_a + r_b) -- one u more on sum e, whose coefficient 148 stays far below the 233 of |v|_1, so the axis
+//       bound does not move with it -- and the face axes rounded 3 + 1 times where the seeded chain rounds 3 times; the sum's
+//       rounding is gone from every axis: the bounds were 288, 235 and 150 u S.)
+//       E = 320 u S holds with 33 u S, 10 %, to spare.
 //   (5) Axes, both boxes axis aligned (identity quaternions; every internal x internal pair): the two quaternion products
 //       return q_a_b(float) exactly (factors 1 and 0), quat_rot_inv returns v exactly, so |dR| <= 4 u + 5 u and t = v.
-//       Face axis of A: u |t_i| + u e_a,i + (9 + 1 + 3) u sum e_b + 2 u S <= 15 u S; face axis of B: (9 + 1 + 3) u |v|_1 +
-//       13 u sum e_a + u e_b,j + 2 u S <= 15 u S; edge-edge: (9 + 1) u on each product + 2 u of fused rounding, + 2 u S:
-//       <= 14 u S.  E = 24 u S.
+//         face of A (i): u |t_i|; chain: (9 + 1) u sum e_b + u e_ai from dR and the inputs, three roundings 3 u (e_ai + sum e_b);
+//           difference u S: u |t_i| + 13 u sum e_b + 4 u e_ai + u S <= 14 u S.
+//         face of B (j): (9 + 1 + 3) u |v|_1; chain 13 u sum e_a + 4 u e_bj; difference u S: <= 14 u S.
+//         edge x edge: (9 + 1) u on each product + 2 u of fused rounding: 12 u |v|_1; chain: (9 + 1) u on each product + four
+//           roundings: 14 u sum e; difference u S: <= 15 u S (before: 14; the face axes 15).
+//       E = 24 u S holds with 9 u S, 37 %, to spare.
 //       Premise: a pair without a leaf (any_leaf = false, the 24 u radius) holds two identity quaternions.  The library's
 //       builders only make such internal boxes; a host-supplied tree may rotate them.  Enforced in pfc_add_mesh: an
 //       internal node whose R is not bitwise the identity gets the exact-only mark (NaN e[0]), so every pair with such a
@@ -268,7 +283,9 @@ __device__ __forceinline__ NodeF load_nodef(const NodeF *n) {
 // 15 axes proves it does not separate on any; everything else is settled by the exact Float64 test.  The constants in the
 // code are 1.44e-6 (>= 24 u = 1.4305e-6) and 1.92e-5 (>= 320 u = 1.9073e-5).  tests/test_gpu_broadphase.py probes touching
 // configurations at 1 -/+ {1e-3, 1e-6, 1e-9, 1e-12} against the oracle for both box kinds; tests/test_bp_error_bound.py
-// samples a NumPy Float32 emulation of this function against these bounds (worst observed: |dR| 13 u, |d_float - d_ref| 8 u S).
+// samples a NumPy Float32 emulation of this function as it stood before the radius chains (worst observed: |dR| 13 u,
+// |d_float - d_ref| 8 u S), tests/test_bp_radii_chain.py one of the chains (worst observed: 6.7 u S with a leaf, 3.0 u S
+// without; touching configurations 2.6 and 1.3 u S).  The constants did not have to change for the chains.
 // one node pair of k_bp_dfs32: returns 0 = separated, 1 = overlapping, 2 = undecided
 __device__ __forceinline__ int test_pair_f32(const NodeF &a, const NodeF &b, bool any_leaf, const float *R12,
                                              const float *q12, const float *t12, float eabs) {
@@ -424,10 +441,7 @@ __global__ void __launch_bounds__(BLK, 4) k_bp_dfs32(Dfs32Args g) {
     __shared__ int und_v[BLK];            // their exact verdicts
     __shared__ double xs[(BLK / 16) * 33];
     __shared__ int s_seed, s_base, s_def[2];   // s_def: parked-pair counters, alternating by iteration parity
-    __shared__ double s_pose[12];         // R_a_b (9, column-major), t_a_b (3) of the current seed's item
-    __shared__ float s_q12[4];            // unit quaternion of R_a_b (Float32), from the item record
-    __shared__ float s_posef[13];         // fl32 of R_a_b, t_a_b (the centre offset of the single-precision test) and bp_eabs
-    __shared__ int s_pose_exact;          // the pose failed pose_quat's check: every test of the seed is settled exactly
+    __shared__ double s_pose[12];         // R_a_b (9, column-major), t_a_b (3) of the current seed's item: the exact test's
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int n_seed = *g.n_seed;
     if (n_seed > g.seed_cap) n_seed = g.seed_cap;
@@ -447,13 +461,27 @@ __global__ void __launch_bounds__(BLK, 4) k_bp_dfs32(Dfs32Args g) {
         }
         const int item = __builtin_amdgcn_readfirstlane(s.item);   // uniform: scalar loads of the pose below
         const ItemRec *it = g.items + item;
-        // the item's pose lives in LDS (broadcast reads inside the iteration) rather than in 33 registers that would
-        // stay live across the call of the exact test
-        if (tid < 9) { const double x = it->R12[tid]; s_pose[tid] = x; s_posef[tid] = (float)x; }
-        else if (tid < 12) { const double x = it->t12[tid - 9]; s_pose[tid] = x; s_posef[tid] = (float)x; }
-        else if (tid < 16) s_q12[tid - 12] = it->q12[tid - 12];     // formed and checked once per item (k_setup_items, pose_quat)
-        else if (tid == 16) s_pose_exact = it->pose_exact;
-        else if (tid == 17) s_posef[12] = it->bp_eabs;
+        // the exact test's Float64 pose lives in LDS (broadcast reads) rather than in 24 registers that would stay live
+        // across the iteration
+        if (tid < 9) s_pose[tid] = it->R12[tid];
+        else if (tid < 12) s_pose[tid] = it->t12[tid - 9];
+        // What the single-precision test reads of the pose is the same for every lane and every iteration of the seed: 18
+        // values held as SCALARS (s_load through the uniform item pointer, once per seed; formed and checked once per item
+        // by k_setup_items).  Each multiply-add of the test takes exactly one of them, so they enter as scalar operands;
+        // before, every lane copied them from LDS into registers in every iteration (SQ_INSTS_LDS of a half-launch of the
+        // 8 192-pose step 29.5 M -> 18.3 M, 104 -> 86 VGPRs).
+        float R12[9], t12[3], q12[4];
+        {
+            cfloat *pf = (cfloat *)it->R12f, *pt = (cfloat *)it->t12f, *pq = (cfloat *)it->q12;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) R12[k] = pf[k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) t12[k] = pt[k];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) q12[k] = pq[k];
+        }
+        const float eabs = *(cfloat *)&it->bp_eabs;
+        const int pose_exact = *(cint *)&it->pose_exact;   // the pose failed pose_quat's check: every test of the seed is settled exactly
         const NodeF *n1 = it->nf1, *n2 = it->nf2;
         int sp = 1, n_out = 0, n_test = 0, n_cand = 0, n_def = 0, n_und = 0;
         if (tid == 0) {
@@ -502,13 +530,6 @@ __global__ void __launch_bounds__(BLK, 4) k_bp_dfs32(Dfs32Args g) {
                 STAMP(u1);
 #endif
                 if (!settle) {
-                    float R12[9], t12[3], q12[4];
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) R12[k] = s_posef[k];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) t12[k] = s_posef[9 + k];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) q12[k] = s_q12[k];
                     // Issue priority: the ~250 instructions of the test run at the default level, everything else of an
                     // iteration (ballots, prefix, push, pop, the next node loads: a few dozen instructions between two
                     // barriers and two memory round trips) one level above it.  In-kernel stamps had shown those short
@@ -517,9 +538,9 @@ __global__ void __launch_bounds__(BLK, 4) k_bp_dfs32(Dfs32Args g) {
                     // first (exclusive 2.06 -> 1.95 ms for the 8 192-pose batch, step 4.40 -> 4.27 ms; levels 1, 2, 3
                     // alike).  The same in the clip kernel and k_integ changed nothing.
                     __builtin_amdgcn_s_setprio(0);
-                    verdict = test_pair_f32(a, b, la || lb, R12, q12, t12, s_posef[12]);
+                    verdict = test_pair_f32(a, b, la || lb, R12, q12, t12, eabs);
                     __builtin_amdgcn_s_setprio(1);
-                    if (s_pose_exact) verdict = 2;
+                    if (pose_exact) verdict = 2;
                 }
             }
             STAMP(u2);

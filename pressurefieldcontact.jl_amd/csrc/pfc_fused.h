@@ -1214,6 +1214,10 @@ __global__ void __launch_bounds__(kFuBlock) k_fused(FuArgs g) {
             r.Ebar1 = I.ins.Ebar1; r.model = I.ins.model; r.nq = nq; r.ins = id; r.pad = 0;
             r.q12[0] = 1.0f; r.q12[1] = r.q12[2] = r.q12[3] = 0.0f; r.pose_exact = 1; r.bp_eabs = 0.0f;      // (the broadphase does not read handed-over records)
             r.pad2[0] = r.pad2[1] = 0;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) r.R12f[k] = (float)r.R12[k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) r.t12f[k] = (float)r.t12[k];
             s_cbase = n_pl ? atomicAdd(g.emit_ctr, n_pl) : 0;
         }
         __syncthreads();

@@ -150,9 +150,9 @@ __global__ void __launch_bounds__(64) k_setup_items(EvalArgs g) {
     {
         double R12[9], t12[3];
 #pragma unroll
-        for (int k = 0; k < 9; ++k) { R12[k] = pb[k]; r.R12[k] = R12[k]; finite &= (__builtin_fabs(R12[k]) <= 1.79769313486231570815e308); }
+        for (int k = 0; k < 9; ++k) { R12[k] = pb[k]; r.R12[k] = R12[k]; r.R12f[k] = (float)R12[k]; finite &= (__builtin_fabs(R12[k]) <= 1.79769313486231570815e308); }
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { t12[k] = pb[9 + k]; r.t12[k] = t12[k]; finite &= (__builtin_fabs(t12[k]) <= 1.79769313486231570815e308); }
+        for (int k = 0; k < 3; ++k) { t12[k] = pb[9 + k]; r.t12[k] = t12[k]; r.t12f[k] = (float)t12[k]; finite &= (__builtin_fabs(t12[k]) <= 1.79769313486231570815e308); }
         float q[4];
         r.pose_exact = pose_quat(R12, q) ? 0 : 1;
         r.q12[0] = q[0]; r.q12[1] = q[1]; r.q12[2] = q[2]; r.q12[3] = q[3];
@@ -183,7 +183,9 @@ __global__ void __launch_bounds__(64) k_setup_items(EvalArgs g) {
 }
 
 // After the broadphase of an evaluation with a broadphase pose of its own: x_r1_r2 of the item records becomes the pose's
-// (the tet-tet op and the Dual passes read it: find_plane_tet, non_friction.jl:164,174-177).
+// (the tet-tet op and the Dual passes read it: find_plane_tet, non_friction.jl:164,174-177).  What only the broadphase reads
+// of a record -- q12, pose_exact, bp_eabs, R12f, t12f -- stays the broadphase pose's: those fields describe ONE pose between
+// them (the single-precision test rotates with q12 and offsets with R12f, t12f), and nothing behind the broadphase reads them.
 __global__ void k_repose(int n_items, const double *__restrict__ pose, ItemRec *__restrict__ items) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_items) return;

@@ -131,7 +131,16 @@ struct alignas(16) ItemRec {  // per (instruction, pose) item: outputs of refres
     // (pfc_bp.h, "Error radius E", (0))
     float bp_eabs;
     int pad2[2];
+    // fl32 of the broadphase's x_r1_r2 (R12f[k] = (float)R12[k], t12f[k] = (float)t12[k] as k_setup_items saw them): the
+    // single-precision test forms its centre offset from these, and k_bp_dfs32 reads them, q12, pose_exact and bp_eabs once
+    // per seed as wave-uniform scalars.  They belong to the pose the broadphase culls with, like q12: k_repose leaves them.
+    float R12f[9], t12f[3];
 };
+static_assert(sizeof(ItemRec) % 16 == 0 && offsetof(ItemRec, R12f) % 16 == 0, "ItemRec layout");
+// Wave-uniform reads of an item record that no kernel reading it this way writes: through the constant address space the
+// compiler emits scalar loads (s_load) whatever stores to other buffers stand between them.
+typedef __attribute__((address_space(4))) const float cfloat;
+typedef __attribute__((address_space(4))) const int cint;
 
 struct alignas(16) WorkRec {  // frontier entry (item, node_a, node_b) or candidate (item, i_1, i_2)
     int item, a, b, pad;
@@ -498,6 +507,10 @@ __device__ __forceinline__ V3 fan_at(const FanFields &f, const V3 &S, const V3 &
 // statements about max d, so only the maximum is carried (v_max3_f32: 8 instructions instead of 30 compares and as many
 // scalar mask operations).  v_max drops a NaN operand, so the caller sends non-finite or huge inputs (S >= 1e18: products
 // could overflow to inf - inf) to the exact test itself; for finite d the verdict is the one of the compare chain.
+// An axis's radius sum r_a + r_b is ONE chain of fused multiply-adds over its non-negative terms -- a face axis seeds the
+// chain with its own extent, an edge x edge axis with its first product -- and is subtracted from |T.L| once: one
+// instruction per axis less than forming r_a and r_b apart and adding them (15 of the test's 227), and every rounding is of
+// a partial sum of non-negative terms, bounded by the whole sum (pfc_bp.h, "Error radius E", (4) and (5)).
 __device__ __forceinline__ int sat15_f32_core(const float *ea, const float *eb, const float *t, const float *R, float E) {
     float aR[9];
 #pragma unroll
@@ -507,42 +520,41 @@ __device__ __forceinline__ int sat15_f32_core(const float *ea, const float *eb, 
 #define AR_(i, j) aR[(i) + 3 * (j)]
 #define AXIS_(tl, rsum) dmax = __builtin_fmaxf(dmax, (tl) - (rsum))
     {
-        const float rb = __builtin_fmaf(AR_(0, 2), eb[2], __builtin_fmaf(AR_(0, 1), eb[1], AR_(0, 0) * eb[0]));
-        dmax = __builtin_fabsf(t[0]) - (ea[0] + rb);
+        const float rs = __builtin_fmaf(AR_(0, 2), eb[2], __builtin_fmaf(AR_(0, 1), eb[1], __builtin_fmaf(AR_(0, 0), eb[0], ea[0])));
+        dmax = __builtin_fabsf(t[0]) - rs;
     }
 #pragma unroll
     for (int i = 1; i < 3; ++i) {
-        const float rb = __builtin_fmaf(AR_(i, 2), eb[2], __builtin_fmaf(AR_(i, 1), eb[1], AR_(i, 0) * eb[0]));
-        AXIS_(__builtin_fabsf(t[i]), ea[i] + rb);
+        const float rs = __builtin_fmaf(AR_(i, 2), eb[2], __builtin_fmaf(AR_(i, 1), eb[1], __builtin_fmaf(AR_(i, 0), eb[0], ea[i])));
+        AXIS_(__builtin_fabsf(t[i]), rs);
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const float tl = __builtin_fabsf(__builtin_fmaf(R_(2, j), t[2], __builtin_fmaf(R_(1, j), t[1], R_(0, j) * t[0])));
-        const float ra = __builtin_fmaf(AR_(2, j), ea[2], __builtin_fmaf(AR_(1, j), ea[1], AR_(0, j) * ea[0]));
-        AXIS_(tl, ra + eb[j]);
+        const float rs = __builtin_fmaf(AR_(2, j), ea[2], __builtin_fmaf(AR_(1, j), ea[1], __builtin_fmaf(AR_(0, j), ea[0], eb[j])));
+        AXIS_(tl, rs);
     }
     constexpr int i100[3] = {1, 0, 0}, i221[3] = {2, 2, 1};
+    // edge x edge, row m of the cross block (u, v the other two rows): e_a,v |R_uj| + e_a,u |R_vj| + e_b' |R_m.| + e_b |R_m.|
+#define EDGE_(m, u, v, j) \
+    __builtin_fmaf(eb[i100[j]], AR_(m, i221[j]), __builtin_fmaf(eb[i221[j]], AR_(m, i100[j]), \
+                   __builtin_fmaf(ea[u], AR_(v, j), ea[v] * AR_(u, j))))
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const float tl = __builtin_fabsf(__builtin_fmaf(t[2], R_(1, j), -(t[1] * R_(2, j))));
-        const float ra = __builtin_fmaf(ea[1], AR_(2, j), ea[2] * AR_(1, j));
-        const float rb = __builtin_fmaf(eb[i100[j]], AR_(0, i221[j]), eb[i221[j]] * AR_(0, i100[j]));
-        AXIS_(tl, ra + rb);
+        AXIS_(tl, EDGE_(0, 1, 2, j));
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const float tl = __builtin_fabsf(__builtin_fmaf(t[0], R_(2, j), -(t[2] * R_(0, j))));
-        const float ra = __builtin_fmaf(ea[0], AR_(2, j), ea[2] * AR_(0, j));
-        const float rb = __builtin_fmaf(eb[i100[j]], AR_(1, i221[j]), eb[i221[j]] * AR_(1, i100[j]));
-        AXIS_(tl, ra + rb);
+        AXIS_(tl, EDGE_(1, 0, 2, j));
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const float tl = __builtin_fabsf(__builtin_fmaf(t[1], R_(0, j), -(t[0] * R_(1, j))));
-        const float ra = __builtin_fmaf(ea[0], AR_(1, j), ea[1] * AR_(0, j));
-        const float rb = __builtin_fmaf(eb[i100[j]], AR_(2, i221[j]), eb[i221[j]] * AR_(2, i100[j]));
-        AXIS_(tl, ra + rb);
+        AXIS_(tl, EDGE_(2, 0, 1, j));
     }
+#undef EDGE_
 #undef AXIS_
 #undef R_
 #undef AR_
