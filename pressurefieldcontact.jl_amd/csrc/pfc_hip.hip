@@ -56,6 +56,7 @@
 #include "../../include/pfc.h"
 #include "pfc_sort.h"
 #include "pfc_hostblocks.h"
+#include "pfc_statecall.h"
 
 namespace pfc {
 
@@ -648,6 +649,8 @@ struct pfc_context {
         DevBuf<double> dbl;
         DevBuf<int> itg;
         std::vector<size_t> od, oi;                 // offsets of the parts (RadauD, RadauI)
+        double *D(int part) const { return dbl.p + od[part]; }
+        int *I(int part) const { return itg.p + oi[part]; }
         // pfc_radau_set_end: the end times live in dbl (RD_TFINAL) and the row counts in itg (RI_ROWS); the trajectory is a block of
         // its own, n_scene x max_rows x (1 + NX), replaced by the next pfc_radau_set_end and freed by pfc_radau_configure,
         // pfc_radau_set_state and with the handle
@@ -664,7 +667,9 @@ struct pfc_context {
             double dt = 0;
             DevBuf<double> cdbl;
             DevBuf<int> citg;
-            size_t od[8] = {0}, oi[2] = {0};
+            size_t od[8] = {0}, oi[2] = {0};      // offsets of the parts (RadauCD, RadauCI)
+            double *D(int part) const { return cdbl.p + od[part]; }
+            int *I(int part) const { return citg.p + oi[part]; }
             std::vector<double> t_last0;
         } ctl;
         void drop_control() { ctl = Control(); }
@@ -1551,6 +1556,10 @@ int make_twin(pfc_context *h) {
 // C ABI
 // =================================================================================================================
 #include "pfc_multi.h"
+
+// The context of what runs on one device only: the handle, or the first shard of a multi-device handle.  Such an entry is
+// on_shard(h, first_ctx(h), body): on a single-device handle on_shard's copy of the message assigns h->err to itself.
+static pfc_context *first_ctx(pfc_context *h) { return h->multi ? h->multi->shard[0] : h; }
 
 extern "C" {
 
@@ -3155,7 +3164,7 @@ int pfc_local_jacobian(pfc_handle h, int n_items, const int *ins_ids, const doub
     if (n_items < 0) return fail(h, PFC_ERR_BAD_ARG, "pfc_local_jacobian: negative n_items");
     if (n_items == 0) return PFC_OK;
     if (!pose || !twist || !wrench || !sdot || !L) return fail(h, PFC_ERR_BAD_ARG, "pfc_local_jacobian: null buffer");
-    pfc_context *c = h->multi ? h->multi->shard[0] : h;
+    pfc_context *c = first_ctx(h);
     HIP_TRY(h, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const size_t n = (size_t)n_items;
@@ -3188,26 +3197,27 @@ int pfc_local_jacobian(pfc_handle h, int n_items, const int *ins_ids, const doub
 // [d_wrench; d_sdot] = L . seeds for every (item, direction): no handle state is read or changed, only the device and its stream.
 int pfc_apply_local_jacobian_device(pfc_handle h, int n_items, int n_dir, const double *d_L, const double *d_dpose, const double *d_dtwist,
                                     const double *d_ds, double *d_dwrench, double *d_dsdot, void *stream) {
-    if (h && h->multi)      // L and the seeds of a multi-device evaluation are on the first device: so is this
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_apply_local_jacobian_device(c, n_items, n_dir, d_L, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, stream); });
-    if (!h || n_items < 0 || n_dir < 1 || n_dir > 16)
-        return fail(h, PFC_ERR_BAD_ARG, "pfc_apply_local_jacobian_device: n_items >= 0 and n_dir in 1..16");
-    if (n_items == 0) return PFC_OK;
-    if (!d_L || !d_dpose || !d_dtwist || !d_dwrench || !d_dsdot)
-        return fail(h, PFC_ERR_BAD_ARG, "pfc_apply_local_jacobian_device: null buffer");
-    if (reinterpret_cast<uintptr_t>(d_L) % 16 != 0) return fail(h, PFC_ERR_BAD_ARG, "pfc_apply_local_jacobian_device: d_L must be 16-byte aligned");
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    hipLaunchKernelGGL(k_ljac_apply, dim3((unsigned)n_items), dim3(64), 0, st, n_dir, d_L, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot);
-    HIP_TRY(h, hipGetLastError());
-    return PFC_OK;
+    if (!h) return PFC_ERR_BAD_ARG;
+    // L and the seeds of a multi-device evaluation are on the first device: so is this
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        if (n_items < 0 || n_dir < 1 || n_dir > 16)
+            return fail(c, PFC_ERR_BAD_ARG, "pfc_apply_local_jacobian_device: n_items >= 0 and n_dir in 1..16");
+        if (n_items == 0) return PFC_OK;
+        if (!d_L || !d_dpose || !d_dtwist || !d_dwrench || !d_dsdot)
+            return fail(c, PFC_ERR_BAD_ARG, "pfc_apply_local_jacobian_device: null buffer");
+        if (reinterpret_cast<uintptr_t>(d_L) % 16 != 0) return fail(c, PFC_ERR_BAD_ARG, "pfc_apply_local_jacobian_device: d_L must be 16-byte aligned");
+        HIP_TRY(c, hipSetDevice(c->device));
+        hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+        hipLaunchKernelGGL(k_ljac_apply, dim3((unsigned)n_items), dim3(64), 0, st, n_dir, d_L, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot);
+        HIP_TRY(c, hipGetLastError());
+        return PFC_OK; });
 }
 
 int pfc_apply_local_jacobian(pfc_handle h, int n_items, int n_dir, const double *L, const double *d_pose, const double *d_twist,
                              const double *d_s, double *d_wrench, double *d_sdot) {
-    pfc_context *c = h && h->multi ? h->multi->shard[0] : h;
-    if (!h || n_items < 0 || n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "pfc_apply_local_jacobian: n_items >= 0 and n_dir in 1..16");
+    if (!h) return PFC_ERR_BAD_ARG;
+    pfc_context *c = first_ctx(h);
+    if (n_items < 0 || n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "pfc_apply_local_jacobian: n_items >= 0 and n_dir in 1..16");
     if (n_items == 0) return PFC_OK;
     if (!L || !d_pose || !d_twist || !d_wrench || !d_sdot) return fail(h, PFC_ERR_BAD_ARG, "pfc_apply_local_jacobian: null buffer");
     HIP_TRY(h, hipSetDevice(c->device));
@@ -3227,16 +3237,17 @@ int pfc_apply_local_jacobian(pfc_handle h, int n_items, int n_dir, const double 
 
 // ---- contact items from body states (pfc_bodies.h) ------------------------------------------------------------------------
 int pfc_set_instruction_bodies(pfc_handle h, int ins, int body_1, int body_2) {
-    if (h && h->multi)      // the table lives with the first device, where the items are formed
-        return on_first_shard(h, [&](pfc_context *c) { return pfc_set_instruction_bodies(c, ins, body_1, body_2); });
-    if (!h || ins < 0 || body_1 < -1 || body_2 < -1)
-        return fail(h, PFC_ERR_BAD_ARG, "pfc_set_instruction_bodies: instruction id >= 0 and body ids >= -1 (-1: the world)");
-    if (h->finalized && ins >= (int)h->ins.size())
-        return fail(h, PFC_ERR_BAD_ARG, "pfc_set_instruction_bodies: the scenario has no instruction %d", ins);
-    if (h->ins_bodies.size() < 2 * ((size_t)ins + 1)) h->ins_bodies.resize(2 * ((size_t)ins + 1), kBodiesUnbound);
-    h->ins_bodies[2 * (size_t)ins] = body_1; h->ins_bodies[2 * (size_t)ins + 1] = body_2;
-    h->bodies_stale = true;
-    return PFC_OK;
+    if (!h) return PFC_ERR_BAD_ARG;
+    // the table lives with the first device, where the items are formed
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        if (ins < 0 || body_1 < -1 || body_2 < -1)
+            return fail(c, PFC_ERR_BAD_ARG, "pfc_set_instruction_bodies: instruction id >= 0 and body ids >= -1 (-1: the world)");
+        if (c->finalized && ins >= (int)c->ins.size())
+            return fail(c, PFC_ERR_BAD_ARG, "pfc_set_instruction_bodies: the scenario has no instruction %d", ins);
+        if (c->ins_bodies.size() < 2 * ((size_t)ins + 1)) c->ins_bodies.resize(2 * ((size_t)ins + 1), kBodiesUnbound);
+        c->ins_bodies[2 * (size_t)ins] = body_1; c->ins_bodies[2 * (size_t)ins + 1] = body_2;
+        c->bodies_stale = true;
+        return PFC_OK; });
 }
 
 // The binding of instruction `ins` checked against n_body: PFC_ERR_STATE if it was never bound.
@@ -3284,6 +3295,13 @@ static int bodies_check_bound_device(pfc_context *h, const char *who, int n_item
     return PFC_OK;
 }
 
+// What pfc_items_from_bodies_device checks, for the entry itself and for the chains that form items (they pass its name).
+static int bodies_check_device(pfc_context *h, const char *who, int n_items, const int *d_ins_ids, int n_scene, int n_body,
+                               const double *d_x_w_b, const double *d_twist_w_b) {
+    const int rc = bodies_check_args(h, who, n_items, d_ins_ids, n_scene, n_body, d_x_w_b, d_twist_w_b);
+    return rc != PFC_OK || n_items == 0 ? rc : bodies_check_bound_device(h, who, n_items, d_ins_ids, n_body);
+}
+
 // The bind table's upload on st if it is stale (the one synchronisation of this path: once per binding, ordered behind st's
 // earlier work).
 static int bodies_upload_bind(pfc_context *h, hipStream_t st) {
@@ -3317,52 +3335,72 @@ int pfc_items_from_bodies_device(pfc_handle h, int n_items, const int *d_ins_ids
                                  const double *d_x_w_b, const double *d_twist_w_b, double *d_pose, double *d_twist, double *d_x_w_r2,
                                  int *d_body_1, int *d_body_2, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_items_from_bodies_device(c, n_items, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_pose, d_twist,
-                                                d_x_w_r2, d_body_1, d_body_2, stream); });
-    const char *who = "pfc_items_from_bodies_device";
-    int rc = bodies_check_args(h, who, n_items, d_ins_ids, n_scene, n_body, d_x_w_b, d_twist_w_b);
-    if (rc != PFC_OK || n_items == 0) return rc;
-    if ((rc = bodies_check_bound_device(h, who, n_items, d_ins_ids, n_body)) != PFC_OK) return rc;
-    return bodies_launch(h, n_items, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_pose, d_twist, d_x_w_r2, d_body_1, d_body_2,
-                         stream ? (hipStream_t)stream : h->stream);
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        const int rc = bodies_check_device(c, "pfc_items_from_bodies_device", n_items, d_ins_ids, n_scene, n_body, d_x_w_b, d_twist_w_b);
+        if (rc != PFC_OK || n_items == 0) return rc;
+        return bodies_launch(c, n_items, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_pose, d_twist, d_x_w_r2, d_body_1,
+                             d_body_2, stream ? (hipStream_t)stream : c->stream); });
 }
 
 int pfc_items_from_bodies(pfc_handle h, int n_items, const int *ins_ids, const int *scene, int n_scene, int n_body, const double *x_w_b,
                           const double *twist_w_b, double *pose, double *twist, double *x_w_r2, int *body_1, int *body_2) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_items_from_bodies(c, n_items, ins_ids, scene, n_scene, n_body, x_w_b, twist_w_b, pose, twist, x_w_r2, body_1, body_2); });
-    const char *who = "pfc_items_from_bodies";
-    int rc = bodies_check_args(h, who, n_items, ins_ids, n_scene, n_body, x_w_b, twist_w_b);
-    if (rc != PFC_OK || n_items == 0) return rc;
-    if ((rc = bodies_check_ids_host(h, who, n_items, ins_ids, scene, n_scene, n_body)) != PFC_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (size_t)n_items, nb = (size_t)n_scene * n_body;
-    Stage sg(h->stage, h->stream);
-    const int k_x = sg.in(x_w_b, nb * 12), k_tw = sg.in(twist_w_b, nb * 6), k_ids = sg.in(ins_ids, n), k_sc = sg.in(scene, n);
-    const int k_pose = sg.out(pose, n * 24), k_twist = sg.out(twist, n * 6), k_xr = sg.out(x_w_r2, n * 12);
-    const int k_b1 = sg.out(body_1, n), k_b2 = sg.out(body_2, n);
-    HIP_TRY(h, sg.commit());
-    rc = bodies_launch(h, n_items, sg.at<int>(k_ids), sg.at<int>(k_sc), n_scene, n_body, sg.at<double>(k_x), sg.at<double>(k_tw),
-                       sg.at<double>(k_pose), sg.at<double>(k_twist), sg.at<double>(k_xr), sg.at<int>(k_b1), sg.at<int>(k_b2), sg.st);
-    if (rc != PFC_OK) return rc;
-    HIP_TRY(h, sg.finish());
-    return PFC_OK;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        const char *who = "pfc_items_from_bodies";
+        int rc = bodies_check_args(c, who, n_items, ins_ids, n_scene, n_body, x_w_b, twist_w_b);
+        if (rc != PFC_OK || n_items == 0) return rc;
+        if ((rc = bodies_check_ids_host(c, who, n_items, ins_ids, scene, n_scene, n_body)) != PFC_OK) return rc;
+        HIP_TRY(c, hipSetDevice(c->device));
+        const size_t n = (size_t)n_items, nb = (size_t)n_scene * n_body;
+        Stage sg(c->stage, c->stream);
+        const int k_x = sg.in(x_w_b, nb * 12), k_tw = sg.in(twist_w_b, nb * 6), k_ids = sg.in(ins_ids, n), k_sc = sg.in(scene, n);
+        const int k_pose = sg.out(pose, n * 24), k_twist = sg.out(twist, n * 6), k_xr = sg.out(x_w_r2, n * 12);
+        const int k_b1 = sg.out(body_1, n), k_b2 = sg.out(body_2, n);
+        HIP_TRY(c, sg.commit());
+        rc = bodies_launch(c, n_items, sg.at<int>(k_ids), sg.at<int>(k_sc), n_scene, n_body, sg.at<double>(k_x), sg.at<double>(k_tw),
+                           sg.at<double>(k_pose), sg.at<double>(k_twist), sg.at<double>(k_xr), sg.at<int>(k_b1), sg.at<int>(k_b2), sg.st);
+        if (rc != PFC_OK) return rc;
+        HIP_TRY(c, sg.finish());
+        return PFC_OK; });
+}
+
+// ---- the chained state calls, over one record of their buffers (pfc_statecall.h) -----------------------------------------------------
+// Each chain is the body of its extern "C" entry (and of its `_more` twin, `more` set): the entry fills a StateCall and calls it.  The
+// kernels of a chain run on the first shard -- its stream unless the caller gave one -- and the evaluation between them is the
+// handle's own, sharded on a multi-device handle.  A chain's own checks carry its entry's name, as when that entry is called from
+// the entry above it.
+static hipStream_t call_stream(const pfc_context *c, const StateCall &S) { return S.stream ? (hipStream_t)S.stream : c->stream; }
+
+static StateCall state_call_head(int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene, void *stream) {
+    StateCall S;
+    S.n_items = n_items; S.n_dir = n_dir; S.ins_ids = d_ins_ids; S.scene = d_scene; S.n_scene = n_scene; S.stream = stream;
+    return S;
 }
 
 // k_items_from_bodies, then exactly pfc_eval_device on the pose and twist it wrote, on the same stream.
+static int eval_bodies(pfc_context *h, const StateCall &S, int n_body) {
+    const StateBufs &V = S.val;
+    if (S.n_items > 0 && (!V.pose || !V.twist))
+        return fail(h, PFC_ERR_BAD_ARG, "pfc_eval_bodies_device: d_pose and d_twist are the evaluation's inputs");
+    const int rc = on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        const int r = bodies_check_device(c, "pfc_items_from_bodies_device", S.n_items, S.ins_ids, S.n_scene, n_body, V.x_w_b, V.twist_w_b);
+        if (r != PFC_OK || S.n_items == 0) return r;
+        return bodies_launch(c, S.n_items, S.ins_ids, S.scene, S.n_scene, n_body, V.x_w_b, V.twist_w_b, V.pose, V.twist, V.x_w_r2, V.body_1,
+                             V.body_2, call_stream(c, S)); });
+    if (rc != PFC_OK) return rc;
+    return pfc_eval_device(h, S.n_items, S.ins_ids, V.pose, V.twist, V.s, V.wrench, V.sdot, V.counts, S.stream);
+}
+
 int pfc_eval_bodies_device(pfc_handle h, int n_items, const int *d_ins_ids, const int *d_scene, int n_scene, int n_body,
                            const double *d_x_w_b, const double *d_twist_w_b, const double *d_s, double *d_pose, double *d_twist,
                            double *d_x_w_r2, int *d_body_1, int *d_body_2, double *d_wrench, double *d_sdot, int *d_counts, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (n_items > 0 && (!d_pose || !d_twist)) return fail(h, PFC_ERR_BAD_ARG, "pfc_eval_bodies_device: d_pose and d_twist are the evaluation's inputs");
-    const int rc = pfc_items_from_bodies_device(h, n_items, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_pose, d_twist,
-                                                d_x_w_r2, d_body_1, d_body_2, stream);
-    if (rc != PFC_OK) return rc;
-    return pfc_eval_device(h, n_items, d_ins_ids, d_pose, d_twist, d_s, d_wrench, d_sdot, d_counts, stream);
+    StateCall S = state_call_head(n_items, 0, d_ins_ids, d_scene, n_scene, stream);
+    StateBufs &V = S.val;
+    V.x_w_b = kept_value(d_x_w_b); V.twist_w_b = kept_value(d_twist_w_b); V.s = d_s;
+    V.pose = d_pose; V.twist = d_twist; V.x_w_r2 = d_x_w_r2; V.body_1 = d_body_1; V.body_2 = d_body_2;
+    V.wrench = d_wrench; V.sdot = d_sdot; V.counts = d_counts;
+    return eval_bodies(h, S, n_body);
 }
 
 int pfc_eval_bodies(pfc_handle h, int n_items, const int *ins_ids, const int *scene, int n_scene, int n_body, const double *x_w_b,
@@ -3410,154 +3448,172 @@ int pfc_dual_seeds_from_bodies_device(pfc_handle h, int n_items, int n_dir, cons
                                       int n_body, const double *d_x_w_b, const double *d_twist_w_b, const double *d_dx_w_b,
                                       const double *d_dtwist_w_b, double *d_dpose, double *d_dtwist, double *d_dx_w_r2, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_dual_seeds_from_bodies_device(c, n_items, n_dir, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_dx_w_b,
-                                                     d_dtwist_w_b, d_dpose, d_dtwist, d_dx_w_r2, stream); });
-    const int rc = bodies_seeds_check_device(h, "pfc_dual_seeds_from_bodies_device", n_items, n_dir, d_ins_ids, n_scene, n_body, d_x_w_b,
-                                             d_twist_w_b);
-    if (rc != PFC_OK || n_items == 0) return rc;
-    return bodies_seeds_launch(h, n_items, n_dir, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b, d_dpose,
-                               d_dtwist, d_dx_w_r2, stream ? (hipStream_t)stream : h->stream);
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        const int rc = bodies_seeds_check_device(c, "pfc_dual_seeds_from_bodies_device", n_items, n_dir, d_ins_ids, n_scene, n_body, d_x_w_b,
+                                                 d_twist_w_b);
+        if (rc != PFC_OK || n_items == 0) return rc;
+        return bodies_seeds_launch(c, n_items, n_dir, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b,
+                                   d_dpose, d_dtwist, d_dx_w_r2, stream ? (hipStream_t)stream : c->stream); });
 }
 
 int pfc_dual_seeds_from_bodies(pfc_handle h, int n_items, int n_dir, const int *ins_ids, const int *scene, int n_scene, int n_body,
                                const double *x_w_b, const double *twist_w_b, const double *d_x_w_b, const double *d_twist_w_b,
                                double *d_pose, double *d_twist, double *d_x_w_r2) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_dual_seeds_from_bodies(c, n_items, n_dir, ins_ids, scene, n_scene, n_body, x_w_b, twist_w_b, d_x_w_b, d_twist_w_b,
-                                              d_pose, d_twist, d_x_w_r2); });
-    const char *who = "pfc_dual_seeds_from_bodies";
-    int rc = bodies_check_args(h, who, n_items, ins_ids, n_scene, n_body, x_w_b, twist_w_b);
-    if (rc != PFC_OK) return rc;
-    if (n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "%s: n_dir must be in 1..16", who);
-    if (n_items == 0) return PFC_OK;
-    if ((rc = bodies_check_ids_host(h, who, n_items, ins_ids, scene, n_scene, n_body)) != PFC_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (size_t)n_items, nb = (size_t)n_scene * n_body, nk = n * n_dir, nbk = nb * n_dir;
-    Stage sg(h->stage, h->stream);
-    const int k_x = sg.in(x_w_b, nb * 12), k_tw = sg.in(twist_w_b, nb * 6), k_dx = sg.in(d_x_w_b, nbk * 12), k_dtw = sg.in(d_twist_w_b, nbk * 6);
-    const int k_ids = sg.in(ins_ids, n), k_sc = sg.in(scene, n);
-    const int k_dpose = sg.out(d_pose, nk * 24), k_dtwist = sg.out(d_twist, nk * 6), k_dxr = sg.out(d_x_w_r2, nk * 12);
-    HIP_TRY(h, sg.commit());
-    rc = bodies_seeds_launch(h, n_items, n_dir, sg.at<int>(k_ids), sg.at<int>(k_sc), n_scene, n_body, sg.at<double>(k_x), sg.at<double>(k_tw),
-                             sg.at<double>(k_dx), sg.at<double>(k_dtw), sg.at<double>(k_dpose), sg.at<double>(k_dtwist), sg.at<double>(k_dxr), sg.st);
-    if (rc != PFC_OK) return rc;
-    HIP_TRY(h, sg.finish());
-    return PFC_OK;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        const char *who = "pfc_dual_seeds_from_bodies";
+        int rc = bodies_check_args(c, who, n_items, ins_ids, n_scene, n_body, x_w_b, twist_w_b);
+        if (rc != PFC_OK) return rc;
+        if (n_dir < 1 || n_dir > 16) return fail(c, PFC_ERR_BAD_ARG, "%s: n_dir must be in 1..16", who);
+        if (n_items == 0) return PFC_OK;
+        if ((rc = bodies_check_ids_host(c, who, n_items, ins_ids, scene, n_scene, n_body)) != PFC_OK) return rc;
+        HIP_TRY(c, hipSetDevice(c->device));
+        const size_t n = (size_t)n_items, nb = (size_t)n_scene * n_body, nk = n * n_dir, nbk = nb * n_dir;
+        Stage sg(c->stage, c->stream);
+        const int k_x = sg.in(x_w_b, nb * 12), k_tw = sg.in(twist_w_b, nb * 6), k_dx = sg.in(d_x_w_b, nbk * 12), k_dtw = sg.in(d_twist_w_b, nbk * 6);
+        const int k_ids = sg.in(ins_ids, n), k_sc = sg.in(scene, n);
+        const int k_dpose = sg.out(d_pose, nk * 24), k_dtwist = sg.out(d_twist, nk * 6), k_dxr = sg.out(d_x_w_r2, nk * 12);
+        HIP_TRY(c, sg.commit());
+        rc = bodies_seeds_launch(c, n_items, n_dir, sg.at<int>(k_ids), sg.at<int>(k_sc), n_scene, n_body, sg.at<double>(k_x), sg.at<double>(k_tw),
+                                 sg.at<double>(k_dx), sg.at<double>(k_dtw), sg.at<double>(k_dpose), sg.at<double>(k_dtwist), sg.at<double>(k_dxr), sg.st);
+        if (rc != PFC_OK) return rc;
+        HIP_TRY(c, sg.finish());
+        return PFC_OK; });
 }
 
-// k_items_from_bodies, k_dual_seeds_from_bodies, then exactly pfc_eval_dual_device on the buffers they wrote, on the same stream.
+// First call: k_items_from_bodies, k_dual_seeds_from_bodies, then exactly pfc_eval_dual_device on the buffers they wrote, on the same
+// stream.  `more`: k_dual_seeds_from_bodies, then exactly pfc_eval_dual_device_more on the seeds it wrote.
+static int eval_dual_bodies(pfc_context *h, const StateCall &S, int n_body, bool more) {
+    const StateBufs &V = S.val, &P = S.par;
+    const char *who = more ? "pfc_eval_dual_bodies_device_more" : "pfc_eval_dual_bodies_device";
+    if (!more) {
+        if (S.n_dir < 1 || S.n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "%s: n_dir must be in 1..16", who);
+        if (S.n_items > 0 && (!V.pose || !V.twist || !P.pose || !P.twist))
+            return fail(h, PFC_ERR_BAD_ARG, "%s: d_pose, d_twist, d_dpose and d_dtwist are the evaluation's inputs", who);
+    } else if (!h->multi) {      // _more's own preconditions, before the seeds are written
+        const int rc = bodies_seeds_check_device(h, who, S.n_items, S.n_dir, S.ins_ids, S.n_scene, n_body, V.x_w_b, V.twist_w_b);
+        if (rc != PFC_OK) return rc;
+        if (!h->device_kept())
+            return fail(h, PFC_ERR_STATE, "%s: no checked pfc_eval_dual_device evaluation on this handle to extend", who);
+        if (S.n_items != h->kept.n)
+            return fail(h, PFC_ERR_BAD_ARG, "%s: n_items is %d, the kept evaluation has %d items", who, S.n_items, h->kept.n);
+        if (!P.pose || !P.twist || !P.wrench || !P.sdot) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    }
+    const int rc = on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        const hipStream_t st = call_stream(c, S);
+        int r = PFC_OK;
+        if (!more) {
+            r = bodies_check_device(c, "pfc_items_from_bodies_device", S.n_items, S.ins_ids, S.n_scene, n_body, V.x_w_b, V.twist_w_b);
+            if (r == PFC_OK && S.n_items > 0)
+                r = bodies_launch(c, S.n_items, S.ins_ids, S.scene, S.n_scene, n_body, V.x_w_b, V.twist_w_b, V.pose, V.twist, V.x_w_r2,
+                                  V.body_1, V.body_2, st);
+            if (r != PFC_OK) return r;
+        }
+        r = bodies_seeds_check_device(c, "pfc_dual_seeds_from_bodies_device", S.n_items, S.n_dir, S.ins_ids, S.n_scene, n_body, V.x_w_b,
+                                      V.twist_w_b);
+        if (r != PFC_OK || S.n_items == 0) return r;
+        return bodies_seeds_launch(c, S.n_items, S.n_dir, S.ins_ids, S.scene, S.n_scene, n_body, V.x_w_b, V.twist_w_b, P.x_w_b, P.twist_w_b,
+                                   P.pose, P.twist, P.x_w_r2, st); });
+    if (rc != PFC_OK) return rc;
+    if (more) return pfc_eval_dual_device_more(h, S.n_dir, P.pose, P.twist, P.s, P.wrench, P.sdot, S.stream);
+    return pfc_eval_dual_device(h, S.n_items, S.n_dir, S.ins_ids, V.pose, V.twist, V.s, P.pose, P.twist, P.s, V.wrench, V.sdot, P.wrench,
+                                P.sdot, V.counts, S.stream);
+}
+
 int pfc_eval_dual_bodies_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene, int n_body,
                                 const double *d_x_w_b, const double *d_twist_w_b, const double *d_dx_w_b, const double *d_dtwist_w_b,
                                 const double *d_s, const double *d_ds, double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1,
                                 int *d_body_2, double *d_dpose, double *d_dtwist, double *d_dx_w_r2, double *d_wrench, double *d_sdot,
                                 double *d_dwrench, double *d_dsdot, int *d_counts, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    const char *who = "pfc_eval_dual_bodies_device";
-    if (n_dir < 1 || n_dir > 16) return fail(h, PFC_ERR_BAD_ARG, "%s: n_dir must be in 1..16", who);
-    if (n_items > 0 && (!d_pose || !d_twist || !d_dpose || !d_dtwist))
-        return fail(h, PFC_ERR_BAD_ARG, "%s: d_pose, d_twist, d_dpose and d_dtwist are the evaluation's inputs", who);
-    int rc = pfc_items_from_bodies_device(h, n_items, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_pose, d_twist, d_x_w_r2,
-                                          d_body_1, d_body_2, stream);
-    if (rc != PFC_OK) return rc;
-    rc = pfc_dual_seeds_from_bodies_device(h, n_items, n_dir, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_dx_w_b,
-                                           d_dtwist_w_b, d_dpose, d_dtwist, d_dx_w_r2, stream);
-    if (rc != PFC_OK) return rc;
-    return pfc_eval_dual_device(h, n_items, n_dir, d_ins_ids, d_pose, d_twist, d_s, d_dpose, d_dtwist, d_ds, d_wrench, d_sdot, d_dwrench,
-                                d_dsdot, d_counts, stream);
+    StateCall S = state_call_head(n_items, n_dir, d_ins_ids, d_scene, n_scene, stream);
+    StateBufs &V = S.val, &P = S.par;
+    V.x_w_b = kept_value(d_x_w_b); V.twist_w_b = kept_value(d_twist_w_b); P.x_w_b = kept_value(d_dx_w_b); P.twist_w_b = kept_value(d_dtwist_w_b);
+    V.s = d_s; P.s = d_ds;
+    V.pose = d_pose; V.twist = d_twist; V.x_w_r2 = d_x_w_r2; V.body_1 = d_body_1; V.body_2 = d_body_2;
+    P.pose = d_dpose; P.twist = d_dtwist; P.x_w_r2 = d_dx_w_r2;
+    V.wrench = d_wrench; V.sdot = d_sdot; P.wrench = d_dwrench; P.sdot = d_dsdot; V.counts = d_counts;
+    return eval_dual_bodies(h, S, n_body, false);
 }
 
-// k_dual_seeds_from_bodies, then exactly pfc_eval_dual_device_more on the seeds it wrote, on the same stream.
 int pfc_eval_dual_bodies_device_more(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene, int n_body,
                                      const double *d_x_w_b, const double *d_twist_w_b, const double *d_dx_w_b, const double *d_dtwist_w_b,
                                      const double *d_ds, double *d_dpose, double *d_dtwist, double *d_dx_w_r2, double *d_dwrench,
                                      double *d_dsdot, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    const char *who = "pfc_eval_dual_bodies_device_more";
-    if (!h->multi) {      // _more's own preconditions, before the seeds are written
-        const int rc = bodies_seeds_check_device(h, who, n_items, n_dir, d_ins_ids, n_scene, n_body, d_x_w_b, d_twist_w_b);
-        if (rc != PFC_OK) return rc;
-        if (!h->device_kept())
-            return fail(h, PFC_ERR_STATE, "%s: no checked pfc_eval_dual_device evaluation on this handle to extend", who);
-        if (n_items != h->kept.n)
-            return fail(h, PFC_ERR_BAD_ARG, "%s: n_items is %d, the kept evaluation has %d items", who, n_items, h->kept.n);
-        if (!d_dpose || !d_dtwist || !d_dwrench || !d_dsdot) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-    }
-    const int rc = pfc_dual_seeds_from_bodies_device(h, n_items, n_dir, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_dx_w_b,
-                                                     d_dtwist_w_b, d_dpose, d_dtwist, d_dx_w_r2, stream);
-    if (rc != PFC_OK) return rc;
-    return pfc_eval_dual_device_more(h, n_dir, d_dpose, d_dtwist, d_ds, d_dwrench, d_dsdot, stream);
+    StateCall S = state_call_head(n_items, n_dir, d_ins_ids, d_scene, n_scene, stream);
+    StateBufs &V = S.val, &P = S.par;
+    V.x_w_b = kept_value(d_x_w_b); V.twist_w_b = kept_value(d_twist_w_b); P.x_w_b = kept_value(d_dx_w_b); P.twist_w_b = kept_value(d_dtwist_w_b);
+    P.s = d_ds; P.pose = d_dpose; P.twist = d_dtwist; P.x_w_r2 = d_dx_w_r2; P.wrench = d_dwrench; P.sdot = d_dsdot;
+    return eval_dual_bodies(h, S, n_body, true);
 }
 
 // ---- kinematics from joint states (pfc_kin.h) -----------------------------------------------------------------------------------
 int pfc_set_mechanism(pfc_handle h, int n_body, const int *parent, const int *joint_type, const double *x_p_j, const double *axis) {
-    if (h && h->multi)      // the tables live with the first device, where the states are formed
-        return on_first_shard(h, [&](pfc_context *c) { return pfc_set_mechanism(c, n_body, parent, joint_type, x_p_j, axis); });
     if (!h) return PFC_ERR_BAD_ARG;
-    const char *who = "pfc_set_mechanism";
-    if (n_body < 1) return fail(h, PFC_ERR_BAD_ARG, "%s: n_body is %d, a mechanism has at least one body", who, n_body);
-    if (!parent || !joint_type || !x_p_j || !axis) return fail(h, PFC_ERR_BAD_ARG, "%s: null table", who);
-    const size_t nb = (size_t)n_body;
-    std::vector<int> jtype(nb), qoff(nb), voff(nb), path_off(nb + 1, 0), path, depth(nb);
-    int nv = 0;
-    for (int b = 0; b < n_body; ++b) {
-        if (parent[b] < -1 || parent[b] >= b)
-            return fail(h, PFC_ERR_BAD_ARG, "%s: body %d has parent %d, outside [-1, %d)", who, b, parent[b], b);
-        const int t = joint_type[b];
-        if (t != PFC_JOINT_FIXED && t != PFC_JOINT_REVOLUTE && t != PFC_JOINT_PRISMATIC && t != PFC_JOINT_FLOATING_MRP)
-            return fail(h, PFC_ERR_BAD_ARG, "%s: body %d has the unknown joint type %d", who, b, t);
-        if (t == PFC_JOINT_REVOLUTE || t == PFC_JOINT_PRISMATIC) {
-            const double *a = axis + 3 * (size_t)b;
-            const double n2 = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2];
-            if (!(std::fabs(n2 - 1.0) <= 1e-12))
-                return fail(h, PFC_ERR_BAD_ARG, "%s: body %d's joint axis is not a unit vector (|a|^2 = %.17g)", who, b, n2);
-        }
-        jtype[b] = t; qoff[b] = voff[b] = nv;      // nq = nv for every joint type here
-        nv += kin_joint_nq(t);
-        depth[b] = parent[b] < 0 ? 1 : depth[parent[b]] + 1;
-        path_off[b + 1] = path_off[b] + depth[b];
-    }
-    path.resize((size_t)path_off[nb]);
-    std::vector<unsigned char> anc(nb * (size_t)nv, 0);
-    for (int b = 0; b < n_body; ++b) {
-        int k = path_off[b + 1];
-        for (int a = b; a >= 0; a = parent[a]) {
-            path[--k] = a;
-            for (int c = 0; c < kin_joint_nq(jtype[a]); ++c) anc[(size_t)b * nv + voff[a] + c] = 1;
-        }
-    }
-    KinHost &K = h->kin;
-    K.blob.clear();
-    K.o_jtype = K.put(jtype); K.o_qoff = K.put(qoff); K.o_voff = K.put(voff); K.o_path_off = K.put(path_off); K.o_path = K.put(path);
-    K.o_x_p_j = K.put(std::vector<double>(x_p_j, x_p_j + 12 * nb)); K.o_axis = K.put(std::vector<double>(axis, axis + 3 * nb));
-    K.o_anc = K.put(anc);
-    {   // the subtrees: b and its descendants in increasing body order (a descendant's path holds b)
-        std::vector<int> sub_off(nb + 1, 0), sub;
+    // the tables live with the first device, where the states are formed
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        const char *who = "pfc_set_mechanism";
+        if (n_body < 1) return fail(c, PFC_ERR_BAD_ARG, "%s: n_body is %d, a mechanism has at least one body", who, n_body);
+        if (!parent || !joint_type || !x_p_j || !axis) return fail(c, PFC_ERR_BAD_ARG, "%s: null table", who);
+        const size_t nb = (size_t)n_body;
+        std::vector<int> jtype(nb), qoff(nb), voff(nb), path_off(nb + 1, 0), path, depth(nb);
+        int nv = 0;
         for (int b = 0; b < n_body; ++b) {
-            for (int d = b; d < n_body; ++d)
-                if (std::find(path.begin() + path_off[d], path.begin() + path_off[d + 1], b) != path.begin() + path_off[d + 1]) sub.push_back(d);
-            sub_off[b + 1] = (int)sub.size();
+            if (parent[b] < -1 || parent[b] >= b)
+                return fail(c, PFC_ERR_BAD_ARG, "%s: body %d has parent %d, outside [-1, %d)", who, b, parent[b], b);
+            const int t = joint_type[b];
+            if (t != PFC_JOINT_FIXED && t != PFC_JOINT_REVOLUTE && t != PFC_JOINT_PRISMATIC && t != PFC_JOINT_FLOATING_MRP)
+                return fail(c, PFC_ERR_BAD_ARG, "%s: body %d has the unknown joint type %d", who, b, t);
+            if (t == PFC_JOINT_REVOLUTE || t == PFC_JOINT_PRISMATIC) {
+                const double *a = axis + 3 * (size_t)b;
+                const double n2 = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2];
+                if (!(std::fabs(n2 - 1.0) <= 1e-12))
+                    return fail(c, PFC_ERR_BAD_ARG, "%s: body %d's joint axis is not a unit vector (|a|^2 = %.17g)", who, b, n2);
+            }
+            jtype[b] = t; qoff[b] = voff[b] = nv;      // nq = nv for every joint type here
+            nv += kin_joint_nq(t);
+            depth[b] = parent[b] < 0 ? 1 : depth[parent[b]] + 1;
+            path_off[b + 1] = path_off[b] + depth[b];
         }
-        K.o_sub_off = K.put(sub_off); K.o_sub = K.put(sub);
-        K.o_inertia = K.put(std::vector<double>(13 * nb, 0.0));
-        K.has_inertia = false;
-    }
-    K.n_body = n_body; K.nq = nv; K.nv = nv;
-    h->kin_stale = true;
-    return PFC_OK;
+        path.resize((size_t)path_off[nb]);
+        std::vector<unsigned char> anc(nb * (size_t)nv, 0);
+        for (int b = 0; b < n_body; ++b) {
+            int k = path_off[b + 1];
+            for (int a = b; a >= 0; a = parent[a]) {
+                path[--k] = a;
+                for (int e = 0; e < kin_joint_nq(jtype[a]); ++e) anc[(size_t)b * nv + voff[a] + e] = 1;
+            }
+        }
+        KinHost &K = c->kin;
+        K.blob.clear();
+        K.o_jtype = K.put(jtype); K.o_qoff = K.put(qoff); K.o_voff = K.put(voff); K.o_path_off = K.put(path_off); K.o_path = K.put(path);
+        K.o_x_p_j = K.put(std::vector<double>(x_p_j, x_p_j + 12 * nb)); K.o_axis = K.put(std::vector<double>(axis, axis + 3 * nb));
+        K.o_anc = K.put(anc);
+        {   // the subtrees: b and its descendants in increasing body order (a descendant's path holds b)
+            std::vector<int> sub_off(nb + 1, 0), sub;
+            for (int b = 0; b < n_body; ++b) {
+                for (int d = b; d < n_body; ++d)
+                    if (std::find(path.begin() + path_off[d], path.begin() + path_off[d + 1], b) != path.begin() + path_off[d + 1]) sub.push_back(d);
+                sub_off[b + 1] = (int)sub.size();
+            }
+            K.o_sub_off = K.put(sub_off); K.o_sub = K.put(sub);
+            K.o_inertia = K.put(std::vector<double>(13 * nb, 0.0));
+            K.has_inertia = false;
+        }
+        K.n_body = n_body; K.nq = nv; K.nv = nv;
+        c->kin_stale = true;
+        return PFC_OK; });
 }
 
 int pfc_mechanism_sizes(pfc_handle h, int *n_body, int *nq, int *nv) {
-    if (h && h->multi) return on_first_shard(h, [&](pfc_context *c) { return pfc_mechanism_sizes(c, n_body, nq, nv); });
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->kin.n_body == 0) return fail(h, PFC_ERR_STATE, "pfc_mechanism_sizes before pfc_set_mechanism");
-    if (n_body) *n_body = h->kin.n_body;
-    if (nq) *nq = h->kin.nq;
-    if (nv) *nv = h->kin.nv;
-    return PFC_OK;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        if (c->kin.n_body == 0) return fail(c, PFC_ERR_STATE, "pfc_mechanism_sizes before pfc_set_mechanism");
+        if (n_body) *n_body = c->kin.n_body;
+        if (nq) *nq = c->kin.nq;
+        if (nv) *nv = c->kin.nv;
+        return PFC_OK; });
 }
 
 // Argument and state checks of both forms of pfc_kinematics.
@@ -3622,30 +3678,27 @@ static int kin_launch(pfc_context *h, int n_scene, const double *q, const double
 int pfc_kinematics_device(pfc_handle h, int n_scene, const double *d_q, const double *d_v, double *d_x_w_b, double *d_twist_w_b,
                           double *d_jac, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_kinematics_device(c, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_jac, stream); });
-    const int rc = kin_check_args(h, "pfc_kinematics_device", n_scene, d_q, d_v, d_twist_w_b != nullptr);
-    if (rc != PFC_OK || n_scene == 0) return rc;
-    return kin_launch(h, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_jac, stream ? (hipStream_t)stream : h->stream);
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        const int rc = kin_check_args(c, "pfc_kinematics_device", n_scene, d_q, d_v, d_twist_w_b != nullptr);
+        if (rc != PFC_OK || n_scene == 0) return rc;
+        return kin_launch(c, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_jac, stream ? (hipStream_t)stream : c->stream); });
 }
 
 int pfc_kinematics(pfc_handle h, int n_scene, const double *q, const double *v, double *x_w_b, double *twist_w_b, double *jac) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) { return pfc_kinematics(c, n_scene, q, v, x_w_b, twist_w_b, jac); });
-    int rc = kin_check_args(h, "pfc_kinematics", n_scene, q, v, twist_w_b != nullptr);
-    if (rc != PFC_OK || n_scene == 0) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t ns = (size_t)n_scene, nb = ns * h->kin.n_body;
-    Stage sg(h->stage, h->stream);
-    const int k_q = sg.in(q, ns * h->kin.nq), k_v = sg.in(v, ns * h->kin.nv);
-    const int k_x = sg.out(x_w_b, nb * 12), k_tw = sg.out(twist_w_b, nb * 6), k_j = sg.out(jac, nb * h->kin.nv * 6);
-    HIP_TRY(h, sg.commit());
-    rc = kin_launch(h, n_scene, sg.at<double>(k_q), sg.at<double>(k_v), sg.at<double>(k_x), sg.at<double>(k_tw), sg.at<double>(k_j), sg.st);
-    if (rc != PFC_OK) return rc;
-    HIP_TRY(h, sg.finish());
-    return PFC_OK;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        int rc = kin_check_args(c, "pfc_kinematics", n_scene, q, v, twist_w_b != nullptr);
+        if (rc != PFC_OK || n_scene == 0) return rc;
+        HIP_TRY(c, hipSetDevice(c->device));
+        const size_t ns = (size_t)n_scene, nb = ns * c->kin.n_body;
+        Stage sg(c->stage, c->stream);
+        const int k_q = sg.in(q, ns * c->kin.nq), k_v = sg.in(v, ns * c->kin.nv);
+        const int k_x = sg.out(x_w_b, nb * 12), k_tw = sg.out(twist_w_b, nb * 6), k_j = sg.out(jac, nb * c->kin.nv * 6);
+        HIP_TRY(c, sg.commit());
+        rc = kin_launch(c, n_scene, sg.at<double>(k_q), sg.at<double>(k_v), sg.at<double>(k_x), sg.at<double>(k_tw), sg.at<double>(k_j), sg.st);
+        if (rc != PFC_OK) return rc;
+        HIP_TRY(c, sg.finish());
+        return PFC_OK; });
 }
 
 // What both forms of pfc_eval_state check before anything is launched or written: the mechanism, the scenario, and the bodies of the
@@ -3664,28 +3717,6 @@ static int eval_state_check(pfc_context *c, const char *who, int n_items, const 
                 : bodies_check_bound_device(c, who, n_items, ins_ids, c->kin.n_body);
 }
 
-int pfc_eval_state_device(pfc_handle h, int n_items, const int *d_ins_ids, const int *d_scene, int n_scene,
-                          const double *d_q, const double *d_v, const double *d_s,
-                          double *d_x_w_b, double *d_twist_w_b, double *d_jac,
-                          double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
-                          double *d_wrench, double *d_sdot, int *d_counts, double *d_f, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    const char *who = "pfc_eval_state_device";
-    pfc_context *c = h->multi ? h->multi->shard[0] : h;
-    int rc = on_shard(h, c, [&](pfc_context *c1) { return eval_state_check(c1, who, n_items, d_ins_ids, d_scene, n_scene, false, d_q, d_v); });
-    if (rc != PFC_OK) return rc;
-    const int n_body = c->kin.n_body, nv = c->kin.nv;
-    const bool scatter = d_f && nv > 0;
-    if (!d_x_w_b || !d_twist_w_b || !d_pose || !d_twist || !d_wrench || !d_sdot ||
-        (scatter && (!d_jac || !d_x_w_r2 || !d_body_1 || !d_body_2)))
-        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-    if ((rc = pfc_kinematics_device(h, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_jac, stream)) != PFC_OK) return rc;
-    rc = pfc_eval_bodies_device(h, n_items, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_s, d_pose, d_twist, d_x_w_r2,
-                                d_body_1, d_body_2, d_wrench, d_sdot, d_counts, stream);
-    if (rc != PFC_OK || !scatter) return rc;
-    return pfc_scatter_generalized_device(h, n_items, d_wrench, d_x_w_r2, d_body_1, d_body_2, d_scene, n_scene, nv, d_jac, d_f, 0, stream);
-}
-
 int pfc_eval_state(pfc_handle h, int n_items, const int *ins_ids, const int *scene, int n_scene,
                    const double *q, const double *v, const double *s,
                    double *x_w_b, double *twist_w_b, double *jac,
@@ -3693,7 +3724,7 @@ int pfc_eval_state(pfc_handle h, int n_items, const int *ins_ids, const int *sce
                    double *wrench, double *sdot, int *counts, double *f) {
     if (!h) return PFC_ERR_BAD_ARG;
     const char *who = "pfc_eval_state";
-    pfc_context *c = h->multi ? h->multi->shard[0] : h;
+    pfc_context *c = first_ctx(h);
     int rc = on_shard(h, c, [&](pfc_context *c1) { return eval_state_check(c1, who, n_items, ins_ids, scene, n_scene, true, q, v); });
     if (rc != PFC_OK) return rc;
     if (n_items > 0 && (!wrench || !sdot)) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
@@ -3728,34 +3759,34 @@ int pfc_eval_state(pfc_handle h, int n_items, const int *ins_ids, const int *sce
 static_assert(PFC_MAX_NV_SOLVE == kDynWave, "k_accel runs one lane per row");
 
 int pfc_set_inertia(pfc_handle h, int n_body, const double *inertia, const double *gravity) {
-    if (h && h->multi) return on_first_shard(h, [&](pfc_context *c) { return pfc_set_inertia(c, n_body, inertia, gravity); });
     if (!h) return PFC_ERR_BAD_ARG;
-    const char *who = "pfc_set_inertia";
-    KinHost &K = h->kin;
-    if (K.n_body == 0) return fail(h, PFC_ERR_STATE, "%s before pfc_set_mechanism", who);
-    if (n_body != K.n_body) return fail(h, PFC_ERR_BAD_ARG, "%s: n_body is %d, the mechanism has %d bodies", who, n_body, K.n_body);
-    if (!inertia || !gravity) return fail(h, PFC_ERR_BAD_ARG, "%s: null table", who);
-    for (int r = 0; r < 3; ++r)
-        if (!std::isfinite(gravity[r])) return fail(h, PFC_ERR_BAD_ARG, "%s: gravity is not finite", who);
-    for (int b = 0; b < n_body; ++b) {
-        const double *in = inertia + 13 * (size_t)b;
-        if (!std::isfinite(in[12]) || in[12] < 0.0) return fail(h, PFC_ERR_BAD_ARG, "%s: body %d has the mass %.17g", who, b, in[12]);
-        double big = 0.0;
-        for (int e = 0; e < 12; ++e) {
-            if (!std::isfinite(in[e])) return fail(h, PFC_ERR_BAD_ARG, "%s: body %d's inertia is not finite", who, b);
-            if (e < 9) big = std::max(big, std::fabs(in[e]));
-        }
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        const char *who = "pfc_set_inertia";
+        KinHost &K = c->kin;
+        if (K.n_body == 0) return fail(c, PFC_ERR_STATE, "%s before pfc_set_mechanism", who);
+        if (n_body != K.n_body) return fail(c, PFC_ERR_BAD_ARG, "%s: n_body is %d, the mechanism has %d bodies", who, n_body, K.n_body);
+        if (!inertia || !gravity) return fail(c, PFC_ERR_BAD_ARG, "%s: null table", who);
         for (int r = 0; r < 3; ++r)
-            for (int c = r + 1; c < 3; ++c)
-                if (std::fabs(in[3 * c + r] - in[3 * r + c]) > 1e-12 * big)
-                    return fail(h, PFC_ERR_BAD_ARG, "%s: body %d's moment is not symmetric (M%d%d = %.17g, M%d%d = %.17g)", who, b, r, c,
-                                in[3 * c + r], c, r, in[3 * r + c]);
-    }
-    std::memcpy(K.blob.data() + K.o_inertia, inertia, sizeof(double) * 13 * (size_t)n_body);
-    for (int r = 0; r < 3; ++r) K.gravity[r] = gravity[r];
-    K.has_inertia = true;
-    h->kin_stale = true;
-    return PFC_OK;
+            if (!std::isfinite(gravity[r])) return fail(c, PFC_ERR_BAD_ARG, "%s: gravity is not finite", who);
+        for (int b = 0; b < n_body; ++b) {
+            const double *in = inertia + 13 * (size_t)b;
+            if (!std::isfinite(in[12]) || in[12] < 0.0) return fail(c, PFC_ERR_BAD_ARG, "%s: body %d has the mass %.17g", who, b, in[12]);
+            double big = 0.0;
+            for (int e = 0; e < 12; ++e) {
+                if (!std::isfinite(in[e])) return fail(c, PFC_ERR_BAD_ARG, "%s: body %d's inertia is not finite", who, b);
+                if (e < 9) big = std::max(big, std::fabs(in[e]));
+            }
+            for (int r = 0; r < 3; ++r)
+                for (int k = r + 1; k < 3; ++k)
+                    if (std::fabs(in[3 * k + r] - in[3 * r + k]) > 1e-12 * big)
+                        return fail(c, PFC_ERR_BAD_ARG, "%s: body %d's moment is not symmetric (M%d%d = %.17g, M%d%d = %.17g)", who, b, r, k,
+                                    in[3 * k + r], k, r, in[3 * r + k]);
+        }
+        std::memcpy(K.blob.data() + K.o_inertia, inertia, sizeof(double) * 13 * (size_t)n_body);
+        for (int r = 0; r < 3; ++r) K.gravity[r] = gravity[r];
+        K.has_inertia = true;
+        c->kin_stale = true;
+        return PFC_OK; });
 }
 
 // What every dynamics call needs of the handle: a mechanism, its inertias, and a scene whose tables fit k_dynamics' LDS.
@@ -3799,32 +3830,29 @@ static int dyn_launch(pfc_context *h, int n_scene, const double *q, const double
 int pfc_dynamics_device(pfc_handle h, int n_scene, const double *d_q, const double *d_v, const double *d_x_w_b, const double *d_twist_w_b,
                         double *d_qdot, double *d_H, double *d_c, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_dynamics_device(c, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_qdot, d_H, d_c, stream); });
-    const int rc = dyn_check_args(h, "pfc_dynamics_device", n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_qdot, d_H, d_c);
-    if (rc != PFC_OK || n_scene == 0) return rc;
-    return dyn_launch(h, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_qdot, d_H, d_c, stream ? (hipStream_t)stream : h->stream);
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        const int rc = dyn_check_args(c, "pfc_dynamics_device", n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_qdot, d_H, d_c);
+        if (rc != PFC_OK || n_scene == 0) return rc;
+        return dyn_launch(c, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_qdot, d_H, d_c, stream ? (hipStream_t)stream : c->stream); });
 }
 
 int pfc_dynamics(pfc_handle h, int n_scene, const double *q, const double *v, const double *x_w_b, const double *twist_w_b,
                  double *qdot, double *H, double *c) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c1) { return pfc_dynamics(c1, n_scene, q, v, x_w_b, twist_w_b, qdot, H, c); });
-    int rc = dyn_check_args(h, "pfc_dynamics", n_scene, q, v, x_w_b, twist_w_b, qdot, H, c);
-    if (rc != PFC_OK || n_scene == 0) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t ns = (size_t)n_scene, nb = ns * h->kin.n_body, nv = (size_t)h->kin.nv;
-    Stage sg(h->stage, h->stream);
-    const int k_q = sg.in(q, ns * h->kin.nq), k_v = sg.in(v, ns * nv), k_x = sg.in(x_w_b, nb * 12), k_tw = sg.in(twist_w_b, nb * 6);
-    const int k_qd = sg.out(qdot, ns * h->kin.nq), k_H = sg.out(H, ns * nv * nv), k_c = sg.out(c, ns * nv);
-    HIP_TRY(h, sg.commit());
-    rc = dyn_launch(h, n_scene, sg.at<double>(k_q), sg.at<double>(k_v), sg.at<double>(k_x), sg.at<double>(k_tw), sg.at<double>(k_qd),
-                    sg.at<double>(k_H), sg.at<double>(k_c), sg.st);
-    if (rc != PFC_OK) return rc;
-    HIP_TRY(h, sg.finish());
-    return PFC_OK;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c1) -> int {
+        int rc = dyn_check_args(c1, "pfc_dynamics", n_scene, q, v, x_w_b, twist_w_b, qdot, H, c);
+        if (rc != PFC_OK || n_scene == 0) return rc;
+        HIP_TRY(c1, hipSetDevice(c1->device));
+        const size_t ns = (size_t)n_scene, nb = ns * c1->kin.n_body, nv = (size_t)c1->kin.nv;
+        Stage sg(c1->stage, c1->stream);
+        const int k_q = sg.in(q, ns * c1->kin.nq), k_v = sg.in(v, ns * nv), k_x = sg.in(x_w_b, nb * 12), k_tw = sg.in(twist_w_b, nb * 6);
+        const int k_qd = sg.out(qdot, ns * c1->kin.nq), k_H = sg.out(H, ns * nv * nv), k_c = sg.out(c, ns * nv);
+        HIP_TRY(c1, sg.commit());
+        rc = dyn_launch(c1, n_scene, sg.at<double>(k_q), sg.at<double>(k_v), sg.at<double>(k_x), sg.at<double>(k_tw), sg.at<double>(k_qd),
+                        sg.at<double>(k_H), sg.at<double>(k_c), sg.st);
+        if (rc != PFC_OK) return rc;
+        HIP_TRY(c1, sg.finish());
+        return PFC_OK; });
 }
 
 // The solve needs the mechanism's nv only; its cap is checked before anything is launched.
@@ -3862,53 +3890,29 @@ static int accel_launch(pfc_context *h, int n_scene, const double *H, const doub
 int pfc_accelerations_device(pfc_handle h, int n_scene, const double *d_H, const double *d_c, const double *d_f, const double *d_tau,
                              double *d_vdot, int *d_info, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_accelerations_device(c, n_scene, d_H, d_c, d_f, d_tau, d_vdot, d_info, stream); });
-    const int rc = accel_check_args(h, "pfc_accelerations_device", n_scene, d_H, d_c, d_f, d_vdot);
-    if (rc != PFC_OK || n_scene == 0) return rc;
-    return accel_launch(h, n_scene, d_H, d_c, d_f, d_tau, d_vdot, d_info, stream ? (hipStream_t)stream : h->stream);
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        const int rc = accel_check_args(c, "pfc_accelerations_device", n_scene, d_H, d_c, d_f, d_vdot);
+        if (rc != PFC_OK || n_scene == 0) return rc;
+        return accel_launch(c, n_scene, d_H, d_c, d_f, d_tau, d_vdot, d_info, stream ? (hipStream_t)stream : c->stream); });
 }
 
 int pfc_accelerations(pfc_handle h, int n_scene, const double *H, const double *c, const double *f, const double *tau, double *vdot,
                       int *info) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c1) { return pfc_accelerations(c1, n_scene, H, c, f, tau, vdot, info); });
-    int rc = accel_check_args(h, "pfc_accelerations", n_scene, H, c, f, vdot);
-    if (rc != PFC_OK || n_scene == 0) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t ns = (size_t)n_scene, nv = (size_t)h->kin.nv;
-    Stage sg(h->stage, h->stream);
-    const int k_H = sg.in(H, ns * nv * nv), k_c = sg.in(c, ns * nv), k_f = sg.in(f, ns * nv), k_t = sg.in(tau, ns * nv);
-    const int k_vd = sg.out(vdot, ns * nv), k_i = sg.out(info, ns);
-    HIP_TRY(h, sg.commit());
-    rc = accel_launch(h, n_scene, sg.at<double>(k_H), sg.at<double>(k_c), sg.at<double>(k_f), sg.at<double>(k_t), sg.at<double>(k_vd),
-                      sg.at<int>(k_i), sg.st);
-    if (rc != PFC_OK) return rc;
-    HIP_TRY(h, sg.finish());
-    return PFC_OK;
-}
-
-int pfc_state_derivative_device(pfc_handle h, int n_items, const int *d_ins_ids, const int *d_scene, int n_scene,
-                                const double *d_q, const double *d_v, const double *d_s, const double *d_tau,
-                                double *d_x_w_b, double *d_twist_w_b, double *d_jac,
-                                double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
-                                double *d_wrench, double *d_sdot, int *d_counts, double *d_f,
-                                double *d_qdot, double *d_H, double *d_c, double *d_vdot, int *d_info, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    const char *who = "pfc_state_derivative_device";
-    pfc_context *c = h->multi ? h->multi->shard[0] : h;
-    int rc = on_shard(h, c, [&](pfc_context *c1) {
-        const int r = dyn_check_state(c1, who);
-        return r != PFC_OK ? r : accel_check_state(c1, who); });
-    if (rc != PFC_OK) return rc;
-    if (!d_f || !d_qdot || !d_H || !d_c || !d_vdot) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-    rc = pfc_eval_state_device(h, n_items, d_ins_ids, d_scene, n_scene, d_q, d_v, d_s, d_x_w_b, d_twist_w_b, d_jac, d_pose, d_twist, d_x_w_r2,
-                               d_body_1, d_body_2, d_wrench, d_sdot, d_counts, d_f, stream);
-    if (rc != PFC_OK) return rc;
-    if ((rc = pfc_dynamics_device(h, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_qdot, d_H, d_c, stream)) != PFC_OK) return rc;
-    return pfc_accelerations_device(h, n_scene, d_H, d_c, d_f, d_tau, d_vdot, d_info, stream);
+    return on_shard(h, first_ctx(h), [&](pfc_context *c1) -> int {
+        int rc = accel_check_args(c1, "pfc_accelerations", n_scene, H, c, f, vdot);
+        if (rc != PFC_OK || n_scene == 0) return rc;
+        HIP_TRY(c1, hipSetDevice(c1->device));
+        const size_t ns = (size_t)n_scene, nv = (size_t)c1->kin.nv;
+        Stage sg(c1->stage, c1->stream);
+        const int k_H = sg.in(H, ns * nv * nv), k_c = sg.in(c, ns * nv), k_f = sg.in(f, ns * nv), k_t = sg.in(tau, ns * nv);
+        const int k_vd = sg.out(vdot, ns * nv), k_i = sg.out(info, ns);
+        HIP_TRY(c1, sg.commit());
+        rc = accel_launch(c1, n_scene, sg.at<double>(k_H), sg.at<double>(k_c), sg.at<double>(k_f), sg.at<double>(k_t), sg.at<double>(k_vd),
+                          sg.at<int>(k_i), sg.st);
+        if (rc != PFC_OK) return rc;
+        HIP_TRY(c1, sg.finish());
+        return PFC_OK; });
 }
 
 int pfc_state_derivative(pfc_handle h, int n_items, const int *ins_ids, const int *scene, int n_scene,
@@ -3919,7 +3923,7 @@ int pfc_state_derivative(pfc_handle h, int n_items, const int *ins_ids, const in
                          double *qdot, double *H, double *c, double *vdot, int *info) {
     if (!h) return PFC_ERR_BAD_ARG;
     const char *who = "pfc_state_derivative";
-    pfc_context *c0 = h->multi ? h->multi->shard[0] : h;
+    pfc_context *c0 = first_ctx(h);
     int rc = on_shard(h, c0, [&](pfc_context *c1) {
         const int r = dyn_check_state(c1, who);
         return r != PFC_OK ? r : accel_check_state(c1, who); });
@@ -3977,33 +3981,30 @@ static int kin_dual_launch(pfc_context *h, int n_scene, int n_dir, const double 
 int pfc_kinematics_dual_device(pfc_handle h, int n_scene, int n_dir, const double *d_q, const double *d_v, const double *d_dq,
                                const double *d_dv, double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_kinematics_dual_device(c, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_dx_w_b, d_dtwist_w_b, d_djac, stream); });
-    const int rc = kin_dual_check_args(h, "pfc_kinematics_dual_device", n_scene, n_dir, d_q, d_v, d_dtwist_w_b != nullptr);
-    if (rc != PFC_OK || n_scene == 0) return rc;
-    return kin_dual_launch(h, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_dx_w_b, d_dtwist_w_b, d_djac, stream ? (hipStream_t)stream : h->stream);
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        const int rc = kin_dual_check_args(c, "pfc_kinematics_dual_device", n_scene, n_dir, d_q, d_v, d_dtwist_w_b != nullptr);
+        if (rc != PFC_OK || n_scene == 0) return rc;
+        return kin_dual_launch(c, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_dx_w_b, d_dtwist_w_b, d_djac,
+                               stream ? (hipStream_t)stream : c->stream); });
 }
 
 int pfc_kinematics_dual(pfc_handle h, int n_scene, int n_dir, const double *q, const double *v, const double *dq, const double *dv,
                         double *dx_w_b, double *dtwist_w_b, double *djac) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_kinematics_dual(c, n_scene, n_dir, q, v, dq, dv, dx_w_b, dtwist_w_b, djac); });
-    int rc = kin_dual_check_args(h, "pfc_kinematics_dual", n_scene, n_dir, q, v, dtwist_w_b != nullptr);
-    if (rc != PFC_OK || n_scene == 0) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t ns = (size_t)n_scene, nk = ns * n_dir, nbk = ns * h->kin.n_body * n_dir;
-    Stage sg(h->stage, h->stream);
-    const int k_q = sg.in(q, ns * h->kin.nq), k_v = sg.in(v, ns * h->kin.nv), k_dq = sg.in(dq, nk * h->kin.nq), k_dv = sg.in(dv, nk * h->kin.nv);
-    const int k_x = sg.out(dx_w_b, nbk * 12), k_tw = sg.out(dtwist_w_b, nbk * 6), k_j = sg.out(djac, nbk * h->kin.nv * 6);
-    HIP_TRY(h, sg.commit());
-    rc = kin_dual_launch(h, n_scene, n_dir, sg.at<double>(k_q), sg.at<double>(k_v), sg.at<double>(k_dq), sg.at<double>(k_dv),
-                         sg.at<double>(k_x), sg.at<double>(k_tw), sg.at<double>(k_j), sg.st);
-    if (rc != PFC_OK) return rc;
-    HIP_TRY(h, sg.finish());
-    return PFC_OK;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        int rc = kin_dual_check_args(c, "pfc_kinematics_dual", n_scene, n_dir, q, v, dtwist_w_b != nullptr);
+        if (rc != PFC_OK || n_scene == 0) return rc;
+        HIP_TRY(c, hipSetDevice(c->device));
+        const size_t ns = (size_t)n_scene, nk = ns * n_dir, nbk = ns * c->kin.n_body * n_dir;
+        Stage sg(c->stage, c->stream);
+        const int k_q = sg.in(q, ns * c->kin.nq), k_v = sg.in(v, ns * c->kin.nv), k_dq = sg.in(dq, nk * c->kin.nq), k_dv = sg.in(dv, nk * c->kin.nv);
+        const int k_x = sg.out(dx_w_b, nbk * 12), k_tw = sg.out(dtwist_w_b, nbk * 6), k_j = sg.out(djac, nbk * c->kin.nv * 6);
+        HIP_TRY(c, sg.commit());
+        rc = kin_dual_launch(c, n_scene, n_dir, sg.at<double>(k_q), sg.at<double>(k_v), sg.at<double>(k_dq), sg.at<double>(k_dv),
+                             sg.at<double>(k_x), sg.at<double>(k_tw), sg.at<double>(k_j), sg.st);
+        if (rc != PFC_OK) return rc;
+        HIP_TRY(c, sg.finish());
+        return PFC_OK; });
 }
 
 // What both chained Dual calls check before anything is launched or written: eval_state_check, n_dir and the Dual grids, and what the
@@ -4015,70 +4016,6 @@ static int eval_dual_state_check(pfc_context *c, const char *who, int n_items, i
     if ((rc = kin_dual_check_args(c, who, n_scene, n_dir, q, v, true)) != PFC_OK) return rc;
     if (scatter && (long long)n_scene * n_items >= (1ll << 31)) return fail(c, PFC_ERR_BAD_ARG, "%s: n_scene * n_items must be below 2^31", who);
     return PFC_OK;
-}
-
-int pfc_eval_dual_state_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
-                               const double *d_q, const double *d_v, const double *d_dq, const double *d_dv,
-                               const double *d_s, const double *d_ds,
-                               double *d_x_w_b, double *d_twist_w_b, double *d_jac,
-                               double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac,
-                               double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
-                               double *d_dpose, double *d_dtwist, double *d_dx_w_r2,
-                               double *d_wrench, double *d_sdot, double *d_dwrench, double *d_dsdot, int *d_counts,
-                               double *d_f, double *d_df, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    const char *who = "pfc_eval_dual_state_device";
-    pfc_context *c = h->multi ? h->multi->shard[0] : h;
-    const bool scatter = d_df && c->kin.nv > 0;
-    int rc = on_shard(h, c, [&](pfc_context *c1) {
-        return eval_dual_state_check(c1, who, n_items, n_dir, d_ins_ids, d_scene, n_scene, d_q, d_v, scatter); });
-    if (rc != PFC_OK) return rc;
-    const int n_body = c->kin.n_body, nv = c->kin.nv;
-    if (!d_x_w_b || !d_twist_w_b || !d_dx_w_b || !d_dtwist_w_b || !d_pose || !d_twist || !d_dpose || !d_dtwist || !d_wrench || !d_sdot ||
-        !d_dwrench || !d_dsdot || (scatter && (!d_jac || !d_djac || !d_x_w_r2 || !d_dx_w_r2 || !d_body_1 || !d_body_2)))
-        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-    if ((rc = pfc_kinematics_device(h, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_jac, stream)) != PFC_OK) return rc;
-    rc = pfc_kinematics_dual_device(h, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_dx_w_b, d_dtwist_w_b, d_djac, stream);
-    if (rc != PFC_OK) return rc;
-    rc = pfc_eval_dual_bodies_device(h, n_items, n_dir, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b, d_s,
-                                     d_ds, d_pose, d_twist, d_x_w_r2, d_body_1, d_body_2, d_dpose, d_dtwist, d_dx_w_r2, d_wrench, d_sdot,
-                                     d_dwrench, d_dsdot, d_counts, stream);
-    if (rc != PFC_OK || !scatter) return rc;
-    return pfc_scatter_generalized_dual_device(h, n_items, n_dir, d_wrench, d_dwrench, d_x_w_r2, d_dx_w_r2, d_body_1, d_body_2, d_scene,
-                                               n_scene, nv, d_jac, d_djac, d_f, d_df, 0, stream);
-}
-
-int pfc_eval_dual_state_device_more(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
-                                    const double *d_q, const double *d_v, const double *d_dq, const double *d_dv, const double *d_ds,
-                                    const double *d_x_w_b, const double *d_twist_w_b, const double *d_jac,
-                                    double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac,
-                                    const double *d_x_w_r2, const int *d_body_1, const int *d_body_2, const double *d_wrench,
-                                    double *d_dpose, double *d_dtwist, double *d_dx_w_r2, double *d_dwrench, double *d_dsdot,
-                                    double *d_df, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    const char *who = "pfc_eval_dual_state_device_more";
-    pfc_context *c = h->multi ? h->multi->shard[0] : h;
-    const bool scatter = d_df && c->kin.nv > 0;
-    int rc = on_shard(h, c, [&](pfc_context *c1) {
-        return eval_dual_state_check(c1, who, n_items, n_dir, d_ins_ids, d_scene, n_scene, d_q, d_v, scatter); });
-    if (rc != PFC_OK) return rc;
-    const int n_body = c->kin.n_body, nv = c->kin.nv;
-    if (!h->multi) {      // _more's own preconditions, before the partials are written
-        if (!h->device_kept())
-            return fail(h, PFC_ERR_STATE, "%s: no checked pfc_eval_dual_device evaluation on this handle to extend", who);
-        if (n_items != h->kept.n)
-            return fail(h, PFC_ERR_BAD_ARG, "%s: n_items is %d, the kept evaluation has %d items", who, n_items, h->kept.n);
-    }
-    if (!d_x_w_b || !d_twist_w_b || !d_dx_w_b || !d_dtwist_w_b || !d_dpose || !d_dtwist || !d_dwrench || !d_dsdot ||
-        (scatter && (!d_jac || !d_djac || !d_x_w_r2 || !d_dx_w_r2 || !d_body_1 || !d_body_2 || !d_wrench)))
-        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-    rc = pfc_kinematics_dual_device(h, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_dx_w_b, d_dtwist_w_b, d_djac, stream);
-    if (rc != PFC_OK) return rc;
-    rc = pfc_eval_dual_bodies_device_more(h, n_items, n_dir, d_ins_ids, d_scene, n_scene, n_body, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b,
-                                          d_ds, d_dpose, d_dtwist, d_dx_w_r2, d_dwrench, d_dsdot, stream);
-    if (rc != PFC_OK || !scatter) return rc;
-    return pfc_scatter_generalized_dual_device(h, n_items, n_dir, d_wrench, d_dwrench, d_x_w_r2, d_dx_w_r2, d_body_1, d_body_2, d_scene,
-                                               n_scene, nv, d_jac, d_djac, nullptr, d_df, 0, stream);
 }
 
 // ---- Dual forward dynamics: partials of qdot, H, c and vdot (the ScatDual instantiation and k_accel_dual of pfc_dyn.h) ------------
@@ -4137,40 +4074,35 @@ int pfc_dynamics_dual_device(pfc_handle h, int n_scene, int n_dir, const double 
                              const double *d_dv, const double *d_x_w_b, const double *d_twist_w_b, const double *d_dx_w_b,
                              const double *d_dtwist_w_b, double *d_dqdot, double *d_dH, double *d_dc, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_dynamics_dual_device(c, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b, d_dqdot,
-                                            d_dH, d_dc, stream); });
-    const int rc = dyn_dual_check_args(h, "pfc_dynamics_dual_device", n_scene, n_dir, d_q, d_v, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b,
-                                       d_dqdot, d_dH, d_dc);
-    if (rc != PFC_OK || n_scene == 0) return rc;
-    return dyn_dual_launch(h, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b, d_dqdot, d_dH, d_dc,
-                           stream ? (hipStream_t)stream : h->stream);
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        const int rc = dyn_dual_check_args(c, "pfc_dynamics_dual_device", n_scene, n_dir, d_q, d_v, d_x_w_b, d_twist_w_b, d_dx_w_b,
+                                           d_dtwist_w_b, d_dqdot, d_dH, d_dc);
+        if (rc != PFC_OK || n_scene == 0) return rc;
+        return dyn_dual_launch(c, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b, d_dqdot, d_dH, d_dc,
+                               stream ? (hipStream_t)stream : c->stream); });
 }
 
 int pfc_dynamics_dual(pfc_handle h, int n_scene, int n_dir, const double *q, const double *v, const double *dq, const double *dv,
                       const double *x_w_b, const double *twist_w_b, const double *dx_w_b, const double *dtwist_w_b,
                       double *dqdot, double *dH, double *dc) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c1) {
-            return pfc_dynamics_dual(c1, n_scene, n_dir, q, v, dq, dv, x_w_b, twist_w_b, dx_w_b, dtwist_w_b, dqdot, dH, dc); });
-    int rc = dyn_dual_check_args(h, "pfc_dynamics_dual", n_scene, n_dir, q, v, x_w_b, twist_w_b, dx_w_b, dtwist_w_b, dqdot, dH, dc);
-    if (rc != PFC_OK || n_scene == 0) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t ns = (size_t)n_scene, nk = ns * n_dir, nb = ns * h->kin.n_body, nv = (size_t)h->kin.nv, nq = (size_t)h->kin.nq;
-    Stage sg(h->stage, h->stream);
-    const int k_q = sg.in(q, ns * nq), k_v = sg.in(v, ns * nv), k_dq = sg.in(dq, nk * nq), k_dv = sg.in(dv, nk * nv);
-    const int k_x = sg.in(x_w_b, nb * 12), k_tw = sg.in(twist_w_b, nb * 6), k_dx = sg.in(dx_w_b, nb * n_dir * 12),
-              k_dtw = sg.in(dtwist_w_b, nb * n_dir * 6);
-    const int k_qd = sg.out(dqdot, nk * nq), k_H = sg.out(dH, nk * nv * nv), k_c = sg.out(dc, nk * nv);
-    HIP_TRY(h, sg.commit());
-    rc = dyn_dual_launch(h, n_scene, n_dir, sg.at<double>(k_q), sg.at<double>(k_v), sg.at<double>(k_dq), sg.at<double>(k_dv),
-                         sg.at<double>(k_x), sg.at<double>(k_tw), sg.at<double>(k_dx), sg.at<double>(k_dtw), sg.at<double>(k_qd),
-                         sg.at<double>(k_H), sg.at<double>(k_c), sg.st);
-    if (rc != PFC_OK) return rc;
-    HIP_TRY(h, sg.finish());
-    return PFC_OK;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        int rc = dyn_dual_check_args(c, "pfc_dynamics_dual", n_scene, n_dir, q, v, x_w_b, twist_w_b, dx_w_b, dtwist_w_b, dqdot, dH, dc);
+        if (rc != PFC_OK || n_scene == 0) return rc;
+        HIP_TRY(c, hipSetDevice(c->device));
+        const size_t ns = (size_t)n_scene, nk = ns * n_dir, nb = ns * c->kin.n_body, nv = (size_t)c->kin.nv, nq = (size_t)c->kin.nq;
+        Stage sg(c->stage, c->stream);
+        const int k_q = sg.in(q, ns * nq), k_v = sg.in(v, ns * nv), k_dq = sg.in(dq, nk * nq), k_dv = sg.in(dv, nk * nv);
+        const int k_x = sg.in(x_w_b, nb * 12), k_tw = sg.in(twist_w_b, nb * 6), k_dx = sg.in(dx_w_b, nb * n_dir * 12),
+                  k_dtw = sg.in(dtwist_w_b, nb * n_dir * 6);
+        const int k_qd = sg.out(dqdot, nk * nq), k_H = sg.out(dH, nk * nv * nv), k_c = sg.out(dc, nk * nv);
+        HIP_TRY(c, sg.commit());
+        rc = dyn_dual_launch(c, n_scene, n_dir, sg.at<double>(k_q), sg.at<double>(k_v), sg.at<double>(k_dq), sg.at<double>(k_dv),
+                             sg.at<double>(k_x), sg.at<double>(k_tw), sg.at<double>(k_dx), sg.at<double>(k_dtw), sg.at<double>(k_qd),
+                             sg.at<double>(k_H), sg.at<double>(k_c), sg.st);
+        if (rc != PFC_OK) return rc;
+        HIP_TRY(c, sg.finish());
+        return PFC_OK; });
 }
 
 static int accel_dual_check_args(pfc_context *h, const char *who, int n_scene, int n_dir, const double *H, const double *c, const double *f,
@@ -4212,38 +4144,33 @@ int pfc_accelerations_dual_device(pfc_handle h, int n_scene, int n_dir, const do
                                   const double *d_tau, const double *d_dH, const double *d_dc, const double *d_df, const double *d_dtau,
                                   double *d_vdot, double *d_dvdot, int *d_info, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_accelerations_dual_device(c, n_scene, n_dir, d_H, d_c, d_f, d_tau, d_dH, d_dc, d_df, d_dtau, d_vdot, d_dvdot, d_info,
-                                                 stream); });
-    const int rc = accel_dual_check_args(h, "pfc_accelerations_dual_device", n_scene, n_dir, d_H, d_c, d_f, d_dH, d_dc, d_df, d_dvdot);
-    if (rc != PFC_OK || n_scene == 0) return rc;
-    return accel_dual_launch(h, n_scene, n_dir, d_H, d_c, d_f, d_tau, d_dH, d_dc, d_df, d_dtau, d_vdot, d_dvdot, d_info,
-                             stream ? (hipStream_t)stream : h->stream);
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        const int rc = accel_dual_check_args(c, "pfc_accelerations_dual_device", n_scene, n_dir, d_H, d_c, d_f, d_dH, d_dc, d_df, d_dvdot);
+        if (rc != PFC_OK || n_scene == 0) return rc;
+        return accel_dual_launch(c, n_scene, n_dir, d_H, d_c, d_f, d_tau, d_dH, d_dc, d_df, d_dtau, d_vdot, d_dvdot, d_info,
+                                 stream ? (hipStream_t)stream : c->stream); });
 }
 
 int pfc_accelerations_dual(pfc_handle h, int n_scene, int n_dir, const double *H, const double *c, const double *f, const double *tau,
                            const double *dH, const double *dc, const double *df, const double *dtau, double *vdot, double *dvdot,
                            int *info) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c1) {
-            return pfc_accelerations_dual(c1, n_scene, n_dir, H, c, f, tau, dH, dc, df, dtau, vdot, dvdot, info); });
-    int rc = accel_dual_check_args(h, "pfc_accelerations_dual", n_scene, n_dir, H, c, f, dH, dc, df, dvdot);
-    if (rc != PFC_OK || n_scene == 0) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t ns = (size_t)n_scene, nk = ns * n_dir, nv = (size_t)h->kin.nv;
-    Stage sg(h->stage, h->stream);
-    const int k_H = sg.in(H, ns * nv * nv), k_c = sg.in(c, ns * nv), k_f = sg.in(f, ns * nv), k_t = sg.in(tau, ns * nv);
-    const int k_dH = sg.in(dH, nk * nv * nv), k_dc = sg.in(dc, nk * nv), k_df = sg.in(df, nk * nv), k_dt = sg.in(dtau, nk * nv);
-    const int k_vd = sg.out(vdot, ns * nv), k_dvd = sg.out(dvdot, nk * nv), k_i = sg.out(info, ns);
-    HIP_TRY(h, sg.commit());
-    rc = accel_dual_launch(h, n_scene, n_dir, sg.at<double>(k_H), sg.at<double>(k_c), sg.at<double>(k_f), sg.at<double>(k_t),
-                           sg.at<double>(k_dH), sg.at<double>(k_dc), sg.at<double>(k_df), sg.at<double>(k_dt), sg.at<double>(k_vd),
-                           sg.at<double>(k_dvd), sg.at<int>(k_i), sg.st);
-    if (rc != PFC_OK) return rc;
-    HIP_TRY(h, sg.finish());
-    return PFC_OK;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c1) -> int {
+        int rc = accel_dual_check_args(c1, "pfc_accelerations_dual", n_scene, n_dir, H, c, f, dH, dc, df, dvdot);
+        if (rc != PFC_OK || n_scene == 0) return rc;
+        HIP_TRY(c1, hipSetDevice(c1->device));
+        const size_t ns = (size_t)n_scene, nk = ns * n_dir, nv = (size_t)c1->kin.nv;
+        Stage sg(c1->stage, c1->stream);
+        const int k_H = sg.in(H, ns * nv * nv), k_c = sg.in(c, ns * nv), k_f = sg.in(f, ns * nv), k_t = sg.in(tau, ns * nv);
+        const int k_dH = sg.in(dH, nk * nv * nv), k_dc = sg.in(dc, nk * nv), k_df = sg.in(df, nk * nv), k_dt = sg.in(dtau, nk * nv);
+        const int k_vd = sg.out(vdot, ns * nv), k_dvd = sg.out(dvdot, nk * nv), k_i = sg.out(info, ns);
+        HIP_TRY(c1, sg.commit());
+        rc = accel_dual_launch(c1, n_scene, n_dir, sg.at<double>(k_H), sg.at<double>(k_c), sg.at<double>(k_f), sg.at<double>(k_t),
+                               sg.at<double>(k_dH), sg.at<double>(k_dc), sg.at<double>(k_df), sg.at<double>(k_dt), sg.at<double>(k_vd),
+                               sg.at<double>(k_dvd), sg.at<int>(k_i), sg.st);
+        if (rc != PFC_OK) return rc;
+        HIP_TRY(c1, sg.finish());
+        return PFC_OK; });
 }
 
 // What both Dual chains check before the first launch, beyond what the Dual evaluation checks itself: the inertias, the Dual LDS
@@ -4253,60 +4180,6 @@ static int state_derivative_dual_check(pfc_context *c, const char *who, int n_sc
     if (rc != PFC_OK) return rc;
     if ((rc = accel_check_state(c, who)) != PFC_OK) return rc;
     return dual_dir_check(c, who, n_scene, n_dir);
-}
-
-int pfc_state_derivative_dual_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
-                                     const double *d_q, const double *d_v, const double *d_dq, const double *d_dv,
-                                     const double *d_s, const double *d_ds, const double *d_tau, const double *d_dtau,
-                                     double *d_x_w_b, double *d_twist_w_b, double *d_jac,
-                                     double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac,
-                                     double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
-                                     double *d_dpose, double *d_dtwist, double *d_dx_w_r2,
-                                     double *d_wrench, double *d_sdot, double *d_dwrench, double *d_dsdot, int *d_counts,
-                                     double *d_f, double *d_df,
-                                     double *d_qdot, double *d_H, double *d_c, double *d_vdot, int *d_info,
-                                     double *d_dqdot, double *d_dH, double *d_dc, double *d_dvdot, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    const char *who = "pfc_state_derivative_dual_device";
-    pfc_context *c = h->multi ? h->multi->shard[0] : h;
-    int rc = on_shard(h, c, [&](pfc_context *c1) { return state_derivative_dual_check(c1, who, n_scene, n_dir); });
-    if (rc != PFC_OK) return rc;
-    if (!d_f || !d_df || !d_qdot || !d_H || !d_c || !d_vdot || !d_dqdot || !d_dH || !d_dc || !d_dvdot)
-        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-    rc = pfc_eval_dual_state_device(h, n_items, n_dir, d_ins_ids, d_scene, n_scene, d_q, d_v, d_dq, d_dv, d_s, d_ds, d_x_w_b, d_twist_w_b,
-                                    d_jac, d_dx_w_b, d_dtwist_w_b, d_djac, d_pose, d_twist, d_x_w_r2, d_body_1, d_body_2, d_dpose, d_dtwist,
-                                    d_dx_w_r2, d_wrench, d_sdot, d_dwrench, d_dsdot, d_counts, d_f, d_df, stream);
-    if (rc != PFC_OK) return rc;
-    if ((rc = pfc_dynamics_device(h, n_scene, d_q, d_v, d_x_w_b, d_twist_w_b, d_qdot, d_H, d_c, stream)) != PFC_OK) return rc;
-    rc = pfc_dynamics_dual_device(h, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b, d_dqdot, d_dH, d_dc,
-                                  stream);
-    if (rc != PFC_OK) return rc;
-    return pfc_accelerations_dual_device(h, n_scene, n_dir, d_H, d_c, d_f, d_tau, d_dH, d_dc, d_df, d_dtau, d_vdot, d_dvdot, d_info, stream);
-}
-
-int pfc_state_derivative_dual_device_more(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
-                                          const double *d_q, const double *d_v, const double *d_dq, const double *d_dv, const double *d_ds,
-                                          const double *d_tau, const double *d_dtau,
-                                          const double *d_x_w_b, const double *d_twist_w_b, const double *d_jac,
-                                          double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac,
-                                          const double *d_x_w_r2, const int *d_body_1, const int *d_body_2, const double *d_wrench,
-                                          double *d_dpose, double *d_dtwist, double *d_dx_w_r2, double *d_dwrench, double *d_dsdot,
-                                          double *d_df, const double *d_H, const double *d_c, const double *d_f,
-                                          double *d_dqdot, double *d_dH, double *d_dc, double *d_dvdot, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    const char *who = "pfc_state_derivative_dual_device_more";
-    pfc_context *c = h->multi ? h->multi->shard[0] : h;
-    int rc = on_shard(h, c, [&](pfc_context *c1) { return state_derivative_dual_check(c1, who, n_scene, n_dir); });
-    if (rc != PFC_OK) return rc;
-    if (!d_df || !d_H || !d_c || !d_f || !d_dqdot || !d_dH || !d_dc || !d_dvdot) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-    rc = pfc_eval_dual_state_device_more(h, n_items, n_dir, d_ins_ids, d_scene, n_scene, d_q, d_v, d_dq, d_dv, d_ds, d_x_w_b, d_twist_w_b, d_jac,
-                                         d_dx_w_b, d_dtwist_w_b, d_djac, d_x_w_r2, d_body_1, d_body_2, d_wrench, d_dpose, d_dtwist, d_dx_w_r2,
-                                         d_dwrench, d_dsdot, d_df, stream);
-    if (rc != PFC_OK) return rc;
-    rc = pfc_dynamics_dual_device(h, n_scene, n_dir, d_q, d_v, d_dq, d_dv, d_x_w_b, d_twist_w_b, d_dx_w_b, d_dtwist_w_b, d_dqdot, d_dH, d_dc,
-                                  stream);
-    if (rc != PFC_OK) return rc;
-    return pfc_accelerations_dual_device(h, n_scene, n_dir, d_H, d_c, d_f, d_tau, d_dH, d_dc, d_df, d_dtau, nullptr, d_dvdot, nullptr, stream);
 }
 
 // The broadphase pose of a host Dual call (m.float's state: calcTriTetIntersections!, non_friction.jl:94-101) is kept in pinned
@@ -4453,24 +4326,24 @@ int pfc_get_stats(pfc_handle h, long long *out8) {
 
 int pfc_get_stage_ms(pfc_handle h, float *out6) {
     if (!h || !out6) return PFC_ERR_BAD_ARG;
-    if (h->multi)      // the first shard's stages (every shard runs the same sequence on its range)
-        return on_first_shard(h, [&](pfc_context *c) { return pfc_get_stage_ms(c, out6); });
-    if (!h->ev_valid) return fail(h, PFC_ERR_STATE, "profile option was off for the last evaluation");
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipEventSynchronize(h->ev[EV_FIN]));
-    for (int k = 0; k < 5; ++k) HIP_TRY(h, hipEventElapsedTime(&out6[k], h->ev[k], h->ev[k + 1]));
-    HIP_TRY(h, hipEventElapsedTime(&out6[5], h->ev[EV_START], h->ev[EV_FIN]));
-    if (h->last_parts == 2 && h->twin && h->twin->ev_valid) {
-        // two concurrent halves: mean duration of a stage over the two half-launches, total = the longer half
-        pfc_context *t = h->twin;
-        float b[6];
-        HIP_TRY(h, hipEventSynchronize(t->ev[EV_FIN]));
-        for (int k = 0; k < 5; ++k) HIP_TRY(h, hipEventElapsedTime(&b[k], t->ev[k], t->ev[k + 1]));
-        HIP_TRY(h, hipEventElapsedTime(&b[5], t->ev[EV_START], t->ev[EV_FIN]));
-        for (int k = 0; k < 5; ++k) out6[k] = 0.5f * (out6[k] + b[k]);
-        if (b[5] > out6[5]) out6[5] = b[5];
-    }
-    return PFC_OK;
+    // the first shard's stages (every shard runs the same sequence on its range)
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        if (!c->ev_valid) return fail(c, PFC_ERR_STATE, "profile option was off for the last evaluation");
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipEventSynchronize(c->ev[EV_FIN]));
+        for (int k = 0; k < 5; ++k) HIP_TRY(c, hipEventElapsedTime(&out6[k], c->ev[k], c->ev[k + 1]));
+        HIP_TRY(c, hipEventElapsedTime(&out6[5], c->ev[EV_START], c->ev[EV_FIN]));
+        if (c->last_parts == 2 && c->twin && c->twin->ev_valid) {
+            // two concurrent halves: mean duration of a stage over the two half-launches, total = the longer half
+            pfc_context *t = c->twin;
+            float b[6];
+            HIP_TRY(c, hipEventSynchronize(t->ev[EV_FIN]));
+            for (int k = 0; k < 5; ++k) HIP_TRY(c, hipEventElapsedTime(&b[k], t->ev[k], t->ev[k + 1]));
+            HIP_TRY(c, hipEventElapsedTime(&b[5], t->ev[EV_START], t->ev[EV_FIN]));
+            for (int k = 0; k < 5; ++k) out6[k] = 0.5f * (out6[k] + b[k]);
+            if (b[5] > out6[5]) out6[5] = b[5];
+        }
+        return PFC_OK; });
 }
 
 int pfc_last_parts(pfc_handle h) { return h ? (h->multi ? pfc_last_parts(h->multi->shard[0]) : (h->last_fused ? 0 : h->last_parts)) : 0; }
@@ -4575,6 +4448,7 @@ int pfc_debug_stiffness(pfc_handle h, int item, double *K36, double *Kis36, doub
 // Both forms of pfc_scatter_generalized behind their checks: f zeroed unless it accumulates, then k_scatter, enqueued on st.
 static int scatter_launch(pfc_context *h, int n_items, int nv, const double *wrench, const double *x_w_r2, const int *body_1, const int *body_2,
                           const int *scene, int n_scene, const double *jac, double *f, int accumulate, hipStream_t st) {
+    HIP_TRY(h, hipSetDevice(h->device));
     if (!accumulate) HIP_TRY(h, hipMemsetAsync(f, 0, sizeof(double) * (size_t)n_scene * nv, st));
     if (n_items > 0) {
         ScatterArgs a;
@@ -4590,44 +4464,41 @@ static int scatter_launch(pfc_context *h, int n_items, int nv, const double *wre
 int pfc_scatter_generalized(pfc_handle h, int n_items, const double *wrench, const double *x_w_r2, const int *body_1,
                             const int *body_2, const int *scene, int n_scene, int n_body, int nv, const double *jac,
                             double *f_out) {
-    if (h && h->multi)      // a few microseconds of work: the first device does it
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_scatter_generalized(c, n_items, wrench, x_w_r2, body_1, body_2, scene, n_scene, n_body, nv, jac, f_out); });
-    if (!h || n_items < 0 || nv <= 0 || n_scene <= 0 || n_body < 0 || !f_out)
-        return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized: bad argument");
-    if (n_items > 0 && (!wrench || !x_w_r2 || !body_1 || !body_2 || (n_body > 0 && !jac)))
-        return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized: null buffer");
-    for (int i = 0; i < n_items; ++i) {
-        if (body_1[i] >= n_body || body_2[i] >= n_body || (scene && (scene[i] < 0 || scene[i] >= n_scene)))
-            return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized: body / scene id out of range (item %d)", i);
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (size_t)n_items, nf = (size_t)n_scene * nv, nj = n ? (size_t)n_body * 6 * nv : 0;
-    Stage sg(h->stage, h->stream);
-    const int k_w = sg.in(wrench, n * 6), k_x = sg.in(x_w_r2, n * 12), k_j = sg.in(jac, nj);
-    const int k_b1 = sg.in(body_1, n), k_b2 = sg.in(body_2, n), k_sc = sg.in(scene, n), k_f = sg.out(f_out, nf);
-    HIP_TRY(h, sg.commit());
-    const int rc = scatter_launch(h, n_items, nv, sg.at<double>(k_w), sg.at<double>(k_x), sg.at<int>(k_b1), sg.at<int>(k_b2), sg.at<int>(k_sc),
-                                  n_scene, sg.at<double>(k_j), sg.at<double>(k_f), 0, sg.st);
-    if (rc != PFC_OK) return rc;
-    HIP_TRY(h, sg.finish());
-    return PFC_OK;
+    if (!h) return PFC_ERR_BAD_ARG;
+    // a few microseconds of work: the first device does it
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        if (n_items < 0 || nv <= 0 || n_scene <= 0 || n_body < 0 || !f_out)
+            return fail(c, PFC_ERR_BAD_ARG, "pfc_scatter_generalized: bad argument");
+        if (n_items > 0 && (!wrench || !x_w_r2 || !body_1 || !body_2 || (n_body > 0 && !jac)))
+            return fail(c, PFC_ERR_BAD_ARG, "pfc_scatter_generalized: null buffer");
+        for (int i = 0; i < n_items; ++i) {
+            if (body_1[i] >= n_body || body_2[i] >= n_body || (scene && (scene[i] < 0 || scene[i] >= n_scene)))
+                return fail(c, PFC_ERR_BAD_ARG, "pfc_scatter_generalized: body / scene id out of range (item %d)", i);
+        }
+        HIP_TRY(c, hipSetDevice(c->device));
+        const size_t n = (size_t)n_items, nf = (size_t)n_scene * nv, nj = n ? (size_t)n_body * 6 * nv : 0;
+        Stage sg(c->stage, c->stream);
+        const int k_w = sg.in(wrench, n * 6), k_x = sg.in(x_w_r2, n * 12), k_j = sg.in(jac, nj);
+        const int k_b1 = sg.in(body_1, n), k_b2 = sg.in(body_2, n), k_sc = sg.in(scene, n), k_f = sg.out(f_out, nf);
+        HIP_TRY(c, sg.commit());
+        const int rc = scatter_launch(c, n_items, nv, sg.at<double>(k_w), sg.at<double>(k_x), sg.at<int>(k_b1), sg.at<int>(k_b2),
+                                      sg.at<int>(k_sc), n_scene, sg.at<double>(k_j), sg.at<double>(k_f), 0, sg.st);
+        if (rc != PFC_OK) return rc;
+        HIP_TRY(c, sg.finish());
+        return PFC_OK; });
 }
 
 int pfc_scatter_generalized_device(pfc_handle h, int n_items, const double *d_wrench, const double *d_x_w_r2, const int *d_body_1,
                                    const int *d_body_2, const int *d_scene, int n_scene, int nv, const double *d_jac, double *d_f,
                                    int accumulate, void *stream) {
-    if (h && h->multi)      // the wrenches of a multi-device evaluation end up on the first device: so does this
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_scatter_generalized_device(c, n_items, d_wrench, d_x_w_r2, d_body_1, d_body_2, d_scene, n_scene, nv, d_jac, d_f, accumulate,
-                                                  stream); });
-    if (!h || n_items < 0 || nv <= 0 || n_scene <= 0 || !d_f)
-        return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_device: bad argument");
-    if (n_items > 0 && (!d_wrench || !d_x_w_r2 || !d_body_1 || !d_body_2 || !d_jac))
-        return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_device: null buffer");
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    return scatter_launch(h, n_items, nv, d_wrench, d_x_w_r2, d_body_1, d_body_2, d_scene, n_scene, d_jac, d_f, accumulate, st);
+    if (!h) return PFC_ERR_BAD_ARG;
+    // the wrenches of a multi-device evaluation end up on the first device: so does this
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        if (n_items < 0 || nv <= 0 || n_scene <= 0 || !d_f) return fail(c, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_device: bad argument");
+        if (n_items > 0 && (!d_wrench || !d_x_w_r2 || !d_body_1 || !d_body_2 || !d_jac))
+            return fail(c, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_device: null buffer");
+        return scatter_launch(c, n_items, nv, d_wrench, d_x_w_r2, d_body_1, d_body_2, d_scene, n_scene, d_jac, d_f, accumulate,
+                              stream ? (hipStream_t)stream : c->stream); });
 }
 
 // pfc_scatter_generalized_dual[_device] behind the scene CSR (keys / off, or NULL: one segment): the world wrenches and the ordered
@@ -4658,42 +4529,63 @@ int pfc_scatter_generalized_dual(pfc_handle h, int n_items, int n_dir, const dou
                                  const double *x_w_r2, const double *d_x_w_r2, const int *body_1, const int *body_2,
                                  const int *scene, int n_scene, int n_body, int nv, const double *jac, const double *d_jac,
                                  double *f_out, double *d_f_out) {
-    if (h && h->multi)      // as pfc_scatter_generalized: the first device does it
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_scatter_generalized_dual(c, n_items, n_dir, wrench, d_wrench, x_w_r2, d_x_w_r2, body_1, body_2, scene, n_scene, n_body, nv,
-                                                jac, d_jac, f_out, d_f_out); });
-    if (!h || n_items < 0 || n_dir < 1 || n_dir > kScatMaxDir || nv <= 0 || n_scene <= 0 || n_body < 0 || !d_f_out)
-        return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual: bad argument");
-    if ((long long)n_scene * n_items >= (1ll << 31))
-        return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual: n_scene * n_items must be below 2^31");
-    if (n_items > 0 && (!wrench || !d_wrench || !x_w_r2 || !body_1 || !body_2 || (n_body > 0 && !jac)))
-        return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual: null buffer");
-    for (int i = 0; i < n_items; ++i) {
-        if (body_1[i] >= n_body || body_2[i] >= n_body || (scene && (scene[i] < 0 || scene[i] >= n_scene)))
-            return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual: body / scene id out of range (item %d)", i);
-    }
+    if (!h) return PFC_ERR_BAD_ARG;
+    // as pfc_scatter_generalized: the first device does it
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        if (n_items < 0 || n_dir < 1 || n_dir > kScatMaxDir || nv <= 0 || n_scene <= 0 || n_body < 0 || !d_f_out)
+            return fail(c, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual: bad argument");
+        if ((long long)n_scene * n_items >= (1ll << 31))
+            return fail(c, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual: n_scene * n_items must be below 2^31");
+        if (n_items > 0 && (!wrench || !d_wrench || !x_w_r2 || !body_1 || !body_2 || (n_body > 0 && !jac)))
+            return fail(c, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual: null buffer");
+        for (int i = 0; i < n_items; ++i) {
+            if (body_1[i] >= n_body || body_2[i] >= n_body || (scene && (scene[i] < 0 || scene[i] >= n_scene)))
+                return fail(c, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual: body / scene id out of range (item %d)", i);
+        }
+        HIP_TRY(c, hipSetDevice(c->device));
+        const size_t n = (size_t)n_items, nd = (size_t)n_dir, nf = (size_t)n_scene * nv, nj = n ? (size_t)n_body * nv * 6 : 0;
+        std::vector<int> keys, off;
+        if (scene && n_items > 0) {      // the items by scene in ascending item order: a counting sort
+            off.assign((size_t)n_scene + 1, 0);
+            for (int i = 0; i < n_items; ++i) ++off[(size_t)scene[i] + 1];
+            for (int s = 0; s < n_scene; ++s) off[(size_t)s + 1] += off[(size_t)s];
+            std::vector<int> fill(off.begin(), off.end() - 1);
+            keys.resize(n);
+            for (int i = 0; i < n_items; ++i) keys[(size_t)fill[(size_t)scene[i]]++] = scene[i] * n_items + i;
+        }
+        Stage sg(c->stage, c->stream);
+        const int k_w = sg.in(wrench, n * 6), k_dw = sg.in(d_wrench, n * nd * 6), k_x = sg.in(x_w_r2, n * 12), k_dx = sg.in(d_x_w_r2, n * nd * 12);
+        const int k_j = sg.in(jac, nj), k_dj = sg.in(d_jac, nj * nd), k_b1 = sg.in(body_1, n), k_b2 = sg.in(body_2, n);
+        const int k_keys = sg.in(keys.empty() ? nullptr : keys.data(), keys.size()), k_off = sg.in(off.empty() ? nullptr : off.data(), off.size());
+        const int k_f = sg.out(f_out, nf), k_df = sg.out(d_f_out, nf * nd);
+        HIP_TRY(c, sg.commit());
+        const int rc = scatter_dual_launch(c, n_items, n_dir, sg.at<double>(k_w), sg.at<double>(k_dw), sg.at<double>(k_x), sg.at<double>(k_dx),
+                                           sg.at<int>(k_b1), sg.at<int>(k_b2), sg.at<int>(k_keys), sg.at<int>(k_off), n_scene, nv,
+                                           sg.at<double>(k_j), sg.at<double>(k_dj), sg.at<double>(k_f), sg.at<double>(k_df), 0, sg.st);
+        if (rc != PFC_OK) return rc;
+        HIP_TRY(c, sg.finish());
+        return PFC_OK; });
+}
+
+// The scene CSR of the device form on st, in the context's own buffers: the items by scene in ascending item order -- sorted keys
+// scene * n_items + item, offsets per scene -- or both null (no d_scene, or no items: one segment).
+static int scatter_dual_csr(pfc_context *h, int n_items, const int *d_scene, int n_scene, hipStream_t st, int **keys, int **off) {
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (size_t)n_items, nd = (size_t)n_dir, nf = (size_t)n_scene * nv, nj = n ? (size_t)n_body * nv * 6 : 0;
-    std::vector<int> keys, off;
-    if (scene && n_items > 0) {      // the items by scene in ascending item order: a counting sort
-        off.assign((size_t)n_scene + 1, 0);
-        for (int i = 0; i < n_items; ++i) ++off[(size_t)scene[i] + 1];
-        for (int s = 0; s < n_scene; ++s) off[(size_t)s + 1] += off[(size_t)s];
-        std::vector<int> fill(off.begin(), off.end() - 1);
-        keys.resize(n);
-        for (int i = 0; i < n_items; ++i) keys[(size_t)fill[(size_t)scene[i]]++] = scene[i] * n_items + i;
-    }
-    Stage sg(h->stage, h->stream);
-    const int k_w = sg.in(wrench, n * 6), k_dw = sg.in(d_wrench, n * nd * 6), k_x = sg.in(x_w_r2, n * 12), k_dx = sg.in(d_x_w_r2, n * nd * 12);
-    const int k_j = sg.in(jac, nj), k_dj = sg.in(d_jac, nj * nd), k_b1 = sg.in(body_1, n), k_b2 = sg.in(body_2, n);
-    const int k_keys = sg.in(keys.empty() ? nullptr : keys.data(), keys.size()), k_off = sg.in(off.empty() ? nullptr : off.data(), off.size());
-    const int k_f = sg.out(f_out, nf), k_df = sg.out(d_f_out, nf * nd);
-    HIP_TRY(h, sg.commit());
-    const int rc = scatter_dual_launch(h, n_items, n_dir, sg.at<double>(k_w), sg.at<double>(k_dw), sg.at<double>(k_x), sg.at<double>(k_dx),
-                                       sg.at<int>(k_b1), sg.at<int>(k_b2), sg.at<int>(k_keys), sg.at<int>(k_off), n_scene, nv, sg.at<double>(k_j),
-                                       sg.at<double>(k_dj), sg.at<double>(k_f), sg.at<double>(k_df), 0, sg.st);
-    if (rc != PFC_OK) return rc;
-    HIP_TRY(h, sg.finish());
+    *keys = *off = nullptr;
+    if (!d_scene || n_items <= 0) return PFC_OK;
+    const size_t n = (size_t)n_items;
+    size_t bytes = 0;
+    HIP_TRY(h, h->sdual_i.ensure(n * 3 + (size_t)n_scene + 2));
+    HIP_TRY(h, pfc_sort_temp_bytes(n, 32, &bytes));
+    HIP_TRY(h, h->sdual_tmp.ensure(bytes ? bytes : 1));
+    *keys = h->sdual_i.p; *off = *keys + n;
+    int *count = *off + n_scene + 1;
+    unsigned *kin = reinterpret_cast<unsigned *>(count + 1), *kout = kin + n;
+    hipLaunchKernelGGL(k_scat_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n_items, n_scene, d_scene, *keys, count);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, pfc_sort_indices(*keys, count, n, kin, kout, h->sdual_tmp.p, h->sdual_tmp.cap, st));
+    hipLaunchKernelGGL(k_scat_off, dim3((unsigned)(((size_t)n_scene + 256) / 256)), dim3(256), 0, st, n_items, n_scene, *keys, *off);
+    HIP_TRY(h, hipGetLastError());
     return PFC_OK;
 }
 
@@ -4701,37 +4593,224 @@ int pfc_scatter_generalized_dual_device(pfc_handle h, int n_items, int n_dir, co
                                         const double *d_x_w_r2, const double *d_dx_w_r2, const int *d_body_1, const int *d_body_2,
                                         const int *d_scene, int n_scene, int nv, const double *d_jac, const double *d_djac,
                                         double *d_f, double *d_df, int accumulate, void *stream) {
-    if (h && h->multi)      // the wrenches of a multi-device evaluation end up on the first device: so does this
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_scatter_generalized_dual_device(c, n_items, n_dir, d_wrench_val, d_dwrench, d_x_w_r2, d_dx_w_r2, d_body_1, d_body_2, d_scene,
-                                                       n_scene, nv, d_jac, d_djac, d_f, d_df, accumulate, stream); });
-    if (!h || n_items < 0 || n_dir < 1 || n_dir > kScatMaxDir || nv <= 0 || n_scene <= 0 || !d_df)
-        return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual_device: bad argument");
-    if ((long long)n_scene * n_items >= (1ll << 31))
-        return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual_device: n_scene * n_items must be below 2^31");
-    if (n_items > 0 && (!d_wrench_val || !d_dwrench || !d_x_w_r2 || !d_body_1 || !d_body_2 || !d_jac))
-        return fail(h, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual_device: null buffer");
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    const bool csr = d_scene && n_items > 0;
-    int *keys = nullptr, *off = nullptr;
-    if (csr) {      // the items by scene in ascending item order: sorted keys scene * n_items + item, offsets per scene
-        const size_t n = (size_t)n_items;
-        size_t bytes = 0;
-        HIP_TRY(h, h->sdual_i.ensure(n * 3 + (size_t)n_scene + 2));
-        HIP_TRY(h, pfc_sort_temp_bytes(n, 32, &bytes));
-        HIP_TRY(h, h->sdual_tmp.ensure(bytes ? bytes : 1));
-        keys = h->sdual_i.p; off = keys + n;
-        int *count = off + n_scene + 1;
-        unsigned *kin = reinterpret_cast<unsigned *>(count + 1), *kout = kin + n;
-        hipLaunchKernelGGL(k_scat_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n_items, n_scene, d_scene, keys, count);
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, pfc_sort_indices(keys, count, n, kin, kout, h->sdual_tmp.p, h->sdual_tmp.cap, st));
-        hipLaunchKernelGGL(k_scat_off, dim3((unsigned)(((size_t)n_scene + 256) / 256)), dim3(256), 0, st, n_items, n_scene, keys, off);
-        HIP_TRY(h, hipGetLastError());
+    if (!h) return PFC_ERR_BAD_ARG;
+    // the wrenches of a multi-device evaluation end up on the first device: so does this
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        if (n_items < 0 || n_dir < 1 || n_dir > kScatMaxDir || nv <= 0 || n_scene <= 0 || !d_df)
+            return fail(c, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual_device: bad argument");
+        if ((long long)n_scene * n_items >= (1ll << 31))
+            return fail(c, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual_device: n_scene * n_items must be below 2^31");
+        if (n_items > 0 && (!d_wrench_val || !d_dwrench || !d_x_w_r2 || !d_body_1 || !d_body_2 || !d_jac))
+            return fail(c, PFC_ERR_BAD_ARG, "pfc_scatter_generalized_dual_device: null buffer");
+        hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+        int *keys, *off;
+        const int rc = scatter_dual_csr(c, n_items, d_scene, n_scene, st, &keys, &off);
+        if (rc != PFC_OK) return rc;
+        return scatter_dual_launch(c, n_items, n_dir, d_wrench_val, d_dwrench, d_x_w_r2, d_dx_w_r2, d_body_1, d_body_2, keys, off, n_scene,
+                                   nv, d_jac, d_djac, d_f, d_df, accumulate, st); });
+}
+
+// ---- the chains from joint states: kinematics, the items and their evaluation, the third-law scatter, dynamics and the solve -----
+// What the stages' own entries would check again has been checked by the chain (eval_state_check, eval_dual_state_check, the
+// state checks of the dynamics and the null-buffer lists): the stage launches are called directly, with the record's fields.
+static int eval_state(pfc_context *h, const StateCall &S) {
+    const char *who = "pfc_eval_state_device";
+    const StateBufs &V = S.val;
+    pfc_context *c = first_ctx(h);
+    int rc = on_shard(h, c, [&](pfc_context *c1) { return eval_state_check(c1, who, S.n_items, S.ins_ids, S.scene, S.n_scene, false, V.q, V.v); });
+    if (rc != PFC_OK) return rc;
+    const int nv = c->kin.nv;
+    const bool scatter = V.f && nv > 0;
+    if (!V.x_w_b || !V.twist_w_b || !V.pose || !V.twist || !V.wrench || !V.sdot || (scatter && (!V.jac || !V.x_w_r2 || !V.body_1 || !V.body_2)))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    rc = on_shard(h, c, [&](pfc_context *c1) { return kin_launch(c1, S.n_scene, V.q, V.v, V.x_w_b, V.twist_w_b, V.jac, call_stream(c1, S)); });
+    if (rc != PFC_OK || (rc = eval_bodies(h, S, c->kin.n_body)) != PFC_OK || !scatter) return rc;
+    return on_shard(h, c, [&](pfc_context *c1) {
+        return scatter_launch(c1, S.n_items, nv, V.wrench, V.x_w_r2, V.body_1, V.body_2, S.scene, S.n_scene, V.jac, V.f, 0, call_stream(c1, S)); });
+}
+
+static int state_derivative(pfc_context *h, const StateCall &S) {
+    const char *who = "pfc_state_derivative_device";
+    const StateBufs &V = S.val;
+    pfc_context *c = first_ctx(h);
+    int rc = on_shard(h, c, [&](pfc_context *c1) {
+        const int r = dyn_check_state(c1, who);
+        return r != PFC_OK ? r : accel_check_state(c1, who); });
+    if (rc != PFC_OK) return rc;
+    if (!V.f || !V.qdot || !V.H || !V.c || !V.vdot) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    if ((rc = eval_state(h, S)) != PFC_OK) return rc;
+    return on_shard(h, c, [&](pfc_context *c1) {
+        const hipStream_t st = call_stream(c1, S);
+        const int r = dyn_launch(c1, S.n_scene, V.q, V.v, V.x_w_b, V.twist_w_b, V.qdot, V.H, V.c, st);
+        return r != PFC_OK ? r : accel_launch(c1, S.n_scene, V.H, V.c, V.f, V.tau, V.vdot, V.info, st); });
+}
+
+// `more`: another chunk of directions at the point of the last checked first call -- only partials are written, the values are read.
+static int eval_dual_state(pfc_context *h, const StateCall &S, bool more) {
+    const char *who = more ? "pfc_eval_dual_state_device_more" : "pfc_eval_dual_state_device";
+    const StateBufs &V = S.val, &P = S.par;
+    pfc_context *c = first_ctx(h);
+    const int nv = c->kin.nv;
+    const bool scatter = P.f && nv > 0;
+    int rc = on_shard(h, c, [&](pfc_context *c1) {
+        return eval_dual_state_check(c1, who, S.n_items, S.n_dir, S.ins_ids, S.scene, S.n_scene, V.q, V.v, scatter); });
+    if (rc != PFC_OK) return rc;
+    if (more && !h->multi) {      // _more's own preconditions, before the partials are written
+        if (!h->device_kept())
+            return fail(h, PFC_ERR_STATE, "%s: no checked pfc_eval_dual_device evaluation on this handle to extend", who);
+        if (S.n_items != h->kept.n)
+            return fail(h, PFC_ERR_BAD_ARG, "%s: n_items is %d, the kept evaluation has %d items", who, S.n_items, h->kept.n);
     }
-    return scatter_dual_launch(h, n_items, n_dir, d_wrench_val, d_dwrench, d_x_w_r2, d_dx_w_r2, d_body_1, d_body_2, keys, off, n_scene,
-                               nv, d_jac, d_djac, d_f, d_df, accumulate, st);
+    if (!V.x_w_b || !V.twist_w_b || !P.x_w_b || !P.twist_w_b || !P.pose || !P.twist || !P.wrench || !P.sdot ||
+        (!more && (!V.pose || !V.twist || !V.wrench || !V.sdot)) ||
+        (scatter && (!V.jac || !P.jac || !V.x_w_r2 || !P.x_w_r2 || !V.body_1 || !V.body_2 || (more && !V.wrench))))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    rc = on_shard(h, c, [&](pfc_context *c1) {
+        const hipStream_t st = call_stream(c1, S);
+        const int r = more ? PFC_OK : kin_launch(c1, S.n_scene, V.q, V.v, V.x_w_b, V.twist_w_b, V.jac, st);
+        return r != PFC_OK ? r : kin_dual_launch(c1, S.n_scene, S.n_dir, V.q, V.v, P.q, P.v, P.x_w_b, P.twist_w_b, P.jac, st); });
+    if (rc != PFC_OK || (rc = eval_dual_bodies(h, S, c->kin.n_body, more)) != PFC_OK || !scatter) return rc;
+    return on_shard(h, c, [&](pfc_context *c1) {
+        const hipStream_t st = call_stream(c1, S);
+        int *keys, *off;
+        const int r = scatter_dual_csr(c1, S.n_items, S.scene, S.n_scene, st, &keys, &off);
+        if (r != PFC_OK) return r;
+        return scatter_dual_launch(c1, S.n_items, S.n_dir, V.wrench, P.wrench, V.x_w_r2, P.x_w_r2, V.body_1, V.body_2, keys, off, S.n_scene, nv,
+                                   V.jac, P.jac, more ? nullptr : V.f, P.f, 0, st); });
+}
+
+static int state_derivative_dual(pfc_context *h, const StateCall &S, bool more) {
+    const char *who = more ? "pfc_state_derivative_dual_device_more" : "pfc_state_derivative_dual_device";
+    const StateBufs &V = S.val, &P = S.par;
+    pfc_context *c = first_ctx(h);
+    int rc = on_shard(h, c, [&](pfc_context *c1) { return state_derivative_dual_check(c1, who, S.n_scene, S.n_dir); });
+    if (rc != PFC_OK) return rc;
+    if (!V.f || !P.f || !V.H || !V.c || !P.qdot || !P.H || !P.c || !P.vdot || (!more && (!V.qdot || !V.vdot)))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    if ((rc = eval_dual_state(h, S, more)) != PFC_OK) return rc;
+    return on_shard(h, c, [&](pfc_context *c1) {
+        const hipStream_t st = call_stream(c1, S);
+        int r = more ? PFC_OK : dyn_launch(c1, S.n_scene, V.q, V.v, V.x_w_b, V.twist_w_b, V.qdot, V.H, V.c, st);
+        if (r != PFC_OK) return r;
+        r = dyn_dual_launch(c1, S.n_scene, S.n_dir, V.q, V.v, P.q, P.v, V.x_w_b, V.twist_w_b, P.x_w_b, P.twist_w_b, P.qdot, P.H, P.c, st);
+        if (r != PFC_OK) return r;
+        return accel_dual_launch(c1, S.n_scene, S.n_dir, V.H, V.c, V.f, V.tau, P.H, P.c, P.f, P.tau, more ? nullptr : V.vdot, P.vdot,
+                                 more ? nullptr : V.info, st); });
+}
+
+// The six entries: one fill of the record each -- the only place a parameter position meets a field name -- and one call.
+int pfc_eval_state_device(pfc_handle h, int n_items, const int *d_ins_ids, const int *d_scene, int n_scene,
+                          const double *d_q, const double *d_v, const double *d_s,
+                          double *d_x_w_b, double *d_twist_w_b, double *d_jac,
+                          double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
+                          double *d_wrench, double *d_sdot, int *d_counts, double *d_f, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    StateCall S = state_call_head(n_items, 0, d_ins_ids, d_scene, n_scene, stream);
+    StateBufs &V = S.val;
+    V.q = d_q; V.v = d_v; V.s = d_s;
+    V.x_w_b = d_x_w_b; V.twist_w_b = d_twist_w_b; V.jac = d_jac;
+    V.pose = d_pose; V.twist = d_twist; V.x_w_r2 = d_x_w_r2; V.body_1 = d_body_1; V.body_2 = d_body_2;
+    V.wrench = d_wrench; V.sdot = d_sdot; V.counts = d_counts; V.f = d_f;
+    return eval_state(h, S);
+}
+
+int pfc_state_derivative_device(pfc_handle h, int n_items, const int *d_ins_ids, const int *d_scene, int n_scene,
+                                const double *d_q, const double *d_v, const double *d_s, const double *d_tau,
+                                double *d_x_w_b, double *d_twist_w_b, double *d_jac,
+                                double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
+                                double *d_wrench, double *d_sdot, int *d_counts, double *d_f,
+                                double *d_qdot, double *d_H, double *d_c, double *d_vdot, int *d_info, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    StateCall S = state_call_head(n_items, 0, d_ins_ids, d_scene, n_scene, stream);
+    StateBufs &V = S.val;
+    V.q = d_q; V.v = d_v; V.s = d_s; V.tau = d_tau;
+    V.x_w_b = d_x_w_b; V.twist_w_b = d_twist_w_b; V.jac = d_jac;
+    V.pose = d_pose; V.twist = d_twist; V.x_w_r2 = d_x_w_r2; V.body_1 = d_body_1; V.body_2 = d_body_2;
+    V.wrench = d_wrench; V.sdot = d_sdot; V.counts = d_counts; V.f = d_f;
+    V.qdot = d_qdot; V.H = d_H; V.c = d_c; V.vdot = d_vdot; V.info = d_info;
+    return state_derivative(h, S);
+}
+
+int pfc_eval_dual_state_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
+                               const double *d_q, const double *d_v, const double *d_dq, const double *d_dv,
+                               const double *d_s, const double *d_ds,
+                               double *d_x_w_b, double *d_twist_w_b, double *d_jac,
+                               double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac,
+                               double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
+                               double *d_dpose, double *d_dtwist, double *d_dx_w_r2,
+                               double *d_wrench, double *d_sdot, double *d_dwrench, double *d_dsdot, int *d_counts,
+                               double *d_f, double *d_df, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    StateCall S = state_call_head(n_items, n_dir, d_ins_ids, d_scene, n_scene, stream);
+    StateBufs &V = S.val, &P = S.par;
+    V.q = d_q; V.v = d_v; V.s = d_s; P.q = d_dq; P.v = d_dv; P.s = d_ds;
+    V.x_w_b = d_x_w_b; V.twist_w_b = d_twist_w_b; V.jac = d_jac; P.x_w_b = d_dx_w_b; P.twist_w_b = d_dtwist_w_b; P.jac = d_djac;
+    V.pose = d_pose; V.twist = d_twist; V.x_w_r2 = d_x_w_r2; V.body_1 = d_body_1; V.body_2 = d_body_2;
+    P.pose = d_dpose; P.twist = d_dtwist; P.x_w_r2 = d_dx_w_r2;
+    V.wrench = d_wrench; V.sdot = d_sdot; P.wrench = d_dwrench; P.sdot = d_dsdot; V.counts = d_counts; V.f = d_f; P.f = d_df;
+    return eval_dual_state(h, S, false);
+}
+
+int pfc_eval_dual_state_device_more(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
+                                    const double *d_q, const double *d_v, const double *d_dq, const double *d_dv, const double *d_ds,
+                                    const double *d_x_w_b, const double *d_twist_w_b, const double *d_jac,
+                                    double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac,
+                                    const double *d_x_w_r2, const int *d_body_1, const int *d_body_2, const double *d_wrench,
+                                    double *d_dpose, double *d_dtwist, double *d_dx_w_r2, double *d_dwrench, double *d_dsdot,
+                                    double *d_df, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    StateCall S = state_call_head(n_items, n_dir, d_ins_ids, d_scene, n_scene, stream);
+    StateBufs &V = S.val, &P = S.par;
+    V.q = d_q; V.v = d_v; P.q = d_dq; P.v = d_dv; P.s = d_ds;
+    V.x_w_b = kept_value(d_x_w_b); V.twist_w_b = kept_value(d_twist_w_b); V.jac = kept_value(d_jac);
+    P.x_w_b = d_dx_w_b; P.twist_w_b = d_dtwist_w_b; P.jac = d_djac;
+    V.x_w_r2 = kept_value(d_x_w_r2); V.body_1 = kept_value(d_body_1); V.body_2 = kept_value(d_body_2); V.wrench = kept_value(d_wrench);
+    P.pose = d_dpose; P.twist = d_dtwist; P.x_w_r2 = d_dx_w_r2; P.wrench = d_dwrench; P.sdot = d_dsdot; P.f = d_df;
+    return eval_dual_state(h, S, true);
+}
+
+int pfc_state_derivative_dual_device(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
+                                     const double *d_q, const double *d_v, const double *d_dq, const double *d_dv,
+                                     const double *d_s, const double *d_ds, const double *d_tau, const double *d_dtau,
+                                     double *d_x_w_b, double *d_twist_w_b, double *d_jac,
+                                     double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac,
+                                     double *d_pose, double *d_twist, double *d_x_w_r2, int *d_body_1, int *d_body_2,
+                                     double *d_dpose, double *d_dtwist, double *d_dx_w_r2,
+                                     double *d_wrench, double *d_sdot, double *d_dwrench, double *d_dsdot, int *d_counts,
+                                     double *d_f, double *d_df,
+                                     double *d_qdot, double *d_H, double *d_c, double *d_vdot, int *d_info,
+                                     double *d_dqdot, double *d_dH, double *d_dc, double *d_dvdot, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    StateCall S = state_call_head(n_items, n_dir, d_ins_ids, d_scene, n_scene, stream);
+    StateBufs &V = S.val, &P = S.par;
+    V.q = d_q; V.v = d_v; V.s = d_s; V.tau = d_tau; P.q = d_dq; P.v = d_dv; P.s = d_ds; P.tau = d_dtau;
+    V.x_w_b = d_x_w_b; V.twist_w_b = d_twist_w_b; V.jac = d_jac; P.x_w_b = d_dx_w_b; P.twist_w_b = d_dtwist_w_b; P.jac = d_djac;
+    V.pose = d_pose; V.twist = d_twist; V.x_w_r2 = d_x_w_r2; V.body_1 = d_body_1; V.body_2 = d_body_2;
+    P.pose = d_dpose; P.twist = d_dtwist; P.x_w_r2 = d_dx_w_r2;
+    V.wrench = d_wrench; V.sdot = d_sdot; P.wrench = d_dwrench; P.sdot = d_dsdot; V.counts = d_counts; V.f = d_f; P.f = d_df;
+    V.qdot = d_qdot; V.H = d_H; V.c = d_c; V.vdot = d_vdot; V.info = d_info; P.qdot = d_dqdot; P.H = d_dH; P.c = d_dc; P.vdot = d_dvdot;
+    return state_derivative_dual(h, S, false);
+}
+
+int pfc_state_derivative_dual_device_more(pfc_handle h, int n_items, int n_dir, const int *d_ins_ids, const int *d_scene, int n_scene,
+                                          const double *d_q, const double *d_v, const double *d_dq, const double *d_dv, const double *d_ds,
+                                          const double *d_tau, const double *d_dtau,
+                                          const double *d_x_w_b, const double *d_twist_w_b, const double *d_jac,
+                                          double *d_dx_w_b, double *d_dtwist_w_b, double *d_djac,
+                                          const double *d_x_w_r2, const int *d_body_1, const int *d_body_2, const double *d_wrench,
+                                          double *d_dpose, double *d_dtwist, double *d_dx_w_r2, double *d_dwrench, double *d_dsdot,
+                                          double *d_df, const double *d_H, const double *d_c, const double *d_f,
+                                          double *d_dqdot, double *d_dH, double *d_dc, double *d_dvdot, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    StateCall S = state_call_head(n_items, n_dir, d_ins_ids, d_scene, n_scene, stream);
+    StateBufs &V = S.val, &P = S.par;
+    V.q = d_q; V.v = d_v; V.tau = d_tau; P.q = d_dq; P.v = d_dv; P.s = d_ds; P.tau = d_dtau;
+    V.x_w_b = kept_value(d_x_w_b); V.twist_w_b = kept_value(d_twist_w_b); V.jac = kept_value(d_jac);
+    P.x_w_b = d_dx_w_b; P.twist_w_b = d_dtwist_w_b; P.jac = d_djac;
+    V.x_w_r2 = kept_value(d_x_w_r2); V.body_1 = kept_value(d_body_1); V.body_2 = kept_value(d_body_2); V.wrench = kept_value(d_wrench);
+    P.pose = d_dpose; P.twist = d_dtwist; P.x_w_r2 = d_dx_w_r2; P.wrench = d_dwrench; P.sdot = d_dsdot; P.f = d_df;
+    V.H = kept_value(d_H); V.c = kept_value(d_c); V.f = kept_value(d_f); P.qdot = d_dqdot; P.H = d_dH; P.c = d_dc; P.vdot = d_dvdot;
+    return state_derivative_dual(h, S, true);
 }
 
 int pfc_debug_stamps(pfc_handle h, long long *out16) {
@@ -4827,11 +4906,8 @@ static int radau_check_nx(pfc_context *h, const char *who, int n_scene, int nx) 
     return PFC_OK;
 }
 
-static int radau_factor_launch(pfc_context *h, int n_scene, int nx, const double *d_neg_J, const double *d_h, const int *d_rule,
-                               const int *d_active, int active_stride, double *d_lu0, double *d_lu1, int *d_perm, int *d_info,
-                               hipStream_t st);
-static pfc_context *radau_ctx(pfc_context *h);
-
+// Every part is a launcher over a validated layout -- what the step's driver calls with the handle's own -- and a public entry that
+// runs on the first shard, validates (radau_layout, radau_chunk), refuses null buffers and calls the launcher.
 // The state layout every part but the factorisation takes, validated: NX = nq + nv + 6 n_br, the bristle items increasing and < n_ips.
 static int radau_layout(pfc_context *h, const char *who, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items,
                         RadauLayout *L) {
@@ -4861,21 +4937,42 @@ static int radau_chunk(pfc_context *h, const char *who, int nx, int chunk, int n
     return PFC_OK;
 }
 
+// Chunk directions [j0, j0 + n_dir) as unit seeds of q, v and s.
+static int radau_seed_launch(pfc_context *h, const RadauLayout &L, int j0, int n_dir, double *d_dq, double *d_dv, double *d_ds,
+                             hipStream_t st) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    RadauSeedArgs a;
+    a.L = L; a.j0 = j0; a.n_dir = n_dir; a.dq = d_dq; a.dv = d_dv; a.ds = d_ds;
+    const size_t total = (size_t)L.n_scene * n_dir * (size_t)(L.nq + L.nv + 6 * L.n_ips);
+    hipLaunchKernelGGL(k_radau_seed, dim3(radau_grid(total)), dim3(kRadBlock), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
 int pfc_radau_seed_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int chunk,
                           int n_chunk, double *d_dq, double *d_dv, double *d_ds, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_radau_seed_device(c, n_scene, nx, nq, nv, n_ips, n_br, br_items, chunk, n_chunk, d_dq, d_dv, d_ds, stream); });
-    const char *who = "pfc_radau_seed_device";
-    RadauSeedArgs a;
-    int rc = radau_layout(h, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &a.L);
-    if (rc != PFC_OK || (rc = radau_chunk(h, who, nx, chunk, n_chunk, &a.j0, &a.n_dir)) != PFC_OK || n_scene == 0) return rc;
-    if ((nq > 0 && !d_dq) || (nv > 0 && !d_dv) || (n_ips > 0 && !d_ds)) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        const char *who = "pfc_radau_seed_device";
+        RadauLayout L;
+        int j0, n_dir;
+        int rc = radau_layout(c, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &L);
+        if (rc != PFC_OK || (rc = radau_chunk(c, who, nx, chunk, n_chunk, &j0, &n_dir)) != PFC_OK || n_scene == 0) return rc;
+        if ((nq > 0 && !d_dq) || (nv > 0 && !d_dv) || (n_ips > 0 && !d_ds)) return fail(c, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+        return radau_seed_launch(c, L, j0, n_dir, d_dq, d_dv, d_ds, stream ? (hipStream_t)stream : c->stream); });
+}
+
+// Columns [j0, j0 + n_dir) of -J from the chunk's partials; `first` (the chunk at j0 = 0) also takes xdot0 from the values.
+static int radau_jacobian_launch(pfc_context *h, const RadauLayout &L, int j0, int n_dir, const double *d_dqdot, const double *d_dvdot,
+                                 const double *d_dsdot, const double *d_qdot, const double *d_vdot, const double *d_sdot, double *d_neg_J,
+                                 double *d_xdot0, double *d_nstate, int *d_istate, hipStream_t st) {
     HIP_TRY(h, hipSetDevice(h->device));
-    a.dq = d_dq; a.dv = d_dv; a.ds = d_ds;
-    const size_t total = (size_t)n_scene * a.n_dir * (size_t)(nq + nv + 6 * n_ips);
-    hipLaunchKernelGGL(k_radau_seed, dim3(radau_grid(total)), dim3(kRadBlock), 0, stream ? (hipStream_t)stream : h->stream, a);
+    RadauJacArgs a;
+    a.L = L; a.j0 = j0; a.n_dir = n_dir; a.first = j0 == 0;
+    a.dqdot = d_dqdot; a.dvdot = d_dvdot; a.dsdot = d_dsdot; a.qdot = d_qdot; a.vdot = d_vdot; a.sdot = d_sdot;
+    a.neg_J = d_neg_J; a.xdot0 = d_xdot0; a.nstate = d_nstate; a.istate = d_istate;
+    const size_t total = (size_t)L.n_scene * (size_t)(n_dir + a.first) * (size_t)L.nx;
+    hipLaunchKernelGGL(k_radau_jac, dim3(radau_grid(total)), dim3(kRadBlock), 0, st, a);
     HIP_TRY(h, hipGetLastError());
     return PFC_OK;
 }
@@ -4885,23 +4982,27 @@ int pfc_radau_jacobian_device(pfc_handle h, int n_scene, int nx, int nq, int nv,
                               const double *d_vdot, const double *d_sdot, double *d_neg_J, double *d_xdot0, double *d_nstate,
                               int *d_istate, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_radau_jacobian_device(c, n_scene, nx, nq, nv, n_ips, n_br, br_items, chunk, n_chunk, d_dqdot, d_dvdot, d_dsdot, d_qdot,
-                                             d_vdot, d_sdot, d_neg_J, d_xdot0, d_nstate, d_istate, stream); });
-    const char *who = "pfc_radau_jacobian_device";
-    RadauJacArgs a;
-    int rc = radau_layout(h, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &a.L);
-    if (rc != PFC_OK || (rc = radau_chunk(h, who, nx, chunk, n_chunk, &a.j0, &a.n_dir)) != PFC_OK || n_scene == 0) return rc;
-    a.first = chunk == 0;
-    if ((nq > 0 && !d_dqdot) || (nv > 0 && !d_dvdot) || (n_br > 0 && !d_dsdot) || !d_neg_J ||
-        (a.first && ((nq > 0 && !d_qdot) || (nv > 0 && !d_vdot) || (n_br > 0 && !d_sdot) || !d_xdot0)))
-        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        const char *who = "pfc_radau_jacobian_device";
+        RadauLayout L;
+        int j0, n_dir;
+        int rc = radau_layout(c, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &L);
+        if (rc != PFC_OK || (rc = radau_chunk(c, who, nx, chunk, n_chunk, &j0, &n_dir)) != PFC_OK || n_scene == 0) return rc;
+        if ((nq > 0 && !d_dqdot) || (nv > 0 && !d_dvdot) || (n_br > 0 && !d_dsdot) || !d_neg_J ||
+            (chunk == 0 && ((nq > 0 && !d_qdot) || (nv > 0 && !d_vdot) || (n_br > 0 && !d_sdot) || !d_xdot0)))
+            return fail(c, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+        return radau_jacobian_launch(c, L, j0, n_dir, d_dqdot, d_dvdot, d_dsdot, d_qdot, d_vdot, d_sdot, d_neg_J, d_xdot0, d_nstate, d_istate,
+                                     stream ? (hipStream_t)stream : c->stream); });
+}
+
+// The stage states into the q, v and s of the 3 n_scene stage-scenes (k_radau_unpack).
+static int radau_unpack_launch(pfc_context *h, const RadauLayout &L, const double *d_x0, const int *d_rule, const int *d_istate, double *d_X,
+                               double *d_q, double *d_v, double *d_s, hipStream_t st) {
     HIP_TRY(h, hipSetDevice(h->device));
-    a.dqdot = d_dqdot; a.dvdot = d_dvdot; a.dsdot = d_dsdot; a.qdot = d_qdot; a.vdot = d_vdot; a.sdot = d_sdot;
-    a.neg_J = d_neg_J; a.xdot0 = d_xdot0; a.nstate = d_nstate; a.istate = d_istate;
-    const size_t total = (size_t)n_scene * (size_t)(a.n_dir + a.first) * (size_t)nx;
-    hipLaunchKernelGGL(k_radau_jac, dim3(radau_grid(total)), dim3(kRadBlock), 0, stream ? (hipStream_t)stream : h->stream, a);
+    RadauUnpackArgs a;
+    a.L = L; a.x0 = d_x0; a.rule = d_rule; a.istate = d_istate; a.X = d_X; a.q = d_q; a.v = d_v; a.s = d_s;
+    const size_t total = 3 * (size_t)L.n_scene * (size_t)(L.nq + L.nv + 6 * L.n_ips);
+    hipLaunchKernelGGL(k_radau_unpack, dim3(radau_grid(total)), dim3(kRadBlock), 0, st, a);
     HIP_TRY(h, hipGetLastError());
     return PFC_OK;
 }
@@ -4910,21 +5011,14 @@ int pfc_radau_unpack_device(pfc_handle h, int n_scene, int nx, int nq, int nv, i
                             const double *d_x0, const int *d_rule, const int *d_istate, double *d_X, double *d_q, double *d_v, double *d_s,
                             void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_radau_unpack_device(c, n_scene, nx, nq, nv, n_ips, n_br, br_items, d_x0, d_rule, d_istate, d_X, d_q, d_v, d_s, stream); });
-    const char *who = "pfc_radau_unpack_device";
-    RadauUnpackArgs a;
-    const int rc = radau_layout(h, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &a.L);
-    if (rc != PFC_OK || n_scene == 0) return rc;
-    if (!d_x0 || !d_rule || !d_istate || !d_X || (nq > 0 && !d_q) || (nv > 0 && !d_v) || (n_ips > 0 && !d_s))
-        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-    HIP_TRY(h, hipSetDevice(h->device));
-    a.x0 = d_x0; a.rule = d_rule; a.istate = d_istate; a.X = d_X; a.q = d_q; a.v = d_v; a.s = d_s;
-    const size_t total = 3 * (size_t)n_scene * (size_t)(nq + nv + 6 * n_ips);
-    hipLaunchKernelGGL(k_radau_unpack, dim3(radau_grid(total)), dim3(kRadBlock), 0, stream ? (hipStream_t)stream : h->stream, a);
-    HIP_TRY(h, hipGetLastError());
-    return PFC_OK;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        const char *who = "pfc_radau_unpack_device";
+        RadauLayout L;
+        const int rc = radau_layout(c, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &L);
+        if (rc != PFC_OK || n_scene == 0) return rc;
+        if (!d_x0 || !d_rule || !d_istate || !d_X || (nq > 0 && !d_q) || (nv > 0 && !d_v) || (n_ips > 0 && !d_s))
+            return fail(c, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+        return radau_unpack_launch(c, L, d_x0, d_rule, d_istate, d_X, d_q, d_v, d_s, stream ? (hipStream_t)stream : c->stream); });
 }
 
 // What k_radau_finish<true> takes beyond k_radau_finish<false>'s arguments (pfc_radau_finish_end_device).
@@ -4936,35 +5030,25 @@ struct RadauEndBufs {
     int *live;
 };
 
+// What the finish parts take beside the layout and the buffers: the MRP offsets in q, {tol_a, tol_r, h_max, h_min} and the rule's bounds.
+struct RadauFinishRule {
+    int n_mrp;
+    const int *mrp_off;
+    const double *params;
+    int k_iter_max, max_rule, cooldown;
+};
+
 // Both finish parts: `end` null launches k_radau_finish<false>, else <true> with those buffers.
-static int radau_finish_launch(pfc_context *h, const char *who, const RadauEndBufs *end, int n_scene, int nx, int nq, int nv, int n_ips,
-                               int n_br, const int *br_items, int n_mrp, const int *mrp_off, const double *params, int k_iter_max,
-                               int max_rule, int cooldown, const double *d_F, const double *d_xdot0, const double *d_X,
-                               const double *d_lu0, const int *d_perm, double *d_x, double *d_t, double *d_h, int *d_rule, int *d_cool,
-                               double *d_enorm, double *d_nstate, int *d_istate, int *d_count, void *stream) {
-    RadauFinishArgs a;
-    const int rc = radau_layout(h, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &a.L);
-    if (rc != PFC_OK) return rc;
-    if (n_mrp < 0 || n_mrp > kRadMaxBr || (n_mrp > 0 && !mrp_off)) return fail(h, PFC_ERR_BAD_ARG, "%s: the list of MRP offsets", who);
-    for (int m = 0; m < n_mrp; ++m)
-        if (mrp_off[m] < 0 || mrp_off[m] + 3 > nq || (m > 0 && mrp_off[m] < mrp_off[m - 1] + 3))
-            return fail(h, PFC_ERR_BAD_ARG, "%s: MRP %d at q offset %d: increasing, disjoint and within nq = %d", who, m, mrp_off[m], nq);
-    if (!params || !(params[0] >= 0.0) || !(params[1] >= 0.0) || !(params[2] > 0.0) || !(params[3] > 0.0))
-        return fail(h, PFC_ERR_BAD_ARG, "%s: params are {tol_a >= 0, tol_r >= 0, h_max > 0, h_min > 0}", who);
-    if (k_iter_max < 1 || max_rule < 1 || max_rule > 2 || cooldown < 0)
-        return fail(h, PFC_ERR_BAD_ARG, "%s: k_iter_max >= 1, max_rule 1 or 2 (rules 3 - 6 are not built), cooldown >= 0", who);
-    if (end && (end->max_rows < 0 || end->max_rows == 1))
-        return fail(h, PFC_ERR_BAD_ARG, "%s: max_rows is %d: 0 (no recording) or at least 2", who, end->max_rows);
-    if (n_scene == 0) return PFC_OK;
-    if (!d_F || !d_xdot0 || !d_X || !d_lu0 || !d_perm || !d_x || !d_t || !d_h ||
-        !d_rule || !d_cool || !d_enorm || !d_nstate || !d_istate || !d_count ||
-        (end && (!end->live || (end->max_rows > 0 && (!end->traj || !end->rows)))))
-        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+static int radau_finish_launch(pfc_context *h, const RadauLayout &L, const RadauFinishRule &r, const RadauEndBufs *end, const double *d_F,
+                               const double *d_xdot0, const double *d_X, const double *d_lu0, const int *d_perm, double *d_x, double *d_t,
+                               double *d_h, int *d_rule, int *d_cool, double *d_enorm, double *d_nstate, int *d_istate, int *d_count,
+                               hipStream_t st) {
     HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    a.k_iter_max = k_iter_max; a.max_rule = max_rule; a.cooldown_reset = cooldown; a.n_mrp = n_mrp;
-    for (int m = 0; m < kRadMaxBr; ++m) a.mrp_off[m] = m < n_mrp ? mrp_off[m] : 0;
-    a.tol_a = params[0]; a.tol_r = params[1]; a.h_max = params[2]; a.h_min = params[3];
+    RadauFinishArgs a;
+    a.L = L;
+    a.k_iter_max = r.k_iter_max; a.max_rule = r.max_rule; a.cooldown_reset = r.cooldown; a.n_mrp = r.n_mrp;
+    for (int m = 0; m < kRadMaxBr; ++m) a.mrp_off[m] = m < r.n_mrp ? r.mrp_off[m] : 0;
+    a.tol_a = r.params[0]; a.tol_r = r.params[1]; a.h_max = r.params[2]; a.h_min = r.params[3];
     for (int r = 0; r < 2; ++r) {
         const RadauTableHost &t = kRadauTables[r];
         a.bhat0[r] = t.bhat0;
@@ -4976,10 +5060,37 @@ static int radau_finish_launch(pfc_context *h, const char *who, const RadauEndBu
     a.t_final = end ? end->t_final : nullptr; a.traj = end ? end->traj : nullptr; a.rows = end ? end->rows : nullptr;
     a.max_rows = end ? end->max_rows : 0; a.live = end ? end->live : nullptr;
     HIP_TRY(h, hipMemsetAsync(d_count, 0, sizeof(int), st));
-    if (end) hipLaunchKernelGGL(k_radau_finish<true>, dim3((unsigned)n_scene), dim3(kRadWave), 0, st, a);
-    else hipLaunchKernelGGL(k_radau_finish<false>, dim3((unsigned)n_scene), dim3(kRadWave), 0, st, a);
+    if (end) hipLaunchKernelGGL(k_radau_finish<true>, dim3((unsigned)L.n_scene), dim3(kRadWave), 0, st, a);
+    else hipLaunchKernelGGL(k_radau_finish<false>, dim3((unsigned)L.n_scene), dim3(kRadWave), 0, st, a);
     HIP_TRY(h, hipGetLastError());
     return PFC_OK;
+}
+
+// Both finish entries behind the forwarder: the layout, the rule's parameters and the buffers checked, then the launcher.
+static int radau_finish_checked(pfc_context *h, const char *who, const RadauEndBufs *end, int n_scene, int nx, int nq, int nv, int n_ips,
+                                int n_br, const int *br_items, const RadauFinishRule &r, const double *d_F, const double *d_xdot0,
+                                const double *d_X, const double *d_lu0, const int *d_perm, double *d_x, double *d_t, double *d_h,
+                                int *d_rule, int *d_cool, double *d_enorm, double *d_nstate, int *d_istate, int *d_count, void *stream) {
+    RadauLayout L;
+    const int rc = radau_layout(h, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &L);
+    if (rc != PFC_OK) return rc;
+    if (r.n_mrp < 0 || r.n_mrp > kRadMaxBr || (r.n_mrp > 0 && !r.mrp_off)) return fail(h, PFC_ERR_BAD_ARG, "%s: the list of MRP offsets", who);
+    for (int m = 0; m < r.n_mrp; ++m)
+        if (r.mrp_off[m] < 0 || r.mrp_off[m] + 3 > nq || (m > 0 && r.mrp_off[m] < r.mrp_off[m - 1] + 3))
+            return fail(h, PFC_ERR_BAD_ARG, "%s: MRP %d at q offset %d: increasing, disjoint and within nq = %d", who, m, r.mrp_off[m], nq);
+    if (!r.params || !(r.params[0] >= 0.0) || !(r.params[1] >= 0.0) || !(r.params[2] > 0.0) || !(r.params[3] > 0.0))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: params are {tol_a >= 0, tol_r >= 0, h_max > 0, h_min > 0}", who);
+    if (r.k_iter_max < 1 || r.max_rule < 1 || r.max_rule > 2 || r.cooldown < 0)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: k_iter_max >= 1, max_rule 1 or 2 (rules 3 - 6 are not built), cooldown >= 0", who);
+    if (end && (end->max_rows < 0 || end->max_rows == 1))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: max_rows is %d: 0 (no recording) or at least 2", who, end->max_rows);
+    if (n_scene == 0) return PFC_OK;
+    if (!d_F || !d_xdot0 || !d_X || !d_lu0 || !d_perm || !d_x || !d_t || !d_h ||
+        !d_rule || !d_cool || !d_enorm || !d_nstate || !d_istate || !d_count ||
+        (end && (!end->live || (end->max_rows > 0 && (!end->traj || !end->rows)))))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    return radau_finish_launch(h, L, r, end, d_F, d_xdot0, d_X, d_lu0, d_perm, d_x, d_t, d_h, d_rule, d_cool, d_enorm, d_nstate, d_istate,
+                               d_count, stream ? (hipStream_t)stream : h->stream);
 }
 
 int pfc_radau_finish_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int n_mrp,
@@ -4988,10 +5099,10 @@ int pfc_radau_finish_device(pfc_handle h, int n_scene, int nx, int nq, int nv, i
                             const double *d_lu0, const int *d_perm, double *d_x, double *d_t, double *d_h, int *d_rule, int *d_cool,
                             double *d_enorm, double *d_nstate, int *d_istate, int *d_count, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
-        return radau_finish_launch(c, "pfc_radau_finish_device", nullptr, n_scene, nx, nq, nv, n_ips, n_br, br_items, n_mrp, mrp_off, params,
-                                   k_iter_max, max_rule, cooldown, d_F, d_xdot0, d_X, d_lu0, d_perm, d_x, d_t, d_h, d_rule, d_cool, d_enorm,
-                                   d_nstate, d_istate, d_count, stream); });
+    const RadauFinishRule r{n_mrp, mrp_off, params, k_iter_max, max_rule, cooldown};
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        return radau_finish_checked(c, "pfc_radau_finish_device", nullptr, n_scene, nx, nq, nv, n_ips, n_br, br_items, r, d_F, d_xdot0, d_X,
+                                    d_lu0, d_perm, d_x, d_t, d_h, d_rule, d_cool, d_enorm, d_nstate, d_istate, d_count, stream); });
 }
 
 int pfc_radau_finish_end_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int n_mrp,
@@ -5002,24 +5113,10 @@ int pfc_radau_finish_end_device(pfc_handle h, int n_scene, int nx, int nq, int n
                                 int *d_rows, int max_rows, int *d_live, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
     const RadauEndBufs end{d_t_final, d_traj, d_rows, max_rows, d_live};
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
-        return radau_finish_launch(c, "pfc_radau_finish_end_device", &end, n_scene, nx, nq, nv, n_ips, n_br, br_items, n_mrp, mrp_off, params,
-                                   k_iter_max, max_rule, cooldown, d_F, d_xdot0, d_X, d_lu0, d_perm, d_x, d_t, d_h, d_rule, d_cool, d_enorm,
-                                   d_nstate, d_istate, d_count, stream); });
-}
-
-int pfc_radau_factor_device(pfc_handle h, int n_scene, int nx, const double *d_neg_J, const double *d_h, const int *d_rule,
-                            const int *d_active, double *d_lu0, double *d_lu1, int *d_perm, int *d_info, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_radau_factor_device(c, n_scene, nx, d_neg_J, d_h, d_rule, d_active, d_lu0, d_lu1, d_perm, d_info, stream); });
-    const char *who = "pfc_radau_factor_device";
-    const int rc = radau_check_nx(h, who, n_scene, nx);
-    if (rc != PFC_OK || n_scene == 0) return rc;
-    if (!d_neg_J || !d_h || !d_rule || !d_lu0 || !d_lu1 || !d_perm || !d_info) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-    return radau_factor_launch(h, n_scene, nx, d_neg_J, d_h, d_rule, d_active, 1, d_lu0, d_lu1, d_perm, d_info,
-                               stream ? (hipStream_t)stream : h->stream);
+    const RadauFinishRule r{n_mrp, mrp_off, params, k_iter_max, max_rule, cooldown};
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        return radau_finish_checked(c, "pfc_radau_finish_end_device", &end, n_scene, nx, nq, nv, n_ips, n_br, br_items, r, d_F, d_xdot0, d_X,
+                                    d_lu0, d_perm, d_x, d_t, d_h, d_rule, d_cool, d_enorm, d_nstate, d_istate, d_count, stream); });
 }
 
 static int radau_factor_launch(pfc_context *h, int n_scene, int nx, const double *d_neg_J, const double *d_h, const int *d_rule,
@@ -5037,27 +5134,26 @@ static int radau_factor_launch(pfc_context *h, int n_scene, int nx, const double
     return PFC_OK;
 }
 
-int pfc_radau_newton_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items,
-                            const double *d_qdot, const double *d_vdot, const double *d_sdot, const double *d_x0, const double *d_h,
-                            const int *d_rule, const double *d_lu0, const double *d_lu1, const int *d_perm, const int *d_info,
-                            double tol_newton, int k_iter_max, double *d_X, double *d_F_save, double *d_nstate, int *d_istate, int *d_count,
-                            void *stream) {
+int pfc_radau_factor_device(pfc_handle h, int n_scene, int nx, const double *d_neg_J, const double *d_h, const int *d_rule,
+                            const int *d_active, double *d_lu0, double *d_lu1, int *d_perm, int *d_info, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    if (h->multi)
-        return on_first_shard(h, [&](pfc_context *c) {
-            return pfc_radau_newton_device(c, n_scene, nx, nq, nv, n_ips, n_br, br_items, d_qdot, d_vdot, d_sdot, d_x0, d_h, d_rule, d_lu0,
-                                           d_lu1, d_perm, d_info, tol_newton, k_iter_max, d_X, d_F_save, d_nstate, d_istate, d_count, stream); });
-    const char *who = "pfc_radau_newton_device";
-    RadauNewtonArgs a;
-    const int rc = radau_layout(h, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &a.L);
-    if (rc != PFC_OK) return rc;
-    if (!(tol_newton >= 0.0) || k_iter_max < 1) return fail(h, PFC_ERR_BAD_ARG, "%s: tol_newton or k_iter_max", who);
-    if (n_scene == 0) return PFC_OK;
-    if ((nq > 0 && !d_qdot) || (nv > 0 && !d_vdot) || (n_br > 0 && !d_sdot) || !d_x0 || !d_h || !d_rule || !d_lu0 || !d_lu1 || !d_perm ||
-        !d_info || !d_X || !d_nstate || !d_istate || !d_count)
-        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        const char *who = "pfc_radau_factor_device";
+        const int rc = radau_check_nx(c, who, n_scene, nx);
+        if (rc != PFC_OK || n_scene == 0) return rc;
+        if (!d_neg_J || !d_h || !d_rule || !d_lu0 || !d_lu1 || !d_perm || !d_info) return fail(c, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+        return radau_factor_launch(c, n_scene, nx, d_neg_J, d_h, d_rule, d_active, 1, d_lu0, d_lu1, d_perm, d_info,
+                                   stream ? (hipStream_t)stream : c->stream); });
+}
+
+// One pass of simple_newton! over the scenes that iterate; *d_count receives how many still do.
+static int radau_newton_launch(pfc_context *h, const RadauLayout &L, const double *d_qdot, const double *d_vdot, const double *d_sdot,
+                               const double *d_x0, const double *d_h, const int *d_rule, const double *d_lu0, const double *d_lu1,
+                               const int *d_perm, const int *d_info, double tol_newton, int k_iter_max, double *d_X, double *d_F_save,
+                               double *d_nstate, int *d_istate, int *d_count, hipStream_t st) {
     HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    RadauNewtonArgs a;
+    a.L = L;
     a.k_iter_max = k_iter_max;
     a.tol_newton = tol_newton;
     a.qdot = d_qdot; a.vdot = d_vdot; a.sdot = d_sdot; a.x0 = d_x0; a.h = d_h; a.rule = d_rule;
@@ -5065,9 +5161,29 @@ int pfc_radau_newton_device(pfc_handle h, int n_scene, int nx, int nq, int nv, i
     a.tab[0] = radau_tab(1); a.tab[1] = radau_tab(2);
     a.X = d_X; a.F_save = d_F_save; a.nstate = d_nstate; a.istate = d_istate; a.count = d_count;
     HIP_TRY(h, hipMemsetAsync(d_count, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_radau_newton, dim3((unsigned)n_scene), dim3(kRadWave), 0, st, a);
+    hipLaunchKernelGGL(k_radau_newton, dim3((unsigned)L.n_scene), dim3(kRadWave), 0, st, a);
     HIP_TRY(h, hipGetLastError());
     return PFC_OK;
+}
+
+int pfc_radau_newton_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items,
+                            const double *d_qdot, const double *d_vdot, const double *d_sdot, const double *d_x0, const double *d_h,
+                            const int *d_rule, const double *d_lu0, const double *d_lu1, const int *d_perm, const int *d_info,
+                            double tol_newton, int k_iter_max, double *d_X, double *d_F_save, double *d_nstate, int *d_istate, int *d_count,
+                            void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
+        const char *who = "pfc_radau_newton_device";
+        RadauLayout L;
+        const int rc = radau_layout(c, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &L);
+        if (rc != PFC_OK) return rc;
+        if (!(tol_newton >= 0.0) || k_iter_max < 1) return fail(c, PFC_ERR_BAD_ARG, "%s: tol_newton or k_iter_max", who);
+        if (n_scene == 0) return PFC_OK;
+        if ((nq > 0 && !d_qdot) || (nv > 0 && !d_vdot) || (n_br > 0 && !d_sdot) || !d_x0 || !d_h || !d_rule || !d_lu0 || !d_lu1 || !d_perm ||
+            !d_info || !d_X || !d_nstate || !d_istate || !d_count)
+            return fail(c, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+        return radau_newton_launch(c, L, d_qdot, d_vdot, d_sdot, d_x0, d_h, d_rule, d_lu0, d_lu1, d_perm, d_info, tol_newton, k_iter_max, d_X,
+                                   d_F_save, d_nstate, d_istate, d_count, stream ? (hipStream_t)stream : c->stream); });
 }
 
 // ---- the Radau IIA step: configuration, state and the driver (solveRadau, src/radau/radau_solve.jl:2-30) -----------------------
@@ -5160,13 +5276,10 @@ static int radau_configure_ctx(pfc_context *c, int n_scene, int n_ips, const int
     return PFC_OK;
 }
 
-// The context the step runs on: the handle, or the first shard of a multi-device handle.
-static pfc_context *radau_ctx(pfc_context *h) { return h->multi ? h->multi->shard[0] : h; }
-
 int pfc_radau_configure(pfc_handle h, int n_scene, int n_ips, const int *ins_ids, const double *params, int k_iter_max, int max_rule,
                         int n_chunk, int cooldown) {
     if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
         return radau_configure_ctx(c, n_scene, n_ips, ins_ids, params, k_iter_max, max_rule, n_chunk, cooldown); });
 }
 
@@ -5178,7 +5291,7 @@ static int radau_need(pfc_context *c, const char *who, bool state) {
 
 int pfc_radau_sizes(pfc_handle h, int *nx, int *n_bristle, int *bristle_items) {
     if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
         const int rc = radau_need(c, "pfc_radau_sizes", false);
         if (rc != PFC_OK) return rc;
         const RadauLayout &L = c->radau.L;
@@ -5190,7 +5303,7 @@ int pfc_radau_sizes(pfc_handle h, int *nx, int *n_bristle, int *bristle_items) {
 
 int pfc_radau_set_state(pfc_handle h, const double *x, const double *t) {
     if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
         const char *who = "pfc_radau_set_state";
         int rc = radau_need(c, who, false);
         if (rc != PFC_OK) return rc;
@@ -5232,7 +5345,7 @@ int pfc_radau_set_state(pfc_handle h, const double *x, const double *t) {
 
 int pfc_radau_set_rule_state(pfc_handle h, const double *h_scene, const int *rule, const int *cooldown) {
     if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
         const char *who = "pfc_radau_set_rule_state";
         const int rc = radau_need(c, who, true);
         if (rc != PFC_OK) return rc;
@@ -5253,7 +5366,7 @@ int pfc_radau_set_rule_state(pfc_handle h, const double *h_scene, const int *rul
 
 int pfc_radau_get_state(pfc_handle h, double *x, double *t) {
     if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
         const int rc = radau_need(c, "pfc_radau_get_state", true);
         if (rc != PFC_OK) return rc;
         pfc_context::RadauHost &R = c->radau;
@@ -5267,7 +5380,7 @@ int pfc_radau_get_state(pfc_handle h, double *x, double *t) {
 
 int pfc_radau_set_tau(pfc_handle h, const double *tau) {
     if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
         const int rc = radau_need(c, "pfc_radau_set_tau", false);
         if (rc != PFC_OK) return rc;
         pfc_context::RadauHost &R = c->radau;
@@ -5290,7 +5403,7 @@ int pfc_radau_set_tau(pfc_handle h, const double *tau) {
 
 int pfc_radau_rule_state(pfc_handle h, double *out7) {
     if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
         const int rc = radau_need(c, "pfc_radau_rule_state", true);
         if (rc != PFC_OK) return rc;
         if (!out7) return fail(c, PFC_ERR_BAD_ARG, "pfc_radau_rule_state: null buffer");
@@ -5346,7 +5459,7 @@ int pfc_radau_control_device(pfc_handle h, int n_scene, int nq, int nv, int n_ac
                              const double *d_seg_ff, const double *d_t, const double *d_q, const double *d_v, const double *d_H,
                              const double *d_c, const int *d_istate, double *d_t_last, int *d_fires, double *d_tau, void *stream) {
     if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
         return radau_control_launch(c, "pfc_radau_control_device", n_scene, nq, nv, n_act, n_seg, dt, d_act, d_kp, d_kd, d_a_max, d_seg_t,
                                     d_seg_q, d_seg_ff, d_t, d_q, d_v, d_H, d_c, d_istate, d_t_last, d_fires, d_tau,
                                     stream ? (hipStream_t)stream : c->stream); });
@@ -5450,7 +5563,7 @@ static int radau_set_controller_ctx(pfc_context *c, int n_act, const int *act, c
 int pfc_radau_set_controller(pfc_handle h, int n_act, const int *act, const double *kp, const double *kd, const double *a_max, double dt,
                              const double *t_last0, int n_seg, const double *seg_t, const double *seg_q, const double *seg_ff) {
     if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
         return radau_set_controller_ctx(c, n_act, act, kp, kd, a_max, dt, t_last0, n_seg, seg_t, seg_q, seg_ff); });
 }
 
@@ -5460,7 +5573,7 @@ int pfc_radau_clear_controller(pfc_handle h) {
 
 int pfc_radau_controller_state(pfc_handle h, double *t_last, int *fires) {
     if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
         const char *who = "pfc_radau_controller_state";
         const int rc = radau_need(c, who, false);
         if (rc != PFC_OK) return rc;
@@ -5476,19 +5589,41 @@ int pfc_radau_controller_state(pfc_handle h, double *t_last, int *fires) {
 
 // The controller at the top of a batch step: H and c at the committed state -- the first n_scene stage-scenes hold x0 after the
 // first unpack, and the Jacobian's first chunk overwrites the buffers used here -- then the law into RD_TAU.
-static int radau_control_step(pfc_context *c, const char *who) {
-    pfc_context::RadauHost &R = c->radau;
+static int radau_control_step(pfc_context *c, const char *who, const StateBufs &V) {
+    const pfc_context::RadauHost &R = c->radau;
     const pfc_context::RadauHost::Control &T = R.ctl;
     const RadauLayout &L = R.L;
-    auto D = [&](int k) { return R.dbl.p + R.od[k]; };
-    auto CD = [&](int k) { return T.cdbl.p + T.od[k]; };
-    int rc = pfc_kinematics_device(c, L.n_scene, D(RD_VQ), D(RD_VV), D(RD_VXWB), D(RD_VTW), nullptr, nullptr);
+    int rc = pfc_kinematics_device(c, L.n_scene, V.q, V.v, V.x_w_b, V.twist_w_b, nullptr, nullptr);
     if (rc != PFC_OK) return rc;
-    rc = pfc_dynamics_device(c, L.n_scene, D(RD_VQ), D(RD_VV), D(RD_VXWB), D(RD_VTW), nullptr, D(RD_VH), D(RD_VC), nullptr);
+    rc = pfc_dynamics_device(c, L.n_scene, V.q, V.v, V.x_w_b, V.twist_w_b, nullptr, V.H, V.c, nullptr);
     if (rc != PFC_OK) return rc;
-    return radau_control_launch(c, who, L.n_scene, L.nq, L.nv, T.n_act, T.n_seg, T.dt, T.citg.p + T.oi[CI_ACT], CD(CD_KP), CD(CD_KD),
-                                CD(CD_AMAX), CD(CD_SEGT), CD(CD_SEGQ), T.has_ff ? CD(CD_SEGFF) : nullptr, D(RD_T), D(RD_VQ), D(RD_VV),
-                                D(RD_VH), D(RD_VC), R.itg.p + R.oi[RI_ISTATE], CD(CD_TLAST), T.citg.p + T.oi[CI_FIRES], D(RD_TAU), c->stream);
+    return radau_control_launch(c, who, L.n_scene, L.nq, L.nv, T.n_act, T.n_seg, T.dt, T.I(CI_ACT), T.D(CD_KP), T.D(CD_KD), T.D(CD_AMAX),
+                                T.D(CD_SEGT), T.D(CD_SEGQ), T.has_ff ? T.D(CD_SEGFF) : nullptr, R.D(RD_T), V.q, V.v, V.H, V.c, R.I(RI_ISTATE),
+                                T.D(CD_TLAST), T.I(CI_FIRES), R.D(RD_TAU), c->stream);
+}
+
+// The handle's blocks as the buffers of the step's state calls -- val: RD_V* / RI_V*, par: RD_DD* -- bound in this one place; the
+// caller sets the heads (n_items, n_scene, n_dir).  q, v, s and their seeds a second time as what unpack and seed write.
+struct RadauStateBufs {
+    StateCall call;
+    double *q, *v, *s, *dq, *dv, *ds;
+};
+
+static RadauStateBufs radau_state_bufs(const pfc_context::RadauHost &R) {
+    RadauStateBufs B;
+    B.call.ins_ids = R.I(RI_VINS); B.call.scene = R.I(RI_VSC);
+    StateBufs &V = B.call.val, &P = B.call.par;
+    V.q = B.q = R.D(RD_VQ); V.v = B.v = R.D(RD_VV); V.s = B.s = R.D(RD_VS); V.tau = R.has_tau || R.ctl.on ? R.D(RD_TAU) : nullptr;
+    V.x_w_b = R.D(RD_VXWB); V.twist_w_b = R.D(RD_VTW); V.jac = R.D(RD_VJAC);
+    V.pose = R.D(RD_VPOSE); V.twist = R.D(RD_VTWI); V.x_w_r2 = R.D(RD_VXR2); V.body_1 = R.I(RI_VB1); V.body_2 = R.I(RI_VB2);
+    V.wrench = R.D(RD_VWR); V.sdot = R.D(RD_VSD); V.counts = R.I(RI_VCNT); V.f = R.D(RD_VF);
+    V.qdot = R.D(RD_VQD); V.H = R.D(RD_VH); V.c = R.D(RD_VC); V.vdot = R.D(RD_VVD); V.info = R.I(RI_VINFO);
+    P.q = B.dq = R.D(RD_DDQ); P.v = B.dv = R.D(RD_DDV); P.s = B.ds = R.D(RD_DDS);
+    P.x_w_b = R.D(RD_DDXWB); P.twist_w_b = R.D(RD_DDTW); P.jac = R.D(RD_DDJAC);
+    P.pose = R.D(RD_DDPOSE); P.twist = R.D(RD_DDTWI); P.x_w_r2 = R.D(RD_DDXR2);
+    P.wrench = R.D(RD_DDWR); P.sdot = R.D(RD_DDSD); P.f = R.D(RD_DDF);
+    P.qdot = R.D(RD_DDQD); P.H = R.D(RD_DDH); P.c = R.D(RD_DDC); P.vdot = R.D(RD_DDVD);
+    return B;
 }
 
 // An evaluation and its pfc_check, re-issued while the work lists grow.
@@ -5514,66 +5649,49 @@ static int radau_read_count(pfc_context *c, int *count, int words = 1) {
 // times and trajectory, and *live receives the scenes that committed a step and did not park.
 static int radau_step_body(pfc_context *c, const char *who, bool end, int *live) {
     int rc = PFC_OK;
-    pfc_context::RadauHost &R = c->radau;
+    const pfc_context::RadauHost &R = c->radau;
     const RadauLayout &L = R.L;
-    const int ns = L.n_scene, n1 = ns * L.n_ips, N3 = 3 * ns, n3 = 3 * n1;
-    auto D = [&](int k) { return R.dbl.p + R.od[k]; };
-    auto I = [&](int k) { return R.itg.p + R.oi[k]; };
-    const double *tau = R.has_tau || R.ctl.on ? D(RD_TAU) : nullptr;
-    const int *br = L.br_items;
-    auto unpack = [&]() {
-        return pfc_radau_unpack_device(c, ns, L.nx, L.nq, L.nv, L.n_ips, L.n_br, br, D(RD_X), I(RI_RULE), I(RI_ISTATE), D(RD_XS), D(RD_VQ),
-                                       D(RD_VV), D(RD_VS), nullptr); };
+    const RadauStateBufs B = radau_state_bufs(R);
+    const hipStream_t st = c->stream;
+    StateCall S = B.call, J = B.call;      // the stage-scenes' values, and the Dual chunks on the first n_scene of them
+    S.n_scene = 3 * L.n_scene; S.n_items = S.n_scene * L.n_ips;
+    J.n_scene = L.n_scene; J.n_items = J.n_scene * L.n_ips;
+    const StateBufs &V = B.call.val, &P = B.call.par;
+    auto unpack = [&]() { return radau_unpack_launch(c, L, R.D(RD_X), R.I(RI_RULE), R.I(RI_ISTATE), R.D(RD_XS), B.q, B.v, B.s, st); };
     // calcJacobian!: no scene is iterating, so every stage-scene -- the first n_scene of them are the scenes themselves -- gets x0
     if ((rc = unpack()) != PFC_OK) return rc;
-    if (R.ctl.on && (rc = radau_control_step(c, who)) != PFC_OK) return rc;
-    const int n_chunks = (L.nx + R.n_chunk - 1) / R.n_chunk;
-    for (int k = 0; k < n_chunks; ++k) {
-        const int nd = std::min(R.n_chunk, L.nx - k * R.n_chunk);
-        rc = pfc_radau_seed_device(c, ns, L.nx, L.nq, L.nv, L.n_ips, L.n_br, br, k, R.n_chunk, D(RD_DDQ), D(RD_DDV), D(RD_DDS), nullptr);
+    if (R.ctl.on && (rc = radau_control_step(c, who, V)) != PFC_OK) return rc;
+    for (int j0 = 0; j0 < L.nx; j0 += R.n_chunk) {
+        J.n_dir = std::min(R.n_chunk, L.nx - j0);
+        if ((rc = radau_seed_launch(c, L, j0, J.n_dir, B.dq, B.dv, B.ds, st)) != PFC_OK) return rc;
+        rc = radau_checked(c, [&]() { return state_derivative_dual(c, J, j0 > 0); });
         if (rc != PFC_OK) return rc;
-        rc = radau_checked(c, [&]() {
-            if (k == 0)
-                return pfc_state_derivative_dual_device(
-                    c, n1, nd, I(RI_VINS), I(RI_VSC), ns, D(RD_VQ), D(RD_VV), D(RD_DDQ), D(RD_DDV), D(RD_VS), D(RD_DDS), tau, nullptr,
-                    D(RD_VXWB), D(RD_VTW), D(RD_VJAC), D(RD_DDXWB), D(RD_DDTW), D(RD_DDJAC), D(RD_VPOSE), D(RD_VTWI), D(RD_VXR2), I(RI_VB1),
-                    I(RI_VB2), D(RD_DDPOSE), D(RD_DDTWI), D(RD_DDXR2), D(RD_VWR), D(RD_VSD), D(RD_DDWR), D(RD_DDSD), I(RI_VCNT), D(RD_VF),
-                    D(RD_DDF), D(RD_VQD), D(RD_VH), D(RD_VC), D(RD_VVD), I(RI_VINFO), D(RD_DDQD), D(RD_DDH), D(RD_DDC), D(RD_DDVD), nullptr);
-            return pfc_state_derivative_dual_device_more(
-                c, n1, nd, I(RI_VINS), I(RI_VSC), ns, D(RD_VQ), D(RD_VV), D(RD_DDQ), D(RD_DDV), D(RD_DDS), tau, nullptr, D(RD_VXWB), D(RD_VTW),
-                D(RD_VJAC), D(RD_DDXWB), D(RD_DDTW), D(RD_DDJAC), D(RD_VXR2), I(RI_VB1), I(RI_VB2), D(RD_VWR), D(RD_DDPOSE), D(RD_DDTWI),
-                D(RD_DDXR2), D(RD_DDWR), D(RD_DDSD), D(RD_DDF), D(RD_VH), D(RD_VC), D(RD_VF), D(RD_DDQD), D(RD_DDH), D(RD_DDC), D(RD_DDVD),
-                nullptr); });
-        if (rc != PFC_OK) return rc;
-        rc = pfc_radau_jacobian_device(c, ns, L.nx, L.nq, L.nv, L.n_ips, L.n_br, br, k, R.n_chunk, D(RD_DDQD), D(RD_DDVD), D(RD_DDSD),
-                                       D(RD_VQD), D(RD_VVD), D(RD_VSD), D(RD_NEGJ), D(RD_XDOT0), D(RD_NSTATE), I(RI_ISTATE), nullptr);
+        rc = radau_jacobian_launch(c, L, j0, J.n_dir, P.qdot, P.vdot, P.sdot, V.qdot, V.vdot, V.sdot, R.D(RD_NEGJ), R.D(RD_XDOT0),
+                                   R.D(RD_NSTATE), R.I(RI_ISTATE), st);
         if (rc != PFC_OK) return rc;
     }
-    const RadauEndBufs eb{R.has_end ? D(RD_TFINAL) : nullptr, R.max_rows > 0 ? R.traj.p : nullptr, R.max_rows > 0 ? I(RI_ROWS) : nullptr,
-                          R.max_rows, I(RI_COUNT) + 1};
-    if (end) HIP_TRY(c, hipMemsetAsync(I(RI_COUNT) + 1, 0, sizeof(int), c->stream));      // live adds up over the attempts' finishes
+    const RadauFinishRule rule{R.n_mrp, R.mrp_off, R.fin, R.k_iter_max, R.max_rule, R.cooldown};
+    const RadauEndBufs eb{R.has_end ? R.D(RD_TFINAL) : nullptr, R.max_rows > 0 ? R.traj.p : nullptr, R.max_rows > 0 ? R.I(RI_ROWS) : nullptr,
+                          R.max_rows, R.I(RI_COUNT) + 1};
+    if (end) HIP_TRY(c, hipMemsetAsync(R.I(RI_COUNT) + 1, 0, sizeof(int), st));      // live adds up over the attempts' finishes
     // solveRadau_inner: attempts until no scene is armed again
     for (int attempt = 0; attempt < 64; ++attempt) {
-        rc = radau_factor_launch(c, ns, L.nx, D(RD_NEGJ), D(RD_H), I(RI_RULE), I(RI_ISTATE) + kRadIter, 8, D(RD_LU0), D(RD_LU1), I(RI_PERM),
-                                 I(RI_INFO), c->stream);
+        rc = radau_factor_launch(c, L.n_scene, L.nx, R.D(RD_NEGJ), R.D(RD_H), R.I(RI_RULE), R.I(RI_ISTATE) + kRadIter, 8, R.D(RD_LU0),
+                                 R.D(RD_LU1), R.I(RI_PERM), R.I(RI_INFO), st);
         if (rc != PFC_OK) return rc;
         int count = 1;
         for (int it = 0; it <= R.k_iter_max && count > 0; ++it) {
             if ((rc = unpack()) != PFC_OK) return rc;
-            rc = radau_checked(c, [&]() {
-                return pfc_state_derivative_device(c, n3, I(RI_VINS), I(RI_VSC), N3, D(RD_VQ), D(RD_VV), D(RD_VS), tau, D(RD_VXWB), D(RD_VTW),
-                                                   D(RD_VJAC), D(RD_VPOSE), D(RD_VTWI), D(RD_VXR2), I(RI_VB1), I(RI_VB2), D(RD_VWR), D(RD_VSD),
-                                                   I(RI_VCNT), D(RD_VF), D(RD_VQD), D(RD_VH), D(RD_VC), D(RD_VVD), I(RI_VINFO), nullptr); });
-            if (rc != PFC_OK) return rc;
-            rc = pfc_radau_newton_device(c, ns, L.nx, L.nq, L.nv, L.n_ips, L.n_br, br, D(RD_VQD), D(RD_VVD), D(RD_VSD), D(RD_X), D(RD_H),
-                                         I(RI_RULE), D(RD_LU0), D(RD_LU1), I(RI_PERM), I(RI_INFO), R.tol_newton, R.k_iter_max, D(RD_XS),
-                                         D(RD_FS), D(RD_NSTATE), I(RI_ISTATE), I(RI_COUNT), nullptr);
+            if ((rc = radau_checked(c, [&]() { return state_derivative(c, S); })) != PFC_OK) return rc;
+            rc = radau_newton_launch(c, L, V.qdot, V.vdot, V.sdot, R.D(RD_X), R.D(RD_H), R.I(RI_RULE), R.D(RD_LU0), R.D(RD_LU1), R.I(RI_PERM),
+                                     R.I(RI_INFO), R.tol_newton, R.k_iter_max, R.D(RD_XS), R.D(RD_FS), R.D(RD_NSTATE), R.I(RI_ISTATE),
+                                     R.I(RI_COUNT), st);
             if (rc != PFC_OK || (rc = radau_read_count(c, &count)) != PFC_OK) return rc;
         }
         if (count > 0) return fail(c, PFC_ERR_STATE, "%s: %d scenes still iterate after k_iter_max + 1 passes", who, count);
-        rc = radau_finish_launch(c, who, end ? &eb : nullptr, ns, L.nx, L.nq, L.nv, L.n_ips, L.n_br, br, R.n_mrp, R.mrp_off, R.fin,
-                                 R.k_iter_max, R.max_rule, R.cooldown, D(RD_FS), D(RD_XDOT0), D(RD_XS), D(RD_LU0), I(RI_PERM), D(RD_X),
-                                 D(RD_T), D(RD_H), I(RI_RULE), I(RI_COOL), D(RD_ENORM), D(RD_NSTATE), I(RI_ISTATE), I(RI_COUNT), nullptr);
+        rc = radau_finish_launch(c, L, rule, end ? &eb : nullptr, R.D(RD_FS), R.D(RD_XDOT0), R.D(RD_XS), R.D(RD_LU0), R.I(RI_PERM), R.D(RD_X),
+                                 R.D(RD_T), R.D(RD_H), R.I(RI_RULE), R.I(RI_COOL), R.D(RD_ENORM), R.D(RD_NSTATE), R.I(RI_ISTATE),
+                                 R.I(RI_COUNT), st);
         int words[2] = {0, 0};
         if (rc != PFC_OK || (rc = radau_read_count(c, words, end ? 2 : 1)) != PFC_OK) return rc;
         count = words[0];
@@ -5590,12 +5708,10 @@ static int radau_step_ctx(pfc_context *c, double *h_taken, int *flags, int *iter
     if (rc != PFC_OK || (rc = radau_step_body(c, who, c->radau.has_end, nullptr)) != PFC_OK) return rc;
     pfc_context::RadauHost &R = c->radau;
     const int ns = R.L.n_scene;
-    auto D = [&](int k) { return R.dbl.p + R.od[k]; };
-    auto I = [&](int k) { return R.itg.p + R.oi[k]; };
     std::vector<double> nst(8 * (size_t)ns);
     std::vector<int> ist(8 * (size_t)ns);
-    HIP_TRY(c, hipMemcpy(nst.data(), D(RD_NSTATE), sizeof(double) * nst.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(ist.data(), I(RI_ISTATE), sizeof(int) * ist.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(nst.data(), R.D(RD_NSTATE), sizeof(double) * nst.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(ist.data(), R.I(RI_ISTATE), sizeof(int) * ist.size(), hipMemcpyDeviceToHost));
     for (int s = 0; s < ns; ++s) {
         const int *is = ist.data() + 8 * (size_t)s;
         if (h_taken) h_taken[s] = is[kRadExit] == 0 ? nst[8 * (size_t)s + kRadHTaken] : 0.0;
@@ -5608,13 +5724,13 @@ static int radau_step_ctx(pfc_context *c, double *h_taken, int *flags, int *iter
 
 int pfc_radau_step(pfc_handle h, double *h_taken, int *flags, int *iters, int *attempts) {
     if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) { return radau_step_ctx(c, h_taken, flags, iters, attempts); });
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) { return radau_step_ctx(c, h_taken, flags, iters, attempts); });
 }
 
 // ---- integration to per-scene end times (integrate_scenario_radau, src/example_integrator.jl) ------------------------------------
 int pfc_radau_set_end(pfc_handle h, const double *t_final, int max_rows) {
     if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
         const char *who = "pfc_radau_set_end";
         const int rc = radau_need(c, who, true);
         if (rc != PFC_OK) return rc;
@@ -5648,7 +5764,7 @@ int pfc_radau_set_end(pfc_handle h, const double *t_final, int max_rows) {
 
 int pfc_radau_integrate(pfc_handle h, int max_steps, int *steps_done, int *n_live) {
     if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
         const char *who = "pfc_radau_integrate";
         int rc = radau_need(c, who, true);
         if (rc != PFC_OK) return rc;
@@ -5672,7 +5788,7 @@ int pfc_radau_integrate(pfc_handle h, int max_steps, int *steps_done, int *n_liv
 
 int pfc_radau_trajectory_rows(pfc_handle h, int *rows) {
     if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
         const char *who = "pfc_radau_trajectory_rows";
         const int rc = radau_need(c, who, true);
         if (rc != PFC_OK) return rc;
@@ -5687,7 +5803,7 @@ int pfc_radau_trajectory_rows(pfc_handle h, int *rows) {
 
 int pfc_radau_trajectory(pfc_handle h, int scene, int row0, int n, double *t, double *x) {
     if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, radau_ctx(h), [&](pfc_context *c) {
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
         const char *who = "pfc_radau_trajectory";
         const int rc = radau_need(c, who, true);
         if (rc != PFC_OK) return rc;

@@ -1,0 +1,30 @@
+// pfc_statecall.h -- the buffers of a chained state call (pfc_eval_bodies_device .. pfc_state_derivative_dual_device_more), by name.
+// Plain C++ (no HIP, no pfc_context).  The groups are those include/pfc.h documents; the same struct holds the values and, a second
+// time, their partials along n_dir directions (a field without a partial -- body_1, body_2, counts, info -- stays null there).
+// Every pointer is a device pointer.  A public entry fills one StateCall from its parameters -- the only place where a parameter
+// position meets a field name -- and the chain and its stages read fields from then on.
+#pragma once
+
+struct StateBufs {
+    const double *q = nullptr, *v = nullptr, *s = nullptr, *tau = nullptr;       // the state and the applied forces: inputs
+    double *x_w_b = nullptr, *twist_w_b = nullptr, *jac = nullptr;               // body states (kinematics)
+    double *pose = nullptr, *twist = nullptr, *x_w_r2 = nullptr;                 // items (formed from the body states)
+    int *body_1 = nullptr, *body_2 = nullptr;
+    double *wrench = nullptr, *sdot = nullptr, *f = nullptr;                     // results (the evaluation and the scatter)
+    int *counts = nullptr;
+    double *qdot = nullptr, *H = nullptr, *c = nullptr, *vdot = nullptr;         // dynamics and the solve
+    int *info = nullptr;
+};
+
+struct StateCall {
+    int n_items = 0, n_dir = 0, n_scene = 0;
+    const int *ins_ids = nullptr, *scene = nullptr;
+    void *stream = nullptr;      // the caller's stream, null: the context's own
+    StateBufs val, par;          // the values, and their partials (Dual calls)
+};
+
+// A buffer that an entry declares const -- the values of a `_more` entry, the body states of the `_bodies` entries -- as the record's
+// field.  Such a call only reads it: every stage it launches takes that field through a const parameter, and a `more` call passes
+// null where a first call passes a value output.
+template <class T>
+T *kept_value(const T *p) { return const_cast<T *>(p); }
