@@ -71,12 +71,31 @@ int pfc_create(int device, pfc_handle *out);
  *       same way, ordered against `stream` by events; pfc_check synchronises every device.
  *   - option "multi_min" (default 8): with fewer than this many items per device fewer devices take part
  *     (pfc_last_shards() tells how many did); every other option is forwarded to all devices;
+ *   - the partition rule (csrc/pfc_partition.h; tests/partition_reference.py states it a second time).  For n items on K devices:
+ *       k_use = clamp(n / max(multi_min, 1), 1, K) devices take part, the others idle;
+ *       cost of item i = 64 + 0.02 * leaves(mesh_1) * leaves(mesh_2) the first time an item list is evaluated (64 where the ids
+ *       are device data the host cannot read), and 64 + node_tests + 4 * candidates of the item in the previous evaluation while
+ *       the list is the same (n_items, ins_ids given or not, the same kind of entry point, and for the host-pointer entry points
+ *       the same ids) and that evaluation succeeded; setting multi_min starts from the leaf products again;
+ *       boundary k (k = 1 .. k_use - 1) lies in front of the first item whose half would cross k / k_use of the total cost
+ *       (acc + 0.5 * cost[i] < target moves on), so within half an item of its target; then it is clamped so that every one of
+ *       the k_use devices has an item at least;
+ *       the ranges of the previous evaluation are kept, not cut again, while the list is the same, k_use is and the most loaded
+ *       device stays within 15 % of the mean under the new costs (worst * k_use <= 1.15 * total): the chunks of one Jacobian
+ *       must see the same ranges to reuse the value pass.  pfc_last_shard_bounds() shows the ranges.
+ *     Validated: any number of shard contexts on ONE device (tests/test_gpu_multi_shards.py: 3 and 8, every entry point named
+ *     here, idle devices, one dominating item, errors in a middle range).  NOT validated: distinct devices, the peer copies
+ *     (hipMemcpyPeerAsync) between them, and the scaling over devices -- no machine with several GPUs has run this code;
  *   - pfc_get_stats sums over the devices; pfc_debug_* go to the device that evaluated the item; pfc_last_parts / _team and
  *     pfc_get_stage_ms report the first device's.
  * Results are those of the single-device handle (counters bit-equal, sums up to their order).
  */
 int pfc_create_multi(const int *devices, int n_devices, pfc_handle *out);
 int pfc_last_shards(pfc_handle h);   /* devices that took part in the last evaluation (1 for a single-device handle) */
+/* Debug view of the last partition: writes bound[0 .. n_used], n_used = pfc_last_shards(h) -- device k evaluated the items
+ * [bound[k], bound[k + 1]) of the last evaluation, bound[0] = 0, bound[n_used] = its n_items -- and returns n_used.  A
+ * single-device handle writes {0, n_items} and returns 1.  -(PFC_ERR_BAD_ARG) when cap < n_used + 1 or bound is NULL. */
+int pfc_last_shard_bounds(pfc_handle h, int *bound, int cap);
 void pfc_destroy(pfc_handle h);
 const char *pfc_last_error(pfc_handle h);
 

@@ -31,6 +31,7 @@ SIGNATURES = {
     "pfc_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "pfc_create_multi": (C.c_int, [_ip, C.c_int, C.POINTER(C.c_void_p)]),
     "pfc_last_shards": (C.c_int, [C.c_void_p]),
+    "pfc_last_shard_bounds": (C.c_int, [C.c_void_p, _ip, C.c_int]),
     "pfc_destroy": (None, [C.c_void_p]),
     "pfc_last_error": (C.c_char_p, [C.c_void_p]),
     "pfc_add_mesh": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip, C.c_int, _ip, _dp, C.c_double, C.c_int,
@@ -154,7 +155,7 @@ class PFCError(RuntimeError):
 
 def build(force: bool = False) -> str:
     """Compile csrc/pfc_hip.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("pfc_hip.hip", "pfc_tree.cpp", "pfc_sort.hip", "pfc_kernels.h", "pfc_bp.h", "pfc_np.h", "pfc_br.h", "pfc_dual.h", "pfc_fused.h", "pfc_clip.h", "pfc_multi.h", "pfc_sort.h", "pfc_surface.h", "pfc_surface_fric.h", "pfc_scatter.h", "pfc_ljac.h", "pfc_bodies.h", "pfc_kin.h", "pfc_dyn.h", "pfc_radau.h", "pfc_radau_tables.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("pfc_hip.hip", "pfc_tree.cpp", "pfc_sort.hip", "pfc_kernels.h", "pfc_bp.h", "pfc_np.h", "pfc_br.h", "pfc_dual.h", "pfc_fused.h", "pfc_clip.h", "pfc_multi.h", "pfc_partition.h", "pfc_sort.h", "pfc_surface.h", "pfc_surface_fric.h", "pfc_scatter.h", "pfc_ljac.h", "pfc_bodies.h", "pfc_kin.h", "pfc_dyn.h", "pfc_radau.h", "pfc_radau_tables.h")]
     srcs.append(os.path.join(os.path.dirname(HERE), "include", "pfc.h"))
     srcs.append(os.path.abspath(__file__))      # the compiler flags live here
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)

@@ -1648,6 +1648,18 @@ int pfc_create_multi(const int *devices, int n_devices, pfc_handle *out) {
 
 int pfc_last_shards(pfc_handle h) { return h ? (h->multi ? h->multi->n_used : 1) : 0; }
 
+int pfc_last_shard_bounds(pfc_handle h, int *bound, int cap) {
+    if (!h) return -PFC_ERR_BAD_ARG;
+    if (!bound) return -fail(h, PFC_ERR_BAD_ARG, "pfc_last_shard_bounds: null buffer");
+    const pfc_multi *M = h->multi;
+    const bool cut = M && (int)M->bound.size() == (int)M->shard.size() + 1;      // (a multi-device handle before its first evaluation: no items, one shard)
+    const int n_used = cut ? M->n_used : 1;
+    if (cap < n_used + 1) return -fail(h, PFC_ERR_BAD_ARG, "pfc_last_shard_bounds: cap %d is less than the %d bounds of %d shards", cap, n_used + 1, n_used);
+    if (cut) for (int k = 0; k <= n_used; ++k) bound[k] = M->bound[k];
+    else { bound[0] = 0; bound[1] = M ? 0 : h->last_n_items; }
+    return n_used;
+}
+
 void pfc_destroy(pfc_handle h) {
     if (!h) return;
     if (h->multi) { multi_destroy(h); delete h; return; }

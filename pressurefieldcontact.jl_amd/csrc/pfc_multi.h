@@ -20,6 +20,7 @@
 // gather / scatter; what it gives up against a longest-first assignment is balance when single items dominate (they do not in
 // the configurations of BASELINE.json: 256 equal scenes, 2 016 pile pairs, batches of poses).
 #pragma once
+#include "pfc_partition.h"
 
 struct pfc_multi {
     std::vector<pfc_context *> shard;
@@ -129,51 +130,27 @@ int multi_run(pfc_context *h, std::vector<std::function<int()>> &jobs) {
 void multi_partition(pfc_context *h, int n, const int *ins_ids, bool has_ids, bool is_dev) {
     pfc_multi *M = h->multi;
     const int K = (int)M->shard.size();
-    int k_use = n / (M->opt_min_items > 0 ? M->opt_min_items : 1);
-    if (k_use > K) k_use = K;
-    if (k_use < 1) k_use = 1;
+    const int k_use = partition_k_use(n, K, M->opt_min_items);
     const bool same_list = M->part_n == n && M->part_ids == has_ids && M->part_dev == is_dev && (int)M->bound.size() == K + 1 &&
                            (is_dev || !ins_ids || std::memcmp(M->part_ins.data(), ins_ids, sizeof(int) * (size_t)n) == 0);
     M->cost.resize((size_t)n);
     if (same_list && M->counts_valid) {
-        for (int i = 0; i < n; ++i) M->cost[i] = 64.0 + (double)M->h_counts.p[4 * (size_t)i] + 4.0 * (double)M->h_counts.p[4 * (size_t)i + 1];
+        for (int i = 0; i < n; ++i) M->cost[i] = partition_cost_counters(M->h_counts.p[4 * (size_t)i], M->h_counts.p[4 * (size_t)i + 1]);
     } else {
         const pfc_context *c0 = M->shard[0];
         for (int i = 0; i < n; ++i) {
-            double c = 64.0;
+            double c = partition_cost_leaves(0.0, 0.0);
             if (!(is_dev && has_ids)) {      // (a device-resident item list cannot be read here: equal costs until the counters are known)
                 const int id = ins_ids ? ins_ids[i] : i;
                 if (id >= 0 && id < (int)c0->ins.size())
-                    c += 0.02 * (double)c0->meshes[c0->ins[id].m1].n_leaf * (double)c0->meshes[c0->ins[id].m2].n_leaf;
+                    c = partition_cost_leaves((double)c0->meshes[c0->ins[id].m1].n_leaf, (double)c0->meshes[c0->ins[id].m2].n_leaf);
             }
             M->cost[i] = c;
         }
     }
-    double total = 0.0;
-    for (int i = 0; i < n; ++i) total += M->cost[i];
-    if (same_list && M->n_used == k_use) {
-        double worst = 0.0;
-        for (int k = 0; k < k_use; ++k) {
-            double c = 0.0;
-            for (int i = M->bound[k]; i < M->bound[k + 1]; ++i) c += M->cost[i];
-            if (c > worst) worst = c;
-        }
-        if (worst * k_use <= 1.15 * total) return;      // still balanced: keep the ranges
-    }
-    M->bound.assign((size_t)K + 1, n);
-    M->bound[0] = 0;
-    double acc = 0.0;
-    int i = 0;
-    for (int k = 1; k < k_use; ++k) {
-        const double target = total * (double)k / (double)k_use;
-        while (i < n && acc + 0.5 * M->cost[i] < target) acc += M->cost[i++];
-        int b = i;
-        if (b < M->bound[k - 1] + 1) b = M->bound[k - 1] + 1;      // every used shard gets an item
-        if (b > n - (k_use - k)) b = n - (k_use - k);
-        while (i < b) acc += M->cost[i++];
-        M->bound[k] = b;
-    }
-    for (int k = k_use; k <= K; ++k) M->bound[k] = n;
+    if (same_list && M->n_used == k_use && partition_keeps(M->cost.data(), n, M->bound.data(), k_use)) return;      // still balanced: keep the ranges
+    M->bound.resize((size_t)K + 1);
+    partition_cut(M->cost.data(), n, k_use, K, M->bound.data());
     M->n_used = k_use;
     M->part_n = n; M->part_ids = has_ids; M->part_dev = is_dev;
     if (ins_ids && !is_dev) M->part_ins.assign(ins_ids, ins_ids + n); else M->part_ins.clear();

@@ -1673,6 +1673,16 @@ class MechanismScenario:
         """Devices that took part in the last evaluation (1 for a single-device scenario)."""
         return int(_lib.lib().pfc_last_shards(self._h))
 
+    def last_shard_bounds(self) -> list:
+        """Debug view of the last partition: [b_0 = 0, b_1, ..., b_used = n_items]; device k evaluated items [b_k, b_k+1).
+        [0, n_items] for a single-device scenario."""
+        L = _lib.lib()
+        out = (C.c_int * (max(L.pfc_last_shards(self._h), 1) + 1))()
+        n = L.pfc_last_shard_bounds(self._h, out, len(out))
+        if n < 0:
+            self._check(-n)
+        return [int(v) for v in out[:n + 1]]
+
     def last_team(self) -> int:
         """Workgroups per item of the last checked evaluation if it ran as one fused kernel (> 1: a team per item), else 0."""
         return int(_lib.lib().pfc_last_team(self._h))
