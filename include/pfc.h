@@ -1284,6 +1284,66 @@ int pfc_radau_set_controller(pfc_handle h, int n_act, const int *act, const doub
 int pfc_radau_clear_controller(pfc_handle h);      /* pfc_radau_set_controller's clearing form */
 int pfc_radau_controller_state(pfc_handle h, double *t_last, int *fires);
 
+/*
+ * The gripper program: the part of the reference's grip_control! that has memory (test/pencil.jl:35-116,147-173) -- a queue of
+ * GripperIns instructions with durations relative to the moment each one starts, the watched body's rotation angle latched at every
+ * switch, and a grip torque chosen from slip_allowed -- in front of the law above, which then runs unchanged: the program writes the
+ * controller's one schedule segment, and the law's tau_a = (sum H acc + c_a) + ff_a is the reference's tau_ext[act] = H4 qdd + C4;
+ * tau_ext[pad] += tau_grip.
+ * The statement.  Per scene a program of n_ins >= 1 instructions and one record.  Instruction j: prog_dt[j] >= 0 (+inf allowed, never
+ * NaN), prog_q[j][0 .. n_act) finite setpoints of the controller's actuated coordinates, prog_slip[j] -inf, +-0, +inf or finite (never
+ * NaN).  Shared by the batch: a watched body, n_grip >= 0 grip coordinates, each one of the controller's act[], and tau_soft, tau_hard,
+ * both finite.  The record: cursor = 0, pops = 0, t0 = +inf, rot_0 = +inf, angle = 0, tau_grip = 0 initially.
+ * At the top of a batch step a scene runs the program if it is neither retired (exit flag 5) nor parked and t_last <= t, the
+ * controller's own clock test, read before the law advances t_last.  A scene that is not due changes nothing, byte for byte.  A due
+ * scene does the following once, in plain Float64, no fma, in the written order:
+ *   1. R = the rotation of x_w_b[scene n_body + body] (column-major, Rij = x[(i - 1) + 3 (j - 1)]):
+ *      a = R32 - R23; b = R13 - R31; c = R21 - R12;  s = sqrt((a a + b b) + c c);  w = ((R11 + R22) + R33) - 1;
+ *      angle = atan2(s, w), in [0, pi]   (the reference takes AngleAxis(rotation(..)).theta of Rotations.jl 0.11.1, which is not
+ *      vendored: parity unpinned, as for principal_value!)
+ *   2. if t0 == +inf: t0 = t
+ *   3. if cursor < n_ins - 1 and prog_dt[cursor] < (t - t0): cursor += 1, pops += 1, t0 = t, rot_0 = angle   (strict <, the
+ *      reference's; one pop per step at most, also the reference's; the last instruction never expires -- a stated deviation: the
+ *      reference would index an empty vector)
+ *   4. sl = prog_slip[cursor]:  sl == -inf: tau_grip = 0;  sl == 0 (so -0.0 too): tau_hard;  sl == +inf: tau_soft;  otherwise
+ *      tau_grip = (fabs(angle - rot_0) < sl) ? tau_soft : tau_hard   (with rot_0 = +inf, the first instruction, or a NaN angle:
+ *      tau_hard, as in the reference)
+ *   5. seg_q[scene][0][a] = prog_q[cursor][a] for every actuated a; seg_ff[scene][0][g] = tau_grip for every grip coordinate g (the
+ *      other entries of seg_ff stay what pfc_radau_set_controller gave); then the record is stored.
+ * Once per step is the reference's result: the reference calls the controller at every addition to t_last with the same (x, t), and
+ * with prog_dt >= 0 a second call at the same t finds t - t0 = 0 after a pop, or an already latched t0, and changes nothing.
+ * pfc_radau_program_device: the part on caller buffers and a caller stream (NULL: the handle's), asynchronous; it reads nothing of the
+ * handle but its device and stream.  d_grip (n_grip ints, each < nv: the caller guarantees it), d_prog_dt and d_prog_slip (n_scene x
+ * n_ins), d_prog_q (n_scene x n_ins x n_act), d_t and d_t_last (n_scene), d_x_w_b (n_scene x n_body x 12, pfc_kinematics_device's
+ * output), d_istate (n_scene x 8, or NULL: every scene is eligible); in/out d_cursor (n_scene x 2: cursor, pops; the caller keeps
+ * cursor in 0 .. n_ins - 1), d_pstate (n_scene x 4: t0, rot_0, angle, tau_grip), d_seg_q (n_scene x n_act) and d_seg_ff (n_scene x
+ * nv).  One launch, one lane per scene.  PFC_ERR_BAD_ARG: nv outside 1 .. PFC_MAX_NV_SOLVE, n_act outside 0 .. nv, n_ins < 1, body
+ * outside 0 .. n_body - 1, n_grip outside 0 .. nv, a grip torque that is not finite, null buffer.
+ * pfc_radau_set_program: the program of the handle's batch (host arrays: grip (n_grip), prog_dt and prog_slip (n_scene x n_ins),
+ * prog_q (n_scene x n_ins x n_act)), copied into device blocks owned by the handle; the records get their initial values.  From then on
+ * the controller's part of every batch step runs the program on the handle's x_w_b after pfc_kinematics_device and before the law;
+ * nothing is read back.  PFC_ERR_STATE without a controller.  PFC_ERR_BAD_ARG, with a message and nothing changed: a controller with
+ * n_seg != 1 or without a seg_ff block; body outside the mechanism; a grip coordinate that is not in act[], or repeated; tau_soft,
+ * tau_hard or a setpoint that is not finite; a prog_dt that is negative or NaN; a prog_slip that is NaN; n_ins < 1.  The new blocks are
+ * allocated before the old ones are freed: PFC_ERR_NOMEM keeps the previous program.  pfc_radau_clear_program removes the program and
+ * puts the controller's segment back to what pfc_radau_set_controller gave: the step issues the launches it issued without one.
+ * pfc_radau_set_controller (any form) and pfc_radau_configure drop the program.  pfc_radau_set_state keeps the program and resets
+ * every record to its initial values (and the segment to pfc_radau_set_controller's).
+ * pfc_radau_program_state: the records (n_scene each, host; any pointer may be NULL); PFC_ERR_STATE without a program.  Multi-device
+ * handles use their first device, as the step does.
+ */
+/* pfc_radau_get_tau: the tau the step reads, 3 n_scene x nv (host; the rows scene, n_scene + scene and 2 n_scene + scene of a scene are
+ * equal): what pfc_radau_set_tau gave, overwritten per scene by the controller's fires; zeros where neither is in force. */
+int pfc_radau_get_tau(pfc_handle h, double *tau);
+int pfc_radau_program_device(pfc_handle h, int n_scene, int n_body, int nv, int n_act, int n_ins, int body, int n_grip, const int *d_grip,
+                             double tau_soft, double tau_hard, const double *d_prog_dt, const double *d_prog_q, const double *d_prog_slip,
+                             const double *d_t, const double *d_t_last, const double *d_x_w_b, const int *d_istate, int *d_cursor,
+                             double *d_pstate, double *d_seg_q, double *d_seg_ff, void *stream);
+int pfc_radau_set_program(pfc_handle h, int body, int n_grip, const int *grip, double tau_soft, double tau_hard, int n_ins,
+                          const double *prog_dt, const double *prog_q, const double *prog_slip);
+int pfc_radau_clear_program(pfc_handle h);
+int pfc_radau_program_state(pfc_handle h, int *cursor, int *pops, double *t0, double *rot_0, double *angle, double *tau_grip);
+
 #ifdef __cplusplus
 }
 #endif

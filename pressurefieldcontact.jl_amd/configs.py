@@ -197,6 +197,79 @@ def pencil_emesh() -> G.EMesh:
     return m.transformed(t=np.array([0.0, 0.0, 0.0035]))      # transform!(eM_penci, SVector(0, 0, penci_rad)), pencil.jl:200
 
 
+def pencil_gripper(is_bristle: bool = False) -> dict:
+    """The scenario of the reference's test/pencil.jl restated in this project's builders: data only, nothing here needs a device.
+    Meshes (ids 0 .. 4): the half plane scaled by 0.6 (tets, Ebar 1e6), the rev_y box surface (rigid, no instruction), two pads --
+    sphere n_div 4 of radius 3.5 mm shifted by -/+ (pad_rad + penci_rad) in y, then scaled (2, 1, 2): 320 tets each, Ebar 1e6 -- and
+    the pencil surface (pencil_emesh).  Bodies (0 .. 4): world -> prismatic z (tra_z) -> revolute y (rev_y) -> {prismatic +y (pad_n),
+    prismatic -y (pad_p)}, world -> MRP-floating pencil; nq = nv = 10, NX = 20 (32 with bristle friction on the two pad items).
+    The four instructions of pencil.jl:218-226: pencil / pad_n, pencil / pad_p, pencil / plane, pad_n / pad_p.  Inertias by
+    geometry.mesh_inertia (rho 16000 for the pads, 400 with d = 3.5 mm for the pencil; the two base bodies are
+    MeshInertiaInfo(ones(3,3), 0, 1.0)); the state of :232-236; the gains, clamp and period of grip_control! and the eleven
+    GripperIns of :59-89 as arrays.
+    Returns dict(workload, mechanism = (parent, joint_type, x_p_j, axis), inertia (5, 13), gravity, ins_bodies, x0 (NX,), controller =
+    dict(act, kp, kd, a_max, dt, t_last0, seg_q (1, 4), seg_ff (1, nv)), program = dict(body, grip, tau_soft, tau_hard, prog_dt,
+    prog_q, prog_slip), radau = dict(h0, h_max, h_min, t_final, max_steps))."""
+    from . import _lib
+    pad_rad, penci_length, penci_rad = 0.0035, 0.16, 0.0035
+    inf = float("inf")
+    plane = G.as_tet_emesh(G.emesh_half_plane()).transformed(R=0.6 * np.eye(3))
+    rev_y = G.as_tri_emesh(G.emesh_box(pad_rad * np.array([1.0, 7.0, 1.0]), pad_rad * np.array([0.0, -4.0, 8.0])))
+    stretch = np.diag([2.0, 1.0, 2.0])
+    pad = G.as_tet_emesh(G.emesh_sphere(pad_rad, 4))
+    pad_n = pad.transformed(t=np.array([0.0, -(pad_rad + penci_rad), 0.0])).transformed(R=stretch)
+    pad_p = pad.transformed(t=np.array([0.0, +(pad_rad + penci_rad), 0.0])).transformed(R=stretch)
+    penci = G.as_tri_emesh(pencil_emesh())
+    meshes = [_mesh("plane", plane, 1.0e6), _mesh("rev_y", rev_y), _mesh("pad_n", pad_n, 1.0e6), _mesh("pad_p", pad_p, 1.0e6),
+              _mesh("pencil", penci)]
+    if is_bristle:
+        pads = dict(model="bristle", chi=0.6, mu_d=0.5, k_bar=8.0e4, magic=1.0e-2, tau=0.01)
+    else:
+        pads = dict(model="regularized", chi=0.6, mu_d=0.5, v_tol=1.0e-5)
+    ins = [InsSpec(4, 2, **pads), InsSpec(4, 3, **pads), InsSpec(4, 0, "regularized", chi=0.6, mu_d=0.5, v_tol=1.0e-5),
+           InsSpec(2, 3, "regularized", chi=0.6, mu_d=0.0, v_tol=1.0e-5)]
+    ins_bodies = [(4, 2), (4, 3), (4, -1), (2, 3)]
+    w = Workload("pencil gripper", meshes, ins, np.arange(4, dtype=np.int32), np.zeros((4, 24)), np.zeros((4, 6)), np.zeros((4, 6)),
+                 {"n_tet_pad": pad_n.n_tet, "n_tri_pencil": penci.n_tri})
+    eye = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
+    mechanism = (np.array([-1, 0, 1, 1, -1], dtype=np.int32),
+                 np.array([_lib.JOINT_PRISMATIC, _lib.JOINT_REVOLUTE, _lib.JOINT_PRISMATIC, _lib.JOINT_PRISMATIC, _lib.JOINT_FLOATING_MRP],
+                          dtype=np.int32),
+                 np.array([eye] * 5), np.array([[0.0, 0.0, 1.0], [0.0, 1.0, 0.0], [0.0, 1.0, 0.0], [0.0, -1.0, 0.0], [0.0, 0.0, 0.0]]))
+    base = np.concatenate([np.ones(9), np.zeros(3), [1.0]])
+    inertia = np.array([base, base, G.mesh_inertia(pad_n, 16000.0), G.mesh_inertia(pad_p, 16000.0), G.mesh_inertia(penci, 400.0, d=penci_rad)])
+    nq = 10
+    x0 = np.zeros(2 * nq + (12 if is_bristle else 0))
+    x0[0], x0[1] = 0.10, np.pi / 4
+    x0[4:7] = [0.0, 0.0, -np.tan(np.pi / 8)]      # MRP(RotZ(-pi/2)) = axis tan(angle / 4)
+    x0[7:10] = [penci_length * -0.8, 0.0, 0.0]
+    w_n = 2 * np.pi / 0.75                        # make_pd_gains(0.75, 1.0)
+    z_high, z_low, th_1, th_2 = 1.2 * penci_length, penci_rad, np.pi / 2, -np.pi / 2
+    rows = [(1.2, -inf, z_low, 0.0), (0.25, inf, z_low, 0.0), (1.3, inf, z_high, 0.0), (0.5, 0.0, z_high, 0.0), (2.0, 0.0, z_high, th_1),
+            (1.5, inf, z_high, th_1), (0.5, 0.0, z_high, th_1), (2.5, 0.0, z_high, th_2), (2.5, 0.2, z_high, th_2), (2.5, 0.2, z_high, th_2),
+            (inf, inf, z_high, th_2)]
+    prog_q = np.array([[z, th, 0.0, 0.0] for _, _, z, th in rows])
+    controller = dict(act=np.arange(4, dtype=np.int32), kp=w_n ** 2, kd=2 * 1.0 * w_n, a_max=np.array([1.0, inf, inf, inf]), dt=0.01,
+                      t_last0=0.0, seg_q=prog_q[:1].copy(), seg_ff=np.zeros((1, nq)))
+    program = dict(body=4, grip=np.array([2, 3], dtype=np.int32), tau_soft=0.3, tau_hard=2.5, prog_dt=np.array([r[0] for r in rows]),
+                   prog_q=prog_q, prog_slip=np.array([r[1] for r in rows]))
+    return dict(workload=w, mechanism=mechanism, inertia=inertia, gravity=(0.0, 0.0, -round(9.8054 * 2 ** 8) / 2 ** 8),
+                ins_bodies=ins_bodies, x0=x0, controller=controller, program=program,
+                radau=dict(h0=0.01, h_max=0.01, h_min=1.0e-14, t_final=18.0, max_steps=8200))
+
+
+def build_gripper_scenario(d: dict, device: int = 0, fixed_order: bool = False) -> MechanismScenario:
+    """pencil_gripper()'s data -> a finalized MechanismScenario with its mechanism, instruction bodies and inertias (HIP)."""
+    m = build_scenario(d["workload"], device=device)
+    if fixed_order:
+        m.set_option("fixed_order", 1)
+    m.set_mechanism(*d["mechanism"])
+    for k, (b1, b2) in enumerate(d["ins_bodies"]):
+        m.set_instruction_bodies(k, b1, b2)
+    m.set_inertia(d["inertia"], d["gravity"])
+    return m
+
+
 def spoon_pencil_pads(n_poses: int = 32, seed: int = 20260105) -> Workload:
     """Real geometry through the path ("lets real reference scenes run"): the reference's spoon surface and its
     swept pencil surface, each against the compliant finger pad of test/pencil.jl:188-190 (sphere n_div 4 of radius 3.5 mm

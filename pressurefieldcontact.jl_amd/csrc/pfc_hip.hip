@@ -211,6 +211,7 @@ __global__ void k_repose(int n_items, const double *__restrict__ pose, ItemRec *
 #include "pfc_kin.h"
 #include "pfc_dyn.h"
 #include "pfc_radau.h"
+#include "pfc_radau_program.h"
 #include "pfc_radau_tables.h"
 
 }  // namespace pfc
@@ -671,6 +672,23 @@ struct pfc_context {
             double *D(int part) const { return cdbl.p + od[part]; }
             int *I(int part) const { return citg.p + oi[part]; }
             std::vector<double> t_last0;
+            std::vector<int> act;                 // the actuated coordinates, for pfc_radau_set_program's validation
+            // pfc_radau_set_program: the instructions and the records (pdbl, parts RadauPD) and the grip coordinates and cursors
+            // (pitg, parts RadauPI) in two blocks of their own, replaced by the next pfc_radau_set_program and freed by
+            // pfc_radau_clear_program, with the controller (so by pfc_radau_set_controller and pfc_radau_configure) and with the
+            // handle.  seg_q0 and seg_ff0 are the controller's segment as pfc_radau_set_controller gave it: the program writes
+            // the segment on the device, pfc_radau_clear_program and pfc_radau_set_state put it back.
+            struct Program {
+                bool on = false;
+                int n_ins = 0, body = 0, n_grip = 0;
+                double tau_soft = 0, tau_hard = 0;
+                DevBuf<double> pdbl;
+                DevBuf<int> pitg;
+                size_t od[4] = {0}, oi[2] = {0};  // offsets of the parts (RadauPD, RadauPI)
+                double *D(int part) const { return pdbl.p + od[part]; }
+                int *I(int part) const { return pitg.p + oi[part]; }
+                std::vector<double> seg_q0, seg_ff0;
+            } prog;
         } ctl;
         void drop_control() { ctl = Control(); }
     } radau;
@@ -5211,6 +5229,10 @@ enum RadauI { RI_RULE, RI_COOL, RI_ISTATE, RI_PERM, RI_INFO, RI_COUNT, RI_VINS, 
 // Parts of the controller's two blocks (pfc_radau_set_controller).
 enum RadauCD { CD_KP, CD_KD, CD_AMAX, CD_SEGT, CD_SEGQ, CD_SEGFF, CD_TLAST, CD_N };
 enum RadauCI { CI_ACT, CI_FIRES, CI_N };
+// Parts of the program's two blocks (pfc_radau_set_program).
+enum RadauPD { PD_DT, PD_Q, PD_SLIP, PD_STATE, PD_N };
+enum RadauPI { PI_GRIP, PI_CURSOR, PI_N };
+static int radau_program_reset(pfc_context *c);
 
 static int radau_configure_ctx(pfc_context *c, int n_scene, int n_ips, const int *ins_ids, const double *params, int k_iter_max,
                                int max_rule, int n_chunk, int cooldown) {
@@ -5350,6 +5372,7 @@ int pfc_radau_set_state(pfc_handle h, const double *x, const double *t) {
             HIP_TRY(c, hipMemcpy(R.ctl.cdbl.p + R.ctl.od[CD_TLAST], R.ctl.has_t0 ? R.ctl.t_last0.data() : tt.data(), sizeof(double) * ns,
                                  hipMemcpyHostToDevice));
             HIP_TRY(c, hipMemcpy(R.ctl.citg.p + R.ctl.oi[CI_FIRES], zero.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
+            if (R.ctl.prog.on && (rc = radau_program_reset(c)) != PFC_OK) return rc;      // the program stays; its records start again
         }
         R.has_state = true;
         return (int)PFC_OK; });
@@ -5410,6 +5433,21 @@ int pfc_radau_set_tau(pfc_handle h, const double *tau) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         for (int k = 0; k < 3; ++k)      // the same tau for the three stage-scenes of a scene
             HIP_TRY(c, hipMemcpy(R.dbl.p + R.od[RD_TAU] + (size_t)k * ns * nv, tau, sizeof(double) * ns * nv, hipMemcpyHostToDevice));
+        return (int)PFC_OK; });
+}
+
+int pfc_radau_get_tau(pfc_handle h, double *tau) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        const int rc = radau_need(c, "pfc_radau_get_tau", false);
+        if (rc != PFC_OK) return rc;
+        if (!tau) return fail(c, PFC_ERR_BAD_ARG, "pfc_radau_get_tau: null buffer");
+        pfc_context::RadauHost &R = c->radau;
+        const size_t n = 3 * (size_t)R.L.n_scene * (size_t)R.L.nv;
+        if (!R.has_tau && !R.ctl.on) { std::fill(tau, tau + n, 0.0); return (int)PFC_OK; }      // the step reads no tau: zeros
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpy(tau, R.dbl.p + R.od[RD_TAU], sizeof(double) * n, hipMemcpyDeviceToHost));
         return (int)PFC_OK; });
 }
 
@@ -5568,7 +5606,8 @@ static int radau_set_controller_ctx(pfc_context *c, int n_act, const int *act, c
     HIP_TRY(c, hipMemcpy(N.citg.p, hi.data(), sizeof(int) * ti, hipMemcpyHostToDevice));
     N.on = true; N.has_ff = seg_ff != nullptr; N.has_t0 = t_last0 != nullptr; N.n_act = n_act; N.n_seg = n_seg; N.dt = dt;
     if (t_last0) N.t_last0.assign(t_last0, t_last0 + ns);
-    R.ctl = std::move(N);
+    N.act.assign(act, act + n_act);
+    R.ctl = std::move(N);      // a program of the previous controller goes with it
     return radau_zero_tau_unless_set(c);
 }
 
@@ -5599,6 +5638,171 @@ int pfc_radau_controller_state(pfc_handle h, double *t_last, int *fires) {
         return (int)PFC_OK; });
 }
 
+// ---- the gripper program (k_radau_program, pfc_radau_program.h; the statement: include/pfc.h) -----------------------------------------
+static int radau_program_launch(pfc_context *h, const char *who, int n_scene, int n_body, int nv, int n_act, int n_ins, int body, int n_grip,
+                                const int *d_grip, double tau_soft, double tau_hard, const double *d_prog_dt, const double *d_prog_q,
+                                const double *d_prog_slip, const double *d_t, const double *d_t_last, const double *d_x_w_b,
+                                const int *d_istate, int *d_cursor, double *d_pstate, double *d_seg_q, double *d_seg_ff, hipStream_t st) {
+    if (n_scene < 0) return fail(h, PFC_ERR_BAD_ARG, "%s: negative n_scene", who);
+    if (nv < 1 || nv > PFC_MAX_NV_SOLVE)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: nv is %d, the law takes 1 .. PFC_MAX_NV_SOLVE = %d coordinates", who, nv, PFC_MAX_NV_SOLVE);
+    if (n_act < 0 || n_act > nv) return fail(h, PFC_ERR_BAD_ARG, "%s: n_act is %d, 0 .. nv = %d", who, n_act, nv);
+    if (n_ins < 1) return fail(h, PFC_ERR_BAD_ARG, "%s: n_ins is %d, at least one instruction", who, n_ins);
+    if (n_body < 1 || body < 0 || body >= n_body) return fail(h, PFC_ERR_BAD_ARG, "%s: body is %d, 0 .. n_body - 1 = %d", who, body, n_body - 1);
+    if (n_grip < 0 || n_grip > nv) return fail(h, PFC_ERR_BAD_ARG, "%s: n_grip is %d, 0 .. nv = %d", who, n_grip, nv);
+    if (!std::isfinite(tau_soft) || !std::isfinite(tau_hard))
+        return fail(h, PFC_ERR_BAD_ARG, "%s: tau_soft is %.17g and tau_hard %.17g: finite grip torques", who, tau_soft, tau_hard);
+    if (n_scene == 0) return PFC_OK;
+    if ((n_act > 0 && (!d_prog_q || !d_seg_q)) || (n_grip > 0 && (!d_grip || !d_seg_ff)) || !d_prog_dt || !d_prog_slip || !d_t || !d_t_last ||
+        !d_x_w_b || !d_cursor || !d_pstate)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    RadauProgramArgs a;
+    a.n_scene = n_scene; a.n_body = n_body; a.nv = nv; a.n_act = n_act; a.n_ins = n_ins; a.body = body; a.n_grip = n_grip;
+    a.tau_soft = tau_soft; a.tau_hard = tau_hard; a.grip = d_grip; a.prog_dt = d_prog_dt; a.prog_slip = d_prog_slip; a.prog_q = d_prog_q;
+    a.t = d_t; a.t_last = d_t_last; a.x_w_b = d_x_w_b; a.istate = d_istate; a.cursor = d_cursor; a.pstate = d_pstate; a.seg_q = d_seg_q;
+    a.seg_ff = d_seg_ff;
+    hipLaunchKernelGGL(k_radau_program, dim3((unsigned)((n_scene + kRadProgBlock - 1) / kRadProgBlock)), dim3(kRadProgBlock), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+int pfc_radau_program_device(pfc_handle h, int n_scene, int n_body, int nv, int n_act, int n_ins, int body, int n_grip, const int *d_grip,
+                             double tau_soft, double tau_hard, const double *d_prog_dt, const double *d_prog_q, const double *d_prog_slip,
+                             const double *d_t, const double *d_t_last, const double *d_x_w_b, const int *d_istate, int *d_cursor,
+                             double *d_pstate, double *d_seg_q, double *d_seg_ff, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        return radau_program_launch(c, "pfc_radau_program_device", n_scene, n_body, nv, n_act, n_ins, body, n_grip, d_grip, tau_soft, tau_hard,
+                                    d_prog_dt, d_prog_q, d_prog_slip, d_t, d_t_last, d_x_w_b, d_istate, d_cursor, d_pstate, d_seg_q, d_seg_ff,
+                                    stream ? (hipStream_t)stream : c->stream); });
+}
+
+// The records to their initial values and the controller's segment to what pfc_radau_set_controller gave (the stream is idle).
+static int radau_program_reset(pfc_context *c) {
+    pfc_context::RadauHost::Control &T = c->radau.ctl;
+    const pfc_context::RadauHost::Control::Program &P = T.prog;
+    const size_t ns = (size_t)c->radau.L.n_scene;
+    const double inf = std::numeric_limits<double>::infinity();
+    std::vector<double> rec(4 * ns, 0.0);
+    for (size_t s = 0; s < ns; ++s) { rec[4 * s] = inf; rec[4 * s + 1] = inf; }
+    const std::vector<int> cur(2 * ns, 0);
+    HIP_TRY(c, hipMemcpy(P.D(PD_STATE), rec.data(), sizeof(double) * 4 * ns, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(P.I(PI_CURSOR), cur.data(), sizeof(int) * 2 * ns, hipMemcpyHostToDevice));
+    if (!P.seg_q0.empty()) HIP_TRY(c, hipMemcpy(T.D(CD_SEGQ), P.seg_q0.data(), sizeof(double) * P.seg_q0.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(T.D(CD_SEGFF), P.seg_ff0.data(), sizeof(double) * P.seg_ff0.size(), hipMemcpyHostToDevice));
+    return PFC_OK;
+}
+
+static int radau_set_program_ctx(pfc_context *c, int body, int n_grip, const int *grip, double tau_soft, double tau_hard, int n_ins,
+                                 const double *prog_dt, const double *prog_q, const double *prog_slip) {
+    const char *who = "pfc_radau_set_program";
+    const int rc = radau_need(c, who, false);
+    if (rc != PFC_OK) return rc;
+    pfc_context::RadauHost &R = c->radau;
+    pfc_context::RadauHost::Control &T = R.ctl;
+    if (!T.on) return fail(c, PFC_ERR_STATE, "%s without a controller (pfc_radau_set_controller)", who);
+    if (T.n_seg != 1 || !T.has_ff)
+        return fail(c, PFC_ERR_BAD_ARG, "%s: the controller has n_seg = %d and %s seg_ff block: the program writes one segment and its feed-forward",
+                    who, T.n_seg, T.has_ff ? "a" : "no");
+    if (body < 0 || body >= c->kin.n_body) return fail(c, PFC_ERR_BAD_ARG, "%s: body is %d, the mechanism has %d", who, body, c->kin.n_body);
+    const size_t ns = (size_t)R.L.n_scene, nv = (size_t)R.L.nv, na = (size_t)T.n_act;
+    if (n_grip < 0 || n_grip > T.n_act || (n_grip > 0 && !grip)) return fail(c, PFC_ERR_BAD_ARG, "%s: n_grip is %d, 0 .. n_act = %d", who, n_grip, T.n_act);
+    for (int g = 0; g < n_grip; ++g) {
+        if (std::find(T.act.begin(), T.act.end(), grip[g]) == T.act.end())
+            return fail(c, PFC_ERR_BAD_ARG, "%s: grip coordinate %d is not one of the controller's actuated coordinates", who, grip[g]);
+        if (std::find(grip, grip + g, grip[g]) != grip + g) return fail(c, PFC_ERR_BAD_ARG, "%s: grip coordinate %d is repeated", who, grip[g]);
+    }
+    if (!std::isfinite(tau_soft) || !std::isfinite(tau_hard))
+        return fail(c, PFC_ERR_BAD_ARG, "%s: tau_soft is %.17g and tau_hard %.17g: finite grip torques", who, tau_soft, tau_hard);
+    if (n_ins < 1 || !prog_dt || !prog_slip || (na > 0 && !prog_q))
+        return fail(c, PFC_ERR_BAD_ARG, "%s: n_ins is %d: at least one instruction, with prog_dt, prog_q and prog_slip given", who, n_ins);
+    const size_t ni = (size_t)n_ins;
+    for (size_t e = 0; e < ns * ni; ++e) {
+        if (!(prog_dt[e] >= 0.0))
+            return fail(c, PFC_ERR_BAD_ARG, "%s: prog_dt %zu of scene %zu is %.17g: a duration is >= 0 (+inf allowed)", who, e % ni, e / ni, prog_dt[e]);
+        if (prog_slip[e] != prog_slip[e]) return fail(c, PFC_ERR_BAD_ARG, "%s: prog_slip %zu of scene %zu is NaN", who, e % ni, e / ni);
+    }
+    for (size_t e = 0; e < ns * ni * na; ++e)
+        if (!std::isfinite(prog_q[e])) return fail(c, PFC_ERR_BAD_ARG, "%s: a setpoint of scene %zu is not finite", who, e / (ni * na));
+    pfc_context::RadauHost::Control::Program N;
+    size_t sd[PD_N], si[PI_N], td = 0, ti = 0;
+    sd[PD_DT] = ns * ni; sd[PD_Q] = ns * ni * na; sd[PD_SLIP] = ns * ni; sd[PD_STATE] = 4 * ns; si[PI_GRIP] = (size_t)n_grip; si[PI_CURSOR] = 2 * ns;
+    for (int k = 0; k < PD_N; ++k) { N.od[k] = td; td += sd[k]; }
+    for (int k = 0; k < PI_N; ++k) { N.oi[k] = ti; ti += si[k]; }
+    std::vector<double> hd(td, 0.0);
+    std::vector<int> hi(ti, 0);
+    std::memcpy(hd.data() + N.od[PD_DT], prog_dt, sizeof(double) * ns * ni);
+    if (na) std::memcpy(hd.data() + N.od[PD_Q], prog_q, sizeof(double) * ns * ni * na);
+    std::memcpy(hd.data() + N.od[PD_SLIP], prog_slip, sizeof(double) * ns * ni);
+    for (int g = 0; g < n_grip; ++g) hi[N.oi[PI_GRIP] + g] = grip[g];
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // the segment as pfc_radau_set_controller gave it: the previous program's copy, or what the device holds
+    if (T.prog.on) { N.seg_q0 = T.prog.seg_q0; N.seg_ff0 = T.prog.seg_ff0; }
+    else {
+        N.seg_q0.resize(ns * na); N.seg_ff0.resize(ns * nv);
+        if (na) HIP_TRY(c, hipMemcpy(N.seg_q0.data(), T.D(CD_SEGQ), sizeof(double) * ns * na, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(N.seg_ff0.data(), T.D(CD_SEGFF), sizeof(double) * ns * nv, hipMemcpyDeviceToHost));
+    }
+    // the new blocks first: if they cannot be had, the previous program stays in force
+    if (N.pdbl.ensure(td) != hipSuccess || N.pitg.ensure(ti) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, PFC_ERR_NOMEM, "%s: no device memory for %zu doubles and %zu ints", who, td, ti);
+    }
+    HIP_TRY(c, hipMemcpy(N.pdbl.p, hd.data(), sizeof(double) * td, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(N.pitg.p, hi.data(), sizeof(int) * ti, hipMemcpyHostToDevice));
+    N.on = true; N.n_ins = n_ins; N.body = body; N.n_grip = n_grip; N.tau_soft = tau_soft; N.tau_hard = tau_hard;
+    T.prog = std::move(N);
+    return radau_program_reset(c);
+}
+
+int pfc_radau_set_program(pfc_handle h, int body, int n_grip, const int *grip, double tau_soft, double tau_hard, int n_ins,
+                          const double *prog_dt, const double *prog_q, const double *prog_slip) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        return radau_set_program_ctx(c, body, n_grip, grip, tau_soft, tau_hard, n_ins, prog_dt, prog_q, prog_slip); });
+}
+
+int pfc_radau_clear_program(pfc_handle h) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        const char *who = "pfc_radau_clear_program";
+        const int rc = radau_need(c, who, false);
+        if (rc != PFC_OK) return rc;
+        pfc_context::RadauHost::Control &T = c->radau.ctl;
+        if (!T.on || !T.prog.on) return (int)PFC_OK;
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        const int rr = radau_program_reset(c);      // the segment goes back to pfc_radau_set_controller's
+        T.prog = pfc_context::RadauHost::Control::Program();
+        return rr; });
+}
+
+int pfc_radau_program_state(pfc_handle h, int *cursor, int *pops, double *t0, double *rot_0, double *angle, double *tau_grip) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        const char *who = "pfc_radau_program_state";
+        const int rc = radau_need(c, who, false);
+        if (rc != PFC_OK) return rc;
+        const pfc_context::RadauHost::Control &T = c->radau.ctl;
+        if (!T.on || !T.prog.on) return fail(c, PFC_ERR_STATE, "%s without a program (pfc_radau_set_program)", who);
+        const size_t ns = (size_t)c->radau.L.n_scene;
+        std::vector<double> rec(4 * ns);
+        std::vector<int> cur(2 * ns);
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpy(rec.data(), T.prog.D(PD_STATE), sizeof(double) * 4 * ns, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(cur.data(), T.prog.I(PI_CURSOR), sizeof(int) * 2 * ns, hipMemcpyDeviceToHost));
+        double *out[4] = {t0, rot_0, angle, tau_grip};
+        for (size_t s = 0; s < ns; ++s) {
+            if (cursor) cursor[s] = cur[2 * s];
+            if (pops) pops[s] = cur[2 * s + 1];
+            for (int k = 0; k < 4; ++k) if (out[k]) out[k][s] = rec[4 * s + k];
+        }
+        return (int)PFC_OK; });
+}
+
 // The controller at the top of a batch step: H and c at the committed state -- the first n_scene stage-scenes hold x0 after the
 // first unpack, and the Jacobian's first chunk overwrites the buffers used here -- then the law into RD_TAU.
 static int radau_control_step(pfc_context *c, const char *who, const StateBufs &V) {
@@ -5607,6 +5811,13 @@ static int radau_control_step(pfc_context *c, const char *who, const StateBufs &
     const RadauLayout &L = R.L;
     int rc = pfc_kinematics_device(c, L.n_scene, V.q, V.v, V.x_w_b, V.twist_w_b, nullptr, nullptr);
     if (rc != PFC_OK) return rc;
+    if (T.prog.on) {      // the program reads the clock before the law advances it, and writes the segment the law reads
+        const pfc_context::RadauHost::Control::Program &P = T.prog;
+        rc = radau_program_launch(c, who, L.n_scene, c->kin.n_body, L.nv, T.n_act, P.n_ins, P.body, P.n_grip, P.I(PI_GRIP), P.tau_soft,
+                                  P.tau_hard, P.D(PD_DT), P.D(PD_Q), P.D(PD_SLIP), R.D(RD_T), T.D(CD_TLAST), V.x_w_b, R.I(RI_ISTATE),
+                                  P.I(PI_CURSOR), P.D(PD_STATE), T.D(CD_SEGQ), T.D(CD_SEGFF), c->stream);
+        if (rc != PFC_OK) return rc;
+    }
     rc = pfc_dynamics_device(c, L.n_scene, V.q, V.v, V.x_w_b, V.twist_w_b, nullptr, V.H, V.c, nullptr);
     if (rc != PFC_OK) return rc;
     return radau_control_launch(c, who, L.n_scene, L.nq, L.nv, T.n_act, T.n_seg, T.dt, T.I(CI_ACT), T.D(CD_KP), T.D(CD_KD), T.D(CD_AMAX),

@@ -22,6 +22,7 @@ counters.  All compute runs in libpfc_hip (HIP, gfx950); nothing here has a CPU 
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Union
 
@@ -1213,6 +1214,13 @@ class MechanismScenario:
         t_a = None if tau is None else np.ascontiguousarray(tau, dtype=np.float64).reshape(self._radau_n_scene, -1)
         self._check(_lib.lib().pfc_radau_set_tau(self._h, None if t_a is None else t_a.ctypes.data_as(_dp)))
 
+    def radau_get_tau(self):
+        """pfc_radau_get_tau: the tau the step reads, (3, n_scene, nv): radau_set_tau's, overwritten by the controller's fires."""
+        n, nv = self._radau_n_scene, self.mechanism_sizes()[2]
+        tau = np.zeros((3, n, nv))
+        self._check(_lib.lib().pfc_radau_get_tau(self._h, tau.ctypes.data_as(_dp)))
+        return tau
+
     def radau_rule_state(self):
         """Per scene: dict of h, rule, cooldown, theta, psi_k, x_err_norm, x_err_norm_next (arrays of n_scene)."""
         out = np.zeros((self._radau_n_scene, 7))
@@ -1300,6 +1308,7 @@ class MechanismScenario:
         p = lambda a: None if a is None else a.ctypes.data_as(_dp)
         self._check(_lib.lib().pfc_radau_set_controller(self._h, int(na), act_a.ctypes.data_as(_ip), p(kp_a), p(kd_a), p(am_a), float(dt),
                                                         p(t0_a), int(n_seg), p(st_a), p(sq_a), p(ff_a)))
+        self._radau_n_act = int(na)
 
     def radau_clear_controller(self):
         """pfc_radau_clear_controller: the step is the step without a controller again."""
@@ -1350,6 +1359,95 @@ class MechanismScenario:
         t_last, fires = self._radau_host_ctl
         return t_last.copy(), fires.copy()
 
+    # ---- the gripper program (include/pfc.h, pfc_radau_set_program; the scalar statement: gripper_program_step below) -----------
+    def _program_arrays(self, prog_dt, prog_q, prog_slip):
+        """(n_ins, prog_dt (n_scene, n_ins), prog_q (n_scene, n_ins, n_act), prog_slip (n_scene, n_ins)): leading scene axes broadcast;
+        n_act is prog_q's last axis."""
+        n_act = np.shape(prog_q)[-1] if np.ndim(prog_q) >= 2 else 0
+        dt = np.asarray(prog_dt, dtype=np.float64)
+        n_ins = dt.shape[-1] if dt.ndim else 1
+        n = getattr(self, "_radau_n_scene", 0) or dt.size // n_ins      # 0: not configured, the library says so
+        dt_a = np.ascontiguousarray(np.broadcast_to(dt.reshape(-1, n_ins), (n, n_ins)))
+        sl_a = np.ascontiguousarray(np.broadcast_to(np.asarray(prog_slip, dtype=np.float64).reshape(-1, n_ins), (n, n_ins)))
+        q_a = np.zeros((n, n_ins, 0)) if n_act == 0 else \
+            np.ascontiguousarray(np.broadcast_to(np.asarray(prog_q, dtype=np.float64).reshape((-1, n_ins, n_act)), (n, n_ins, n_act)))
+        return n_ins, dt_a, q_a, sl_a
+
+    def radau_set_program(self, body: int, grip, tau_soft: float, tau_hard: float, prog_dt, prog_q, prog_slip):
+        """pfc_radau_set_program: a gripper program in front of the controller of radau_set_controller (one segment, with seg_ff).
+        body the watched body; grip the grip coordinates (each one of the controller's act);
+        prog_dt (n_scene, n_ins) or (n_ins,) the durations, prog_q (n_scene, n_ins, n_act) or (n_ins, n_act) the setpoints, prog_slip
+        like prog_dt: -inf no grip, 0 tau_hard, +inf tau_soft, finite: tau_soft until the body has turned by that angle since the
+        instruction began, then tau_hard."""
+        n_ins, dt_a, q_a, sl_a = self._program_arrays(prog_dt, prog_q, prog_slip)
+        if q_a.shape[2] != getattr(self, "_radau_n_act", q_a.shape[2]):
+            raise ValueError("radau_set_program: prog_q has %d setpoints per instruction, the controller %d actuated coordinates"
+                             % (q_a.shape[2], self._radau_n_act))
+        g_a = np.ascontiguousarray(grip, dtype=np.int32).reshape(-1)
+        self._check(_lib.lib().pfc_radau_set_program(self._h, int(body), int(g_a.size), g_a.ctypes.data_as(_ip), float(tau_soft),
+                                                     float(tau_hard), int(n_ins), dt_a.ctypes.data_as(_dp), q_a.ctypes.data_as(_dp),
+                                                     sl_a.ctypes.data_as(_dp)))
+
+    def radau_clear_program(self):
+        """pfc_radau_clear_program: the controller is the controller of radau_set_controller again."""
+        self._check(_lib.lib().pfc_radau_clear_program(self._h))
+
+    def radau_program_state(self):
+        """The records of the device program: dict of cursor, pops (int32) and t0, rot_0, angle, tau_grip, arrays of n_scene."""
+        n = getattr(self, "_radau_n_scene", 0)
+        cur, pops = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        d = [np.zeros(n) for _ in range(4)]
+        self._check(_lib.lib().pfc_radau_program_state(self._h, cur.ctypes.data_as(_ip), pops.ctypes.data_as(_ip),
+                                                       *[a.ctypes.data_as(_dp) for a in d]))
+        return dict(cursor=cur, pops=pops, t0=d[0], rot_0=d[1], angle=d[2], tau_grip=d[3])
+
+    def radau_program_device(self, n_scene: int, n_body: int, nv: int, n_act: int, n_ins: int, body: int, n_grip: int, d_grip: int,
+                             tau_soft: float, tau_hard: float, d_prog_dt: int, d_prog_q: int, d_prog_slip: int, d_t: int, d_t_last: int,
+                             d_x_w_b: int, d_istate: int, d_cursor: int, d_pstate: int, d_seg_q: int, d_seg_ff: int, stream: int = 0):
+        """pfc_radau_program_device: the program's part on raw device addresses (0: NULL); asynchronous on `stream`."""
+        a = [d_prog_dt, d_prog_q, d_prog_slip, d_t, d_t_last, d_x_w_b, d_istate, d_cursor, d_pstate, d_seg_q, d_seg_ff, stream]
+        self._check(_lib.lib().pfc_radau_program_device(self._h, int(n_scene), int(n_body), int(nv), int(n_act), int(n_ins), int(body),
+                                                        int(n_grip), d_grip or None, float(tau_soft), float(tau_hard),
+                                                        *[x or None for x in a]))
+
+    def gripper_program_fn(self, act, kp, kd, seg_ff, body: int, grip, tau_soft: float, tau_hard: float, prog_dt, prog_q, prog_slip,
+                           a_max=None):
+        """fn(x, t, scene) -> tau for integrate_scenario_radau(discrete_controller=(fn, dt, t_last0)): the program and the law of
+        radau_set_program + radau_set_controller on the host, with a record per scene -- the angle from the host form `kinematics`
+        (math.atan2), gripper_program_step, then computed_torque_pd on `dynamics`' H and c with the segment the program wrote.
+        seg_ff (n_scene, nv) or (nv,): the feed-forward of the one segment; the arrays as radau_set_program's.  fn.records is the list
+        of the scenes' records."""
+        n = self._radau_n_scene
+        _, nq, nv = self.mechanism_sizes()
+        act_l = [int(a) for a in np.asarray(act).reshape(-1)]
+        na = len(act_l)
+        vec = lambda a: [float(e) for e in np.broadcast_to(np.asarray(a, dtype=np.float64), (na,))]
+        kp_l, kd_l = vec(kp), vec(kd)
+        am_l = None if a_max is None else vec(a_max)
+        grip_l = [int(g) for g in np.asarray(grip).reshape(-1)]
+        _, dt_a, q_a, sl_a = self._program_arrays(prog_dt, prog_q, prog_slip)
+        ff = np.array(np.broadcast_to(np.asarray(seg_ff, dtype=np.float64).reshape(-1, nv), (n, nv)))      # written by the program
+        records = [dict(PROGRAM_RECORD0) for _ in range(n)]
+        body = int(body)
+
+        def fn(x, t, scene):
+            q, v = np.asarray(x[:nq], dtype=np.float64), np.asarray(x[nq:nq + nv], dtype=np.float64)
+            x_w_b, tw, _ = self.kinematics(q, v, want_jac=False)
+            angle = rotation_angle(x_w_b[0, body, :9])
+            records[scene], seg_q, tau_grip = gripper_program_step(records[scene], t, angle, dt_a[scene].tolist(), q_a[scene].tolist(),
+                                                                   sl_a[scene].tolist(), tau_soft, tau_hard)
+            for g in grip_l:
+                ff[scene, g] = tau_grip
+            _, H, c = self.dynamics(q, v, x_w_b, tw)
+            return computed_torque_pd(q.tolist(), v.tolist(), H[0].tolist(), c[0].tolist(), float(t), act_l, kp_l, kd_l, [0.0], [seg_q],
+                                      [ff[scene].tolist()], am_l)
+        fn.records = records
+        return fn
+
+    def radau_host_tau(self):
+        """tau (n_scene, nv) as the host route last set it (integrate_scenario_radau(discrete_controller=...))."""
+        return self._radau_host_tau.copy()
+
     def _integrate_with_callback(self, tf, max_steps: int, discrete_controller):
         """The host route: the reference's loop (src/example_integrator.jl:25-30) per live scene before every batch step -- t_last by
         repeated addition, fn called at every addition -- then radau_set_tau and one radau_step."""
@@ -1381,6 +1479,7 @@ class MechanismScenario:
             rows = self.radau_trajectory_rows()
             live = (fl == 0) & ~(tf < t) & (rows < max_rows)      # neither retired (5) nor parked (6, or by this commit)
         self._radau_host_ctl = (t_last, fires)
+        self._radau_host_tau = tau
 
     def integrate_scenario_radau(self, t_final, max_steps: int = 1000, discrete_controller=None):
         """The reference's integrate_scenario_radau for every scene of the batch: from the state as it is, each scene steps while
@@ -1778,6 +1877,52 @@ def computed_torque_pd(q, v, H, c, t, act, kp, kd, seg_t, seg_q, seg_ff=None, a_
             s = s + float(H[co][cb]) * acc[b]
         tau[co] = (s + float(c[co])) + ff[co]
     return tau
+
+
+# ---- the gripper program: the scalar statement of include/pfc.h (pfc_radau_program_device) in Python floats -------------------------
+PROGRAM_RECORD0 = dict(cursor=0, pops=0, t0=float("inf"), rot_0=float("inf"), angle=0.0, tau_grip=0.0)
+
+
+def rotation_angle(R, atan2=math.atan2) -> float:
+    """The angle in [0, pi] of a rotation, in the written order.  R is (3, 3) (R[i][j]) or flat column-major (the first nine of a
+    body's x_w_b record): a = R32 - R23, b = R13 - R31, c = R21 - R12; s = sqrt((a a + b b) + c c); w = ((R11 + R22) + R33) - 1;
+    atan2(s, w).  atan2: the function to take it with (the tests pass a high-precision one)."""
+    A = np.asarray(R, dtype=np.float64)
+    x = [float(e) for e in (A.reshape(-1, order="F") if A.ndim == 2 else A.reshape(-1)[:9])]      # x[(i - 1) + 3 (j - 1)] = Rij
+    s, w = rotation_angle_terms(x)
+    return float(atan2(s, w))
+
+
+def rotation_angle_terms(x):
+    """(s, w) of rotation_angle from the nine column-major entries, as Python floats."""
+    a, b, c = x[5] - x[7], x[6] - x[2], x[1] - x[3]
+    s = math.sqrt((a * a + b * b) + c * c)
+    w = ((x[0] + x[4]) + x[8]) - 1.0
+    return s, w
+
+
+def gripper_program_step(record, t, angle, prog_dt, prog_q, prog_slip, tau_soft, tau_hard):
+    """One due evaluation of a scene's program (steps 2 - 5 of the statement; the angle of step 1 is given).  record: dict of cursor,
+    pops, t0, rot_0, angle, tau_grip (PROGRAM_RECORD0 initially); prog_dt (n_ins), prog_q (n_ins x n_act), prog_slip (n_ins).
+    Returns (the new record, the segment's setpoints prog_q[cursor], tau_grip); `record` is not changed."""
+    inf = float("inf")
+    t, angle = float(t), float(angle)
+    cursor, pops, t0, rot_0 = int(record["cursor"]), int(record["pops"]), float(record["t0"]), float(record["rot_0"])
+    if t0 == inf:
+        t0 = t
+    if cursor < len(prog_dt) - 1 and float(prog_dt[cursor]) < (t - t0):
+        cursor, pops, t0, rot_0 = cursor + 1, pops + 1, t, angle
+    sl = float(prog_slip[cursor])
+    if sl == -inf:
+        tau_grip = 0.0
+    elif sl == 0.0:
+        tau_grip = float(tau_hard)
+    elif sl == inf:
+        tau_grip = float(tau_soft)
+    else:
+        tau_grip = float(tau_soft) if abs(angle - rot_0) < sl else float(tau_hard)
+    new = dict(cursor=cursor, pops=pops, t0=t0, rot_0=rot_0, angle=angle, tau_grip=tau_grip)
+    return new, [float(e) for e in prog_q[cursor]], tau_grip
 
 
 def relative_pose(R_w1, t_w1, R_w2, t_w2) -> np.ndarray:
