@@ -272,6 +272,42 @@ private:
     }
 };
 
+// A block of doubles and a block of ints, each carved into the parts of an enum whose last value (ND, NI) counts them.  layout()
+// turns the parts' sizes into offsets and totals -- kRound: every part rounded up to 32 doubles / 64 ints, an empty part taking one
+// element; otherwise packed -- and ensure() allocates the double block, then the int block.  put() and get() are synchronous copies
+// of n elements between the host and a part (from its element `at`); the host pointer's type picks the block.
+template <auto ND, auto NI, bool kRound>
+struct PartBlocks {
+    using PartD = decltype(ND);
+    using PartI = decltype(NI);
+    DevBuf<double> dbl;
+    DevBuf<int> itg;
+    size_t od[ND] = {0}, oi[NI] = {0}, td = 0, ti = 0;
+    double *D(PartD part) const { return &dbl.p[od[part]]; }
+    int *I(PartI part) const { return &itg.p[oi[part]]; }
+    void layout(const size_t (&sd)[ND], const size_t (&si)[NI]) {
+        td = ti = 0;
+        for (int k = 0; k < ND; ++k) { od[k] = td; td += kRound ? (std::max<size_t>(sd[k], 1) + 31) & ~(size_t)31 : sd[k]; }
+        for (int k = 0; k < NI; ++k) { oi[k] = ti; ti += kRound ? (std::max<size_t>(si[k], 1) + 63) & ~(size_t)63 : si[k]; }
+    }
+    hipError_t ensure() {
+        const hipError_t e = dbl.ensure(td);
+        return e != hipSuccess ? e : itg.ensure(ti);
+    }
+    hipError_t put(PartD part, const double *host, size_t n, size_t at = 0) const {
+        return hipMemcpy(D(part) + at, host, sizeof(double) * n, hipMemcpyHostToDevice);
+    }
+    hipError_t put(PartI part, const int *host, size_t n, size_t at = 0) const {
+        return hipMemcpy(I(part) + at, host, sizeof(int) * n, hipMemcpyHostToDevice);
+    }
+    hipError_t get(double *host, PartD part, size_t n, size_t at = 0) const {
+        return hipMemcpy(host, D(part) + at, sizeof(double) * n, hipMemcpyDeviceToHost);
+    }
+    hipError_t get(int *host, PartI part, size_t n, size_t at = 0) const {
+        return hipMemcpy(host, I(part) + at, sizeof(int) * n, hipMemcpyDeviceToHost);
+    }
+};
+
 // A pinned host block of cap elements: grown to kSlack times what is asked for, never shrunk, zeroed when it is allocated
 // (completion words are polled from these blocks: never start from stale bytes).
 template <class T, int kSlack = 1>
@@ -407,6 +443,23 @@ struct HostMesh {
 };
 
 enum { EV_START = 0, EV_SETUP, EV_BP, EV_NP, EV_BR, EV_FIN, EV_COUNT };
+
+// Parts of the Radau handle's two blocks (pfc_context::RadauHost, pfc_radau_configure).  The value buffers (RD_V*, RI_V*) are those of
+// pfc_state_derivative_device on the 3 n_scene stage-scenes; the Jacobian chunks run on the first n_scene of them -- before the first
+// attempt every stage-scene holds x0 -- and write their value outputs there as well, so only the partials (RD_DD*) have buffers of
+// their own.
+enum RadauD { RD_X, RD_T, RD_H, RD_ENORM, RD_NSTATE, RD_XS, RD_FS, RD_XDOT0, RD_NEGJ, RD_LU0, RD_LU1, RD_TAU,
+              RD_VQ, RD_VV, RD_VS, RD_VXWB, RD_VTW, RD_VJAC, RD_VPOSE, RD_VTWI, RD_VXR2, RD_VWR, RD_VSD, RD_VF, RD_VQD, RD_VH, RD_VC, RD_VVD,
+              RD_DDQ, RD_DDV, RD_DDS, RD_DDXWB, RD_DDTW, RD_DDJAC, RD_DDPOSE, RD_DDTWI, RD_DDXR2, RD_DDWR, RD_DDSD, RD_DDF, RD_DDQD, RD_DDH,
+              RD_DDC, RD_DDVD, RD_TFINAL, RD_N };
+// RI_COUNT has two words: the count a newton or finish part returns, and the scenes live after a batch step (k_radau_finish<true>).
+enum RadauI { RI_RULE, RI_COOL, RI_ISTATE, RI_PERM, RI_INFO, RI_COUNT, RI_VINS, RI_VSC, RI_VB1, RI_VB2, RI_VCNT, RI_VINFO, RI_ROWS, RI_N };
+// Parts of the controller's two blocks (pfc_radau_set_controller).
+enum RadauCD { CD_KP, CD_KD, CD_AMAX, CD_SEGT, CD_SEGQ, CD_SEGFF, CD_TLAST, CD_N };
+enum RadauCI { CI_ACT, CI_FIRES, CI_N };
+// Parts of the program's two blocks (pfc_radau_set_program).
+enum RadauPD { PD_DT, PD_Q, PD_SLIP, PD_STATE, PD_N };
+enum RadauPI { PI_GRIP, PI_CURSOR, PI_N };
 
 }  // namespace
 
@@ -642,16 +695,12 @@ struct pfc_context {
     // pfc_contact_surface_fric (pfc_surface_fric.h): per item the moment and friction records of its waves and eig_item's block
     DevBuf<double> sfric_mom, sfric_sum, sfric_res;
     // the Radau IIA step (pfc_radau.h): integrator state and workspace of pfc_radau_configure, carved out of two blocks
-    struct RadauHost {
+    // The blocks' parts are the enums above; RadauHost rounds its parts, the controller and the program pack theirs (PartBlocks).
+    struct RadauHost : PartBlocks<RD_N, RI_N, true> {
         bool configured = false, has_state = false, has_tau = false;
         RadauLayout L;
         int n_chunk = 0, k_iter_max = 0, max_rule = 0, cooldown = 0, n_mrp = 0, mrp_off[kRadMaxBr];
         double h0 = 0, tol_newton = 0, fin[4];      // fin = {tol_a, tol_r, h_max, h_min}
-        DevBuf<double> dbl;
-        DevBuf<int> itg;
-        std::vector<size_t> od, oi;                 // offsets of the parts (RadauD, RadauI)
-        double *D(int part) const { return dbl.p + od[part]; }
-        int *I(int part) const { return itg.p + oi[part]; }
         // pfc_radau_set_end: the end times live in dbl (RD_TFINAL) and the row counts in itg (RI_ROWS); the trajectory is a block of
         // its own, n_scene x max_rows x (1 + NX), replaced by the next pfc_radau_set_end and freed by pfc_radau_configure,
         // pfc_radau_set_state and with the handle
@@ -659,34 +708,24 @@ struct pfc_context {
         int max_rows = 0;
         DevBuf<double> traj;
         void drop_end() { has_end = false; max_rows = 0; traj.release(); }
-        // pfc_radau_set_controller: law, schedules, t_last (cdbl, parts RadauCD) and act, the counters (citg, parts RadauCI) in two
-        // blocks of their own, replaced by the next pfc_radau_set_controller and freed by its clearing form, pfc_radau_configure and
-        // with the handle.  t_last0 stays on the host for pfc_radau_set_state.
-        struct Control {
+        // pfc_radau_set_controller: law, schedules, t_last (parts RadauCD) and act, the counters (parts RadauCI) in two blocks of
+        // their own, replaced by the next pfc_radau_set_controller and freed by its clearing form, pfc_radau_configure and with the
+        // handle.  t_last0 stays on the host for pfc_radau_set_state.
+        struct Control : PartBlocks<CD_N, CI_N, false> {
             bool on = false, has_ff = false, has_t0 = false;
             int n_act = 0, n_seg = 0;
             double dt = 0;
-            DevBuf<double> cdbl;
-            DevBuf<int> citg;
-            size_t od[8] = {0}, oi[2] = {0};      // offsets of the parts (RadauCD, RadauCI)
-            double *D(int part) const { return cdbl.p + od[part]; }
-            int *I(int part) const { return citg.p + oi[part]; }
             std::vector<double> t_last0;
             std::vector<int> act;                 // the actuated coordinates, for pfc_radau_set_program's validation
-            // pfc_radau_set_program: the instructions and the records (pdbl, parts RadauPD) and the grip coordinates and cursors
-            // (pitg, parts RadauPI) in two blocks of their own, replaced by the next pfc_radau_set_program and freed by
-            // pfc_radau_clear_program, with the controller (so by pfc_radau_set_controller and pfc_radau_configure) and with the
-            // handle.  seg_q0 and seg_ff0 are the controller's segment as pfc_radau_set_controller gave it: the program writes
-            // the segment on the device, pfc_radau_clear_program and pfc_radau_set_state put it back.
-            struct Program {
+            // pfc_radau_set_program: the instructions and the records (parts RadauPD) and the grip coordinates and cursors (parts
+            // RadauPI) in two blocks of their own, replaced by the next pfc_radau_set_program and freed by pfc_radau_clear_program,
+            // with the controller (so by pfc_radau_set_controller and pfc_radau_configure) and with the handle.  seg_q0 and seg_ff0
+            // are the controller's segment as pfc_radau_set_controller gave it: the program writes the segment on the device,
+            // pfc_radau_clear_program and pfc_radau_set_state put it back.
+            struct Program : PartBlocks<PD_N, PI_N, false> {
                 bool on = false;
                 int n_ins = 0, body = 0, n_grip = 0;
                 double tau_soft = 0, tau_hard = 0;
-                DevBuf<double> pdbl;
-                DevBuf<int> pitg;
-                size_t od[4] = {0}, oi[2] = {0};  // offsets of the parts (RadauPD, RadauPI)
-                double *D(int part) const { return pdbl.p + od[part]; }
-                int *I(int part) const { return pitg.p + oi[part]; }
                 std::vector<double> seg_q0, seg_ff0;
             } prog;
         } ctl;
@@ -4892,1163 +4931,7 @@ int pfc_selftest_kis(pfc_handle h, int n, const double *Kbar36, const double *dK
     return PFC_OK;
 }
 
-// ---- parts of the Radau IIA step (pfc_radau.h; the constants: pfc_radau_tables.h, generated by scripts/radau_tables.py) ----------
-static_assert(PFC_MAX_NX_RADAU == kRadWave, "k_radau_factor and k_radau_newton run one lane per state");
-
-int pfc_radau_table(int rule, int *ns, double *c, double *A, double *lam, double *T, double *Tinv, double *bhat) {
-    if (rule < 1 || rule > 2) return PFC_ERR_BAD_ARG;
-    const RadauTableHost &t = kRadauTables[rule - 1];
-    const int s = t.ns;
-    if (ns) *ns = s;
-    if (c) std::memcpy(c, t.c, sizeof(double) * s);
-    if (A) std::memcpy(A, t.A, sizeof(double) * s * s);
-    if (lam) std::memcpy(lam, t.lam, sizeof(double) * 2 * s);
-    if (T) std::memcpy(T, t.T, sizeof(double) * 2 * s * s);
-    if (Tinv) std::memcpy(Tinv, t.Tinv, sizeof(double) * 2 * s * s);
-    if (bhat) { bhat[0] = t.bhat0; std::memcpy(bhat + 1, t.bhat, sizeof(double) * s); }
-    return PFC_OK;
-}
-
-// What the kernels read of a rule's table: columns 0 and 1 of T, rows 0 and 1 of T^-1 (the third of each is a conjugate).
-static RadauTab radau_tab(int rule) {
-    const RadauTableHost &t = kRadauTables[rule - 1];
-    const int s = t.ns;
-    RadauTab r;
-    std::memset(&r, 0, sizeof r);
-    for (int e = 0; e < s * s; ++e) r.A[e] = t.A[e];
-    r.lam0 = t.lam[0];
-    if (s > 1) { r.lam1_re = t.lam[2]; r.lam1_im = t.lam[3]; }
-    for (int k = 0; k < s; ++k) {
-        r.T0[k] = t.T[2 * (k * s)];
-        r.Ti0[k] = t.Tinv[2 * k];
-        if (s > 1) {
-            r.T1_re[k] = t.T[2 * (k * s + 1)]; r.T1_im[k] = t.T[2 * (k * s + 1) + 1];
-            r.Ti1_re[k] = t.Tinv[2 * (s + k)]; r.Ti1_im[k] = t.Tinv[2 * (s + k) + 1];
-        }
-    }
-    return r;
-}
-
-static int radau_check_nx(pfc_context *h, const char *who, int n_scene, int nx) {
-    if (n_scene < 0) return fail(h, PFC_ERR_BAD_ARG, "%s: negative n_scene", who);
-    if (nx < 1 || nx > PFC_MAX_NX_RADAU)
-        return fail(h, PFC_ERR_BAD_ARG, "%s: NX is %d, the step takes 1 .. PFC_MAX_NX_RADAU = %d states per scene", who, nx, PFC_MAX_NX_RADAU);
-    return PFC_OK;
-}
-
-// Every part is a launcher over a validated layout -- what the step's driver calls with the handle's own -- and a public entry that
-// runs on the first shard, validates (radau_layout, radau_chunk), refuses null buffers and calls the launcher.
-// The state layout every part but the factorisation takes, validated: NX = nq + nv + 6 n_br, the bristle items increasing and < n_ips.
-static int radau_layout(pfc_context *h, const char *who, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items,
-                        RadauLayout *L) {
-    const int rc = radau_check_nx(h, who, n_scene, nx);
-    if (rc != PFC_OK) return rc;
-    if (nq < 0 || nv < 0 || n_ips < 0 || n_br < 0 || n_br > kRadMaxBr || (long long)nq + nv + 6ll * n_br != nx)
-        return fail(h, PFC_ERR_BAD_ARG, "%s: NX = %d is not nq + nv + 6 bristle items (nq = %d, nv = %d, %d items)", who, nx, nq, nv, n_br);
-    if (n_br > 0 && !br_items) return fail(h, PFC_ERR_BAD_ARG, "%s: null bristle item list", who);
-    for (int k = 0; k < n_br; ++k)
-        if (br_items[k] < 0 || br_items[k] >= n_ips || (k > 0 && br_items[k] <= br_items[k - 1]))
-            return fail(h, PFC_ERR_BAD_ARG, "%s: bristle item %d is %d: the items are increasing and below n_ips = %d", who, k, br_items[k], n_ips);
-    if (n_ips > (1 << 24)) return fail(h, PFC_ERR_BAD_ARG, "%s: n_ips is %d, at most 2^24 items per scene", who, n_ips);
-    L->n_scene = n_scene; L->nx = nx; L->nq = nq; L->nv = nv; L->n_ips = n_ips; L->n_br = n_br;
-    for (int k = 0; k < kRadMaxBr; ++k) L->br_items[k] = k < n_br ? br_items[k] : 0;
-    return PFC_OK;
-}
-
-static unsigned radau_grid(size_t total) { return (unsigned)std::min<size_t>((total + kRadBlock - 1) / kRadBlock, 4096); }
-
-// The chunk's first state and its directions: chunk k of n_chunk-wide chunks covers states [k n_chunk, min((k + 1) n_chunk, NX)).
-static int radau_chunk(pfc_context *h, const char *who, int nx, int chunk, int n_chunk, int *j0, int *n_dir) {
-    if (n_chunk < 1 || n_chunk > 16) return fail(h, PFC_ERR_BAD_ARG, "%s: n_chunk is %d, 1 .. 16 directions per chunk", who, n_chunk);
-    if (chunk < 0 || (long long)chunk * n_chunk >= nx)
-        return fail(h, PFC_ERR_BAD_ARG, "%s: chunk %d of %d-wide chunks starts beyond NX = %d", who, chunk, n_chunk, nx);
-    *j0 = chunk * n_chunk;
-    *n_dir = std::min(n_chunk, nx - *j0);
-    return PFC_OK;
-}
-
-// Chunk directions [j0, j0 + n_dir) as unit seeds of q, v and s.
-static int radau_seed_launch(pfc_context *h, const RadauLayout &L, int j0, int n_dir, double *d_dq, double *d_dv, double *d_ds,
-                             hipStream_t st) {
-    HIP_TRY(h, hipSetDevice(h->device));
-    RadauSeedArgs a;
-    a.L = L; a.j0 = j0; a.n_dir = n_dir; a.dq = d_dq; a.dv = d_dv; a.ds = d_ds;
-    const size_t total = (size_t)L.n_scene * n_dir * (size_t)(L.nq + L.nv + 6 * L.n_ips);
-    hipLaunchKernelGGL(k_radau_seed, dim3(radau_grid(total)), dim3(kRadBlock), 0, st, a);
-    HIP_TRY(h, hipGetLastError());
-    return PFC_OK;
-}
-
-int pfc_radau_seed_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int chunk,
-                          int n_chunk, double *d_dq, double *d_dv, double *d_ds, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
-        const char *who = "pfc_radau_seed_device";
-        RadauLayout L;
-        int j0, n_dir;
-        int rc = radau_layout(c, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &L);
-        if (rc != PFC_OK || (rc = radau_chunk(c, who, nx, chunk, n_chunk, &j0, &n_dir)) != PFC_OK || n_scene == 0) return rc;
-        if ((nq > 0 && !d_dq) || (nv > 0 && !d_dv) || (n_ips > 0 && !d_ds)) return fail(c, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-        return radau_seed_launch(c, L, j0, n_dir, d_dq, d_dv, d_ds, stream ? (hipStream_t)stream : c->stream); });
-}
-
-// Columns [j0, j0 + n_dir) of -J from the chunk's partials; `first` (the chunk at j0 = 0) also takes xdot0 from the values.
-static int radau_jacobian_launch(pfc_context *h, const RadauLayout &L, int j0, int n_dir, const double *d_dqdot, const double *d_dvdot,
-                                 const double *d_dsdot, const double *d_qdot, const double *d_vdot, const double *d_sdot, double *d_neg_J,
-                                 double *d_xdot0, double *d_nstate, int *d_istate, hipStream_t st) {
-    HIP_TRY(h, hipSetDevice(h->device));
-    RadauJacArgs a;
-    a.L = L; a.j0 = j0; a.n_dir = n_dir; a.first = j0 == 0;
-    a.dqdot = d_dqdot; a.dvdot = d_dvdot; a.dsdot = d_dsdot; a.qdot = d_qdot; a.vdot = d_vdot; a.sdot = d_sdot;
-    a.neg_J = d_neg_J; a.xdot0 = d_xdot0; a.nstate = d_nstate; a.istate = d_istate;
-    const size_t total = (size_t)L.n_scene * (size_t)(n_dir + a.first) * (size_t)L.nx;
-    hipLaunchKernelGGL(k_radau_jac, dim3(radau_grid(total)), dim3(kRadBlock), 0, st, a);
-    HIP_TRY(h, hipGetLastError());
-    return PFC_OK;
-}
-
-int pfc_radau_jacobian_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int chunk,
-                              int n_chunk, const double *d_dqdot, const double *d_dvdot, const double *d_dsdot, const double *d_qdot,
-                              const double *d_vdot, const double *d_sdot, double *d_neg_J, double *d_xdot0, double *d_nstate,
-                              int *d_istate, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
-        const char *who = "pfc_radau_jacobian_device";
-        RadauLayout L;
-        int j0, n_dir;
-        int rc = radau_layout(c, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &L);
-        if (rc != PFC_OK || (rc = radau_chunk(c, who, nx, chunk, n_chunk, &j0, &n_dir)) != PFC_OK || n_scene == 0) return rc;
-        if ((nq > 0 && !d_dqdot) || (nv > 0 && !d_dvdot) || (n_br > 0 && !d_dsdot) || !d_neg_J ||
-            (chunk == 0 && ((nq > 0 && !d_qdot) || (nv > 0 && !d_vdot) || (n_br > 0 && !d_sdot) || !d_xdot0)))
-            return fail(c, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-        return radau_jacobian_launch(c, L, j0, n_dir, d_dqdot, d_dvdot, d_dsdot, d_qdot, d_vdot, d_sdot, d_neg_J, d_xdot0, d_nstate, d_istate,
-                                     stream ? (hipStream_t)stream : c->stream); });
-}
-
-// The stage states into the q, v and s of the 3 n_scene stage-scenes (k_radau_unpack).
-static int radau_unpack_launch(pfc_context *h, const RadauLayout &L, const double *d_x0, const int *d_rule, const int *d_istate, double *d_X,
-                               double *d_q, double *d_v, double *d_s, hipStream_t st) {
-    HIP_TRY(h, hipSetDevice(h->device));
-    RadauUnpackArgs a;
-    a.L = L; a.x0 = d_x0; a.rule = d_rule; a.istate = d_istate; a.X = d_X; a.q = d_q; a.v = d_v; a.s = d_s;
-    const size_t total = 3 * (size_t)L.n_scene * (size_t)(L.nq + L.nv + 6 * L.n_ips);
-    hipLaunchKernelGGL(k_radau_unpack, dim3(radau_grid(total)), dim3(kRadBlock), 0, st, a);
-    HIP_TRY(h, hipGetLastError());
-    return PFC_OK;
-}
-
-int pfc_radau_unpack_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items,
-                            const double *d_x0, const int *d_rule, const int *d_istate, double *d_X, double *d_q, double *d_v, double *d_s,
-                            void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
-        const char *who = "pfc_radau_unpack_device";
-        RadauLayout L;
-        const int rc = radau_layout(c, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &L);
-        if (rc != PFC_OK || n_scene == 0) return rc;
-        if (!d_x0 || !d_rule || !d_istate || !d_X || (nq > 0 && !d_q) || (nv > 0 && !d_v) || (n_ips > 0 && !d_s))
-            return fail(c, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-        return radau_unpack_launch(c, L, d_x0, d_rule, d_istate, d_X, d_q, d_v, d_s, stream ? (hipStream_t)stream : c->stream); });
-}
-
-// What k_radau_finish<true> takes beyond k_radau_finish<false>'s arguments (pfc_radau_finish_end_device).
-struct RadauEndBufs {
-    const double *t_final;
-    double *traj;
-    int *rows;
-    int max_rows;
-    int *live;
-};
-
-// What the finish parts take beside the layout and the buffers: the MRP offsets in q, {tol_a, tol_r, h_max, h_min} and the rule's bounds.
-struct RadauFinishRule {
-    int n_mrp;
-    const int *mrp_off;
-    const double *params;
-    int k_iter_max, max_rule, cooldown;
-};
-
-// Both finish parts: `end` null launches k_radau_finish<false>, else <true> with those buffers.
-static int radau_finish_launch(pfc_context *h, const RadauLayout &L, const RadauFinishRule &r, const RadauEndBufs *end, const double *d_F,
-                               const double *d_xdot0, const double *d_X, const double *d_lu0, const int *d_perm, double *d_x, double *d_t,
-                               double *d_h, int *d_rule, int *d_cool, double *d_enorm, double *d_nstate, int *d_istate, int *d_count,
-                               hipStream_t st) {
-    HIP_TRY(h, hipSetDevice(h->device));
-    RadauFinishArgs a;
-    a.L = L;
-    a.k_iter_max = r.k_iter_max; a.max_rule = r.max_rule; a.cooldown_reset = r.cooldown; a.n_mrp = r.n_mrp;
-    for (int m = 0; m < kRadMaxBr; ++m) a.mrp_off[m] = m < r.n_mrp ? r.mrp_off[m] : 0;
-    a.tol_a = r.params[0]; a.tol_r = r.params[1]; a.h_max = r.params[2]; a.h_min = r.params[3];
-    for (int r = 0; r < 2; ++r) {
-        const RadauTableHost &t = kRadauTables[r];
-        a.bhat0[r] = t.bhat0;
-        for (int k = 0; k < 3; ++k) { a.bhat[r][k] = t.bhat[k]; a.a_last[r][k] = k < t.ns ? t.A[(t.ns - 1) * t.ns + k] : 0.0; }
-    }
-    a.F = d_F; a.xdot0 = d_xdot0; a.X = d_X; a.lu0 = d_lu0; a.perm = d_perm;
-    a.x = d_x; a.t = d_t; a.h = d_h; a.rule = d_rule; a.cool = d_cool; a.enorm = d_enorm; a.nstate = d_nstate; a.istate = d_istate;
-    a.count = d_count;
-    a.t_final = end ? end->t_final : nullptr; a.traj = end ? end->traj : nullptr; a.rows = end ? end->rows : nullptr;
-    a.max_rows = end ? end->max_rows : 0; a.live = end ? end->live : nullptr;
-    HIP_TRY(h, hipMemsetAsync(d_count, 0, sizeof(int), st));
-    if (end) hipLaunchKernelGGL(k_radau_finish<true>, dim3((unsigned)L.n_scene), dim3(kRadWave), 0, st, a);
-    else hipLaunchKernelGGL(k_radau_finish<false>, dim3((unsigned)L.n_scene), dim3(kRadWave), 0, st, a);
-    HIP_TRY(h, hipGetLastError());
-    return PFC_OK;
-}
-
-// Both finish entries behind the forwarder: the layout, the rule's parameters and the buffers checked, then the launcher.
-static int radau_finish_checked(pfc_context *h, const char *who, const RadauEndBufs *end, int n_scene, int nx, int nq, int nv, int n_ips,
-                                int n_br, const int *br_items, const RadauFinishRule &r, const double *d_F, const double *d_xdot0,
-                                const double *d_X, const double *d_lu0, const int *d_perm, double *d_x, double *d_t, double *d_h,
-                                int *d_rule, int *d_cool, double *d_enorm, double *d_nstate, int *d_istate, int *d_count, void *stream) {
-    RadauLayout L;
-    const int rc = radau_layout(h, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &L);
-    if (rc != PFC_OK) return rc;
-    if (r.n_mrp < 0 || r.n_mrp > kRadMaxBr || (r.n_mrp > 0 && !r.mrp_off)) return fail(h, PFC_ERR_BAD_ARG, "%s: the list of MRP offsets", who);
-    for (int m = 0; m < r.n_mrp; ++m)
-        if (r.mrp_off[m] < 0 || r.mrp_off[m] + 3 > nq || (m > 0 && r.mrp_off[m] < r.mrp_off[m - 1] + 3))
-            return fail(h, PFC_ERR_BAD_ARG, "%s: MRP %d at q offset %d: increasing, disjoint and within nq = %d", who, m, r.mrp_off[m], nq);
-    if (!r.params || !(r.params[0] >= 0.0) || !(r.params[1] >= 0.0) || !(r.params[2] > 0.0) || !(r.params[3] > 0.0))
-        return fail(h, PFC_ERR_BAD_ARG, "%s: params are {tol_a >= 0, tol_r >= 0, h_max > 0, h_min > 0}", who);
-    if (r.k_iter_max < 1 || r.max_rule < 1 || r.max_rule > 2 || r.cooldown < 0)
-        return fail(h, PFC_ERR_BAD_ARG, "%s: k_iter_max >= 1, max_rule 1 or 2 (rules 3 - 6 are not built), cooldown >= 0", who);
-    if (end && (end->max_rows < 0 || end->max_rows == 1))
-        return fail(h, PFC_ERR_BAD_ARG, "%s: max_rows is %d: 0 (no recording) or at least 2", who, end->max_rows);
-    if (n_scene == 0) return PFC_OK;
-    if (!d_F || !d_xdot0 || !d_X || !d_lu0 || !d_perm || !d_x || !d_t || !d_h ||
-        !d_rule || !d_cool || !d_enorm || !d_nstate || !d_istate || !d_count ||
-        (end && (!end->live || (end->max_rows > 0 && (!end->traj || !end->rows)))))
-        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-    return radau_finish_launch(h, L, r, end, d_F, d_xdot0, d_X, d_lu0, d_perm, d_x, d_t, d_h, d_rule, d_cool, d_enorm, d_nstate, d_istate,
-                               d_count, stream ? (hipStream_t)stream : h->stream);
-}
-
-int pfc_radau_finish_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int n_mrp,
-                            const int *mrp_off, const double *params, int k_iter_max, int max_rule, int cooldown,
-                            const double *d_F, const double *d_xdot0, const double *d_X,
-                            const double *d_lu0, const int *d_perm, double *d_x, double *d_t, double *d_h, int *d_rule, int *d_cool,
-                            double *d_enorm, double *d_nstate, int *d_istate, int *d_count, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    const RadauFinishRule r{n_mrp, mrp_off, params, k_iter_max, max_rule, cooldown};
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        return radau_finish_checked(c, "pfc_radau_finish_device", nullptr, n_scene, nx, nq, nv, n_ips, n_br, br_items, r, d_F, d_xdot0, d_X,
-                                    d_lu0, d_perm, d_x, d_t, d_h, d_rule, d_cool, d_enorm, d_nstate, d_istate, d_count, stream); });
-}
-
-int pfc_radau_finish_end_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items, int n_mrp,
-                                const int *mrp_off, const double *params, int k_iter_max, int max_rule, int cooldown,
-                                const double *d_F, const double *d_xdot0, const double *d_X,
-                                const double *d_lu0, const int *d_perm, double *d_x, double *d_t, double *d_h, int *d_rule, int *d_cool,
-                                double *d_enorm, double *d_nstate, int *d_istate, int *d_count, const double *d_t_final, double *d_traj,
-                                int *d_rows, int max_rows, int *d_live, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    const RadauEndBufs end{d_t_final, d_traj, d_rows, max_rows, d_live};
-    const RadauFinishRule r{n_mrp, mrp_off, params, k_iter_max, max_rule, cooldown};
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        return radau_finish_checked(c, "pfc_radau_finish_end_device", &end, n_scene, nx, nq, nv, n_ips, n_br, br_items, r, d_F, d_xdot0, d_X,
-                                    d_lu0, d_perm, d_x, d_t, d_h, d_rule, d_cool, d_enorm, d_nstate, d_istate, d_count, stream); });
-}
-
-static int radau_factor_launch(pfc_context *h, int n_scene, int nx, const double *d_neg_J, const double *d_h, const int *d_rule,
-                               const int *d_active, int active_stride, double *d_lu0, double *d_lu1, int *d_perm, int *d_info,
-                               hipStream_t st) {
-    HIP_TRY(h, hipSetDevice(h->device));
-    RadauFactorArgs a;
-    a.n_scene = n_scene; a.nx = nx; a.neg_J = d_neg_J; a.h = d_h; a.rule = d_rule; a.active = d_active; a.active_stride = active_stride;
-    a.lam0[0] = kRadauTables[0].lam[0]; a.lam0[1] = kRadauTables[1].lam[0];
-    a.lam1_re = kRadauTables[1].lam[2]; a.lam1_im = kRadauTables[1].lam[3];
-    a.lu0 = d_lu0; a.lu1 = d_lu1; a.perm = d_perm; a.info = d_info;
-    // one size for both factors: see k_radau_factor
-    hipLaunchKernelGGL(k_radau_factor, dim3(2u * (unsigned)n_scene), dim3(kRadWave), sizeof(RadC) * (size_t)nx * (size_t)nx, st, a);
-    HIP_TRY(h, hipGetLastError());
-    return PFC_OK;
-}
-
-int pfc_radau_factor_device(pfc_handle h, int n_scene, int nx, const double *d_neg_J, const double *d_h, const int *d_rule,
-                            const int *d_active, double *d_lu0, double *d_lu1, int *d_perm, int *d_info, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
-        const char *who = "pfc_radau_factor_device";
-        const int rc = radau_check_nx(c, who, n_scene, nx);
-        if (rc != PFC_OK || n_scene == 0) return rc;
-        if (!d_neg_J || !d_h || !d_rule || !d_lu0 || !d_lu1 || !d_perm || !d_info) return fail(c, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-        return radau_factor_launch(c, n_scene, nx, d_neg_J, d_h, d_rule, d_active, 1, d_lu0, d_lu1, d_perm, d_info,
-                                   stream ? (hipStream_t)stream : c->stream); });
-}
-
-// One pass of simple_newton! over the scenes that iterate; *d_count receives how many still do.
-static int radau_newton_launch(pfc_context *h, const RadauLayout &L, const double *d_qdot, const double *d_vdot, const double *d_sdot,
-                               const double *d_x0, const double *d_h, const int *d_rule, const double *d_lu0, const double *d_lu1,
-                               const int *d_perm, const int *d_info, double tol_newton, int k_iter_max, double *d_X, double *d_F_save,
-                               double *d_nstate, int *d_istate, int *d_count, hipStream_t st) {
-    HIP_TRY(h, hipSetDevice(h->device));
-    RadauNewtonArgs a;
-    a.L = L;
-    a.k_iter_max = k_iter_max;
-    a.tol_newton = tol_newton;
-    a.qdot = d_qdot; a.vdot = d_vdot; a.sdot = d_sdot; a.x0 = d_x0; a.h = d_h; a.rule = d_rule;
-    a.lu0 = d_lu0; a.lu1 = d_lu1; a.perm = d_perm; a.info = d_info;
-    a.tab[0] = radau_tab(1); a.tab[1] = radau_tab(2);
-    a.X = d_X; a.F_save = d_F_save; a.nstate = d_nstate; a.istate = d_istate; a.count = d_count;
-    HIP_TRY(h, hipMemsetAsync(d_count, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_radau_newton, dim3((unsigned)L.n_scene), dim3(kRadWave), 0, st, a);
-    HIP_TRY(h, hipGetLastError());
-    return PFC_OK;
-}
-
-int pfc_radau_newton_device(pfc_handle h, int n_scene, int nx, int nq, int nv, int n_ips, int n_br, const int *br_items,
-                            const double *d_qdot, const double *d_vdot, const double *d_sdot, const double *d_x0, const double *d_h,
-                            const int *d_rule, const double *d_lu0, const double *d_lu1, const int *d_perm, const int *d_info,
-                            double tol_newton, int k_iter_max, double *d_X, double *d_F_save, double *d_nstate, int *d_istate, int *d_count,
-                            void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) -> int {
-        const char *who = "pfc_radau_newton_device";
-        RadauLayout L;
-        const int rc = radau_layout(c, who, n_scene, nx, nq, nv, n_ips, n_br, br_items, &L);
-        if (rc != PFC_OK) return rc;
-        if (!(tol_newton >= 0.0) || k_iter_max < 1) return fail(c, PFC_ERR_BAD_ARG, "%s: tol_newton or k_iter_max", who);
-        if (n_scene == 0) return PFC_OK;
-        if ((nq > 0 && !d_qdot) || (nv > 0 && !d_vdot) || (n_br > 0 && !d_sdot) || !d_x0 || !d_h || !d_rule || !d_lu0 || !d_lu1 || !d_perm ||
-            !d_info || !d_X || !d_nstate || !d_istate || !d_count)
-            return fail(c, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-        return radau_newton_launch(c, L, d_qdot, d_vdot, d_sdot, d_x0, d_h, d_rule, d_lu0, d_lu1, d_perm, d_info, tol_newton, k_iter_max, d_X,
-                                   d_F_save, d_nstate, d_istate, d_count, stream ? (hipStream_t)stream : c->stream); });
-}
-
-// ---- the Radau IIA step: configuration, state and the driver (solveRadau, src/radau/radau_solve.jl:2-30) -----------------------
-// Parts of the handle's two blocks.  The value buffers (RD_V*, RI_V*) are those of pfc_state_derivative_device on the 3 n_scene
-// stage-scenes; the Jacobian chunks run on the first n_scene of them -- before the first attempt every stage-scene holds x0 -- and
-// write their value outputs there as well, so only the partials (RD_DD*) have buffers of their own.
-enum RadauD { RD_X, RD_T, RD_H, RD_ENORM, RD_NSTATE, RD_XS, RD_FS, RD_XDOT0, RD_NEGJ, RD_LU0, RD_LU1, RD_TAU,
-              RD_VQ, RD_VV, RD_VS, RD_VXWB, RD_VTW, RD_VJAC, RD_VPOSE, RD_VTWI, RD_VXR2, RD_VWR, RD_VSD, RD_VF, RD_VQD, RD_VH, RD_VC, RD_VVD,
-              RD_DDQ, RD_DDV, RD_DDS, RD_DDXWB, RD_DDTW, RD_DDJAC, RD_DDPOSE, RD_DDTWI, RD_DDXR2, RD_DDWR, RD_DDSD, RD_DDF, RD_DDQD, RD_DDH,
-              RD_DDC, RD_DDVD, RD_TFINAL, RD_N };
-// RI_COUNT has two words: the count a newton or finish part returns, and the scenes live after a batch step (k_radau_finish<true>).
-enum RadauI { RI_RULE, RI_COOL, RI_ISTATE, RI_PERM, RI_INFO, RI_COUNT, RI_VINS, RI_VSC, RI_VB1, RI_VB2, RI_VCNT, RI_VINFO, RI_ROWS, RI_N };
-// Parts of the controller's two blocks (pfc_radau_set_controller).
-enum RadauCD { CD_KP, CD_KD, CD_AMAX, CD_SEGT, CD_SEGQ, CD_SEGFF, CD_TLAST, CD_N };
-enum RadauCI { CI_ACT, CI_FIRES, CI_N };
-// Parts of the program's two blocks (pfc_radau_set_program).
-enum RadauPD { PD_DT, PD_Q, PD_SLIP, PD_STATE, PD_N };
-enum RadauPI { PI_GRIP, PI_CURSOR, PI_N };
-static int radau_program_reset(pfc_context *c);
-
-static int radau_configure_ctx(pfc_context *c, int n_scene, int n_ips, const int *ins_ids, const double *params, int k_iter_max,
-                               int max_rule, int n_chunk, int cooldown) {
-    const char *who = "pfc_radau_configure";
-    pfc_context::RadauHost &R = c->radau;
-    if (!c->finalized) return fail(c, PFC_ERR_STATE, "%s before pfc_finalize", who);
-    if (n_chunk < 1 || n_chunk > 16) return fail(c, PFC_ERR_BAD_ARG, "%s: n_chunk is %d, 1 .. 16 directions per chunk", who, n_chunk);
-    if (n_scene < 1 || n_scene > (1 << 20)) return fail(c, PFC_ERR_BAD_ARG, "%s: n_scene is %d", who, n_scene);
-    int rc = state_derivative_dual_check(c, who, n_scene, n_chunk);      // the mechanism, its inertias, the nv cap, the Dual LDS limit
-    if (rc != PFC_OK) return rc;
-    if (max_rule < 1 || max_rule > 2) return fail(c, PFC_ERR_BAD_ARG, "%s: max_rule is %d: rules 1 and 2 only (3 - 6 are not built)", who, max_rule);
-    if (n_ips < 1 || n_ips > 4096 || !ins_ids) return fail(c, PFC_ERR_BAD_ARG, "%s: 1 .. 4096 items per scene and their instruction ids", who);
-    static const double defaults[6] = {1e-4, 1e-4, 1e-4, 1e-16, 0.01, 1e-8};      // h0, tol_a, tol_r, tol_newton, h_max, h_min
-    const double *p = params ? params : defaults;
-    if (!(p[0] > 0.0) || !(p[1] >= 0.0) || !(p[2] >= 0.0) || !(p[3] >= 0.0) || !(p[4] > 0.0) || !(p[5] > 0.0) || !std::isfinite(p[0]) ||
-        k_iter_max < 1 || cooldown < 0)
-        return fail(c, PFC_ERR_BAD_ARG, "%s: h0, h_max, h_min > 0, the tolerances >= 0, k_iter_max >= 1, cooldown >= 0", who);
-    const KinHost &K = c->kin;
-    // the step counts items, bodies and their rows in int: 3 n_scene n_ips items and 3 n_scene n_body bodies, 24 words a row at most
-    if (3ll * n_scene * (long long)std::max(n_ips, K.n_body) > (long long)std::numeric_limits<int>::max() / 24)
-        return fail(c, PFC_ERR_BAD_ARG, "%s: 3 n_scene x max(n_ips, n_body) = 3 x %d x %d is beyond what the step indexes (INT_MAX / 24)", who,
-                    n_scene, std::max(n_ips, K.n_body));
-    std::vector<int> br;
-    for (int k = 0; k < n_ips; ++k) {
-        if (ins_ids[k] < 0 || ins_ids[k] >= (int)c->ins.size())
-            return fail(c, PFC_ERR_BAD_ARG, "%s: item %d uses instruction %d, the scenario has %d", who, k, ins_ids[k], (int)c->ins.size());
-        if (c->ins[ins_ids[k]].model == PFC_BRISTLE) br.push_back(k);
-    }
-    const long long nx = (long long)K.nq + K.nv + 6ll * (long long)br.size();
-    if (nx < 1 || nx > PFC_MAX_NX_RADAU)
-        return fail(c, PFC_ERR_BAD_ARG, "%s: NX = nq + nv + 6 bristle items = %d + %d + 6 x %d = %lld, at most PFC_MAX_NX_RADAU = %d", who, K.nq,
-                    K.nv, (int)br.size(), nx, PFC_MAX_NX_RADAU);
-    RadauLayout L;
-    rc = radau_layout(c, who, n_scene, (int)nx, K.nq, K.nv, n_ips, (int)br.size(), br.data(), &L);
-    if (rc != PFC_OK) return rc;
-    R.configured = false; R.has_state = false; R.has_tau = false;
-    R.L = L; R.n_chunk = n_chunk; R.k_iter_max = k_iter_max; R.max_rule = max_rule; R.cooldown = cooldown;
-    R.h0 = p[0]; R.tol_newton = p[3]; R.fin[0] = p[1]; R.fin[1] = p[2]; R.fin[2] = p[4]; R.fin[3] = p[5];
-    R.n_mrp = 0;
-    const int *jtype = (const int *)(K.blob.data() + K.o_jtype), *qoff = (const int *)(K.blob.data() + K.o_qoff);
-    for (int b = 0; b < K.n_body; ++b)
-        if (jtype[b] == PFC_JOINT_FLOATING_MRP && R.n_mrp < kRadMaxBr) R.mrp_off[R.n_mrp++] = qoff[b];
-    const size_t ns = (size_t)n_scene, N3 = 3 * ns, n3 = N3 * (size_t)n_ips, n1 = ns * (size_t)n_ips, nd = (size_t)n_chunk, nb = (size_t)K.n_body;
-    const size_t n = (size_t)nx, nq = (size_t)K.nq, nv = (size_t)K.nv;
-    size_t sd[RD_N], si[RI_N];
-    sd[RD_X] = ns * n; sd[RD_T] = ns; sd[RD_H] = ns; sd[RD_ENORM] = 2 * ns; sd[RD_NSTATE] = 8 * ns; sd[RD_XS] = N3 * n; sd[RD_FS] = N3 * n; sd[RD_XDOT0] = ns * n;
-    sd[RD_NEGJ] = ns * n * n; sd[RD_LU0] = ns * n * n; sd[RD_LU1] = 2 * ns * n * n; sd[RD_TAU] = N3 * nv;
-    sd[RD_VQ] = N3 * nq; sd[RD_VV] = N3 * nv; sd[RD_VS] = n3 * 6; sd[RD_VXWB] = N3 * nb * 12; sd[RD_VTW] = N3 * nb * 6; sd[RD_VJAC] = N3 * nb * nv * 6;
-    sd[RD_VPOSE] = n3 * 24; sd[RD_VTWI] = n3 * 6; sd[RD_VXR2] = n3 * 12; sd[RD_VWR] = n3 * 6; sd[RD_VSD] = n3 * 6; sd[RD_VF] = N3 * nv;
-    sd[RD_VQD] = N3 * nq; sd[RD_VH] = N3 * nv * nv; sd[RD_VC] = N3 * nv; sd[RD_VVD] = N3 * nv;
-    sd[RD_DDQ] = ns * nd * nq; sd[RD_DDV] = ns * nd * nv; sd[RD_DDS] = n1 * nd * 6; sd[RD_DDXWB] = ns * nb * nd * 12; sd[RD_DDTW] = ns * nb * nd * 6;
-    sd[RD_DDJAC] = ns * nb * nd * nv * 6; sd[RD_DDPOSE] = n1 * nd * 24; sd[RD_DDTWI] = n1 * nd * 6; sd[RD_DDXR2] = n1 * nd * 12;
-    sd[RD_DDWR] = n1 * nd * 6; sd[RD_DDSD] = n1 * nd * 6; sd[RD_DDF] = ns * nd * nv; sd[RD_DDQD] = ns * nd * nq; sd[RD_DDH] = ns * nd * nv * nv;
-    sd[RD_DDC] = ns * nd * nv; sd[RD_DDVD] = ns * nd * nv; sd[RD_TFINAL] = ns;
-    si[RI_RULE] = ns; si[RI_COOL] = ns; si[RI_ISTATE] = 8 * ns; si[RI_PERM] = 2 * ns * n; si[RI_INFO] = 2 * ns; si[RI_COUNT] = 2;
-    si[RI_VINS] = n3; si[RI_VSC] = n3; si[RI_VB1] = n3; si[RI_VB2] = n3; si[RI_VCNT] = 4 * n3; si[RI_VINFO] = N3; si[RI_ROWS] = ns;
-    R.od.assign(RD_N, 0); R.oi.assign(RI_N, 0);
-    size_t td = 0, ti = 0;
-    for (int k = 0; k < RD_N; ++k) { R.od[k] = td; td += (std::max<size_t>(sd[k], 1) + 31) & ~(size_t)31; }
-    for (int k = 0; k < RI_N; ++k) { R.oi[k] = ti; ti += (std::max<size_t>(si[k], 1) + 63) & ~(size_t)63; }
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    R.drop_end();
-    R.drop_control();
-    HIP_TRY(c, R.dbl.ensure(td));
-    HIP_TRY(c, R.itg.ensure(ti));
-    HIP_TRY(c, hipMemset(R.dbl.p, 0, sizeof(double) * td));
-    HIP_TRY(c, hipMemset(R.itg.p, 0, sizeof(int) * ti));
-    std::vector<int> tab(2 * n3);
-    for (size_t ss = 0; ss < N3; ++ss)
-        for (int k = 0; k < n_ips; ++k) { tab[ss * n_ips + k] = ins_ids[k]; tab[n3 + ss * n_ips + k] = (int)ss; }
-    HIP_TRY(c, hipMemcpy(R.itg.p + R.oi[RI_VINS], tab.data(), sizeof(int) * n3, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(R.itg.p + R.oi[RI_VSC], tab.data() + n3, sizeof(int) * n3, hipMemcpyHostToDevice));
-    R.configured = true;
-    return PFC_OK;
-}
-
-int pfc_radau_configure(pfc_handle h, int n_scene, int n_ips, const int *ins_ids, const double *params, int k_iter_max, int max_rule,
-                        int n_chunk, int cooldown) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        return radau_configure_ctx(c, n_scene, n_ips, ins_ids, params, k_iter_max, max_rule, n_chunk, cooldown); });
-}
-
-static int radau_need(pfc_context *c, const char *who, bool state) {
-    if (!c->radau.configured) return fail(c, PFC_ERR_STATE, "%s before pfc_radau_configure", who);
-    if (state && !c->radau.has_state) return fail(c, PFC_ERR_STATE, "%s before pfc_radau_set_state", who);
-    return PFC_OK;
-}
-
-int pfc_radau_sizes(pfc_handle h, int *nx, int *n_bristle, int *bristle_items) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        const int rc = radau_need(c, "pfc_radau_sizes", false);
-        if (rc != PFC_OK) return rc;
-        const RadauLayout &L = c->radau.L;
-        if (nx) *nx = L.nx;
-        if (n_bristle) *n_bristle = L.n_br;
-        if (bristle_items) for (int k = 0; k < L.n_br; ++k) bristle_items[k] = L.br_items[k];
-        return (int)PFC_OK; });
-}
-
-int pfc_radau_set_state(pfc_handle h, const double *x, const double *t) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        const char *who = "pfc_radau_set_state";
-        int rc = radau_need(c, who, false);
-        if (rc != PFC_OK) return rc;
-        if (!x) return fail(c, PFC_ERR_BAD_ARG, "%s: null state", who);
-        pfc_context::RadauHost &R = c->radau;
-        const size_t ns = (size_t)R.L.n_scene, n = (size_t)R.L.nx;
-        for (size_t e = 0; e < ns * n; ++e)
-            if (!std::isfinite(x[e])) return fail(c, PFC_ERR_NONFINITE, "%s: x of scene %zu is not finite", who, e / n);
-        const double inf = std::numeric_limits<double>::infinity();
-        std::vector<double> hh(ns, R.h0), tt(ns, 0.0), en(2 * ns, -9999.0), nst(8 * ns, 0.0);
-        std::vector<int> rule(ns, 1), cool(ns, R.cooldown), ist(8 * ns, 0);
-        for (size_t s = 0; s < ns; ++s) {
-            if (t) tt[s] = t[s];
-            double *a = nst.data() + 8 * s;
-            a[kRadTheta] = -9999.0; a[kRadThetaPrev] = -9999.0; a[kRadPsi] = 9999.0; a[kRadRes1] = inf; a[kRadRes2] = inf;
-            ist[8 * s + kRadFlag] = -1; ist[8 * s + kRadExit] = -9999;
-        }
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        double *D = R.dbl.p; int *I = R.itg.p;
-        HIP_TRY(c, hipMemcpy(D + R.od[RD_X], x, sizeof(double) * ns * n, hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(D + R.od[RD_T], tt.data(), sizeof(double) * ns, hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(D + R.od[RD_H], hh.data(), sizeof(double) * ns, hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(D + R.od[RD_ENORM], en.data(), sizeof(double) * 2 * ns, hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(D + R.od[RD_NSTATE], nst.data(), sizeof(double) * 8 * ns, hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(I + R.oi[RI_RULE], rule.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(I + R.oi[RI_COOL], cool.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(I + R.oi[RI_ISTATE], ist.data(), sizeof(int) * 8 * ns, hipMemcpyHostToDevice));
-        R.drop_end();      // no scene is parked, and an end that was set is gone with the trajectory that started at the old state
-        if (R.ctl.on) {    // law and schedule stay; the controller's clock starts again
-            const std::vector<int> zero(ns, 0);
-            HIP_TRY(c, hipMemcpy(R.ctl.cdbl.p + R.ctl.od[CD_TLAST], R.ctl.has_t0 ? R.ctl.t_last0.data() : tt.data(), sizeof(double) * ns,
-                                 hipMemcpyHostToDevice));
-            HIP_TRY(c, hipMemcpy(R.ctl.citg.p + R.ctl.oi[CI_FIRES], zero.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
-            if (R.ctl.prog.on && (rc = radau_program_reset(c)) != PFC_OK) return rc;      // the program stays; its records start again
-        }
-        R.has_state = true;
-        return (int)PFC_OK; });
-}
-
-int pfc_radau_set_rule_state(pfc_handle h, const double *h_scene, const int *rule, const int *cooldown) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        const char *who = "pfc_radau_set_rule_state";
-        const int rc = radau_need(c, who, true);
-        if (rc != PFC_OK) return rc;
-        pfc_context::RadauHost &R = c->radau;
-        const size_t ns = (size_t)R.L.n_scene;
-        for (size_t s = 0; s < ns; ++s) {
-            if (h_scene && !(h_scene[s] > 0.0 && std::isfinite(h_scene[s]))) return fail(c, PFC_ERR_BAD_ARG, "%s: h of scene %zu is %.17g", who, s, h_scene[s]);
-            if (rule && (rule[s] < 1 || rule[s] > R.max_rule)) return fail(c, PFC_ERR_BAD_ARG, "%s: rule of scene %zu is %d, 1 .. max_rule = %d", who, s, rule[s], R.max_rule);
-            if (cooldown && cooldown[s] < 0) return fail(c, PFC_ERR_BAD_ARG, "%s: cooldown of scene %zu is %d", who, s, cooldown[s]);
-        }
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (h_scene) HIP_TRY(c, hipMemcpy(R.dbl.p + R.od[RD_H], h_scene, sizeof(double) * ns, hipMemcpyHostToDevice));
-        if (rule) HIP_TRY(c, hipMemcpy(R.itg.p + R.oi[RI_RULE], rule, sizeof(int) * ns, hipMemcpyHostToDevice));
-        if (cooldown) HIP_TRY(c, hipMemcpy(R.itg.p + R.oi[RI_COOL], cooldown, sizeof(int) * ns, hipMemcpyHostToDevice));
-        return (int)PFC_OK; });
-}
-
-int pfc_radau_get_state(pfc_handle h, double *x, double *t) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        const int rc = radau_need(c, "pfc_radau_get_state", true);
-        if (rc != PFC_OK) return rc;
-        pfc_context::RadauHost &R = c->radau;
-        const size_t ns = (size_t)R.L.n_scene, n = (size_t)R.L.nx;
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (x) HIP_TRY(c, hipMemcpy(x, R.dbl.p + R.od[RD_X], sizeof(double) * ns * n, hipMemcpyDeviceToHost));
-        if (t) HIP_TRY(c, hipMemcpy(t, R.dbl.p + R.od[RD_T], sizeof(double) * ns, hipMemcpyDeviceToHost));
-        return (int)PFC_OK; });
-}
-
-int pfc_radau_set_tau(pfc_handle h, const double *tau) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        const int rc = radau_need(c, "pfc_radau_set_tau", false);
-        if (rc != PFC_OK) return rc;
-        pfc_context::RadauHost &R = c->radau;
-        const size_t ns = (size_t)R.L.n_scene, nv = (size_t)R.L.nv;
-        R.has_tau = tau != nullptr && nv > 0;
-        if (!R.has_tau && R.ctl.on) {      // with a controller the step reads RD_TAU: NULL means zeros there as well
-            HIP_TRY(c, hipSetDevice(c->device));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            HIP_TRY(c, hipMemset(R.dbl.p + R.od[RD_TAU], 0, sizeof(double) * 3 * ns * nv));
-        }
-        if (!R.has_tau) return (int)PFC_OK;
-        for (size_t e = 0; e < ns * nv; ++e)
-            if (!std::isfinite(tau[e])) return fail(c, PFC_ERR_NONFINITE, "pfc_radau_set_tau: tau of scene %zu is not finite", e / nv);
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (int k = 0; k < 3; ++k)      // the same tau for the three stage-scenes of a scene
-            HIP_TRY(c, hipMemcpy(R.dbl.p + R.od[RD_TAU] + (size_t)k * ns * nv, tau, sizeof(double) * ns * nv, hipMemcpyHostToDevice));
-        return (int)PFC_OK; });
-}
-
-int pfc_radau_get_tau(pfc_handle h, double *tau) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        const int rc = radau_need(c, "pfc_radau_get_tau", false);
-        if (rc != PFC_OK) return rc;
-        if (!tau) return fail(c, PFC_ERR_BAD_ARG, "pfc_radau_get_tau: null buffer");
-        pfc_context::RadauHost &R = c->radau;
-        const size_t n = 3 * (size_t)R.L.n_scene * (size_t)R.L.nv;
-        if (!R.has_tau && !R.ctl.on) { std::fill(tau, tau + n, 0.0); return (int)PFC_OK; }      // the step reads no tau: zeros
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, hipMemcpy(tau, R.dbl.p + R.od[RD_TAU], sizeof(double) * n, hipMemcpyDeviceToHost));
-        return (int)PFC_OK; });
-}
-
-int pfc_radau_rule_state(pfc_handle h, double *out7) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        const int rc = radau_need(c, "pfc_radau_rule_state", true);
-        if (rc != PFC_OK) return rc;
-        if (!out7) return fail(c, PFC_ERR_BAD_ARG, "pfc_radau_rule_state: null buffer");
-        pfc_context::RadauHost &R = c->radau;
-        const size_t ns = (size_t)R.L.n_scene;
-        std::vector<double> hh(ns), en(2 * ns), nst(8 * ns);
-        std::vector<int> rule(ns), cool(ns);
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, hipMemcpy(hh.data(), R.dbl.p + R.od[RD_H], sizeof(double) * ns, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(en.data(), R.dbl.p + R.od[RD_ENORM], sizeof(double) * 2 * ns, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(nst.data(), R.dbl.p + R.od[RD_NSTATE], sizeof(double) * 8 * ns, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(rule.data(), R.itg.p + R.oi[RI_RULE], sizeof(int) * ns, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(cool.data(), R.itg.p + R.oi[RI_COOL], sizeof(int) * ns, hipMemcpyDeviceToHost));
-        for (size_t s = 0; s < ns; ++s) {
-            double *o = out7 + 7 * s;
-            o[0] = hh[s]; o[1] = rule[s]; o[2] = cool[s]; o[3] = nst[8 * s + kRadTheta]; o[4] = nst[8 * s + kRadPsi];
-            o[5] = en[2 * s]; o[6] = en[2 * s + 1];
-        }
-        return (int)PFC_OK; });
-}
-
-// ---- the discrete controller (k_radau_control; the statement: include/pfc.h) ---------------------------------------------------------
-static_assert(PFC_RADAU_MAX_FIRES == kRadMaxFires, "the bound of k_radau_control's t_last loop");
-
-static int radau_control_launch(pfc_context *h, const char *who, int n_scene, int nq, int nv, int n_act, int n_seg, double dt,
-                                const int *d_act, const double *d_kp, const double *d_kd, const double *d_a_max, const double *d_seg_t,
-                                const double *d_seg_q, const double *d_seg_ff, const double *d_t, const double *d_q, const double *d_v,
-                                const double *d_H, const double *d_c, const int *d_istate, double *d_t_last, int *d_fires, double *d_tau,
-                                hipStream_t st) {
-    if (n_scene < 0) return fail(h, PFC_ERR_BAD_ARG, "%s: negative n_scene", who);
-    if (nv < 1 || nv > PFC_MAX_NV_SOLVE || nq < 1 || nq > kRadWave)
-        return fail(h, PFC_ERR_BAD_ARG, "%s: nv is %d and nq %d, the law takes 1 .. PFC_MAX_NV_SOLVE = %d coordinates", who, nv, nq, PFC_MAX_NV_SOLVE);
-    if (n_act < 0 || n_act > std::min(nq, nv)) return fail(h, PFC_ERR_BAD_ARG, "%s: n_act is %d, 0 .. min(nq, nv) = %d", who, n_act, std::min(nq, nv));
-    if (n_seg < 1) return fail(h, PFC_ERR_BAD_ARG, "%s: n_seg is %d, at least one segment", who, n_seg);
-    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(h, PFC_ERR_BAD_ARG, "%s: dt is %.17g, finite and > 0", who, dt);
-    if (n_scene == 0) return PFC_OK;
-    if ((n_act > 0 && (!d_act || !d_kp || !d_kd || !d_a_max || !d_seg_q || !d_q || !d_H || !d_c)) || (n_seg > 1 && !d_seg_t) || !d_t ||
-        !d_v || !d_t_last || !d_fires || !d_tau)
-        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-    HIP_TRY(h, hipSetDevice(h->device));
-    RadauControlArgs a;
-    a.n_scene = n_scene; a.nq = nq; a.nv = nv; a.n_act = n_act; a.n_seg = n_seg; a.dt = dt;
-    a.act = d_act; a.kp = d_kp; a.kd = d_kd; a.a_max = d_a_max; a.seg_t = d_seg_t; a.seg_q = d_seg_q; a.seg_ff = d_seg_ff;
-    a.t = d_t; a.q = d_q; a.v = d_v; a.H = d_H; a.c = d_c; a.istate = d_istate; a.t_last = d_t_last; a.fires = d_fires; a.tau = d_tau;
-    hipLaunchKernelGGL(k_radau_control, dim3((unsigned)n_scene), dim3(kRadWave), 0, st, a);
-    HIP_TRY(h, hipGetLastError());
-    return PFC_OK;
-}
-
-int pfc_radau_control_device(pfc_handle h, int n_scene, int nq, int nv, int n_act, int n_seg, double dt, const int *d_act,
-                             const double *d_kp, const double *d_kd, const double *d_a_max, const double *d_seg_t, const double *d_seg_q,
-                             const double *d_seg_ff, const double *d_t, const double *d_q, const double *d_v, const double *d_H,
-                             const double *d_c, const int *d_istate, double *d_t_last, int *d_fires, double *d_tau, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        return radau_control_launch(c, "pfc_radau_control_device", n_scene, nq, nv, n_act, n_seg, dt, d_act, d_kp, d_kd, d_a_max, d_seg_t,
-                                    d_seg_q, d_seg_ff, d_t, d_q, d_v, d_H, d_c, d_istate, d_t_last, d_fires, d_tau,
-                                    stream ? (hipStream_t)stream : c->stream); });
-}
-
-// tau lives in RD_TAU while a controller is set; without pfc_radau_set_tau's array the block must read as zeros.
-static int radau_zero_tau_unless_set(pfc_context *c) {
-    pfc_context::RadauHost &R = c->radau;
-    if (R.has_tau) return PFC_OK;
-    HIP_TRY(c, hipMemset(R.dbl.p + R.od[RD_TAU], 0, sizeof(double) * 3 * (size_t)R.L.n_scene * (size_t)R.L.nv));
-    return PFC_OK;
-}
-
-static int radau_set_controller_ctx(pfc_context *c, int n_act, const int *act, const double *kp, const double *kd, const double *a_max,
-                                    double dt, const double *t_last0, int n_seg, const double *seg_t, const double *seg_q,
-                                    const double *seg_ff) {
-    const char *who = "pfc_radau_set_controller";
-    int rc = radau_need(c, who, false);
-    if (rc != PFC_OK) return rc;
-    pfc_context::RadauHost &R = c->radau;
-    const KinHost &K = c->kin;
-    const size_t ns = (size_t)R.L.n_scene, nv = (size_t)R.L.nv;
-    if (n_act == 0 && n_seg == 0 && !act && !kp && !kd && !a_max && !t_last0 && !seg_t && !seg_q && !seg_ff) {      // the clearing form
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        R.drop_control();
-        return radau_zero_tau_unless_set(c);
-    }
-    if (R.L.nv < 1 || R.L.nq != R.L.nv)
-        return fail(c, PFC_ERR_BAD_ARG, "%s: the mechanism has nq = %d and nv = %d: the law needs coordinates, the same in q and v", who, R.L.nq, R.L.nv);
-    if (n_act < 0 || n_act > R.L.nv || (n_act > 0 && (!act || !kp || !kd || !seg_q)))
-        return fail(c, PFC_ERR_BAD_ARG, "%s: n_act is %d (0 .. nv = %d) with act, kp, kd and seg_q given", who, n_act, R.L.nv);
-    if (n_seg < 1 || (n_seg > 1 && !seg_t)) return fail(c, PFC_ERR_BAD_ARG, "%s: n_seg is %d: at least one segment, with its start times", who, n_seg);
-    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(c, PFC_ERR_BAD_ARG, "%s: dt is %.17g, finite and > 0", who, dt);
-    if (dt * (double)PFC_RADAU_MAX_FIRES < R.fin[2])
-        return fail(c, PFC_ERR_BAD_ARG, "%s: dt is %.17g: a step of h_max = %.17g would need more than PFC_RADAU_MAX_FIRES = %d additions", who,
-                    dt, R.fin[2], PFC_RADAU_MAX_FIRES);
-    // the joint that owns a coordinate: revolute and prismatic joints own one, at the same offset in q and v
-    std::vector<int> owner(nv, PFC_JOINT_FIXED);
-    const int *jtype = (const int *)(K.blob.data() + K.o_jtype), *qoff = (const int *)(K.blob.data() + K.o_qoff);
-    const int *voff = (const int *)(K.blob.data() + K.o_voff);
-    for (int b = 0; b < K.n_body; ++b) {
-        const int w = jtype[b] == PFC_JOINT_FLOATING_MRP ? 6 : jtype[b] == PFC_JOINT_FIXED ? 0 : 1;
-        for (int k = 0; k < w && voff[b] + k < (int)nv; ++k) owner[voff[b] + k] = qoff[b] == voff[b] ? jtype[b] : PFC_JOINT_FIXED;
-    }
-    for (int a = 0; a < n_act; ++a) {
-        if (act[a] < 0 || act[a] >= (int)nv || (a > 0 && act[a] <= act[a - 1]))
-            return fail(c, PFC_ERR_BAD_ARG, "%s: actuated coordinate %d is %d: strictly increasing and below nv = %d", who, a, act[a], (int)nv);
-        if (owner[act[a]] != PFC_JOINT_REVOLUTE && owner[act[a]] != PFC_JOINT_PRISMATIC)
-            return fail(c, PFC_ERR_BAD_ARG, "%s: actuated coordinate %d belongs to a floating or fixed joint: revolute and prismatic only", who, act[a]);
-        if (!std::isfinite(kp[a]) || !std::isfinite(kd[a])) return fail(c, PFC_ERR_BAD_ARG, "%s: gain of coordinate %d is not finite", who, act[a]);
-        if (a_max && !(a_max[a] > 0.0)) return fail(c, PFC_ERR_BAD_ARG, "%s: a_max of coordinate %d is %.17g, not > 0", who, act[a], a_max[a]);
-    }
-    const size_t sg = (size_t)n_seg, na = (size_t)n_act;
-    for (size_t s = 0; s < ns; ++s) {
-        for (size_t j = 1; j < sg; ++j) {
-            const double a = seg_t[s * sg + j];
-            if (a != a || (j > 1 && a < seg_t[s * sg + j - 1]))
-                return fail(c, PFC_ERR_BAD_ARG, "%s: start time %zu of scene %zu is %.17g: the start times must not decrease", who, j, s, a);
-        }
-        for (size_t e = 0; e < sg * na; ++e)
-            if (!std::isfinite(seg_q[s * sg * na + e])) return fail(c, PFC_ERR_BAD_ARG, "%s: a setpoint of scene %zu is not finite", who, s);
-        for (size_t e = 0; seg_ff && e < sg * nv; ++e)
-            if (!std::isfinite(seg_ff[s * sg * nv + e])) return fail(c, PFC_ERR_BAD_ARG, "%s: a feed-forward torque of scene %zu is not finite", who, s);
-        if (t_last0 && !std::isfinite(t_last0[s])) return fail(c, PFC_ERR_BAD_ARG, "%s: t_last0 of scene %zu is not finite", who, s);
-    }
-    pfc_context::RadauHost::Control N;
-    size_t sd[CD_N], si[CI_N], td = 0, ti = 0;
-    sd[CD_KP] = na; sd[CD_KD] = na; sd[CD_AMAX] = na; sd[CD_SEGT] = ns * sg; sd[CD_SEGQ] = ns * sg * na; sd[CD_SEGFF] = seg_ff ? ns * sg * nv : 0;
-    sd[CD_TLAST] = ns; si[CI_ACT] = na; si[CI_FIRES] = ns;
-    for (int k = 0; k < CD_N; ++k) { N.od[k] = td; td += sd[k]; }
-    for (int k = 0; k < CI_N; ++k) { N.oi[k] = ti; ti += si[k]; }
-    std::vector<double> hd(td, 0.0);
-    std::vector<int> hi(ti, 0);
-    const double inf = std::numeric_limits<double>::infinity();
-    for (size_t a = 0; a < na; ++a) {
-        hd[N.od[CD_KP] + a] = kp[a]; hd[N.od[CD_KD] + a] = kd[a]; hd[N.od[CD_AMAX] + a] = a_max ? a_max[a] : inf;
-        hi[N.oi[CI_ACT] + a] = act[a];
-    }
-    for (size_t s = 0; s < ns; ++s)
-        for (size_t j = 1; j < sg; ++j) hd[N.od[CD_SEGT] + s * sg + j] = seg_t[s * sg + j];      // entry 0 is not read: +0.0
-    if (na) std::memcpy(hd.data() + N.od[CD_SEGQ], seg_q, sizeof(double) * ns * sg * na);
-    if (seg_ff) std::memcpy(hd.data() + N.od[CD_SEGFF], seg_ff, sizeof(double) * ns * sg * nv);
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (t_last0) std::memcpy(hd.data() + N.od[CD_TLAST], t_last0, sizeof(double) * ns);
-    else if (R.has_state) HIP_TRY(c, hipMemcpy(hd.data() + N.od[CD_TLAST], R.dbl.p + R.od[RD_T], sizeof(double) * ns, hipMemcpyDeviceToHost));
-    // the new blocks first: if they cannot be had, the previous controller stays in force
-    if (N.cdbl.ensure(td) != hipSuccess || N.citg.ensure(ti) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, PFC_ERR_NOMEM, "%s: no device memory for %zu doubles and %zu ints", who, td, ti);
-    }
-    HIP_TRY(c, hipMemcpy(N.cdbl.p, hd.data(), sizeof(double) * td, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(N.citg.p, hi.data(), sizeof(int) * ti, hipMemcpyHostToDevice));
-    N.on = true; N.has_ff = seg_ff != nullptr; N.has_t0 = t_last0 != nullptr; N.n_act = n_act; N.n_seg = n_seg; N.dt = dt;
-    if (t_last0) N.t_last0.assign(t_last0, t_last0 + ns);
-    N.act.assign(act, act + n_act);
-    R.ctl = std::move(N);      // a program of the previous controller goes with it
-    return radau_zero_tau_unless_set(c);
-}
-
-int pfc_radau_set_controller(pfc_handle h, int n_act, const int *act, const double *kp, const double *kd, const double *a_max, double dt,
-                             const double *t_last0, int n_seg, const double *seg_t, const double *seg_q, const double *seg_ff) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        return radau_set_controller_ctx(c, n_act, act, kp, kd, a_max, dt, t_last0, n_seg, seg_t, seg_q, seg_ff); });
-}
-
-int pfc_radau_clear_controller(pfc_handle h) {
-    return pfc_radau_set_controller(h, 0, nullptr, nullptr, nullptr, nullptr, 0.0, nullptr, 0, nullptr, nullptr, nullptr);
-}
-
-int pfc_radau_controller_state(pfc_handle h, double *t_last, int *fires) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        const char *who = "pfc_radau_controller_state";
-        const int rc = radau_need(c, who, false);
-        if (rc != PFC_OK) return rc;
-        pfc_context::RadauHost &R = c->radau;
-        if (!R.ctl.on) return fail(c, PFC_ERR_STATE, "%s without a controller (pfc_radau_set_controller)", who);
-        const size_t ns = (size_t)R.L.n_scene;
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (t_last) HIP_TRY(c, hipMemcpy(t_last, R.ctl.cdbl.p + R.ctl.od[CD_TLAST], sizeof(double) * ns, hipMemcpyDeviceToHost));
-        if (fires) HIP_TRY(c, hipMemcpy(fires, R.ctl.citg.p + R.ctl.oi[CI_FIRES], sizeof(int) * ns, hipMemcpyDeviceToHost));
-        return (int)PFC_OK; });
-}
-
-// ---- the gripper program (k_radau_program, pfc_radau_program.h; the statement: include/pfc.h) -----------------------------------------
-static int radau_program_launch(pfc_context *h, const char *who, int n_scene, int n_body, int nv, int n_act, int n_ins, int body, int n_grip,
-                                const int *d_grip, double tau_soft, double tau_hard, const double *d_prog_dt, const double *d_prog_q,
-                                const double *d_prog_slip, const double *d_t, const double *d_t_last, const double *d_x_w_b,
-                                const int *d_istate, int *d_cursor, double *d_pstate, double *d_seg_q, double *d_seg_ff, hipStream_t st) {
-    if (n_scene < 0) return fail(h, PFC_ERR_BAD_ARG, "%s: negative n_scene", who);
-    if (nv < 1 || nv > PFC_MAX_NV_SOLVE)
-        return fail(h, PFC_ERR_BAD_ARG, "%s: nv is %d, the law takes 1 .. PFC_MAX_NV_SOLVE = %d coordinates", who, nv, PFC_MAX_NV_SOLVE);
-    if (n_act < 0 || n_act > nv) return fail(h, PFC_ERR_BAD_ARG, "%s: n_act is %d, 0 .. nv = %d", who, n_act, nv);
-    if (n_ins < 1) return fail(h, PFC_ERR_BAD_ARG, "%s: n_ins is %d, at least one instruction", who, n_ins);
-    if (n_body < 1 || body < 0 || body >= n_body) return fail(h, PFC_ERR_BAD_ARG, "%s: body is %d, 0 .. n_body - 1 = %d", who, body, n_body - 1);
-    if (n_grip < 0 || n_grip > nv) return fail(h, PFC_ERR_BAD_ARG, "%s: n_grip is %d, 0 .. nv = %d", who, n_grip, nv);
-    if (!std::isfinite(tau_soft) || !std::isfinite(tau_hard))
-        return fail(h, PFC_ERR_BAD_ARG, "%s: tau_soft is %.17g and tau_hard %.17g: finite grip torques", who, tau_soft, tau_hard);
-    if (n_scene == 0) return PFC_OK;
-    if ((n_act > 0 && (!d_prog_q || !d_seg_q)) || (n_grip > 0 && (!d_grip || !d_seg_ff)) || !d_prog_dt || !d_prog_slip || !d_t || !d_t_last ||
-        !d_x_w_b || !d_cursor || !d_pstate)
-        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-    HIP_TRY(h, hipSetDevice(h->device));
-    RadauProgramArgs a;
-    a.n_scene = n_scene; a.n_body = n_body; a.nv = nv; a.n_act = n_act; a.n_ins = n_ins; a.body = body; a.n_grip = n_grip;
-    a.tau_soft = tau_soft; a.tau_hard = tau_hard; a.grip = d_grip; a.prog_dt = d_prog_dt; a.prog_slip = d_prog_slip; a.prog_q = d_prog_q;
-    a.t = d_t; a.t_last = d_t_last; a.x_w_b = d_x_w_b; a.istate = d_istate; a.cursor = d_cursor; a.pstate = d_pstate; a.seg_q = d_seg_q;
-    a.seg_ff = d_seg_ff;
-    hipLaunchKernelGGL(k_radau_program, dim3((unsigned)((n_scene + kRadProgBlock - 1) / kRadProgBlock)), dim3(kRadProgBlock), 0, st, a);
-    HIP_TRY(h, hipGetLastError());
-    return PFC_OK;
-}
-
-int pfc_radau_program_device(pfc_handle h, int n_scene, int n_body, int nv, int n_act, int n_ins, int body, int n_grip, const int *d_grip,
-                             double tau_soft, double tau_hard, const double *d_prog_dt, const double *d_prog_q, const double *d_prog_slip,
-                             const double *d_t, const double *d_t_last, const double *d_x_w_b, const int *d_istate, int *d_cursor,
-                             double *d_pstate, double *d_seg_q, double *d_seg_ff, void *stream) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        return radau_program_launch(c, "pfc_radau_program_device", n_scene, n_body, nv, n_act, n_ins, body, n_grip, d_grip, tau_soft, tau_hard,
-                                    d_prog_dt, d_prog_q, d_prog_slip, d_t, d_t_last, d_x_w_b, d_istate, d_cursor, d_pstate, d_seg_q, d_seg_ff,
-                                    stream ? (hipStream_t)stream : c->stream); });
-}
-
-// The records to their initial values and the controller's segment to what pfc_radau_set_controller gave (the stream is idle).
-static int radau_program_reset(pfc_context *c) {
-    pfc_context::RadauHost::Control &T = c->radau.ctl;
-    const pfc_context::RadauHost::Control::Program &P = T.prog;
-    const size_t ns = (size_t)c->radau.L.n_scene;
-    const double inf = std::numeric_limits<double>::infinity();
-    std::vector<double> rec(4 * ns, 0.0);
-    for (size_t s = 0; s < ns; ++s) { rec[4 * s] = inf; rec[4 * s + 1] = inf; }
-    const std::vector<int> cur(2 * ns, 0);
-    HIP_TRY(c, hipMemcpy(P.D(PD_STATE), rec.data(), sizeof(double) * 4 * ns, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(P.I(PI_CURSOR), cur.data(), sizeof(int) * 2 * ns, hipMemcpyHostToDevice));
-    if (!P.seg_q0.empty()) HIP_TRY(c, hipMemcpy(T.D(CD_SEGQ), P.seg_q0.data(), sizeof(double) * P.seg_q0.size(), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(T.D(CD_SEGFF), P.seg_ff0.data(), sizeof(double) * P.seg_ff0.size(), hipMemcpyHostToDevice));
-    return PFC_OK;
-}
-
-static int radau_set_program_ctx(pfc_context *c, int body, int n_grip, const int *grip, double tau_soft, double tau_hard, int n_ins,
-                                 const double *prog_dt, const double *prog_q, const double *prog_slip) {
-    const char *who = "pfc_radau_set_program";
-    const int rc = radau_need(c, who, false);
-    if (rc != PFC_OK) return rc;
-    pfc_context::RadauHost &R = c->radau;
-    pfc_context::RadauHost::Control &T = R.ctl;
-    if (!T.on) return fail(c, PFC_ERR_STATE, "%s without a controller (pfc_radau_set_controller)", who);
-    if (T.n_seg != 1 || !T.has_ff)
-        return fail(c, PFC_ERR_BAD_ARG, "%s: the controller has n_seg = %d and %s seg_ff block: the program writes one segment and its feed-forward",
-                    who, T.n_seg, T.has_ff ? "a" : "no");
-    if (body < 0 || body >= c->kin.n_body) return fail(c, PFC_ERR_BAD_ARG, "%s: body is %d, the mechanism has %d", who, body, c->kin.n_body);
-    const size_t ns = (size_t)R.L.n_scene, nv = (size_t)R.L.nv, na = (size_t)T.n_act;
-    if (n_grip < 0 || n_grip > T.n_act || (n_grip > 0 && !grip)) return fail(c, PFC_ERR_BAD_ARG, "%s: n_grip is %d, 0 .. n_act = %d", who, n_grip, T.n_act);
-    for (int g = 0; g < n_grip; ++g) {
-        if (std::find(T.act.begin(), T.act.end(), grip[g]) == T.act.end())
-            return fail(c, PFC_ERR_BAD_ARG, "%s: grip coordinate %d is not one of the controller's actuated coordinates", who, grip[g]);
-        if (std::find(grip, grip + g, grip[g]) != grip + g) return fail(c, PFC_ERR_BAD_ARG, "%s: grip coordinate %d is repeated", who, grip[g]);
-    }
-    if (!std::isfinite(tau_soft) || !std::isfinite(tau_hard))
-        return fail(c, PFC_ERR_BAD_ARG, "%s: tau_soft is %.17g and tau_hard %.17g: finite grip torques", who, tau_soft, tau_hard);
-    if (n_ins < 1 || !prog_dt || !prog_slip || (na > 0 && !prog_q))
-        return fail(c, PFC_ERR_BAD_ARG, "%s: n_ins is %d: at least one instruction, with prog_dt, prog_q and prog_slip given", who, n_ins);
-    const size_t ni = (size_t)n_ins;
-    for (size_t e = 0; e < ns * ni; ++e) {
-        if (!(prog_dt[e] >= 0.0))
-            return fail(c, PFC_ERR_BAD_ARG, "%s: prog_dt %zu of scene %zu is %.17g: a duration is >= 0 (+inf allowed)", who, e % ni, e / ni, prog_dt[e]);
-        if (prog_slip[e] != prog_slip[e]) return fail(c, PFC_ERR_BAD_ARG, "%s: prog_slip %zu of scene %zu is NaN", who, e % ni, e / ni);
-    }
-    for (size_t e = 0; e < ns * ni * na; ++e)
-        if (!std::isfinite(prog_q[e])) return fail(c, PFC_ERR_BAD_ARG, "%s: a setpoint of scene %zu is not finite", who, e / (ni * na));
-    pfc_context::RadauHost::Control::Program N;
-    size_t sd[PD_N], si[PI_N], td = 0, ti = 0;
-    sd[PD_DT] = ns * ni; sd[PD_Q] = ns * ni * na; sd[PD_SLIP] = ns * ni; sd[PD_STATE] = 4 * ns; si[PI_GRIP] = (size_t)n_grip; si[PI_CURSOR] = 2 * ns;
-    for (int k = 0; k < PD_N; ++k) { N.od[k] = td; td += sd[k]; }
-    for (int k = 0; k < PI_N; ++k) { N.oi[k] = ti; ti += si[k]; }
-    std::vector<double> hd(td, 0.0);
-    std::vector<int> hi(ti, 0);
-    std::memcpy(hd.data() + N.od[PD_DT], prog_dt, sizeof(double) * ns * ni);
-    if (na) std::memcpy(hd.data() + N.od[PD_Q], prog_q, sizeof(double) * ns * ni * na);
-    std::memcpy(hd.data() + N.od[PD_SLIP], prog_slip, sizeof(double) * ns * ni);
-    for (int g = 0; g < n_grip; ++g) hi[N.oi[PI_GRIP] + g] = grip[g];
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    // the segment as pfc_radau_set_controller gave it: the previous program's copy, or what the device holds
-    if (T.prog.on) { N.seg_q0 = T.prog.seg_q0; N.seg_ff0 = T.prog.seg_ff0; }
-    else {
-        N.seg_q0.resize(ns * na); N.seg_ff0.resize(ns * nv);
-        if (na) HIP_TRY(c, hipMemcpy(N.seg_q0.data(), T.D(CD_SEGQ), sizeof(double) * ns * na, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(N.seg_ff0.data(), T.D(CD_SEGFF), sizeof(double) * ns * nv, hipMemcpyDeviceToHost));
-    }
-    // the new blocks first: if they cannot be had, the previous program stays in force
-    if (N.pdbl.ensure(td) != hipSuccess || N.pitg.ensure(ti) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, PFC_ERR_NOMEM, "%s: no device memory for %zu doubles and %zu ints", who, td, ti);
-    }
-    HIP_TRY(c, hipMemcpy(N.pdbl.p, hd.data(), sizeof(double) * td, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(N.pitg.p, hi.data(), sizeof(int) * ti, hipMemcpyHostToDevice));
-    N.on = true; N.n_ins = n_ins; N.body = body; N.n_grip = n_grip; N.tau_soft = tau_soft; N.tau_hard = tau_hard;
-    T.prog = std::move(N);
-    return radau_program_reset(c);
-}
-
-int pfc_radau_set_program(pfc_handle h, int body, int n_grip, const int *grip, double tau_soft, double tau_hard, int n_ins,
-                          const double *prog_dt, const double *prog_q, const double *prog_slip) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        return radau_set_program_ctx(c, body, n_grip, grip, tau_soft, tau_hard, n_ins, prog_dt, prog_q, prog_slip); });
-}
-
-int pfc_radau_clear_program(pfc_handle h) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        const char *who = "pfc_radau_clear_program";
-        const int rc = radau_need(c, who, false);
-        if (rc != PFC_OK) return rc;
-        pfc_context::RadauHost::Control &T = c->radau.ctl;
-        if (!T.on || !T.prog.on) return (int)PFC_OK;
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        const int rr = radau_program_reset(c);      // the segment goes back to pfc_radau_set_controller's
-        T.prog = pfc_context::RadauHost::Control::Program();
-        return rr; });
-}
-
-int pfc_radau_program_state(pfc_handle h, int *cursor, int *pops, double *t0, double *rot_0, double *angle, double *tau_grip) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        const char *who = "pfc_radau_program_state";
-        const int rc = radau_need(c, who, false);
-        if (rc != PFC_OK) return rc;
-        const pfc_context::RadauHost::Control &T = c->radau.ctl;
-        if (!T.on || !T.prog.on) return fail(c, PFC_ERR_STATE, "%s without a program (pfc_radau_set_program)", who);
-        const size_t ns = (size_t)c->radau.L.n_scene;
-        std::vector<double> rec(4 * ns);
-        std::vector<int> cur(2 * ns);
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, hipMemcpy(rec.data(), T.prog.D(PD_STATE), sizeof(double) * 4 * ns, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(cur.data(), T.prog.I(PI_CURSOR), sizeof(int) * 2 * ns, hipMemcpyDeviceToHost));
-        double *out[4] = {t0, rot_0, angle, tau_grip};
-        for (size_t s = 0; s < ns; ++s) {
-            if (cursor) cursor[s] = cur[2 * s];
-            if (pops) pops[s] = cur[2 * s + 1];
-            for (int k = 0; k < 4; ++k) if (out[k]) out[k][s] = rec[4 * s + k];
-        }
-        return (int)PFC_OK; });
-}
-
-// The controller at the top of a batch step: H and c at the committed state -- the first n_scene stage-scenes hold x0 after the
-// first unpack, and the Jacobian's first chunk overwrites the buffers used here -- then the law into RD_TAU.
-static int radau_control_step(pfc_context *c, const char *who, const StateBufs &V) {
-    const pfc_context::RadauHost &R = c->radau;
-    const pfc_context::RadauHost::Control &T = R.ctl;
-    const RadauLayout &L = R.L;
-    int rc = pfc_kinematics_device(c, L.n_scene, V.q, V.v, V.x_w_b, V.twist_w_b, nullptr, nullptr);
-    if (rc != PFC_OK) return rc;
-    if (T.prog.on) {      // the program reads the clock before the law advances it, and writes the segment the law reads
-        const pfc_context::RadauHost::Control::Program &P = T.prog;
-        rc = radau_program_launch(c, who, L.n_scene, c->kin.n_body, L.nv, T.n_act, P.n_ins, P.body, P.n_grip, P.I(PI_GRIP), P.tau_soft,
-                                  P.tau_hard, P.D(PD_DT), P.D(PD_Q), P.D(PD_SLIP), R.D(RD_T), T.D(CD_TLAST), V.x_w_b, R.I(RI_ISTATE),
-                                  P.I(PI_CURSOR), P.D(PD_STATE), T.D(CD_SEGQ), T.D(CD_SEGFF), c->stream);
-        if (rc != PFC_OK) return rc;
-    }
-    rc = pfc_dynamics_device(c, L.n_scene, V.q, V.v, V.x_w_b, V.twist_w_b, nullptr, V.H, V.c, nullptr);
-    if (rc != PFC_OK) return rc;
-    return radau_control_launch(c, who, L.n_scene, L.nq, L.nv, T.n_act, T.n_seg, T.dt, T.I(CI_ACT), T.D(CD_KP), T.D(CD_KD), T.D(CD_AMAX),
-                                T.D(CD_SEGT), T.D(CD_SEGQ), T.has_ff ? T.D(CD_SEGFF) : nullptr, R.D(RD_T), V.q, V.v, V.H, V.c, R.I(RI_ISTATE),
-                                T.D(CD_TLAST), T.I(CI_FIRES), R.D(RD_TAU), c->stream);
-}
-
-// The handle's blocks as the buffers of the step's state calls -- val: RD_V* / RI_V*, par: RD_DD* -- bound in this one place; the
-// caller sets the heads (n_items, n_scene, n_dir).  q, v, s and their seeds a second time as what unpack and seed write.
-struct RadauStateBufs {
-    StateCall call;
-    double *q, *v, *s, *dq, *dv, *ds;
-};
-
-static RadauStateBufs radau_state_bufs(const pfc_context::RadauHost &R) {
-    RadauStateBufs B;
-    B.call.ins_ids = R.I(RI_VINS); B.call.scene = R.I(RI_VSC);
-    StateBufs &V = B.call.val, &P = B.call.par;
-    V.q = B.q = R.D(RD_VQ); V.v = B.v = R.D(RD_VV); V.s = B.s = R.D(RD_VS); V.tau = R.has_tau || R.ctl.on ? R.D(RD_TAU) : nullptr;
-    V.x_w_b = R.D(RD_VXWB); V.twist_w_b = R.D(RD_VTW); V.jac = R.D(RD_VJAC);
-    V.pose = R.D(RD_VPOSE); V.twist = R.D(RD_VTWI); V.x_w_r2 = R.D(RD_VXR2); V.body_1 = R.I(RI_VB1); V.body_2 = R.I(RI_VB2);
-    V.wrench = R.D(RD_VWR); V.sdot = R.D(RD_VSD); V.counts = R.I(RI_VCNT); V.f = R.D(RD_VF);
-    V.qdot = R.D(RD_VQD); V.H = R.D(RD_VH); V.c = R.D(RD_VC); V.vdot = R.D(RD_VVD); V.info = R.I(RI_VINFO);
-    P.q = B.dq = R.D(RD_DDQ); P.v = B.dv = R.D(RD_DDV); P.s = B.ds = R.D(RD_DDS);
-    P.x_w_b = R.D(RD_DDXWB); P.twist_w_b = R.D(RD_DDTW); P.jac = R.D(RD_DDJAC);
-    P.pose = R.D(RD_DDPOSE); P.twist = R.D(RD_DDTWI); P.x_w_r2 = R.D(RD_DDXR2);
-    P.wrench = R.D(RD_DDWR); P.sdot = R.D(RD_DDSD); P.f = R.D(RD_DDF);
-    P.qdot = R.D(RD_DDQD); P.H = R.D(RD_DDH); P.c = R.D(RD_DDC); P.vdot = R.D(RD_DDVD);
-    return B;
-}
-
-// An evaluation and its pfc_check, re-issued while the work lists grow.
-static int radau_checked(pfc_context *c, const std::function<int()> &issue) {
-    for (int k = 0; k < 40; ++k) {
-        int rc = issue();
-        if (rc != PFC_OK) return rc;
-        rc = pfc_check(c);
-        if (rc != PFC_ERR_OVERFLOW) return rc;
-    }
-    return fail(c, PFC_ERR_OVERFLOW, "pfc_radau_step: the work lists still overflow after 40 re-issues");
-}
-
-// The count word, or (words = 2) the count and the live word behind it, in one copy.
-static int radau_read_count(pfc_context *c, int *count, int words = 1) {
-    pfc_context::RadauHost &R = c->radau;
-    HIP_TRY(c, hipMemcpyAsync(count, R.itg.p + R.oi[RI_COUNT], sizeof(int) * (size_t)words, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return PFC_OK;
-}
-
-// One batch step, the body of pfc_radau_step and pfc_radau_integrate.  `end`: the finish is k_radau_finish<true> on the handle's end
-// times and trajectory, and *live receives the scenes that committed a step and did not park.
-static int radau_step_body(pfc_context *c, const char *who, bool end, int *live) {
-    int rc = PFC_OK;
-    const pfc_context::RadauHost &R = c->radau;
-    const RadauLayout &L = R.L;
-    const RadauStateBufs B = radau_state_bufs(R);
-    const hipStream_t st = c->stream;
-    StateCall S = B.call, J = B.call;      // the stage-scenes' values, and the Dual chunks on the first n_scene of them
-    S.n_scene = 3 * L.n_scene; S.n_items = S.n_scene * L.n_ips;
-    J.n_scene = L.n_scene; J.n_items = J.n_scene * L.n_ips;
-    const StateBufs &V = B.call.val, &P = B.call.par;
-    auto unpack = [&]() { return radau_unpack_launch(c, L, R.D(RD_X), R.I(RI_RULE), R.I(RI_ISTATE), R.D(RD_XS), B.q, B.v, B.s, st); };
-    // calcJacobian!: no scene is iterating, so every stage-scene -- the first n_scene of them are the scenes themselves -- gets x0
-    if ((rc = unpack()) != PFC_OK) return rc;
-    if (R.ctl.on && (rc = radau_control_step(c, who, V)) != PFC_OK) return rc;
-    for (int j0 = 0; j0 < L.nx; j0 += R.n_chunk) {
-        J.n_dir = std::min(R.n_chunk, L.nx - j0);
-        if ((rc = radau_seed_launch(c, L, j0, J.n_dir, B.dq, B.dv, B.ds, st)) != PFC_OK) return rc;
-        rc = radau_checked(c, [&]() { return state_derivative_dual(c, J, j0 > 0); });
-        if (rc != PFC_OK) return rc;
-        rc = radau_jacobian_launch(c, L, j0, J.n_dir, P.qdot, P.vdot, P.sdot, V.qdot, V.vdot, V.sdot, R.D(RD_NEGJ), R.D(RD_XDOT0),
-                                   R.D(RD_NSTATE), R.I(RI_ISTATE), st);
-        if (rc != PFC_OK) return rc;
-    }
-    const RadauFinishRule rule{R.n_mrp, R.mrp_off, R.fin, R.k_iter_max, R.max_rule, R.cooldown};
-    const RadauEndBufs eb{R.has_end ? R.D(RD_TFINAL) : nullptr, R.max_rows > 0 ? R.traj.p : nullptr, R.max_rows > 0 ? R.I(RI_ROWS) : nullptr,
-                          R.max_rows, R.I(RI_COUNT) + 1};
-    if (end) HIP_TRY(c, hipMemsetAsync(R.I(RI_COUNT) + 1, 0, sizeof(int), st));      // live adds up over the attempts' finishes
-    // solveRadau_inner: attempts until no scene is armed again
-    for (int attempt = 0; attempt < 64; ++attempt) {
-        rc = radau_factor_launch(c, L.n_scene, L.nx, R.D(RD_NEGJ), R.D(RD_H), R.I(RI_RULE), R.I(RI_ISTATE) + kRadIter, 8, R.D(RD_LU0),
-                                 R.D(RD_LU1), R.I(RI_PERM), R.I(RI_INFO), st);
-        if (rc != PFC_OK) return rc;
-        int count = 1;
-        for (int it = 0; it <= R.k_iter_max && count > 0; ++it) {
-            if ((rc = unpack()) != PFC_OK) return rc;
-            if ((rc = radau_checked(c, [&]() { return state_derivative(c, S); })) != PFC_OK) return rc;
-            rc = radau_newton_launch(c, L, V.qdot, V.vdot, V.sdot, R.D(RD_X), R.D(RD_H), R.I(RI_RULE), R.D(RD_LU0), R.D(RD_LU1), R.I(RI_PERM),
-                                     R.I(RI_INFO), R.tol_newton, R.k_iter_max, R.D(RD_XS), R.D(RD_FS), R.D(RD_NSTATE), R.I(RI_ISTATE),
-                                     R.I(RI_COUNT), st);
-            if (rc != PFC_OK || (rc = radau_read_count(c, &count)) != PFC_OK) return rc;
-        }
-        if (count > 0) return fail(c, PFC_ERR_STATE, "%s: %d scenes still iterate after k_iter_max + 1 passes", who, count);
-        rc = radau_finish_launch(c, L, rule, end ? &eb : nullptr, R.D(RD_FS), R.D(RD_XDOT0), R.D(RD_XS), R.D(RD_LU0), R.I(RI_PERM), R.D(RD_X),
-                                 R.D(RD_T), R.D(RD_H), R.I(RI_RULE), R.I(RI_COOL), R.D(RD_ENORM), R.D(RD_NSTATE), R.I(RI_ISTATE),
-                                 R.I(RI_COUNT), st);
-        int words[2] = {0, 0};
-        if (rc != PFC_OK || (rc = radau_read_count(c, words, end ? 2 : 1)) != PFC_OK) return rc;
-        count = words[0];
-        if (live) *live = words[1];
-        if (count == 0) break;
-        if (attempt == 63) return fail(c, PFC_ERR_STATE, "%s: scenes are still armed after 64 attempts", who);
-    }
-    return PFC_OK;
-}
-
-static int radau_step_ctx(pfc_context *c, double *h_taken, int *flags, int *iters, int *attempts) {
-    const char *who = "pfc_radau_step";
-    int rc = radau_need(c, who, true);
-    if (rc != PFC_OK || (rc = radau_step_body(c, who, c->radau.has_end, nullptr)) != PFC_OK) return rc;
-    pfc_context::RadauHost &R = c->radau;
-    const int ns = R.L.n_scene;
-    std::vector<double> nst(8 * (size_t)ns);
-    std::vector<int> ist(8 * (size_t)ns);
-    HIP_TRY(c, hipMemcpy(nst.data(), R.D(RD_NSTATE), sizeof(double) * nst.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(ist.data(), R.I(RI_ISTATE), sizeof(int) * ist.size(), hipMemcpyDeviceToHost));
-    for (int s = 0; s < ns; ++s) {
-        const int *is = ist.data() + 8 * (size_t)s;
-        if (h_taken) h_taken[s] = is[kRadExit] == 0 ? nst[8 * (size_t)s + kRadHTaken] : 0.0;
-        if (flags) flags[s] = is[kRadExit];
-        if (iters) iters[s] = is[kRadExitIter];
-        if (attempts) attempts[s] = is[kRadAttempts];
-    }
-    return PFC_OK;
-}
-
-int pfc_radau_step(pfc_handle h, double *h_taken, int *flags, int *iters, int *attempts) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) { return radau_step_ctx(c, h_taken, flags, iters, attempts); });
-}
-
-// ---- integration to per-scene end times (integrate_scenario_radau, src/example_integrator.jl) ------------------------------------
-int pfc_radau_set_end(pfc_handle h, const double *t_final, int max_rows) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        const char *who = "pfc_radau_set_end";
-        const int rc = radau_need(c, who, true);
-        if (rc != PFC_OK) return rc;
-        pfc_context::RadauHost &R = c->radau;
-        const size_t ns = (size_t)R.L.n_scene, w = 1 + (size_t)R.L.nx;
-        if (max_rows < 0 || max_rows == 1) return fail(c, PFC_ERR_BAD_ARG, "%s: max_rows is %d: 0 (no recording) or at least 2", who, max_rows);
-        std::vector<double> tf(ns, std::numeric_limits<double>::infinity());
-        for (size_t s = 0; t_final && s < ns; ++s) {
-            if (t_final[s] != t_final[s]) return fail(c, PFC_ERR_BAD_ARG, "%s: t_final of scene %zu is NaN", who, s);
-            tf[s] = t_final[s];
-        }
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        DevBuf<double> block;      // the new trajectory first: if it cannot be had, the previous end stays in force
-        if (max_rows > 0 && block.ensure(ns * (size_t)max_rows * w) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, PFC_ERR_NOMEM, "%s: no device memory for %zu scenes x %d rows x %zu doubles", who, ns, max_rows, w);
-        }
-        R.traj = std::move(block);
-        R.max_rows = max_rows; R.has_end = true;
-        HIP_TRY(c, hipMemcpyAsync(R.dbl.p + R.od[RD_TFINAL], tf.data(), sizeof(double) * ns, hipMemcpyHostToDevice, c->stream));
-        RadauSetEndArgs a;
-        a.n_scene = R.L.n_scene; a.nx = R.L.nx; a.max_rows = max_rows;
-        a.x = R.dbl.p + R.od[RD_X]; a.t = R.dbl.p + R.od[RD_T]; a.traj = R.traj.p; a.rows = R.itg.p + R.oi[RI_ROWS];
-        a.istate = R.itg.p + R.oi[RI_ISTATE];
-        hipLaunchKernelGGL(k_radau_set_end, dim3(radau_grid(ns * w)), dim3(kRadBlock), 0, c->stream, a);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipStreamSynchronize(c->stream));      // tf is read until here
-        return (int)PFC_OK; });
-}
-
-int pfc_radau_integrate(pfc_handle h, int max_steps, int *steps_done, int *n_live) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        const char *who = "pfc_radau_integrate";
-        int rc = radau_need(c, who, true);
-        if (rc != PFC_OK) return rc;
-        if (max_steps < 0) return fail(c, PFC_ERR_BAD_ARG, "%s: max_steps is %d", who, max_steps);
-        pfc_context::RadauHost &R = c->radau;
-        // the scenes live at the start, read once: neither retired (exit flag 5) nor parked
-        std::vector<int> ist(8 * (size_t)R.L.n_scene);
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, hipMemcpy(ist.data(), R.itg.p + R.oi[RI_ISTATE], sizeof(int) * ist.size(), hipMemcpyDeviceToHost));
-        int live = 0, steps = 0;
-        for (int s = 0; s < R.L.n_scene; ++s) live += ist[8 * (size_t)s + kRadExit] != 5 && ist[8 * (size_t)s + kRadIntSpare] == 0;
-        while (rc == PFC_OK && live > 0 && steps < max_steps) {
-            rc = radau_step_body(c, who, true, &live);
-            if (rc == PFC_OK) ++steps;
-        }
-        if (steps_done) *steps_done = steps;
-        if (n_live) *n_live = live;
-        return rc; });
-}
-
-int pfc_radau_trajectory_rows(pfc_handle h, int *rows) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        const char *who = "pfc_radau_trajectory_rows";
-        const int rc = radau_need(c, who, true);
-        if (rc != PFC_OK) return rc;
-        pfc_context::RadauHost &R = c->radau;
-        if (!R.has_end) return fail(c, PFC_ERR_STATE, "%s before pfc_radau_set_end", who);
-        if (!rows) return fail(c, PFC_ERR_BAD_ARG, "%s: null buffer", who);
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, hipMemcpy(rows, R.itg.p + R.oi[RI_ROWS], sizeof(int) * (size_t)R.L.n_scene, hipMemcpyDeviceToHost));
-        return (int)PFC_OK; });
-}
-
-int pfc_radau_trajectory(pfc_handle h, int scene, int row0, int n, double *t, double *x) {
-    if (!h) return PFC_ERR_BAD_ARG;
-    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
-        const char *who = "pfc_radau_trajectory";
-        const int rc = radau_need(c, who, true);
-        if (rc != PFC_OK) return rc;
-        pfc_context::RadauHost &R = c->radau;
-        if (!R.has_end) return fail(c, PFC_ERR_STATE, "%s before pfc_radau_set_end", who);
-        if (scene < 0 || scene >= R.L.n_scene) return fail(c, PFC_ERR_BAD_ARG, "%s: scene %d of %d", who, scene, R.L.n_scene);
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        int have = 0;
-        HIP_TRY(c, hipMemcpy(&have, R.itg.p + R.oi[RI_ROWS] + scene, sizeof(int), hipMemcpyDeviceToHost));
-        if (row0 < 0 || n < 0 || (long long)row0 + n > (long long)have)
-            return fail(c, PFC_ERR_BAD_ARG, "%s: rows %d .. %d + %d of scene %d, which has %d", who, row0, row0, n, scene, have);
-        if (n == 0) return (int)PFC_OK;
-        const size_t nx = (size_t)R.L.nx, w = 1 + nx;
-        std::vector<double> buf((size_t)n * w);
-        HIP_TRY(c, hipMemcpy(buf.data(), R.traj.p + ((size_t)scene * (size_t)R.max_rows + (size_t)row0) * w, sizeof(double) * buf.size(),
-                             hipMemcpyDeviceToHost));
-        for (size_t r = 0; r < (size_t)n; ++r) {
-            if (t) t[r] = buf[r * w];
-            if (x) std::memcpy(x + r * nx, buf.data() + r * w + 1, sizeof(double) * nx);
-        }
-        return (int)PFC_OK; });
-}
+// ---- the Radau IIA host driver: the parts, configuration and state, controller, gripper program, batch step, integration -------------
+#include "pfc_radau_host.h"
 
 }  // extern "C"

@@ -107,3 +107,63 @@ def test_every_allocation_is_freed_once():
                 not ln.startswith("pfc unpinned"), f"allocation log line not understood (a failed allocation?): {ln}"
     assert n_alloc - n_pinned >= 100 and n_pinned >= 10, (n_alloc, n_pinned)      # the log is on and the paths ran
     assert not live, f"{len(live)} blocks never freed, e.g. {sorted(live)[:5]}"
+
+
+# The six blocks of the Radau handle on the two-scene slider (tests/test_gpu_radau_program.py: n_scene = 2, one regularized item,
+# nq = nv = 2, NX = 4, n_body = 2, n_chunk = 6, controller n_act = 2 / n_seg = 1 with seg_ff, program n_ins = 3 / n_grip = 1), as
+# (bytes, element size) in the order of the calls.  Recorded from the log of the commit before the part-block type; the formulas:
+#   pfc_radau_configure rounds each part up to 32 doubles / 64 ints, an empty part taking one element:
+#     doubles  10 x 32 (x, t, h, enorm, nstate, X, F, xdot0, -J, LU0) + 64 (LU1) + 32 (tau) + 1152 (16 value parts)
+#              + 1824 (16 partial parts) + 32 (t_final) = 3424;   ints  13 parts x 64 = 832
+#   pfc_radau_set_controller packs:  kp 2 + kd 2 + a_max 2 + seg_t 2 + seg_q 4 + seg_ff 4 + t_last 2 = 18;  act 2 + fires 2 = 4
+#   pfc_radau_set_program packs:     prog_dt 6 + prog_q 12 + prog_slip 6 + records 8 = 32;  grip 1 + cursors 4 = 5
+_RADAU_BLOCKS = {"configure": [(8 * 3424, 8), (4 * 832, 4)], "controller": [(8 * 18, 8), (4 * 4, 4)], "program": [(8 * 32, 8), (4 * 5, 4)]}
+
+
+def radau_child():
+    """The child process: the three calls that allocate a pair of blocks, each between two marks in the log, a step, the close."""
+    import pfc_pkg
+    import test_gpu_radau_program as P
+    pfc = pfc_pkg.load()
+    m = P.T._slider(pfc, two=True)
+
+    def marked(name, call):
+        print(f"mark {name}", file=sys.stderr, flush=True)
+        call()
+        print("mark end", file=sys.stderr, flush=True)
+
+    marked("configure", lambda: m.radau_configure(2, [0]))
+    m.radau_set_state(P.SLIDER_X0)
+    marked("controller", lambda: m.radau_set_controller(**P.SLIDER_CTL))
+    marked("program", lambda: m.radau_set_program(**P.SLIDER_PROG))
+    assert m.radau_step()["flags"].tolist() == [0, 0]
+    m.close()
+
+
+def test_radau_blocks_have_their_sizes_and_are_freed_once():
+    """Both layout rules of the handle's part blocks (rounded parts for the step's two blocks, packed parts for the controller's
+    and the program's), the double block before the int block, and each of the six freed exactly once."""
+    env = dict(os.environ, PFC_LOG_ALLOC="1")
+    code = f"import sys; sys.path[:0] = [{ROOT!r}, {TESTS!r}]; import test_gpu_ownership as t; t.radau_child()"
+    r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True)
+    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
+    alloc = re.compile(r"^pfc alloc (0x[0-9a-f]+) \.\. 0x[0-9a-f]+ \((\d+) bytes, element (\d+)\)$")
+    free = re.compile(r"^pfc free (0x[0-9a-f]+)$")
+    call, got, live, others, n_freed = None, {}, set(), set(), 0
+    for ln in r.stderr.splitlines():
+        a, f = alloc.match(ln), free.match(ln)
+        if ln.startswith("mark "):
+            call = None if ln == "mark end" else ln[5:]
+        elif a:
+            assert a.group(1) not in live and a.group(1) not in others, f"allocated twice without a free in between: {ln}"
+            (live if call else others).add(a.group(1))
+            if call:
+                got.setdefault(call, []).append((int(a.group(2)), int(a.group(3))))
+        elif f:
+            assert f.group(1) in live or f.group(1) in others, f"freed without a live allocation (a second free?): {ln}"
+            n_freed += f.group(1) in live
+            live.discard(f.group(1))
+            others.discard(f.group(1))
+    print("radau blocks:", got)
+    assert got == _RADAU_BLOCKS, got
+    assert not live and n_freed == 6, (live, n_freed)
