@@ -1099,7 +1099,8 @@ int pfc_radau_get_state(pfc_handle h, double *x, double *t);      /* either may 
  * in place of the reset values -- a restart from pfc_radau_rule_state's figures, or scenes that start at different h.
  * PFC_ERR_BAD_ARG, and nothing is changed, for an h that is not finite and > 0, a rule or a cooldown out of range. */
 int pfc_radau_set_rule_state(pfc_handle h, const double *h_scene, const int *rule, const int *cooldown);
-/* tau (n_scene x nv, host; NULL: zeros), held constant over a step; its partials are zero.  With a controller set
+/* tau (n_scene x nv, host; NULL: zeros), held constant over a step; its partials are zero (a torque that varies inside a step, with
+ * partials: pfc_radau_set_feedback below, which adds its law to this tau).  With a controller set
  * (pfc_radau_set_controller) the value of a scene lasts until the controller first fires for it: a fire overwrites all nv entries. */
 int pfc_radau_set_tau(pfc_handle h, const double *tau);
 /*
@@ -1283,6 +1284,73 @@ int pfc_radau_set_controller(pfc_handle h, int n_act, const int *act, const doub
                              const double *t_last0, int n_seg, const double *seg_t, const double *seg_q, const double *seg_ff);
 int pfc_radau_clear_controller(pfc_handle h);      /* pfc_radau_set_controller's clearing form */
 int pfc_radau_controller_state(pfc_handle h, double *t_last, int *fires);
+
+/*
+ * Continuous joint feedback: the reference's continuous_controller(tm, t), called inside calcXd!
+ * (src/contact_algorithms_non_friction.jl:29) at every stage evaluation with that stage's time and on the Dual state of every
+ * Jacobian chunk, so that its torque is part of the differential equation and its partials are part of the matrix Radau factors.
+ * The law is the discrete controller's computed-torque PD above with the same tables (act, kp, kd, a_max, seg_t, seg_q, seg_ff),
+ * evaluated continuously instead of at clock ticks: no dt, no t_last.  Plain Float64, no fma, in the written order.
+ * The value, per row (a scene or a stage-scene; row r reads the schedule of scene r % n_scene; nq = nv):
+ *   k = the number of j in 1 .. n_seg - 1 with seg_t[j] <= t
+ *   for every actuated a: acc_a = (-(kd_a v_a)) - kp_a (q_a - seg_q[k][a]);  if acc_a < -a_max_a: acc_a = -a_max_a;  if acc_a >
+ *     a_max_a: acc_a = a_max_a   (a_max NULL: no clamp; a NaN passes)
+ *   law_a = ((..((0 + H[a,b_0] acc_b_0) + H[a,b_1] acc_b_1) ..) + c_a) + ff[k][a], b over act in increasing order, ff = 0.0 where
+ *     seg_ff is NULL: computed_torque_pd's tau_a
+ *   an actuated coordinate: tau_out_a = law_a + tau_in_a, or law_a where tau_in is NULL
+ *   a coordinate i that is not actuated: with seg_ff given tau_out_i = ff[k][i] + tau_in_i (ff[k][i] where tau_in is NULL); with
+ *     seg_ff NULL tau_out_i is tau_in_i copied -- not added to zero, so a signed zero survives -- and +0.0 where tau_in is NULL
+ * The partials, per (row, direction): the value statement instantiated on the (value, partial) number of the Dual kinematics and
+ * dynamics, product rule d(a b) = da b + a db, no fma; t, the tables and tau_in are constants:
+ *   dacc_a = (-(kd_a dv_a)) - kp_a dq_a;  dacc_a = 0.0 where either clamp test of the value engaged
+ *   dtau_a = ((..((0 + (dH[a,b_0] acc_b_0 + H[a,b_0] dacc_b_0)) + (dH[a,b_1] acc_b_1 + H[a,b_1] dacc_b_1)) ..) + dc_a, acc clamped
+ *   dtau_i = 0.0 for a coordinate that is not actuated
+ * pfc_feedback_device, pfc_feedback_dual_device: the parts on caller buffers and a caller stream (NULL: the handle's),
+ * asynchronous, like pfc_radau_control_device; they read nothing of the handle but its device and stream.  d_act (n_act ints; the
+ * caller guarantees 0 <= act[b] < nv, increasing), d_kp, d_kd, d_a_max (n_act; d_a_max may be NULL), d_seg_t (n_scene x n_seg; may be
+ * NULL with n_seg = 1), d_seg_q (n_scene x n_seg x n_act), d_seg_ff (n_scene x n_seg x nv, or NULL); d_t (n_rows), d_q, d_v, d_c (n_rows
+ * x nv), d_H (n_rows x nv x nv, row-major: pfc_dynamics_device's outputs), d_tau_in (n_rows x nv, or NULL), d_tau_out (n_rows x nv).
+ * The Dual part: d_dq, d_dv (n_rows x n_dir x nv: the chunk's seeds; either may be NULL: zeros), d_dH (n_rows x n_dir x nv x nv) and
+ * d_dc (n_rows x n_dir x nv), pfc_dynamics_dual_device's outputs; d_dtau (n_rows x n_dir x nv).  One launch each: n_rows, or n_rows
+ * n_dir, one-wave workgroups, a lane per coordinate.  PFC_ERR_BAD_ARG before any launch: nv outside 1 .. PFC_MAX_NV_SOLVE, n_act
+ * outside 0 .. nv, n_seg < 1, n_scene < 1, n_rows negative or no multiple of n_scene, n_dir outside 1 .. 16, null buffer.
+ */
+int pfc_feedback_device(pfc_handle h, int n_rows, int n_scene, int nv, int n_act, int n_seg, const int *d_act, const double *d_kp,
+                        const double *d_kd, const double *d_a_max, const double *d_seg_t, const double *d_seg_q, const double *d_seg_ff,
+                        const double *d_t, const double *d_q, const double *d_v, const double *d_H, const double *d_c,
+                        const double *d_tau_in, double *d_tau_out, void *stream);
+int pfc_feedback_dual_device(pfc_handle h, int n_rows, int n_dir, int n_scene, int nv, int n_act, int n_seg, const int *d_act,
+                             const double *d_kp, const double *d_kd, const double *d_a_max, const double *d_seg_t, const double *d_seg_q,
+                             const double *d_t, const double *d_q, const double *d_v, const double *d_H, const double *d_dq,
+                             const double *d_dv, const double *d_dH, const double *d_dc, double *d_dtau, void *stream);
+/*
+ * pfc_radau_set_feedback: the law of the handle's batch (host arrays, the sizes above with the handle's n_scene and nv), copied into
+ * device blocks owned by the handle.  After pfc_radau_configure (PFC_ERR_STATE before it).  From then on, in every batch step of
+ * pfc_radau_step and pfc_radau_integrate, pfc_state_derivative_device on the 3 n_scene stage-scenes evaluates the law between the
+ * dynamics and the solve at the stage times, and every Jacobian chunk evaluates its partials (the first chunk its value as well) at
+ * the scenes' t, as calcJacobian! does; the solve reads the summed tau and, in a chunk, dtau.  One launch more per Newton pass, two
+ * per first chunk and one per later chunk, one per attempt for the stage times; nothing is read back.
+ * The stage times are filled once per attempt, behind the factorisation (h and the rule change only between attempts): row
+ * s n_scene + i is (c_s h_i) + t_i -- two roundings, no fma, the reference's table.c[i] * rr.step.h + t -- for s < NS(rule_i), t_i for
+ * every other row.  pfc_radau_stage_times: the 3 n_scene doubles the last attempt used (host; zeros before the first step with this law;
+ * PFC_ERR_STATE without a law).  The summed tau (3 n_scene x nv), its partials (n_scene x n_chunk x nv) and the stage times live in the
+ * law's own blocks: a handle without a law allocates what it allocated before.
+ * tau.  The held tau keeps its meaning and its block: pfc_radau_set_tau, the discrete controller, the program and pfc_radau_get_tau
+ * are what they were, and the law reads the held tau as its tau_in (NULL where none is in force).  The reference sums
+ * ((f - c) + tau_cont) + tau_disc (`rhs = f - c + tm.tau_ext + m.tau_ext`); the device sums (f - c) + (tau_cont + tau_disc): the
+ * two differ in the last bit.  A retired or parked scene is still evaluated (the shape is fixed) and still ignored: its x, t, h,
+ * rule and norms stay byte for byte.
+ * PFC_ERR_BAD_ARG, with a message and nothing changed (the previous law stays in force): a coordinate out of [0, nv), not strictly
+ * increasing, or owned by a floating or fixed joint; n_seg < 1; a gain that is not finite; a negative (or NaN) a_max; start times that
+ * decrease from index 1 or are NaN; setpoints or feed-forward that are not finite.  The new blocks are allocated before the old ones
+ * are freed: PFC_ERR_NOMEM leaves the previous law in force.  pfc_radau_configure drops the law; pfc_radau_set_state keeps it.
+ * pfc_radau_clear_feedback: the step is the step without a law again, launch for launch.  Only this law is built: arbitrary
+ * callbacks stay on the host, one batch step at a time.  Multi-device handles use their first device, as the step does.
+ */
+int pfc_radau_set_feedback(pfc_handle h, int n_act, const int *act, const double *kp, const double *kd, const double *a_max, int n_seg,
+                           const double *seg_t, const double *seg_q, const double *seg_ff);
+int pfc_radau_clear_feedback(pfc_handle h);
+int pfc_radau_stage_times(pfc_handle h, double *out);
 
 /*
  * The gripper program: the part of the reference's grip_control! that has memory (test/pencil.jl:35-116,147-173) -- a queue of

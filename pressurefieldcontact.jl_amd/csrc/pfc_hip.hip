@@ -31,6 +31,8 @@
 //                  (pfc_set_inertia, pfc_dynamics); k_accel: vdot = H^-1 ((f - c) + tau) by Cholesky (pfc_accelerations,
 //                  pfc_state_derivative); k_dynamics_dual / k_accel_dual: their partials for the seed directions of a Jacobian
 //                  chunk (pfc_dynamics_dual, pfc_accelerations_dual, pfc_state_derivative_dual_device[_more])
+//   pfc_feedback.h k_feedback / k_feedback_dual: the continuous joint feedback law between the dynamics and the solve, value and
+//                  partials (pfc_feedback_device, pfc_feedback_dual_device, pfc_radau_set_feedback); k_radau_stage_times
 //   pfc_multi.h    host code: multi-device handles (pfc_create_multi)
 // This file: mesh record preparation (k_prep_tri, k_prep_tet), per-item setup (k_setup_items), work-list management,
 // hipGraph capture / replay, the two-half evaluation and every extern "C" entry point.
@@ -212,6 +214,7 @@ __global__ void k_repose(int n_items, const double *__restrict__ pose, ItemRec *
 #include "pfc_dyn.h"
 #include "pfc_radau.h"
 #include "pfc_radau_program.h"
+#include "pfc_feedback.h"
 #include "pfc_radau_tables.h"
 
 }  // namespace pfc
@@ -457,6 +460,11 @@ enum RadauI { RI_RULE, RI_COOL, RI_ISTATE, RI_PERM, RI_INFO, RI_COUNT, RI_VINS, 
 // Parts of the controller's two blocks (pfc_radau_set_controller).
 enum RadauCD { CD_KP, CD_KD, CD_AMAX, CD_SEGT, CD_SEGQ, CD_SEGFF, CD_TLAST, CD_N };
 enum RadauCI { CI_ACT, CI_FIRES, CI_N };
+// Parts of the continuous feedback law's two blocks (pfc_radau_set_feedback).
+// FD_TAUS: the summed tau the solve reads, 3 n_scene x nv; FD_DDTAU: its partials, n_scene x n_chunk x nv; FD_TSTAGE: the stage
+// times, 3 n_scene.
+enum RadauFD { FD_KP, FD_KD, FD_AMAX, FD_SEGT, FD_SEGQ, FD_SEGFF, FD_TAUS, FD_DDTAU, FD_TSTAGE, FD_N };
+enum RadauFI { FI_ACT, FI_N };
 // Parts of the program's two blocks (pfc_radau_set_program).
 enum RadauPD { PD_DT, PD_Q, PD_SLIP, PD_STATE, PD_N };
 enum RadauPI { PI_GRIP, PI_CURSOR, PI_N };
@@ -730,6 +738,14 @@ struct pfc_context {
             } prog;
         } ctl;
         void drop_control() { ctl = Control(); }
+        // pfc_radau_set_feedback: the continuous law's tables and its workspace -- the summed tau, its partials, the stage times --
+        // (parts RadauFD, RadauFI) in two blocks of their own, replaced by the next pfc_radau_set_feedback and freed by
+        // pfc_radau_clear_feedback, pfc_radau_configure and with the handle: a handle without a law allocates what it allocated.
+        struct Feedback : PartBlocks<FD_N, FI_N, false> {
+            bool on = false, has_ff = false, has_amax = false;
+            int n_act = 0, n_seg = 0;
+        } fb;
+        void drop_feedback() { fb = Feedback(); }
     } radau;
 };
 
@@ -4242,6 +4258,97 @@ int pfc_accelerations_dual(pfc_handle h, int n_scene, int n_dir, const double *H
         return PFC_OK; });
 }
 
+// ---- the continuous feedback law (k_feedback, k_feedback_dual: pfc_feedback.h; the statements: include/pfc.h) -------------------------
+// What both parts check of the law's sizes and tables before any launch.
+static int feedback_check_law(pfc_context *h, const char *who, int nv, const FeedbackLaw &w) {
+    if (nv < 1 || nv > PFC_MAX_NV_SOLVE)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: nv is %d, the law takes 1 .. PFC_MAX_NV_SOLVE = %d coordinates", who, nv, PFC_MAX_NV_SOLVE);
+    if (w.n_act < 0 || w.n_act > nv) return fail(h, PFC_ERR_BAD_ARG, "%s: n_act is %d, 0 .. nv = %d", who, w.n_act, nv);
+    if (w.n_seg < 1) return fail(h, PFC_ERR_BAD_ARG, "%s: n_seg is %d, at least one segment", who, w.n_seg);
+    if (w.n_sched < 1) return fail(h, PFC_ERR_BAD_ARG, "%s: n_scene is %d, at least one scene's schedule", who, w.n_sched);
+    return PFC_OK;
+}
+
+static bool feedback_law_null(const FeedbackLaw &w) {
+    return (w.n_act > 0 && (!w.act || !w.kp || !w.kd || !w.seg_q)) || (w.n_seg > 1 && !w.seg_t) || !w.t;
+}
+
+static int feedback_launch(pfc_context *h, const FeedbackArgs &a, hipStream_t st) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_feedback, dim3((unsigned)a.n_rows), dim3(kFbWave), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+static int feedback_dual_launch(pfc_context *h, const FeedbackDualArgs &a, hipStream_t st) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_feedback_dual, dim3((unsigned)a.n_scene * (unsigned)a.n_dir), dim3(kFbWave), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+// The parts behind the public entries and the chains: sizes and buffers checked, then the launcher.
+static int feedback_checked(pfc_context *h, const char *who, const FeedbackArgs &a, hipStream_t st) {
+    const int rc = feedback_check_law(h, who, a.nv, a.w);
+    if (rc != PFC_OK) return rc;
+    if (a.n_rows < 0 || a.n_rows % a.w.n_sched != 0)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: n_rows is %d, a multiple >= 0 of n_scene = %d", who, a.n_rows, a.w.n_sched);
+    if (a.n_rows == 0) return PFC_OK;
+    if (feedback_law_null(a.w) || !a.q || !a.v || !a.H || !a.c || !a.w.tau) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    return feedback_launch(h, a, st);
+}
+
+static int feedback_dual_checked(pfc_context *h, const char *who, const FeedbackDualArgs &a, hipStream_t st) {
+    int rc = feedback_check_law(h, who, a.nv, a.w);
+    if (rc != PFC_OK || (rc = dual_dir_check(h, who, a.n_scene, a.n_dir)) != PFC_OK) return rc;
+    if (a.n_scene % a.w.n_sched != 0)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: n_rows is %d, a multiple of n_scene = %d", who, a.n_scene, a.w.n_sched);
+    if (a.n_scene == 0) return PFC_OK;
+    if (feedback_law_null(a.w) || !a.q || !a.v || (a.w.n_act > 0 && (!a.H || !a.dH || !a.dc)) || !a.w.dtau) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    return feedback_dual_launch(h, a, st);
+}
+
+// The law of a chained call on its value buffers: tau = law + V.tau into law->tau.
+static int feedback_of_call(pfc_context *h, const char *who, const StateCall &S, hipStream_t st) {
+    FeedbackArgs a{};
+    a.w = *S.law; a.n_rows = S.n_scene; a.nv = h->kin.nv;
+    a.q = S.val.q; a.v = S.val.v; a.H = S.val.H; a.c = S.val.c; a.tau_in = S.val.tau;
+    return feedback_checked(h, who, a, st);
+}
+
+static int feedback_dual_of_call(pfc_context *h, const char *who, const StateCall &S, hipStream_t st) {
+    FeedbackDualArgs a{};
+    a.w = *S.law; a.n_scene = S.n_scene; a.n_dir = S.n_dir; a.nv = h->kin.nv;
+    a.q = S.val.q; a.v = S.val.v; a.H = S.val.H; a.dq = S.par.q; a.dv = S.par.v; a.dH = S.par.H; a.dc = S.par.c;
+    return feedback_dual_checked(h, who, a, st);
+}
+
+int pfc_feedback_device(pfc_handle h, int n_rows, int n_scene, int nv, int n_act, int n_seg, const int *d_act, const double *d_kp,
+                        const double *d_kd, const double *d_a_max, const double *d_seg_t, const double *d_seg_q, const double *d_seg_ff,
+                        const double *d_t, const double *d_q, const double *d_v, const double *d_H, const double *d_c,
+                        const double *d_tau_in, double *d_tau_out, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    FeedbackArgs a{};
+    a.w.n_sched = n_scene; a.w.n_act = n_act; a.w.n_seg = n_seg; a.w.act = d_act; a.w.kp = d_kp; a.w.kd = d_kd; a.w.a_max = d_a_max;
+    a.w.seg_t = d_seg_t; a.w.seg_q = d_seg_q; a.w.seg_ff = d_seg_ff; a.w.t = d_t; a.w.tau = d_tau_out;
+    a.n_rows = n_rows; a.nv = nv; a.q = d_q; a.v = d_v; a.H = d_H; a.c = d_c; a.tau_in = d_tau_in;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        return feedback_checked(c, "pfc_feedback_device", a, stream ? (hipStream_t)stream : c->stream); });
+}
+
+int pfc_feedback_dual_device(pfc_handle h, int n_rows, int n_dir, int n_scene, int nv, int n_act, int n_seg, const int *d_act,
+                             const double *d_kp, const double *d_kd, const double *d_a_max, const double *d_seg_t, const double *d_seg_q,
+                             const double *d_t, const double *d_q, const double *d_v, const double *d_H, const double *d_dq,
+                             const double *d_dv, const double *d_dH, const double *d_dc, double *d_dtau, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    FeedbackDualArgs a{};
+    a.w.n_sched = n_scene; a.w.n_act = n_act; a.w.n_seg = n_seg; a.w.act = d_act; a.w.kp = d_kp; a.w.kd = d_kd; a.w.a_max = d_a_max;
+    a.w.seg_t = d_seg_t; a.w.seg_q = d_seg_q; a.w.t = d_t; a.w.dtau = d_dtau;
+    a.n_scene = n_rows; a.n_dir = n_dir; a.nv = nv; a.q = d_q; a.v = d_v; a.H = d_H; a.dq = d_dq; a.dv = d_dv; a.dH = d_dH; a.dc = d_dc;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        return feedback_dual_checked(c, "pfc_feedback_dual_device", a, stream ? (hipStream_t)stream : c->stream); });
+}
+
 // What both Dual chains check before the first launch, beyond what the Dual evaluation checks itself: the inertias, the Dual LDS
 // limit, the nv cap and n_dir.
 static int state_derivative_dual_check(pfc_context *c, const char *who, int n_scene, int n_dir) {
@@ -4710,8 +4817,9 @@ static int state_derivative(pfc_context *h, const StateCall &S) {
     if ((rc = eval_state(h, S)) != PFC_OK) return rc;
     return on_shard(h, c, [&](pfc_context *c1) {
         const hipStream_t st = call_stream(c1, S);
-        const int r = dyn_launch(c1, S.n_scene, V.q, V.v, V.x_w_b, V.twist_w_b, V.qdot, V.H, V.c, st);
-        return r != PFC_OK ? r : accel_launch(c1, S.n_scene, V.H, V.c, V.f, V.tau, V.vdot, V.info, st); });
+        int r = dyn_launch(c1, S.n_scene, V.q, V.v, V.x_w_b, V.twist_w_b, V.qdot, V.H, V.c, st);
+        if (r == PFC_OK && S.law) r = feedback_of_call(c1, who, S, st);
+        return r != PFC_OK ? r : accel_launch(c1, S.n_scene, V.H, V.c, V.f, S.law ? S.law->tau : V.tau, V.vdot, V.info, st); });
 }
 
 // `more`: another chunk of directions at the point of the last checked first call -- only partials are written, the values are read.
@@ -4763,8 +4871,12 @@ static int state_derivative_dual(pfc_context *h, const StateCall &S, bool more) 
         if (r != PFC_OK) return r;
         r = dyn_dual_launch(c1, S.n_scene, S.n_dir, V.q, V.v, P.q, P.v, V.x_w_b, V.twist_w_b, P.x_w_b, P.twist_w_b, P.qdot, P.H, P.c, st);
         if (r != PFC_OK) return r;
-        return accel_dual_launch(c1, S.n_scene, S.n_dir, V.H, V.c, V.f, V.tau, P.H, P.c, P.f, P.tau, more ? nullptr : V.vdot, P.vdot,
-                                 more ? nullptr : V.info, st); });
+        if (S.law) {      // the law's value on a first chunk only (a `more` chunk reads what it left), its partials on every chunk
+            if (!more && (r = feedback_of_call(c1, who, S, st)) != PFC_OK) return r;
+            if ((r = feedback_dual_of_call(c1, who, S, st)) != PFC_OK) return r;
+        }
+        return accel_dual_launch(c1, S.n_scene, S.n_dir, V.H, V.c, V.f, S.law ? S.law->tau : V.tau, P.H, P.c, P.f,
+                                 S.law ? S.law->dtau : P.tau, more ? nullptr : V.vdot, P.vdot, more ? nullptr : V.info, st); });
 }
 
 // The six entries: one fill of the record each -- the only place a parameter position meets a field name -- and one call.

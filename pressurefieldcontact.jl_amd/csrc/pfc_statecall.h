@@ -16,11 +16,26 @@ struct StateBufs {
     int *info = nullptr;
 };
 
+// The continuous feedback law of a call (pfc_feedback_device's arguments; the kernels: pfc_feedback.h).  The tables have the shapes
+// of pfc_radau_set_controller's for n_sched scenes; row r of a call reads the schedule of scene r % n_sched.
+struct FeedbackLaw {
+    int n_sched = 0, n_act = 0, n_seg = 0;
+    const int *act = nullptr;                                                   // n_act
+    const double *kp = nullptr, *kd = nullptr, *a_max = nullptr;                // n_act; a_max null: no clamp
+    const double *seg_t = nullptr, *seg_q = nullptr, *seg_ff = nullptr;         // n_sched x n_seg, x n_act, x nv; seg_ff null: zeros
+    const double *t = nullptr;                                                  // one time per row
+    double *tau = nullptr;       // rows x nv: the law plus the call's tau -- what the solve reads
+    double *dtau = nullptr;      // n_scene x n_dir x nv: its partials (Dual calls)
+};
+
 struct StateCall {
     int n_items = 0, n_dir = 0, n_scene = 0;
     const int *ins_ids = nullptr, *scene = nullptr;
     void *stream = nullptr;      // the caller's stream, null: the context's own
     StateBufs val, par;          // the values, and their partials (Dual calls)
+    // null in every public entry: the chain launches what it launched without one.  Set (the Radau driver): the law is evaluated
+    // between the dynamics and the solve, which then reads law->tau and, in a Dual call, law->dtau in place of val.tau and par.tau
+    const FeedbackLaw *law = nullptr;
 };
 
 // A buffer that an entry declares const -- the values of a `_more` entry, the body states of the `_bodies` entries -- as the record's

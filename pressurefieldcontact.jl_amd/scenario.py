@@ -1359,6 +1359,57 @@ class MechanismScenario:
         t_last, fires = self._radau_host_ctl
         return t_last.copy(), fires.copy()
 
+    # ---- continuous feedback (include/pfc.h, pfc_radau_set_feedback; the scalar statements: feedback_pd, feedback_pd_partials) ---
+    def radau_set_feedback(self, act, kp, kd, seg_t, seg_q, seg_ff=None, a_max=None):
+        """pfc_radau_set_feedback: radau_set_controller's computed-torque PD law evaluated inside the differential equation -- at
+        every stage evaluation with that stage's time, and with its partials in every Jacobian chunk -- and added to the held tau
+        (radau_set_tau, the discrete controller).  The arrays are radau_set_controller's, without dt and t_last0."""
+        n = getattr(self, "_radau_n_scene", 0)
+        nv = self.mechanism_sizes()[2]
+        act_a = np.ascontiguousarray(act, dtype=np.int32).reshape(-1)
+        na = act_a.size
+        vec = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (na,)))
+        kp_a, kd_a = vec(kp), vec(kd)
+        am_a = None if a_max is None else vec(a_max)
+        st = np.asarray(seg_t, dtype=np.float64)
+        n_seg = st.shape[-1] if st.ndim else 1
+        st_a = np.ascontiguousarray(np.broadcast_to(st.reshape(-1, n_seg), (n, n_seg)))
+        sq_a = np.zeros((n, n_seg, 0)) if na == 0 else \
+            np.ascontiguousarray(np.broadcast_to(np.asarray(seg_q, dtype=np.float64).reshape((-1, n_seg, na)), (n, n_seg, na)))
+        ff_a = None if seg_ff is None else np.ascontiguousarray(
+            np.broadcast_to(np.asarray(seg_ff, dtype=np.float64).reshape((-1, n_seg, nv)), (n, n_seg, nv)))
+        p = lambda a: None if a is None else a.ctypes.data_as(_dp)
+        self._check(_lib.lib().pfc_radau_set_feedback(self._h, int(na), act_a.ctypes.data_as(_ip), p(kp_a), p(kd_a), p(am_a), int(n_seg),
+                                                      p(st_a), p(sq_a), p(ff_a)))
+
+    def radau_clear_feedback(self):
+        """pfc_radau_clear_feedback: the step is the step without a continuous law again."""
+        self._check(_lib.lib().pfc_radau_clear_feedback(self._h))
+
+    def radau_stage_times(self):
+        """pfc_radau_stage_times: (3, n_scene), the times at which the last attempt evaluated the continuous law: row s of scene i
+        is (c_s h_i) + t_i for s < NS(rule_i) and t_i otherwise.  With a law set (the library says so otherwise)."""
+        out = np.zeros((3, getattr(self, "_radau_n_scene", 0)))
+        self._check(_lib.lib().pfc_radau_stage_times(self._h, out.ctypes.data_as(_dp)))
+        return out
+
+    def feedback_device(self, n_rows: int, n_scene: int, nv: int, n_act: int, n_seg: int, d_act: int, d_kp: int, d_kd: int, d_a_max: int,
+                        d_seg_t: int, d_seg_q: int, d_seg_ff: int, d_t: int, d_q: int, d_v: int, d_H: int, d_c: int, d_tau_in: int,
+                        d_tau_out: int, stream: int = 0):
+        """pfc_feedback_device: the law's value on raw device addresses (0: NULL for d_a_max, d_seg_ff, d_tau_in and, with one
+        segment, d_seg_t); asynchronous on `stream`."""
+        a = [d_act, d_kp, d_kd, d_a_max, d_seg_t, d_seg_q, d_seg_ff, d_t, d_q, d_v, d_H, d_c, d_tau_in, d_tau_out, stream]
+        self._check(_lib.lib().pfc_feedback_device(self._h, int(n_rows), int(n_scene), int(nv), int(n_act), int(n_seg), *[x or None for x in a]))
+
+    def feedback_dual_device(self, n_rows: int, n_dir: int, n_scene: int, nv: int, n_act: int, n_seg: int, d_act: int, d_kp: int,
+                             d_kd: int, d_a_max: int, d_seg_t: int, d_seg_q: int, d_t: int, d_q: int, d_v: int, d_H: int, d_dq: int,
+                             d_dv: int, d_dH: int, d_dc: int, d_dtau: int, stream: int = 0):
+        """pfc_feedback_dual_device: the law's partials along n_dir directions on raw device addresses (0: NULL for d_a_max, d_dq,
+        d_dv); asynchronous on `stream`."""
+        a = [d_act, d_kp, d_kd, d_a_max, d_seg_t, d_seg_q, d_t, d_q, d_v, d_H, d_dq, d_dv, d_dH, d_dc, d_dtau, stream]
+        self._check(_lib.lib().pfc_feedback_dual_device(self._h, int(n_rows), int(n_dir), int(n_scene), int(nv), int(n_act), int(n_seg),
+                                                        *[x or None for x in a]))
+
     # ---- the gripper program (include/pfc.h, pfc_radau_set_program; the scalar statement: gripper_program_step below) -----------
     def _program_arrays(self, prog_dt, prog_q, prog_slip):
         """(n_ins, prog_dt (n_scene, n_ins), prog_q (n_scene, n_ins, n_act), prog_slip (n_scene, n_ins)): leading scene axes broadcast;
@@ -1481,7 +1532,7 @@ class MechanismScenario:
         self._radau_host_ctl = (t_last, fires)
         self._radau_host_tau = tau
 
-    def integrate_scenario_radau(self, t_final, max_steps: int = 1000, discrete_controller=None):
+    def integrate_scenario_radau(self, t_final, max_steps: int = 1000, discrete_controller=None, continuous_controller=None):
         """The reference's integrate_scenario_radau for every scene of the batch: from the state as it is, each scene steps while
         t_final < t is false (t_final a scalar or (n_scene,); the last step is not shortened) and for at most max_steps steps.  Returns
         per scene (data_time, data_state), the reference's return value: the start and every step.  A scene whose step size fell
@@ -1491,14 +1542,23 @@ class MechanismScenario:
         t_last0) is the reference's general DiscreteControl instead, on the host: before every batch step, for every live scene,
         `while t_last <= t: t_last += dt; tau[scene] = fn(x, t, scene)` (at most RADAU_MAX_FIRES additions per step), then
         radau_set_tau and one radau_step -- any Python law, one batch step at a time, x downloaded and tau uploaded per step.  tau
-        starts from zeros; t_last0 None is every scene's t now.  Not to be combined with radau_set_controller."""
+        starts from zeros; t_last0 None is every scene's t now.  Not to be combined with radau_set_controller.
+        continuous_controller: the reference's continuous slot, here the tables of radau_set_feedback as a dict (act, kp, kd, seg_t,
+        seg_q and optionally seg_ff, a_max): the law is set for this run -- evaluated on the device inside the differential
+        equation, with either kind of discrete controller beside it -- and cleared when the run ends."""
         n = self._radau_n_scene
         tf = np.ascontiguousarray(np.broadcast_to(np.asarray(t_final, dtype=np.float64), (n,)))
-        self.radau_set_end(tf, int(max_steps) + 1)
-        if discrete_controller is None:
-            self.radau_integrate(int(max_steps))
-        else:
-            self._integrate_with_callback(tf, int(max_steps), discrete_controller)
+        if continuous_controller is not None:
+            self.radau_set_feedback(**continuous_controller)
+        try:
+            self.radau_set_end(tf, int(max_steps) + 1)
+            if discrete_controller is None:
+                self.radau_integrate(int(max_steps))
+            else:
+                self._integrate_with_callback(tf, int(max_steps), discrete_controller)
+        finally:
+            if continuous_controller is not None:
+                self.radau_clear_feedback()
         rows = self.radau_trajectory_rows()
         out = [self.radau_trajectory(s, rows[s]) for s in range(n)]
         # a scene stops by parking -- past its end, or its rows full -- or by retiring with exit flag 5
@@ -1877,6 +1937,50 @@ def computed_torque_pd(q, v, H, c, t, act, kp, kd, seg_t, seg_q, seg_ff=None, a_
             s = s + float(H[co][cb]) * acc[b]
         tau[co] = (s + float(c[co])) + ff[co]
     return tau
+
+
+# ---- continuous feedback: the scalar statements of include/pfc.h (pfc_feedback_device, pfc_feedback_dual_device) in Python floats ----
+def feedback_pd(q, v, H, c, t, tau_in, act, kp, kd, seg_t, seg_q, seg_ff=None, a_max=None):
+    """The continuous law of one row: computed_torque_pd at (q, v, H, c, t) plus tau_in (nv floats, or None).  An actuated
+    coordinate: law_a + tau_in_a; any other: ff[k][i] + tau_in_i with seg_ff given, tau_in_i copied (a signed zero survives) without;
+    tau_in None: the law alone, +0.0 where there is none."""
+    law = computed_torque_pd(q, v, H, c, t, act, kp, kd, seg_t, seg_q, seg_ff, a_max)
+    if tau_in is None:
+        return law
+    actuated = set(int(co) for co in act)
+    return [law[i] + float(tau_in[i]) if (i in actuated or seg_ff is not None) else float(tau_in[i]) for i in range(len(law))]
+
+
+def feedback_pd_partials(q, v, H, t, dq, dv, dH, dc, act, kp, kd, seg_t, seg_q, a_max=None):
+    """The partials of feedback_pd along one direction: dq, dv (nv, or None: zeros) the seeds, dH (nv x nv) and dc (nv) the partials
+    of H and c.  The value statement on (value, partial) numbers with the product rule d(a b) = da b + a db; t, the tables and
+    tau_in are constants.  dacc_a = (-(kd_a dv_a)) - kp_a dq_a, 0.0 where the value's clamp engaged; dtau_a = ((0 + (dH[a][b0]
+    acc_b0 + H[a][b0] dacc_b0)) + ..) + dc_a; 0.0 for a coordinate that is not actuated.  Returns dtau (nv floats)."""
+    t = float(t)
+    nv = len(dc)
+    k = sum(1 for j in range(1, len(seg_t)) if float(seg_t[j]) <= t)
+    acc, dacc = [], []
+    for a, co in enumerate(act):
+        e = float(q[co]) - float(seg_q[k][a])
+        x = (-(float(kd[a]) * float(v[co]))) - float(kp[a]) * e
+        dqa = 0.0 if dq is None else float(dq[co])
+        dva = 0.0 if dv is None else float(dv[co])
+        dx = (-(float(kd[a]) * dva)) - float(kp[a]) * dqa
+        if a_max is not None:
+            am = float(a_max[a])
+            if x < -am:
+                x, dx = -am, 0.0
+            if x > am:
+                x, dx = am, 0.0
+        acc.append(x)
+        dacc.append(dx)
+    dtau = [0.0] * nv
+    for co in act:
+        s = 0.0
+        for b, cb in enumerate(act):
+            s = s + (float(dH[co][cb]) * acc[b] + float(H[co][cb]) * dacc[b])
+        dtau[co] = s + float(dc[co])
+    return dtau
 
 
 # ---- the gripper program: the scalar statement of include/pfc.h (pfc_radau_program_device) in Python floats -------------------------
