@@ -1333,7 +1333,7 @@ int pfc_feedback_dual_device(pfc_handle h, int n_rows, int n_dir, int n_scene, i
  * The stage times are filled once per attempt, behind the factorisation (h and the rule change only between attempts): row
  * s n_scene + i is (c_s h_i) + t_i -- two roundings, no fma, the reference's table.c[i] * rr.step.h + t -- for s < NS(rule_i), t_i for
  * every other row.  pfc_radau_stage_times: the 3 n_scene doubles the last attempt used (host; zeros before the first step with this law;
- * PFC_ERR_STATE without a law).  The summed tau (3 n_scene x nv), its partials (n_scene x n_chunk x nv) and the stage times live in the
+ * PFC_ERR_STATE without a law and without body wrenches, below).  The summed tau (3 n_scene x nv), its partials (n_scene x n_chunk x nv) and the stage times live in the
  * law's own blocks: a handle without a law allocates what it allocated before.
  * tau.  The held tau keeps its meaning and its block: pfc_radau_set_tau, the discrete controller, the program and pfc_radau_get_tau
  * are what they were, and the law reads the held tau as its tau_in (NULL where none is in force).  The reference sums
@@ -1351,6 +1351,71 @@ int pfc_radau_set_feedback(pfc_handle h, int n_act, const int *act, const double
                            const double *seg_t, const double *seg_q, const double *seg_ff);
 int pfc_radau_clear_feedback(pfc_handle h);
 int pfc_radau_stage_times(pfc_handle h, double *out);
+
+/*
+ * Applied body wrenches: a moment and a force on a body, acting at a point of the body's frame, on a per-scene schedule of
+ * piecewise-constant segments -- a push on a box, a disturbance on a held object, a thruster that turns with its body, a random shove
+ * per scene.  With the reference one writes J' w in continuous_controller; here the projection runs on the device inside the
+ * differential equation, at every stage evaluation with that stage's time, and its partials -- the geometric stiffness of a
+ * world-frame force at an offset point, the rotation of a body-frame follower load -- on the Dual state of every Jacobian chunk, so
+ * that they are part of the matrix Radau factors.  Plain Float64, no fma, in the written order.
+ * A call applies n_w wrenches.  Per wrench k, shared by all scenes: body[k] in [0, n_body); frame[k], 0: the components are along
+ * the world axes, 1: along the body's axes, so that the load turns with the body; point[k], 3 doubles in the body frame.  Per scene
+ * and segment: seg_w[scene][seg][k] = [moment (3); force (3)].
+ * The value, per row (a scene or a stage-scene; row r reads the schedule of scene r % n_scene), with x_w_b = (R, t) (R column-major)
+ * of body[k] of the row and J its Jacobian (pfc_kinematics_device's d_x_w_b and d_jac):
+ *   seg = the number of j in 1 .. n_seg - 1 with seg_t[j] <= t  (the feedback law's search: a time on a start reads the new segment)
+ *   [m; f] = seg_w[scene][seg][k], p = point[k]
+ *   r_i = ((R_i0 p0 + R_i1 p1) + R_i2 p2) + t_i                                  the application point in world
+ *   frame 1: F_i = (R_i0 f0 + R_i1 f1) + R_i2 f2, M_i likewise from m;   frame 0: F = f, M = m
+ *   W = [M_i + (r x F)_i; F], (r x F)_0 = r1 F2 - r2 F1, (r x F)_1 = r2 F0 - r0 F2, (r x F)_2 = r0 F1 - r1 F0 (pfc_dynamics_device's
+ *     cross product): the wrench in world about the world origin; frame 1 is transform(wrench, (R, r)) of the scatter
+ *   tau_k,j = ((J0j W0 + J1j W1) + J2j W2) + ((J3j W3 + J4j W4) + J5j W5)        torque! for coordinate j
+ *   tau_out_j = (..((tau_in_j + tau_0,j) + tau_1,j) ..), k ascending; where tau_in is NULL the sum starts from +0.0; n_w = 0 copies
+ *     tau_in (a signed zero survives) or writes +0.0
+ * The partials, per (row, direction): the same statements instantiated on the (value, partial) number of the Dual kinematics, with
+ * d(a b) = da b + a db, sums componentwise, no fma; x_w_b and J are {value, dx_w_b or djac of pfc_kinematics_dual_device}; t, the
+ * tables, the points and the loads are constants {x, 0.0}:
+ *   dtau_out_j = (..((dtau_in_j + d tau_0,j) + d tau_1,j) ..); where dtau_in is NULL the sum starts from +0.0
+ * pfc_body_wrench_device, pfc_body_wrench_dual_device: the parts on caller buffers and a caller stream (NULL: the handle's),
+ * asynchronous, like pfc_feedback_device; they read nothing of the handle but its device and stream.  d_body, d_frame (n_w ints; the
+ * caller guarantees 0 <= body[k] < n_body -- the kernels follow it unchecked -- and a frame other than 1 is read as 0), d_point (n_w x
+ * 3), d_seg_t (n_scene x n_seg; may be NULL with n_seg = 1; entry 0 of a scene is not read), d_seg_w (n_scene x n_seg x n_w x 6), d_t
+ * (n_rows), d_x_w_b (n_rows n_body x 12), d_jac (n_rows n_body x nv x 6), d_tau_in (n_rows x nv, or NULL), d_tau_out (n_rows x nv; may
+ * be d_tau_in).  The Dual part: d_dx_w_b (n_rows n_body x n_dir x 12), d_djac (n_rows n_body x n_dir x nv x 6), d_dtau_in (n_rows x
+ * n_dir x nv, or NULL), d_dtau (n_rows x n_dir x nv).  One launch each: n_rows, or n_rows n_dir, one-wave workgroups, a lane per
+ * coordinate.  PFC_ERR_BAD_ARG before any launch: nv outside 1 .. PFC_MAX_NV_SOLVE, n_body < 1, n_w < 0, n_seg < 1, n_scene < 1,
+ * n_rows negative or no multiple of n_scene, n_dir outside 1 .. 16, null buffer (with n_w = 0 the tables and the kinematics may be
+ * NULL).
+ */
+int pfc_body_wrench_device(pfc_handle h, int n_rows, int n_scene, int n_body, int nv, int n_w, int n_seg, const int *d_body,
+                           const int *d_frame, const double *d_point, const double *d_seg_t, const double *d_seg_w, const double *d_t,
+                           const double *d_x_w_b, const double *d_jac, const double *d_tau_in, double *d_tau_out, void *stream);
+int pfc_body_wrench_dual_device(pfc_handle h, int n_rows, int n_dir, int n_scene, int n_body, int nv, int n_w, int n_seg,
+                                const int *d_body, const int *d_frame, const double *d_point, const double *d_seg_t,
+                                const double *d_seg_w, const double *d_t, const double *d_x_w_b, const double *d_jac,
+                                const double *d_dx_w_b, const double *d_djac, const double *d_dtau_in, double *d_dtau, void *stream);
+/*
+ * pfc_radau_set_body_wrenches: the wrenches of the handle's batch (host arrays, the sizes above with the handle's n_scene and the
+ * mechanism's n_body), copied into device blocks owned by the handle.  After pfc_radau_configure (PFC_ERR_STATE before it).  From
+ * then on, in every batch step, the chain of the 3 n_scene stage-scenes evaluates them after the dynamics and after the law, if one
+ * is set, at the stage times, and every Jacobian chunk evaluates their partials (the first chunk their value as well) at the scenes'
+ * t; their tau_in is the law's summed tau where a law is set and the held tau otherwise, their dtau_in the law's partials or none,
+ * and the solve reads their outputs.  The right-hand side is therefore (f - c) + ((law + held) + ext_0 + ext_1 + ..), summed left to
+ * right.  One launch more per Newton pass, two per first chunk, one per later chunk; the stage times (pfc_radau_set_feedback) are
+ * filled once per attempt when a law or wrenches are set, and pfc_radau_stage_times answers in both cases.  The summed tau, its
+ * partials and, while no law is set, the stage times live in the wrenches' own blocks: a handle without wrenches allocates what it
+ * allocated before.  A retired or parked scene is still evaluated and still ignored.
+ * PFC_ERR_BAD_ARG, with a message and nothing changed (the previous wrenches stay in force): n_w < 0; n_seg < 1; a body outside
+ * [0, n_body); a frame other than 0 or 1; a point or a load that is not finite; start times that decrease from index 1 or are NaN.
+ * The new blocks are allocated before the old ones are freed: PFC_ERR_NOMEM leaves the previous wrenches in force.
+ * pfc_radau_configure drops the wrenches; pfc_radau_set_state keeps them.  pfc_radau_clear_body_wrenches: the step is the step
+ * without wrenches again, launch for launch.  A wrench depends on the state through the body's pose only: springs, drag and
+ * arbitrary callbacks stay on the host.  Multi-device handles use their first device, as the step does.
+ */
+int pfc_radau_set_body_wrenches(pfc_handle h, int n_w, const int *body, const int *frame, const double *point, int n_seg,
+                                const double *seg_t, const double *seg_w);
+int pfc_radau_clear_body_wrenches(pfc_handle h);
 
 /*
  * The gripper program: the part of the reference's grip_control! that has memory (test/pencil.jl:35-116,147-173) -- a queue of

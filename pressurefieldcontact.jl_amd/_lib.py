@@ -154,6 +154,10 @@ SIGNATURES = {
     "pfc_radau_set_feedback": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp]),
     "pfc_radau_clear_feedback": (C.c_int, [C.c_void_p]),
     "pfc_radau_stage_times": (C.c_int, [C.c_void_p, _dp]),
+    "pfc_body_wrench_device": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 11),
+    "pfc_body_wrench_dual_device": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 13),
+    "pfc_radau_set_body_wrenches": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _dp, C.c_int, _dp, _dp]),
+    "pfc_radau_clear_body_wrenches": (C.c_int, [C.c_void_p]),
 }
 
 
@@ -165,7 +169,7 @@ class PFCError(RuntimeError):
 
 def build(force: bool = False) -> str:
     """Compile csrc/pfc_hip.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("pfc_hip.hip", "pfc_tree.cpp", "pfc_sort.hip", "pfc_kernels.h", "pfc_bp.h", "pfc_np.h", "pfc_br.h", "pfc_dual.h", "pfc_fused.h", "pfc_clip.h", "pfc_multi.h", "pfc_partition.h", "pfc_sort.h", "pfc_surface.h", "pfc_surface_fric.h", "pfc_scatter.h", "pfc_ljac.h", "pfc_bodies.h", "pfc_kin.h", "pfc_dyn.h", "pfc_radau.h", "pfc_radau_tables.h", "pfc_radau_program.h", "pfc_feedback.h", "pfc_radau_host.h", "pfc_hostblocks.h", "pfc_statecall.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("pfc_hip.hip", "pfc_tree.cpp", "pfc_sort.hip", "pfc_kernels.h", "pfc_bp.h", "pfc_np.h", "pfc_br.h", "pfc_dual.h", "pfc_fused.h", "pfc_clip.h", "pfc_multi.h", "pfc_partition.h", "pfc_sort.h", "pfc_surface.h", "pfc_surface_fric.h", "pfc_scatter.h", "pfc_ljac.h", "pfc_bodies.h", "pfc_kin.h", "pfc_dyn.h", "pfc_radau.h", "pfc_radau_tables.h", "pfc_radau_program.h", "pfc_feedback.h", "pfc_body_wrench.h", "pfc_radau_host.h", "pfc_hostblocks.h", "pfc_statecall.h")]
     srcs.append(os.path.join(os.path.dirname(HERE), "include", "pfc.h"))
     srcs.append(os.path.abspath(__file__))      # the compiler flags live here
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)

@@ -33,6 +33,8 @@
 //                  chunk (pfc_dynamics_dual, pfc_accelerations_dual, pfc_state_derivative_dual_device[_more])
 //   pfc_feedback.h k_feedback / k_feedback_dual: the continuous joint feedback law between the dynamics and the solve, value and
 //                  partials (pfc_feedback_device, pfc_feedback_dual_device, pfc_radau_set_feedback); k_radau_stage_times
+//   pfc_body_wrench.h k_body_wrench / k_body_wrench_dual: applied body wrenches projected into tau behind the law, value and
+//                  partials (pfc_body_wrench_device, pfc_body_wrench_dual_device, pfc_radau_set_body_wrenches)
 //   pfc_multi.h    host code: multi-device handles (pfc_create_multi)
 // This file: mesh record preparation (k_prep_tri, k_prep_tet), per-item setup (k_setup_items), work-list management,
 // hipGraph capture / replay, the two-half evaluation and every extern "C" entry point.
@@ -215,6 +217,7 @@ __global__ void k_repose(int n_items, const double *__restrict__ pose, ItemRec *
 #include "pfc_radau.h"
 #include "pfc_radau_program.h"
 #include "pfc_feedback.h"
+#include "pfc_body_wrench.h"
 #include "pfc_radau_tables.h"
 
 }  // namespace pfc
@@ -465,6 +468,11 @@ enum RadauCI { CI_ACT, CI_FIRES, CI_N };
 // times, 3 n_scene.
 enum RadauFD { FD_KP, FD_KD, FD_AMAX, FD_SEGT, FD_SEGQ, FD_SEGFF, FD_TAUS, FD_DDTAU, FD_TSTAGE, FD_N };
 enum RadauFI { FI_ACT, FI_N };
+// Parts of the applied body wrenches' two blocks (pfc_radau_set_body_wrenches).
+// WD_TAUS: the summed tau the solve reads, 3 n_scene x nv; WD_DDTAU: its partials, n_scene x n_chunk x nv; WD_TSTAGE: the stage
+// times, 3 n_scene, used while no law is set (with a law its FD_TSTAGE is).
+enum RadauWD { WD_POINT, WD_SEGT, WD_SEGW, WD_TAUS, WD_DDTAU, WD_TSTAGE, WD_N };
+enum RadauWI { WI_BODY, WI_FRAME, WI_N };
 // Parts of the program's two blocks (pfc_radau_set_program).
 enum RadauPD { PD_DT, PD_Q, PD_SLIP, PD_STATE, PD_N };
 enum RadauPI { PI_GRIP, PI_CURSOR, PI_N };
@@ -746,6 +754,13 @@ struct pfc_context {
             int n_act = 0, n_seg = 0;
         } fb;
         void drop_feedback() { fb = Feedback(); }
+        // pfc_radau_set_body_wrenches: the wrenches' tables and their workspace (parts RadauWD, RadauWI) in two blocks of their
+        // own, with the life cycle of the law's: a handle without wrenches allocates what it allocated.
+        struct Push : PartBlocks<WD_N, WI_N, false> {
+            bool on = false;
+            int n_w = 0, n_seg = 0;
+        } push;
+        void drop_push() { push = Push(); }
     } radau;
 };
 
@@ -4349,6 +4364,103 @@ int pfc_feedback_dual_device(pfc_handle h, int n_rows, int n_dir, int n_scene, i
         return feedback_dual_checked(c, "pfc_feedback_dual_device", a, stream ? (hipStream_t)stream : c->stream); });
 }
 
+// ---- applied body wrenches (k_body_wrench, k_body_wrench_dual: pfc_body_wrench.h; the statements: include/pfc.h) ------------------------
+// What both parts check of the sizes and tables before any launch.
+static int body_wrench_check(pfc_context *h, const char *who, int nv, const BodyWrenches &w) {
+    if (nv < 1 || nv > PFC_MAX_NV_SOLVE)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: nv is %d, the wrenches take 1 .. PFC_MAX_NV_SOLVE = %d coordinates", who, nv, PFC_MAX_NV_SOLVE);
+    if (w.n_body < 1) return fail(h, PFC_ERR_BAD_ARG, "%s: n_body is %d, at least one body", who, w.n_body);
+    if (w.n_w < 0) return fail(h, PFC_ERR_BAD_ARG, "%s: n_w is %d, not negative", who, w.n_w);
+    if (w.n_seg < 1) return fail(h, PFC_ERR_BAD_ARG, "%s: n_seg is %d, at least one segment", who, w.n_seg);
+    if (w.n_sched < 1) return fail(h, PFC_ERR_BAD_ARG, "%s: n_scene is %d, at least one scene's schedule", who, w.n_sched);
+    return PFC_OK;
+}
+
+static bool body_wrench_null(const BodyWrenches &w) {
+    return (w.n_w > 0 && (!w.body || !w.frame || !w.point || !w.seg_w)) || (w.n_seg > 1 && !w.seg_t) || !w.t;
+}
+
+static int body_wrench_launch(pfc_context *h, const BodyWrenchArgs &a, hipStream_t st) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_body_wrench, dim3((unsigned)a.n_rows), dim3(kBwWave), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+static int body_wrench_dual_launch(pfc_context *h, const BodyWrenchDualArgs &a, hipStream_t st) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_body_wrench_dual, dim3((unsigned)a.n_scene * (unsigned)a.n_dir), dim3(kBwWave), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    return PFC_OK;
+}
+
+// The parts behind the public entries and the chains: sizes and buffers checked, then the launcher.
+static int body_wrench_checked(pfc_context *h, const char *who, const BodyWrenchArgs &a, hipStream_t st) {
+    const int rc = body_wrench_check(h, who, a.nv, a.w);
+    if (rc != PFC_OK) return rc;
+    if (a.n_rows < 0 || a.n_rows % a.w.n_sched != 0)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: n_rows is %d, a multiple >= 0 of n_scene = %d", who, a.n_rows, a.w.n_sched);
+    if (a.n_rows == 0) return PFC_OK;
+    if (body_wrench_null(a.w) || (a.w.n_w > 0 && (!a.x_w_b || !a.jac)) || !a.w.tau) return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    return body_wrench_launch(h, a, st);
+}
+
+static int body_wrench_dual_checked(pfc_context *h, const char *who, const BodyWrenchDualArgs &a, hipStream_t st) {
+    int rc = body_wrench_check(h, who, a.nv, a.w);
+    if (rc != PFC_OK || (rc = dual_dir_check(h, who, a.n_scene, a.n_dir)) != PFC_OK) return rc;
+    if (a.n_scene % a.w.n_sched != 0)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: n_rows is %d, a multiple of n_scene = %d", who, a.n_scene, a.w.n_sched);
+    if (a.n_scene == 0) return PFC_OK;
+    if (body_wrench_null(a.w) || (a.w.n_w > 0 && (!a.x_w_b || !a.jac || !a.dx_w_b || !a.djac)) || !a.w.dtau)
+        return fail(h, PFC_ERR_BAD_ARG, "%s: null buffer", who);
+    return body_wrench_dual_launch(h, a, st);
+}
+
+// The wrenches of a chained call on its value buffers, behind the law: tau = (law->tau or V.tau) + the wrenches into push->tau.
+static int body_wrench_of_call(pfc_context *h, const char *who, const StateCall &S, hipStream_t st) {
+    BodyWrenchArgs a{};
+    a.w = *S.push; a.n_rows = S.n_scene; a.nv = h->kin.nv;
+    a.x_w_b = S.val.x_w_b; a.jac = S.val.jac; a.tau_in = S.law ? S.law->tau : S.val.tau;
+    return body_wrench_checked(h, who, a, st);
+}
+
+static int body_wrench_dual_of_call(pfc_context *h, const char *who, const StateCall &S, hipStream_t st) {
+    BodyWrenchDualArgs a{};
+    a.w = *S.push; a.n_scene = S.n_scene; a.n_dir = S.n_dir; a.nv = h->kin.nv;
+    a.x_w_b = S.val.x_w_b; a.jac = S.val.jac; a.dx_w_b = S.par.x_w_b; a.djac = S.par.jac; a.dtau_in = S.law ? S.law->dtau : S.par.tau;
+    return body_wrench_dual_checked(h, who, a, st);
+}
+
+// The tau and dtau the solve of a chained call reads: the wrenches' sums, else the law's, else the call's own.
+static const double *solve_tau(const StateCall &S) { return S.push ? S.push->tau : S.law ? S.law->tau : S.val.tau; }
+static const double *solve_dtau(const StateCall &S) { return S.push ? S.push->dtau : S.law ? S.law->dtau : S.par.tau; }
+
+int pfc_body_wrench_device(pfc_handle h, int n_rows, int n_scene, int n_body, int nv, int n_w, int n_seg, const int *d_body,
+                           const int *d_frame, const double *d_point, const double *d_seg_t, const double *d_seg_w, const double *d_t,
+                           const double *d_x_w_b, const double *d_jac, const double *d_tau_in, double *d_tau_out, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    BodyWrenchArgs a{};
+    a.w.n_sched = n_scene; a.w.n_body = n_body; a.w.n_w = n_w; a.w.n_seg = n_seg; a.w.body = d_body; a.w.frame = d_frame;
+    a.w.point = d_point; a.w.seg_t = d_seg_t; a.w.seg_w = d_seg_w; a.w.t = d_t; a.w.tau = d_tau_out;
+    a.n_rows = n_rows; a.nv = nv; a.x_w_b = d_x_w_b; a.jac = d_jac; a.tau_in = d_tau_in;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        return body_wrench_checked(c, "pfc_body_wrench_device", a, stream ? (hipStream_t)stream : c->stream); });
+}
+
+int pfc_body_wrench_dual_device(pfc_handle h, int n_rows, int n_dir, int n_scene, int n_body, int nv, int n_w, int n_seg,
+                                const int *d_body, const int *d_frame, const double *d_point, const double *d_seg_t,
+                                const double *d_seg_w, const double *d_t, const double *d_x_w_b, const double *d_jac,
+                                const double *d_dx_w_b, const double *d_djac, const double *d_dtau_in, double *d_dtau, void *stream) {
+    if (!h) return PFC_ERR_BAD_ARG;
+    BodyWrenchDualArgs a{};
+    a.w.n_sched = n_scene; a.w.n_body = n_body; a.w.n_w = n_w; a.w.n_seg = n_seg; a.w.body = d_body; a.w.frame = d_frame;
+    a.w.point = d_point; a.w.seg_t = d_seg_t; a.w.seg_w = d_seg_w; a.w.t = d_t; a.w.dtau = d_dtau;
+    a.n_scene = n_rows; a.n_dir = n_dir; a.nv = nv; a.x_w_b = d_x_w_b; a.jac = d_jac; a.dx_w_b = d_dx_w_b; a.djac = d_djac;
+    a.dtau_in = d_dtau_in;
+    return on_shard(h, first_ctx(h), [&](pfc_context *c) {
+        return body_wrench_dual_checked(c, "pfc_body_wrench_dual_device", a, stream ? (hipStream_t)stream : c->stream); });
+}
+
 // What both Dual chains check before the first launch, beyond what the Dual evaluation checks itself: the inertias, the Dual LDS
 // limit, the nv cap and n_dir.
 static int state_derivative_dual_check(pfc_context *c, const char *who, int n_scene, int n_dir) {
@@ -4819,7 +4931,8 @@ static int state_derivative(pfc_context *h, const StateCall &S) {
         const hipStream_t st = call_stream(c1, S);
         int r = dyn_launch(c1, S.n_scene, V.q, V.v, V.x_w_b, V.twist_w_b, V.qdot, V.H, V.c, st);
         if (r == PFC_OK && S.law) r = feedback_of_call(c1, who, S, st);
-        return r != PFC_OK ? r : accel_launch(c1, S.n_scene, V.H, V.c, V.f, S.law ? S.law->tau : V.tau, V.vdot, V.info, st); });
+        if (r == PFC_OK && S.push) r = body_wrench_of_call(c1, who, S, st);
+        return r != PFC_OK ? r : accel_launch(c1, S.n_scene, V.H, V.c, V.f, solve_tau(S), V.vdot, V.info, st); });
 }
 
 // `more`: another chunk of directions at the point of the last checked first call -- only partials are written, the values are read.
@@ -4875,8 +4988,12 @@ static int state_derivative_dual(pfc_context *h, const StateCall &S, bool more) 
             if (!more && (r = feedback_of_call(c1, who, S, st)) != PFC_OK) return r;
             if ((r = feedback_dual_of_call(c1, who, S, st)) != PFC_OK) return r;
         }
-        return accel_dual_launch(c1, S.n_scene, S.n_dir, V.H, V.c, V.f, S.law ? S.law->tau : V.tau, P.H, P.c, P.f,
-                                 S.law ? S.law->dtau : P.tau, more ? nullptr : V.vdot, P.vdot, more ? nullptr : V.info, st); });
+        if (S.push) {     // the wrenches behind the law, likewise
+            if (!more && (r = body_wrench_of_call(c1, who, S, st)) != PFC_OK) return r;
+            if ((r = body_wrench_dual_of_call(c1, who, S, st)) != PFC_OK) return r;
+        }
+        return accel_dual_launch(c1, S.n_scene, S.n_dir, V.H, V.c, V.f, solve_tau(S), P.H, P.c, P.f, solve_dtau(S),
+                                 more ? nullptr : V.vdot, P.vdot, more ? nullptr : V.info, st); });
 }
 
 // The six entries: one fill of the record each -- the only place a parameter position meets a field name -- and one call.

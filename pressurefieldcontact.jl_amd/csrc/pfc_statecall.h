@@ -28,6 +28,18 @@ struct FeedbackLaw {
     double *dtau = nullptr;      // n_scene x n_dir x nv: its partials (Dual calls)
 };
 
+// The applied body wrenches of a call (pfc_body_wrench_device's arguments; the kernels: pfc_body_wrench.h).  The schedule has
+// n_sched scenes; row r of a call reads the loads of scene r % n_sched.
+struct BodyWrenches {
+    int n_sched = 0, n_body = 0, n_w = 0, n_seg = 0;
+    const int *body = nullptr, *frame = nullptr;                                // n_w: the body, 0 world axes / 1 body axes
+    const double *point = nullptr;                                              // n_w x 3, in the body frame
+    const double *seg_t = nullptr, *seg_w = nullptr;                            // n_sched x n_seg, x n_w x 6 [moment; force]
+    const double *t = nullptr;                                                  // one time per row
+    double *tau = nullptr;       // rows x nv: the wrenches' torques plus the tau in front of them -- what the solve reads
+    double *dtau = nullptr;      // n_scene x n_dir x nv: its partials (Dual calls)
+};
+
 struct StateCall {
     int n_items = 0, n_dir = 0, n_scene = 0;
     const int *ins_ids = nullptr, *scene = nullptr;
@@ -36,6 +48,9 @@ struct StateCall {
     // null in every public entry: the chain launches what it launched without one.  Set (the Radau driver): the law is evaluated
     // between the dynamics and the solve, which then reads law->tau and, in a Dual call, law->dtau in place of val.tau and par.tau
     const FeedbackLaw *law = nullptr;
+    // null in every public entry, likewise.  Set (the Radau driver): the wrenches are evaluated behind the law -- on law->tau and
+    // law->dtau where a law is set, on val.tau and par.tau otherwise -- and the solve reads push->tau and push->dtau
+    const BodyWrenches *push = nullptr;
 };
 
 // A buffer that an entry declares const -- the values of a `_more` entry, the body states of the `_bodies` entries -- as the record's

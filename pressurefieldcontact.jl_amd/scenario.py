@@ -1388,7 +1388,7 @@ class MechanismScenario:
 
     def radau_stage_times(self):
         """pfc_radau_stage_times: (3, n_scene), the times at which the last attempt evaluated the continuous law: row s of scene i
-        is (c_s h_i) + t_i for s < NS(rule_i) and t_i otherwise.  With a law set (the library says so otherwise)."""
+        is (c_s h_i) + t_i for s < NS(rule_i) and t_i otherwise.  With a law or body wrenches set (the library says so otherwise)."""
         out = np.zeros((3, getattr(self, "_radau_n_scene", 0)))
         self._check(_lib.lib().pfc_radau_stage_times(self._h, out.ctypes.data_as(_dp)))
         return out
@@ -1409,6 +1409,47 @@ class MechanismScenario:
         a = [d_act, d_kp, d_kd, d_a_max, d_seg_t, d_seg_q, d_t, d_q, d_v, d_H, d_dq, d_dv, d_dH, d_dc, d_dtau, stream]
         self._check(_lib.lib().pfc_feedback_dual_device(self._h, int(n_rows), int(n_dir), int(n_scene), int(nv), int(n_act), int(n_seg),
                                                         *[x or None for x in a]))
+
+    # ---- applied body wrenches (include/pfc.h, pfc_radau_set_body_wrenches; the scalar statements: body_wrench_tau[_partials]) ----
+    def radau_set_body_wrenches(self, body, frame, point, seg_t, seg_w):
+        """pfc_radau_set_body_wrenches: n_w wrenches -- body (n_w,), frame (n_w,; 0 world axes, 1 body axes), point (n_w, 3) in the
+        body frame -- with loads seg_w (n_scene, n_seg, n_w, 6) = [moment; force] on the schedule seg_t (n_scene, n_seg); leading
+        scene axes broadcast.  Projected into tau on the device inside the differential equation, behind the continuous law, with
+        their partials in every Jacobian chunk."""
+        n = getattr(self, "_radau_n_scene", 0)
+        body_a = np.ascontiguousarray(body, dtype=np.int32).reshape(-1)
+        nw = body_a.size
+        frame_a = np.ascontiguousarray(np.broadcast_to(np.asarray(frame, dtype=np.int32), (nw,)))
+        point_a = np.ascontiguousarray(np.broadcast_to(np.asarray(point, dtype=np.float64).reshape(-1, 3), (nw, 3)))
+        st = np.asarray(seg_t, dtype=np.float64)
+        n_seg = st.shape[-1] if st.ndim else 1
+        st_a = np.ascontiguousarray(np.broadcast_to(st.reshape(-1, n_seg), (n, n_seg)))
+        sw_a = np.ascontiguousarray(np.broadcast_to(np.asarray(seg_w, dtype=np.float64).reshape((-1, n_seg, nw, 6)), (n, n_seg, nw, 6)))
+        self._check(_lib.lib().pfc_radau_set_body_wrenches(self._h, int(nw), body_a.ctypes.data_as(_ip), frame_a.ctypes.data_as(_ip),
+                                                           point_a.ctypes.data_as(_dp), int(n_seg), st_a.ctypes.data_as(_dp),
+                                                           sw_a.ctypes.data_as(_dp)))
+
+    def radau_clear_body_wrenches(self):
+        """pfc_radau_clear_body_wrenches: the step is the step without wrenches again."""
+        self._check(_lib.lib().pfc_radau_clear_body_wrenches(self._h))
+
+    def body_wrench_device(self, n_rows: int, n_scene: int, n_body: int, nv: int, n_w: int, n_seg: int, d_body: int, d_frame: int,
+                           d_point: int, d_seg_t: int, d_seg_w: int, d_t: int, d_x_w_b: int, d_jac: int, d_tau_in: int, d_tau_out: int,
+                           stream: int = 0):
+        """pfc_body_wrench_device: the wrenches' torques added to d_tau_in on raw device addresses (0: NULL for d_tau_in and, with
+        one segment, d_seg_t); asynchronous on `stream`."""
+        a = [d_body, d_frame, d_point, d_seg_t, d_seg_w, d_t, d_x_w_b, d_jac, d_tau_in, d_tau_out, stream]
+        self._check(_lib.lib().pfc_body_wrench_device(self._h, int(n_rows), int(n_scene), int(n_body), int(nv), int(n_w), int(n_seg),
+                                                      *[x or None for x in a]))
+
+    def body_wrench_dual_device(self, n_rows: int, n_dir: int, n_scene: int, n_body: int, nv: int, n_w: int, n_seg: int, d_body: int,
+                                d_frame: int, d_point: int, d_seg_t: int, d_seg_w: int, d_t: int, d_x_w_b: int, d_jac: int, d_dx_w_b: int,
+                                d_djac: int, d_dtau_in: int, d_dtau: int, stream: int = 0):
+        """pfc_body_wrench_dual_device: the partials of the wrenches' torques along n_dir directions, added to d_dtau_in (0: NULL),
+        on raw device addresses; asynchronous on `stream`."""
+        a = [d_body, d_frame, d_point, d_seg_t, d_seg_w, d_t, d_x_w_b, d_jac, d_dx_w_b, d_djac, d_dtau_in, d_dtau, stream]
+        self._check(_lib.lib().pfc_body_wrench_dual_device(self._h, int(n_rows), int(n_dir), int(n_scene), int(n_body), int(nv), int(n_w),
+                                                           int(n_seg), *[x or None for x in a]))
 
     # ---- the gripper program (include/pfc.h, pfc_radau_set_program; the scalar statement: gripper_program_step below) -----------
     def _program_arrays(self, prog_dt, prog_q, prog_slip):
@@ -1981,6 +2022,78 @@ def feedback_pd_partials(q, v, H, t, dq, dv, dH, dc, act, kp, kd, seg_t, seg_q, 
             s = s + (float(dH[co][cb]) * acc[b] + float(H[co][cb]) * dacc[b])
         dtau[co] = s + float(dc[co])
     return dtau
+
+
+# ---- applied body wrenches: the scalar statements of include/pfc.h (pfc_body_wrench_device, pfc_body_wrench_dual_device) ------------
+class _Dual:
+    """ScatDual (csrc/pfc_scatter.h) in Python floats: a value and one partial; sums componentwise, d(a b) = da b + a db."""
+    __slots__ = ("v", "d")
+
+    def __init__(self, v, d=0.0):
+        self.v, self.d = float(v), float(d)
+
+    def __add__(self, o):
+        return _Dual(self.v + o.v, self.d + o.d)
+
+    def __sub__(self, o):
+        return _Dual(self.v - o.v, self.d - o.d)
+
+    def __mul__(self, o):
+        return _Dual(self.v * o.v, self.d * o.v + self.v * o.d)
+
+
+def _body_wrench_world(frame, x, p, l, lit):
+    """W = [M + r x F; F] of the load l = [m; f] at point p of the body with pose x = (R column-major, t), on floats or _Dual
+    numbers (lit lifts a constant): the one statement both body_wrench_tau and body_wrench_tau_partials run."""
+    p0, p1, p2 = lit(p[0]), lit(p[1]), lit(p[2])
+    w = [lit(e) for e in l]
+    r = [((x[i] * p0 + x[3 + i] * p1) + x[6 + i] * p2) + x[9 + i] for i in range(3)]
+    if frame == 1:
+        F = [(x[i] * w[3] + x[3 + i] * w[4]) + x[6 + i] * w[5] for i in range(3)]
+        M = [(x[i] * w[0] + x[3 + i] * w[1]) + x[6 + i] * w[2] for i in range(3)]
+    else:
+        F, M = w[3:], w[:3]
+    cr = [r[1] * F[2] - r[2] * F[1], r[2] * F[0] - r[0] * F[2], r[0] * F[1] - r[1] * F[0]]
+    return [M[i] + cr[i] for i in range(3)] + F
+
+
+def _body_wrench_segment(seg_t, t):
+    return sum(1 for j in range(1, len(seg_t)) if float(seg_t[j]) <= float(t))
+
+
+def body_wrench_tau(x_w_b, jac, t, tau_in, body, frame, point, seg_t, seg_w):
+    """The applied body wrenches of one row: x_w_b (n_body x 12) and jac (n_body x nv x 6) of pfc_kinematics, the row's time t,
+    tau_in (nv floats, or None: the sum starts from +0.0), body, frame (n_w), point (n_w x 3), the scene's schedule seg_t (n_seg)
+    and seg_w (n_seg x n_w x 6, [moment; force]).  Per wrench, k ascending: the application point r = ((R[:,0] p0 + R[:,1] p1) +
+    R[:,2] p2) + t_b; frame 1: F = R f, M = R m, frame 0: copies; W = [M + r x F; F]; tau_k,j = ((J0 W0 + J1 W1) + J2 W2) + ((J3 W3
+    + J4 W4) + J5 W5); tau_out_j = (..(tau_in_j + tau_0,j) + ..).  Returns tau_out (nv floats)."""
+    nv = len(jac[0])
+    seg = _body_wrench_segment(seg_t, t)
+    out = [0.0 if tau_in is None else float(tau_in[j]) for j in range(nv)]
+    for k, b in enumerate(body):
+        x = [float(e) for e in x_w_b[b]]
+        W = _body_wrench_world(int(frame[k]), x, point[k], seg_w[seg][k], float)
+        for j in range(nv):
+            J = [float(e) for e in jac[b][j]]
+            out[j] = out[j] + (((J[0] * W[0] + J[1] * W[1]) + J[2] * W[2]) + ((J[3] * W[3] + J[4] * W[4]) + J[5] * W[5]))
+    return out
+
+
+def body_wrench_tau_partials(x_w_b, jac, dx_w_b, djac, t, dtau_in, body, frame, point, seg_t, seg_w):
+    """The partials of body_wrench_tau along one direction: dx_w_b (n_body x 12) and djac (n_body x nv x 6) of pfc_kinematics_dual
+    for that direction.  The value statement on (value, partial) numbers with ScatDual's rules (_Dual); t, the tables, the points and
+    the loads are constants {x, 0.0}.  dtau_out_j = (..(dtau_in_j + d tau_0,j) + ..), from +0.0 where dtau_in is None.  Returns
+    dtau_out (nv floats)."""
+    nv = len(jac[0])
+    seg = _body_wrench_segment(seg_t, t)
+    out = [0.0 if dtau_in is None else float(dtau_in[j]) for j in range(nv)]
+    for k, b in enumerate(body):
+        x = [_Dual(x_w_b[b][e], dx_w_b[b][e]) for e in range(12)]
+        W = _body_wrench_world(int(frame[k]), x, point[k], seg_w[seg][k], _Dual)
+        for j in range(nv):
+            J = [_Dual(jac[b][j][e], djac[b][j][e]) for e in range(6)]
+            out[j] = out[j] + (((J[0] * W[0] + J[1] * W[1]) + J[2] * W[2]) + ((J[3] * W[3] + J[4] * W[4]) + J[5] * W[5])).d
+    return out
 
 
 # ---- the gripper program: the scalar statement of include/pfc.h (pfc_radau_program_device) in Python floats -------------------------
